@@ -87,6 +87,9 @@ def parse(argv=None):
                     "reading the hand-over launch's precomputed rows")
     ap.add_argument("--lookup-nt", action="store_true", help="TT_OPT_LOOKUP_NT: non-temporal stores of the looked-up rows (A/B)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the HBM-resident lookup leg and the configs[4] leg of the default run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (result dict, trained state; fixed samples of the "
+                         "large arrays) as DIR/<name>.npy, float32 / float64, at most 64 MB (rank 0; the leg that gives `value`)")
     ap.add_argument("--unroll", type=int, default=1, help="training steps per graph launch (unrolled.UnrolledTrainStep: the hand-over launches become "
                                                           "graph nodes re-pointed per launch; one graph launch costs ~8 us on this runtime); unsharded step only")
     return ap.parse_args(argv)
@@ -265,8 +268,9 @@ class Leg:
                 i += 1
         return res
 
-    def run(self):
-        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks."""
+    def run(self, dump_dir=None):
+        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks.  dump_dir: write the
+        last timed step's outputs there (dump_outputs) before anything else runs on the device."""
         import torch
         from jodalrob_twotower_amd import ops
         args, ctx = self.args, self.ctx
@@ -285,6 +289,8 @@ class Leg:
         ctx["fence"]()
         dt = time.perf_counter() - t0
         ops.set_timer(None)
+        if dump_dir is not None:                                 # (the second pass below overwrites the captured step's results)
+            dump_outputs(dump_dir, self.task, res)
         # the captured step's hand-over launch also does the lookup (tt_batch_ingest_lookup)?  Then the stamps are that launch's:
         # its tile workgroups (the gather phase) come first, the copy roles behind them
         self.fused_handover = self.gstep is not None and getattr(self.gstep, "_x_static", None) is not None
@@ -339,6 +345,51 @@ class Leg:
         gc.collect()
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 8192          # rows of a large parameter (an embedding table) in a dump
+DUMP_SIM_ROWS = 512              # rows of the B x B similarity matrix in a dump (16 MB at B = 8192)
+
+
+def dump_outputs(out_dir, task, res):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy (float32; float64 where the source is).
+    result.*: the step's result dict -- loss and metrics, and a fixed sample of DUMP_SIM_ROWS rows of the similarity matrix plus
+    its diagonal.
+    param.* / buffer.*: the trained state the step leaves; arrays of more than DUMP_SAMPLE_ROWS rows (the embedding tables) as
+    a fixed sample of rows.  The samples come from a seeded generator, so two runs with the same arguments dump the same entries."""
+    import numpy as np
+    import torch
+
+    def rows(n, k):
+        if n <= k:
+            return None
+        return torch.from_numpy(np.sort(np.random.default_rng(1234).choice(n, k, replace=False)))
+
+    def host(t):
+        t = torch.as_tensor(t).detach()
+        return t.to("cpu", torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32).numpy()
+
+    arrays = {}
+    for k in ("loss", "accuracy", "positive_similarity_mean", "negative_similarity_mean", "similarity_gap"):
+        if k in res:
+            arrays[f"result.{k}"] = host(res[k]).reshape(-1)
+    if "similarity_matrix" in res:
+        S = res["similarity_matrix"]
+        idx = rows(S.shape[0], DUMP_SIM_ROWS)
+        arrays["result.similarity_matrix.rows"] = host(S if idx is None else S[idx.to(S.device)])
+        arrays["result.similarity_matrix.diagonal"] = host(S.diagonal())
+    for kind, named in (("param", task.named_parameters()), ("buffer", task.named_buffers())):
+        for name, t in named:
+            idx = rows(t.shape[0], DUMP_SAMPLE_ROWS) if t.dim() > 0 else None
+            arrays[f"{kind}.{name}"] = host(t if idx is None else t[idx.to(t.device)])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def run(args):
@@ -562,7 +613,7 @@ def bench_single(args, ctx, sharded):
     rows_c = args.rows_company or 1_000_000
     B = args.batch
     leg = Leg(args, ctx, B, rows_n, rows_c, sharded, negatives=args.negatives or "local", sync_bn=args.sync_bn)
-    leg.run()
+    leg.run(dump_dir=args.dump_outputs)
     is_c1 = B == 8192 and args.final_dim == 64 and args.hidden == "128,64" and args.zipf is None and rows_n == 1_000_000 and rows_c == 1_000_000 and args.score_dtype == "bf16"
     out = base_line(args, leg, 1, "weak", B)
     out["config"] = config_of(args, leg, 1, ctx, B, ("configs[1]: " if is_c1 else "variant of configs[1]: ") +
@@ -628,7 +679,7 @@ def bench_multi(args, ctx):
         # `value` at N > 1: every GPU keeps the N = 1 job's batch (8192 pairs PER GPU; per-GPU work fixed: "scaling": "weak"),
         # tables sharded row-wise -- the data-parallel job whose global batch grows with N
         leg = Leg(args, ctx, Bg, rows_n, rows_c, True, negatives=args.negatives or "local", sync_bn=args.sync_bn, label="weak")
-        leg.run()
+        leg.run(dump_dir=args.dump_outputs if rank == 0 else None)
         out = base_line(args, leg, world, "weak", Bg * world)
         #  the top-level number at N > 1 is NOT the batch-8192 job of N = 1 split N ways: say so in the metric text
         # itself, so that nobody compares it with a global-batch figure under the same key; that job is `value_global_batch_8192`
@@ -645,7 +696,7 @@ def bench_multi(args, ctx):
         # global batch (tests: test_two_processes_equal_single_process); latency-bound at 8192 / N pairs per GPU
         neg = args.negatives or "global"
         leg = Leg(args, ctx, Bg // world, rows_n, rows_c, True, negatives=neg, sync_bn=(neg == "global") or args.sync_bn, label="strong")
-        leg.run()
+        leg.run(dump_dir=args.dump_outputs if (rank == 0 and out is None) else None)      # (the leg that gives `value`)
         st = base_line(args, leg, world, "strong", Bg)
         cfg = config_of(args, leg, world, ctx, Bg, f"{cname}: {desc}; GLOBAL batch {Bg} ({Bg // world} pairs per GPU), global in-batch negatives + SyncBN")
         if out is None:

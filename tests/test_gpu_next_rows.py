@@ -484,3 +484,22 @@ def test_bench_multi_gpu_path_with_two_ranks_on_one_gpu():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and "PER GPU" in d["metric"]
     assert d["config"]["launch"].startswith("segmented graph replay") and d["roofline"]["mean_launch_us"] > 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: the timed steps' count is --steps, the line carries ms_per_step, and DIR holds the LAST timed step's
+    outputs -- its loss is the line's final_loss -- as float32 / float64 .npy files, 64 MB at most, with the similarity matrix and the
+    embedding tables as fixed row samples."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--no-cpu-baseline", "--no-h2d",
+                        "--no-extra-legs", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0
+    files = {f.name[:-4]: np.load(f) for f in out.glob("*.npy")}
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["result.loss"].shape == (1,) and float(files["result.loss"][0]) == d["final_loss"]
+    assert files["result.similarity_matrix.rows"].shape == (512, 8192) and files["result.similarity_matrix.diagonal"].shape == (8192,)
+    tables = [a for k, a in files.items() if k.startswith("param.") and "embeddings" in k]
+    assert tables and max(a.shape[0] for a in tables) == 8192 and all(np.isfinite(a).all() for a in files.values())

@@ -1829,7 +1829,7 @@ def test_padded_exchange_multi_rank_on_one_gpu(tt, G, x_dtype, grad_bf16):
 def test_sync_bn_phases_at_world_one_equal_the_whole_pass(tt, manifest, schema_real, hidden, D, mlp):
     """tt_tower_params.sync_phase 1 + 2 with ONE rank (the all-gather hands back the rank's own statistics) == the uncut
     pass, bit for bit: unit rows, BN running statistics and every gradient, dropout on.  [128, 64] -> 64 takes the fused
-    tail kernels; scripts/train.py's own [512, 256] -> 128 (/root/reference/scripts/train.py:106-107) and an odd fp32 shape
+    tail kernels; scripts/train.py's own [512, 256] -> 128 (the reference's scripts/train.py:106-107) and an odd fp32 shape
     take the separate kernels, cut at the same place."""
     class Solo:
         world, rank = 1, 0
@@ -2046,7 +2046,7 @@ def test_bf16_step_vs_rounded_oracle(tt, schema_real, tmp_path, ctx_option, rows
     no mask) against the f64 oracle with the kernels' operand rounding: loss, both towers' embeddings, the metrics, every
     dense gradient and the sparse row gradients, each with its own stated bound.  Second case: the real (unscaled)
     vocabularies at a ragged batch and T = 0.5.  Third case: scripts/train.py's own towers ([512, 256] -> 128,
-    /root/reference/scripts/train.py:106-107) -- the wide tail kernels and the separate fast GEMMs of the first block (the
+    the reference's scripts/train.py:106-107) -- the wide tail kernels and the separate fast GEMMs of the first block (the
     one-launch front / first-block backward do not take h0 = 512), at a batch of 35 x 64 rows.  Last three cases: BASELINE
     configs[4]'s step -- final_embedding_dim 256, score_dtype "fp8" (e4m3 operands for the score products and, by default,
     for the gradient products with block-scaled e4m3 softmax weights; "fp8_s": TT_OPT_FP8_GRAD 0, bf16 gradient products) -- at
