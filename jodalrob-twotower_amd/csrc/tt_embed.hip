@@ -7,6 +7,7 @@
 #include "tt_riders.h"
 
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -1556,23 +1557,28 @@ struct CopyArgs {
   int64_t bytes[TT_MAX_COPIES];
 };
 
-__global__ __launch_bounds__(kThreads) void copy_multi_kernel(CopyArgs a) {
-  const int seg = blockIdx.y;
+// blockDim.x for the roles below: blockDim.x itself goes through the device library's partial-workgroup select, which only a
+// kernel body folds into one load; the builtin is that one load (HIP launches are uniform), so a role compiles as it would inline
+__device__ __forceinline__ uint32_t role_threads() { return __builtin_amdgcn_workgroup_size_x(); }
+
+// one copy segment per grid row: the 16-byte body strided over the row's workgroups, the byte tail by its first workgroup
+__device__ __forceinline__ void copy_segment_role(const CopyArgs& a, int seg) {
   const int64_t n16 = a.bytes[seg] / 16, tail0 = n16 * 16;
   const float4* __restrict__ s = reinterpret_cast<const float4*>(a.src[seg]);
   float4* __restrict__ d = reinterpret_cast<float4*>(a.dst[seg]);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) d[i] = s[i];
+  const int64_t stride = (int64_t)gridDim.x * role_threads();
+  for (int64_t i = (int64_t)blockIdx.x * role_threads() + threadIdx.x; i < n16; i += stride) d[i] = s[i];
   if (blockIdx.x == 0)
-    for (int64_t i = tail0 + threadIdx.x; i < a.bytes[seg]; i += blockDim.x) a.dst[seg][i] = a.src[seg][i];
+    for (int64_t i = tail0 + threadIdx.x; i < a.bytes[seg]; i += role_threads()) a.dst[seg][i] = a.src[seg][i];
 }
 
-// Batch hand-over of a graph-replayed step: the copy segments of copy_multi_kernel plus, per side, the fused row of every id
-// in KEY-MAJOR order (rows_km[side_base + k * B + b] = key_row_offset[k] + clamp(ids[b * K + k])) -- the input
-// tt_dedup_plan_keyed_km sorts.  A key's rows sit one per K * 4 bytes in the lookup's sample-major array: gathered by the sort
-// itself that is a 128-byte line per lane (6.5 of a share's 18 us); here a workgroup reads 64 samples' ids as one run, turns the
-// tile in LDS and writes 256-byte runs per key.  Grid row 0: every side's 64-sample tiles, side by side (dispatched first: the
-// few transposing workgroups must not queue behind the thousands of copy workgroups); row y >= 1: copy segment y - 1.
+__global__ __launch_bounds__(kThreads) void copy_multi_kernel(CopyArgs a) { copy_segment_role(a, blockIdx.y); }
+
+// Batch hand-over of a graph-replayed step (tt_batch_ingest*): the copy segments of copy_multi_kernel plus, per side, the fused
+// row of every id in KEY-MAJOR order (key_major_tile_role).  Grid rows of the launch: row 0 = every side's tiles (dispatched
+// first: the few tile workgroups must not queue behind the thousands of copy workgroups); from the stores only, rows
+// 1 .. n_sides = the dense feature rows of side y - 1 (dense_rows_role); then one row per copy segment; last, when the launch
+// carries conversions, the cvt row.
 constexpr int kIngestMaxK = 64;
 // f32 -> bf16 (RNE) copies riding in the hand-over launch (tt_cvt_list): the towers' bf16 weight shadows, refreshed every step
 struct CvtDev {
@@ -1611,65 +1617,8 @@ struct IngestArgs {
   uint32_t* dev_err;
 };
 
-__global__ __launch_bounds__(kThreads) void batch_ingest_kernel(IngestArgs a) {
-  if ((int)blockIdx.y == a.n_copy + 1) { cvt_role(a.v); return; }        // (last grid row, present when a.v.n > 0)
-  if (blockIdx.y >= 1) {
-    const int seg = blockIdx.y - 1;
-    const int64_t n16 = a.c.bytes[seg] / 16, tail0 = n16 * 16;
-    const float4* __restrict__ s = reinterpret_cast<const float4*>(a.c.src[seg]);
-    float4* __restrict__ d = reinterpret_cast<float4*>(a.c.dst[seg]);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) d[i] = s[i];
-    if (blockIdx.x == 0)
-      for (int64_t i = tail0 + threadIdx.x; i < a.c.bytes[seg]; i += blockDim.x) a.c.dst[seg][i] = a.c.src[seg][i];
-    return;
-  }
-  // row 0 of the grid: every side's 64-sample tiles side by side (an own grid row per side meant a thousand empty workgroups each)
-  const int B = a.B, tiles = (B + 63) / 64;
-  const int si = (int)blockIdx.x / tiles, tile = (int)blockIdx.x % tiles;
-  if (si >= a.n_sides) return;
-  const int K = a.K[si];
-  __shared__ int32_t tl[kIngestMaxK][65];
-  __shared__ int64_t s_off[kIngestMaxK], s_hi[kIngestMaxK];
-  const int64_t* __restrict__ ids = a.ids[si];
-  if ((int)threadIdx.x < K) {
-    s_off[threadIdx.x] = a.off[si][threadIdx.x];
-    s_hi[threadIdx.x] = a.vocab[si][threadIdx.x] - 1;
-  }
-  __syncthreads();
-  constexpr int PER = kIngestMaxK * 64 / kThreads;            // ids per thread and tile: all loads issued before the first use
-  {
-    const int b0 = tile * 64;
-    const int nb = min(64, B - b0), n = nb * K;
-    int64_t idv[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {                           // the tile's ids are one contiguous run
-      const int e = threadIdx.x + u * kThreads;
-      idv[u] = ids[(int64_t)b0 * K + (e < n ? e : 0)];
-    }
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int e = threadIdx.x + u * kThreads;
-      if (e < n) {
-        const int bl = e / K, k = e - bl * K;
-        int64_t id = idv[u];
-        id = id < 0 ? 0 : (id > s_hi[k] ? s_hi[k] : id);      // clamp: cat_embed.py:117 (as the lookup)
-        tl[k][bl] = (int32_t)row_in_table(s_off[k] + id, a.table_rows, a.dev_err);
-        if (a.rows_sm) a.rows_sm[a.side_base[si] + (int64_t)b0 * K + e] = tl[k][bl];
-      }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < K * 64; e += kThreads) {
-      const int k = e >> 6, bl = e & 63;
-      if (bl < nb) a.rows_km[a.side_base[si] + (int64_t)k * B + b0 + bl] = tl[k][bl];
-    }
-  }
-}
-
-// The hand-over straight from the device-resident feature stores (tt_batch_ingest_store): grid row 0 = every side's 64-sample
-// tiles (entity rows of the tile's pairs -> the tile's ids as one sample-major run + the key-major fused rows, turned in LDS as
-// above); rows 1 .. n_sides = the dense feature rows of side y - 1 (16-byte pieces, a row's pieces on consecutive lanes);
-// the rows after that = the copy segments.
+// The hand-over straight from the device-resident feature stores (tt_batch_ingest_store*): the batch's ids and dense features
+// come out of the stores through the pair list instead of from a staged batch.
 struct StoreIngestArgs {
   IngestArgs g;                                  // ids[] unused
   const int64_t* order;
@@ -1683,68 +1632,74 @@ struct StoreIngestArgs {
   int32_t n_rows[TT_MAX_SIDES];                  // entity rows of the store (0 = unchecked): indices are clamped into [0, n_rows)
 };
 
+// the store row of sample b of side si
+__device__ __forceinline__ int64_t store_entity(const StoreIngestArgs& a, int si, int b) {
+  const int64_t o = a.order ? a.order[b] : b;
+  int64_t e = a.entity[si][o * a.entity_stride[si]];
+  const int64_t nr = a.n_rows[si];
+  if (nr > 0) e = e < 0 ? 0 : (e >= nr ? nr - 1 : e);
+  return e;
+}
+
+// the dense feature rows of side si: 16-byte pieces (VEC) or floats, a row's pieces on consecutive lanes
 template <bool VEC>
-__global__ __launch_bounds__(kThreads) void batch_ingest_store_kernel(StoreIngestArgs a) {
-  const int B = a.g.B;
-  if ((int)blockIdx.y == 1 + a.g.n_sides + a.g.n_copy) { cvt_role(a.g.v); return; }
-  if ((int)blockIdx.y > a.g.n_sides) {
-    const int seg = blockIdx.y - 1 - a.g.n_sides;
-    const int64_t n16 = a.g.c.bytes[seg] / 16, tail0 = n16 * 16;
-    const float4* __restrict__ s = reinterpret_cast<const float4*>(a.g.c.src[seg]);
-    float4* __restrict__ d = reinterpret_cast<float4*>(a.g.c.dst[seg]);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) d[i] = s[i];
-    if (blockIdx.x == 0)
-      for (int64_t i = tail0 + threadIdx.x; i < a.g.c.bytes[seg]; i += blockDim.x) a.g.c.dst[seg][i] = a.g.c.src[seg][i];
-    return;
+__device__ __forceinline__ void dense_rows_role(const StoreIngestArgs& __restrict__ a, int si) {
+  const int dd = a.dense_dim[si];
+  if (dd == 0) return;
+  const int per = VEC ? dd / 4 : dd;                           // pieces per row
+  const int64_t total = (int64_t)a.g.B * per, stride = (int64_t)gridDim.x * role_threads();
+  for (int64_t t = (int64_t)blockIdx.x * role_threads() + threadIdx.x; t < total; t += stride) {
+    const int b = (int)(t / per), j = (int)(t - (int64_t)b * per);
+    const int64_t e = store_entity(a, si, b);
+    if (VEC) reinterpret_cast<float4*>(a.dense_out[si] + (int64_t)b * dd)[j] = reinterpret_cast<const float4*>(a.dense_store[si] + e * dd)[j];
+    else a.dense_out[si][(int64_t)b * dd + j] = a.dense_store[si][e * dd + j];
   }
-  if (blockIdx.y >= 1) {                                       // dense feature rows of one side
-    const int si = blockIdx.y - 1;
-    const int dd = a.dense_dim[si];
-    if (dd == 0) return;
-    const int64_t* __restrict__ ent = a.entity[si];
-    const int64_t es = a.entity_stride[si];
-    const int per = VEC ? dd / 4 : dd;                         // pieces per row
-    const int64_t total = (int64_t)B * per, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-      const int b = (int)(t / per), j = (int)(t - (int64_t)b * per);
-      const int64_t o = a.order ? a.order[b] : b;
-      int64_t e = ent[o * es];
-      if (a.n_rows[si] > 0) e = e < 0 ? 0 : (e >= a.n_rows[si] ? a.n_rows[si] - 1 : e);
-      if (VEC) reinterpret_cast<float4*>(a.dense_out[si] + (int64_t)b * dd)[j] = reinterpret_cast<const float4*>(a.dense_store[si] + e * dd)[j];
-      else a.dense_out[si][(int64_t)b * dd + j] = a.dense_store[si][e * dd + j];
-    }
-    return;
-  }
-  const int tiles = (B + 63) / 64;
+}
+
+__device__ __forceinline__ const IngestArgs& ingest_part(const IngestArgs& a) { return a; }
+__device__ __forceinline__ const IngestArgs& ingest_part(const StoreIngestArgs& a) { return a.g; }
+__device__ __forceinline__ const int64_t* id_source(const IngestArgs& a, int si) { return a.ids[si]; }
+__device__ __forceinline__ const int64_t* id_source(const StoreIngestArgs& a, int si) { return a.cat_store[si]; }
+
+// Grid row 0 of the hand-over without the lookup: every side's 64-sample tiles side by side (an own grid row per side meant a
+// thousand empty workgroups each).  A tile writes the fused row of each of its ids in KEY-MAJOR order
+// (rows_km[side_base + k * B + b] = key_row_offset[k] + clamp(ids[b * K + k])) -- the input tt_dedup_plan_keyed_km sorts.  A key's
+// rows sit one per K * 4 bytes in the lookup's sample-major array: gathered by the sort itself that is a 128-byte line per lane
+// (6.5 of a share's 18 us); here a workgroup reads 64 samples' ids as one run, turns the tile in LDS and writes 256-byte runs
+// per key.  A = IngestArgs: the ids are the sample-major ids[]; A = StoreIngestArgs: they come from the stores (order ->
+// entity -> cat_store) and are also written to ids_out, and the key-major rows are optional.
+template <class A>
+__device__ __forceinline__ void key_major_tile_role(const A& __restrict__ a) {
+  constexpr bool FROM_STORE = std::is_same<A, StoreIngestArgs>::value;
+  const IngestArgs& g = ingest_part(a);
+  const int B = g.B, tiles = (B + 63) / 64;
   const int si = (int)blockIdx.x / tiles, tile = (int)blockIdx.x % tiles;
-  if (si >= a.g.n_sides) return;
-  const int K = a.g.K[si];
+  if (si >= g.n_sides) return;
+  const int K = g.K[si];
   __shared__ int32_t tl[kIngestMaxK][65];
   __shared__ int64_t s_off[kIngestMaxK], s_hi[kIngestMaxK], s_ent[64];
+  const int64_t* __restrict__ ids = id_source(a, si);           // sample-major ids, or the store's id rows
   const int b0 = tile * 64;
   const int nb = min(64, B - b0), n = nb * K;
   if ((int)threadIdx.x < K) {
-    s_off[threadIdx.x] = a.g.off[si][threadIdx.x];
-    s_hi[threadIdx.x] = a.g.vocab[si][threadIdx.x] - 1;
+    s_off[threadIdx.x] = g.off[si][threadIdx.x];
+    s_hi[threadIdx.x] = g.vocab[si][threadIdx.x] - 1;
   }
-  if ((int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + nb) {
-    const int bl = threadIdx.x - 64;
-    const int64_t o = a.order ? a.order[b0 + bl] : b0 + bl;
-    int64_t e = a.entity[si][o * a.entity_stride[si]];
-    if (a.n_rows[si] > 0) e = e < 0 ? 0 : (e >= a.n_rows[si] ? a.n_rows[si] - 1 : e);
-    s_ent[bl] = e;
-  }
+  if constexpr (FROM_STORE)
+    if ((int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + nb) s_ent[threadIdx.x - 64] = store_entity(a, si, b0 + threadIdx.x - 64);
   __syncthreads();
-  constexpr int PER = kIngestMaxK * 64 / kThreads;
-  const int64_t* __restrict__ cat = a.cat_store[si];
+  constexpr int PER = kIngestMaxK * 64 / kThreads;            // ids per thread and tile: all loads issued before the first use
   int64_t idv[PER];
 #pragma unroll
-  for (int u = 0; u < PER; ++u) {                              // a sample's K ids are one contiguous run of its entity row
+  for (int u = 0; u < PER; ++u) {                             // the tile's ids (a sample's: of its entity row) are one contiguous run
     const int e = threadIdx.x + u * kThreads;
     const int ec = e < n ? e : 0;
-    const int bl = ec / K, k = ec - bl * K;
-    idv[u] = cat[s_ent[bl] * K + k];
+    if constexpr (FROM_STORE) {
+      const int bl = ec / K, k = ec - bl * K;
+      idv[u] = ids[s_ent[bl] * K + k];
+    } else {
+      idv[u] = ids[(int64_t)b0 * K + ec];
+    }
   }
 #pragma unroll
   for (int u = 0; u < PER; ++u) {
@@ -1752,18 +1707,32 @@ __global__ __launch_bounds__(kThreads) void batch_ingest_store_kernel(StoreInges
     if (e < n) {
       const int bl = e / K, k = e - bl * K;
       int64_t id = idv[u];
-      a.ids_out[si][(int64_t)b0 * K + e] = id;                 // sample-major: the KJT values() of the batch
-      id = id < 0 ? 0 : (id > s_hi[k] ? s_hi[k] : id);         // clamp: cat_embed.py:117 (as the lookup)
-      tl[k][bl] = (int32_t)row_in_table(s_off[k] + id, a.g.table_rows, a.g.dev_err);
-      if (a.g.rows_sm) a.g.rows_sm[a.g.side_base[si] + (int64_t)b0 * K + e] = tl[k][bl];
+      if constexpr (FROM_STORE) a.ids_out[si][(int64_t)b0 * K + e] = id;  // sample-major: the KJT values() of the batch
+      id = id < 0 ? 0 : (id > s_hi[k] ? s_hi[k] : id);        // clamp: cat_embed.py:117 (as the lookup)
+      tl[k][bl] = (int32_t)row_in_table(s_off[k] + id, g.table_rows, g.dev_err);
+      if (g.rows_sm) g.rows_sm[g.side_base[si] + (int64_t)b0 * K + e] = tl[k][bl];
     }
   }
-  if (a.g.rows_km == nullptr) return;
+  if (FROM_STORE && g.rows_km == nullptr) return;
   __syncthreads();
   for (int e = threadIdx.x; e < K * 64; e += kThreads) {
     const int k = e >> 6, bl = e & 63;
-    if (bl < nb) a.g.rows_km[a.g.side_base[si] + (int64_t)k * B + b0 + bl] = tl[k][bl];
+    if (bl < nb) g.rows_km[g.side_base[si] + (int64_t)k * B + b0 + bl] = tl[k][bl];
   }
+}
+
+__global__ __launch_bounds__(kThreads) void batch_ingest_kernel(IngestArgs a) {
+  if ((int)blockIdx.y == a.n_copy + 1) { cvt_role(a.v); return; }        // (last grid row, present when a.v.n > 0)
+  if (blockIdx.y >= 1) { copy_segment_role(a.c, blockIdx.y - 1); return; }
+  key_major_tile_role(a);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void batch_ingest_store_kernel(StoreIngestArgs a) {
+  if ((int)blockIdx.y == 1 + a.g.n_sides + a.g.n_copy) { cvt_role(a.g.v); return; }
+  if ((int)blockIdx.y > a.g.n_sides) { copy_segment_role(a.g.c, blockIdx.y - 1 - a.g.n_sides); return; }
+  if (blockIdx.y >= 1) { dense_rows_role<VEC>(a, blockIdx.y - 1); return; }
+  key_major_tile_role(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1799,36 +1768,8 @@ __device__ __forceinline__ void ingest_lookup_body(const StoreIngestArgs& a, con
   const int B = a.g.B;
   const int first_copy_row = 1 + (FROM_STORE ? a.g.n_sides : 0);
   if ((int)blockIdx.y == first_copy_row + a.g.n_copy) { cvt_role(a.g.v); return; }
-  if ((int)blockIdx.y >= first_copy_row) {                     // copy segments
-    const int seg = blockIdx.y - first_copy_row;
-    const int64_t n16 = a.g.c.bytes[seg] / 16, tail0 = n16 * 16;
-    const float4* __restrict__ s = reinterpret_cast<const float4*>(a.g.c.src[seg]);
-    float4* __restrict__ d = reinterpret_cast<float4*>(a.g.c.dst[seg]);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) d[i] = s[i];
-    if (blockIdx.x == 0)
-      for (int64_t i = tail0 + threadIdx.x; i < a.g.c.bytes[seg]; i += blockDim.x) a.g.c.dst[seg][i] = a.g.c.src[seg][i];
-    return;
-  }
-  if (FROM_STORE && blockIdx.y >= 1) {                         // dense feature rows of one side
-    const int si = blockIdx.y - 1;
-    const int dd = a.dense_dim[si];
-    if (dd == 0) return;
-    const int64_t* __restrict__ ent = a.entity[si];
-    const int64_t es = a.entity_stride[si];
-    const int64_t nr = a.n_rows[si];
-    const int per = VEC ? dd / 4 : dd;
-    const int64_t total = (int64_t)B * per, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-      const int b = (int)(t / per), j = (int)(t - (int64_t)b * per);
-      const int64_t o = a.order ? a.order[b] : b;
-      int64_t e = ent[o * es];
-      if (nr > 0) e = e < 0 ? 0 : (e >= nr ? nr - 1 : e);
-      if (VEC) reinterpret_cast<float4*>(a.dense_out[si] + (int64_t)b * dd)[j] = reinterpret_cast<const float4*>(a.dense_store[si] + e * dd)[j];
-      else a.dense_out[si][(int64_t)b * dd + j] = a.dense_store[si][e * dd + j];
-    }
-    return;
-  }
+  if ((int)blockIdx.y >= first_copy_row) { copy_segment_role(a.g.c, blockIdx.y - first_copy_row); return; }
+  if (FROM_STORE && blockIdx.y >= 1) { dense_rows_role<VEC>(a, blockIdx.y - 1); return; }
   // ---- row 0: tiles ----
   int si = 0;
 #pragma unroll
@@ -1864,11 +1805,7 @@ __device__ __forceinline__ void ingest_lookup_body(const StoreIngestArgs& a, con
     const int bl = ec / K, k = ec - bl * K;
     blv[cc] = bl; kv[cc] = k;
     if (FROM_STORE) {
-      const int64_t o = a.order ? a.order[b0 + bl] : b0 + bl;
-      int64_t en = a.entity[si][o * a.entity_stride[si]];
-      const int64_t nr = a.n_rows[si];
-      if (nr > 0) en = en < 0 ? 0 : (en >= nr ? nr - 1 : en);
-      idv[cc] = a.cat_store[si][en * K + k];
+      idv[cc] = a.cat_store[si][store_entity(a, si, b0 + bl) * K + k];
     } else {
       idv[cc] = a.g.ids[si][(int64_t)b0 * K + ec];
     }
@@ -2905,113 +2842,6 @@ static int handover_launch(tt_ctx* ctx, const void* fn, dim3 grid, void** args, 
   return TT_OK;
 }
 
-int tt_batch_ingest(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
-                    int32_t n_sides, int64_t B, int32_t* rows_km, int32_t* rows_sm, int64_t table_rows, const tt_cvt_list* cvt, tt_stream stream) {
-  TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "tt_batch_ingest: bad copy arguments");
-  TT_CHECK_ARG(sides && rows_km && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1, "tt_batch_ingest: bad side arguments");
-  TT_CHECK_ARG(table_rows >= 0 && table_rows <= INT32_MAX, "tt_batch_ingest: table_rows %lld out of range", (long long)table_rows);
-  IngestArgs a{};
-  int64_t mx = 0, slots = 0;
-  for (int i = 0; i < n; ++i) {
-    TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "tt_batch_ingest: segment %d NULL", i);
-    TT_CHECK_ARG(tt_aligned(dst[i], 16) && tt_aligned(src[i], 16), "tt_batch_ingest: segment %d not 16-byte aligned", i);
-    a.c.dst[i] = reinterpret_cast<char*>(dst[i]);
-    a.c.src[i] = reinterpret_cast<const char*>(src[i]);
-    a.c.bytes[i] = bytes[i];
-    mx = bytes[i] > mx ? bytes[i] : mx;
-  }
-  a.n_copy = n;
-  a.n_sides = n_sides;
-  a.B = (int32_t)B;
-  a.rows_km = rows_km;
-  a.rows_sm = rows_sm;
-  a.table_rows = (int32_t)table_rows;
-  a.dev_err = ctx->dev_err;
-  for (int i = 0; i < n_sides; ++i) {
-    const tt_embed_side& s = sides[i];
-    TT_CHECK_ARG(s.K >= 1 && s.ids && s.key_row_offset && s.key_vocab, "tt_batch_ingest: side %d NULL / no keys", i);
-    if (s.K > kIngestMaxK) {
-      tt_set_error("tt_batch_ingest: side %d has %d keys (max %d)", i, s.K, kIngestMaxK);
-      return TT_ERR_UNSUPPORTED;
-    }
-    a.ids[i] = s.ids; a.off[i] = s.key_row_offset; a.vocab[i] = s.key_vocab; a.K[i] = s.K;
-    a.side_base[i] = (int32_t)slots;
-    slots += B * s.K;
-  }
-  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "tt_batch_ingest: too many slots");
-  const int cvt_rows = fill_cvt("tt_batch_ingest", cvt, &a.v, &mx);
-  if (cvt_rows < 0) return cvt_rows;
-  int64_t gx = tt_cdiv(mx / 16 + 1, kThreads);
-  const int64_t cap = (int64_t)ctx->num_cus * 4;
-  if (gx > cap) gx = cap;
-  const int64_t tiles = tt_cdiv(B, 64) * n_sides;        // row 0 holds every tile (the copy rows stride over their segments)
-  if (tiles > gx) gx = tiles;
-  void* args[] = {&a};
-  return handover_launch(ctx, reinterpret_cast<const void*>(batch_ingest_kernel), dim3((unsigned)gx, (unsigned)(n + 1 + cvt_rows)), args,
-                         reinterpret_cast<hipStream_t>(stream));
-}
-
-int tt_batch_ingest_store(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
-                          const tt_store_side* stores, int32_t n_sides, int64_t B, const int64_t* order, int32_t* rows_km, int32_t* rows_sm,
-                          int64_t table_rows, const tt_cvt_list* cvt, tt_stream stream) {
-  TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "tt_batch_ingest_store: bad copy arguments");
-  TT_CHECK_ARG(table_rows >= 0 && table_rows <= INT32_MAX, "tt_batch_ingest_store: table_rows %lld out of range", (long long)table_rows);
-  TT_CHECK_ARG(sides && stores && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1, "tt_batch_ingest_store: bad side arguments");
-  StoreIngestArgs a{};
-  int64_t mx = 0, slots = 0, dense_pieces = 0;
-  bool vec = true;
-  for (int i = 0; i < n; ++i) {
-    TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "tt_batch_ingest_store: segment %d NULL", i);
-    TT_CHECK_ARG(tt_aligned(dst[i], 16) && tt_aligned(src[i], 16), "tt_batch_ingest_store: segment %d not 16-byte aligned", i);
-    a.g.c.dst[i] = reinterpret_cast<char*>(dst[i]);
-    a.g.c.src[i] = reinterpret_cast<const char*>(src[i]);
-    a.g.c.bytes[i] = bytes[i];
-    mx = bytes[i] > mx ? bytes[i] : mx;
-  }
-  a.g.n_copy = n;
-  a.g.n_sides = n_sides;
-  a.g.B = (int32_t)B;
-  a.g.rows_km = rows_km;
-  a.g.rows_sm = rows_sm;
-  a.g.table_rows = (int32_t)table_rows;
-  a.g.dev_err = ctx->dev_err;
-  a.order = order;
-  for (int i = 0; i < n_sides; ++i) {
-    const tt_embed_side& s = sides[i];
-    const tt_store_side& t = stores[i];
-    TT_CHECK_ARG(s.K >= 1 && s.key_row_offset && s.key_vocab, "tt_batch_ingest_store: side %d NULL / no keys", i);
-    TT_CHECK_ARG(t.entity && t.entity_stride >= 1 && t.cat_store && t.ids_out && t.dense_dim >= 0 &&
-                 (t.dense_dim == 0 || (t.dense_store && t.dense_out)), "tt_batch_ingest_store: store %d NULL / bad shape", i);
-    if (s.K > kIngestMaxK) {
-      tt_set_error("tt_batch_ingest_store: side %d has %d keys (max %d)", i, s.K, kIngestMaxK);
-      return TT_ERR_UNSUPPORTED;
-    }
-    a.g.off[i] = s.key_row_offset; a.g.vocab[i] = s.key_vocab; a.g.K[i] = s.K;
-    a.g.side_base[i] = (int32_t)slots;
-    slots += B * s.K;
-    a.entity[i] = t.entity; a.entity_stride[i] = t.entity_stride; a.dense_store[i] = t.dense_store; a.cat_store[i] = t.cat_store;
-    a.dense_out[i] = t.dense_out; a.ids_out[i] = t.ids_out; a.dense_dim[i] = t.dense_dim;
-    a.n_rows[i] = t.n_rows > 0 ? t.n_rows : 0;
-    vec = vec && t.dense_dim % 4 == 0 && tt_aligned(t.dense_store, 16) && tt_aligned(t.dense_out, 16);
-    const int64_t p = B * (int64_t)t.dense_dim;
-    dense_pieces = p > dense_pieces ? p : dense_pieces;
-  }
-  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "tt_batch_ingest_store: too many slots");
-  const int cvt_rows = fill_cvt("tt_batch_ingest_store", cvt, &a.g.v, &mx);
-  if (cvt_rows < 0) return cvt_rows;
-  int64_t gx = tt_cdiv(mx / 16 + 1, kThreads);
-  const int64_t rows_wg = tt_cdiv(vec ? dense_pieces / 4 : dense_pieces, kThreads);
-  if (rows_wg > gx) gx = rows_wg;
-  const int64_t cap = (int64_t)ctx->num_cus * 8;
-  if (gx > cap) gx = cap;
-  const int64_t tiles = tt_cdiv(B, 64) * n_sides;        // row 0 holds every tile (the other rows stride over their work)
-  if (tiles > gx) gx = tiles;
-  const dim3 grid((unsigned)gx, (unsigned)(1 + n_sides + n + cvt_rows));
-  void* args[] = {&a};
-  return handover_launch(ctx, vec ? reinterpret_cast<const void*>(batch_ingest_store_kernel<true>) : reinterpret_cast<const void*>(batch_ingest_store_kernel<false>),
-                         grid, args, reinterpret_cast<hipStream_t>(stream));
-}
-
 // shared by the two fused hand-over + lookup entries: checks the lookup half and fills LookupPart; returns the tile count or < 0
 static int64_t fill_lookup_part(tt_ctx* ctx, const char* who, const tt_embed_side* sides, int32_t n_sides, int64_t B, const tt_ingest_lookup* lk,
                                 LookupPart* lp) {
@@ -3061,22 +2891,28 @@ static int64_t fill_lookup_part(tt_ctx* ctx, const char* who, const tt_embed_sid
   return tiles;
 }
 
-#define TT_INGEST_LOOKUP_FN(FROM_STORE, VEC)                                                                              \
-  (lp.E == 8 ? reinterpret_cast<const void*>(ingest_lookup_kernel<1, FROM_STORE, VEC>)                                    \
-   : lp.E == 16 ? reinterpret_cast<const void*>(ingest_lookup_kernel<2, FROM_STORE, VEC>)                                 \
-   : lp.E == 32 ? reinterpret_cast<const void*>(ingest_lookup_kernel<4, FROM_STORE, VEC>)                                 \
-                : reinterpret_cast<const void*>(ingest_lookup_kernel<8, FROM_STORE, VEC>))
-
-int tt_batch_ingest_lookup(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
-                           int32_t n_sides, int64_t B, int32_t* rows_km, const tt_ingest_lookup* lk, const tt_cvt_list* cvt, tt_stream stream) {
-  TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "tt_batch_ingest_lookup: bad copy arguments");
-  TT_CHECK_ARG(sides && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1, "tt_batch_ingest_lookup: bad side arguments");
-  StoreIngestArgs a{};
-  LookupPart lp{};
-  int64_t mx = 0, slots = 0;
+// Everything the four hand-over entries share.  stores != nullptr: the ids and dense features come from the device stores
+// (StoreIngestArgs); lk != nullptr: the launch also looks the rows up (LookupPart).  Checks the arguments -- error strings
+// carry the entry's name `who` -- and fills the kernel arguments and the grid.
+struct Handover {
+  StoreIngestArgs a;
+  LookupPart lp;
+  dim3 grid;
+  bool vec;            // store forms: every side's dense rows move in 16-byte pieces
+};
+static int build_handover(tt_ctx* ctx, const char* who, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
+                          const tt_embed_side* sides, const tt_store_side* stores, int32_t n_sides, int64_t B, const int64_t* order,
+                          int32_t* rows_km, int32_t* rows_sm, int64_t table_rows, const tt_cvt_list* cvt, const tt_ingest_lookup* lk,
+                          Handover* h) {
+  TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "%s: bad copy arguments", who);
+  TT_CHECK_ARG(sides && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1, "%s: bad side arguments", who);
+  TT_CHECK_ARG(table_rows >= 0 && table_rows <= INT32_MAX, "%s: table_rows %lld out of range", who, (long long)table_rows);
+  *h = Handover{};
+  StoreIngestArgs& a = h->a;
+  int64_t mx = 0, slots = 0, dense_pieces = 0;
   for (int i = 0; i < n; ++i) {
-    TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "tt_batch_ingest_lookup: segment %d NULL", i);
-    TT_CHECK_ARG(tt_aligned(dst[i], 16) && tt_aligned(src[i], 16), "tt_batch_ingest_lookup: segment %d not 16-byte aligned", i);
+    TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "%s: segment %d NULL", who, i);
+    TT_CHECK_ARG(tt_aligned(dst[i], 16) && tt_aligned(src[i], 16), "%s: segment %d not 16-byte aligned", who, i);
     a.g.c.dst[i] = reinterpret_cast<char*>(dst[i]);
     a.g.c.src[i] = reinterpret_cast<const char*>(src[i]);
     a.g.c.bytes[i] = bytes[i];
@@ -3086,87 +2922,103 @@ int tt_batch_ingest_lookup(tt_ctx* ctx, int32_t n, void* const* dst, const void*
   a.g.n_sides = n_sides;
   a.g.B = (int32_t)B;
   a.g.rows_km = rows_km;
+  a.g.rows_sm = rows_sm;
+  a.g.table_rows = (int32_t)table_rows;
+  a.g.dev_err = ctx->dev_err;
+  a.order = order;
+  h->vec = true;
   for (int i = 0; i < n_sides; ++i) {
     const tt_embed_side& s = sides[i];
-    TT_CHECK_ARG(s.K >= 1 && s.ids && s.key_row_offset && s.key_vocab, "tt_batch_ingest_lookup: side %d NULL / no keys", i);
+    TT_CHECK_ARG(s.K >= 1 && (stores || s.ids) && s.key_row_offset && s.key_vocab, "%s: side %d NULL / no keys", who, i);
     if (s.K > kIngestMaxK) {
-      tt_set_error("tt_batch_ingest_lookup: side %d has %d keys (max %d)", i, s.K, kIngestMaxK);
+      tt_set_error("%s: side %d has %d keys (max %d)", who, i, s.K, kIngestMaxK);
       return TT_ERR_UNSUPPORTED;
     }
-    a.g.ids[i] = s.ids; a.g.off[i] = s.key_row_offset; a.g.vocab[i] = s.key_vocab; a.g.K[i] = s.K;
+    a.g.ids[i] = stores ? nullptr : s.ids; a.g.off[i] = s.key_row_offset; a.g.vocab[i] = s.key_vocab; a.g.K[i] = s.K;
     a.g.side_base[i] = (int32_t)slots;
     slots += B * s.K;
+    if (!stores) continue;
+    const tt_store_side& t = stores[i];
+    TT_CHECK_ARG(t.entity && t.entity_stride >= 1 && t.cat_store && t.ids_out && t.dense_dim >= 0 && t.n_rows >= 0 &&
+                 (t.dense_dim == 0 || (t.dense_store && t.dense_out)), "%s: store %d NULL / bad shape", who, i);
+    a.entity[i] = t.entity; a.entity_stride[i] = t.entity_stride; a.dense_store[i] = t.dense_store; a.cat_store[i] = t.cat_store;
+    a.dense_out[i] = t.dense_out; a.ids_out[i] = t.ids_out; a.dense_dim[i] = t.dense_dim;
+    a.n_rows[i] = t.n_rows;
+    h->vec = h->vec && t.dense_dim % 4 == 0 && tt_aligned(t.dense_store, 16) && tt_aligned(t.dense_out, 16);
+    const int64_t p = B * (int64_t)t.dense_dim;
+    dense_pieces = p > dense_pieces ? p : dense_pieces;
   }
-  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "tt_batch_ingest_lookup: too many slots");
-  const int64_t tiles = fill_lookup_part(ctx, "tt_batch_ingest_lookup", sides, n_sides, B, lk, &lp);
-  if (tiles < 0) return (int)tiles;
-  const int cvt_rows = fill_cvt("tt_batch_ingest_lookup", cvt, &a.g.v, &mx);
+  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "%s: too many slots", who);
+  int64_t tiles = tt_cdiv(B, 64) * n_sides;                // row 0 holds every tile (the other rows stride over their work)
+  if (lk) {
+    tiles = fill_lookup_part(ctx, who, sides, n_sides, B, lk, &h->lp);
+    if (tiles < 0) return (int)tiles;
+  }
+  const int cvt_rows = fill_cvt(who, cvt, &a.g.v, &mx);
   if (cvt_rows < 0) return cvt_rows;
   int64_t gx = tt_cdiv(mx / 16 + 1, kThreads);
-  const int64_t cap = (int64_t)ctx->num_cus * 4;
+  const int64_t rows_wg = tt_cdiv(h->vec ? dense_pieces / 4 : dense_pieces, kThreads);
+  if (rows_wg > gx) gx = rows_wg;
+  // workgroups per CU the copy and dense rows stride with: the forms from a staged batch keep copy_multi's 4, the store forms
+  // take 8 (as written with the dense-feature rows; no measurement of either choice is recorded)
+  const int64_t cap = (int64_t)ctx->num_cus * (stores ? 8 : 4);
   if (gx > cap) gx = cap;
   if (tiles > gx) gx = tiles;
-  const dim3 grid((unsigned)gx, (unsigned)(n + 1 + cvt_rows));
-  void* args[] = {&a, &lp};
-  return handover_launch(ctx, TT_INGEST_LOOKUP_FN(false, true), grid, args, reinterpret_cast<hipStream_t>(stream));
+  h->grid = dim3((unsigned)gx, (unsigned)(1 + (stores ? n_sides : 0) + n + cvt_rows));
+  return TT_OK;
+}
+
+#define TT_INGEST_LOOKUP_FN(FROM_STORE, VEC)                                                                              \
+  (h.lp.E == 8 ? reinterpret_cast<const void*>(ingest_lookup_kernel<1, FROM_STORE, VEC>)                                  \
+   : h.lp.E == 16 ? reinterpret_cast<const void*>(ingest_lookup_kernel<2, FROM_STORE, VEC>)                               \
+   : h.lp.E == 32 ? reinterpret_cast<const void*>(ingest_lookup_kernel<4, FROM_STORE, VEC>)                               \
+                  : reinterpret_cast<const void*>(ingest_lookup_kernel<8, FROM_STORE, VEC>))
+
+int tt_batch_ingest(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
+                    int32_t n_sides, int64_t B, int32_t* rows_km, int32_t* rows_sm, int64_t table_rows, const tt_cvt_list* cvt, tt_stream stream) {
+  TT_CHECK_ARG(rows_km, "tt_batch_ingest: bad side arguments");      // (this form's tiles always write the key-major rows)
+  Handover h;
+  const int rc = build_handover(ctx, "tt_batch_ingest", n, dst, src, bytes, sides, nullptr, n_sides, B, nullptr, rows_km, rows_sm,
+                                table_rows, cvt, nullptr, &h);
+  if (rc != TT_OK) return rc;
+  void* args[] = {&h.a.g};
+  return handover_launch(ctx, reinterpret_cast<const void*>(batch_ingest_kernel), h.grid, args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_batch_ingest_store(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
+                          const tt_store_side* stores, int32_t n_sides, int64_t B, const int64_t* order, int32_t* rows_km, int32_t* rows_sm,
+                          int64_t table_rows, const tt_cvt_list* cvt, tt_stream stream) {
+  TT_CHECK_ARG(stores, "tt_batch_ingest_store: bad side arguments");
+  Handover h;
+  const int rc = build_handover(ctx, "tt_batch_ingest_store", n, dst, src, bytes, sides, stores, n_sides, B, order, rows_km, rows_sm,
+                                table_rows, cvt, nullptr, &h);
+  if (rc != TT_OK) return rc;
+  void* args[] = {&h.a};
+  return handover_launch(ctx, h.vec ? reinterpret_cast<const void*>(batch_ingest_store_kernel<true>) : reinterpret_cast<const void*>(batch_ingest_store_kernel<false>),
+                         h.grid, args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_batch_ingest_lookup(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const tt_embed_side* sides,
+                           int32_t n_sides, int64_t B, int32_t* rows_km, const tt_ingest_lookup* lk, const tt_cvt_list* cvt, tt_stream stream) {
+  Handover h;
+  const int rc = build_handover(ctx, "tt_batch_ingest_lookup", n, dst, src, bytes, sides, nullptr, n_sides, B, nullptr, rows_km, nullptr, 0,
+                                cvt, lk, &h);
+  if (rc != TT_OK) return rc;
+  void* args[] = {&h.a, &h.lp};
+  return handover_launch(ctx, TT_INGEST_LOOKUP_FN(false, true), h.grid, args, reinterpret_cast<hipStream_t>(stream));
 }
 
 int tt_batch_ingest_store_lookup(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
                                  const tt_embed_side* sides, const tt_store_side* stores, int32_t n_sides, int64_t B, const int64_t* order,
                                  int32_t* rows_km, const tt_ingest_lookup* lk, const tt_cvt_list* cvt, tt_stream stream) {
-  TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "tt_batch_ingest_store_lookup: bad copy arguments");
-  TT_CHECK_ARG(sides && stores && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1, "tt_batch_ingest_store_lookup: bad side arguments");
-  StoreIngestArgs a{};
-  LookupPart lp{};
-  int64_t mx = 0, slots = 0, dense_pieces = 0;
-  bool vec = true;
-  for (int i = 0; i < n; ++i) {
-    TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "tt_batch_ingest_store_lookup: segment %d NULL", i);
-    TT_CHECK_ARG(tt_aligned(dst[i], 16) && tt_aligned(src[i], 16), "tt_batch_ingest_store_lookup: segment %d not 16-byte aligned", i);
-    a.g.c.dst[i] = reinterpret_cast<char*>(dst[i]);
-    a.g.c.src[i] = reinterpret_cast<const char*>(src[i]);
-    a.g.c.bytes[i] = bytes[i];
-    mx = bytes[i] > mx ? bytes[i] : mx;
-  }
-  a.g.n_copy = n;
-  a.g.n_sides = n_sides;
-  a.g.B = (int32_t)B;
-  a.g.rows_km = rows_km;
-  a.order = order;
-  for (int i = 0; i < n_sides; ++i) {
-    const tt_embed_side& s = sides[i];
-    const tt_store_side& t = stores[i];
-    TT_CHECK_ARG(s.K >= 1 && s.key_row_offset && s.key_vocab, "tt_batch_ingest_store_lookup: side %d NULL / no keys", i);
-    TT_CHECK_ARG(t.entity && t.entity_stride >= 1 && t.cat_store && t.ids_out && t.dense_dim >= 0 && t.n_rows >= 0 &&
-                 (t.dense_dim == 0 || (t.dense_store && t.dense_out)), "tt_batch_ingest_store_lookup: store %d NULL / bad shape", i);
-    if (s.K > kIngestMaxK) {
-      tt_set_error("tt_batch_ingest_store_lookup: side %d has %d keys (max %d)", i, s.K, kIngestMaxK);
-      return TT_ERR_UNSUPPORTED;
-    }
-    a.g.off[i] = s.key_row_offset; a.g.vocab[i] = s.key_vocab; a.g.K[i] = s.K;
-    a.g.side_base[i] = (int32_t)slots;
-    slots += B * s.K;
-    a.entity[i] = t.entity; a.entity_stride[i] = t.entity_stride; a.dense_store[i] = t.dense_store; a.cat_store[i] = t.cat_store;
-    a.dense_out[i] = t.dense_out; a.ids_out[i] = t.ids_out; a.dense_dim[i] = t.dense_dim;
-    a.n_rows[i] = t.n_rows > 0 ? t.n_rows : 0;
-    vec = vec && t.dense_dim % 4 == 0 && tt_aligned(t.dense_store, 16) && tt_aligned(t.dense_out, 16);
-    const int64_t p = B * (int64_t)t.dense_dim;
-    dense_pieces = p > dense_pieces ? p : dense_pieces;
-  }
-  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "tt_batch_ingest_store_lookup: too many slots");
-  const int64_t tiles = fill_lookup_part(ctx, "tt_batch_ingest_store_lookup", sides, n_sides, B, lk, &lp);
-  if (tiles < 0) return (int)tiles;
-  const int cvt_rows = fill_cvt("tt_batch_ingest_store_lookup", cvt, &a.g.v, &mx);
-  if (cvt_rows < 0) return cvt_rows;
-  int64_t gx = tt_cdiv(mx / 16 + 1, kThreads);
-  const int64_t rows_wg = tt_cdiv(vec ? dense_pieces / 4 : dense_pieces, kThreads);
-  if (rows_wg > gx) gx = rows_wg;
-  const int64_t cap = (int64_t)ctx->num_cus * 8;
-  if (gx > cap) gx = cap;
-  if (tiles > gx) gx = tiles;
-  const dim3 grid((unsigned)gx, (unsigned)(1 + n_sides + n + cvt_rows));
-  void* args[] = {&a, &lp};
-  return handover_launch(ctx, vec ? TT_INGEST_LOOKUP_FN(true, true) : TT_INGEST_LOOKUP_FN(true, false), grid, args, reinterpret_cast<hipStream_t>(stream));
+  TT_CHECK_ARG(stores, "tt_batch_ingest_store_lookup: bad side arguments");
+  Handover h;
+  const int rc = build_handover(ctx, "tt_batch_ingest_store_lookup", n, dst, src, bytes, sides, stores, n_sides, B, order, rows_km, nullptr,
+                                0, cvt, lk, &h);
+  if (rc != TT_OK) return rc;
+  void* args[] = {&h.a, &h.lp};
+  return handover_launch(ctx, h.vec ? TT_INGEST_LOOKUP_FN(true, true) : TT_INGEST_LOOKUP_FN(true, false), h.grid, args,
+                         reinterpret_cast<hipStream_t>(stream));
 }
 
 int tt_batch_gather(tt_ctx* ctx, const int64_t* entity, int64_t B, const float* dense_store, int32_t dense_dim,

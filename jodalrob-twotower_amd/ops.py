@@ -663,17 +663,24 @@ def linear_fwd(X, W, bias, relu=False):
     return Y
 
 
+def _copy_segments(pairs, who):
+    """[(dst, src)] contiguous same-sized tensors -> (n, dst, src, nb): the ctypes arrays of one launch's copy segments."""
+    for d, s_ in pairs:
+        if d.numel() * d.element_size() != s_.numel() * s_.element_size() or not d.is_contiguous() or not s_.is_contiguous():
+            raise ValueError(f"{who}: segments must be contiguous and equally sized")
+    n = len(pairs)
+    dst = (L.vp * max(n, 1))(*[d.data_ptr() for d, _ in pairs])
+    src = (L.vp * max(n, 1))(*[s_.data_ptr() for _, s_ in pairs])
+    nb = (L.i64 * max(n, 1))(*[d.numel() * d.element_size() for d, _ in pairs])
+    return n, dst, src, nb
+
+
 def copy_multi(pairs):
     """pairs: [(dst, src)] contiguous same-sized tensors on one device -> one launch."""
     if not pairs:
         return
-    dev, n = pairs[0][0].device, len(pairs)
-    dst = (L.vp * n)(*[d.data_ptr() for d, _ in pairs])
-    src = (L.vp * n)(*[s.data_ptr() for _, s in pairs])
-    nb = (L.i64 * n)(*[d.numel() * d.element_size() for d, _ in pairs])
-    for d, s_ in pairs:
-        if d.numel() * d.element_size() != s_.numel() * s_.element_size() or not d.is_contiguous() or not s_.is_contiguous():
-            raise ValueError("copy_multi: segments must be contiguous and equally sized")
+    dev = pairs[0][0].device
+    n, dst, src, nb = _copy_segments(pairs, "copy_multi")
     with _timed("tt_copy_multi"):
         L.check(L.load().tt_copy_multi(L.ctx(dev), n, dst, src, nb, L.stream(dev)), "tt_copy_multi")
 
@@ -723,6 +730,8 @@ def _lookup_part(table: torch.Tensor):
 
 
 def _embed_sides(sides, B, dev, who, with_ids: bool, with_out: bool):
+    """sides -> (tt_embed_side array, sum(B*K)).  with_ids: the sides' own ids (False: the hand-over reads them from the stores);
+    with_out: the sides' output views (the fused hand-over + lookup)."""
     arr = (L.EmbedSide * len(sides))()
     M = 0
     for i, s in enumerate(sides):
@@ -739,6 +748,11 @@ def _embed_sides(sides, B, dev, who, with_ids: bool, with_out: bool):
     return arr, M
 
 
+def _check_rows(rows, M, who, name):
+    if rows is not None and (rows.dtype != torch.int32 or rows.numel() != M or not rows.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous int32 tensor of sum(B*K) elements")
+
+
 def batch_ingest(pairs, sides: Sequence[LookupSide], B: int, rows_km: Optional[torch.Tensor], table: Optional[torch.Tensor] = None,
                  rows_sm: Optional[torch.Tensor] = None, cvt=None, table_rows: int = 0):
     """copy_multi's segments plus, per side, the fused rows of the side's ids in key-major order (tt_batch_ingest): the batch
@@ -748,40 +762,17 @@ def batch_ingest(pairs, sides: Sequence[LookupSide], B: int, rows_km: Optional[t
     the input of embed_lookup_rows.  table_rows (without `table`): the size of the row space the fused rows index -- a row outside
     it is stored as the last row and raises the device error word (_lib.check_device_errors), so neither embed_lookup_rows nor the
     plan's consumers touch memory outside the table; 0 = unchecked."""
+    dev = table.device if table is not None else rows_km.device
+    n, dst, src, nb = _copy_segments(pairs, "batch_ingest")
+    arr, M = _embed_sides(sides, B, dev, "batch_ingest", True, table is not None)
+    _check_rows(rows_km, M, "batch_ingest", "rows_km")
     if table is not None:
-        dev, n = table.device, len(pairs)
-        dst = (L.vp * max(n, 1))(*[d.data_ptr() for d, _ in pairs])
-        src = (L.vp * max(n, 1))(*[s.data_ptr() for _, s in pairs])
-        nb = (L.i64 * max(n, 1))(*[d.numel() * d.element_size() for d, _ in pairs])
-        for d, s_ in pairs:
-            if d.numel() * d.element_size() != s_.numel() * s_.element_size() or not d.is_contiguous() or not s_.is_contiguous():
-                raise ValueError("batch_ingest: segments must be contiguous and equally sized")
-        arr, M = _embed_sides(sides, B, dev, "batch_ingest", True, True)
-        if rows_km is not None and (rows_km.dtype != torch.int32 or rows_km.numel() != M or not rows_km.is_contiguous()):
-            raise ValueError("batch_ingest: rows_km must be a contiguous int32 tensor of sum(B*K) elements")
         lk = _lookup_part(table)
         with _timed("tt_batch_ingest_lookup"):
             L.check(L.load().tt_batch_ingest_lookup(L.ctx(dev), n, dst, src, nb, arr, len(sides), B, L.ptr(rows_km), C.byref(lk), _cvt_list(cvt),
                                                     L.stream(dev)), "tt_batch_ingest_lookup")
         return
-    dev, n = rows_km.device, len(pairs)
-    dst = (L.vp * max(n, 1))(*[d.data_ptr() for d, _ in pairs])
-    src = (L.vp * max(n, 1))(*[s.data_ptr() for _, s in pairs])
-    nb = (L.i64 * max(n, 1))(*[d.numel() * d.element_size() for d, _ in pairs])
-    for d, s_ in pairs:
-        if d.numel() * d.element_size() != s_.numel() * s_.element_size() or not d.is_contiguous() or not s_.is_contiguous():
-            raise ValueError("batch_ingest: segments must be contiguous and equally sized")
-    arr = (L.EmbedSide * len(sides))()
-    M = 0
-    for i, s in enumerate(sides):
-        if s.ids.dtype != torch.int64 or not s.ids.is_contiguous() or s.ids.device != dev or s.ids.numel() != B * s.K:
-            raise ValueError(f"batch_ingest: side {i} needs {B}*{s.K} contiguous int64 ids on {dev}")
-        arr[i] = L.EmbedSide(L.ptr(s.ids), L.ptr(s.key_row_offset), L.ptr(s.key_vocab), None, 0, s.K, TT_F32)
-        M += B * s.K
-    if rows_km.dtype != torch.int32 or rows_km.numel() != M or not rows_km.is_contiguous():
-        raise ValueError("batch_ingest: rows_km must be a contiguous int32 tensor of sum(B*K) elements")
-    if rows_sm is not None and (rows_sm.dtype != torch.int32 or rows_sm.numel() != M or not rows_sm.is_contiguous()):
-        raise ValueError("batch_ingest: rows_sm must be a contiguous int32 tensor of sum(B*K) elements")
+    _check_rows(rows_sm, M, "batch_ingest", "rows_sm")
     with _timed("tt_batch_ingest"):
         L.check(L.load().tt_batch_ingest(L.ctx(dev), n, dst, src, nb, arr, len(sides), B, L.ptr(rows_km), L.ptr(rows_sm), int(table_rows),
                                          _cvt_list(cvt), L.stream(dev)), "tt_batch_ingest")
@@ -807,19 +798,16 @@ def batch_ingest_store(pairs, sides: Sequence[LookupSide], stores: Sequence[Stor
     Without `order` the entity view must hold the batch (B entries at its stride); a pair list or offset that does not is a
     ValueError here, not an out-of-bounds read on the device (the reference raises IndexError / KeyError:
     unified_bid_data_loader.py:495-498); entity indices are clamped into the store by the kernel (tt_store_side.n_rows)."""
-    dev, n = stores[0].dense_out.device, len(pairs)
+    dev = stores[0].dense_out.device
     for i, t in enumerate(stores):
         if t.entity.dtype != torch.int64 or t.entity.dim() != 1 or t.entity_stride < 1 or t.entity.device != dev:
             raise ValueError(f"batch_ingest_store: store {i}: entity must be a 1-D int64 view on {dev}")
         need = (B - 1) * t.entity_stride + 1 if order is None else 1
         if t.entity.numel() < need:
             raise ValueError(f"batch_ingest_store: store {i}: the batch runs past the pair list ({t.entity.numel()} entries, {need} needed)")
-    dst = (L.vp * max(n, 1))(*[d.data_ptr() for d, _ in pairs])
-    src = (L.vp * max(n, 1))(*[s.data_ptr() for _, s in pairs])
-    nb = (L.i64 * max(n, 1))(*[d.numel() * d.element_size() for d, _ in pairs])
-    arr = (L.EmbedSide * len(sides))()
+    n, dst, src, nb = _copy_segments(pairs, "batch_ingest_store")
+    arr, M = _embed_sides(sides, B, dev, "batch_ingest_store", False, table is not None)
     st = (L.StoreSide * len(sides))()
-    M = 0
     for i, (s, t) in enumerate(zip(sides, stores)):
         dd = t.dense_store.shape[1]
         if t.cat_store.dtype != torch.int64 or t.cat_store.shape[1] != s.K or not t.cat_store.is_contiguous() or \
@@ -828,17 +816,9 @@ def batch_ingest_store(pairs, sides: Sequence[LookupSide], stores: Sequence[Stor
         if t.dense_out.shape != (B, dd) or not t.dense_out.is_contiguous() or t.dense_out.dtype != torch.float32 or \
                 t.ids_out.numel() != B * s.K or t.ids_out.dtype != torch.int64 or not t.ids_out.is_contiguous():
             raise ValueError(f"batch_ingest_store: side {i}: static buffers must be contiguous f32 [{B}, {dd}] and int64 [{B * s.K}]")
-        if table is not None:
-            if s.out.shape[0] != B or s.out.device != dev:
-                raise ValueError(f"batch_ingest_store: side {i}: output view must be [B, K*E] on {dev}")
-            arr[i] = L.EmbedSide(None, L.ptr(s.key_row_offset), L.ptr(s.key_vocab), L.ptr(s.out), s.out.stride(0), s.K, _dt(s.out))
-        else:
-            arr[i] = L.EmbedSide(None, L.ptr(s.key_row_offset), L.ptr(s.key_vocab), None, 0, s.K, TT_F32)
         st[i] = L.StoreSide(L.ptr(t.entity), t.entity_stride, L.ptr(t.dense_store), L.ptr(t.cat_store), L.ptr(t.dense_out), L.ptr(t.ids_out), dd,
                             min(int(t.dense_store.shape[0]), 2 ** 31 - 1))
-        M += B * s.K
-    if rows_km is not None and (rows_km.dtype != torch.int32 or rows_km.numel() != M or not rows_km.is_contiguous()):
-        raise ValueError("batch_ingest_store: rows_km must be a contiguous int32 tensor of sum(B*K) elements")
+    _check_rows(rows_km, M, "batch_ingest_store", "rows_km")
     if order is not None:
         if order.dtype != torch.int64 or not order.is_contiguous() or order_offset < 0 or order_offset + B > order.numel():
             raise ValueError("batch_ingest_store: order must be a contiguous int64 tensor holding the batch's B entries")
@@ -851,8 +831,7 @@ def batch_ingest_store(pairs, sides: Sequence[LookupSide], stores: Sequence[Stor
             L.check(L.load().tt_batch_ingest_store_lookup(L.ctx(dev), n, dst, src, nb, arr, st, len(sides), B, order_ptr, L.ptr(rows_km),
                                                           C.byref(lk), _cvt_list(cvt), L.stream(dev)), "tt_batch_ingest_store_lookup")
         return
-    if rows_sm is not None and (rows_sm.dtype != torch.int32 or rows_sm.numel() != M or not rows_sm.is_contiguous()):
-        raise ValueError("batch_ingest_store: rows_sm must be a contiguous int32 tensor of sum(B*K) elements")
+    _check_rows(rows_sm, M, "batch_ingest_store", "rows_sm")
     with _timed("tt_batch_ingest_store"):
         L.check(L.load().tt_batch_ingest_store(L.ctx(dev), n, dst, src, nb, arr, st, len(sides), B, order_ptr, L.ptr(rows_km), L.ptr(rows_sm),
                                                int(table_rows), _cvt_list(cvt), L.stream(dev)), "tt_batch_ingest_store")
