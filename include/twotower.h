@@ -89,6 +89,9 @@ uint64_t tt_launch_count(void);
 /* TT_OPT_CHAIN_SPIN (default 2^22): polls after which a tile of a chained launch stops waiting for a predecessor (it then raises
  * the device error word instead of hanging the GPU); tests lower it to provoke the error path. */
 #define TT_OPT_CHAIN_SPIN 8
+/* TT_OPT_RETRIEVE_SPLITS (default 0 = chosen from the shapes): catalogue splits of tt_retrieve_topk_* (clamped to
+ * [1, min(32, ceil(nC / 32))]).  Every value gives the same results bit for bit (tests vary it). */
+#define TT_OPT_RETRIEVE_SPLITS 9
 int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value);
 /* Device-side errors.  A kernel that cannot complete its contract without hanging or faulting the GPU (a tile of a chained
  * segment-head launch whose bounded wait for a predecessor expired; a lookup whose decoded row lies outside the table it was given
@@ -564,6 +567,36 @@ int tt_diag_rank_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int
  * predict_batch :195 and evaluator.py:35); k <= 64 */
 int tt_topk_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t lds, int32_t k,
                  float* vals, int64_t* idx, tt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Catalogue-wide retrieval: the k best catalogue rows of every query, and optionally the rank of a given positive, in one
+ * sweep over the catalogue that never writes a score to memory (what a user of the trained towers searches with; the
+ * in-batch tt_score_matrix + tt_topk_rows pair only ranks the companies of one batch).
+ *   queries Q [nQ, D], catalogue C [nC, D]; 1 <= D <= 256, 1 <= nC < 2^31, 0 <= k <= min(64, nC).
+ *   tt_retrieve_topk_bf16: Q_packed / C_packed are tt_score_pack_bf16 images (reused as they are); the score is
+ *     s(q, c) = <bf16 image row q, bf16 image row c> in f32 on v_mfma_f32_32x32x16_bf16, i.e. <Q_q, C_c> times the product of
+ *     the scales the two images were packed with (pack the catalogue with inv_t and the queries with 1 for s = cos / T on
+ *     L2-normalised towers; nothing is normalised here).
+ *   tt_retrieve_topk_f32: plain row-major f32 Q and C; s(q, c) = inv_t * (f32 FMA chain over d = 0 .. D-1, in that order).
+ * Outputs (k >= 1; vals and idx required): vals f32 [nQ, k] and idx int64 [nQ, k], per query sorted by value descending, ties
+ *   to the LOWER catalogue index (tt_topk_rows's order).
+ * Rank (positives != NULL, then rank != NULL, else both NULL): positives [nQ] int32 (positives_i64 = 0) or int64 (1); rank int32
+ *   [nQ] = #{c : s(q,c) > s(q,p)} + #{c < p : s(q,c) == s(q,p)} (tt_diag_rank_rows's rule), -1 where p is outside [0, nC).
+ *   The positive's score comes from the same instruction sequence as every other score, and the counts from the same sweep
+ *   as the top-k.  k = 0 asks for ranks only (positives required).
+ * Workspace: tt_retrieve_workspace_bytes(nQ, nC, D, k) bytes (0 for an invalid shape), 16-byte aligned, caller memory.
+ * Scores are assumed finite (a NaN score is never selected; -inf entries fill a list only when nothing better exists, idx -1).
+ * Three launches on `stream` (positive scores, sweep, per-query merge), no host synchronisation and no allocation: a search
+ * can be captured into a graph (one stream, no parallel branches).  Results are bitwise identical from run to run and for
+ * every split count (TT_OPT_RETRIEVE_SPLITS).  A bad argument returns TT_ERR_INVALID_ARG and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+size_t tt_retrieve_workspace_bytes(int64_t nQ, int64_t nC, int32_t D, int32_t k);
+int tt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D, int32_t k,
+                          const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
+                          size_t workspace_bytes, tt_stream stream);
+int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
+                         const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
+                         size_t workspace_bytes, tt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Generic Linear used by the one-off feature projection -- replaces FeatureProjector.forward

@@ -17,9 +17,10 @@ from .feature_projector import FeatureProjector                                 
 from .feature_preprocessor import FeaturePreprocessor                             # noqa: F401
 from .evaluator import TwoTowerEvaluator                                          # noqa: F401
 from .optim import FusedAdam                                                      # noqa: F401
+from .retrieval import CatalogIndex                                               # noqa: F401
 
 __all__ = ["KeyedJaggedTensor", "build_batch_kjt", "SideSchema", "PairSchema", "TorchRecSchema",
            "build_torchrec_schema_from_meta", "classify_columns", "CategoricalEmbedder", "EmbeddingStore",
            "create_categorical_embedder", "BaseTower", "NoticeTower", "CompanyTower", "TwoTowerModel",
            "create_two_tower_model", "TwoTowerTrainTask", "create_two_tower_train_task", "FeatureProjector",
-           "FeaturePreprocessor", "TwoTowerEvaluator", "FusedAdam"]
+           "FeaturePreprocessor", "TwoTowerEvaluator", "FusedAdam", "CatalogIndex"]

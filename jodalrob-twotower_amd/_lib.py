@@ -155,6 +155,9 @@ SIGNATURES = {
     "tt_score_dense_bwd": (C.c_int, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "tt_diag_rank_rows": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp]),
     "tt_topk_rows": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, vp, vp]),
+    "tt_retrieve_workspace_bytes": (sz, [i64, i64, i32, i32]),
+    "tt_retrieve_topk_bf16": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "tt_retrieve_topk_f32": (C.c_int, [vp, vp, i64, vp, i64, i32, f32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "tt_linear_fwd": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, i64, i32, i32, i32, vp]),
     "tt_route_workspace_bytes": (sz, [i64, i32]),
     "tt_route_bucket": (C.c_int, [vp, vp, vp, i64, i32, i32, C.POINTER(i32), i32, vp, vp, vp, vp, vp, vp, sz, vp]),
@@ -235,6 +238,7 @@ TT_OPT_FP8_GRAD = 5
 TT_OPT_CHAINED = 6
 TT_OPT_LOOKUP_NT = 7
 TT_OPT_CHAIN_SPIN = 8
+TT_OPT_RETRIEVE_SPLITS = 9
 
 
 def set_option(device: torch.device, option: int, value: int):

@@ -34,6 +34,7 @@ struct tt_ctx {
   int chained;              // TT_OPT_CHAINED: use them (default 1); 0 = the multi-launch forms (same results; tests compare)
   uint32_t* dev_err;        // sticky device-side error word (TT_DEVERR_*): behind the chain pool; tt_ctx_check_device_errors
   int chain_spin;           // TT_OPT_CHAIN_SPIN: polls before a chained tile gives up (default 2^22)
+  int retrieve_splits;      // TT_OPT_RETRIEVE_SPLITS: catalogue splits of tt_retrieve_topk_* (0 = chosen from the shapes)
   int lookup_nt;            // TT_OPT_LOOKUP_NT: the fused hand-over + lookup launch stores its bf16 rows non-temporally (default 0)
   // hand-over launches as nodes of a captured graph (tt_handover_retarget): while ho_exec is set, tt_batch_ingest* re-point node
   // ho_node of that executable graph at their arguments instead of launching; ho_last = the node the last tt_batch_ingest* call left

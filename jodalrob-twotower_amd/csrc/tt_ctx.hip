@@ -80,6 +80,7 @@ int tt_ctx_create(int device, tt_ctx** out) {
   c->chain_used = 0;
   c->chained = 1;
   c->chain_spin = 1 << 22;
+  c->retrieve_splits = 0;
   c->dev_err = nullptr;
   c->ho_exec = c->ho_node = c->ho_last = nullptr;
   {
@@ -132,6 +133,10 @@ int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value) {
     case TT_OPT_CHAIN_SPIN:
       TT_CHECK_ARG(value >= 1, "tt_ctx_set_option: TT_OPT_CHAIN_SPIN needs a value >= 1");
       ctx->chain_spin = value;
+      break;
+    case TT_OPT_RETRIEVE_SPLITS:
+      TT_CHECK_ARG(value >= 0, "tt_ctx_set_option: TT_OPT_RETRIEVE_SPLITS needs a value >= 0");
+      ctx->retrieve_splits = value;
       break;
     default: tt_set_error("tt_ctx_set_option: unknown option %d", option); return TT_ERR_INVALID_ARG;
   }

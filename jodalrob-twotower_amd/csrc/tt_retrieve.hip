@@ -1,0 +1,514 @@
+// Catalogue-wide top-k retrieval and rank (tt_retrieve_topk_bf16 / tt_retrieve_topk_f32): the catalogue streams past the
+// queries in 32-row tiles, every query keeps its best k, and no score is ever written to memory.
+//
+// Three launches on the caller's stream, no host synchronisation:
+//   pos   (rank only)  the positive's score s_p of every query, computed by the SAME tile routine as the sweep, so that the
+//                      sweep's comparisons against it are bit-for-bit;
+//   sweep              grid (query tile of 32 x catalogue split).  A wave owns 32 queries and the split's tiles; per tile it forms
+//                      the 32 x 32 score block X[row][query] with lane (c, h) holding query c and rows rowmap(r, h) (as in
+//                      tt_score_bf16.hip).  Each query has a running threshold (its k-th best so far): one v_max3 chain and one
+//                      compare on the accumulators reject a tile in the common case.  Scores that pass go into the query's LDS
+//                      candidate region; when a region is nearly full the wave selects the k best of it (binary search for
+//                      the k-th largest order key, index tie break) and raises the threshold.  The split's k best (unsorted)
+//                      and its rank counts go to the workspace;
+//   merge              one wave per query: the k best of the S partial lists, sorted, and the summed rank.
+// Order: value descending, then lower catalogue index (tt_topk_rows).  Rank: #{c : s > s_p} + #{c < p : s == s_p}
+// (tt_diag_rank_rows).  Every score comes from one instruction sequence whichever wave or split computes it, and the selection
+// is exact under a total order, so results are bitwise identical across runs and split counts.
+#include "tt_score_bf16.h"
+
+#include <math.h>
+
+namespace {
+
+using namespace ttscore;
+
+constexpr int kRetWaves = 2;        // waves per sweep workgroup (each its own 32 queries; kept at <= 64 KB of LDS for k = 64)
+constexpr int kRetCap = 64;         // candidate slots per query beyond the k kept ones (>= 32: room for one whole tile)
+constexpr int kRetMaxSplits = 32;
+constexpr int32_t kSentIdx = 0x7fffffff;   // index of an empty list entry (order key 0: below every score)
+
+// order-preserving key of a score: larger float <=> larger key; -0 and +0 share one key
+__device__ __forceinline__ uint32_t okey(float x) {
+  const uint32_t u = __float_as_uint(x + 0.f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float okey_val(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// largest float below x (x >= s_p  <=>  x > below(s_p) for the rank's "tie before the positive" rows)
+__device__ __forceinline__ float below(float x) {
+  if (x != x || x == -INFINITY) return x;
+  if (x == 0.f) return -__uint_as_float(1u);
+  const uint32_t u = __float_as_uint(x);
+  return __uint_as_float(x > 0.f ? u - 1 : u + 1);
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ---- score tiles: acc[r] = s(query 32 qt + c, catalogue row 32 t + rowmap(r, h)) ----------------------------------------------
+template <int KS>
+struct TileBf16 {             // packed images (tt_score_pack_bf16): s = <Q, C> times the scales the images carry
+  const __bf16* q_rows;
+  const __bf16* c_rows;
+  bf16x8 qf[KS];
+  struct Frag { bf16x8 v[KS]; };
+  __device__ __forceinline__ void load_queries(int64_t qt, int c, int h, int64_t) { load_bfrag<KS>(q_rows, qt, c, h, qf); }
+  __device__ __forceinline__ void load(int64_t t, int c, int h, Frag& f) const { load_bfrag<KS>(c_rows, t, c, h, f.v); }
+  __device__ __forceinline__ void score(const Frag& f, int64_t, int, int, f32x16& acc) const {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.v[s], qf[s], acc, 0, 0, 0);
+  }
+};
+
+template <bool VEC>
+struct TileF32 {              // plain f32 rows: s = inv_t * (f32 FMA chain over k = 0 .. D-1)
+  const float* Q;
+  const float* Cm;
+  int64_t nQ, nC;
+  int D;
+  float inv_t;
+  const float* qrow;
+  struct Frag {};
+  __device__ __forceinline__ void load_queries(int64_t qt, int c, int, int64_t) {
+    const int64_t q = 32 * qt + c;
+    qrow = Q + (q < nQ ? q : nQ - 1) * D;
+  }
+  __device__ __forceinline__ void load(int64_t, int, int, Frag&) const {}
+  __device__ __forceinline__ void score(const Frag&, int64_t t, int, int h, f32x16& acc) const {
+    const float* rp[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t row = 32 * t + rowmap(r, h);
+      rp[r] = Cm + (row < nC ? row : nC - 1) * D;
+      acc[r] = 0.f;
+    }
+    if (VEC) {
+      for (int k = 0; k < D; k += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(qrow + k);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float4 v = *reinterpret_cast<const float4*>(rp[r] + k);
+          acc[r] = fmaf(q.w, v.w, fmaf(q.z, v.z, fmaf(q.y, v.y, fmaf(q.x, v.x, acc[r]))));
+        }
+      }
+    } else {
+      for (int k = 0; k < D; ++k) {
+        const float q = qrow[k];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = fmaf(q, rp[r][k], acc[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] *= inv_t;
+  }
+};
+
+struct RetArgs {
+  int64_t nQ, nC;
+  int k, S;
+  const int32_t* pos32;       // positives (one of the two, or both NULL)
+  const int64_t* pos64;
+  float* sp;                  // [nQ] positive scores (NaN: positive out of range)
+  int32_t* part_rank;         // [nQ][S] or NULL
+  uint32_t* part_key;         // [nQ][S][k] order keys (0 = empty)
+  int32_t* part_idx;          // [nQ][S][k]
+  float* vals;                // [nQ][k] out
+  int64_t* idx;               // [nQ][k] out
+  int32_t* rank;              // [nQ] out or NULL
+};
+
+__device__ __forceinline__ int64_t positive_of(const RetArgs& a, int64_t q) { return a.pos64 ? a.pos64[q] : (int64_t)a.pos32[q]; }
+
+// ---- pos: s_p per query ---------------------------------------------------------------------------------------------------------
+template <class Tile>
+__global__ __launch_bounds__(64) void retrieve_pos_kernel(Tile tile, RetArgs a) {
+  const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
+  const int64_t qt = blockIdx.x, q0 = 32 * qt;
+  tile.load_queries(qt, c, h, a.nQ);
+  for (int i = 0; i < 32 && q0 + i < a.nQ; ++i) {
+    const int64_t p = positive_of(a, q0 + i);                 // wave-uniform
+    if (p < 0 || p >= a.nC) {
+      if (lane == 0) a.sp[q0 + i] = __uint_as_float(0x7fc00000u);
+      continue;
+    }
+    typename Tile::Frag f;
+    f32x16 acc;
+    tile.load(p / 32, c, h, f);
+    tile.score(f, p / 32, c, h, acc);
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (rowmap(r, h) == (int)(p & 31)) v = acc[r];
+    if (c == i && h == (int)((p >> 2) & 1)) a.sp[q0 + i] = v;
+  }
+}
+
+// ---- sweep ------------------------------------------------------------------------------------------------------------------
+template <class Tile>
+__global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
+  extern __shared__ uint32_t ret_lds[];
+  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+  const int wave = threadIdx.x >> 6;
+  const int64_t qt = (int64_t)blockIdx.x * kRetWaves + wave, q0 = 32 * qt;
+  if (q0 >= a.nQ) return;                                       // (no workgroup barriers below: the waves are independent)
+  const int s = blockIdx.y, S = a.S, k = a.k;
+  const int64_t nT = (a.nC + 31) / 32, tb = nT * s / S, te = nT * (s + 1) / S;
+  const int slots = k + kRetCap;
+  uint32_t* keys = ret_lds + (size_t)wave * slots * 64;         // [slot][query c]
+  int32_t* ids = reinterpret_cast<int32_t*>(keys + slots * 32);
+  const int64_t q = q0 + c;
+  const bool qok = q < a.nQ;
+  tile.load_queries(qt, c, h, a.nQ);
+
+  const bool want_rank = a.part_rank != nullptr, want_topk = k > 0;
+  int64_t p = -1, tp = -1;
+  float sp = 0.f, sp_lo = 0.f;
+  if (want_rank && qok) {
+    p = positive_of(a, q);
+    sp = a.sp[q];
+    tp = p >= 0 ? p / 32 : -1;
+    sp_lo = below(sp);
+  }
+  int rcnt = 0;
+  float thr = -INFINITY;                                        // the query's k-th best so far (both lanes of a query agree)
+  int cnt = 0;                                                  // filled slots of the query's region
+
+  // the k best of slots [0, cnt) of every query whose region holds more than k; region [0, k) afterwards
+  auto select = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const bool act = cnt > k;
+    const int n = act ? cnt : 0;
+    uint32_t K = 0;                                             // k-th largest key
+    for (int b = 31; b >= 0; --b) {
+      const uint32_t tr = K | (1u << b);
+      int ge = 0;
+      for (int i = h; i < n; i += 2) ge += keys[i * 32 + c] >= tr ? 1 : 0;
+      ge += __shfl_xor(ge, 32);
+      if (ge >= k) K = tr;
+    }
+    int gt = 0, eq = 0;
+    for (int i = h; i < n; i += 2) {
+      const uint32_t x = keys[i * 32 + c];
+      gt += x > K ? 1 : 0;
+      eq += x == K ? 1 : 0;
+    }
+    gt += __shfl_xor(gt, 32);
+    eq += __shfl_xor(eq, 32);
+    const int need = k - gt;                                    // >= 1
+    const bool tie = act && eq > need;
+    int32_t I = kSentIdx;                                       // the need-th smallest index among key == K
+    if (__any(tie)) {
+      int32_t J = 0;
+      for (int b = 30; b >= 0; --b) {
+        const int32_t cand = J | (1 << b);
+        int lt = 0;
+        if (tie)
+          for (int i = h; i < n; i += 2) lt += (keys[i * 32 + c] == K && ids[i * 32 + c] < cand) ? 1 : 0;
+        lt += __shfl_xor(lt, 32);
+        if (lt < need) J = cand;
+      }
+      if (tie) I = J;
+    }
+    if (act && h == 0) {                                        // in-place compaction, 8 slots read ahead of the writes
+      int w = 0;
+      for (int i0 = 0; i0 < n; i0 += 8) {
+        uint32_t kk[8];
+        int32_t ii[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          kk[j] = i0 + j < n ? keys[(i0 + j) * 32 + c] : 0u;
+          ii[j] = i0 + j < n ? ids[(i0 + j) * 32 + c] : kSentIdx;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (i0 + j < n && (kk[j] > K || (kk[j] == K && ii[j] <= I))) {
+            keys[w * 32 + c] = kk[j];
+            ids[w * 32 + c] = ii[j];
+            ++w;
+          }
+      }
+    }
+    if (act) {
+      cnt = k;
+      thr = okey_val(K);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+
+  typename Tile::Frag f;
+  tile.load(tb, c, h, f);
+  for (int64_t t = tb; t < te; ++t) {
+    f32x16 acc;
+    tile.score(f, t, c, h, acc);
+    if (t + 1 < te) tile.load(t + 1, c, h, f);                 // next tile's operands fly while this one is filtered
+    const int64_t r0 = 32 * t;
+    if (r0 + 32 > a.nC) {                                       // ragged last tile: rows past the catalogue never count
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (r0 + rowmap(r, h) >= a.nC) acc[r] = -INFINITY;
+    }
+    if (want_rank) {
+      if (!__any(t == tp)) {                                    // whole tile before (ties count) or after (they do not) p
+        const float th = t < tp ? sp_lo : sp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rcnt += acc[r] > th ? 1 : 0;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int64_t row = r0 + rowmap(r, h);
+          rcnt += (acc[r] > sp || (acc[r] == sp && row < p)) ? 1 : 0;
+        }
+      }
+    }
+    if (want_topk) {
+      float m = max3_asm(acc[0], acc[1], acc[2]);
+#pragma unroll
+      for (int r = 3; r < 15; r += 2) m = max3_asm(m, acc[r], acc[r + 1]);
+      m = fmaxf(m, acc[15]);
+      if (__any(m > thr)) {
+        int mine = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mine += acc[r] > thr ? 1 : 0;
+        const int other = __shfl_xor(mine, 32);
+        int w = cnt + (h ? other : 0);                          // half 0's candidates first, then half 1's
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (acc[r] > thr) {
+            keys[w * 32 + c] = okey(acc[r]);
+            ids[w * 32 + c] = (int32_t)(r0 + rowmap(r, h));
+            ++w;
+          }
+        cnt += mine + other;
+        if (__any(cnt > k + kRetCap - 32)) select();
+      }
+    }
+  }
+  if (want_topk) {
+    if (__any(cnt > k)) select();
+    if (qok) {
+      uint32_t* pk = a.part_key + (q * S + s) * k;
+      int32_t* pi = a.part_idx + (q * S + s) * k;
+      for (int i = h; i < k; i += 2) {
+        pk[i] = i < cnt ? keys[i * 32 + c] : 0u;
+        pi[i] = i < cnt ? ids[i * 32 + c] : kSentIdx;
+      }
+    }
+  }
+  if (want_rank) {
+    rcnt += __shfl_xor(rcnt, 32);
+    if (qok && h == 0) a.part_rank[q * S + s] = rcnt;
+  }
+}
+
+// ---- merge: one wave per query ------------------------------------------------------------------------------------------------
+template <int PER>
+__global__ __launch_bounds__(64) void retrieve_merge_kernel(RetArgs a) {
+  const int lane = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const int S = a.S, k = a.k;
+  if (a.rank && lane == 0) {
+    const int64_t p = positive_of(a, q);
+    int r = 0;
+    for (int s = 0; s < S; ++s) r += a.part_rank[q * S + s];
+    a.rank[q] = (p >= 0 && p < a.nC) ? r : -1;
+  }
+  if (k == 0) return;
+  const int n = S * k;
+  const uint32_t* pk = a.part_key + q * n;
+  const int32_t* pi = a.part_idx + q * n;
+  uint32_t kk[PER];
+  int32_t ii[PER];
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int i = lane + 64 * j;
+    kk[j] = i < n ? pk[i] : 0u;
+    ii[j] = i < n ? pi[i] : kSentIdx;
+    if (kk[j] == 0u) ii[j] = kSentIdx - i;                      // empty entries: distinct, after every real index
+  }
+  uint32_t K = 0;
+  for (int b = 31; b >= 0; --b) {
+    const uint32_t tr = K | (1u << b);
+    int ge = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) ge += kk[j] >= tr ? 1 : 0;
+    if (wave_sum(ge) >= k) K = tr;
+  }
+  int gt = 0, eq = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    gt += kk[j] > K ? 1 : 0;
+    eq += kk[j] == K ? 1 : 0;
+  }
+  gt = wave_sum(gt);
+  eq = wave_sum(eq);
+  const int need = k - gt;
+  int32_t I = kSentIdx;
+  if (eq > need) {                                              // wave-uniform
+    int32_t J = 0;
+    for (int b = 30; b >= 0; --b) {
+      const int32_t cand = J | (1 << b);
+      int lt = 0;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) lt += (kk[j] == K && ii[j] < cand) ? 1 : 0;
+      if (wave_sum(lt) < need) J = cand;
+    }
+    I = J;
+  }
+  __shared__ uint32_t sk[64];
+  __shared__ int32_t si[64];
+  int base = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const bool sel = kk[j] > K || (kk[j] == K && ii[j] <= I);
+    const uint64_t m = __ballot(sel);
+    const int at = base + __popcll(m & ((1ull << lane) - 1));
+    if (sel && at < 64) {                                       // (exactly k <= 64 are selected)
+      sk[at] = kk[j];
+      si[at] = ii[j];
+    }
+    base += __popcll(m);
+  }
+  __syncthreads();
+  if (lane < k) {
+    const uint32_t mk = sk[lane];
+    const int32_t mi = si[lane];
+    int pos = 0;
+    for (int j = 0; j < k; ++j) pos += (sk[j] > mk || (sk[j] == mk && si[j] < mi)) ? 1 : 0;
+    const bool empty = mk == 0u;
+    a.vals[q * k + pos] = empty ? -INFINITY : okey_val(mk);
+    a.idx[q * k + pos] = empty ? -1 : (int64_t)mi;
+  }
+}
+
+int ret_max_splits(int64_t nC) {
+  const int64_t nT = (nC + 31) / 32;
+  return (int)(nT < kRetMaxSplits ? nT : kRetMaxSplits);
+}
+
+struct RetLayout {
+  size_t sp, rank, key, idx, total;
+};
+RetLayout ret_layout(int64_t nQ, int64_t nC, int k) {
+  const int64_t S = ret_max_splits(nC);
+  RetLayout L;
+  L.sp = 0;
+  L.rank = L.sp + (size_t)rup(nQ * 4, 256);
+  L.key = L.rank + (size_t)rup(nQ * S * 4, 256);
+  L.idx = L.key + (size_t)rup(nQ * S * k * 4, 256);
+  L.total = L.idx + (size_t)rup(nQ * S * k * 4, 256);
+  return L;
+}
+
+bool ret_shape_ok(int64_t nQ, int64_t nC, int D, int k) {
+  return nQ >= 1 && nC >= 1 && nC < (int64_t(1) << 31) && D >= 1 && D <= 256 && k >= 0 && k <= 64 && k <= nC;
+}
+
+template <class Tile>
+int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k, const void* positives,
+               int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace, hipStream_t st) {
+  const int64_t nT = tt_cdiv(nC, 32), nQt = tt_cdiv(nQ, 32);
+  const int cap = ret_max_splits(nC);
+  int64_t S;
+  if (ctx->retrieve_splits > 0) {
+    S = ctx->retrieve_splits;
+  } else {                                                      // ~8 waves per CU, at least 16 tiles per split
+    S = tt_cdiv(8 * (int64_t)ctx->num_cus, nQt);
+    const int64_t lim = nT / 16 > 1 ? nT / 16 : 1;
+    S = S < lim ? S : lim;
+  }
+  S = S < cap ? S : cap;
+  S = S > 1 ? S : 1;
+  const RetLayout lay = ret_layout(nQ, nC, k);
+  char* ws = reinterpret_cast<char*>(workspace);
+  RetArgs a{};
+  a.nQ = nQ;
+  a.nC = nC;
+  a.k = k;
+  a.S = (int)S;
+  a.pos32 = positives && !positives_i64 ? reinterpret_cast<const int32_t*>(positives) : nullptr;
+  a.pos64 = positives && positives_i64 ? reinterpret_cast<const int64_t*>(positives) : nullptr;
+  a.sp = reinterpret_cast<float*>(ws + lay.sp);
+  a.part_rank = positives ? reinterpret_cast<int32_t*>(ws + lay.rank) : nullptr;
+  a.part_key = reinterpret_cast<uint32_t*>(ws + lay.key);
+  a.part_idx = reinterpret_cast<int32_t*>(ws + lay.idx);
+  a.vals = vals;
+  a.idx = idx;
+  a.rank = positives ? rank : nullptr;
+  if (positives) {
+    retrieve_pos_kernel<Tile><<<(unsigned)nQt, 64, 0, st>>>(tile, a);
+    TT_LAUNCH_CHECK();
+  }
+  const size_t lds = (size_t)kRetWaves * (k + kRetCap) * 32 * 8;
+  retrieve_sweep_kernel<Tile><<<dim3((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S), kRetWaves * 64, lds, st>>>(tile, a);
+  TT_LAUNCH_CHECK();
+  const int64_t n = S * k;
+  if (n <= 128) retrieve_merge_kernel<2><<<(unsigned)nQ, 64, 0, st>>>(a);
+  else if (n <= 512) retrieve_merge_kernel<8><<<(unsigned)nQ, 64, 0, st>>>(a);
+  else retrieve_merge_kernel<kRetMaxSplits><<<(unsigned)nQ, 64, 0, st>>>(a);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+#define TT_RET_CHECK_COMMON(NAME)                                                                                                 \
+  TT_CHECK_ARG(ctx != nullptr, NAME ": NULL context");                                                                           \
+  TT_CHECK_ARG(ret_shape_ok(nQ, nC, D, k), NAME ": bad shape nQ=%lld nC=%lld D=%d k=%d (need nQ >= 1, 1 <= nC < 2^31, "         \
+               "1 <= D <= 256, 0 <= k <= min(64, nC))", (long long)nQ, (long long)nC, D, k);                                     \
+  TT_CHECK_ARG(k > 0 || positives != nullptr, NAME ": k = 0 asks for nothing (pass positives and rank, or k >= 1)");             \
+  TT_CHECK_ARG(k == 0 || (vals != nullptr && idx != nullptr), NAME ": k = %d needs vals and idx", k);                           \
+  TT_CHECK_ARG((positives == nullptr) == (rank == nullptr), NAME ": positives and rank go together (both or neither)");          \
+  TT_CHECK_ARG(workspace != nullptr && tt_aligned(workspace, 16), NAME ": workspace NULL or not 16-byte aligned");            \
+  TT_CHECK_ARG(workspace_bytes >= ret_layout(nQ, nC, k).total, NAME ": workspace of %zu bytes < %zu (tt_retrieve_workspace_bytes)", \
+               workspace_bytes, ret_layout(nQ, nC, k).total)
+
+}  // namespace
+
+extern "C" {
+
+size_t tt_retrieve_workspace_bytes(int64_t nQ, int64_t nC, int32_t D, int32_t k) {
+  if (!ret_shape_ok(nQ, nC, D, k)) return 0;
+  return ret_layout(nQ, nC, k).total;
+}
+
+int tt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D, int32_t k,
+                          const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
+                          size_t workspace_bytes, tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_retrieve_topk_bf16");
+  TT_CHECK_ARG(Q_packed && C_packed && tt_aligned(Q_packed, 16) && tt_aligned(C_packed, 16),
+               "tt_retrieve_topk_bf16: packed images NULL or not 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Dp = padded_d(D);
+#define TT_RET_BF16(KS)                                                                                                 \
+  do {                                                                                                                  \
+    TileBf16<KS> tile{};                                                                                                \
+    tile.q_rows = view(Q_packed, nQ, D).rows;                                                                           \
+    tile.c_rows = view(C_packed, nC, D).rows;                                                                           \
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st); \
+  } while (0)
+  if (Dp == 32) TT_RET_BF16(2);
+  if (Dp == 64) TT_RET_BF16(4);
+  if (Dp == 128) TT_RET_BF16(8);
+  TT_RET_BF16(16);
+#undef TT_RET_BF16
+}
+
+int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
+                         const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
+                         size_t workspace_bytes, tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_retrieve_topk_f32");
+  TT_CHECK_ARG(Q && Cm, "tt_retrieve_topk_f32: NULL embeddings");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (D % 4 == 0 && tt_aligned(Q, 16) && tt_aligned(Cm, 16)) {
+    TileF32<true> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st);
+  }
+  TileF32<false> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
+  return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st);
+}
+
+}  // extern "C"

@@ -95,6 +95,52 @@ class TwoTowerEvaluator:
             self.print_comprehensive_results(out)
         return out
 
+    @torch.no_grad()
+    def evaluate_catalog(self, model, notice_store, index, pairs, ks=(5, 10), batch_size: int = 8192) -> Dict[str, float]:
+        """Recall@k and MRR against the WHOLE catalogue instead of the other B - 1 companies of a batch.  `pairs` [P, 2] holds
+        (notice entity, company entity) rows; `index` is a retrieval.CatalogIndex whose row i is company entity i
+        (CatalogIndex.from_store).  Each pair's notice goes through the notice tower (eval mode, batch_size rows at a time)
+        and its company is the positive; its rank among all nC catalogue rows is #{c : s > s_p} + #{c < p : s == s_p}.  As in
+        the in-batch metric, a notice's OTHER positive companies count as negatives.  Returns recall@k for every k in ks, mrr,
+        catalog_size and num_queries.  The model's train()/eval() state is restored afterwards."""
+        from .retrieval import CatalogIndex
+        if not isinstance(index, CatalogIndex):
+            raise TypeError("index must be a CatalogIndex")
+        ks = tuple(int(k) for k in ks)
+        if not ks or min(ks) < 1:
+            raise ValueError(f"every k of ks must be >= 1, got {ks}")
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        tower_model = model.two_tower_model if hasattr(model, "two_tower_model") else model
+        D = getattr(tower_model, "final_embedding_dim", None)
+        if D is not None and int(D) != index.dim:
+            raise ValueError(f"catalogue dimension {index.dim} != the towers' {D}")
+        pairs = torch.as_tensor(pairs)
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+            raise ValueError("pairs must be a non-empty [P, 2] array of (notice, company) entity rows")
+        pairs = pairs.to(torch.int64)
+        lo, hi = int(pairs[:, 1].min()), int(pairs[:, 1].max())
+        if lo < 0 or hi >= index.size:
+            raise ValueError(f"pair company rows must be in [0, {index.size}), got [{lo}, {hi}]")
+        pairs = pairs.to(index.device)
+        modes = [(m, m.training) for m in model.modules()]
+        model.eval()
+        try:
+            ranks = []
+            for s in range(0, pairs.shape[0], batch_size):
+                p = pairs[s:s + batch_size]
+                q = tower_model.get_notice_embeddings(notice_store.gather(p[:, 0].contiguous()))
+                ranks.append(index.rank(q, p[:, 1].contiguous()))
+            r = torch.cat(ranks) if len(ranks) > 1 else ranks[0]
+        finally:
+            for m, was in modes:
+                m.training = was
+        out = {f"recall@{k}": (r < k).float().mean().item() for k in ks}
+        out["mrr"] = (1.0 / (r.float() + 1.0)).mean().item()
+        out["catalog_size"] = index.size
+        out["num_queries"] = int(r.numel())
+        return out
+
     def _fast_eval(self, model, dataloader):
         """A GraphedEvalStep for (model, loader batch size) when the loader is a device-resident DevicePairLoader with at least one
         full batch and the model is this package's task on a GPU; cached on the evaluator.  None: the batch-by-batch loop."""

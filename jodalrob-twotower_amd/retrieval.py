@@ -1,0 +1,154 @@
+"""CatalogIndex -- catalogue-wide retrieval with the trained towers.
+
+The training step ranks a notice against the companies of its own batch.  A user of the model searches the whole company
+catalogue: the catalogue is embedded once (company tower, eval mode) and packed once, and every search streams it past the
+queries in one fused score + select sweep (tt_retrieve_topk_bf16 / tt_retrieve_topk_f32) that never writes the nQ x nC score
+matrix to memory.
+
+    index = CatalogIndex.from_store(model, company_store)         # row i of the index = entity i of the store
+    vals, idx = index.search(notice_embeddings, k=10)             # s = <q, c> / T, value descending, ties -> lower index
+    ranks = index.rank(notice_embeddings, positives)              # #{c : s > s_p} + #{c < p : s == s_p}
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import ops
+from .config import settings
+
+MAX_K = 64
+
+
+class CatalogIndex:
+    """A packed catalogue of nC rows of dimension D.  score_dtype 'bf16' keeps the tt_score_pack_bf16 image of C / T (queries
+    are packed unscaled, so the score is <bf16(q), bf16(c / T)> in f32); 'fp32' keeps C as it is and scores with an f32 FMA
+    chain times 1 / T.  'fp8' (a training-time mode) falls back to bf16 here: the index has no fp8 images."""
+
+    def __init__(self, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None):
+        if not torch.is_tensor(C) or C.dim() != 2 or C.shape[0] < 1 or not 1 <= C.shape[1] <= 256:
+            raise ValueError("the catalogue must be a [nC >= 1, 1 <= D <= 256] tensor")
+        if C.shape[0] >= 2 ** 31:
+            raise ValueError("the catalogue holds at most 2^31 - 1 rows")
+        score_dtype = score_dtype or settings.score_dtype
+        if score_dtype not in ("fp32", "bf16", "fp8"):
+            raise ValueError(f"score_dtype must be 'fp32', 'bf16' or 'fp8', got {score_dtype!r}")
+        if float(temperature) <= 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        self.score_dtype = "fp32" if score_dtype == "fp32" else "bf16"
+        self.temperature = float(temperature)
+        self.inv_t = 1.0 / self.temperature
+        self.device = C.device
+        self.size, self.dim = int(C.shape[0]), int(C.shape[1])
+        C = C.detach().to(torch.float32).contiguous()
+        if self.score_dtype == "bf16":
+            self.data = ops.score_pack_bf16(C, self.inv_t)
+        else:
+            self.data = C
+        self._ws = {}
+
+    @classmethod
+    def from_embeddings(cls, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None) -> "CatalogIndex":
+        """Index of ready embeddings C [nC, D] (the towers' outputs are L2-normalised; nothing is normalised here).
+        score_dtype: 'fp32' | 'bf16' | 'fp8' (-> bf16); default: the package's score_dtype setting (TT_SCORE_DTYPE)."""
+        return cls(C, temperature, score_dtype)
+
+    @classmethod
+    @torch.no_grad()
+    def from_store(cls, model, company_store, chunk: int = 8192, score_dtype: Optional[str] = None) -> "CatalogIndex":
+        """Embeds every entity of a DeviceFeatureStore through the company tower, `chunk` rows at a time, in eval mode (running
+        BatchNorm statistics, no dropout), and indexes the result: row i of the index is entity i of the store.  `model` is a
+        TwoTowerTrainTask (its temperature and score_dtype are used) or a TwoTowerModel (temperature 1).  The model's
+        train()/eval() state is restored afterwards."""
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        task = model if hasattr(model, "two_tower_model") else None
+        tower_model = task.two_tower_model if task is not None else model
+        temperature = float(task.temperature) if task is not None else 1.0
+        if score_dtype is None and task is not None:
+            score_dtype = task.score_dtype
+        n = len(company_store)
+        if n < 1:
+            raise ValueError("the company store is empty")
+        modes = [(m, m.training) for m in model.modules()]
+        model.eval()
+        try:
+            dev = company_store.device
+            parts = []
+            for s in range(0, n, chunk):
+                ent = torch.arange(s, min(s + chunk, n), dtype=torch.int64, device=dev)
+                emb = tower_model.get_company_embeddings(company_store.gather(ent))
+                parts.append(emb.detach().float())
+            C = torch.cat(parts, 0) if len(parts) > 1 else parts[0]
+        finally:
+            for m, was in modes:
+                m.training = was
+        return cls(C, temperature, score_dtype)
+
+    # ---- queries ------------------------------------------------------------------------------------------------------
+    def _check_queries(self, Q: torch.Tensor) -> torch.Tensor:
+        if not torch.is_tensor(Q) or Q.dim() != 2 or Q.shape[0] < 1:
+            raise ValueError("queries must be a [nQ >= 1, D] tensor")
+        if Q.shape[1] != self.dim:
+            raise ValueError(f"query dimension {Q.shape[1]} != catalogue dimension {self.dim}")
+        if Q.device != self.device:
+            raise ValueError(f"queries on {Q.device}, catalogue on {self.device}")
+        return Q.detach().to(torch.float32).contiguous()
+
+    def _check_k(self, k: int) -> int:
+        k = int(k)
+        if not 1 <= k <= min(MAX_K, self.size):
+            raise ValueError(f"k must be in [1, min({MAX_K}, catalogue size {self.size})], got {k}")
+        return k
+
+    def _check_positives(self, positives, nQ: int) -> torch.Tensor:
+        if not torch.is_tensor(positives) or positives.shape != (nQ,):
+            raise ValueError(f"positives must be a tensor of shape ({nQ},)")
+        if positives.dtype not in (torch.int32, torch.int64):
+            positives = positives.to(torch.int64)
+        return positives.to(self.device).contiguous()
+
+    def _workspace(self, nQ: int, k: int) -> torch.Tensor:
+        need = ops.retrieve_workspace_bytes(nQ, self.size, self.dim, k)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            self._ws[key] = ws
+        return ws
+
+    def _call(self, Q: torch.Tensor, k: int, positives):
+        nQ = Q.shape[0]
+        ws = self._workspace(nQ, k)
+        if self.score_dtype == "bf16":
+            q = ops.score_pack_bf16(Q, 1.0)
+            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws)
+        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws)
+
+    def search(self, Q: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(vals f32 [nQ, k], idx int64 [nQ, k]): every query's k best catalogue rows, value descending, ties to the lower
+        index.  1 <= k <= min(64, catalogue size)."""
+        k = self._check_k(k)
+        Q = self._check_queries(Q)
+        vals, idx, _ = self._call(Q, k, None)
+        return vals, idx
+
+    def search_with_rank(self, Q: torch.Tensor, k: int, positives) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """search() and rank() from one sweep over the catalogue."""
+        k = self._check_k(k)
+        Q = self._check_queries(Q)
+        return self._call(Q, k, self._check_positives(positives, Q.shape[0]))
+
+    def rank(self, Q: torch.Tensor, positives) -> torch.Tensor:
+        """int32 [nQ]: 0-based rank of catalogue row positives[i] for query i among ALL catalogue rows,
+        #{c : s > s_p} + #{c < p : s == s_p} (tt_diag_rank_rows's rule); -1 where the positive is outside [0, nC)."""
+        Q = self._check_queries(Q)
+        return self._call(Q, 0, self._check_positives(positives, Q.shape[0]))[2]
+
+    def __len__(self) -> int:
+        return self.size
+
+    def __repr__(self) -> str:
+        return f"CatalogIndex(size={self.size}, dim={self.dim}, score_dtype={self.score_dtype!r}, temperature={self.temperature})"
+

@@ -268,6 +268,30 @@ class TwoTowerTrainTask(nn.Module):
             vals, idx = ops.topk_rows(sim, top_k)
             return {"top_similarities": vals, "top_indices": idx, "all_similarities": sim}
 
+    @_no_dynamo
+    def predict_catalog(self, notice_batch, index, top_k: int = 10) -> Dict[str, torch.Tensor]:
+        """Top-k companies of the whole catalogue `index` (a retrieval.CatalogIndex) for every notice of `notice_batch` (the
+        notice side's {"dense", "kjt"}, or a full batch with a "notice" entry): {"top_similarities" f32 [B, top_k],
+        "top_indices" int64 [B, top_k]} -- index rows, value descending, ties to the lower index.  The notice tower runs in
+        eval mode; the task's train()/eval() state is restored afterwards.  (predict_batch ranks within one batch.)"""
+        from .retrieval import CatalogIndex
+        if not isinstance(index, CatalogIndex):
+            raise TypeError("index must be a CatalogIndex")
+        index._check_k(top_k)
+        if index.dim != self.two_tower_model.final_embedding_dim:
+            raise ValueError(f"catalogue dimension {index.dim} != the towers' {self.two_tower_model.final_embedding_dim}")
+        notice = notice_batch["notice"] if "notice" in notice_batch else notice_batch
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            with torch.no_grad():
+                q = self.two_tower_model.get_notice_embeddings(notice)
+                vals, idx = index.search(q, top_k)
+        finally:
+            for m, was in modes:
+                m.training = was
+        return {"top_similarities": vals, "top_indices": idx}
+
     def diagonal_ranks(self, batch):
         """0-based rank of each positive in its row (count of strictly larger scores, ties before the
         diagonal counted) -- the quantity Recall@K / MRR need, without the B x B matrix."""

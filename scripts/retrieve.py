@@ -1,0 +1,112 @@
+"""Catalogue-wide retrieval with a trained two-tower model: embeds every company of the company store once (CatalogIndex), then
+reports Recall@5/10 and MRR of the test pairs against the WHOLE catalogue and prints a few notices' top-k companies.
+
+    python scripts/retrieve.py [--checkpoint output/models/final_model.pt] [--final-dim 64] [--hidden 128,64]
+                               [--entities 10000] [--pairs 100000] [--score-dtype fp32|bf16] [--top-k 10]
+
+The data are the synthetic feature / pair source scripts/train.py uses (same arguments give the same stores, so a checkpoint
+written by `scripts/train.py --entities N --pairs P` is evaluated on its own test split).  Without --checkpoint the task is
+trained for --train-steps steps first, so that the figures mean something.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "jodalrob-twotower_amd" / "dropin"))
+
+from src.torchrec_preprocess.schema import build_torchrec_schema_from_meta    # noqa: E402
+from src.towers.pairs.unified_bid_data_loader import create_unified_bid_dataloaders  # noqa: E402
+from src.towers.two_tower_train_task import create_two_tower_train_task       # noqa: E402
+from jodalrob_twotower_amd import synthetic                                   # noqa: E402
+from jodalrob_twotower_amd.evaluator import TwoTowerEvaluator                 # noqa: E402
+from jodalrob_twotower_amd.retrieval import CatalogIndex                      # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--checkpoint", default=None, help="a scripts/train.py checkpoint (model_state_dict) or model_weights.pt")
+    ap.add_argument("--entities", type=int, default=10_000)
+    ap.add_argument("--pairs", type=int, default=100_000)
+    ap.add_argument("--batch-size", type=int, default=256)
+    ap.add_argument("--hidden", default="128,64")
+    ap.add_argument("--final-dim", type=int, default=64)
+    ap.add_argument("--score-dtype", default=None, help="fp32 | bf16 (default: the package setting, TT_SCORE_DTYPE)")
+    ap.add_argument("--train-steps", type=int, default=200, help="without --checkpoint: train this many steps first")
+    ap.add_argument("--top-k", type=int, default=10)
+    ap.add_argument("--examples", type=int, default=3)
+    a = ap.parse_args()
+
+    device = torch.device("cuda:0")
+    real = synthetic.load_real_schema(ROOT / "jodalrob-twotower_amd" / "schema_real.json")
+    meta_rows = [synthetic.META_HEADER]
+    for side in ("notice", "company"):
+        for c in real[side]["pk_cols"]:
+            meta_rows.append(f"{side},{c},text,Y,,,,0,,Y,Y,,")
+        for c in real[side]["numeric"]:
+            meta_rows.append(f"{side},{c},numeric,Y,,,,0,,,,,")
+        for c, v in zip(real[side]["categorical"], real[side]["vocab_sizes"]):
+            meta_rows.append(f"{side},{c},text,Y,,Y,{v - 10},0,,,,,")
+        for c in real[side]["text"]:
+            meta_rows.append(f"{side},{c},text,Y,,N,,0,,,,,")
+    meta = Path(tempfile.mkdtemp(prefix="tt_retrieve_")) / "metadata.csv"
+    meta.write_text("\n".join(meta_rows) + "\n", encoding="utf-8")
+    schema = build_torchrec_schema_from_meta(notice_table="notice", company_table="company", pair_table="bid_two_tower",
+                                             pair_notice_id_cols=["bidntceno", "bidntceord"], pair_company_id_cols=["bizno"],
+                                             metadata_path=str(meta))
+    source = synthetic.SyntheticSource(a.entities, a.entities, a.pairs, real["notice"]["vocab_sizes"], real["company"]["vocab_sizes"])
+    train_loader, test_loader = create_unified_bid_dataloaders(source, schema, batch_size=a.batch_size, test_split=0.2,
+                                                               shuffle_seed=42, test_mode=True, pair_limit=a.pairs, device=device)
+    task = create_two_tower_train_task(schema.notice.categorical, schema.company.categorical, metadata_path=str(meta),
+                                       categorical_embedding_dim=32, notice_dense_input_dim=256, company_dense_input_dim=128,
+                                       tower_hidden_dims=[int(h) for h in a.hidden.split(",")], final_embedding_dim=a.final_dim,
+                                       dropout_rate=0.1, temperature=1.0, device=device, score_dtype=a.score_dtype)
+    if a.checkpoint:
+        ckpt = torch.load(a.checkpoint, map_location=device, weights_only=True)
+        task.load_state_dict(ckpt.get("model_state_dict", ckpt))
+        print(f"loaded {a.checkpoint}")
+    else:
+        opt = torch.optim.Adam(task.parameters(), lr=1e-3)
+        task.train()
+        steps = 0
+        while steps < a.train_steps:
+            for batch in train_loader:
+                opt.zero_grad()
+                task(batch).backward()
+                opt.step()
+                steps += 1
+                if steps >= a.train_steps:
+                    break
+        print(f"no checkpoint: trained {steps} steps on the synthetic pairs")
+
+    t0 = time.time()
+    index = CatalogIndex.from_store(task, test_loader.company)
+    torch.cuda.synchronize()
+    print(f"{index!r} built in {time.time() - t0:.2f} s")
+    pairs = test_loader.pairs
+    ev = TwoTowerEvaluator(device=device)
+    t0 = time.time()
+    m = ev.evaluate_catalog(task, test_loader.notice, index, pairs)
+    print(f"catalogue-wide metrics over {m['num_queries']} test pairs and {m['catalog_size']} companies "
+          f"({time.time() - t0:.2f} s):")
+    for key in ("recall@5", "recall@10", "mrr"):
+        print(f"  {key:10s} {m[key]:.4f}")
+    print(f"  random baseline: recall@5 {5 / m['catalog_size']:.5f}, recall@10 {10 / m['catalog_size']:.5f}")
+
+    ex = pairs[:a.examples]
+    pred = task.predict_catalog(test_loader.notice.gather(ex[:, 0].contiguous()), index, top_k=a.top_k)
+    for i in range(ex.shape[0]):
+        print(f"notice {int(ex[i, 0])} (positive company {int(ex[i, 1])}): top-{a.top_k} companies "
+              f"{pred['top_indices'][i].tolist()}")
+        print(f"    scores {[round(v, 4) for v in pred['top_similarities'][i].tolist()]}")
+
+
+if __name__ == "__main__":
+    main()

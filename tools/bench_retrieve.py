@@ -1,0 +1,113 @@
+"""Catalogue-wide top-k retrieval: the fused score + select kernels (tt_retrieve_topk_bf16 / _f32) against chunked
+torch.mm + torch.topk on the same inputs.
+
+    python tools/bench_retrieve.py [--nq 8192] [--nc 65536 1048576] [--d 64 256] [--k 10 64] [--dtypes bf16 fp32]
+                                   [--reps 3] [--out profiles/retrieve_bench.json]
+
+One JSON line per case: kernel ms per search and scores/s, the MFMA fraction of 2.5 PF dense bf16 (2 nQ nC D flops), the
+catalogue read rate (bytes of the catalogue operand per search) against 8 TB/s, and the baseline's ms and how many rows'
+index sets agree with the kernel's.  The baseline keeps at most 1 GiB of f32 scores alive per chunk (bf16: torch.mm of the two
+bf16 images, bf16 scores; fp32: f32 scores), takes the chunk's top-k and merges it into the running top-k.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+PEAK_BF16 = 2.5e15
+PEAK_HBM = 8.0e12
+
+
+def _time(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return min(ms), sum(ms) / len(ms)
+
+
+def baseline(Q, Cm, k, inv_t, bf16):
+    nQ, nC = Q.shape[0], Cm.shape[0]
+    chunk = max(k, min(nC, (1 << 28) // nQ))                   # <= 1 GiB of f32 scores
+    q = Q.to(torch.bfloat16) if bf16 else Q
+    best_v = best_i = None
+    for s in range(0, nC, chunk):
+        c = Cm[s:s + chunk]
+        S = (q @ (c * inv_t).to(torch.bfloat16).T).float() if bf16 else (q @ c.T) * inv_t
+        v, i = torch.topk(S, min(k, S.shape[1]), dim=1)
+        i = i + s
+        if best_v is None:
+            best_v, best_i = v, i
+        else:
+            v2, j = torch.topk(torch.cat([best_v, v], 1), k, dim=1)
+            best_i = torch.gather(torch.cat([best_i, i], 1), 1, j)
+            best_v = v2
+    return best_v, best_i
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nq", type=int, default=8192)
+    ap.add_argument("--nc", type=int, nargs="+", default=[65536, 1 << 20])
+    ap.add_argument("--d", type=int, nargs="+", default=[64, 256])
+    ap.add_argument("--k", type=int, nargs="+", default=[10, 64])
+    ap.add_argument("--dtypes", nargs="+", default=["bf16", "fp32"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    from jodalrob_twotower_amd.retrieval import CatalogIndex
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    rows = []
+    for nc in args.nc:
+        for d in args.d:
+            Q = torch.randn((args.nq, d), generator=g, device=dev)
+            Q /= Q.norm(dim=1, keepdim=True)
+            Cm = torch.randn((nc, d), generator=g, device=dev)
+            Cm /= Cm.norm(dim=1, keepdim=True)
+            for dt in args.dtypes:
+                index = CatalogIndex.from_embeddings(Cm, temperature=0.05, score_dtype=dt)
+                for k in args.k:
+                    best, mean = _time(lambda: index.search(Q, k), args.reps)
+                    vals, idx = index.search(Q, k)
+                    flops = 2.0 * args.nq * nc * d
+                    cat_bytes = nc * (2 * (32 if d <= 32 else 64 if d <= 64 else 128 if d <= 128 else 256) if dt == "bf16" else 4 * d)
+                    row = {"nq": args.nq, "nc": nc, "d": d, "k": k, "dtype": dt, "ms": round(best, 4), "ms_mean": round(mean, 4),
+                           "scores_per_s": args.nq * nc / (best * 1e-3),
+                           "mfma_frac_of_2.5PF": flops / (best * 1e-3) / PEAK_BF16,
+                           "catalog_read_frac_of_8TBs": cat_bytes / (best * 1e-3) / PEAK_HBM}
+                    if not args.no_baseline:
+                        bms, _ = _time(lambda: baseline(Q, Cm, k, index.inv_t, dt == "bf16"), max(1, args.reps - 1))
+                        bv, bi = baseline(Q, Cm, k, index.inv_t, dt == "bf16")
+                        same = (torch.sort(bi, 1).values == torch.sort(idx, 1).values).all(1)
+                        row.update({"torch_ms": round(bms, 4), "speedup_vs_torch": bms / best,
+                                    "index_sets_agree_frac": float(same.float().mean()),
+                                    "max_abs_val_diff": float((bv - vals).abs().max())})
+                        del bv, bi
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+                del index
+                torch.cuda.empty_cache()
+            del Q, Cm
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "rows": rows}, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
