@@ -608,12 +608,15 @@ def score_matrix(A, Bm, inv_t):
     return S
 
 
-def score_dense_fwd(n, c, inv_t: float, loss_type: int, label_smoothing: float):
-    """Dense loss path (tt_score_dense_fwd): returns (S [B, B], stats, out8, loss[1]) -- S and stats feed score_dense_bwd."""
+def score_dense_fwd(n, c, inv_t: float, loss_type: int, label_smoothing: float, hit=None):
+    """Dense loss path (tt_score_dense_fwd): returns (S [B, B], stats, out8, loss[1]) -- S and stats feed score_dense_bwd.
+    hit (optional int32 [2 B]): receives the per-row / per-column top-1 flags (first argmax == diagonal)."""
     dev, B, D = n.device, n.shape[0], n.shape[1]
     S = torch.empty((B, B), dtype=torch.float32, device=dev)
     stats = torch.empty(6 * B, dtype=torch.float32, device=dev)
-    hit = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    if hit is None:
+        hit = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.numel() >= 2 * B
     out8 = torch.empty(8, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     with _timed("tt_score_dense_fwd"):

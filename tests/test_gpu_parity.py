@@ -3,6 +3,8 @@
 
 Bars: ids / row indices / ranks / top-k indices bit-exact; looked-up rows bit-exact (f32 copy);
 fp32 results rtol 2e-5 (forward), 3e-4 (gradients: different summation order), stated per assert.
+The default f32 mode and the dense loss path at real shapes (B up to 8192) and at the kernels' branch edges are checked against
+the f64 oracle in tests/test_gpu_f32_parity.py.
 """
 import json
 
@@ -103,7 +105,8 @@ def test_task_matches_reference_golden(tt, manifest, case):
 def test_loss_variants_match_reference_golden(tt, case):
     """loss_type="cosine_embedding" and label_smoothing != 0 (two_tower_train_task.py:114-160) run on the dense loss path
     (tt_score_dense_fwd / _bwd: materialised score matrix, f32): loss, metrics and every gradient against the reference's
-    own vectors.  (Cosine gradients: see tests/test_oracle_golden.py::test_loss_variants_match_reference.)"""
+    own vectors.  (Cosine gradients: see tests/test_oracle_golden.py::test_loss_variants_match_reference.)  These fixtures are
+    small (B <= 24, D = 8); the same path at B up to 8192, stage by stage: tests/test_gpu_f32_parity.py."""
     import json
     cfg = json.loads((GOLD / "loss_variants.json").read_text())["cases"][case]
     g = load_case(case)
