@@ -540,6 +540,31 @@ int tt_score_fwd_sym_fp8(tt_ctx* ctx, const void* N_packed, const void* C_packed
                          size_t workspace_bytes, tt_stream stream);
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t,
                      float shift, const float* d_loss, float scale, tt_stream stream);
+/* bf16x3 (split-bf16) form of the score kernels: near-f32 products on the bf16 MFMA.  Each f32 operand x (after its scale) is
+ * written as hi + lo, hi = bf16(x), lo = bf16(x - hi) (round-to-nearest-even), and every product a b as
+ * hi_a hi_b + hi_a lo_b + lo_a hi_b: three v_mfma_f32_32x32x16_bf16 chains into one f32 accumulator, in the fixed order
+ * (hi_b lo_a, lo_b hi_a, hi_b hi_a).  Error per product term <= ~3 * 2^-16 |a b| (the dropped lo lo term and the two
+ * residuals) against 2 * 2^-11 for TF32 operands and 2 * 2^-8 for bf16.  Softmax, loss, temperature limit (2/T <= 80) and fixed
+ * shift as the bf16 calls.
+ * Layout: tt_score_pack2_bf16x3 writes [hi image | lo image], each tt_score_pack_bytes(R, D) bytes in tt_score_pack_bf16's
+ * layout (tt_score_pack_x3_bytes(R, D) = twice that, 16-byte aligned); the hi image is bit-identical to tt_score_pack2_bf16's,
+ * padding is zero in both; `scale` as there (applied before the split).
+ * tt_score_fwd_sym_bf16x3 = tt_score_fwd_sym_bf16 on such operands (same workspace); tt_score_fwd_bf16x3 = tt_score_fwd_bf16
+ * (square and rectangular directions); tt_score_bwd_bf16x3 = tt_score_bwd_bf16: S recomputed as above, the f32 softmax
+ * weights split in registers (w_hi = bf16(w), w_lo = bf16(w - w_hi)), dA += w_hi B_lo + w_lo B_hi + w_hi B_hi.  Shapes:
+ * 1 <= D <= 256, any B >= 1 (ragged tails).  No host synchronisation; every sum in a fixed order: bitwise reproducible.
+ * Tolerance: tests/test_gpu_score_bf16x3.py (against the f64 oracle and the TF32-rounded oracle). */
+size_t tt_score_pack_x3_bytes(int64_t R, int32_t D);
+int tt_score_pack2_bf16x3(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, const float* X1, int64_t R1,
+                          void* packed1, int32_t D, float scale0, float scale1, tt_stream stream);
+int tt_score_fwd_sym_bf16x3(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                            float shift, float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row,
+                            float* inv_col, float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
+                            size_t workspace_bytes, tt_stream stream);
+int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t,
+                        float shift, tt_stream stream);
+int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t,
+                        float shift, const float* d_loss, float scale, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

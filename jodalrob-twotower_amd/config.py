@@ -5,7 +5,8 @@ The reference's driver builds its task through `create_two_tower_train_task(...)
 unchanged selects the fast path with three environment variables -- nothing else in the package or the library reads the
 environment:
 
-    TT_SCORE_DTYPE      fp32 (default: exact-f32 parity path) | bf16 | fp8     score-matrix operands
+    TT_SCORE_DTYPE      fp32 (default: exact-f32 parity path) | bf16 | bf16x3 (split-bf16: near-f32 on the bf16 MFMA) | fp8
+                                                                                score-matrix operands
     TT_MLP_DTYPE        fp32 (default) | bf16                                   tower Linear operands
     TT_EMBEDDING_GRAD   dense (default: `.grad` of every table, as nn.Embedding) | sparse (row lists for FusedAdam)
     TT_SYNC_DEBUG       1: synchronise after every C-ABI call (localises an asynchronous fault to its entry point)

@@ -81,6 +81,21 @@ inline PackedView view(const void* packed, int64_t R, int D) {
   const __bf16* base = reinterpret_cast<const __bf16*>(packed);
   return PackedView{base, base + Rp * Dp};
 }
+// a - b as one subtraction: never contracted with the multiply that produced a (the lo part of a bf16x3 split is formed
+// from the rounded value, as its definition says)
+__device__ __forceinline__ float sub_nc(float a, float b) {
+  float r;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// bf16x3 packing (split-bf16 operands): [hi image | lo image], each one bf16 packing as above of the same R x D -- hi =
+// bf16(scale x), lo = bf16(scale x - hi) -- so the lo image starts tt_score_pack_bytes(R, D) = 4 Rp Dp bytes after the hi one.
+inline size_t x3_half_bytes(int64_t R, int D) { return (size_t)(4 * rup(R > 0 ? R : 1, 64) * padded_d(D)); }
+inline PackedView view_lo(const void* packed, int64_t R, int D) {
+  return view(reinterpret_cast<const char*>(packed) + x3_half_bytes(R, D), R, D);
+}
+
 // fp8 packing: [fp8 rows image: Rp * Dp bytes | bf16 fragment image: Rp * Dp * 2 bytes | fp8 fragment image: Rp * Dp bytes];
 // Dp is a multiple of 64 here.  The fp8 fragment image is the second operand of the gradient products with K = 64 rows per
 // MFMA: [pair of 32-row tiles P][32-column block d][part 0..1][half h][column c][16 bytes], byte j of part p = element

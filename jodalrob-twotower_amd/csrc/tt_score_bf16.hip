@@ -23,9 +23,11 @@ namespace {
 using namespace ttscore;
 
 // ---- pack ------------------------------------------------------------------------------------------
-struct PackArgs { const float* X; int64_t R, Rp; __bf16* rows; __bf16* frag; float scale; };
+struct PackArgs { const float* X; int64_t R, Rp; __bf16* rows; __bf16* frag; float scale; __bf16* rows_lo; __bf16* frag_lo; };
 struct PackBatch { PackArgs a[2]; };
 
+// X3 (bf16x3 packing): also the lo images, bf16(p - hi) of p = scale x, in the same layout.
+template <bool X3>
 __global__ __launch_bounds__(256) void pack_bf16_kernel(PackBatch batch, int D, int Dp) {
   const PackArgs& pa = batch.a[blockIdx.y];
   const float* __restrict__ X = pa.X;
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(PackBatch batch, int D, 
   const int64_t nchunk = Rp * Dp / 8;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < 2 * nchunk; c += stride) {
-    bf16x8 v;
+    bf16x8 v, vl;
     if (c < nchunk) {                                   // k-fragment image [t][k-step][half][row in tile][8]
       const int ci = (int)(c & 31), hh = (int)((c >> 5) & 1);
       const int64_t q = c >> 6;
@@ -44,8 +46,13 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(PackBatch batch, int D, 
       const int64_t row = 32 * (q / (Dp / 16)) + ci;
       const int d0 = 16 * ks + 8 * hh;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (__bf16)((row < R && d0 + j < D) ? X[row * D + d0 + j] * sc : 0.f);
+      for (int j = 0; j < 8; ++j) {
+        const float p = (row < R && d0 + j < D) ? X[row * D + d0 + j] * sc : 0.f;
+        v[j] = (__bf16)p;
+        if (X3) vl[j] = (__bf16)sub_nc(p, (float)v[j]);
+      }
       *reinterpret_cast<bf16x8*>(rows + c * 8) = v;
+      if (X3) *reinterpret_cast<bf16x8*>(pa.rows_lo + c * 8) = vl;
     } else {                                            // fragment-ordered image [t][s][h][d][8]
       const int64_t f = c - nchunk;
       const int d = (int)(f % Dp);
@@ -55,9 +62,12 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(PackBatch batch, int D, 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int64_t row = 32 * t + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);
-        v[j] = (__bf16)((row < R && d < D) ? X[row * D + d] * sc : 0.f);
+        const float p = (row < R && d < D) ? X[row * D + d] * sc : 0.f;
+        v[j] = (__bf16)p;
+        if (X3) vl[j] = (__bf16)sub_nc(p, (float)v[j]);
       }
       *reinterpret_cast<bf16x8*>(frag + f * 8) = v;
+      if (X3) *reinterpret_cast<bf16x8*>(pa.frag_lo + f * 8) = vl;
     }
   }
 }
@@ -74,6 +84,8 @@ struct DirFwd {
   float c1;            // exponent scale for this direction's products: inv_t * log2(e) / (scale the operand images carry)
   float unscale;       // product -> s / T
   float* inv_sumexp;   // optional out: 1 / (the sum as accumulated), the factor the backward kernel multiplies by
+  const __bf16* a_lo;  // bf16x3 operands only: the lo rows images of A and B
+  const __bf16* b_lo;
 };
 struct FwdArgs {
   DirFwd d[2];
@@ -93,6 +105,9 @@ struct DirBwd {
   const float* inv_a;  // optional: DirFwd::inv_sumexp of the A rows / of the B rows (then no reciprocals in the tile loop)
   const float* inv_b;
   const char* b_frag8;  // fp8 packing only: the B rows' fp8 fragment image (score_bwd_rows8_kernel)
+  const __bf16* a_lo;   // bf16x3 operands only: the lo images (rows of A, rows and fragment image of B)
+  const __bf16* b_lo;
+  const __bf16* b_frag_lo;
 };
 struct BwdArgs {
   DirBwd d[2];
@@ -113,6 +128,34 @@ __device__ __forceinline__ void mfma1(const bf16x8 (&bf)[KS], const bf16x8 (&are
     for (int i = 0; i < AT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[s], ares[i][s], acc[i], 0, 0, 0);
 }
 
+// bf16x3: S tile = hi_b lo_a + lo_b hi_a + hi_b hi_a, three chains into ONE accumulator in this fixed order (the small
+// correction terms first).  The same order in every x3 kernel: the forward, the sym forward and the backward recompute
+// bit-identical S tiles.  X3 = false: mfma1.
+template <int KS, int AT, bool X3>
+__device__ __forceinline__ void mfma_s(const bf16x8 (&bh)[KS], const bf16x8 (&bl)[X3 ? KS : 1], const bf16x8 (&ah)[AT][KS],
+                                       const bf16x8 (&al)[AT][X3 ? KS : 1], f32x16 (&acc)[AT]) {
+  if constexpr (!X3) {
+    mfma1<KS, AT>(bh, ah, acc);
+  } else {
+#pragma unroll
+    for (int i = 0; i < AT; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int i = 0; i < AT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[s], al[i][s], acc[i], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int i = 0; i < AT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[s], ah[i][s], acc[i], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int i = 0; i < AT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[s], ah[i][s], acc[i], 0, 0, 0);
+  }
+}
+
 template <int KS, int AT>
 __device__ __forceinline__ void gemm1(const __bf16* __restrict__ b_rows, int64_t t, int c, int h, const bf16x8 (&ares)[AT][KS],
                                       f32x16 (&acc)[AT]) {
@@ -126,9 +169,10 @@ __device__ __forceinline__ void gemm1(const __bf16* __restrict__ b_rows, int64_t
 // term is exp2(acc) with no multiply-add in front -- one VALU op less per score in kernels that are bound by VALU issue --
 // and the constant factor 2^c2 of the fixed shift goes onto the finished row sums (|acc| <= log2(e) / T <= 58 for the
 // supported temperatures: no overflow without the shift).  Rank / diagonal comparisons are scale-free.
-template <int KS, int AT, int NW, bool UNIT>
+// X3: bf16x3 operands (mfma_s); the lo images are read beside the hi ones, everything after the S tile is unchanged.
+template <int KS, int AT, int NW, bool UNIT, bool X3 = false>
 __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
-  constexpr int ROWS = 32 * AT;
+  constexpr int ROWS = 32 * AT, KL = X3 ? KS : 1;
   __shared__ float part_e[NW][ROWS];
   __shared__ float part_s[NW][ROWS];
   __shared__ int part_c[NW][ROWS];
@@ -139,6 +183,8 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
   DirFwd dr;
   dr.a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
   dr.b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
+  dr.a_lo = d1 ? args.d[1].a_lo : args.d[0].a_lo;
+  dr.b_lo = d1 ? args.d[1].b_lo : args.d[0].b_lo;
   dr.sumexp = d1 ? args.d[1].sumexp : args.d[0].sumexp;
   dr.diag = d1 ? args.d[1].diag : args.d[0].diag;
   dr.rank = d1 ? args.d[1].rank : args.d[0].rank;
@@ -155,9 +201,12 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nT = (Rb + 31) / 32;
-  bf16x8 ares[AT][KS];
+  bf16x8 ares[AT][KS], ares_lo[AT][KL];
 #pragma unroll
-  for (int i = 0; i < AT; ++i) load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
+  for (int i = 0; i < AT; ++i) {
+    load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
+    if (X3) load_bfrag<KL>(dr.a_lo, a0 / 32 + i, c, h, ares_lo[i]);
+  }
   int pos[AT];
   float dg[AT];
 #pragma unroll
@@ -169,7 +218,10 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
     const int td1 = (posmax / 32) < nT - 1 ? posmax / 32 : nT - 1;
     for (int t = td0; t <= td1; ++t) {
       f32x16 acc[AT];
-      gemm1<KS, AT>(dr.b_rows, t, c, h, ares, acc);
+      bf16x8 bh[KS], bl[KL];
+      load_bfrag<KS>(dr.b_rows, t, c, h, bh);
+      if (X3) load_bfrag<KL>(dr.b_lo, t, c, h, bl);
+      mfma_s<KS, AT, X3>(bh, bl, ares, ares_lo, acc);
 #pragma unroll
       for (int i = 0; i < AT; ++i)
 #pragma unroll
@@ -284,19 +336,26 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
   };
   // operand prefetch PFD tiles ahead (a ring of register buffers, the loop unrolled over it so no buffer is copied): a tile
   // is ~150 ns of work for a wave, an L2 hit several times that -- one tile of lookahead left the waves waiting on loads
-  constexpr int PFD = KS <= 4 ? 3 : (KS <= 8 ? 2 : 1);
-  bf16x8 bq[PFD][KS];
+  // (X3: twice the operand registers per tile -- one tile less of lookahead)
+  constexpr int PFD = X3 ? (KS <= 4 ? 2 : 1) : (KS <= 4 ? 3 : (KS <= 8 ? 2 : 1));
+  bf16x8 bq[PFD][KS], bql[PFD][KL];
 #pragma unroll
   for (int p = 0; p < PFD; ++p)
-    if (wave + p * NW < nT) load_bfrag<KS>(dr.b_rows, wave + p * NW, c, h, bq[p]);
+    if (wave + p * NW < nT) {
+      load_bfrag<KS>(dr.b_rows, wave + p * NW, c, h, bq[p]);
+      if (X3) load_bfrag<KL>(dr.b_lo, wave + p * NW, c, h, bql[p]);
+    }
   for (int t0 = wave; t0 < nT; t0 += PFD * NW) {
 #pragma unroll
     for (int p = 0; p < PFD; ++p) {
       const int t = t0 + p * NW;
       if (t < nT) {                                                         // wave-uniform
         f32x16 acc[AT];
-        mfma1<KS, AT>(bq[p], ares, acc);
-        if (t + PFD * NW < nT) load_bfrag<KS>(dr.b_rows, t + PFD * NW, c, h, bq[p]);    // refill behind the MFMAs that read it
+        mfma_s<KS, AT, X3>(bq[p], bql[p], ares, ares_lo, acc);
+        if (t + PFD * NW < nT) {                                            // refill behind the MFMAs that read it
+          load_bfrag<KS>(dr.b_rows, t + PFD * NW, c, h, bq[p]);
+          if (X3) load_bfrag<KL>(dr.b_lo, t + PFD * NW, c, h, bql[p]);
+        }
         epilogue(acc, t);
       }
     }
@@ -349,23 +408,32 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
 // ---- backward --------------------------------------------------------------------------------------
 // One tile's worth of streamed operands: the b tile's fragments for the first product, its fragment-ordered image for the
 // second, and the 16 softmax reciprocals (or exp-sums) of its rows this lane half needs.
-template <int KS>
+// X3: the lo images' fragments as well (bl, bml).
+template <int KS, bool X3 = false>
 struct BwdTile {
+  static constexpr int KL = X3 ? KS : 1, DL = X3 ? KS / 2 : 1;
   bf16x8 b[KS];
+  bf16x8 bl[KL];
   bf16x8 bm[2][KS / 2];
+  bf16x8 bml[2][DL];
   float4 iv[4];
 };
 
-template <int KS>
-__device__ __forceinline__ void bwd_tile_load(BwdTile<KS>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
-                                              const float* __restrict__ ivsrc, int t, int c, int h) {
+template <int KS, bool X3>
+__device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
+                                              const float* __restrict__ ivsrc, int t, int c, int h,
+                                              const __bf16* __restrict__ b_lo = nullptr, const __bf16* __restrict__ b_frag_lo = nullptr) {
   constexpr int Dp = KS * 16, DT = KS / 2;
   load_bfrag<KS>(b_rows, t, c, h, T.b);
+  if constexpr (X3) load_bfrag<KS>(b_lo, t, c, h, T.bl);
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int d = 0; d < DT; ++d)
-      T.bm[s][d] = *reinterpret_cast<const bf16x8*>(b_frag + (((((int64_t)t * 2 + s) * 2 + h) * Dp + 32 * d + c) * 8));
+    for (int d = 0; d < DT; ++d) {
+      const int64_t o = ((((int64_t)t * 2 + s) * 2 + h) * Dp + 32 * d + c) * 8;
+      T.bm[s][d] = *reinterpret_cast<const bf16x8*>(b_frag + o);
+      if constexpr (X3) T.bml[s][d] = *reinterpret_cast<const bf16x8*>(b_frag_lo + o);
+    }
 #pragma unroll
   for (int q = 0; q < 4; ++q) T.iv[q] = *reinterpret_cast<const float4*>(ivsrc + 32 * t + 4 * h + 8 * q);
 }
@@ -375,15 +443,20 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS>& T, const __bf16* __re
 // the reciprocals inside the tile body: hipcc then cannot count the loads in flight and drained them all (s_waitcnt
 // vmcnt(0)) twice per tile -- the prefetch never overlapped anything and the kernel ran at a third of its issue rate.
 // The per-row reciprocal arrays must be readable up to a multiple of 32 rows (tt_score_bwd_dir).
-template <int KS, int AT, int NW, bool UNIT>
+// X3 (tt_score_bwd_bf16x3): S recomputed with mfma_s from the hi / lo images; the f32 softmax weights are split in registers,
+// w_hi = bf16(w), w_lo = bf16(w - w_hi), and dA += w_hi B_lo + w_lo B_hi + w_hi B_hi (in this order, per b tile).
+template <int KS, int AT, int NW, bool UNIT, bool X3 = false>
 __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
-  constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2;
+  constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2, KL = X3 ? KS : 1;
   __shared__ float red[(NW / 2) * ROWS * Dp];
   const bool d1 = blockIdx.y != 0;                    // scalar selects, 32-bit positions: see the forward kernel
   DirBwd dr;
   dr.a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
   dr.b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
   dr.b_frag = d1 ? args.d[1].b_frag : args.d[0].b_frag;
+  dr.a_lo = d1 ? args.d[1].a_lo : args.d[0].a_lo;
+  dr.b_lo = d1 ? args.d[1].b_lo : args.d[0].b_lo;
+  dr.b_frag_lo = d1 ? args.d[1].b_frag_lo : args.d[0].b_frag_lo;
   dr.sumexp_a = d1 ? args.d[1].sumexp_a : args.d[0].sumexp_a;
   dr.sumexp_b = d1 ? args.d[1].sumexp_b : args.d[0].sumexp_b;
   dr.dA = d1 ? args.d[1].dA : args.d[0].dA;
@@ -398,12 +471,13 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nT = (Rb + 31) / 32;
-  bf16x8 ares[AT][KS];
+  bf16x8 ares[AT][KS], ares_lo[AT][KL];
   float ia[AT];
   int pos[AT];
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
     load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
+    if (X3) load_bfrag<KL>(dr.a_lo, a0 / 32 + i, c, h, ares_lo[i]);
     const int a = a0 + 32 * i + c;
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
     pos[i] = a + off;
@@ -419,7 +493,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const bool have_inv = inv_b != nullptr;                      // wave-uniform
   const float* const ivsrc = have_inv ? inv_b : dr.sumexp_b;
   const int tlast = nT - 1;
-  auto compute = [&](const BwdTile<KS>& T, int t) {
+  auto compute = [&](const BwdTile<KS, X3>& T, int t) {
     const int b_lo = 32 * t;
     float ib[16];
 #pragma unroll
@@ -436,10 +510,16 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
 #pragma unroll
     for (int i = 0; i < AT; ++i) {
       f32x16 acc;
+      if constexpr (X3) {
+        f32x16 a1[1];
+        mfma_s<KS, 1, true>(T.b, T.bl, reinterpret_cast<const bf16x8(&)[1][KS]>(ares[i]), reinterpret_cast<const bf16x8(&)[1][KL]>(ares_lo[i]), a1);
+        acc = a1[0];
+      } else {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.b[s], ares[i][s], acc, 0, 0, 0);
+        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.b[s], ares[i][s], acc, 0, 0, 0);
+      }
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -453,25 +533,45 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
         for (int r = 0; r < 16; ++r)
           if (b_lo + rowmap(r, h) == pos[i]) w[r] -= 2.f;
       }
-      bf16x8 wf[2];
+      bf16x8 wf[2], wl[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) wf[s][j] = (__bf16)w[8 * s + j];
+        for (int j = 0; j < 8; ++j) {
+          wf[s][j] = (__bf16)w[8 * s + j];
+          if (X3) wl[s][j] = (__bf16)sub_nc(w[8 * s + j], (float)wf[s][j]);
+        }
+      if constexpr (X3) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s], T.bml[s][d], dacc[i][d], 0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[s], T.bm[s][d], dacc[i][d], 0, 0, 0);
+      }
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s], T.bm[s][d], dacc[i][d], 0, 0, 0);
     }
   };
-  BwdTile<KS> T0, T1;
-  bwd_tile_load<KS>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h);
+  BwdTile<KS, X3> T0, T1;
+  if constexpr (X3 && KS == 16) {                              // x3, D = 256: one tile in flight (two are 544 registers)
+    for (int t = wave; t < nT; t += NW) {
+      bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo);
+      compute(T0, t);
+    }
+  } else {
+  bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h, dr.b_lo, dr.b_frag_lo);
   __builtin_amdgcn_sched_barrier(0);                           // (issue order pinned: see the forward kernels)
   for (int t = wave; t < nT; t += 2 * NW) {
-    bwd_tile_load<KS>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h);
+    bwd_tile_load<KS, X3>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h, dr.b_lo, dr.b_frag_lo);
     compute(T0, t);
-    bwd_tile_load<KS>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h);
+    bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h, dr.b_lo, dr.b_frag_lo);
     if (t + NW < nT) compute(T1, t + NW);
+  }
   }
   // fixed-order tree over the NW waves: upper half writes, lower half adds
 #pragma unroll
@@ -1360,7 +1460,7 @@ int tt_score_pack2_bf16(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0,
   int64_t grid = tt_cdiv(maxchunks, 256);
   const int64_t cap = (int64_t)ctx->num_cus * 4;
   if (grid > cap) grid = cap;
-  pack_bf16_kernel<<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
+  pack_bf16_kernel<false><<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -1583,6 +1683,121 @@ int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, 
   else if (Dp == 128) TT_BWD8(8, 2, 4);
   else TT_BWD8(16, 1, 8);
 #undef TT_BWD8
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// ---- bf16x3 (split-bf16) operands: [hi image | lo image] packings, three bf16 MFMAs per product ------------------------
+size_t tt_score_pack_x3_bytes(int64_t R, int32_t D) { return 2 * tt_score_pack_bytes(R, D); }
+
+int tt_score_pack2_bf16x3(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, const float* X1, int64_t R1, void* packed1,
+                          int32_t D, float scale0, float scale1, tt_stream stream) {
+  TT_CHECK_ARG(ctx && X0 && packed0, "tt_score_pack2_bf16x3: NULL argument");
+  TT_CHECK_ARG(R0 >= 1 && D >= 1 && D <= 256 && (X1 == nullptr || (packed1 && R1 >= 1)), "tt_score_pack2_bf16x3: bad shape");
+  TT_CHECK_ARG(tt_aligned(packed0, 16) && tt_aligned(packed1, 16), "tt_score_pack2_bf16x3: packed buffers must be 16-byte aligned");
+  const int Dp = padded_d(D);
+  PackBatch b{};
+  const int n = X1 ? 2 : 1;
+  int64_t maxchunks = 1;
+  for (int i = 0; i < n; ++i) {
+    const int64_t R = i ? R1 : R0, Rp = rup(R, 64);
+    __bf16* base = reinterpret_cast<__bf16*>(i ? packed1 : packed0);
+    __bf16* lo = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(base) + x3_half_bytes(R, D));
+    const float sc = i ? scale1 : scale0;
+    b.a[i] = PackArgs{i ? X1 : X0, R, Rp, base, base + Rp * Dp, sc == 0.f ? 1.f : sc, lo, lo + Rp * Dp};
+    const int64_t chunks = 2 * Rp * Dp / 8;
+    maxchunks = chunks > maxchunks ? chunks : maxchunks;
+  }
+  int64_t grid = tt_cdiv(maxchunks, 256);
+  const int64_t cap = (int64_t)ctx->num_cus * 4;
+  if (grid > cap) grid = cap;
+  pack_bf16_kernel<true><<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                        tt_stream stream) {
+  TT_CHECK_ARG(ctx && dirs && (n_dirs == 1 || n_dirs == 2), "tt_score_fwd_bf16x3: need 1 or 2 directions");
+  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_fwd_bf16x3: D=%d not in [1,256]", D);
+  if (2.f * fabsf(inv_t) > 80.f) {
+    tt_set_error("tt_score_fwd_bf16x3: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", inv_t);
+    return TT_ERR_UNSUPPORTED;
+  }
+  FwdArgs a{};
+  int64_t maxRa = 0;
+  bool unit = true;
+  for (int i = 0; i < 2; ++i) {
+    const tt_score_fwd_dir& d = dirs[i < n_dirs ? i : 0];
+    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp && d.Ra >= 1 && d.Rb >= 1, "tt_score_fwd_bf16x3: bad direction %d", i);
+    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale;
+    a.d[i] = DirFwd{view(d.A_packed, d.Ra, D).rows, view(d.B_packed, d.Rb, D).rows, d.Ra, d.Rb, d.diag_offset, d.sumexp, d.diag, d.rank, d.sumscore,
+                    d.rank ? (d.rank_mode == 1 ? 1 : 2) : 0, inv_t * kLog2e / ab, inv_t / ab, d.inv_sumexp,
+                    view_lo(d.A_packed, d.Ra, D).rows, view_lo(d.B_packed, d.Rb, D).rows};
+    unit = unit && ab == inv_t * kLog2e;
+    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
+  }
+  a.c2 = -shift * kLog2e;
+  a.kexp = exp2f(a.c2);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Dp = padded_d(D);
+#define TT_FWD3(KS, AT, NW)                                                                                    \
+  do {                                                                                                         \
+    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
+    if (unit) score_fwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                      \
+    else score_fwd_bf16_kernel<KS, AT, NW, false, true><<<grid, NW * 64, 0, st>>>(a);                          \
+  } while (0)
+  if (Dp == 32) TT_FWD3(2, 2, 8);
+  else if (Dp == 64) TT_FWD3(4, 1, 8);
+  else if (Dp == 128) TT_FWD3(8, 1, 8);
+  else TT_FWD3(16, 1, 4);                               // one wave per SIMD: the hi / lo fragments of A and of a b tile are 256 registers
+#undef TT_FWD3
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
+// takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
+// workgroup-staged form's stages would both double for the lo images.  One wave per SIMD (4 waves): the hi and lo operands of
+// two b tiles in flight need more than the 256 registers a wave gets at two waves per SIMD.
+int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                        const float* d_loss, float scale, tt_stream stream) {
+  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "tt_score_bwd_bf16x3: need 1 or 2 directions");
+  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_bwd_bf16x3: D=%d not in [1,256]", D);
+  BwdArgs a{};
+  int64_t maxRa = 0;
+  bool unit = true;
+  for (int i = 0; i < 2; ++i) {
+    const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
+    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1,
+                 "tt_score_bwd_bf16x3: bad direction %d", i);
+    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16) && (d.inv_b == nullptr || tt_aligned(d.inv_b, 16)),
+                 "tt_score_bwd_bf16x3: per-row arrays must be 16-byte aligned");
+    const PackedView vb = view(d.B_packed, d.Rb, D), vbl = view_lo(d.B_packed, d.Rb, D);
+    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
+    a.d[i] = DirBwd{view(d.A_packed, d.Ra, D).rows, vb.rows, vb.frag, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA,
+                    inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b, nullptr, view_lo(d.A_packed, d.Ra, D).rows, vbl.rows, vbl.frag};
+    unit = unit && ab == inv_t * kLog2e;
+    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
+  }
+  a.c2 = -shift * kLog2e;
+  a.kexp = exp2f(a.c2);
+  a.d_loss = d_loss;
+  a.D = D;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Dp = padded_d(D);
+#define TT_BWD3(KS, AT, NW)                                                                                    \
+  do {                                                                                                         \
+    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
+    if (unit) score_bwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                      \
+    else score_bwd_bf16_kernel<KS, AT, NW, false, true><<<grid, NW * 64, 0, st>>>(a);                          \
+  } while (0)
+  // two a tiles per workgroup at D <= 64: half the workgroups, half the L2 bytes of the streamed b images
+  if (Dp == 32) TT_BWD3(2, 2, 4);
+  else if (Dp == 64) TT_BWD3(4, 2, 4);
+  else if (Dp == 128) TT_BWD3(8, 1, 4);
+  else TT_BWD3(16, 1, 4);
+#undef TT_BWD3
   TT_LAUNCH_CHECK();
   return TT_OK;
 }

@@ -62,6 +62,8 @@ struct SymArgs {
   float* cs;                           // [n_chunks][Rp]: exp-sum per (a chunk, b)
   float* diag_raw;                     // [R] the positives' products, as the MFMA delivers them
   int want_rank;
+  const void* a_lo;                    // bf16x3 (X3 kernels): the lo rows images
+  const void* b_lo;
 };
 
 // Notice tiles are staged through LDS once per WORKGROUP (all 8 waves sweep the same tiles I): read straight from L2 by
@@ -69,15 +71,17 @@ struct SymArgs {
 // the L2's ~11 TB/s, not at its VALU rate.  A stage = TS tiles (8 KB; 16 KB at D = 64 and D = 256) in the images' own fragment order, so
 // the copy is verbatim (16 bytes per thread) and a wave's ds_read_b128 of a fragment is 1 KB contiguous: conflict-free.
 // Double buffered, one barrier per stage; the next stage's global loads are in flight while this one is computed.
-template <int KS, bool FP8>
+// X3: a staged tile is the hi image's tile followed by the lo image's (kImgB bytes each).
+template <int KS, bool FP8, bool X3 = false>
 struct SymStage {
-  static constexpr int kTileB = FP8 ? KS * 512 : KS * 1024;                 // bytes of one 32-row tile of the rows image
+  static constexpr int kImgB = FP8 ? KS * 512 : KS * 1024;                  // bytes of one 32-row tile of the rows image
+  static constexpr int kTileB = X3 ? 2 * kImgB : kImgB;
   // tiles per stage (D = 64: 2 -> 4 tiles, half the barriers: sweep 22.2 -> 20.8 us).  8-KB tiles: 2 for bf16 D = 128; the fp8
   // D = 256 kernel holds two company tiles per wave and spills with two notice tiles' fragments in flight (256 VGPRs + scratch)
   static constexpr int TS = kTileB <= 4096 ? 4 : ((kTileB <= 8192 && !FP8) ? 2 : 1);
   static constexpr int kBytes = TS * kTileB;
   static constexpr int LPT = kBytes / (kSymThreads * 16);                   // 16-byte pieces per thread per stage
-  static_assert(LPT >= 1 && LPT * kSymThreads * 16 == kBytes && kTileB % 1024 == 0, "stage must be whole 16-byte pieces, a wave's 64 inside one tile");
+  static_assert(LPT >= 1 && LPT * kSymThreads * 16 == kBytes && kImgB % 1024 == 0, "stage must be whole 16-byte pieces, a wave's 64 inside one tile");
 };
 
 // JT company tiles per wave (fp8, D = 256: 2).  With one tile per wave and one notice tile per stage a wave meets a workgroup
@@ -85,10 +89,13 @@ struct SymStage {
 // MFMA chains, the barriers and stage copies per score halve, and the slab of row partials has half the rows.  The two tiles'
 // row partials are added (and their maxima joined) in registers before the slot is written: tiles J0, J0 + 1 lie on the same
 // side of the positives of every notice tile but their own.
-template <int KS, bool UNIT, bool FP8, int JT>
+// X3: bf16x3 operands -- the S tile is mfma_s's three chains (hi_b lo_a, lo_b hi_a, hi_b hi_a): bit-identical to the directional
+// x3 forward's row direction.
+template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false>
 __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
-  using ST = SymStage<KS, FP8>;
-  constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, K64 = FP8 ? KS / 4 : 1;
+  using ST = SymStage<KS, FP8, X3>;
+  constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, kImgB = ST::kImgB, K64 = FP8 ? KS / 4 : 1, KL = X3 ? KS : 1;
+  static_assert(!X3 || (!FP8 && JT == 1), "bf16x3: bf16 images, one company tile per wave");
   static_assert(!FP8 || KS % 4 == 0, "fp8 operands come in K = 64 steps");
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [3][8 waves][NI * 32] slots | 2 stage buffers
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -111,6 +118,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) colacc[j][r] = 0.f;
   bf16x8 bres[JT][FP8 ? 1 : KS];
+  bf16x8 bres_lo[JT][KL];
   i32x8 bres8[JT][K64];
   const int n_full = R / 32;                               // tiles below n_full hold 32 valid rows
   bool jact[JT], jfull[JT];
@@ -122,6 +130,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
     dg_keep[j] = kNegBig;
     if (FP8) load_f8frag<K64>(reinterpret_cast<const char*>(g.b_rows), jact[j] ? J0 + j : 0, c, h, bres8[j]);
     else load_bfrag<(FP8 ? 1 : KS)>(reinterpret_cast<const __bf16*>(g.b_rows), jact[j] ? J0 + j : 0, c, h, bres[j]);
+    if (X3) load_bfrag<KL>(reinterpret_cast<const __bf16*>(g.b_lo), jact[j] ? J0 + j : 0, c, h, bres_lo[j]);
   }
   // stage loader: the stage's tiles go STRAIGHT into the LDS buffer by LDS-DMA (global_load_lds_dwordx4: lane l of a wave writes
   // 16 bytes at the wave's base + 16 l), piece p = tid + 512 q of the stage at byte 16 p; tiles past the image's end are clamped
@@ -134,7 +143,9 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
       const int off = (q * kSymThreads + (int)threadIdx.x) * 16;           // byte offset inside the stage
       const int tl = off / kTileB;                                         // tile of the stage this piece belongs to (wave-uniform)
       const int tile = min(I0 + st * TS + tl, nT - 1);
-      const char* src = reinterpret_cast<const char*>(g.a_rows) + (int64_t)tile * kTileB + (off - tl * kTileB);
+      const int in = off - tl * kTileB;                                    // X3: >= kImgB = the lo image's tile (wave-uniform)
+      const char* src = (X3 && in >= kImgB) ? reinterpret_cast<const char*>(g.a_lo) + (int64_t)tile * kImgB + (in - kImgB)
+                                            : reinterpret_cast<const char*>(g.a_rows) + (int64_t)tile * kImgB + in;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(stage + buf * ST::kBytes + (q * kSymThreads + wave * 64) * 16), 16, 0, 0);
     }
@@ -164,6 +175,21 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
           for (int s = 0; s < K64; ++s)
 #pragma unroll
             for (int j = 0; j < JT; ++j) acc[j] = mfma_f8(bres8[j][s], af8[s], acc[j]);
+        } else if (X3) {
+          // mfma_s's order with the notice fragments read in two bursts: the lo fragments feed the first chain only
+          bf16x8 af[KS];
+#pragma unroll
+          for (int s = 0; s < KS; ++s) af[s] = *reinterpret_cast<const bf16x8*>(sb + tl * kTileB + kImgB + ((s * 2 + h) * 32 + c) * 16);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int s = 0; s < KS; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bres[0][s], af[s], acc[0], 0, 0, 0);
+#pragma unroll
+          for (int s = 0; s < KS; ++s) af[s] = *reinterpret_cast<const bf16x8*>(sb + tl * kTileB + ((s * 2 + h) * 32 + c) * 16);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int s = 0; s < KS; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bres_lo[0][s], af[s], acc[0], 0, 0, 0);
+#pragma unroll
+          for (int s = 0; s < KS; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bres[0][s], af[s], acc[0], 0, 0, 0);
         } else {
           bf16x8 af[FP8 ? 1 : KS];
 #pragma unroll
@@ -287,6 +313,7 @@ struct Fin1Args {
   float* rowsum; float* colsum; float* inv_row; float* inv_col; float* diag; int32_t* row_rank;
   const void* a_rows; const void* b_rows;
   int fp8;                             // the rows images hold fp8 (tt_score_bf16.h) instead of bf16
+  const void* a_lo; const void* b_lo;  // bf16x3: the lo rows images (their columns are added to the hi images')
   float* part;                         // [n_wg][4 + 2 * Dp]: l, hits, dsum, (pad), U[Dp], V[Dp]
 };
 
@@ -333,6 +360,7 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
     const int chunks = f.KS * 64;                          // per tile
     for (int img = 0; img < 2; ++img) {
       const __bf16* base = reinterpret_cast<const __bf16*>(img ? f.b_rows : f.a_rows);
+      const __bf16* lo = reinterpret_cast<const __bf16*>(img ? f.b_lo : f.a_lo);
       for (int ch0 = 0; ch0 < chunks; ch0 += 256) {
         const int ch = ch0 + t;
         float acc8[8];
@@ -346,6 +374,11 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
               const bf16x8 vv = *reinterpret_cast<const bf16x8*>(base + (tile * chunks + ch) * 8);
 #pragma unroll
               for (int j = 0; j < 8; ++j) acc8[j] += (float)vv[j];
+              if (lo) {
+                const bf16x8 vl = *reinterpret_cast<const bf16x8*>(lo + (tile * chunks + ch) * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc8[j] += (float)vl[j];
+              }
             }
           }
         }
@@ -474,7 +507,7 @@ inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D) {
 static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
                        float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col, float* diag,
                        int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
-                       bool fp8, const char* who) {
+                       bool fp8, const char* who, bool x3 = false) {
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
   TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
@@ -496,6 +529,10 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   SymArgs g{};
   g.a_rows = fp8 ? static_cast<const void*>(view8(N_packed, B, D).rows8) : static_cast<const void*>(view(N_packed, B, D).rows);
   g.b_rows = fp8 ? static_cast<const void*>(view8(C_packed, B, D).rows8) : static_cast<const void*>(view(C_packed, B, D).rows);
+  if (x3) {
+    g.a_lo = view_lo(N_packed, B, D).rows;
+    g.b_lo = view_lo(C_packed, B, D).rows;
+  }
   g.R = (int)B; g.nT = L.nT; g.NI = L.NI; g.Rp = L.Rp;
   g.c1 = inv_t * kLog2e / ab;
   g.c2 = -shift * kLog2e;
@@ -517,7 +554,23 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
     if (unit) score_fwd_sym_kernel<KS, true, F8, JT_><<<grid, kSymThreads, lds, st>>>(g);                               \
     else score_fwd_sym_kernel<KS, false, F8, JT_><<<grid, kSymThreads, lds, st>>>(g);                                   \
   } while (0)
-  if (fp8) {
+#define TT_SYM3(KS)                                                                                                     \
+  do {                                                                                                                  \
+    const size_t lds = slot_bytes + 2 * SymStage<KS, false, true>::kBytes;                                              \
+    if (unit) {                                                                                                         \
+      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, true, false, 1, true>);                                                \
+      score_fwd_sym_kernel<KS, true, false, 1, true><<<grid, kSymThreads, lds, st>>>(g);                                \
+    } else {                                                                                                            \
+      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, false, false, 1, true>);                                               \
+      score_fwd_sym_kernel<KS, false, false, 1, true><<<grid, kSymThreads, lds, st>>>(g);                               \
+    }                                                                                                                   \
+  } while (0)
+  if (x3) {
+    if (L.Dp == 32) TT_SYM3(2);
+    else if (L.Dp == 64) TT_SYM3(4);
+    else if (L.Dp == 128) TT_SYM3(8);
+    else TT_SYM3(16);
+  } else if (fp8) {
     if (L.Dp == 64) TT_SYM(4, true, 1);
     else if (L.Dp == 128) TT_SYM(8, true, 1);
     else TT_SYM(16, true, 2);
@@ -528,6 +581,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
     else TT_SYM(16, false, 1);
   }
 #undef TT_SYM
+#undef TT_SYM3
   TT_LAUNCH_CHECK();
   Fin1Args f{};
   f.rs = g.rs; f.mb = g.mb; f.ma = g.ma; f.cs = g.cs; f.diag_raw = g.diag_raw;
@@ -536,6 +590,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   f.rowsum = rowsum; f.colsum = colsum; f.inv_row = inv_row; f.inv_col = inv_col; f.diag = diag; f.row_rank = row_rank;
   f.a_rows = g.a_rows; f.b_rows = g.b_rows;
   f.fp8 = fp8 ? 1 : 0;
+  f.a_lo = g.a_lo; f.b_lo = g.b_lo;
   f.part = reinterpret_cast<float*>(ws + L.off_part);
   score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   TT_LAUNCH_CHECK();
@@ -583,6 +638,14 @@ int tt_score_fwd_sym_fp8(tt_ctx* ctx, const void* N_packed, const void* C_packed
                          tt_stream stream) {
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, true, "tt_score_fwd_sym_fp8");
+}
+
+int tt_score_fwd_sym_bf16x3(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
+                            float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col,
+                            float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
+                            tt_stream stream) {
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3", true);
 }
 
 }  // extern "C"

@@ -24,7 +24,8 @@ MAX_K = 64
 class CatalogIndex:
     """A packed catalogue of nC rows of dimension D.  score_dtype 'bf16' keeps the tt_score_pack_bf16 image of C / T (queries
     are packed unscaled, so the score is <bf16(q), bf16(c / T)> in f32); 'fp32' keeps C as it is and scores with an f32 FMA
-    chain times 1 / T.  'fp8' (a training-time mode) falls back to bf16 here: the index has no fp8 images."""
+    chain times 1 / T.  'fp8' (a training-time mode) falls back to bf16 here: the index has no fp8 images.  'bf16x3' (also a
+    training-time mode: near-f32 products) falls back to the exact 'fp32' sweep -- the fallback that keeps its precision."""
 
     def __init__(self, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None):
         if not torch.is_tensor(C) or C.dim() != 2 or C.shape[0] < 1 or not 1 <= C.shape[1] <= 256:
@@ -32,11 +33,11 @@ class CatalogIndex:
         if C.shape[0] >= 2 ** 31:
             raise ValueError("the catalogue holds at most 2^31 - 1 rows")
         score_dtype = score_dtype or settings.score_dtype
-        if score_dtype not in ("fp32", "bf16", "fp8"):
-            raise ValueError(f"score_dtype must be 'fp32', 'bf16' or 'fp8', got {score_dtype!r}")
+        if score_dtype not in ("fp32", "bf16", "bf16x3", "fp8"):
+            raise ValueError(f"score_dtype must be 'fp32', 'bf16', 'bf16x3' or 'fp8', got {score_dtype!r}")
         if float(temperature) <= 0.0:
             raise ValueError(f"temperature must be > 0, got {temperature}")
-        self.score_dtype = "fp32" if score_dtype == "fp32" else "bf16"
+        self.score_dtype = "fp32" if score_dtype in ("fp32", "bf16x3") else "bf16"
         self.temperature = float(temperature)
         self.inv_t = 1.0 / self.temperature
         self.device = C.device
@@ -51,7 +52,7 @@ class CatalogIndex:
     @classmethod
     def from_embeddings(cls, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None) -> "CatalogIndex":
         """Index of ready embeddings C [nC, D] (the towers' outputs are L2-normalised; nothing is normalised here).
-        score_dtype: 'fp32' | 'bf16' | 'fp8' (-> bf16); default: the package's score_dtype setting (TT_SCORE_DTYPE)."""
+        score_dtype: 'fp32' | 'bf16' | 'bf16x3' (-> fp32) | 'fp8' (-> bf16); default: the package's score_dtype setting (TT_SCORE_DTYPE)."""
         return cls(C, temperature, score_dtype)
 
     @classmethod

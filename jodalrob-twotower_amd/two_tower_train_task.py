@@ -48,13 +48,15 @@ class _DenseLossFn(torch.autograd.Function):
 
 class _ScoreCEFn(torch.autograd.Function):
     """loss = 0.5 * [CE(S, diag) + CE(S^T, diag)],  S = N C^T / T   (:99-134); out8 carries the metrics.
-    score_dtype 'fp32': exact-f32 MFMA path (parity); 'bf16': bf16-operand MFMA fast path."""
+    score_dtype 'fp32': exact-f32 MFMA path (parity); 'bf16': bf16-operand MFMA fast path; 'bf16x3': split-bf16 operands
+    (hi + lo, three bf16 MFMAs per product: near-f32 products on the bf16 pipe)."""
 
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
+        ctx.x3 = False
         if score_dtype == "fp8":
             # e4m3 operands for the S products (v_mfma_scale_f32_32x32x64_f8f6f4: twice the bf16 MFMA rate), everything else as
             # the bf16 path; always the single-pass forward and the workgroup-staged backward (BASELINE configs[4])
@@ -69,7 +71,28 @@ class _ScoreCEFn(torch.autograd.Function):
             ctx.set_materialize_grads(False)
             return loss, out8, row_rank
         ctx.fp8 = False
-        if score_dtype == "bf16":
+        if score_dtype == "bf16x3":
+            # as the bf16 branch on [hi | lo] images (tt_score_pack2_bf16x3); the towers' fused tail emits bf16 images only, so
+            # the pack is always its own launch.  Both images unscaled: the split of inv_t * log2(e) * n (the "unit" form) would
+            # carry the scale's rounding into every operand -- one multiply-add more per score keeps operands that are exact in
+            # bf16 exact here (D = 1: every product exact, as in fp32).
+            scale_n = 1.0
+            Np, Cp = ops.score_pack2_bf16x3(n, c, scale_n, 1.0)
+            ctx.x3 = True
+            if not want_col_rank and not full_rank:
+                rowsum, colsum, diag, row_rank, inv, out8, loss = ops.score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, x3=True)
+                ctx.packed = (Np, Cp, scale_n, inv)
+                ctx.save_for_backward(n, c, rowsum, colsum)
+                ctx.inv_t, ctx.shift = inv_t, shift
+                ctx.mark_non_differentiable(out8, row_rank)
+                ctx.set_materialize_grads(False)
+                return loss, out8, row_rank
+            rowsum, colsum, diag, row_rank, col_rank, sumscore, inv = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, want_col_rank,
+                                                                                         full_rank, scale_n, with_inv=True, x3=True)
+            if not want_col_rank:
+                col_rank = row_rank
+            ctx.packed = (Np, Cp, scale_n, inv)
+        elif score_dtype == "bf16":
             # scale_n: the notice image holds bf16(scale_n * n) -- with scale_n = inv_t * log2(e) the exponent scale of the
             # softmax rides in the MFMA and the kernels skip a multiply-add per score (results are scale-free).
             # The towers' fused tail can emit the packed operand images itself (tt_tower_acts.emb_packed): one launch fewer.
@@ -115,7 +138,7 @@ class _ScoreCEFn(torch.autograd.Function):
         scale = ctx.inv_t / (2.0 * B)
         if ctx.packed is not None:
             dN, dC = ops.score_bwd_bf16(ctx.packed[0], ctx.packed[1], B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale,
-                                        ctx.packed[2], ctx.packed[3], fp8=ctx.fp8)
+                                        ctx.packed[2], ctx.packed[3], fp8=ctx.fp8, x3=ctx.x3)
         else:
             dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale)
             dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale)
@@ -167,8 +190,8 @@ class TwoTowerTrainTask(nn.Module):
                  label_smoothing: float = 0.0, score_dtype: str = None):
         super().__init__()
         self.score_dtype = score_dtype or settings.score_dtype
-        if self.score_dtype not in ("fp32", "bf16", "fp8"):
-            raise ValueError(f"score_dtype must be 'fp32', 'bf16' or 'fp8', got {self.score_dtype!r}")
+        if self.score_dtype not in ("fp32", "bf16", "bf16x3", "fp8"):
+            raise ValueError(f"score_dtype must be 'fp32', 'bf16', 'bf16x3' or 'fp8', got {self.score_dtype!r}")
         if self.score_dtype == "bf16" and settings.tower_pack:       # (settings.tower_pack = False: separate pack launch; tests)
             for tw in (two_tower_model.notice_tower, two_tower_model.company_tower):
                 tw.pack_for_score = True
