@@ -108,6 +108,55 @@ def embed_grad_sparse(d_concat: np.ndarray, ids_clamped: np.ndarray, row_offsets
 
 
 # ------------------------------------------------------------------------------------------------
+# dropout mask of the HIP kernels (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip dropout_scale): the mask is never
+# stored; every kernel regenerates it from (seed, element index).  Element (r, c) of hidden block i of tower t (t = the tower's
+# slot in the batched launch: 0 notice, 1 company; 0 for a tower launched alone) has index
+#   salt + r * H + c,   salt = (((i + 1) << 40) ^ (t << 52)) + rng_row_offset * H          (all mod 2^64)
+# and is kept iff uniform01(seed, index) >= p (compared in f32); kept elements are scaled by f32(1) / (f32(1) - f32(p)).
+# ------------------------------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+_M64 = (1 << 64) - 1
+
+
+def mix32(x):
+    """tt_mix32 on uint32 arrays (wrapping arithmetic)"""
+    x = np.asarray(x, dtype=np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def uniform01(seed: int, idx) -> np.ndarray:
+    """tt_uniform01(seed, idx) as float32: seed a Python int (taken mod 2^64), idx uint64 array"""
+    seed = int(seed) & _M64
+    idx = np.asarray(idx, dtype=np.uint64)
+    lo = (idx & np.uint64(_M32)).astype(np.uint32)
+    hi = (idx >> np.uint64(32)).astype(np.uint32)
+    h = mix32(lo ^ np.uint32(seed & _M32) ^ ((hi ^ np.uint32(seed >> 32)) * np.uint32(0x9E3779B9)))
+    return (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def dropout_salt(t: int, i: int, H: int, row_offset: int = 0) -> int:
+    """the element-index offset of hidden block i of tower slot t (csrc/tt_tower.hip, tt_towers_mlp_fwd / _bwd)"""
+    return (((((i + 1) << 40) ^ (t << 52)) & _M64) + row_offset * H) & _M64
+
+
+def dropout_keep(seed: int, t: int, i: int, B: int, H: int, p: float, row_offset: int = 0) -> np.ndarray:
+    """bool [B, H]: the kernels' keep mask of hidden block i (width H) of tower slot t at dropout rate p; seed is the
+    kernels' effective seed (the host seed plus a captured step's device word, mod 2^64)"""
+    salt = dropout_salt(t, i, H, row_offset)
+    idx = (np.uint64(salt) + np.arange(B * H, dtype=np.uint64)).reshape(B, H)      # wraps mod 2^64
+    return uniform01(seed, idx) >= np.float32(p)
+
+
+def dropout_scale(p: float) -> np.float32:
+    """the kept elements' factor as the kernels form it: f32(1) / (f32(1) - f32(p))"""
+    return np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+
+
+# ------------------------------------------------------------------------------------------------
 # a6/a7  tower  (src/towers/tower/base_tower.py:71-147)
 # ------------------------------------------------------------------------------------------------
 def tower_layout(state: dict, prefix: str, keys):
@@ -118,12 +167,15 @@ def tower_layout(state: dict, prefix: str, keys):
     return i, 4 * i
 
 
-def tower_fwd(state: dict, prefix: str, keys, vocab_sizes, dense, values, train: bool, dtype=np.float32, q=None):
+def tower_fwd(state: dict, prefix: str, keys, vocab_sizes, dense, values, train: bool, dtype=np.float32, q=None, dropout=None):
     """BaseTower.forward.  Returns (emb [B,D], cache, bn_updates).
     x = cat[dense W0^T + b0 | embed concat]          base_tower.py:133-139
-    per hidden block: BN(ReLU(x W^T + b)) (dropout p=0 / eval: identity)   base_tower.py:88-93
+    per hidden block: Dropout(BN(ReLU(x W^T + b)))   base_tower.py:88-93
     y = h W_f^T + b_f ; y / max(||y||, 1e-12)        base_tower.py:97,145
     q: operand rounding of the bf16 mode (q_bf16) -- every Linear's two operands, and the stored tower input x.
+    dropout: None (p = 0 / eval: identity) or (p, {(prefix, i): keep bool [B, H_i]}): in train mode block i's output is
+    BN(...) * keep * scale with scale = dropout_scale(p); a block without an entry is not dropped.  The BN statistics and the
+    running-stat updates are taken before dropout; under q the dropped, scaled activation is the next Linear's operand.
     """
     f = lambda a: np.asarray(a, dtype=dtype)
     q = q or _ident
@@ -157,7 +209,14 @@ def tower_fwd(state: dict, prefix: str, keys, vocab_sizes, dense, values, train:
         rstd = 1.0 / np.sqrt(var + dtype(BN_EPS))
         xhat = (a - mean) * rstd
         out = xhat * g + be
-        cache["blocks"].append({"inp": h, "W": W, "pre": pre, "xhat": xhat, "rstd": rstd, "g": g})
+        drop = None
+        if train and dropout is not None and (prefix, i) in dropout[1]:
+            keep = np.asarray(dropout[1][(prefix, i)], dtype=bool)
+            if keep.shape != out.shape:
+                raise ValueError(f"dropout mask of {prefix} block {i}: shape {keep.shape}, activation {out.shape}")
+            drop = np.where(keep, dtype(dropout_scale(dropout[0])), dtype(0))
+            out = out * drop
+        cache["blocks"].append({"inp": h, "W": W, "pre": pre, "xhat": xhat, "rstd": rstd, "g": g, "drop": drop})
         h = out
     Wf, bf = f(state[f"{prefix}mlp.{fin}.weight"]), f(state[f"{prefix}mlp.{fin}.bias"])
     y = q(h) @ q(Wf).T + bf
@@ -170,7 +229,8 @@ def tower_fwd(state: dict, prefix: str, keys, vocab_sizes, dense, values, train:
 
 def tower_bwd(cache: dict, d_emb: np.ndarray, prefix: str, keys, vocab_sizes, table_grads: str = "dense",
               proj_grad: str = "direct"):
-    """Backward of tower_fwd (train-mode BN, dropout p=0).  Returns {state_dict key: grad}.
+    """Backward of tower_fwd (train-mode BN; a dropped block's gradient is dh * keep * scale before the BN backward).
+    Returns {state_dict key: grad}.
     table_grads: "dense" = the reference's dense [V_k, E] arrays; "none" = skip them (the caller takes the
     slot gradients `_d_concat` and forms the sparse-unique rows itself: 1 M-row tables).
     proj_grad: how the dense projection's gradients are formed under operand rounding (without rounding the two are the
@@ -192,6 +252,8 @@ def tower_bwd(cache: dict, d_emb: np.ndarray, prefix: str, keys, vocab_sizes, ta
     for i in reversed(range(nblk)):
         blk = cache["blocks"][i]
         xhat, rstd, g = blk["xhat"], blk["rstd"], blk["g"]
+        if blk.get("drop") is not None:
+            dh = dh * blk["drop"]
         grads[f"{prefix}mlp.{4 * i + 2}.weight"] = (dh * xhat).sum(axis=0)
         grads[f"{prefix}mlp.{4 * i + 2}.bias"] = dh.sum(axis=0)
         if cache["train"]:
@@ -351,7 +413,7 @@ NT, CT = "two_tower_model.notice_tower.", "two_tower_model.company_tower."
 
 def task_step(state, batch, keys_n, keys_c, vocab_n, vocab_c, temperature=1.0, train=True, backward=True,
               dtype=np.float32, rounding=None, table_grads="dense", keep_sim=True, proj_grad="direct",
-              loss_type="cross_entropy", label_smoothing=0.0, score_rounding=None):
+              loss_type="cross_entropy", label_smoothing=0.0, score_rounding=None, dropout=None):
     """One forward (+backward) of the task.  batch: dict with notice_ids/company_ids [B,K] (or flat
     values) and notice_dense/company_dense.  Returns dict(loss, metrics, sim, notice_emb, company_emb,
     grads{state key: array}, bn_updates).
@@ -359,7 +421,8 @@ def task_step(state, batch, keys_n, keys_c, vocab_n, vocab_c, temperature=1.0, t
     score_rounding="fp8" (with rounding="bf16"; BASELINE configs[4], score_dtype="fp8"): the score matrix AND the two gradient
     products are formed from e4m3 operands (score_operands_fp8), the softmax weights block-scaled e4m3 (q_block_e4m3), the
     diagonal's weight exact on the bf16 operand's row.  score_rounding="fp8_s" (TT_OPT_FP8_GRAD 0): only the score matrix from
-    e4m3 operands; gradient products from the bf16 ones with bf16 weights."""
+    e4m3 operands; gradient products from the bf16 ones with bf16 weights.
+    dropout: (p, {(tower prefix NT / CT, block i): keep [B, H_i]}) -- see tower_fwd; None = no dropout."""
     q = q_bf16 if rounding == "bf16" else None
     if rounding not in (None, "bf16"):
         raise ValueError(f"rounding must be None or 'bf16', got {rounding!r}")
@@ -369,8 +432,8 @@ def task_step(state, batch, keys_n, keys_c, vocab_n, vocab_c, temperature=1.0, t
     vals_c = np.asarray(batch["company_ids"]).reshape(-1)
     if batch["notice_dense"].shape[0] != batch["company_dense"].shape[0]:
         raise ValueError("notice/company batch size mismatch")          # two_tower_train_task.py:64-67
-    ne, cn, bn_n = tower_fwd(state, NT, keys_n, vocab_n, batch["notice_dense"], vals_n, train, dtype, q)
-    ce, cc, bn_c = tower_fwd(state, CT, keys_c, vocab_c, batch["company_dense"], vals_c, train, dtype, q)
+    ne, cn, bn_n = tower_fwd(state, NT, keys_n, vocab_n, batch["notice_dense"], vals_n, train, dtype, q, dropout)
+    ce, cc, bn_c = tower_fwd(state, CT, keys_c, vocab_c, batch["company_dense"], vals_c, train, dtype, q, dropout)
     sn, sc = score_operands_bf16(ne, ce, temperature) if q is not None else (ne, ce)
     prod = None
     if score_rounding is not None:

@@ -235,3 +235,126 @@ def test_loss_variants_match_reference(case):
             assert np.abs(out["grads"][k] - v).max() <= 5e-2 * gmax + 1e-6, k
         else:
             np.testing.assert_allclose(out["grads"][k], v, rtol=2e-4, atol=2e-7, err_msg=k)
+
+
+def test_dropout_step_matches_reference():
+    """A training step with dropout on (p = 0.3, two hidden blocks: base_tower.py:88-93) against vectors the reference produced
+    with its own nn.Dropout (oracle/gen_golden_dropout.py): the oracle, fed the masks the reference drew, matches the loss, the
+    metrics, both embeddings, every gradient and the BatchNorm running statistics (taken before dropout) at this file's
+    tolerances.  Without the masks it does not: the fixture pins the dropout terms, not just the rest of the step."""
+    cfg = json.loads((GOLD / "dropout_cases.json").read_text())["cases"]["dropout_train"]
+    g = load_case("dropout_train")
+    masks = {}
+    for k, v in split_prefix(g, "mask.").items():
+        prefix, i = k.rsplit(".", 1)
+        masks[(prefix + ".", int(i))] = v
+    assert sorted(masks) == sorted((pre, i) for pre in (O.NT, O.CT) for i in range(len(cfg["hidden"]) - 1))
+    for (pre, i), keep in masks.items():
+        assert keep.shape == (cfg["B"], cfg["hidden"][i + 1]) and 0 < keep.mean() < 1
+    args = (split_prefix(g, "state."), split_prefix(g, "in."), cfg["keys_n"], cfg["keys_c"], cfg["vocab_n"], cfg["vocab_c"])
+    out = O.task_step(*args, temperature=cfg["T"], train=True, dropout=(cfg["p"], masks))
+    np.testing.assert_allclose(out["notice_emb"], g["out.notice_emb"], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(out["company_emb"], g["out.company_emb"], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(out["sim"], g["sim"], rtol=RTOL, atol=5e-6)
+    np.testing.assert_allclose(out["loss"], g["out.loss"], rtol=RTOL)
+    assert float(out["accuracy"]) == float(g["out.accuracy"])
+    for k in ("positive_similarity_mean", "negative_similarity_mean", "similarity_gap"):
+        np.testing.assert_allclose(out[k], g["out." + k], rtol=1e-4, atol=1e-6)
+    ref = split_prefix(g, "grad.")
+    assert set(ref) == set(out["grads"])
+    for k, v in ref.items():
+        np.testing.assert_allclose(out["grads"][k], v, rtol=2e-4, atol=2e-7, err_msg=k)
+    after = split_prefix(g, "state_after.")
+    assert len(after) == 3 * len(masks)
+    for k, v in after.items():
+        np.testing.assert_allclose(out["bn_updates"][k], v, rtol=RTOL, atol=ATOL, err_msg=k)
+    plain = O.task_step(*args, temperature=cfg["T"], train=True)
+    assert abs(plain["loss"] - g["out.loss"]) > 1e-3 * abs(g["out.loss"])
+    # the second block's statistics see the first block's dropped activations; the first block's do not
+    for pre in (O.NT, O.CT):
+        np.testing.assert_array_equal(plain["bn_updates"][pre + "mlp.2.running_mean"], out["bn_updates"][pre + "mlp.2.running_mean"])
+        assert not np.allclose(plain["bn_updates"][pre + "mlp.6.running_mean"], out["bn_updates"][pre + "mlp.6.running_mean"])
+
+
+def test_dropout_oracle_without_masks_is_unchanged(manifest):
+    """dropout=None, an empty mask dict and eval mode with masks all give exactly the p = 0 step"""
+    cfg = manifest["cases"]["deep_temp"]
+    g = load_case("deep_temp")
+    args = (split_prefix(g, "state."), split_prefix(g, "in."), cfg["keys_n"], cfg["keys_c"], cfg["vocab_n"], cfg["vocab_c"], cfg["T"])
+    base = O.task_step(*args, True)
+    for out in (O.task_step(*args, True, dropout=None), O.task_step(*args, True, dropout=(0.5, {}))):
+        assert out["loss"] == base["loss"]
+        for k, v in base["grads"].items():
+            assert np.array_equal(out["grads"][k], v), k
+    B = g["in.notice_dense"].shape[0]
+    masks = {(pre, i): np.zeros((B, h), bool) for pre in (O.NT, O.CT) for i, h in enumerate(cfg["hidden"][1:])}
+    ev0, ev1 = O.task_step(*args, False, backward=False), O.task_step(*args, False, backward=False, dropout=(0.5, masks))
+    assert np.array_equal(ev0["notice_emb"], ev1["notice_emb"]) and np.array_equal(ev0["company_emb"], ev1["company_emb"])
+
+
+# ---- the kernels' dropout mask restated in plain Python (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip)
+def _mix32_scalar(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def _keep_scalar(seed, idx, p):
+    import struct
+    seed &= (1 << 64) - 1
+    idx &= (1 << 64) - 1
+    lo, hi = idx & 0xFFFFFFFF, idx >> 32
+    h = _mix32_scalar(lo ^ (seed & 0xFFFFFFFF) ^ (((hi ^ (seed >> 32)) * 0x9E3779B9) & 0xFFFFFFFF))
+    u = (h >> 8) * 2.0 ** -24                                          # exact: h >> 8 < 2^24
+    pf = struct.unpack("f", struct.pack("f", p))[0]                    # the kernel's float p
+    return u >= pf
+
+
+@pytest.mark.parametrize("seed,t,i,row_offset,p", [
+    (5, 0, 0, 0, 0.1),
+    (12345678901, 1, 1, 0, 0.3),
+    (2 ** 63, 0, 2, 0, 0.5),                                   # seed at 2^63
+    ((1 << 64) - 1, 1, 0, 3, 0.2),                             # the largest seed, and a row offset
+    (0xFFFFFFFF_00000000 + 0x9E3779B9, 1, 7, 1 << 20, 0.25),   # hi seed word all ones; index near 2^60
+    (3, 0, 1, 0, 0.0),                                         # p = 0: everything kept
+    (77, 1, 0, 0, 0.999),                                      # p close to 1
+    (77, 1, 0, 0, 1.0 - 2.0 ** -24),                           # the largest f32 below 1
+])
+def test_dropout_keep_matches_scalar_hash(seed, t, i, row_offset, p):
+    """oracle_np.dropout_keep (vectorised uint32 / uint64 numpy) == a scalar plain-Python copy of the kernels' hash, for every
+    element of a block: indices whose high word is nonzero (the salt always has one), seeds at and above 2^63, row offsets."""
+    B, H = 13, 37
+    got = O.dropout_keep(seed, t, i, B, H, p, row_offset)
+    salt = ((((i + 1) << 40) ^ (t << 52)) + row_offset * H) % (1 << 64)
+    assert salt >> 32 != 0
+    want = np.array([[_keep_scalar(seed, salt + r * H + c, p) for c in range(H)] for r in range(B)])
+    assert got.dtype == bool and np.array_equal(got, want)
+    if p == 0.0:
+        assert got.all()
+    if p > 0.99:
+        assert got.mean() < 0.05
+
+
+def test_dropout_keep_seed_and_index_wrap():
+    """seed + a captured step's device word past 2^64, and an index past 2^64, wrap as the kernels' uint64 arithmetic does"""
+    base, word = (1 << 64) - 5, 1 << 62
+    a = O.dropout_keep(base + word, 0, 0, 8, 16, 0.4)
+    assert np.array_equal(a, O.dropout_keep((base + word) % (1 << 64), 0, 0, 8, 16, 0.4))
+    want = np.array([[_keep_scalar(base + word, (1 << 40) + r * 16 + c, 0.4) for c in range(16)] for r in range(8)])
+    assert np.array_equal(a, want)
+    # an index run that crosses 2^64: a row offset that puts row 32 of the block past the wrap
+    t, i, H = 1, 2, 16
+    off = ((1 << 64) - O.dropout_salt(t, i, H)) // H - 32
+    salt = O.dropout_salt(t, i, H, row_offset=off)
+    assert salt + 31 * H + H - 1 < (1 << 64) <= salt + 33 * H
+    got = O.dropout_keep(99, t, i, 64, H, 0.3, row_offset=off)
+    want = np.array([[_keep_scalar(99, (salt + r * H + c) % (1 << 64), 0.3) for c in range(H)] for r in range(64)])
+    assert np.array_equal(got, want)
+    # the scale as the kernels form it
+    for p in (0.1, 0.3, 0.5):
+        assert O.dropout_scale(p) == np.float32(1) / (np.float32(1) - np.float32(p))
+        assert O.dropout_scale(p).dtype == np.float32
