@@ -297,6 +297,40 @@ int tt_adam_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_
                               int64_t M, const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes,
                               int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               const float* hparams_dev, tt_stream stream);
+
+/* Row-wise Adagrad for the embedding tables (FBGEMM's EXACT_ROWWISE_ADAGRAD): ONE f32 accumulator per table row, `sum`
+ * [table_rows], zero initially.  For a row w (E floats) with gradient g:
+ *   g' = g + weight_decay * w   (coupled, as Adam's; only when weight_decay != 0)
+ *   s += sum_j g'_j^2 / E;   w -= lr / (sqrt(s) + eps) * g'
+ * The row's sum is formed in a fixed order (lane-local in column order, then an xor butterfly over the row's lanes): two
+ * runs on the same inputs, and a graph replay against eager calls, give the same bits.  E <= 1024 (E <= 256 when E % 4 != 0).
+ * hparams_dev: NULL, or device floats [0] = lr [1] = eps [2] = weight_decay read instead of the host scalars (graph replay).
+ *   tt_rowwise_adagrad_sparse_step: the U rows of a dedup plan; entries of unique_rows >= table_rows are skipped (routing
+ *                                   pads); rows not in the plan are not touched
+ *   tt_rowwise_adagrad_dense_step : every row of a dense-mode [table_rows, E] store gradient */
+int tt_rowwise_adagrad_sparse_step(tt_ctx* ctx, float* table, float* sum, int64_t table_rows, int32_t E,
+                                   const int32_t* unique_rows, const float* grad_rows, const int32_t* n_unique, int64_t M,
+                                   float lr, float eps, float weight_decay, const float* hparams_dev, tt_stream stream);
+int tt_rowwise_adagrad_dense_step(tt_ctx* ctx, float* table, float* sum, const float* grad, int64_t table_rows, int32_t E,
+                                  float lr, float eps, float weight_decay, const float* hparams_dev, tt_stream stream);
+/* tt_adam_multi_step (<= 32 tensors, the first hyper-parameter set) and tt_rowwise_adagrad_sparse_step (the table_* set) in
+ * ONE launch: the towers and the tables sit in different parameter groups.  Equal to the two separate entries. */
+int tt_adam_rowwise_adagrad_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev,
+                                       float* table, float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows,
+                                       const float* grad_rows, const int32_t* n_unique, int64_t M, float table_lr,
+                                       float table_eps, float table_weight_decay, const float* table_hparams_dev,
+                                       tt_stream stream);
+/* the same for a gradient whose long-row finish was deferred (TT_GRAD_DEFER_FINISH): workgroups of the launch complete each
+ * long row into grad_rows (bit-identical to the reduction's own finish), then reduce that row's g'^2 over all E columns and
+ * update it; grad_rows is complete when the launch has run. */
+int tt_adam_rowwise_adagrad_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step,
+                                              float lr, float beta1, float beta2, float eps, float weight_decay,
+                                              const float* hparams_dev, float* table, float* sum, int64_t table_rows, int32_t E,
+                                              const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique, int64_t M,
+                                              const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes,
+                                              float table_lr, float table_eps, float table_weight_decay,
+                                              const float* table_hparams_dev, tt_stream stream);
 /* The deferred finish on its own (sparse mode: out = grad_rows [M, E]) -- for a consumer other than the fused optimiser. */
 int tt_embed_grad_finish(tt_ctx* ctx, int32_t E, const int32_t* seg_offsets, int64_t M, float* out, void* workspace,
                          size_t workspace_bytes, tt_stream stream);

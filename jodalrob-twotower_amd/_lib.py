@@ -117,6 +117,12 @@ SIGNATURES = {
                                      f32, vp, vp]),
     "tt_adam_fused_step_finish": (C.c_int, [vp, C.POINTER(AdamTensor), i32, vp, vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, sz, i64, f32,
                                             f32, f32, f32, f32, vp, vp]),
+    "tt_rowwise_adagrad_sparse_step": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, vp, i64, f32, f32, f32, vp, vp]),
+    "tt_rowwise_adagrad_dense_step": (C.c_int, [vp, vp, vp, vp, i64, i32, f32, f32, f32, vp, vp]),
+    "tt_adam_rowwise_adagrad_fused_step": (C.c_int, [vp, C.POINTER(AdamTensor), i32, i64, f32, f32, f32, f32, f32, vp, vp, vp, i64, i32,
+                                                     vp, vp, vp, i64, f32, f32, f32, vp, vp]),
+    "tt_adam_rowwise_adagrad_fused_step_finish": (C.c_int, [vp, C.POINTER(AdamTensor), i32, i64, f32, f32, f32, f32, f32, vp, vp, vp,
+                                                            i64, i32, vp, vp, vp, i64, vp, vp, sz, f32, f32, f32, vp, vp]),
     "tt_embed_grad_finish": (C.c_int, [vp, i32, vp, i64, vp, vp, sz, vp]),
     "tt_ctx_set_option": (C.c_int, [vp, i32, i32]),
     "tt_flush_deferred": (C.c_int, [vp, vp]),

@@ -1298,9 +1298,14 @@ __global__ __launch_bounds__(kSegThreads) TT_SEG_OCC void seg_reduce_chunk_slab_
 // (a binary key at B = 8192 has ~4096-slot rows = 256 partials)
 constexpr int kFinishMaxFloats = 4096;     // (kThreads / LG) * E floats of LDS
 // emit(u, col, total): called once per (long row, column) by the thread that added the group sums
-template <int VEC, typename EMIT>
+// done(u): called by every thread of the workgroup once all of row u's emits have happened and are visible to the workgroup
+struct NoRowDone {
+  __device__ void operator()(int32_t) const {}
+};
+template <int VEC, typename EMIT, typename DONE = NoRowDone>
 __device__ __forceinline__ void long_rows_finish(int32_t E, uint32_t C, const int32_t* __restrict__ seg, const GradWs& ws, uint32_t LG,
-                                                 uint32_t bid, uint32_t nblocks, float* __restrict__ part, EMIT&& emit) {
+                                                 uint32_t bid, uint32_t nblocks, float* __restrict__ part, EMIT&& emit,
+                                                 DONE&& done = DONE{}) {
   const uint32_t nlong = (uint32_t)ws.counters[2];        // the long-row count as seg_chunk_body saw it
   const uint32_t grp = threadIdx.x / LG, lig = threadIdx.x % LG, ngrp = blockDim.x / LG;
   for (uint32_t li = bid; li < nlong; li += nblocks) {
@@ -1338,6 +1343,7 @@ __device__ __forceinline__ void long_rows_finish(int32_t E, uint32_t C, const in
       emit(u, col, tot);
     }
     __syncthreads();
+    done(u);     // (whatever it reads was written before the barrier above; the next row's emits follow the next barrier)
   }
 }
 
@@ -1531,6 +1537,154 @@ __global__ __launch_bounds__(kThreads) void adam_fused_kernel(AdamFusedArgs a, f
       }
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// a17b: row-wise Adagrad (one f32 accumulator per table row)
+//   g' = g + wd * w;  s += sum_j g'_j^2 / E;  w -= lr / (sqrt(s) + eps) * g'
+// A row is owned by LG lanes of one wave (LG a power of two <= 64, the adam_sparse_kernel mapping); each lane holds its
+// chunks of g' in registers, the row's sum of squares is formed lane-locally in chunk order and then by an xor butterfly
+// over the LG lanes (no LDS, no atomics).  Every lane of the group ends with the same bits, so any lane may write s.
+// ------------------------------------------------------------------------------------------------
+struct AdagradK {
+  float lr, eps, wd;
+  const float* dev;   // optional device copy of the three scalars above (graph replay): [0] lr [1] eps [2] wd
+};
+
+__device__ __forceinline__ AdagradK adagrad_resolve(const AdagradK& k) {
+  if (k.dev == nullptr) return k;
+  AdagradK r;
+  r.lr = k.dev[0]; r.eps = k.dev[1]; r.wd = k.dev[2];
+  r.dev = nullptr;
+  return r;
+}
+
+constexpr int kAdagradMaxChunks = 4;   // chunks of one row per lane: E <= 4 * 64 * VEC
+
+// the update of one table row by its LG lanes (lig = lane in group); g: the row's gradient, w: its weights, s: its accumulator
+template <int VEC>
+__device__ __forceinline__ void adagrad_row(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s, int32_t E,
+                                            uint32_t C, uint32_t LG, uint32_t lig, const AdagradK& k) {
+  float gp[kAdagradMaxChunks][VEC], wp[kAdagradMaxChunks][VEC];
+  float sq = 0.f;
+#pragma unroll
+  for (int c = 0; c < kAdagradMaxChunks; ++c) {
+    const uint32_t chunk = lig + (uint32_t)c * LG;
+    if (chunk < C) {
+      if constexpr (VEC == 4) {
+        const float4 gg = *reinterpret_cast<const float4*>(g + chunk * 4);
+        const float4 ww = *reinterpret_cast<const float4*>(w + chunk * 4);
+        gp[c][0] = gg.x; gp[c][1] = gg.y; gp[c][2] = gg.z; gp[c][3] = gg.w;
+        wp[c][0] = ww.x; wp[c][1] = ww.y; wp[c][2] = ww.z; wp[c][3] = ww.w;
+      } else {
+        gp[c][0] = g[chunk];
+        wp[c][0] = w[chunk];
+      }
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        gp[c][e] = k.wd != 0.f ? __builtin_fmaf(k.wd, wp[c][e], gp[c][e]) : gp[c][e];
+        sq = __builtin_fmaf(gp[c][e], gp[c][e], sq);
+      }
+    }
+  }
+  for (uint32_t off = LG >> 1; off >= 1; off >>= 1) sq += __shfl_xor(sq, (int)off, 64);
+  const float snew = *s + sq / (float)E;
+  const float step = k.lr / (sqrtf(snew) + k.eps);
+#pragma unroll
+  for (int c = 0; c < kAdagradMaxChunks; ++c) {
+    const uint32_t chunk = lig + (uint32_t)c * LG;
+    if (chunk < C) {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) wp[c][e] = __builtin_fmaf(-step, gp[c][e], wp[c][e]);
+      if constexpr (VEC == 4) *reinterpret_cast<float4*>(w + chunk * 4) = make_float4(wp[c][0], wp[c][1], wp[c][2], wp[c][3]);
+      else w[chunk] = wp[c][0];
+    }
+  }
+  if (lig == 0) *s = snew;
+}
+
+// the row-sparse update over the looked-up rows; LONG_SKIP: rows whose segment is longer than kLongSeg are left to the
+// long-row workgroups of the fused finish launch.  `first` blocks of the grid belong to other roles.
+template <int VEC, bool LONG_SKIP>
+__device__ __forceinline__ void adagrad_sparse_rows(float* __restrict__ table, float* __restrict__ sum, int32_t E, uint32_t C,
+                                                    const int32_t* __restrict__ unique_rows, const float* __restrict__ grad_rows,
+                                                    const int32_t* __restrict__ n_unique, const AdagradK& k, uint32_t LG,
+                                                    int64_t table_rows, const int32_t* __restrict__ seg, uint32_t first) {
+  const uint32_t U = (uint32_t)*n_unique;
+  const uint32_t gthread = (blockIdx.x - first) * blockDim.x + threadIdx.x;
+  const uint32_t lig = gthread % LG;
+  const uint32_t ngroups = (gridDim.x - first) * blockDim.x / LG;
+  for (uint32_t u = gthread / LG; u < U; u += ngroups) {
+    const int64_t row = unique_rows[u];
+    if (row >= table_rows) continue;                   // routing pad (multi-GPU fixed-capacity buckets)
+    if (LONG_SKIP && seg[u + 1] - seg[u] > kLongSeg) continue;   // finished and applied by the long-row blocks
+    adagrad_row<VEC>(table + row * E, grad_rows + (int64_t)u * E, sum + row, E, C, LG, lig, k);
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void adagrad_sparse_kernel(float* __restrict__ table, float* __restrict__ sum, int32_t E, uint32_t C,
+                                                                 const int32_t* __restrict__ unique_rows,
+                                                                 const float* __restrict__ grad_rows, const int32_t* __restrict__ n_unique,
+                                                                 AdagradK k0, uint32_t LG, int64_t table_rows) {
+  const AdagradK k = adagrad_resolve(k0);
+  adagrad_sparse_rows<VEC, false>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, nullptr, 0);
+}
+
+// dense gradient mode: every row of the [R, E] store
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void adagrad_dense_kernel(float* __restrict__ table, float* __restrict__ sum,
+                                                                const float* __restrict__ grad, int64_t R, int32_t E, uint32_t C,
+                                                                AdagradK k0, uint32_t LG) {
+  const AdagradK k = adagrad_resolve(k0);
+  const uint64_t gthread = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lig = (uint32_t)(gthread % LG);
+  const uint64_t ngroups = (uint64_t)gridDim.x * blockDim.x / LG;
+  for (uint64_t r = gthread / LG; r < (uint64_t)R; r += ngroups)
+    adagrad_row<VEC>(table + (int64_t)r * E, grad + (int64_t)r * E, sum + r, E, C, LG, lig, k);
+}
+
+// tower Adam (blocks [0, nd), as adam_fused_kernel) + the table's row-wise Adagrad in ONE launch, two hyper-parameter sets.
+// LONG (TT_GRAD_DEFER_FINISH): blocks [nd, nd + nlb) finish a long row's gradient as seg_long_finish_kernel does (into
+// grad_rows and a copy in LDS); once all E columns exist, the block's first LG lanes apply adagrad_row to that row from the
+// LDS copy -- the same values and the same reduction order as the row blocks, so the result equals the separate entries.
+template <int VEC, bool LONG>
+__global__ __launch_bounds__(kThreads) void adam_adagrad_fused_kernel(AdamFusedArgs a, AdamK ak0, float* __restrict__ table,
+                                                                     float* __restrict__ sum, int32_t E, uint32_t C,
+                                                                     const int32_t* __restrict__ unique_rows, float* __restrict__ grad_rows,
+                                                                     const int32_t* __restrict__ n_unique, AdagradK gk0, uint32_t LG,
+                                                                     int64_t table_rows, const int32_t* __restrict__ seg, GradWs ws, int nlb) {
+  const int nd = a.blk0[a.n];
+  if ((int)blockIdx.x < nd) {
+    const AdamK k = adam_resolve(ak0);
+    int ti = 0;
+    for (int i = 1; i < a.n; ++i)
+      if ((int)blockIdx.x >= a.blk0[i]) ti = i;
+    const tt_adam_tensor t = a.t[ti];
+    const int64_t nb = a.blk0[ti + 1] - a.blk0[ti];
+    const int64_t stride = nb * blockDim.x;
+    for (int64_t i = (int64_t)((int)blockIdx.x - a.blk0[ti]) * blockDim.x + threadIdx.x; i < t.n; i += stride) {
+      float pp = t.p[i], mm = t.m[i], vv = t.v[i];
+      adam1(pp, t.g[i], mm, vv, k);
+      t.p[i] = pp; t.m[i] = mm; t.v[i] = vv;
+    }
+    return;
+  }
+  const AdagradK k = adagrad_resolve(gk0);
+  const int first = nd + (LONG ? nlb : 0);
+  if (LONG && (int)blockIdx.x < first) {
+    __shared__ float part[kFinishMaxFloats];
+    __shared__ __attribute__((aligned(16))) float rowg[kFinishMaxFloats / 4];   // E <= kFinishMaxFloats * LG / kThreads <= 1024
+    long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x - nd, (uint32_t)nlb, part, [&](int32_t u, int32_t col, float tot) {
+      grad_rows[(int64_t)u * E + col] = tot;
+      rowg[col] = tot;
+    }, [&](int32_t u) {
+      const int64_t row = unique_rows[u];
+      if (threadIdx.x < LG && row < table_rows) adagrad_row<VEC>(table + row * E, rowg, sum + row, E, C, LG, threadIdx.x, k);
+    });
+    return;
+  }
+  adagrad_sparse_rows<VEC, LONG>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, seg, (uint32_t)first);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2696,6 +2850,145 @@ int tt_adam_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_
   return adam_fused_impl(ctx, tensors, n_tensors, table, m, v, table_rows, E, unique_rows, grad_rows, n_unique, M, seg_offsets,
                          grad_workspace, grad_workspace_bytes, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, stream,
                          "tt_adam_fused_step_finish");
+}
+
+// ---- row-wise Adagrad ----
+static AdagradK make_adagrad(float lr, float eps, float wd, const float* dev) {
+  AdagradK k;
+  k.lr = lr; k.eps = eps; k.wd = wd;
+  k.dev = dev;
+  return k;
+}
+
+// the row mapping shared by the row-wise Adagrad entries; false (error set) when a lane would own more chunks than it holds
+static bool adagrad_mapping(const char* who, int32_t E, bool vec4, uint32_t* C, uint32_t* LG) {
+  *C = vec4 ? E / 4 : E;
+  *LG = pow2_at_least(*C) > 64 ? 64 : pow2_at_least(*C);
+  if (*C > (uint32_t)kAdagradMaxChunks * *LG) {
+    tt_set_error("%s: E=%d too wide (max %d, or %d when E %% 4 != 0)", who, E, kAdagradMaxChunks * 64 * 4, kAdagradMaxChunks * 64);
+    return false;
+  }
+  return true;
+}
+
+static int flush_before_optimiser(tt_ctx* ctx, tt_stream stream) {
+  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
+  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
+    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
+  return TT_OK;
+}
+
+int tt_rowwise_adagrad_sparse_step(tt_ctx* ctx, float* table, float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows,
+                                   const float* grad_rows, const int32_t* n_unique, int64_t M, float lr, float eps, float weight_decay,
+                                   const float* hparams_dev, tt_stream stream) {
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  TT_CHECK_ARG(ctx && table && sum, "tt_rowwise_adagrad_sparse_step: NULL state");
+  TT_CHECK_ARG(E >= 1 && M >= 0 && table_rows >= 1, "tt_rowwise_adagrad_sparse_step: bad E/M/table_rows");
+  if (M == 0) return TT_OK;
+  TT_CHECK_ARG(unique_rows && grad_rows && n_unique, "tt_rowwise_adagrad_sparse_step: NULL plan");
+  const AdagradK k = make_adagrad(lr, eps, weight_decay, hparams_dev);
+  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad_rows, 16);
+  uint32_t C, LG;
+  if (!adagrad_mapping("tt_rowwise_adagrad_sparse_step", E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int grid = grid_for(ctx, M * LG);
+  if (vec4) adagrad_sparse_kernel<4><<<grid, kThreads, 0, st>>>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows);
+  else adagrad_sparse_kernel<1><<<grid, kThreads, 0, st>>>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_rowwise_adagrad_dense_step(tt_ctx* ctx, float* table, float* sum, const float* grad, int64_t table_rows, int32_t E, float lr,
+                                  float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  TT_CHECK_ARG(ctx && table && sum && grad, "tt_rowwise_adagrad_dense_step: NULL state");
+  TT_CHECK_ARG(E >= 1 && table_rows >= 1, "tt_rowwise_adagrad_dense_step: bad E/table_rows");
+  const AdagradK k = make_adagrad(lr, eps, weight_decay, hparams_dev);
+  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad, 16);
+  uint32_t C, LG;
+  if (!adagrad_mapping("tt_rowwise_adagrad_dense_step", E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int grid = grid_for(ctx, table_rows * LG);
+  if (vec4) adagrad_dense_kernel<4><<<grid, kThreads, 0, st>>>(table, sum, grad, table_rows, E, C, k, LG);
+  else adagrad_dense_kernel<1><<<grid, kThreads, 0, st>>>(table, sum, grad, table_rows, E, C, k, LG);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+static int adam_adagrad_fused_impl(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, const float* hparams_dev, float* table, float* sum,
+                                   int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique,
+                                   int64_t M, const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes,
+                                   float table_lr, float table_eps, float table_weight_decay, const float* table_hparams_dev,
+                                   tt_stream stream, const char* who) {
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  TT_CHECK_ARG(ctx && tensors && table && sum && unique_rows && grad_rows && n_unique, "%s: NULL argument", who);
+  TT_CHECK_ARG(n_tensors >= 1 && n_tensors <= kAdamMulti, "%s: n_tensors=%d not in [1,%d]", who, n_tensors, kAdamMulti);
+  TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 1 && table_rows >= 1, "%s: bad step/E/M/table_rows", who);
+  AdamFusedArgs a{};
+  a.n = n_tensors;
+  int nd = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const tt_adam_tensor& t = tensors[i];
+    TT_CHECK_ARG(t.n >= 0 && (t.n == 0 || (t.p && t.g && t.m && t.v)), "%s: tensor %d has NULL pointers", who, i);
+    a.t[i] = t;
+    a.blk0[i] = nd;
+    int64_t nb = tt_cdiv(t.n > 0 ? t.n : 1, kThreads);
+    nd += (int)(nb > 64 ? 64 : nb);
+  }
+  a.blk0[n_tensors] = nd;
+  const AdamK ak = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
+  const AdagradK gk = make_adagrad(table_lr, table_eps, table_weight_decay, table_hparams_dev);
+  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad_rows, 16);
+  uint32_t C, LG;
+  if (!adagrad_mapping(who, E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (grad_workspace) {
+    // the reduction's deferred finish (tt_embed_grad_bwd with TT_GRAD_DEFER_FINISH) rides in this launch
+    TT_CHECK_ARG(seg_offsets, "%s: NULL seg_offsets", who);
+    if (grad_workspace_bytes < tt_embed_grad_workspace_bytes(M, E)) {
+      tt_set_error("%s: gradient workspace %zu < required %zu", who, grad_workspace_bytes, tt_embed_grad_workspace_bytes(M, E));
+      return TT_ERR_WORKSPACE;
+    }
+    if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
+      tt_set_error("%s: E=%d too wide for the long-row finish (max %d)", who, E, kFinishMaxFloats * (int)LG / kThreads);
+      return TT_ERR_UNSUPPORTED;
+    }
+    const GradLayout gl = grad_layout(reinterpret_cast<char*>(grad_workspace), M, E);
+    const int nlb = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);
+    const int grid = nd + nlb + grid_for(ctx, M * LG);
+    if (vec4) adam_adagrad_fused_kernel<4, true><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, seg_offsets, gl.ws, nlb);
+    else adam_adagrad_fused_kernel<1, true><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, seg_offsets, gl.ws, nlb);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+  }
+  const int grid = nd + grid_for(ctx, M * LG);
+  if (vec4) adam_adagrad_fused_kernel<4, false><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, nullptr, GradWs{}, 0);
+  else adam_adagrad_fused_kernel<1, false><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, nullptr, GradWs{}, 0);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_adam_rowwise_adagrad_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev, float* table,
+                                       float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows, const float* grad_rows,
+                                       const int32_t* n_unique, int64_t M, float table_lr, float table_eps, float table_weight_decay,
+                                       const float* table_hparams_dev, tt_stream stream) {
+  return adam_adagrad_fused_impl(ctx, tensors, n_tensors, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, table, sum, table_rows,
+                                 E, unique_rows, const_cast<float*>(grad_rows), n_unique, M, nullptr, nullptr, 0, table_lr, table_eps,
+                                 table_weight_decay, table_hparams_dev, stream, "tt_adam_rowwise_adagrad_fused_step");
+}
+
+int tt_adam_rowwise_adagrad_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr,
+                                              float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev,
+                                              float* table, float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows,
+                                              float* grad_rows, const int32_t* n_unique, int64_t M, const int32_t* seg_offsets,
+                                              void* grad_workspace, size_t grad_workspace_bytes, float table_lr, float table_eps,
+                                              float table_weight_decay, const float* table_hparams_dev, tt_stream stream) {
+  TT_CHECK_ARG(grad_workspace, "tt_adam_rowwise_adagrad_fused_step_finish: NULL gradient workspace");
+  return adam_adagrad_fused_impl(ctx, tensors, n_tensors, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, table, sum, table_rows,
+                                 E, unique_rows, grad_rows, n_unique, M, seg_offsets, grad_workspace, grad_workspace_bytes, table_lr,
+                                 table_eps, table_weight_decay, table_hparams_dev, stream, "tt_adam_rowwise_adagrad_fused_step_finish");
 }
 
 int tt_embed_grad_finish(tt_ctx* ctx, int32_t E, const int32_t* seg_offsets, int64_t M, float* out, void* workspace,

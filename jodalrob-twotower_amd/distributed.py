@@ -12,7 +12,7 @@ The reference is single-GPU (no collective anywhere: SURVEY.md §2.1); this is n
                gather their rows (tt_embed_lookup_fwd on the local shard), (5) all-to-all of the pooled
                rows back, un-permuted straight into the towers' MLP input buffers; the backward mirrors
                it: all-to-all of the row gradients to the owners, duplicate-row plan + segmented
-               reduction there, then the (sparse) Adam update on the local shard.
+               reduction there, then the (sparse) Adam or row-wise Adagrad update on the local shard.
   * towers   : dense weights replicated; gradients summed with one all-reduce per tower over the flat
                gradient buffer tt_tower_mlp_bwd fills (0.3 MB: latency-bound, a single call).
                BatchNorm statistics are per rank (as torch DDP without SyncBatchNorm).

@@ -306,11 +306,12 @@ class GraphedTrainStep:
             if store.weight is None or not store.optim_parameters():
                 continue
             st = opt._state_of(store)
+            keys = ("sum",) if "sum" in st else ("m", "v")                 # row-wise Adagrad: one [R] accumulator; Adam: two [R, E] moments
             rows = self._touched_rows(store) if store.grad_mode == "sparse" else None
-            if rows is None and 3 * store.weight.numel() * 4 > (8 << 30):
+            if rows is None and (store.weight.numel() + sum(st[k].numel() for k in keys)) * 4 > (8 << 30):
                 rows = torch.empty(0, dtype=torch.int64, device=store.weight.device)     # too large to copy whole: left as the warm-up leaves it
             pick = (lambda t: t[rows].clone()) if rows is not None else (lambda t: t.clone())
-            snap["stores"].append((store, rows, pick(store.weight), pick(st["m"]), pick(st["v"]), st["step"]))
+            snap["stores"].append((store, rows, pick(store.weight), {k: pick(st[k]) for k in keys}, st["step"]))
         snap["steps"] = [(st, st["step"].clone()) for st in opt.state.values() if "step" in st]
         return snap
 
@@ -328,12 +329,16 @@ class GraphedTrainStep:
                     st["exp_avg"].zero_(); st["exp_avg_sq"].zero_(); st["step"] = torch.tensor(0.0)
                 else:
                     st["exp_avg"].copy_(st0[0]); st["exp_avg_sq"].copy_(st0[1]); st["step"] = st0[2].clone()
-        for store, rows, w, m, v, step in snap["stores"]:
+        for store, rows, w, saved, step in snap["stores"]:
             st = opt._state_of(store)
             if rows is None:
-                store.weight.copy_(w); st["m"].copy_(m); st["v"].copy_(v)
+                store.weight.copy_(w)
+                for k, t in saved.items():
+                    st[k].copy_(t)
             elif rows.numel():
-                store.weight[rows] = w; st["m"][rows] = m; st["v"][rows] = v
+                store.weight[rows] = w
+                for k, t in saved.items():
+                    st[k][rows] = t
             st["step"] = step
         known = {id(st): val for st, val in snap["steps"]}
         for st in opt.state.values():
@@ -355,6 +360,9 @@ class GraphedTrainStep:
         # the optimiser) advance the bias corrections exactly as they do in an all-eager loop
         step = self.opt.peek_step() + 1 + ahead
         for gi, g in enumerate(self.opt.param_groups):
+            if g.get("table_optimizer", "adam") == "rowwise_adagrad":        # the row-wise Adagrad entries read [lr, eps, weight_decay]
+                host[gi * 8: gi * 8 + 3] = torch.tensor([float(g["lr"]), g["eps"], g["weight_decay"]])
+                continue
             hp = ops.adam_hparams(step, float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
             host[gi * 8: gi * 8 + 6] = torch.tensor(hp)
         host[ng * 8:].view(torch.int64).random_()

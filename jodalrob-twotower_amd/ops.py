@@ -342,6 +342,51 @@ def adam_fused(items, table, m, v, plan: DedupPlan, grad_rows, step, lr, b1, b2,
                                             lr, b1, b2, eps, wd, L.ptr(hp_dev), L.stream(dev)), "tt_adam_fused_step")
 
 
+# ---------------------------------------------------------------------------------------------- row-wise Adagrad (tables)
+# hp_dev: NULL or device floats [lr, eps, weight_decay] read instead of the host scalars (graph replay)
+def rowwise_adagrad_sparse(table, acc, plan: DedupPlan, grad_rows, lr, eps, wd, hp_dev=None):
+    """Row-wise Adagrad over the plan's rows of `table` [R, E]; acc: the [R] per-row accumulator."""
+    dev = table.device
+    embed_grad_finish(plan)
+    with _timed("tt_rowwise_adagrad_sparse_step"):
+        L.check(L.load().tt_rowwise_adagrad_sparse_step(L.ctx(dev), L.ptr(table), L.ptr(acc), table.shape[0], table.shape[1],
+                                                        L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M,
+                                                        lr, eps, wd, L.ptr(hp_dev), L.stream(dev)), "tt_rowwise_adagrad_sparse_step")
+
+
+def rowwise_adagrad_dense(table, acc, grad, lr, eps, wd, hp_dev=None):
+    """Row-wise Adagrad over every row of `table` [R, E] with a dense [R, E] gradient."""
+    dev = table.device
+    with _timed("tt_rowwise_adagrad_dense_step"):
+        L.check(L.load().tt_rowwise_adagrad_dense_step(L.ctx(dev), L.ptr(table), L.ptr(acc), L.ptr(grad), table.shape[0], table.shape[1],
+                                                       lr, eps, wd, L.ptr(hp_dev), L.stream(dev)), "tt_rowwise_adagrad_dense_step")
+
+
+def adam_rowwise_adagrad_fused(items, step, lr, b1, b2, eps, wd, hp_dev, table, acc, plan: DedupPlan, grad_rows, t_lr, t_eps, t_wd,
+                               t_hp_dev=None):
+    """adam_multi(items) with the towers' hyper-parameters + rowwise_adagrad_sparse(table rows) with the table's, one launch."""
+    dev = table.device
+    arr = (L.AdamTensor * len(items))()
+    for i, (p, g, mm, vv) in enumerate(items):
+        arr[i] = L.AdamTensor(p.data_ptr(), g.data_ptr(), mm.data_ptr(), vv.data_ptr(), p.numel())
+    if plan.finish_deferred is not None:
+        if plan.finish_deferred.data_ptr() != grad_rows.data_ptr():
+            raise RuntimeError("adam_rowwise_adagrad_fused: the plan's deferred gradient is not the one handed to the optimiser")
+        ws, E = plan.grad_ws
+        with _timed("tt_adam_rowwise_adagrad_fused_step"):
+            L.check(L.load().tt_adam_rowwise_adagrad_fused_step_finish(
+                L.ctx(dev), arr, len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.ptr(table), L.ptr(acc), table.shape[0],
+                table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M, L.ptr(plan.seg_offsets),
+                L.ptr(ws), ws.numel(), t_lr, t_eps, t_wd, L.ptr(t_hp_dev), L.stream(dev)), "tt_adam_rowwise_adagrad_fused_step_finish")
+        plan.finish_deferred = None
+        return
+    with _timed("tt_adam_rowwise_adagrad_fused_step"):
+        L.check(L.load().tt_adam_rowwise_adagrad_fused_step(
+            L.ctx(dev), arr, len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.ptr(table), L.ptr(acc), table.shape[0],
+            table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M, t_lr, t_eps, t_wd,
+            L.ptr(t_hp_dev), L.stream(dev)), "tt_adam_rowwise_adagrad_fused_step")
+
+
 # ---------------------------------------------------------------------------------------------- tower MLP
 def _fill(arr, tensors):
     for i, t in enumerate(tensors):

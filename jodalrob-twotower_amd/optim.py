@@ -13,6 +13,16 @@ train_task.parameters(), ...)` (works with LambdaLR warm-up: lr is read from par
 State layout matches torch.optim.Adam ('step', 'exp_avg', 'exp_avg_sq' per parameter; for table
 parameters these are views into store-level buffers), so optimizer.state_dict() round-trips through
 the reference's checkpoint format (scripts/train.py:506-511).
+
+Row-wise Adagrad for the tables (FBGEMM's EXACT_ROWWISE_ADAGRAD; for_task(table_optimizer="rowwise_adagrad")):
+the table parameters sit in a parameter group of their own carrying table_optimizer="rowwise_adagrad", and
+their state is {'step', 'sum'} -- 'sum' a [num_embeddings] view into one store-level [R] f32 accumulator, so
+the optimiser state is R floats instead of Adam's 2 x R x E.  Per looked-up row:
+    g' = g + weight_decay * w;   sum += mean_j(g'_j^2);   w -= lr / (sqrt(sum) + eps) * g'
+  * sparse grad mode : tt_rowwise_adagrad_sparse_step over the step's rows (exactly the dense update when
+                       weight_decay = 0: a row with no gradient does not move)
+  * dense grad mode  : tt_rowwise_adagrad_dense_step over all R rows
+  * tower Adam + the looked-up rows: one tt_adam_rowwise_adagrad_fused_step launch
 """
 from __future__ import annotations
 
@@ -22,6 +32,13 @@ import torch
 
 from . import ops
 from .cat_embed import EmbeddingStore
+
+
+TABLE_OPTIMIZERS = ("adam", "rowwise_adagrad")
+
+
+def _kind(group) -> str:
+    return group.get("table_optimizer", "adam")
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -35,14 +52,57 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_cache = None         # current_step() as of the last eager change (peek_step)
 
     @classmethod
-    def for_task(cls, task, **kw):
-        """Collect the embedding stores of a TwoTowerTrainTask / TwoTowerModel / tower automatically."""
-        return cls(task.parameters(), stores=find_stores(task), **kw)
+    def for_task(cls, task, table_optimizer: str = "adam", table_lr=None, table_eps: float = 1e-8, table_weight_decay=None, **kw):
+        """Collect the embedding stores of a TwoTowerTrainTask / TwoTowerModel / tower automatically.
+
+        table_optimizer="rowwise_adagrad": the tables go in a parameter group of their own (table_optimizer="rowwise_adagrad",
+        lr=table_lr, eps=table_eps, weight_decay=table_weight_decay; None inherits the towers' value), updated by row-wise
+        Adagrad; the towers keep Adam.  A scheduler such as LambdaLR scales both groups' lr."""
+        if table_optimizer not in TABLE_OPTIMIZERS:
+            raise ValueError(f"table_optimizer must be one of {TABLE_OPTIMIZERS}, got {table_optimizer!r}")
+        stores = find_stores(task)
+        if table_optimizer == "adam":
+            if table_lr is not None or table_weight_decay is not None:
+                raise ValueError("table_lr / table_weight_decay apply to table_optimizer='rowwise_adagrad' only")
+            return cls(task.parameters(), stores=stores, **kw)
+        table_ids = {id(p) for s in stores for p in s.optim_parameters()}
+        params = list(task.parameters())
+        towers = [p for p in params if id(p) not in table_ids]
+        tables = [p for p in params if id(p) in table_ids]
+        if not tables:
+            raise ValueError("table_optimizer='rowwise_adagrad': the task has no embedding tables")
+        lr = kw.get("lr", 1e-3)
+        table_group = {"params": tables, "table_optimizer": "rowwise_adagrad", "lr": lr if table_lr is None else table_lr,
+                       "eps": table_eps, "weight_decay": kw.get("weight_decay", 0.0) if table_weight_decay is None else table_weight_decay}
+        groups = ([{"params": towers}] if towers else []) + [table_group]
+        return cls(groups, stores=stores, **kw)
+
+    def add_param_group(self, param_group):
+        kind = param_group.get("table_optimizer", "adam")
+        if kind not in TABLE_OPTIMIZERS:
+            raise ValueError(f"table_optimizer must be one of {TABLE_OPTIMIZERS}, got {kind!r}")
+        if kind == "rowwise_adagrad":
+            lr, eps, wd = (param_group.get(k, self.defaults[k]) for k in ("lr", "eps", "weight_decay"))
+            if not (lr >= 0 and eps > 0 and wd >= 0):
+                raise ValueError(f"invalid row-wise Adagrad hyper-parameters (lr={lr}, eps={eps}, weight_decay={wd}): "
+                                 "lr >= 0, eps > 0, weight_decay >= 0")
+        super().add_param_group(param_group)
 
     # ---- store-level state --------------------------------------------------------------------------
+    def _group_of_store(self, store: EmbeddingStore):
+        members = store.optim_parameters()
+        if members:
+            for group in self.param_groups:
+                if any(members[0] is p for p in group["params"]):
+                    return group
+        return None
+
     def _state_of(self, store: EmbeddingStore) -> dict:
+        group = self._group_of_store(store)
+        if group is not None and _kind(group) == "rowwise_adagrad":
+            return self._rowwise_state_of(store)
         st = self._store_state.get(id(store))
-        if st is None or st["m"].shape != store.weight.shape or st["m"].device != store.weight.device:
+        if st is None or "m" not in st or st["m"].shape != store.weight.shape or st["m"].device != store.weight.device:
             st = {"m": torch.zeros_like(store.weight), "v": torch.zeros_like(store.weight), "step": 0}
             self._store_state[id(store)] = st
             shard = getattr(store, "shard_param", None)
@@ -55,6 +115,22 @@ class FusedAdam(torch.optim.Optimizer):
                     p = emb.embeddings[k].weight
                     self.state[p] = {"step": torch.tensor(0.0), "exp_avg": st["m"][off:off + n],
                                      "exp_avg_sq": st["v"][off:off + n]}
+                    off += n
+        return st
+
+    def _rowwise_state_of(self, store: EmbeddingStore) -> dict:
+        st = self._store_state.get(id(store))
+        if st is None or "sum" not in st or st["sum"].shape[0] != store.weight.shape[0] or st["sum"].device != store.weight.device:
+            st = {"sum": torch.zeros(store.weight.shape[0], dtype=torch.float32, device=store.weight.device), "step": 0}
+            self._store_state[id(store)] = st
+            shard = getattr(store, "shard_param", None)
+            if shard is not None:                            # sharded store: one parameter = the local rows, one [local_rows] buffer
+                self.state[shard] = {"step": torch.tensor(0.0), "sum": st["sum"]}
+            for emb in ([] if shard is not None else store.members):   # per-parameter [num_embeddings] views
+                off = emb.row_base
+                for k in emb.keys:
+                    n = emb.vocab_sizes[k]
+                    self.state[emb.embeddings[k].weight] = {"step": torch.tensor(0.0), "sum": st["sum"][off:off + n]}
                     off += n
         return st
 
@@ -83,6 +159,8 @@ class FusedAdam(torch.optim.Optimizer):
             for p in group["params"]:
                 if id(p) in table_ids or p.grad is None:
                     continue
+                if _kind(group) != "adam":
+                    raise ValueError("a table_optimizer='rowwise_adagrad' parameter group holds embedding-table parameters only")
                 st = self.state[p]
                 if not st:
                     st["step"] = torch.tensor(0.0)
@@ -97,6 +175,18 @@ class FusedAdam(torch.optim.Optimizer):
                 by_step.setdefault(it[4], []).append(it[:4])
             for s_no, its in by_step.items():
                 fuse = self._fusable_store(group, s_no, len(its), len(by_step))
+                if fuse is not None and len(fuse) == 3:   # tower Adam + the row-wise Adagrad of another group's table: one launch
+                    store, st, tgroup = fuse
+                    plan, grad_rows = store.sparse_grad
+                    st["step"] += 1
+                    thp = None if self._hp_dev is None else self._hp_dev[self.param_groups.index(tgroup)]
+                    ops.adam_rowwise_adagrad_fused(its, s_no, group["lr"], b1, b2, group["eps"], group["weight_decay"], hp,
+                                                   store.weight, st["sum"], plan, grad_rows, tgroup["lr"], tgroup["eps"],
+                                                   tgroup["weight_decay"], thp)
+                    store.sparse_grad = None
+                    for p in store.optim_parameters():
+                        self.state[p]["step"] = torch.tensor(float(st["step"]))
+                    continue
                 if fuse is not None:      # tower weights + looked-up table rows: one launch
                     store, st = fuse
                     plan, grad_rows = store.sparse_grad
@@ -119,6 +209,23 @@ class FusedAdam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             hp = None if self._hp_dev is None else self._hp_dev[self.param_groups.index(group)]
             st = self._state_of(store)
+            if _kind(group) == "rowwise_adagrad":
+                if store.grad_mode == "sparse":
+                    if store.sparse_grad is None:
+                        continue
+                    plan, grad_rows = store.sparse_grad
+                    st["step"] += 1
+                    ops.rowwise_adagrad_sparse(store.weight, st["sum"], plan, grad_rows, group["lr"], group["eps"],
+                                               group["weight_decay"], hp)
+                    store.sparse_grad = None
+                else:
+                    if store.grad is None or any(p.grad is None for p in members):
+                        continue
+                    st["step"] += 1
+                    ops.rowwise_adagrad_dense(store.weight, st["sum"], store.grad, group["lr"], group["eps"], group["weight_decay"], hp)
+                for p in members:
+                    self.state[p]["step"] = torch.tensor(float(st["step"]))
+                continue
             if store.grad_mode == "sparse":
                 if store.sparse_grad is None:
                     continue
@@ -138,7 +245,9 @@ class FusedAdam(torch.optim.Optimizer):
         return loss
 
     def _fusable_store(self, group, s_no: int, n_items: int, n_buckets: int):
-        """The one sparse-gradient store of `group` whose next step number is s_no (else None)."""
+        """The one sparse-gradient store of `group` whose next step number is s_no -> (store, state); when `group` has no
+        store, the one row-wise Adagrad store of another group with a pending sparse gradient -> (store, state, its group);
+        else None."""
         if n_buckets != 1 or not (1 <= n_items <= 32):
             return None
         cands = []
@@ -146,7 +255,15 @@ class FusedAdam(torch.optim.Optimizer):
             members = store.optim_parameters()
             if members and any(members[0] is p for p in group["params"]):
                 cands.append(store)
-        if len(cands) != 1:
+        if not cands and _kind(group) == "adam":
+            rw = [(s, g) for s in self._stores for g in [self._group_of_store(s)] if g is not None and _kind(g) == "rowwise_adagrad"]
+            if len(rw) != 1:
+                return None
+            store, tgroup = rw[0]
+            if store.grad_mode != "sparse" or store.sparse_grad is None or store.sparse_grad[0].M < 1:
+                return None
+            return store, self._state_of(store), tgroup
+        if len(cands) != 1 or _kind(group) != "adam":
             return None
         store = cands[0]
         if store.grad_mode != "sparse" or store.sparse_grad is None or store.sparse_grad[0].M < 1:
@@ -193,11 +310,56 @@ class FusedAdam(torch.optim.Optimizer):
         for store in self._stores:
             store.sparse_grad = None
 
+    def _check_table_state(self, state_dict):
+        """Refuses a state whose table optimiser differs from this one's (an Adam state into a row-wise group, or the reverse)."""
+        saved = state_dict.get("param_groups", [])
+        if len(saved) != len(self.param_groups):
+            kinds, skinds = {_kind(g) for g in self.param_groups}, {g.get("table_optimizer", "adam") for g in saved}
+            if kinds != skinds:
+                raise ValueError(f"load_state_dict: the state was saved with table_optimizer {sorted(skinds)}, this optimiser uses "
+                                 f"{sorted(kinds)}")
+            return                                                   # torch's own check reports it
+        table_ids = self._table_param_ids()
+        for group, sg in zip(self.param_groups, saved):
+            kind, skind = _kind(group), sg.get("table_optimizer", "adam")
+            if kind != skind:
+                raise ValueError(f"load_state_dict: the state was saved with table_optimizer={skind!r}, this optimiser's group uses "
+                                 f"{kind!r}")
+            for p, idx in zip(group["params"], sg["params"]):
+                s = state_dict["state"].get(idx)
+                if id(p) not in table_ids or not s:
+                    continue
+                if (kind == "rowwise_adagrad" and "exp_avg" in s) or (kind == "adam" and "sum" in s):
+                    raise ValueError(f"load_state_dict: a table parameter's saved state {sorted(s)} does not belong to "
+                                     f"table_optimizer={kind!r}")
+
+    def _load_rowwise(self, store):
+        """After torch's load: copy the loaded per-parameter 'sum' into fresh store-level buffers (the kernels update those)."""
+        shard = getattr(store, "shard_param", None)
+        params = [shard] if shard is not None else [emb.embeddings[k].weight for emb in store.members for k in emb.keys]
+        loaded = {id(p): dict(self.state[p]) for p in params if p in self.state and "sum" in self.state[p]}
+        self._store_state.pop(id(store), None)
+        if not loaded:
+            return
+        st = self._rowwise_state_of(store)
+        for p in params:
+            old = loaded.get(id(p))
+            if old is not None:
+                self.state[p]["sum"].copy_(old["sum"].to(self.state[p]["sum"].device))
+                st["step"] = max(st["step"], int(float(old["step"])))
+        for p in params:
+            self.state[p]["step"] = torch.tensor(float(st["step"]))
+
     def load_state_dict(self, state_dict):
+        self._check_table_state(state_dict)
         super().load_state_dict(state_dict)
         self._step_cache = None
         # re-point the table parameters' moments at store-level buffers (the kernels update those; self.state holds views)
         for store in self._stores:
+            group = self._group_of_store(store)
+            if group is not None and _kind(group) == "rowwise_adagrad":
+                self._load_rowwise(store)
+                continue
             shard = getattr(store, "shard_param", None)
             if shard is not None:
                 # row-wise sharded store: ONE parameter = this rank's rows, its moments are the store-level buffers themselves

@@ -101,6 +101,9 @@ def main():
     ap.add_argument("--hidden", default="128,64", help="tower_hidden_dims (the reference driver trains 512,256: scripts/train.py:106)")
     ap.add_argument("--final-dim", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--table-optimizer", choices=["adam", "rowwise_adagrad"], default="adam",
+                    help="optimiser of the embedding tables (the towers keep Adam); rowwise_adagrad keeps one float per table row")
+    ap.add_argument("--table-lr", type=float, default=None, help="learning rate of the tables under rowwise_adagrad (default: the towers' learning rate)")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
     a = ap.parse_args()
     config = {"batch_size": a.batch_size, "test_split": 0.2, "shuffle_seed": 42, "pair_limit": a.pairs,
@@ -140,7 +143,8 @@ def main():
                                              final_embedding_dim=config["final_embedding_dim"], dropout_rate=config["dropout_rate"],
                                              temperature=config["temperature"], loss_type=config["loss_type"], device=device,
                                              **(dict(embedding_grad="sparse", score_dtype="bf16", mlp_dtype="bf16") if a.fast else {}))
-    optimizer = FusedAdam.for_task(train_task, lr=config["learning_rate"], weight_decay=config["weight_decay"])
+    optimizer = FusedAdam.for_task(train_task, lr=config["learning_rate"], weight_decay=config["weight_decay"],
+                                   table_optimizer=a.table_optimizer, table_lr=a.table_lr)
     warmup_steps = max(1, int(len(train_loader) * config["warmup_ratio"]))
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda s: s / warmup_steps if s < warmup_steps else 1.0, last_epoch=-1)
     start_epoch = 0
