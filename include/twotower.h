@@ -656,6 +656,24 @@ int tt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const v
 int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
                          const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
                          size_t workspace_bytes, tt_stream stream);
+/* Retrieval with per-query exclusion lists: tt_retrieve_topk_bf16 / _f32 with two more arguments after `rank`.
+ *   excl_offsets int64 [nQ + 1] (excl_offsets[0] = 0, non-decreasing) and excl_rows int32 [excl_offsets[nQ]]: query q's
+ *   exclusion set E_q is excl_rows[excl_offsets[q] .. excl_offsets[q+1]), ASCENDING; duplicates are allowed and rows outside
+ *   [0, nC) match nothing.  Both pointers are required (8- and 4-byte aligned); a list may be empty.
+ *   top-k: the k best rows of {c not in E_q} in the same order; slots beyond the eligible rows are -inf / -1.
+ *   rank:  #{c not in E_q : s > s_p} + #{c not in E_q, c < p : s == s_p}; p never counts against itself, so whether p is in
+ *          E_q makes no difference; -1 where p is outside [0, nC).
+ * With every list empty the results are bitwise those of the plain entry; they are bitwise identical across runs and split
+ * counts.  Same workspace (tt_retrieve_workspace_bytes), launches and graph capture rules as the plain entries.  A bad argument
+ * returns TT_ERR_INVALID_ARG and launches nothing. */
+int tt_excl_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, void* workspace, size_t workspace_bytes,
+                               tt_stream stream);
+int tt_excl_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, void* workspace, size_t workspace_bytes,
+                              tt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Generic Linear used by the one-off feature projection -- replaces FeatureProjector.forward

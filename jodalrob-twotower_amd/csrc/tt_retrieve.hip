@@ -15,6 +15,12 @@
 // Order: value descending, then lower catalogue index (tt_topk_rows).  Rank: #{c : s > s_p} + #{c < p : s == s_p}
 // (tt_diag_rank_rows).  Every score comes from one instruction sequence whichever wave or split computes it, and the selection
 // is exact under a total order, so results are bitwise identical across runs and split counts.
+//
+// Exclusion lists (tt_excl_retrieve_topk_*: the sweep's EXCL = true instantiation): query q's ascending CSR list of catalogue
+// rows is removed before the k-th-best filter and the rank counts see them.  Each lane holds a cursor into its query's list
+// (binary-searched to the split's first row) and the next excluded row in a register: a tile without excluded rows costs one
+// compare and one __any; otherwise the wave walks the tile's entries and sets the matching scores to -inf, which neither the
+// filter (threshold >= -inf, strict compare) nor the rank counts (strict compare against a finite s_p) ever take.
 #include "tt_score_bf16.h"
 
 #include <math.h>
@@ -121,6 +127,8 @@ struct RetArgs {
   float* vals;                // [nQ][k] out
   int64_t* idx;               // [nQ][k] out
   int32_t* rank;              // [nQ] out or NULL
+  const int64_t* excl_off;    // [nQ + 1] CSR offsets of the exclusion lists (EXCL sweep only)
+  const int32_t* excl_rows;   // [excl_off[nQ]] ascending catalogue rows per query
 };
 
 __device__ __forceinline__ int64_t positive_of(const RetArgs& a, int64_t q) { return a.pos64 ? a.pos64[q] : (int64_t)a.pos32[q]; }
@@ -150,7 +158,7 @@ __global__ __launch_bounds__(64) void retrieve_pos_kernel(Tile tile, RetArgs a) 
 }
 
 // ---- sweep ------------------------------------------------------------------------------------------------------------------
-template <class Tile>
+template <class Tile, bool EXCL>
 __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
   extern __shared__ uint32_t ret_lds[];
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -174,6 +182,25 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
     sp = a.sp[q];
     tp = p >= 0 ? p / 32 : -1;
     sp_lo = below(sp);
+  }
+  // exclusion cursor: e indexes query q's list, nxt is the excluded row it points at (INT32_MAX: none left in this split)
+  int64_t e = 0, ee = 0;
+  int32_t nxt = INT32_MAX;
+  if (EXCL && qok) {
+    const int64_t tot = a.excl_off[a.nQ];
+    int64_t lo = a.excl_off[q], hi = a.excl_off[q + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi < tot ? hi : tot;
+    hi = hi > lo ? hi : lo;
+    ee = hi;
+    const int64_t first = 32 * tb;                              // first entry >= the split's first row
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)a.excl_rows[mid] < first) lo = mid + 1;
+      else hi = mid;
+    }
+    e = lo;
+    nxt = e < ee ? a.excl_rows[e] : INT32_MAX;
   }
   int rcnt = 0;
   float thr = -INFINITY;                                        // the query's k-th best so far (both lanes of a query agree)
@@ -252,6 +279,22 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (r0 + rowmap(r, h) >= a.nC) acc[r] = -INFINITY;
+    }
+    if (EXCL) {                                                 // nxt >= r0 here: every entry below the tile is consumed
+      const int64_t lim = r0 + 32;
+      if (__any(nxt < lim)) {
+        uint32_t xm = 0;                                        // bit j: row r0 + j is excluded for this lane's query
+        do {                                                    // wave-uniform: ends with every lane past the tile
+          if (nxt < lim) {
+            xm |= 1u << (uint32_t)(nxt - r0);
+            ++e;
+            nxt = e < ee ? a.excl_rows[e] : INT32_MAX;
+          }
+        } while (__any(nxt < lim));
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if ((xm >> rowmap(r, h)) & 1u) acc[r] = -INFINITY;
+      }
     }
     if (want_rank) {
       if (!__any(t == tp)) {                                    // whole tile before (ties count) or after (they do not) p
@@ -411,7 +454,8 @@ bool ret_shape_ok(int64_t nQ, int64_t nC, int D, int k) {
 
 template <class Tile>
 int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k, const void* positives,
-               int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace, hipStream_t st) {
+               int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
+               const int32_t* excl_rows, void* workspace, hipStream_t st) {
   const int64_t nT = tt_cdiv(nC, 32), nQt = tt_cdiv(nQ, 32);
   const int cap = ret_max_splits(nC);
   int64_t S;
@@ -440,12 +484,16 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   a.vals = vals;
   a.idx = idx;
   a.rank = positives ? rank : nullptr;
+  a.excl_off = excl_off;
+  a.excl_rows = excl_rows;
   if (positives) {
     retrieve_pos_kernel<Tile><<<(unsigned)nQt, 64, 0, st>>>(tile, a);
     TT_LAUNCH_CHECK();
   }
   const size_t lds = (size_t)kRetWaves * (k + kRetCap) * 32 * 8;
-  retrieve_sweep_kernel<Tile><<<dim3((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S), kRetWaves * 64, lds, st>>>(tile, a);
+  const dim3 grid((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S);
+  if (excl_off) retrieve_sweep_kernel<Tile, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  else retrieve_sweep_kernel<Tile, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
   TT_LAUNCH_CHECK();
   const int64_t n = S * k;
   if (n <= 128) retrieve_merge_kernel<2><<<(unsigned)nQ, 64, 0, st>>>(a);
@@ -466,6 +514,44 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   TT_CHECK_ARG(workspace_bytes >= ret_layout(nQ, nC, k).total, NAME ": workspace of %zu bytes < %zu (tt_retrieve_workspace_bytes)", \
                workspace_bytes, ret_layout(nQ, nC, k).total)
 
+#define TT_RET_CHECK_BF16(NAME)                                                                                                   \
+  TT_CHECK_ARG(Q_packed && C_packed && tt_aligned(Q_packed, 16) && tt_aligned(C_packed, 16),                                     \
+               NAME ": packed images NULL or not 16-byte aligned")
+
+#define TT_RET_CHECK_EXCL(NAME)                                                                                                   \
+  TT_CHECK_ARG(excl_offsets != nullptr && tt_aligned(excl_offsets, 8), NAME ": excl_offsets NULL or not 8-byte aligned");       \
+  TT_CHECK_ARG(excl_rows != nullptr && tt_aligned(excl_rows, 4), NAME ": excl_rows NULL or not 4-byte aligned")
+
+// (arguments checked by the caller; excl_off == NULL launches the plain sweep)
+int ret_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D, int32_t k,
+             const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
+             const int32_t* excl_rows, void* workspace, hipStream_t st) {
+  const int Dp = padded_d(D);
+#define TT_RET_BF16(KS)                                                                                                 \
+  do {                                                                                                                  \
+    TileBf16<KS> tile{};                                                                                                \
+    tile.q_rows = view(Q_packed, nQ, D).rows;                                                                           \
+    tile.c_rows = view(C_packed, nC, D).rows;                                                                           \
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st); \
+  } while (0)
+  if (Dp == 32) TT_RET_BF16(2);
+  if (Dp == 64) TT_RET_BF16(4);
+  if (Dp == 128) TT_RET_BF16(8);
+  TT_RET_BF16(16);
+#undef TT_RET_BF16
+}
+
+int ret_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
+            const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
+            const int32_t* excl_rows, void* workspace, hipStream_t st) {
+  if (D % 4 == 0 && tt_aligned(Q, 16) && tt_aligned(Cm, 16)) {
+    TileF32<true> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st);
+  }
+  TileF32<false> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
+  return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -479,22 +565,9 @@ int tt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const v
                           const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, void* workspace,
                           size_t workspace_bytes, tt_stream stream) {
   TT_RET_CHECK_COMMON("tt_retrieve_topk_bf16");
-  TT_CHECK_ARG(Q_packed && C_packed && tt_aligned(Q_packed, 16) && tt_aligned(C_packed, 16),
-               "tt_retrieve_topk_bf16: packed images NULL or not 16-byte aligned");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Dp = padded_d(D);
-#define TT_RET_BF16(KS)                                                                                                 \
-  do {                                                                                                                  \
-    TileBf16<KS> tile{};                                                                                                \
-    tile.q_rows = view(Q_packed, nQ, D).rows;                                                                           \
-    tile.c_rows = view(C_packed, nC, D).rows;                                                                           \
-    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st); \
-  } while (0)
-  if (Dp == 32) TT_RET_BF16(2);
-  if (Dp == 64) TT_RET_BF16(4);
-  if (Dp == 128) TT_RET_BF16(8);
-  TT_RET_BF16(16);
-#undef TT_RET_BF16
+  TT_RET_CHECK_BF16("tt_retrieve_topk_bf16");
+  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, workspace,
+                  reinterpret_cast<hipStream_t>(stream));
 }
 
 int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
@@ -502,13 +575,30 @@ int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* C
                          size_t workspace_bytes, tt_stream stream) {
   TT_RET_CHECK_COMMON("tt_retrieve_topk_f32");
   TT_CHECK_ARG(Q && Cm, "tt_retrieve_topk_f32: NULL embeddings");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (D % 4 == 0 && tt_aligned(Q, 16) && tt_aligned(Cm, 16)) {
-    TileF32<true> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
-    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st);
-  }
-  TileF32<false> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
-  return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, workspace, st);
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, workspace,
+                 reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_excl_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, void* workspace, size_t workspace_bytes,
+                               tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_excl_retrieve_topk_bf16");
+  TT_RET_CHECK_BF16("tt_excl_retrieve_topk_bf16");
+  TT_RET_CHECK_EXCL("tt_excl_retrieve_topk_bf16");
+  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
+                  workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_excl_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, void* workspace, size_t workspace_bytes,
+                              tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_excl_retrieve_topk_f32");
+  TT_CHECK_ARG(Q && Cm, "tt_excl_retrieve_topk_f32: NULL embeddings");
+  TT_RET_CHECK_EXCL("tt_excl_retrieve_topk_f32");
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows, workspace,
+                 reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -96,14 +96,18 @@ class TwoTowerEvaluator:
         return out
 
     @torch.no_grad()
-    def evaluate_catalog(self, model, notice_store, index, pairs, ks=(5, 10), batch_size: int = 8192) -> Dict[str, float]:
+    def evaluate_catalog(self, model, notice_store, index, pairs, ks=(5, 10), batch_size: int = 8192,
+                         filter_pairs=None) -> Dict[str, float]:
         """Recall@k and MRR against the WHOLE catalogue instead of the other B - 1 companies of a batch.  `pairs` [P, 2] holds
         (notice entity, company entity) rows; `index` is a retrieval.CatalogIndex whose row i is company entity i
         (CatalogIndex.from_store).  Each pair's notice goes through the notice tower (eval mode, batch_size rows at a time)
         and its company is the positive; its rank among all nC catalogue rows is #{c : s > s_p} + #{c < p : s == s_p}.  As in
-        the in-batch metric, a notice's OTHER positive companies count as negatives.  Returns recall@k for every k in ks, mrr,
-        catalog_size and num_queries.  The model's train()/eval() state is restored afterwards."""
-        from .retrieval import CatalogIndex
+        the in-batch metric, a notice's OTHER positive companies count as negatives -- unless `filter_pairs` [P', 2] (notice,
+        company) rows are given: then every company paired with the query's notice in filter_pairs is left out of its ranking
+        (the filtered rank; the positive itself never counts against itself, so filter_pairs may hold it, e.g. all known
+        train and test pairs).  Returns recall@k for every k in ks, mrr, catalog_size and num_queries.  The model's
+        train()/eval() state is restored afterwards."""
+        from .retrieval import CatalogIndex, exclusions_from_pairs
         if not isinstance(index, CatalogIndex):
             raise TypeError("index must be a CatalogIndex")
         ks = tuple(int(k) for k in ks)
@@ -123,6 +127,11 @@ class TwoTowerEvaluator:
         if lo < 0 or hi >= index.size:
             raise ValueError(f"pair company rows must be in [0, {index.size}), got [{lo}, {hi}]")
         pairs = pairs.to(index.device)
+        if filter_pairs is not None:
+            filter_pairs = torch.as_tensor(filter_pairs)
+            if filter_pairs.dim() != 2 or filter_pairs.shape[1] != 2:
+                raise ValueError("filter_pairs must be a [P', 2] array of (notice, company) entity rows")
+            filter_pairs = filter_pairs.to(device=index.device, dtype=torch.int64)
         modes = [(m, m.training) for m in model.modules()]
         model.eval()
         try:
@@ -130,7 +139,8 @@ class TwoTowerEvaluator:
             for s in range(0, pairs.shape[0], batch_size):
                 p = pairs[s:s + batch_size]
                 q = tower_model.get_notice_embeddings(notice_store.gather(p[:, 0].contiguous()))
-                ranks.append(index.rank(q, p[:, 1].contiguous()))
+                ex = None if filter_pairs is None else exclusions_from_pairs(p[:, 0], filter_pairs, index.size)
+                ranks.append(index.rank(q, p[:, 1].contiguous(), exclude=ex))
             r = torch.cat(ranks) if len(ranks) > 1 else ranks[0]
         finally:
             for m, was in modes:

@@ -724,9 +724,10 @@ def retrieve_workspace_bytes(nQ: int, nC: int, D: int, k: int) -> int:
     return int(L.load().tt_retrieve_workspace_bytes(int(nQ), int(nC), int(D), int(k)))
 
 
-def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace):
+def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=None):
     """One tt_retrieve_topk_* call: Q / C are packed bf16 images (bf16=True) or f32 [n, D] rows.  Returns (vals, idx, rank);
-    vals / idx are None for k = 0, rank is None without positives."""
+    vals / idx are None for k = 0, rank is None without positives.  exclude=(offsets int64 [nQ + 1], rows int32): per-query
+    exclusion lists in CSR form, each list ascending (tt_excl_retrieve_topk_*)."""
     dev = C.device
     lib = L.load()
     vals = torch.empty((nQ, k), dtype=torch.float32, device=dev) if k else None
@@ -736,33 +737,57 @@ def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace):
         if positives.dtype not in (torch.int32, torch.int64) or positives.shape != (nQ,) or not positives.is_contiguous():
             raise ValueError(f"positives must be a contiguous int32/int64 tensor of shape ({nQ},)")
         rank = torch.empty(nQ, dtype=torch.int32, device=dev)
+    if exclude is not None:
+        off, rows = exclude
+        if off.dtype != torch.int64 or off.shape != (nQ + 1,) or not off.is_contiguous() or off.device != dev:
+            raise ValueError(f"exclusion offsets must be a contiguous int64 tensor of shape ({nQ + 1},) on {dev}")
+        if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous() or rows.device != dev:
+            raise ValueError(f"exclusion rows must be a contiguous 1-D int32 tensor on {dev}")
+        if rows.numel() == 0:                                     # (the entry wants a pointer even for empty lists)
+            rows = torch.zeros(1, dtype=torch.int32, device=dev)
     need = lib.tt_retrieve_workspace_bytes(nQ, nC, D, k)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     pos_i64 = 1 if positives is not None and positives.dtype == torch.int64 else 0
-    name = "tt_retrieve_topk_bf16" if bf16 else "tt_retrieve_topk_f32"
+    if exclude is None:
+        name = "tt_retrieve_topk_bf16" if bf16 else "tt_retrieve_topk_f32"
+        with _timed(name):
+            if bf16:
+                rc = lib.tt_retrieve_topk_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, k, L.ptr(positives), pos_i64, L.ptr(vals),
+                                               L.ptr(idx), L.ptr(rank), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            else:
+                rc = lib.tt_retrieve_topk_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, k, L.ptr(positives), pos_i64,
+                                              L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            L.check(rc, name)
+        return vals, idx, rank
+    name = "tt_excl_retrieve_topk_bf16" if bf16 else "tt_excl_retrieve_topk_f32"
     with _timed(name):
         if bf16:
-            rc = lib.tt_retrieve_topk_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, k, L.ptr(positives), pos_i64, L.ptr(vals),
-                                           L.ptr(idx), L.ptr(rank), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            rc = lib.tt_excl_retrieve_topk_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, k, L.ptr(positives), pos_i64, L.ptr(vals),
+                                                L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(workspace), workspace.numel(),
+                                                L.stream(dev))
         else:
-            rc = lib.tt_retrieve_topk_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, k, L.ptr(positives), pos_i64,
-                                          L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            rc = lib.tt_excl_retrieve_topk_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, k, L.ptr(positives), pos_i64,
+                                               L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(workspace),
+                                               workspace.numel(), L.stream(dev))
         L.check(rc, name)
     return vals, idx, rank
 
 
-def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None):
+def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None, exclude=None):
     """Top-k of every query over the whole catalogue (tt_retrieve_topk_bf16 / _f32): (vals f32 [nQ, k], idx int64 [nQ, k]),
-    value descending, ties to the lower index.  With positives, (vals, idx, rank) from the same sweep."""
-    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace)
+    value descending, ties to the lower index.  With positives, (vals, idx, rank) from the same sweep.  exclude=(offsets,
+    rows): query q's rows rows[offsets[q]:offsets[q+1]] (ascending) are left out of its top-k and rank
+    (tt_excl_retrieve_topk_*)."""
+    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude)
     return (vals, idx) if positives is None else (vals, idx, rank)
 
 
-def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=None):
+def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=None, exclude=None):
     """Rank of each query's positive among all catalogue rows (k = 0 call): int32 [nQ],
-    #{c : s > s_p} + #{c < p : s == s_p}, -1 for a positive outside [0, nC)."""
-    return _retrieve(Q, nQ, C, nC, D, 0, inv_t, bf16, positives, workspace)[2]
+    #{c : s > s_p} + #{c < p : s == s_p}, -1 for a positive outside [0, nC).  With exclude=(offsets, rows), only rows outside
+    the query's list count."""
+    return _retrieve(Q, nQ, C, nC, D, 0, inv_t, bf16, positives, workspace, exclude)[2]
 
 
 # ---------------------------------------------------------------------------------------------- misc

@@ -8,6 +8,11 @@ matrix to memory.
     index = CatalogIndex.from_store(model, company_store)         # row i of the index = entity i of the store
     vals, idx = index.search(notice_embeddings, k=10)             # s = <q, c> / T, value descending, ties -> lower index
     ranks = index.rank(notice_embeddings, positives)              # #{c : s > s_p} + #{c < p : s == s_p}
+
+Every search also takes exclude=(offsets, rows), per-query exclusion lists in CSR form: query i's rows
+rows[offsets[i]:offsets[i+1]] are left out of its top-k and its rank, inside the same sweep
+(tt_excl_retrieve_topk_bf16 / _f32).  exclusions_from_pairs builds them from known (query key, row) pairs -- the filtered
+ranking of link-prediction evaluation, or the companies that already bid on a notice when serving.
 """
 from __future__ import annotations
 
@@ -19,6 +24,33 @@ from . import ops
 from .config import settings
 
 MAX_K = 64
+
+
+def exclusions_from_pairs(query_keys, pairs, nC: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Canonical exclusion lists (offsets int64 [nQ + 1], rows int32 [offsets[-1]]) on query_keys' device: query i's list
+    holds every c with (query_keys[i], c) a row of `pairs` [P, 2], ascending, without duplicates.  Repeated keys get the same
+    list; a key without pairs gets an empty one.  Raises ValueError for a pair row outside [0, nC)."""
+    keys = torch.as_tensor(query_keys)
+    dev = keys.device
+    keys = keys.to(torch.int64).reshape(-1).contiguous()
+    pairs = torch.as_tensor(pairs).to(device=dev, dtype=torch.int64)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be a [P, 2] array of (query key, catalogue row) rows")
+    if pairs.shape[0]:
+        lo, hi = int(pairs[:, 1].min()), int(pairs[:, 1].max())
+        if lo < 0 or hi >= nC:
+            raise ValueError(f"pair catalogue rows must be in [0, {nC}), got [{lo}, {hi}]")
+    up = torch.unique(pairs, dim=0) if pairs.shape[0] else pairs          # sorted by (key, row), duplicates removed
+    pk, pc = up[:, 0].contiguous(), up[:, 1].contiguous()
+    first = torch.searchsorted(pk, keys, right=False)
+    count = torch.searchsorted(pk, keys, right=True) - first
+    offsets = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(count, 0)
+    n = int(offsets[-1])
+    j = torch.arange(n, dtype=torch.int64, device=dev)
+    q = torch.searchsorted(offsets[1:], j, right=True)                  # the query entry j belongs to
+    rows = pc[first[q] + (j - offsets[q])].to(torch.int32)
+    return offsets, rows
 
 
 class CatalogIndex:
@@ -110,6 +142,26 @@ class CatalogIndex:
             positives = positives.to(torch.int64)
         return positives.to(self.device).contiguous()
 
+    def _check_exclude(self, exclude, nQ: int):
+        """(offsets int64 [nQ + 1], rows int32) with every query's list sorted ascending, from a caller's CSR pair.  Rows may
+        be int32 or int64 (converted) and in any order within a list; rows outside [0, nC) match nothing.  The offsets are
+        used clamped to [0, len(rows)] and non-decreasing (no host synchronisation here: a search stays capturable)."""
+        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2:
+            raise ValueError("exclude must be an (offsets, rows) pair")
+        off, rows = exclude
+        if not torch.is_tensor(off) or off.dtype != torch.int64 or off.shape != (nQ + 1,):
+            raise ValueError(f"exclude offsets must be an int64 tensor of shape ({nQ + 1},)")
+        if not torch.is_tensor(rows) or rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 1:
+            raise ValueError("exclude rows must be a 1-D int32 or int64 tensor")
+        if off.device != self.device or rows.device != self.device:
+            raise ValueError(f"exclude on {off.device} / {rows.device}, catalogue on {self.device}")
+        n = rows.numel()
+        off = torch.cummax(off.clamp(0, n), 0).values.contiguous()
+        seg = torch.searchsorted(off, torch.arange(n, dtype=torch.int64, device=self.device), right=True)
+        rows = rows.to(torch.int64).clamp(-1, self.size)                   # (outside [0, nC) either way: int32 without wrapping)
+        order = torch.argsort(seg * (1 << 32) + rows)                       # (list, row): sorts within each list only
+        return off, rows[order].to(torch.int32).contiguous()
+
     def _workspace(self, nQ: int, k: int) -> torch.Tensor:
         need = ops.retrieve_workspace_bytes(nQ, self.size, self.dim, k)
         key = torch.cuda.current_stream(self.device).cuda_stream
@@ -119,33 +171,41 @@ class CatalogIndex:
             self._ws[key] = ws
         return ws
 
-    def _call(self, Q: torch.Tensor, k: int, positives):
+    def _call(self, Q: torch.Tensor, k: int, positives, exclude=None):
         nQ = Q.shape[0]
         ws = self._workspace(nQ, k)
         if self.score_dtype == "bf16":
             q = ops.score_pack_bf16(Q, 1.0)
-            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws)
-        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws)
+            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws, exclude)
+        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws, exclude)
 
-    def search(self, Q: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, Q: torch.Tensor, k: int = 10, exclude=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(vals f32 [nQ, k], idx int64 [nQ, k]): every query's k best catalogue rows, value descending, ties to the lower
-        index.  1 <= k <= min(64, catalogue size)."""
+        index.  1 <= k <= min(64, catalogue size).  exclude=(offsets int64 [nQ + 1], rows): query i's rows
+        rows[offsets[i]:offsets[i+1]] are left out; if fewer than k rows remain, the last slots are -inf / -1."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
-        vals, idx, _ = self._call(Q, k, None)
+        ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
+        vals, idx, _ = self._call(Q, k, None, ex)
         return vals, idx
 
-    def search_with_rank(self, Q: torch.Tensor, k: int, positives) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """search() and rank() from one sweep over the catalogue."""
+    def search_with_rank(self, Q: torch.Tensor, k: int, positives, exclude=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """search() and rank() from one sweep over the catalogue (the same exclusion lists for both)."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
-        return self._call(Q, k, self._check_positives(positives, Q.shape[0]))
+        pos = self._check_positives(positives, Q.shape[0])
+        ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
+        return self._call(Q, k, pos, ex)
 
-    def rank(self, Q: torch.Tensor, positives) -> torch.Tensor:
+    def rank(self, Q: torch.Tensor, positives, exclude=None) -> torch.Tensor:
         """int32 [nQ]: 0-based rank of catalogue row positives[i] for query i among ALL catalogue rows,
-        #{c : s > s_p} + #{c < p : s == s_p} (tt_diag_rank_rows's rule); -1 where the positive is outside [0, nC)."""
+        #{c : s > s_p} + #{c < p : s == s_p} (tt_diag_rank_rows's rule); -1 where the positive is outside [0, nC).
+        exclude=(offsets, rows): only rows outside query i's list count -- the filtered rank.  The positive never counts
+        against itself, so it may be in its own list."""
         Q = self._check_queries(Q)
-        return self._call(Q, 0, self._check_positives(positives, Q.shape[0]))[2]
+        pos = self._check_positives(positives, Q.shape[0])
+        ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
+        return self._call(Q, 0, pos, ex)[2]
 
     def __len__(self) -> int:
         return self.size

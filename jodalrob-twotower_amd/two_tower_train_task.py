@@ -292,11 +292,13 @@ class TwoTowerTrainTask(nn.Module):
             return {"top_similarities": vals, "top_indices": idx, "all_similarities": sim}
 
     @_no_dynamo
-    def predict_catalog(self, notice_batch, index, top_k: int = 10) -> Dict[str, torch.Tensor]:
+    def predict_catalog(self, notice_batch, index, top_k: int = 10, exclude=None) -> Dict[str, torch.Tensor]:
         """Top-k companies of the whole catalogue `index` (a retrieval.CatalogIndex) for every notice of `notice_batch` (the
         notice side's {"dense", "kjt"}, or a full batch with a "notice" entry): {"top_similarities" f32 [B, top_k],
         "top_indices" int64 [B, top_k]} -- index rows, value descending, ties to the lower index.  The notice tower runs in
-        eval mode; the task's train()/eval() state is restored afterwards.  (predict_batch ranks within one batch.)"""
+        eval mode; the task's train()/eval() state is restored afterwards.  (predict_batch ranks within one batch.)
+        exclude=(offsets, rows): per-notice exclusion lists (CatalogIndex.search), e.g. companies that already bid on it
+        (retrieval.exclusions_from_pairs)."""
         from .retrieval import CatalogIndex
         if not isinstance(index, CatalogIndex):
             raise TypeError("index must be a CatalogIndex")
@@ -309,7 +311,7 @@ class TwoTowerTrainTask(nn.Module):
         try:
             with torch.no_grad():
                 q = self.two_tower_model.get_notice_embeddings(notice)
-                vals, idx = index.search(q, top_k)
+                vals, idx = index.search(q, top_k, exclude=exclude)
         finally:
             for m, was in modes:
                 m.training = was

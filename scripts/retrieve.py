@@ -2,7 +2,10 @@
 reports Recall@5/10 and MRR of the test pairs against the WHOLE catalogue and prints a few notices' top-k companies.
 
     python scripts/retrieve.py [--checkpoint output/models/final_model.pt] [--final-dim 64] [--hidden 128,64]
-                               [--entities 10000] [--pairs 100000] [--score-dtype fp32|bf16] [--top-k 10]
+                               [--entities 10000] [--pairs 100000] [--score-dtype fp32|bf16] [--top-k 10] [--filtered]
+
+--filtered also prints the filtered metrics (each test pair ranked without its notice's other known companies, train and
+test pairs alike) and leaves every notice's known companies out of its example top-k list.
 
 The data are the synthetic feature / pair source scripts/train.py uses (same arguments give the same stores, so a checkpoint
 written by `scripts/train.py --entities N --pairs P` is evaluated on its own test split).  Without --checkpoint the task is
@@ -27,7 +30,7 @@ from src.towers.pairs.unified_bid_data_loader import create_unified_bid_dataload
 from src.towers.two_tower_train_task import create_two_tower_train_task       # noqa: E402
 from jodalrob_twotower_amd import synthetic                                   # noqa: E402
 from jodalrob_twotower_amd.evaluator import TwoTowerEvaluator                 # noqa: E402
-from jodalrob_twotower_amd.retrieval import CatalogIndex                      # noqa: E402
+from jodalrob_twotower_amd.retrieval import CatalogIndex, exclusions_from_pairs  # noqa: E402
 
 
 def main():
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--train-steps", type=int, default=200, help="without --checkpoint: train this many steps first")
     ap.add_argument("--top-k", type=int, default=10)
     ap.add_argument("--examples", type=int, default=3)
+    ap.add_argument("--filtered", action="store_true",
+                    help="also rank without each notice's other known companies (train + test pairs)")
     a = ap.parse_args()
 
     device = torch.device("cuda:0")
@@ -96,14 +101,18 @@ def main():
     m = ev.evaluate_catalog(task, test_loader.notice, index, pairs)
     print(f"catalogue-wide metrics over {m['num_queries']} test pairs and {m['catalog_size']} companies "
           f"({time.time() - t0:.2f} s):")
+    known = torch.cat([train_loader.pairs, test_loader.pairs]) if a.filtered else None   # (the loaders share one entity store)
+    mf = ev.evaluate_catalog(task, test_loader.notice, index, pairs, filter_pairs=known) if a.filtered else None
     for key in ("recall@5", "recall@10", "mrr"):
-        print(f"  {key:10s} {m[key]:.4f}")
+        print(f"  {key:10s} {m[key]:.4f}" + (f"   filtered {mf[key]:.4f}" if mf else ""))
     print(f"  random baseline: recall@5 {5 / m['catalog_size']:.5f}, recall@10 {10 / m['catalog_size']:.5f}")
 
     ex = pairs[:a.examples]
-    pred = task.predict_catalog(test_loader.notice.gather(ex[:, 0].contiguous()), index, top_k=a.top_k)
+    excl = exclusions_from_pairs(ex[:, 0], known, index.size) if a.filtered else None
+    pred = task.predict_catalog(test_loader.notice.gather(ex[:, 0].contiguous()), index, top_k=a.top_k, exclude=excl)
     for i in range(ex.shape[0]):
-        print(f"notice {int(ex[i, 0])} (positive company {int(ex[i, 1])}): top-{a.top_k} companies "
+        seen = f", {int(excl[0][i + 1] - excl[0][i])} known companies left out" if a.filtered else ""
+        print(f"notice {int(ex[i, 0])} (positive company {int(ex[i, 1])}{seen}): top-{a.top_k} companies "
               f"{pred['top_indices'][i].tolist()}")
         print(f"    scores {[round(v, 4) for v in pred['top_similarities'][i].tolist()]}")
 

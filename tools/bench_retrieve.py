@@ -2,12 +2,16 @@
 torch.mm + torch.topk on the same inputs.
 
     python tools/bench_retrieve.py [--nq 8192] [--nc 65536 1048576] [--d 64 256] [--k 10 64] [--dtypes bf16 fp32]
-                                   [--reps 3] [--out profiles/retrieve_bench.json]
+                                   [--reps 3] [--out profiles/retrieve_bench.json] [--exclude 0 16 256]
 
 One JSON line per case: kernel ms per search and scores/s, the MFMA fraction of 2.5 PF dense bf16 (2 nQ nC D flops), the
 catalogue read rate (bytes of the catalogue operand per search) against 8 TB/s, and the baseline's ms and how many rows'
 index sets agree with the kernel's.  The baseline keeps at most 1 GiB of f32 scores alive per chunk (bf16: torch.mm of the two
 bf16 images, bf16 scores; fp32: f32 scores), takes the chunk's top-k and merges it into the running top-k.
+
+--exclude L [L ...] (no baseline then): per case and L, every query gets L random distinct catalogue rows as its exclusion
+list, and the exclusion search (tt_excl_retrieve_topk_*) is timed against the plain search in the same process, the two
+alternating rep by rep; one JSON line per (case, L) with both times and their ratio.
 """
 from __future__ import annotations
 
@@ -58,6 +62,52 @@ def baseline(Q, Cm, k, inv_t, bf16):
     return best_v, best_i
 
 
+def random_exclusions(nq, nc, L, g, dev):
+    """L distinct rows per query, ascending: a sorted draw from [0, nc - L] plus 0 .. L-1."""
+    off = torch.arange(nq + 1, dtype=torch.int64, device=dev) * L
+    if L == 0:
+        return off, torch.zeros(0, dtype=torch.int32, device=dev)
+    r = torch.sort(torch.randint(0, nc - L + 1, (nq, L), generator=g, device=dev), dim=1).values
+    r += torch.arange(L, device=dev)
+    return off, r.reshape(-1).to(torch.int32).contiguous()
+
+
+def exclude_rows(index, Q, k, nc, d, dt, args):
+    from jodalrob_twotower_amd import ops
+    dev = Q.device
+    g = torch.Generator(device=dev).manual_seed(1)
+    nq = Q.shape[0]
+    ws = index._workspace(nq, k)
+    q = ops.score_pack_bf16(Q, 1.0) if index.score_dtype == "bf16" else Q
+    bf16 = index.score_dtype == "bf16"
+    out = []
+    for L in args.exclude:
+        ex = random_exclusions(nq, nc, L, g, dev)
+
+        def plain():
+            ops._retrieve(q, nq, index.data, nc, d, k, index.inv_t, bf16, None, ws)
+
+        def excl():
+            ops._retrieve(q, nq, index.data, nc, d, k, index.inv_t, bf16, None, ws, ex)
+
+        pm, xm = [], []
+        for _ in range(args.reps):                               # alternating, so both see the same clocks and caches
+            pm.append(_time(plain, 1)[0])
+            xm.append(_time(excl, 1)[0])
+        vals, idx = index.search(Q, k, exclude=ex)
+        hit = 0
+        if L:
+            lists = ex[1].view(nq, L).long()
+            hit = int((idx[:, :, None] == lists[:, None, :]).any(2).sum())
+        row = {"nq": nq, "nc": nc, "d": d, "k": k, "dtype": dt, "exclude_L": L, "plain_ms": round(min(pm), 4),
+               "excl_ms": round(min(xm), 4), "excl_over_plain": round(min(xm) / min(pm), 4),
+               "plain_ms_all": [round(x, 4) for x in pm], "excl_ms_all": [round(x, 4) for x in xm],
+               "excluded_rows_returned": hit}
+        print(json.dumps(row), flush=True)
+        out.append(row)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=8192)
@@ -68,6 +118,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--exclude", type=int, nargs="+", action="extend", default=None,
+                    help="exclusion list lengths L to time against the plain search (repeatable)")
     args = ap.parse_args()
 
     from jodalrob_twotower_amd.retrieval import CatalogIndex
@@ -83,6 +135,9 @@ def main():
             for dt in args.dtypes:
                 index = CatalogIndex.from_embeddings(Cm, temperature=0.05, score_dtype=dt)
                 for k in args.k:
+                    if args.exclude is not None:
+                        rows.extend(exclude_rows(index, Q, k, nc, d, dt, args))
+                        continue
                     best, mean = _time(lambda: index.search(Q, k), args.reps)
                     vals, idx = index.search(Q, k)
                     flops = 2.0 * args.nq * nc * d
