@@ -599,6 +599,58 @@ int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dir
                         float shift, tt_stream stream);
 int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t,
                         float shift, const float* d_loss, float scale, tt_stream stream);
+/* ---- logQ sampling-bias correction of the in-batch softmax (Yi et al., RecSys 2019) ----------------------------------
+ * A batch is a uniform draw of PAIRS, so an entity is sampled as a negative in proportion to its pair count and the plain
+ * in-batch softmax pushes frequent entities down hardest.  With lqN[a] / lqC[b] the log sampling probabilities (<= 0) of the
+ * batch's notice a and company b, and s_ab = <n_a, c_b> / T:
+ *   row direction     s^_ab  = s_ab - lqC[b]        column direction   s^'_ab = s_ab - lqN[a]
+ *   loss = 0.5 * [ mean_a (logsumexp_b s^_ab - s^_aa) + mean_b (logsumexp_a s^'_ab - s^'_bb) ]      (the positive corrected too)
+ *   d loss / d s_ab = (1 / 2B) [ softmax_row(s^)_ab + softmax_col(s^')_ab - 2 [a == b] ]
+ * Numeric form: on the fixed-shift sums of the plain entries, the row sums add e_ab w_b and the column sums e_ab u_a with
+ * the sampling weights w_b = exp(-40 - lqC[b]), u_a = exp(-40 - lqN[a]) in [e^-40, 1] (lq CLAMPED to [-40, 0] first:
+ * lq < -40 counts as -40, lq > 0 as 0; the constant 40 cancels in every softmax, so nothing overflows).  The loss uses
+ * log w = -40 - lq exactly.  The smallest term, e^(-2/T - 40), must stay a normal float: the *_lq entries support 2/T <= 40
+ * (T >= 0.05) and return TT_ERR_UNSUPPORTED above that.  Metrics (out8, diag, ranks) stay on the RAW scores -- serving
+ * ranks raw scores -- and are bitwise those of the plain entry; only rowsum / colsum / inv_* / the loss / the gradients
+ * change.  Per-row arrays: f32, device, 16-byte aligned.  bf16 / bf16x3 operands and the f32 parity path; no fp8 form.
+ *
+ * tt_score_fwd_sym_bf16_lq / _bf16x3_lq = tt_score_fwd_sym_bf16 / _bf16x3 plus lq_n / lq_c [B] (inputs) and w_n / w_c
+ * [round_up(B, 64)] (outputs: u / w above per row, 0 past B) -- the backward's sampling weights.  rowsum / colsum / inv_row /
+ * inv_col are the corrected sums (scaled by the constant e^-40).
+ * tt_score_bwd_bf16_lq / _bf16x3_lq = tt_score_bwd_bf16 / _bf16x3 plus, per direction, the sampling weights of its A rows and
+ * of its B rows (tt_score_bwd_lq: the forward's w_n / w_c -- direction (N, C): {w_n, w_c}, direction (C, N): {w_c, w_n});
+ * the inv / sumexp arrays must be the _lq forward's.  Weight of (a, b): e_ab (w_b / rowsum_a + w_a / colsum_b).
+ * tt_score_dir_fwd_lq = tt_score_dir_fwd with sumexp[a] = sum_b exp(s_ab - shift) exp(-40 - lq_b[b]) (lq_b [Rb]: the B rows'
+ * log probabilities); tt_score_loss_finish_lq = tt_score_loss_finish with the corrected positives (lq_n, lq_c [B]);
+ * tt_score_dir_bwd_lq = tt_score_dir_bwd with the weight exp(s_ab - shift) (w_b / sumexp_a[a] + w_a / sumexp_b[b]), w from
+ * lq_a [Ra] / lq_b [Rb] as above. */
+typedef struct tt_score_bwd_lq {
+  const float* w_a; /* [Ra] sampling weights of the direction's A rows */
+  const float* w_b; /* [round_up(Rb, 32)] of its B rows, read a whole 32-row tile at a time (entries past Rb finite); 16-byte aligned */
+} tt_score_bwd_lq;
+int tt_score_fwd_sym_bf16_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                             float shift, float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c, float* rowsum,
+                             float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag,
+                             int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
+                             tt_stream stream);
+int tt_score_fwd_sym_bf16x3_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                               float shift, float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c,
+                               float* rowsum, float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c,
+                               float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
+                               size_t workspace_bytes, tt_stream stream);
+int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
+                         float inv_t, float shift, const float* d_loss, float scale, tt_stream stream);
+int tt_score_bwd_bf16x3_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
+                           float inv_t, float shift, const float* d_loss, float scale, tt_stream stream);
+int tt_score_dir_fwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
+                        float shift, int64_t diag_offset, const float* lq_b, float* sumexp, float* diag, int32_t* rank,
+                        float* sumscore, tt_stream stream);
+int tt_score_loss_finish_lq(tt_ctx* ctx, int64_t B, float shift, const float* lq_n, const float* lq_c, const float* rowsum,
+                            const float* colsum, const float* diag, const int32_t* row_rank, const int32_t* col_rank,
+                            const float* sumscore, float* out8, float* loss_out, tt_stream stream);
+int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
+                        float shift, int64_t diag_offset, const float* lq_a, const float* lq_b, const float* sumexp_a,
+                        const float* sumexp_b, const float* d_loss, float scale, float* dA, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

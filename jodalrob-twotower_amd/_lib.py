@@ -68,6 +68,10 @@ class ScoreBwdDir(C.Structure):
                 ("sumexp_a", vp), ("sumexp_b", vp), ("dA", vp), ("ab_scale", f32), ("b_scale", f32), ("inv_a", vp), ("inv_b", vp)]
 
 
+class ScoreBwdLq(C.Structure):
+    _fields_ = [("w_a", vp), ("w_b", vp)]
+
+
 _H = vp * TT_MAX_HIDDEN
 
 
@@ -160,6 +164,15 @@ SIGNATURES = {
     "tt_score_fwd_sym_bf16x3": (C.c_int, [vp, vp, vp, i64, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "tt_score_fwd_bf16x3": (C.c_int, [vp, C.POINTER(ScoreFwdDir), i32, i32, f32, f32, vp]),
     "tt_score_bwd_bf16x3": (C.c_int, [vp, C.POINTER(ScoreBwdDir), i32, i32, f32, f32, vp, f32, vp]),
+    "tt_score_fwd_sym_bf16_lq": (C.c_int, [vp, vp, vp, i64, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           sz, vp]),
+    "tt_score_fwd_sym_bf16x3_lq": (C.c_int, [vp, vp, vp, i64, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             sz, vp]),
+    "tt_score_bwd_bf16_lq": (C.c_int, [vp, C.POINTER(ScoreBwdDir), C.POINTER(ScoreBwdLq), i32, i32, f32, f32, vp, f32, vp]),
+    "tt_score_bwd_bf16x3_lq": (C.c_int, [vp, C.POINTER(ScoreBwdDir), C.POINTER(ScoreBwdLq), i32, i32, f32, f32, vp, f32, vp]),
+    "tt_score_dir_fwd_lq": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp, vp]),
+    "tt_score_loss_finish_lq": (C.c_int, [vp, i64, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_score_dir_bwd_lq": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp, f32, vp, vp]),
     "tt_score_matrix": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, vp, i64, vp]),
     "tt_score_dense_workspace_bytes": (sz, [i64, i32]),
     "tt_score_dense_fwd": (C.c_int, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp, vp]),

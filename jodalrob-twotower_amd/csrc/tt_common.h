@@ -88,6 +88,15 @@ extern std::atomic<uint64_t> tt_launches;
     }                                                                                                               \
   } while (0)
 
+// logQ sampling-bias correction of the in-batch softmax (the *_lq score entries, twotower.h): a row's log sampling probability
+// lq is clamped to [-kLqL, 0] and enters the softmax sums as the weight exp(-kLqL - lq) in [e^-kLqL, 1] -- the constant kLqL
+// cancels in every softmax, so the weights never exceed 1.  Every kernel takes a weight through this one function (bitwise the
+// same value wherever it is formed); the loss uses log w = -kLqL - lq exactly.
+constexpr float kLqL = 40.f;
+constexpr float kLqMaxTwoInvT = 40.f;  // smallest term e^(-2/T - kLqL) stays a normal float: 2/T <= 40 for the *_lq entries
+__device__ __forceinline__ float tt_lq_log_weight(float lq) { return -kLqL - fminf(fmaxf(lq, -kLqL), 0.f); }
+__device__ __forceinline__ float tt_lq_weight(float lq) { return expf(tt_lq_log_weight(lq)); }
+
 static inline int64_t tt_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool tt_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 

@@ -71,11 +71,13 @@ __device__ __forceinline__ float diag_score(const float* __restrict__ A, const f
   return acc * inv_t;
 }
 
-template <bool VEC>
+// LQ (tt_score_dir_fwd_lq): sumexp adds exp(s - shift) w_b, w_b = tt_lq_weight(lq_b[b]) the B row's sampling weight
+template <bool VEC, bool LQ = false>
 __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 float* __restrict__ sumexp, float* __restrict__ diag_out,
-                                                                int32_t* __restrict__ rank_out, float* __restrict__ sumscore) {
+                                                                int32_t* __restrict__ rank_out, float* __restrict__ sumscore,
+                                                                const float* __restrict__ lq_b = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float diag_s[RB];
@@ -114,12 +116,14 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
     for (int h = 0; h < 2; ++h) {
       const int64_t col = c0 + wc * 64 + h * 32 + li;
       const bool cv = col < Rb;
+      const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 1.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float s = (h == 0 ? acc0[r] : acc1[r]) * inv_t;
         const int64_t pos = r0 + wr * 32 + rowmap(r, lh) + diag_off;
         if (cv) {
-          se[r] += __expf(s - shift);
+          if constexpr (LQ) se[r] += __expf(s - shift) * wb;
+          else se[r] += __expf(s - shift);
           ss[r] += s;
           rk[r] += (s > dg[r] || (s == dg[r] && col < pos)) ? 1 : 0;
         }
@@ -144,12 +148,14 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
   }
 }
 
-// backward of one direction; NCH = ceil(D / 64) feature chunks kept as MFMA accumulators
-template <int NCH, bool VEC>
+// backward of one direction; NCH = ceil(D / 64) feature chunks kept as MFMA accumulators.
+// LQ (tt_score_dir_bwd_lq): the weight of (a, b) is exp(s - shift) (w_b / sumexp_a + w_a / sumexp_b), w the sampling weights
+template <int NCH, bool VEC, bool LQ = false>
 __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 const float* __restrict__ sumexp_a, const float* __restrict__ sumexp_b,
-                                                                const float* __restrict__ d_loss, float scale, float* __restrict__ dA) {
+                                                                const float* __restrict__ d_loss, float scale, float* __restrict__ dA,
+                                                                const float* __restrict__ lq_a = nullptr, const float* __restrict__ lq_b = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float Ws[RB * LDW];
@@ -157,11 +163,12 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
   const int wr = wave & 1, wc = wave >> 1, li = lane & 31, lh = lane >> 5;
   const int64_t r0 = (int64_t)blockIdx.x * RB;
   if (NCH == 1) stage<RB, VEC>(A, Ra, D, r0, 0, As, t);
-  float ia[16];
+  float ia[16], ua[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t a = r0 + wr * 32 + rowmap(r, lh);
     ia[r] = a < Ra ? 1.f / sumexp_a[a] : 0.f;
+    if constexpr (LQ) ua[r] = a < Ra ? tt_lq_weight(lq_a[a]) : 0.f;
   }
   f32x16 dacc[NCH];
 #pragma unroll
@@ -187,13 +194,15 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
       const int64_t col = c0 + cl;
       const bool cv = col < Rb;
       const float ib = cv ? 1.f / sumexp_b[col] : 0.f;
+      const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 32 + rowmap(r, lh);
         const float s = (h == 0 ? acc0[r] : acc1[r]) * inv_t;
         float w = 0.f;
         if (cv) {
-          w = __expf(s - shift) * (ia[r] + ib);
+          if constexpr (LQ) w = __expf(s - shift) * (wb * ia[r] + ua[r] * ib);
+          else w = __expf(s - shift) * (ia[r] + ib);
           if (col == r0 + row + diag_off) w -= 2.f;
         }
         Ws[row * LDW + cl] = w;
@@ -239,6 +248,60 @@ __global__ __launch_bounds__(1024) void loss_finish_kernel(int64_t B, float shif
   for (int64_t i = threadIdx.x; i < B; i += blockDim.x) {
     const float d = diag[i];
     l += (logf(rowsum[i]) + shift - d) + (logf(colsum[i]) + shift - d);
+    hit += row_rank[i] == 0 ? 1.f : 0.f;
+    chit += col_rank[i] == 0 ? 1.f : 0.f;
+    dsum += d;
+    tot += sumscore ? sumscore[i] : 0.f;
+  }
+  // the five sums together: butterfly inside the wave, one LDS exchange, fixed order across the 16 waves
+  float v[5] = {l, hit, chit, dsum, tot};
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) v[j] += __shfl_xor(v[j], o);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) sh5[j][threadIdx.x >> 6] = v[j];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      float t = 0.f;
+      for (int w = 0; w < nw; ++w) t += sh5[j][w];
+      v[j] = t;
+    }
+    l = v[0]; hit = v[1]; chit = v[2]; dsum = v[3]; tot = v[4];
+  }
+  if (threadIdx.x == 0) {
+    const float fb = (float)B;
+    const float pos = dsum / fb;
+    const float neg = (tot - dsum) / (fb * fb - fb);       // mean over the off-diagonal (nan for B == 1, as torch)
+    out[0] = 0.5f * l / fb;
+    out[1] = hit / fb;
+    out[2] = pos;
+    out[3] = neg;
+    out[4] = pos - neg;
+    out[5] = chit / fb;
+    out[6] = tot;
+    out[7] = 0.f;
+    if (loss_out) loss_out[0] = out[0];
+  }
+}
+
+// tt_score_loss_finish_lq: loss_finish_kernel with each direction's term less the log weight of its positive (-kLqL - lq, exactly)
+__global__ __launch_bounds__(1024) void loss_finish_lq_kernel(int64_t B, float shift, const float* __restrict__ rowsum,
+                                                           const float* __restrict__ colsum, const float* __restrict__ diag,
+                                                           const int32_t* __restrict__ row_rank, const int32_t* __restrict__ col_rank,
+                                                           const float* __restrict__ sumscore, float* __restrict__ out,
+                                                           float* __restrict__ loss_out, const float* __restrict__ lq_n,
+                                                           const float* __restrict__ lq_c) {
+  __shared__ float sh5[5][16];
+  float l = 0.f, hit = 0.f, chit = 0.f, dsum = 0.f, tot = 0.f;
+#pragma unroll 4
+  for (int64_t i = threadIdx.x; i < B; i += blockDim.x) {
+    const float d = diag[i];
+    l += (logf(rowsum[i]) + shift - d - tt_lq_log_weight(lq_c[i])) + (logf(colsum[i]) + shift - d - tt_lq_log_weight(lq_n[i]));
     hit += row_rank[i] == 0 ? 1.f : 0.f;
     chit += col_rank[i] == 0 ? 1.f : 0.f;
     dsum += d;
@@ -520,6 +583,68 @@ int tt_score_dir_bwd(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, i
 #define TT_BWD(NCHV)                                                                                                          \
   if (v) score_dir_bwd_kernel<NCHV, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA); \
   else score_dir_bwd_kernel<NCHV, false><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA);
+  switch (nch) {
+    case 1: TT_BWD(1) break;
+    case 2: TT_BWD(2) break;
+    case 3: TT_BWD(3) break;
+    default: TT_BWD(4) break;
+  }
+#undef TT_BWD
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_dir_fwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                        int64_t diag_offset, const float* lq_b, float* sumexp, float* diag, int32_t* rank, float* sumscore,
+                        tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && lq_b && sumexp && diag && rank, "tt_score_dir_fwd_lq: NULL argument");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_fwd_lq: bad shape");
+  TT_CHECK_ARG(Ra < ((int64_t)1 << 31) && Rb < ((int64_t)1 << 31), "tt_score_dir_fwd_lq: too many rows");
+  if (2.f * fabsf(inv_t) > kLqMaxTwoInvT) {
+    tt_set_error("tt_score_dir_fwd_lq: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", inv_t, kLqMaxTwoInvT);
+    return TT_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
+  if (vec_ok(A, D) && vec_ok(Bm, D))
+    score_dir_fwd_kernel<true, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
+  else
+    score_dir_fwd_kernel<false, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_loss_finish_lq(tt_ctx* ctx, int64_t B, float shift, const float* lq_n, const float* lq_c, const float* rowsum,
+                            const float* colsum, const float* diag, const int32_t* row_rank, const int32_t* col_rank,
+                            const float* sumscore, float* out8, float* loss_out, tt_stream stream) {
+  TT_CHECK_ARG(ctx && lq_n && lq_c && rowsum && colsum && diag && row_rank && col_rank && out8, "tt_score_loss_finish_lq: NULL argument");
+  TT_CHECK_ARG(B >= 1, "tt_score_loss_finish_lq: B < 1");
+  loss_finish_lq_kernel<<<1, 1024, 0, reinterpret_cast<hipStream_t>(stream)>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore,
+                                                                                  out8, loss_out, lq_n, lq_c);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                        int64_t diag_offset, const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b,
+                        const float* d_loss, float scale, float* dA, tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && lq_a && lq_b && sumexp_a && sumexp_b && d_loss && dA, "tt_score_dir_bwd_lq: NULL argument");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_bwd_lq: bad shape");
+  if (D > 4 * DK) {
+    tt_set_error("tt_score_dir_bwd_lq: D=%d > %d not supported", D, 4 * DK);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (2.f * fabsf(inv_t) > kLqMaxTwoInvT) {
+    tt_set_error("tt_score_dir_bwd_lq: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", inv_t, kLqMaxTwoInvT);
+    return TT_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
+  const bool v = vec_ok(A, D) && vec_ok(Bm, D);
+  const int nch = (D + DK - 1) / DK;
+#define TT_BWD(NCHV)                                                                                                          \
+  if (v) score_dir_bwd_kernel<NCHV, true, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA, lq_a, lq_b); \
+  else score_dir_bwd_kernel<NCHV, false, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA, lq_a, lq_b);
   switch (nch) {
     case 1: TT_BWD(1) break;
     case 2: TT_BWD(2) break;

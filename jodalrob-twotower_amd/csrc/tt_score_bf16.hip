@@ -114,6 +114,9 @@ struct BwdArgs {
   float c2, kexp;
   const float* d_loss;
   int D;
+  // LQ kernels (tt_score_bwd_bf16_lq): per direction the sampling weights of the A rows and of the B rows (tt_score_bwd_lq)
+  const float* wt_a[2];
+  const float* wt_b[2];
 };
 
 template <int KS, int AT>
@@ -409,7 +412,8 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
 // One tile's worth of streamed operands: the b tile's fragments for the first product, its fragment-ordered image for the
 // second, and the 16 softmax reciprocals (or exp-sums) of its rows this lane half needs.
 // X3: the lo images' fragments as well (bl, bml).
-template <int KS, bool X3 = false>
+// LQ: the 16 sampling weights of those rows as well (wv).
+template <int KS, bool X3 = false, bool LQ = false>
 struct BwdTile {
   static constexpr int KL = X3 ? KS : 1, DL = X3 ? KS / 2 : 1;
   bf16x8 b[KS];
@@ -417,12 +421,14 @@ struct BwdTile {
   bf16x8 bm[2][KS / 2];
   bf16x8 bml[2][DL];
   float4 iv[4];
+  float4 wv[LQ ? 4 : 1];
 };
 
-template <int KS, bool X3>
-__device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
+template <int KS, bool X3, bool LQ>
+__device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
                                               const float* __restrict__ ivsrc, int t, int c, int h,
-                                              const __bf16* __restrict__ b_lo = nullptr, const __bf16* __restrict__ b_frag_lo = nullptr) {
+                                              const __bf16* __restrict__ b_lo = nullptr, const __bf16* __restrict__ b_frag_lo = nullptr,
+                                              const float* __restrict__ wsrc = nullptr) {
   constexpr int Dp = KS * 16, DT = KS / 2;
   load_bfrag<KS>(b_rows, t, c, h, T.b);
   if constexpr (X3) load_bfrag<KS>(b_lo, t, c, h, T.bl);
@@ -436,6 +442,10 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3>& T, const __bf16* 
     }
 #pragma unroll
   for (int q = 0; q < 4; ++q) T.iv[q] = *reinterpret_cast<const float4*>(ivsrc + 32 * t + 4 * h + 8 * q);
+  if constexpr (LQ) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) T.wv[q] = *reinterpret_cast<const float4*>(wsrc + 32 * t + 4 * h + 8 * q);
+  }
 }
 
 // Structure of the tile loop: TWO operand buffers, the loop unrolled over them, every load issued unconditionally (past the
@@ -445,7 +455,9 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3>& T, const __bf16* 
 // The per-row reciprocal arrays must be readable up to a multiple of 32 rows (tt_score_bwd_dir).
 // X3 (tt_score_bwd_bf16x3): S recomputed with mfma_s from the hi / lo images; the f32 softmax weights are split in registers,
 // w_hi = bf16(w), w_lo = bf16(w - w_hi), and dA += w_hi B_lo + w_lo B_hi + w_hi B_hi (in this order, per b tile).
-template <int KS, int AT, int NW, bool UNIT, bool X3 = false>
+// LQ (tt_score_bwd_bf16_lq): the weight of (a, b) is e_ab (w_b / rowsum_a + w_a / colsum_b) with the sampling weights w of the
+// two rows -- one multiply more per element than e_ab (1 / rowsum_a + 1 / colsum_b).
+template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false>
 __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2, KL = X3 ? KS : 1;
   __shared__ float red[(NW / 2) * ROWS * Dp];
@@ -463,6 +475,8 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
   const float* const inv_a = d1 ? args.d[1].inv_a : args.d[0].inv_a;
   const float* const inv_b = d1 ? args.d[1].inv_b : args.d[0].inv_b;
+  const float* const wt_a = d1 ? args.wt_a[1] : args.wt_a[0];     // (LQ)
+  const float* const wt_b = d1 ? args.wt_b[1] : args.wt_b[0];
   const float c2 = args.c2, kx = UNIT ? args.kexp : 1.f;     // without the forward's reciprocals: 1 / raw sum = 2^c2 / stored sum
   const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
   const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
@@ -472,7 +486,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nT = (Rb + 31) / 32;
   bf16x8 ares[AT][KS], ares_lo[AT][KL];
-  float ia[AT];
+  float ia[AT], ua[AT];
   int pos[AT];
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
@@ -480,6 +494,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
     if (X3) load_bfrag<KL>(dr.a_lo, a0 / 32 + i, c, h, ares_lo[i]);
     const int a = a0 + 32 * i + c;
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
+    if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
     pos[i] = a + off;
   }
   const int posmin = a0 + off, posmax = a0 + ROWS - 1 + off;
@@ -493,11 +508,16 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const bool have_inv = inv_b != nullptr;                      // wave-uniform
   const float* const ivsrc = have_inv ? inv_b : dr.sumexp_b;
   const int tlast = nT - 1;
-  auto compute = [&](const BwdTile<KS, X3>& T, int t) {
+  constexpr bool WLATE = LQ && KS == 16;                       // LQ, D = 256: weights loaded behind the S product, not a tile ahead
+  auto compute = [&](const BwdTile<KS, X3, LQ && !WLATE>& T, int t) {
     const int b_lo = 32 * t;
-    float ib[16];
+    float ib[16], wb[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { ib[4 * q] = T.iv[q].x; ib[4 * q + 1] = T.iv[q].y; ib[4 * q + 2] = T.iv[q].z; ib[4 * q + 3] = T.iv[q].w; }
+    if constexpr (LQ && !WLATE) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { wb[4 * q] = T.wv[q].x; wb[4 * q + 1] = T.wv[q].y; wb[4 * q + 2] = T.wv[q].z; wb[4 * q + 3] = T.wv[q].w; }
+    }
     if (!have_inv) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) ib[r] = __builtin_amdgcn_rcpf(ib[r]) * kx;
@@ -520,10 +540,18 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.b[s], ares[i][s], acc, 0, 0, 0);
       }
+      if constexpr (WLATE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 v = *reinterpret_cast<const float4*>(wt_b + b_lo + 4 * h + 8 * q);
+          wb[4 * q] = v.x; wb[4 * q + 1] = v.y; wb[4 * q + 2] = v.z; wb[4 * q + 3] = v.w;
+        }
+      }
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) * (ia[i] + ib[r]);
+        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) *
+               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
       if (b_lo + 31 >= Rb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -557,19 +585,19 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
         for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s], T.bm[s][d], dacc[i][d], 0, 0, 0);
     }
   };
-  BwdTile<KS, X3> T0, T1;
+  BwdTile<KS, X3, LQ && !WLATE> T0, T1;
   if constexpr (X3 && KS == 16) {                              // x3, D = 256: one tile in flight (two are 544 registers)
     for (int t = wave; t < nT; t += NW) {
-      bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo);
+      bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo, wt_b);
       compute(T0, t);
     }
   } else {
-  bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h, dr.b_lo, dr.b_frag_lo);
+  bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
   __builtin_amdgcn_sched_barrier(0);                           // (issue order pinned: see the forward kernels)
   for (int t = wave; t < nT; t += 2 * NW) {
-    bwd_tile_load<KS, X3>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h, dr.b_lo, dr.b_frag_lo);
+    bwd_tile_load<KS, X3, LQ && !WLATE>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
     compute(T0, t);
-    bwd_tile_load<KS, X3>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h, dr.b_lo, dr.b_frag_lo);
+    bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
     if (t + NW < nT) compute(T1, t + NW);
   }
   }
@@ -625,7 +653,8 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
 // nothing 23.4 -- streaming is no longer the largest term; per SIMD the gradient + S MFMAs (34 GFLOP for both directions: every
 // direction recomputes S) need ~20 us of the matrix pipe, the softmax VALU work ~24 us, the loads ~20 us, and a wave runs the
 // three one after the other.
-template <int KS, int AT, bool UNIT>
+// LQ: as score_bwd_bf16_kernel's.
+template <int KS, int AT, bool UNIT, bool LQ = false>
 __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
   constexpr int NW = 8, Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2;
   constexpr int TLD = Dp + 8;                                   // LDS row of the parked tile: 144 B at D = 64 (conflict-free b128 writes)
@@ -643,6 +672,8 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
   const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
   const float* const inv_a = d1 ? args.d[1].inv_a : args.d[0].inv_a;
   const float* const inv_b = d1 ? args.d[1].inv_b : args.d[0].inv_b;
+  const float* const wt_a = d1 ? args.wt_a[1] : args.wt_a[0];     // (LQ)
+  const float* const wt_b = d1 ? args.wt_b[1] : args.wt_b[0];
   const float c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
   const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
   const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
@@ -652,13 +683,14 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nT = (Rb + 31) / 32;
   bf16x8 ares[AT][KS];
-  float ia[AT];
+  float ia[AT], ua[AT];
   int pos[AT];
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
     load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
     const int a = a0 + 32 * i + c;
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
+    if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
     pos[i] = a + off;
   }
   const int posmin = a0 + off, posmax = a0 + ROWS - 1 + off;
@@ -678,19 +710,29 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
   __bf16* const wr_at = tile + c * TLD + 8 * h;
   const int g16 = lane & 15, cg = (lane >> 4) & 1;
   const __bf16* const tr_at = tile + (4 * h + (g16 >> 2)) * TLD + 16 * cg + 4 * (g16 & 3);
-  struct Tile { bf16x8 b[KS]; float4 iv[4]; };
+  // LQ, D = 128: the weights are loaded behind the tile's S product, not a tile ahead (two tiles' 32 more registers spilled)
+  constexpr bool WLATE = LQ && KS >= 8;
+  struct Tile { bf16x8 b[KS]; float4 iv[4]; float4 wv[LQ ? 4 : 1]; };
   auto load = [&](Tile& T, int t) {
     load_bfrag<KS>(dr.b_rows, t, c, h, T.b);
 #pragma unroll
     for (int q = 0; q < 4; ++q) T.iv[q] = *reinterpret_cast<const float4*>(ivsrc + 32 * t + 4 * h + 8 * q);
+    if constexpr (LQ && !WLATE) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) T.wv[q] = *reinterpret_cast<const float4*>(wt_b + 32 * t + 4 * h + 8 * q);
+    }
   };
   auto compute = [&](const Tile& T, int t) {
     const int b_lo = 32 * t;
 #pragma unroll
     for (int s2 = 0; s2 < KS; ++s2) *reinterpret_cast<bf16x8*>(wr_at + 16 * s2) = T.b[s2];
-    float ib[16];
+    float ib[16], wb[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { ib[4 * q] = T.iv[q].x; ib[4 * q + 1] = T.iv[q].y; ib[4 * q + 2] = T.iv[q].z; ib[4 * q + 3] = T.iv[q].w; }
+    if constexpr (LQ && !WLATE) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { wb[4 * q] = T.wv[q].x; wb[4 * q + 1] = T.wv[q].y; wb[4 * q + 2] = T.wv[q].z; wb[4 * q + 3] = T.wv[q].w; }
+    }
     if (!have_inv) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) ib[r] = __builtin_amdgcn_rcpf(ib[r]) * kx;
@@ -720,10 +762,18 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
       for (int s2 = 0; s2 < KS; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.b[s2], ares[i][s2], acc, 0, 0, 0);
+      if constexpr (WLATE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 v = *reinterpret_cast<const float4*>(wt_b + b_lo + 4 * h + 8 * q);
+          wb[4 * q] = v.x; wb[4 * q + 1] = v.y; wb[4 * q + 2] = v.z; wb[4 * q + 3] = v.w;
+        }
+      }
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) * (ia[i] + ib[r]);
+        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) *
+               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
       if (b_lo + 31 >= Rb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -805,7 +855,9 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
 // half the A-fragment registers and half the staged bytes); the second products stay bf16.
 // AT = 2, NWV = 4: one wave per SIMD with the whole register file; AT = 1, NWV = 8: two waves per SIMD (256 registers each:
 // the hardware then runs one wave's softmax weights beside the other's MFMAs).
-template <int KS, bool UNIT, bool FP8, int AT, int NWV>
+// LQ: as score_bwd_bf16_kernel's; the tile's 32 sampling weights ride in the stage behind its 32 reciprocals (the stage's
+// 256-byte per-row slot held 128 bytes).
+template <int KS, bool UNIT, bool FP8, int AT, int NWV, bool LQ = false>
 __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) {
   constexpr int NTH = NWV * 64, DT = KS / 2, Dp = KS * 16, K64 = FP8 ? KS / 4 : 1;
   constexpr int kRowsB = FP8 ? KS * 512 : KS * 1024, kFragB = KS * 1024, kIvB = 256, kStageB = kRowsB + kFragB + kIvB;
@@ -826,6 +878,8 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
   const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
   const float* const inv_a = d1 ? args.d[1].inv_a : args.d[0].inv_a;
   const float* const inv_b = d1 ? args.d[1].inv_b : args.d[0].inv_b;
+  const float* const wt_a = d1 ? args.wt_a[1] : args.wt_a[0];     // (LQ)
+  const float* const wt_b = d1 ? args.wt_b[1] : args.wt_b[0];
   const float c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
   const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
   const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
@@ -837,7 +891,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
   bf16x8 ares[AT][(FP8 || ALDS) ? 1 : KS];
   i32x8 ares8[AT][K64];
   bf16x8* const a_lds = reinterpret_cast<bf16x8*>(lds_raw + 2 * kStageB) + (size_t)wave * AT * KS * 64 + lane;   // (ALDS) [a tile][k-step][lane]
-  float ia[AT];
+  float ia[AT], ua[AT];
   int pos[AT];
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
@@ -849,6 +903,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
     } else load_bfrag<((FP8 || ALDS) ? 1 : KS)>(dr.a_rows, min(at0 + i, nTa_img - 1), c, h, ares[i]);
     const int a = 32 * (at0 + i) + c;
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
+    if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
     pos[i] = a + off;
   }
   const int posmin = 32 * at0 + off, posmax = 32 * (at0 + AT) - 1 + off;
@@ -880,8 +935,9 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
                                          (__attribute__((address_space(3))) void*)(base + (wave * 64 + NTH * q) * 16), 16, 0, 0);
       }
     }
-    if (wave == 0 && lane < 8)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ivsrc + 32 * tn + 4 * lane),
+    if (wave == 0 && lane < (LQ ? 16 : 8))
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(LQ && lane >= 8 ? wt_b + 32 * tn + 4 * (lane - 8)
+                                                                                                    : ivsrc + 32 * tn + 4 * lane),
                                        (__attribute__((address_space(3))) void*)(base + kRowsB + kFragB), 16, 0, 0);
   };
   stage_dma(0, 0);
@@ -936,11 +992,18 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
             acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j], ALDS ? af[i][j] : ares[i][(FP8 || ALDS) ? 0 : s0 + j], acc[i], 0, 0, 0);
       }
     }
-    float ib[16];
+    float ib[16], wb[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4 v = *reinterpret_cast<const float4*>(ivp + 4 * h + 8 * q);
       ib[4 * q] = v.x; ib[4 * q + 1] = v.y; ib[4 * q + 2] = v.z; ib[4 * q + 3] = v.w;
+    }
+    if constexpr (LQ) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(ivp + 32 + 4 * h + 8 * q);
+        wb[4 * q] = v.x; wb[4 * q + 1] = v.y; wb[4 * q + 2] = v.z; wb[4 * q + 3] = v.w;
+      }
     }
     if (!have_inv) {
 #pragma unroll
@@ -957,7 +1020,8 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[i][r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][r], c1, c2))) * (ia[i] + ib[r]);
+        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[i][r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][r], c1, c2))) *
+               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
       if (ragged) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -1427,6 +1491,22 @@ __global__ __launch_bounds__(256) void pack_fp8_tile_kernel(PackBatch batch, int
 
 }  // namespace
 
+// the *_lq backward entries: per-direction sampling weights into the launch arguments (lq == NULL: the plain entry)
+static int bwd_lq_args(BwdArgs& a, const tt_score_bwd_lq* lq, int32_t n_dirs, float inv_t, const char* who) {
+  if (!lq) return TT_OK;
+  if (2.f * fabsf(inv_t) > kLqMaxTwoInvT) {
+    tt_set_error("%s: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", who, inv_t, kLqMaxTwoInvT);
+    return TT_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < 2; ++i) {
+    const tt_score_bwd_lq& q = lq[i < n_dirs ? i : 0];
+    TT_CHECK_ARG(q.w_a && q.w_b && tt_aligned(q.w_b, 16), "%s: direction %d: w_a / w_b NULL or w_b not 16-byte aligned", who, i);
+    a.wt_a[i] = q.w_a;
+    a.wt_b[i] = q.w_b;
+  }
+  return TT_OK;
+}
+
 extern "C" {
 
 size_t tt_score_pack_bytes(int64_t R, int32_t D) {
@@ -1510,23 +1590,27 @@ int tt_score_fwd_bf16(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs,
   return TT_OK;
 }
 
-int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
-                      const float* d_loss, float scale, tt_stream stream) {
-  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "tt_score_bwd_bf16: need 1 or 2 directions");
-  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_bwd_bf16: D=%d not in [1,256]", D);
+}  // extern "C"
+
+// tt_score_bwd_bf16 and, with lq != NULL, tt_score_bwd_bf16_lq (the LQ instantiations)
+static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                    const float* d_loss, float scale, tt_stream stream, const tt_score_bwd_lq* lq, const char* who) {
+  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
+  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
   BwdArgs a{};
+  if (int rc = bwd_lq_args(a, lq, n_dirs, inv_t, who)) return rc;
   int64_t maxRa = 0;
   bool unit = true;
   for (int i = 0; i < 2; ++i) {
     const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
     TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1,
-                 "tt_score_bwd_bf16: bad direction %d", i);
-    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16), "tt_score_bwd_bf16: sumexp_b must be 16-byte aligned");
+                 "%s: bad direction %d", who, i);
+    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16), "%s: sumexp_b must be 16-byte aligned", who);
     const PackedView vb = view(d.B_packed, d.Rb, D);
     const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
     a.d[i] = DirBwd{view(d.A_packed, d.Ra, D).rows, vb.rows, vb.frag, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA,
                       inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b};
-    TT_CHECK_ARG(d.inv_b == nullptr || tt_aligned(d.inv_b, 16), "tt_score_bwd_bf16: inv_b must be 16-byte aligned");
+    TT_CHECK_ARG(d.inv_b == nullptr || tt_aligned(d.inv_b, 16), "%s: inv_b must be 16-byte aligned", who);
     unit = unit && ab == inv_t * kLog2e;
     maxRa = d.Ra > maxRa ? d.Ra : maxRa;
   }
@@ -1539,7 +1623,9 @@ int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs,
 #define TT_BWD(KS, AT, NW)                                                                                     \
   do {                                                                                                         \
     const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (unit) score_bwd_bf16_kernel<KS, AT, NW, true><<<grid, NW * 64, 0, st>>>(a);                            \
+    if (lq && unit) score_bwd_bf16_kernel<KS, AT, NW, true, false, true><<<grid, NW * 64, 0, st>>>(a);        \
+    else if (lq) score_bwd_bf16_kernel<KS, AT, NW, false, false, true><<<grid, NW * 64, 0, st>>>(a);           \
+    else if (unit) score_bwd_bf16_kernel<KS, AT, NW, true><<<grid, NW * 64, 0, st>>>(a);                       \
     else score_bwd_bf16_kernel<KS, AT, NW, false><<<grid, NW * 64, 0, st>>>(a);                                \
   } while (0)
   // enough rows for every SIMD to own 64 of them: the workgroup-staged form (no split along b, operands shared through LDS)
@@ -1548,7 +1634,13 @@ int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs,
   do {                                                                                                         \
     const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT_ * NWV_), (unsigned)n_dirs);                              \
     const size_t lds = 2 * (size_t)(KS * 2048 + 256) + (KS == 16 ? (size_t)NWV_ * AT_ * KS * 1024 : 0);        \
-    if (unit) {                                                                                                \
+    if (lq && unit) {                                                                                          \
+      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, true, false, AT_, NWV_, true>);                              \
+      score_bwd_rows_kernel<KS, true, false, AT_, NWV_, true><<<grid, NWV_ * 64, lds, st>>>(a);                \
+    } else if (lq) {                                                                                           \
+      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, false, false, AT_, NWV_, true>);                             \
+      score_bwd_rows_kernel<KS, false, false, AT_, NWV_, true><<<grid, NWV_ * 64, lds, st>>>(a);               \
+    } else if (unit) {                                                                                         \
       TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, true, false, AT_, NWV_>);                                    \
       score_bwd_rows_kernel<KS, true, false, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                      \
     } else {                                                                                                   \
@@ -1569,17 +1661,34 @@ int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs,
   if (Dp == 32) TT_BWD(2, 2, 8);
   else if (Dp == 64) {                                    // one streamed image, transposing LDS reads
     const dim3 grid((unsigned)tt_cdiv(maxRa, 64), (unsigned)n_dirs);
-    if (unit) score_bwd_tr_kernel<4, 2, true><<<grid, 512, 0, st>>>(a);
+    if (lq && unit) score_bwd_tr_kernel<4, 2, true, true><<<grid, 512, 0, st>>>(a);
+    else if (lq) score_bwd_tr_kernel<4, 2, false, true><<<grid, 512, 0, st>>>(a);
+    else if (unit) score_bwd_tr_kernel<4, 2, true><<<grid, 512, 0, st>>>(a);
     else score_bwd_tr_kernel<4, 2, false><<<grid, 512, 0, st>>>(a);
   } else if (Dp == 128) {                                 // the one-image form, one a tile per workgroup
     const dim3 grid((unsigned)tt_cdiv(maxRa, 32), (unsigned)n_dirs);
-    if (unit) score_bwd_tr_kernel<8, 1, true><<<grid, 512, 0, st>>>(a);
+    if (lq && unit) score_bwd_tr_kernel<8, 1, true, true><<<grid, 512, 0, st>>>(a);
+    else if (lq) score_bwd_tr_kernel<8, 1, false, true><<<grid, 512, 0, st>>>(a);
+    else if (unit) score_bwd_tr_kernel<8, 1, true><<<grid, 512, 0, st>>>(a);
     else score_bwd_tr_kernel<8, 1, false><<<grid, 512, 0, st>>>(a);
   }
   else TT_BWD(16, 1, 4);
 #undef TT_BWD
   TT_LAUNCH_CHECK();
   return TT_OK;
+}
+
+extern "C" {
+
+int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                      const float* d_loss, float scale, tt_stream stream) {
+  return bwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, nullptr, "tt_score_bwd_bf16");
+}
+
+int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
+                         float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
+  TT_CHECK_ARG(lq, "tt_score_bwd_bf16_lq: NULL lq");
+  return bwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, lq, "tt_score_bwd_bf16_lq");
 }
 
 size_t tt_score_pack_fp8_bytes(int64_t R, int32_t D) {
@@ -1760,19 +1869,23 @@ int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dir
 // takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
 // workgroup-staged form's stages would both double for the lo images.  One wave per SIMD (4 waves): the hi and lo operands of
 // two b tiles in flight need more than the 256 registers a wave gets at two waves per SIMD.
-int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
-                        const float* d_loss, float scale, tt_stream stream) {
-  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "tt_score_bwd_bf16x3: need 1 or 2 directions");
-  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_bwd_bf16x3: D=%d not in [1,256]", D);
+}  // extern "C"
+
+// tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq
+static int bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                      const float* d_loss, float scale, tt_stream stream, const tt_score_bwd_lq* lq, const char* who) {
+  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
+  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
   BwdArgs a{};
+  if (int rc = bwd_lq_args(a, lq, n_dirs, inv_t, who)) return rc;
   int64_t maxRa = 0;
   bool unit = true;
   for (int i = 0; i < 2; ++i) {
     const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
     TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1,
-                 "tt_score_bwd_bf16x3: bad direction %d", i);
+                 "%s: bad direction %d", who, i);
     TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16) && (d.inv_b == nullptr || tt_aligned(d.inv_b, 16)),
-                 "tt_score_bwd_bf16x3: per-row arrays must be 16-byte aligned");
+                 "%s: per-row arrays must be 16-byte aligned", who);
     const PackedView vb = view(d.B_packed, d.Rb, D), vbl = view_lo(d.B_packed, d.Rb, D);
     const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
     a.d[i] = DirBwd{view(d.A_packed, d.Ra, D).rows, vb.rows, vb.frag, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA,
@@ -1789,7 +1902,9 @@ int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dir
 #define TT_BWD3(KS, AT, NW)                                                                                    \
   do {                                                                                                         \
     const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (unit) score_bwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                      \
+    if (lq && unit) score_bwd_bf16_kernel<KS, AT, NW, true, true, true><<<grid, NW * 64, 0, st>>>(a);          \
+    else if (lq) score_bwd_bf16_kernel<KS, AT, NW, false, true, true><<<grid, NW * 64, 0, st>>>(a);             \
+    else if (unit) score_bwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                 \
     else score_bwd_bf16_kernel<KS, AT, NW, false, true><<<grid, NW * 64, 0, st>>>(a);                          \
   } while (0)
   // two a tiles per workgroup at D <= 64: half the workgroups, half the L2 bytes of the streamed b images
@@ -1800,6 +1915,19 @@ int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dir
 #undef TT_BWD3
   TT_LAUNCH_CHECK();
   return TT_OK;
+}
+
+extern "C" {
+
+int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                        const float* d_loss, float scale, tt_stream stream) {
+  return bwd_bf16x3(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, nullptr, "tt_score_bwd_bf16x3");
+}
+
+int tt_score_bwd_bf16x3_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
+                           float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
+  TT_CHECK_ARG(lq, "tt_score_bwd_bf16x3_lq: NULL lq");
+  return bwd_bf16x3(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, lq, "tt_score_bwd_bf16x3_lq");
 }
 
 }  // extern "C"

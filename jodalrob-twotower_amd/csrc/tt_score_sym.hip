@@ -64,6 +64,8 @@ struct SymArgs {
   int want_rank;
   const void* a_lo;                    // bf16x3 (X3 kernels): the lo rows images
   const void* b_lo;
+  const float* lq_n;                   // LQ kernels: [R] log sampling probabilities of the notice rows a / company rows b
+  const float* lq_c;
 };
 
 // Notice tiles are staged through LDS once per WORKGROUP (all 8 waves sweep the same tiles I): read straight from L2 by
@@ -91,7 +93,12 @@ struct SymStage {
 // side of the positives of every notice tile but their own.
 // X3: bf16x3 operands -- the S tile is mfma_s's three chains (hi_b lo_a, lo_b hi_a, hi_b hi_a): bit-identical to the directional
 // x3 forward's row direction.
-template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false>
+// LQ: logQ-corrected sums (tt_score_fwd_sym_bf16_lq): row sums add e_ab w_b, column sums e_ab u_a, with w / u the sampling weights
+// of the companies / notices (tt_lq_weight).  w_b is per register -- 16 weights per lane, formed once for the resident tile J;
+// u_a is per lane -- the workgroup forms the weights of its NI * 32 notice rows once, into LDS behind the stage buffers, and a
+// wave reads one per swept tile.  The column accumulators take an fma where they took an add; the row partial two fma chains.  (Plain fmas, not inline asm: an
+// asm fma reading the v_exp_f32 result right behind it skips the trans-use wait state the compiler inserts for its own ops.)
+template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false>
 __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   using ST = SymStage<KS, FP8, X3>;
   constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, kImgB = ST::kImgB, K64 = FP8 ? KS / 4 : 1, KL = X3 ? KS : 1;
@@ -106,10 +113,35 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   float* s_mb = lds + (1 * kSymWaves + wave) * slots;
   float* s_ma = lds + (2 * kSymWaves + wave) * slots;
   char* stage = reinterpret_cast<char*>(lds + 3 * kSymWaves * slots);
+  float* s_wn = reinterpret_cast<float*>(stage + 2 * ST::kBytes);   // (LQ) [NI * 32] notice weights u_a
+  // (LQ, bf16x3 at D = 256: the resident tile's company weights live in LDS, [wave][32], read per tile -- in registers they spilled)
+  constexpr bool WLDS = LQ && X3 && KS == 16;
+  float* s_wc = s_wn + NI * 32 + wave * 32;
   const int J0 = ((int)blockIdx.x * kSymWaves + wave) * JT;  // this wave's company tiles J0 .. J0 + JT - 1
   const int I0 = (int)blockIdx.y * NI, I1 = min(I0 + NI, nT);
   const bool active = J0 < nT;
   for (int i = lane; i < slots; i += 64) { s_sum[i] = 0.f; s_mb[i] = kNegBig; s_ma[i] = kNegBig; }
+  float wb[JT][WLDS ? 1 : 16];                             // (LQ) company weights w_b of the resident tiles, 0 past R
+  if constexpr (LQ) {
+    static_assert(!FP8, "logQ correction: bf16 and bf16x3 operands only");
+    for (int i = threadIdx.x; i < slots; i += kSymThreads) {
+      const int a = I0 * 32 + i;
+      s_wn[i] = a < R ? tt_lq_weight(g.lq_n[a]) : 0.f;    // (read after the sweep's first barrier)
+    }
+    if constexpr (WLDS) {
+      if (lane < 32) s_wc[lane] = 32 * J0 + lane < R ? tt_lq_weight(g.lq_c[32 * J0 + lane]) : 0.f;
+    } else {
+#pragma unroll
+      for (int j = 0; j < JT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int b = 32 * (J0 + j) + rowmap(r, h);
+          wb[j][(WLDS ? 0 : r)] = b < R ? tt_lq_weight(g.lq_c[b]) : 0.f;
+        }
+    }
+  }
+  // the company weight of register r (resident tile j)
+  auto wreg = [&](int j, int r) -> float { if constexpr (WLDS) return s_wc[rowmap(r, h)]; else return wb[j][(WLDS ? 0 : r)]; };
   const float c1 = g.c1, c2 = g.c2;
   auto ex = [&](float x) { return UNIT ? __builtin_amdgcn_exp2f(x) : __builtin_amdgcn_exp2f(__builtin_fmaf(x, c1, c2)); };
   float colacc[JT][16];
@@ -201,6 +233,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
             for (int j = 0; j < JT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bres[j][s], af[s], acc[j], 0, 0, 0);
         }
         const int il = (I - I0) * 32 + c;
+        const float ua = LQ ? s_wn[il] : 1.f;
         float rs_tot = 0.f, xb_tot = kNegBig, xa_tot = kNegBig;
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
@@ -209,11 +242,20 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
             float e[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) e[r] = ex(acc[j][r]);
+            if constexpr (LQ) {
+#pragma unroll
+              for (int r = 0; r < 16; ++r) colacc[j][r] = __builtin_fmaf(e[r], ua, colacc[j][r]);
+              float t0 = e[0] * wreg(j, 0), t1 = e[8] * wreg(j, 8);
+#pragma unroll
+              for (int r = 1; r < 8; ++r) { t0 = __builtin_fmaf(e[r], wreg(j, r), t0); t1 = __builtin_fmaf(e[8 + r], wreg(j, 8 + r), t1); }
+              rs_tot += half_sum(t0 + t1);
+            } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) colacc[j][r] = add_asm(colacc[j][r], e[r]);
             float t0 = (e[0] + e[1]) + (e[2] + e[3]), t1 = (e[4] + e[5]) + (e[6] + e[7]);
             float t2 = (e[8] + e[9]) + (e[10] + e[11]), t3 = (e[12] + e[13]) + (e[14] + e[15]);
             rs_tot += half_sum((t0 + t1) + (t2 + t3));
+            }
             if (g.want_rank) {
               float m = max3_asm(acc[j][0], acc[j][1], acc[j][2]);
 #pragma unroll
@@ -232,8 +274,13 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
               const float x = acc[j][r];
               const bool valid = b < R && a < R;
               const float e = valid ? ex(x) : 0.f;
-              colacc[j][r] += e;
-              rsum += e;
+              if constexpr (LQ) {
+                colacc[j][r] = __builtin_fmaf(e, ua, colacc[j][r]);
+                rsum = __builtin_fmaf(e, wreg(j, r), rsum);
+              } else {
+                colacc[j][r] += e;
+                rsum += e;
+              }
               xb = (valid && b < a) ? fmaxf(xb, x) : xb;
               xa = (valid && b > a) ? fmaxf(xa, x) : xa;
               dg = (b == a) ? x : dg;
@@ -315,6 +362,8 @@ struct Fin1Args {
   int fp8;                             // the rows images hold fp8 (tt_score_bf16.h) instead of bf16
   const void* a_lo; const void* b_lo;  // bf16x3: the lo rows images (their columns are added to the hi images')
   float* part;                         // [n_wg][4 + 2 * Dp]: l, hits, dsum, (pad), U[Dp], V[Dp]
+  const float* lq_n; const float* lq_c;  // LQ: [R] log sampling probabilities of the notice / company rows
+  float* w_n; float* w_c;              // LQ: their weights tt_lq_weight(lq) (0 past R): what tt_score_bwd_bf16_lq takes
 };
 
 __device__ __forceinline__ float slab_sum4(const float* __restrict__ slab, int64_t Rp, int n, int q, int i) {
@@ -340,6 +389,9 @@ __device__ __forceinline__ float slab_max4(const float* __restrict__ slab, int64
   return s;
 }
 
+// LQ: the row and column terms subtract the positive's log weight (the corrected positive s_ii - lq_i), taken exactly as
+// -kLqL - lq, never as the log of a rounded weight; the weights themselves go out for the backward.
+template <bool LQ = false>
 __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
   const int i = blockIdx.x * kFinRows + lane;              // slab rows are padded: i < Rp always
@@ -445,7 +497,14 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
       f.rowsum[i] = rs_shifted;
       f.colsum[i] = cs_shifted;
       f.diag[i] = d;
-      l = (logf(rs_shifted) + f.shift - d) + (logf(cs_shifted) + f.shift - d);
+      if constexpr (LQ) {
+        const float lqn = f.lq_n[i], lqc = f.lq_c[i];
+        l = (logf(rs_shifted) + f.shift - d - tt_lq_log_weight(lqc)) + (logf(cs_shifted) + f.shift - d - tt_lq_log_weight(lqn));
+        f.w_n[i] = tt_lq_weight(lqn);
+        f.w_c[i] = tt_lq_weight(lqc);
+      } else {
+        l = (logf(rs_shifted) + f.shift - d) + (logf(cs_shifted) + f.shift - d);
+      }
       dsum = d;
       if (f.want_rank) {
         const float xb = fmaxf(fmaxf(red[2][0][lane], red[2][1][lane]), fmaxf(red[2][2][lane], red[2][3][lane]));
@@ -457,6 +516,7 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
     } else {
       // rows past the end, up to this workgroup's 64: tt_score_bwd_bf16 reads the reciprocals a whole 32-row tile at a time
       f.inv_row[i] = 0.f; f.inv_col[i] = 0.f; f.rowsum[i] = 1.f; f.colsum[i] = 1.f;
+      if constexpr (LQ) { f.w_n[i] = 0.f; f.w_c[i] = 0.f; }
     }
     float v[3] = {l, hit, dsum};                           // butterfly inside the one wave that holds the rows
 #pragma unroll
@@ -507,12 +567,18 @@ inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D) {
 static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
                        float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col, float* diag,
                        int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
-                       bool fp8, const char* who, bool x3 = false) {
+                       bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
+                       float* w_n = nullptr, float* w_c = nullptr) {
+  const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
   TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
   if (2.f * fabsf(inv_t) > 80.f) {
     tt_set_error("%s: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", who, inv_t);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (lq && 2.f * fabsf(inv_t) > kLqMaxTwoInvT) {
+    tt_set_error("%s: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", who, inv_t, kLqMaxTwoInvT);
     return TT_ERR_UNSUPPORTED;
   }
   tt_ctx sized = *ctx;
@@ -542,12 +608,26 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   g.cs = reinterpret_cast<float*>(ws + L.off_cs);
   g.diag_raw = reinterpret_cast<float*>(ws + L.off_diag);
   g.want_rank = want_rank ? 1 : 0;
+  g.lq_n = lq_n;
+  g.lq_c = lq_c;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // fp8, D = 256: two company tiles per wave (half the workgroups along J, half the slab rows)
   const int jt = (fp8 && L.Dp == 256) ? 2 : 1;
   const int n_groups = (int)tt_cdiv(L.nT, kSymWaves * jt);
   const dim3 grid((unsigned)n_groups, (unsigned)L.n_chunks);
   const size_t slot_bytes = sizeof(float) * 3 * kSymWaves * L.NI * 32;
+  const size_t wn_bytes = sizeof(float) * (L.NI * 32 + kSymWaves * 32);   // (LQ) notice weights (+ company weights, x3 D = 256)
+#define TT_SYMLQ(KS, X3_)                                                                                               \
+  do {                                                                                                                  \
+    const size_t lds = slot_bytes + 2 * SymStage<KS, false, X3_>::kBytes + wn_bytes;                                    \
+    if (unit) {                                                                                                         \
+      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, true, false, 1, X3_, true>);                                           \
+      score_fwd_sym_kernel<KS, true, false, 1, X3_, true><<<grid, kSymThreads, lds, st>>>(g);                           \
+    } else {                                                                                                            \
+      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, false, false, 1, X3_, true>);                                          \
+      score_fwd_sym_kernel<KS, false, false, 1, X3_, true><<<grid, kSymThreads, lds, st>>>(g);                          \
+    }                                                                                                                   \
+  } while (0)
 #define TT_SYM(KS, F8, JT_)                                                                                             \
   do {                                                                                                                  \
     const size_t lds = slot_bytes + 2 * SymStage<KS, F8>::kBytes;                                                       \
@@ -565,7 +645,19 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
       score_fwd_sym_kernel<KS, false, false, 1, true><<<grid, kSymThreads, lds, st>>>(g);                               \
     }                                                                                                                   \
   } while (0)
-  if (x3) {
+  if (lq) {
+    if (x3) {
+      if (L.Dp == 32) TT_SYMLQ(2, true);
+      else if (L.Dp == 64) TT_SYMLQ(4, true);
+      else if (L.Dp == 128) TT_SYMLQ(8, true);
+      else TT_SYMLQ(16, true);
+    } else {
+      if (L.Dp == 32) TT_SYMLQ(2, false);
+      else if (L.Dp == 64) TT_SYMLQ(4, false);
+      else if (L.Dp == 128) TT_SYMLQ(8, false);
+      else TT_SYMLQ(16, false);
+    }
+  } else if (x3) {
     if (L.Dp == 32) TT_SYM3(2);
     else if (L.Dp == 64) TT_SYM3(4);
     else if (L.Dp == 128) TT_SYM3(8);
@@ -582,6 +674,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   }
 #undef TT_SYM
 #undef TT_SYM3
+#undef TT_SYMLQ
   TT_LAUNCH_CHECK();
   Fin1Args f{};
   f.rs = g.rs; f.mb = g.mb; f.ma = g.ma; f.cs = g.cs; f.diag_raw = g.diag_raw;
@@ -592,7 +685,9 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   f.fp8 = fp8 ? 1 : 0;
   f.a_lo = g.a_lo; f.b_lo = g.b_lo;
   f.part = reinterpret_cast<float*>(ws + L.off_part);
-  score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
+  f.lq_n = lq_n; f.lq_c = lq_c; f.w_n = w_n; f.w_c = w_c;
+  if (lq) score_sym_finish1_kernel<true><<<(unsigned)L.n_wg, 256, 0, st>>>(f);
+  else score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   TT_LAUNCH_CHECK();
   Finish2Rider fr{f.part, L.n_wg, L.Dp, (float)B, f.unscale, out8, loss_out};
   if (L.n_wg >= 256) {                                   // large batches: fold the records 32 to one before the one-workgroup reduction
@@ -646,6 +741,24 @@ int tt_score_fwd_sym_bf16x3(tt_ctx* ctx, const void* N_packed, const void* C_pac
                             tt_stream stream) {
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3", true);
+}
+
+int tt_score_fwd_sym_bf16_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
+                             float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c, float* rowsum, float* colsum,
+                             float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8,
+                             float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(lq_n && lq_c && w_n && w_c, "tt_score_fwd_sym_bf16_lq: NULL argument");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_lq", false, lq_n, lq_c, w_n, w_c);
+}
+
+int tt_score_fwd_sym_bf16x3_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                               float shift, float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c, float* rowsum,
+                               float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank,
+                               float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(lq_n && lq_c && w_n && w_c, "tt_score_fwd_sym_bf16x3_lq: NULL argument");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3_lq", true, lq_n, lq_c, w_n, w_c);
 }
 
 }  // extern "C"

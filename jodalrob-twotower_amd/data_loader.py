@@ -48,7 +48,9 @@ class DevicePairLoader:
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
-                 shuffle: bool, seed: int = 42):
+                 shuffle: bool, seed: int = 42, log_q=None):
+        """log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
+        every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
@@ -58,6 +60,24 @@ class DevicePairLoader:
         # a third of a 68-ms epoch at batch 8192 (profiles/NOTES.md, round 4)
         self._gen = torch.Generator(device=self.pairs.device)
         self._gen.manual_seed(seed)
+        self.log_q = None
+        self.set_log_q(log_q)
+
+    def set_log_q(self, log_q) -> None:
+        """(notice [Nn], company [Nc]) f32 log sampling probabilities per entity, or None: turns the logQ correction on / off for
+        every batch this loader produces from now on."""
+        if log_q is None:
+            self.log_q = None
+            return
+        if not isinstance(log_q, (tuple, list)) or len(log_q) != 2:
+            raise ValueError("log_q must be a (notice, company) pair of per-entity f32 tensors")
+        out = []
+        for name, t, n in (("notice", log_q[0], len(self.notice)), ("company", log_q[1], len(self.company))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n:
+                raise ValueError(f"log_q {name}: need a float32 tensor of shape [{n}], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            out.append(t.to(self.pairs.device).contiguous())
+        self.log_q = tuple(out)
 
     def __len__(self) -> int:
         return (self.pairs.shape[0] + self.batch_size - 1) // self.batch_size
@@ -70,7 +90,28 @@ class DevicePairLoader:
 
     def batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
         sel = self.pairs[lo:lo + self.batch_size] if order is None else self.pairs[order[lo:lo + self.batch_size]]
-        return {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        if self.log_q is not None:
+            out["notice"]["log_q"] = self.log_q[0][sel[:, 0]]
+            out["company"]["log_q"] = self.log_q[1][sel[:, 1]]
+        return out
+
+    def epoch_log_q(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """f32 [n_batches, 2, Bp] (Bp = batch_size rounded up to 4): the pairs' log q (notice row, company row) in this epoch's order,
+        batch k's two sides at [k, 0, :m] / [k, 1, :m] -- ONE gather per epoch.  Every slice starts 16 bytes aligned, as the hand-over
+        launch's copy segments must (a [2, P] array's slices would not whenever P or the batch size is not a multiple of 4).
+        None without log_q."""
+        if self.log_q is None:
+            return None
+        n, B = self.pairs.shape[0], self.batch_size
+        sel = self.pairs if order is None else self.pairs[order]
+        nb, Bp = (n + B - 1) // B, (B + 3) // 4 * 4
+        flat = torch.zeros((2, nb * B), dtype=torch.float32, device=self.pairs.device)
+        flat[0, :n] = self.log_q[0][sel[:, 0]]
+        flat[1, :n] = self.log_q[1][sel[:, 1]]
+        out = torch.zeros((nb, 2, Bp), dtype=torch.float32, device=self.pairs.device)
+        out[:, :, :B] = flat.view(2, nb, B).transpose(0, 1)
+        return out
 
     def __iter__(self) -> Iterator[Dict]:
         order = self.epoch_order()
@@ -104,6 +145,10 @@ class DevicePairLoader:
         order = self.epoch_order()
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))
+        lq = self.epoch_log_q(order)
+        if lq is not None and U > 1:
+            raise NotImplementedError("the logQ correction is not supported by the unrolled step")
+        kw = lambda lo, m: {} if lq is None else {"log_q": (lq[lo // B, 0, :m], lq[lo // B, 1, :m])}
         lo = 0
         while U > 1 and lo + U * B <= n:                      # unrolled.UnrolledTrainStep: U full batches per graph launch
             for r in graphed_step.steps_from_store(self.notice, self.company, self.pairs, order, [lo + j * B for j in range(U)]):
@@ -111,9 +156,9 @@ class DevicePairLoader:
             lo += U * B
         for lo in range(lo, n, B):
             if lo + B <= n:
-                yield graphed_step.step_from_store(self.notice, self.company, self.pairs, order, lo)
+                yield graphed_step.step_from_store(self.notice, self.company, self.pairs, order, lo, **kw(lo, B))
             elif ragged_step is not None and ragged_step.static["notice"]["dense"].shape[0] == n - lo:
-                yield ragged_step.step_from_store(self.notice, self.company, self.pairs, order, lo)
+                yield ragged_step.step_from_store(self.notice, self.company, self.pairs, order, lo, **kw(lo, n - lo))
             elif eager_step is not None:
                 yield eager_step(self.batch(order, lo))
 
@@ -124,8 +169,15 @@ class DevicePairLoader:
         r = n % B
         if r == 0 or n < B:
             return None
+        return self._head(r)
+
+    def _head(self, r: int) -> Dict:
         sel = self.pairs[:r]
-        return {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        if self.log_q is not None:
+            out["notice"]["log_q"] = self.log_q[0][sel[:, 0]]
+            out["company"]["log_q"] = self.log_q[1][sel[:, 1]]
+        return out
 
 
 def sklearn_split_indices(n: int, test_size: float, seed: int) -> Tuple[np.ndarray, np.ndarray]:

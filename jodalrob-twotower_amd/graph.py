@@ -29,6 +29,7 @@ from .optim import FusedAdam
 
 class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
+    _log_q_ok = True               # batches may carry "log_q" (the logQ correction); the unrolled / segmented steps refuse them
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
@@ -43,6 +44,14 @@ class GraphedTrainStep:
         tt_score_loss_finish) += the step's figures inside the replay -- an epoch's mean loss / accuracy (the reference driver's
         avg_train_loss: scripts/train.py:357-358) without a host sync per step.  metric_sums: add into THIS tensor (another captured
         step's sums: the two then share one epoch total; what it holds survives this object's warm-up)."""
+        # logQ correction: an example batch with "log_q" (either side) gives both sides a static [B] buffer; every hand-over then
+        # brings this step's values as two more copy segments of its one launch (the captured forward reads the buffers)
+        self._has_log_q = any(example_batch[side].get("log_q") is not None for side in ("notice", "company"))
+        if self._has_log_q:
+            if not self._log_q_ok:
+                raise NotImplementedError(f"the logQ correction (a batch with 'log_q') is not supported by {type(self).__name__}")
+            if getattr(task, "exchange", None) is not None:
+                raise NotImplementedError("the logQ correction (a batch with 'log_q') is not supported by the sharded task")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
@@ -51,6 +60,12 @@ class GraphedTrainStep:
         self.static = {side: {"dense": example_batch[side]["dense"].clone(),
                               "kjt": KeyedJaggedTensor(example_batch[side]["kjt"].keys(), example_batch[side]["kjt"].values().clone())}
                        for side in ("notice", "company")}
+        if self._has_log_q:
+            B = example_batch["notice"]["dense"].shape[0]
+            self._lq_zero = torch.zeros(B, dtype=torch.float32, device=dev)
+            for side in ("notice", "company"):
+                t = example_batch[side].get("log_q")
+                self.static[side]["log_q"] = self._check_log_q(t, side, B, dev).clone() if t is not None else self._lq_zero.clone()
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
@@ -384,11 +399,35 @@ class GraphedTrainStep:
         ops.copy_multi([self._fill_slot()])
         self._mark_slot()
 
+    @staticmethod
+    def _check_log_q(t, side, B, dev):
+        """t as a contiguous, 16-byte aligned f32 [B] on dev (the hand-over launch's copy segments must be aligned: a misaligned
+        view is copied once)"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"{side} log_q must be a float32 tensor of shape [{B}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != dev:
+            raise ValueError(f"{side} log_q is on {t.device}, the captured step on {dev}")
+        t = t.contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    def _log_q_pairs(self, lq_n, lq_c):
+        """copy segments of this step's log q into the static buffers (a side given as None: zeros)"""
+        B, dev = self._lq_zero.shape[0], self._lq_zero.device
+        return [(self.static[side]["log_q"], self._check_log_q(t, side, B, dev) if t is not None else self._lq_zero)
+                for side, t in (("notice", lq_n), ("company", lq_c))]
+
     def _handover_pairs(self, batch: Optional[Dict]):
         """(copy segments, per-side id sources) that hand `batch` over into the static buffers (None: nothing to copy)."""
         pairs, src_ids = [], []                                 # src_ids per side: where this step's ids are read from
         if batch is None:
             return pairs, None
+        lq_n, lq_c = batch["notice"].get("log_q"), batch["company"].get("log_q")
+        if (lq_n is not None or lq_c is not None) != self._has_log_q:
+            raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
+                             " a log_q, the batch " + ("has none" if self._has_log_q else "carries one"))
+        if self._has_log_q:
+            pairs += self._log_q_pairs(lq_n, lq_c)
         for side in ("notice", "company"):
             d, v = batch[side]["dense"], batch[side]["kjt"].values()
             sd, sv = self.static[side]["dense"], self.static[side]["kjt"].values()
@@ -423,19 +462,28 @@ class GraphedTrainStep:
             ex.poll_overflow()                                  # sharded tables: a bucket overflow rejects the step (non-blocking)
         return self.result
 
-    def step_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor] = None, offset: int = 0):
+    def step_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor] = None, offset: int = 0,
+                        log_q=None):
         """Train on the B pairs `pairs[order[offset : offset + B]]` (order None: `pairs[offset : offset + B]`) gathered straight
         out of the device-resident feature stores into the static buffers -- ONE launch (tt_batch_ingest_store: dense rows, ids,
         key-major fused rows, the step scalars) and the replay; nothing per step crosses PCIe and no batch tensors are built
         (the reference assembles the batch on the host and copies it over: unified_bid_data_loader.py:461-504, :630-684;
         scripts/train.py:261-273).  `pairs`: int64 [P, 2] on the device, (notice row, company row) per pair; the stores are
-        data_loader.DeviceFeatureStore objects (`.dense` f32 [N, D], `.categorical` int64 [N, K])."""
-        self._ingest_from_store(notice_store, company_store, pairs, order, offset)
+        data_loader.DeviceFeatureStore objects (`.dense` f32 [N, D], `.categorical` int64 [N, K]).
+        log_q: (notice, company) f32 [B] of this step's pairs for a step captured with a log_q (DevicePairLoader.step_batches passes
+        slices of its per-epoch array): two more copy segments of the same launch."""
+        if (log_q is not None) != self._has_log_q:
+            raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
+                             " a log_q, step_from_store got " + ("none" if self._has_log_q else "one"))
+        self._ingest_from_store(notice_store, company_store, pairs, order, offset,
+                                extra=self._log_q_pairs(*log_q) if log_q is not None else None)
         self._mark_slot()
         return self._replay()
 
-    def _ingest_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor], offset: int, ahead: int = 0):
-        """The hand-over launch of step_from_store (tt_batch_ingest_store) into the static buffers; `ahead`: _fill_slot."""
+    def _ingest_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor], offset: int, ahead: int = 0,
+                           extra=None):
+        """The hand-over launch of step_from_store (tt_batch_ingest_store) into the static buffers; `ahead`: _fill_slot; `extra`:
+        more copy segments for the same launch."""
         B = self.static["notice"]["dense"].shape[0]
         if pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
             raise ValueError("step_from_store: pairs must be a contiguous int64 [P, 2] tensor")
@@ -453,7 +501,7 @@ class GraphedTrainStep:
             sides.append(ops.LookupSide(None, e._key_row_offset, e._key_vocab, outs[i], len(e.keys)))
             stores.append(ops.StoreSide(flat[base + i:], 2, fs.dense, fs.categorical, sd, sv))
         rows_km = self._ingest[2] if self._ingest is not None else None
-        ops.batch_ingest_store([self._fill_slot(ahead)], sides, stores, B, order, rows_km, offset if order is not None else 0,
+        ops.batch_ingest_store((extra or []) + [self._fill_slot(ahead)], sides, stores, B, order, rows_km, offset if order is not None else 0,
                                table=self._ingest[0].weight if xs is not None else None,
                                rows_sm=getattr(self, "_rows_sm", None) if (self._ingest is not None and xs is None) else None,
                                cvt=self._cvt(), table_rows=self._table_rows(self._ingest[0]) if self._ingest is not None else 0)

@@ -620,6 +620,110 @@ def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, sc
     return dN, dC
 
 
+# ---- logQ sampling-bias correction (the *_lq entries of include/twotower.h) ----------------------------------------------
+LQ_MAX_TWO_INV_T = 40.0      # the *_lq entries support 2/T <= 40 (T >= 0.05)
+
+
+def _lq_vec(lq, B, dev, name):
+    """f32 [B] log sampling probabilities, contiguous on `dev` (validated: no device sync)"""
+    if not isinstance(lq, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(lq).__name__}")
+    if lq.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {lq.dtype}")
+    if lq.dim() != 1 or lq.shape[0] != B:
+        raise ValueError(f"{name} must have shape [{B}], got {list(lq.shape)}")
+    if lq.device != dev:
+        raise ValueError(f"{name} is on {lq.device}, the scores on {dev}")
+    return lq.contiguous()
+
+
+def _lq_check_t(inv_t):
+    if 2.0 * abs(inv_t) > LQ_MAX_TWO_INV_T:
+        raise ValueError(f"logQ correction needs 2/T <= {LQ_MAX_TWO_INV_T:g} (T >= 0.05), got 1/T = {inv_t:g}")
+
+
+def score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n: float = 1.0, want_rank: bool = True, x3: bool = False):
+    """logQ-corrected score_fwd_sym (tt_score_fwd_sym_bf16_lq / _bf16x3_lq): lq_n / lq_c f32 [B] log sampling probabilities of
+    the batch's notices / companies.  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), (w_n, w_c), out8, loss):
+    (w_n, w_c) are the sampling weights score_bwd_bf16_lq takes."""
+    dev = Np.device
+    lq_n, lq_c = _lq_vec(lq_n, B, dev, "lq_n"), _lq_vec(lq_c, B, dev, "lq_c")
+    Bp = (B + 63) // 64 * 64
+    f = torch.empty((7, Bp), dtype=torch.float32, device=dev)         # rowsum, colsum, diag, 1/rowsum', 1/colsum', w_n, w_c
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    out8 = torch.empty(8, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lib = L.load()
+    if L.riders_deferred(dev, 2):
+        ws = torch.empty(lib.tt_score_fwd_sym_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
+        out8._tt_keep = ws
+    else:
+        ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
+    name = "tt_score_fwd_sym_bf16x3_lq" if x3 else "tt_score_fwd_sym_bf16_lq"
+    with _timed(name):
+        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), L.ptr(lq_n),
+                                   L.ptr(lq_c), L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]), L.ptr(f[5]), L.ptr(f[6]),
+                                   L.ptr(f[2]), L.ptr(rank), L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
+    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), (f[5][:B], f[6][:B]), out8, loss
+
+
+def score_bwd_bf16_lq(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, w, scale_n: float = 1.0, inv=None, x3: bool = False):
+    """logQ-corrected score_bwd_bf16 (tt_score_bwd_bf16_lq / _bf16x3_lq): w = (w_n, w_c) and rowsum / colsum / inv from
+    score_fwd_sym_lq (w_n / w_c are views of arrays padded to 64 rows, as the kernels read them)."""
+    dev = Np.device
+    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
+    arr = (L.ScoreBwdDir * 2)()
+    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
+    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)
+    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)
+    lq = (L.ScoreBwdLq * 2)()
+    lq[0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))                     # direction (N, C): A = notices, B = companies
+    lq[1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
+    name = "tt_score_bwd_bf16x3_lq" if x3 else "tt_score_bwd_bf16_lq"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), arr, lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
+    return dN, dC
+
+
+def score_dir_fwd_lq(A, Bm, inv_t, shift, lq_b, diag_offset=0, want_sumscore=True):
+    """score_dir_fwd with the B rows' log sampling probabilities lq_b [Rb] (tt_score_dir_fwd_lq)."""
+    dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
+    lq_b = _lq_vec(lq_b, Rb, dev, "lq_b")
+    f = torch.empty((3, Ra), dtype=torch.float32, device=dev)
+    rank = torch.empty(Ra, dtype=torch.int32, device=dev)
+    with _timed("tt_score_dir_fwd_lq"):
+        L.check(L.load().tt_score_dir_fwd_lq(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(lq_b),
+                                             L.ptr(f[0]), L.ptr(f[1]), L.ptr(rank), L.ptr(f[2]) if want_sumscore else None,
+                                             L.stream(dev)), "tt_score_dir_fwd_lq")
+    return f[0], f[1], rank, f[2]
+
+
+def score_loss_finish_lq(B, shift, lq_n, lq_c, rowsum, colsum, diag, row_rank, col_rank, sumscore):
+    """score_loss_finish with the corrected positives (tt_score_loss_finish_lq)."""
+    dev = rowsum.device
+    lq_n, lq_c = _lq_vec(lq_n, B, dev, "lq_n"), _lq_vec(lq_c, B, dev, "lq_c")
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    with _timed("tt_score_loss_finish_lq"):
+        L.check(L.load().tt_score_loss_finish_lq(L.ctx(dev), B, shift, L.ptr(lq_n), L.ptr(lq_c), L.ptr(rowsum), L.ptr(colsum),
+                                                 L.ptr(diag), L.ptr(row_rank), L.ptr(col_rank), L.ptr(sumscore), L.ptr(out),
+                                                 L.ptr(loss), L.stream(dev)), "tt_score_loss_finish_lq")
+    return out, loss
+
+
+def score_dir_bwd_lq(A, Bm, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale):
+    """score_dir_bwd with the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq)."""
+    dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
+    lq_a, lq_b = _lq_vec(lq_a, Ra, dev, "lq_a"), _lq_vec(lq_b, Rb, dev, "lq_b")
+    dA = torch.empty_like(A)
+    with _timed("tt_score_dir_bwd_lq"):
+        L.check(L.load().tt_score_dir_bwd_lq(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(lq_a),
+                                             L.ptr(lq_b), L.ptr(sumexp_a), L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA),
+                                             L.stream(dev)), "tt_score_dir_bwd_lq")
+    return dA
+
+
 def score_fwd_bf16_rect(Ap0, Bp0, Ap1, Bp1, Ra, Rb, off, D, inv_t, shift, full_rank=True):
     """Rectangular form (global in-batch negatives): direction 0 = rows of A0 [Ra] against all rows of B0 [Rb], direction 1 =
     rows of A1 [Ra] against B1 [Rb]; the positive of local row a sits at column a + off.  Returns (sumexp0, sumexp1, diag,

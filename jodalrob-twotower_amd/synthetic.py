@@ -76,7 +76,10 @@ class SyntheticSource:
     positive (notice, company) pairs."""
 
     def __init__(self, n_notice: int, n_company: int, n_pairs: int, vocab_notice, vocab_company, seed: int = 0,
-                 text_dim: int = 768):
+                 text_dim: int = 768, pair_zipf_alpha: Optional[float] = None):
+        """pair_zipf_alpha: draw each pair's company from a Zipf(alpha) law over company rank (company 0 the most paired) instead
+        of uniformly -- bidding data's skew; None keeps the uniform draw and its random stream exactly."""
+        self.pair_zipf_alpha = pair_zipf_alpha
         self.n = {"notice": n_notice, "company": n_company}
         self.vocab = {"notice": list(vocab_notice), "company": list(vocab_company)}
         self.n_pairs, self.seed, self.text_dim = n_pairs, seed, text_dim
@@ -105,4 +108,7 @@ class SyntheticSource:
         rng = np.random.default_rng([self.seed, 3])
         n = self.n_pairs if limit is None else min(self.n_pairs, limit)
         ni, ci = rng.integers(0, self.n["notice"], n), rng.integers(0, self.n["company"], n)
+        if self.pair_zipf_alpha is not None:
+            w = np.arange(1, self.n["company"] + 1, dtype=np.float64) ** -float(self.pair_zipf_alpha)
+            ci = np.random.default_rng([self.seed, 4]).choice(self.n["company"], n, p=w / w.sum())
         return [((f"N{a:09d}", "00"), f"{1000000000 + b}") for a, b in zip(ni, ci)]

@@ -49,14 +49,20 @@ class _DenseLossFn(torch.autograd.Function):
 class _ScoreCEFn(torch.autograd.Function):
     """loss = 0.5 * [CE(S, diag) + CE(S^T, diag)],  S = N C^T / T   (:99-134); out8 carries the metrics.
     score_dtype 'fp32': exact-f32 MFMA path (parity); 'bf16': bf16-operand MFMA fast path; 'bf16x3': split-bf16 operands
-    (hi + lo, three bf16 MFMAs per product: near-f32 products on the bf16 pipe)."""
+    (hi + lo, three bf16 MFMAs per product: near-f32 products on the bf16 pipe).
+    lq_n / lq_c (f32 [B], both or neither): logQ sampling-bias correction (include/twotower.h *_lq entries) -- the loss and the
+    gradients of the corrected softmax, metrics on the raw scores."""
 
     @staticmethod
-    def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None):
+    def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
+                lq_n=None, lq_c=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
         ctx.x3 = False
+        ctx.lq = None
+        if lq_n is not None:
+            return _ScoreCEFn._forward_lq(ctx, n, c, inv_t, shift, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c)
         if score_dtype == "fp8":
             # e4m3 operands for the S products (v_mfma_scale_f32_32x32x64_f8f6f4: twice the bf16 MFMA rate), everything else as
             # the bf16 path; always the single-pass forward and the workgroup-staged backward (BASELINE configs[4])
@@ -128,21 +134,69 @@ class _ScoreCEFn(torch.autograd.Function):
         return loss, out8, row_rank
 
     @staticmethod
+    def _forward_lq(ctx, n, c, inv_t, shift, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c):
+        """The corrected forward: bf16 / bf16x3 always on the symmetric kernel (its row ranks and metrics are the raw scores'); the
+        first call's column top-1 rate (a diagnostic only) comes from the uncorrected two-direction kernel."""
+        B, D = n.shape
+        ops._lq_check_t(inv_t)
+        if score_dtype in ("bf16", "bf16x3"):
+            x3 = score_dtype == "bf16x3"
+            if x3:
+                scale_n = 1.0
+                Np, Cp = ops.score_pack2_bf16x3(n, c, scale_n, 1.0)
+            elif packed_n is not None and packed_c is not None:
+                Np, Cp = packed_n, packed_c
+                scale_n = 1.0 if scale_n is None else scale_n
+            else:
+                scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
+                Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
+            rowsum, colsum, diag, row_rank, inv, w, out8, loss = ops.score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n,
+                                                                                      True, x3=x3)
+            if want_col_rank:
+                col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
+                out8 = out8.clone()
+                out8[5] = (col_rank == 0).float().mean()
+            ctx.packed = (Np, Cp, scale_n, inv)
+            ctx.x3 = x3
+            ctx.lq = w
+        else:
+            rowsum, diag, row_rank, sumscore = ops.score_dir_fwd_lq(n, c, inv_t, shift, lq_c, 0, True)
+            colsum, _, col_rank, _ = ops.score_dir_fwd_lq(c, n, inv_t, shift, lq_n, 0, False)
+            out8, loss = ops.score_loss_finish_lq(B, shift, lq_n, lq_c, rowsum, colsum, diag, row_rank, col_rank, sumscore)
+            ctx.packed = None
+            ctx.lq = (lq_n.contiguous(), lq_c.contiguous())
+        ctx.fp8 = False
+        ctx.save_for_backward(n, c, rowsum, colsum)
+        ctx.inv_t, ctx.shift = inv_t, shift
+        ctx.mark_non_differentiable(out8, row_rank)
+        ctx.set_materialize_grads(False)
+        return loss, out8, row_rank
+
+    @staticmethod
     def backward(ctx, d_loss, _d_out8, _d_rank):
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return None, None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None, None, None
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
+        if ctx.lq is not None:
+            if ctx.packed is not None:
+                dN, dC = ops.score_bwd_bf16_lq(ctx.packed[0], ctx.packed[1], B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale,
+                                               ctx.lq, ctx.packed[2], ctx.packed[3], x3=ctx.x3)
+            else:
+                lqn, lqc = ctx.lq
+                dN = ops.score_dir_bwd_lq(n, c, ctx.inv_t, ctx.shift, 0, lqn, lqc, rowsum, colsum, d_loss, scale)
+                dC = ops.score_dir_bwd_lq(c, n, ctx.inv_t, ctx.shift, 0, lqc, lqn, colsum, rowsum, d_loss, scale)
+            return dN, dC, None, None, None, None, None, None, None, None, None
         if ctx.packed is not None:
             dN, dC = ops.score_bwd_bf16(ctx.packed[0], ctx.packed[1], B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale,
                                         ctx.packed[2], ctx.packed[3], fp8=ctx.fp8, x3=ctx.x3)
         else:
             dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale)
             dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale)
-        return dN, dC, None, None, None, None, None, None, None
+        return dN, dC, None, None, None, None, None, None, None, None, None
 
 
 class _Result(dict):
@@ -216,9 +270,14 @@ class TwoTowerTrainTask(nn.Module):
         nb, cb = notice_input["dense"].size(0), company_input["dense"].size(0)
         if nb != cb:                                                                         # :64-67
             raise ValueError(f"Notice와 Company 배치 크기가 다릅니다: {nb} vs {cb}")
+        lq = self._batch_log_q(notice_input, company_input, nb)
         notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
-        loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                       not hasattr(self, "_pair_check_done"))
+        if lq is None:
+            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
+                                           not hasattr(self, "_pair_check_done"))
+        else:
+            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
+                                           not hasattr(self, "_pair_check_done"), log_q=lq)
         if not hasattr(self, "_pair_check_done"):                                            # :82-84
             self._verify_positive_pair_alignment(out8)
             self._pair_check_done = True
@@ -249,8 +308,43 @@ class TwoTowerTrainTask(nn.Module):
                           sim_thunk=lambda: ops.score_matrix(n_det, c_det, inv_t))
             return res, rank
 
-    def _score_ce(self, n, c, inv_t, first_call):
-        """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it."""
+    def _batch_log_q(self, notice_input, company_input, B):
+        """(lq_n, lq_c) f32 [B] from the batch's "log_q" entries (logQ correction; a missing side counts as zeros), or None when
+        neither side carries one.  Refuses what the corrected loss does not cover -- never ignores a log_q."""
+        lq_n, lq_c = notice_input.get("log_q"), company_input.get("log_q")
+        if lq_n is None and lq_c is None:
+            return None
+        if self._dense_loss:
+            raise ValueError("the logQ correction (a batch with 'log_q') is not supported by the dense loss path "
+                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
+        if self.score_dtype == "fp8":
+            raise ValueError("the logQ correction (a batch with 'log_q') is not supported for score_dtype='fp8'")
+        ref = notice_input["dense"]
+        out = []
+        for name, t in (("notice", lq_n), ("company", lq_c)):
+            if t is None:
+                out.append(torch.zeros(B, dtype=torch.float32, device=ref.device))
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
+                raise ValueError(f"batch['{name}']['log_q'] must be a float32 tensor of shape [{B}], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            if t.device != ref.device:
+                raise ValueError(f"batch['{name}']['log_q'] is on {t.device}, the batch on {ref.device}")
+            out.append(t.contiguous())
+        return out[0], out[1]
+
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None):
+        """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it.
+        log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn)."""
+        if log_q is not None:
+            if self._dense_loss or self.score_dtype == "fp8":
+                raise ValueError("the logQ correction covers the fused cross-entropy with score_dtype fp32 / bf16 / bf16x3 only")
+            if n.shape != c.shape:
+                raise ValueError("the logQ correction needs as many notice rows as company rows")
+            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
+            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
+                return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, None, None, None, log_q[0], log_q[1])
+            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], log_q[0], log_q[1])
         if self._dense_loss:
             if n.shape != c.shape:
                 raise ValueError("the dense loss path needs as many notice rows as company rows")

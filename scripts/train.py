@@ -104,6 +104,11 @@ def main():
     ap.add_argument("--table-optimizer", choices=["adam", "rowwise_adagrad"], default="adam",
                     help="optimiser of the embedding tables (the towers keep Adam); rowwise_adagrad keeps one float per table row")
     ap.add_argument("--table-lr", type=float, default=None, help="learning rate of the tables under rowwise_adagrad (default: the towers' learning rate)")
+    ap.add_argument("--pair-zipf", type=float, default=None,
+                    help="synthetic pairs: each pair's company drawn from a Zipf(A) law over company rank (default: uniform)")
+    ap.add_argument("--logq-correction", action="store_true",
+                    help="logQ sampling-bias correction of the in-batch softmax: log sampling probabilities estimated from the TRAIN pairs, "
+                         "attached to the train loader only (evaluation stays uncorrected)")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
     a = ap.parse_args()
     config = {"batch_size": a.batch_size, "test_split": 0.2, "shuffle_seed": 42, "pair_limit": a.pairs,
@@ -131,10 +136,16 @@ def main():
     schema = build_torchrec_schema_from_meta(notice_table="notice", company_table="company", pair_table="bid_two_tower",
                                              pair_notice_id_cols=["bidntceno", "bidntceord"], pair_company_id_cols=["bizno"],
                                              metadata_path=str(meta))
-    source = synthetic.SyntheticSource(a.entities, a.entities, a.pairs, real["notice"]["vocab_sizes"], real["company"]["vocab_sizes"])
+    source = synthetic.SyntheticSource(a.entities, a.entities, a.pairs, real["notice"]["vocab_sizes"], real["company"]["vocab_sizes"],
+                                       pair_zipf_alpha=a.pair_zipf)
     train_loader, test_loader = create_unified_bid_dataloaders(source, schema, batch_size=config["batch_size"],
                                                                test_split=config["test_split"], shuffle_seed=config["shuffle_seed"],
                                                                test_mode=True, pair_limit=config["pair_limit"], device=device)
+    if a.logq_correction:                                # exact: batches are uniform draws from this fixed pair list
+        from jodalrob_twotower_amd.sampling_bias import log_sampling_probs
+        tp = train_loader.pairs
+        train_loader.set_log_q((log_sampling_probs(tp[:, 0], len(train_loader.notice)),
+                                log_sampling_probs(tp[:, 1], len(train_loader.company))))
     train_task = create_two_tower_train_task(schema.notice.categorical, schema.company.categorical, metadata_path=str(meta),
                                              categorical_embedding_dim=config["categorical_embedding_dim"],
                                              notice_dense_input_dim=config["notice_dense_input_dim"],
