@@ -5,8 +5,24 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 
 #include "twotower.h"
+
+// runtime flags -> template arguments: tt_dispatch(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+// and returns its result (one instantiation of f's body per combination of flags)
+template <class F>
+inline auto tt_dispatch(F&& f) {
+  return f();
+}
+template <class F, class... Bs>
+inline auto tt_dispatch(F&& f, bool b, Bs... bs) {
+  if (b) return tt_dispatch([&](auto... c) { return f(std::true_type{}, c...); }, bs...);
+  return tt_dispatch([&](auto... c) { return f(std::false_type{}, c...); }, bs...);
+}
+// an int as a template argument of a generic lambda (tile shapes: go(tt_c<4>, tt_c<2>, tt_c<8>))
+template <int N>
+constexpr std::integral_constant<int, N> tt_c{};
 
 struct tt_ctx {
   int device;

@@ -536,6 +536,51 @@ inline bool vec_ok(const float* p, int D) { return tt_aligned(p, 16) && (D % 4 =
 
 }  // namespace
 
+// tt_score_dir_fwd and, with lq_b != NULL, tt_score_dir_fwd_lq (arguments checked by the entries)
+static int dir_fwd(const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift, int64_t diag_offset,
+                   const float* lq_b, float* sumexp, float* diag, int32_t* rank, float* sumscore, tt_stream stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
+  tt_dispatch([&](auto vec, auto lq) {
+    score_dir_fwd_kernel<vec, lq><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
+  }, vec_ok(A, D) && vec_ok(Bm, D), lq_b != nullptr);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// tt_score_loss_finish and, with lq_n / lq_c != NULL, tt_score_loss_finish_lq
+static int loss_finish(int64_t B, float shift, const float* lq_n, const float* lq_c, const float* rowsum, const float* colsum,
+                       const float* diag, const int32_t* row_rank, const int32_t* col_rank, const float* sumscore, float* out8,
+                       float* loss_out, tt_stream stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (lq_n) loss_finish_lq_kernel<<<1, 1024, 0, st>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out, lq_n, lq_c);
+  else loss_finish_kernel<<<1, 1024, 0, st>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// tt_score_dir_bwd and, with lq_a / lq_b != NULL, tt_score_dir_bwd_lq
+static int dir_bwd(const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift, int64_t diag_offset,
+                   const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale,
+                   float* dA, tt_stream stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
+  const auto go = [&](auto nch) {
+    tt_dispatch([&](auto vec, auto lq) {
+      score_dir_bwd_kernel<nch, vec, lq><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss,
+                                                                     scale, dA, lq_a, lq_b);
+    }, vec_ok(A, D) && vec_ok(Bm, D), lq_a != nullptr);
+  };
+  switch ((D + DK - 1) / DK) {
+    case 1: go(tt_c<1>); break;
+    case 2: go(tt_c<2>); break;
+    case 3: go(tt_c<3>); break;
+    default: go(tt_c<4>); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 extern "C" {
 
 int tt_score_dir_fwd(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
@@ -547,14 +592,7 @@ int tt_score_dir_fwd(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, i
     tt_set_error("tt_score_dir_fwd: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", inv_t);
     return TT_ERR_UNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
-  if (vec_ok(A, D) && vec_ok(Bm, D))
-    score_dir_fwd_kernel<true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore);
-  else
-    score_dir_fwd_kernel<false><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return dir_fwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, nullptr, sumexp, diag, rank, sumscore, stream);
 }
 
 int tt_score_loss_finish(tt_ctx* ctx, int64_t B, float shift, const float* rowsum, const float* colsum, const float* diag,
@@ -562,9 +600,7 @@ int tt_score_loss_finish(tt_ctx* ctx, int64_t B, float shift, const float* rowsu
                          tt_stream stream) {
   TT_CHECK_ARG(ctx && rowsum && colsum && diag && row_rank && col_rank && out8, "tt_score_loss_finish: NULL argument");
   TT_CHECK_ARG(B >= 1, "tt_score_loss_finish: B < 1");
-  loss_finish_kernel<<<1, 1024, 0, reinterpret_cast<hipStream_t>(stream)>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return loss_finish(B, shift, nullptr, nullptr, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out, stream);
 }
 
 int tt_score_dir_bwd(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
@@ -576,22 +612,7 @@ int tt_score_dir_bwd(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, i
     tt_set_error("tt_score_dir_bwd: D=%d > %d not supported", D, 4 * DK);
     return TT_ERR_UNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
-  const bool v = vec_ok(A, D) && vec_ok(Bm, D);
-  const int nch = (D + DK - 1) / DK;
-#define TT_BWD(NCHV)                                                                                                          \
-  if (v) score_dir_bwd_kernel<NCHV, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA); \
-  else score_dir_bwd_kernel<NCHV, false><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA);
-  switch (nch) {
-    case 1: TT_BWD(1) break;
-    case 2: TT_BWD(2) break;
-    case 3: TT_BWD(3) break;
-    default: TT_BWD(4) break;
-  }
-#undef TT_BWD
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, nullptr, nullptr, sumexp_a, sumexp_b, d_loss, scale, dA, stream);
 }
 
 int tt_score_dir_fwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
@@ -604,14 +625,7 @@ int tt_score_dir_fwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra
     tt_set_error("tt_score_dir_fwd_lq: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", inv_t, kLqMaxTwoInvT);
     return TT_ERR_UNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
-  if (vec_ok(A, D) && vec_ok(Bm, D))
-    score_dir_fwd_kernel<true, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
-  else
-    score_dir_fwd_kernel<false, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return dir_fwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_b, sumexp, diag, rank, sumscore, stream);
 }
 
 int tt_score_loss_finish_lq(tt_ctx* ctx, int64_t B, float shift, const float* lq_n, const float* lq_c, const float* rowsum,
@@ -619,10 +633,7 @@ int tt_score_loss_finish_lq(tt_ctx* ctx, int64_t B, float shift, const float* lq
                             const float* sumscore, float* out8, float* loss_out, tt_stream stream) {
   TT_CHECK_ARG(ctx && lq_n && lq_c && rowsum && colsum && diag && row_rank && col_rank && out8, "tt_score_loss_finish_lq: NULL argument");
   TT_CHECK_ARG(B >= 1, "tt_score_loss_finish_lq: B < 1");
-  loss_finish_lq_kernel<<<1, 1024, 0, reinterpret_cast<hipStream_t>(stream)>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore,
-                                                                                  out8, loss_out, lq_n, lq_c);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return loss_finish(B, shift, lq_n, lq_c, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out, stream);
 }
 
 int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
@@ -638,22 +649,7 @@ int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra
     tt_set_error("tt_score_dir_bwd_lq: 1/temperature = %g: the logQ-corrected softmax needs 2/T <= %g", inv_t, kLqMaxTwoInvT);
     return TT_ERR_UNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
-  const bool v = vec_ok(A, D) && vec_ok(Bm, D);
-  const int nch = (D + DK - 1) / DK;
-#define TT_BWD(NCHV)                                                                                                          \
-  if (v) score_dir_bwd_kernel<NCHV, true, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA, lq_a, lq_b); \
-  else score_dir_bwd_kernel<NCHV, false, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, dA, lq_a, lq_b);
-  switch (nch) {
-    case 1: TT_BWD(1) break;
-    case 2: TT_BWD(2) break;
-    case 3: TT_BWD(3) break;
-    default: TT_BWD(4) break;
-  }
-#undef TT_BWD
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream);
 }
 
 int tt_score_matrix(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float* S,

@@ -1507,6 +1507,210 @@ static int bwd_lq_args(BwdArgs& a, const tt_score_bwd_lq* lq, int32_t n_dirs, fl
   return TT_OK;
 }
 
+// (KS, AT, NW) of the two-direction forward per padded D = 32, 64, 128, 256
+constexpr int kFwdTile[2][4][3] = {
+    // bf16.  D <= 64: 32 rows per wave (AT = 1), 8 waves, 2 workgroups per CU measured best (43.6 us; AT = 2: 48.0, 4 waves:
+    // 53.4, 16 waves: 48.7 at B = 8192)
+    {{2, 2, 8}, {4, 1, 8}, {8, 2, 8}, {16, 1, 8}},
+    // bf16x3.  D = 256: one wave per SIMD: the hi / lo fragments of A and of a b tile are 256 registers
+    {{2, 2, 8}, {4, 1, 8}, {8, 1, 8}, {16, 1, 4}},
+};
+
+// tt_score_fwd_bf16 / tt_score_fwd_bf16x3 (x3: the operands are [hi | lo] packings)
+static int fwd_bf16(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift, tt_stream stream,
+                    bool x3, const char* who) {
+  TT_CHECK_ARG(ctx && dirs && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
+  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
+  if (2.f * fabsf(inv_t) > 80.f) {
+    tt_set_error("%s: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", who, inv_t);
+    return TT_ERR_UNSUPPORTED;
+  }
+  FwdArgs a{};
+  int64_t maxRa = 0;
+  bool unit = true;
+  for (int i = 0; i < 2; ++i) {
+    const tt_score_fwd_dir& d = dirs[i < n_dirs ? i : 0];
+    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp && d.Ra >= 1 && d.Rb >= 1, "%s: bad direction %d", who, i);
+    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale;
+    a.d[i] = DirFwd{view(d.A_packed, d.Ra, D).rows, view(d.B_packed, d.Rb, D).rows, d.Ra, d.Rb, d.diag_offset, d.sumexp, d.diag, d.rank, d.sumscore,
+                    d.rank ? (d.rank_mode == 1 ? 1 : 2) : 0, inv_t * kLog2e / ab, inv_t / ab, d.inv_sumexp};
+    if (x3) {
+      a.d[i].a_lo = view_lo(d.A_packed, d.Ra, D).rows;
+      a.d[i].b_lo = view_lo(d.B_packed, d.Rb, D).rows;
+    }
+    unit = unit && ab == inv_t * kLog2e;                // exactly: the caller got the scale from tt_score_unit_scale(inv_t)
+    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
+  }
+  a.c2 = -shift * kLog2e;
+  a.kexp = exp2f(a.c2);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const auto go = [&](auto x3c, auto di) {
+    constexpr int KS = kFwdTile[x3c][di][0], AT = kFwdTile[x3c][di][1], NW = kFwdTile[x3c][di][2];
+    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);
+    tt_dispatch([&](auto u) { score_fwd_bf16_kernel<KS, AT, NW, u, x3c><<<grid, NW * 64, 0, st>>>(a); }, unit);
+  };
+  tt_dispatch([&](auto x3c) {
+    switch (padded_d(D)) {
+      case 32: return go(x3c, tt_c<0>);
+      case 64: return go(x3c, tt_c<1>);
+      case 128: return go(x3c, tt_c<2>);
+      default: return go(x3c, tt_c<3>);
+    }
+  }, x3);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// ---- backward: the launch arguments of every form, then one launch per form --------------------------------------------
+enum class Operands { bf16, bf16x3, fp8 };
+
+struct BwdSetup {
+  BwdArgs a;
+  int64_t maxRa;
+  int n_dirs;
+  bool unit, lq;
+};
+
+// checks the entry's arguments and fills the launch arguments from tt_score_bwd_dir[] (lq != NULL: the *_lq entries)
+static int bwd_setup(BwdSetup& s, Operands op, tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs,
+                     int32_t D, float inv_t, float shift, const float* d_loss, float scale, const char* who) {
+  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
+  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
+  s = BwdSetup{};
+  if (int rc = bwd_lq_args(s.a, lq, n_dirs, inv_t, who)) return rc;
+  s.n_dirs = n_dirs;
+  s.unit = true;
+  s.lq = lq != nullptr;
+  for (int i = 0; i < 2; ++i) {
+    const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
+    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1, "%s: bad direction %d", who, i);
+    if (op == Operands::bf16) {
+      TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16), "%s: sumexp_b must be 16-byte aligned", who);
+      TT_CHECK_ARG(d.inv_b == nullptr || tt_aligned(d.inv_b, 16), "%s: inv_b must be 16-byte aligned", who);
+    } else {
+      TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16) && (d.inv_b == nullptr || tt_aligned(d.inv_b, 16)),
+                   "%s: per-row arrays must be 16-byte aligned", who);
+    }
+    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
+    DirBwd& r = s.a.d[i];
+    r = DirBwd{nullptr, nullptr, nullptr, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA, inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b};
+    if (op == Operands::fp8) {
+      const PackedView8 va = view8(d.A_packed, d.Ra, D), vb = view8(d.B_packed, d.Rb, D);
+      r.a_rows = reinterpret_cast<const __bf16*>(va.rows8);
+      r.b_rows = reinterpret_cast<const __bf16*>(vb.rows8);
+      r.b_frag = vb.frag;
+      r.b_frag8 = vb.frag8;
+    } else {
+      const PackedView vb = view(d.B_packed, d.Rb, D);
+      r.a_rows = view(d.A_packed, d.Ra, D).rows;
+      r.b_rows = vb.rows;
+      r.b_frag = vb.frag;
+      if (op == Operands::bf16x3) {
+        const PackedView vbl = view_lo(d.B_packed, d.Rb, D);
+        r.a_lo = view_lo(d.A_packed, d.Ra, D).rows;
+        r.b_lo = vbl.rows;
+        r.b_frag_lo = vbl.frag;
+      }
+    }
+    s.unit = s.unit && ab == inv_t * kLog2e;
+    s.maxRa = d.Ra > s.maxRa ? d.Ra : s.maxRa;
+  }
+  s.a.c2 = -shift * kLog2e;
+  s.a.kexp = exp2f(s.a.c2);
+  s.a.d_loss = d_loss;
+  s.a.D = D;
+  return TT_OK;
+}
+
+// b-split form (score_bwd_bf16_kernel)
+template <int KS, int AT, int NW, bool X3>
+static void launch_bsplit(const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
+  tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, X3, l><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
+}
+
+// one streamed image, transposing LDS reads (score_bwd_tr_kernel)
+template <int KS, int AT>
+static void launch_tr(const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
+  tt_dispatch([&](auto u, auto l) { score_bwd_tr_kernel<KS, AT, u, l><<<grid, 512, 0, st>>>(s.a); }, s.unit, s.lq);
+}
+
+// workgroup-staged form (score_bwd_rows_kernel); FP8: fp8 S operands (no logQ form)
+template <int KS, bool FP8, int AT, int NWV>
+static int launch_rows(tt_ctx* ctx, const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT * NWV), (unsigned)s.n_dirs);
+  const size_t lds = 2 * (size_t)((FP8 ? KS * 512 : KS * 1024) + KS * 1024 + 256) + (!FP8 && KS == 16 ? (size_t)NWV * AT * KS * 1024 : 0);
+  const auto go = [&](auto u, auto l) -> int {
+    TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, u, FP8, AT, NWV, l>);
+    score_bwd_rows_kernel<KS, u, FP8, AT, NWV, l><<<grid, NWV * 64, lds, st>>>(s.a);
+    return TT_OK;
+  };
+  if constexpr (FP8) return tt_dispatch([&](auto u) { return go(u, std::false_type{}); }, s.unit);
+  else return tt_dispatch(go, s.unit, s.lq);
+}
+
+// fp8 operands for both products (score_bwd_rows8_kernel)
+template <int KS, int AT, int NWV>
+static int launch_rows8(tt_ctx* ctx, const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT * NWV), (unsigned)s.n_dirs);
+  const size_t lds = (size_t)4 * KS * 1024 + 512 + (KS == 16 ? (size_t)NWV * AT * KS * 512 : 0);
+  return tt_dispatch([&](auto u) -> int {
+    TT_LDS_ONCE(lds, &score_bwd_rows8_kernel<KS, u, AT, NWV>);
+    score_bwd_rows8_kernel<KS, u, AT, NWV><<<grid, NWV * 64, lds, st>>>(s.a);
+    return TT_OK;
+  }, s.unit);
+}
+
+// tt_score_bwd_bf16 and, with lq != NULL, tt_score_bwd_bf16_lq
+static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t,
+                    float shift, const float* d_loss, float scale, tt_stream stream, const char* who) {
+  BwdSetup s;
+  if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Dp = padded_d(D);
+  // enough rows for every SIMD to own 64 of them: the workgroup-staged form (no split along b, operands shared through LDS)
+  if (s.maxRa >= ctx->score_bwd_rows_min && Dp >= 64) {
+    // D = 256: one a tile per wave with its A fragments in LDS (16 KB per wave: four waves beside the two 33-KB stages) -- with
+    // two a tiles per wave the A fragments (128 registers) and the accumulators (256) filled the whole file and hipcc shuttled
+    // hundreds of values between AGPRs, VGPRs and scratch (20-116 bytes of scratch per lane in the tile loop)
+    const int rc = Dp == 64 ? launch_rows<4, false, 2, 4>(ctx, s, st)
+                   : Dp == 128 ? launch_rows<8, false, 2, 4>(ctx, s, st) : launch_rows<16, false, 1, 4>(ctx, s, st);
+    if (rc) return rc;
+  } else if (Dp == 32) {
+    launch_bsplit<2, 2, 8, false>(s, st);
+  } else if (Dp == 64) {
+    launch_tr<4, 2>(s, st);
+  } else if (Dp == 128) {                                 // the one-image form, one a tile per workgroup
+    launch_tr<8, 1>(s, st);
+  } else {
+    launch_bsplit<16, 1, 4, false>(s, st);
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq.
+// One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
+// takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
+// workgroup-staged form's stages would both double for the lo images.  One wave per SIMD (4 waves): the hi and lo operands of
+// two b tiles in flight need more than the 256 registers a wave gets at two waves per SIMD.
+static int bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t,
+                      float shift, const float* d_loss, float scale, tt_stream stream, const char* who) {
+  BwdSetup s;
+  if (int rc = bwd_setup(s, Operands::bf16x3, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // two a tiles per workgroup at D <= 64: half the workgroups, half the L2 bytes of the streamed b images
+  switch (padded_d(D)) {
+    case 32: launch_bsplit<2, 2, 4, true>(s, st); break;
+    case 64: launch_bsplit<4, 2, 4, true>(s, st); break;
+    case 128: launch_bsplit<8, 1, 4, true>(s, st); break;
+    default: launch_bsplit<16, 1, 4, true>(s, st); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 extern "C" {
 
 size_t tt_score_pack_bytes(int64_t R, int32_t D) {
@@ -1551,144 +1755,18 @@ int tt_score_pack_bf16(tt_ctx* ctx, const float* X, int64_t R, int32_t D, float 
 
 int tt_score_fwd_bf16(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                       tt_stream stream) {
-  TT_CHECK_ARG(ctx && dirs && (n_dirs == 1 || n_dirs == 2), "tt_score_fwd_bf16: need 1 or 2 directions");
-  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_fwd_bf16: D=%d not in [1,256]", D);
-  if (2.f * fabsf(inv_t) > 80.f) {
-    tt_set_error("tt_score_fwd_bf16: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", inv_t);
-    return TT_ERR_UNSUPPORTED;
-  }
-  FwdArgs a{};
-  int64_t maxRa = 0;
-  bool unit = true;
-  for (int i = 0; i < 2; ++i) {
-    const tt_score_fwd_dir& d = dirs[i < n_dirs ? i : 0];
-    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp && d.Ra >= 1 && d.Rb >= 1, "tt_score_fwd_bf16: bad direction %d", i);
-    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale;
-    a.d[i] = DirFwd{view(d.A_packed, d.Ra, D).rows, view(d.B_packed, d.Rb, D).rows, d.Ra, d.Rb, d.diag_offset, d.sumexp, d.diag, d.rank, d.sumscore,
-                      d.rank ? (d.rank_mode == 1 ? 1 : 2) : 0, inv_t * kLog2e / ab, inv_t / ab, d.inv_sumexp};
-    unit = unit && ab == inv_t * kLog2e;                // exactly: the caller got the scale from tt_score_unit_scale(inv_t)
-    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
-  }
-  a.c2 = -shift * kLog2e;
-  a.kexp = exp2f(a.c2);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Dp = padded_d(D);
-#define TT_FWD(KS, AT, NW)                                                                                     \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (unit) score_fwd_bf16_kernel<KS, AT, NW, true><<<grid, NW * 64, 0, st>>>(a);                            \
-    else score_fwd_bf16_kernel<KS, AT, NW, false><<<grid, NW * 64, 0, st>>>(a);                                \
-  } while (0)
-  // D <= 64: 32 rows per wave (AT = 1), 8 waves, 2 workgroups per CU measured best (43.6 us; AT = 2: 48.0, 4 waves: 53.4,
-  // 16 waves: 48.7 at B = 8192)
-  if (Dp == 32) TT_FWD(2, 2, 8);
-  else if (Dp == 64) TT_FWD(4, 1, 8);
-  else if (Dp == 128) TT_FWD(8, 2, 8);
-  else TT_FWD(16, 1, 8);
-#undef TT_FWD
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return fwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, stream, false, "tt_score_fwd_bf16");
 }
-
-}  // extern "C"
-
-// tt_score_bwd_bf16 and, with lq != NULL, tt_score_bwd_bf16_lq (the LQ instantiations)
-static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
-                    const float* d_loss, float scale, tt_stream stream, const tt_score_bwd_lq* lq, const char* who) {
-  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
-  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
-  BwdArgs a{};
-  if (int rc = bwd_lq_args(a, lq, n_dirs, inv_t, who)) return rc;
-  int64_t maxRa = 0;
-  bool unit = true;
-  for (int i = 0; i < 2; ++i) {
-    const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
-    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1,
-                 "%s: bad direction %d", who, i);
-    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16), "%s: sumexp_b must be 16-byte aligned", who);
-    const PackedView vb = view(d.B_packed, d.Rb, D);
-    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
-    a.d[i] = DirBwd{view(d.A_packed, d.Ra, D).rows, vb.rows, vb.frag, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA,
-                      inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b};
-    TT_CHECK_ARG(d.inv_b == nullptr || tt_aligned(d.inv_b, 16), "%s: inv_b must be 16-byte aligned", who);
-    unit = unit && ab == inv_t * kLog2e;
-    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
-  }
-  a.c2 = -shift * kLog2e;
-  a.kexp = exp2f(a.c2);
-  a.d_loss = d_loss;
-  a.D = D;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Dp = padded_d(D);
-#define TT_BWD(KS, AT, NW)                                                                                     \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (lq && unit) score_bwd_bf16_kernel<KS, AT, NW, true, false, true><<<grid, NW * 64, 0, st>>>(a);        \
-    else if (lq) score_bwd_bf16_kernel<KS, AT, NW, false, false, true><<<grid, NW * 64, 0, st>>>(a);           \
-    else if (unit) score_bwd_bf16_kernel<KS, AT, NW, true><<<grid, NW * 64, 0, st>>>(a);                       \
-    else score_bwd_bf16_kernel<KS, AT, NW, false><<<grid, NW * 64, 0, st>>>(a);                                \
-  } while (0)
-  // enough rows for every SIMD to own 64 of them: the workgroup-staged form (no split along b, operands shared through LDS)
-  if (maxRa >= ctx->score_bwd_rows_min && Dp >= 64) {
-#define TT_BWD_ROWS(KS, AT_, NWV_)                                                                             \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT_ * NWV_), (unsigned)n_dirs);                              \
-    const size_t lds = 2 * (size_t)(KS * 2048 + 256) + (KS == 16 ? (size_t)NWV_ * AT_ * KS * 1024 : 0);        \
-    if (lq && unit) {                                                                                          \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, true, false, AT_, NWV_, true>);                              \
-      score_bwd_rows_kernel<KS, true, false, AT_, NWV_, true><<<grid, NWV_ * 64, lds, st>>>(a);                \
-    } else if (lq) {                                                                                           \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, false, false, AT_, NWV_, true>);                             \
-      score_bwd_rows_kernel<KS, false, false, AT_, NWV_, true><<<grid, NWV_ * 64, lds, st>>>(a);               \
-    } else if (unit) {                                                                                         \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, true, false, AT_, NWV_>);                                    \
-      score_bwd_rows_kernel<KS, true, false, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                      \
-    } else {                                                                                                   \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, false, false, AT_, NWV_>);                                   \
-      score_bwd_rows_kernel<KS, false, false, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                     \
-    }                                                                                                          \
-  } while (0)
-    // D = 256: one a tile per wave with its A fragments in LDS (16 KB per wave: four waves beside the two 33-KB stages) -- with
-    // two a tiles per wave the A fragments (128 registers) and the accumulators (256) filled the whole file and hipcc shuttled
-    // hundreds of values between AGPRs, VGPRs and scratch (20-116 bytes of scratch per lane in the tile loop)
-    if (Dp == 64) TT_BWD_ROWS(4, 2, 4);
-    else if (Dp == 128) TT_BWD_ROWS(8, 2, 4);
-    else TT_BWD_ROWS(16, 1, 4);
-#undef TT_BWD_ROWS
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-  }
-  if (Dp == 32) TT_BWD(2, 2, 8);
-  else if (Dp == 64) {                                    // one streamed image, transposing LDS reads
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 64), (unsigned)n_dirs);
-    if (lq && unit) score_bwd_tr_kernel<4, 2, true, true><<<grid, 512, 0, st>>>(a);
-    else if (lq) score_bwd_tr_kernel<4, 2, false, true><<<grid, 512, 0, st>>>(a);
-    else if (unit) score_bwd_tr_kernel<4, 2, true><<<grid, 512, 0, st>>>(a);
-    else score_bwd_tr_kernel<4, 2, false><<<grid, 512, 0, st>>>(a);
-  } else if (Dp == 128) {                                 // the one-image form, one a tile per workgroup
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32), (unsigned)n_dirs);
-    if (lq && unit) score_bwd_tr_kernel<8, 1, true, true><<<grid, 512, 0, st>>>(a);
-    else if (lq) score_bwd_tr_kernel<8, 1, false, true><<<grid, 512, 0, st>>>(a);
-    else if (unit) score_bwd_tr_kernel<8, 1, true><<<grid, 512, 0, st>>>(a);
-    else score_bwd_tr_kernel<8, 1, false><<<grid, 512, 0, st>>>(a);
-  }
-  else TT_BWD(16, 1, 4);
-#undef TT_BWD
-  TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
-extern "C" {
 
 int tt_score_bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                       const float* d_loss, float scale, tt_stream stream) {
-  return bwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, nullptr, "tt_score_bwd_bf16");
+  return bwd_bf16(ctx, dirs, nullptr, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16");
 }
 
 int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
                          float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
   TT_CHECK_ARG(lq, "tt_score_bwd_bf16_lq: NULL lq");
-  return bwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, lq, "tt_score_bwd_bf16_lq");
+  return bwd_bf16(ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_lq");
 }
 
 size_t tt_score_pack_fp8_bytes(int64_t R, int32_t D) {
@@ -1732,66 +1810,19 @@ int tt_score_pack2_fp8(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, 
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                      const float* d_loss, float scale, tt_stream stream) {
-  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "tt_score_bwd_fp8: need 1 or 2 directions");
-  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_bwd_fp8: D=%d not in [1,256]", D);
-  BwdArgs a{};
-  int64_t maxRa = 0;
-  bool unit = true;
-  for (int i = 0; i < 2; ++i) {
-    const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
-    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1, "tt_score_bwd_fp8: bad direction %d", i);
-    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16) && (d.inv_b == nullptr || tt_aligned(d.inv_b, 16)), "tt_score_bwd_fp8: per-row arrays must be 16-byte aligned");
-    const PackedView8 va = view8(d.A_packed, d.Ra, D), vb = view8(d.B_packed, d.Rb, D);
-    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
-    a.d[i] = DirBwd{reinterpret_cast<const __bf16*>(va.rows8), reinterpret_cast<const __bf16*>(vb.rows8), vb.frag, d.Ra, d.Rb, d.diag_offset,
-                    d.sumexp_a, d.sumexp_b, d.dA, inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b, vb.frag8};
-    unit = unit && ab == inv_t * kLog2e;
-    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
-  }
-  a.c2 = -shift * kLog2e;
-  a.kexp = exp2f(a.c2);
-  a.d_loss = d_loss;
-  a.D = D;
+  BwdSetup s;
+  if (int rc = bwd_setup(s, Operands::fp8, ctx, dirs, nullptr, n_dirs, D, inv_t, shift, d_loss, scale, "tt_score_bwd_fp8")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int Dp = padded_d8(D);
   // D = 256: two waves per SIMD, one a tile each (the 128 accumulator registers of a 32 x 256 block leave room for nothing
   // more); narrower: one wave per SIMD with two a tiles.
-  if (ctx->fp8_grad) {                                     // TT_OPT_FP8_GRAD (default): e4m3 gradient products, block-scaled weights
-#define TT_BWD88(KS, AT_, NWV_)                                                                                \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT_ * NWV_), (unsigned)n_dirs);                              \
-    const size_t lds = (size_t)4 * KS * 1024 + 512 + (KS == 16 ? (size_t)NWV_ * AT_ * KS * 512 : 0);           \
-    if (unit) {                                                                                                \
-      TT_LDS_ONCE(lds, &score_bwd_rows8_kernel<KS, true, AT_, NWV_>);                                          \
-      score_bwd_rows8_kernel<KS, true, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                            \
-    } else {                                                                                                   \
-      TT_LDS_ONCE(lds, &score_bwd_rows8_kernel<KS, false, AT_, NWV_>);                                         \
-      score_bwd_rows8_kernel<KS, false, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                           \
-    }                                                                                                          \
-  } while (0)
-    if (Dp == 64) TT_BWD88(4, 2, 4);
-    else if (Dp == 128) TT_BWD88(8, 2, 4);
-    else TT_BWD88(16, 1, 8);
-#undef TT_BWD88
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-  }
-#define TT_BWD8(KS, AT_, NWV_)                                                                                 \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT_ * NWV_), (unsigned)n_dirs);                              \
-    const size_t lds = 2 * (size_t)(KS * 512 + KS * 1024 + 256);                                               \
-    if (unit) {                                                                                                \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, true, true, AT_, NWV_>);                                     \
-      score_bwd_rows_kernel<KS, true, true, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                       \
-    } else {                                                                                                   \
-      TT_LDS_ONCE(lds, &score_bwd_rows_kernel<KS, false, true, AT_, NWV_>);                                    \
-      score_bwd_rows_kernel<KS, false, true, AT_, NWV_><<<grid, NWV_ * 64, lds, st>>>(a);                      \
-    }                                                                                                          \
-  } while (0)
-  if (Dp == 64) TT_BWD8(4, 2, 4);
-  else if (Dp == 128) TT_BWD8(8, 2, 4);
-  else TT_BWD8(16, 1, 8);
-#undef TT_BWD8
+  int rc;
+  if (ctx->fp8_grad)                                       // TT_OPT_FP8_GRAD (default): e4m3 gradient products, block-scaled weights
+    rc = Dp == 64 ? launch_rows8<4, 2, 4>(ctx, s, st) : Dp == 128 ? launch_rows8<8, 2, 4>(ctx, s, st) : launch_rows8<16, 1, 8>(ctx, s, st);
+  else
+    rc = Dp == 64    ? launch_rows<4, true, 2, 4>(ctx, s, st)
+         : Dp == 128 ? launch_rows<8, true, 2, 4>(ctx, s, st) : launch_rows<16, true, 1, 8>(ctx, s, st);
+  if (rc) return rc;
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -1827,107 +1858,18 @@ int tt_score_pack2_bf16x3(tt_ctx* ctx, const float* X0, int64_t R0, void* packed
 
 int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                         tt_stream stream) {
-  TT_CHECK_ARG(ctx && dirs && (n_dirs == 1 || n_dirs == 2), "tt_score_fwd_bf16x3: need 1 or 2 directions");
-  TT_CHECK_ARG(D >= 1 && D <= 256, "tt_score_fwd_bf16x3: D=%d not in [1,256]", D);
-  if (2.f * fabsf(inv_t) > 80.f) {
-    tt_set_error("tt_score_fwd_bf16x3: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", inv_t);
-    return TT_ERR_UNSUPPORTED;
-  }
-  FwdArgs a{};
-  int64_t maxRa = 0;
-  bool unit = true;
-  for (int i = 0; i < 2; ++i) {
-    const tt_score_fwd_dir& d = dirs[i < n_dirs ? i : 0];
-    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp && d.Ra >= 1 && d.Rb >= 1, "tt_score_fwd_bf16x3: bad direction %d", i);
-    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale;
-    a.d[i] = DirFwd{view(d.A_packed, d.Ra, D).rows, view(d.B_packed, d.Rb, D).rows, d.Ra, d.Rb, d.diag_offset, d.sumexp, d.diag, d.rank, d.sumscore,
-                    d.rank ? (d.rank_mode == 1 ? 1 : 2) : 0, inv_t * kLog2e / ab, inv_t / ab, d.inv_sumexp,
-                    view_lo(d.A_packed, d.Ra, D).rows, view_lo(d.B_packed, d.Rb, D).rows};
-    unit = unit && ab == inv_t * kLog2e;
-    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
-  }
-  a.c2 = -shift * kLog2e;
-  a.kexp = exp2f(a.c2);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Dp = padded_d(D);
-#define TT_FWD3(KS, AT, NW)                                                                                    \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (unit) score_fwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                      \
-    else score_fwd_bf16_kernel<KS, AT, NW, false, true><<<grid, NW * 64, 0, st>>>(a);                          \
-  } while (0)
-  if (Dp == 32) TT_FWD3(2, 2, 8);
-  else if (Dp == 64) TT_FWD3(4, 1, 8);
-  else if (Dp == 128) TT_FWD3(8, 1, 8);
-  else TT_FWD3(16, 1, 4);                               // one wave per SIMD: the hi / lo fragments of A and of a b tile are 256 registers
-#undef TT_FWD3
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  return fwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, stream, true, "tt_score_fwd_bf16x3");
 }
-
-// One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
-// takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
-// workgroup-staged form's stages would both double for the lo images.  One wave per SIMD (4 waves): the hi and lo operands of
-// two b tiles in flight need more than the 256 registers a wave gets at two waves per SIMD.
-}  // extern "C"
-
-// tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq
-static int bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
-                      const float* d_loss, float scale, tt_stream stream, const tt_score_bwd_lq* lq, const char* who) {
-  TT_CHECK_ARG(ctx && dirs && d_loss && (n_dirs == 1 || n_dirs == 2), "%s: need 1 or 2 directions", who);
-  TT_CHECK_ARG(D >= 1 && D <= 256, "%s: D=%d not in [1,256]", who, D);
-  BwdArgs a{};
-  if (int rc = bwd_lq_args(a, lq, n_dirs, inv_t, who)) return rc;
-  int64_t maxRa = 0;
-  bool unit = true;
-  for (int i = 0; i < 2; ++i) {
-    const tt_score_bwd_dir& d = dirs[i < n_dirs ? i : 0];
-    TT_CHECK_ARG(d.A_packed && d.B_packed && d.sumexp_a && d.sumexp_b && d.dA && d.Ra >= 1 && d.Rb >= 1,
-                 "%s: bad direction %d", who, i);
-    TT_CHECK_ARG(tt_aligned(d.sumexp_b, 16) && (d.inv_b == nullptr || tt_aligned(d.inv_b, 16)),
-                 "%s: per-row arrays must be 16-byte aligned", who);
-    const PackedView vb = view(d.B_packed, d.Rb, D), vbl = view_lo(d.B_packed, d.Rb, D);
-    const float ab = d.ab_scale == 0.f ? 1.f : d.ab_scale, bs = d.b_scale == 0.f ? 1.f : d.b_scale;
-    a.d[i] = DirBwd{view(d.A_packed, d.Ra, D).rows, vb.rows, vb.frag, d.Ra, d.Rb, d.diag_offset, d.sumexp_a, d.sumexp_b, d.dA,
-                    inv_t * kLog2e / ab, scale / bs, d.inv_a, d.inv_b, nullptr, view_lo(d.A_packed, d.Ra, D).rows, vbl.rows, vbl.frag};
-    unit = unit && ab == inv_t * kLog2e;
-    maxRa = d.Ra > maxRa ? d.Ra : maxRa;
-  }
-  a.c2 = -shift * kLog2e;
-  a.kexp = exp2f(a.c2);
-  a.d_loss = d_loss;
-  a.D = D;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Dp = padded_d(D);
-#define TT_BWD3(KS, AT, NW)                                                                                    \
-  do {                                                                                                         \
-    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * AT), (unsigned)n_dirs);                                      \
-    if (lq && unit) score_bwd_bf16_kernel<KS, AT, NW, true, true, true><<<grid, NW * 64, 0, st>>>(a);          \
-    else if (lq) score_bwd_bf16_kernel<KS, AT, NW, false, true, true><<<grid, NW * 64, 0, st>>>(a);             \
-    else if (unit) score_bwd_bf16_kernel<KS, AT, NW, true, true><<<grid, NW * 64, 0, st>>>(a);                 \
-    else score_bwd_bf16_kernel<KS, AT, NW, false, true><<<grid, NW * 64, 0, st>>>(a);                          \
-  } while (0)
-  // two a tiles per workgroup at D <= 64: half the workgroups, half the L2 bytes of the streamed b images
-  if (Dp == 32) TT_BWD3(2, 2, 4);
-  else if (Dp == 64) TT_BWD3(4, 2, 4);
-  else if (Dp == 128) TT_BWD3(8, 1, 4);
-  else TT_BWD3(16, 1, 4);
-#undef TT_BWD3
-  TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
-extern "C" {
 
 int tt_score_bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                         const float* d_loss, float scale, tt_stream stream) {
-  return bwd_bf16x3(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, nullptr, "tt_score_bwd_bf16x3");
+  return bwd_bf16x3(ctx, dirs, nullptr, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16x3");
 }
 
 int tt_score_bwd_bf16x3_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D,
                            float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
   TT_CHECK_ARG(lq, "tt_score_bwd_bf16x3_lq: NULL lq");
-  return bwd_bf16x3(ctx, dirs, n_dirs, D, inv_t, shift, d_loss, scale, stream, lq, "tt_score_bwd_bf16x3_lq");
+  return bwd_bf16x3(ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16x3_lq");
 }
 
 }  // extern "C"

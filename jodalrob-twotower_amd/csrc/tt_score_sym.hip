@@ -617,64 +617,32 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   const dim3 grid((unsigned)n_groups, (unsigned)L.n_chunks);
   const size_t slot_bytes = sizeof(float) * 3 * kSymWaves * L.NI * 32;
   const size_t wn_bytes = sizeof(float) * (L.NI * 32 + kSymWaves * 32);   // (LQ) notice weights (+ company weights, x3 D = 256)
-#define TT_SYMLQ(KS, X3_)                                                                                               \
-  do {                                                                                                                  \
-    const size_t lds = slot_bytes + 2 * SymStage<KS, false, X3_>::kBytes + wn_bytes;                                    \
-    if (unit) {                                                                                                         \
-      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, true, false, 1, X3_, true>);                                           \
-      score_fwd_sym_kernel<KS, true, false, 1, X3_, true><<<grid, kSymThreads, lds, st>>>(g);                           \
-    } else {                                                                                                            \
-      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, false, false, 1, X3_, true>);                                          \
-      score_fwd_sym_kernel<KS, false, false, 1, X3_, true><<<grid, kSymThreads, lds, st>>>(g);                          \
-    }                                                                                                                   \
-  } while (0)
-#define TT_SYM(KS, F8, JT_)                                                                                             \
-  do {                                                                                                                  \
-    const size_t lds = slot_bytes + 2 * SymStage<KS, F8>::kBytes;                                                       \
-    if (unit) score_fwd_sym_kernel<KS, true, F8, JT_><<<grid, kSymThreads, lds, st>>>(g);                               \
-    else score_fwd_sym_kernel<KS, false, F8, JT_><<<grid, kSymThreads, lds, st>>>(g);                                   \
-  } while (0)
-#define TT_SYM3(KS)                                                                                                     \
-  do {                                                                                                                  \
-    const size_t lds = slot_bytes + 2 * SymStage<KS, false, true>::kBytes;                                              \
-    if (unit) {                                                                                                         \
-      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, true, false, 1, true>);                                                \
-      score_fwd_sym_kernel<KS, true, false, 1, true><<<grid, kSymThreads, lds, st>>>(g);                                \
-    } else {                                                                                                            \
-      TT_LDS_ONCE(lds, &score_fwd_sym_kernel<KS, false, false, 1, true>);                                               \
-      score_fwd_sym_kernel<KS, false, false, 1, true><<<grid, kSymThreads, lds, st>>>(g);                               \
-    }                                                                                                                   \
-  } while (0)
-  if (lq) {
-    if (x3) {
-      if (L.Dp == 32) TT_SYMLQ(2, true);
-      else if (L.Dp == 64) TT_SYMLQ(4, true);
-      else if (L.Dp == 128) TT_SYMLQ(8, true);
-      else TT_SYMLQ(16, true);
-    } else {
-      if (L.Dp == 32) TT_SYMLQ(2, false);
-      else if (L.Dp == 64) TT_SYMLQ(4, false);
-      else if (L.Dp == 128) TT_SYMLQ(8, false);
-      else TT_SYMLQ(16, false);
-    }
-  } else if (x3) {
-    if (L.Dp == 32) TT_SYM3(2);
-    else if (L.Dp == 64) TT_SYM3(4);
-    else if (L.Dp == 128) TT_SYM3(8);
-    else TT_SYM3(16);
-  } else if (fp8) {
-    if (L.Dp == 64) TT_SYM(4, true, 1);
-    else if (L.Dp == 128) TT_SYM(8, true, 1);
-    else TT_SYM(16, true, 2);
+  // one launch per form (fp8 has neither an x3 nor an LQ form); only the x3 and LQ forms set their LDS limit
+  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc) -> int {
+    constexpr int JT = fp8c && ks == 16 ? 2 : 1;                  // = jt
+    const size_t lds = slot_bytes + 2 * SymStage<ks, fp8c, x3c>::kBytes + (lqc ? wn_bytes : 0);
+    return tt_dispatch([&](auto u) -> int {
+      if constexpr (x3c || lqc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc>);
+      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc><<<grid, kSymThreads, lds, st>>>(g);
+      return TT_OK;
+    }, unit);
+  };
+  const std::false_type no{};
+  int rc;
+  if (fp8) {
+    const std::true_type yes{};
+    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no) : go(tt_c<16>, yes, no, no));
   } else {
-    if (L.Dp == 32) TT_SYM(2, false, 1);
-    else if (L.Dp == 64) TT_SYM(4, false, 1);
-    else if (L.Dp == 128) TT_SYM(8, false, 1);
-    else TT_SYM(16, false, 1);
+    rc = tt_dispatch([&](auto x3c, auto lqc) {
+      switch (L.Dp) {
+        case 32: return go(tt_c<2>, no, x3c, lqc);
+        case 64: return go(tt_c<4>, no, x3c, lqc);
+        case 128: return go(tt_c<8>, no, x3c, lqc);
+        default: return go(tt_c<16>, no, x3c, lqc);
+      }
+    }, x3, lq);
   }
-#undef TT_SYM
-#undef TT_SYM3
-#undef TT_SYMLQ
+  if (rc) return rc;
   TT_LAUNCH_CHECK();
   Fin1Args f{};
   f.rs = g.rs; f.mb = g.mb; f.ma = g.ma; f.cs = g.cs; f.diag_raw = g.diag_raw;

@@ -471,35 +471,72 @@ def towers_bwd(params_list, acts_list, d_embs, grads_list, B, train, p_drop, see
 
 
 # ---------------------------------------------------------------------------------------------- score / loss
-def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True):
+# logQ sampling-bias correction (the *_lq entries of include/twotower.h): the score wrappers take the log sampling
+# probabilities as optional arguments and call the _lq entry when they are given
+LQ_MAX_TWO_INV_T = 40.0      # the *_lq entries support 2/T <= 40 (T >= 0.05)
+
+
+def _lq_vec(lq, B, dev, name):
+    """f32 [B] log sampling probabilities, contiguous on `dev` (validated: no device sync)"""
+    if not isinstance(lq, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(lq).__name__}")
+    if lq.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {lq.dtype}")
+    if lq.dim() != 1 or lq.shape[0] != B:
+        raise ValueError(f"{name} must have shape [{B}], got {list(lq.shape)}")
+    if lq.device != dev:
+        raise ValueError(f"{name} is on {lq.device}, the scores on {dev}")
+    return lq.contiguous()
+
+
+def _lq_check_t(inv_t):
+    if 2.0 * abs(inv_t) > LQ_MAX_TWO_INV_T:
+        raise ValueError(f"logQ correction needs 2/T <= {LQ_MAX_TWO_INV_T:g} (T >= 0.05), got 1/T = {inv_t:g}")
+
+
+def _lq_pair(a, b, Ra, Rb, dev, names):
+    """() without logQ, else the two validated vectors (the caller holds them for the duration of the call)"""
+    return () if a is None else (_lq_vec(a, Ra, dev, names[0]), _lq_vec(b, Rb, dev, names[1]))
+
+
+def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True, lq_b=None):
+    """lq_b: the B rows' log sampling probabilities [Rb] (tt_score_dir_fwd_lq)."""
     dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
+    lq = () if lq_b is None else (_lq_vec(lq_b, Rb, dev, "lq_b"),)
     f = torch.empty((3, Ra), dtype=torch.float32, device=dev)       # sumexp, diag, sumscore
     rank = torch.empty(Ra, dtype=torch.int32, device=dev)
-    with _timed("tt_score_dir_fwd"):
-        L.check(L.load().tt_score_dir_fwd(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(f[0]),
-                                          L.ptr(f[1]), L.ptr(rank), L.ptr(f[2]) if want_sumscore else None, L.stream(dev)),
-                "tt_score_dir_fwd")
+    name = "tt_score_dir_fwd_lq" if lq else "tt_score_dir_fwd"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *map(L.ptr, lq),
+                                        L.ptr(f[0]), L.ptr(f[1]), L.ptr(rank), L.ptr(f[2]) if want_sumscore else None, L.stream(dev)),
+                name)
     return f[0], f[1], rank, f[2]
 
 
-def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore):
-    """Returns (out8, loss): the loss is its own 0-dim tensor so that autograd sees a plain output."""
+def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=None, lq_c=None):
+    """Returns (out8, loss): the loss is its own 0-dim tensor so that autograd sees a plain output.
+    lq_n / lq_c (both or neither): the corrected positives (tt_score_loss_finish_lq)."""
     dev = rowsum.device
+    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
     out = torch.empty(8, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    with _timed("tt_score_loss_finish"):
-        L.check(L.load().tt_score_loss_finish(L.ctx(dev), B, shift, L.ptr(rowsum), L.ptr(colsum), L.ptr(diag), L.ptr(row_rank),
-                                              L.ptr(col_rank), L.ptr(sumscore), L.ptr(out), L.ptr(loss), L.stream(dev)),
-                "tt_score_loss_finish")
+    name = "tt_score_loss_finish_lq" if lq else "tt_score_loss_finish"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), B, shift, *map(L.ptr, lq), L.ptr(rowsum), L.ptr(colsum), L.ptr(diag),
+                                        L.ptr(row_rank), L.ptr(col_rank), L.ptr(sumscore), L.ptr(out), L.ptr(loss), L.stream(dev)),
+                name)
     return out, loss
 
 
-def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale):
+def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=None, lq_b=None):
+    """lq_a / lq_b (both or neither): the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq)."""
     dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
+    lq = _lq_pair(lq_a, lq_b, Ra, Rb, dev, ("lq_a", "lq_b"))
     dA = torch.empty_like(A)
-    with _timed("tt_score_dir_bwd"):
-        L.check(L.load().tt_score_dir_bwd(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(sumexp_a),
-                                          L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA), L.stream(dev)), "tt_score_dir_bwd")
+    name = "tt_score_dir_bwd_lq" if lq else "tt_score_dir_bwd"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *map(L.ptr, lq),
+                                        L.ptr(sumexp_a), L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA), L.stream(dev)), name)
     return dA
 
 
@@ -578,12 +615,17 @@ def score_pack2_fp8(X0, X1, scale0: float = 1.0, scale1: float = 1.0):
     return b0, b1
 
 
-def score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False):
-    """Single-pass symmetric forward of the square problem (tt_score_fwd_sym_bf16 / _fp8 / _bf16x3): returns (rowsum, colsum, diag,
-    row_rank, (inv_row, inv_col), out8, loss) -- loss its own 0-dim tensor so that autograd sees a plain output."""
+def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False,
+             lq_n=None, lq_c=None):
+    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq): returns (rowsum, colsum, diag, row_rank,
+    (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n / lq_c given,
+    tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None."""
     dev = Np.device
+    if lq_n is not None and fp8:
+        raise ValueError("the logQ-corrected symmetric forward has no fp8 form")
+    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
     Bp = (B + 63) // 64 * 64                                           # the kernel fills the entries past B (read by tt_score_bwd_bf16)
-    f = torch.empty((5, Bp), dtype=torch.float32, device=dev)         # rowsum, colsum, diag, 1/rowsum', 1/colsum'
+    f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
     rank = torch.empty(B, dtype=torch.int32, device=dev)
     out8 = torch.empty(8, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
@@ -593,135 +635,69 @@ def score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: b
         out8._tt_keep = ws
     else:
         ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
-    name = "tt_score_fwd_sym_fp8" if fp8 else ("tt_score_fwd_sym_bf16x3" if x3 else "tt_score_fwd_sym_bf16")
-    fn = getattr(lib, name)
+    name = ("tt_score_fwd_sym_fp8" if fp8 else ("tt_score_fwd_sym_bf16x3" if x3 else "tt_score_fwd_sym_bf16")) + ("_lq" if lq else "")
+    w_out = (L.ptr(f[5]), L.ptr(f[6])) if lq else ()
     with _timed(name):
-        L.check(fn(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), L.ptr(f[0]), L.ptr(f[1]),
-                                          L.ptr(f[3]), L.ptr(f[4]), L.ptr(f[2]), L.ptr(rank), L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(),
-                                          L.stream(dev)), name)
-    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), out8, loss
+        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), *map(L.ptr, lq),
+                                   L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]), *w_out, L.ptr(f[2]), L.ptr(rank), L.ptr(out8),
+                                   L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
+    w = (f[5][:B], f[6][:B]) if lq else None
+    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), out8, loss, w
+
+
+def score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False):
+    """Single-pass symmetric forward of the square problem (tt_score_fwd_sym_bf16 / _fp8 / _bf16x3): returns (rowsum, colsum, diag,
+    row_rank, (inv_row, inv_col), out8, loss) -- loss its own 0-dim tensor so that autograd sees a plain output."""
+    return _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, fp8, x3)[:7]
+
+
+def score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n: float = 1.0, want_rank: bool = True, x3: bool = False):
+    """logQ-corrected score_fwd_sym (tt_score_fwd_sym_bf16_lq / _bf16x3_lq): lq_n / lq_c f32 [B] log sampling probabilities of
+    the batch's notices / companies.  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), (w_n, w_c), out8, loss):
+    (w_n, w_c) are the sampling weights score_bwd_bf16(..., w=) takes."""
+    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, x3, lq_n, lq_c)
+    return r[:5] + (r[7],) + r[5:7]
 
 
 def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n: float = 1.0, inv=None, fp8: bool = False,
-                   x3: bool = False):
+                   x3: bool = False, w=None):
     """inv: (inv_row, inv_col) from score_fwd_bf16(..., with_inv=True) with the same scale_n (optional).
-    fp8: the operands are tt_score_pack2_fp8 buffers (tt_score_bwd_fp8); x3: score_pack2_bf16x3 buffers (tt_score_bwd_bf16x3)."""
+    fp8: the operands are tt_score_pack2_fp8 buffers (tt_score_bwd_fp8); x3: score_pack2_bf16x3 buffers (tt_score_bwd_bf16x3).
+    w: (w_n, w_c) from score_fwd_sym_lq, with its rowsum / colsum / inv: the logQ-corrected backward
+    (tt_score_bwd_bf16_lq / _bf16x3_lq; w_n / w_c are views of arrays padded to 64 rows, as the kernels read them)."""
     dev = Np.device
+    if w is not None and fp8:
+        raise ValueError("the logQ-corrected backward has no fp8 form")
     dN = torch.empty((B, D), dtype=torch.float32, device=dev)
     dC = torch.empty((B, D), dtype=torch.float32, device=dev)
     arr = (L.ScoreBwdDir * 2)()
     ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
     arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)   # B = company: unscaled
     arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)  # B = notice image
-    name = "tt_score_bwd_fp8" if fp8 else ("tt_score_bwd_bf16x3" if x3 else "tt_score_bwd_bf16")
-    fn = getattr(L.load(), name)
+    lq = ()
+    if w is not None:
+        lq = ((L.ScoreBwdLq * 2)(),)
+        lq[0][0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))              # direction (N, C): A = notices, B = companies
+        lq[0][1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
+    name = ("tt_score_bwd_fp8" if fp8 else ("tt_score_bwd_bf16x3" if x3 else "tt_score_bwd_bf16")) + ("_lq" if lq else "")
     with _timed(name):
-        L.check(fn(L.ctx(dev), arr, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
+        L.check(getattr(L.load(), name)(L.ctx(dev), arr, *lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
     return dN, dC
-
-
-# ---- logQ sampling-bias correction (the *_lq entries of include/twotower.h) ----------------------------------------------
-LQ_MAX_TWO_INV_T = 40.0      # the *_lq entries support 2/T <= 40 (T >= 0.05)
-
-
-def _lq_vec(lq, B, dev, name):
-    """f32 [B] log sampling probabilities, contiguous on `dev` (validated: no device sync)"""
-    if not isinstance(lq, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor, got {type(lq).__name__}")
-    if lq.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {lq.dtype}")
-    if lq.dim() != 1 or lq.shape[0] != B:
-        raise ValueError(f"{name} must have shape [{B}], got {list(lq.shape)}")
-    if lq.device != dev:
-        raise ValueError(f"{name} is on {lq.device}, the scores on {dev}")
-    return lq.contiguous()
-
-
-def _lq_check_t(inv_t):
-    if 2.0 * abs(inv_t) > LQ_MAX_TWO_INV_T:
-        raise ValueError(f"logQ correction needs 2/T <= {LQ_MAX_TWO_INV_T:g} (T >= 0.05), got 1/T = {inv_t:g}")
-
-
-def score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n: float = 1.0, want_rank: bool = True, x3: bool = False):
-    """logQ-corrected score_fwd_sym (tt_score_fwd_sym_bf16_lq / _bf16x3_lq): lq_n / lq_c f32 [B] log sampling probabilities of
-    the batch's notices / companies.  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), (w_n, w_c), out8, loss):
-    (w_n, w_c) are the sampling weights score_bwd_bf16_lq takes."""
-    dev = Np.device
-    lq_n, lq_c = _lq_vec(lq_n, B, dev, "lq_n"), _lq_vec(lq_c, B, dev, "lq_c")
-    Bp = (B + 63) // 64 * 64
-    f = torch.empty((7, Bp), dtype=torch.float32, device=dev)         # rowsum, colsum, diag, 1/rowsum', 1/colsum', w_n, w_c
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    out8 = torch.empty(8, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    lib = L.load()
-    if L.riders_deferred(dev, 2):
-        ws = torch.empty(lib.tt_score_fwd_sym_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
-        out8._tt_keep = ws
-    else:
-        ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
-    name = "tt_score_fwd_sym_bf16x3_lq" if x3 else "tt_score_fwd_sym_bf16_lq"
-    with _timed(name):
-        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), L.ptr(lq_n),
-                                   L.ptr(lq_c), L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]), L.ptr(f[5]), L.ptr(f[6]),
-                                   L.ptr(f[2]), L.ptr(rank), L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
-    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), (f[5][:B], f[6][:B]), out8, loss
 
 
 def score_bwd_bf16_lq(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, w, scale_n: float = 1.0, inv=None, x3: bool = False):
-    """logQ-corrected score_bwd_bf16 (tt_score_bwd_bf16_lq / _bf16x3_lq): w = (w_n, w_c) and rowsum / colsum / inv from
-    score_fwd_sym_lq (w_n / w_c are views of arrays padded to 64 rows, as the kernels read them)."""
-    dev = Np.device
-    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
-    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
-    arr = (L.ScoreBwdDir * 2)()
-    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
-    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)
-    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)
-    lq = (L.ScoreBwdLq * 2)()
-    lq[0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))                     # direction (N, C): A = notices, B = companies
-    lq[1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
-    name = "tt_score_bwd_bf16x3_lq" if x3 else "tt_score_bwd_bf16_lq"
-    with _timed(name):
-        L.check(getattr(L.load(), name)(L.ctx(dev), arr, lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
-    return dN, dC
+    """score_bwd_bf16(..., w=w): the logQ-corrected backward."""
+    return score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n, inv, x3=x3, w=w)
 
 
 def score_dir_fwd_lq(A, Bm, inv_t, shift, lq_b, diag_offset=0, want_sumscore=True):
-    """score_dir_fwd with the B rows' log sampling probabilities lq_b [Rb] (tt_score_dir_fwd_lq)."""
-    dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
-    lq_b = _lq_vec(lq_b, Rb, dev, "lq_b")
-    f = torch.empty((3, Ra), dtype=torch.float32, device=dev)
-    rank = torch.empty(Ra, dtype=torch.int32, device=dev)
-    with _timed("tt_score_dir_fwd_lq"):
-        L.check(L.load().tt_score_dir_fwd_lq(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(lq_b),
-                                             L.ptr(f[0]), L.ptr(f[1]), L.ptr(rank), L.ptr(f[2]) if want_sumscore else None,
-                                             L.stream(dev)), "tt_score_dir_fwd_lq")
-    return f[0], f[1], rank, f[2]
-
-
-def score_loss_finish_lq(B, shift, lq_n, lq_c, rowsum, colsum, diag, row_rank, col_rank, sumscore):
-    """score_loss_finish with the corrected positives (tt_score_loss_finish_lq)."""
-    dev = rowsum.device
-    lq_n, lq_c = _lq_vec(lq_n, B, dev, "lq_n"), _lq_vec(lq_c, B, dev, "lq_c")
-    out = torch.empty(8, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    with _timed("tt_score_loss_finish_lq"):
-        L.check(L.load().tt_score_loss_finish_lq(L.ctx(dev), B, shift, L.ptr(lq_n), L.ptr(lq_c), L.ptr(rowsum), L.ptr(colsum),
-                                                 L.ptr(diag), L.ptr(row_rank), L.ptr(col_rank), L.ptr(sumscore), L.ptr(out),
-                                                 L.ptr(loss), L.stream(dev)), "tt_score_loss_finish_lq")
-    return out, loss
+    """score_dir_fwd(..., lq_b=lq_b)"""
+    return score_dir_fwd(A, Bm, inv_t, shift, diag_offset, want_sumscore, lq_b=lq_b)
 
 
 def score_dir_bwd_lq(A, Bm, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale):
-    """score_dir_bwd with the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq)."""
-    dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
-    lq_a, lq_b = _lq_vec(lq_a, Ra, dev, "lq_a"), _lq_vec(lq_b, Rb, dev, "lq_b")
-    dA = torch.empty_like(A)
-    with _timed("tt_score_dir_bwd_lq"):
-        L.check(L.load().tt_score_dir_bwd_lq(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, L.ptr(lq_a),
-                                             L.ptr(lq_b), L.ptr(sumexp_a), L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA),
-                                             L.stream(dev)), "tt_score_dir_bwd_lq")
-    return dA
+    """score_dir_bwd(..., lq_a=lq_a, lq_b=lq_b)"""
+    return score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=lq_a, lq_b=lq_b)
 
 
 def score_fwd_bf16_rect(Ap0, Bp0, Ap1, Bp1, Ra, Rb, off, D, inv_t, shift, full_rank=True):

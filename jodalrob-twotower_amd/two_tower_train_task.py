@@ -59,45 +59,26 @@ class _ScoreCEFn(torch.autograd.Function):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
-        ctx.x3 = False
-        ctx.lq = None
-        if lq_n is not None:
-            return _ScoreCEFn._forward_lq(ctx, n, c, inv_t, shift, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c)
-        if score_dtype == "fp8":
+        lq = lq_n is not None
+        fp8, x3 = score_dtype == "fp8", score_dtype == "bf16x3"
+        if lq:
+            if fp8:
+                raise ValueError("the logQ correction has no fp8 form")
+            ops._lq_check_t(inv_t)
+        # the operands, once per mode
+        Np = Cp = None
+        if fp8:
             # e4m3 operands for the S products (v_mfma_scale_f32_32x32x64_f8f6f4: twice the bf16 MFMA rate), everything else as
             # the bf16 path; always the single-pass forward and the workgroup-staged backward (BASELINE configs[4])
             scale_n = ops.score_unit_scale(inv_t)
             Np, Cp = ops.score_pack2_fp8(n, c, scale_n, 1.0)
-            rowsum, colsum, diag, row_rank, inv, out8, loss = ops.score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, fp8=True)
-            ctx.packed = (Np, Cp, scale_n, inv)
-            ctx.fp8 = True
-            ctx.save_for_backward(n, c, rowsum, colsum)
-            ctx.inv_t, ctx.shift = inv_t, shift
-            ctx.mark_non_differentiable(out8, row_rank)
-            ctx.set_materialize_grads(False)
-            return loss, out8, row_rank
-        ctx.fp8 = False
-        if score_dtype == "bf16x3":
-            # as the bf16 branch on [hi | lo] images (tt_score_pack2_bf16x3); the towers' fused tail emits bf16 images only, so
-            # the pack is always its own launch.  Both images unscaled: the split of inv_t * log2(e) * n (the "unit" form) would
-            # carry the scale's rounding into every operand -- one multiply-add more per score keeps operands that are exact in
-            # bf16 exact here (D = 1: every product exact, as in fp32).
+        elif x3:
+            # as bf16 on [hi | lo] images (tt_score_pack2_bf16x3); the towers' fused tail emits bf16 images only, so the pack is
+            # always its own launch.  Both images unscaled: the split of inv_t * log2(e) * n (the "unit" form) would carry the
+            # scale's rounding into every operand -- one multiply-add more per score keeps operands that are exact in bf16 exact
+            # here (D = 1: every product exact, as in fp32).
             scale_n = 1.0
             Np, Cp = ops.score_pack2_bf16x3(n, c, scale_n, 1.0)
-            ctx.x3 = True
-            if not want_col_rank and not full_rank:
-                rowsum, colsum, diag, row_rank, inv, out8, loss = ops.score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, x3=True)
-                ctx.packed = (Np, Cp, scale_n, inv)
-                ctx.save_for_backward(n, c, rowsum, colsum)
-                ctx.inv_t, ctx.shift = inv_t, shift
-                ctx.mark_non_differentiable(out8, row_rank)
-                ctx.set_materialize_grads(False)
-                return loss, out8, row_rank
-            rowsum, colsum, diag, row_rank, col_rank, sumscore, inv = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, want_col_rank,
-                                                                                         full_rank, scale_n, with_inv=True, x3=True)
-            if not want_col_rank:
-                col_rank = row_rank
-            ctx.packed = (Np, Cp, scale_n, inv)
         elif score_dtype == "bf16":
             # scale_n: the notice image holds bf16(scale_n * n) -- with scale_n = inv_t * log2(e) the exponent scale of the
             # softmax rides in the MFMA and the kernels skip a multiply-add per score (results are scale-free).
@@ -108,25 +89,32 @@ class _ScoreCEFn(torch.autograd.Function):
             else:
                 scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
                 Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
-            if not want_col_rank and not full_rank:
-                # steady state of training: ONE sweep of the B x B tiles serves both softmax directions (tt_score_fwd_sym_bf16)
-                rowsum, colsum, diag, row_rank, inv, out8, loss = ops.score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True)
-                ctx.packed = (Np, Cp, scale_n, inv)
-                ctx.save_for_backward(n, c, rowsum, colsum)
-                ctx.inv_t, ctx.shift = inv_t, shift
-                ctx.mark_non_differentiable(out8, row_rank)
-                ctx.set_materialize_grads(False)
-                return loss, out8, row_rank
-            rowsum, colsum, diag, row_rank, col_rank, sumscore, inv = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, want_col_rank,
-                                                                                         full_rank, scale_n, with_inv=True)
-            if not want_col_rank:
-                col_rank = row_rank                      # placeholder: column top-1 rate is only a first-call diagnostic
-            ctx.packed = (Np, Cp, scale_n, inv)
+        # the kernel form, once.  Symmetric: ONE sweep of the B x B tiles serves both softmax directions -- the steady state of
+        # training, and always for fp8 and the logQ correction (its row ranks and metrics are the raw scores').  Otherwise the
+        # first call's diagnostics (column / full ranks) on the two-direction kernel, or the f32 path's two directional sweeps.
+        w = None
+        if Np is not None and (fp8 or lq or not (want_col_rank or full_rank)):
+            rowsum, colsum, diag, row_rank, inv, out8, loss, w = ops._fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, fp8, x3,
+                                                                              lq_n, lq_c)
+            if lq and want_col_rank:
+                # the first call's column top-1 rate (a diagnostic only) from the uncorrected two-direction kernel
+                col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
+                out8 = out8.clone()
+                out8[5] = (col_rank == 0).float().mean()
         else:
-            rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True)
-            colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False)
-            ctx.packed = None
-        out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore)
+            if Np is not None:
+                rowsum, colsum, diag, row_rank, col_rank, sumscore, inv = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, want_col_rank,
+                                                                                             full_rank, scale_n, with_inv=True, x3=x3)
+                if not want_col_rank:
+                    col_rank = row_rank                  # placeholder: column top-1 rate is only a first-call diagnostic
+            else:
+                rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c)
+                colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n)
+                if lq:
+                    w = (lq_n.contiguous(), lq_c.contiguous())
+            out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c)
+        ctx.packed = None if Np is None else (Np, Cp, scale_n, inv)
+        ctx.fp8, ctx.x3, ctx.lq = fp8, x3, w
         ctx.save_for_backward(n, c, rowsum, colsum)
         ctx.inv_t, ctx.shift = inv_t, shift
         ctx.mark_non_differentiable(out8, row_rank)
@@ -134,69 +122,23 @@ class _ScoreCEFn(torch.autograd.Function):
         return loss, out8, row_rank
 
     @staticmethod
-    def _forward_lq(ctx, n, c, inv_t, shift, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c):
-        """The corrected forward: bf16 / bf16x3 always on the symmetric kernel (its row ranks and metrics are the raw scores'); the
-        first call's column top-1 rate (a diagnostic only) comes from the uncorrected two-direction kernel."""
-        B, D = n.shape
-        ops._lq_check_t(inv_t)
-        if score_dtype in ("bf16", "bf16x3"):
-            x3 = score_dtype == "bf16x3"
-            if x3:
-                scale_n = 1.0
-                Np, Cp = ops.score_pack2_bf16x3(n, c, scale_n, 1.0)
-            elif packed_n is not None and packed_c is not None:
-                Np, Cp = packed_n, packed_c
-                scale_n = 1.0 if scale_n is None else scale_n
-            else:
-                scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
-                Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
-            rowsum, colsum, diag, row_rank, inv, w, out8, loss = ops.score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n,
-                                                                                      True, x3=x3)
-            if want_col_rank:
-                col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
-                out8 = out8.clone()
-                out8[5] = (col_rank == 0).float().mean()
-            ctx.packed = (Np, Cp, scale_n, inv)
-            ctx.x3 = x3
-            ctx.lq = w
-        else:
-            rowsum, diag, row_rank, sumscore = ops.score_dir_fwd_lq(n, c, inv_t, shift, lq_c, 0, True)
-            colsum, _, col_rank, _ = ops.score_dir_fwd_lq(c, n, inv_t, shift, lq_n, 0, False)
-            out8, loss = ops.score_loss_finish_lq(B, shift, lq_n, lq_c, rowsum, colsum, diag, row_rank, col_rank, sumscore)
-            ctx.packed = None
-            ctx.lq = (lq_n.contiguous(), lq_c.contiguous())
-        ctx.fp8 = False
-        ctx.save_for_backward(n, c, rowsum, colsum)
-        ctx.inv_t, ctx.shift = inv_t, shift
-        ctx.mark_non_differentiable(out8, row_rank)
-        ctx.set_materialize_grads(False)
-        return loss, out8, row_rank
-
-    @staticmethod
     def backward(ctx, d_loss, _d_out8, _d_rank):
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return None, None, None, None, None, None, None, None, None, None, None
+            return (None,) * 11
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
-        if ctx.lq is not None:
-            if ctx.packed is not None:
-                dN, dC = ops.score_bwd_bf16_lq(ctx.packed[0], ctx.packed[1], B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale,
-                                               ctx.lq, ctx.packed[2], ctx.packed[3], x3=ctx.x3)
-            else:
-                lqn, lqc = ctx.lq
-                dN = ops.score_dir_bwd_lq(n, c, ctx.inv_t, ctx.shift, 0, lqn, lqc, rowsum, colsum, d_loss, scale)
-                dC = ops.score_dir_bwd_lq(c, n, ctx.inv_t, ctx.shift, 0, lqc, lqn, colsum, rowsum, d_loss, scale)
-            return dN, dC, None, None, None, None, None, None, None, None, None
         if ctx.packed is not None:
-            dN, dC = ops.score_bwd_bf16(ctx.packed[0], ctx.packed[1], B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale,
-                                        ctx.packed[2], ctx.packed[3], fp8=ctx.fp8, x3=ctx.x3)
+            Np, Cp, scale_n, inv = ctx.packed
+            dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, fp8=ctx.fp8,
+                                        x3=ctx.x3, w=ctx.lq)
         else:
-            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale)
-            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale)
-        return dN, dC, None, None, None, None, None, None, None, None, None
+            lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
+            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc)
+            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn)
+        return (dN, dC) + (None,) * 9
 
 
 class _Result(dict):
