@@ -203,6 +203,9 @@ int tt_dedup_plan_keyed_km(tt_ctx* ctx, const int32_t* rows_km, const int32_t* s
  * are summed chunk by chunk, and the list of those rows / chunks depends on the plan only.  Built here -- into the workspace
  * tt_embed_grad_bwd will be called with (size tt_embed_grad_workspace_bytes(M, E), flag TT_GRAD_PLANNED; nobody else may touch
  * it in between) -- the reduction's row pass and chunk pass run as ONE launch instead of one after the other.
+ * The list and its counters belong to the plan: the reductions over it (tt_embed_grad_bwd with TT_GRAD_PLANNED, the deferred
+ * finishes) read them and leave them as they are, so any number of reductions may run over one plan (several backward passes
+ * of one forward: TT_GRAD_DENSE_SET, then TT_GRAD_DENSE_ACC).  Building the plan again resets them.
  * rows_key_major: 0 = the lookup's slot-major rows, 1 = tt_batch_ingest's [key][sample] rows. */
 int tt_dedup_plan_keyed_long(tt_ctx* ctx, const int32_t* rows, int32_t rows_key_major, const int32_t* side_K /* host [n_sides] */,
                              int32_t n_sides, int64_t B, int32_t E, int32_t* sorted_src, int32_t* unique_rows,

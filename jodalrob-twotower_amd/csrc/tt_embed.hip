@@ -1347,7 +1347,10 @@ __device__ __forceinline__ void long_rows_finish(int32_t E, uint32_t C, const in
   }
 }
 
-template <int VEC>
+// RESET: the words [0] / [1] were counted up by this reduction's row pass (unplanned).  Planned, they are the PLAN's: its
+// compaction counted them and every reduction over that plan reads them again, so they are left as they are (a graph replay
+// rebuilds the plan, and keyed_sort_kernel zeroes them in front of its compaction).
+template <int VEC, bool RESET = true>
 __global__ __launch_bounds__(kThreads) void seg_long_finish_kernel(int32_t E, uint32_t C, const int32_t* __restrict__ seg,
                                                                   const int32_t* __restrict__ unique_rows, int32_t mode,
                                                                   float* __restrict__ out, GradWs ws, uint32_t LG) {
@@ -1355,7 +1358,7 @@ __global__ __launch_bounds__(kThreads) void seg_long_finish_kernel(int32_t E, ui
   // nobody reads the live words [0] / [1] any more (counters[2] holds the snapshot), so one thread zeroes them here for the
   // next call -- a caller that keeps the words between calls needs no zeroing launch
   // (a "last workgroup done" atomic instead cost 35 us: 2048 same-address atomics with return serialise at ~17 ns each)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { ws.counters[0] = 0; ws.counters[1] = 0; }
+  if (RESET && blockIdx.x == 0 && threadIdx.x == 0) { ws.counters[0] = 0; ws.counters[1] = 0; }
   long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x, gridDim.x, part, [&](int32_t u, int32_t col, float tot) {
     const int64_t orow = mode == TT_GRAD_SPARSE ? (int64_t)u : (int64_t)unique_rows[u];
     float* o = out + orow * E + col;
@@ -2629,6 +2632,11 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   a.total_slots = (uint32_t)slots;
   const uint32_t LG = pow2_at_least(a.C) > 64 ? 64 : pow2_at_least(a.C);
   const int dt = srcs[0].dtype;
+  // (before any launch: a refused call leaves the caller's counters and the plan's workspace as they were)
+  if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
+    tt_set_error("tt_embed_grad_bwd: E=%d too wide for the long-row finish (max %d)", E, kFinishMaxFloats * (int)LG / kThreads);
+    return TT_ERR_UNSUPPORTED;
+  }
   GradLayout gl = grad_layout(reinterpret_cast<char*>(workspace), M, E);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = tt_riders_flush(ctx, st)) return rc;      // a plan compaction nobody hosted: this reduction reads its output
@@ -2651,10 +2659,6 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   const int g1 = grid_for(ctx, M * LG);
   const int g2 = grid_for(ctx, gl.max_chunks * LG);
   const int g3 = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);   // a workgroup per long row
-  if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
-    tt_set_error("tt_embed_grad_bwd: E=%d too wide for the long-row finish (max %d)", E, kFinishMaxFloats * (int)LG / kThreads);
-    return TT_ERR_UNSUPPORTED;
-  }
   // all sources share one element type (checked above): it is a template parameter of the kernels, and so is
   // the lane-group width when every lane of a group owns exactly one chunk (shared decode, see sum_range)
 #define TT_SEG_LAUNCH(V, D, G)                                                                                                  \
@@ -2669,14 +2673,14 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
       TT_LAUNCH_CHECK();                                                                                                        \
       slabs->n = 0;                                                                                                             \
       slabs->maxtotal = 1;                                                                                                      \
-      if (!defer) seg_long_finish_kernel<V><<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG);   \
+      if (!defer) seg_long_finish_kernel<V, false><<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG); \
       break;                                                                                                                    \
     }                                                                                                                           \
     if (planned) {                                                                                                              \
       seg_reduce_chunk_kernel<V, D, G><<<g1 + g2, kThreads, 0, st>>>(a, sorted_src, seg_offsets, unique_rows, n_unique, mode,   \
                                                                      out, gl.ws, LG, (uint32_t)g1);                             \
       TT_LAUNCH_CHECK();                                                                                                        \
-      if (!defer) seg_long_finish_kernel<V><<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG);   \
+      if (!defer) seg_long_finish_kernel<V, false><<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG); \
       break;                                                                                                                    \
     }                                                                                                                           \
     seg_reduce_kernel<V, D, G><<<g1, kThreads, 0, st>>>(a, sorted_src, seg_offsets, unique_rows, n_unique, mode, out, gl.ws, LG, \
@@ -3005,8 +3009,9 @@ int tt_embed_grad_finish(tt_ctx* ctx, int32_t E, const int32_t* seg_offsets, int
   const GradLayout gl = grad_layout(reinterpret_cast<char*>(workspace), M, E);
   const int g3 = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (vec4) seg_long_finish_kernel<4><<<g3, kThreads, 0, st>>>(E, C, seg_offsets, nullptr, TT_GRAD_SPARSE, out, gl.ws, LG);
-  else seg_long_finish_kernel<1><<<g3, kThreads, 0, st>>>(E, C, seg_offsets, nullptr, TT_GRAD_SPARSE, out, gl.ws, LG);
+  // (deferred only from a planned reduction: the counters are the plan's)
+  if (vec4) seg_long_finish_kernel<4, false><<<g3, kThreads, 0, st>>>(E, C, seg_offsets, nullptr, TT_GRAD_SPARSE, out, gl.ws, LG);
+  else seg_long_finish_kernel<1, false><<<g3, kThreads, 0, st>>>(E, C, seg_offsets, nullptr, TT_GRAD_SPARSE, out, gl.ws, LG);
   TT_LAUNCH_CHECK();
   return TT_OK;
 }

@@ -107,6 +107,33 @@ def embed_grad_sparse(d_concat: np.ndarray, ids_clamped: np.ndarray, row_offsets
     return uniq.astype(np.int64), out.astype(d_concat.dtype)
 
 
+# Exactly summable gradient values: multiples of 2^-4 with |j| <= jmax (jmax <= 3: exact in bf16 as well).  Every partial sum
+# of such values is a multiple of 2^-4; while a row's sum of |x| stays below 2^20 every one of them fits f32's 24-bit
+# significand, so ANY summation order gives the exact f64 sum -- a kernel's result must then equal it bit for bit.
+EXACT_GRID = 2.0 ** -4
+EXACT_ABS_LIMIT = 2.0 ** 20
+
+
+def exact_grid_values(rng, shape, jmax: int = 3) -> np.ndarray:
+    return (rng.integers(-jmax, jmax + 1, size=shape).astype(np.float64) * EXACT_GRID).astype(np.float32)
+
+
+def row_sums_f64(rows: np.ndarray, vals: np.ndarray):
+    """Per distinct row of `rows` [M] (ascending): (rows [U], sum of vals [U, E] in f64, sum of |vals| [U, E] in f64, count [U]).
+    Sort plus np.add.reduceat: no Python loop however many slots."""
+    order = np.argsort(rows, kind="stable")
+    rs = rows[order]
+    v = np.asarray(vals, dtype=np.float64)[order]
+    uniq, start, cnt = np.unique(rs, return_index=True, return_counts=True)
+    return uniq, np.add.reduceat(v, start, axis=0), np.add.reduceat(np.abs(v), start, axis=0), cnt
+
+
+def exact_sum_precondition(abs_sums) -> bool:
+    """True when every row's sum of |x| (prior included) keeps all partial sums of grid values exact in f32."""
+    a = np.asarray(abs_sums, dtype=np.float64)
+    return bool(a.size == 0 or a.max() < EXACT_ABS_LIMIT)
+
+
 # ------------------------------------------------------------------------------------------------
 # dropout mask of the HIP kernels (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip dropout_scale): the mask is never
 # stored; every kernel regenerates it from (seed, element index).  Element (r, c) of hidden block i of tower t (t = the tower's
@@ -514,12 +541,15 @@ def adam_step(p, g, m, v, t, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0):
     p -= (lr / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + eps)
 
 
-def sparse_adam_rows(table, m, v, step_rows, rows, grad_rows, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0):
-    """Row-wise sparse Adam of this build (NOT in the reference; DESIGN.md 'optimiser semantics'):
-    only the looked-up rows are touched; each row keeps its own step count for bias correction."""
-    for r, g in zip(rows, grad_rows):
-        step_rows[r] += 1
-        adam_step(table[r], g.astype(table.dtype), m[r], v[r], int(step_rows[r]), lr, b1, b2, eps, wd)
+def sparse_adam_rows(table, m, v, step, rows, grad_rows, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0):
+    """Row-sparse Adam of this build (NOT in the reference): only the distinct looked-up `rows` are
+    updated, each with its gradient row, and the bias correction uses the optimiser's GLOBAL step count `step` (1-based), as
+    FusedAdam and the kernels do -- a row that skipped steps is not corrected for them.  In place on table, m, v."""
+    rows = np.asarray(rows)
+    assert len(np.unique(rows)) == len(rows), "rows must be distinct"
+    p, mm, vv = table[rows], m[rows], v[rows]
+    adam_step(p, np.asarray(grad_rows).astype(table.dtype), mm, vv, int(step), lr, b1, b2, eps, wd)
+    table[rows], m[rows], v[rows] = p, mm, vv
 
 
 # ------------------------------------------------------------------------------------------------

@@ -317,6 +317,50 @@ def test_f32_step_vs_f64_oracle(tt, schema_real, tmp_path, rows_per_tower, B, T,
     _assert_step(report, ref_metric, mat, vec, B, F32_STEP_BOUNDS)
 
 
+def test_f32_step_slab_form_vs_f64_oracle(tt, schema_real, tmp_path, monkeypatch):
+    """The bench shape of test_f32_step_vs_f64_oracle (B = 8192, sparse, planned) with the towers' slab reduction deferred into
+    the embedding gradient's launch (seg_reduce_chunk_slab_kernel, what GraphedTrainStep replays), under F32_STEP_BOUNDS."""
+    from jodalrob_twotower_amd import config as _cfg
+    monkeypatch.setattr(_cfg.settings, "grad_planned", True)
+    task, schema = _real_task(tt, schema_real, tmp_path, 1_000_000, [128, 64], 64, 1.0, "sparse")
+    dev = torch.device(DEV)
+    _L.set_defer_slab_reduce(dev, True)
+    try:
+        report, ref_metric, mat, vec = _step_vs_oracle(task, schema, 8192, 1.0, "sparse", seed=2468)
+        pending = bool(_L.load().tt_deferred_pending(_L.ctx(dev)))
+    finally:
+        _L.set_defer_slab_reduce(dev, False)
+    assert not pending
+    store = task.two_tower_model.embedding_store
+    store = store() if callable(store) else store
+    assert store.sparse_grad[0].grad_ws is not None                  # the planned workspace: the slab form of the launch
+    _print("f32 step (slab form) vs f64 oracle", report)
+    _assert_step(report, ref_metric, mat, vec, 8192, F32_STEP_BOUNDS)
+
+
+def test_f32_step_second_backward_over_retained_graph(tt, schema_real, tmp_path, monkeypatch):
+    """Dense table gradients (the default) on the real schema at B = 4096 (keyed plan with the long-row list): two backward
+    passes over one retained graph give exactly twice the first pass's gradients, tables (TT_GRAD_DENSE_SET, then
+    TT_GRAD_DENSE_ACC over the same plan: the rows of more than 64 slots included) and dense parameters alike."""
+    from jodalrob_twotower_amd import config as _cfg
+    from jodalrob_twotower_amd import synthetic
+    monkeypatch.setattr(_cfg.settings, "grad_planned", True)
+    task, (kn, kc, vn, vc) = _real_task(tt, schema_real, tmp_path, None, [128, 64], 64, 1.0, "dense")
+    batch = synthetic.make_batch(4096, vn, vc, kn, kc, 256, 128, torch.device(DEV), seed=97)
+    loss = task(batch, return_metrics=True)["loss"]
+    loss.backward(retain_graph=True)
+    first = {n: p.grad.clone() for n, p in task.named_parameters() if p.grad is not None}
+    loss.backward()
+    assert len(first) == len(list(task.parameters()))
+    n_tables = 0
+    for n, p in task.named_parameters():
+        n_tables += "categorical_embedder" in n
+        assert first[n].abs().max() > 0, n
+        bad = int((p.grad != 2 * first[n]).sum())
+        assert bad == 0, (n, bad)
+    assert n_tables > 0
+
+
 # ------------------------------------------------------------------------------------------------ 3. the dense loss path
 # tt_score_dense_fwd = tt_gemm_nt (S = N C^T / T), dense_row_stats, dense_col_stats, dense_finish; tt_score_dense_bwd =
 # dense_grad (S -> dS in place), tt_gemm_nn_batched (dN = dS C, K = B), tt_gemm_tn_batched (dC = dS^T N, split-K slabs over B).
