@@ -1369,6 +1369,10 @@ __global__ __launch_bounds__(kThreads) void seg_long_finish_kernel(int32_t E, ui
 // ------------------------------------------------------------------------------------------------
 // a17: Adam
 // ------------------------------------------------------------------------------------------------
+// blockDim.x for code shared between kernels (roles): blockDim.x itself goes through the device library's partial-workgroup select, which only a
+// kernel body folds into one load; the builtin is that one load (HIP launches are uniform), so a role compiles as it would inline
+__device__ __forceinline__ uint32_t role_threads() { return __builtin_amdgcn_workgroup_size_x(); }
+
 struct AdamK {
   float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, wd;
   const float* dev;   // optional device copy of the six scalars above (graph replay)
@@ -1384,7 +1388,7 @@ __device__ __forceinline__ AdamK adam_resolve(const AdamK& k) {
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamK& k) {
   // explicit fused multiply-adds: left to the compiler, the contraction of a * b + c * d differs from one inlining context
-  // to the next (the float4 row path and the scalar long-row path of adam_fused_kernel disagreed in the last bit)
+  // to the next (the float4 row path and the scalar long-row path of the fused launch disagreed in the last bit)
   g = k.wd != 0.f ? __builtin_fmaf(k.wd, p, g) : g;
   m = __builtin_fmaf(k.b1, m, (1.f - k.b1) * g);
   v = __builtin_fmaf(k.b2, v, (1.f - k.b2) * g * g);
@@ -1432,36 +1436,25 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a, A
   }
 }
 
+// the update of one table row by its LG lanes (lig = lane in group); g: the row's gradient; w / m / v: the [R, E] weights and
+// moments, the row starts at element `off` of each (one offset for the three, as they share a layout)
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void adam_sparse_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
-                                                              int32_t E, uint32_t C, const int32_t* __restrict__ unique_rows,
-                                                              const float* __restrict__ grad_rows, const int32_t* __restrict__ n_unique,
-                                                              AdamK k0, uint32_t LG, int64_t table_rows) {
-  const AdamK k = adam_resolve(k0);
-  const uint32_t U = (uint32_t)*n_unique;
-  const uint32_t gthread = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lig = gthread % LG;
-  const uint32_t ngroups = gridDim.x * blockDim.x / LG;
-  for (uint32_t u = gthread / LG; u < U; u += ngroups) {
-    const int64_t row = unique_rows[u];
-    if (row >= table_rows) continue;                   // routing pad (multi-GPU fixed-capacity buckets)
-    for (uint32_t chunk = lig; chunk < C; chunk += LG) {
-      const int64_t o = row * E + chunk * VEC;
-      const float* gp = grad_rows + (int64_t)u * E + chunk * VEC;
-      if (VEC == 4) {
-        float4 pp = *reinterpret_cast<float4*>(table + o), mm = *reinterpret_cast<float4*>(m + o),
-               vv = *reinterpret_cast<float4*>(v + o);
-        const float4 gg = *reinterpret_cast<const float4*>(gp);
-        adam1(pp.x, gg.x, mm.x, vv.x, k); adam1(pp.y, gg.y, mm.y, vv.y, k);
-        adam1(pp.z, gg.z, mm.z, vv.z, k); adam1(pp.w, gg.w, mm.w, vv.w, k);
-        *reinterpret_cast<float4*>(table + o) = pp;
-        *reinterpret_cast<float4*>(m + o) = mm;
-        *reinterpret_cast<float4*>(v + o) = vv;
-      } else {
-        float pp = table[o], mm = m[o], vv = v[o];
-        adam1(pp, gp[0], mm, vv, k);
-        table[o] = pp; m[o] = mm; v[o] = vv;
-      }
+__device__ __forceinline__ void adam_row(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                         int64_t off, uint32_t C, uint32_t LG, uint32_t lig, const AdamK& k) {
+  for (uint32_t chunk = lig; chunk < C; chunk += LG) {
+    const int64_t o = off + chunk * VEC;
+    if constexpr (VEC == 4) {
+      float4 pp = *reinterpret_cast<float4*>(w + o), mm = *reinterpret_cast<float4*>(m + o), vv = *reinterpret_cast<float4*>(v + o);
+      const float4 gg = *reinterpret_cast<const float4*>(g + chunk * VEC);
+      adam1(pp.x, gg.x, mm.x, vv.x, k); adam1(pp.y, gg.y, mm.y, vv.y, k);
+      adam1(pp.z, gg.z, mm.z, vv.z, k); adam1(pp.w, gg.w, mm.w, vv.w, k);
+      *reinterpret_cast<float4*>(w + o) = pp;
+      *reinterpret_cast<float4*>(m + o) = mm;
+      *reinterpret_cast<float4*>(v + o) = vv;
+    } else {
+      float pp = w[o], mm = m[o], vv = v[o];
+      adam1(pp, g[chunk], mm, vv, k);
+      w[o] = pp; m[o] = mm; v[o] = vv;
     }
   }
 }
@@ -1474,71 +1467,18 @@ struct AdamFusedArgs {
   int32_t n;
 };
 
-// LONG: the gradient reduction left its long rows unfinished (TT_GRAD_DEFER_FINISH): blocks [nd, nd + nlb) add a long row's
-// chunk partials exactly as seg_long_finish_kernel does, store the sum into grad_rows and update that table row; the row
-// blocks skip those rows.  One launch fewer in the step's dependent chain, the same values.
-template <int VEC, bool LONG>
-__global__ __launch_bounds__(kThreads) void adam_fused_kernel(AdamFusedArgs a, float* __restrict__ table, float* __restrict__ m,
-                                                             float* __restrict__ v, int32_t E, uint32_t C,
-                                                             const int32_t* __restrict__ unique_rows, float* __restrict__ grad_rows,
-                                                             const int32_t* __restrict__ n_unique, AdamK k0, uint32_t LG, int64_t table_rows,
-                                                             const int32_t* __restrict__ seg, GradWs ws, int nlb) {
-  const AdamK k = adam_resolve(k0);
-  const int nd = a.blk0[a.n];
-  if ((int)blockIdx.x < nd) {
-    int ti = 0;
-    for (int i = 1; i < a.n; ++i)
-      if ((int)blockIdx.x >= a.blk0[i]) ti = i;
-    const tt_adam_tensor t = a.t[ti];
-    const int64_t nb = a.blk0[ti + 1] - a.blk0[ti];
-    const int64_t stride = nb * blockDim.x;
-    for (int64_t i = (int64_t)((int)blockIdx.x - a.blk0[ti]) * blockDim.x + threadIdx.x; i < t.n; i += stride) {
-      float pp = t.p[i], mm = t.m[i], vv = t.v[i];
-      adam1(pp, t.g[i], mm, vv, k);
-      t.p[i] = pp; t.m[i] = mm; t.v[i] = vv;
-    }
-    return;
-  }
-  const int first = nd + (LONG ? nlb : 0);
-  if (LONG && (int)blockIdx.x < first) {
-    __shared__ float part[kFinishMaxFloats];
-    long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x - nd, (uint32_t)nlb, part, [&](int32_t u, int32_t col, float tot) {
-      grad_rows[(int64_t)u * E + col] = tot;
-      const int64_t row = unique_rows[u];
-      if (row >= table_rows) return;
-      const int64_t o = row * E + col;
-      float pp = table[o], mm = m[o], vv = v[o];
-      adam1(pp, tot, mm, vv, k);
-      table[o] = pp; m[o] = mm; v[o] = vv;
-    });
-    return;
-  }
-  const uint32_t U = (uint32_t)*n_unique;
-  const uint32_t gthread = (blockIdx.x - first) * blockDim.x + threadIdx.x;
-  const uint32_t lig = gthread % LG;
-  const uint32_t ngroups = (gridDim.x - first) * blockDim.x / LG;
-  for (uint32_t u = gthread / LG; u < U; u += ngroups) {
-    const int64_t row = unique_rows[u];
-    if (row >= table_rows) continue;                   // routing pad (multi-GPU fixed-capacity buckets)
-    if (LONG && seg[u + 1] - seg[u] > kLongSeg) continue;   // finished and applied by the long-row blocks
-    for (uint32_t chunk = lig; chunk < C; chunk += LG) {
-      const int64_t o = row * E + chunk * VEC;
-      const float* gp = grad_rows + (int64_t)u * E + chunk * VEC;
-      if (VEC == 4) {
-        float4 pp = *reinterpret_cast<float4*>(table + o), mm = *reinterpret_cast<float4*>(m + o),
-               vv = *reinterpret_cast<float4*>(v + o);
-        const float4 gg = *reinterpret_cast<const float4*>(gp);
-        adam1(pp.x, gg.x, mm.x, vv.x, k); adam1(pp.y, gg.y, mm.y, vv.y, k);
-        adam1(pp.z, gg.z, mm.z, vv.z, k); adam1(pp.w, gg.w, mm.w, vv.w, k);
-        *reinterpret_cast<float4*>(table + o) = pp;
-        *reinterpret_cast<float4*>(m + o) = mm;
-        *reinterpret_cast<float4*>(v + o) = vv;
-      } else {
-        float pp = table[o], mm = m[o], vv = v[o];
-        adam1(pp, gp[0], mm, vv, k);
-        table[o] = pp; m[o] = mm; v[o] = vv;
-      }
-    }
+// the dense-tensor role of block `bid` < nd: find its tensor in the prefix table, stride over it with the tensor's blocks
+__device__ __forceinline__ void adam_dense_role(const AdamFusedArgs& a, int bid, const AdamK& k) {
+  int ti = 0;
+  for (int i = 1; i < a.n; ++i)
+    if (bid >= a.blk0[i]) ti = i;
+  const tt_adam_tensor t = a.t[ti];
+  const int64_t nb = a.blk0[ti + 1] - a.blk0[ti];
+  const int64_t stride = nb * role_threads();
+  for (int64_t i = (int64_t)(bid - a.blk0[ti]) * role_threads() + threadIdx.x; i < t.n; i += stride) {
+    float pp = t.p[i], mm = t.m[i], vv = t.v[i];
+    adam1(pp, t.g[i], mm, vv, k);
+    t.p[i] = pp; t.m[i] = mm; t.v[i] = vv;
   }
 }
 
@@ -1606,23 +1546,89 @@ __device__ __forceinline__ void adagrad_row(float* __restrict__ w, const float* 
   if (lig == 0) *s = snew;
 }
 
+// ------------------------------------------------------------------------------------------------
+// a17c: the row rules and the launches built from them
+// A row rule is what an optimiser does to one looked-up table row: its state, its hyper-parameters (resolve() once per
+// thread, before anything else; it is handed the towers' Adam set), row() for a row whose gradient is complete in grad_rows,
+// and the two long_rows_finish hooks for a row whose gradient the long-row blocks are still adding up (long_col: EMIT, one
+// finished column, already stored to grad_rows; long_done: DONE; `row` may be a routing pad there: >= table_rows).
+// The rule types are plain structs, not templates: tools/bench_table_optimizer.py reads them out of the kernel names.
+// ------------------------------------------------------------------------------------------------
+struct AdamRows {
+  float* m;   // [R, E] moments
+  float* v;
+  AdamK k;    // the towers' set: the fused Adam launch has one (the host leaves it empty)
+  __device__ __forceinline__ void resolve(const AdamK& towers) { k = adam_resolve(towers); }
+  template <int VEC>
+  __device__ __forceinline__ void row(float* __restrict__ table, int64_t row, const float* __restrict__ g, int32_t E, uint32_t C,
+                                      uint32_t LG, uint32_t lig) const {
+    adam_row<VEC>(table, g, m, v, row * E, C, LG, lig, k);
+  }
+  // EMIT: each column is applied by the thread that finished it
+  __device__ __forceinline__ void long_col(float* __restrict__ table, int64_t row, int64_t table_rows, int32_t E, int32_t col,
+                                           float tot) const {
+    if (row >= table_rows) return;
+    const int64_t o = row * E + col;
+    float pp = table[o], mm = m[o], vv = v[o];
+    adam1(pp, tot, mm, vv, k);
+    table[o] = pp; m[o] = mm; v[o] = vv;
+  }
+  // DONE: nothing left to do (NoRowDone)
+  template <int VEC>
+  __device__ __forceinline__ void long_done(float*, int64_t, int64_t, int32_t, uint32_t, uint32_t) const {}
+};
+
+struct AdagradRows {
+  float* sum;   // [R] accumulators
+  AdagradK k;
+  __device__ __forceinline__ void resolve(const AdamK&) { k = adagrad_resolve(k); }
+  template <int VEC>
+  __device__ __forceinline__ void row(float* __restrict__ table, int64_t row, const float* __restrict__ g, int32_t E, uint32_t C,
+                                      uint32_t LG, uint32_t lig) const {
+    adagrad_row<VEC>(table + row * E, g, sum + row, E, C, LG, lig, k);
+  }
+  // the long row's gradient as the workgroup finishes it (only launches that call the hooks carry it)
+  static __device__ __forceinline__ float* row_copy() {
+    __shared__ __attribute__((aligned(16))) float rowg[kFinishMaxFloats / 4];   // E <= kFinishMaxFloats * LG / kThreads <= 1024
+    return rowg;
+  }
+  // EMIT: the column goes into the LDS copy of the row
+  __device__ __forceinline__ void long_col(float*, int64_t, int64_t, int32_t, int32_t col, float tot) const { row_copy()[col] = tot; }
+  // DONE: all E columns exist: the block's first LG lanes apply adagrad_row from the copy -- the same values and the same
+  // reduction order as the row blocks
+  template <int VEC>
+  __device__ __forceinline__ void long_done(float* __restrict__ table, int64_t row, int64_t table_rows, int32_t E, uint32_t C,
+                                            uint32_t LG) const {
+    if (threadIdx.x < LG && row < table_rows) adagrad_row<VEC>(table + row * E, row_copy(), sum + row, E, C, LG, threadIdx.x, k);
+  }
+};
+
 // the row-sparse update over the looked-up rows; LONG_SKIP: rows whose segment is longer than kLongSeg are left to the
 // long-row workgroups of the fused finish launch.  `first` blocks of the grid belong to other roles.
-template <int VEC, bool LONG_SKIP>
-__device__ __forceinline__ void adagrad_sparse_rows(float* __restrict__ table, float* __restrict__ sum, int32_t E, uint32_t C,
-                                                    const int32_t* __restrict__ unique_rows, const float* __restrict__ grad_rows,
-                                                    const int32_t* __restrict__ n_unique, const AdagradK& k, uint32_t LG,
-                                                    int64_t table_rows, const int32_t* __restrict__ seg, uint32_t first) {
+template <int VEC, bool LONG_SKIP, typename RULE>
+__device__ __forceinline__ void sparse_rows(const RULE& r, float* __restrict__ table, int32_t E, uint32_t C,
+                                            const int32_t* __restrict__ unique_rows, const float* __restrict__ grad_rows,
+                                            const int32_t* __restrict__ n_unique, uint32_t LG, int64_t table_rows,
+                                            const int32_t* __restrict__ seg, uint32_t first) {
   const uint32_t U = (uint32_t)*n_unique;
-  const uint32_t gthread = (blockIdx.x - first) * blockDim.x + threadIdx.x;
+  const uint32_t gthread = (blockIdx.x - first) * role_threads() + threadIdx.x;
   const uint32_t lig = gthread % LG;
-  const uint32_t ngroups = (gridDim.x - first) * blockDim.x / LG;
+  const uint32_t ngroups = (gridDim.x - first) * role_threads() / LG;
   for (uint32_t u = gthread / LG; u < U; u += ngroups) {
     const int64_t row = unique_rows[u];
     if (row >= table_rows) continue;                   // routing pad (multi-GPU fixed-capacity buckets)
     if (LONG_SKIP && seg[u + 1] - seg[u] > kLongSeg) continue;   // finished and applied by the long-row blocks
-    adagrad_row<VEC>(table + row * E, grad_rows + (int64_t)u * E, sum + row, E, C, LG, lig, k);
+    r.template row<VEC>(table, row, grad_rows + (int64_t)u * E, E, C, LG, lig);
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void adam_sparse_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
+                                                              int32_t E, uint32_t C, const int32_t* __restrict__ unique_rows,
+                                                              const float* __restrict__ grad_rows, const int32_t* __restrict__ n_unique,
+                                                              AdamK k0, uint32_t LG, int64_t table_rows) {
+  const AdamRows r{m, v, adam_resolve(k0)};
+  sparse_rows<VEC, false>(r, table, E, C, unique_rows, grad_rows, n_unique, LG, table_rows, nullptr, 0);
 }
 
 template <int VEC>
@@ -1630,8 +1636,8 @@ __global__ __launch_bounds__(kThreads) void adagrad_sparse_kernel(float* __restr
                                                                  const int32_t* __restrict__ unique_rows,
                                                                  const float* __restrict__ grad_rows, const int32_t* __restrict__ n_unique,
                                                                  AdagradK k0, uint32_t LG, int64_t table_rows) {
-  const AdagradK k = adagrad_resolve(k0);
-  adagrad_sparse_rows<VEC, false>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, nullptr, 0);
+  const AdagradRows r{sum, adagrad_resolve(k0)};
+  sparse_rows<VEC, false>(r, table, E, C, unique_rows, grad_rows, n_unique, LG, table_rows, nullptr, 0);
 }
 
 // dense gradient mode: every row of the [R, E] store
@@ -1647,47 +1653,33 @@ __global__ __launch_bounds__(kThreads) void adagrad_dense_kernel(float* __restri
     adagrad_row<VEC>(table + (int64_t)r * E, grad + (int64_t)r * E, sum + r, E, C, LG, lig, k);
 }
 
-// tower Adam (blocks [0, nd), as adam_fused_kernel) + the table's row-wise Adagrad in ONE launch, two hyper-parameter sets.
-// LONG (TT_GRAD_DEFER_FINISH): blocks [nd, nd + nlb) finish a long row's gradient as seg_long_finish_kernel does (into
-// grad_rows and a copy in LDS); once all E columns exist, the block's first LG lanes apply adagrad_row to that row from the
-// LDS copy -- the same values and the same reduction order as the row blocks, so the result equals the separate entries.
-template <int VEC, bool LONG>
-__global__ __launch_bounds__(kThreads) void adam_adagrad_fused_kernel(AdamFusedArgs a, AdamK ak0, float* __restrict__ table,
-                                                                     float* __restrict__ sum, int32_t E, uint32_t C,
-                                                                     const int32_t* __restrict__ unique_rows, float* __restrict__ grad_rows,
-                                                                     const int32_t* __restrict__ n_unique, AdagradK gk0, uint32_t LG,
-                                                                     int64_t table_rows, const int32_t* __restrict__ seg, GradWs ws, int nlb) {
+// the towers' Adam + the looked-up table rows under RULE in ONE launch (AdagradRows brings a hyper-parameter set of its own; a
+// block resolves the one set its role needs: two device-scalar reads in a row are two memory latencies).  Blocks [0, nd): the dense tensors.  LONG: the gradient reduction left its long rows unfinished
+// (TT_GRAD_DEFER_FINISH): blocks [nd, nd + nlb) add a long row's chunk partials exactly as seg_long_finish_kernel does, store
+// the sum into grad_rows and update that table row through the rule's hooks; the row blocks behind them skip those rows.  One
+// launch fewer in the step's dependent chain, the same values as the separate entries.
+template <typename RULE, int VEC, bool LONG>
+__global__ __launch_bounds__(kThreads) void fused_step_kernel(AdamFusedArgs a, AdamK ak0, RULE r, float* __restrict__ table, int32_t E,
+                                                             uint32_t C, const int32_t* __restrict__ unique_rows,
+                                                             float* __restrict__ grad_rows, const int32_t* __restrict__ n_unique,
+                                                             uint32_t LG, int64_t table_rows, const int32_t* __restrict__ seg, GradWs ws,
+                                                             int nlb) {
   const int nd = a.blk0[a.n];
   if ((int)blockIdx.x < nd) {
-    const AdamK k = adam_resolve(ak0);
-    int ti = 0;
-    for (int i = 1; i < a.n; ++i)
-      if ((int)blockIdx.x >= a.blk0[i]) ti = i;
-    const tt_adam_tensor t = a.t[ti];
-    const int64_t nb = a.blk0[ti + 1] - a.blk0[ti];
-    const int64_t stride = nb * blockDim.x;
-    for (int64_t i = (int64_t)((int)blockIdx.x - a.blk0[ti]) * blockDim.x + threadIdx.x; i < t.n; i += stride) {
-      float pp = t.p[i], mm = t.m[i], vv = t.v[i];
-      adam1(pp, t.g[i], mm, vv, k);
-      t.p[i] = pp; t.m[i] = mm; t.v[i] = vv;
-    }
+    adam_dense_role(a, (int)blockIdx.x, adam_resolve(ak0));
     return;
   }
-  const AdagradK k = adagrad_resolve(gk0);
+  r.resolve(ak0);
   const int first = nd + (LONG ? nlb : 0);
   if (LONG && (int)blockIdx.x < first) {
     __shared__ float part[kFinishMaxFloats];
-    __shared__ __attribute__((aligned(16))) float rowg[kFinishMaxFloats / 4];   // E <= kFinishMaxFloats * LG / kThreads <= 1024
     long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x - nd, (uint32_t)nlb, part, [&](int32_t u, int32_t col, float tot) {
       grad_rows[(int64_t)u * E + col] = tot;
-      rowg[col] = tot;
-    }, [&](int32_t u) {
-      const int64_t row = unique_rows[u];
-      if (threadIdx.x < LG && row < table_rows) adagrad_row<VEC>(table + row * E, rowg, sum + row, E, C, LG, threadIdx.x, k);
-    });
+      r.long_col(table, unique_rows[u], table_rows, E, col, tot);
+    }, [&](int32_t u) { r.template long_done<VEC>(table, unique_rows[u], table_rows, E, C, LG); });
     return;
   }
-  adagrad_sparse_rows<VEC, LONG>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, seg, (uint32_t)first);
+  sparse_rows<VEC, LONG>(r, table, E, C, unique_rows, grad_rows, n_unique, LG, table_rows, seg, (uint32_t)first);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1713,10 +1705,6 @@ struct CopyArgs {
   const char* src[TT_MAX_COPIES];
   int64_t bytes[TT_MAX_COPIES];
 };
-
-// blockDim.x for the roles below: blockDim.x itself goes through the device library's partial-workgroup select, which only a
-// kernel body folds into one load; the builtin is that one load (HIP launches are uniform), so a role compiles as it would inline
-__device__ __forceinline__ uint32_t role_threads() { return __builtin_amdgcn_workgroup_size_x(); }
 
 // one copy segment per grid row: the 16-byte body strided over the row's workgroups, the byte tail by its first workgroup
 __device__ __forceinline__ void copy_segment_role(const CopyArgs& a, int seg) {
@@ -2273,6 +2261,18 @@ inline GradLayout grad_layout(char* base, int64_t M, int32_t E) {
   return g;
 }
 
+// the row mapping of the reduction and the optimiser: a row is C chunks of VEC floats (VEC = 4 when vec4), owned by LG lanes
+inline void row_mapping(int32_t E, bool vec4, uint32_t* C, uint32_t* LG) {
+  *C = (uint32_t)(vec4 ? E / 4 : E);
+  *LG = pow2_at_least(*C) > 64 ? 64 : pow2_at_least(*C);
+}
+
+// workgroups of a long-row finish: one per long row the workspace can list, at most eight per CU
+inline int long_row_blocks(const tt_ctx* ctx, const GradLayout& gl) {
+  const int64_t cap = (int64_t)ctx->num_cus * 8;
+  return (int)(gl.max_long < cap ? gl.max_long : cap);
+}
+
 template <int BITS>
 int sort_pass(hipStream_t st, const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t M, int shift,
               uint32_t* hist, uint32_t* total, uint32_t nblk) {
@@ -2316,6 +2316,93 @@ static int fill_cvt(const char* who, const tt_cvt_list* cvt, CvtDev* v, int64_t*
   }
   v->n = cvt->n;
   return 1;
+}
+
+// ---- optimiser launches ----
+// every optimiser entry starts here, before it looks at its arguments
+int flush_before_optimiser(tt_ctx* ctx, tt_stream stream) {
+  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
+  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
+    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
+  return TT_OK;
+}
+
+AdagradK make_adagrad(float lr, float eps, float wd, const float* dev) {
+  AdagradK k;
+  k.lr = lr; k.eps = eps; k.wd = wd;
+  k.dev = dev;
+  return k;
+}
+
+// adagrad_row holds a lane's chunks of the row in registers: false (error set) when a lane would own more than it holds
+bool adagrad_fits(const char* who, int32_t E, uint32_t C, uint32_t LG) {
+  if (C > (uint32_t)kAdagradMaxChunks * LG) {
+    tt_set_error("%s: E=%d too wide (max %d, or %d when E %% 4 != 0)", who, E, kAdagradMaxChunks * 64 * 4, kAdagradMaxChunks * 64);
+    return false;
+  }
+  return true;
+}
+
+// ---- the towers' Adam + the looked-up rows under a row rule, one launch ----
+// what the host asks of a rule: is its state there, does it allow float4 rows, does the row fit its row()
+bool rule_state(const AdamRows& r) { return r.m && r.v; }
+bool rule_state(const AdagradRows& r) { return r.sum != nullptr; }
+bool rule_vec4(const AdamRows& r) { return tt_aligned(r.m, 16) && tt_aligned(r.v, 16); }
+bool rule_vec4(const AdagradRows&) { return true; }      // (one accumulator per row: no vector access to it)
+bool rule_fits(const AdamRows&, const char*, int32_t, uint32_t, uint32_t) { return true; }
+bool rule_fits(const AdagradRows&, const char* who, int32_t E, uint32_t C, uint32_t LG) { return adagrad_fits(who, E, C, LG); }
+
+// grad_workspace != NULL: the reduction's deferred finish (tt_embed_grad_bwd with TT_GRAD_DEFER_FINISH) rides in this launch
+template <typename RULE>
+int fused_step_impl(tt_ctx* ctx, const char* who, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, const AdamK& ak,
+                           const RULE& rule, float* table, int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows,
+                           const int32_t* n_unique, int64_t M, const int32_t* seg_offsets, void* grad_workspace,
+                           size_t grad_workspace_bytes, tt_stream stream) {
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  TT_CHECK_ARG(ctx && tensors && table && rule_state(rule) && unique_rows && grad_rows && n_unique, "%s: NULL argument", who);
+  TT_CHECK_ARG(n_tensors >= 1 && n_tensors <= kAdamMulti, "%s: n_tensors=%d not in [1,%d]", who, n_tensors, kAdamMulti);
+  TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 1 && table_rows >= 1, "%s: bad step/E/M/table_rows", who);
+  AdamFusedArgs a{};
+  a.n = n_tensors;
+  int nd = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const tt_adam_tensor& t = tensors[i];
+    TT_CHECK_ARG(t.n >= 0 && (t.n == 0 || (t.p && t.g && t.m && t.v)), "%s: tensor %d has NULL pointers", who, i);
+    a.t[i] = t;
+    a.blk0[i] = nd;
+    int64_t nb = tt_cdiv(t.n > 0 ? t.n : 1, kThreads);
+    nd += (int)(nb > 64 ? 64 : nb);
+  }
+  a.blk0[n_tensors] = nd;
+  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && rule_vec4(rule) && tt_aligned(grad_rows, 16);
+  uint32_t C, LG;
+  row_mapping(E, vec4, &C, &LG);
+  if (!rule_fits(rule, who, E, C, LG)) return TT_ERR_UNSUPPORTED;
+  GradWs ws{};
+  int nlb = 0;
+  if (grad_workspace) {
+    TT_CHECK_ARG(seg_offsets, "%s: NULL seg_offsets", who);
+    if (grad_workspace_bytes < tt_embed_grad_workspace_bytes(M, E)) {
+      tt_set_error("%s: gradient workspace %zu < required %zu", who, grad_workspace_bytes, tt_embed_grad_workspace_bytes(M, E));
+      return TT_ERR_WORKSPACE;
+    }
+    if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
+      tt_set_error("%s: E=%d too wide for the long-row finish (max %d)", who, E, kFinishMaxFloats * (int)LG / kThreads);
+      return TT_ERR_UNSUPPORTED;
+    }
+    const GradLayout gl = grad_layout(reinterpret_cast<char*>(grad_workspace), M, E);
+    ws = gl.ws;
+    nlb = long_row_blocks(ctx, gl);
+  }
+  const int grid = nd + nlb + grid_for(ctx, M * LG);
+  auto launch = [&](auto kernel) {
+    kernel<<<grid, kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, ak, rule, table, E, C, unique_rows, grad_rows, n_unique, LG,
+                                                                         table_rows, seg_offsets, ws, nlb);
+  };
+  if (grad_workspace) vec4 ? launch(fused_step_kernel<RULE, 4, true>) : launch(fused_step_kernel<RULE, 1, true>);
+  else vec4 ? launch(fused_step_kernel<RULE, 4, false>) : launch(fused_step_kernel<RULE, 1, false>);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
 }
 
 }  // namespace
@@ -2628,9 +2715,9 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
     slots += B * s.K;
   }
   TT_CHECK_ARG(slots == M, "tt_embed_grad_bwd: sum(B*K)=%lld != M=%lld", (long long)slots, (long long)M);
-  a.C = (uint32_t)(vec4 ? E / 4 : E);
+  uint32_t LG;
+  row_mapping(E, vec4, &a.C, &LG);
   a.total_slots = (uint32_t)slots;
-  const uint32_t LG = pow2_at_least(a.C) > 64 ? 64 : pow2_at_least(a.C);
   const int dt = srcs[0].dtype;
   // (before any launch: a refused call leaves the caller's counters and the plan's workspace as they were)
   if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
@@ -2658,7 +2745,7 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   const int nsx = slabs ? tt_slab_role_blocks_x(slabs) : 0;
   const int g1 = grid_for(ctx, M * LG);
   const int g2 = grid_for(ctx, gl.max_chunks * LG);
-  const int g3 = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);   // a workgroup per long row
+  const int g3 = long_row_blocks(ctx, gl);
   // all sources share one element type (checked above): it is a template parameter of the kernels, and so is
   // the lane-group width when every lane of a group owns exactly one chunk (shared decode, see sum_range)
 #define TT_SEG_LAUNCH(V, D, G)                                                                                                  \
@@ -2716,9 +2803,7 @@ void tt_adam_hparams(int64_t step, float lr, float beta1, float beta2, float eps
 
 int tt_adam_dense_step(tt_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1,
                        float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
   TT_CHECK_ARG(ctx && (n == 0 || (p && g && m && v)), "tt_adam_dense_step: NULL argument");
   TT_CHECK_ARG(step >= 1 && n >= 0, "tt_adam_dense_step: step must be >= 1");
   if (n == 0) return TT_OK;
@@ -2736,9 +2821,7 @@ int tt_adam_dense_step(tt_ctx* ctx, float* p, const float* g, float* m, float* v
 
 int tt_adam_multi_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr, float beta1,
                        float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
   TT_CHECK_ARG(ctx && (n_tensors == 0 || tensors), "tt_adam_multi_step: NULL argument");
   TT_CHECK_ARG(step >= 1 && n_tensors >= 0, "tt_adam_multi_step: step must be >= 1");
   const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
@@ -2764,121 +2847,20 @@ int tt_adam_multi_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_ten
 int tt_sparse_adam_step(tt_ctx* ctx, float* table, float* m, float* v, int64_t table_rows, int32_t E, const int32_t* unique_rows,
                         const float* grad_rows, const int32_t* n_unique, int64_t M, int64_t step, float lr, float beta1, float beta2, float eps,
                         float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
+  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
   TT_CHECK_ARG(ctx && table && m && v, "tt_sparse_adam_step: NULL state");
   TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 0 && table_rows >= 1, "tt_sparse_adam_step: bad step/E/M/table_rows");
   if (M == 0) return TT_OK;
   TT_CHECK_ARG(unique_rows && grad_rows && n_unique, "tt_sparse_adam_step: NULL plan");
   const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
   const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(m, 16) && tt_aligned(v, 16) && tt_aligned(grad_rows, 16);
-  const uint32_t C = vec4 ? E / 4 : E;
-  const uint32_t LG = pow2_at_least(C) > 64 ? 64 : pow2_at_least(C);
+  uint32_t C, LG;
+  row_mapping(E, vec4, &C, &LG);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int grid = grid_for(ctx, M * LG);
   if (vec4) adam_sparse_kernel<4><<<grid, kThreads, 0, st>>>(table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows);
   else adam_sparse_kernel<1><<<grid, kThreads, 0, st>>>(table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows);
   TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
-static int adam_fused_impl(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, float* table, float* m, float* v,
-                           int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique, int64_t M,
-                           const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes, int64_t step, float lr,
-                           float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream,
-                           const char* who) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
-  TT_CHECK_ARG(ctx && tensors && table && m && v && unique_rows && grad_rows && n_unique, "%s: NULL argument", who);
-  TT_CHECK_ARG(n_tensors >= 1 && n_tensors <= kAdamMulti, "%s: n_tensors=%d not in [1,%d]", who, n_tensors, kAdamMulti);
-  TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 1 && table_rows >= 1, "%s: bad step/E/M/table_rows", who);
-  AdamFusedArgs a{};
-  a.n = n_tensors;
-  int nd = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    const tt_adam_tensor& t = tensors[i];
-    TT_CHECK_ARG(t.n >= 0 && (t.n == 0 || (t.p && t.g && t.m && t.v)), "%s: tensor %d has NULL pointers", who, i);
-    a.t[i] = t;
-    a.blk0[i] = nd;
-    int64_t nb = tt_cdiv(t.n > 0 ? t.n : 1, kThreads);
-    nd += (int)(nb > 64 ? 64 : nb);
-  }
-  a.blk0[n_tensors] = nd;
-  const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
-  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(m, 16) && tt_aligned(v, 16) && tt_aligned(grad_rows, 16);
-  const uint32_t C = vec4 ? E / 4 : E;
-  const uint32_t LG = pow2_at_least(C) > 64 ? 64 : pow2_at_least(C);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (grad_workspace) {
-    // the reduction's deferred finish (tt_embed_grad_bwd with TT_GRAD_DEFER_FINISH) rides in this launch
-    TT_CHECK_ARG(seg_offsets, "%s: NULL seg_offsets", who);
-    if (grad_workspace_bytes < tt_embed_grad_workspace_bytes(M, E)) {
-      tt_set_error("%s: gradient workspace %zu < required %zu", who, grad_workspace_bytes, tt_embed_grad_workspace_bytes(M, E));
-      return TT_ERR_WORKSPACE;
-    }
-    if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
-      tt_set_error("%s: E=%d too wide for the long-row finish (max %d)", who, E, kFinishMaxFloats * (int)LG / kThreads);
-      return TT_ERR_UNSUPPORTED;
-    }
-    const GradLayout gl = grad_layout(reinterpret_cast<char*>(grad_workspace), M, E);
-    const int nlb = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);
-    const int grid = nd + nlb + grid_for(ctx, M * LG);
-    if (vec4) adam_fused_kernel<4, true><<<grid, kThreads, 0, st>>>(a, table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, seg_offsets, gl.ws, nlb);
-    else adam_fused_kernel<1, true><<<grid, kThreads, 0, st>>>(a, table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, seg_offsets, gl.ws, nlb);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-  }
-  const int grid = nd + grid_for(ctx, M * LG);
-  if (vec4) adam_fused_kernel<4, false><<<grid, kThreads, 0, st>>>(a, table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, nullptr, GradWs{}, 0);
-  else adam_fused_kernel<1, false><<<grid, kThreads, 0, st>>>(a, table, m, v, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows, nullptr, GradWs{}, 0);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
-int tt_adam_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, float* table, float* m, float* v, int64_t table_rows,
-                       int32_t E,
-                       const int32_t* unique_rows, const float* grad_rows, const int32_t* n_unique, int64_t M, int64_t step, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  return adam_fused_impl(ctx, tensors, n_tensors, table, m, v, table_rows, E, unique_rows, const_cast<float*>(grad_rows), n_unique, M,
-                         nullptr, nullptr, 0, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, stream, "tt_adam_fused_step");
-}
-
-int tt_adam_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, float* table, float* m, float* v,
-                              int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique,
-                              int64_t M, const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes, int64_t step,
-                              float lr, float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev,
-                              tt_stream stream) {
-  TT_CHECK_ARG(grad_workspace, "tt_adam_fused_step_finish: NULL gradient workspace");
-  return adam_fused_impl(ctx, tensors, n_tensors, table, m, v, table_rows, E, unique_rows, grad_rows, n_unique, M, seg_offsets,
-                         grad_workspace, grad_workspace_bytes, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, stream,
-                         "tt_adam_fused_step_finish");
-}
-
-// ---- row-wise Adagrad ----
-static AdagradK make_adagrad(float lr, float eps, float wd, const float* dev) {
-  AdagradK k;
-  k.lr = lr; k.eps = eps; k.wd = wd;
-  k.dev = dev;
-  return k;
-}
-
-// the row mapping shared by the row-wise Adagrad entries; false (error set) when a lane would own more chunks than it holds
-static bool adagrad_mapping(const char* who, int32_t E, bool vec4, uint32_t* C, uint32_t* LG) {
-  *C = vec4 ? E / 4 : E;
-  *LG = pow2_at_least(*C) > 64 ? 64 : pow2_at_least(*C);
-  if (*C > (uint32_t)kAdagradMaxChunks * *LG) {
-    tt_set_error("%s: E=%d too wide (max %d, or %d when E %% 4 != 0)", who, E, kAdagradMaxChunks * 64 * 4, kAdagradMaxChunks * 64);
-    return false;
-  }
-  return true;
-}
-
-static int flush_before_optimiser(tt_ctx* ctx, tt_stream stream) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
   return TT_OK;
 }
 
@@ -2893,7 +2875,8 @@ int tt_rowwise_adagrad_sparse_step(tt_ctx* ctx, float* table, float* sum, int64_
   const AdagradK k = make_adagrad(lr, eps, weight_decay, hparams_dev);
   const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad_rows, 16);
   uint32_t C, LG;
-  if (!adagrad_mapping("tt_rowwise_adagrad_sparse_step", E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
+  row_mapping(E, vec4, &C, &LG);
+  if (!adagrad_fits("tt_rowwise_adagrad_sparse_step", E, C, LG)) return TT_ERR_UNSUPPORTED;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int grid = grid_for(ctx, M * LG);
   if (vec4) adagrad_sparse_kernel<4><<<grid, kThreads, 0, st>>>(table, sum, E, C, unique_rows, grad_rows, n_unique, k, LG, table_rows);
@@ -2910,7 +2893,8 @@ int tt_rowwise_adagrad_dense_step(tt_ctx* ctx, float* table, float* sum, const f
   const AdagradK k = make_adagrad(lr, eps, weight_decay, hparams_dev);
   const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad, 16);
   uint32_t C, LG;
-  if (!adagrad_mapping("tt_rowwise_adagrad_dense_step", E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
+  row_mapping(E, vec4, &C, &LG);
+  if (!adagrad_fits("tt_rowwise_adagrad_dense_step", E, C, LG)) return TT_ERR_UNSUPPORTED;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int grid = grid_for(ctx, table_rows * LG);
   if (vec4) adagrad_dense_kernel<4><<<grid, kThreads, 0, st>>>(table, sum, grad, table_rows, E, C, k, LG);
@@ -2919,58 +2903,24 @@ int tt_rowwise_adagrad_dense_step(tt_ctx* ctx, float* table, float* sum, const f
   return TT_OK;
 }
 
-static int adam_adagrad_fused_impl(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr, float beta1,
-                                   float beta2, float eps, float weight_decay, const float* hparams_dev, float* table, float* sum,
-                                   int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique,
-                                   int64_t M, const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes,
-                                   float table_lr, float table_eps, float table_weight_decay, const float* table_hparams_dev,
-                                   tt_stream stream, const char* who) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
-  TT_CHECK_ARG(ctx && tensors && table && sum && unique_rows && grad_rows && n_unique, "%s: NULL argument", who);
-  TT_CHECK_ARG(n_tensors >= 1 && n_tensors <= kAdamMulti, "%s: n_tensors=%d not in [1,%d]", who, n_tensors, kAdamMulti);
-  TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 1 && table_rows >= 1, "%s: bad step/E/M/table_rows", who);
-  AdamFusedArgs a{};
-  a.n = n_tensors;
-  int nd = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    const tt_adam_tensor& t = tensors[i];
-    TT_CHECK_ARG(t.n >= 0 && (t.n == 0 || (t.p && t.g && t.m && t.v)), "%s: tensor %d has NULL pointers", who, i);
-    a.t[i] = t;
-    a.blk0[i] = nd;
-    int64_t nb = tt_cdiv(t.n > 0 ? t.n : 1, kThreads);
-    nd += (int)(nb > 64 ? 64 : nb);
-  }
-  a.blk0[n_tensors] = nd;
-  const AdamK ak = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
-  const AdagradK gk = make_adagrad(table_lr, table_eps, table_weight_decay, table_hparams_dev);
-  const bool vec4 = (E % 4 == 0) && tt_aligned(table, 16) && tt_aligned(grad_rows, 16);
-  uint32_t C, LG;
-  if (!adagrad_mapping(who, E, vec4, &C, &LG)) return TT_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (grad_workspace) {
-    // the reduction's deferred finish (tt_embed_grad_bwd with TT_GRAD_DEFER_FINISH) rides in this launch
-    TT_CHECK_ARG(seg_offsets, "%s: NULL seg_offsets", who);
-    if (grad_workspace_bytes < tt_embed_grad_workspace_bytes(M, E)) {
-      tt_set_error("%s: gradient workspace %zu < required %zu", who, grad_workspace_bytes, tt_embed_grad_workspace_bytes(M, E));
-      return TT_ERR_WORKSPACE;
-    }
-    if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
-      tt_set_error("%s: E=%d too wide for the long-row finish (max %d)", who, E, kFinishMaxFloats * (int)LG / kThreads);
-      return TT_ERR_UNSUPPORTED;
-    }
-    const GradLayout gl = grad_layout(reinterpret_cast<char*>(grad_workspace), M, E);
-    const int nlb = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);
-    const int grid = nd + nlb + grid_for(ctx, M * LG);
-    if (vec4) adam_adagrad_fused_kernel<4, true><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, seg_offsets, gl.ws, nlb);
-    else adam_adagrad_fused_kernel<1, true><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, seg_offsets, gl.ws, nlb);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-  }
-  const int grid = nd + grid_for(ctx, M * LG);
-  if (vec4) adam_adagrad_fused_kernel<4, false><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, nullptr, GradWs{}, 0);
-  else adam_adagrad_fused_kernel<1, false><<<grid, kThreads, 0, st>>>(a, ak, table, sum, E, C, unique_rows, grad_rows, n_unique, gk, LG, table_rows, nullptr, GradWs{}, 0);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+int tt_adam_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, float* table, float* m, float* v, int64_t table_rows,
+                       int32_t E,
+                       const int32_t* unique_rows, const float* grad_rows, const int32_t* n_unique, int64_t M, int64_t step, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
+  const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
+  return fused_step_impl(ctx, "tt_adam_fused_step", tensors, n_tensors, step, k, AdamRows{m, v, {}}, table, table_rows, E, unique_rows,
+                         const_cast<float*>(grad_rows), n_unique, M, nullptr, nullptr, 0, stream);
+}
+
+int tt_adam_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, float* table, float* m, float* v,
+                              int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows, const int32_t* n_unique,
+                              int64_t M, const int32_t* seg_offsets, void* grad_workspace, size_t grad_workspace_bytes, int64_t step,
+                              float lr, float beta1, float beta2, float eps, float weight_decay, const float* hparams_dev,
+                              tt_stream stream) {
+  TT_CHECK_ARG(grad_workspace, "tt_adam_fused_step_finish: NULL gradient workspace");
+  const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
+  return fused_step_impl(ctx, "tt_adam_fused_step_finish", tensors, n_tensors, step, k, AdamRows{m, v, {}}, table, table_rows, E,
+                         unique_rows, grad_rows, n_unique, M, seg_offsets, grad_workspace, grad_workspace_bytes, stream);
 }
 
 int tt_adam_rowwise_adagrad_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr,
@@ -2978,9 +2928,10 @@ int tt_adam_rowwise_adagrad_fused_step(tt_ctx* ctx, const tt_adam_tensor* tensor
                                        float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows, const float* grad_rows,
                                        const int32_t* n_unique, int64_t M, float table_lr, float table_eps, float table_weight_decay,
                                        const float* table_hparams_dev, tt_stream stream) {
-  return adam_adagrad_fused_impl(ctx, tensors, n_tensors, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, table, sum, table_rows,
-                                 E, unique_rows, const_cast<float*>(grad_rows), n_unique, M, nullptr, nullptr, 0, table_lr, table_eps,
-                                 table_weight_decay, table_hparams_dev, stream, "tt_adam_rowwise_adagrad_fused_step");
+  return fused_step_impl(ctx, "tt_adam_rowwise_adagrad_fused_step", tensors, n_tensors, step,
+                         make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev),
+                         AdagradRows{sum, make_adagrad(table_lr, table_eps, table_weight_decay, table_hparams_dev)}, table, table_rows, E,
+                         unique_rows, const_cast<float*>(grad_rows), n_unique, M, nullptr, nullptr, 0, stream);
 }
 
 int tt_adam_rowwise_adagrad_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr,
@@ -2990,9 +2941,10 @@ int tt_adam_rowwise_adagrad_fused_step_finish(tt_ctx* ctx, const tt_adam_tensor*
                                               void* grad_workspace, size_t grad_workspace_bytes, float table_lr, float table_eps,
                                               float table_weight_decay, const float* table_hparams_dev, tt_stream stream) {
   TT_CHECK_ARG(grad_workspace, "tt_adam_rowwise_adagrad_fused_step_finish: NULL gradient workspace");
-  return adam_adagrad_fused_impl(ctx, tensors, n_tensors, step, lr, beta1, beta2, eps, weight_decay, hparams_dev, table, sum, table_rows,
-                                 E, unique_rows, grad_rows, n_unique, M, seg_offsets, grad_workspace, grad_workspace_bytes, table_lr,
-                                 table_eps, table_weight_decay, table_hparams_dev, stream, "tt_adam_rowwise_adagrad_fused_step_finish");
+  return fused_step_impl(ctx, "tt_adam_rowwise_adagrad_fused_step_finish", tensors, n_tensors, step,
+                         make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev),
+                         AdagradRows{sum, make_adagrad(table_lr, table_eps, table_weight_decay, table_hparams_dev)}, table, table_rows, E,
+                         unique_rows, grad_rows, n_unique, M, seg_offsets, grad_workspace, grad_workspace_bytes, stream);
 }
 
 int tt_embed_grad_finish(tt_ctx* ctx, int32_t E, const int32_t* seg_offsets, int64_t M, float* out, void* workspace,
@@ -3004,10 +2956,10 @@ int tt_embed_grad_finish(tt_ctx* ctx, int32_t E, const int32_t* seg_offsets, int
     return TT_ERR_WORKSPACE;
   }
   const bool vec4 = (E % 4 == 0) && tt_aligned(out, 16);
-  const uint32_t C = vec4 ? E / 4 : E;
-  const uint32_t LG = pow2_at_least(C) > 64 ? 64 : pow2_at_least(C);
+  uint32_t C, LG;
+  row_mapping(E, vec4, &C, &LG);
   const GradLayout gl = grad_layout(reinterpret_cast<char*>(workspace), M, E);
-  const int g3 = (int)(gl.max_long < (int64_t)ctx->num_cus * 8 ? gl.max_long : (int64_t)ctx->num_cus * 8);
+  const int g3 = long_row_blocks(ctx, gl);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // (deferred only from a planned reduction: the counters are the plan's)
   if (vec4) seg_long_finish_kernel<4, false><<<g3, kThreads, 0, st>>>(E, C, seg_offsets, nullptr, TT_GRAD_SPARSE, out, gl.ws, LG);

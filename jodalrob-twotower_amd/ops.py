@@ -297,17 +297,37 @@ def adam_dense(p, g, m, v, step, lr, b1, b2, eps, wd, hp_dev=None):
                                             eps, wd, L.ptr(hp_dev), L.stream(dev)), "tt_adam_dense_step")
 
 
+def _adam_tensors(items):
+    """items: [(p, g, m, v)] float32 contiguous tensors on one device -> the tt_adam_tensor array of the optimiser entries."""
+    arr = (L.AdamTensor * len(items))()
+    for i, (p, g, m, v) in enumerate(items):
+        arr[i] = L.AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+    return arr
+
+
+def _fused_step(who, entry, head, plan: "DedupPlan", grad_rows, tail):
+    """One fused optimiser call `entry`(*head, *tail) -- or, when the plan's long-row finish is deferred, `entry`_finish with the
+    plan's (seg_offsets, workspace, workspace_bytes) between head and tail, which completes grad_rows on the way."""
+    fin = ()
+    if plan.finish_deferred is not None:
+        if plan.finish_deferred.data_ptr() != grad_rows.data_ptr():
+            raise RuntimeError(f"{who}: the plan's deferred gradient is not the one handed to the optimiser")
+        ws = plan.grad_ws[0]
+        fin = (L.ptr(plan.seg_offsets), L.ptr(ws), ws.numel())
+    name = entry + "_finish" if fin else entry
+    with _timed(entry):
+        L.check(getattr(L.load(), name)(*head, *fin, *tail), name)
+    plan.finish_deferred = None
+
+
 def adam_multi(items, step, lr, b1, b2, eps, wd, hp_dev=None):
     """items: [(p, g, m, v)] float32 contiguous tensors on one device."""
     if not items:
         return
     dev = items[0][0].device
-    arr = (L.AdamTensor * len(items))()
-    for i, (p, g, m, v) in enumerate(items):
-        arr[i] = L.AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
     with _timed("tt_adam_multi_step"):
-        L.check(L.load().tt_adam_multi_step(L.ctx(dev), arr, len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.stream(dev)),
-                "tt_adam_multi_step")
+        L.check(L.load().tt_adam_multi_step(L.ctx(dev), _adam_tensors(items), len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev),
+                                            L.stream(dev)), "tt_adam_multi_step")
 
 
 def adam_sparse(table, m, v, plan: DedupPlan, grad_rows, step, lr, b1, b2, eps, wd, hp_dev=None):
@@ -322,24 +342,10 @@ def adam_sparse(table, m, v, plan: DedupPlan, grad_rows, step, lr, b1, b2, eps, 
 def adam_fused(items, table, m, v, plan: DedupPlan, grad_rows, step, lr, b1, b2, eps, wd, hp_dev=None):
     """adam_multi(items) + adam_sparse(table rows) with one set of hyper-parameters, one launch."""
     dev = table.device
-    arr = (L.AdamTensor * len(items))()
-    for i, (p, g, mm, vv) in enumerate(items):
-        arr[i] = L.AdamTensor(p.data_ptr(), g.data_ptr(), mm.data_ptr(), vv.data_ptr(), p.numel())
-    if plan.finish_deferred is not None:
-        if plan.finish_deferred.data_ptr() != grad_rows.data_ptr():
-            raise RuntimeError("adam_fused: the plan's deferred gradient is not the one handed to the optimiser")
-        ws, E = plan.grad_ws
-        with _timed("tt_adam_fused_step"):
-            L.check(L.load().tt_adam_fused_step_finish(L.ctx(dev), arr, len(items), L.ptr(table), L.ptr(m), L.ptr(v), table.shape[0],
-                                                       table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique),
-                                                       plan.M, L.ptr(plan.seg_offsets), L.ptr(ws), ws.numel(), step, lr, b1, b2, eps, wd,
-                                                       L.ptr(hp_dev), L.stream(dev)), "tt_adam_fused_step_finish")
-        plan.finish_deferred = None
-        return
-    with _timed("tt_adam_fused_step"):
-        L.check(L.load().tt_adam_fused_step(L.ctx(dev), arr, len(items), L.ptr(table), L.ptr(m), L.ptr(v), table.shape[0], table.shape[1],
-                                            L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M, step,
-                                            lr, b1, b2, eps, wd, L.ptr(hp_dev), L.stream(dev)), "tt_adam_fused_step")
+    head = (L.ctx(dev), _adam_tensors(items), len(items), L.ptr(table), L.ptr(m), L.ptr(v), table.shape[0], table.shape[1],
+            L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M)
+    tail = (step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.stream(dev))
+    _fused_step("adam_fused", "tt_adam_fused_step", head, plan, grad_rows, tail)
 
 
 # ---------------------------------------------------------------------------------------------- row-wise Adagrad (tables)
@@ -366,25 +372,10 @@ def adam_rowwise_adagrad_fused(items, step, lr, b1, b2, eps, wd, hp_dev, table, 
                                t_hp_dev=None):
     """adam_multi(items) with the towers' hyper-parameters + rowwise_adagrad_sparse(table rows) with the table's, one launch."""
     dev = table.device
-    arr = (L.AdamTensor * len(items))()
-    for i, (p, g, mm, vv) in enumerate(items):
-        arr[i] = L.AdamTensor(p.data_ptr(), g.data_ptr(), mm.data_ptr(), vv.data_ptr(), p.numel())
-    if plan.finish_deferred is not None:
-        if plan.finish_deferred.data_ptr() != grad_rows.data_ptr():
-            raise RuntimeError("adam_rowwise_adagrad_fused: the plan's deferred gradient is not the one handed to the optimiser")
-        ws, E = plan.grad_ws
-        with _timed("tt_adam_rowwise_adagrad_fused_step"):
-            L.check(L.load().tt_adam_rowwise_adagrad_fused_step_finish(
-                L.ctx(dev), arr, len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.ptr(table), L.ptr(acc), table.shape[0],
-                table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M, L.ptr(plan.seg_offsets),
-                L.ptr(ws), ws.numel(), t_lr, t_eps, t_wd, L.ptr(t_hp_dev), L.stream(dev)), "tt_adam_rowwise_adagrad_fused_step_finish")
-        plan.finish_deferred = None
-        return
-    with _timed("tt_adam_rowwise_adagrad_fused_step"):
-        L.check(L.load().tt_adam_rowwise_adagrad_fused_step(
-            L.ctx(dev), arr, len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.ptr(table), L.ptr(acc), table.shape[0],
-            table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M, t_lr, t_eps, t_wd,
-            L.ptr(t_hp_dev), L.stream(dev)), "tt_adam_rowwise_adagrad_fused_step")
+    head = (L.ctx(dev), _adam_tensors(items), len(items), step, lr, b1, b2, eps, wd, L.ptr(hp_dev), L.ptr(table), L.ptr(acc),
+            table.shape[0], table.shape[1], L.ptr(plan.unique_rows), L.ptr(grad_rows), L.ptr(plan.n_unique), plan.M)
+    tail = (t_lr, t_eps, t_wd, L.ptr(t_hp_dev), L.stream(dev))
+    _fused_step("adam_rowwise_adagrad_fused", "tt_adam_rowwise_adagrad_fused_step", head, plan, grad_rows, tail)
 
 
 # ---------------------------------------------------------------------------------------------- tower MLP

@@ -175,29 +175,22 @@ class FusedAdam(torch.optim.Optimizer):
                 by_step.setdefault(it[4], []).append(it[:4])
             for s_no, its in by_step.items():
                 fuse = self._fusable_store(group, s_no, len(its), len(by_step))
-                if fuse is not None and len(fuse) == 3:   # tower Adam + the row-wise Adagrad of another group's table: one launch
-                    store, st, tgroup = fuse
-                    plan, grad_rows = store.sparse_grad
-                    st["step"] += 1
+                if fuse is None:
+                    ops.adam_multi(its, s_no, group["lr"], b1, b2, group["eps"], group["weight_decay"], hp)
+                    continue
+                store, st, tgroup = fuse          # tower weights + the looked-up rows of that store: one launch
+                plan, grad_rows = store.sparse_grad
+                st["step"] += 1
+                if _kind(tgroup) == "rowwise_adagrad":   # (another group's table, its own hyper-parameters)
                     thp = None if self._hp_dev is None else self._hp_dev[self.param_groups.index(tgroup)]
                     ops.adam_rowwise_adagrad_fused(its, s_no, group["lr"], b1, b2, group["eps"], group["weight_decay"], hp,
                                                    store.weight, st["sum"], plan, grad_rows, tgroup["lr"], tgroup["eps"],
                                                    tgroup["weight_decay"], thp)
-                    store.sparse_grad = None
-                    for p in store.optim_parameters():
-                        self.state[p]["step"] = torch.tensor(float(st["step"]))
-                    continue
-                if fuse is not None:      # tower weights + looked-up table rows: one launch
-                    store, st = fuse
-                    plan, grad_rows = store.sparse_grad
-                    st["step"] += 1
+                else:
                     ops.adam_fused(its, store.weight, st["m"], st["v"], plan, grad_rows, s_no, group["lr"], b1, b2,
                                    group["eps"], group["weight_decay"], hp)
-                    store.sparse_grad = None
-                    for p in store.optim_parameters():
-                        self.state[p]["step"] = torch.tensor(float(st["step"]))
-                    continue
-                ops.adam_multi(its, s_no, group["lr"], b1, b2, group["eps"], group["weight_decay"], hp)
+                store.sparse_grad = None
+                self._write_step(store, st)
         # ---- embedding stores ----
         for store in self._stores:
             members = store.optim_parameters()
@@ -209,67 +202,51 @@ class FusedAdam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             hp = None if self._hp_dev is None else self._hp_dev[self.param_groups.index(group)]
             st = self._state_of(store)
-            if _kind(group) == "rowwise_adagrad":
-                if store.grad_mode == "sparse":
-                    if store.sparse_grad is None:
-                        continue
-                    plan, grad_rows = store.sparse_grad
-                    st["step"] += 1
-                    ops.rowwise_adagrad_sparse(store.weight, st["sum"], plan, grad_rows, group["lr"], group["eps"],
-                                               group["weight_decay"], hp)
-                    store.sparse_grad = None
-                else:
-                    if store.grad is None or any(p.grad is None for p in members):
-                        continue
-                    st["step"] += 1
-                    ops.rowwise_adagrad_dense(store.weight, st["sum"], store.grad, group["lr"], group["eps"], group["weight_decay"], hp)
-                for p in members:
-                    self.state[p]["step"] = torch.tensor(float(st["step"]))
-                continue
-            if store.grad_mode == "sparse":
-                if store.sparse_grad is None:
-                    continue
-                plan, grad_rows = store.sparse_grad
-                st["step"] += 1
-                ops.adam_sparse(store.weight, st["m"], st["v"], plan, grad_rows, st["step"], group["lr"], b1, b2,
-                                group["eps"], group["weight_decay"], hp)
-                store.sparse_grad = None
+            sparse, rowwise = store.grad_mode == "sparse", _kind(group) == "rowwise_adagrad"
+            if sparse:
+                pending = store.sparse_grad is not None      # (None also once a fused launch above has applied it)
             else:
-                if store.grad is None or any(p.grad is None for p in members):
-                    continue
-                st["step"] += 1
-                ops.adam_dense(store.weight, store.grad, st["m"], st["v"], st["step"], group["lr"], b1, b2,
-                               group["eps"], group["weight_decay"], hp)
-            for p in members:
-                self.state[p]["step"] = torch.tensor(float(st["step"]))
+                pending = store.grad is not None and all(p.grad is not None for p in members)
+            if not pending:
+                continue
+            st["step"] += 1
+            lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
+            if sparse:
+                plan, grad_rows = store.sparse_grad
+                if rowwise:
+                    ops.rowwise_adagrad_sparse(store.weight, st["sum"], plan, grad_rows, lr, eps, wd, hp)
+                else:
+                    ops.adam_sparse(store.weight, st["m"], st["v"], plan, grad_rows, st["step"], lr, b1, b2, eps, wd, hp)
+                store.sparse_grad = None
+            elif rowwise:
+                ops.rowwise_adagrad_dense(store.weight, st["sum"], store.grad, lr, eps, wd, hp)
+            else:
+                ops.adam_dense(store.weight, store.grad, st["m"], st["v"], st["step"], lr, b1, b2, eps, wd, hp)
+            self._write_step(store, st)
         return loss
 
+    def _write_step(self, store, st):
+        for p in store.optim_parameters():
+            self.state[p]["step"] = torch.tensor(float(st["step"]))
+
     def _fusable_store(self, group, s_no: int, n_items: int, n_buckets: int):
-        """The one sparse-gradient store of `group` whose next step number is s_no -> (store, state); when `group` has no
-        store, the one row-wise Adagrad store of another group with a pending sparse gradient -> (store, state, its group);
-        else None."""
-        if n_buckets != 1 or not (1 <= n_items <= 32):
+        """(store, state, the store's group) of the one store whose pending sparse gradient can ride in the launch that steps
+        `group`'s tower tensors to s_no: `group`'s own Adam store when its next step is s_no, or, when `group` has no store, the
+        one row-wise Adagrad store of another group; else None."""
+        if n_buckets != 1 or not (1 <= n_items <= 32) or _kind(group) != "adam":
             return None
-        cands = []
-        for store in self._stores:
-            members = store.optim_parameters()
-            if members and any(members[0] is p for p in group["params"]):
-                cands.append(store)
-        if not cands and _kind(group) == "adam":
-            rw = [(s, g) for s in self._stores for g in [self._group_of_store(s)] if g is not None and _kind(g) == "rowwise_adagrad"]
-            if len(rw) != 1:
-                return None
-            store, tgroup = rw[0]
-            if store.grad_mode != "sparse" or store.sparse_grad is None or store.sparse_grad[0].M < 1:
-                return None
-            return store, self._state_of(store), tgroup
-        if len(cands) != 1 or _kind(group) != "adam":
+        own = [s for s in self._stores if self._group_of_store(s) is group]
+        if own:
+            cands = [(s, group) for s in own]
+        else:
+            cands = [(s, g) for s in self._stores for g in [self._group_of_store(s)] if g is not None and _kind(g) == "rowwise_adagrad"]
+        if len(cands) != 1:
             return None
-        store = cands[0]
+        store, tgroup = cands[0]
         if store.grad_mode != "sparse" or store.sparse_grad is None or store.sparse_grad[0].M < 1:
             return None
         st = self._state_of(store)
-        return (store, st) if st["step"] + 1 == s_no else None
+        return (store, st, tgroup) if tgroup is not group or st["step"] + 1 == s_no else None
 
     def advance_steps(self, n: int):
         """Account for `n` optimiser steps executed by graph replays (step counters live on the host;

@@ -10,7 +10,7 @@ runs bench.run and prints torch.cuda.max_memory_allocated() after it, and torch.
 
 --rows: 1m = configs[1] (1 M + 1 M rows); 100m = one GPU with --rows-notice 100000000 --rows-company 10000000.
 --profile: one run per (rows, optimiser) under `rocprofv3 --kernel-trace --stats`, reporting the optimiser launch's
-average time (adam_fused_kernel / adam_adagrad_fused_kernel) instead of the step time.
+average time (fused_step_kernel<AdamRows, ...> / fused_step_kernel<AdagradRows, ...>) instead of the step time.
 Prints one JSON line: per rows setting and optimiser the ms/step and pairs/s of every round, their medians, the peak memory."""
 import argparse
 import csv
@@ -25,7 +25,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 ROWS = {"1m": [], "100m": ["--rows-notice", "100000000", "--rows-company", "10000000"]}
 OPTS = ("adam", "rowwise_adagrad")
-LAUNCH = {"adam": r"adam_fused_kernel<", "rowwise_adagrad": r"adam_adagrad_fused_kernel<"}
+LAUNCH = {"adam": r"fused_step_kernel<[^>]*AdamRows,", "rowwise_adagrad": r"fused_step_kernel<[^>]*AdagradRows,"}
 
 
 def child(opt, rows, steps, warmup):
