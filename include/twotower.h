@@ -72,7 +72,11 @@ uint64_t tt_launch_count(void);
  * grid row of their fused tail kernels (two launches fewer in the step's dependent chain; same bodies: bit-identical), and
  * tt_flush_deferred, tt_embed_grad_bwd, tt_embed_grad_finish and the tt_adam_* entries launch whatever is still queued.  Until
  * then the plan's unique_rows / seg_offsets / n_unique and the forward's loss_out / out8 are NOT written: for callers that run
- * the whole step back to back (GraphedTrainStep); tt_deferred_pending() covers the queue. */
+ * the whole step back to back (GraphedTrainStep); tt_deferred_pending() covers the queue.  With the compaction queued, the plan's
+ * SORT waits in the queue too: tt_towers_mlp_fwd issues it behind its front kernel and in front of the fused tail, with one
+ * workgroup per tower in its grid that finishes the BatchNorm batch statistics once (the tail's workgroups then read the finished
+ * mean / rstd instead of merging the chunk partials each; same merge order: bit-identical); towers without the fused narrow tail leave
+ * it to the same flush as the compaction.  `rows` must stay valid and unchanged until then. */
 #define TT_OPT_DEFER_RIDERS 4
 /* TT_OPT_FP8_GRAD (default 1): tt_score_bwd_fp8 forms the gradient products dA = W B from e4m3 operands as well (softmax weights
  * block-scaled per row and 32 consecutive b rows, the diagonal weight kept apart in f32: tt_score_bwd_fp8 below); 0 = bf16 weights and bf16

@@ -29,7 +29,10 @@ uint32_t* tt_chain_for(tt_ctx* ctx, hipStream_t stream) {
 }
 
 int tt_riders_flush(tt_ctx* ctx, hipStream_t st) {
-  if (!ctx || !ctx->riders || (ctx->riders->c_wg == 0 && ctx->riders->f_wg == 0)) return TT_OK;
+  if (!ctx || !ctx->riders) return TT_OK;
+  if (ctx->riders->s_on)                                 // a sort nobody hosted: in front of its compaction, no statistics riders
+    if (int rc = tt_keyed_sort_launch(ctx, st, nullptr, 0)) return rc;
+  if (ctx->riders->c_wg == 0 && ctx->riders->f_wg == 0) return TT_OK;
   riders_kernel<<<ctx->riders->c_wg + ctx->riders->f_wg, kRiderThreads, 0, st>>>(*ctx->riders);
   ctx->riders->c_wg = ctx->riders->f_wg = 0;
   TT_LAUNCH_CHECK();
@@ -74,7 +77,8 @@ int tt_ctx_create(int device, tt_ctx** out) {
   c->defer_riders = 0;
   c->fp8_grad = 1;
   c->riders = new tt_riders();
-  c->riders->c_wg = c->riders->f_wg = 0;
+  c->riders->c_wg = c->riders->f_wg = c->riders->s_on = 0;
+  c->bn_fin = nullptr;
   c->chain = nullptr;
   c->chain_words = 0;
   c->chain_used = 0;
@@ -90,9 +94,11 @@ int tt_ctx_create(int device, tt_ctx** out) {
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->chain), sizeof(uint32_t) * (kChainWords * kChainSlices + 64));
     if (e == hipSuccess) e = hipMemset(c->chain, 0, sizeof(uint32_t) * (kChainWords * kChainSlices + 64));
     if (e == hipSuccess) c->dev_err = c->chain + (size_t)kChainWords * kChainSlices;       // (its own 256-byte line behind the pool)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->bn_fin), sizeof(float) * TT_MAX_SIDES * kBnFinStride);
     (void)hipSetDevice(prev);
     if (e != hipSuccess) {
       tt_set_error("tt_ctx_create: %s", hipGetErrorString(e));
+      if (c->chain) (void)hipFree(c->chain);
       delete c->riders;
       delete c;
       return TT_ERR_HIP;
@@ -107,6 +113,7 @@ int tt_ctx_destroy(tt_ctx* ctx) {
   if (ctx && ctx->deferred) tt_gemm_tn_pending_destroy(ctx->deferred);
   if (ctx) delete ctx->riders;
   if (ctx && ctx->chain) (void)hipFree(ctx->chain);
+  if (ctx && ctx->bn_fin) (void)hipFree(ctx->bn_fin);
   delete ctx;
   return TT_OK;
 }
@@ -189,7 +196,7 @@ int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream stream) {
 
 int tt_deferred_pending(const tt_ctx* ctx) {
   if (!ctx) return 0;
-  return ((ctx->deferred && ctx->deferred->n > 0) ? 1 : 0) | ((ctx->riders && (ctx->riders->c_wg > 0 || ctx->riders->f_wg > 0)) ? 2 : 0);
+  return ((ctx->deferred && ctx->deferred->n > 0) ? 1 : 0) | ((ctx->riders && (ctx->riders->c_wg > 0 || ctx->riders->f_wg > 0 || ctx->riders->s_on)) ? 2 : 0);
 }
 
 int tt_ctx_num_cus(const tt_ctx* ctx) { return ctx ? ctx->num_cus : 0; }

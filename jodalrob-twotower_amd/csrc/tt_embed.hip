@@ -572,34 +572,36 @@ __global__ __launch_bounds__(kThreads) void head_chained_kernel(const uint32_t* 
 constexpr int kKeyedB = 8192;          // max ids per key (LDS: 2 x 32 KB keys + 2 x 16 KB values + 16 KB histograms + 32 KB lane sets)
 constexpr int kKeyedThreads = 1024;
 
-struct KeyedArgs {
-  int32_t side_base[TT_MAX_SIDES + 1];   // first slot of side i
-  int32_t key_base[TT_MAX_SIDES + 1];    // first key instance of side i
-  int32_t K[TT_MAX_SIDES];
-  int32_t n_sides;
-  int32_t B;
-  int32_t parts;                         // workgroups per key (range partition of the key's rows)
-};
+static_assert(kKeyedThreads == kRiderThreads, "the statistics riders run in the sort's workgroups");
 constexpr int kKeyedMaxParts = 8;
-// (PlanLong, the long-row list the compaction builds for the gradient reduction: tt_riders.h)
+// (KeyedArgs; PlanLong, the long-row list the compaction builds for the gradient reduction: tt_riders.h)
+// (bf_wg > 0: the FIRST bf_wg workgroups -- dispatched first, so they start at once even when the sort fills every CU -- finish the
+// towers' BatchNorm statistics, one tower each, and return: tt_riders.h.  They use the head of `keys` for their 12 KB of triples.  The
+// sort's workgroups follow; bf_wg == 0 is the kernel as it was.)
 
 __global__ __launch_bounds__(kKeyedThreads) void keyed_sort_kernel(KeyedArgs a, const int32_t* __restrict__ rows,
                                                                   int32_t* __restrict__ sorted_src, int32_t* __restrict__ uniq_stage,
                                                                   int32_t* __restrict__ seg_stage, int32_t* __restrict__ ucount,
                                                                   int32_t* __restrict__ ubase, int32_t* __restrict__ uend, bool key_major,
-                                                                  int32_t* __restrict__ long_counters) {
+                                                                  int32_t* __restrict__ long_counters, BnFinishRiders bf, int bf_wg) {
   __shared__ uint32_t keys[2][kKeyedB];
   __shared__ uint16_t vals[2][kKeyedB];
   __shared__ uint32_t whist[16][256];
   __shared__ unsigned long long peers_mask[16][256];   // lane sets per (wave, digit); all zero between batches
   __shared__ uint32_t red[32];
+  static_assert(sizeof(Wf) * 16 * 64 <= sizeof(keys), "the statistics rider's triples live in keys");
+  if ((int)blockIdx.x < bf_wg) {
+    bn_finish_body(bf.r[blockIdx.x], reinterpret_cast<Wf(*)[64]>(&keys[0][0]));
+    return;
+  }
+  const int wg = (int)blockIdx.x - bf_wg;                // the sort's own workgroup index
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // `parts` workgroups per key: every one loads the key's B rows and builds the same bucket histogram, then scatters, ranks and
   // writes only the buckets of ITS share of the key's row range (whole rows: a row never straddles two shares) -- the sorted
   // positions follow from the common prefix, so there is nothing to merge.  Every workgroup of a key reaches the same decision
   // about the LSD fallback (same histogram); share 0 then sorts the whole key alone.
-  const int P = a.parts, ki = (int)blockIdx.x / P, part = (int)blockIdx.x % P, B = a.B;
-  if (long_counters && blockIdx.x == 0 && tid < 2) long_counters[tid] = 0;      // the compaction (next launch) counts from zero
+  const int P = a.parts, ki = wg / P, part = wg % P, B = a.B;
+  if (long_counters && wg == 0 && tid < 2) long_counters[tid] = 0;      // the compaction (next launch) counts from zero
   for (int d = tid; d < 16 * 256; d += kKeyedThreads) (&peers_mask[0][0])[d] = 0ull;
   int side = 0;
 #pragma unroll
@@ -796,7 +798,7 @@ __global__ __launch_bounds__(kKeyedThreads) void keyed_sort_kernel(KeyedArgs a, 
     e_lo = 0;
     e_hi = part == 0 ? B : 0;
     if (part != 0) {
-      if (tid == 0) { ucount[blockIdx.x] = 0; ubase[blockIdx.x] = ki * B; uend[blockIdx.x] = ki * B; }
+      if (tid == 0) { ucount[wg] = 0; ubase[wg] = ki * B; uend[wg] = ki * B; }
       return;
     }
   }
@@ -914,9 +916,9 @@ __global__ __launch_bounds__(kKeyedThreads) void keyed_sort_kernel(KeyedArgs a, 
     }
   }
   if (tid == kKeyedThreads - 1) {
-    ucount[blockIdx.x] = (int32_t)u;
-    ubase[blockIdx.x] = (int32_t)(gbase + e_lo);
-    uend[blockIdx.x] = (int32_t)(gbase + e_hi);           // where the share's last segment ends
+    ucount[wg] = (int32_t)u;
+    ubase[wg] = (int32_t)(gbase + e_lo);
+    uend[wg] = (int32_t)(gbase + e_hi);           // where the share's last segment ends
   }
 }
 
@@ -2407,6 +2409,17 @@ int fused_step_impl(tt_ctx* ctx, const char* who, const tt_adam_tensor* tensors,
 
 }  // namespace
 
+int tt_keyed_sort_launch(tt_ctx* ctx, hipStream_t st, const BnFinishRiders* bf, int bf_wg) {
+  if (!ctx || !ctx->riders || !ctx->riders->s_on) return TT_OK;
+  const KeyedSortQueued& q = ctx->riders->s;
+  if (!bf || bf_wg < 0 || bf_wg > TT_MAX_SIDES) bf_wg = 0;
+  keyed_sort_kernel<<<bf_wg + q.grid, kKeyedThreads, 0, st>>>(q.a, q.rows, q.sorted_src, q.uniq_stage, q.seg_stage, q.ucount, q.ubase, q.uend,
+                                                              q.key_major, q.long_counters, bf_wg > 0 ? *bf : BnFinishRiders{}, bf_wg);
+  ctx->riders->s_on = 0;
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 extern "C" {
 
 #ifdef TT_SEG_STAMPS
@@ -2636,17 +2649,22 @@ static int dedup_plan_keyed_impl(tt_ctx* ctx, const int32_t* rows, const int32_t
   if (parts > kKeyedMaxParts) parts = kKeyedMaxParts;
   while (parts > 1 && (int64_t)n_keys * parts > (int64_t)ctx->num_cus) --parts;        // a workgroup needs a CU of its own (144 KB of LDS)
   a.parts = parts;
-  keyed_sort_kernel<<<n_keys * parts, kKeyedThreads, 0, st>>>(a, rows, sorted_src, uniq_stage, seg_stage, ucount, ubase, uend, key_major,
-                                                              pl.counters);
-  TT_LAUNCH_CHECK();
+  const KeyedSortQueued sq{a, rows, sorted_src, uniq_stage, seg_stage, ucount, ubase, uend, key_major, pl.counters, n_keys * parts};
   const CompactRider cr{uniq_stage, seg_stage, ucount, ubase, uend, pl, n_keys * parts, slots, unique_rows, seg_offsets, n_unique};
   if (ctx->defer_riders & 1) {                           // rides beside the towers' tail_fwd (tt_riders.h); a second plan before that
     if (ctx->riders->c_wg > 0)                           // launch takes the queue's place, the older one is launched now
       if (int rc = tt_riders_flush(ctx, st)) return rc;
+    // ... and the sort itself waits for the towers' forward, which issues it behind its front kernel with the BatchNorm statistics
+    // riders in its grid (nothing reads the plan before the compaction does)
+    ctx->riders->s = sq;
+    ctx->riders->s_on = 1;
     ctx->riders->c = cr;
     ctx->riders->c_wg = n_keys * parts;
     return TT_OK;
   }
+  keyed_sort_kernel<<<sq.grid, kKeyedThreads, 0, st>>>(a, rows, sorted_src, uniq_stage, seg_stage, ucount, ubase, uend, key_major,
+                                                       pl.counters, BnFinishRiders{}, 0);
+  TT_LAUNCH_CHECK();
   keyed_compact_kernel<<<n_keys * parts, kKeyedThreads, 0, st>>>(cr);
   TT_LAUNCH_CHECK();
   return TT_OK;

@@ -26,12 +26,136 @@ struct CompactRider {
 struct Finish2Rider {
   const float* part; int n_wg, Dp; float fb, unscale; float* out; float* loss_out;
 };
+// The towers' BatchNorm batch statistics, finished ONCE per tower instead of by every tail workgroup: the chunk partials that
+// tower_front / tail_head leave behind are merged by one workgroup per tower riding in front of the keyed plan's sort (its grid
+// leaves CUs idle and it depends on nothing the towers produce), and the kernel boundary behind the sort hands (mean, rstd) to
+// every workgroup of tail_fwd.  What the in-tail finish does once per tower -- the saved statistics of the backward, the running
+// estimates, num_batches_tracked -- happens here instead, never in both places.
+struct BnFinishRider {
+  const float* partial; int64_t pstride; int nchunks, H;          // as BnStatArgs (pstride: floats between chunks, never 0 here)
+  float* mean; float* rstd; float* rm; float* rv; int64_t* nbt;
+  float* out;                                                     // [2][H]: mean, rstd (context-owned: tt_ctx::bn_fin)
+};
+struct BnFinishRiders { BnFinishRider r[TT_MAX_SIDES]; };
+constexpr int kBnFinStride = 2 * 64;                              // floats per tower in tt_ctx::bn_fin (the narrow tail: H <= 64)
+
+// the keyed plan's sort (keyed_sort_kernel, tt_embed.hip): argument block, and the launch itself while it is held back
+struct KeyedArgs {
+  int32_t side_base[TT_MAX_SIDES + 1];   // first slot of side i
+  int32_t key_base[TT_MAX_SIDES + 1];    // first key instance of side i
+  int32_t K[TT_MAX_SIDES];
+  int32_t n_sides;
+  int32_t B;
+  int32_t parts;                         // workgroups per key (range partition of the key's rows)
+};
+struct KeyedSortQueued {
+  KeyedArgs a; const int32_t* rows; int32_t* sorted_src; int32_t* uniq_stage; int32_t* seg_stage; int32_t* ucount; int32_t* ubase;
+  int32_t* uend; bool key_major; int32_t* long_counters; int grid;
+};
 struct tt_riders {
   CompactRider c; int c_wg;        // c_wg > 0: queued, needs that many workgroups
   Finish2Rider f; int f_wg;
+  // s_on: the sort whose compaction is queued in `c` has not been launched either -- tt_towers_mlp_fwd issues it BEHIND its front
+  // kernel with the statistics riders in its grid (tt_riders_flush launches it, without riders, in front of the compaction)
+  KeyedSortQueued s; int s_on;
 };
 
 #ifdef __HIPCC__
+// ---- column statistics of relu(pre): Welford per thread, Chan combine ------------------------
+constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;
+constexpr int kMaxChunks = 128;  // row chunks of the two-stage column reductions
+struct Wf {
+  float n, mean, m2;
+};
+__device__ __forceinline__ Wf wf_combine(Wf a, Wf b) {
+  if (b.n == 0.f) return a;
+  if (a.n == 0.f) return b;
+  Wf o;
+  o.n = a.n + b.n;
+  const float d = b.mean - a.mean, w = b.n / o.n;      // one division per combine (the chains of 32 are latency-bound)
+  o.mean = a.mean + d * w;
+  o.m2 = a.m2 + b.m2 + d * d * (a.n * w);
+  return o;
+}
+
+// Canonical merge order of the chunk statistics (round 4; every finish -- bn_stats_finish_kernel, the fused tails, the SyncBN hand-over,
+// the statistics rider -- uses it, so their results stay bit-identical to each other).  Chunk lane jl owns chunks jl, jl + 4, jl + 8, ...
+// in four SUB-CHAINS of kMaxChunks / 16 chunks each:   lane(jl) = ((C0 + C1) + C2) + C3,  C_s = ((v[8 s] + v[8 s + 1]) + ...) + v[8 s + 7];
+// the four lanes then merge as (lane0 + lane1) + (lane2 + lane3).  Sub-chains exist so that a 1024-thread workgroup can give each one to
+// its own thread (16 per column: 8 triples in flight per thread instead of 32 -- 52 registers, two workgroups per CU) without changing
+// the association; before, a lane was one chain of 32.
+constexpr int kSubChain = kMaxChunks / 16;
+__device__ __forceinline__ Wf wf_lane_merge(const Wf* v /* [kMaxChunks / 4] */) {
+  Wf o{0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    Wf cs{0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < kSubChain; ++i) cs = wf_combine(cs, v[kSubChain * s + i]);
+    o = wf_combine(o, cs);
+  }
+  return o;
+}
+
+// The finish as a 1024-thread workgroup runs it (the fused forward tail, or the statistics rider: ONE order, two hosts), in two steps
+// around a barrier.  Step 1, thread (c, rq) = (t & 63, t >> 6): sub-chain rq >> 2 of chunk lane rq & 3 of column c -> sh[rq][c].
+__device__ __forceinline__ Wf bn_finish_subchain(const float* __restrict__ partial, int64_t ps, int nchunks, int H, int c, int rq) {
+  Wf cs{0.f, 0.f, 0.f};
+  if (c < H) {
+    const int jl = rq & 3, sc = rq >> 2;
+    Wf v[kSubChain];
+#pragma unroll
+    for (int i = 0; i < kSubChain; ++i) {
+      const int k = jl + 4 * (kSubChain * sc + i);
+      const float* q = partial + (int64_t)min(k, nchunks - 1) * ps;      // (clamped address, no branch around the loads)
+      const float x0 = q[c], x1 = q[H + c], x2 = q[2 * H + c];
+      v[i] = k < nchunks ? Wf{x0, x1, x2} : Wf{0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < kSubChain; ++i) cs = wf_combine(cs, v[i]);
+  }
+  return cs;
+}
+// Step 2, one thread per column c < H: the sub-chains of every lane, the four lanes, variance and rstd.  `once`: this thread also
+// does what happens once per tower and pass (saved statistics, running estimates as nn.BatchNorm1d -- momentum 0.1, unbiased
+// variance --, num_batches_tracked).
+__device__ __forceinline__ void bn_finish_column(const Wf (*sh)[64], int c, bool once, float* mean_out, float* rstd_out, float* rm,
+                                                 float* rv, int64_t* nbt, float& mean, float& rstd) {
+  Wf ln[4];
+#pragma unroll
+  for (int jl = 0; jl < 4; ++jl) {                       // lane(jl) = ((C0 + C1) + C2) + C3, starting from the empty statistic
+    Wf o{0.f, 0.f, 0.f};
+#pragma unroll
+    for (int sc = 0; sc < 4; ++sc) o = wf_combine(o, sh[4 * sc + jl][c]);
+    ln[jl] = o;
+  }
+  const Wf o = wf_combine(wf_combine(ln[0], ln[1]), wf_combine(ln[2], ln[3]));
+  const float var = o.n > 0.f ? o.m2 / o.n : 0.f;
+  mean = o.mean;
+  rstd = 1.f / sqrtf(var + kBnEps);
+  if (once) {
+    mean_out[c] = o.mean;
+    rstd_out[c] = rstd;
+    if (rm) {
+      rm[c] = (1.f - kBnMomentum) * rm[c] + kBnMomentum * o.mean;
+      rv[c] = (1.f - kBnMomentum) * rv[c] + kBnMomentum * (o.n > 1.f ? o.m2 / (o.n - 1.f) : var);
+    }
+    if (nbt && c == 0) nbt[0] += 1;
+  }
+}
+// the statistics rider's workgroup (kRiderThreads threads); sh: 16 x 64 triples of the host kernel's LDS
+__device__ __forceinline__ void bn_finish_body(const BnFinishRider& r, Wf (*sh)[64]) {
+  const int t = threadIdx.x, c = t & 63, rq = t >> 6;
+  sh[rq][c] = bn_finish_subchain(r.partial, r.pstride, r.nchunks, r.H, c, rq);
+  __syncthreads();
+  if (t < 64 && c < r.H) {
+    float mean, rstd;
+    bn_finish_column(sh, c, true, r.mean, r.rstd, r.rm, r.rv, r.nbt, mean, rstd);
+    r.out[c] = mean;
+    r.out[r.H + c] = rstd;
+  }
+}
+
 // workgroup ki of the keyed plan's compaction (kRiderThreads threads)
 __device__ __forceinline__ void compact_body(const CompactRider& cr, int ki) {
   const int32_t* __restrict__ uniq_stage = cr.uniq_stage;
@@ -153,3 +277,5 @@ __device__ __forceinline__ void finish2_body(const Finish2Rider& fr) {
 
 // launches whatever the context still holds (stand-alone kernels); defined in tt_ctx.hip
 int tt_riders_flush(tt_ctx* ctx, hipStream_t st);
+// launches the held-back sort (riders->s_on) with bf_wg statistics riders in front of its grid; defined in tt_embed.hip
+int tt_keyed_sort_launch(tt_ctx* ctx, hipStream_t st, const BnFinishRiders* bf, int bf_wg);

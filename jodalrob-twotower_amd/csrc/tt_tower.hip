@@ -7,48 +7,15 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f, kNormEps = 1e-12f;
-constexpr int kMaxChunks = 128;  // row chunks of the two-stage column reductions
+constexpr float kNormEps = 1e-12f;
+// (column statistics of relu(pre) -- Wf, wf_combine, the canonical merge order wf_lane_merge, kMaxChunks -- live in tt_riders.h:
+// the statistics rider in the keyed sort's launch shares them)
 
 __device__ __forceinline__ float dropout_scale(bool on, float p, uint64_t seed, uint64_t idx) {
   if (!on) return 1.f;
   return tt_uniform01(seed, idx) >= p ? 1.f / (1.f - p) : 0.f;
 }
 __device__ __forceinline__ uint64_t seed_of(uint64_t seed, const uint64_t* seed_dev) { return seed_dev ? seed + seed_dev[0] : seed; }
-
-// ---- column statistics of relu(pre): Welford per thread, Chan combine ------------------------
-struct Wf {
-  float n, mean, m2;
-};
-__device__ __forceinline__ Wf wf_combine(Wf a, Wf b) {
-  if (b.n == 0.f) return a;
-  if (a.n == 0.f) return b;
-  Wf o;
-  o.n = a.n + b.n;
-  const float d = b.mean - a.mean, w = b.n / o.n;      // one division per combine (the chains of 32 are latency-bound)
-  o.mean = a.mean + d * w;
-  o.m2 = a.m2 + b.m2 + d * d * (a.n * w);
-  return o;
-}
-
-// Canonical merge order of the chunk statistics (round 4; every finish -- bn_stats_finish_kernel, the fused tails, the SyncBN hand-over
-// -- uses it, so their results stay bit-identical to each other).  Chunk lane jl owns chunks jl, jl + 4, jl + 8, ... in four SUB-CHAINS of
-// kMaxChunks / 16 chunks each:   lane(jl) = ((C0 + C1) + C2) + C3,  C_s = ((v[8 s] + v[8 s + 1]) + ...) + v[8 s + 7];
-// the four lanes then merge as (lane0 + lane1) + (lane2 + lane3).  Sub-chains exist so that the fused forward tail can give each one to
-// its own thread (16 per column: 8 triples in flight per thread instead of 32 -- 52 registers, two workgroups per CU) without changing
-// the association; before, a lane was one chain of 32.
-constexpr int kSubChain = kMaxChunks / 16;
-__device__ __forceinline__ Wf wf_lane_merge(const Wf* v /* [kMaxChunks / 4] */) {
-  Wf o{0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    Wf cs{0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < kSubChain; ++i) cs = wf_combine(cs, v[kSubChain * s + i]);
-    o = wf_combine(o, cs);
-  }
-  return o;
-}
 
 template <typename A>
 struct Batch {
@@ -742,6 +709,7 @@ struct TailFwdArgs {
   const float* g; const float* b; uint64_t salt; float* act;
   const float* w_out; const float* b_out; int D; float* y; float* emb;
   __bf16* pk_rows; __bf16* pk_frag; int Dp; float pk_scale;   // optional: the score kernels' two operand images of emb (tt_score_pack_bf16)
+  const float* fin = nullptr;   // tail_fwd_kernel<true>: [2][H] mean, rstd, finished by the statistics rider in the keyed sort's launch
 };
 
 static_assert(kTailThreads == kRiderThreads, "the riders run in the tail kernels' workgroups");
@@ -759,6 +727,9 @@ __device__ unsigned long long g_tail_stamps[2][512 * 8];
 #define TT_TAIL_STAMP(k, i) do { } while (0)
 #endif
 
+// FIN: the statistics arrive finished (f.fin: one workgroup per tower has merged the chunk partials in front of the keyed sort, whose
+// launch lies between tower_front and this one) -- 2 * H floats per workgroup instead of 3 * H * nchunks, no merge, no triples in LDS.
+template <bool FIN>
 __global__ __launch_bounds__(kTailThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void tail_fwd_kernel(Batch<TailFwdArgs> batch, bool drop, float p, uint64_t seed0,
                      const uint64_t* __restrict__ seed_dev, CompactRider cr, int cr_wg) {
@@ -772,7 +743,7 @@ void tail_fwd_kernel(Batch<TailFwdArgs> batch, bool drop, float p, uint64_t seed
   const int m0 = blockIdx.x * 64;
   if (m0 >= B) return;
   TT_TAIL_STAMP(0, 0);
-  __shared__ Wf sh[16][64];
+  __shared__ Wf sh[FIN ? 1 : 16][64];
   __shared__ float s_mean[64], s_rstd[64];
   __shared__ __attribute__((aligned(16))) __bf16 As[64 * kTailLd];
   __shared__ __attribute__((aligned(16))) __bf16 Bs[64 * kTailLd];
@@ -786,23 +757,13 @@ void tail_fwd_kernel(Batch<TailFwdArgs> batch, bool drop, float p, uint64_t seed
     const float v = a.pre[(int64_t)min(r, B - 1) * H + min(c, H - 1)];     // (clamped address, no branch around the load)
     pre[j] = (c < H && r < B) ? v : 0.f;
   }
-  {                                                      // thread (c, rq): sub-chain rq >> 2 of chunk lane rq & 3 (wf_lane_merge's order)
-    Wf cs{0.f, 0.f, 0.f};
-    if (c < H) {
-      const int jl = rq & 3, sc = rq >> 2;
-      Wf v[kSubChain];
-      const int64_t ps = a.pstride ? a.pstride : 3 * H;
-#pragma unroll
-      for (int i = 0; i < kSubChain; ++i) {
-        const int k = jl + 4 * (kSubChain * sc + i);
-        const float* q = a.partial + (int64_t)min(k, a.nchunks - 1) * ps;      // (clamped address, no branch around the loads)
-        const float x0 = q[c], x1 = q[H + c], x2 = q[2 * H + c];
-        v[i] = k < a.nchunks ? Wf{x0, x1, x2} : Wf{0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < kSubChain; ++i) cs = wf_combine(cs, v[i]);
-    }
-    sh[rq][c] = cs;
+  float fm = 0.f, fr = 0.f;
+  if (FIN) {                                             // every thread fetches its column's pair: no LDS, no barrier before the apply
+    const float v0 = f.fin[min(c, H - 1)], v1 = f.fin[H + min(c, H - 1)];
+    fm = c < H ? v0 : 0.f;
+    fr = c < H ? v1 : 0.f;
+  } else {                                               // thread (c, rq): sub-chain rq >> 2 of chunk lane rq & 3 (wf_lane_merge's order)
+    sh[rq][c] = bn_finish_subchain(a.partial, a.pstride ? a.pstride : 3 * H, a.nchunks, H, c, rq);
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {                          // W_out [D, H] -> Bs[n][k]
@@ -810,37 +771,22 @@ void tail_fwd_kernel(Batch<TailFwdArgs> batch, bool drop, float p, uint64_t seed
     const float w = f.w_out[(int64_t)min(n, D - 1) * H + min(c, H - 1)];
     Bs[n * kTailLd + c] = (__bf16)((n < D && c < H) ? w : 0.f);
   }
-  __syncthreads();
-  TT_TAIL_STAMP(0, 1);
-  if (t < 64 && c < H) {
-    Wf ln[4];
-#pragma unroll
-    for (int jl = 0; jl < 4; ++jl) {                       // lane(jl) = ((C0 + C1) + C2) + C3, starting from the empty statistic
-      Wf o{0.f, 0.f, 0.f};
-#pragma unroll
-      for (int sc = 0; sc < 4; ++sc) o = wf_combine(o, sh[4 * sc + jl][c]);
-      ln[jl] = o;
+  if (!FIN) {
+    __syncthreads();
+    TT_TAIL_STAMP(0, 1);
+    if (t < 64 && c < H) {
+      bn_finish_column(sh, c, blockIdx.x == 0, a.mean, a.rstd, a.rm, a.rv, a.nbt, fm, fr);
+      s_mean[c] = fm;
+      s_rstd[c] = fr;
     }
-    const Wf o = wf_combine(wf_combine(ln[0], ln[1]), wf_combine(ln[2], ln[3]));
-    const float var = o.n > 0.f ? o.m2 / o.n : 0.f;
-    const float rstd = 1.f / sqrtf(var + kBnEps);
-    s_mean[c] = o.mean;
-    s_rstd[c] = rstd;
-    if (blockIdx.x == 0) {
-      a.mean[c] = o.mean;
-      a.rstd[c] = rstd;
-      if (a.rm) {
-        a.rm[c] = (1.f - kBnMomentum) * a.rm[c] + kBnMomentum * o.mean;
-        a.rv[c] = (1.f - kBnMomentum) * a.rv[c] + kBnMomentum * (o.n > 1.f ? o.m2 / (o.n - 1.f) : var);
-      }
-      if (a.nbt && c == 0) a.nbt[0] += 1;
-    }
+    __syncthreads();
+  } else {
+    TT_TAIL_STAMP(0, 1);
   }
-  __syncthreads();
   TT_TAIL_STAMP(0, 2);
   {
     const uint64_t seed = drop ? seed_of(seed0, seed_dev) : 0;
-    const float mean = c < H ? s_mean[c] : 0.f, rstd = c < H ? s_rstd[c] : 0.f;
+    const float mean = FIN ? fm : (c < H ? s_mean[c] : 0.f), rstd = FIN ? fr : (c < H ? s_rstd[c] : 0.f);
     const float g = c < H ? f.g[c] : 0.f, bb = c < H ? f.b[c] : 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1914,10 +1860,25 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
           tf.a[t].Dp = Dp;
           tf.a[t].pk_scale = A[t]->emb_pack_scale == 0.f ? 1.f : A[t]->emb_pack_scale;
         }
+      bool fin = false;
+      if (ctx->riders->s_on) {
+        // the keyed plan's sort has been held back for this place (TT_OPT_DEFER_RIDERS): behind the front kernel, with one workgroup
+        // per tower in its grid that finishes the chunk statistics once -- the tail then reads 2 * H floats per workgroup
+        BnFinishRiders bf{};
+        fin = phase == 0 && ctx->bn_fin != nullptr;       // (SyncBN's second half merges rank triples: in the tail, as before)
+        for (int t = 0; t < n && fin; ++t) {
+          const BnStatArgs& s = bs.a[t];
+          bf.r[t] = BnFinishRider{s.partial, s.pstride ? s.pstride : 3 * s.H, s.nchunks, s.H, s.mean, s.rstd, s.rm, s.rv, s.nbt,
+                                  ctx->bn_fin + t * kBnFinStride};
+          tf.a[t].fin = bf.r[t].out;
+        }
+        if (int rc = tt_keyed_sort_launch(ctx, st, &bf, fin ? n : 0)) return rc;
+      }
       const int cr_wg = ctx->riders->c_wg;               // a queued plan compaction rides in one extra grid row
       const int64_t gx = tt_cdiv(B, 64) > cr_wg ? tt_cdiv(B, 64) : cr_wg;
-      tail_fwd_kernel<<<dim3((unsigned)gx, (unsigned)(n + (cr_wg > 0 ? 1 : 0))), kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev,
-                                                                                                       ctx->riders->c, cr_wg);
+      const dim3 grid((unsigned)gx, (unsigned)(n + (cr_wg > 0 ? 1 : 0)));
+      if (fin) tail_fwd_kernel<true><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->riders->c, cr_wg);
+      else tail_fwd_kernel<false><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->riders->c, cr_wg);
       ctx->riders->c_wg = 0;
       TT_LAUNCH_CHECK();
       return TT_OK;

@@ -324,7 +324,9 @@ class _TowersFn(torch.autograd.Function):
         # duplicate-row plans: depend on ids only, first needed in the backward.  In line on the launch stream (a side stream
         # overlapped the sort with the score kernels, but a captured graph with two streams is replayed node by node with
         # cross-queue signals: 4-6 us gaps in front of eight kernels -- as much as the overlap saved), and BEFORE the towers'
-        # forward: with TT_OPT_DEFER_RIDERS the plan's compaction then rides in the towers' tail launch
+        # forward: with TT_OPT_DEFER_RIDERS the plan's compaction then rides in the towers' tail launch, and the sort itself is
+        # queued by this call and issued by the towers' forward between its front and tail kernels (it hosts the workgroups that
+        # finish the BatchNorm statistics once per tower: tt_riders.h)
         for pl in plans:
             if len(pl) == 6:
                 store, psides, _, rows, want_plan, key_major = pl
