@@ -96,6 +96,20 @@ uint64_t tt_launch_count(void);
 /* TT_OPT_RETRIEVE_SPLITS (default 0 = chosen from the shapes): catalogue splits of tt_retrieve_topk_* (clamped to
  * [1, min(32, ceil(nC / 32))]).  Every value gives the same results bit for bit (tests vary it). */
 #define TT_OPT_RETRIEVE_SPLITS 9
+/* TT_OPT_FUSE_SCORE_TAIL (default 0; independent of TT_OPT_DEFER_RIDERS): tt_score_bwd_bf16 leaves its launch QUEUED in the context
+ * instead of launching it when the call takes the one-image transposing form at padded D = 64 (below TT_OPT_SCORE_BWD_ROWS_MIN
+ * rows) with two directions over square problems of one size (Ra == Rb) -- every other entry, shape and the logQ form launch at once.
+ * The next tt_towers_mlp_bwd launches it with the towers' backward head (L2-normalise backward, d_act, the output layer's gradient
+ * slabs, the BN column sums) in the epilogue of its workgroups -- one launch instead of two, no round trip of d_emb, same values in
+ * the same order: bit-identical -- when the fused narrow tail applies (no sync_phase), there are two towers whose last hidden width and d_out are 64,
+ * the row chunks are 64 rows each (chunk x = rows 64 x .. 64 x + 63, the score workgroup's rows), it is called on the stream the
+ * score backward was queued on and its d_emb[t] are exactly the queued dA of direction t.  A loss reduction queued under
+ * TT_OPT_DEFER_RIDERS then rides the tail's second launch.  Otherwise tt_towers_mlp_bwd launches the queued score backward on its own
+ * in front of itself.  Until then dA is NOT written.  tt_flush_deferred, tt_embed_grad_bwd, tt_embed_grad_finish, the tt_adam_* /
+ * tt_rowwise_adagrad_* entries, another queueing tt_score_bwd_bf16 and setting this option to 0 launch a score backward that is
+ * still queued (always on the stream it was queued on); tt_deferred_pending() shows it as bit 2.  A queued launch runs exactly
+ * once.  For callers that run the whole step back to back (GraphedTrainStep). */
+#define TT_OPT_FUSE_SCORE_TAIL 10
 int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value);
 /* Device-side errors.  A kernel that cannot complete its contract without hanging or faulting the GPU (a tile of a chained
  * segment-head launch whose bounded wait for a predecessor expired; a lookup whose decoded row lies outside the table it was given
@@ -120,7 +134,7 @@ int tt_handover_captured_node(tt_ctx* ctx, void** node);
 int tt_flush_deferred(tt_ctx* ctx, tt_stream stream);
 /* only the queued slab reduction (the one thing that lives in the caller's shared scratch buffer) */
 int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream stream);
-/* bit 0: a slab reduction is queued; bit 1: riders (TT_OPT_DEFER_RIDERS) are queued */
+/* bit 0: a slab reduction is queued; bit 1: riders (TT_OPT_DEFER_RIDERS) are queued; bit 2: a score backward (TT_OPT_FUSE_SCORE_TAIL) */
 int tt_deferred_pending(const tt_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------

@@ -265,6 +265,7 @@ TT_OPT_CHAINED = 6
 TT_OPT_LOOKUP_NT = 7
 TT_OPT_CHAIN_SPIN = 8
 TT_OPT_RETRIEVE_SPLITS = 9
+TT_OPT_FUSE_SCORE_TAIL = 10
 
 
 def set_option(device: torch.device, option: int, value: int):
@@ -294,6 +295,12 @@ def set_defer_riders(device: torch.device, on, loss_only: bool = False):
     else:
         _riders_on.pop(idx, None)
         flush_deferred(device)
+
+
+def set_fuse_score_tail(device: torch.device, on: bool):
+    """tt_score_bwd_bf16 leaves its launch queued in the context and tt_towers_mlp_bwd runs it with the towers' backward head in its
+    epilogue (include/twotower.h: TT_OPT_FUSE_SCORE_TAIL).  Switching it off launches a score backward that is still queued."""
+    check(load().tt_ctx_set_option(ctx(device), TT_OPT_FUSE_SCORE_TAIL, 1 if on else 0), "tt_ctx_set_option")
 
 
 def riders_deferred(device: torch.device, which: int = 3) -> bool:

@@ -39,6 +39,10 @@ struct tt_ctx {
   int defer_riders;         // TT_OPT_DEFER_RIDERS, as a mask: 1 plan compaction, 2 score loss reduction queue in `riders` (tt_riders.h)
   int fp8_grad;             // TT_OPT_FP8_GRAD: tt_score_bwd_fp8 forms the gradient products from e4m3 operands too (default 1)
   struct tt_riders* riders;
+  // TT_OPT_FUSE_SCORE_TAIL: tt_score_bwd_bf16 leaves its launch queued here (score_q, allocated on first use) when the towers'
+  // backward can run it with the backward head in its epilogue (tt_tail_bwd.h)
+  int fuse_score_tail;
+  struct ScoreBwdQueued* score_q;
   float* bn_fin;            // [TT_MAX_SIDES][2][64]: the towers' finished BatchNorm batch statistics (mean, rstd) of the step in flight,
                             // written by the statistics riders in the keyed sort's launch and read by tail_fwd (tt_riders.h)
   // chained single-launch scans (segment heads, owner routing): small device buffers that are all-zero between launches -- word 0

@@ -2,6 +2,7 @@
 #include "tt_common.h"
 #include "tt_gemm.h"
 #include "tt_riders.h"
+#include "tt_tail_bwd.h"
 
 #include <mutex>
 
@@ -29,6 +30,7 @@ uint32_t* tt_chain_for(tt_ctx* ctx, hipStream_t stream) {
 }
 
 int tt_riders_flush(tt_ctx* ctx, hipStream_t st) {
+  if (int rc = tt_score_bwd_flush(ctx)) return rc;       // a score backward nobody hosted (TT_OPT_FUSE_SCORE_TAIL): whoever flushes may read d_emb
   if (!ctx || !ctx->riders) return TT_OK;
   if (ctx->riders->s_on)                                 // a sort nobody hosted: in front of its compaction, no statistics riders
     if (int rc = tt_keyed_sort_launch(ctx, st, nullptr, 0)) return rc;
@@ -75,6 +77,8 @@ int tt_ctx_create(int device, tt_ctx** out) {
   c->keyed_parts = 0;
   c->score_bwd_rows_min = 32768;
   c->defer_riders = 0;
+  c->fuse_score_tail = 0;
+  c->score_q = nullptr;
   c->fp8_grad = 1;
   c->riders = new tt_riders();
   c->riders->c_wg = c->riders->f_wg = c->riders->s_on = 0;
@@ -112,6 +116,7 @@ int tt_ctx_create(int device, tt_ctx** out) {
 int tt_ctx_destroy(tt_ctx* ctx) {
   if (ctx && ctx->deferred) tt_gemm_tn_pending_destroy(ctx->deferred);
   if (ctx) delete ctx->riders;
+  tt_score_bwd_queue_destroy(ctx);
   if (ctx && ctx->chain) (void)hipFree(ctx->chain);
   if (ctx && ctx->bn_fin) (void)hipFree(ctx->bn_fin);
   delete ctx;
@@ -135,6 +140,10 @@ int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value) {
       ctx->defer_riders = value == 1 ? 3 : value;      // 1 = both riders (as 3), 2 = the loss reduction only
       break;
     case TT_OPT_FP8_GRAD: ctx->fp8_grad = value != 0; break;
+    case TT_OPT_FUSE_SCORE_TAIL:
+      ctx->fuse_score_tail = value != 0;
+      if (!value) return tt_score_bwd_flush(ctx);        // (on the stream it was queued on)
+      break;
     case TT_OPT_CHAINED: ctx->chained = value != 0; break;
     case TT_OPT_LOOKUP_NT: ctx->lookup_nt = value != 0; break;
     case TT_OPT_CHAIN_SPIN:
@@ -196,7 +205,8 @@ int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream stream) {
 
 int tt_deferred_pending(const tt_ctx* ctx) {
   if (!ctx) return 0;
-  return ((ctx->deferred && ctx->deferred->n > 0) ? 1 : 0) | ((ctx->riders && (ctx->riders->c_wg > 0 || ctx->riders->f_wg > 0 || ctx->riders->s_on)) ? 2 : 0);
+  return ((ctx->deferred && ctx->deferred->n > 0) ? 1 : 0) | ((ctx->riders && (ctx->riders->c_wg > 0 || ctx->riders->f_wg > 0 || ctx->riders->s_on)) ? 2 : 0) |
+         (tt_score_bwd_queued(ctx) ? 4 : 0);
 }
 
 int tt_ctx_num_cus(const tt_ctx* ctx) { return ctx ? ctx->num_cus : 0; }

@@ -15,6 +15,7 @@
 //     the second product in the k-permutation the accumulator registers impose.
 //   * partial results of the NW waves are combined through LDS in a fixed tree order.
 #include "tt_score_bf16.h"
+#include "tt_tail_bwd.h"
 
 #include <stdlib.h>
 
@@ -654,12 +655,28 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
 // direction recomputes S) need ~20 us of the matrix pipe, the softmax VALU work ~24 us, the loads ~20 us, and a wave runs the
 // three one after the other.
 // LQ: as score_bwd_bf16_kernel's.
-template <int KS, int AT, bool UNIT, bool LQ = false>
-__global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
+// TAIL (KS = 4, AT = 2, no LQ; TT_OPT_FUSE_SCORE_TAIL, launched by tt_towers_mlp_bwd): the workgroup goes on with the towers' backward head (tt_tail_bwd.h) of
+// tower blockIdx.y, row chunk blockIdx.x -- the 64 rows whose d_emb wave 0 holds when the tree is done.  The head's loads that
+// depend on nothing the sweep produces are issued in front of the tree (ares and the streamed tiles are dead there); the head's
+// LDS lies over `red` (whole: the tree has read it), the f32 tile of d_emb behind it.  Sweep and tree are the same code.
+// (one __global__ template for both: the sweep must compile exactly as it does without a tail)
+template <bool TAIL>
+struct TailHost {};
+template <>
+struct TailHost<true> { tttail::Batch<tttail::TailBwdArgs> batch; bool drop; float p; uint64_t seed0; const uint64_t* seed_dev; };
+
+template <int KS, int AT, bool UNIT, bool LQ = false, bool TAIL = false>
+__global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHost<TAIL> th) {
   constexpr int NW = 8, Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2;
   constexpr int TLD = Dp + 8;                                   // LDS row of the parked tile: 144 B at D = 64 (conflict-free b128 writes)
-  __shared__ float red[(NW / 2) * ROWS * Dp];
-  __shared__ __attribute__((aligned(16))) __bf16 park[NW][32 * TLD];
+  constexpr int kRedB = (NW / 2) * ROWS * Dp * 4, kParkB = NW * 32 * TLD * 2;
+  static_assert(!TAIL || (KS == 4 && AT == 2 && !LQ && tttail::kTailBwdLds + 64 * tttail::kTailTileLd * 4 <= kRedB + kParkB),
+                "the tail's head and its d_emb tile lie over red | park of the <4, 2> form");
+  __shared__ float red_s[TAIL ? 1 : (NW / 2) * ROWS * Dp];
+  __shared__ __attribute__((aligned(16))) __bf16 park_s[TAIL ? 1 : NW][32 * TLD];
+  __shared__ __attribute__((aligned(16))) char smem[TAIL ? kRedB + kParkB : 16];       // TAIL: red | park as ONE buffer
+  float* const red = TAIL ? reinterpret_cast<float*>(smem) : red_s;
+  __bf16 (*const park)[32 * TLD] = TAIL ? reinterpret_cast<__bf16 (*)[32 * TLD]>(smem + kRedB) : park_s;
   using s16x4 = __attribute__((ext_vector_type(4))) short;
   using s16x8 = __attribute__((ext_vector_type(8))) short;
   const bool d1 = blockIdx.y != 0;
@@ -803,6 +820,15 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
     load(T0, min(t + 2 * NW, tlast));
     if (t + NW < nT) compute(T1, t + NW);
   }
+  [[maybe_unused]] tttail::TailBwdConst<512> hk;
+  [[maybe_unused]] tttail::TailBwdRows<512> hv;
+  [[maybe_unused]] uint64_t hseed = 0;
+  if constexpr (TAIL) {
+    const tttail::TailBwdArgs& f = th.batch.a[blockIdx.y];
+    tttail::tail_bwd_load_const<512>(f, hk);
+    tttail::tail_bwd_load_rows<512, true>(f, min(f.col.B, a0 + 64), a0, hv);
+    if (th.drop) hseed = tttail::seed_of(th.seed0, th.seed_dev);
+  }
 #pragma unroll
   for (int half = NW / 2; half >= 1; half >>= 1) {
     if (wave >= half && wave < 2 * half) {
@@ -826,6 +852,7 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
     }
     __syncthreads();
   }
+  [[maybe_unused]] float* const htile = reinterpret_cast<float*>(smem + tttail::kTailBwdLds);
   if (wave == 0) {
     const float g = args.d_loss[0] * out_scale;
 #pragma unroll
@@ -837,8 +864,10 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args) {
           const int a = a0 + 32 * i + rowmap(r, h);
           const int dd = 32 * d + c;
           if (a < Ra && dd < args.D) dr.dA[(int64_t)a * args.D + dd] = dacc[i][d][r] * g;
+          if constexpr (TAIL) htile[(32 * i + rowmap(r, h)) * tttail::kTailTileLd + dd] = dacc[i][d][r] * g;
         }
   }
+  if constexpr (TAIL) tttail::tail_bwd_head<512, true>(th.batch.a[blockIdx.y], blockIdx.x, th.drop, th.p, hseed, smem, htile, &hk, &hv);
 }
 
 // ---- backward, large-batch form ---------------------------------------------------------------------
@@ -1633,7 +1662,60 @@ static void launch_bsplit(const BwdSetup& s, hipStream_t st) {
 template <int KS, int AT>
 static void launch_tr(const BwdSetup& s, hipStream_t st) {
   const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
-  tt_dispatch([&](auto u, auto l) { score_bwd_tr_kernel<KS, AT, u, l><<<grid, 512, 0, st>>>(s.a); }, s.unit, s.lq);
+  tt_dispatch([&](auto u, auto l) { score_bwd_tr_kernel<KS, AT, u, l><<<grid, 512, 0, st>>>(s.a, TailHost<false>{}); }, s.unit, s.lq);
+}
+
+// ---- TT_OPT_FUSE_SCORE_TAIL: a launch_tr<4, 2> launch held back in the context (tt_tail_bwd.h) -----------------------------------
+// Held: two directions over square problems of the same size, no logQ -- what the towers' backward can host.  Launched exactly once:
+// by tt_score_tail_bwd_launch (with the towers' backward head in its epilogue) or by tt_score_bwd_flush (the stand-alone kernel).
+struct ScoreBwdQueued {
+  BwdSetup s;
+  hipStream_t st;
+  bool on = false;
+};
+
+static bool bwd_queue(tt_ctx* ctx, const BwdSetup& s, hipStream_t st) {
+  const DirBwd* d = s.a.d;
+  if (!ctx->fuse_score_tail || s.lq || s.n_dirs != 2 || d[0].Ra != d[0].Rb || d[1].Ra != d[1].Rb || d[0].Ra != d[1].Ra) return false;
+  if (!ctx->score_q) ctx->score_q = new ScoreBwdQueued();
+  ctx->score_q->s = s;
+  ctx->score_q->st = st;
+  ctx->score_q->on = true;
+  return true;
+}
+
+int tt_score_bwd_queued(const tt_ctx* ctx) { return ctx && ctx->score_q && ctx->score_q->on ? 1 : 0; }
+
+void tt_score_bwd_queued_outputs(const tt_ctx* ctx, const float** dA, int64_t* rows, hipStream_t* st) {
+  const ScoreBwdQueued& q = *ctx->score_q;
+  dA[0] = q.s.a.d[0].dA;
+  dA[1] = q.s.a.d[1].dA;
+  *rows = q.s.maxRa;
+  *st = q.st;
+}
+
+int tt_score_bwd_flush(tt_ctx* ctx) {
+  if (!tt_score_bwd_queued(ctx)) return TT_OK;
+  ctx->score_q->on = false;
+  launch_tr<4, 2>(ctx->score_q->s, ctx->score_q->st);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_tail_bwd_launch(tt_ctx* ctx, const tttail::Batch<tttail::TailBwdArgs>& tb, bool drop, float p, uint64_t seed,
+                             const uint64_t* seed_dev) {
+  TT_CHECK_ARG(tt_score_bwd_queued(ctx), "tt_score_tail_bwd_launch: no score backward is queued");
+  ScoreBwdQueued& q = *ctx->score_q;
+  q.on = false;
+  const dim3 grid((unsigned)tt_cdiv(q.s.maxRa, 64), 2);
+  tt_dispatch([&](auto u) { score_bwd_tr_kernel<4, 2, u, false, true><<<grid, 512, 0, q.st>>>(q.s.a, TailHost<true>{tb, drop, p, seed, seed_dev}); }, q.s.unit);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+void tt_score_bwd_queue_destroy(tt_ctx* ctx) {
+  if (ctx) delete ctx->score_q;
+  if (ctx) ctx->score_q = nullptr;
 }
 
 // workgroup-staged form (score_bwd_rows_kernel); FP8: fp8 S operands (no logQ form)
@@ -1680,6 +1762,8 @@ static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bw
   } else if (Dp == 32) {
     launch_bsplit<2, 2, 8, false>(s, st);
   } else if (Dp == 64) {
+    if (int rc = tt_score_bwd_flush(ctx)) return rc;      // (one launch waits at a time)
+    if (bwd_queue(ctx, s, st)) return TT_OK;              // TT_OPT_FUSE_SCORE_TAIL: tt_towers_mlp_bwd launches it, or a flush
     launch_tr<4, 2>(s, st);
   } else if (Dp == 128) {                                 // the one-image form, one a tile per workgroup
     launch_tr<8, 1>(s, st);

@@ -3,24 +3,15 @@
 // ReLU / BN / dropout / L2-normalise as fused elementwise and row-wise kernels.
 #include "tt_gemm.h"
 #include "tt_riders.h"
+#include "tt_tail_bwd.h"
 
 namespace {
 
+using namespace tttail;   // Batch, ColArgs, dropout_scale, seed_of, mul_rn, the tail tiles' constants, TailBwdArgs (tt_tail_bwd.h)
+
 constexpr int kThreads = 256;
-constexpr float kNormEps = 1e-12f;
 // (column statistics of relu(pre) -- Wf, wf_combine, the canonical merge order wf_lane_merge, kMaxChunks -- live in tt_riders.h:
 // the statistics rider in the keyed sort's launch shares them)
-
-__device__ __forceinline__ float dropout_scale(bool on, float p, uint64_t seed, uint64_t idx) {
-  if (!on) return 1.f;
-  return tt_uniform01(seed, idx) >= p ? 1.f / (1.f - p) : 0.f;
-}
-__device__ __forceinline__ uint64_t seed_of(uint64_t seed, const uint64_t* seed_dev) { return seed_dev ? seed + seed_dev[0] : seed; }
-
-template <typename A>
-struct Batch {
-  A a[TT_MAX_SIDES];
-};
 
 // grid (colblocks of 64, nchunks, towers); thread = (column, row-lane of 4)
 struct BnStatArgs {
@@ -126,18 +117,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(Batch<BnApplyArgs> b
   }
 }
 
-// ---- deterministic two-stage column sums of the BatchNorm backward ------------------------------
-//   da = d_act * dropscale ; xhat from pre ; S1 = sum da, S2 = sum da * xhat
-struct ColArgs {
-  const float* x; int64_t ldx;
-  const float* pre; const float* mean; const float* rstd;
-  uint64_t salt;
-  int B, H, rows_per_chunk, nchunks;
-  float* partial; float* out0; float* out1;
-  int64_t pstride = 0;   // floats between chunks when READING partial (0 = 2 * H)
-  float out_scale = 1.f; // colsum_finish_kernel: S1 / S2 are stored times this (1 / ranks under SyncBN); the raw sums go to sums_raw
-  float* sums_raw = nullptr;   // optional [2 * H]: the unscaled S1 | S2 for bn_bwd_apply_kernel
-};
+// ---- deterministic two-stage column sums of the BatchNorm backward (ColArgs: tt_tail_bwd.h) -------
 
 __global__ __launch_bounds__(kThreads) void colsum_partial_kernel(Batch<ColArgs> batch, bool drop, float p, uint64_t seed0,
                                                                  const uint64_t* __restrict__ seed_dev) {
@@ -228,11 +208,6 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(Batch<BnBwdArgs>
 }
 
 // ---- row-wise L2 normalise: one wave per row ---------------------------------------------------
-// a product that is rounded on its own (HIP's __fmul_rn is a plain `*`, which the compiler still contracts)
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
@@ -369,11 +344,7 @@ static bool launch_l2norm_fast(hipStream_t st, const Batch<NormArgs>& na, int n,
 // and the BN gradients come out bit-identical); only the output-layer weight / bias gradients are summed over
 // different row chunks.  Workgroups of 1024 threads cover 64 rows: thread (c, rq) = column c, rows rq + 16 j; the
 // ordered column reductions run on the first 256 threads (c, rl) exactly as in the unfused kernels.
-using tl_f32x16 = __attribute__((ext_vector_type(16))) float;
-using tl_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 constexpr int kTailThreads = 1024;
-constexpr int kTailLd = 72;      // bf16 elements per LDS row of a 64-wide operand tile (144 B: aligned 16-B fragments)
-constexpr int kTailLdF = 65;     // f32 row stride of the staging tiles
 
 // (A) finish the split-K block GEMM (slabs + bias -> pre) and take the per-chunk BN statistics of relu(pre) in the same
 // pass over the rows: slab_reduce_kernel + bn_stats_partial_kernel.  grid (nchunks, towers)
@@ -1057,17 +1028,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_fwd_wide_kernel(Batch<TailF
   }
 }
 
-// (C) backward head: L2-normalise backward -> d_y; d_act = d_y . W_out; the chunk's share of the output-layer weight /
-// bias gradients (d_y^T . act, column sums of d_y) into slabs; per-chunk BN column sums S1 / S2.  One workgroup per
-// row chunk (the chunks of colsum_partial_kernel), 64 rows at a time.  d_act leaves this kernel already multiplied by
-// the dropout scale (tail_bwd_apply_kernel does not regenerate the mask).  grid (nchunks, towers)
-struct TailBwdArgs {
-  const float* y; const float* emb; const float* d_emb; float* d_y; int D;
-  const float* w_out; const float* act; float* d_act;
-  ColArgs col;                       // x / ldx unused: d_act is taken from the tile
-  float* w_slab; float* b_slab;      // [nchunks][D * H], [nchunks][D]
-};
-
+// (C) backward head (tt_tail_bwd.h: tail_bwd_head, the body this kernel shares with score_bwd_tr_kernel's TAIL form).  grid (nchunks, towers)
 // (fr_on: the FIRST grid row is one workgroup running the symmetric score forward's loss reduction -- tt_riders.h)
 __global__ __launch_bounds__(kTailThreads) void tail_bwd_kernel(Batch<TailBwdArgs> batch, bool drop, float p, uint64_t seed0,
                                                                const uint64_t* __restrict__ seed_dev, Finish2Rider fr, int fr_on) {
@@ -1076,162 +1037,10 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_kernel(Batch<TailBwdArg
     return;
   }
   const TailBwdArgs& f = batch.a[blockIdx.y - fr_on];
-  const ColArgs& a = f.col;
-  const int H = a.H, D = f.D;
-  if ((int)blockIdx.x >= a.nchunks) return;
-  // dyA [row][d] | dyT [d][row] | (XH f32 tile aliases these two once the MFMAs are done) ; Wn [h][d] ; actT [h][row]
-  __shared__ __attribute__((aligned(16))) __bf16 dy2[2 * 64 * kTailLd];
-  __shared__ __attribute__((aligned(16))) __bf16 Wn[64 * kTailLd];
-  __shared__ __attribute__((aligned(16))) __bf16 actT[64 * kTailLd];
-  __shared__ float DY[64 * kTailLdF];                                   // d_y, then d_act, of the 64 rows
-  __shared__ float sh[3][4][64];
-  static_assert(sizeof(float) * 64 * kTailLdF <= sizeof(__bf16) * 2 * 64 * kTailLd, "XH must fit over dyA | dyT");
-  __bf16* dyA = dy2;
-  __bf16* dyT = dy2 + 64 * kTailLd;
-  float* XH = reinterpret_cast<float*>(dy2);
-  const int t = threadIdx.x, c = t & 63, rq = t >> 6;
-  const int lane = c, wave = rq;
-  const int r0 = blockIdx.x * a.rows_per_chunk, r1 = min(a.B, r0 + a.rows_per_chunk);
+  if ((int)blockIdx.x >= f.col.nchunks) return;
+  __shared__ __attribute__((aligned(16))) char smem[kTailBwdLds];
   const uint64_t seed = drop ? seed_of(seed0, seed_dev) : 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {                         // W_out [D, H]: element (k = d, n = h) -> Wn[h][d]
-    const int d = rq + 16 * j;
-    const float w = f.w_out[(int64_t)min(d, D - 1) * H + min(c, H - 1)];
-    Wn[c * kTailLd + d] = (__bf16)((d < D && c < H) ? w : 0.f);
-  }
-  const float mean = c < H ? a.mean[c] : 0.f, rstd = c < H ? a.rstd[c] : 0.f;
-  tl_f32x16 accw;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) accw[i] = 0.f;
-  float s0 = 0.f, s1 = 0.f, cs = 0.f;
-  for (int b0 = r0; b0 < r1; b0 += 64) {
-    // 1. d_y of rows b0 .. b0 + 63: one wave per row as l2norm_bwd_kernel, four independent rows per wave in flight
-    float yv[4], e[4], de[4], ss[4], dot[4], xh[4], sc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = b0 + wave * 4 + j;
-      const bool ok = r < r1 && lane < D;                 // (unconditional loads at clamped addresses: a load under a per-lane
-      const int64_t i = (int64_t)min(r, r1 - 1) * D + min(lane, D - 1);   //  condition is waited for before the next is issued)
-      const float v0 = f.y[i], v1 = f.emb[i], v2 = f.d_emb[i];
-      yv[j] = ok ? v0 : 0.f;
-      e[j] = ok ? v1 : 0.f;
-      de[j] = ok ? v2 : 0.f;
-    }
-    float av[4], pr[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                       // thread (c, rq): rows rq + 16 j of act / pre
-      const int r = b0 + rq + 16 * j;
-      const bool ok = c < H && r < r1;
-      const int64_t i = (int64_t)min(r, r1 - 1) * H + min(c, H - 1);
-      const float v0 = f.act[i], v1 = a.pre[i];
-      av[j] = ok ? v0 : 0.f;
-      pr[j] = ok ? v1 : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      ss[j] = mul_rn(yv[j], yv[j]);
-      dot[j] = mul_rn(e[j], de[j]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        ss[j] += __shfl_xor(ss[j], o);
-        dot[j] += __shfl_xor(dot[j], o);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = wave * 4 + j, r = b0 + row;
-      const float nrm = sqrtf(ss[j]);
-      const float den = fmaxf(nrm, kNormEps);
-      float out = nrm > kNormEps ? (de[j] - e[j] * dot[j]) / den : de[j] / den;
-      if (r < r1 && lane < D) f.d_y[(int64_t)r * D + lane] = out;
-      else out = 0.f;
-      DY[row * kTailLdF + lane] = out;
-      dyA[row * kTailLd + lane] = (__bf16)out;
-      dyT[lane * kTailLd + row] = (__bf16)out;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = rq + 16 * j, r = b0 + row;
-      actT[c * kTailLd + row] = (__bf16)av[j];
-      xh[j] = (fmaxf(pr[j], 0.f) - mean) * rstd;
-      sc[j] = (c < H && r < r1) ? dropout_scale(drop, p, seed, a.salt + (uint64_t)((int64_t)r * H + c)) : 0.f;
-    }
-    __syncthreads();
-    // 2. bias-gradient column sums of d_y, data gradient d_act = d_y . W_out, weight-gradient tile += d_y^T . act
-    const int wr = (wave >> 1) & 1, wc = wave & 1, li = lane & 31, lh = lane >> 5;
-    tl_f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    if (wave < 4) {
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) cs += DY[(rq + 4 * j) * kTailLdF + c];
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2) {
-        const int ko = 16 * s2 + 8 * lh;
-        const tl_bf16x8 a1 = *reinterpret_cast<const tl_bf16x8*>(dyA + (wr * 32 + li) * kTailLd + ko);
-        const tl_bf16x8 b1 = *reinterpret_cast<const tl_bf16x8*>(Wn + (wc * 32 + li) * kTailLd + ko);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-        const tl_bf16x8 a2 = *reinterpret_cast<const tl_bf16x8*>(dyT + (wr * 32 + li) * kTailLd + ko);
-        const tl_bf16x8 b2 = *reinterpret_cast<const tl_bf16x8*>(actT + (wc * 32 + li) * kTailLd + ko);
-        accw = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, accw, 0, 0, 0);
-      }
-    }
-    __syncthreads();                                     // DY (as d_y), dyA and dyT have been read
-    if (wave < 4) {
-      const int n = wc * 32 + li;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) DY[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * kTailLdF + n] = acc[r];
-    }
-    __syncthreads();
-    // 3. d_act (times the dropout scale) out; da and xhat staged for the ordered column sums
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = rq + 16 * j, r = b0 + row;
-      const float da = DY[row * kTailLdF + c] * sc[j];
-      if (c < H && r < r1) f.d_act[(int64_t)r * H + c] = da;
-      DY[row * kTailLdF + c] = da;
-      XH[row * kTailLdF + c] = xh[j];
-    }
-    __syncthreads();
-    if (t < 256 && c < H) {                              // colsum_partial_kernel's order: rows r0 + rq, + 4, ...
-      const int nrow = min(64, r1 - b0);
-      for (int row = rq; row < nrow; row += 4) {
-        const float da = DY[row * kTailLdF + c];
-        s0 += da;
-        s1 += da * XH[row * kTailLdF + c];
-      }
-    }
-    __syncthreads();
-  }
-  if (t < 256) {
-    sh[0][rq][c] = s0;
-    sh[1][rq][c] = s1;
-    sh[2][rq][c] = cs;
-  }
-  __syncthreads();
-  if (t < 64) {
-    if (c < H) {
-      float* q = a.partial + (int64_t)blockIdx.x * 2 * H;
-      q[c] = ((sh[0][0][c] + sh[0][1][c]) + sh[0][2][c]) + sh[0][3][c];
-      q[H + c] = ((sh[1][0][c] + sh[1][1][c]) + sh[1][2][c]) + sh[1][3][c];
-    }
-    if (c < D) f.b_slab[(int64_t)blockIdx.x * D + c] = ((sh[2][0][c] + sh[2][1][c]) + sh[2][2][c]) + sh[2][3][c];
-  }
-  if (wave < 4) {
-    const int wr = wave >> 1, wc = wave & 1, li = lane & 31, lh = lane >> 5;
-    float* ws = f.w_slab + (int64_t)blockIdx.x * D * H;
-    const int n = wc * 32 + li;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (m < D && n < H) ws[(int64_t)m * H + n] = accw[r];
-    }
-  }
+  tail_bwd_head<kTailThreads, false>(f, blockIdx.x, drop, p, seed, smem, nullptr, nullptr, nullptr);
 }
 
 // (D) S1 / S2 finish (every workgroup, colsum_finish_kernel's order) + BN backward apply in place on the (already
@@ -1243,8 +1052,14 @@ struct TailApplyArgs {
   float out_scale;      // BN weight / bias gradients are stored times this (1 / ranks under SyncBN: see twotower.h)
 };
 
-__global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(Batch<TailApplyArgs> batch) {
-  const TailApplyArgs& ta = batch.a[blockIdx.y];
+// (fr_on: the FIRST grid row is one workgroup running the symmetric score forward's loss reduction, as in tail_bwd_kernel -- its
+// host when the score backward's launch runs the backward head, whose workgroups have 512 threads)
+__global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(Batch<TailApplyArgs> batch, Finish2Rider fr, int fr_on) {
+  if (fr_on && blockIdx.y == 0) {
+    if (blockIdx.x == 0) finish2_body(fr);
+    return;
+  }
+  const TailApplyArgs& ta = batch.a[blockIdx.y - fr_on];
   const ColArgs& a = ta.col;
   const BnBwdArgs& b = ta.bn;
   const int H = a.H, B = a.B;
@@ -1984,6 +1799,9 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     for (int t = 0; t < n; ++t)
       TT_CHECK_ARG(G[t] && (phase == 1 ? G[t]->s_sync_local != nullptr : G[t]->s_sync_all != nullptr), "tt_towers_mlp_bwd: NULL SyncBN buffer");
   }
+  // a score backward held back for this pass (TT_OPT_FUSE_SCORE_TAIL) writes d_emb: only the fused narrow tail can host it (below)
+  if (!(fused && phase == 0))
+    if (int rc = tt_score_bwd_flush(ctx)) return rc;
   if (!fused && !wide && phase != 2) {
     if (!launch_l2norm_fast<true>(st, na, n, B)) l2norm_bwd_kernel<<<dim3((unsigned)tt_cdiv(B, 4), (unsigned)n), kThreads, 0, st>>>(na);
     TT_LAUNCH_CHECK();
@@ -2031,7 +1849,24 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
                               w_slab, b_slab, D, g->w_out, g->b_out, nchunks, 1.f / (float)ranks};
       cmax = nchunks > cmax ? nchunks : cmax;
     }
-    if (phase != 2) {
+    // a score backward that waits in the context (TT_OPT_FUSE_SCORE_TAIL) runs the head in its own launch when its workgroups
+    // are the head's: two towers, H = D = 64, 64-row chunks numbered like its 64-row tiles, its dA exactly d_emb in tower order
+    bool hosted = false;
+    if (tt_score_bwd_queued(ctx)) {
+      const float* qd[2];
+      int64_t qrows;
+      hipStream_t qst;
+      tt_score_bwd_queued_outputs(ctx, qd, &qrows, &qst);
+      hosted = phase == 0 && n == 2 && qst == st && qrows == B && qd[0] == d_emb[0] && qd[1] == d_emb[1];
+      for (int t = 0; hosted && t < n; ++t)
+        hosted = tb.a[t].D == 64 && tb.a[t].col.H == 64 && tb.a[t].col.rows_per_chunk == 64 && tb.a[t].col.nchunks == (int)tt_cdiv(B, 64);
+      if (hosted) {
+        if (int rc = tt_score_tail_bwd_launch(ctx, tb, drop, dropout_p, seed, seed_dev)) return rc;
+      } else if (int rc = tt_score_bwd_flush(ctx)) {
+        return rc;
+      }
+    }
+    if (phase != 2 && !hosted) {
       const int fr_on = ctx->riders->f_wg > 0 ? 1 : 0;    // a queued loss reduction rides in one extra grid row
       tail_bwd_kernel<<<dim3((unsigned)cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev, ctx->riders->f,
                                                                                            fr_on);
@@ -2045,8 +1880,13 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
       TT_LAUNCH_CHECK();
       return TT_OK;
     }
-    tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)n), kTailThreads, 0, st>>>(tp);
-    TT_LAUNCH_CHECK();
+    {
+      // (the head ran in the score backward's 512-thread workgroups: the loss reduction rides here instead -- only the host reads it)
+      const int fr_on = hosted && ctx->riders->f_wg > 0 ? 1 : 0;
+      tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tp, ctx->riders->f, fr_on);
+      if (fr_on) ctx->riders->f_wg = 0;
+      TT_LAUNCH_CHECK();
+    }
   } else if (wide) {
     // L2-normalise backward, the output layer's data-gradient GEMM and the BN column sums of the last block in one kernel (the
     // weight-gradient GEMM stays the split-K one); column-sum finish + BN backward apply in a second, below

@@ -33,9 +33,11 @@ class GraphedTrainStep:
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
-                 accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None):
+                 accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None, fuse_score_tail: bool = True):
         """defer_long / defer_slabs: the long rows' finish rides in the optimiser's launch and the towers' slab reduction in the
         embedding gradient's (both bit-identical to the separate launches; the arguments exist for that comparison).
+        fuse_score_tail: the score backward waits for the towers' backward, which launches it with its own first kernel's work in
+        the epilogue (one launch fewer where the shapes allow it, bit-identical; independent of defer_riders; not for a sharded task).
         preserve_state: the eager warm-up steps (allocator + first-call paths) are REAL steps on the example batch; with this flag
         everything they change -- weights, Adam moments and step counts, BatchNorm running statistics -- is put back before the
         capture, so a captured loop starts from the state an eager loop starts from (row-sparse tables: only the example batch's
@@ -56,6 +58,7 @@ class GraphedTrainStep:
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
         self._defer_long, self._defer_slabs, self._defer_riders = bool(defer_long), bool(defer_slabs), bool(defer_riders)
+        self._fuse_score_tail = bool(fuse_score_tail)
         dev = example_batch["notice"]["dense"].device
         self.static = {side: {"dense": example_batch[side]["dense"].clone(),
                               "kjt": KeyedJaggedTensor(example_batch[side]["kjt"].keys(), example_batch[side]["kjt"].values().clone())}
@@ -252,9 +255,14 @@ class GraphedTrainStep:
         # in the chain).  A sharded task's exchange reads the plan at once: only the loss reduction rides there (and not under SyncBN,
         # whose tail kernels run in two phases with a collective between them)
         riders = self._defer_riders and self._ingest is not None and (ex is None or not getattr(self.task, "sync_bn", False))
+        # the score backward waits in the context for the towers' backward (TT_OPT_FUSE_SCORE_TAIL): nothing but the library touches
+        # d_emb between the two.  A sharded task scales d_emb by 1 / world in between and its score backward is rectangular: off
+        fuse = self._fuse_score_tail and ex is None
         for t, _, sh in self._shadows:                 # the hand-over launch in front of this step has refreshed them
             t._w16 = (sh[0], sh[1:])
         try:
+            if fuse:
+                L.set_fuse_score_tail(dev, True)
             if riders:
                 L.set_defer_riders(dev, True, loss_only=ex is not None)
             res = self.task(self.static, return_metrics=self.return_metrics)
@@ -275,6 +283,8 @@ class GraphedTrainStep:
         finally:
             for t, _, _ in self._shadows:
                 t._w16 = None
+            if fuse:
+                L.set_fuse_score_tail(dev, False)      # (launches a score backward nobody hosted: a backward that never reached the towers)
             if riders:
                 L.set_defer_riders(dev, False)         # (launches what nobody hosted: e.g. the loss reduction of a forward-only pass)
             for st in stores:
