@@ -54,11 +54,12 @@ int tt_ctx_num_cus(const tt_ctx* ctx);
  * captured step is the step's launch count (collectives and the caller's own kernels are not in it); a measurement aid */
 uint64_t tt_launch_count(void);
 
-/* Options of a context.  TT_OPT_DEFER_SLAB_REDUCE (default 0): tt_towers_mlp_bwd's one-launch first-block backward leaves the
- * split-K slab reduction of its weight gradients queued in the context instead of launching it; the next tt_embed_grad_bwd
- * with TT_GRAD_PLANNED runs it in the first workgroups of its own launch (the two are independent: one launch fewer in the
- * step's dependent chain); tt_flush_deferred launches it on its own, and the tt_adam_* entries do that themselves before
- * they read a gradient.  Nothing else may write the towers' workspace while tt_deferred_pending() is 1. */
+/* Options of a context.  Three of them make an entry leave a launch QUEUED in the context instead of issuing it; one rule holds for
+ * all three (tt_flush_deferred below states it: who launches what is still queued, on which stream, exactly once).
+ * TT_OPT_DEFER_SLAB_REDUCE (default 0): tt_towers_mlp_bwd's one-launch first-block backward queues the split-K slab reduction of
+ * its weight gradients; the next tt_embed_grad_bwd with TT_GRAD_PLANNED runs it in the first workgroups of its own launch (the two
+ * are independent: one launch fewer in the step's dependent chain).  Nothing else may write the towers' workspace while bit 0 of
+ * tt_deferred_pending() is set. */
 #define TT_OPT_DEFER_SLAB_REDUCE 1
 /* TT_OPT_KEYED_PARTS (default 0 = chosen from the batch size): workgroups per key of tt_dedup_plan_keyed* -- every value gives
  * the same plan bit for bit (tests vary it).  TT_OPT_SCORE_BWD_ROWS_MIN (default 32768): number of rows from which
@@ -67,16 +68,15 @@ uint64_t tt_launch_count(void);
 #define TT_OPT_KEYED_PARTS 2
 #define TT_OPT_SCORE_BWD_ROWS_MIN 3
 /* TT_OPT_DEFER_RIDERS (default 0; 1 or 3 = both riders, 2 = only the loss reduction -- a caller that reads the plan right after
- * building it, as the sharded exchange does): tt_dedup_plan_keyed* leaves the plan's compaction, and tt_score_fwd_sym_* its last reduction
- * (loss_out / out8), QUEUED in the context instead of launching them: tt_towers_mlp_fwd / tt_towers_mlp_bwd run them in an extra
- * grid row of their fused tail kernels (two launches fewer in the step's dependent chain; same bodies: bit-identical), and
- * tt_flush_deferred, tt_embed_grad_bwd, tt_embed_grad_finish and the tt_adam_* entries launch whatever is still queued.  Until
- * then the plan's unique_rows / seg_offsets / n_unique and the forward's loss_out / out8 are NOT written: for callers that run
- * the whole step back to back (GraphedTrainStep); tt_deferred_pending() covers the queue.  With the compaction queued, the plan's
+ * building it, as the sharded exchange does): tt_dedup_plan_keyed* queues the plan's compaction, and tt_score_fwd_sym_* its last reduction
+ * (loss_out / out8): tt_towers_mlp_fwd / tt_towers_mlp_bwd run them in an extra grid row of their fused tail kernels (two launches
+ * fewer in the step's dependent chain; same bodies: bit-identical).  Until they have run, the plan's unique_rows / seg_offsets /
+ * n_unique and the forward's loss_out / out8 are NOT written.  With the compaction queued, the plan's
  * SORT waits in the queue too: tt_towers_mlp_fwd issues it behind its front kernel and in front of the fused tail, with one
  * workgroup per tower in its grid that finishes the BatchNorm batch statistics once (the tail's workgroups then read the finished
- * mean / rstd instead of merging the chunk partials each; same merge order: bit-identical); towers without the fused narrow tail leave
- * it to the same flush as the compaction.  `rows` must stay valid and unchanged until then. */
+ * mean / rstd instead of merging the chunk partials each; same merge order: bit-identical); towers without the fused narrow tail
+ * host neither.  `rows` must stay valid and unchanged until the sort has run.  A second queueing call launches the older occupant
+ * first. */
 #define TT_OPT_DEFER_RIDERS 4
 /* TT_OPT_FP8_GRAD (default 1): tt_score_bwd_fp8 forms the gradient products dA = W B from e4m3 operands as well (softmax weights
  * block-scaled per row and 32 consecutive b rows, the diagonal weight kept apart in f32: tt_score_bwd_fp8 below); 0 = bf16 weights and bf16
@@ -105,10 +105,8 @@ uint64_t tt_launch_count(void);
  * the row chunks are 64 rows each (chunk x = rows 64 x .. 64 x + 63, the score workgroup's rows), it is called on the stream the
  * score backward was queued on and its d_emb[t] are exactly the queued dA of direction t.  A loss reduction queued under
  * TT_OPT_DEFER_RIDERS then rides the tail's second launch.  Otherwise tt_towers_mlp_bwd launches the queued score backward on its own
- * in front of itself.  Until then dA is NOT written.  tt_flush_deferred, tt_embed_grad_bwd, tt_embed_grad_finish, the tt_adam_* /
- * tt_rowwise_adagrad_* entries, another queueing tt_score_bwd_bf16 and setting this option to 0 launch a score backward that is
- * still queued (always on the stream it was queued on); tt_deferred_pending() shows it as bit 2.  A queued launch runs exactly
- * once.  For callers that run the whole step back to back (GraphedTrainStep). */
+ * in front of itself.  Until then dA is NOT written.  Another queueing tt_score_bwd_bf16 and setting this option to 0 also launch a
+ * score backward that is still queued. */
 #define TT_OPT_FUSE_SCORE_TAIL 10
 int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value);
 /* Device-side errors.  A kernel that cannot complete its contract without hanging or faulting the GPU (a tile of a chained
@@ -131,10 +129,22 @@ int tt_ctx_check_device_errors(tt_ctx* ctx, tt_stream stream);
  * Reference counterpart: none (torch.compile(mode="reduce-overhead") replays one step per launch, scripts/train.py:223-225). */
 int tt_handover_retarget(tt_ctx* ctx, void* graph_exec, void* node);
 int tt_handover_captured_node(tt_ctx* ctx, void** node);
+/* What the three queueing options (TT_OPT_DEFER_SLAB_REDUCE, TT_OPT_DEFER_RIDERS, TT_OPT_FUSE_SCORE_TAIL) leave in the context
+ * runs exactly once: inside the launch of the entry that hosts it (named at each option), or on its own at the first of these
+ * flush points -- tt_flush_deferred (everything); tt_embed_grad_bwd (everything; the slab reduction inside its own launch on a
+ * planned workspace); every tt_adam_* / tt_rowwise_adagrad_* entry (everything, before it reads a gradient); tt_towers_mlp_bwd (a score
+ * backward it cannot host).  Order: score backward, the plan's sort, its compaction and the loss reduction (one launch when they
+ * leave together), slab reduction.  Streams: a queued launch runs on the stream of the call that QUEUED it, whoever flushes it, and
+ * an entry hosts it only when called on that stream (otherwise it is launched on its own stream first) -- its inputs are ordered
+ * there.  The `stream` argument of the two calls below therefore does not choose where queued work runs; it is kept for the ABI.
+ * Switching TT_OPT_DEFER_SLAB_REDUCE or TT_OPT_DEFER_RIDERS off launches nothing by itself (call tt_flush_deferred);
+ * TT_OPT_FUSE_SCORE_TAIL = 0 launches a queued score backward.  For callers that run the whole step back to back
+ * (GraphedTrainStep). */
 int tt_flush_deferred(tt_ctx* ctx, tt_stream stream);
 /* only the queued slab reduction (the one thing that lives in the caller's shared scratch buffer) */
 int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream stream);
-/* bit 0: a slab reduction is queued; bit 1: riders (TT_OPT_DEFER_RIDERS) are queued; bit 2: a score backward (TT_OPT_FUSE_SCORE_TAIL) */
+/* bit 0: a slab reduction is queued; bit 1: the plan's sort / compaction or the loss reduction (TT_OPT_DEFER_RIDERS); bit 2: a score
+ * backward (TT_OPT_FUSE_SCORE_TAIL) */
 int tt_deferred_pending(const tt_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------

@@ -343,7 +343,8 @@ class handover_retarget:
 
 
 def flush_deferred(device: torch.device):
-    """Launch a queued slab reduction now (no-op when nothing is queued)."""
+    """Launch everything the context still holds queued -- a score backward, the keyed plan's sort and compaction, the loss reduction,
+    the slab reduction, in that order, each on the stream it was queued on (no-op when nothing is queued)."""
     lib = load()
     c = ctx(device)
     if lib.tt_deferred_pending(c):

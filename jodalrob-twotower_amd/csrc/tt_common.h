@@ -30,19 +30,10 @@ struct tt_ctx {
   size_t lds_per_block;
   unsigned long long* lookup_stamps;   // optional device ring (tt_embed_lookup_set_profile)
   int lookup_stamp_slots;
-  // TT_OPT_DEFER_SLAB_REDUCE: tt_towers_mlp_bwd leaves the split-K slab reduction of its weight gradients queued here; the
-  // next tt_embed_grad_bwd on a planned workspace runs it inside its own launch, tt_flush_deferred / the Adam entries otherwise
-  int defer_slab_reduce;
-  struct TnPending* deferred;
+  struct tt_deferred* dq;   // the step's queued launches and the three options that queue them (tt_deferred.h)
   int keyed_parts;          // TT_OPT_KEYED_PARTS: workgroups per key of the keyed dedup plan (0 = chosen from the batch)
   int score_bwd_rows_min;   // TT_OPT_SCORE_BWD_ROWS_MIN: rows from which tt_score_bwd_bf16 takes the workgroup-staged form
-  int defer_riders;         // TT_OPT_DEFER_RIDERS, as a mask: 1 plan compaction, 2 score loss reduction queue in `riders` (tt_riders.h)
   int fp8_grad;             // TT_OPT_FP8_GRAD: tt_score_bwd_fp8 forms the gradient products from e4m3 operands too (default 1)
-  struct tt_riders* riders;
-  // TT_OPT_FUSE_SCORE_TAIL: tt_score_bwd_bf16 leaves its launch queued here (score_q, allocated on first use) when the towers'
-  // backward can run it with the backward head in its epilogue (tt_tail_bwd.h)
-  int fuse_score_tail;
-  struct ScoreBwdQueued* score_q;
   float* bn_fin;            // [TT_MAX_SIDES][2][64]: the towers' finished BatchNorm batch statistics (mean, rstd) of the step in flight,
                             // written by the statistics riders in the keyed sort's launch and read by tail_fwd (tt_riders.h)
   // chained single-launch scans (segment heads, owner routing): small device buffers that are all-zero between launches -- word 0

@@ -1,11 +1,10 @@
 // Context, error string, ABI version.
 #include "tt_common.h"
-#include "tt_gemm.h"
-#include "tt_riders.h"
-#include "tt_tail_bwd.h"
+#include "tt_deferred.h"
 
 #include <mutex>
 
+#include <stdlib.h>
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -29,15 +28,70 @@ uint32_t* tt_chain_for(tt_ctx* ctx, hipStream_t stream) {
   return ctx->chain + (size_t)(ctx->chain_used++) * kChainWords;
 }
 
-int tt_riders_flush(tt_ctx* ctx, hipStream_t st) {
-  if (int rc = tt_score_bwd_flush(ctx)) return rc;       // a score backward nobody hosted (TT_OPT_FUSE_SCORE_TAIL): whoever flushes may read d_emb
-  if (!ctx || !ctx->riders) return TT_OK;
-  if (ctx->riders->s_on)                                 // a sort nobody hosted: in front of its compaction, no statistics riders
-    if (int rc = tt_keyed_sort_launch(ctx, st, nullptr, 0)) return rc;
-  if (ctx->riders->c_wg == 0 && ctx->riders->f_wg == 0) return TT_OK;
-  riders_kernel<<<ctx->riders->c_wg + ctx->riders->f_wg, kRiderThreads, 0, st>>>(*ctx->riders);
-  ctx->riders->c_wg = ctx->riders->f_wg = 0;
-  TT_LAUNCH_CHECK();
+// ---- the step's queued launches (tt_deferred.h) ----
+int tt_deferred_flush(tt_ctx* ctx, int mask) {
+  if (!ctx) return TT_OK;
+  tt_deferred& q = *ctx->dq;
+  mask &= q.on; q.on &= ~mask;
+  if (mask & TT_DQ_SCORE_BWD)
+    if (int rc = tt_score_bwd_run(q.score, q.st[0])) return rc;
+  if (mask & TT_DQ_SORT)                                 // in front of its compaction, no statistics riders
+    if (int rc = tt_keyed_sort_run(q.sort, q.st[1], nullptr, 0)) return rc;
+  // compaction and loss reduction: one launch where they leave together on one stream, one each otherwise
+  const int c_wg = (mask & TT_DQ_COMPACT) ? q.compact_wg : 0, f_wg = (mask & TT_DQ_LOSS) ? 1 : 0;
+  const bool together = c_wg && f_wg && q.st[2] == q.st[3];
+  if (c_wg) {
+    riders_kernel<<<c_wg + (together ? 1 : 0), kRiderThreads, 0, q.st[2]>>>(tt_riders{q.compact, c_wg, q.loss});
+    TT_LAUNCH_CHECK();
+  }
+  if (f_wg && !together) {
+    riders_kernel<<<1, kRiderThreads, 0, q.st[3]>>>(tt_riders{q.compact, 0, q.loss});
+    TT_LAUNCH_CHECK();
+  }
+  return (mask & TT_DQ_SLABS) ? tt_gemm_tn_flush(q.st[4], &q.slabs) : TT_OK;
+}
+
+int tt_deferred_host(tt_ctx* ctx, int mask, hipStream_t st, int* mine) {
+  const tt_deferred& q = *ctx->dq;
+  *mine = mask & q.on;
+  for (int i = 0; i < kDqSlots; ++i)
+    if ((*mine & (1 << i)) && q.st[i] != st) *mine &= ~(1 << i);
+  return tt_deferred_flush(ctx, mask & ~*mine);
+}
+
+int tt_deferred_queue_score_bwd(tt_ctx* ctx, hipStream_t st, const void* setup, size_t bytes, const float* dA0, const float* dA1, int64_t rows) {
+  tt_deferred& q = *ctx->dq;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;       // (one launch waits at a time)
+  if (!q.score) q.score = malloc(bytes);
+  TT_CHECK_ARG(q.score != nullptr, "queued score backward: out of memory");
+  memcpy(q.score, setup, bytes);
+  q.score_dA[0] = dA0; q.score_dA[1] = dA1; q.score_rows = rows;
+  q.st[0] = st; q.on |= TT_DQ_SCORE_BWD;
+  return TT_OK;
+}
+int tt_deferred_queue_plan(tt_ctx* ctx, hipStream_t st, const KeyedSortQueued& sort, const CompactRider& compact, int compact_wg) {
+  tt_deferred& q = *ctx->dq;
+  if (q.on & TT_DQ_COMPACT)                              // a second plan takes the queue's place, the older one is launched now
+    if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD | TT_DQ_RIDERS)) return rc;
+  q.sort = sort; q.compact = compact; q.compact_wg = compact_wg;
+  q.st[1] = q.st[2] = st; q.on |= TT_DQ_SORT | TT_DQ_COMPACT;
+  return TT_OK;
+}
+int tt_deferred_queue_loss(tt_ctx* ctx, hipStream_t st, const Finish2Rider& loss) {
+  tt_deferred& q = *ctx->dq;
+  if (q.on & TT_DQ_LOSS)
+    if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD | TT_DQ_RIDERS)) return rc;
+  q.loss = loss;
+  q.st[3] = st; q.on |= TT_DQ_LOSS;
+  return TT_OK;
+}
+int tt_deferred_queue_slabs(tt_ctx* ctx, hipStream_t st, TnPending* p) {
+  if (!p || p->n == 0) return TT_OK;
+  tt_deferred& q = *ctx->dq;
+  TT_CHECK_ARG(!(q.on & TT_DQ_SLABS), "deferred slab reduction: the previous one was never flushed");
+  q.slabs = *p;
+  p->n = 0; p->maxtotal = 1;
+  q.st[4] = st; q.on |= TT_DQ_SLABS;
   return TT_OK;
 }
 
@@ -72,16 +126,10 @@ int tt_ctx_create(int device, tt_ctx** out) {
   c->lds_per_block = prop.sharedMemPerBlock;
   c->lookup_stamps = nullptr;
   c->lookup_stamp_slots = 0;
-  c->defer_slab_reduce = 0;
-  c->deferred = nullptr;
+  c->dq = new tt_deferred();
   c->keyed_parts = 0;
   c->score_bwd_rows_min = 32768;
-  c->defer_riders = 0;
-  c->fuse_score_tail = 0;
-  c->score_q = nullptr;
   c->fp8_grad = 1;
-  c->riders = new tt_riders();
-  c->riders->c_wg = c->riders->f_wg = c->riders->s_on = 0;
   c->bn_fin = nullptr;
   c->chain = nullptr;
   c->chain_words = 0;
@@ -103,7 +151,7 @@ int tt_ctx_create(int device, tt_ctx** out) {
     if (e != hipSuccess) {
       tt_set_error("tt_ctx_create: %s", hipGetErrorString(e));
       if (c->chain) (void)hipFree(c->chain);
-      delete c->riders;
+      delete c->dq;
       delete c;
       return TT_ERR_HIP;
     }
@@ -114,9 +162,8 @@ int tt_ctx_create(int device, tt_ctx** out) {
 }
 
 int tt_ctx_destroy(tt_ctx* ctx) {
-  if (ctx && ctx->deferred) tt_gemm_tn_pending_destroy(ctx->deferred);
-  if (ctx) delete ctx->riders;
-  tt_score_bwd_queue_destroy(ctx);
+  if (ctx) free(ctx->dq->score);
+  if (ctx) delete ctx->dq;
   if (ctx && ctx->chain) (void)hipFree(ctx->chain);
   if (ctx && ctx->bn_fin) (void)hipFree(ctx->bn_fin);
   delete ctx;
@@ -126,7 +173,7 @@ int tt_ctx_destroy(tt_ctx* ctx) {
 int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value) {
   TT_CHECK_ARG(ctx != nullptr, "tt_ctx_set_option: NULL context");
   switch (option) {
-    case TT_OPT_DEFER_SLAB_REDUCE: ctx->defer_slab_reduce = value != 0; break;
+    case TT_OPT_DEFER_SLAB_REDUCE: ctx->dq->defer_slabs = value != 0; break;
     case TT_OPT_KEYED_PARTS:
       TT_CHECK_ARG(value >= 0, "tt_ctx_set_option: TT_OPT_KEYED_PARTS needs a value >= 0");
       ctx->keyed_parts = value;
@@ -137,12 +184,12 @@ int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value) {
       break;
     case TT_OPT_DEFER_RIDERS:
       TT_CHECK_ARG(value >= 0 && value <= 3, "tt_ctx_set_option: TT_OPT_DEFER_RIDERS takes 0 .. 3");
-      ctx->defer_riders = value == 1 ? 3 : value;      // 1 = both riders (as 3), 2 = the loss reduction only
+      ctx->dq->defer_riders = value == 1 ? 3 : value;     // 1 = both riders (as 3), 2 = the loss reduction only
       break;
     case TT_OPT_FP8_GRAD: ctx->fp8_grad = value != 0; break;
     case TT_OPT_FUSE_SCORE_TAIL:
-      ctx->fuse_score_tail = value != 0;
-      if (!value) return tt_score_bwd_flush(ctx);        // (on the stream it was queued on)
+      ctx->dq->fuse_score_tail = value != 0;
+      if (!value) return tt_deferred_flush(ctx, TT_DQ_SCORE_BWD);
       break;
     case TT_OPT_CHAINED: ctx->chained = value != 0; break;
     case TT_OPT_LOOKUP_NT: ctx->lookup_nt = value != 0; break;
@@ -192,21 +239,19 @@ int tt_handover_captured_node(tt_ctx* ctx, void** node) {
   return TT_OK;
 }
 
-int tt_flush_deferred(tt_ctx* ctx, tt_stream stream) {
+int tt_flush_deferred(tt_ctx* ctx, tt_stream) {
   TT_CHECK_ARG(ctx != nullptr, "tt_flush_deferred: NULL context");
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
-  return tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream));
+  return tt_deferred_flush(ctx, TT_DQ_ALL);
 }
 
-int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream stream) {
+int tt_flush_deferred_slabs(tt_ctx* ctx, tt_stream) {
   TT_CHECK_ARG(ctx != nullptr, "tt_flush_deferred_slabs: NULL context");
-  return tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream));
+  return tt_deferred_flush(ctx, TT_DQ_SLABS);
 }
 
 int tt_deferred_pending(const tt_ctx* ctx) {
-  if (!ctx) return 0;
-  return ((ctx->deferred && ctx->deferred->n > 0) ? 1 : 0) | ((ctx->riders && (ctx->riders->c_wg > 0 || ctx->riders->f_wg > 0 || ctx->riders->s_on)) ? 2 : 0) |
-         (tt_score_bwd_queued(ctx) ? 4 : 0);
+  const int on = ctx ? ctx->dq->on : 0;
+  return ((on & TT_DQ_SLABS) ? 1 : 0) | ((on & TT_DQ_RIDERS) ? 2 : 0) | ((on & TT_DQ_SCORE_BWD) ? 4 : 0);
 }
 
 int tt_ctx_num_cus(const tt_ctx* ctx) { return ctx ? ctx->num_cus : 0; }

@@ -3,8 +3,7 @@
 // device-side batch gather.  All kernels are HBM-bound byte movers: 64-wide waves, 16-byte lanes,
 // grids capped at 8 workgroups per CU with grid-stride loops.
 #include "tt_common.h"
-#include "tt_gemm.h"
-#include "tt_riders.h"
+#include "tt_deferred.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -2321,14 +2320,8 @@ static int fill_cvt(const char* who, const tt_cvt_list* cvt, CvtDev* v, int64_t*
 }
 
 // ---- optimiser launches ----
-// every optimiser entry starts here, before it looks at its arguments
-int flush_before_optimiser(tt_ctx* ctx, tt_stream stream) {
-  if (int rc = tt_riders_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;       // (a queued plan compaction: its rows are read here)
-  if (ctx && ctx->deferred && ctx->deferred->n > 0)      // a queued slab reduction: the gradients are not complete before it
-    if (int rc = tt_gemm_deferred_flush(ctx, reinterpret_cast<hipStream_t>(stream))) return rc;
-  return TT_OK;
-}
-
+// (every optimiser entry starts with tt_deferred_flush(ctx, TT_DQ_ALL), before it looks at its arguments: a queued compaction's rows
+// are read here, and the gradients are not complete before a queued score backward and slab reduction)
 AdagradK make_adagrad(float lr, float eps, float wd, const float* dev) {
   AdagradK k;
   k.lr = lr; k.eps = eps; k.wd = wd;
@@ -2360,7 +2353,7 @@ int fused_step_impl(tt_ctx* ctx, const char* who, const tt_adam_tensor* tensors,
                            const RULE& rule, float* table, int64_t table_rows, int32_t E, const int32_t* unique_rows, float* grad_rows,
                            const int32_t* n_unique, int64_t M, const int32_t* seg_offsets, void* grad_workspace,
                            size_t grad_workspace_bytes, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && tensors && table && rule_state(rule) && unique_rows && grad_rows && n_unique, "%s: NULL argument", who);
   TT_CHECK_ARG(n_tensors >= 1 && n_tensors <= kAdamMulti, "%s: n_tensors=%d not in [1,%d]", who, n_tensors, kAdamMulti);
   TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 1 && table_rows >= 1, "%s: bad step/E/M/table_rows", who);
@@ -2409,13 +2402,10 @@ int fused_step_impl(tt_ctx* ctx, const char* who, const tt_adam_tensor* tensors,
 
 }  // namespace
 
-int tt_keyed_sort_launch(tt_ctx* ctx, hipStream_t st, const BnFinishRiders* bf, int bf_wg) {
-  if (!ctx || !ctx->riders || !ctx->riders->s_on) return TT_OK;
-  const KeyedSortQueued& q = ctx->riders->s;
+int tt_keyed_sort_run(const KeyedSortQueued& q, hipStream_t st, const BnFinishRiders* bf, int bf_wg) {
   if (!bf || bf_wg < 0 || bf_wg > TT_MAX_SIDES) bf_wg = 0;
   keyed_sort_kernel<<<bf_wg + q.grid, kKeyedThreads, 0, st>>>(q.a, q.rows, q.sorted_src, q.uniq_stage, q.seg_stage, q.ucount, q.ubase, q.uend,
                                                               q.key_major, q.long_counters, bf_wg > 0 ? *bf : BnFinishRiders{}, bf_wg);
-  ctx->riders->s_on = 0;
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -2651,20 +2641,10 @@ static int dedup_plan_keyed_impl(tt_ctx* ctx, const int32_t* rows, const int32_t
   a.parts = parts;
   const KeyedSortQueued sq{a, rows, sorted_src, uniq_stage, seg_stage, ucount, ubase, uend, key_major, pl.counters, n_keys * parts};
   const CompactRider cr{uniq_stage, seg_stage, ucount, ubase, uend, pl, n_keys * parts, slots, unique_rows, seg_offsets, n_unique};
-  if (ctx->defer_riders & 1) {                           // rides beside the towers' tail_fwd (tt_riders.h); a second plan before that
-    if (ctx->riders->c_wg > 0)                           // launch takes the queue's place, the older one is launched now
-      if (int rc = tt_riders_flush(ctx, st)) return rc;
-    // ... and the sort itself waits for the towers' forward, which issues it behind its front kernel with the BatchNorm statistics
-    // riders in its grid (nothing reads the plan before the compaction does)
-    ctx->riders->s = sq;
-    ctx->riders->s_on = 1;
-    ctx->riders->c = cr;
-    ctx->riders->c_wg = n_keys * parts;
-    return TT_OK;
-  }
-  keyed_sort_kernel<<<sq.grid, kKeyedThreads, 0, st>>>(a, rows, sorted_src, uniq_stage, seg_stage, ucount, ubase, uend, key_major,
-                                                       pl.counters, BnFinishRiders{}, 0);
-  TT_LAUNCH_CHECK();
+  // TT_OPT_DEFER_RIDERS: the compaction rides beside the towers' tail_fwd, and the sort itself waits for the towers' forward, which
+  // issues it behind its front kernel with the BatchNorm statistics riders in its grid (nothing reads the plan before the compaction)
+  if (ctx->dq->defer_riders & 1) return tt_deferred_queue_plan(ctx, st, sq, cr, n_keys * parts);
+  if (int rc = tt_keyed_sort_run(sq, st, nullptr, 0)) return rc;
   keyed_compact_kernel<<<n_keys * parts, kKeyedThreads, 0, st>>>(cr);
   TT_LAUNCH_CHECK();
   return TT_OK;
@@ -2744,7 +2724,7 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   }
   GradLayout gl = grad_layout(reinterpret_cast<char*>(workspace), M, E);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = tt_riders_flush(ctx, st)) return rc;      // a plan compaction nobody hosted: this reduction reads its output
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL & ~TT_DQ_SLABS)) return rc;      // nobody hosted them: this reduction reads the plan (and d_emb's products)
   if (planned) {
     // counters and lists were written into THIS workspace by tt_dedup_plan_keyed_long: nothing to zero, nothing to register
   } else if (counters) {
@@ -2755,11 +2735,9 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   }
   // a slab reduction the tower backward left in the context: inside this launch when the workspace is the plan's own (nothing
   // here then writes the shared scratch the slabs live in), launched on its own first otherwise
-  TnPending* slabs = (ctx->deferred && ctx->deferred->n > 0) ? ctx->deferred : nullptr;
-  if (slabs && !planned) {
-    if (int rc = tt_gemm_deferred_flush(ctx, st)) return rc;
-    slabs = nullptr;
-  }
+  int host_slabs = 0;
+  if (int rc = planned ? tt_deferred_host(ctx, TT_DQ_SLABS, st, &host_slabs) : tt_deferred_flush(ctx, TT_DQ_SLABS)) return rc;
+  const TnPending* slabs = host_slabs ? &ctx->dq->slabs : nullptr;
   const int nsx = slabs ? tt_slab_role_blocks_x(slabs) : 0;
   const int g1 = grid_for(ctx, M * LG);
   const int g2 = grid_for(ctx, gl.max_chunks * LG);
@@ -2776,8 +2754,7 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
           a, sorted_src, seg_offsets, unique_rows, n_unique, mode, out, gl.ws, LG, (uint32_t)g1s, slabs->sb, (uint32_t)nsxs,    \
           (uint32_t)slabs->n, (uint32_t)nss);                                                                                   \
       TT_LAUNCH_CHECK();                                                                                                        \
-      slabs->n = 0;                                                                                                             \
-      slabs->maxtotal = 1;                                                                                                      \
+      tt_deferred_taken(ctx, TT_DQ_SLABS);                                                                                      \
       if (!defer) seg_long_finish_kernel<V, false><<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG); \
       break;                                                                                                                    \
     }                                                                                                                           \
@@ -2821,7 +2798,7 @@ void tt_adam_hparams(int64_t step, float lr, float beta1, float beta2, float eps
 
 int tt_adam_dense_step(tt_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1,
                        float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && (n == 0 || (p && g && m && v)), "tt_adam_dense_step: NULL argument");
   TT_CHECK_ARG(step >= 1 && n >= 0, "tt_adam_dense_step: step must be >= 1");
   if (n == 0) return TT_OK;
@@ -2839,7 +2816,7 @@ int tt_adam_dense_step(tt_ctx* ctx, float* p, const float* g, float* m, float* v
 
 int tt_adam_multi_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_tensors, int64_t step, float lr, float beta1,
                        float beta2, float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && (n_tensors == 0 || tensors), "tt_adam_multi_step: NULL argument");
   TT_CHECK_ARG(step >= 1 && n_tensors >= 0, "tt_adam_multi_step: step must be >= 1");
   const AdamK k = make_adam(step, lr, beta1, beta2, eps, weight_decay, hparams_dev);
@@ -2865,7 +2842,7 @@ int tt_adam_multi_step(tt_ctx* ctx, const tt_adam_tensor* tensors, int32_t n_ten
 int tt_sparse_adam_step(tt_ctx* ctx, float* table, float* m, float* v, int64_t table_rows, int32_t E, const int32_t* unique_rows,
                         const float* grad_rows, const int32_t* n_unique, int64_t M, int64_t step, float lr, float beta1, float beta2, float eps,
                         float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && table && m && v, "tt_sparse_adam_step: NULL state");
   TT_CHECK_ARG(step >= 1 && E >= 1 && M >= 0 && table_rows >= 1, "tt_sparse_adam_step: bad step/E/M/table_rows");
   if (M == 0) return TT_OK;
@@ -2885,7 +2862,7 @@ int tt_sparse_adam_step(tt_ctx* ctx, float* table, float* m, float* v, int64_t t
 int tt_rowwise_adagrad_sparse_step(tt_ctx* ctx, float* table, float* sum, int64_t table_rows, int32_t E, const int32_t* unique_rows,
                                    const float* grad_rows, const int32_t* n_unique, int64_t M, float lr, float eps, float weight_decay,
                                    const float* hparams_dev, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && table && sum, "tt_rowwise_adagrad_sparse_step: NULL state");
   TT_CHECK_ARG(E >= 1 && M >= 0 && table_rows >= 1, "tt_rowwise_adagrad_sparse_step: bad E/M/table_rows");
   if (M == 0) return TT_OK;
@@ -2905,7 +2882,7 @@ int tt_rowwise_adagrad_sparse_step(tt_ctx* ctx, float* table, float* sum, int64_
 
 int tt_rowwise_adagrad_dense_step(tt_ctx* ctx, float* table, float* sum, const float* grad, int64_t table_rows, int32_t E, float lr,
                                   float eps, float weight_decay, const float* hparams_dev, tt_stream stream) {
-  if (int rc = flush_before_optimiser(ctx, stream)) return rc;
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;
   TT_CHECK_ARG(ctx && table && sum && grad, "tt_rowwise_adagrad_dense_step: NULL state");
   TT_CHECK_ARG(E >= 1 && table_rows >= 1, "tt_rowwise_adagrad_dense_step: bad E/table_rows");
   const AdagradK k = make_adagrad(lr, eps, weight_decay, hparams_dev);

@@ -156,13 +156,8 @@ __device__ __forceinline__ void slab_reduce_block(const SlabBatch& batch, int bx
 }
 #endif
 
-TnPending* tt_gemm_tn_pending_create();
-void tt_gemm_tn_pending_destroy(TnPending*);
 int tt_gemm_tn_batched(hipStream_t st, const GemmTN* items, int n, TnPending* pending = nullptr);
 int tt_gemm_tn_flush(hipStream_t st, TnPending* pending);
-// move the queue into the context instead of flushing it (tt_ctx.defer_slab_reduce); launch whatever the context holds
-int tt_gemm_tn_defer(tt_ctx* ctx, TnPending* pending);
-int tt_gemm_deferred_flush(tt_ctx* ctx, hipStream_t st);
 
 // First-block backward of up to TT_MAX_SIDES towers in ONE launch (bf16 operands, edge-free shapes): per tower
 //   dW = d_pre^T . x (+ db = column sums of d_pre),  d_x[:, h0:] = d_pre . W[:, h0:],  G = d_pre^T . dense,

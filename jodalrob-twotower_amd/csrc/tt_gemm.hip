@@ -791,22 +791,6 @@ size_t tt_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t R) {
   return sizeof(float) * (size_t)tn_splits(M, N, R) * ((size_t)M * (size_t)N + (size_t)M) + 256;
 }
 
-// (TnPending: tt_gemm.h)
-TnPending* tt_gemm_tn_pending_create() { return new TnPending(); }
-void tt_gemm_tn_pending_destroy(TnPending* p) { delete p; }
-
-int tt_gemm_tn_defer(tt_ctx* ctx, TnPending* p) {
-  if (!p || p->n == 0) return TT_OK;
-  if (!ctx->deferred) ctx->deferred = tt_gemm_tn_pending_create();
-  TT_CHECK_ARG(ctx->deferred->n == 0, "deferred slab reduction: the previous one was never flushed");
-  *ctx->deferred = *p;
-  p->n = 0;
-  p->maxtotal = 1;
-  return TT_OK;
-}
-
-int tt_gemm_deferred_flush(tt_ctx* ctx, hipStream_t st) { return ctx && ctx->deferred ? tt_gemm_tn_flush(st, ctx->deferred) : TT_OK; }
-
 int tt_gemm_tn_flush(hipStream_t st, TnPending* p) {
   if (!p || p->n == 0) return TT_OK;
   int blocks = (int)tt_cdiv(p->maxtotal, THREADS);

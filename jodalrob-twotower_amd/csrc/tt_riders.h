@@ -1,11 +1,10 @@
-// "Riders": two small roles of the training step that depend on nothing the launches around them produce and are worth one launch
+// "Riders": small roles of the training step that depend on nothing the launches around them produce and are worth one launch
 // each in the step's dependent chain (~5 us + a boundary) -- the compaction of the keyed duplicate-row plan (needs every sort
-// workgroup's head count; first consumer: tt_embed_grad_bwd) and the last reduction of the symmetric score forward (loss + metrics:
-// read by the host only).  With TT_OPT_DEFER_RIDERS set on the context, tt_dedup_plan_keyed* / tt_score_fwd_sym_* leave them queued
-// here instead of launching them, and the towers' fused tail kernels (1024-thread workgroups, like both roles) run them in one
-// extra grid row: the compaction beside tail_fwd, the loss reduction beside tail_bwd.  tt_flush_deferred, tt_embed_grad_bwd and the
-// tt_adam_* entries launch whatever is still queued (towers whose shapes do not take the fused tail).  Bodies are shared between the
-// stand-alone kernels and the host kernels, so results are bit-identical (test).
+// workgroup's head count; first consumer: tt_embed_grad_bwd), the last reduction of the symmetric score forward (loss + metrics:
+// read by the host only) and the finish of the towers' BatchNorm batch statistics.  This header holds their argument structs and
+// their device bodies, which the stand-alone kernels and the host kernels (the towers' fused tails, 1024-thread workgroups like
+// every role here; the keyed plan's sort) share, so results are bit-identical (test).  How they are queued, hosted and flushed:
+// tt_deferred.h.
 #pragma once
 #include "tt_common.h"
 
@@ -39,7 +38,7 @@ struct BnFinishRider {
 struct BnFinishRiders { BnFinishRider r[TT_MAX_SIDES]; };
 constexpr int kBnFinStride = 2 * 64;                              // floats per tower in tt_ctx::bn_fin (the narrow tail: H <= 64)
 
-// the keyed plan's sort (keyed_sort_kernel, tt_embed.hip): argument block, and the launch itself while it is held back
+// the keyed plan's sort (keyed_sort_kernel, tt_embed.hip): argument block, and the whole launch (while it is held back: tt_deferred.h)
 struct KeyedArgs {
   int32_t side_base[TT_MAX_SIDES + 1];   // first slot of side i
   int32_t key_base[TT_MAX_SIDES + 1];    // first key instance of side i
@@ -52,12 +51,10 @@ struct KeyedSortQueued {
   KeyedArgs a; const int32_t* rows; int32_t* sorted_src; int32_t* uniq_stage; int32_t* seg_stage; int32_t* ucount; int32_t* ubase;
   int32_t* uend; bool key_major; int32_t* long_counters; int grid;
 };
+// argument block of the two grid-row riders' stand-alone launch (riders_kernel, tt_ctx.hip): c_wg workgroups compact, one more reduces
 struct tt_riders {
-  CompactRider c; int c_wg;        // c_wg > 0: queued, needs that many workgroups
-  Finish2Rider f; int f_wg;
-  // s_on: the sort whose compaction is queued in `c` has not been launched either -- tt_towers_mlp_fwd issues it BEHIND its front
-  // kernel with the statistics riders in its grid (tt_riders_flush launches it, without riders, in front of the compaction)
-  KeyedSortQueued s; int s_on;
+  CompactRider c; int c_wg;
+  Finish2Rider f;
 };
 
 #ifdef __HIPCC__
@@ -274,8 +271,3 @@ __device__ __forceinline__ void finish2_body(const Finish2Rider& fr) {
   }
 }
 #endif
-
-// launches whatever the context still holds (stand-alone kernels); defined in tt_ctx.hip
-int tt_riders_flush(tt_ctx* ctx, hipStream_t st);
-// launches the held-back sort (riders->s_on) with bf_wg statistics riders in front of its grid; defined in tt_embed.hip
-int tt_keyed_sort_launch(tt_ctx* ctx, hipStream_t st, const BnFinishRiders* bf, int bf_wg);

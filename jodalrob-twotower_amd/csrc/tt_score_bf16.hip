@@ -16,6 +16,7 @@
 //   * partial results of the NW waves are combined through LDS in a fixed tree order.
 #include "tt_score_bf16.h"
 #include "tt_tail_bwd.h"
+#include "tt_deferred.h"
 
 #include <stdlib.h>
 
@@ -1665,57 +1666,32 @@ static void launch_tr(const BwdSetup& s, hipStream_t st) {
   tt_dispatch([&](auto u, auto l) { score_bwd_tr_kernel<KS, AT, u, l><<<grid, 512, 0, st>>>(s.a, TailHost<false>{}); }, s.unit, s.lq);
 }
 
-// ---- TT_OPT_FUSE_SCORE_TAIL: a launch_tr<4, 2> launch held back in the context (tt_tail_bwd.h) -----------------------------------
+// ---- TT_OPT_FUSE_SCORE_TAIL: a launch_tr<4, 2> launch held back in the context (slot TT_DQ_SCORE_BWD, tt_deferred.h) --------------
 // Held: two directions over square problems of the same size, no logQ -- what the towers' backward can host.  Launched exactly once:
-// by tt_score_tail_bwd_launch (with the towers' backward head in its epilogue) or by tt_score_bwd_flush (the stand-alone kernel).
-struct ScoreBwdQueued {
-  BwdSetup s;
-  hipStream_t st;
-  bool on = false;
-};
+// by tt_score_tail_bwd_launch (with the towers' backward head in its epilogue) or by tt_deferred_flush (tt_score_bwd_run).
+static_assert(std::is_trivially_copyable<BwdSetup>::value, "the queue keeps a byte copy of BwdSetup");
 
-static bool bwd_queue(tt_ctx* ctx, const BwdSetup& s, hipStream_t st) {
+static bool bwd_hostable(const tt_ctx* ctx, const BwdSetup& s) {
   const DirBwd* d = s.a.d;
-  if (!ctx->fuse_score_tail || s.lq || s.n_dirs != 2 || d[0].Ra != d[0].Rb || d[1].Ra != d[1].Rb || d[0].Ra != d[1].Ra) return false;
-  if (!ctx->score_q) ctx->score_q = new ScoreBwdQueued();
-  ctx->score_q->s = s;
-  ctx->score_q->st = st;
-  ctx->score_q->on = true;
-  return true;
+  return ctx->dq->fuse_score_tail && !s.lq && s.n_dirs == 2 && d[0].Ra == d[0].Rb && d[1].Ra == d[1].Rb && d[0].Ra == d[1].Ra;
 }
 
-int tt_score_bwd_queued(const tt_ctx* ctx) { return ctx && ctx->score_q && ctx->score_q->on ? 1 : 0; }
-
-void tt_score_bwd_queued_outputs(const tt_ctx* ctx, const float** dA, int64_t* rows, hipStream_t* st) {
-  const ScoreBwdQueued& q = *ctx->score_q;
-  dA[0] = q.s.a.d[0].dA;
-  dA[1] = q.s.a.d[1].dA;
-  *rows = q.s.maxRa;
-  *st = q.st;
-}
-
-int tt_score_bwd_flush(tt_ctx* ctx) {
-  if (!tt_score_bwd_queued(ctx)) return TT_OK;
-  ctx->score_q->on = false;
-  launch_tr<4, 2>(ctx->score_q->s, ctx->score_q->st);
+int tt_score_bwd_run(const void* setup, hipStream_t st) {
+  launch_tr<4, 2>(*static_cast<const BwdSetup*>(setup), st);
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
 
 int tt_score_tail_bwd_launch(tt_ctx* ctx, const tttail::Batch<tttail::TailBwdArgs>& tb, bool drop, float p, uint64_t seed,
                              const uint64_t* seed_dev) {
-  TT_CHECK_ARG(tt_score_bwd_queued(ctx), "tt_score_tail_bwd_launch: no score backward is queued");
-  ScoreBwdQueued& q = *ctx->score_q;
-  q.on = false;
-  const dim3 grid((unsigned)tt_cdiv(q.s.maxRa, 64), 2);
-  tt_dispatch([&](auto u) { score_bwd_tr_kernel<4, 2, u, false, true><<<grid, 512, 0, q.st>>>(q.s.a, TailHost<true>{tb, drop, p, seed, seed_dev}); }, q.s.unit);
+  TT_CHECK_ARG(ctx->dq->on & TT_DQ_SCORE_BWD, "tt_score_tail_bwd_launch: no score backward is queued");
+  const BwdSetup& s = *static_cast<const BwdSetup*>(ctx->dq->score);
+  hipStream_t st = ctx->dq->st[0];
+  tt_deferred_taken(ctx, TT_DQ_SCORE_BWD);
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 64), 2);
+  tt_dispatch([&](auto u) { score_bwd_tr_kernel<4, 2, u, false, true><<<grid, 512, 0, st>>>(s.a, TailHost<true>{tb, drop, p, seed, seed_dev}); }, s.unit);
   TT_LAUNCH_CHECK();
   return TT_OK;
-}
-
-void tt_score_bwd_queue_destroy(tt_ctx* ctx) {
-  if (ctx) delete ctx->score_q;
-  if (ctx) ctx->score_q = nullptr;
 }
 
 // workgroup-staged form (score_bwd_rows_kernel); FP8: fp8 S operands (no logQ form)
@@ -1762,8 +1738,9 @@ static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bw
   } else if (Dp == 32) {
     launch_bsplit<2, 2, 8, false>(s, st);
   } else if (Dp == 64) {
-    if (int rc = tt_score_bwd_flush(ctx)) return rc;      // (one launch waits at a time)
-    if (bwd_queue(ctx, s, st)) return TT_OK;              // TT_OPT_FUSE_SCORE_TAIL: tt_towers_mlp_bwd launches it, or a flush
+    if (bwd_hostable(ctx, s))                             // TT_OPT_FUSE_SCORE_TAIL: tt_towers_mlp_bwd launches it, or a flush
+      return tt_deferred_queue_score_bwd(ctx, st, &s, sizeof(s), s.a.d[0].dA, s.a.d[1].dA, s.maxRa);
+    if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;      // (a queued one goes in front of this launch)
     launch_tr<4, 2>(s, st);
   } else if (Dp == 128) {                                 // the one-image form, one a tile per workgroup
     launch_tr<8, 1>(s, st);

@@ -19,7 +19,7 @@
 // sum of all scores (negative_similarity_mean): sum_ab n_a . c_b = (sum_a n_a) . (sum_b c_b) -- finish1 adds the operand
 // images' columns instead of the kernel adding 67 M products.
 #include "tt_score_bf16.h"
-#include "tt_riders.h"
+#include "tt_deferred.h"
 
 #include <stdlib.h>
 
@@ -666,13 +666,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
     fr.part = part2;
     fr.n_wg = n2;
   }
-  if (ctx->defer_riders & 2) {                           // rides beside the towers' tail_bwd (tt_riders.h): nothing on the device reads it
-    if (ctx->riders->f_wg > 0)
-      if (int rc = tt_riders_flush(ctx, st)) return rc;
-    ctx->riders->f = fr;
-    ctx->riders->f_wg = 1;
-    return TT_OK;
-  }
+  if (ctx->dq->defer_riders & 2) return tt_deferred_queue_loss(ctx, st, fr);      // rides beside the towers' tail_bwd: nothing on the device reads it
   score_sym_finish2_kernel<<<1, kRiderThreads, 0, st>>>(fr);
   TT_LAUNCH_CHECK();
   return TT_OK;

@@ -284,14 +284,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
 
 }  // namespace tttail
 
-// ---- the score backward held back for the towers' backward (TT_OPT_FUSE_SCORE_TAIL; tt_score_bf16.hip) ----------------------------
-// 1 while a tt_score_bwd_bf16 launch waits in the context
-int tt_score_bwd_queued(const tt_ctx* ctx);
-// the queued launch's gradient buffers (dA of its two directions), rows per direction and stream
-void tt_score_bwd_queued_outputs(const tt_ctx* ctx, const float** dA, int64_t* rows, hipStream_t* st);
-// launches the queued score backward on its own (the stand-alone kernel, on the stream it was queued on); no-op when nothing waits
-int tt_score_bwd_flush(tt_ctx* ctx);
-// the queued score backward and the towers' backward head as ONE launch (score_bwd_tr_kernel<4, 2, UNIT, false, true>); empties the queue
+// ---- the score backward held back for the towers' backward (TT_OPT_FUSE_SCORE_TAIL; slot TT_DQ_SCORE_BWD of tt_deferred.h) ---------
+// it and the towers' backward head as ONE launch (score_bwd_tr_kernel<4, 2, UNIT, false, true>, tt_score_bf16.hip) on its stream; takes the slot
 int tt_score_tail_bwd_launch(tt_ctx* ctx, const tttail::Batch<tttail::TailBwdArgs>& tb, bool drop, float p, uint64_t seed,
                              const uint64_t* seed_dev);
-void tt_score_bwd_queue_destroy(tt_ctx* ctx);

@@ -1,8 +1,7 @@
 // Tower MLP (BaseTower.forward after the lookup, and its backward): Linear layers on the f32 MFMA
 // GEMM tiles of tt_gemm.hip, BatchNorm1d statistics as deterministic two-stage column reductions,
 // ReLU / BN / dropout / L2-normalise as fused elementwise and row-wise kernels.
-#include "tt_gemm.h"
-#include "tt_riders.h"
+#include "tt_deferred.h"
 #include "tt_tail_bwd.h"
 
 namespace {
@@ -1676,9 +1675,11 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
           tf.a[t].pk_scale = A[t]->emb_pack_scale == 0.f ? 1.f : A[t]->emb_pack_scale;
         }
       bool fin = false;
-      if (ctx->riders->s_on) {
-        // the keyed plan's sort has been held back for this place (TT_OPT_DEFER_RIDERS): behind the front kernel, with one workgroup
-        // per tower in its grid that finishes the chunk statistics once -- the tail then reads 2 * H floats per workgroup
+      int mine = 0;                                     // of the keyed plan (TT_OPT_DEFER_RIDERS): what this call hosts
+      if (int rc = tt_deferred_host(ctx, TT_DQ_SORT | TT_DQ_COMPACT, st, &mine)) return rc;
+      if (mine & TT_DQ_SORT) {
+        // the keyed plan's sort has been held back for this place: behind the front kernel, with one workgroup per tower in its
+        // grid that finishes the chunk statistics once -- the tail then reads 2 * H floats per workgroup
         BnFinishRiders bf{};
         fin = phase == 0 && ctx->bn_fin != nullptr;       // (SyncBN's second half merges rank triples: in the tail, as before)
         for (int t = 0; t < n && fin; ++t) {
@@ -1687,14 +1688,14 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
                                   ctx->bn_fin + t * kBnFinStride};
           tf.a[t].fin = bf.r[t].out;
         }
-        if (int rc = tt_keyed_sort_launch(ctx, st, &bf, fin ? n : 0)) return rc;
+        if (int rc = tt_keyed_sort_run(ctx->dq->sort, st, &bf, fin ? n : 0)) return rc;
       }
-      const int cr_wg = ctx->riders->c_wg;               // a queued plan compaction rides in one extra grid row
+      const int cr_wg = (mine & TT_DQ_COMPACT) ? ctx->dq->compact_wg : 0;      // a queued plan compaction rides in one extra grid row
       const int64_t gx = tt_cdiv(B, 64) > cr_wg ? tt_cdiv(B, 64) : cr_wg;
       const dim3 grid((unsigned)gx, (unsigned)(n + (cr_wg > 0 ? 1 : 0)));
-      if (fin) tail_fwd_kernel<true><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->riders->c, cr_wg);
-      else tail_fwd_kernel<false><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->riders->c, cr_wg);
-      ctx->riders->c_wg = 0;
+      if (fin) tail_fwd_kernel<true><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->dq->compact, cr_wg);
+      else tail_fwd_kernel<false><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->dq->compact, cr_wg);
+      tt_deferred_taken(ctx, mine);
       TT_LAUNCH_CHECK();
       return TT_OK;
     }
@@ -1801,7 +1802,7 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   }
   // a score backward held back for this pass (TT_OPT_FUSE_SCORE_TAIL) writes d_emb: only the fused narrow tail can host it (below)
   if (!(fused && phase == 0))
-    if (int rc = tt_score_bwd_flush(ctx)) return rc;
+    if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
   if (!fused && !wide && phase != 2) {
     if (!launch_l2norm_fast<true>(st, na, n, B)) l2norm_bwd_kernel<<<dim3((unsigned)tt_cdiv(B, 4), (unsigned)n), kThreads, 0, st>>>(na);
     TT_LAUNCH_CHECK();
@@ -1819,10 +1820,7 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   }
   for (int t = 0; t < n; ++t) tn[t].bf16 = nn[t].bf16 = P[0]->compute_dtype == TT_BF16;
   // the slab reductions of all weight-gradient GEMMs run as ONE launch at the end (nothing in this pass reads them)
-  struct PendingGuard {
-    TnPending* p = tt_gemm_tn_pending_create();
-    ~PendingGuard() { tt_gemm_tn_pending_destroy(p); }
-  } pend;
+  TnPending pend;
   if (fused) {
     // L2-normalise backward, both output-layer GEMMs and the BN column sums of the last block in one kernel; the BN
     // backward apply (after the batch-wide S1 / S2) in a second
@@ -1851,26 +1849,24 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     }
     // a score backward that waits in the context (TT_OPT_FUSE_SCORE_TAIL) runs the head in its own launch when its workgroups
     // are the head's: two towers, H = D = 64, 64-row chunks numbered like its 64-row tiles, its dA exactly d_emb in tower order
+    int mine = 0;                                       // of the score backward and the loss reduction: what is queued on this stream
+    if (int rc = tt_deferred_host(ctx, TT_DQ_SCORE_BWD | TT_DQ_LOSS, st, &mine)) return rc;
     bool hosted = false;
-    if (tt_score_bwd_queued(ctx)) {
-      const float* qd[2];
-      int64_t qrows;
-      hipStream_t qst;
-      tt_score_bwd_queued_outputs(ctx, qd, &qrows, &qst);
-      hosted = phase == 0 && n == 2 && qst == st && qrows == B && qd[0] == d_emb[0] && qd[1] == d_emb[1];
+    if (mine & TT_DQ_SCORE_BWD) {
+      hosted = phase == 0 && n == 2 && ctx->dq->score_rows == B && ctx->dq->score_dA[0] == d_emb[0] && ctx->dq->score_dA[1] == d_emb[1];
       for (int t = 0; hosted && t < n; ++t)
         hosted = tb.a[t].D == 64 && tb.a[t].col.H == 64 && tb.a[t].col.rows_per_chunk == 64 && tb.a[t].col.nchunks == (int)tt_cdiv(B, 64);
       if (hosted) {
         if (int rc = tt_score_tail_bwd_launch(ctx, tb, drop, dropout_p, seed, seed_dev)) return rc;
-      } else if (int rc = tt_score_bwd_flush(ctx)) {
+      } else if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) {
         return rc;
       }
     }
+    const int fr_on = (mine & TT_DQ_LOSS) ? 1 : 0;       // a queued loss reduction rides in one extra grid row of one of the two launches
     if (phase != 2 && !hosted) {
-      const int fr_on = ctx->riders->f_wg > 0 ? 1 : 0;    // a queued loss reduction rides in one extra grid row
-      tail_bwd_kernel<<<dim3((unsigned)cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev, ctx->riders->f,
+      tail_bwd_kernel<<<dim3((unsigned)cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev, ctx->dq->loss,
                                                                                            fr_on);
-      ctx->riders->f_wg = 0;
+      tt_deferred_taken(ctx, TT_DQ_LOSS & mine);
       TT_LAUNCH_CHECK();
     }
     if (phase == 1) {                                   // SyncBN: hand this rank's column sums to the caller and stop
@@ -1882,9 +1878,9 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     }
     {
       // (the head ran in the score backward's 512-thread workgroups: the loss reduction rides here instead -- only the host reads it)
-      const int fr_on = hosted && ctx->riders->f_wg > 0 ? 1 : 0;
-      tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tp, ctx->riders->f, fr_on);
-      if (fr_on) ctx->riders->f_wg = 0;
+      const int fr_here = hosted ? fr_on : 0;
+      tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)(n + fr_here)), kTailThreads, 0, st>>>(tp, ctx->dq->loss, fr_here);
+      if (fr_here) tt_deferred_taken(ctx, TT_DQ_LOSS);
       TT_LAUNCH_CHECK();
     }
   } else if (wide) {
@@ -1905,10 +1901,10 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
       }
       tail_bwd_wide_kernel<<<dim3((unsigned)cmax, (unsigned)n), kWideBwdThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev);
       TT_LAUNCH_CHECK();
-      if (int rc = tt_gemm_tn_batched(st, tn, n, pend.p)) return rc;
+      if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
     }
   } else if (phase != 2) {
-    if (int rc = tt_gemm_tn_batched(st, tn, n, pend.p)) return rc;
+    if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
     if (int rc = tt_gemm_nn_batched(st, nn, n)) return rc;
   }
   for (int i = nh - 1; i >= 0; --i) {
@@ -1950,7 +1946,7 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
         TT_LAUNCH_CHECK();
       }
       if (phase == 1) {                                 // SyncBN on the separate kernels: hand this rank's column sums out and stop
-        if (int rc = tt_gemm_tn_flush(st, pend.p)) return rc;     // (the output layer's weight-gradient slabs)
+        if (int rc = tt_gemm_tn_flush(st, &pend)) return rc;     // (the output layer's weight-gradient slabs)
         Batch<LocalArgs> la{};
         for (int t = 0; t < n; ++t) la.a[t] = LocalArgs{cb.a[t].partial, cb.a[t].nchunks, cb.a[t].H, G[t]->s_sync_local};
         tail_local_colsum_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(la);
@@ -1999,12 +1995,12 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
         gb[t].w16 = P[t]->w_bf16[0];
       }
       if (ok && tt_gemm_back_supported(gb, n)) {
-        if (int rc = tt_gemm_back_batched(st, gb, n, pend.p)) return rc;
-        if (ctx->defer_slab_reduce) return tt_gemm_tn_defer(ctx, pend.p);     // rides in tt_embed_grad_bwd's launch
-        return tt_gemm_tn_flush(st, pend.p);
+        if (int rc = tt_gemm_back_batched(st, gb, n, &pend)) return rc;
+        if (ctx->dq->defer_slabs) return tt_deferred_queue_slabs(ctx, st, &pend);     // rides in tt_embed_grad_bwd's launch
+        return tt_gemm_tn_flush(st, &pend);
       }
     }
-    if (int rc = tt_gemm_tn_batched(st, tn, n, pend.p)) return rc;
+    if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
     if (int rc = tt_gemm_nn_batched(st, nn, n)) return rc;
   }
   // dense projection: d_x[:, 0:h0]
@@ -2016,10 +2012,10 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     tn[t].a_bf16 = P[t]->dx_dtype == TT_BF16;
   }
   for (int t = 0; t < n; ++t) tn[t].bf16 = P[0]->compute_dtype == TT_BF16;
-  if (int rc = tt_gemm_tn_batched(st, tn, n, pend.p)) return rc;
+  if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
   // (not deferred like the one-launch first-block backward above: at these widths the slabs are HBM traffic, not launch
   //  latency -- measured 0.508 ms per step either way at scripts/train.py's [512, 256] -> 128)
-  return tt_gemm_tn_flush(st, pend.p);
+  return tt_gemm_tn_flush(st, &pend);
 }
 
 int tt_tower_mlp_fwd(tt_ctx* ctx, const tt_tower_params* p, const tt_tower_acts* a, int64_t B, int32_t train, float dropout_p,
