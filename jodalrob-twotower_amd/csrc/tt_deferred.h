@@ -49,7 +49,7 @@ int tt_deferred_queue_score_bwd(tt_ctx* ctx, hipStream_t st, const void* setup, 
 int tt_deferred_queue_plan(tt_ctx* ctx, hipStream_t st, const KeyedSortQueued& sort, const CompactRider& compact, int compact_wg);
 int tt_deferred_queue_loss(tt_ctx* ctx, hipStream_t st, const Finish2Rider& loss);
 int tt_deferred_queue_slabs(tt_ctx* ctx, hipStream_t st, TnPending* pending);
-// The launchers of the two payloads whose kernels live elsewhere (they know nothing of the queue): keyed_sort_kernel (tt_embed.hip)
+// The launchers of the two payloads whose kernels live elsewhere (they know nothing of the queue): keyed_sort_kernel (tt_plan.hip)
 // with bf_wg statistics riders in front of its grid (bf NULL: none); the stand-alone score backward (tt_score_bf16.hip) from the
 // opaque copy of its arguments
 int tt_keyed_sort_run(const KeyedSortQueued& q, hipStream_t st, const BnFinishRiders* bf, int bf_wg);

@@ -38,7 +38,7 @@ struct BnFinishRider {
 struct BnFinishRiders { BnFinishRider r[TT_MAX_SIDES]; };
 constexpr int kBnFinStride = 2 * 64;                              // floats per tower in tt_ctx::bn_fin (the narrow tail: H <= 64)
 
-// the keyed plan's sort (keyed_sort_kernel, tt_embed.hip): argument block, and the whole launch (while it is held back: tt_deferred.h)
+// the keyed plan's sort (keyed_sort_kernel, tt_plan.hip): argument block, and the whole launch (while it is held back: tt_deferred.h)
 struct KeyedArgs {
   int32_t side_base[TT_MAX_SIDES + 1];   // first slot of side i
   int32_t key_base[TT_MAX_SIDES + 1];    // first key instance of side i

@@ -319,10 +319,11 @@ static bool launch_l2norm_fast(hipStream_t st, const Batch<NormArgs>& na, int n,
   if (D % 64 != 0 || D < 64 || D > 256) return false;
   constexpr int RW = BWD ? 2 : 4;
   const dim3 grid((unsigned)tt_cdiv(B, 4 * RW), (unsigned)n);
-#define TT_L2(NC)                                                                              \
-  do {                                                                                         \
-    if (BWD) l2norm_bwd_fast_kernel<NC, RW><<<grid, kThreads, 0, st>>>(na);                    \
-    else l2norm_fwd_fast_kernel<NC, RW><<<grid, kThreads, 0, st>>>(na);                        \
+  auto launch = [&](auto kernel) { kernel<<<grid, kThreads, 0, st>>>(na); };
+#define TT_L2(NC)                                        \
+  do {                                                   \
+    if (BWD) launch(l2norm_bwd_fast_kernel<NC, RW>);     \
+    else launch(l2norm_fwd_fast_kernel<NC, RW>);         \
   } while (0)
   switch (D / 64) {
     case 1: TT_L2(1); break;

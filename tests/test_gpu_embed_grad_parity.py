@@ -202,6 +202,10 @@ EXACT_CASES = [
     ("w1024-misaligned-general", 14, 200, [1], 1024, "edge", "general", "unplanned", {"misaligned": True}),
     ("w16-ld-odd", 15, 4096, [2, 3], 16, "edge", "general", "unplanned", {"pad_ld": 1}),
     ("w8-ld-odd-bf16-planned", 16, 4096, [1, 2], 8, "edge", "keyed_long", "planned", {"pad_ld": 3, "src_dtype": "bf16"}),
+    # the planned launch with no slab items on the scalar path: two rows of ~65 slots per key (either side of kLongSeg in one
+    # plan; counts 62 / 68 / 70 / 60 and 66 / 64 / 76 / 54), fewer chunk workgroups than kChunkFirst
+    ("w3-keyed-long-vocab2", 33, 130, [1, 1], 3, "uniform", "keyed_long", "planned", {"vocab": 2}),
+    ("w3-keyed-long-vocab2-bf16", 34, 130, [1, 1], 3, "uniform", "keyed_long", "planned", {"vocab": 2, "src_dtype": "bf16"}),
     # sides: up to four of unequal K with K = 1 (the magic = 2^32 - 1 fix-up) and padded rows; batches at the edges
     ("sides4-B1", 17, 1, [3, 1, 5, 2], 8, "uniform", "keyed_long", "planned", {"pad_ld": 4}),
     ("sides4-B63", 18, 63, [1, 4, 1, 2], 4, "uniform", "keyed", "unplanned", {"pad_ld": 4}),

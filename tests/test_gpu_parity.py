@@ -1096,7 +1096,7 @@ def test_dedup_plan_keyed_random_shapes(tt, ctx_option, seed):
     seg = pk.seg_offsets[:U + 1].cpu().numpy()
     assert np.array_equal(seg, np.concatenate([heads, [len(rows)]]))
     if E and pk.grad_ws is not None:                      # the long-row list: every row longer than 64 slots, tiled by 64-slot chunks
-        ws = pk.grad_ws[0].cpu().numpy()                  # layout: grad_layout() in csrc/tt_embed.hip (256-byte aligned regions)
+        ws = pk.grad_ws[0].cpu().numpy()                  # layout: grad_layout() in csrc/tt_grad_ws.h (256-byte aligned regions)
         M = len(rows)
         al = lambda n: (n + 255) // 256 * 256
         max_long = M // 64 + 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # seg_reduce_chunk_slab: role layouts 2 (shipping candidate), 3, 4 and the previous library; rocprofv3 kernel time + step time, one box
-# (tools/probe/libtwotower_layoutN.so / libtwotower_prev.so: measurement builds, -DTT_SEG_LAYOUT=N / the commit before; not kept in the tree)
+# (tools/probe/libtwotower_layoutN.so / libtwotower_prev.so: measurement builds with another order of the roles / the commit before; not kept in the tree)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/r04_b22; mkdir -p $out
 A="--no-extra-legs --no-cpu-baseline --no-h2d"
