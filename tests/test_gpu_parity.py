@@ -203,6 +203,7 @@ def test_real_schema_golden(tt, manifest, schema_real):
 # ------------------------------------------------------------------------------------------- kernels vs oracle
 @pytest.mark.parametrize("E,B,out_dtype", [(32, 257, "f32"), (32, 1024, "bf16"), (8, 33, "f32"), (6, 19, "f32"), (64, 5, "f32")])
 def test_lookup_bit_exact(tt, E, B, out_dtype):
+    """(the full matrix -- every dispatch branch of the lookup, the gather and the hand-over: tests/test_gpu_lookup_handover.py)"""
     from jodalrob_twotower_amd import ops
     rng = np.random.default_rng(E * 1000 + B)
     vocabs = [[12, 300, 7, 5000], [3, 64]]
