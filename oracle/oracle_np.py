@@ -383,6 +383,29 @@ def score_ce_bwd(N, C, S, lse, temperature=1.0, dloss=1.0, q=None, prod_operands
     return W @ C, W.T @ N
 
 
+def score_dir_terms(A, Bm, T, off, sum_a, sum_b):
+    """One direction of the loss of two_tower_train_task.py:99-134 on a rectangular problem: rows a of A [Ra, D] against all rows b
+    of Bm [Rb, D], the positive of row a at column a + off (global in-batch negatives: A holds the local rows, Bm everybody's).
+    With s_ab = <a, b> / T, the fixed shift 1 / T (unit rows) and e_ab = exp(s_ab - shift):
+        W[a, b]   = e_ab (1 / sum_a[a] + 1 / sum_b[b]) - 2 [b == a + off]
+        mag[a, b] = |e_ab (1 / sum_a[a] + 1 / sum_b[b])| + 2 [b == a + off]
+    sum_a [Ra] = sum_b e_ab, sum_b [Rb] = the shifted exp-sum of column b over ALL rows of the other side (the caller's: here
+    only Ra of them are known).  The gradient is dA = k W Bm with k = dloss / (2 B T); mag is the weights' size before the
+    cancellation on the positive, for error bounds (at one row, w = 1 + 1 - 2 = 0 but mag = 4).  Returns (W, mag).
+    On a square problem with off = 0 and its own sums, k W Bm is score_ce_bwd's dN."""
+    A, Bm = np.asarray(A), np.asarray(Bm)
+    Ra, Rb = A.shape[0], Bm.shape[0]
+    t = A.dtype.type(T)
+    E = np.exp((A @ Bm.T) / t - 1 / t)
+    W = E * (1 / np.asarray(sum_a, dtype=A.dtype)[:, None] + 1 / np.asarray(sum_b, dtype=A.dtype)[None, :])
+    mag = np.abs(W)
+    pos = np.arange(Ra) + off
+    ok = (pos >= 0) & (pos < Rb)
+    W[np.arange(Ra)[ok], pos[ok]] -= 2
+    mag[np.arange(Ra)[ok], pos[ok]] += 2
+    return W, mag
+
+
 def score_operands_fp8(N, C, temperature=1.0):
     """The S-product operands of the fp8 score kernels: fp8(64 * scale * x) / (64 * scale), scale = 1/T * log2(e) on the
     notice side and 1 on the company side (tt_score_pack2_fp8); the products are formed through f32 first, as the pack kernel does."""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import _score_forms as F
 import oracle_np as O
 from conftest import GOLD, load_case, split_prefix
 from params_init import init_state_numpy, synth_batch_numpy
@@ -452,6 +453,14 @@ def test_score_bf16_path_vs_oracle(tt):
         for got, ref in ((tn.grad, dN), (tc.grad, dC)):
             g = got.cpu().numpy().astype(np.float64)
             assert np.linalg.norm(g - ref) <= 1e-2 * np.linalg.norm(ref), (B, D, np.linalg.norm(g - ref) / np.linalg.norm(ref))
+        # per element, the derived bar of tests/test_gpu_score_bf16_forms.py: the unrounded f64 weights on the backward's own sums
+        # (the forward kernel again on the same images: the same bits as the sums autograd saved)
+        grp = F.Group(B, B, 0, D, T, True)
+        rs, cs = ops.score_fwd_bf16(*ops.score_pack2_bf16(tn.detach(), tc.detach(), sn, 1.0), B, D, 1.0 / T, 1.0 / T, True, True, sn)[:2]
+        rs, cs = rs.cpu().numpy(), cs.cpu().numpy()
+        for got, (A_, B_, sa, sb) in ((tn.grad, (nb, cb, rs, cs)), (tc.grad, (cb, nb, cs, rs))):
+            ref, magsum = F.grad_reference(grp, A_, B_, sa, sb, float(np.float32((1.0 / T) / (2.0 * B))))
+            assert F.bound_fraction(got.cpu().numpy(), ref, magsum, F.rho(grp)) <= 1.0, (B, D)
         d = np.diagonal(S)[:, None]
         exp_rank = (S > d).sum(1) + ((S == d) & (np.arange(B)[None, :] < np.arange(B)[:, None])).sum(1)
         got_rank = rank.cpu().numpy()
@@ -2163,7 +2172,9 @@ def test_bf16_step_vs_rounded_oracle(tt, schema_real, tmp_path, ctx_option, rows
 
 
 @pytest.mark.parametrize("B,D,T", [(300, 64, 1.0), (129, 16, 0.5), (64, 6, 0.25), (1000, 128, 1.0), (257, 200, 2.0), (2048, 64, 1.0), (70, 32, 1.0),
-                                   (8192, 64, 1.0), (33, 64, 1.0), (1, 8, 1.0), (4100, 64, 0.5)])
+                                   (8192, 64, 1.0), (33, 64, 1.0), (1, 8, 1.0), (4100, 64, 0.5),
+                                   # the square shapes of tests/test_gpu_score_bf16_forms.py: B at the tile edges, D at every padded width
+                                   (31, 8, 0.5), (32, 33, 1.0), (63, 65, 2.0), (65, 129, 1.0), (127, 256, 0.5), (129, 200, 1.0), (257, 32, 2.0)])
 @pytest.mark.parametrize("prescale", [True, False])
 def test_score_sym_forward(tt, B, D, T, prescale):
     """tt_score_fwd_sym_bf16 (every tile of S computed ONCE for both softmax directions) against (a) the two-direction kernel

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import oracle_np as O
+from _score_forms import rank_bracket as _rank_bracket
 from params_init import init_state_numpy, synth_batch_numpy
 from test_gpu_parity import DEV, _rel, tt, make_task, to_batch, load_state, BF16_VS_REFERENCE_BOUNDS  # noqa: F401
 from test_gpu_f32_parity import _tied_pair, _maxrel, _print, _step_vs_oracle, _assert_step
@@ -124,22 +125,6 @@ def _x3_node(n, c, inv_t, sym):
     torch.cuda.synchronize()
     return (float(loss.item()), out8.cpu().numpy(), dN.cpu().numpy(), dC.cpu().numpy(), dg.cpu().numpy(), rs.cpu().numpy(),
             cs.cpu().numpy()) + extra
-
-
-def _rank_bracket(S, M_cols, delta):
-    """per row i of S: f64 counts #{j : s_ij > s_ii + d_i} and #{j : s_ij >= s_ii - d_i}, with exact ties (bitwise equal operand
-    rows M_cols[j] == M_cols[i]: equal scores in every arithmetic) placed by the lower-index rule"""
-    d = np.diagonal(S)[:, None]
-    lo = (S > d + delta[:, None]).sum(1)
-    hi = (S >= d - delta[:, None]).sum(1)
-    groups = {}
-    for j, row in enumerate(M_cols):
-        groups.setdefault(row.tobytes(), []).append(j)
-    for js in groups.values():
-        for i in js:
-            lo[i] += sum(j < i for j in js)      # an exact tie before the positive counts ...
-            hi[i] -= sum(j > i for j in js)      # ... one after it does not
-    return lo, hi
 
 
 @pytest.mark.parametrize("B,D,T", X3_CASES)
