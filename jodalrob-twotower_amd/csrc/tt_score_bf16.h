@@ -56,15 +56,19 @@ constexpr int kFp8ScaleE8M0 = 0x79797979;               // 2^-6 in every byte
 
 inline int fp8_tile_bytes(int Dp) { return Dp * 32; }
 
+// a lane's 32 bytes of one K = 64 step: its 16-byte pieces of part 0 and part 1 lie 1024 bytes apart in every fp8 image (global
+// memory or an LDS stage of it)
+__device__ __forceinline__ i32x8 f8frag_at(const char* q) {
+  const i32x4 lo = *reinterpret_cast<const i32x4*>(q);
+  const i32x4 hi = *reinterpret_cast<const i32x4*>(q + 1024);
+  return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
 template <int K64>
 __device__ __forceinline__ void load_f8frag(const char* __restrict__ rows8, int64_t t, int c, int h, i32x8 (&f)[K64]) {
   const char* p = rows8 + (t * K64 * 4 + h) * 512 + c * 16;          // [(s * 2 + part) * 2 + half][row][16]
 #pragma unroll
-  for (int s = 0; s < K64; ++s) {
-    const i32x4 lo = *reinterpret_cast<const i32x4*>(p + (s * 4) * 512);
-    const i32x4 hi = *reinterpret_cast<const i32x4*>(p + (s * 4 + 2) * 512);
-    f[s] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  }
+  for (int s = 0; s < K64; ++s) f[s] = f8frag_at(p + (s * 4) * 512);
 }
 
 __device__ __forceinline__ f32x16 mfma_f8(const i32x8& a, const i32x8& b, const f32x16& c) {

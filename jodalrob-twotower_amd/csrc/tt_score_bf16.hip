@@ -14,112 +14,13 @@
 //     of the first product, and [tile][k-step][half][d][8] whose 16-B chunks are exactly the B operand of
 //     the second product in the k-permutation the accumulator registers impose.
 //   * partial results of the NW waves are combined through LDS in a fixed tree order.
-#include "tt_score_bf16.h"
+#include "tt_score_bwd_parts.h"
 #include "tt_tail_bwd.h"
 #include "tt_deferred.h"
 
 #include <stdlib.h>
 
 namespace {
-
-using namespace ttscore;
-
-// ---- pack ------------------------------------------------------------------------------------------
-struct PackArgs { const float* X; int64_t R, Rp; __bf16* rows; __bf16* frag; float scale; __bf16* rows_lo; __bf16* frag_lo; };
-struct PackBatch { PackArgs a[2]; };
-
-// X3 (bf16x3 packing): also the lo images, bf16(p - hi) of p = scale x, in the same layout.
-template <bool X3>
-__global__ __launch_bounds__(256) void pack_bf16_kernel(PackBatch batch, int D, int Dp) {
-  const PackArgs& pa = batch.a[blockIdx.y];
-  const float* __restrict__ X = pa.X;
-  const int64_t R = pa.R, Rp = pa.Rp;
-  __bf16* __restrict__ rows = pa.rows;
-  __bf16* __restrict__ frag = pa.frag;
-  const float sc = pa.scale;
-  const int64_t nchunk = Rp * Dp / 8;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < 2 * nchunk; c += stride) {
-    bf16x8 v, vl;
-    if (c < nchunk) {                                   // k-fragment image [t][k-step][half][row in tile][8]
-      const int ci = (int)(c & 31), hh = (int)((c >> 5) & 1);
-      const int64_t q = c >> 6;
-      const int ks = (int)(q % (Dp / 16));
-      const int64_t row = 32 * (q / (Dp / 16)) + ci;
-      const int d0 = 16 * ks + 8 * hh;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float p = (row < R && d0 + j < D) ? X[row * D + d0 + j] * sc : 0.f;
-        v[j] = (__bf16)p;
-        if (X3) vl[j] = (__bf16)sub_nc(p, (float)v[j]);
-      }
-      *reinterpret_cast<bf16x8*>(rows + c * 8) = v;
-      if (X3) *reinterpret_cast<bf16x8*>(pa.rows_lo + c * 8) = vl;
-    } else {                                            // fragment-ordered image [t][s][h][d][8]
-      const int64_t f = c - nchunk;
-      const int d = (int)(f % Dp);
-      const int64_t rest = f / Dp;
-      const int h = (int)(rest & 1), s = (int)((rest >> 1) & 1);
-      const int64_t t = rest >> 2;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int64_t row = 32 * t + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);
-        const float p = (row < R && d < D) ? X[row * D + d] * sc : 0.f;
-        v[j] = (__bf16)p;
-        if (X3) vl[j] = (__bf16)sub_nc(p, (float)v[j]);
-      }
-      *reinterpret_cast<bf16x8*>(frag + f * 8) = v;
-      if (X3) *reinterpret_cast<bf16x8*>(pa.frag_lo + f * 8) = vl;
-    }
-  }
-}
-
-struct DirFwd {
-  const __bf16* a_rows;
-  const __bf16* b_rows;
-  int64_t Ra, Rb, off;
-  float* sumexp;
-  float* diag;
-  int32_t* rank;
-  float* sumscore;
-  int32_t rank_mode;   // 0 none, 1 top-1 flag (rank = 0/1), 2 full rank
-  float c1;            // exponent scale for this direction's products: inv_t * log2(e) / (scale the operand images carry)
-  float unscale;       // product -> s / T
-  float* inv_sumexp;   // optional out: 1 / (the sum as accumulated), the factor the backward kernel multiplies by
-  const __bf16* a_lo;  // bf16x3 operands only: the lo rows images of A and B
-  const __bf16* b_lo;
-};
-struct FwdArgs {
-  DirFwd d[2];
-  float c2, kexp;      // exponent offset (-shift * log2 e); UNIT kernels leave it out of the terms and scale the row sums by 2^c2
-};
-
-struct DirBwd {
-  const __bf16* a_rows;
-  const __bf16* b_rows;
-  const __bf16* b_frag;
-  int64_t Ra, Rb, off;
-  const float* sumexp_a;
-  const float* sumexp_b;
-  float* dA;
-  float c1;            // as DirFwd::c1
-  float out_scale;     // scale / (the B image's scale)
-  const float* inv_a;  // optional: DirFwd::inv_sumexp of the A rows / of the B rows (then no reciprocals in the tile loop)
-  const float* inv_b;
-  const char* b_frag8;  // fp8 packing only: the B rows' fp8 fragment image (score_bwd_rows8_kernel)
-  const __bf16* a_lo;   // bf16x3 operands only: the lo images (rows of A, rows and fragment image of B)
-  const __bf16* b_lo;
-  const __bf16* b_frag_lo;
-};
-struct BwdArgs {
-  DirBwd d[2];
-  float c2, kexp;
-  const float* d_loss;
-  int D;
-  // LQ kernels (tt_score_bwd_bf16_lq): per direction the sampling weights of the A rows and of the B rows (tt_score_bwd_lq)
-  const float* wt_a[2];
-  const float* wt_b[2];
-};
 
 template <int KS, int AT>
 __device__ __forceinline__ void mfma1(const bf16x8 (&bf)[KS], const bf16x8 (&ares)[AT][KS], f32x16 (&acc)[AT]) {
@@ -181,26 +82,11 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
   __shared__ float part_e[NW][ROWS];
   __shared__ float part_s[NW][ROWS];
   __shared__ int part_c[NW][ROWS];
-  // the direction's fields are picked with scalar selects (indexing the by-value argument with blockIdx.y made
-  // every field -- and with it the whole tile loop's control flow -- live in vector registers), and row counts /
-  // positions are 32-bit: the loop counter, the tile classification and their branches then run on the SALU
-  const bool d1 = blockIdx.y != 0;
-  DirFwd dr;
-  dr.a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
-  dr.b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
-  dr.a_lo = d1 ? args.d[1].a_lo : args.d[0].a_lo;
-  dr.b_lo = d1 ? args.d[1].b_lo : args.d[0].b_lo;
-  dr.sumexp = d1 ? args.d[1].sumexp : args.d[0].sumexp;
-  dr.diag = d1 ? args.d[1].diag : args.d[0].diag;
-  dr.rank = d1 ? args.d[1].rank : args.d[0].rank;
-  dr.sumscore = d1 ? args.d[1].sumscore : args.d[0].sumscore;
-  dr.rank_mode = d1 ? args.d[1].rank_mode : args.d[0].rank_mode;
-  const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, unscale = d1 ? args.d[1].unscale : args.d[0].unscale;
-  float* const inv_out = d1 ? args.d[1].inv_sumexp : args.d[0].inv_sumexp;
-  const float c2 = args.c2;
+  const FwdSel dr = select_dir(args, blockIdx.y != 0);
+  const float c1 = dr.c1, unscale = dr.unscale, c2 = args.c2;
+  float* const inv_out = dr.inv_sumexp;
   auto ex = [&](float x) { return UNIT ? __builtin_amdgcn_exp2f(x) : __builtin_amdgcn_exp2f(__builtin_fmaf(x, c1, c2)); };
-  const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
-  const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
+  const int Ra = dr.Ra, Rb = dr.Rb, off = dr.off;
   const int a0 = (int)blockIdx.x * ROWS;
   if (a0 >= Ra) return;
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -463,7 +349,9 @@ template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false>
 __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2, KL = X3 ? KS : 1;
   __shared__ float red[(NW / 2) * ROWS * Dp];
-  const bool d1 = blockIdx.y != 0;                    // scalar selects, 32-bit positions: see the forward kernel
+  // (this kernel's own copy of select_dir, a_row_setup and zero_acc, and its own sweep, tree and store: through the parts its
+  //  D = 256 instantiations change their scratch size, and the forward's registers move with them -- profiles/NOTES.md)
+  const bool d1 = blockIdx.y != 0;
   DirBwd dr;
   dr.a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
   dr.b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
@@ -552,8 +440,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) *
-               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
+        w[r] = softmax_term<UNIT, LQ>(acc[r], c1, c2, ia[i], ua[i], ib[r], wb[r]);
       if (b_lo + 31 >= Rb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -680,21 +567,10 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
   __bf16 (*const park)[32 * TLD] = TAIL ? reinterpret_cast<__bf16 (*)[32 * TLD]>(smem + kRedB) : park_s;
   using s16x4 = __attribute__((ext_vector_type(4))) short;
   using s16x8 = __attribute__((ext_vector_type(8))) short;
-  const bool d1 = blockIdx.y != 0;
-  DirBwd dr;
-  dr.a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
-  dr.b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
-  dr.sumexp_a = d1 ? args.d[1].sumexp_a : args.d[0].sumexp_a;
-  dr.sumexp_b = d1 ? args.d[1].sumexp_b : args.d[0].sumexp_b;
-  dr.dA = d1 ? args.d[1].dA : args.d[0].dA;
-  const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
-  const float* const inv_a = d1 ? args.d[1].inv_a : args.d[0].inv_a;
-  const float* const inv_b = d1 ? args.d[1].inv_b : args.d[0].inv_b;
-  const float* const wt_a = d1 ? args.wt_a[1] : args.wt_a[0];     // (LQ)
-  const float* const wt_b = d1 ? args.wt_b[1] : args.wt_b[0];
-  const float c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
-  const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
-  const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
+  const BwdSel dr = select_dir(args, blockIdx.y != 0);
+  const float c1 = dr.c1, c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
+  const int Ra = dr.Ra, Rb = dr.Rb, off = dr.off;
+  const float* const wt_b = dr.wt_b;
   const int a0 = (int)blockIdx.x * ROWS;
   if (a0 >= Ra) return;
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -706,21 +582,13 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
     load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
-    const int a = a0 + 32 * i + c;
-    ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
-    if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
-    pos[i] = a + off;
+    a_row_setup<LQ>(dr, kx, a0 + 32 * i + c, ia[i], ua[i], pos[i]);
   }
   const int posmin = a0 + off, posmax = a0 + ROWS - 1 + off;
   f32x16 dacc[AT][DT];
-#pragma unroll
-  for (int i = 0; i < AT; ++i)
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dacc[i][d][r] = 0.f;
-  const bool have_inv = inv_b != nullptr;
-  const float* const ivsrc = have_inv ? inv_b : dr.sumexp_b;
+  zero_acc(dacc);
+  const bool have_inv = dr.inv_b != nullptr;
+  const float* const ivsrc = have_inv ? dr.inv_b : dr.sumexp_b;
   const int tlast = nT - 1;
   __bf16* const tile = park[wave];
   // parked-tile addresses: write = row c, columns 16 s + 8 h; transposing read = block row q of this lane's 16-lane group,
@@ -790,8 +658,7 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2))) *
-               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
+        w[r] = softmax_term<UNIT, LQ>(acc[r], c1, c2, ia[i], ua[i], ib[r], wb[r]);
       if (b_lo + 31 >= Rb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -812,7 +679,7 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
         for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s2], bm[s2][d], dacc[i][d], 0, 0, 0);
     }
   };
-  Tile T0, T1;
+  Tile T0, T1;                                                 // (why the sweep has this shape: score_bwd_bf16_kernel's comment)
   load(T0, min(wave, tlast));
   __builtin_amdgcn_sched_barrier(0);
   for (int t = wave; t < nT; t += 2 * NW) {
@@ -855,7 +722,7 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
   }
   [[maybe_unused]] float* const htile = reinterpret_cast<float*>(smem + tttail::kTailBwdLds);
   if (wave == 0) {
-    const float g = args.d_loss[0] * out_scale;
+    const float g = args.d_loss[0] * dr.out_scale;
 #pragma unroll
     for (int i = 0; i < AT; ++i)
 #pragma unroll
@@ -887,6 +754,8 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
 // the hardware then runs one wave's softmax weights beside the other's MFMAs).
 // LQ: as score_bwd_bf16_kernel's; the tile's 32 sampling weights ride in the stage behind its 32 reciprocals (the stage's
 // 256-byte per-row slot held 128 bytes).
+// (Its own copy of select_dir, a_row_setup, zero_acc and the fp8 fragment read: with them the non-unit D = 128 instantiations read the
+// stage in more, smaller LDS reads and wait four or five times more per tile -- profiles/NOTES.md, "score backward parts".)
 template <int KS, bool UNIT, bool FP8, int AT, int NWV, bool LQ = false>
 __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) {
   constexpr int NTH = NWV * 64, DT = KS / 2, Dp = KS * 16, K64 = FP8 ? KS / 4 : 1;
@@ -1050,8 +919,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows_kernel(BwdArgs args) 
       float w[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        w[r] = (UNIT ? __builtin_amdgcn_exp2f(acc[i][r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][r], c1, c2))) *
-               (LQ ? __builtin_fmaf(ua[i], ib[r], wb[r] * ia[i]) : ia[i] + ib[r]);
+        w[r] = softmax_term<UNIT, LQ>(acc[i][r], c1, c2, ia[i], ua[i], ib[r], wb[r]);
       if (ragged) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -1136,20 +1004,14 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
   // stages, [wave][k64-step][part][lane] 16-byte pieces (8 KB per wave), and are read back beside the b fragments
   constexpr bool ALDS = KS == 16;
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-  const bool d1 = blockIdx.y != 0;
-  const char* const a_rows = reinterpret_cast<const char*>(d1 ? args.d[1].a_rows : args.d[0].a_rows);
-  const char* const g_rows = reinterpret_cast<const char*>(d1 ? args.d[1].b_rows : args.d[0].b_rows);
-  const char* const g_frag = d1 ? args.d[1].b_frag8 : args.d[0].b_frag8;
-  const __bf16* const b_frag16 = d1 ? args.d[1].b_frag : args.d[0].b_frag;
-  const float* const sumexp_a = d1 ? args.d[1].sumexp_a : args.d[0].sumexp_a;
-  const float* const sumexp_b = d1 ? args.d[1].sumexp_b : args.d[0].sumexp_b;
-  float* const dA = d1 ? args.d[1].dA : args.d[0].dA;
-  const float c1 = d1 ? args.d[1].c1 : args.d[0].c1, out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
-  const float* const inv_a = d1 ? args.d[1].inv_a : args.d[0].inv_a;
-  const float* const inv_b = d1 ? args.d[1].inv_b : args.d[0].inv_b;
-  const float c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
-  const int Ra = (int)(d1 ? args.d[1].Ra : args.d[0].Ra), Rb = (int)(d1 ? args.d[1].Rb : args.d[0].Rb);
-  const int off = (int)(d1 ? args.d[1].off : args.d[0].off);
+  const BwdSel dr = select_dir(args, blockIdx.y != 0);
+  const char* const a_rows = reinterpret_cast<const char*>(dr.a_rows);
+  const char* const g_rows = reinterpret_cast<const char*>(dr.b_rows);
+  const char* const g_frag = dr.b_frag8;
+  const __bf16* const b_frag16 = dr.b_frag;
+  float* const dA = dr.dA;
+  const float c1 = dr.c1, c2 = args.c2, kx = UNIT ? args.kexp : 1.f;
+  const int Ra = dr.Ra, Rb = dr.Rb, off = dr.off;
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nP = (Rb + 63) / 64, nTa_img = (int)(rup(Ra, 64) / 32);
@@ -1169,21 +1031,15 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
         a_lds[((i * K64 + s2) * 2 + 1) * 64] = *reinterpret_cast<const i32x4*>(pa + (s2 * 4 + 2) * 512);
       }
     } else load_f8frag<(ALDS ? 1 : K64)>(a_rows, min(at0 + i, nTa_img - 1), c, h, ares8[i]);
-    const int a = 32 * (at0 + i) + c;
-    ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(sumexp_a[a]) * kx) : 0.f;
-    pos[i] = a + off;
+    [[maybe_unused]] float ua;
+    a_row_setup<false>(dr, kx, 32 * (at0 + i) + c, ia[i], ua, pos[i]);
     wd[i] = 0.f;                                                            // stays 0 in the lanes that never meet the diagonal
   }
   const int posmin = 32 * at0 + off, posmax = 32 * (at0 + AT) - 1 + off;
   f32x16 dacc[AT][DT];
-#pragma unroll
-  for (int i = 0; i < AT; ++i)
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dacc[i][d][r] = 0.f;
-  const bool have_inv = inv_b != nullptr;
-  const float* const ivsrc = have_inv ? inv_b : sumexp_b;
+  zero_acc(dacc);
+  const bool have_inv = dr.inv_b != nullptr;
+  const float* const ivsrc = have_inv ? dr.inv_b : dr.sumexp_b;
   const int iv_last = (int)rup(Rb, 32) - 4;                                  // the per-row arrays are readable up to a multiple of 32 rows
   // stage = the pair's [two rows-image tiles | fp8 fragment image | 64 reciprocals], by LDS-DMA as in score_bwd_rows_kernel
   auto stage_dma = [&](int pn, int rbuf, int fbuf) {
@@ -1208,12 +1064,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
   // flight while fragment d's MFMAs issue
   auto grad = [&](const char* fb) {
     i32x8 bm8[2];
-    auto bm_read = [&](int d, i32x8& dst) {
-      const char* q = fb + (d * 4 + h) * 512 + c * 16;
-      const i32x4 lo = *reinterpret_cast<const i32x4*>(q);
-      const i32x4 hi = *reinterpret_cast<const i32x4*>(q + 1024);
-      dst = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
+    auto bm_read = [&](int d, i32x8& dst) { dst = f8frag_at(fb + (d * 4 + h) * 512 + c * 16); };
     bm_read(0, bm8[0]);
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
@@ -1245,18 +1096,10 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
     i32x8 bf8[2][2], af8[2][AT];
     auto s_read = [&](int s, i32x8 (&bdst)[2], i32x8 (&adst)[AT]) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const char* q = rb + t * (kRowsB / 2) + (s * 4 + h) * 512 + c * 16;
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(q);
-        const i32x4 hi = *reinterpret_cast<const i32x4*>(q + 1024);
-        bdst[t] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-      if (ALDS) {
+      for (int t = 0; t < 2; ++t) bdst[t] = f8frag_at(rb + t * (kRowsB / 2) + (s * 4 + h) * 512 + c * 16);
+      if (ALDS) {                                                          // (its two pieces lie 64 lanes = 1024 bytes apart too)
 #pragma unroll
-        for (int i = 0; i < AT; ++i) {
-          const i32x4 lo = a_lds[((i * K64 + s) * 2) * 64], hi = a_lds[((i * K64 + s) * 2 + 1) * 64];
-          adst[i] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        }
+        for (int i = 0; i < AT; ++i) adst[i] = f8frag_at(reinterpret_cast<const char*>(a_lds + ((i * K64 + s) * 2) * 64));
       }
     };
     s_read(0, bf8[0], af8[0]);
@@ -1294,8 +1137,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
 #pragma unroll
       for (int i = 0; i < AT; ++i) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          acc[i][t][r] = (UNIT ? __builtin_amdgcn_exp2f(acc[i][t][r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][t][r], c1, c2))) * (ia[i] + ib[r]);
+        for (int r = 0; r < 16; ++r) acc[i][t][r] = softmax_term<UNIT, false>(acc[i][t][r], c1, c2, ia[i], 0.f, ib[r], 0.f);
         if (ragged) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][t][r] = b_lo + 32 * t + rowmap(r, h) < Rb ? acc[i][t][r] : 0.f;
@@ -1345,7 +1187,7 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
   }
   // epilogue: + (w_aa - 2) b[pos_a] with the bf16 image's row (a lane holds the diagonal weight of row a = its column index c,
   // the accumulators are laid out by row: one cross-lane read per register)
-  const float g = args.d_loss[0] * out_scale;
+  const float g = args.d_loss[0] * dr.out_scale;
   const int nTb_img = (int)(rup(Rb, 64) / 32);
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
@@ -1369,153 +1211,6 @@ __global__ __launch_bounds__(NWV * 64) void score_bwd_rows8_kernel(BwdArgs args)
         }
       }
     }
-  }
-}
-
-// ---- fp8 pack: [fp8 rows image | bf16 fragment image | fp8 fragment image] (tt_score_bf16.h) ----------------
-// saturating: past e4m3's largest finite value the conversion would give NaN (64 * scale * x reaches 448 once |x| / T > 4.85,
-// e.g. a row with one dominant coordinate at T = 0.2)
-__device__ __forceinline__ float fp8_clamp(float v) { return __builtin_fminf(__builtin_fmaxf(v, -448.f), 448.f); }
-
-__global__ __launch_bounds__(256) void pack_fp8_kernel(PackBatch batch, int D, int Dp) {
-  const PackArgs& pa = batch.a[blockIdx.y];
-  const float* __restrict__ X = pa.X;
-  const int64_t R = pa.R, Rp = pa.Rp;
-  char* __restrict__ rows8 = reinterpret_cast<char*>(pa.rows);
-  __bf16* __restrict__ frag = pa.frag;
-  const float sc = pa.scale;
-  const int64_t n8 = Rp * Dp / 16, nfr = Rp * Dp / 8;      // 16-byte chunks of the rows image / of the bf16 fragment image
-  char* __restrict__ frag8 = reinterpret_cast<char*>(frag) + Rp * Dp * 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int cpt = Dp * 2;                                   // fp8 chunks per 32-row tile
-  for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < 2 * n8 + nfr; ci += stride) {
-    if (ci >= n8 + nfr) {                                   // fp8 fragment image [P][d][part][h][c][16]
-      const int64_t f = ci - n8 - nfr;
-      const int64_t P = f / (Dp * 4);
-      const int w = (int)(f - P * (Dp * 4)), c = w & 31, h = (w >> 5) & 1, part = (w >> 6) & 1, d = w >> 7;
-      const int col = 32 * d + c;
-      i32x4 o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int64_t row = 64 * P + 32 * part + rowmap(4 * q + j, h);
-          v[j] = (row < R && col < D) ? fp8_clamp(X[row * D + col] * sc * kFp8Up) : 0.f;
-        }
-        int u = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-        u = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], u, true);
-        o[q] = u;
-      }
-      *reinterpret_cast<i32x4*>(frag8 + f * 16) = o;
-    } else if (ci < n8) {
-      const int64_t t = ci / cpt;
-      const int w = (int)(ci - t * cpt), row_in = w & 31, g5 = w >> 5;
-      const int d0 = 64 * (g5 >> 2) + 32 * (g5 & 1) + 16 * ((g5 >> 1) & 1);
-      const int64_t row = 32 * t + row_in;
-      float v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = (row < R && d0 + j < D) ? fp8_clamp(X[row * D + d0 + j] * sc * kFp8Up) : 0.f;
-      i32x4 o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        int u = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * q], v[4 * q + 1], 0, false);
-        u = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * q + 2], v[4 * q + 3], u, true);
-        o[q] = u;
-      }
-      *reinterpret_cast<i32x4*>(rows8 + ci * 16) = o;
-    } else {                                               // fragment-ordered bf16 image [t][s][h][d][8], as pack_bf16_kernel
-      const int64_t f = ci - n8;
-      const int d = (int)(f % Dp);
-      const int64_t rest = f / Dp;
-      const int h = (int)(rest & 1), s = (int)((rest >> 1) & 1);
-      const int64_t t = rest >> 2;
-      bf16x8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int64_t row = 32 * t + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);
-        v[j] = (__bf16)((row < R && d < D) ? X[row * D + d] * sc : 0.f);
-      }
-      *reinterpret_cast<bf16x8*>(frag + f * 8) = v;
-    }
-  }
-}
-
-
-// The same three images from ONE read of X: a workgroup stages 64 rows (a tile pair) in LDS -- coalesced, 16 bytes per lane -- and
-// every thread then assembles 16-byte chunks of the images from there.  pack_fp8_kernel reads X once per image, the rows image
-// with 64 different rows per wave-instruction (536 MB of traffic for 134 MB of input at B = 65536, D = 256: 179 us).  Same
-// arithmetic per element: bit-identical images (tests compare the packed buffers with torch's conversion).
-constexpr int kPackTileRows = 64, kPackPad = 4;
-__global__ __launch_bounds__(256) void pack_fp8_tile_kernel(PackBatch batch, int D, int Dp) {
-  extern __shared__ __attribute__((aligned(16))) float xt[];          // [64][Dp + 4]
-  const PackArgs& pa = batch.a[blockIdx.y];
-  const float* __restrict__ X = pa.X;
-  const int64_t R = pa.R, Rp = pa.Rp;
-  const int64_t P = blockIdx.x;
-  if (P * kPackTileRows >= Rp) return;
-  char* __restrict__ rows8 = reinterpret_cast<char*>(pa.rows);
-  __bf16* __restrict__ frag = pa.frag;
-  char* __restrict__ frag8 = reinterpret_cast<char*>(frag) + Rp * Dp * 2;
-  const float sc = pa.scale;
-  const int ld = Dp + kPackPad, tid = threadIdx.x;
-  // stage: rows 64 P .. 64 P + 63, columns [0, Dp); zero outside [0, R) x [0, D)
-  if (D == Dp && (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
-    const int per_row = Dp / 4;
-    for (int e = tid; e < kPackTileRows * per_row; e += 256) {
-      const int r = e / per_row, c4 = e - r * per_row;
-      const int64_t row = P * kPackTileRows + r;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < R) v = reinterpret_cast<const float4*>(X + row * D)[c4];
-      *reinterpret_cast<float4*>(xt + r * ld + 4 * c4) = v;
-    }
-  } else {
-    for (int e = tid; e < kPackTileRows * Dp; e += 256) {
-      const int r = e / Dp, c = e - r * Dp;
-      const int64_t row = P * kPackTileRows + r;
-      xt[r * ld + c] = (row < R && c < D) ? X[row * D + c] : 0.f;
-    }
-  }
-  __syncthreads();
-  // fp8 rows image: tiles 2 P, 2 P + 1; chunk w of a tile = (row w & 31, group w >> 5)
-  const int cpt = Dp * 2;
-  for (int e = tid; e < 2 * cpt; e += 256) {
-    const int t = e / cpt, w = e - t * cpt, row_in = w & 31, g5 = w >> 5;
-    const int d0 = 64 * (g5 >> 2) + 32 * (g5 & 1) + 16 * ((g5 >> 1) & 1);
-    const float* src = xt + (32 * t + row_in) * ld + d0;
-    i32x4 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = *reinterpret_cast<const float4*>(src + 4 * q);
-      int u = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v.x * sc * kFp8Up), fp8_clamp(v.y * sc * kFp8Up), 0, false);
-      u = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v.z * sc * kFp8Up), fp8_clamp(v.w * sc * kFp8Up), u, true);
-      o[q] = u;
-    }
-    *reinterpret_cast<i32x4*>(rows8 + ((2 * P + t) * cpt + w) * 16) = o;
-  }
-  // bf16 fragment image [t][s][h][d][8]
-  for (int e = tid; e < 8 * Dp; e += 256) {
-    const int d = e % Dp, rest = e / Dp, h = rest & 1, s2 = (rest >> 1) & 1, t = rest >> 2;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(xt[(32 * t + 16 * s2 + 8 * (j >> 2) + 4 * h + (j & 3)) * ld + d] * sc);
-    *reinterpret_cast<bf16x8*>(frag + ((((2 * P + t) * 2 + s2) * 2 + h) * Dp + d) * 8) = v;
-  }
-  // fp8 fragment image [P][d][part][h][c][16]
-  for (int e = tid; e < 4 * Dp; e += 256) {
-    const int c = e & 31, h = (e >> 5) & 1, part = (e >> 6) & 1, d = e >> 7;
-    const int col = 32 * d + c;
-    i32x4 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fp8_clamp(xt[(32 * part + rowmap(4 * q + j, h)) * ld + col] * sc * kFp8Up);
-      int u = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-      u = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], u, true);
-      o[q] = u;
-    }
-    *reinterpret_cast<i32x4*>(frag8 + (P * (Dp * 4) + e) * 16) = o;
   }
 }
 
@@ -1774,45 +1469,7 @@ static int bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_
 
 extern "C" {
 
-size_t tt_score_pack_bytes(int64_t R, int32_t D) {
-  if (R < 0 || D < 1 || D > 256) return 0;
-  return (size_t)(4 * rup(R > 0 ? R : 1, 64) * padded_d(D));
-}
-
 float tt_score_unit_scale(float inv_t) { return inv_t * kLog2e; }
-
-int tt_score_pack2_bf16(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, const float* X1, int64_t R1, void* packed1,
-                        int32_t D, float scale0, float scale1, tt_stream stream) {
-  TT_CHECK_ARG(ctx && X0 && packed0, "tt_score_pack_bf16: NULL argument");
-  TT_CHECK_ARG(R0 >= 1 && D >= 1 && (X1 == nullptr || (packed1 && R1 >= 1)), "tt_score_pack_bf16: bad shape");
-  if (D > 256) {
-    tt_set_error("tt_score_pack_bf16: D=%d > 256 not supported", D);
-    return TT_ERR_UNSUPPORTED;
-  }
-  TT_CHECK_ARG(tt_aligned(packed0, 16) && tt_aligned(packed1, 16), "tt_score_pack_bf16: packed buffers must be 16-byte aligned");
-  const int Dp = padded_d(D);
-  PackBatch b{};
-  const int n = X1 ? 2 : 1;
-  int64_t maxchunks = 1;
-  for (int i = 0; i < n; ++i) {
-    const int64_t R = i ? R1 : R0, Rp = rup(R, 64);     // a workgroup reads up to 64 consecutive rows of its operand
-    __bf16* base = reinterpret_cast<__bf16*>(i ? packed1 : packed0);
-    const float sc = i ? scale1 : scale0;
-    b.a[i] = PackArgs{i ? X1 : X0, R, Rp, base, base + Rp * Dp, sc == 0.f ? 1.f : sc};
-    const int64_t chunks = 2 * Rp * Dp / 8;
-    maxchunks = chunks > maxchunks ? chunks : maxchunks;
-  }
-  int64_t grid = tt_cdiv(maxchunks, 256);
-  const int64_t cap = (int64_t)ctx->num_cus * 4;
-  if (grid > cap) grid = cap;
-  pack_bf16_kernel<false><<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
-int tt_score_pack_bf16(tt_ctx* ctx, const float* X, int64_t R, int32_t D, float scale, void* packed, tt_stream stream) {
-  return tt_score_pack2_bf16(ctx, X, R, packed, nullptr, 0, nullptr, D, scale, 1.f, stream);
-}
 
 int tt_score_fwd_bf16(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                       tt_stream stream) {
@@ -1828,45 +1485,6 @@ int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_sco
                          float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
   TT_CHECK_ARG(lq, "tt_score_bwd_bf16_lq: NULL lq");
   return bwd_bf16(ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_lq");
-}
-
-size_t tt_score_pack_fp8_bytes(int64_t R, int32_t D) {
-  if (R < 0 || D < 1 || D > 256) return 0;
-  return (size_t)(4 * rup(R > 0 ? R : 1, 64) * padded_d8(D));
-}
-
-int tt_score_pack2_fp8(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, const float* X1, int64_t R1, void* packed1,
-                       int32_t D, float scale0, float scale1, tt_stream stream) {
-  TT_CHECK_ARG(ctx && X0 && packed0, "tt_score_pack2_fp8: NULL argument");
-  TT_CHECK_ARG(R0 >= 1 && D >= 1 && D <= 256 && (X1 == nullptr || (packed1 && R1 >= 1)), "tt_score_pack2_fp8: bad shape");
-  TT_CHECK_ARG(tt_aligned(packed0, 16) && tt_aligned(packed1, 16), "tt_score_pack2_fp8: packed buffers must be 16-byte aligned");
-  const int Dp = padded_d8(D);
-  PackBatch b{};
-  const int n = X1 ? 2 : 1;
-  int64_t maxchunks = 1;
-  for (int i = 0; i < n; ++i) {
-    const int64_t R = i ? R1 : R0, Rp = rup(R, 64);
-    char* base = reinterpret_cast<char*>(i ? packed1 : packed0);
-    const float sc = i ? scale1 : scale0;
-    b.a[i] = PackArgs{i ? X1 : X0, R, Rp, reinterpret_cast<__bf16*>(base), reinterpret_cast<__bf16*>(base + Rp * Dp), sc == 0.f ? 1.f : sc};
-    const int64_t chunks = 2 * (Rp * Dp / 16) + Rp * Dp / 8;
-    maxchunks = chunks > maxchunks ? chunks : maxchunks;
-  }
-  int64_t maxRp = 0;
-  for (int i = 0; i < n; ++i) maxRp = b.a[i].Rp > maxRp ? b.a[i].Rp : maxRp;
-  if (maxRp >= 4096) {                                   // enough tile pairs to fill the chip: one read of X through LDS
-    const size_t lds = (size_t)kPackTileRows * (Dp + kPackPad) * sizeof(float);
-    TT_LDS_ONCE(lds, &pack_fp8_tile_kernel);
-    pack_fp8_tile_kernel<<<dim3((unsigned)(maxRp / kPackTileRows), (unsigned)n), 256, lds, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-  }
-  int64_t grid = tt_cdiv(maxchunks, 256);
-  const int64_t cap = (int64_t)ctx->num_cus * 4;
-  if (grid > cap) grid = cap;
-  pack_fp8_kernel<<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
 }
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
@@ -1889,34 +1507,6 @@ int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, 
 }
 
 // ---- bf16x3 (split-bf16) operands: [hi image | lo image] packings, three bf16 MFMAs per product ------------------------
-size_t tt_score_pack_x3_bytes(int64_t R, int32_t D) { return 2 * tt_score_pack_bytes(R, D); }
-
-int tt_score_pack2_bf16x3(tt_ctx* ctx, const float* X0, int64_t R0, void* packed0, const float* X1, int64_t R1, void* packed1,
-                          int32_t D, float scale0, float scale1, tt_stream stream) {
-  TT_CHECK_ARG(ctx && X0 && packed0, "tt_score_pack2_bf16x3: NULL argument");
-  TT_CHECK_ARG(R0 >= 1 && D >= 1 && D <= 256 && (X1 == nullptr || (packed1 && R1 >= 1)), "tt_score_pack2_bf16x3: bad shape");
-  TT_CHECK_ARG(tt_aligned(packed0, 16) && tt_aligned(packed1, 16), "tt_score_pack2_bf16x3: packed buffers must be 16-byte aligned");
-  const int Dp = padded_d(D);
-  PackBatch b{};
-  const int n = X1 ? 2 : 1;
-  int64_t maxchunks = 1;
-  for (int i = 0; i < n; ++i) {
-    const int64_t R = i ? R1 : R0, Rp = rup(R, 64);
-    __bf16* base = reinterpret_cast<__bf16*>(i ? packed1 : packed0);
-    __bf16* lo = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(base) + x3_half_bytes(R, D));
-    const float sc = i ? scale1 : scale0;
-    b.a[i] = PackArgs{i ? X1 : X0, R, Rp, base, base + Rp * Dp, sc == 0.f ? 1.f : sc, lo, lo + Rp * Dp};
-    const int64_t chunks = 2 * Rp * Dp / 8;
-    maxchunks = chunks > maxchunks ? chunks : maxchunks;
-  }
-  int64_t grid = tt_cdiv(maxchunks, 256);
-  const int64_t cap = (int64_t)ctx->num_cus * 4;
-  if (grid > cap) grid = cap;
-  pack_bf16_kernel<true><<<dim3((unsigned)grid, (unsigned)n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(b, D, Dp);
-  TT_LAUNCH_CHECK();
-  return TT_OK;
-}
-
 int tt_score_fwd_bf16x3(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,
                         tt_stream stream) {
   return fwd_bf16(ctx, dirs, n_dirs, D, inv_t, shift, stream, true, "tt_score_fwd_bf16x3");
