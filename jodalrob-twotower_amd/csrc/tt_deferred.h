@@ -16,7 +16,7 @@ enum : int {
   TT_DQ_SCORE_BWD = 1,   // tt_score_bwd_bf16's launch (TT_OPT_FUSE_SCORE_TAIL); host: tt_towers_mlp_bwd through tt_score_tail_bwd_launch
   TT_DQ_SORT = 2,        // the keyed plan's sort (TT_OPT_DEFER_RIDERS & 1); host: tt_towers_mlp_fwd, with the BatchNorm statistics riders
   TT_DQ_COMPACT = 4,     // the keyed plan's compaction (same option); host: tail_fwd_kernel's extra grid row
-  TT_DQ_LOSS = 8,        // the symmetric score forward's last reduction (TT_OPT_DEFER_RIDERS & 2); host: tail_bwd / tail_bwd_apply
+  TT_DQ_LOSS = 8,        // the symmetric score forward's last reduction (TT_OPT_DEFER_RIDERS & 2); host: tail_bwd, or gemm_back behind a hosted head
   TT_DQ_SLABS = 16,      // split-K slab reduction of the towers' weight gradients (TT_OPT_DEFER_SLAB_REDUCE); host: tt_embed_grad_bwd
   TT_DQ_RIDERS = TT_DQ_SORT | TT_DQ_COMPACT | TT_DQ_LOSS, TT_DQ_ALL = 31,
 };

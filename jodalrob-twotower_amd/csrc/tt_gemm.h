@@ -3,6 +3,7 @@
 // Every launcher takes up to TT_MAX_SIDES independent problems (the towers) and covers them with ONE launch.
 #pragma once
 #include "tt_common.h"
+#include "tt_riders.h"
 
 // C[M,N] = act(alpha * A[M,K] . W[N,K]^T + bias)  (nn.Linear forward; alpha = 1/T for score matrices)
 struct GemmNT {
@@ -178,4 +179,5 @@ struct GemmBack {
 };
 bool tt_gemm_back_supported(const GemmBack* items, int n);
 size_t tt_gemm_back_g_workspace_bytes(int64_t H, int64_t h0, int64_t din, int64_t B);
-int tt_gemm_back_batched(hipStream_t st, const GemmBack* items, int n, TnPending* pending);
+// rider: the symmetric score forward's queued loss reduction (slot TT_DQ_LOSS of tt_deferred.h) runs as the launch's first workgroup
+int tt_gemm_back_batched(hipStream_t st, const GemmBack* items, int n, TnPending* pending, const Finish2Rider* rider = nullptr);

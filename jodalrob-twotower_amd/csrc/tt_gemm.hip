@@ -599,14 +599,22 @@ struct BackBatch {
   int n;
 };
 
+// fr_on: the FIRST workgroup runs the symmetric score forward's loss reduction instead (tt_riders.h; slot TT_DQ_LOSS of tt_deferred.h:
+// only the host reads what it writes, and this is the backward's longest launch), in the tiles' LDS
+static_assert(sizeof(BackSmem) >= sizeof(float) * kFinish2Lds, "the loss reduction runs in the tiles' LDS");
 template <bool X_BF16>
-__global__ __launch_bounds__(THREADS, 4) void gemm_back_kernel(BackBatch b) {
+__global__ __launch_bounds__(THREADS, 4) void gemm_back_kernel(BackBatch b, Finish2Rider fr, int fr_on) {
+  __shared__ __attribute__((aligned(16))) BackSmem sm;
+  if (fr_on && blockIdx.x == 0) {
+    finish2_body<THREADS>(fr, reinterpret_cast<float*>(&sm));
+    return;
+  }
+  const int wg = (int)blockIdx.x - fr_on;
   int p = 0;
-  while (p + 1 < b.n && (int)blockIdx.x >= b.wg_end[p]) ++p;
-  const int local = (int)blockIdx.x - (p ? b.wg_end[p - 1] : 0);
+  while (p + 1 < b.n && wg >= b.wg_end[p]) ++p;
+  const int local = wg - (p ? b.wg_end[p - 1] : 0);
   const int split = local / b.tiles[p], tile = local % b.tiles[p];
   const int bx = tile % b.tiles_m[p], by = tile / b.tiles_m[p];
-  __shared__ __attribute__((aligned(16))) BackSmem sm;
   const GemmArgs& g = b.g[p];
   if (b.role[p] == 0) gemm_fast_tile<1, 1, true, false, X_BF16>(g, split, bx, by, sm);
   else if (b.role[p] == 1) gemm_fast_tile<1, 1, false, false, false, true>(g, split, bx, by, sm);
@@ -876,7 +884,7 @@ bool tt_gemm_back_supported(const GemmBack* it, int n) {
   return true;
 }
 
-int tt_gemm_back_batched(hipStream_t st, const GemmBack* it, int n, TnPending* pending) {
+int tt_gemm_back_batched(hipStream_t st, const GemmBack* it, int n, TnPending* pending, const Finish2Rider* rider) {
   if (!pending || !tt_gemm_back_supported(it, n)) {
     tt_set_error("tt_gemm_back: unsupported shapes / missing pending queue");
     return TT_ERR_INVALID_ARG;
@@ -927,8 +935,10 @@ int tt_gemm_back_batched(hipStream_t st, const GemmBack* it, int n, TnPending* p
       wg += tm * tn_ * b.g[p].splits;
       b.wg_end[p] = wg;
     }
-  if (it[0].x_bf16) gemm_back_kernel<true><<<wg, THREADS, 0, st>>>(b);
-  else gemm_back_kernel<false><<<wg, THREADS, 0, st>>>(b);
+  const int fr_on = rider ? 1 : 0;
+  const Finish2Rider fr = rider ? *rider : Finish2Rider{};
+  if (it[0].x_bf16) gemm_back_kernel<true><<<wg + fr_on, THREADS, 0, st>>>(b, fr, fr_on);
+  else gemm_back_kernel<false><<<wg + fr_on, THREADS, 0, st>>>(b, fr, fr_on);
   TT_LAUNCH_CHECK();
   if (pending->n + ns > kSlabItems)
     if (int rc = tt_gemm_tn_flush(st, pending)) return rc;

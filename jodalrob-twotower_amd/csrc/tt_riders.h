@@ -3,8 +3,8 @@
 // workgroup's head count; first consumer: tt_embed_grad_bwd), the last reduction of the symmetric score forward (loss + metrics:
 // read by the host only) and the finish of the towers' BatchNorm batch statistics.  This header holds their argument structs and
 // their device bodies, which the stand-alone kernels and the host kernels (the towers' fused tails, 1024-thread workgroups like
-// every role here; the keyed plan's sort) share, so results are bit-identical (test).  How they are queued, hosted and flushed:
-// tt_deferred.h.
+// every role here; the keyed plan's sort; gemm_back_kernel, whose 256 threads run the loss reduction in the 1024-thread order) share,
+// so results are bit-identical (test).  How they are queued, hosted and flushed: tt_deferred.h.
 #pragma once
 #include "tt_common.h"
 
@@ -213,28 +213,45 @@ __device__ __forceinline__ void compact_body(const CompactRider& cr, int ki) {
   }
 }
 
-// the one workgroup (kRiderThreads threads) that adds the symmetric forward's partial records in a fixed order (thread (j, q):
-// records q, q + 4, ... of entry j, the four partial sums in order); loss and metrics (out8 as tt_score_loss_finish)
-__device__ __forceinline__ void finish2_body(const Finish2Rider& fr) {
+// the one workgroup that adds the symmetric forward's partial records in a fixed order (item (j, q): records q, q + 4, ... of entry
+// j, the four partial sums in order); loss and metrics (out8 as tt_score_loss_finish).  The order is the one of a kRiderThreads
+// workgroup whose thread i runs item (i & 255, i >> 8); a host with NT threads (a power of two, 256 at least) lets thread t stand in
+// for the threads t, t + NT, ... of that workgroup, each item summed in its own order with the items' loads in flight together:
+// the same sums, the same results.  lds: kFinish2Lds floats.
+constexpr int kFinish2Lds = 4 * (4 + 2 * 256) + 256;
+template <int NT>
+__device__ __forceinline__ void finish2_body(const Finish2Rider& fr, float* lds) {
+  static_assert(NT >= 256 && kRiderThreads % NT == 0, "thread t stands in for the threads t + NT i of a kRiderThreads workgroup");
+  constexpr int NI = kRiderThreads / NT;
   const float* __restrict__ part = fr.part;
   const int n_wg = fr.n_wg, Dp = fr.Dp;
   const float fb = fr.fb, unscale = fr.unscale;
   float* __restrict__ out = fr.out;
   float* __restrict__ loss_out = fr.loss_out;
 
-  __shared__ float red[4][4 + 2 * 256];
-  __shared__ float prod[256];
-  const int t = threadIdx.x, q = t >> 8, j0 = t & 255, stride = 4 + 2 * Dp;
+  float (*red)[4 + 2 * 256] = reinterpret_cast<float (*)[4 + 2 * 256]>(lds);
+  float* prod = lds + 4 * (4 + 2 * 256);
+  const int t = threadIdx.x, q0 = t >> 8, j0 = t & 255, stride = 4 + 2 * Dp;
   for (int j = j0; j < stride; j += 256) {
-    float s = 0.f;
-    for (int w0 = q; w0 < n_wg; w0 += 32) {
-      float v[8];
+    float s[NI];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = w0 + 4 * k < n_wg ? part[(int64_t)(w0 + 4 * k) * stride + j] : 0.f;
+    for (int i = 0; i < NI; ++i) s[i] = 0.f;
+    for (int w0 = q0; w0 < n_wg; w0 += 32) {               // (item i: q = q0 + (NT / 256) i, its records q + 32 m + 4 k)
+      float v[NI][8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) s += v[k];
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int w = w0 + (NT / 256) * i + 4 * k;
+          v[i][k] = w < n_wg ? part[w * stride + j] : 0.f;       // (32-bit: n_wg * stride is a few thousand)
+        }
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[i] += v[i][k];
     }
-    red[q][j] = s;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) red[q0 + (NT / 256) * i][j] = s[i];
   }
   __syncthreads();
   if (t < 256) {
@@ -269,5 +286,10 @@ __device__ __forceinline__ void finish2_body(const Finish2Rider& fr) {
       if (loss_out) loss_out[0] = out[0];
     }
   }
+}
+// as a kRiderThreads workgroup of its own runs it (the stand-alone kernels, the tails' extra grid row)
+__device__ __forceinline__ void finish2_body(const Finish2Rider& fr) {
+  __shared__ float lds[kFinish2Lds];
+  finish2_body<kRiderThreads>(fr, lds);
 }
 #endif

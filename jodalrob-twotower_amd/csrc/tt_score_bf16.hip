@@ -15,6 +15,17 @@
 //     the second product in the k-permutation the accumulator registers impose.
 //   * partial results of the NW waves are combined through LDS in a fixed tree order.
 #include "tt_score_bwd_parts.h"
+// measurement aid, compiled in with -DTT_POST_STAMPS only (tools/post_sweep_stamps.py): what the hosted score backward's workgroups
+// do behind their sweep -- device-clock stamps of thread 0: 0 start, 1 end of its sweep, 2 the head's loads issued, 3 / 4 behind
+// the reduction's two barriers, 5 the flat sums added and dA stored, 6 behind the barrier in front of the head, 8 + i behind
+// barrier i of the head (tt_tail_bwd.h), 14 its end.  Written with plain vector stores, compiled out of the product.
+#ifdef TT_POST_STAMPS
+__device__ unsigned long long g_post_stamps[512 * 16];
+#define TT_POST_STAMP(i) do { if (threadIdx.x == 0) g_post_stamps[((blockIdx.y * gridDim.x + blockIdx.x) & 511) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TT_HEAD_STAMP(i) TT_POST_STAMP(8 + (i))
+#else
+#define TT_POST_STAMP(i) do { } while (0)
+#endif
 #include "tt_tail_bwd.h"
 #include "tt_deferred.h"
 
@@ -544,9 +555,13 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
 // three one after the other.
 // LQ: as score_bwd_bf16_kernel's.
 // TAIL (KS = 4, AT = 2, no LQ; TT_OPT_FUSE_SCORE_TAIL, launched by tt_towers_mlp_bwd): the workgroup goes on with the towers' backward head (tt_tail_bwd.h) of
-// tower blockIdx.y, row chunk blockIdx.x -- the 64 rows whose d_emb wave 0 holds when the tree is done.  The head's loads that
-// depend on nothing the sweep produces are issued in front of the tree (ares and the streamed tiles are dead there); the head's
-// LDS lies over `red` (whole: the tree has read it), the f32 tile of d_emb behind it.  Sweep and tree are the same code.
+// tower blockIdx.y, row chunk blockIdx.x -- the 64 rows of d_emb this workgroup sums.  The head's loads that depend on nothing the
+// sweep produces are issued in front of the reduction (ares and the streamed tiles are dead there).  Where the other forms run the
+// tree's second and third rounds and let wave 0 store dA, the reduction here is FLAT behind round one: waves
+// 0 .. 3 put their sums back into the four slabs, one barrier, and thread (wave w, lane d) of all eight waves adds rows 8 w .. 8 w + 7
+// of column d as (s0 + s2) + (s1 + s3) -- the tree's own association ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)), bit for bit --,
+// stores them to dA and keeps them: that is the thread that normalises those rows in the head.  The head's LDS lies over `red`
+// (one more barrier: every wave has read the slabs).  The sweep is the same code.
 // (one __global__ template for both: the sweep must compile exactly as it does without a tail)
 template <bool TAIL>
 struct TailHost {};
@@ -558,8 +573,8 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
   constexpr int NW = 8, Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2;
   constexpr int TLD = Dp + 8;                                   // LDS row of the parked tile: 144 B at D = 64 (conflict-free b128 writes)
   constexpr int kRedB = (NW / 2) * ROWS * Dp * 4, kParkB = NW * 32 * TLD * 2;
-  static_assert(!TAIL || (KS == 4 && AT == 2 && !LQ && tttail::kTailBwdLds + 64 * tttail::kTailTileLd * 4 <= kRedB + kParkB),
-                "the tail's head and its d_emb tile lie over red | park of the <4, 2> form");
+  static_assert(!TAIL || (KS == 4 && AT == 2 && !LQ && tttail::kTailBwdLds <= kRedB + kParkB),
+                "the tail's head lies over red | park of the <4, 2> form");
   __shared__ float red_s[TAIL ? 1 : (NW / 2) * ROWS * Dp];
   __shared__ __attribute__((aligned(16))) __bf16 park_s[TAIL ? 1 : NW][32 * TLD];
   __shared__ __attribute__((aligned(16))) char smem[TAIL ? kRedB + kParkB : 16];       // TAIL: red | park as ONE buffer
@@ -573,6 +588,7 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
   const float* const wt_b = dr.wt_b;
   const int a0 = (int)blockIdx.x * ROWS;
   if (a0 >= Ra) return;
+  if constexpr (TAIL) TT_POST_STAMP(0);
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nT = (Rb + 31) / 32;
@@ -692,15 +708,16 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
   [[maybe_unused]] tttail::TailBwdRows<512> hv;
   [[maybe_unused]] uint64_t hseed = 0;
   if constexpr (TAIL) {
+    TT_POST_STAMP(1);
     const tttail::TailBwdArgs& f = th.batch.a[blockIdx.y];
     tttail::tail_bwd_load_const<512>(f, hk);
     tttail::tail_bwd_load_rows<512, true>(f, min(f.col.B, a0 + 64), a0, hv);
     if (th.drop) hseed = tttail::seed_of(th.seed0, th.seed_dev);
+    TT_POST_STAMP(2);
   }
-#pragma unroll
-  for (int half = NW / 2; half >= 1; half >>= 1) {
-    if (wave >= half && wave < 2 * half) {
-      float* slab = red + (wave - half) * ROWS * Dp;
+  if constexpr (TAIL) {
+    if (wave >= NW / 2) {                                        // round one of the tree
+      float* slab = red + (wave - NW / 2) * ROWS * Dp;
 #pragma unroll
       for (int i = 0; i < AT; ++i)
 #pragma unroll
@@ -709,33 +726,76 @@ __global__ __launch_bounds__(512) void score_bwd_tr_kernel(BwdArgs args, TailHos
           for (int r = 0; r < 16; ++r) slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c] = dacc[i][d][r];
     }
     __syncthreads();
-    if (wave < half) {
-      const float* slab = red + wave * ROWS * Dp;
+    TT_POST_STAMP(3);
+    if (wave < NW / 2) {                                         // (a lane writes the addresses it has read: no barrier between)
+      float* slab = red + wave * ROWS * Dp;
 #pragma unroll
       for (int i = 0; i < AT; ++i)
 #pragma unroll
         for (int d = 0; d < DT; ++d)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) dacc[i][d][r] += slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c];
+          for (int r = 0; r < 16; ++r) {
+            float* at = slab + (32 * i + rowmap(r, h)) * Dp + 32 * d + c;
+            *at = dacc[i][d][r] + *at;
+          }
     }
     __syncthreads();
-  }
-  [[maybe_unused]] float* const htile = reinterpret_cast<float*>(smem + tttail::kTailBwdLds);
-  if (wave == 0) {
+    TT_POST_STAMP(4);
+    const tttail::TailBwdArgs& f = th.batch.a[blockIdx.y];
     const float g = args.d_loss[0] * dr.out_scale;
+    constexpr int R = tttail::TailBwdRows<512>::R;
+    static_assert(R * NW == ROWS && Dp == 64, "thread (wave, lane): rows wave R .. wave R + R - 1 of column lane");
 #pragma unroll
-    for (int i = 0; i < AT; ++i)
+    for (int j = 0; j < R; ++j) {
+      const float* at = red + (wave * R + j) * Dp + lane;
+      const float s0 = at[0], s1 = at[ROWS * Dp], s2 = at[2 * ROWS * Dp], s3 = at[3 * ROWS * Dp];
+      const float v = ((s0 + s2) + (s1 + s3)) * g;
+      const int a = a0 + wave * R + j;
+      if (a < Ra && lane < args.D) dr.dA[(int64_t)a * args.D + lane] = v;
+      hv.de[j] = (a < f.col.B && lane < f.D) ? v : 0.f;
+    }
+    TT_POST_STAMP(5);
+    __syncthreads();                                             // the slabs are read: the head's LDS lies over them
+    TT_POST_STAMP(6);
+    tttail::tail_bwd_head<512, true>(f, blockIdx.x, th.drop, th.p, hseed, smem, &hk, &hv);
+  } else {
 #pragma unroll
-      for (int d = 0; d < DT; ++d)
+    for (int half = NW / 2; half >= 1; half >>= 1) {
+      if (wave >= half && wave < 2 * half) {
+        float* slab = red + (wave - half) * ROWS * Dp;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int a = a0 + 32 * i + rowmap(r, h);
-          const int dd = 32 * d + c;
-          if (a < Ra && dd < args.D) dr.dA[(int64_t)a * args.D + dd] = dacc[i][d][r] * g;
-          if constexpr (TAIL) htile[(32 * i + rowmap(r, h)) * tttail::kTailTileLd + dd] = dacc[i][d][r] * g;
-        }
+        for (int i = 0; i < AT; ++i)
+#pragma unroll
+          for (int d = 0; d < DT; ++d)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c] = dacc[i][d][r];
+      }
+      __syncthreads();
+      if (wave < half) {
+        const float* slab = red + wave * ROWS * Dp;
+#pragma unroll
+        for (int i = 0; i < AT; ++i)
+#pragma unroll
+          for (int d = 0; d < DT; ++d)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dacc[i][d][r] += slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c];
+      }
+      __syncthreads();
+    }
+    if (wave == 0) {
+      const float g = args.d_loss[0] * dr.out_scale;
+#pragma unroll
+      for (int i = 0; i < AT; ++i)
+#pragma unroll
+        for (int d = 0; d < DT; ++d)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int a = a0 + 32 * i + rowmap(r, h);
+            const int dd = 32 * d + c;
+            if (a < Ra && dd < args.D) dr.dA[(int64_t)a * args.D + dd] = dacc[i][d][r] * g;
+          }
+    }
   }
-  if constexpr (TAIL) tttail::tail_bwd_head<512, true>(th.batch.a[blockIdx.y], blockIdx.x, th.drop, th.p, hseed, smem, htile, &hk, &hv);
 }
 
 // ---- backward, large-batch form ---------------------------------------------------------------------
@@ -1522,5 +1582,11 @@ int tt_score_bwd_bf16x3_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_s
   TT_CHECK_ARG(lq, "tt_score_bwd_bf16x3_lq: NULL lq");
   return bwd_bf16x3(ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16x3_lq");
 }
+
+#ifdef TT_POST_STAMPS
+int tt_debug_post_stamps(unsigned long long* host_out /* [512 * 16] */) {
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_post_stamps), sizeof(unsigned long long) * 512 * 16, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+}
+#endif
 
 }  // extern "C"

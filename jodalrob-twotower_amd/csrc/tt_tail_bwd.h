@@ -1,11 +1,17 @@
 // The backward head of the towers' fused narrow tail as ONE device body with two hosts (as tt_riders.h does for the riders):
 // tail_bwd_kernel (tt_tower.hip: 1024-thread workgroups, d_emb read from global memory) and score_bwd_tr_kernel<4, 2, UNIT, false, true>
-// (tt_score_bf16.hip: the score backward's 512-thread workgroups, which hold their 64 rows of d_emb in an LDS tile when their
-// cross-wave tree is done -- no kernel boundary, no 4 MB round trip).  Only the elementwise phases depend on the thread count
+// (tt_score_bf16.hip: the score backward's 512-thread workgroups, whose flat final reduction leaves every thread the 8 values of
+// d_emb the head wants from it, in registers -- no kernel boundary, no 4 MB round trip).  Only the elementwise phases depend on the thread count
 // (thread (c, rq) owns rows rq + NT / 64 * j); everything whose order matters -- the two MFMA chains, the cs column sums, the
 // ordered S1 / S2 sums, the sh[.][0..3] merges -- runs in the first four waves in one fixed order: bit-identical results.
 #pragma once
 #include "tt_common.h"
+
+// measurement aid: a host built with phase stamps (tt_score_bf16.hip under -DTT_POST_STAMPS) defines TT_HEAD_STAMP in front of this
+// header; the head then stamps behind each of its barriers
+#ifndef TT_HEAD_STAMP
+#define TT_HEAD_STAMP(i) do { } while (0)
+#endif
 
 namespace tttail {
 
@@ -61,9 +67,6 @@ struct TailBwdArgs {
 // once the MFMAs are done) ; Wn [h][d] ; actT [h][row] ; DY (d_y, then d_act, of the 64 rows) ; sh
 constexpr int kTailBwdLds = 2 * (2 * 64 * kTailLd) + 2 * (64 * kTailLd) + 2 * (64 * kTailLd) + 4 * (64 * kTailLdF) + 4 * (3 * 4 * 64);
 static_assert(sizeof(float) * 64 * kTailLdF <= sizeof(__bf16) * 2 * 64 * kTailLd, "XH must fit over dyA | dyT");
-// the caller's f32 tile of d_emb (TILE hosts): [64 rows][kTailTileLd] -- rows 4 apart land 32 banks apart (the MFMA accumulator's
-// two lane halves write rows r and r + 4 in one instruction)
-constexpr int kTailTileLd = 72;
 
 // what a workgroup of NT threads loads for the head: the part that depends on nothing but the launch's arguments ...
 template <int NT>
@@ -71,7 +74,7 @@ struct TailBwdConst {
   static constexpr int R = 64 * 64 / NT;              // rows (and W_out rows) per thread
   float w[R], mean, rstd;
 };
-// ... and 64 rows' worth of y, emb (d_emb unless an LDS tile brings it), act and pre
+// ... and 64 rows' worth of y, emb (d_emb unless the host brings it), act and pre
 template <int NT>
 struct TailBwdRows {
   static constexpr int R = 64 * 64 / NT;
@@ -94,7 +97,7 @@ __device__ __forceinline__ void tail_bwd_load_const(const TailBwdArgs& f, TailBw
 
 // rows b0 .. b0 + 63 (below r1).  L2 part: one wave per row as l2norm_bwd_kernel, R independent rows per wave in flight;
 // act / pre: thread (c, rq), rows rq + NWV j
-template <int NT, bool TILE>
+template <int NT, bool REGS>
 __device__ __forceinline__ void tail_bwd_load_rows(const TailBwdArgs& f, int r1, int b0, TailBwdRows<NT>& v) {
   constexpr int NWV = NT / 64, R = TailBwdRows<NT>::R;
   const int H = f.col.H, D = f.D;
@@ -108,7 +111,7 @@ __device__ __forceinline__ void tail_bwd_load_rows(const TailBwdArgs& f, int r1,
     const float v0 = f.y[i], v1 = f.emb[i];
     v.yv[j] = ok ? v0 : 0.f;
     v.e[j] = ok ? v1 : 0.f;
-    if constexpr (!TILE) {
+    if constexpr (!REGS) {
       const float v2 = f.d_emb[i];
       v.de[j] = ok ? v2 : 0.f;
     }
@@ -125,12 +128,12 @@ __device__ __forceinline__ void tail_bwd_load_rows(const TailBwdArgs& f, int r1,
 }
 
 // The head of row chunk `chunk` on a workgroup of NT threads (1024 or 512).  smem: kTailBwdLds bytes.
-// TILE: the chunk is 64 rows (rows_per_chunk == 64), `tile` holds their d_emb as f32 [64][kTailTileLd] (written by this
-// workgroup: the body synchronises before it reads it), and pk / pv were loaded by the caller (tail_bwd_load_const /
-// tail_bwd_load_rows<NT, true> of the chunk's rows) -- ahead of whatever it had to wait for.
-template <int NT, bool TILE>
+// REGS: the chunk is 64 rows (rows_per_chunk == 64) and pk / pv were loaded by the caller (tail_bwd_load_const /
+// tail_bwd_load_rows<NT, true> of the chunk's rows) -- ahead of whatever it had to wait for --, which also left d_emb in pv->de:
+// thread (lane, wave) holds rows wave R + j of column lane, zero past the chunk's last row and past D.  smem is free when the body starts.
+template <int NT, bool REGS>
 __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, bool drop, float p, uint64_t seed, char* smem,
-                                              const float* tile, const TailBwdConst<NT>* pk, const TailBwdRows<NT>* pv) {
+                                              const TailBwdConst<NT>* pk, const TailBwdRows<NT>* pv) {
   static_assert(NT == 1024 || NT == 512, "the ordered parts run in the first four waves; the rest splits 64 rows over NT / 64");
   constexpr int NWV = NT / 64, R = 64 * 64 / NT;
   const ColArgs& a = f.col;
@@ -147,7 +150,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
   const int lane = c, wave = rq;
   const int r0 = chunk * a.rows_per_chunk, r1 = min(a.B, r0 + a.rows_per_chunk);
   TailBwdConst<NT> k;
-  if constexpr (TILE) k = *pk;
+  if constexpr (REGS) k = *pk;
   else tail_bwd_load_const<NT>(f, k);
 #pragma unroll
   for (int j = 0; j < R; ++j) {
@@ -162,15 +165,8 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
   for (int b0 = r0; b0 < r1; b0 += 64) {
     // 1. d_y of rows b0 .. b0 + 63: one wave per row as l2norm_bwd_kernel, R independent rows per wave in flight
     TailBwdRows<NT> v;
-    if constexpr (TILE) {
+    if constexpr (REGS) {
       v = *pv;
-      __syncthreads();                                   // the caller's tile is written
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        const int row = wave * R + j;
-        const float v2 = tile[row * kTailTileLd + lane];
-        v.de[j] = (b0 + row < r1 && lane < D) ? v2 : 0.f;
-      }
     } else {
       tail_bwd_load_rows<NT, false>(f, r1, b0, v);
     }
@@ -208,6 +204,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
       sc[j] = (c < H && r < r1) ? dropout_scale(drop, p, seed, a.salt + (uint64_t)((int64_t)r * H + c)) : 0.f;
     }
     __syncthreads();
+    TT_HEAD_STAMP(0);
     // 2. bias-gradient column sums of d_y, data gradient d_act = d_y . W_out, weight-gradient tile += d_y^T . act
     const int wr = (wave >> 1) & 1, wc = wave & 1, li = lane & 31, lh = lane >> 5;
     tl_f32x16 acc;
@@ -230,12 +227,14 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
       }
     }
     __syncthreads();                                     // DY (as d_y), dyA and dyT have been read
+    TT_HEAD_STAMP(1);
     if (wave < 4) {
       const int n = wc * 32 + li;
 #pragma unroll
       for (int r = 0; r < 16; ++r) DY[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * kTailLdF + n] = acc[r];
     }
     __syncthreads();
+    TT_HEAD_STAMP(2);
     // 3. d_act (times the dropout scale) out; da and xhat staged for the ordered column sums
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -246,6 +245,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
       XH[row * kTailLdF + c] = xh[j];
     }
     __syncthreads();
+    TT_HEAD_STAMP(3);
     if (t < 256 && c < H) {                              // colsum_partial_kernel's order: rows r0 + rq, + 4, ...
       const int nrow = min(64, r1 - b0);
       for (int row = rq; row < nrow; row += 4) {
@@ -255,6 +255,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
       }
     }
     __syncthreads();
+    TT_HEAD_STAMP(4);
   }
   if (t < 256) {
     sh[0][rq][c] = s0;
@@ -262,6 +263,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
     sh[2][rq][c] = cs;
   }
   __syncthreads();
+  TT_HEAD_STAMP(5);
   if (t < 64) {
     if (c < H) {
       float* q = a.partial + (int64_t)chunk * 2 * H;
@@ -280,6 +282,7 @@ __device__ __forceinline__ void tail_bwd_head(const TailBwdArgs& f, int chunk, b
       if (m < D && n < H) ws[(int64_t)m * H + n] = accw[r];
     }
   }
+  TT_HEAD_STAMP(6);
 }
 
 }  // namespace tttail

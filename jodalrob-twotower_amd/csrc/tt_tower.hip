@@ -1040,7 +1040,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_kernel(Batch<TailBwdArg
   if ((int)blockIdx.x >= f.col.nchunks) return;
   __shared__ __attribute__((aligned(16))) char smem[kTailBwdLds];
   const uint64_t seed = drop ? seed_of(seed0, seed_dev) : 0;
-  tail_bwd_head<kTailThreads, false>(f, blockIdx.x, drop, p, seed, smem, nullptr, nullptr, nullptr);
+  tail_bwd_head<kTailThreads, false>(f, blockIdx.x, drop, p, seed, smem, nullptr, nullptr);
 }
 
 // (D) S1 / S2 finish (every workgroup, colsum_finish_kernel's order) + BN backward apply in place on the (already
@@ -1053,7 +1053,7 @@ struct TailApplyArgs {
 };
 
 // (fr_on: the FIRST grid row is one workgroup running the symmetric score forward's loss reduction, as in tail_bwd_kernel -- its
-// host when the score backward's launch runs the backward head, whose workgroups have 512 threads)
+// host when the score backward's launch runs the backward head and the pass has no first-block launch (gemm_back_kernel) to leave it to)
 __global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(Batch<TailApplyArgs> batch, Finish2Rider fr, int fr_on) {
   if (fr_on && blockIdx.y == 0) {
     if (blockIdx.x == 0) finish2_body(fr);
@@ -1822,6 +1822,23 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   for (int t = 0; t < n; ++t) tn[t].bf16 = nn[t].bf16 = P[0]->compute_dtype == TT_BF16;
   // the slab reductions of all weight-gradient GEMMs run as ONE launch at the end (nothing in this pass reads them)
   TnPending pend;
+  // first block + projection as ONE launch (tt_gemm.h: GemmBack; d_pre of block 0 arrives in scratch[0]): its items, and whether
+  // the pass will take it -- asked twice: by the tail, which leaves a queued loss reduction to that launch, and at the launch
+  GemmBack gb[TT_MAX_SIDES];
+  auto back_items = [&]() {
+    if (nh < 1 || P[0]->compute_dtype != TT_BF16) return false;
+    for (int t = 0; t < n; ++t) {
+      const tt_tower_grads* g = G[t];
+      const int wx = P[t]->h0 + P[t]->kcat_e;
+      if (P[t]->flags & TT_TOWER_UNFUSED_BACK) return false;
+      gb[t] = GemmBack{g->scratch[0], P[t]->hidden[0], A[t]->x, wx, wx, P[t]->x_dtype == TT_BF16, A[t]->dense, P[t]->din, P[t]->din,
+                       P[t]->w[0], P[t]->h0, reinterpret_cast<float*>(g->d_x), wx, P[t]->dx_dtype == TT_BF16, g->w[0], g->b[0],
+                       g->w_proj, g->b_proj, ws[t].tn[1], ws[t].tn_bytes[1], ws[t].tn[0], ws[t].tn_bytes[0], B};
+      gb[t].w16 = P[t]->w_bf16[0];
+    }
+    return tt_gemm_back_supported(gb, n);
+  };
+  bool loss_to_back = false;                             // the tail left a queued loss reduction to that launch
   if (fused) {
     // L2-normalise backward, both output-layer GEMMs and the BN column sums of the last block in one kernel; the BN
     // backward apply (after the batch-wide S1 / S2) in a second
@@ -1863,7 +1880,10 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
         return rc;
       }
     }
-    const int fr_on = (mine & TT_DQ_LOSS) ? 1 : 0;       // a queued loss reduction rides in one extra grid row of one of the two launches
+    // a queued loss reduction rides in tail_bwd's extra grid row; where the score backward ran the head (512-thread workgroups) it
+    // waits for the first block's launch below -- only the host reads it, and tail_bwd_apply's workgroups are on the step's chain
+    // -- or, in a pass without that launch, rides in tail_bwd_apply's extra grid row
+    const int fr_on = (mine & TT_DQ_LOSS) ? 1 : 0;
     if (phase != 2 && !hosted) {
       tail_bwd_kernel<<<dim3((unsigned)cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev, ctx->dq->loss,
                                                                                            fr_on);
@@ -1878,8 +1898,8 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
       return TT_OK;
     }
     {
-      // (the head ran in the score backward's 512-thread workgroups: the loss reduction rides here instead -- only the host reads it)
-      const int fr_here = hosted ? fr_on : 0;
+      loss_to_back = hosted && fr_on && back_items();
+      const int fr_here = hosted && fr_on && !loss_to_back ? 1 : 0;
       tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)(n + fr_here)), kTailThreads, 0, st>>>(tp, ctx->dq->loss, fr_here);
       if (fr_here) tt_deferred_taken(ctx, TT_DQ_LOSS);
       TT_LAUNCH_CHECK();
@@ -1984,19 +2004,12 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     if (i == 0 && P[0]->compute_dtype == TT_BF16) {
       // first block + projection: three independent products of d_pre in ONE launch (tt_gemm.h: GemmBack); the projection's
       // gradients come out of the slab-reduction launch, d_x[:, 0:h0] is not materialised
-      GemmBack gb[TT_MAX_SIDES];
-      bool ok = true;
-      for (int t = 0; t < n; ++t) {
-        const tt_tower_grads* g = G[t];
-        const int wx = P[t]->h0 + P[t]->kcat_e;
-        ok = ok && !(P[t]->flags & TT_TOWER_UNFUSED_BACK);
-        gb[t] = GemmBack{tn[t].A, P[t]->hidden[0], A[t]->x, wx, wx, P[t]->x_dtype == TT_BF16, A[t]->dense, P[t]->din, P[t]->din,
-                         P[t]->w[0], P[t]->h0, reinterpret_cast<float*>(g->d_x), wx, P[t]->dx_dtype == TT_BF16, g->w[0], g->b[0],
-                         g->w_proj, g->b_proj, ws[t].tn[1], ws[t].tn_bytes[1], ws[t].tn[0], ws[t].tn_bytes[0], B};
-        gb[t].w16 = P[t]->w_bf16[0];
-      }
-      if (ok && tt_gemm_back_supported(gb, n)) {
-        if (int rc = tt_gemm_back_batched(st, gb, n, &pend)) return rc;
+      if (back_items()) {
+        int mine = 0;
+        if (loss_to_back)
+          if (int rc = tt_deferred_host(ctx, TT_DQ_LOSS, st, &mine)) return rc;
+        if (int rc = tt_gemm_back_batched(st, gb, n, &pend, (mine & TT_DQ_LOSS) ? &ctx->dq->loss : nullptr)) return rc;
+        tt_deferred_taken(ctx, mine & TT_DQ_LOSS);
         if (ctx->dq->defer_slabs) return tt_deferred_queue_slabs(ctx, st, &pend);     // rides in tt_embed_grad_bwd's launch
         return tt_gemm_tn_flush(st, &pend);
       }
