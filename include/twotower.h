@@ -697,16 +697,19 @@ int tt_score_dense_bwd(tt_ctx* ctx, const float* N, const float* Cm, int64_t B, 
                        float label_smoothing, float* S, const float* stats, const float* d_loss, float* dN, float* dC,
                        void* workspace, size_t workspace_bytes, tt_stream stream);
 /* dense score matrix S[Ra, Rb] = A Bm^T * inv_t (result["similarity_matrix"], predict_batch
- * "all_similarities": two_tower_train_task.py:94, :206) */
+ * "all_similarities": two_tower_train_task.py:94, :206); an empty side (Ra == 0 or Rb == 0) launches nothing and its
+ * pointers may be NULL */
 int tt_score_matrix(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D,
                     float inv_t, float* S, int64_t lds, tt_stream stream);
 /* rank of the positive column of every row of a dense matrix (evaluator MRR / Recall@K on a given
  * similarity matrix: src/evaluation/evaluator.py:45-71):
- *   rank[r] = #{c: S[r,c] > S[r,r+off]} + #{c < r+off: S[r,c] == S[r,r+off]} */
+ *   rank[r] = #{c: S[r,c] > S[r,r+off]} + #{c < r+off: S[r,c] == S[r,r+off]},
+ *   -1 where the positive column r+off is outside [0, Ccols) (the retrieval entries' rule: such a row has no rank) */
 int tt_diag_rank_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t lds,
                       int64_t diag_offset, int32_t* rank, tt_stream stream);
 /* per-row top-k of a dense matrix, descending, ties -> lower column first (torch.topk use in
- * predict_batch :195 and evaluator.py:35); k <= 64 */
+ * predict_batch :195 and evaluator.py:35); k <= 64.  A NaN is never selected (-inf entries are, with their own column); when a
+ * row holds fewer than k non-NaN entries the remaining slots are (-inf, -1). */
 int tt_topk_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t lds, int32_t k,
                  float* vals, int64_t* idx, tt_stream stream);
 

@@ -519,13 +519,15 @@ __global__ __launch_bounds__(kThreads) void diag_rank_rows_kernel(const float* _
   if (row >= R) return;
   const int64_t pos = row + off;
   const float* s = S + row * lds;
+  if (pos < 0 || pos >= C) {                     // no positive in this row: -1, as the retrieval entries (0 would be a perfect rank)
+    if (lane == 0) rank[row] = -1;
+    return;
+  }
   int cnt = 0;
-  if (pos >= 0 && pos < C) {
-    const float d = s[pos];
-    for (int64_t c = lane; c < C; c += 64) {
-      const float v = s[c];
-      cnt += (v > d || (v == d && c < pos)) ? 1 : 0;
-    }
+  const float d = s[pos];
+  for (int64_t c = lane; c < C; c += 64) {
+    const float v = s[c];
+    cnt += (v > d || (v == d && c < pos)) ? 1 : 0;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
@@ -654,7 +656,7 @@ int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra
 
 int tt_score_matrix(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float* S,
                     int64_t lds, tt_stream stream) {
-  TT_CHECK_ARG(ctx && A && Bm && S, "tt_score_matrix: NULL argument");
+  TT_CHECK_ARG(ctx && (Ra == 0 || Rb == 0 || (A && Bm && S)), "tt_score_matrix: NULL argument");
   TT_CHECK_ARG(Ra >= 0 && Rb >= 0 && D >= 1 && lds >= Rb, "tt_score_matrix: bad shape");
   TT_CHECK_ARG(Ra < ((int64_t)1 << 31) && Rb < ((int64_t)1 << 31), "tt_score_matrix: too many rows");
   return tt_gemm_nt(reinterpret_cast<hipStream_t>(stream), A, D, Bm, D, nullptr, S, lds, Ra, Rb, D, false, inv_t);
@@ -673,6 +675,7 @@ int tt_diag_rank_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int
 int tt_topk_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t lds, int32_t k, float* vals, int64_t* idx,
                  tt_stream stream) {
   TT_CHECK_ARG(ctx && (R == 0 || (S && vals && idx)), "tt_topk_rows: NULL argument");
+  TT_CHECK_ARG(R >= 0 && Ccols >= 1 && lds >= Ccols, "tt_topk_rows: bad shape");
   TT_CHECK_ARG(k >= 1 && k <= 64 && k <= Ccols, "tt_topk_rows: k=%d not in [1, min(64, %lld)]", k, (long long)Ccols);
   if (R == 0) return TT_OK;
   topk_rows_kernel<<<(unsigned)tt_cdiv(R, 4), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(S, R, Ccols, lds, k, vals, idx);

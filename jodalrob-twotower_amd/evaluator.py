@@ -25,11 +25,21 @@ class TwoTowerEvaluator:
         s = similarity_matrix.detach().float()
         return ops.diag_rank_rows(s if s.stride(1) == 1 else s.contiguous())
 
+    @staticmethod
+    def _need_every_positive(similarity_matrix: torch.Tensor, who: str):
+        """Rows past the last column have no positive (rank -1) and so no reciprocal rank: the reference fails there too (:66,
+        .item() on an empty match).  Raised from the shapes, before anything is launched."""
+        r, c = similarity_matrix.shape
+        if r > c:
+            raise ValueError(f"{who}: a [{r}, {c}] similarity matrix has no positive column for rows {c}..{r - 1}")
+
     def compute_recall_at_k(self, similarity_matrix: torch.Tensor, k: int) -> torch.Tensor:        # :20-43
         k = min(k, similarity_matrix.size(1))
-        return (self._ranks(similarity_matrix) < k).float().mean()
+        ranks = self._ranks(similarity_matrix)
+        return ((ranks >= 0) & (ranks < k)).float().mean()      # rank -1: no positive in the row (R > C), a miss as in the reference
 
     def compute_mrr(self, similarity_matrix: torch.Tensor) -> torch.Tensor:                         # :45-71
+        self._need_every_positive(similarity_matrix, "compute_mrr")
         return (1.0 / (self._ranks(similarity_matrix).float() + 1.0)).mean()
 
     def metrics_from_ranks(self, ranks: torch.Tensor, basic: Dict) -> Dict[str, float]:
@@ -45,6 +55,7 @@ class TwoTowerEvaluator:
                 "recall@10_improvement": r10 > rr10}
 
     def compute_comprehensive_metrics(self, similarity_matrix: torch.Tensor, basic_metrics: Dict) -> Dict[str, float]:   # :73-121
+        self._need_every_positive(similarity_matrix, "compute_comprehensive_metrics")
         return self.metrics_from_ranks(self._ranks(similarity_matrix), basic_metrics)
 
     @torch.no_grad()

@@ -864,9 +864,10 @@ def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=N
 # ---------------------------------------------------------------------------------------------- misc
 def linear_fwd(X, W, bias, relu=False):
     dev, M, K, N = X.device, X.shape[0], X.shape[1], W.shape[0]
-    assert X.stride(1) == 1 and W.is_contiguous()
+    assert (M == 0 or X.stride(1) == 1) and W.is_contiguous()
     Y = torch.empty((M, N), dtype=torch.float32, device=dev)
-    L.check(L.load().tt_linear_fwd(L.ctx(dev), L.ptr(X), X.stride(0), L.ptr(W), L.ptr(bias), L.ptr(Y), N, M, N, K, int(relu),
+    ldx = X.stride(0) if M else K                                 # (an empty tensor's strides say nothing: they may be 0)
+    L.check(L.load().tt_linear_fwd(L.ctx(dev), L.ptr(X), ldx, L.ptr(W), L.ptr(bias), L.ptr(Y), N, M, N, K, int(relu),
                                    L.stream(dev)), "tt_linear_fwd")
     return Y
 
