@@ -760,6 +760,35 @@ int tt_excl_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const flo
                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
                               const int64_t* excl_offsets, const int32_t* excl_rows, void* workspace, size_t workspace_bytes,
                               tt_stream stream);
+/* Retrieval with per-query attribute filters (eligibility): the exclusion entries with tags, W, q_any and q_all after `excl_rows`.
+ *   tags uint32 [nC][W]: W tag words per catalogue row, 1 <= W <= 4 (up to 128 attribute bits), 16-byte aligned.
+ *   q_any uint32 [nQ][W] or NULL: if any[q, :] is all zero, query q is unrestricted on this predicate; otherwise row c must share
+ *     at least one bit with it: there is a w with tags[c,w] & any[q,w] != 0.
+ *   q_all uint32 [nQ][W] or NULL: row c must hold every required bit: tags[c,w] & all[q,w] == all[q,w] for all w (an all-zero
+ *     all[q, :] requires nothing).
+ *   eligible(q, c) is the AND of the two.  A NULL mask pointer makes its predicate always true; both NULL is an argument error.
+ *   The masks are 4-byte aligned.  excl_offsets and excl_rows may both be NULL here (no lists); one NULL and one not is an error.
+ *   With lists, a row counts when it is eligible AND not in E_q.
+ *   top-k: the k best eligible rows, value descending, ties to the lower index; slots beyond the eligible rows are -inf / -1.
+ *   rank:  #{eligible c : s > s_p} + #{eligible c < p : s == s_p}; p never counts against itself, so whether p is eligible
+ *          makes no difference; -1 where p is outside [0, nC).
+ * (One-hot bits under `any` give "is one of these"; flag bits under `all` give "holds every one of these"; equality on a code
+ * of V values is an `all` test on 2 ceil(log2 V) bits, the tag holding the code's binary digits and next to them their
+ * complement, the query requiring exactly the encoding of its code and nothing for "don't care".)
+ * With all-zero masks the results are bitwise those of the plain entry (with lists: of the exclusion entry); they are bitwise
+ * identical across runs and split counts.  No tag of a row at or past nC is read.  Same workspace
+ * (tt_retrieve_workspace_bytes), three launches on `stream`, no synchronisation, no allocation, and the graph capture rules of
+ * the plain entries.  A bad argument returns TT_ERR_INVALID_ARG and launches nothing. */
+int tt_filt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, const uint32_t* tags, int32_t W,
+                               const uint32_t* q_any, const uint32_t* q_all, void* workspace, size_t workspace_bytes,
+                               tt_stream stream);
+int tt_filt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, const uint32_t* tags, int32_t W,
+                              const uint32_t* q_any, const uint32_t* q_all, void* workspace, size_t workspace_bytes,
+                              tt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Generic Linear used by the one-off feature projection -- replaces FeatureProjector.forward

@@ -21,6 +21,11 @@
 // (binary-searched to the split's first row) and the next excluded row in a register: a tile without excluded rows costs one
 // compare and one __any; otherwise the wave walks the tile's entries and sets the matching scores to -inf, which neither the
 // filter (threshold >= -inf, strict compare) nor the rank counts (strict compare against a finite s_p) ever take.
+//
+// Attribute filters (tt_filt_retrieve_topk_*: the sweep's FILT = true instantiations): catalogue row c carries W tag words, query
+// q an `any` and an `all` mask of W words; rows that fail (tags & any) != 0 (unless any == 0) or (tags & all) == all get -inf at
+// the same point as the excluded ones.  A tile's 32 W tag words are contiguous: the wave reads them with one coalesced load
+// (W > 2: two, 16 rows each) a tile ahead, one word per lane, and every lane fetches the words of its 16 rows with ds_bpermute.
 #include "tt_score_bf16.h"
 
 #include <math.h>
@@ -129,6 +134,10 @@ struct RetArgs {
   int32_t* rank;              // [nQ] out or NULL
   const int64_t* excl_off;    // [nQ + 1] CSR offsets of the exclusion lists (EXCL sweep only)
   const int32_t* excl_rows;   // [excl_off[nQ]] ascending catalogue rows per query
+  const uint32_t* tags;       // [nC][W] tag words of the catalogue rows (FILT sweep only)
+  const uint32_t* q_any;      // [nQ][W] or NULL: a row must share a bit with a non-zero mask
+  const uint32_t* q_all;      // [nQ][W] or NULL: a row must hold every bit of the mask
+  int W;                      // 1 .. 4
 };
 
 __device__ __forceinline__ int64_t positive_of(const RetArgs& a, int64_t q) { return a.pos64 ? a.pos64[q] : (int64_t)a.pos32[q]; }
@@ -157,8 +166,30 @@ __global__ __launch_bounds__(64) void retrieve_pos_kernel(Tile tile, RetArgs a) 
   }
 }
 
+// attribute filter of one tile: -inf for the rows whose tags miss a required bit (mall) or share none with a non-zero many.
+// tg0 / tg1: the tile's tag words as the sweep loads them; the word of row rowmap(r, h) sits in lane (row - R j) WW + w of tg[j].
+template <int WW>
+__device__ __forceinline__ void filter_tile(f32x16& acc, int h, uint32_t tg0, uint32_t tg1, const uint32_t (&many)[4],
+                                            const uint32_t (&mall)[4], uint32_t hit0) {
+  constexpr int R = WW <= 2 ? 32 : 16;
+  int base = 16 * h * WW;                                       // byte address of lane 4 h WW
+  asm volatile("" : "+v"(base));                                // opaque per tile: base + constant folds into the offset field
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = rowmap(r, 0), j = row / R;
+    uint32_t bad = 0u, hit = hit0;
+#pragma unroll
+    for (int w = 0; w < WW; ++w) {
+      const uint32_t x = (uint32_t)__builtin_amdgcn_ds_bpermute(base + 4 * ((row - R * j) * WW + w), (int)(j ? tg1 : tg0));
+      bad |= mall[w] & ~x;
+      hit |= many[w] & x;
+    }
+    if (bad != 0u || hit == 0u) acc[r] = -INFINITY;
+  }
+}
+
 // ---- sweep ------------------------------------------------------------------------------------------------------------------
-template <class Tile, bool EXCL>
+template <class Tile, bool EXCL, bool FILT>
 __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
   extern __shared__ uint32_t ret_lds[];
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
@@ -201,6 +232,30 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
     }
     e = lo;
     nxt = e < ee ? a.excl_rows[e] : INT32_MAX;
+  }
+  // attribute filter: the query's masks (hit0: an all-zero `any` is satisfied from the start) and the tile's tag words.  tg[j]
+  // holds the words of rows 32 t + R j .. + R - 1 (R = 32 for W <= 2, else 16), word i of them in lane i
+  const int W = FILT ? a.W : 0;
+  uint32_t many[4] = {0u, 0u, 0u, 0u}, mall[4] = {0u, 0u, 0u, 0u};
+  uint32_t hit0 = 1u, tg[2] = {0u, 0u};
+  auto load_tags = [&](int64_t t) {                             // clamped: no word at or past tags[nC W] is read
+    const int64_t last = a.nC * W - 1, i0 = 32 * t * W + lane, i1 = i0 + 16 * W;
+    tg[0] = a.tags[i0 < last ? i0 : last];
+    if (W > 2) tg[1] = a.tags[i1 < last ? i1 : last];
+  };
+  if (FILT) {
+    if (qok) {
+      uint32_t o = 0u;
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        if (w < W) {
+          many[w] = a.q_any ? a.q_any[q * W + w] : 0u;
+          mall[w] = a.q_all ? a.q_all[q * W + w] : 0u;
+          o |= many[w];
+        }
+      hit0 = o == 0u ? 1u : 0u;
+    }
+    load_tags(tb);
   }
   int rcnt = 0;
   float thr = -INFINITY;                                        // the query's k-th best so far (both lanes of a query agree)
@@ -274,6 +329,8 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
     f32x16 acc;
     tile.score(f, t, c, h, acc);
     if (t + 1 < te) tile.load(t + 1, c, h, f);                 // next tile's operands fly while this one is filtered
+    const uint32_t tg0 = tg[0], tg1 = tg[1];
+    if (FILT && t + 1 < te) load_tags(t + 1);
     const int64_t r0 = 32 * t;
     if (r0 + 32 > a.nC) {                                       // ragged last tile: rows past the catalogue never count
 #pragma unroll
@@ -295,6 +352,12 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
         for (int r = 0; r < 16; ++r)
           if ((xm >> rowmap(r, h)) & 1u) acc[r] = -INFINITY;
       }
+    }
+    if (FILT) {                                                 // (W is wave-uniform: one of four straight-line copies)
+      if (W == 1) filter_tile<1>(acc, h, tg0, tg1, many, mall, hit0);
+      else if (W == 2) filter_tile<2>(acc, h, tg0, tg1, many, mall, hit0);
+      else if (W == 3) filter_tile<3>(acc, h, tg0, tg1, many, mall, hit0);
+      else filter_tile<4>(acc, h, tg0, tg1, many, mall, hit0);
     }
     if (want_rank) {
       if (!__any(t == tp)) {                                    // whole tile before (ties count) or after (they do not) p
@@ -452,10 +515,18 @@ bool ret_shape_ok(int64_t nQ, int64_t nC, int D, int k) {
   return nQ >= 1 && nC >= 1 && nC < (int64_t(1) << 31) && D >= 1 && D <= 256 && k >= 0 && k <= 64 && k <= nC;
 }
 
+struct RetFilt {              // attribute filter of a call (tags == NULL: none)
+  const uint32_t* tags;
+  int32_t W;
+  const uint32_t* q_any;
+  const uint32_t* q_all;
+};
+constexpr RetFilt kNoFilt{nullptr, 0, nullptr, nullptr};
+
 template <class Tile>
 int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k, const void* positives,
                int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
-               const int32_t* excl_rows, void* workspace, hipStream_t st) {
+               const int32_t* excl_rows, const RetFilt& flt, void* workspace, hipStream_t st) {
   const int64_t nT = tt_cdiv(nC, 32), nQt = tt_cdiv(nQ, 32);
   const int cap = ret_max_splits(nC);
   int64_t S;
@@ -486,14 +557,24 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   a.rank = positives ? rank : nullptr;
   a.excl_off = excl_off;
   a.excl_rows = excl_rows;
+  a.tags = flt.tags;
+  a.q_any = flt.q_any;
+  a.q_all = flt.q_all;
+  a.W = flt.W;
   if (positives) {
     retrieve_pos_kernel<Tile><<<(unsigned)nQt, 64, 0, st>>>(tile, a);
     TT_LAUNCH_CHECK();
   }
   const size_t lds = (size_t)kRetWaves * (k + kRetCap) * 32 * 8;
   const dim3 grid((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S);
-  if (excl_off) retrieve_sweep_kernel<Tile, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
-  else retrieve_sweep_kernel<Tile, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  if (flt.tags) {
+    if (excl_off) retrieve_sweep_kernel<Tile, true, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    else retrieve_sweep_kernel<Tile, false, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  } else if (excl_off) {
+    retrieve_sweep_kernel<Tile, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  } else {
+    retrieve_sweep_kernel<Tile, false, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  }
   TT_LAUNCH_CHECK();
   const int64_t n = S * k;
   if (n <= 128) retrieve_merge_kernel<2><<<(unsigned)nQ, 64, 0, st>>>(a);
@@ -522,17 +603,26 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   TT_CHECK_ARG(excl_offsets != nullptr && tt_aligned(excl_offsets, 8), NAME ": excl_offsets NULL or not 8-byte aligned");       \
   TT_CHECK_ARG(excl_rows != nullptr && tt_aligned(excl_rows, 4), NAME ": excl_rows NULL or not 4-byte aligned")
 
-// (arguments checked by the caller; excl_off == NULL launches the plain sweep)
+// filter entries: tags with 1 <= W <= 4 and at least one mask; the exclusion pair both given or both NULL
+#define TT_RET_CHECK_FILT(NAME)                                                                                                   \
+  TT_CHECK_ARG(W >= 1 && W <= 4, NAME ": W = %d tag words (need 1 <= W <= 4)", W);                                               \
+  TT_CHECK_ARG(tags != nullptr && tt_aligned(tags, 16), NAME ": tags NULL or not 16-byte aligned");                              \
+  TT_CHECK_ARG(q_any != nullptr || q_all != nullptr, NAME ": q_any and q_all both NULL (use the plain or the exclusion entry)"); \
+  TT_CHECK_ARG(tt_aligned(q_any, 4) && tt_aligned(q_all, 4), NAME ": q_any or q_all not 4-byte aligned");                        \
+  TT_CHECK_ARG((excl_offsets == nullptr) == (excl_rows == nullptr), NAME ": excl_offsets and excl_rows go together");            \
+  TT_CHECK_ARG(tt_aligned(excl_offsets, 8) && tt_aligned(excl_rows, 4), NAME ": excl_offsets not 8- or excl_rows not 4-byte aligned")
+
+// (arguments checked by the caller; excl_off == NULL launches the sweep without lists, flt.tags == NULL the one without filter)
 int ret_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D, int32_t k,
              const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
-             const int32_t* excl_rows, void* workspace, hipStream_t st) {
+             const int32_t* excl_rows, const RetFilt& flt, void* workspace, hipStream_t st) {
   const int Dp = padded_d(D);
 #define TT_RET_BF16(KS)                                                                                                 \
   do {                                                                                                                  \
     TileBf16<KS> tile{};                                                                                                \
     tile.q_rows = view(Q_packed, nQ, D).rows;                                                                           \
     tile.c_rows = view(C_packed, nC, D).rows;                                                                           \
-    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st); \
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, flt, workspace, st); \
   } while (0)
   if (Dp == 32) TT_RET_BF16(2);
   if (Dp == 64) TT_RET_BF16(4);
@@ -543,13 +633,13 @@ int ret_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed
 
 int ret_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t, int32_t k,
             const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
-            const int32_t* excl_rows, void* workspace, hipStream_t st) {
+            const int32_t* excl_rows, const RetFilt& flt, void* workspace, hipStream_t st) {
   if (D % 4 == 0 && tt_aligned(Q, 16) && tt_aligned(Cm, 16)) {
     TileF32<true> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
-    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st);
+    return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, flt, workspace, st);
   }
   TileF32<false> tile{Q, Cm, nQ, nC, D, inv_t, nullptr};
-  return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, workspace, st);
+  return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, flt, workspace, st);
 }
 
 }  // namespace
@@ -566,7 +656,7 @@ int tt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const v
                           size_t workspace_bytes, tt_stream stream) {
   TT_RET_CHECK_COMMON("tt_retrieve_topk_bf16");
   TT_RET_CHECK_BF16("tt_retrieve_topk_bf16");
-  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, workspace,
+  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, kNoFilt, workspace,
                   reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -575,7 +665,7 @@ int tt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* C
                          size_t workspace_bytes, tt_stream stream) {
   TT_RET_CHECK_COMMON("tt_retrieve_topk_f32");
   TT_CHECK_ARG(Q && Cm, "tt_retrieve_topk_f32: NULL embeddings");
-  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, workspace,
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, nullptr, nullptr, kNoFilt, workspace,
                  reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -587,7 +677,7 @@ int tt_excl_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, co
   TT_RET_CHECK_BF16("tt_excl_retrieve_topk_bf16");
   TT_RET_CHECK_EXCL("tt_excl_retrieve_topk_bf16");
   return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
-                  workspace, reinterpret_cast<hipStream_t>(stream));
+                  kNoFilt, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 int tt_excl_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
@@ -597,8 +687,32 @@ int tt_excl_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const flo
   TT_RET_CHECK_COMMON("tt_excl_retrieve_topk_f32");
   TT_CHECK_ARG(Q && Cm, "tt_excl_retrieve_topk_f32: NULL embeddings");
   TT_RET_CHECK_EXCL("tt_excl_retrieve_topk_f32");
-  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows, workspace,
-                 reinterpret_cast<hipStream_t>(stream));
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows, kNoFilt,
+                 workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_filt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, const uint32_t* tags, int32_t W,
+                               const uint32_t* q_any, const uint32_t* q_all, void* workspace, size_t workspace_bytes,
+                               tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_filt_retrieve_topk_bf16");
+  TT_RET_CHECK_BF16("tt_filt_retrieve_topk_bf16");
+  TT_RET_CHECK_FILT("tt_filt_retrieve_topk_bf16");
+  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
+                  RetFilt{tags, W, q_any, q_all}, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_filt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, const uint32_t* tags, int32_t W,
+                              const uint32_t* q_any, const uint32_t* q_all, void* workspace, size_t workspace_bytes,
+                              tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_filt_retrieve_topk_f32");
+  TT_CHECK_ARG(Q && Cm, "tt_filt_retrieve_topk_f32: NULL embeddings");
+  TT_RET_CHECK_FILT("tt_filt_retrieve_topk_f32");
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
+                 RetFilt{tags, W, q_any, q_all}, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

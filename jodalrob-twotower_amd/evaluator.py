@@ -108,7 +108,7 @@ class TwoTowerEvaluator:
 
     @torch.no_grad()
     def evaluate_catalog(self, model, notice_store, index, pairs, ks=(5, 10), batch_size: int = 8192,
-                         filter_pairs=None) -> Dict[str, float]:
+                         filter_pairs=None, allow=None, require=None) -> Dict[str, float]:
         """Recall@k and MRR against the WHOLE catalogue instead of the other B - 1 companies of a batch.  `pairs` [P, 2] holds
         (notice entity, company entity) rows; `index` is a retrieval.CatalogIndex whose row i is company entity i
         (CatalogIndex.from_store).  Each pair's notice goes through the notice tower (eval mode, batch_size rows at a time)
@@ -116,7 +116,9 @@ class TwoTowerEvaluator:
         the in-batch metric, a notice's OTHER positive companies count as negatives -- unless `filter_pairs` [P', 2] (notice,
         company) rows are given: then every company paired with the query's notice in filter_pairs is left out of its ranking
         (the filtered rank; the positive itself never counts against itself, so filter_pairs may hold it, e.g. all known
-        train and test pairs).  Returns recall@k for every k in ks, mrr, catalog_size and num_queries.  The model's
+        train and test pairs).  allow / require: one attribute mask row per row of `pairs` ([P] or [P, W] integers, for an index
+        built with tags=): each query is ranked among the rows eligible under its masks only (CatalogIndex.search); they
+        combine with filter_pairs.  Returns recall@k for every k in ks, mrr, catalog_size and num_queries.  The model's
         train()/eval() state is restored afterwards."""
         from .retrieval import CatalogIndex, exclusions_from_pairs
         if not isinstance(index, CatalogIndex):
@@ -143,6 +145,7 @@ class TwoTowerEvaluator:
             if filter_pairs.dim() != 2 or filter_pairs.shape[1] != 2:
                 raise ValueError("filter_pairs must be a [P', 2] array of (notice, company) entity rows")
             filter_pairs = filter_pairs.to(device=index.device, dtype=torch.int64)
+        filt = index._check_filter(allow, require, int(pairs.shape[0]))
         modes = [(m, m.training) for m in model.modules()]
         model.eval()
         try:
@@ -151,7 +154,9 @@ class TwoTowerEvaluator:
                 p = pairs[s:s + batch_size]
                 q = tower_model.get_notice_embeddings(notice_store.gather(p[:, 0].contiguous()))
                 ex = None if filter_pairs is None else exclusions_from_pairs(p[:, 0], filter_pairs, index.size)
-                ranks.append(index.rank(q, p[:, 1].contiguous(), exclude=ex))
+                al = None if filt is None or filt[2] is None else filt[2][s:s + batch_size]
+                rq = None if filt is None or filt[3] is None else filt[3][s:s + batch_size]
+                ranks.append(index.rank(q, p[:, 1].contiguous(), exclude=ex, allow=al, require=rq))
             r = torch.cat(ranks) if len(ranks) > 1 else ranks[0]
         finally:
             for m, was in modes:

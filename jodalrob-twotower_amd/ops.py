@@ -795,10 +795,12 @@ def retrieve_workspace_bytes(nQ: int, nC: int, D: int, k: int) -> int:
     return int(L.load().tt_retrieve_workspace_bytes(int(nQ), int(nC), int(D), int(k)))
 
 
-def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=None):
+def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=None, filt=None):
     """One tt_retrieve_topk_* call: Q / C are packed bf16 images (bf16=True) or f32 [n, D] rows.  Returns (vals, idx, rank);
     vals / idx are None for k = 0, rank is None without positives.  exclude=(offsets int64 [nQ + 1], rows int32): per-query
-    exclusion lists in CSR form, each list ascending (tt_excl_retrieve_topk_*)."""
+    exclusion lists in CSR form, each list ascending (tt_excl_retrieve_topk_*).  filt=(tags int32 [nC, W], W, any, all):
+    attribute filter (tt_filt_retrieve_topk_*, with or without exclude); any / all are int32 [nQ, W] masks or None, not
+    both None."""
     dev = C.device
     lib = L.load()
     vals = torch.empty((nQ, k), dtype=torch.float32, device=dev) if k else None
@@ -820,6 +822,27 @@ def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=Non
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     pos_i64 = 1 if positives is not None and positives.dtype == torch.int64 else 0
+    if filt is not None:
+        tags, W, m_any, m_all = filt
+        W = int(W)
+        if tags.dtype != torch.int32 or tags.shape != (nC, W) or not tags.is_contiguous() or tags.device != dev:
+            raise ValueError(f"tags must be a contiguous int32 tensor of shape ({nC}, {W}) on {dev}")
+        for what, m in (("any", m_any), ("all", m_all)):
+            if m is not None and (m.dtype != torch.int32 or m.shape != (nQ, W) or not m.is_contiguous() or m.device != dev):
+                raise ValueError(f"the {what} mask must be a contiguous int32 tensor of shape ({nQ}, {W}) on {dev}")
+        off, rows = (off, rows) if exclude is not None else (None, None)
+        name = "tt_filt_retrieve_topk_bf16" if bf16 else "tt_filt_retrieve_topk_f32"
+        with _timed(name):
+            if bf16:
+                rc = lib.tt_filt_retrieve_topk_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, k, L.ptr(positives), pos_i64,
+                                                    L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(tags), W,
+                                                    L.ptr(m_any), L.ptr(m_all), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            else:
+                rc = lib.tt_filt_retrieve_topk_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, k, L.ptr(positives), pos_i64,
+                                                   L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(tags), W,
+                                                   L.ptr(m_any), L.ptr(m_all), L.ptr(workspace), workspace.numel(), L.stream(dev))
+            L.check(rc, name)
+        return vals, idx, rank
     if exclude is None:
         name = "tt_retrieve_topk_bf16" if bf16 else "tt_retrieve_topk_f32"
         with _timed(name):
@@ -845,20 +868,20 @@ def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=Non
     return vals, idx, rank
 
 
-def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None, exclude=None):
+def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None, exclude=None, filt=None):
     """Top-k of every query over the whole catalogue (tt_retrieve_topk_bf16 / _f32): (vals f32 [nQ, k], idx int64 [nQ, k]),
     value descending, ties to the lower index.  With positives, (vals, idx, rank) from the same sweep.  exclude=(offsets,
     rows): query q's rows rows[offsets[q]:offsets[q+1]] (ascending) are left out of its top-k and rank
-    (tt_excl_retrieve_topk_*)."""
-    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude)
+    (tt_excl_retrieve_topk_*).  filt=(tags, W, any, all): only rows eligible under the query's masks (tt_filt_retrieve_topk_*)."""
+    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude, filt)
     return (vals, idx) if positives is None else (vals, idx, rank)
 
 
-def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=None, exclude=None):
+def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=None, exclude=None, filt=None):
     """Rank of each query's positive among all catalogue rows (k = 0 call): int32 [nQ],
     #{c : s > s_p} + #{c < p : s == s_p}, -1 for a positive outside [0, nC).  With exclude=(offsets, rows), only rows outside
-    the query's list count."""
-    return _retrieve(Q, nQ, C, nC, D, 0, inv_t, bf16, positives, workspace, exclude)[2]
+    the query's list count; with filt=(tags, W, any, all), only eligible rows."""
+    return _retrieve(Q, nQ, C, nC, D, 0, inv_t, bf16, positives, workspace, exclude, filt)[2]
 
 
 # ---------------------------------------------------------------------------------------------- misc

@@ -13,6 +13,14 @@ Every search also takes exclude=(offsets, rows), per-query exclusion lists in CS
 rows[offsets[i]:offsets[i+1]] are left out of its top-k and its rank, inside the same sweep
 (tt_excl_retrieve_topk_bf16 / _f32).  exclusions_from_pairs builds them from known (query key, row) pairs -- the filtered
 ranking of link-prediction evaluation, or the companies that already bid on a notice when serving.
+
+An index built with tags= (up to 128 attribute bits per row) also takes allow= / require=, per-query masks: a row is eligible
+for query i when it shares a bit with allow[i] (unless allow[i] is zero) and holds every bit of require[i] -- again inside the
+sweep (tt_filt_retrieve_topk_bf16 / _f32), and combinable with exclude=.  onehot_bits and equality_bits build tags and masks:
+
+    tags = equality_bits(region_code, 315) | onehot_bits(licence_class, 12, first_bit=18)      # fields: disjoint bit ranges
+    index = CatalogIndex.from_store(model, company_store, tags=tags)
+    index.search(q, 10, require=equality_bits(wanted_region, 315))                             # -1: don't care
 """
 from __future__ import annotations
 
@@ -53,13 +61,93 @@ def exclusions_from_pairs(query_keys, pairs, nC: int) -> Tuple[torch.Tensor, tor
     return offsets, rows
 
 
+MAX_TAG_WORDS = 4
+
+
+def _field(codes, n_values: int, first_bit: int, n_bits: int, words):
+    codes = torch.as_tensor(codes)
+    if codes.dim() != 1 or codes.dtype.is_floating_point or codes.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError("codes must be a 1-D integer tensor")
+    n_values, first_bit = int(n_values), int(first_bit)
+    if n_values < 1 or first_bit < 0:
+        raise ValueError(f"n_values must be >= 1 and first_bit >= 0, got {n_values} and {first_bit}")
+    need = -(-(first_bit + n_bits) // 32)
+    W = max(need, 1) if words is None else int(words)
+    if not 1 <= W <= MAX_TAG_WORDS or need > W:
+        raise ValueError(f"a field of {n_bits} bits at bit {first_bit} does not fit in {32 * min(max(W, 1), MAX_TAG_WORDS)} bits "
+                         f"(words = {words}, at most {MAX_TAG_WORDS})")
+    codes = codes.to(torch.int64)
+    if codes.numel() and int(codes.max()) >= n_values:
+        raise ValueError(f"codes must be < n_values = {n_values} (negative: no bits), got {int(codes.max())}")
+    return codes, W
+
+
+def _set_bits(out, rows_on, bit):
+    """ORs bit `bit` [n] (a position in the 32 W bit row) into out int64 [n, W] where rows_on."""
+    word = (bit // 32).clamp(0, out.shape[1] - 1)
+    val = torch.where(rows_on, torch.ones_like(bit) << (bit % 32), torch.zeros_like(bit))
+    out.scatter_(1, word[:, None], out.gather(1, word[:, None]) | val[:, None])
+
+
+def _as_words(out):
+    """int64 words in [0, 2^32) -> the same bit patterns as int32."""
+    return torch.where(out >= 2 ** 31, out - 2 ** 32, out).to(torch.int32).contiguous()
+
+
+def onehot_bits(codes, n_values: int, first_bit: int = 0, words: Optional[int] = None) -> torch.Tensor:
+    """int32 [n, W] with bit first_bit + codes[i] set in row i (bit b is bit b % 32 of word b // 32); a negative code sets
+    nothing.  As a catalogue tag under `allow`, "the row's value is one of the query's"; rows and queries use the same call.
+    W = words, or as many words as the field's n_values bits at first_bit need.  Raises ValueError for a code >= n_values or
+    a field that does not fit in 32 W bits (W <= 4).  Fields are combined by | over disjoint bit ranges."""
+    codes, W = _field(codes, n_values, first_bit, int(n_values), words)
+    out = torch.zeros((codes.numel(), W), dtype=torch.int64, device=codes.device)
+    on = codes >= 0
+    _set_bits(out, on, torch.where(on, codes, torch.zeros_like(codes)) + int(first_bit))
+    return _as_words(out)
+
+
+def equality_bits(codes, n_values: int, first_bit: int = 0, words: Optional[int] = None) -> torch.Tensor:
+    """int32 [n, W]: the binary-plus-complement encoding of codes[i] in 2 b bits at first_bit, b = ceil(log2 n_values) (at least
+    1): bit first_bit + j is binary digit j of the code, bit first_bit + b + j its complement.  With the same call on the
+    catalogue side (tags) and on the query side (`require`), a row holds every required bit exactly when the two codes are
+    equal.  A negative code gives zero bits: "don't care" for a query, and a catalogue row that satisfies no requirement.
+    Raises ValueError like onehot_bits."""
+    b = max(1, (int(n_values) - 1).bit_length())
+    codes, W = _field(codes, n_values, first_bit, 2 * b, words)
+    out = torch.zeros((codes.numel(), W), dtype=torch.int64, device=codes.device)
+    on = codes >= 0
+    for j in range(b):
+        digit = ((codes >> j) & 1) == 1
+        pos = torch.where(digit, torch.full_like(codes, int(first_bit) + j), torch.full_like(codes, int(first_bit) + b + j))
+        _set_bits(out, on, pos)
+    return _as_words(out)
+
+
+def _check_words(x, n: int, what: str, device, W: Optional[int] = None) -> torch.Tensor:
+    """An integer tensor [n] or [n, W] as contiguous int32 [n, W] (bit patterns kept; no host synchronisation)."""
+    if not torch.is_tensor(x) or x.dtype not in (torch.int32, torch.int64, torch.uint8, torch.int16, torch.int8):
+        raise ValueError(f"{what} must be an integer tensor")
+    if x.dim() == 1:
+        x = x[:, None]
+    if x.dim() != 2 or x.shape[0] != n or not 1 <= x.shape[1] <= MAX_TAG_WORDS or (W is not None and x.shape[1] != W):
+        want = f"({n},) or ({n}, W <= {MAX_TAG_WORDS})" if W is None else f"({n}, {W})" + (f" or ({n},)" if W == 1 else "")
+        raise ValueError(f"{what} must have shape {want}, got {tuple(x.shape)}")
+    if x.device != device:
+        raise ValueError(f"{what} on {x.device}, catalogue on {device}")
+    if x.dtype == torch.int64:                                             # values in [0, 2^32) keep their low 32 bits
+        x = torch.where(x >= 2 ** 31, x - 2 ** 32, x)
+    return x.to(torch.int32).contiguous()
+
+
 class CatalogIndex:
     """A packed catalogue of nC rows of dimension D.  score_dtype 'bf16' keeps the tt_score_pack_bf16 image of C / T (queries
     are packed unscaled, so the score is <bf16(q), bf16(c / T)> in f32); 'fp32' keeps C as it is and scores with an f32 FMA
     chain times 1 / T.  'fp8' (a training-time mode) falls back to bf16 here: the index has no fp8 images.  'bf16x3' (also a
-    training-time mode: near-f32 products) falls back to the exact 'fp32' sweep -- the fallback that keeps its precision."""
+    training-time mode: near-f32 products) falls back to the exact 'fp32' sweep -- the fallback that keeps its precision.
+    tags: an integer tensor [nC] or [nC, W <= 4] on the catalogue's device, W 32-bit tag words per row (onehot_bits,
+    equality_bits), kept as contiguous int32 [nC, W]; the searches of an index with tags take allow= / require=."""
 
-    def __init__(self, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None):
+    def __init__(self, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None, tags=None):
         if not torch.is_tensor(C) or C.dim() != 2 or C.shape[0] < 1 or not 1 <= C.shape[1] <= 256:
             raise ValueError("the catalogue must be a [nC >= 1, 1 <= D <= 256] tensor")
         if C.shape[0] >= 2 ** 31:
@@ -74,6 +162,8 @@ class CatalogIndex:
         self.inv_t = 1.0 / self.temperature
         self.device = C.device
         self.size, self.dim = int(C.shape[0]), int(C.shape[1])
+        self.tags = None if tags is None else _check_words(tags, self.size, "tags", self.device)
+        self.tag_words = 0 if self.tags is None else int(self.tags.shape[1])
         C = C.detach().to(torch.float32).contiguous()
         if self.score_dtype == "bf16":
             self.data = ops.score_pack_bf16(C, self.inv_t)
@@ -82,18 +172,20 @@ class CatalogIndex:
         self._ws = {}
 
     @classmethod
-    def from_embeddings(cls, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None) -> "CatalogIndex":
+    def from_embeddings(cls, C: torch.Tensor, temperature: float = 1.0, score_dtype: Optional[str] = None,
+                        tags=None) -> "CatalogIndex":
         """Index of ready embeddings C [nC, D] (the towers' outputs are L2-normalised; nothing is normalised here).
-        score_dtype: 'fp32' | 'bf16' | 'bf16x3' (-> fp32) | 'fp8' (-> bf16); default: the package's score_dtype setting (TT_SCORE_DTYPE)."""
-        return cls(C, temperature, score_dtype)
+        score_dtype: 'fp32' | 'bf16' | 'bf16x3' (-> fp32) | 'fp8' (-> bf16); default: the package's score_dtype setting (TT_SCORE_DTYPE).
+        tags: the rows' attribute tag words, [nC] or [nC, W] integers (see the class)."""
+        return cls(C, temperature, score_dtype, tags)
 
     @classmethod
     @torch.no_grad()
-    def from_store(cls, model, company_store, chunk: int = 8192, score_dtype: Optional[str] = None) -> "CatalogIndex":
+    def from_store(cls, model, company_store, chunk: int = 8192, score_dtype: Optional[str] = None, tags=None) -> "CatalogIndex":
         """Embeds every entity of a DeviceFeatureStore through the company tower, `chunk` rows at a time, in eval mode (running
         BatchNorm statistics, no dropout), and indexes the result: row i of the index is entity i of the store.  `model` is a
         TwoTowerTrainTask (its temperature and score_dtype are used) or a TwoTowerModel (temperature 1).  The model's
-        train()/eval() state is restored afterwards."""
+        train()/eval() state is restored afterwards.  tags: one row of attribute tag words per entity of the store."""
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         task = model if hasattr(model, "two_tower_model") else None
@@ -104,6 +196,8 @@ class CatalogIndex:
         n = len(company_store)
         if n < 1:
             raise ValueError("the company store is empty")
+        if tags is not None:
+            tags = _check_words(tags, n, "tags", torch.device(company_store.device))
         modes = [(m, m.training) for m in model.modules()]
         model.eval()
         try:
@@ -117,7 +211,7 @@ class CatalogIndex:
         finally:
             for m, was in modes:
                 m.training = was
-        return cls(C, temperature, score_dtype)
+        return cls(C, temperature, score_dtype, tags)
 
     # ---- queries ------------------------------------------------------------------------------------------------------
     def _check_queries(self, Q: torch.Tensor) -> torch.Tensor:
@@ -162,6 +256,17 @@ class CatalogIndex:
         order = torch.argsort(seg * (1 << 32) + rows)                       # (list, row): sorts within each list only
         return off, rows[order].to(torch.int32).contiguous()
 
+    def _check_filter(self, allow, require, nQ: int):
+        """None without masks, else the filt argument of ops._retrieve: (tags, W, allow, require) with the masks as contiguous
+        int32 [nQ, W] (a [nQ] mask for W = 1).  No host synchronisation: a filtered search stays capturable."""
+        if allow is None and require is None:
+            return None
+        if self.tags is None:
+            raise ValueError("allow= / require= need an index built with tags=")
+        a = None if allow is None else _check_words(allow, nQ, "allow", self.device, self.tag_words)
+        r = None if require is None else _check_words(require, nQ, "require", self.device, self.tag_words)
+        return self.tags, self.tag_words, a, r
+
     def _workspace(self, nQ: int, k: int) -> torch.Tensor:
         need = ops.retrieve_workspace_bytes(nQ, self.size, self.dim, k)
         key = torch.cuda.current_stream(self.device).cuda_stream
@@ -171,45 +276,51 @@ class CatalogIndex:
             self._ws[key] = ws
         return ws
 
-    def _call(self, Q: torch.Tensor, k: int, positives, exclude=None):
+    def _call(self, Q: torch.Tensor, k: int, positives, exclude=None, filt=None):
         nQ = Q.shape[0]
         ws = self._workspace(nQ, k)
         if self.score_dtype == "bf16":
             q = ops.score_pack_bf16(Q, 1.0)
-            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws, exclude)
-        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws, exclude)
+            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws, exclude, filt)
+        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws, exclude, filt)
 
-    def search(self, Q: torch.Tensor, k: int = 10, exclude=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, Q: torch.Tensor, k: int = 10, exclude=None, allow=None, require=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(vals f32 [nQ, k], idx int64 [nQ, k]): every query's k best catalogue rows, value descending, ties to the lower
         index.  1 <= k <= min(64, catalogue size).  exclude=(offsets int64 [nQ + 1], rows): query i's rows
-        rows[offsets[i]:offsets[i+1]] are left out; if fewer than k rows remain, the last slots are -inf / -1."""
+        rows[offsets[i]:offsets[i+1]] are left out; if fewer than k rows remain, the last slots are -inf / -1.
+        allow / require (an index with tags only): integer masks [nQ] or [nQ, W]; only rows that share a bit with a non-zero
+        allow[i] and hold every bit of require[i] are eligible for query i.  They combine with exclude."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
         ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
-        vals, idx, _ = self._call(Q, k, None, ex)
+        vals, idx, _ = self._call(Q, k, None, ex, self._check_filter(allow, require, Q.shape[0]))
         return vals, idx
 
-    def search_with_rank(self, Q: torch.Tensor, k: int, positives, exclude=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """search() and rank() from one sweep over the catalogue (the same exclusion lists for both)."""
+    def search_with_rank(self, Q: torch.Tensor, k: int, positives, exclude=None, allow=None,
+                         require=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """search() and rank() from one sweep over the catalogue (the same exclusion lists and masks for both)."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
         pos = self._check_positives(positives, Q.shape[0])
         ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
-        return self._call(Q, k, pos, ex)
+        return self._call(Q, k, pos, ex, self._check_filter(allow, require, Q.shape[0]))
 
-    def rank(self, Q: torch.Tensor, positives, exclude=None) -> torch.Tensor:
+    def rank(self, Q: torch.Tensor, positives, exclude=None, allow=None, require=None) -> torch.Tensor:
         """int32 [nQ]: 0-based rank of catalogue row positives[i] for query i among ALL catalogue rows,
         #{c : s > s_p} + #{c < p : s == s_p} (tt_diag_rank_rows's rule); -1 where the positive is outside [0, nC).
         exclude=(offsets, rows): only rows outside query i's list count -- the filtered rank.  The positive never counts
-        against itself, so it may be in its own list."""
+        against itself, so it may be in its own list.  allow / require: only eligible rows count (see search); whether the
+        positive itself is eligible makes no difference."""
         Q = self._check_queries(Q)
         pos = self._check_positives(positives, Q.shape[0])
         ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
-        return self._call(Q, 0, pos, ex)[2]
+        return self._call(Q, 0, pos, ex, self._check_filter(allow, require, Q.shape[0]))[2]
 
     def __len__(self) -> int:
         return self.size
 
     def __repr__(self) -> str:
-        return f"CatalogIndex(size={self.size}, dim={self.dim}, score_dtype={self.score_dtype!r}, temperature={self.temperature})"
+        tags = f", tag_words={self.tag_words}" if self.tags is not None else ""
+        return (f"CatalogIndex(size={self.size}, dim={self.dim}, score_dtype={self.score_dtype!r}, "
+                f"temperature={self.temperature}{tags})")
 

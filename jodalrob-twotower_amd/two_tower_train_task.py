@@ -328,13 +328,15 @@ class TwoTowerTrainTask(nn.Module):
             return {"top_similarities": vals, "top_indices": idx, "all_similarities": sim}
 
     @_no_dynamo
-    def predict_catalog(self, notice_batch, index, top_k: int = 10, exclude=None) -> Dict[str, torch.Tensor]:
+    def predict_catalog(self, notice_batch, index, top_k: int = 10, exclude=None, allow=None,
+                        require=None) -> Dict[str, torch.Tensor]:
         """Top-k companies of the whole catalogue `index` (a retrieval.CatalogIndex) for every notice of `notice_batch` (the
         notice side's {"dense", "kjt"}, or a full batch with a "notice" entry): {"top_similarities" f32 [B, top_k],
         "top_indices" int64 [B, top_k]} -- index rows, value descending, ties to the lower index.  The notice tower runs in
         eval mode; the task's train()/eval() state is restored afterwards.  (predict_batch ranks within one batch.)
         exclude=(offsets, rows): per-notice exclusion lists (CatalogIndex.search), e.g. companies that already bid on it
-        (retrieval.exclusions_from_pairs)."""
+        (retrieval.exclusions_from_pairs).  allow / require: per-notice attribute masks for an index built with tags=
+        (CatalogIndex.search): only eligible companies are returned."""
         from .retrieval import CatalogIndex
         if not isinstance(index, CatalogIndex):
             raise TypeError("index must be a CatalogIndex")
@@ -342,12 +344,15 @@ class TwoTowerTrainTask(nn.Module):
         if index.dim != self.two_tower_model.final_embedding_dim:
             raise ValueError(f"catalogue dimension {index.dim} != the towers' {self.two_tower_model.final_embedding_dim}")
         notice = notice_batch["notice"] if "notice" in notice_batch else notice_batch
+        if allow is not None or require is not None:                  # refused here, before the tower runs
+            n = allow if allow is not None else require
+            index._check_filter(allow, require, int(n.shape[0]) if torch.is_tensor(n) and n.dim() >= 1 else -1)
         modes = [(m, m.training) for m in self.modules()]
         self.eval()
         try:
             with torch.no_grad():
                 q = self.two_tower_model.get_notice_embeddings(notice)
-                vals, idx = index.search(q, top_k, exclude=exclude)
+                vals, idx = index.search(q, top_k, exclude=exclude, allow=allow, require=require)
         finally:
             for m, was in modes:
                 m.training = was

@@ -3,9 +3,14 @@ reports Recall@5/10 and MRR of the test pairs against the WHOLE catalogue and pr
 
     python scripts/retrieve.py [--checkpoint output/models/final_model.pt] [--final-dim 64] [--hidden 128,64]
                                [--entities 10000] [--pairs 100000] [--score-dtype fp32|bf16] [--top-k 10] [--filtered]
+                               [--restrict-key KEY]
 
 --filtered also prints the filtered metrics (each test pair ranked without its notice's other known companies, train and
 test pairs alike) and leaves every notice's known companies out of its example top-k list.
+
+--restrict-key KEY tags the catalogue with equality_bits of the company store's categorical column KEY (e.g. rgncd) and
+restricts every test pair's query to the companies that share its positive company's code -- a stand-in for a notice's
+regional restriction, which keeps every positive eligible -- and prints the restricted metrics beside the others.
 
 The data are the synthetic feature / pair source scripts/train.py uses (same arguments give the same stores, so a checkpoint
 written by `scripts/train.py --entities N --pairs P` is evaluated on its own test split).  Without --checkpoint the task is
@@ -30,7 +35,7 @@ from src.towers.pairs.unified_bid_data_loader import create_unified_bid_dataload
 from src.towers.two_tower_train_task import create_two_tower_train_task       # noqa: E402
 from jodalrob_twotower_amd import synthetic                                   # noqa: E402
 from jodalrob_twotower_amd.evaluator import TwoTowerEvaluator                 # noqa: E402
-from jodalrob_twotower_amd.retrieval import CatalogIndex, exclusions_from_pairs  # noqa: E402
+from jodalrob_twotower_amd.retrieval import CatalogIndex, equality_bits, exclusions_from_pairs  # noqa: E402
 
 
 def main():
@@ -47,6 +52,8 @@ def main():
     ap.add_argument("--examples", type=int, default=3)
     ap.add_argument("--filtered", action="store_true",
                     help="also rank without each notice's other known companies (train + test pairs)")
+    ap.add_argument("--restrict-key", default=None, metavar="KEY",
+                    help="also rank each test pair among the companies that share its positive's code in this company column")
     a = ap.parse_args()
 
     device = torch.device("cuda:0")
@@ -92,7 +99,15 @@ def main():
         print(f"no checkpoint: trained {steps} steps on the synthetic pairs")
 
     t0 = time.time()
-    index = CatalogIndex.from_store(task, test_loader.company)
+    codes = n_codes = None
+    if a.restrict_key:
+        company = test_loader.company
+        if a.restrict_key not in company.keys:
+            raise SystemExit(f"--restrict-key {a.restrict_key}: not a categorical column of the company store {company.keys}")
+        codes = company.categorical[:, company.keys.index(a.restrict_key)].contiguous()
+        n_codes = int(codes.max()) + 1
+    tags = None if codes is None else equality_bits(codes, n_codes)
+    index = CatalogIndex.from_store(task, test_loader.company, tags=tags)
     torch.cuda.synchronize()
     print(f"{index!r} built in {time.time() - t0:.2f} s")
     pairs = test_loader.pairs
@@ -103,13 +118,20 @@ def main():
           f"({time.time() - t0:.2f} s):")
     known = torch.cat([train_loader.pairs, test_loader.pairs]) if a.filtered else None   # (the loaders share one entity store)
     mf = ev.evaluate_catalog(task, test_loader.notice, index, pairs, filter_pairs=known) if a.filtered else None
+    want = None if codes is None else equality_bits(codes[pairs[:, 1]], n_codes)       # the code of the pair's own positive
+    mr = ev.evaluate_catalog(task, test_loader.notice, index, pairs, require=want) if want is not None else None
     for key in ("recall@5", "recall@10", "mrr"):
-        print(f"  {key:10s} {m[key]:.4f}" + (f"   filtered {mf[key]:.4f}" if mf else ""))
+        print(f"  {key:10s} {m[key]:.4f}" + (f"   filtered {mf[key]:.4f}" if mf else "")
+              + (f"   restricted to {a.restrict_key} {mr[key]:.4f}" if mr else ""))
+    if mr:
+        share = float((codes[None, :] == codes[pairs[:1024, 1]][:, None]).float().mean())
+        print(f"  {a.restrict_key}: {n_codes} codes in {index.tag_words} tag word(s), {share:.4f} of the catalogue eligible per query")
     print(f"  random baseline: recall@5 {5 / m['catalog_size']:.5f}, recall@10 {10 / m['catalog_size']:.5f}")
 
     ex = pairs[:a.examples]
     excl = exclusions_from_pairs(ex[:, 0], known, index.size) if a.filtered else None
-    pred = task.predict_catalog(test_loader.notice.gather(ex[:, 0].contiguous()), index, top_k=a.top_k, exclude=excl)
+    pred = task.predict_catalog(test_loader.notice.gather(ex[:, 0].contiguous()), index, top_k=a.top_k, exclude=excl,
+                                require=None if want is None else want[:a.examples])
     for i in range(ex.shape[0]):
         seen = f", {int(excl[0][i + 1] - excl[0][i])} known companies left out" if a.filtered else ""
         print(f"notice {int(ex[i, 0])} (positive company {int(ex[i, 1])}{seen}): top-{a.top_k} companies "

@@ -3,6 +3,7 @@ torch.mm + torch.topk on the same inputs.
 
     python tools/bench_retrieve.py [--nq 8192] [--nc 65536 1048576] [--d 64 256] [--k 10 64] [--dtypes bf16 fp32]
                                    [--reps 3] [--out profiles/retrieve_bench.json] [--exclude 0 16 256]
+                                   [--filter 1 4 --eligible 1.0 0.1]
 
 One JSON line per case: kernel ms per search and scores/s, the MFMA fraction of 2.5 PF dense bf16 (2 nQ nC D flops), the
 catalogue read rate (bytes of the catalogue operand per search) against 8 TB/s, and the baseline's ms and how many rows'
@@ -12,6 +13,11 @@ bf16 images, bf16 scores; fp32: f32 scores), takes the chunk's top-k and merges 
 --exclude L [L ...] (no baseline then): per case and L, every query gets L random distinct catalogue rows as its exclusion
 list, and the exclusion search (tt_excl_retrieve_topk_*) is timed against the plain search in the same process, the two
 alternating rep by rep; one JSON line per (case, L) with both times and their ratio.
+
+--filter W [W ...] with --eligible P [P ...] (no baseline then): per case, W and P, every catalogue row gets W random tag words
+whose last word has each bit set with probability P, and query q requires bit q % 32 of that word, so a share P of the rows is
+eligible per query.  The filtered search (tt_filt_retrieve_topk_*) is timed against the plain search in the same process, the
+two alternating, best of --reps (use 5); one JSON line per (case, W, P) with both times and their ratio.
 """
 from __future__ import annotations
 
@@ -108,6 +114,53 @@ def exclude_rows(index, Q, k, nc, d, dt, args):
     return out
 
 
+def filter_rows(index, Q, k, nc, d, dt, args):
+    from jodalrob_twotower_amd import ops
+    dev = Q.device
+    g = torch.Generator(device=dev).manual_seed(2)
+    nq = Q.shape[0]
+    ws = index._workspace(nq, k)
+    bf16 = index.score_dtype == "bf16"
+    q = ops.score_pack_bf16(Q, 1.0) if bf16 else Q
+    out = []
+    for W in args.filter:
+        for P in args.eligible:
+            tags = torch.randint(-2 ** 31, 2 ** 31, (nc, W), generator=g, device=dev, dtype=torch.int64)
+            last = torch.zeros(nc, dtype=torch.int64, device=dev)
+            for b in range(32):
+                last |= (torch.rand(nc, generator=g, device=dev) < P).long() << b
+            tags[:, W - 1] = torch.where(last >= 2 ** 31, last - 2 ** 32, last)
+            tags = tags.to(torch.int32).contiguous()
+            bit = torch.arange(nq, device=dev) % 32
+            need = torch.zeros((nq, W), dtype=torch.int64, device=dev)
+            need[:, W - 1] = torch.where(bit == 31, torch.full_like(bit, -2 ** 31), 1 << bit)
+            need = need.to(torch.int32).contiguous()
+            filt = (tags, W, None, need)
+
+            def plain():
+                ops._retrieve(q, nq, index.data, nc, d, k, index.inv_t, bf16, None, ws)
+
+            def filtered():
+                ops._retrieve(q, nq, index.data, nc, d, k, index.inv_t, bf16, None, ws, None, filt)
+
+            pm, fm = [], []
+            for _ in range(args.reps):                           # alternating, so both see the same clocks and caches
+                pm.append(_time(plain, 1)[0])
+                fm.append(_time(filtered, 1)[0])
+            vals, idx, _ = ops._retrieve(q, nq, index.data, nc, d, k, index.inv_t, bf16, None, ws, None, filt)
+            got = tags[idx.clamp(min=0), W - 1]                   # [nq, k]: the returned rows' last tag word
+            ineligible = int((((got >> bit[:, None]) & 1) == 0)[idx >= 0].sum())
+            share = float(((tags[:, W - 1][None, :4096] >> bit[:64, None]) & 1).float().mean())
+            row = {"nq": nq, "nc": nc, "d": d, "k": k, "dtype": dt, "filter_W": W, "eligible_P": P,
+                   "eligible_share_measured": round(share, 4), "plain_ms": round(min(pm), 4), "filt_ms": round(min(fm), 4),
+                   "filt_over_plain": round(min(fm) / min(pm), 4), "plain_ms_all": [round(x, 4) for x in pm],
+                   "filt_ms_all": [round(x, 4) for x in fm], "ineligible_rows_returned": ineligible}
+            print(json.dumps(row), flush=True)
+            out.append(row)
+            del tags, need
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=8192)
@@ -120,6 +173,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--exclude", type=int, nargs="+", action="extend", default=None,
                     help="exclusion list lengths L to time against the plain search (repeatable)")
+    ap.add_argument("--filter", type=int, nargs="+", default=None, help="tag words W (1 .. 4) to time against the plain search")
+    ap.add_argument("--eligible", type=float, nargs="+", default=[1.0, 0.1], help="share of rows eligible per query (--filter)")
     args = ap.parse_args()
 
     from jodalrob_twotower_amd.retrieval import CatalogIndex
@@ -135,6 +190,9 @@ def main():
             for dt in args.dtypes:
                 index = CatalogIndex.from_embeddings(Cm, temperature=0.05, score_dtype=dt)
                 for k in args.k:
+                    if args.filter is not None:
+                        rows.extend(filter_rows(index, Q, k, nc, d, dt, args))
+                        continue
                     if args.exclude is not None:
                         rows.extend(exclude_rows(index, Q, k, nc, d, dt, args))
                         continue
