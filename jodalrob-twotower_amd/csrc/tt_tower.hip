@@ -1548,6 +1548,341 @@ int check_batch(int32_t n, const tt_tower_params* const* P, int64_t B, float dro
   return TT_OK;
 }
 
+// ---- the two passes: state, per-block argument builders, GEMM items, the SyncBN cut, the fused paths ----------------------------
+// What one call of tt_towers_mlp_fwd / _bwd works on, built once per call (G, d_emb: backward only)
+struct Pass {
+  tt_ctx* ctx; hipStream_t st; int n;
+  const tt_tower_params* const* P; const tt_tower_acts* const* A; const tt_tower_grads* const* G; const float* const* d_emb;
+  int64_t B; WsLayout ws[TT_MAX_SIDES];
+  bool train, drop; float dropout_p; uint64_t seed; const uint64_t* seed_dev;
+  int phase, nh; bool bf16;
+};
+inline Pass make_pass(tt_ctx* ctx, tt_stream stream, int n, const tt_tower_params* const* P, const tt_tower_acts* const* A,
+                      const tt_tower_grads* const* G, const float* const* d_emb, int64_t B, int32_t train, float dropout_p, uint64_t seed,
+                      const uint64_t* seed_dev, void* const* workspaces) {
+  Pass p{ctx, reinterpret_cast<hipStream_t>(stream), n, P, A, G, d_emb, B, {}, train != 0, train && dropout_p > 0.f, dropout_p, seed, seed_dev,
+         P[0]->sync_phase, P[0]->n_hidden, P[0]->compute_dtype == TT_BF16};
+  for (int t = 0; t < n; ++t) p.ws[t] = ws_layout(P[t], B, reinterpret_cast<char*>(workspaces[t]));
+  return p;
+}
+int check_sync_phase(const Pass& p, const char* who) {
+  if (p.phase == 0) return TT_OK;
+  if (p.nh != 1 || !p.train) {
+    tt_set_error("%s: sync_phase %d needs a training pass over towers with exactly one hidden block (the pass is cut at its BatchNorm)", who, p.phase);
+    return TT_ERR_UNSUPPORTED;
+  }
+  for (int t = 0; t < p.n; ++t) {
+    const float* buf = p.G ? (!p.G[t] ? nullptr : p.phase == 1 ? p.G[t]->s_sync_local : p.G[t]->s_sync_all)
+                           : (p.phase == 1 ? p.A[t]->bn_sync_local : p.A[t]->bn_sync_all);
+    TT_CHECK_ARG(buf != nullptr, "%s: NULL SyncBN buffer", who);
+  }
+  return TT_OK;
+}
+// The dropout salt of hidden block i of tower slot t.  Dropout element index = GLOBAL row * H + column: the rank's first row enters
+// through the salt.  Restated by oracle/oracle_np.py (dropout_salt) and tests/test_oracle_golden.py (the mask tests).
+inline uint64_t block_salt(const tt_tower_params* p, int t, int i) {
+  return (((uint64_t)(i + 1) << 40) ^ ((uint64_t)t << 52)) + (uint64_t)p->rng_row_offset * (uint64_t)p->hidden[i];
+}
+// Layers are numbered 0 .. nh: hidden block i, then the output Linear as layer nh.  Layer i reads layer_in (in_width wide) and its
+// backward writes the gradient of that input to d_in; block i's own gradient (d_act, then d_pre in place) is d_in of layer i + 1.
+inline const float* layer_in(const Pass& p, int i, int t) { return i == 0 ? reinterpret_cast<const float*>(p.A[t]->x) : p.A[t]->act[i - 1]; }
+inline float* d_in(const Pass& p, int i, int t) { return i == 0 ? reinterpret_cast<float*>(p.G[t]->d_x) : p.G[t]->scratch[i - 1]; }
+inline int block_chunks(const Pass& p, int i, int t) { return chunks_for(p.B, p.P[t]->hidden[i]); }
+struct BlockDims { int hmax = 1, cmax = 1; int64_t tmax = 1; };   // of block i over the towers: widest, most chunks, most elements
+inline BlockDims block_dims(const Pass& p, int i) {
+  BlockDims d;
+  for (int t = 0; t < p.n; ++t) {
+    const int H = p.P[t]->hidden[i], nchunks = block_chunks(p, i, t);
+    d.hmax = H > d.hmax ? H : d.hmax;
+    d.cmax = nchunks > d.cmax ? nchunks : d.cmax;
+    d.tmax = p.B * H > d.tmax ? p.B * H : d.tmax;
+  }
+  return d;
+}
+inline BnStatArgs bn_stat_args(const Pass& p, int i, int t) {
+  const tt_tower_params* P = p.P[t]; const tt_tower_acts* A = p.A[t];
+  const int nchunks = block_chunks(p, i, t);
+  return BnStatArgs{A->pre[i], (int)p.B, P->hidden[i], (int)tt_cdiv(p.B, nchunks), nchunks, p.ws[t].col, A->mean[i], A->rstd[i],
+                    P->bn_rm[i], P->bn_rv[i], P->bn_nbt[i]};
+}
+inline BnApplyArgs bn_apply_args(const Pass& p, int i, int t) {
+  const tt_tower_params* P = p.P[t]; const tt_tower_acts* A = p.A[t];
+  return BnApplyArgs{A->pre[i], p.B * P->hidden[i], P->hidden[i], A->mean[i], A->rstd[i], P->bn_w[i], P->bn_b[i], block_salt(P, t, i), A->act[i]};
+}
+// S1 = sum da -> bn bias grad ; S2 = sum da*xhat -> bn weight grad  (x: where da is read; the tail kernels take it from their tile)
+inline ColArgs col_args(const Pass& p, int i, int t, const float* x, int64_t ldx) {
+  const tt_tower_acts* A = p.A[t];
+  const int nchunks = block_chunks(p, i, t);
+  return ColArgs{x, ldx, A->pre[i], A->mean[i], A->rstd[i], block_salt(p.P[t], t, i), (int)p.B, p.P[t]->hidden[i], (int)tt_cdiv(p.B, nchunks),
+                 nchunks, p.ws[t].col, p.G[t]->bn_b[i], p.G[t]->bn_w[i]};
+}
+inline BnBwdArgs bn_bwd_args(const Pass& p, int i, int t) {
+  const tt_tower_params* P = p.P[t]; const tt_tower_acts* A = p.A[t];
+  return BnBwdArgs{d_in(p, i + 1, t), A->pre[i], p.B * P->hidden[i], P->hidden[i], 1.f / (float)p.B, A->mean[i], A->rstd[i], P->bn_w[i],
+                   p.G[t]->bn_b[i], p.G[t]->bn_w[i], block_salt(P, t, i)};
+}
+int check_block_grads(const Pass& p, int i) {
+  for (int t = 0; t < p.n; ++t)
+    TT_CHECK_ARG(p.G[t]->w[i] && p.G[t]->b[i] && p.G[t]->bn_w[i] && p.G[t]->bn_b[i], "tt_towers_mlp_bwd: NULL gradient buffers of block %d", i);
+  return TT_OK;
+}
+// GEMM items, complete as they come out.  Forward, C[B, N] = A[B, K] . W[N, K]^T + bias:
+inline GemmNT nt_item(const Pass& p, int t, const float* A, const float* W, const float* bias, float* C, int64_t ldc, int N, int K) {
+  GemmNT g{A, K, W, K, bias, C, ldc, p.B, N, K, false, 1.f};
+  g.bf16 = p.bf16; g.workspace = p.ws[t].gemm; g.workspace_bytes = p.ws[t].gemm_bytes;
+  return g;
+}
+// Backward of layer i from its output gradient dY [B, M] (d_y, or block i's d_pre):  dW [M, N] = dY^T . in (+ the bias gradient, its
+// column sums) into workspace slot 1 + i, and d_in [B, N] = dY . W
+inline GemmTN tn_item(const Pass& p, int t, int slot, const float* A, int64_t lda, const float* Bm, float* C, int M, int N, float* colsum) {
+  GemmTN g{A, lda, Bm, N, C, N, M, N, p.B, p.ws[t].tn[slot], p.ws[t].tn_bytes[slot], colsum};
+  g.bf16 = p.bf16;
+  return g;
+}
+int launch_layer_nt(const Pass& p, int i, NtDeferred* defer) {
+  GemmNT nt[TT_MAX_SIDES];
+  const bool out = i == p.nh;
+  for (int t = 0; t < p.n; ++t) {
+    const tt_tower_params* P = p.P[t];
+    const int N = out ? P->d_out : P->hidden[i];
+    nt[t] = nt_item(p, t, layer_in(p, i, t), out ? P->w_out : P->w[i], out ? P->b_out : P->b[i], out ? p.A[t]->y : p.A[t]->pre[i], N, N, in_width(P, i));
+    nt[t].a_bf16 = i == 0 && P->x_dtype == TT_BF16;
+    nt[t].defer = defer ? &defer[t] : nullptr;
+  }
+  return tt_gemm_nt_batched(p.st, nt, p.n);
+}
+int launch_layer_bwd(const Pass& p, int i, TnPending* pend, bool data_grad = true) {
+  GemmTN tn[TT_MAX_SIDES]; GemmNN nn[TT_MAX_SIDES];
+  const bool out = i == p.nh;
+  for (int t = 0; t < p.n; ++t) {
+    const tt_tower_params* P = p.P[t]; const tt_tower_grads* g = p.G[t];
+    const int M = out ? P->d_out : P->hidden[i], N = in_width(P, i);
+    const float* dY = out ? g->d_y : d_in(p, i + 1, t);
+    tn[t] = tn_item(p, t, 1 + i, dY, M, layer_in(p, i, t), out ? g->w_out : g->w[i], M, N, out ? g->b_out : g->b[i]);
+    tn[t].b_bf16 = i == 0 && P->x_dtype == TT_BF16;
+    nn[t] = GemmNN{dY, M, out ? P->w_out : P->w[i], N, d_in(p, i, t), N, p.B, N, M};
+    nn[t].bf16 = p.bf16; nn[t].c_bf16 = i == 0 && P->dx_dtype == TT_BF16;
+  }
+  if (int rc = tt_gemm_tn_batched(p.st, tn, p.n, pend)) return rc;
+  return data_grad ? tt_gemm_nn_batched(p.st, nn, p.n) : TT_OK;
+}
+
+// ---- SyncBN: the pass is cut at its one BatchNorm (twotower.h: sync_phase).  Phase 1 hands this rank's chunk-merged statistics
+// (forward) / column sums (backward) to the caller and stops; phase 2 continues with every rank's share as one "chunk" each
+int sync_hand_out_stats(const Pass& p, const Batch<BnStatArgs>& bs, int hmax) {
+  Batch<LocalArgs> la{};
+  for (int t = 0; t < p.n; ++t) la.a[t] = LocalArgs{bs.a[t].partial, bs.a[t].nchunks, bs.a[t].H, p.A[t]->bn_sync_local};
+  tail_local_stats_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)p.n), kThreads, 0, p.st>>>(la);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+inline void sync_take_rank_stats(const Pass& p, Batch<BnStatArgs>& bs) {
+  for (int t = 0; t < p.n; ++t) {
+    bs.a[t].partial = const_cast<float*>(p.A[t]->bn_sync_all); bs.a[t].nchunks = p.P[t]->sync_ranks; bs.a[t].pstride = p.A[t]->bn_sync_stride;
+  }
+}
+int sync_hand_out_colsums(const Pass& p, const Batch<ColArgs>& cols, int gx) {
+  Batch<LocalArgs> la{};
+  for (int t = 0; t < p.n; ++t) la.a[t] = LocalArgs{cols.a[t].partial, cols.a[t].nchunks, cols.a[t].H, p.G[t]->s_sync_local};
+  tail_local_colsum_kernel<<<dim3((unsigned)gx, (unsigned)p.n), kThreads, 0, p.st>>>(la);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+// S1 / S2 of every rank, one "chunk" each, over ranks * B rows; returns 1 / ranks, the scale of the stored BN weight / bias gradients.
+// The tail apply kernels (raw == nullptr) finish the sums in every workgroup, use them from there and scale what they store by
+// TailApplyArgs::out_scale, so their caller takes the return value and `col` is a copy beside the one the head used.  The separate
+// kernels pass S1 / S2 through memory: colsum_finish_kernel stores the gradients scaled (col.out_scale) and the unscaled sums
+// bn_bwd_apply_kernel needs go to `raw`.  That is the one difference between the three places this was written out, and it is on purpose.
+inline float sync_take_rank_colsums(const Pass& p, ColArgs& col, BnBwdArgs& bn, int t, float* raw) {
+  const int ranks = p.P[t]->sync_ranks;
+  col.partial = const_cast<float*>(p.G[t]->s_sync_all); col.nchunks = ranks; col.pstride = p.G[t]->s_sync_stride;
+  bn.invB = 1.f / ((float)p.B * (float)ranks);
+  if (raw) { col.out_scale = 1.f / (float)ranks; col.sums_raw = raw; bn.S1 = raw; bn.S2 = raw + col.H; }
+  return 1.f / (float)ranks;
+}
+
+// ---- forward paths --------------------------------------------------------------------------------------------------------------
+// the score kernels' two operand images of emb, written by the tail itself (tt_score_pack_bf16's layout)
+inline void pack_target(const Pass& p, TailFwdArgs& tf, int t) {
+  if (!p.A[t]->emb_packed) return;
+  tf.Dp = p.P[t]->d_out <= 32 ? 32 : (p.P[t]->d_out <= 64 ? 64 : 128);
+  tf.pk_rows = reinterpret_cast<__bf16*>(p.A[t]->emb_packed);
+  tf.pk_frag = tf.pk_rows + tt_cdiv(p.B, 64) * 64 * tf.Dp;
+  tf.pk_scale = p.A[t]->emb_pack_scale == 0.f ? 1.f : p.A[t]->emb_pack_scale;
+}
+inline Batch<TailFwdArgs> tail_fwd_args(const Pass& p, int i, const Batch<BnStatArgs>& bs) {
+  Batch<TailFwdArgs> tf{};
+  for (int t = 0; t < p.n; ++t) {
+    const tt_tower_params* P = p.P[t];
+    tf.a[t] = TailFwdArgs{bs.a[t], P->bn_w[i], P->bn_b[i], block_salt(P, t, i), p.A[t]->act[i], P->w_out, P->b_out, P->d_out,
+                          p.A[t]->y, p.A[t]->emb, nullptr, nullptr, 0, 1.f};
+    pack_target(p, tf.a[t], t);
+  }
+  return tf;
+}
+// The fused narrow tail (tail_fusable) from block i's pre-activations -- or, behind a split-K block GEMM, its slabs `nd` -- to the
+// unit rows: the chunk statistics in the same pass as slabs (+ bias) -> pre, then everything else in one kernel.  Ends the pass.
+int fwd_narrow_tail(const Pass& p, int i, Batch<BnStatArgs>& bs, const NtDeferred* nd, bool front, const BlockDims& dim) {
+  tt_ctx* ctx = p.ctx; hipStream_t st = p.st; const int n = p.n;
+  if (p.phase != 2) {
+    if (front) {                                      // projection + block Linear + chunk statistics in one launch
+      Batch<FrontArgs> fb{};
+      bool w16 = true;                                // every tower brings bf16 shadows of both weights (16-byte aligned)
+      for (int t = 0; t < n; ++t) {
+        const tt_tower_params* P = p.P[t]; const tt_tower_acts* A = p.A[t];
+        const int wx = P->h0 + P->kcat_e;
+        fb.a[t] = FrontArgs{A->dense, P->din, P->din, P->w_proj, P->b_proj, P->h0, reinterpret_cast<uint16_t*>(A->x), wx, wx, P->w[i], P->b[i],
+                            A->pre[i], bs.a[t], reinterpret_cast<const uint16_t*>(P->w_proj_bf16), reinterpret_cast<const uint16_t*>(P->w_bf16[i])};
+        w16 = w16 && P->w_proj_bf16 && P->w_bf16[i] && tt_aligned(P->w_proj_bf16, 16) && tt_aligned(P->w_bf16[i], 16);
+      }
+      if (w16) {
+        TT_LDS_ONCE(kFrontLds, tower_front_kernel<true>);
+        tower_front_kernel<true><<<dim3((unsigned)dim.cmax, (unsigned)n), kFrontThreads, kFrontLds, st>>>(fb);
+      } else {
+        TT_LDS_ONCE(kFrontLds, tower_front_kernel<false>);
+        tower_front_kernel<false><<<dim3((unsigned)dim.cmax, (unsigned)n), kFrontThreads, kFrontLds, st>>>(fb);
+      }
+    } else if (nd[0].splits > 0) {
+      Batch<HeadArgs> hb{};
+      for (int t = 0; t < n; ++t) hb.a[t] = HeadArgs{nd[t].slabs, nd[t].slab_stride, nd[t].splits, p.P[t]->b[i], p.A[t]->pre[i], bs.a[t]};
+      tail_head_kernel<<<dim3((unsigned)dim.cmax, (unsigned)n), kTailThreads, 0, st>>>(hb);
+    } else {
+      bn_stats_partial_kernel<<<dim3(1, (unsigned)dim.cmax, (unsigned)n), kThreads, 0, st>>>(bs);
+    }
+    TT_LAUNCH_CHECK();
+  }
+  if (p.phase == 1) return sync_hand_out_stats(p, bs, dim.hmax);
+  if (p.phase == 2) sync_take_rank_stats(p, bs);
+  Batch<TailFwdArgs> tf = tail_fwd_args(p, i, bs);
+  bool fin = false;
+  int mine = 0;                                     // of the keyed plan (TT_OPT_DEFER_RIDERS): what this call hosts
+  if (int rc = tt_deferred_host(ctx, TT_DQ_SORT | TT_DQ_COMPACT, st, &mine)) return rc;
+  if (mine & TT_DQ_SORT) {
+    // the keyed plan's sort has been held back for this place: behind the front kernel, with one workgroup per tower in its
+    // grid that finishes the chunk statistics once -- the tail then reads 2 * H floats per workgroup
+    BnFinishRiders bf{};
+    fin = p.phase == 0 && ctx->bn_fin != nullptr;     // (SyncBN's second half merges rank triples: in the tail, as before)
+    for (int t = 0; t < n && fin; ++t) {
+      const BnStatArgs& s = bs.a[t];
+      bf.r[t] = BnFinishRider{s.partial, s.pstride ? s.pstride : 3 * s.H, s.nchunks, s.H, s.mean, s.rstd, s.rm, s.rv, s.nbt,
+                              ctx->bn_fin + t * kBnFinStride};
+      tf.a[t].fin = bf.r[t].out;
+    }
+    if (int rc = tt_keyed_sort_run(ctx->dq->sort, st, &bf, fin ? n : 0)) return rc;
+  }
+  const int cr_wg = (mine & TT_DQ_COMPACT) ? ctx->dq->compact_wg : 0;      // a queued plan compaction rides in one extra grid row
+  const int64_t gx = tt_cdiv(p.B, 64) > cr_wg ? tt_cdiv(p.B, 64) : cr_wg;
+  const dim3 grid((unsigned)gx, (unsigned)(n + (cr_wg > 0 ? 1 : 0)));
+  if (fin) tail_fwd_kernel<true><<<grid, kTailThreads, 0, st>>>(tf, p.drop, p.dropout_p, p.seed, p.seed_dev, ctx->dq->compact, cr_wg);
+  else tail_fwd_kernel<false><<<grid, kTailThreads, 0, st>>>(tf, p.drop, p.dropout_p, p.seed, p.seed_dev, ctx->dq->compact, cr_wg);
+  tt_deferred_taken(ctx, mine);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+// The wide tail (wide_tail_ok) behind the chunk statistics of block i: statistics finish + BN apply + dropout + output Linear +
+// L2 normalise + the score kernels' operand images in one launch.  Ends the pass.
+int fwd_wide_tail(const Pass& p, int i, const Batch<BnStatArgs>& bs) {
+  tt_ctx* ctx = p.ctx;
+  TT_LDS_ONCE(kWideLds, tail_fwd_wide_kernel);
+  tail_fwd_wide_kernel<<<dim3((unsigned)tt_cdiv(p.B, 64), (unsigned)p.n), kTailThreads, kWideLds, p.st>>>(tail_fwd_args(p, i, bs), p.drop, p.dropout_p, p.seed, p.seed_dev);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+// ---- backward paths -------------------------------------------------------------------------------------------------------------
+// First block + projection as ONE launch (tt_gemm.h: GemmBack; d_pre of block 0 arrives in scratch[0]): its items, and whether the
+// pass takes it.  Asked once per call, before the tail: the tail leaves a queued loss reduction to that launch.
+bool back_items(const Pass& p, GemmBack* gb) {
+  if (p.nh < 1 || !p.bf16) return false;
+  for (int t = 0; t < p.n; ++t) {
+    const tt_tower_params* P = p.P[t]; const tt_tower_grads* g = p.G[t];
+    const int wx = P->h0 + P->kcat_e;
+    if (P->flags & TT_TOWER_UNFUSED_BACK) return false;
+    gb[t] = GemmBack{g->scratch[0], P->hidden[0], p.A[t]->x, wx, wx, P->x_dtype == TT_BF16, p.A[t]->dense, P->din, P->din,
+                     P->w[0], P->h0, reinterpret_cast<float*>(g->d_x), wx, P->dx_dtype == TT_BF16, g->w[0], g->b[0],
+                     g->w_proj, g->b_proj, p.ws[t].tn[1], p.ws[t].tn_bytes[1], p.ws[t].tn[0], p.ws[t].tn_bytes[0], p.B};
+    gb[t].w16 = P->w_bf16[0];
+  }
+  return tt_gemm_back_supported(gb, p.n);
+}
+// which launch of the pass runs a queued loss reduction (the symmetric score forward's, TT_DQ_LOSS) in an extra grid row
+enum LossHost { kLossNobody, kLossTailBwd, kLossGemmBack, kLossTailBwdApply };
+// The fused narrow tail's backward: L2-normalise backward, both output-layer GEMMs and the BN column sums of the last block in one
+// kernel; the BN backward apply (after the batch-wide S1 / S2) in a second.  *loss: who hosts a queued loss reduction.
+int bwd_narrow_tail(const Pass& p, bool back, LossHost* loss) {
+  tt_ctx* ctx = p.ctx; hipStream_t st = p.st; const int n = p.n, i = p.nh - 1;
+  if (int rc = check_block_grads(p, i)) return rc;
+  Batch<ColArgs> cb{}; Batch<TailBwdArgs> tb{}; Batch<TailApplyArgs> tp{};
+  for (int t = 0; t < n; ++t) {
+    const tt_tower_params* P = p.P[t]; const tt_tower_grads* g = p.G[t];
+    const int H = P->hidden[i], D = P->d_out;
+    cb.a[t] = col_args(p, i, t, nullptr, 0);
+    const int nchunks = cb.a[t].nchunks;
+    float* w_slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p.ws[t].tn[p.nh + 1]) + 255) & ~uintptr_t(255));
+    float* b_slab = w_slab + (size_t)nchunks * D * H;
+    tb.a[t] = TailBwdArgs{p.A[t]->y, p.A[t]->emb, p.d_emb[t], g->d_y, D, P->w_out, p.A[t]->act[i], d_in(p, p.nh, t), cb.a[t], w_slab, b_slab};
+    tp.a[t] = TailApplyArgs{cb.a[t], bn_bwd_args(p, i, t), w_slab, b_slab, D, g->w_out, g->b_out, nchunks, 1.f};
+    if (p.phase == 2) tp.a[t].out_scale = sync_take_rank_colsums(p, tp.a[t].col, tp.a[t].bn, t, nullptr);
+  }
+  // a score backward that waits in the context (TT_OPT_FUSE_SCORE_TAIL) runs the head in its own launch when its workgroups
+  // are the head's: two towers, H = D = 64, 64-row chunks numbered like its 64-row tiles, its dA exactly d_emb in tower order
+  int mine = 0;                                       // of the score backward and the loss reduction: what is queued on this stream
+  if (int rc = tt_deferred_host(ctx, TT_DQ_SCORE_BWD | TT_DQ_LOSS, st, &mine)) return rc;
+  bool hosted = false;
+  if (mine & TT_DQ_SCORE_BWD) {
+    hosted = p.phase == 0 && n == 2 && ctx->dq->score_rows == p.B && ctx->dq->score_dA[0] == p.d_emb[0] && ctx->dq->score_dA[1] == p.d_emb[1];
+    for (int t = 0; hosted && t < n; ++t)
+      hosted = tb.a[t].D == 64 && tb.a[t].col.H == 64 && tb.a[t].col.rows_per_chunk == 64 && tb.a[t].col.nchunks == (int)tt_cdiv(p.B, 64);
+    if (hosted) {
+      if (int rc = tt_score_tail_bwd_launch(ctx, tb, p.drop, p.dropout_p, p.seed, p.seed_dev)) return rc;
+    } else if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) {
+      return rc;
+    }
+  }
+  // a queued loss reduction rides in tail_bwd's extra grid row; where the score backward ran the head (512-thread workgroups) it
+  // waits for the first block's launch -- only the host reads it, and tail_bwd_apply's workgroups are on the step's chain
+  // -- or, in a pass without that launch, rides in tail_bwd_apply's extra grid row.  (SyncBN's second half launches no tail_bwd and
+  // hosts no score backward: the reduction stays queued.)
+  *loss = !(mine & TT_DQ_LOSS) ? kLossNobody : hosted ? (back ? kLossGemmBack : kLossTailBwdApply) : p.phase != 2 ? kLossTailBwd : kLossNobody;
+  if (p.phase != 2 && !hosted) {
+    const int fr_on = *loss == kLossTailBwd;
+    tail_bwd_kernel<<<dim3((unsigned)block_dims(p, i).cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, p.drop, p.dropout_p, p.seed, p.seed_dev, ctx->dq->loss, fr_on);
+    tt_deferred_taken(ctx, TT_DQ_LOSS & mine);
+    TT_LAUNCH_CHECK();
+  }
+  if (p.phase == 1) return sync_hand_out_colsums(p, cb, 1);        // (fused tail: H <= 64)
+  const int fr_here = *loss == kLossTailBwdApply;
+  tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(p.B, 64), (unsigned)(n + fr_here)), kTailThreads, 0, st>>>(tp, ctx->dq->loss, fr_here);
+  if (fr_here) tt_deferred_taken(ctx, TT_DQ_LOSS);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+// The wide tail's backward head: L2-normalise backward, the output layer's data-gradient GEMM and the BN column sums of the last
+// block in one kernel (the weight-gradient GEMM stays the split-K one); column-sum finish + BN backward apply in a second, in
+// the block loop
+int bwd_wide_head(const Pass& p, TnPending* pend) {
+  const int i = p.nh - 1;
+  Batch<TailBwdArgs> tb{};
+  for (int t = 0; t < p.n; ++t)
+    tb.a[t] = TailBwdArgs{p.A[t]->y, p.A[t]->emb, p.d_emb[t], p.G[t]->d_y, p.P[t]->d_out, p.P[t]->w_out, nullptr, d_in(p, p.nh, t),
+                          col_args(p, i, t, nullptr, 0), nullptr, nullptr};
+  tail_bwd_wide_kernel<<<dim3((unsigned)block_dims(p, i).cmax, (unsigned)p.n), kWideBwdThreads, 0, p.st>>>(tb, p.drop, p.dropout_p, p.seed, p.seed_dev);
+  TT_LAUNCH_CHECK();
+  return launch_layer_bwd(p, p.nh, pend, false);
+}
+// First block + projection: three independent products of d_pre in ONE launch (tt_gemm.h: GemmBack); the projection's gradients
+// come out of the slab-reduction launch, d_x[:, 0:h0] is not materialised.  Ends the pass.
+int bwd_first_block_back(const Pass& p, const GemmBack* gb, TnPending* pend, bool with_loss) {
+  tt_ctx* ctx = p.ctx;
+  int mine = 0;
+  if (with_loss)
+    if (int rc = tt_deferred_host(ctx, TT_DQ_LOSS, p.st, &mine)) return rc;
+  if (int rc = tt_gemm_back_batched(p.st, gb, p.n, pend, (mine & TT_DQ_LOSS) ? &ctx->dq->loss : nullptr)) return rc;
+  tt_deferred_taken(ctx, mine & TT_DQ_LOSS);
+  if (ctx->dq->defer_slabs) return tt_deferred_queue_slabs(ctx, p.st, pend);     // rides in tt_embed_grad_bwd's launch
+  return tt_gemm_tn_flush(p.st, pend);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1563,206 +1898,59 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   TT_CHECK_ARG(ctx && A, "tt_towers_mlp_fwd: NULL argument");
   if (int rc = check_batch(n, P, B, dropout_p, workspaces, workspace_bytes, "tt_towers_mlp_fwd")) return rc;
   if (B == 0) return TT_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  WsLayout ws[TT_MAX_SIDES];
-  const float* in[TT_MAX_SIDES];
-  int in_w[TT_MAX_SIDES];
-  GemmNT nt[TT_MAX_SIDES];
-  for (int t = 0; t < n; ++t) {
+  for (int t = 0; t < n; ++t)
     TT_CHECK_ARG(A[t] && A[t]->dense && A[t]->x && A[t]->y && A[t]->emb, "tt_towers_mlp_fwd: NULL activation buffers");
-    ws[t] = ws_layout(P[t], B, reinterpret_cast<char*>(workspaces[t]));
-    const int wx = P[t]->h0 + P[t]->kcat_e;
-    // x[:, 0:h0] = dense W_proj^T + b_proj        (base_tower.py:133)
-    nt[t] = GemmNT{A[t]->dense, P[t]->din, P[t]->w_proj, P[t]->din, P[t]->b_proj, reinterpret_cast<float*>(A[t]->x), wx, B, P[t]->h0,
-                   P[t]->din, false, 1.f};
-    nt[t].c_bf16 = P[t]->x_dtype == TT_BF16;
-    in[t] = reinterpret_cast<const float*>(A[t]->x);
-    in_w[t] = wx;
-  }
-  const bool drop = train && dropout_p > 0.f;
-  const int nh = P[0]->n_hidden;
+  const Pass p = make_pass(ctx, stream, n, P, A, nullptr, nullptr, B, train, dropout_p, seed, seed_dev, workspaces);
+  hipStream_t st = p.st;
+  if (int rc = check_sync_phase(p, "tt_towers_mlp_fwd")) return rc;
+  const int nh = p.nh, phase = p.phase;
   const bool fused = tail_fusable(n, P, train);
-  const int phase = P[0]->sync_phase;
-  if (phase != 0) {
-    if (nh != 1 || !train) {
-      tt_set_error("tt_towers_mlp_fwd: sync_phase %d needs a training pass over towers with exactly one hidden block (the pass is cut at its BatchNorm)", phase);
-      return TT_ERR_UNSUPPORTED;
-    }
-    for (int t = 0; t < n; ++t)
-      TT_CHECK_ARG(phase == 1 ? A[t]->bn_sync_local != nullptr : A[t]->bn_sync_all != nullptr, "tt_towers_mlp_fwd: NULL SyncBN buffer");
-  }
-  for (int t = 0; t < n; ++t) { nt[t].bf16 = P[0]->compute_dtype == TT_BF16; nt[t].workspace = ws[t].gemm; nt[t].workspace_bytes = ws[t].gemm_bytes; }
   const bool front = fused && front_fusable(n, P, A);    // projection + block Linear + chunk statistics in one launch
-  if (phase != 2 && !front)
+  if (phase != 2 && !front) {
+    GemmNT nt[TT_MAX_SIDES];                              // x[:, 0:h0] = dense W_proj^T + b_proj        (base_tower.py:133)
+    for (int t = 0; t < n; ++t) {
+      nt[t] = nt_item(p, t, A[t]->dense, P[t]->w_proj, P[t]->b_proj, reinterpret_cast<float*>(A[t]->x), P[t]->h0 + P[t]->kcat_e, P[t]->h0, P[t]->din);
+      nt[t].c_bf16 = P[t]->x_dtype == TT_BF16;
+    }
     if (int rc = tt_gemm_nt_batched(st, nt, n)) return rc;
+  }
   NtDeferred nd[TT_MAX_SIDES];
   for (int i = 0; i < nh; ++i) {
     const bool tail = fused && i == nh - 1;
-    Batch<BnStatArgs> bs{};
-    Batch<BnApplyArgs> ba{};
-    int hmax = 1, cmax = 1;
-    int64_t tmax = 1;
+    Batch<BnStatArgs> bs{}; Batch<BnApplyArgs> ba{};
     for (int t = 0; t < n; ++t) {
-      const int H = P[t]->hidden[i];
       TT_CHECK_ARG(A[t]->pre[i] && A[t]->act[i] && A[t]->mean[i] && A[t]->rstd[i], "tt_towers_mlp_fwd: NULL buffers of block %d", i);
-      nt[t] = GemmNT{in[t], in_w[t], P[t]->w[i], in_w[t], P[t]->b[i], A[t]->pre[i], H, B, H, in_w[t], false, 1.f};
-      nt[t].a_bf16 = i == 0 && P[t]->x_dtype == TT_BF16;
-      const int nchunks = chunks_for(B, H);
-      bs.a[t] = BnStatArgs{A[t]->pre[i], (int)B, H, (int)tt_cdiv(B, nchunks), nchunks, ws[t].col, A[t]->mean[i], A[t]->rstd[i],
-                           P[t]->bn_rm[i], P[t]->bn_rv[i], P[t]->bn_nbt[i]};
-      // dropout element index = GLOBAL row * H + column: the rank's first row enters through the salt
-      ba.a[t] = BnApplyArgs{A[t]->pre[i], B * H, H, A[t]->mean[i], A[t]->rstd[i], P[t]->bn_w[i], P[t]->bn_b[i],
-                            (((uint64_t)(i + 1) << 40) ^ ((uint64_t)t << 52)) + (uint64_t)P[t]->rng_row_offset * (uint64_t)H, A[t]->act[i]};
-      hmax = H > hmax ? H : hmax;
-      cmax = nchunks > cmax ? nchunks : cmax;
-      tmax = B * H > tmax ? B * H : tmax;
+      bs.a[t] = bn_stat_args(p, i, t);
+      ba.a[t] = bn_apply_args(p, i, t);
     }
-    for (int t = 0; t < n; ++t) {
-      nt[t].bf16 = P[0]->compute_dtype == TT_BF16; nt[t].workspace = ws[t].gemm; nt[t].workspace_bytes = ws[t].gemm_bytes;
-      nt[t].defer = tail ? &nd[t] : nullptr;
-    }
+    const BlockDims dim = block_dims(p, i);
     if (phase != 2 && !(front && tail))
-      if (int rc = tt_gemm_nt_batched(st, nt, n)) return rc;
-    if (tail) {
-      // slabs (+ bias) -> pre with the chunk statistics in the same pass, then everything up to the unit rows in one kernel
-      if (phase != 2) {
-        if (front) {
-          Batch<FrontArgs> fb{};
-          bool w16 = true;                                // every tower brings bf16 shadows of both weights (16-byte aligned)
-          for (int t = 0; t < n; ++t) {
-            fb.a[t] = FrontArgs{A[t]->dense, P[t]->din, P[t]->din, P[t]->w_proj, P[t]->b_proj, P[t]->h0,
-                                reinterpret_cast<uint16_t*>(A[t]->x), in_w[t], in_w[t], P[t]->w[i], P[t]->b[i], A[t]->pre[i], bs.a[t],
-                                reinterpret_cast<const uint16_t*>(P[t]->w_proj_bf16), reinterpret_cast<const uint16_t*>(P[t]->w_bf16[i])};
-            w16 = w16 && P[t]->w_proj_bf16 && P[t]->w_bf16[i] && tt_aligned(P[t]->w_proj_bf16, 16) && tt_aligned(P[t]->w_bf16[i], 16);
-          }
-          if (w16) {
-            TT_LDS_ONCE(kFrontLds, tower_front_kernel<true>);
-            tower_front_kernel<true><<<dim3((unsigned)cmax, (unsigned)n), kFrontThreads, kFrontLds, st>>>(fb);
-          } else {
-            TT_LDS_ONCE(kFrontLds, tower_front_kernel<false>);
-            tower_front_kernel<false><<<dim3((unsigned)cmax, (unsigned)n), kFrontThreads, kFrontLds, st>>>(fb);
-          }
-        } else if (nd[0].splits > 0) {
-          Batch<HeadArgs> hb{};
-          for (int t = 0; t < n; ++t) hb.a[t] = HeadArgs{nd[t].slabs, nd[t].slab_stride, nd[t].splits, P[t]->b[i], A[t]->pre[i], bs.a[t]};
-          tail_head_kernel<<<dim3((unsigned)cmax, (unsigned)n), kTailThreads, 0, st>>>(hb);
-        } else {
-          bn_stats_partial_kernel<<<dim3(1, (unsigned)cmax, (unsigned)n), kThreads, 0, st>>>(bs);
-        }
-        TT_LAUNCH_CHECK();
-      }
-      if (phase == 1) {                                 // SyncBN: hand this rank's statistics to the caller and stop
-        Batch<LocalArgs> la{};
-        for (int t = 0; t < n; ++t) la.a[t] = LocalArgs{bs.a[t].partial, bs.a[t].nchunks, bs.a[t].H, A[t]->bn_sync_local};
-        tail_local_stats_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(la);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-      }
-      if (phase == 2)                                   // ... and continue with every rank's triple as one "chunk"
-        for (int t = 0; t < n; ++t) {
-          bs.a[t].partial = const_cast<float*>(A[t]->bn_sync_all); bs.a[t].nchunks = P[t]->sync_ranks; bs.a[t].pstride = A[t]->bn_sync_stride;
-        }
-      Batch<TailFwdArgs> tf{};
-      for (int t = 0; t < n; ++t)
-        tf.a[t] = TailFwdArgs{bs.a[t], P[t]->bn_w[i], P[t]->bn_b[i], ba.a[t].salt, A[t]->act[i], P[t]->w_out, P[t]->b_out, P[t]->d_out,
-                              A[t]->y, A[t]->emb, nullptr, nullptr, 0, 1.f};
-      for (int t = 0; t < n; ++t)
-        if (A[t]->emb_packed) {
-          const int Dp = P[t]->d_out <= 32 ? 32 : 64;
-          __bf16* base = reinterpret_cast<__bf16*>(A[t]->emb_packed);
-          tf.a[t].pk_rows = base;
-          tf.a[t].pk_frag = base + tt_cdiv(B, 64) * 64 * Dp;
-          tf.a[t].Dp = Dp;
-          tf.a[t].pk_scale = A[t]->emb_pack_scale == 0.f ? 1.f : A[t]->emb_pack_scale;
-        }
-      bool fin = false;
-      int mine = 0;                                     // of the keyed plan (TT_OPT_DEFER_RIDERS): what this call hosts
-      if (int rc = tt_deferred_host(ctx, TT_DQ_SORT | TT_DQ_COMPACT, st, &mine)) return rc;
-      if (mine & TT_DQ_SORT) {
-        // the keyed plan's sort has been held back for this place: behind the front kernel, with one workgroup per tower in its
-        // grid that finishes the chunk statistics once -- the tail then reads 2 * H floats per workgroup
-        BnFinishRiders bf{};
-        fin = phase == 0 && ctx->bn_fin != nullptr;       // (SyncBN's second half merges rank triples: in the tail, as before)
-        for (int t = 0; t < n && fin; ++t) {
-          const BnStatArgs& s = bs.a[t];
-          bf.r[t] = BnFinishRider{s.partial, s.pstride ? s.pstride : 3 * s.H, s.nchunks, s.H, s.mean, s.rstd, s.rm, s.rv, s.nbt,
-                                  ctx->bn_fin + t * kBnFinStride};
-          tf.a[t].fin = bf.r[t].out;
-        }
-        if (int rc = tt_keyed_sort_run(ctx->dq->sort, st, &bf, fin ? n : 0)) return rc;
-      }
-      const int cr_wg = (mine & TT_DQ_COMPACT) ? ctx->dq->compact_wg : 0;      // a queued plan compaction rides in one extra grid row
-      const int64_t gx = tt_cdiv(B, 64) > cr_wg ? tt_cdiv(B, 64) : cr_wg;
-      const dim3 grid((unsigned)gx, (unsigned)(n + (cr_wg > 0 ? 1 : 0)));
-      if (fin) tail_fwd_kernel<true><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->dq->compact, cr_wg);
-      else tail_fwd_kernel<false><<<grid, kTailThreads, 0, st>>>(tf, drop, dropout_p, seed, seed_dev, ctx->dq->compact, cr_wg);
-      tt_deferred_taken(ctx, mine);
-      TT_LAUNCH_CHECK();
-      return TT_OK;
-    }
+      if (int rc = launch_layer_nt(p, i, tail ? nd : nullptr)) return rc;
+    if (tail) return fwd_narrow_tail(p, i, bs, nd, front, dim);
     if (train) {
       if (phase != 2) {
-        bn_stats_partial_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)cmax, (unsigned)n), kThreads, 0, st>>>(bs);
+        bn_stats_partial_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 64), (unsigned)dim.cmax, (unsigned)n), kThreads, 0, st>>>(bs);
         TT_LAUNCH_CHECK();
       }
-      if (phase == 1) {                                 // SyncBN on the separate kernels (any width): hand this rank's statistics out and stop
-        Batch<LocalArgs> la{};
-        for (int t = 0; t < n; ++t) la.a[t] = LocalArgs{bs.a[t].partial, bs.a[t].nchunks, bs.a[t].H, A[t]->bn_sync_local};
-        tail_local_stats_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(la);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-      }
-      if (phase == 2)                                   // ... and continue with every rank's triple as one "chunk"
-        for (int t = 0; t < n; ++t) {
-          bs.a[t].partial = const_cast<float*>(A[t]->bn_sync_all); bs.a[t].nchunks = P[t]->sync_ranks; bs.a[t].pstride = A[t]->bn_sync_stride;
-        }
-      if (i == nh - 1 && !fused && wide_tail_ok(n, P, train)) {
-        // statistics finish + BN apply + dropout + output Linear + L2 normalise + the score kernels' operand images in one launch
-        TT_LDS_ONCE(kWideLds, tail_fwd_wide_kernel);
-        Batch<TailFwdArgs> tf{};
-        for (int t = 0; t < n; ++t) {
-          tf.a[t] = TailFwdArgs{bs.a[t], P[t]->bn_w[i], P[t]->bn_b[i], ba.a[t].salt, A[t]->act[i], P[t]->w_out, P[t]->b_out, P[t]->d_out,
-                                A[t]->y, A[t]->emb, nullptr, nullptr, 0, 1.f};
-          if (A[t]->emb_packed) {
-            const int Dp = P[t]->d_out <= 32 ? 32 : (P[t]->d_out <= 64 ? 64 : 128);
-            __bf16* base = reinterpret_cast<__bf16*>(A[t]->emb_packed);
-            tf.a[t].pk_rows = base;
-            tf.a[t].pk_frag = base + tt_cdiv(B, 64) * 64 * Dp;
-            tf.a[t].Dp = Dp;
-            tf.a[t].pk_scale = A[t]->emb_pack_scale == 0.f ? 1.f : A[t]->emb_pack_scale;
-          }
-        }
-        tail_fwd_wide_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)n), kTailThreads, kWideLds, st>>>(tf, drop, dropout_p, seed, seed_dev);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-      }
-      bn_stats_finish_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(bs);
+      if (phase == 1) return sync_hand_out_stats(p, bs, dim.hmax);       // SyncBN on the separate kernels (any width)
+      if (phase == 2) sync_take_rank_stats(p, bs);
+      if (i == nh - 1 && !fused && wide_tail_ok(n, P, train)) return fwd_wide_tail(p, i, bs);
+      bn_stats_finish_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 64), (unsigned)n), kThreads, 0, st>>>(bs);
       TT_LAUNCH_CHECK();
     } else {
-      bn_eval_prepare_kernel<<<dim3((unsigned)tt_cdiv(hmax, 256), (unsigned)n), 256, 0, st>>>(bs);
+      bn_eval_prepare_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 256), (unsigned)n), 256, 0, st>>>(bs);
       TT_LAUNCH_CHECK();
     }
-    bn_apply_kernel<<<dim3((unsigned)ew_grid(ctx, tmax, n), (unsigned)n), kThreads, 0, st>>>(ba, drop, dropout_p, seed, seed_dev);
+    bn_apply_kernel<<<dim3((unsigned)ew_grid(ctx, dim.tmax, n), (unsigned)n), kThreads, 0, st>>>(ba, p.drop, dropout_p, seed, seed_dev);
     TT_LAUNCH_CHECK();
-    for (int t = 0; t < n; ++t) {
-      in[t] = A[t]->act[i];
-      in_w[t] = P[t]->hidden[i];
-    }
   }
+  // output Linear, L2 normalise; emb_packed is honoured on every path: here by the pack kernel
+  if (int rc = launch_layer_nt(p, nh, nullptr)) return rc;
   Batch<NormArgs> na{};
-  int dmax = 1;
-  for (int t = 0; t < n; ++t) {
-    nt[t] = GemmNT{in[t], in_w[t], P[t]->w_out, in_w[t], P[t]->b_out, A[t]->y, P[t]->d_out, B, P[t]->d_out, in_w[t], false, 1.f};
-    nt[t].a_bf16 = nh == 0 && P[t]->x_dtype == TT_BF16;
-    na.a[t] = NormArgs{A[t]->y, nullptr, nullptr, (int)B, P[t]->d_out, A[t]->emb};
-    dmax = P[t]->d_out > dmax ? P[t]->d_out : dmax;
-  }
-  for (int t = 0; t < n; ++t) { nt[t].bf16 = P[0]->compute_dtype == TT_BF16; nt[t].workspace = ws[t].gemm; nt[t].workspace_bytes = ws[t].gemm_bytes; }
-  if (int rc = tt_gemm_nt_batched(st, nt, n)) return rc;
+  for (int t = 0; t < n; ++t) na.a[t] = NormArgs{A[t]->y, nullptr, nullptr, (int)B, P[t]->d_out, A[t]->emb};
   if (!launch_l2norm_fast<false>(st, na, n, B)) l2norm_fwd_kernel<<<dim3((unsigned)tt_cdiv(B, 4), (unsigned)n), kThreads, 0, st>>>(na);
   TT_LAUNCH_CHECK();
-  (void)dmax;
-  for (int t = 0; t < n; ++t)                            // emb_packed is honoured on every path: here by the pack kernel
+  for (int t = 0; t < n; ++t)
     if (A[t]->emb_packed)
       if (int rc = tt_score_pack_bf16(ctx, A[t]->emb, B, P[t]->d_out, A[t]->emb_pack_scale, A[t]->emb_packed, stream)) return rc;
   return TT_OK;
@@ -1775,257 +1963,88 @@ int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   TT_CHECK_ARG(ctx && A && G && d_emb, "tt_towers_mlp_bwd: NULL argument");
   if (int rc = check_batch(n, P, B, dropout_p, workspaces, workspace_bytes, "tt_towers_mlp_bwd")) return rc;
   TT_CHECK_ARG(B >= 1, "tt_towers_mlp_bwd: B < 1");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool drop = train && dropout_p > 0.f;
-  const int nh = P[0]->n_hidden;
-  WsLayout ws[TT_MAX_SIDES];
-  float* dcur[TT_MAX_SIDES];
-  Batch<NormArgs> na{};
-  GemmTN tn[TT_MAX_SIDES];
-  GemmNN nn[TT_MAX_SIDES];
   for (int t = 0; t < n; ++t) {
     const tt_tower_grads* g = G[t];
     TT_CHECK_ARG(A[t] && g && d_emb[t] && g->w_proj && g->b_proj && g->w_out && g->b_out && g->d_x && g->d_y,
                  "tt_towers_mlp_bwd: NULL gradient buffers");
-    ws[t] = ws_layout(P[t], B, reinterpret_cast<char*>(workspaces[t]));
-    na.a[t] = NormArgs{A[t]->y, A[t]->emb, d_emb[t], (int)B, P[t]->d_out, g->d_y};
   }
+  const Pass p = make_pass(ctx, stream, n, P, A, G, d_emb, B, train, dropout_p, seed, seed_dev, workspaces);
+  hipStream_t st = p.st;
+  const int nh = p.nh, phase = p.phase;
   const bool fused = tail_fusable(n, P, train);
   const bool wide = !fused && wide_tail_ok(n, P, train);  // tail_bwd_wide_kernel + tail_bwd_apply_wide_kernel
-  const int phase = P[0]->sync_phase;
-  if (phase != 0) {
-    if (nh != 1 || !train) {
-      tt_set_error("tt_towers_mlp_bwd: sync_phase %d needs a training pass over towers with exactly one hidden block (the pass is cut at its BatchNorm)", phase);
-      return TT_ERR_UNSUPPORTED;
-    }
-    for (int t = 0; t < n; ++t)
-      TT_CHECK_ARG(G[t] && (phase == 1 ? G[t]->s_sync_local != nullptr : G[t]->s_sync_all != nullptr), "tt_towers_mlp_bwd: NULL SyncBN buffer");
-  }
-  // a score backward held back for this pass (TT_OPT_FUSE_SCORE_TAIL) writes d_emb: only the fused narrow tail can host it (below)
+  if (int rc = check_sync_phase(p, "tt_towers_mlp_bwd")) return rc;
+  // a score backward held back for this pass (TT_OPT_FUSE_SCORE_TAIL) writes d_emb: only the fused narrow tail can host it
   if (!(fused && phase == 0))
     if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
   if (!fused && !wide && phase != 2) {
+    Batch<NormArgs> na{};
+    for (int t = 0; t < n; ++t) na.a[t] = NormArgs{A[t]->y, A[t]->emb, d_emb[t], (int)B, P[t]->d_out, G[t]->d_y};
     if (!launch_l2norm_fast<true>(st, na, n, B)) l2norm_bwd_kernel<<<dim3((unsigned)tt_cdiv(B, 4), (unsigned)n), kThreads, 0, st>>>(na);
     TT_LAUNCH_CHECK();
   }
-  for (int t = 0; t < n; ++t) {
-    const tt_tower_grads* g = G[t];
-    const float* in_last = nh == 0 ? reinterpret_cast<const float*>(A[t]->x) : A[t]->act[nh - 1];
-    const int lw = last_width(P[t]);
-    tn[t] = GemmTN{g->d_y, P[t]->d_out, in_last, lw, g->w_out, lw, P[t]->d_out, lw, B, ws[t].tn[nh + 1], ws[t].tn_bytes[nh + 1], g->b_out};
-    dcur[t] = nh == 0 ? reinterpret_cast<float*>(g->d_x) : g->scratch[nh - 1];
-    TT_CHECK_ARG(dcur[t], "tt_towers_mlp_bwd: NULL scratch buffer");
-    nn[t] = GemmNN{g->d_y, P[t]->d_out, P[t]->w_out, lw, dcur[t], lw, B, lw, P[t]->d_out};
-    tn[t].b_bf16 = nh == 0 && P[t]->x_dtype == TT_BF16;
-    nn[t].c_bf16 = nh == 0 && P[t]->dx_dtype == TT_BF16;
-  }
-  for (int t = 0; t < n; ++t) tn[t].bf16 = nn[t].bf16 = P[0]->compute_dtype == TT_BF16;
+  for (int t = 0; t < n; ++t) TT_CHECK_ARG(d_in(p, nh, t), "tt_towers_mlp_bwd: NULL scratch buffer");
   // the slab reductions of all weight-gradient GEMMs run as ONE launch at the end (nothing in this pass reads them)
   TnPending pend;
-  // first block + projection as ONE launch (tt_gemm.h: GemmBack; d_pre of block 0 arrives in scratch[0]): its items, and whether
-  // the pass will take it -- asked twice: by the tail, which leaves a queued loss reduction to that launch, and at the launch
   GemmBack gb[TT_MAX_SIDES];
-  auto back_items = [&]() {
-    if (nh < 1 || P[0]->compute_dtype != TT_BF16) return false;
-    for (int t = 0; t < n; ++t) {
-      const tt_tower_grads* g = G[t];
-      const int wx = P[t]->h0 + P[t]->kcat_e;
-      if (P[t]->flags & TT_TOWER_UNFUSED_BACK) return false;
-      gb[t] = GemmBack{g->scratch[0], P[t]->hidden[0], A[t]->x, wx, wx, P[t]->x_dtype == TT_BF16, A[t]->dense, P[t]->din, P[t]->din,
-                       P[t]->w[0], P[t]->h0, reinterpret_cast<float*>(g->d_x), wx, P[t]->dx_dtype == TT_BF16, g->w[0], g->b[0],
-                       g->w_proj, g->b_proj, ws[t].tn[1], ws[t].tn_bytes[1], ws[t].tn[0], ws[t].tn_bytes[0], B};
-      gb[t].w16 = P[t]->w_bf16[0];
-    }
-    return tt_gemm_back_supported(gb, n);
-  };
-  bool loss_to_back = false;                             // the tail left a queued loss reduction to that launch
+  const bool back = back_items(p, gb);                   // the first block's one launch: decided once, for the tail and for block 0
+  LossHost loss = kLossNobody;
+  // the output layer (and, in the tails, the last block's column sums)
   if (fused) {
-    // L2-normalise backward, both output-layer GEMMs and the BN column sums of the last block in one kernel; the BN
-    // backward apply (after the batch-wide S1 / S2) in a second
-    const int i = nh - 1;
-    Batch<TailBwdArgs> tb{};
-    Batch<TailApplyArgs> tp{};
-    int cmax = 1;
-    for (int t = 0; t < n; ++t) {
-      const tt_tower_grads* g = G[t];
-      const int H = P[t]->hidden[i], D = P[t]->d_out;
-      TT_CHECK_ARG(g->w[i] && g->b[i] && g->bn_w[i] && g->bn_b[i], "tt_towers_mlp_bwd: NULL gradient buffers of block %d", i);
-      const int nchunks = chunks_for(B, H);
-      const uint64_t salt = (((uint64_t)(i + 1) << 40) ^ ((uint64_t)t << 52)) + (uint64_t)P[t]->rng_row_offset * (uint64_t)H;
-      const ColArgs col{nullptr, 0, A[t]->pre[i], A[t]->mean[i], A[t]->rstd[i], salt, (int)B, H, (int)tt_cdiv(B, nchunks), nchunks,
-                        ws[t].col, g->bn_b[i], g->bn_w[i]};
-      float* w_slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws[t].tn[nh + 1]) + 255) & ~uintptr_t(255));
-      float* b_slab = w_slab + (size_t)nchunks * D * H;
-      tb.a[t] = TailBwdArgs{A[t]->y, A[t]->emb, d_emb[t], g->d_y, D, P[t]->w_out, A[t]->act[i], dcur[t], col, w_slab, b_slab};
-      ColArgs colD = col;                               // SyncBN: S1 / S2 of every rank, one "chunk" each, over ranks * B rows
-      const int ranks = phase == 2 ? P[t]->sync_ranks : 1;
-      if (phase == 2) { colD.partial = const_cast<float*>(g->s_sync_all); colD.nchunks = ranks; colD.pstride = g->s_sync_stride; }
-      tp.a[t] = TailApplyArgs{colD, BnBwdArgs{dcur[t], A[t]->pre[i], B * H, H, 1.f / ((float)B * (float)ranks), A[t]->mean[i], A[t]->rstd[i],
-                                              P[t]->bn_w[i], g->bn_b[i], g->bn_w[i], salt},
-                              w_slab, b_slab, D, g->w_out, g->b_out, nchunks, 1.f / (float)ranks};
-      cmax = nchunks > cmax ? nchunks : cmax;
-    }
-    // a score backward that waits in the context (TT_OPT_FUSE_SCORE_TAIL) runs the head in its own launch when its workgroups
-    // are the head's: two towers, H = D = 64, 64-row chunks numbered like its 64-row tiles, its dA exactly d_emb in tower order
-    int mine = 0;                                       // of the score backward and the loss reduction: what is queued on this stream
-    if (int rc = tt_deferred_host(ctx, TT_DQ_SCORE_BWD | TT_DQ_LOSS, st, &mine)) return rc;
-    bool hosted = false;
-    if (mine & TT_DQ_SCORE_BWD) {
-      hosted = phase == 0 && n == 2 && ctx->dq->score_rows == B && ctx->dq->score_dA[0] == d_emb[0] && ctx->dq->score_dA[1] == d_emb[1];
-      for (int t = 0; hosted && t < n; ++t)
-        hosted = tb.a[t].D == 64 && tb.a[t].col.H == 64 && tb.a[t].col.rows_per_chunk == 64 && tb.a[t].col.nchunks == (int)tt_cdiv(B, 64);
-      if (hosted) {
-        if (int rc = tt_score_tail_bwd_launch(ctx, tb, drop, dropout_p, seed, seed_dev)) return rc;
-      } else if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) {
-        return rc;
-      }
-    }
-    // a queued loss reduction rides in tail_bwd's extra grid row; where the score backward ran the head (512-thread workgroups) it
-    // waits for the first block's launch below -- only the host reads it, and tail_bwd_apply's workgroups are on the step's chain
-    // -- or, in a pass without that launch, rides in tail_bwd_apply's extra grid row
-    const int fr_on = (mine & TT_DQ_LOSS) ? 1 : 0;
-    if (phase != 2 && !hosted) {
-      tail_bwd_kernel<<<dim3((unsigned)cmax, (unsigned)(n + fr_on)), kTailThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev, ctx->dq->loss,
-                                                                                           fr_on);
-      tt_deferred_taken(ctx, TT_DQ_LOSS & mine);
-      TT_LAUNCH_CHECK();
-    }
-    if (phase == 1) {                                   // SyncBN: hand this rank's column sums to the caller and stop
-      Batch<LocalArgs> la{};
-      for (int t = 0; t < n; ++t) la.a[t] = LocalArgs{tb.a[t].col.partial, tb.a[t].col.nchunks, tb.a[t].col.H, G[t]->s_sync_local};
-      tail_local_colsum_kernel<<<dim3(1, (unsigned)n), kThreads, 0, st>>>(la);                  // (fused tail: H <= 64)
-      TT_LAUNCH_CHECK();
-      return TT_OK;
-    }
-    {
-      loss_to_back = hosted && fr_on && back_items();
-      const int fr_here = hosted && fr_on && !loss_to_back ? 1 : 0;
-      tail_bwd_apply_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)(n + fr_here)), kTailThreads, 0, st>>>(tp, ctx->dq->loss, fr_here);
-      if (fr_here) tt_deferred_taken(ctx, TT_DQ_LOSS);
-      TT_LAUNCH_CHECK();
-    }
+    if (int rc = bwd_narrow_tail(p, back, &loss)) return rc;
+    if (phase == 1) return TT_OK;                         // SyncBN: the column sums are handed out, the pass stops
   } else if (wide) {
-    // L2-normalise backward, the output layer's data-gradient GEMM and the BN column sums of the last block in one kernel (the
-    // weight-gradient GEMM stays the split-K one); column-sum finish + BN backward apply in a second, below
-    const int i = nh - 1;
-    if (phase != 2) {
-      Batch<TailBwdArgs> tb{};
-      int cmax = 1;
-      for (int t = 0; t < n; ++t) {
-        const int H = P[t]->hidden[i];
-        const int nchunks = chunks_for(B, H);
-        const uint64_t salt = (((uint64_t)(i + 1) << 40) ^ ((uint64_t)t << 52)) + (uint64_t)P[t]->rng_row_offset * (uint64_t)H;
-        const ColArgs col{nullptr, 0, A[t]->pre[i], A[t]->mean[i], A[t]->rstd[i], salt, (int)B, H, (int)tt_cdiv(B, nchunks), nchunks,
-                          ws[t].col, G[t]->bn_b[i], G[t]->bn_w[i]};
-        tb.a[t] = TailBwdArgs{A[t]->y, A[t]->emb, d_emb[t], G[t]->d_y, P[t]->d_out, P[t]->w_out, nullptr, dcur[t], col, nullptr, nullptr};
-        cmax = nchunks > cmax ? nchunks : cmax;
-      }
-      tail_bwd_wide_kernel<<<dim3((unsigned)cmax, (unsigned)n), kWideBwdThreads, 0, st>>>(tb, drop, dropout_p, seed, seed_dev);
-      TT_LAUNCH_CHECK();
-      if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
-    }
+    if (phase != 2)
+      if (int rc = bwd_wide_head(p, &pend)) return rc;
   } else if (phase != 2) {
-    if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
-    if (int rc = tt_gemm_nn_batched(st, nn, n)) return rc;
+    if (int rc = launch_layer_bwd(p, nh, &pend)) return rc;
   }
   for (int i = nh - 1; i >= 0; --i) {
-    Batch<ColArgs> cb{};
-    Batch<BnBwdArgs> bb{};
-    int hmax = 1, cmax = 1;
-    int64_t tmax = 1;
+    const bool last = i == nh - 1;
+    if (int rc = check_block_grads(p, i)) return rc;
+    Batch<ColArgs> cb{}; Batch<BnBwdArgs> bb{};
     for (int t = 0; t < n; ++t) {
-      const tt_tower_grads* g = G[t];
-      const int H = P[t]->hidden[i];
-      TT_CHECK_ARG(g->w[i] && g->b[i] && g->bn_w[i] && g->bn_b[i], "tt_towers_mlp_bwd: NULL gradient buffers of block %d", i);
-      const int nchunks = chunks_for(B, H);
-      const uint64_t salt = (((uint64_t)(i + 1) << 40) ^ ((uint64_t)t << 52)) + (uint64_t)P[t]->rng_row_offset * (uint64_t)H;
-      // S1 = sum da -> bn bias grad ; S2 = sum da*xhat -> bn weight grad
-      cb.a[t] = ColArgs{dcur[t], H, A[t]->pre[i], A[t]->mean[i], A[t]->rstd[i], salt, (int)B, H, (int)tt_cdiv(B, nchunks), nchunks,
-                        ws[t].col, g->bn_b[i], g->bn_w[i]};
-      bb.a[t] = BnBwdArgs{dcur[t], A[t]->pre[i], B * H, H, 1.f / (float)B, A[t]->mean[i], A[t]->rstd[i], P[t]->bn_w[i], g->bn_b[i],
-                          g->bn_w[i], salt};
-      hmax = H > hmax ? H : hmax;
-      cmax = nchunks > cmax ? nchunks : cmax;
-      tmax = B * H > tmax ? B * H : tmax;
+      cb.a[t] = col_args(p, i, t, d_in(p, i + 1, t), P[t]->hidden[i]);
+      bb.a[t] = bn_bwd_args(p, i, t);
     }
-    if (wide && i == nh - 1 && phase != 1) {
+    const BlockDims dim = block_dims(p, i);
+    if (wide && last && phase != 1) {
       // the column sums of tail_bwd_wide_kernel (phase 2: of every rank, one "chunk" each) finished and applied in one launch
       Batch<TailApplyArgs> tp{};
       for (int t = 0; t < n; ++t) {
-        ColArgs colD = cb.a[t];
-        const int ranks = phase == 2 ? P[t]->sync_ranks : 1;
-        if (phase == 2) { colD.partial = const_cast<float*>(G[t]->s_sync_all); colD.nchunks = ranks; colD.pstride = G[t]->s_sync_stride; }
-        BnBwdArgs bn = bb.a[t];
-        bn.invB = 1.f / ((float)B * (float)ranks);
-        tp.a[t] = TailApplyArgs{colD, bn, nullptr, nullptr, P[t]->d_out, nullptr, nullptr, 0, 1.f / (float)ranks};
+        tp.a[t] = TailApplyArgs{cb.a[t], bb.a[t], nullptr, nullptr, P[t]->d_out, nullptr, nullptr, 0, 1.f};
+        if (phase == 2) tp.a[t].out_scale = sync_take_rank_colsums(p, tp.a[t].col, tp.a[t].bn, t, nullptr);
       }
       tail_bwd_apply_wide_kernel<<<dim3((unsigned)tt_cdiv(B, 64), (unsigned)n), kTailThreads, 0, st>>>(tp);
       TT_LAUNCH_CHECK();
-    } else if (!(fused && i == nh - 1)) {
-      if (phase != 2 && !(wide && i == nh - 1)) {
-        colsum_partial_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)cmax, (unsigned)n), kThreads, 0, st>>>(cb, drop, dropout_p, seed, seed_dev);
+    } else if (!(fused && last)) {                        // (the narrow tail has applied the last block's BN backward)
+      if (phase != 2 && !(wide && last)) {
+        colsum_partial_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 64), (unsigned)dim.cmax, (unsigned)n), kThreads, 0, st>>>(cb, p.drop, dropout_p, seed, seed_dev);
         TT_LAUNCH_CHECK();
       }
-      if (phase == 1) {                                 // SyncBN on the separate kernels: hand this rank's column sums out and stop
+      if (phase == 1) {                                   // SyncBN on the separate kernels: hand this rank's column sums out and stop
         if (int rc = tt_gemm_tn_flush(st, &pend)) return rc;     // (the output layer's weight-gradient slabs)
-        Batch<LocalArgs> la{};
-        for (int t = 0; t < n; ++t) la.a[t] = LocalArgs{cb.a[t].partial, cb.a[t].nchunks, cb.a[t].H, G[t]->s_sync_local};
-        tail_local_colsum_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(la);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
+        return sync_hand_out_colsums(p, cb, (int)tt_cdiv(dim.hmax, 64));
       }
-      if (phase == 2)                                   // S1 / S2 of every rank, one "chunk" each, over ranks * B rows
-        for (int t = 0; t < n; ++t) {
-          const int ranks = P[t]->sync_ranks, H = P[t]->hidden[i];
-          float* raw = ws[t].col + 2 * (size_t)hmax * kMaxChunks;         // (the third third of the column workspace is free here)
-          cb.a[t].partial = const_cast<float*>(G[t]->s_sync_all); cb.a[t].nchunks = ranks; cb.a[t].pstride = G[t]->s_sync_stride;
-          cb.a[t].out_scale = 1.f / (float)ranks; cb.a[t].sums_raw = raw;
-          bb.a[t].invB = 1.f / ((float)B * (float)ranks); bb.a[t].S1 = raw; bb.a[t].S2 = raw + H;
-        }
-      colsum_finish_kernel<<<dim3((unsigned)tt_cdiv(hmax, 64), (unsigned)n), kThreads, 0, st>>>(cb);
+      if (phase == 2)
+        for (int t = 0; t < n; ++t)                       // (the third third of the column workspace is free here)
+          sync_take_rank_colsums(p, cb.a[t], bb.a[t], t, p.ws[t].col + 2 * (size_t)dim.hmax * kMaxChunks);
+      colsum_finish_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 64), (unsigned)n), kThreads, 0, st>>>(cb);
       TT_LAUNCH_CHECK();
-      bn_bwd_apply_kernel<<<dim3((unsigned)ew_grid(ctx, tmax, n), (unsigned)n), kThreads, 0, st>>>(bb, train != 0, drop, dropout_p, seed, seed_dev);
+      bn_bwd_apply_kernel<<<dim3((unsigned)ew_grid(ctx, dim.tmax, n), (unsigned)n), kThreads, 0, st>>>(bb, p.train, p.drop, dropout_p, seed, seed_dev);
       TT_LAUNCH_CHECK();
     }
-    for (int t = 0; t < n; ++t) {
-      const tt_tower_grads* g = G[t];
-      const int H = P[t]->hidden[i];
-      const int iw = in_width(P[t], i);
-      const float* in_i = i == 0 ? reinterpret_cast<const float*>(A[t]->x) : A[t]->act[i - 1];
-      tn[t] = GemmTN{dcur[t], H, in_i, iw, g->w[i], iw, H, iw, B, ws[t].tn[1 + i], ws[t].tn_bytes[1 + i], g->b[i]};
-      tn[t].b_bf16 = i == 0 && P[t]->x_dtype == TT_BF16;
-      float* dnext = i == 0 ? reinterpret_cast<float*>(g->d_x) : g->scratch[i - 1];
-      TT_CHECK_ARG(dnext, "tt_towers_mlp_bwd: NULL scratch buffer");
-      nn[t] = GemmNN{dcur[t], H, P[t]->w[i], iw, dnext, iw, B, iw, H};
-      nn[t].c_bf16 = i == 0 && P[t]->dx_dtype == TT_BF16;
-      dcur[t] = dnext;
-    }
-    for (int t = 0; t < n; ++t) tn[t].bf16 = nn[t].bf16 = P[0]->compute_dtype == TT_BF16;
-    if (i == 0 && P[0]->compute_dtype == TT_BF16) {
-      // first block + projection: three independent products of d_pre in ONE launch (tt_gemm.h: GemmBack); the projection's
-      // gradients come out of the slab-reduction launch, d_x[:, 0:h0] is not materialised
-      if (back_items()) {
-        int mine = 0;
-        if (loss_to_back)
-          if (int rc = tt_deferred_host(ctx, TT_DQ_LOSS, st, &mine)) return rc;
-        if (int rc = tt_gemm_back_batched(st, gb, n, &pend, (mine & TT_DQ_LOSS) ? &ctx->dq->loss : nullptr)) return rc;
-        tt_deferred_taken(ctx, mine & TT_DQ_LOSS);
-        if (ctx->dq->defer_slabs) return tt_deferred_queue_slabs(ctx, st, &pend);     // rides in tt_embed_grad_bwd's launch
-        return tt_gemm_tn_flush(st, &pend);
-      }
-    }
-    if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
-    if (int rc = tt_gemm_nn_batched(st, nn, n)) return rc;
+    for (int t = 0; t < n; ++t) TT_CHECK_ARG(d_in(p, i, t), "tt_towers_mlp_bwd: NULL scratch buffer");
+    if (i == 0 && back) return bwd_first_block_back(p, gb, &pend, loss == kLossGemmBack);
+    if (int rc = launch_layer_bwd(p, i, &pend)) return rc;
   }
-  // dense projection: d_x[:, 0:h0]
+  // dense projection: from d_x[:, 0:h0]
+  GemmTN tn[TT_MAX_SIDES];
   for (int t = 0; t < n; ++t) {
-    const tt_tower_grads* g = G[t];
-    const int wx = P[t]->h0 + P[t]->kcat_e;
-    tn[t] = GemmTN{reinterpret_cast<const float*>(g->d_x), wx, A[t]->dense, P[t]->din, g->w_proj, P[t]->din, P[t]->h0, P[t]->din, B,
-                   ws[t].tn[0], ws[t].tn_bytes[0], g->b_proj};
+    tn[t] = tn_item(p, t, 0, reinterpret_cast<const float*>(G[t]->d_x), P[t]->h0 + P[t]->kcat_e, A[t]->dense, G[t]->w_proj, P[t]->h0, P[t]->din,
+                    G[t]->b_proj);
     tn[t].a_bf16 = P[t]->dx_dtype == TT_BF16;
   }
-  for (int t = 0; t < n; ++t) tn[t].bf16 = P[0]->compute_dtype == TT_BF16;
   if (int rc = tt_gemm_tn_batched(st, tn, n, &pend)) return rc;
   // (not deferred like the one-launch first-block backward above: at these widths the slabs are HBM traffic, not launch
   //  latency -- measured 0.508 ms per step either way at scripts/train.py's [512, 256] -> 128)

@@ -14,7 +14,6 @@ table gradients.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
@@ -46,6 +45,51 @@ def _sync_comm(sides):
 
 def _al(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+def _run_pass(items, one, many, key, sync):
+    """The dispatch of a tower pass, forward or backward, over items = (side, *that side's arguments of the C call): SyncBN in
+    two calls around ONE all-gather (twotower.h: sync_phase); one fused call (horizontal fusion: one launch per layer step covers
+    every tower) when the towers share B, depth and key(side); else one call per tower.  one / many: ops.tower_* / ops.towers_*.
+    sync = (position in an item of the struct that holds the SyncBN pointers, its field for this rank's buffer, for the gathered
+    one, for the gathered one's stride, floats per hidden column: forward 3 -- (n, mean, M2) -- backward 2 -- (S1, S2), added in
+    rank order).  A batched call runs on the first side's seed, which every side then takes.  Returns the SyncBN buffers or None."""
+    sides = [it[0] for it in items]
+    comm = _sync_comm(sides)
+    if comm is None and not (len(sides) > 1 and len({(s.B, s.tower.n_hidden) + key(s) for s in sides}) == 1):
+        for s, *args in items:
+            one(s.tower._params(), *args, s.B, s.train, s.p_drop, s.seed, s.emb.device, s.tower._seed_dev)
+        return None
+    s0 = sides[0]
+    params = [s.tower._params() for s in sides]
+    args = [list(col) for col in zip(*(it[1:] for it in items))]
+    call = lambda: many(params, *args, s0.B, s0.train, s0.p_drop, s0.seed, s0.emb.device, s0.tower._seed_dev)
+    keep = None
+    if comm is None:
+        call()
+    else:
+        at, local, gathered, stride, per = sync
+        widths = [per * s.tower.tower_hidden_dims[1] for s in sides]
+        loc = torch.empty(sum(widths), dtype=torch.float32, device=s0.emb.device)
+        where = [(it[at], p, 4 * sum(widths[:k])) for k, (it, p) in enumerate(zip(items, params))]
+        for s, (holder, p, off) in zip(sides, where):
+            setattr(holder, local, loc.data_ptr() + off)
+            p.sync_phase, p.sync_ranks, p.rng_row_offset = 1, comm.world, comm.rank * s.B
+        try:
+            call()                                  # stops at the local statistics / column sums
+            allg = comm.all_gather(loc)
+            for holder, p, off in where:
+                setattr(holder, gathered, allg.data_ptr() + off)
+                setattr(holder, stride, loc.numel())
+                p.sync_phase = 2
+            call()                                  # merges every rank's share in rank order
+        finally:
+            for p in params:
+                p.sync_phase = 0
+        keep = (loc, allg)
+    for s in sides:
+        s.seed = s0.seed
+    return keep
 
 
 class BaseTower(nn.Module):
@@ -341,45 +385,10 @@ class _TowersFn(torch.autograd.Function):
                     plan.keep = rows                    # keep the sort input alive until it has run
                 pl[:] = [store, psides, plan]
         live = [s for s in sides if s.B]
-        fused = len(live) > 1 and len({s.B for s in live}) == 1 and len({s.tower.n_hidden for s in live}) == 1 and \
-            len({(s.train, s.p_drop) for s in live}) == 1
-        comm = _sync_comm(live)
-        if comm is not None:
-            # SyncBN: the pass stops at the local BN statistics, ONE all-gather carries every tower's (n, mean, M2) triples,
-            # and the second half merges them in rank order (twotower.h: sync_phase)
-            s0 = live[0]
-            widths = [3 * s.tower.tower_hidden_dims[1] for s in live]
-            loc = torch.empty(sum(widths), dtype=torch.float32, device=s0.emb.device)
-            params = [s.tower._params() for s in live]
-            off = 0
-            for s, p, w in zip(live, params, widths):
-                s.acts_struct.bn_sync_local = loc.data_ptr() + 4 * off
-                p.sync_phase, p.sync_ranks, p.rng_row_offset = 1, comm.world, comm.rank * s.B
-                off += w
-            try:
-                ops.towers_fwd(params, [s.acts_struct for s in live], s0.B, s0.train, s0.p_drop, s0.seed, s0.emb.device, s0.tower._seed_dev)
-                allg = comm.all_gather(loc)
-                off = 0
-                for s, p, w in zip(live, params, widths):
-                    s.acts_struct.bn_sync_all, s.acts_struct.bn_sync_stride = allg.data_ptr() + 4 * off, loc.numel()
-                    p.sync_phase = 2
-                    off += w
-                ops.towers_fwd(params, [s.acts_struct for s in live], s0.B, s0.train, s0.p_drop, s0.seed, s0.emb.device, s0.tower._seed_dev)
-            finally:
-                for p in params:
-                    p.sync_phase = 0
-            for s in live:
-                s.seed, s.sync_keep = s0.seed, (loc, allg)
-        elif fused:           # horizontal fusion: one launch per layer step covers every tower
-            s0 = live[0]
-            ops.towers_fwd([s.tower._params() for s in live], [s.acts_struct for s in live], s0.B, s0.train, s0.p_drop, s0.seed,
-                           s0.emb.device, s0.tower._seed_dev)
-            for s in live:
-                s.seed = s0.seed
-        else:
-            for s in live:
-                tw = s.tower
-                ops.tower_fwd(tw._params(), s.acts_struct, s.B, s.train, s.p_drop, s.seed, s.emb.device, tw._seed_dev)
+        keep = _run_pass([(s, s.acts_struct) for s in live], ops.tower_fwd, ops.towers_fwd, lambda s: (s.train, s.p_drop),
+                         (1, "bn_sync_local", "bn_sync_all", "bn_sync_stride", 3))
+        for s in live if keep else ():
+            s.sync_keep = keep
         for s in sides:
             s.tower._last_packed = None if s.packed is None else (s.packed, float(s.tower.pack_scale))
         ctx.sides, ctx.plans, ctx.spans, ctx.n_flat = sides, plans, spans, len(flat)
@@ -445,42 +454,8 @@ class _TowersFn(torch.autograd.Function):
             for i, v in enumerate(views):
                 grads[pos + 2 + i] = v
             dxs[id(s)] = d_x[:, tw.tower_hidden_dims[0]:]
-        fused = len(prepared) > 1 and len({s.B for s, _, _ in prepared}) == 1 and \
-            len({s.tower.n_hidden for s, _, _ in prepared}) == 1 and len({(s.train, s.p_drop, s.seed) for s, _, _ in prepared}) == 1
-        comm = _sync_comm([s for s, _, _ in prepared])
-        if comm is not None:
-            s0 = prepared[0][0]
-            widths = [2 * s.tower.tower_hidden_dims[1] for s, _, _ in prepared]
-            loc = torch.empty(sum(widths), dtype=torch.float32, device=s0.emb.device)
-            params = [s.tower._params() for s, _, _ in prepared]
-            args = ([s.acts_struct for s, _, _ in prepared], [d for _, d, _ in prepared], [g for _, _, g in prepared], s0.B, s0.train,
-                    s0.p_drop, s0.seed, s0.emb.device, s0.tower._seed_dev)
-            off = 0
-            for (s, _, g), p, w in zip(prepared, params, widths):
-                g.s_sync_local = loc.data_ptr() + 4 * off
-                p.sync_phase, p.sync_ranks, p.rng_row_offset = 1, comm.world, comm.rank * s.B
-                off += w
-            try:
-                ops.towers_bwd(params, *args)
-                allg = comm.all_gather(loc)                         # every rank's (S1, S2), added in rank order
-                off = 0
-                for (s, _, g), p, w in zip(prepared, params, widths):
-                    g.s_sync_all, g.s_sync_stride = allg.data_ptr() + 4 * off, loc.numel()
-                    p.sync_phase = 2
-                    off += w
-                ops.towers_bwd(params, *args)
-            finally:
-                for p in params:
-                    p.sync_phase = 0
-        elif fused:
-            s0 = prepared[0][0]
-            ops.towers_bwd([s.tower._params() for s, _, _ in prepared], [s.acts_struct for s, _, _ in prepared],
-                           [d for _, d, _ in prepared], [g for _, _, g in prepared], s0.B, s0.train, s0.p_drop, s0.seed,
-                           s0.emb.device, s0.tower._seed_dev)
-        else:
-            for s, d_emb, g in prepared:
-                ops.tower_bwd(s.tower._params(), s.acts_struct, d_emb, g, s.B, s.train, s.p_drop, s.seed, s.emb.device,
-                              s.tower._seed_dev)
+        _run_pass([(s, s.acts_struct, d, g) for s, d, g in prepared], ops.tower_bwd, ops.towers_bwd, lambda s: (s.train, s.p_drop, s.seed),
+                  (3, "s_sync_local", "s_sync_all", "s_sync_stride", 2))
         if exch is not None:
             # the exchange's backward first: its local reduction is the launch that hosts a queued (deferred) slab reduction
             if ctx.exch_state is not None:

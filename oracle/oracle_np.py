@@ -135,7 +135,7 @@ def exact_sum_precondition(abs_sums) -> bool:
 
 
 # ------------------------------------------------------------------------------------------------
-# dropout mask of the HIP kernels (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip dropout_scale): the mask is never
+# dropout mask of the HIP kernels (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tail_bwd.h dropout_scale, csrc/tt_tower.hip block_salt): the mask is never
 # stored; every kernel regenerates it from (seed, element index).  Element (r, c) of hidden block i of tower t (t = the tower's
 # slot in the batched launch: 0 notice, 1 company; 0 for a tower launched alone) has index
 #   salt + r * H + c,   salt = (((i + 1) << 40) ^ (t << 52)) + rng_row_offset * H          (all mod 2^64)
@@ -166,7 +166,7 @@ def uniform01(seed: int, idx) -> np.ndarray:
 
 
 def dropout_salt(t: int, i: int, H: int, row_offset: int = 0) -> int:
-    """the element-index offset of hidden block i of tower slot t (csrc/tt_tower.hip, tt_towers_mlp_fwd / _bwd)"""
+    """the element-index offset of hidden block i of tower slot t (csrc/tt_tower.hip, block_salt)"""
     return (((((i + 1) << 40) ^ (t << 52)) & _M64) + row_offset * H) & _M64
 
 

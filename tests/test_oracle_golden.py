@@ -292,7 +292,7 @@ def test_dropout_oracle_without_masks_is_unchanged(manifest):
     assert np.array_equal(ev0["notice_emb"], ev1["notice_emb"]) and np.array_equal(ev0["company_emb"], ev1["company_emb"])
 
 
-# ---- the kernels' dropout mask restated in plain Python (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip)
+# ---- the kernels' dropout mask restated in plain Python (csrc/tt_common.h tt_mix32 / tt_uniform01, csrc/tt_tower.hip block_salt)
 def _mix32_scalar(x):
     x &= 0xFFFFFFFF
     x ^= x >> 16
