@@ -682,6 +682,41 @@ int tt_score_loss_finish_lq(tt_ctx* ctx, int64_t B, float shift, const float* lq
 int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
                         float shift, int64_t diag_offset, const float* lq_a, const float* lq_b, const float* sumexp_a,
                         const float* sumexp_b, const float* d_loss, float scale, float* dA, tt_stream stream);
+/* ---- repeated-entity mask of the in-batch softmax (TFRS: remove_accidental_hits) ---------------------------------------
+ * A notice has many bidders, so one batch holds several pairs of the same notice (and of the same company): row a's other
+ * known bidders, and exact copies of its positive, sit in its denominator as negatives.  With ent_n[i] / ent_c[i] the notice
+ * and the company that row i of the batch stands for (any int32 values are ordinary ids), a pair (a, b), a != b, is MASKED iff
+ * ent_n[a] == ent_n[b] or ent_c[a] == ent_c[b]; the diagonal never is.  The mask is symmetric.  A masked pair adds nothing to
+ * row a's sum nor to column b's and gets zero softmax weight; a row whose negatives are all masked keeps its positive term, so
+ * no sum is ever zero.  With M the mask and R / C the row- / column-direction logits (S, or the logQ-corrected ones above):
+ *   loss = 0.5 * [ mean_a (lse_b R.masked_fill(M, -inf)[a, :] - R[a, a]) + mean_b (lse_a C.masked_fill(M, -inf)[:, b] - C[b, b]) ]
+ *   d loss / d s_ab = (1 / 2B) [ softmax_row(R')_ab + softmax_col(C')_ab - 2 [a == b] ]
+ * Metrics (out8[1:], diag, ranks) stay on the RAW scores, bitwise those of the plain entry; rowsum / colsum / inv_* / the loss /
+ * the gradients change.  tt_score_loss_finish / _lq serve unchanged (the positive term is never masked).
+ * One set of entries: ent_n / ent_c (int32, device, [round_up(B, 64)] readable, 16-byte aligned, entries past B ignored) plus
+ * OPTIONAL logQ arguments -- NULL = uncorrected, non-NULL = as the *_lq entry (both or neither; then 2/T <= 40).  Square
+ * problems only (Ra == Rb, diag_offset == 0, both directions the same B); bf16 operands and the f32 parity path: anything else
+ * returns TT_ERR_UNSUPPORTED.
+ * tt_score_fwd_sym_bf16_mask = tt_score_fwd_sym_bf16 (lq_n NULL; w_n / w_c ignored) or tt_score_fwd_sym_bf16_lq on the masked sums.
+ * tt_score_bwd_bf16_mask = tt_score_bwd_bf16 (lq NULL) or tt_score_bwd_bf16_lq with zero weight for masked pairs; the inv /
+ * sumexp arrays must be the masked forward's.  Always the b-split kernel form; never hosted by the towers' backward launch (a
+ * queued score backward is launched in front of it).
+ * tt_score_dir_fwd_mask / tt_score_dir_bwd_mask = tt_score_dir_fwd / _bwd (lq NULL) or their _lq forms, masked. */
+int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                               float shift, float ab_scale, int32_t want_rank, const int32_t* ent_n, const int32_t* ent_c,
+                               const float* lq_n, const float* lq_c, float* rowsum, float* colsum, float* inv_row,
+                               float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8,
+                               float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream);
+int tt_score_bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* ent_n, const int32_t* ent_c,
+                           const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                           const float* d_loss, float scale, tt_stream stream);
+int tt_score_dir_fwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
+                          float shift, int64_t diag_offset, const int32_t* ent_n, const int32_t* ent_c, const float* lq_b,
+                          float* sumexp, float* diag, int32_t* rank, float* sumscore, tt_stream stream);
+int tt_score_dir_bwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
+                          float shift, int64_t diag_offset, const int32_t* ent_n, const int32_t* ent_c, const float* lq_a,
+                          const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale,
+                          float* dA, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

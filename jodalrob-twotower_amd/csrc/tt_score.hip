@@ -72,12 +72,16 @@ __device__ __forceinline__ float diag_score(const float* __restrict__ A, const f
 }
 
 // LQ (tt_score_dir_fwd_lq): sumexp adds exp(s - shift) w_b, w_b = tt_lq_weight(lq_b[b]) the B row's sampling weight
-template <bool VEC, bool LQ = false>
+// MK (tt_score_dir_fwd_mask; square, diag_off == 0): a pair a != b whose rows share a notice or a company id adds nothing to sumexp;
+// the diagonal, the ranks and the score sums stay on the raw scores
+template <bool VEC, bool LQ = false, bool MK = false>
 __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 float* __restrict__ sumexp, float* __restrict__ diag_out,
                                                                 int32_t* __restrict__ rank_out, float* __restrict__ sumscore,
-                                                                const float* __restrict__ lq_b = nullptr) {
+                                                                const float* __restrict__ lq_b = nullptr,
+                                                                const int32_t* __restrict__ ent_n = nullptr,
+                                                                const int32_t* __restrict__ ent_c = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float diag_s[RB];
@@ -101,6 +105,15 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
     dg[r] = diag_s[wr * 32 + rowmap(r, lh)];
     se[r] = 0.f; ss[r] = 0.f; rk[r] = 0;
   }
+  [[maybe_unused]] int ean[16], eac[16];                  // (MK) ids of this lane's 16 rows a
+  if constexpr (MK) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t a = r0 + wr * 32 + rowmap(r, lh);
+      ean[r] = a < Ra ? ent_n[a] : 0;
+      eac[r] = a < Ra ? ent_c[a] : 0;
+    }
+  }
   for (int64_t c0 = 0; c0 < Rb; c0 += CB) {
     f32x16 acc0, acc1;
 #pragma unroll
@@ -117,11 +130,25 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
       const int64_t col = c0 + wc * 64 + h * 32 + li;
       const bool cv = col < Rb;
       const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 1.f;
+      [[maybe_unused]] int ebn = 0, ebc = 0;
+      if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float s = (h == 0 ? acc0[r] : acc1[r]) * inv_t;
         const int64_t pos = r0 + wr * 32 + rowmap(r, lh) + diag_off;
-        if (cv) {
+        if constexpr (MK) {
+          // the plain instantiations' contractions written out (hipcc fuses s - shift and ss += s with the product s = acc / T there,
+          // and does not behind the select here): an inert mask gives the plain entry's sums and metrics bit for bit
+          if (cv) {
+            const float x = h == 0 ? acc0[r] : acc1[r];
+            float e = __expf(__builtin_fmaf(x, inv_t, -shift));
+            e = (col != pos && ((ean[r] == ebn) | (eac[r] == ebc))) ? 0.f : e;
+            if constexpr (LQ) se[r] += e * wb;
+            else se[r] += e;
+            ss[r] = __builtin_fmaf(x, inv_t, ss[r]);
+            rk[r] += (s > dg[r] || (s == dg[r] && col < pos)) ? 1 : 0;
+          }
+        } else if (cv) {
           if constexpr (LQ) se[r] += __expf(s - shift) * wb;
           else se[r] += __expf(s - shift);
           ss[r] += s;
@@ -150,12 +177,15 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
 
 // backward of one direction; NCH = ceil(D / 64) feature chunks kept as MFMA accumulators.
 // LQ (tt_score_dir_bwd_lq): the weight of (a, b) is exp(s - shift) (w_b / sumexp_a + w_a / sumexp_b), w the sampling weights
-template <int NCH, bool VEC, bool LQ = false>
+// MK (tt_score_dir_bwd_mask; square, diag_off == 0): a masked pair (score_dir_fwd_kernel) weighs nothing
+template <int NCH, bool VEC, bool LQ = false, bool MK = false>
 __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 const float* __restrict__ sumexp_a, const float* __restrict__ sumexp_b,
                                                                 const float* __restrict__ d_loss, float scale, float* __restrict__ dA,
-                                                                const float* __restrict__ lq_a = nullptr, const float* __restrict__ lq_b = nullptr) {
+                                                                const float* __restrict__ lq_a = nullptr, const float* __restrict__ lq_b = nullptr,
+                                                                const int32_t* __restrict__ ent_n = nullptr,
+                                                                const int32_t* __restrict__ ent_c = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float Ws[RB * LDW];
@@ -164,11 +194,13 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
   const int64_t r0 = (int64_t)blockIdx.x * RB;
   if (NCH == 1) stage<RB, VEC>(A, Ra, D, r0, 0, As, t);
   float ia[16], ua[16];
+  [[maybe_unused]] int ean[16], eac[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t a = r0 + wr * 32 + rowmap(r, lh);
     ia[r] = a < Ra ? 1.f / sumexp_a[a] : 0.f;
     if constexpr (LQ) ua[r] = a < Ra ? tt_lq_weight(lq_a[a]) : 0.f;
+    if constexpr (MK) { ean[r] = a < Ra ? ent_n[a] : 0; eac[r] = a < Ra ? ent_c[a] : 0; }
   }
   f32x16 dacc[NCH];
 #pragma unroll
@@ -195,6 +227,8 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
       const bool cv = col < Rb;
       const float ib = cv ? 1.f / sumexp_b[col] : 0.f;
       const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 0.f;
+      [[maybe_unused]] int ebn = 0, ebc = 0;
+      if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 32 + rowmap(r, lh);
@@ -203,6 +237,13 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
         if (cv) {
           if constexpr (LQ) w = __expf(s - shift) * (wb * ia[r] + ua[r] * ib);
           else w = __expf(s - shift) * (ia[r] + ib);
+          if constexpr (MK) {
+            // (the diagonal as the plain instantiations compile it: e (ia + ib) - 2 in one fma -- an inert mask gives their bits)
+            if (col == r0 + row + diag_off) {
+              if constexpr (!LQ) w = __builtin_fmaf(ia[r] + ib, __expf(s - shift), -2.f);
+              else w -= 2.f;
+            } else if ((ean[r] == ebn) | (eac[r] == ebc)) w = 0.f;
+          } else
           if (col == r0 + row + diag_off) w -= 2.f;
         }
         Ws[row * LDW + cl] = w;
@@ -540,9 +581,18 @@ inline bool vec_ok(const float* p, int D) { return tt_aligned(p, 16) && (D % 4 =
 
 // tt_score_dir_fwd and, with lq_b != NULL, tt_score_dir_fwd_lq (arguments checked by the entries)
 static int dir_fwd(const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift, int64_t diag_offset,
-                   const float* lq_b, float* sumexp, float* diag, int32_t* rank, float* sumscore, tt_stream stream) {
+                   const float* lq_b, float* sumexp, float* diag, int32_t* rank, float* sumscore, tt_stream stream,
+                   const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
+  if (ent_n) {                                           // tt_score_dir_fwd_mask
+    tt_dispatch([&](auto vec, auto lq) {
+      score_dir_fwd_kernel<vec, lq, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore,
+                                                                     lq_b, ent_n, ent_c);
+    }, vec_ok(A, D) && vec_ok(Bm, D), lq_b != nullptr);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+  }
   tt_dispatch([&](auto vec, auto lq) {
     score_dir_fwd_kernel<vec, lq><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp, diag, rank, sumscore, lq_b);
   }, vec_ok(A, D) && vec_ok(Bm, D), lq_b != nullptr);
@@ -564,10 +614,17 @@ static int loss_finish(int64_t B, float shift, const float* lq_n, const float* l
 // tt_score_dir_bwd and, with lq_a / lq_b != NULL, tt_score_dir_bwd_lq
 static int dir_bwd(const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift, int64_t diag_offset,
                    const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale,
-                   float* dA, tt_stream stream) {
+                   float* dA, tt_stream stream, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
   const auto go = [&](auto nch) {
+    if (ent_n) {                                         // tt_score_dir_bwd_mask
+      tt_dispatch([&](auto vec, auto lq) {
+        score_dir_bwd_kernel<nch, vec, lq, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b,
+                                                                             d_loss, scale, dA, lq_a, lq_b, ent_n, ent_c);
+      }, vec_ok(A, D) && vec_ok(Bm, D), lq_a != nullptr);
+      return;
+    }
     tt_dispatch([&](auto vec, auto lq) {
       score_dir_bwd_kernel<nch, vec, lq><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss,
                                                                      scale, dA, lq_a, lq_b);
@@ -652,6 +709,43 @@ int tt_score_dir_bwd_lq(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra
     return TT_ERR_UNSUPPORTED;
   }
   return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream);
+}
+
+// the masked directional entries: square problems only; lq NULL = uncorrected
+static int mask_dir_check(const char* who, int64_t Ra, int64_t Rb, int64_t diag_offset, float inv_t, bool lq) {
+  if (Ra != Rb || diag_offset != 0) {
+    tt_set_error("%s: the repeated-entity mask covers the square problem only (Ra == Rb, diag_offset == 0)", who);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (2.f * fabsf(inv_t) > (lq ? kLqMaxTwoInvT : 80.f)) {
+    tt_set_error("%s: 1/temperature = %g: needs 2/T <= %g", who, inv_t, lq ? kLqMaxTwoInvT : 80.f);
+    return TT_ERR_UNSUPPORTED;
+  }
+  return TT_OK;
+}
+
+int tt_score_dir_fwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                          int64_t diag_offset, const int32_t* ent_n, const int32_t* ent_c, const float* lq_b, float* sumexp,
+                          float* diag, int32_t* rank, float* sumscore, tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && ent_n && ent_c && sumexp && diag && rank, "tt_score_dir_fwd_mask: NULL argument");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_fwd_mask: bad shape");
+  TT_CHECK_ARG(Ra < ((int64_t)1 << 31) && Rb < ((int64_t)1 << 31), "tt_score_dir_fwd_mask: too many rows");
+  if (int rc = mask_dir_check("tt_score_dir_fwd_mask", Ra, Rb, diag_offset, inv_t, lq_b != nullptr)) return rc;
+  return dir_fwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_b, sumexp, diag, rank, sumscore, stream, ent_n, ent_c);
+}
+
+int tt_score_dir_bwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                          int64_t diag_offset, const int32_t* ent_n, const int32_t* ent_c, const float* lq_a, const float* lq_b,
+                          const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale, float* dA, tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && ent_n && ent_c && sumexp_a && sumexp_b && d_loss && dA, "tt_score_dir_bwd_mask: NULL argument");
+  TT_CHECK_ARG((lq_a != nullptr) == (lq_b != nullptr), "tt_score_dir_bwd_mask: lq_a and lq_b go together");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_bwd_mask: bad shape");
+  if (D > 4 * DK) {
+    tt_set_error("tt_score_dir_bwd_mask: D=%d > %d not supported", D, 4 * DK);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (int rc = mask_dir_check("tt_score_dir_bwd_mask", Ra, Rb, diag_offset, inv_t, lq_a != nullptr)) return rc;
+  return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream, ent_n, ent_c);
 }
 
 int tt_score_matrix(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float* S,

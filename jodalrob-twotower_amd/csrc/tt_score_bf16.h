@@ -33,6 +33,11 @@ __device__ __forceinline__ float add_asm(float a, float b) {
   return r;
 }
 
+// the repeated-entity mask (tt_score_*_mask entries): a pair (a, b), a != b, whose rows stand for the same notice or the same company
+// is no negative of either direction -- it leaves both softmax sums and gets no weight.  The caller keeps the diagonal out (its ids
+// are equal by construction).
+__device__ __forceinline__ bool same_entity(int en_a, int ec_a, int en_b, int ec_b) { return (en_a == en_b) | (ec_a == ec_b); }
+
 // fragments of 32-row tile t of a rows image [tile][k-step][half][row][8]: a wave-instruction reads 1 KB contiguous
 template <int KS>
 __device__ __forceinline__ void load_bfrag(const __bf16* __restrict__ b_rows, int64_t t, int c, int h, bf16x8 (&bf)[KS]) {

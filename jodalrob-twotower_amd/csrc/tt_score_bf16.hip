@@ -312,7 +312,8 @@ __global__ __launch_bounds__(NW * 64) void score_fwd_bf16_kernel(FwdArgs args) {
 // second, and the 16 softmax reciprocals (or exp-sums) of its rows this lane half needs.
 // X3: the lo images' fragments as well (bl, bml).
 // LQ: the 16 sampling weights of those rows as well (wv).
-template <int KS, bool X3 = false, bool LQ = false>
+// MK: their 16 notice ids and 16 company ids as well (en, ec).
+template <int KS, bool X3 = false, bool LQ = false, bool MK = false>
 struct BwdTile {
   static constexpr int KL = X3 ? KS : 1, DL = X3 ? KS / 2 : 1;
   bf16x8 b[KS];
@@ -321,13 +322,15 @@ struct BwdTile {
   bf16x8 bml[2][DL];
   float4 iv[4];
   float4 wv[LQ ? 4 : 1];
+  int4 en[MK ? 4 : 1], ec[MK ? 4 : 1];
 };
 
-template <int KS, bool X3, bool LQ>
-__device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
+template <int KS, bool X3, bool LQ, bool MK = false>
+__device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ, MK>& T, const __bf16* __restrict__ b_rows, const __bf16* __restrict__ b_frag,
                                               const float* __restrict__ ivsrc, int t, int c, int h,
                                               const __bf16* __restrict__ b_lo = nullptr, const __bf16* __restrict__ b_frag_lo = nullptr,
-                                              const float* __restrict__ wsrc = nullptr) {
+                                              const float* __restrict__ wsrc = nullptr, const int32_t* __restrict__ ensrc = nullptr,
+                                              const int32_t* __restrict__ ecsrc = nullptr) {
   constexpr int Dp = KS * 16, DT = KS / 2;
   load_bfrag<KS>(b_rows, t, c, h, T.b);
   if constexpr (X3) load_bfrag<KS>(b_lo, t, c, h, T.bl);
@@ -345,6 +348,13 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ>& T, const __bf
 #pragma unroll
     for (int q = 0; q < 4; ++q) T.wv[q] = *reinterpret_cast<const float4*>(wsrc + 32 * t + 4 * h + 8 * q);
   }
+  if constexpr (MK) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      T.en[q] = *reinterpret_cast<const int4*>(ensrc + 32 * t + 4 * h + 8 * q);
+      T.ec[q] = *reinterpret_cast<const int4*>(ecsrc + 32 * t + 4 * h + 8 * q);
+    }
+  }
 }
 
 // Structure of the tile loop: TWO operand buffers, the loop unrolled over them, every load issued unconditionally (past the
@@ -356,9 +366,14 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ>& T, const __bf
 // w_hi = bf16(w), w_lo = bf16(w - w_hi), and dA += w_hi B_lo + w_lo B_hi + w_hi B_hi (in this order, per b tile).
 // LQ (tt_score_bwd_bf16_lq): the weight of (a, b) is e_ab (w_b / rowsum_a + w_a / colsum_b) with the sampling weights w of the
 // two rows -- one multiply more per element than e_ab (1 / rowsum_a + 1 / colsum_b).
-template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false>
+// MK (tt_score_bwd_bf16_mask; square problems, bf16 operands): a pair whose rows share a notice or a company id weighs nothing
+// (softmax_term); the b tile's ids travel with its operands, a tile ahead -- at D = 256 they are loaded behind the S product, as the
+// LQ weights are there.  One wave per SIMD in every masked instantiation (launch_bsplit_mk): the ids of two tiles in flight are
+// 64 registers more.
+template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false, bool MK = false>
 __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2, KL = X3 ? KS : 1;
+  static_assert(!MK || !X3, "the repeated-entity mask: bf16 operands only");
   __shared__ float red[(NW / 2) * ROWS * Dp];
   // (this kernel's own copy of select_dir, a_row_setup and zero_acc, and its own sweep, tree and store: through the parts its
   //  D = 256 instantiations change their scratch size, and the forward's registers move with them -- profiles/NOTES.md)
@@ -389,6 +404,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   bf16x8 ares[AT][KS], ares_lo[AT][KL];
   float ia[AT], ua[AT];
   int pos[AT];
+  [[maybe_unused]] int ean[AT], eac[AT];                       // (MK) the a rows' notice / company ids
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
     load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
@@ -396,6 +412,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
     const int a = a0 + 32 * i + c;
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
     if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
+    if constexpr (MK) { ean[i] = a < Ra ? args.ent_n[a] : 0; eac[i] = a < Ra ? args.ent_c[a] : 0; }
     pos[i] = a + off;
   }
   const int posmin = a0 + off, posmax = a0 + ROWS - 1 + off;
@@ -410,9 +427,20 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   const float* const ivsrc = have_inv ? inv_b : dr.sumexp_b;
   const int tlast = nT - 1;
   constexpr bool WLATE = LQ && KS == 16;                       // LQ, D = 256: weights loaded behind the S product, not a tile ahead
-  auto compute = [&](const BwdTile<KS, X3, LQ && !WLATE>& T, int t) {
+  constexpr bool ELATE = MK && KS == 16;                       // MK, D = 256: the ids likewise
+  [[maybe_unused]] const int32_t* const ent_n = args.ent_n;
+  [[maybe_unused]] const int32_t* const ent_c = args.ent_c;
+  auto compute = [&](const BwdTile<KS, X3, LQ && !WLATE, MK && !ELATE>& T, int t) {
     const int b_lo = 32 * t;
     float ib[16], wb[16];
+    [[maybe_unused]] int ebn[16], ebc[16];                     // (MK) the b rows' ids, in the accumulator's row order
+    if constexpr (MK && !ELATE) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ebn[4 * q] = T.en[q].x; ebn[4 * q + 1] = T.en[q].y; ebn[4 * q + 2] = T.en[q].z; ebn[4 * q + 3] = T.en[q].w;
+        ebc[4 * q] = T.ec[q].x; ebc[4 * q + 1] = T.ec[q].y; ebc[4 * q + 2] = T.ec[q].z; ebc[4 * q + 3] = T.ec[q].w;
+      }
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) { ib[4 * q] = T.iv[q].x; ib[4 * q + 1] = T.iv[q].y; ib[4 * q + 2] = T.iv[q].z; ib[4 * q + 3] = T.iv[q].w; }
     if constexpr (LQ && !WLATE) {
@@ -448,10 +476,34 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
           wb[4 * q] = v.x; wb[4 * q + 1] = v.y; wb[4 * q + 2] = v.z; wb[4 * q + 3] = v.w;
         }
       }
+      if constexpr (ELATE) {
+        if (i == 0) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int4 vn = *reinterpret_cast<const int4*>(ent_n + b_lo + 4 * h + 8 * q);
+            const int4 vc = *reinterpret_cast<const int4*>(ent_c + b_lo + 4 * h + 8 * q);
+            ebn[4 * q] = vn.x; ebn[4 * q + 1] = vn.y; ebn[4 * q + 2] = vn.z; ebn[4 * q + 3] = vn.w;
+            ebc[4 * q] = vc.x; ebc[4 * q + 1] = vc.y; ebc[4 * q + 2] = vc.z; ebc[4 * q + 3] = vc.w;
+          }
+        }
+      }
       float w[16];
+      if constexpr (MK) {
+        if (band) {                                            // the tile(s) of the positives: the diagonal is never masked
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            w[r] = softmax_term<UNIT, LQ, true>(acc[r], c1, c2, ia[i], ua[i], ib[r], wb[r],
+                                                same_entity(ean[i], eac[i], ebn[r], ebc[r]) && b_lo + rowmap(r, h) != pos[i]);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            w[r] = softmax_term<UNIT, LQ, true>(acc[r], c1, c2, ia[i], ua[i], ib[r], wb[r], same_entity(ean[i], eac[i], ebn[r], ebc[r]));
+        }
+      } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         w[r] = softmax_term<UNIT, LQ>(acc[r], c1, c2, ia[i], ua[i], ib[r], wb[r]);
+      }
       if (b_lo + 31 >= Rb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
@@ -485,19 +537,19 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
         for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s], T.bm[s][d], dacc[i][d], 0, 0, 0);
     }
   };
-  BwdTile<KS, X3, LQ && !WLATE> T0, T1;
-  if constexpr (X3 && KS == 16) {                              // x3, D = 256: one tile in flight (two are 544 registers)
+  BwdTile<KS, X3, LQ && !WLATE, MK && !ELATE> T0, T1;
+  if constexpr ((X3 || MK) && KS == 16) {                      // x3 / MK, D = 256: one tile in flight (x3: two are 544 registers)
     for (int t = wave; t < nT; t += NW) {
-      bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo, wt_b);
+      bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo, wt_b, ent_n, ent_c);
       compute(T0, t);
     }
   } else {
-  bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
+  bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(wave, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b, ent_n, ent_c);
   __builtin_amdgcn_sched_barrier(0);                           // (issue order pinned: see the forward kernels)
   for (int t = wave; t < nT; t += 2 * NW) {
-    bwd_tile_load<KS, X3, LQ && !WLATE>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
+    bwd_tile_load<KS, X3, LQ && !WLATE>(T1, dr.b_rows, dr.b_frag, ivsrc, min(t + NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b, ent_n, ent_c);
     compute(T0, t);
-    bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b);
+    bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, min(t + 2 * NW, tlast), c, h, dr.b_lo, dr.b_frag_lo, wt_b, ent_n, ent_c);
     if (t + NW < nT) compute(T1, t + NW);
   }
   }
@@ -1414,6 +1466,13 @@ static void launch_bsplit(const BwdSetup& s, hipStream_t st) {
   tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, X3, l><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
 }
 
+// its masked instantiations (tt_score_bwd_bf16_mask)
+template <int KS, int AT, int NW>
+static void launch_bsplit_mk(const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
+  tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, false, l, true><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
+}
+
 // one streamed image, transposing LDS reads (score_bwd_tr_kernel)
 template <int KS, int AT>
 static void launch_tr(const BwdSetup& s, hipStream_t st) {
@@ -1506,6 +1565,36 @@ static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bw
   return TT_OK;
 }
 
+// tt_score_bwd_bf16_mask: the square problem with the repeated-entity mask (lq NULL: uncorrected).
+// One form for every shape, the b-split kernel: it takes any B and D <= 256 and the ids ride with its streamed tiles.  Masked
+// instantiations of the transposing and the workgroup-staged forms: not built (profiles/NOTES.md, "repeated-entity mask").  One wave
+// per SIMD, two a tiles per workgroup at D <= 64, as the bf16x3 launches -- the b ids of two tiles in flight are 64 registers.
+// Never queued for the towers' backward launch: a queued score backward goes in front of it.
+static int bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* ent_n, const int32_t* ent_c, const tt_score_bwd_lq* lq,
+                         int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss, float scale, tt_stream stream,
+                         const char* who) {
+  TT_CHECK_ARG(ent_n && ent_c && tt_aligned(ent_n, 16) && tt_aligned(ent_c, 16), "%s: ent_n / ent_c NULL or not 16-byte aligned", who);
+  BwdSetup s;
+  if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
+  for (int i = 0; i < n_dirs; ++i)
+    if (dirs[i].Ra != dirs[i].Rb || dirs[i].diag_offset != 0 || dirs[i].Ra != dirs[0].Ra) {
+      tt_set_error("%s: the repeated-entity mask covers the square problem only (Ra == Rb, diag_offset == 0)", who);
+      return TT_ERR_UNSUPPORTED;
+    }
+  s.a.ent_n = ent_n;
+  s.a.ent_c = ent_c;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
+  switch (padded_d(D)) {
+    case 32: launch_bsplit_mk<2, 2, 4>(s, st); break;
+    case 64: launch_bsplit_mk<4, 2, 4>(s, st); break;
+    case 128: launch_bsplit_mk<8, 1, 4>(s, st); break;
+    default: launch_bsplit_mk<16, 1, 4>(s, st); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 // tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq.
 // One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
 // takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
@@ -1545,6 +1634,12 @@ int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_sco
                          float inv_t, float shift, const float* d_loss, float scale, tt_stream stream) {
   TT_CHECK_ARG(lq, "tt_score_bwd_bf16_lq: NULL lq");
   return bwd_bf16(ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_lq");
+}
+
+int tt_score_bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* ent_n, const int32_t* ent_c,
+                           const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
+                           float scale, tt_stream stream) {
+  return bwd_bf16_mask(ctx, dirs, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_mask");
 }
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,

@@ -58,6 +58,10 @@ struct BwdArgs {
   // LQ kernels (tt_score_bwd_bf16_lq): per direction the sampling weights of the A rows and of the B rows (tt_score_bwd_lq)
   const float* wt_a[2];
   const float* wt_b[2];
+  // MK kernels (tt_score_bwd_bf16_mask; the b-split form, which reads the arguments itself): the rows' notice / company ids, the same
+  // two arrays for both directions (square problem)
+  const int32_t* ent_n;
+  const int32_t* ent_c;
 };
 
 // ---- the direction select ----------------------------------------------------------------------------------------------------
@@ -154,12 +158,16 @@ __device__ __forceinline__ void zero_acc(f32x16 (&dacc)[AT][DT]) {
 // ---- the softmax weight of a pair (a, b): the loss's gradient ------------------------------------------------------------------
 // e_ab (1 / rowsum_a + 1 / colsum_b) from the S accumulator x: e_ab = exp2(x) in the UNIT kernels (the operand images carry the
 // exponent's scale), exp2(x c1 + c2) otherwise.  LQ (tt_score_bwd_bf16_lq): e_ab (w_b / rowsum_a + w_a / colsum_b) with the sampling
-// weights w of the two rows -- one multiply more.  THE formula: every backward form takes it from here.
-template <bool UNIT, bool LQ>
-__device__ __forceinline__ float softmax_term(float x, float c1, float c2, float ia, float ua, float ib, float wb) {
+// weights w of the two rows -- one multiply more.  MK (tt_score_bwd_bf16_mask): 0 for a masked pair (same_entity; the caller keeps
+// the diagonal out).  THE formula: every backward form takes it from here.
+template <bool UNIT, bool LQ, bool MK = false>
+__device__ __forceinline__ float softmax_term(float x, float c1, float c2, float ia, float ua, float ib, float wb, bool masked = false) {
   const float e = UNIT ? __builtin_amdgcn_exp2f(x) : __builtin_amdgcn_exp2f(__builtin_fmaf(x, c1, c2));
-  if constexpr (LQ) return e * __builtin_fmaf(ua, ib, wb * ia);
-  else return e * (ia + ib);
+  float w;
+  if constexpr (LQ) w = e * __builtin_fmaf(ua, ib, wb * ia);
+  else w = e * (ia + ib);
+  if constexpr (MK) w = masked ? 0.f : w;
+  return w;
 }
 
 }  // namespace

@@ -66,6 +66,8 @@ struct SymArgs {
   const void* b_lo;
   const float* lq_n;                   // LQ kernels: [R] log sampling probabilities of the notice rows a / company rows b
   const float* lq_c;
+  const int32_t* ent_n;                // MK kernels: [R] notice / company ids of the rows (the same row stands for one pair)
+  const int32_t* ent_c;
 };
 
 // Notice tiles are staged through LDS once per WORKGROUP (all 8 waves sweep the same tiles I): read straight from L2 by
@@ -98,7 +100,11 @@ struct SymStage {
 // u_a is per lane -- the workgroup forms the weights of its NI * 32 notice rows once, into LDS behind the stage buffers, and a
 // wave reads one per swept tile.  The column accumulators take an fma where they took an add; the row partial two fma chains.  (Plain fmas, not inline asm: an
 // asm fma reading the v_exp_f32 result right behind it skips the trans-use wait state the compiler inserts for its own ops.)
-template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false>
+// MK: the repeated-entity mask (tt_score_fwd_sym_bf16_mask): e_ab of a pair a != b whose rows share a notice or a company id is zeroed
+// before it enters either sum; the maxima (ranks) and the diagonal stay on the raw scores.  The a rows' two ids ride in LDS behind
+// s_wn, [2][NI * 32], read one pair per swept tile; the resident tile's 2 x 16 ids are per register -- at D = 256 in LDS, [2][wave][32],
+// as WLDS keeps the weights (ELDS).  Ids past R are never compared: those rows are only met on the per-element path, behind `valid`.
+template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false, bool MK = false>
 __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   using ST = SymStage<KS, FP8, X3>;
   constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, kImgB = ST::kImgB, K64 = FP8 ? KS / 4 : 1, KL = X3 ? KS : 1;
@@ -117,6 +123,12 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   // (LQ, bf16x3 at D = 256: the resident tile's company weights live in LDS, [wave][32], read per tile -- in registers they spilled)
   constexpr bool WLDS = LQ && X3 && KS == 16;
   float* s_wc = s_wn + NI * 32 + wave * 32;
+  static_assert(!MK || (!FP8 && !X3 && JT == 1), "the repeated-entity mask: bf16 operands only");
+  constexpr bool ELDS = MK && KS == 16;
+  int* s_ean = reinterpret_cast<int*>(s_wn + (LQ ? NI * 32 + kSymWaves * 32 : 0));   // (MK) [NI * 32] notice ids of the a rows
+  int* s_eac = s_ean + NI * 32;                                                       //      their company ids
+  int* s_ebn = s_eac + NI * 32 + wave * 32;                                           // (ELDS) the resident tile's ids, [2][wave][32]
+  int* s_ebc = s_ebn + kSymWaves * 32;
   const int J0 = ((int)blockIdx.x * kSymWaves + wave) * JT;  // this wave's company tiles J0 .. J0 + JT - 1
   const int I0 = (int)blockIdx.y * NI, I1 = min(I0 + NI, nT);
   const bool active = J0 < nT;
@@ -140,6 +152,33 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
         }
     }
   }
+  [[maybe_unused]] int ebn[ELDS ? 1 : 16], ebc[ELDS ? 1 : 16];   // (MK) ids of the resident tile's rows b
+  if constexpr (MK) {
+    for (int i = threadIdx.x; i < slots; i += kSymThreads) {
+      const int a = I0 * 32 + i;
+      s_ean[i] = a < R ? g.ent_n[a] : 0;                  // (read after the sweep's first barrier)
+      s_eac[i] = a < R ? g.ent_c[a] : 0;
+    }
+    if constexpr (ELDS) {
+      if (lane < 32) {
+        const int b = 32 * J0 + lane;
+        s_ebn[lane] = b < R ? g.ent_n[b] : 0;
+        s_ebc[lane] = b < R ? g.ent_c[b] : 0;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int b = 32 * J0 + rowmap(r, h);
+        ebn[(ELDS ? 0 : r)] = b < R ? g.ent_n[b] : 0;
+        ebc[(ELDS ? 0 : r)] = b < R ? g.ent_c[b] : 0;
+      }
+    }
+  }
+  // (MK) is (a, register r of the resident tile) a masked pair?  (the diagonal: the caller's business)
+  auto masked = [&](int ean, int eac, int r) -> bool {
+    if constexpr (ELDS) return same_entity(ean, eac, s_ebn[rowmap(r, h)], s_ebc[rowmap(r, h)]);
+    else return same_entity(ean, eac, ebn[(ELDS ? 0 : r)], ebc[(ELDS ? 0 : r)]);
+  };
   // the company weight of register r (resident tile j)
   auto wreg = [&](int j, int r) -> float { if constexpr (WLDS) return s_wc[rowmap(r, h)]; else return wb[j][(WLDS ? 0 : r)]; };
   const float c1 = g.c1, c2 = g.c2;
@@ -234,6 +273,8 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
         }
         const int il = (I - I0) * 32 + c;
         const float ua = LQ ? s_wn[il] : 1.f;
+        [[maybe_unused]] int ean = 0, eac = 0;
+        if constexpr (MK) { ean = s_ean[il]; eac = s_eac[il]; }
         float rs_tot = 0.f, xb_tot = kNegBig, xa_tot = kNegBig;
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
@@ -242,6 +283,10 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
             float e[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) e[r] = ex(acc[j][r]);
+            if constexpr (MK) {                            // (I != J: no positive in this tile)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) e[r] = masked(ean, eac, r) ? 0.f : e[r];
+            }
             if constexpr (LQ) {
 #pragma unroll
               for (int r = 0; r < 16; ++r) colacc[j][r] = __builtin_fmaf(e[r], ua, colacc[j][r]);
@@ -273,7 +318,8 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
               const int b = 32 * J + rowmap(r, h);
               const float x = acc[j][r];
               const bool valid = b < R && a < R;
-              const float e = valid ? ex(x) : 0.f;
+              float e = valid ? ex(x) : 0.f;
+              if constexpr (MK) e = (b != a && masked(ean, eac, r)) ? 0.f : e;
               if constexpr (LQ) {
                 colacc[j][r] = __builtin_fmaf(e, ua, colacc[j][r]);
                 rsum = __builtin_fmaf(e, wreg(j, r), rsum);
@@ -568,8 +614,9 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
                        float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col, float* diag,
                        int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
                        bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
-                       float* w_n = nullptr, float* w_c = nullptr) {
+                       float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr) {
   const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
+  const bool mk = ent_n != nullptr;                        // tt_score_fwd_sym_bf16_mask passes both (checked there)
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
   TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
@@ -610,6 +657,8 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   g.want_rank = want_rank ? 1 : 0;
   g.lq_n = lq_n;
   g.lq_c = lq_c;
+  g.ent_n = ent_n;
+  g.ent_c = ent_c;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // fp8, D = 256: two company tiles per wave (half the workgroups along J, half the slab rows)
   const int jt = (fp8 && L.Dp == 256) ? 2 : 1;
@@ -617,28 +666,39 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   const dim3 grid((unsigned)n_groups, (unsigned)L.n_chunks);
   const size_t slot_bytes = sizeof(float) * 3 * kSymWaves * L.NI * 32;
   const size_t wn_bytes = sizeof(float) * (L.NI * 32 + kSymWaves * 32);   // (LQ) notice weights (+ company weights, x3 D = 256)
-  // one launch per form (fp8 has neither an x3 nor an LQ form); only the x3 and LQ forms set their LDS limit
-  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc) -> int {
+  const size_t ent_bytes = sizeof(int) * 2 * (L.NI * 32 + kSymWaves * 32); // (MK) the a rows' ids (+ the resident tiles', D = 256)
+  // one launch per form (fp8 has neither an x3 nor an LQ form, the mask bf16 operands only); only the x3, LQ and MK forms set their LDS limit
+  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc, auto mkc) -> int {
     constexpr int JT = fp8c && ks == 16 ? 2 : 1;                  // = jt
-    const size_t lds = slot_bytes + 2 * SymStage<ks, fp8c, x3c>::kBytes + (lqc ? wn_bytes : 0);
+    const size_t lds = slot_bytes + 2 * SymStage<ks, fp8c, x3c>::kBytes + (lqc ? wn_bytes : 0) + (mkc ? ent_bytes : 0);
     return tt_dispatch([&](auto u) -> int {
-      if constexpr (x3c || lqc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc>);
-      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc><<<grid, kSymThreads, lds, st>>>(g);
+      if constexpr (x3c || lqc || mkc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc>);
+      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc><<<grid, kSymThreads, lds, st>>>(g);
       return TT_OK;
     }, unit);
   };
   const std::false_type no{};
   int rc;
-  if (fp8) {
+  if (mk) {
     const std::true_type yes{};
-    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no) : go(tt_c<16>, yes, no, no));
+    rc = tt_dispatch([&](auto lqc) {
+      switch (L.Dp) {
+        case 32: return go(tt_c<2>, no, no, lqc, yes);
+        case 64: return go(tt_c<4>, no, no, lqc, yes);
+        case 128: return go(tt_c<8>, no, no, lqc, yes);
+        default: return go(tt_c<16>, no, no, lqc, yes);
+      }
+    }, lq);
+  } else if (fp8) {
+    const std::true_type yes{};
+    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no) : go(tt_c<16>, yes, no, no, no));
   } else {
     rc = tt_dispatch([&](auto x3c, auto lqc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, x3c, lqc);
-        case 64: return go(tt_c<4>, no, x3c, lqc);
-        case 128: return go(tt_c<8>, no, x3c, lqc);
-        default: return go(tt_c<16>, no, x3c, lqc);
+        case 32: return go(tt_c<2>, no, x3c, lqc, no);
+        case 64: return go(tt_c<4>, no, x3c, lqc, no);
+        case 128: return go(tt_c<8>, no, x3c, lqc, no);
+        default: return go(tt_c<16>, no, x3c, lqc, no);
       }
     }, x3, lq);
   }
@@ -721,6 +781,19 @@ int tt_score_fwd_sym_bf16x3_lq(tt_ctx* ctx, const void* N_packed, const void* C_
   TT_CHECK_ARG(lq_n && lq_c && w_n && w_c, "tt_score_fwd_sym_bf16x3_lq: NULL argument");
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3_lq", true, lq_n, lq_c, w_n, w_c);
+}
+
+int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                               float shift, float ab_scale, int32_t want_rank, const int32_t* ent_n, const int32_t* ent_c,
+                               const float* lq_n, const float* lq_c, float* rowsum, float* colsum, float* inv_row, float* inv_col,
+                               float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
+                               size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(ent_n && ent_c, "tt_score_fwd_sym_bf16_mask: NULL ent_n / ent_c");
+  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_mask: lq_n and lq_c go together");
+  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_mask: the logQ correction needs w_n / w_c");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_mask", false, lq_n, lq_c,
+                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c);
 }
 
 }  // extern "C"

@@ -48,20 +48,33 @@ class DevicePairLoader:
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
-                 shuffle: bool, seed: int = 42, log_q=None):
-        """log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
+                 shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False):
+        """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
+        task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
+        log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
         every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
             raise KeyError("pair refers to an entity that is not in the feature store")      # reference raises KeyError: :495-498
         self.pairs = torch.from_numpy(pairs).to(notice.device)
+        self.entity = None
+        self.set_mask_repeats(mask_repeats)
         # the epoch permutation is drawn where it is used: a host randperm of 1.6 M pairs + its upload cost ~20 ms per epoch,
         # a third of a 68-ms epoch at batch 8192 (profiles/NOTES.md, round 4)
         self._gen = torch.Generator(device=self.pairs.device)
         self._gen.manual_seed(seed)
         self.log_q = None
         self.set_log_q(log_q)
+
+    def set_mask_repeats(self, mask_repeats: bool) -> None:
+        """Turns the repeated-entity mask on / off for every batch this loader produces from now on: with it `entity` holds the pair
+        table's columns as int32 [2, P] (notice indices, company indices)."""
+        self.entity = None
+        if mask_repeats:
+            if self.pairs.numel() and int(self.pairs.max()) > np.iinfo(np.int32).max:
+                raise ValueError("mask_repeats: an entity index does not fit int32")
+            self.entity = self.pairs.t().to(torch.int32).contiguous()
 
     def set_log_q(self, log_q) -> None:
         """(notice [Nn], company [Nc]) f32 log sampling probabilities per entity, or None: turns the logQ correction on / off for
@@ -94,6 +107,23 @@ class DevicePairLoader:
         if self.log_q is not None:
             out["notice"]["log_q"] = self.log_q[0][sel[:, 0]]
             out["company"]["log_q"] = self.log_q[1][sel[:, 1]]
+        if self.entity is not None:
+            out["notice"]["entity"] = sel[:, 0].to(torch.int32)
+            out["company"]["entity"] = sel[:, 1].to(torch.int32)
+        return out
+
+    def epoch_entity(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """int32 [n_batches, 2, Bp] (Bp = batch_size rounded up to 4): the pairs' (notice index, company index) in this epoch's order,
+        laid out as epoch_log_q's array -- ONE gather per epoch, every slice 16 bytes aligned.  None without mask_repeats."""
+        if self.entity is None:
+            return None
+        n, B = self.pairs.shape[0], self.batch_size
+        ent = self.entity if order is None else self.entity[:, order]
+        nb, Bp = (n + B - 1) // B, (B + 3) // 4 * 4
+        flat = torch.zeros((2, nb * B), dtype=torch.int32, device=self.pairs.device)
+        flat[:, :n] = ent
+        out = torch.zeros((nb, 2, Bp), dtype=torch.int32, device=self.pairs.device)
+        out[:, :, :B] = flat.view(2, nb, B).transpose(0, 1)
         return out
 
     def epoch_log_q(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -148,7 +178,11 @@ class DevicePairLoader:
         lq = self.epoch_log_q(order)
         if lq is not None and U > 1:
             raise NotImplementedError("the logQ correction is not supported by the unrolled step")
-        kw = lambda lo, m: {} if lq is None else {"log_q": (lq[lo // B, 0, :m], lq[lo // B, 1, :m])}
+        ent = self.epoch_entity(order)
+        if ent is not None and U > 1:
+            raise NotImplementedError("the repeated-entity mask is not supported by the unrolled step")
+        kw = lambda lo, m: {**({} if lq is None else {"log_q": (lq[lo // B, 0, :m], lq[lo // B, 1, :m])}),
+                            **({} if ent is None else {"entity": (ent[lo // B, 0, :m], ent[lo // B, 1, :m])})}
         lo = 0
         while U > 1 and lo + U * B <= n:                      # unrolled.UnrolledTrainStep: U full batches per graph launch
             for r in graphed_step.steps_from_store(self.notice, self.company, self.pairs, order, [lo + j * B for j in range(U)]):
@@ -177,6 +211,9 @@ class DevicePairLoader:
         if self.log_q is not None:
             out["notice"]["log_q"] = self.log_q[0][sel[:, 0]]
             out["company"]["log_q"] = self.log_q[1][sel[:, 1]]
+        if self.entity is not None:
+            out["notice"]["entity"] = sel[:, 0].to(torch.int32)
+            out["company"]["entity"] = sel[:, 1].to(torch.int32)
         return out
 
 

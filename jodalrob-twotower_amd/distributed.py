@@ -547,9 +547,11 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
             self.exchange.poll_overflow()          # rejects a step whose rows did not fit the buckets (non-blocking, <= poll_lag steps late)
         return super().forward(batch, return_metrics)
 
-    def _score_ce(self, n, c, inv_t, first_call, log_q=None):
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None):
         if log_q is not None:
             raise NotImplementedError("the logQ correction (a batch with 'log_q') is not supported by the sharded task")
+        if entity is not None:
+            raise NotImplementedError("the repeated-entity mask (a batch with 'entity') is not supported by the sharded task")
         if self.negatives == "global" and self.exchange.world > 1:
             if self._dense_loss:
                 raise NotImplementedError("global in-batch negatives support the default cross-entropy loss only")

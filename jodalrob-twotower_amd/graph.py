@@ -30,6 +30,7 @@ from .optim import FusedAdam
 class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
     _log_q_ok = True               # batches may carry "log_q" (the logQ correction); the unrolled / segmented steps refuse them
+    _entity_ok = True              # batches may carry "entity" (the repeated-entity mask); likewise
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
@@ -54,6 +55,14 @@ class GraphedTrainStep:
                 raise NotImplementedError(f"the logQ correction (a batch with 'log_q') is not supported by {type(self).__name__}")
             if getattr(task, "exchange", None) is not None:
                 raise NotImplementedError("the logQ correction (a batch with 'log_q') is not supported by the sharded task")
+        # repeated-entity mask: an example batch with "entity" (either side) gives both sides a static int32 [B] buffer, filled at every
+        # hand-over through the same copy segments (a side the batch does not carry: its row indices, all-distinct)
+        self._has_entity = any(example_batch[side].get("entity") is not None for side in ("notice", "company"))
+        if self._has_entity:
+            if not self._entity_ok:
+                raise NotImplementedError(f"the repeated-entity mask (a batch with 'entity') is not supported by {type(self).__name__}")
+            if getattr(task, "exchange", None) is not None:
+                raise NotImplementedError("the repeated-entity mask (a batch with 'entity') is not supported by the sharded task")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
@@ -69,6 +78,12 @@ class GraphedTrainStep:
             for side in ("notice", "company"):
                 t = example_batch[side].get("log_q")
                 self.static[side]["log_q"] = self._check_log_q(t, side, B, dev).clone() if t is not None else self._lq_zero.clone()
+        if self._has_entity:
+            B = example_batch["notice"]["dense"].shape[0]
+            self._ent_iota = torch.arange(B, dtype=torch.int32, device=dev)
+            for side in ("notice", "company"):
+                t = example_batch[side].get("entity")
+                self.static[side]["entity"] = self._check_entity(t, side, B, dev).clone() if t is not None else self._ent_iota.clone()
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
@@ -421,6 +436,23 @@ class GraphedTrainStep:
         t = t.contiguous()
         return t if t.data_ptr() % 16 == 0 else t.clone()
 
+    @staticmethod
+    def _check_entity(t, side, B, dev):
+        """t as a contiguous, 16-byte aligned int32 [B] on dev (as _check_log_q)"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"{side} entity must be an int32 tensor of shape [{B}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != dev:
+            raise ValueError(f"{side} entity is on {t.device}, the captured step on {dev}")
+        t = t.contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    def _entity_pairs(self, ent_n, ent_c):
+        """copy segments of this step's entity ids into the static buffers (a side given as None: the row indices)"""
+        B, dev = self._ent_iota.shape[0], self._ent_iota.device
+        return [(self.static[side]["entity"], self._check_entity(t, side, B, dev) if t is not None else self._ent_iota)
+                for side, t in (("notice", ent_n), ("company", ent_c))]
+
     def _log_q_pairs(self, lq_n, lq_c):
         """copy segments of this step's log q into the static buffers (a side given as None: zeros)"""
         B, dev = self._lq_zero.shape[0], self._lq_zero.device
@@ -438,6 +470,12 @@ class GraphedTrainStep:
                              " a log_q, the batch " + ("has none" if self._has_log_q else "carries one"))
         if self._has_log_q:
             pairs += self._log_q_pairs(lq_n, lq_c)
+        ent_n, ent_c = batch["notice"].get("entity"), batch["company"].get("entity")
+        if (ent_n is not None or ent_c is not None) != self._has_entity:
+            raise ValueError("entity mismatch: the step was captured " + ("with" if self._has_entity else "without") +
+                             " entity ids, the batch " + ("has none" if self._has_entity else "carries them"))
+        if self._has_entity:
+            pairs += self._entity_pairs(ent_n, ent_c)
         for side in ("notice", "company"):
             d, v = batch[side]["dense"], batch[side]["kjt"].values()
             sd, sv = self.static[side]["dense"], self.static[side]["kjt"].values()
@@ -473,7 +511,7 @@ class GraphedTrainStep:
         return self.result
 
     def step_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor] = None, offset: int = 0,
-                        log_q=None):
+                        log_q=None, entity=None):
         """Train on the B pairs `pairs[order[offset : offset + B]]` (order None: `pairs[offset : offset + B]`) gathered straight
         out of the device-resident feature stores into the static buffers -- ONE launch (tt_batch_ingest_store: dense rows, ids,
         key-major fused rows, the step scalars) and the replay; nothing per step crosses PCIe and no batch tensors are built
@@ -481,12 +519,17 @@ class GraphedTrainStep:
         scripts/train.py:261-273).  `pairs`: int64 [P, 2] on the device, (notice row, company row) per pair; the stores are
         data_loader.DeviceFeatureStore objects (`.dense` f32 [N, D], `.categorical` int64 [N, K]).
         log_q: (notice, company) f32 [B] of this step's pairs for a step captured with a log_q (DevicePairLoader.step_batches passes
-        slices of its per-epoch array): two more copy segments of the same launch."""
+        slices of its per-epoch array): two more copy segments of the same launch.
+        entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
+        DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise."""
         if (log_q is not None) != self._has_log_q:
             raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
                              " a log_q, step_from_store got " + ("none" if self._has_log_q else "one"))
-        self._ingest_from_store(notice_store, company_store, pairs, order, offset,
-                                extra=self._log_q_pairs(*log_q) if log_q is not None else None)
+        if (entity is not None) != self._has_entity:
+            raise ValueError("entity mismatch: the step was captured " + ("with" if self._has_entity else "without") +
+                             " entity ids, step_from_store got " + ("none" if self._has_entity else "them"))
+        extra = (self._log_q_pairs(*log_q) if log_q is not None else []) + (self._entity_pairs(*entity) if entity is not None else [])
+        self._ingest_from_store(notice_store, company_store, pairs, order, offset, extra=extra or None)
         self._mark_slot()
         return self._replay()
 

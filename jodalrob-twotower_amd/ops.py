@@ -490,12 +490,57 @@ def _lq_pair(a, b, Ra, Rb, dev, names):
     return () if a is None else (_lq_vec(a, Ra, dev, names[0]), _lq_vec(b, Rb, dev, names[1]))
 
 
-def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True, lq_b=None):
-    """lq_b: the B rows' log sampling probabilities [Rb] (tt_score_dir_fwd_lq)."""
+# repeated-entity mask (the *_mask entries of include/twotower.h): the score wrappers take the rows' notice / company ids as
+# optional arguments `ent=(ent_n, ent_c)` and call the _mask entry when they are given
+def _ent_vec(e, B, dev, name):
+    """int32 [B] entity ids on `dev` (validated: no device sync)"""
+    if not isinstance(e, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(e).__name__}")
+    if e.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {e.dtype}")
+    if e.dim() != 1 or e.shape[0] != B:
+        raise ValueError(f"{name} must have shape [{B}], got {list(e.shape)}")
+    if e.device != dev:
+        raise ValueError(f"{name} is on {e.device}, the scores on {dev}")
+    return e
+
+
+def score_mask_ids(ent_n, ent_c, B, dev):
+    """(ent_n, ent_c) as the *_mask entries read them: ONE int32 [2, round_up(B, 64)] array (rows 16-byte aligned, the entries past
+    B zero and ignored); a side given as None counts as all-distinct (its row index)."""
+    Bp = (B + 63) // 64 * 64
+    if B == Bp and ent_n is not None and ent_c is not None:          # whole tiles: the arrays as they are (no copy, no launch)
+        en, ec = _ent_vec(ent_n, B, dev, "ent_n"), _ent_vec(ent_c, B, dev, "ent_c")
+        if en.is_contiguous() and ec.is_contiguous() and en.data_ptr() % 16 == 0 and ec.data_ptr() % 16 == 0:
+            return en, ec
+    out = torch.zeros((2, Bp), dtype=torch.int32, device=dev)
+    for k, (e, name) in enumerate(((ent_n, "ent_n"), (ent_c, "ent_c"))):
+        if e is None:
+            out[k, :B] = torch.arange(B, dtype=torch.int32, device=dev)
+        else:
+            out[k, :B] = _ent_vec(e, B, dev, name)
+    return out[0], out[1]
+
+
+def _mask_args(ent, lq, n_lq):
+    """the _mask entries' (ent_n, ent_c, lq...) arguments: NULL where the call has no logQ vectors"""
+    return (L.ptr(ent[0]), L.ptr(ent[1])) + (tuple(map(L.ptr, lq)) if lq else (None,) * n_lq)
+
+
+def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True, lq_b=None, ent=None):
+    """lq_b: the B rows' log sampling probabilities [Rb] (tt_score_dir_fwd_lq).
+    ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask (tt_score_dir_fwd_mask, square problems)."""
     dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
     lq = () if lq_b is None else (_lq_vec(lq_b, Rb, dev, "lq_b"),)
     f = torch.empty((3, Ra), dtype=torch.float32, device=dev)       # sumexp, diag, sumscore
     rank = torch.empty(Ra, dtype=torch.int32, device=dev)
+    if ent is not None:
+        name = "tt_score_dir_fwd_mask"
+        with _timed(name):
+            L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *_mask_args(ent, lq, 1),
+                                            L.ptr(f[0]), L.ptr(f[1]), L.ptr(rank), L.ptr(f[2]) if want_sumscore else None, L.stream(dev)),
+                    name)
+        return f[0], f[1], rank, f[2]
     name = "tt_score_dir_fwd_lq" if lq else "tt_score_dir_fwd"
     with _timed(name):
         L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *map(L.ptr, lq),
@@ -519,11 +564,18 @@ def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumsco
     return out, loss
 
 
-def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=None, lq_b=None):
-    """lq_a / lq_b (both or neither): the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq)."""
+def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=None, lq_b=None, ent=None):
+    """lq_a / lq_b (both or neither): the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq).
+    ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask (tt_score_dir_bwd_mask, square problems)."""
     dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
     lq = _lq_pair(lq_a, lq_b, Ra, Rb, dev, ("lq_a", "lq_b"))
     dA = torch.empty_like(A)
+    if ent is not None:
+        name = "tt_score_dir_bwd_mask"
+        with _timed(name):
+            L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *_mask_args(ent, lq, 2),
+                                            L.ptr(sumexp_a), L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA), L.stream(dev)), name)
+        return dA
     name = "tt_score_dir_bwd_lq" if lq else "tt_score_dir_bwd"
     with _timed(name):
         L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *map(L.ptr, lq),
@@ -607,13 +659,16 @@ def score_pack2_fp8(X0, X1, scale0: float = 1.0, scale1: float = 1.0):
 
 
 def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False,
-             lq_n=None, lq_c=None):
-    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq): returns (rowsum, colsum, diag, row_rank,
-    (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n / lq_c given,
-    tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None."""
+             lq_n=None, lq_c=None, ent=None):
+    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq, score_fwd_sym_mask): returns (rowsum, colsum, diag,
+    row_rank, (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n / lq_c given,
+    tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None.  ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask
+    (tt_score_fwd_sym_bf16_mask, bf16 operands only)."""
     dev = Np.device
     if lq_n is not None and fp8:
         raise ValueError("the logQ-corrected symmetric forward has no fp8 form")
+    if ent is not None and (fp8 or x3):
+        raise ValueError("the masked symmetric forward takes bf16 operands only")
     lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
     Bp = (B + 63) // 64 * 64                                           # the kernel fills the entries past B (read by tt_score_bwd_bf16)
     f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
@@ -628,8 +683,12 @@ def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool =
         ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
     name = ("tt_score_fwd_sym_fp8" if fp8 else ("tt_score_fwd_sym_bf16x3" if x3 else "tt_score_fwd_sym_bf16")) + ("_lq" if lq else "")
     w_out = (L.ptr(f[5]), L.ptr(f[6])) if lq else ()
+    if ent is not None:
+        name, pre, w_out = "tt_score_fwd_sym_bf16_mask", _mask_args(ent, lq, 2), w_out or (None, None)
+    else:
+        pre = tuple(map(L.ptr, lq))
     with _timed(name):
-        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), *map(L.ptr, lq),
+        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), *pre,
                                    L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]), *w_out, L.ptr(f[2]), L.ptr(rank), L.ptr(out8),
                                    L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
     w = (f[5][:B], f[6][:B]) if lq else None
@@ -650,8 +709,16 @@ def score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n: float = 1.
     return r[:5] + (r[7],) + r[5:7]
 
 
+def score_fwd_sym_mask(Np, Cp, B, D, inv_t, shift, ent, lq_n=None, lq_c=None, scale_n: float = 1.0, want_rank: bool = True):
+    """score_fwd_sym with the repeated-entity mask (tt_score_fwd_sym_bf16_mask): ent = score_mask_ids(ent_n, ent_c, B, dev); lq_n /
+    lq_c optional (both or neither).  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, out8, loss), w = (w_n, w_c)
+    with logQ, else None -- what score_bwd_bf16(..., w=, ent=) takes."""
+    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, False, lq_n, lq_c, ent)
+    return r[:5] + (r[7],) + r[5:7]
+
+
 def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n: float = 1.0, inv=None, fp8: bool = False,
-                   x3: bool = False, w=None):
+                   x3: bool = False, w=None, ent=None):
     """inv: (inv_row, inv_col) from score_fwd_bf16(..., with_inv=True) with the same scale_n (optional).
     fp8: the operands are tt_score_pack2_fp8 buffers (tt_score_bwd_fp8); x3: score_pack2_bf16x3 buffers (tt_score_bwd_bf16x3).
     w: (w_n, w_c) from score_fwd_sym_lq, with its rowsum / colsum / inv: the logQ-corrected backward
@@ -659,6 +726,8 @@ def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, sc
     dev = Np.device
     if w is not None and fp8:
         raise ValueError("the logQ-corrected backward has no fp8 form")
+    if ent is not None and (fp8 or x3):
+        raise ValueError("the masked backward takes bf16 operands only")
     dN = torch.empty((B, D), dtype=torch.float32, device=dev)
     dC = torch.empty((B, D), dtype=torch.float32, device=dev)
     arr = (L.ScoreBwdDir * 2)()
@@ -671,6 +740,8 @@ def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, sc
         lq[0][0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))              # direction (N, C): A = notices, B = companies
         lq[0][1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
     name = ("tt_score_bwd_fp8" if fp8 else ("tt_score_bwd_bf16x3" if x3 else "tt_score_bwd_bf16")) + ("_lq" if lq else "")
+    if ent is not None:                                            # (ent: score_mask_ids' padded arrays, with the masked forward's sums)
+        name, lq = "tt_score_bwd_bf16_mask", (L.ptr(ent[0]), L.ptr(ent[1]), lq[0] if lq else None)
     with _timed(name):
         L.check(getattr(L.load(), name)(L.ctx(dev), arr, *lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
     return dN, dC

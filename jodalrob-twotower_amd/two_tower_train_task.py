@@ -51,16 +51,26 @@ class _ScoreCEFn(torch.autograd.Function):
     score_dtype 'fp32': exact-f32 MFMA path (parity); 'bf16': bf16-operand MFMA fast path; 'bf16x3': split-bf16 operands
     (hi + lo, three bf16 MFMAs per product: near-f32 products on the bf16 pipe).
     lq_n / lq_c (f32 [B], both or neither): logQ sampling-bias correction (include/twotower.h *_lq entries) -- the loss and the
-    gradients of the corrected softmax, metrics on the raw scores."""
+    gradients of the corrected softmax, metrics on the raw scores.
+    ent_n / ent_c (int32 [B], either or both; a missing side counts as all-distinct): the repeated-entity mask (include/twotower.h
+    *_mask entries) -- pairs a != b whose rows share a notice or a company leave both softmax sums; score_dtype 'bf16' and 'fp32'
+    only; combines with lq_n / lq_c; metrics on the raw scores."""
 
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
-                lq_n=None, lq_c=None):
+                lq_n=None, lq_c=None, ent_n=None, ent_c=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
         lq = lq_n is not None
         fp8, x3 = score_dtype == "fp8", score_dtype == "bf16x3"
+        ent = None
+        if ent_n is not None or ent_c is not None:
+            if fp8 or x3:
+                raise ValueError(f"the repeated-entity mask has no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
+            if c.shape != n.shape:
+                raise ValueError("the repeated-entity mask needs as many notice rows as company rows")
+            ent = ops.score_mask_ids(ent_n, ent_c, B, n.device)
         if lq:
             if fp8:
                 raise ValueError("the logQ correction has no fp8 form")
@@ -90,13 +100,14 @@ class _ScoreCEFn(torch.autograd.Function):
                 scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
                 Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
         # the kernel form, once.  Symmetric: ONE sweep of the B x B tiles serves both softmax directions -- the steady state of
-        # training, and always for fp8 and the logQ correction (its row ranks and metrics are the raw scores').  Otherwise the
+        # training, and always for fp8, the logQ correction and the repeated-entity mask (their row ranks and metrics are the raw
+        # scores').  Otherwise the
         # first call's diagnostics (column / full ranks) on the two-direction kernel, or the f32 path's two directional sweeps.
         w = None
-        if Np is not None and (fp8 or lq or not (want_col_rank or full_rank)):
+        if Np is not None and (fp8 or lq or ent is not None or not (want_col_rank or full_rank)):
             rowsum, colsum, diag, row_rank, inv, out8, loss, w = ops._fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, fp8, x3,
-                                                                              lq_n, lq_c)
-            if lq and want_col_rank:
+                                                                              lq_n, lq_c, ent)
+            if (lq or ent is not None) and want_col_rank:
                 # the first call's column top-1 rate (a diagnostic only) from the uncorrected two-direction kernel
                 col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
                 out8 = out8.clone()
@@ -108,13 +119,13 @@ class _ScoreCEFn(torch.autograd.Function):
                 if not want_col_rank:
                     col_rank = row_rank                  # placeholder: column top-1 rate is only a first-call diagnostic
             else:
-                rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c)
-                colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n)
+                rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c, ent=ent)
+                colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n, ent=ent)
                 if lq:
                     w = (lq_n.contiguous(), lq_c.contiguous())
             out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c)
         ctx.packed = None if Np is None else (Np, Cp, scale_n, inv)
-        ctx.fp8, ctx.x3, ctx.lq = fp8, x3, w
+        ctx.fp8, ctx.x3, ctx.lq, ctx.ent = fp8, x3, w, ent
         ctx.save_for_backward(n, c, rowsum, colsum)
         ctx.inv_t, ctx.shift = inv_t, shift
         ctx.mark_non_differentiable(out8, row_rank)
@@ -126,19 +137,19 @@ class _ScoreCEFn(torch.autograd.Function):
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return (None,) * 11
+            return (None,) * 13
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
         if ctx.packed is not None:
             Np, Cp, scale_n, inv = ctx.packed
             dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, fp8=ctx.fp8,
-                                        x3=ctx.x3, w=ctx.lq)
+                                        x3=ctx.x3, w=ctx.lq, ent=ctx.ent)
         else:
             lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
-            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc)
-            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn)
-        return (dN, dC) + (None,) * 9
+            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent)
+            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent)
+        return (dN, dC) + (None,) * 11
 
 
 class _Result(dict):
@@ -213,8 +224,12 @@ class TwoTowerTrainTask(nn.Module):
         if nb != cb:                                                                         # :64-67
             raise ValueError(f"Notice와 Company 배치 크기가 다릅니다: {nb} vs {cb}")
         lq = self._batch_log_q(notice_input, company_input, nb)
+        ent = self._batch_entity(notice_input, company_input, nb)
         notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
-        if lq is None:
+        if ent is not None:
+            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
+                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent)
+        elif lq is None:
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
                                            not hasattr(self, "_pair_check_done"))
         else:
@@ -275,9 +290,41 @@ class TwoTowerTrainTask(nn.Module):
             out.append(t.contiguous())
         return out[0], out[1]
 
-    def _score_ce(self, n, c, inv_t, first_call, log_q=None):
+    def _batch_entity(self, notice_input, company_input, B):
+        """(ent_n, ent_c) int32 [B] (a missing side: None, all-distinct) from the batch's "entity" entries (the repeated-entity mask),
+        or None when neither side carries one.  Refuses what the masked loss does not cover -- never ignores an entity array."""
+        ent_n, ent_c = notice_input.get("entity"), company_input.get("entity")
+        if ent_n is None and ent_c is None:
+            return None
+        if self._dense_loss:
+            raise ValueError("the repeated-entity mask (a batch with 'entity') is not supported by the dense loss path "
+                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
+        if self.score_dtype in ("fp8", "bf16x3"):
+            raise ValueError(f"the repeated-entity mask (a batch with 'entity') is not supported for score_dtype={self.score_dtype!r}")
+        ref = notice_input["dense"]
+        for name, t in (("notice", ent_n), ("company", ent_c)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
+                raise ValueError(f"batch['{name}']['entity'] must be an int32 tensor of shape [{B}], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            if t.device != ref.device:
+                raise ValueError(f"batch['{name}']['entity'] is on {t.device}, the batch on {ref.device}")
+        return ent_n, ent_c
+
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None):
         """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it.
-        log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn)."""
+        log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn).  entity: (ent_n, ent_c) -- the repeated-entity mask."""
+        if entity is not None:
+            if self._dense_loss or self.score_dtype in ("fp8", "bf16x3"):
+                raise ValueError("the repeated-entity mask covers the fused cross-entropy with score_dtype fp32 / bf16 only")
+            if n.shape != c.shape:
+                raise ValueError("the repeated-entity mask needs as many notice rows as company rows")
+            lqs = log_q if log_q is not None else (None, None)
+            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
+            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
+                return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, None, None, None, lqs[0], lqs[1], entity[0], entity[1])
+            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], entity[0], entity[1])
         if log_q is not None:
             if self._dense_loss or self.score_dtype == "fp8":
                 raise ValueError("the logQ correction covers the fused cross-entropy with score_dtype fp32 / bf16 / bf16x3 only")

@@ -106,6 +106,9 @@ def main():
     ap.add_argument("--table-lr", type=float, default=None, help="learning rate of the tables under rowwise_adagrad (default: the towers' learning rate)")
     ap.add_argument("--pair-zipf", type=float, default=None,
                     help="synthetic pairs: each pair's company drawn from a Zipf(A) law over company rank (default: uniform)")
+    ap.add_argument("--mask-repeats", action="store_true",
+                    help="mask the in-batch negatives that repeat a row's notice or company (the repeated-entity mask): the train loader "
+                         "attaches each pair's notice / company index (evaluation stays unmasked); combines with --logq-correction")
     ap.add_argument("--logq-correction", action="store_true",
                     help="logQ sampling-bias correction of the in-batch softmax: log sampling probabilities estimated from the TRAIN pairs, "
                          "attached to the train loader only (evaluation stays uncorrected)")
@@ -141,6 +144,8 @@ def main():
     train_loader, test_loader = create_unified_bid_dataloaders(source, schema, batch_size=config["batch_size"],
                                                                test_split=config["test_split"], shuffle_seed=config["shuffle_seed"],
                                                                test_mode=True, pair_limit=config["pair_limit"], device=device)
+    if a.mask_repeats:
+        train_loader.set_mask_repeats(True)
     if a.logq_correction:                                # exact: batches are uniform draws from this fixed pair list
         from jodalrob_twotower_amd.sampling_bias import log_sampling_probs
         tp = train_loader.pairs
