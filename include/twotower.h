@@ -752,7 +752,7 @@ int tt_topk_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t 
  * Catalogue-wide retrieval: the k best catalogue rows of every query, and optionally the rank of a given positive, in one
  * sweep over the catalogue that never writes a score to memory (what a user of the trained towers searches with; the
  * in-batch tt_score_matrix + tt_topk_rows pair only ranks the companies of one batch).
- *   queries Q [nQ, D], catalogue C [nC, D]; 1 <= D <= 256, 1 <= nC < 2^31, 0 <= k <= min(64, nC).
+ *   queries Q [nQ, D], catalogue C [nC, D]; 1 <= D <= 256, 1 <= nC < 2^31, 0 <= k <= min(512, nC).
  *   tt_retrieve_topk_bf16: Q_packed / C_packed are tt_score_pack_bf16 images (reused as they are); the score is
  *     s(q, c) = <bf16 image row q, bf16 image row c> in f32 on v_mfma_f32_32x32x16_bf16, i.e. <Q_q, C_c> times the product of
  *     the scales the two images were packed with (pack the catalogue with inv_t and the queries with 1 for s = cos / T on
@@ -764,7 +764,10 @@ int tt_topk_rows(tt_ctx* ctx, const float* S, int64_t R, int64_t Ccols, int64_t 
  *   [nQ] = #{c : s(q,c) > s(q,p)} + #{c < p : s(q,c) == s(q,p)} (tt_diag_rank_rows's rule), -1 where p is outside [0, nC).
  *   The positive's score comes from the same instruction sequence as every other score, and the counts from the same sweep
  *   as the top-k.  k = 0 asks for ranks only (positives required).
- * Workspace: tt_retrieve_workspace_bytes(nQ, nC, D, k) bytes (0 for an invalid shape), 16-byte aligned, caller memory.
+ * Workspace: tt_retrieve_workspace_bytes(nQ, nC, D, k) bytes (0 for an invalid shape), 16-byte aligned, caller memory.  For k > 64
+ *   the catalogue splits are capped so that splits x k <= 2048: the size never exceeds that of the same call with k = 64.
+ * k > 64 (up to 512) runs the sweep's large-k form: same scores, order, filler and rank, one wave per workgroup with up to the
+ *   CU's whole 160 KB of LDS.  A call with k <= 64 is unaffected.
  * Scores are assumed finite (a NaN score is never selected; -inf entries fill a list only when nothing better exists, idx -1).
  * Three launches on `stream` (positive scores, sweep, per-query merge), no host synchronisation and no allocation: a search
  * can be captured into a graph (one stream, no parallel branches).  Results are bitwise identical from run to run and for

@@ -26,6 +26,10 @@
 // q an `any` and an `all` mask of W words; rows that fail (tags & any) != 0 (unless any == 0) or (tags & all) == all get -inf at
 // the same point as the excluded ones.  A tile's 32 W tag words are contiguous: the wave reads them with one coalesced load
 // (W > 2: two, 16 rows each) a tile ahead, one word per lane, and every lane fetches the words of its 16 rows with ds_bpermute.
+//
+// k up to 512 (the sweep's and the merge's BIGK = true instantiations, k > 64): the same sweep with one wave per workgroup and
+// a region of ret_big_slots(k) slots per query, up to the CU's whole 160 KB of LDS at k > 256; the splits are capped so that
+// S k <= 2048, which keeps the merge's selection and the workspace of the k = 64 call.  k <= 64 runs the code it always ran.
 #include "tt_score_bf16.h"
 
 #include <math.h>
@@ -34,9 +38,21 @@ namespace {
 
 using namespace ttscore;
 
-constexpr int kRetWaves = 2;        // waves per sweep workgroup (each its own 32 queries; kept at <= 64 KB of LDS for k = 64)
+constexpr int kRetWaves = 2;        // waves per sweep workgroup, k <= 64 (each its own 32 queries; <= 64 KB of LDS at k = 64)
 constexpr int kRetCap = 64;         // candidate slots per query beyond the k kept ones (>= 32: room for one whole tile)
 constexpr int kRetMaxSplits = 32;
+constexpr int kRetSmallK = 64;      // k above this runs the large-k sweep (BIGK: one wave per workgroup) and the strided merge
+constexpr int kRetMaxK = 512;
+constexpr size_t kRetBigLds = 640 * 32 * 8;                    // a CU's whole LDS (160 KB): 640 slots of 32 queries x (key, index)
+
+// Slots of a query's region in the large-k sweep (one wave per workgroup).  The CU's 640 slots go evenly to as many waves, at
+// most four, as leave every region k + kRetCap slots or more: 4 waves for k <= 96, 3 for k <= 146, 2 for k <= 256, else 1.  What
+// a region holds beyond k is spare room, so a select() comes every slots - k - 32 candidates or more, not every 32.  (210, not
+// 213: every size is a whole number of 1280-byte LDS allocation granules.)
+__host__ __device__ constexpr int ret_big_slots(int k) { return k <= 96 ? 160 : k <= 146 ? 210 : k <= 256 ? 320 : 640; }
+static_assert(ret_big_slots(kRetSmallK + 1) >= kRetSmallK + 1 + kRetCap && ret_big_slots(96) >= 96 + kRetCap &&
+              ret_big_slots(146) >= 146 + kRetCap && ret_big_slots(256) >= 256 + kRetCap && ret_big_slots(kRetMaxK) >= kRetMaxK + kRetCap &&
+              (size_t)ret_big_slots(kRetMaxK) * 256 <= kRetBigLds, "a region holds k + kRetCap slots and fits the CU");
 constexpr int32_t kSentIdx = 0x7fffffff;   // index of an empty list entry (order key 0: below every score)
 
 // order-preserving key of a score: larger float <=> larger key; -0 and +0 share one key
@@ -189,16 +205,19 @@ __device__ __forceinline__ void filter_tile(f32x16& acc, int h, uint32_t tg0, ui
 }
 
 // ---- sweep ------------------------------------------------------------------------------------------------------------------
-template <class Tile, bool EXCL, bool FILT>
-__global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
+// BIGK (64 < k <= 512): one wave per workgroup and ret_big_slots(k) slots per query, up to the CU's whole 160 KB; select() skips
+// the key bits its bounds share.  Everything else -- tiles, EXCL / FILT steps, the filter, the rank counts -- is the k <= 64 form's.
+template <class Tile, bool EXCL, bool FILT, bool BIGK>
+__global__ __launch_bounds__((BIGK ? 1 : kRetWaves) * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
+  constexpr int NW = BIGK ? 1 : kRetWaves;
   extern __shared__ uint32_t ret_lds[];
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-  const int wave = threadIdx.x >> 6;
-  const int64_t qt = (int64_t)blockIdx.x * kRetWaves + wave, q0 = 32 * qt;
+  const int wave = BIGK ? 0 : threadIdx.x >> 6;
+  const int64_t qt = (int64_t)blockIdx.x * NW + wave, q0 = 32 * qt;
   if (q0 >= a.nQ) return;                                       // (no workgroup barriers below: the waves are independent)
   const int s = blockIdx.y, S = a.S, k = a.k;
   const int64_t nT = (a.nC + 31) / 32, tb = nT * s / S, te = nT * (s + 1) / S;
-  const int slots = k + kRetCap;
+  const int slots = BIGK ? ret_big_slots(k) : k + kRetCap;
   uint32_t* keys = ret_lds + (size_t)wave * slots * 64;         // [slot][query c]
   int32_t* ids = reinterpret_cast<int32_t*>(keys + slots * 32);
   const int64_t q = q0 + c;
@@ -260,6 +279,7 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
   int rcnt = 0;
   float thr = -INFINITY;                                        // the query's k-th best so far (both lanes of a query agree)
   int cnt = 0;                                                  // filled slots of the query's region
+  float top = -INFINITY;                                        // BIGK: no score this lane put into the region exceeds it
 
   // the k best of slots [0, cnt) of every query whose region holds more than k; region [0, k) afterwards
   auto select = [&]() {
@@ -267,10 +287,33 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
     const bool act = cnt > k;
     const int n = act ? cnt : 0;
     uint32_t K = 0;                                             // k-th largest key
-    for (int b = 31; b >= 0; --b) {
+    int btop = 31;
+    if constexpr (BIGK) {
+      // Every key of the region lies in [okey(thr), okey(top)], so the k-th largest shares the leading bits the two bounds
+      // share: the search starts below them (the wave at its queries' highest differing bit; a bit above a query's own is
+      // set already or fails its test, so K is what the full search finds).  Typically 9 or more of the 32 passes go.
+      const uint32_t lo = okey(thr), hi = okey(fmaxf(top, __shfl_xor(top, 32)));
+      const uint32_t d = hi >= lo ? lo ^ hi : 0xffffffffu;       // (hi < lo cannot be: the full search then)
+      btop = !act ? -1 : d ? 31 - __clz(d) : -1;                 // the query's highest differing bit
+      K = btop >= 0 ? hi & ~((2u << btop) - 1u) : hi;            // (2u << 31 wraps to 0: no bits kept)
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        const int x = __shfl_xor(btop, o);
+        btop = x > btop ? x : btop;
+      }
+    }
+    for (int b = btop; b >= 0; --b) {
       const uint32_t tr = K | (1u << b);
-      int ge = 0;
-      for (int i = h; i < n; i += 2) ge += keys[i * 32 + c] >= tr ? 1 : 0;
+      int ge = 0, i = h;
+      if constexpr (BIGK)                                       // eight reads in flight: at most four waves share the CU's LDS
+        for (; i + 14 < n; i += 16) {
+          uint32_t x[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = keys[(i + 2 * j) * 32 + c];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ge += x[j] >= tr ? 1 : 0;
+        }
+      for (; i < n; i += 2) ge += keys[i * 32 + c] >= tr ? 1 : 0;
       ge += __shfl_xor(ge, 32);
       if (ge >= k) K = tr;
     }
@@ -391,7 +434,8 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
             ++w;
           }
         cnt += mine + other;
-        if (__any(cnt > k + kRetCap - 32)) select();
+        if constexpr (BIGK) top = fmaxf(top, m);
+        if (__any(cnt > slots - 32)) select();
       }
     }
   }
@@ -413,8 +457,10 @@ __global__ __launch_bounds__(kRetWaves * 64) void retrieve_sweep_kernel(Tile til
 }
 
 // ---- merge: one wave per query ------------------------------------------------------------------------------------------------
-template <int PER>
+// (BIGK: k up to 512 -- the staging arrays hold kRetMaxK entries and a lane places every 64th of them)
+template <int PER, bool BIGK>
 __global__ __launch_bounds__(64) void retrieve_merge_kernel(RetArgs a) {
+  constexpr int KM = BIGK ? kRetMaxK : kRetSmallK;
   const int lane = threadIdx.x;
   const int64_t q = blockIdx.x;
   const int S = a.S, k = a.k;
@@ -466,42 +512,59 @@ __global__ __launch_bounds__(64) void retrieve_merge_kernel(RetArgs a) {
     }
     I = J;
   }
-  __shared__ uint32_t sk[64];
-  __shared__ int32_t si[64];
+  __shared__ uint32_t sk[KM];
+  __shared__ int32_t si[KM];
   int base = 0;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const bool sel = kk[j] > K || (kk[j] == K && ii[j] <= I);
     const uint64_t m = __ballot(sel);
     const int at = base + __popcll(m & ((1ull << lane) - 1));
-    if (sel && at < 64) {                                       // (exactly k <= 64 are selected)
+    if (sel && at < KM) {                                       // (exactly k <= KM are selected)
       sk[at] = kk[j];
       si[at] = ii[j];
     }
     base += __popcll(m);
   }
   __syncthreads();
-  if (lane < k) {
-    const uint32_t mk = sk[lane];
-    const int32_t mi = si[lane];
-    int pos = 0;
-    for (int j = 0; j < k; ++j) pos += (sk[j] > mk || (sk[j] == mk && si[j] < mi)) ? 1 : 0;
-    const bool empty = mk == 0u;
-    a.vals[q * k + pos] = empty ? -INFINITY : okey_val(mk);
-    a.idx[q * k + pos] = empty ? -1 : (int64_t)mi;
+  if constexpr (!BIGK) {
+    if (lane < k) {
+      const uint32_t mk = sk[lane];
+      const int32_t mi = si[lane];
+      int pos = 0;
+      for (int j = 0; j < k; ++j) pos += (sk[j] > mk || (sk[j] == mk && si[j] < mi)) ? 1 : 0;
+      const bool empty = mk == 0u;
+      a.vals[q * k + pos] = empty ? -INFINITY : okey_val(mk);
+      a.idx[q * k + pos] = empty ? -1 : (int64_t)mi;
+    }
+  } else {
+    for (int i = lane; i < k; i += 64) {
+      const uint32_t mk = sk[i];
+      const int32_t mi = si[i];
+      int pos = 0;
+      for (int j = 0; j < k; ++j) pos += (sk[j] > mk || (sk[j] == mk && si[j] < mi)) ? 1 : 0;
+      const bool empty = mk == 0u;
+      a.vals[q * k + pos] = empty ? -INFINITY : okey_val(mk);
+      a.idx[q * k + pos] = empty ? -1 : (int64_t)mi;
+    }
   }
 }
 
-int ret_max_splits(int64_t nC) {
+// Most splits of a call.  k > 64: as many as keep S k within what the same catalogue's k = 64 call has (at most 32 x 64 = 2048
+// entries), so that the merge's selection over 2048 entries holds and the workspace never exceeds the k = 64 one.
+int ret_max_splits(int64_t nC, int k) {
   const int64_t nT = (nC + 31) / 32;
-  return (int)(nT < kRetMaxSplits ? nT : kRetMaxSplits);
+  const int64_t S = nT < kRetMaxSplits ? nT : kRetMaxSplits;
+  if (k <= kRetSmallK) return (int)S;
+  const int64_t cap = S * kRetSmallK / k;                       // S = 32: 2048 / k.  (k <= nC <= 32 nT, so never below 2)
+  return (int)(cap > 1 ? cap : 1);
 }
 
 struct RetLayout {
   size_t sp, rank, key, idx, total;
 };
 RetLayout ret_layout(int64_t nQ, int64_t nC, int k) {
-  const int64_t S = ret_max_splits(nC);
+  const int64_t S = ret_max_splits(nC, k);
   RetLayout L;
   L.sp = 0;
   L.rank = L.sp + (size_t)rup(nQ * 4, 256);
@@ -512,7 +575,7 @@ RetLayout ret_layout(int64_t nQ, int64_t nC, int k) {
 }
 
 bool ret_shape_ok(int64_t nQ, int64_t nC, int D, int k) {
-  return nQ >= 1 && nC >= 1 && nC < (int64_t(1) << 31) && D >= 1 && D <= 256 && k >= 0 && k <= 64 && k <= nC;
+  return nQ >= 1 && nC >= 1 && nC < (int64_t(1) << 31) && D >= 1 && D <= 256 && k >= 0 && k <= kRetMaxK && k <= nC;
 }
 
 struct RetFilt {              // attribute filter of a call (tags == NULL: none)
@@ -528,7 +591,7 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
                int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank, const int64_t* excl_off,
                const int32_t* excl_rows, const RetFilt& flt, void* workspace, hipStream_t st) {
   const int64_t nT = tt_cdiv(nC, 32), nQt = tt_cdiv(nQ, 32);
-  const int cap = ret_max_splits(nC);
+  const int cap = ret_max_splits(nC, k);
   int64_t S;
   if (ctx->retrieve_splits > 0) {
     S = ctx->retrieve_splits;
@@ -565,21 +628,45 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
     retrieve_pos_kernel<Tile><<<(unsigned)nQt, 64, 0, st>>>(tile, a);
     TT_LAUNCH_CHECK();
   }
+  const int64_t n = S * k;
+  if (k > kRetSmallK) {                                         // large-k form: one wave per workgroup, up to the CU's whole LDS
+    const size_t lds = (size_t)ret_big_slots(k) * 32 * 8;
+    const dim3 grid((unsigned)nQt, (unsigned)S);
+#define TT_RET_BIG(E, F)                                                                 \
+  do {                                                                                   \
+    TT_LDS_ONCE(kRetBigLds, &retrieve_sweep_kernel<Tile, E, F, true>);                   \
+    retrieve_sweep_kernel<Tile, E, F, true><<<grid, 64, lds, st>>>(tile, a);             \
+  } while (0)
+    if (flt.tags) {
+      if (excl_off) TT_RET_BIG(true, true);
+      else TT_RET_BIG(false, true);
+    } else if (excl_off) {
+      TT_RET_BIG(true, false);
+    } else {
+      TT_RET_BIG(false, false);
+    }
+#undef TT_RET_BIG
+    TT_LAUNCH_CHECK();
+    if (n <= 128) retrieve_merge_kernel<2, true><<<(unsigned)nQ, 64, 0, st>>>(a);
+    else if (n <= 512) retrieve_merge_kernel<8, true><<<(unsigned)nQ, 64, 0, st>>>(a);
+    else retrieve_merge_kernel<kRetMaxSplits, true><<<(unsigned)nQ, 64, 0, st>>>(a);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+  }
   const size_t lds = (size_t)kRetWaves * (k + kRetCap) * 32 * 8;
   const dim3 grid((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S);
   if (flt.tags) {
-    if (excl_off) retrieve_sweep_kernel<Tile, true, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
-    else retrieve_sweep_kernel<Tile, false, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    if (excl_off) retrieve_sweep_kernel<Tile, true, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    else retrieve_sweep_kernel<Tile, false, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
   } else if (excl_off) {
-    retrieve_sweep_kernel<Tile, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    retrieve_sweep_kernel<Tile, true, false, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
   } else {
-    retrieve_sweep_kernel<Tile, false, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    retrieve_sweep_kernel<Tile, false, false, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
   }
   TT_LAUNCH_CHECK();
-  const int64_t n = S * k;
-  if (n <= 128) retrieve_merge_kernel<2><<<(unsigned)nQ, 64, 0, st>>>(a);
-  else if (n <= 512) retrieve_merge_kernel<8><<<(unsigned)nQ, 64, 0, st>>>(a);
-  else retrieve_merge_kernel<kRetMaxSplits><<<(unsigned)nQ, 64, 0, st>>>(a);
+  if (n <= 128) retrieve_merge_kernel<2, false><<<(unsigned)nQ, 64, 0, st>>>(a);
+  else if (n <= 512) retrieve_merge_kernel<8, false><<<(unsigned)nQ, 64, 0, st>>>(a);
+  else retrieve_merge_kernel<kRetMaxSplits, false><<<(unsigned)nQ, 64, 0, st>>>(a);
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -587,7 +674,7 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
 #define TT_RET_CHECK_COMMON(NAME)                                                                                                 \
   TT_CHECK_ARG(ctx != nullptr, NAME ": NULL context");                                                                           \
   TT_CHECK_ARG(ret_shape_ok(nQ, nC, D, k), NAME ": bad shape nQ=%lld nC=%lld D=%d k=%d (need nQ >= 1, 1 <= nC < 2^31, "         \
-               "1 <= D <= 256, 0 <= k <= min(64, nC))", (long long)nQ, (long long)nC, D, k);                                     \
+               "1 <= D <= 256, 0 <= k <= min(512, nC))", (long long)nQ, (long long)nC, D, k);                                    \
   TT_CHECK_ARG(k > 0 || positives != nullptr, NAME ": k = 0 asks for nothing (pass positives and rank, or k >= 1)");             \
   TT_CHECK_ARG(k == 0 || (vals != nullptr && idx != nullptr), NAME ": k = %d needs vals and idx", k);                           \
   TT_CHECK_ARG((positives == nullptr) == (rank == nullptr), NAME ": positives and rank go together (both or neither)");          \

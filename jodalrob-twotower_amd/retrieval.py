@@ -9,6 +9,9 @@ matrix to memory.
     vals, idx = index.search(notice_embeddings, k=10)             # s = <q, c> / T, value descending, ties -> lower index
     ranks = index.rank(notice_embeddings, positives)              # #{c : s > s_p} + #{c < p : s == s_p}
 
+k goes up to MAX_K = 512 (candidates for a re-ranker, hard negatives past the near-duplicates): the same exact order, filler rule
+and bitwise reproducibility at every k; k > 64 runs the sweep's large-k form (one wave per workgroup).
+
 Every search also takes exclude=(offsets, rows), per-query exclusion lists in CSR form: query i's rows
 rows[offsets[i]:offsets[i+1]] are left out of its top-k and its rank, inside the same sweep
 (tt_excl_retrieve_topk_bf16 / _f32).  exclusions_from_pairs builds them from known (query key, row) pairs -- the filtered
@@ -31,7 +34,7 @@ import torch
 from . import ops
 from .config import settings
 
-MAX_K = 64
+MAX_K = 512
 
 
 def exclusions_from_pairs(query_keys, pairs, nC: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -286,7 +289,7 @@ class CatalogIndex:
 
     def search(self, Q: torch.Tensor, k: int = 10, exclude=None, allow=None, require=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(vals f32 [nQ, k], idx int64 [nQ, k]): every query's k best catalogue rows, value descending, ties to the lower
-        index.  1 <= k <= min(64, catalogue size).  exclude=(offsets int64 [nQ + 1], rows): query i's rows
+        index.  1 <= k <= min(512, catalogue size).  exclude=(offsets int64 [nQ + 1], rows): query i's rows
         rows[offsets[i]:offsets[i+1]] are left out; if fewer than k rows remain, the last slots are -inf / -1.
         allow / require (an index with tags only): integer masks [nQ] or [nQ, W]; only rows that share a bit with a non-zero
         allow[i] and hold every bit of require[i] are eligible for query i.  They combine with exclude."""
@@ -298,7 +301,8 @@ class CatalogIndex:
 
     def search_with_rank(self, Q: torch.Tensor, k: int, positives, exclude=None, allow=None,
                          require=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """search() and rank() from one sweep over the catalogue (the same exclusion lists and masks for both)."""
+        """search() and rank() from one sweep over the catalogue (the same exclusion lists and masks for both);
+        1 <= k <= min(512, catalogue size)."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
         pos = self._check_positives(positives, Q.shape[0])

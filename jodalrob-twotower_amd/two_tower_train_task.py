@@ -379,7 +379,8 @@ class TwoTowerTrainTask(nn.Module):
                         require=None) -> Dict[str, torch.Tensor]:
         """Top-k companies of the whole catalogue `index` (a retrieval.CatalogIndex) for every notice of `notice_batch` (the
         notice side's {"dense", "kjt"}, or a full batch with a "notice" entry): {"top_similarities" f32 [B, top_k],
-        "top_indices" int64 [B, top_k]} -- index rows, value descending, ties to the lower index.  The notice tower runs in
+        "top_indices" int64 [B, top_k]} -- index rows, value descending, ties to the lower index; 1 <= top_k <= min(512, catalogue
+        size) (retrieval.MAX_K).  The notice tower runs in
         eval mode; the task's train()/eval() state is restored afterwards.  (predict_batch ranks within one batch.)
         exclude=(offsets, rows): per-notice exclusion lists (CatalogIndex.search), e.g. companies that already bid on it
         (retrieval.exclusions_from_pairs).  allow / require: per-notice attribute masks for an index built with tags=

@@ -48,7 +48,7 @@ def main():
     ap.add_argument("--final-dim", type=int, default=64)
     ap.add_argument("--score-dtype", default=None, help="fp32 | bf16 (default: the package setting, TT_SCORE_DTYPE)")
     ap.add_argument("--train-steps", type=int, default=200, help="without --checkpoint: train this many steps first")
-    ap.add_argument("--top-k", type=int, default=10)
+    ap.add_argument("--top-k", type=int, default=10, help="1 .. min(512, --entities): rows printed per example notice")
     ap.add_argument("--examples", type=int, default=3)
     ap.add_argument("--filtered", action="store_true",
                     help="also rank without each notice's other known companies (train + test pairs)")

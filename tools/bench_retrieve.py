@@ -8,7 +8,8 @@ torch.mm + torch.topk on the same inputs.
 One JSON line per case: kernel ms per search and scores/s, the MFMA fraction of 2.5 PF dense bf16 (2 nQ nC D flops), the
 catalogue read rate (bytes of the catalogue operand per search) against 8 TB/s, and the baseline's ms and how many rows'
 index sets agree with the kernel's.  The baseline keeps at most 1 GiB of f32 scores alive per chunk (bf16: torch.mm of the two
-bf16 images, bf16 scores; fp32: f32 scores), takes the chunk's top-k and merges it into the running top-k.
+bf16 images, bf16 scores; fp32: f32 scores), takes the chunk's top-k and merges it into the running top-k.  --k takes every k the
+index does (1 .. 512; k > 64 runs the sweep's large-k form), and the baseline runs for each of them.
 
 --exclude L [L ...] (no baseline then): per case and L, every query gets L random distinct catalogue rows as its exclusion
 list, and the exclusion search (tt_excl_retrieve_topk_*) is timed against the plain search in the same process, the two
@@ -166,7 +167,7 @@ def main():
     ap.add_argument("--nq", type=int, default=8192)
     ap.add_argument("--nc", type=int, nargs="+", default=[65536, 1 << 20])
     ap.add_argument("--d", type=int, nargs="+", default=[64, 256])
-    ap.add_argument("--k", type=int, nargs="+", default=[10, 64])
+    ap.add_argument("--k", type=int, nargs="+", default=[10, 64], help="1 .. 512 each (retrieval.MAX_K)")
     ap.add_argument("--dtypes", nargs="+", default=["bf16", "fp32"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-baseline", action="store_true")
