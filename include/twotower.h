@@ -717,6 +717,39 @@ int tt_score_dir_bwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t 
                           float shift, int64_t diag_offset, const int32_t* ent_n, const int32_t* ent_c, const float* lq_a,
                           const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale,
                           float* dA, tt_stream stream);
+/* ---- per-pair sample weights of the in-batch softmax (TFRS: sample_weight) ------------------------------------------------
+ * Pair a (row a of both sides) carries a raw weight w[a].  w' = w with every entry that is not a positive finite number set
+ * to 0; g_a = w'_a * B / sum(w'), all 0 when the sum is 0.  With l_a the pair's two softmax terms (row direction and column
+ * direction, corrected and masked as the entries above define them):
+ *   loss = (1 / B) sum_a g_a l_a                       (= sum w' l / sum w': the weighted mean)
+ *   d loss / d s_ab = (1 / 2B) [ g_a softmax_row_ab + g_b softmax_col_ab - 2 g_a [a == b] ]
+ * A zero-weight pair has no positive term and no softmax of its own; its rows still stand in the other pairs' sums.  rowsum /
+ * colsum are the UNWEIGHTED sums, metrics (out8[1:], diag, ranks) stay on the raw scores, bitwise the plain entry's.  All-ones
+ * weights give the plain loss.  Square problems, bf16 operands and the f32 parity path only; the logQ vectors and the entity ids
+ * are OPTIONAL in every _pw entry (NULL = without; each pair both or neither).
+ * tt_score_prepare_pw: g_out [round_up(B, 64)] (16-byte aligned; 0 past B) from w [B], one launch, fixed summation order.
+ * tt_score_fwd_sym_bf16_pw: the masked symmetric forward's arguments plus g.  The loss term of row i is multiplied by g[i] and
+ * inv_row[i] / inv_col[i] come out FOLDED, g[i] / rowsum_i and g[i] / colsum_i.
+ * tt_score_bwd_bf16_pw: inv_a / inv_b of every direction must be that forward's folded arrays (NULL: argument error); the
+ * diagonal's -2 becomes -2 g_a.  Always the b-split kernel form; never hosted by the towers' backward launch (a queued score
+ * backward is launched in front of it).
+ * tt_score_loss_finish_pw / tt_score_dir_bwd_pw: the f32 parity path (the directional forwards serve unchanged). */
+int tt_score_prepare_pw(tt_ctx* ctx, const float* w, int64_t B, float* g_out, tt_stream stream);
+int tt_score_fwd_sym_bf16_pw(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
+                             float shift, float ab_scale, int32_t want_rank, const float* g, const int32_t* ent_n,
+                             const int32_t* ent_c, const float* lq_n, const float* lq_c, float* rowsum, float* colsum,
+                             float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank,
+                             float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream);
+int tt_score_bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g, const int32_t* ent_n,
+                         const int32_t* ent_c, const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift,
+                         const float* d_loss, float scale, tt_stream stream);
+int tt_score_loss_finish_pw(tt_ctx* ctx, int64_t B, float shift, const float* g, const float* lq_n, const float* lq_c,
+                            const float* rowsum, const float* colsum, const float* diag, const int32_t* row_rank,
+                            const int32_t* col_rank, const float* sumscore, float* out8, float* loss_out, tt_stream stream);
+int tt_score_dir_bwd_pw(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t,
+                        float shift, int64_t diag_offset, const float* g, const int32_t* ent_n, const int32_t* ent_c,
+                        const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b,
+                        const float* d_loss, float scale, float* dA, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

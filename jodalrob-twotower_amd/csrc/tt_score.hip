@@ -178,14 +178,17 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
 // backward of one direction; NCH = ceil(D / 64) feature chunks kept as MFMA accumulators.
 // LQ (tt_score_dir_bwd_lq): the weight of (a, b) is exp(s - shift) (w_b / sumexp_a + w_a / sumexp_b), w the sampling weights
 // MK (tt_score_dir_bwd_mask; square, diag_off == 0): a masked pair (score_dir_fwd_kernel) weighs nothing
-template <int NCH, bool VEC, bool LQ = false, bool MK = false>
+// PW (tt_score_dir_bwd_pw; square, diag_off == 0): per-pair sample weights g -- the reciprocals are g_a / sumexp_a and g_b / sumexp_b,
+// the diagonal's -2 is -2 g_a
+template <int NCH, bool VEC, bool LQ = false, bool MK = false, bool PW = false>
 __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 const float* __restrict__ sumexp_a, const float* __restrict__ sumexp_b,
                                                                 const float* __restrict__ d_loss, float scale, float* __restrict__ dA,
                                                                 const float* __restrict__ lq_a = nullptr, const float* __restrict__ lq_b = nullptr,
                                                                 const int32_t* __restrict__ ent_n = nullptr,
-                                                                const int32_t* __restrict__ ent_c = nullptr) {
+                                                                const int32_t* __restrict__ ent_c = nullptr,
+                                                                const float* __restrict__ pw_g = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float Ws[RB * LDW];
@@ -195,10 +198,12 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
   if (NCH == 1) stage<RB, VEC>(A, Ra, D, r0, 0, As, t);
   float ia[16], ua[16];
   [[maybe_unused]] int ean[16], eac[16];
+  [[maybe_unused]] float ga[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t a = r0 + wr * 32 + rowmap(r, lh);
     ia[r] = a < Ra ? 1.f / sumexp_a[a] : 0.f;
+    if constexpr (PW) { ga[r] = a < Ra ? pw_g[a] : 0.f; ia[r] *= ga[r]; }
     if constexpr (LQ) ua[r] = a < Ra ? tt_lq_weight(lq_a[a]) : 0.f;
     if constexpr (MK) { ean[r] = a < Ra ? ent_n[a] : 0; eac[r] = a < Ra ? ent_c[a] : 0; }
   }
@@ -225,7 +230,8 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
       const int cl = wc * 64 + h * 32 + li;
       const int64_t col = c0 + cl;
       const bool cv = col < Rb;
-      const float ib = cv ? 1.f / sumexp_b[col] : 0.f;
+      float ib = cv ? 1.f / sumexp_b[col] : 0.f;
+      if constexpr (PW) ib *= cv ? pw_g[col] : 0.f;
       const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 0.f;
       [[maybe_unused]] int ebn = 0, ebc = 0;
       if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
@@ -237,7 +243,10 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
         if (cv) {
           if constexpr (LQ) w = __expf(s - shift) * (wb * ia[r] + ua[r] * ib);
           else w = __expf(s - shift) * (ia[r] + ib);
-          if constexpr (MK) {
+          if constexpr (PW) {
+            if (col == r0 + row + diag_off) w = __builtin_fmaf(-2.f, ga[r], w);
+            else if constexpr (MK) { if ((ean[r] == ebn) | (eac[r] == ebc)) w = 0.f; }
+          } else if constexpr (MK) {
             // (the diagonal as the plain instantiations compile it: e (ia + ib) - 2 in one fma -- an inert mask gives their bits)
             if (col == r0 + row + diag_off) {
               if constexpr (!LQ) w = __builtin_fmaf(ia[r] + ib, __expf(s - shift), -2.f);
@@ -379,6 +388,61 @@ __global__ __launch_bounds__(1024) void loss_finish_lq_kernel(int64_t B, float s
     out[4] = pos - neg;
     out[5] = chit / fb;
     out[6] = tot;
+    out[7] = 0.f;
+    if (loss_out) loss_out[0] = out[0];
+  }
+}
+
+// tt_score_loss_finish_pw: each pair's two terms times its weight g_i (tt_score_prepare_pw); LQ as loss_finish_lq_kernel.  The
+// metrics are the unweighted ones.  (g_i = 1: the product is exact -- the bits of the kernels above.)
+template <bool LQ>
+__global__ __launch_bounds__(1024) void loss_finish_pw_kernel(int64_t B, float shift, const float* __restrict__ rowsum,
+                                                              const float* __restrict__ colsum, const float* __restrict__ diag,
+                                                              const int32_t* __restrict__ row_rank, const int32_t* __restrict__ col_rank,
+                                                              const float* __restrict__ sumscore, float* __restrict__ out,
+                                                              float* __restrict__ loss_out, const float* __restrict__ lq_n,
+                                                              const float* __restrict__ lq_c, const float* __restrict__ pw_g) {
+  __shared__ float sh5[5][16];
+  float l = 0.f, hit = 0.f, chit = 0.f, dsum = 0.f, tot = 0.f;
+#pragma unroll 4
+  for (int64_t i = threadIdx.x; i < B; i += blockDim.x) {
+    const float d = diag[i];
+    float li;
+    if constexpr (LQ) li = (logf(rowsum[i]) + shift - d - tt_lq_log_weight(lq_c[i])) + (logf(colsum[i]) + shift - d - tt_lq_log_weight(lq_n[i]));
+    else li = (logf(rowsum[i]) + shift - d) + (logf(colsum[i]) + shift - d);
+    l += pw_g[i] * li;
+    hit += row_rank[i] == 0 ? 1.f : 0.f;
+    chit += col_rank[i] == 0 ? 1.f : 0.f;
+    dsum += d;
+    tot += sumscore ? sumscore[i] : 0.f;
+  }
+  float v[5] = {l, hit, chit, dsum, tot};
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) v[j] += __shfl_xor(v[j], o);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) sh5[j][threadIdx.x >> 6] = v[j];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      float t = 0.f;
+      for (int w = 0; w < nw; ++w) t += sh5[j][w];
+      v[j] = t;
+    }
+    const float fb = (float)B;
+    const float pos = v[3] / fb;
+    const float neg = (v[4] - v[3]) / (fb * fb - fb);
+    out[0] = 0.5f * v[0] / fb;
+    out[1] = v[1] / fb;
+    out[2] = pos;
+    out[3] = neg;
+    out[4] = pos - neg;
+    out[5] = v[2] / fb;
+    out[6] = v[4];
     out[7] = 0.f;
     if (loss_out) loss_out[0] = out[0];
   }
@@ -614,10 +678,18 @@ static int loss_finish(int64_t B, float shift, const float* lq_n, const float* l
 // tt_score_dir_bwd and, with lq_a / lq_b != NULL, tt_score_dir_bwd_lq
 static int dir_bwd(const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift, int64_t diag_offset,
                    const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale,
-                   float* dA, tt_stream stream, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr) {
+                   float* dA, tt_stream stream, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr,
+                   const float* pw_g = nullptr) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)tt_cdiv(Ra, RB);
   const auto go = [&](auto nch) {
+    if (pw_g) {                                          // tt_score_dir_bwd_pw
+      tt_dispatch([&](auto vec, auto lq, auto mk) {
+        score_dir_bwd_kernel<nch, vec, lq, mk, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b,
+                                                                                 d_loss, scale, dA, lq_a, lq_b, ent_n, ent_c, pw_g);
+      }, vec_ok(A, D) && vec_ok(Bm, D), lq_a != nullptr, ent_n != nullptr);
+      return;
+    }
     if (ent_n) {                                         // tt_score_dir_bwd_mask
       tt_dispatch([&](auto vec, auto lq) {
         score_dir_bwd_kernel<nch, vec, lq, true><<<grid, kThreads, 0, st>>>(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, sumexp_a, sumexp_b,
@@ -746,6 +818,44 @@ int tt_score_dir_bwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t 
   }
   if (int rc = mask_dir_check("tt_score_dir_bwd_mask", Ra, Rb, diag_offset, inv_t, lq_a != nullptr)) return rc;
   return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream, ent_n, ent_c);
+}
+
+// the pair-weight entries of the f32 parity path: g from tt_score_prepare_pw; ids and logQ vectors optional
+int tt_score_loss_finish_pw(tt_ctx* ctx, int64_t B, float shift, const float* g, const float* lq_n, const float* lq_c,
+                            const float* rowsum, const float* colsum, const float* diag, const int32_t* row_rank,
+                            const int32_t* col_rank, const float* sumscore, float* out8, float* loss_out, tt_stream stream) {
+  TT_CHECK_ARG(ctx && g && rowsum && colsum && diag && row_rank && col_rank && out8, "tt_score_loss_finish_pw: NULL argument");
+  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_loss_finish_pw: lq_n and lq_c go together");
+  TT_CHECK_ARG(B >= 1, "tt_score_loss_finish_pw: B < 1");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  tt_dispatch([&](auto lq) {
+    loss_finish_pw_kernel<lq><<<1, 1024, 0, st>>>(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, out8, loss_out, lq_n, lq_c, g);
+  }, lq_n != nullptr);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_dir_bwd_pw(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                        int64_t diag_offset, const float* g, const int32_t* ent_n, const int32_t* ent_c, const float* lq_a,
+                        const float* lq_b, const float* sumexp_a, const float* sumexp_b, const float* d_loss, float scale, float* dA,
+                        tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && g && sumexp_a && sumexp_b && d_loss && dA, "tt_score_dir_bwd_pw: NULL argument");
+  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "tt_score_dir_bwd_pw: ent_n and ent_c go together");
+  TT_CHECK_ARG((lq_a != nullptr) == (lq_b != nullptr), "tt_score_dir_bwd_pw: lq_a and lq_b go together");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_bwd_pw: bad shape");
+  if (D > 4 * DK) {
+    tt_set_error("tt_score_dir_bwd_pw: D=%d > %d not supported", D, 4 * DK);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (Ra != Rb || diag_offset != 0) {
+    tt_set_error("tt_score_dir_bwd_pw: pair weights cover the square problem only (Ra == Rb, diag_offset == 0)");
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (2.f * fabsf(inv_t) > (lq_a ? kLqMaxTwoInvT : 80.f)) {
+    tt_set_error("tt_score_dir_bwd_pw: 1/temperature = %g: needs 2/T <= %g", inv_t, lq_a ? kLqMaxTwoInvT : 80.f);
+    return TT_ERR_UNSUPPORTED;
+  }
+  return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream, ent_n, ent_c, g);
 }
 
 int tt_score_matrix(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float* S,

@@ -370,10 +370,14 @@ __device__ __forceinline__ void bwd_tile_load(BwdTile<KS, X3, LQ, MK>& T, const 
 // (softmax_term); the b tile's ids travel with its operands, a tile ahead -- at D = 256 they are loaded behind the S product, as the
 // LQ weights are there.  One wave per SIMD in every masked instantiation (launch_bsplit_mk): the ids of two tiles in flight are
 // 64 registers more.
-template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false, bool MK = false>
+// PW (tt_score_bwd_bf16_pw; square problems, bf16 operands): per-pair sample weights.  inv_a / inv_b are the weighted forward's
+// folded reciprocals g / sum, so every off-diagonal weight is right as softmax_term forms it; the only new work is the diagonal,
+// -2 g_a in place of -2 (before the weight is rounded to bf16), g_a one more value loaded at the a rows' setup.
+template <int KS, int AT, int NW, bool UNIT, bool X3 = false, bool LQ = false, bool MK = false, bool PW = false>
 __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2, KL = X3 ? KS : 1;
   static_assert(!MK || !X3, "the repeated-entity mask: bf16 operands only");
+  static_assert(!PW || !X3, "pair weights: bf16 operands only");
   __shared__ float red[(NW / 2) * ROWS * Dp];
   // (this kernel's own copy of select_dir, a_row_setup and zero_acc, and its own sweep, tree and store: through the parts its
   //  D = 256 instantiations change their scratch size, and the forward's registers move with them -- profiles/NOTES.md)
@@ -405,6 +409,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   float ia[AT], ua[AT];
   int pos[AT];
   [[maybe_unused]] int ean[AT], eac[AT];                       // (MK) the a rows' notice / company ids
+  [[maybe_unused]] float ga[AT];                               // (PW) the a rows' pair weights
 #pragma unroll
   for (int i = 0; i < AT; ++i) {
     load_bfrag<KS>(dr.a_rows, a0 / 32 + i, c, h, ares[i]);
@@ -413,6 +418,7 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
     ia[i] = a < Ra ? (inv_a ? inv_a[a] : __builtin_amdgcn_rcpf(dr.sumexp_a[a]) * kx) : 0.f;
     if constexpr (LQ) ua[i] = a < Ra ? wt_a[a] : 0.f;
     if constexpr (MK) { ean[i] = a < Ra ? args.ent_n[a] : 0; eac[i] = a < Ra ? args.ent_c[a] : 0; }
+    if constexpr (PW) ga[i] = a < Ra ? args.pw_g[a] : 0.f;
     pos[i] = a + off;
   }
   const int posmin = a0 + off, posmax = a0 + ROWS - 1 + off;
@@ -509,9 +515,15 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
         for (int r = 0; r < 16; ++r) w[r] = b_lo + rowmap(r, h) < Rb ? w[r] : 0.f;
       }
       if (band) {
+        if constexpr (PW) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (b_lo + rowmap(r, h) == pos[i]) w[r] = __builtin_fmaf(-2.f, ga[i], w[r]);
+        } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (b_lo + rowmap(r, h) == pos[i]) w[r] -= 2.f;
+        }
       }
       bf16x8 wf[2], wl[2];
 #pragma unroll
@@ -538,7 +550,8 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
     }
   };
   BwdTile<KS, X3, LQ && !WLATE, MK && !ELATE> T0, T1;
-  if constexpr ((X3 || MK) && KS == 16) {                      // x3 / MK, D = 256: one tile in flight (x3: two are 544 registers)
+  if constexpr ((X3 || MK || PW) && KS == 16) {                // x3 / MK / PW, D = 256: one tile in flight (x3: two are 544 registers;
+                                                               // PW without ids: two spilled 20-36 bytes per lane, as the plain form does)
     for (int t = wave; t < nT; t += NW) {
       bwd_tile_load<KS, X3, LQ && !WLATE>(T0, dr.b_rows, dr.b_frag, ivsrc, t, c, h, dr.b_lo, dr.b_frag_lo, wt_b, ent_n, ent_c);
       compute(T0, t);
@@ -1473,6 +1486,14 @@ static void launch_bsplit_mk(const BwdSetup& s, hipStream_t st) {
   tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, false, l, true><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
 }
 
+// its pair-weight instantiations (tt_score_bwd_bf16_pw), with and without the mask
+template <int KS, int AT, int NW>
+static void launch_bsplit_pw(const BwdSetup& s, hipStream_t st) {
+  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
+  tt_dispatch([&](auto u, auto l, auto m) { score_bwd_bf16_kernel<KS, AT, NW, u, false, l, m, true><<<grid, NW * 64, 0, st>>>(s.a); },
+              s.unit, s.lq, s.a.ent_n != nullptr);
+}
+
 // one streamed image, transposing LDS reads (score_bwd_tr_kernel)
 template <int KS, int AT>
 static void launch_tr(const BwdSetup& s, hipStream_t st) {
@@ -1595,6 +1616,40 @@ static int bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_
   return TT_OK;
 }
 
+// tt_score_bwd_bf16_pw: the square problem with per-pair sample weights; ent_n / ent_c NULL: unmasked, lq NULL: uncorrected.
+// As the masked entry: the b-split kernel for every shape, on the masked launches' tiles (one wave per SIMD) with or without ids,
+// never queued for the towers' backward launch.  The reciprocals must be the weighted forward's: without them the kernel would form
+// unweighted ones from the sums.
+static int bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g, const int32_t* ent_n, const int32_t* ent_c,
+                       const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss, float scale,
+                       tt_stream stream, const char* who) {
+  TT_CHECK_ARG(g, "%s: NULL g", who);
+  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "%s: ent_n and ent_c go together", who);
+  TT_CHECK_ARG(!ent_n || (tt_aligned(ent_n, 16) && tt_aligned(ent_c, 16)), "%s: ent_n / ent_c not 16-byte aligned", who);
+  BwdSetup s;
+  if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
+  for (int i = 0; i < n_dirs; ++i) {
+    if (dirs[i].Ra != dirs[i].Rb || dirs[i].diag_offset != 0 || dirs[i].Ra != dirs[0].Ra) {
+      tt_set_error("%s: pair weights cover the square problem only (Ra == Rb, diag_offset == 0)", who);
+      return TT_ERR_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(dirs[i].inv_a && dirs[i].inv_b, "%s: direction %d: inv_a / inv_b (the weighted forward's folded reciprocals) are required", who, i);
+  }
+  s.a.ent_n = ent_n;
+  s.a.ent_c = ent_c;
+  s.a.pw_g = g;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
+  switch (padded_d(D)) {
+    case 32: launch_bsplit_pw<2, 2, 4>(s, st); break;
+    case 64: launch_bsplit_pw<4, 2, 4>(s, st); break;
+    case 128: launch_bsplit_pw<8, 1, 4>(s, st); break;
+    default: launch_bsplit_pw<16, 1, 4>(s, st); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 // tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq.
 // One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
 // takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
@@ -1640,6 +1695,12 @@ int tt_score_bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int3
                            const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
                            float scale, tt_stream stream) {
   return bwd_bf16_mask(ctx, dirs, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_mask");
+}
+
+int tt_score_bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g, const int32_t* ent_n, const int32_t* ent_c,
+                         const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
+                         float scale, tt_stream stream) {
+  return bwd_bf16_pw(ctx, dirs, g, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_pw");
 }
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,

@@ -62,6 +62,9 @@ struct BwdArgs {
   // two arrays for both directions (square problem)
   const int32_t* ent_n;
   const int32_t* ent_c;
+  // PW kernels (tt_score_bwd_bf16_pw; the b-split form): the normalised pair weights g (tt_score_prepare_pw), one array for both
+  // directions; inv_a / inv_b are then the weighted forward's folded reciprocals
+  const float* pw_g;
 };
 
 // ---- the direction select ----------------------------------------------------------------------------------------------------

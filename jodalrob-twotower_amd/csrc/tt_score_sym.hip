@@ -410,6 +410,7 @@ struct Fin1Args {
   float* part;                         // [n_wg][4 + 2 * Dp]: l, hits, dsum, (pad), U[Dp], V[Dp]
   const float* lq_n; const float* lq_c;  // LQ: [R] log sampling probabilities of the notice / company rows
   float* w_n; float* w_c;              // LQ: their weights tt_lq_weight(lq) (0 past R): what tt_score_bwd_bf16_lq takes
+  const float* pw_g;                   // PW: [round_up(R, 64)] normalised pair weights (tt_score_prepare_pw)
 };
 
 __device__ __forceinline__ float slab_sum4(const float* __restrict__ slab, int64_t Rp, int n, int q, int i) {
@@ -437,7 +438,10 @@ __device__ __forceinline__ float slab_max4(const float* __restrict__ slab, int64
 
 // LQ: the row and column terms subtract the positive's log weight (the corrected positive s_ii - lq_i), taken exactly as
 // -kLqL - lq, never as the log of a rounded weight; the weights themselves go out for the backward.
-template <bool LQ = false>
+// PW (tt_score_fwd_sym_bf16_pw): row i's loss term times its pair weight g_i, and the reciprocals FOLDED, g_i / rowsum_i and
+// g_i / colsum_i -- the backward's off-diagonal weights e_ab (ia + ib) and e_ab (ua ib + wb ia) are then the weighted ones as they
+// stand.  rowsum / colsum stay the unweighted sums.  (g_i = 1: every product below is exact -- the plain entry's bits.)
+template <bool LQ = false, bool PW = false>
 __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
   const int i = blockIdx.x * kFinRows + lane;              // slab rows are padded: i < Rp always
@@ -537,8 +541,13 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
       const float rsum = (red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane]);
       const float csum = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
       const float draw = f.diag_raw[i], d = draw * f.unscale;
+      if constexpr (PW) {
+        f.inv_row[i] = f.pw_g[i] * (1.f / rsum);
+        f.inv_col[i] = f.pw_g[i] * (1.f / csum);
+      } else {
       f.inv_row[i] = 1.f / rsum;
       f.inv_col[i] = 1.f / csum;
+      }
       const float rs_shifted = f.unit ? rsum * f.kexp : rsum, cs_shifted = f.unit ? csum * f.kexp : csum;
       f.rowsum[i] = rs_shifted;
       f.colsum[i] = cs_shifted;
@@ -551,6 +560,7 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
       } else {
         l = (logf(rs_shifted) + f.shift - d) + (logf(cs_shifted) + f.shift - d);
       }
+      if constexpr (PW) l *= f.pw_g[i];
       dsum = d;
       if (f.want_rank) {
         const float xb = fmaxf(fmaxf(red[2][0][lane], red[2][1][lane]), fmaxf(red[2][2][lane], red[2][3][lane]));
@@ -575,6 +585,37 @@ __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
 }
 
 __global__ __launch_bounds__(kRiderThreads) void score_sym_finish2_kernel(Finish2Rider fr) { finish2_body(fr); }
+
+// ---- tt_score_prepare_pw: raw pair weights -> g = w' B / sum(w') --------------------------------------------------------------
+// One workgroup.  w' keeps the positive finite entries (a bit test: sign clear, exponent not all ones, not zero) and zeroes the
+// rest.  The sum has ONE order for a given B: thread t adds w'[t], w'[t + 1024], ...; a butterfly inside each wave; the 16 wave
+// sums in wave order.  A power-of-two factor on every weight scales each partial sum, the total and B / total exactly, so g keeps
+// its bits.  Entries B .. round_up(B, 64) - 1 are written as 0.
+constexpr int kPwThreads = 1024;
+__device__ __forceinline__ float pw_clamp(float w) {
+  const uint32_t u = __float_as_uint(w);
+  return (u - 1u) < 0x7f7fffffu ? w : 0.f;                 // 0 < bits < 0x7f800000
+}
+__global__ __launch_bounds__(kPwThreads) void score_prepare_pw_kernel(const float* __restrict__ w, int B, float* __restrict__ g) {
+  __shared__ float sh[kPwThreads / 64];
+  __shared__ float s_k;
+  const int t = threadIdx.x;
+  float s = 0.f;
+  for (int i = t; i < B; i += kPwThreads) s += pw_clamp(w[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((t & 63) == 0) sh[t >> 6] = s;
+  __syncthreads();
+  if (t == 0) {
+    float tot = 0.f;
+    for (int q = 0; q < kPwThreads / 64; ++q) tot += sh[q];
+    s_k = tot > 0.f ? (float)B / tot : 0.f;
+  }
+  __syncthreads();
+  const float k = s_k;
+  const int Bp = (B + 63) / 64 * 64;
+  for (int i = t; i < Bp; i += kPwThreads) g[i] = i < B ? pw_clamp(w[i]) * k : 0.f;
+}
 
 struct SymLayout {
   int nT, NI, n_groups, n_chunks, n_wg, Dp;
@@ -614,7 +655,8 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
                        float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col, float* diag,
                        int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
                        bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
-                       float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr) {
+                       float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr,
+                       const float* pw_g = nullptr) {
   const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
   const bool mk = ent_n != nullptr;                        // tt_score_fwd_sym_bf16_mask passes both (checked there)
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
@@ -714,7 +756,9 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   f.a_lo = g.a_lo; f.b_lo = g.b_lo;
   f.part = reinterpret_cast<float*>(ws + L.off_part);
   f.lq_n = lq_n; f.lq_c = lq_c; f.w_n = w_n; f.w_c = w_c;
-  if (lq) score_sym_finish1_kernel<true><<<(unsigned)L.n_wg, 256, 0, st>>>(f);
+  f.pw_g = pw_g;
+  if (pw_g) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
+  else if (lq) score_sym_finish1_kernel<true><<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   else score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   TT_LAUNCH_CHECK();
   Finish2Rider fr{f.part, L.n_wg, L.Dp, (float)B, f.unscale, out8, loss_out};
@@ -794,6 +838,28 @@ int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_mask", false, lq_n, lq_c,
                      lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c);
+}
+
+int tt_score_prepare_pw(tt_ctx* ctx, const float* w, int64_t B, float* g_out, tt_stream stream) {
+  TT_CHECK_ARG(ctx && w && g_out, "tt_score_prepare_pw: NULL argument");
+  TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30), "tt_score_prepare_pw: bad B=%lld", (long long)B);
+  score_prepare_pw_kernel<<<1, kPwThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(w, (int)B, g_out);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_fwd_sym_bf16_pw(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
+                             float ab_scale, int32_t want_rank, const float* g, const int32_t* ent_n, const int32_t* ent_c,
+                             const float* lq_n, const float* lq_c, float* rowsum, float* colsum, float* inv_row, float* inv_col,
+                             float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
+                             size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(g, "tt_score_fwd_sym_bf16_pw: NULL g");
+  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "tt_score_fwd_sym_bf16_pw: ent_n and ent_c go together");
+  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_pw: lq_n and lq_c go together");
+  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_pw: the logQ correction needs w_n / w_c");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_pw", false, lq_n, lq_c,
+                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c, g);
 }
 
 }  // extern "C"

@@ -48,11 +48,13 @@ class DevicePairLoader:
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
-                 shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False):
+                 shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None):
         """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
         task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
         log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
-        every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction."""
+        every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction.
+        pair_weight: optional f32 [P], one raw sample weight per row of `pairs` (pair_weights.inverse_count_weights): every batch
+        then carries "pair_weight" [B] and the train task takes the weighted mean of the pairs' loss terms."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
@@ -66,6 +68,21 @@ class DevicePairLoader:
         self._gen.manual_seed(seed)
         self.log_q = None
         self.set_log_q(log_q)
+        self.pair_weight = None
+        self.set_pair_weight(pair_weight)
+
+    def set_pair_weight(self, pair_weight) -> None:
+        """f32 [P] raw sample weights, one per row of the pair table, or None: turns pair weights on / off for every batch this
+        loader produces from now on."""
+        if pair_weight is None:
+            self.pair_weight = None
+            return
+        P = self.pairs.shape[0]
+        t = pair_weight
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != P:
+            raise ValueError(f"pair_weight: need a float32 tensor of shape [{P}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        self.pair_weight = t.to(self.pairs.device).contiguous()
 
     def set_mask_repeats(self, mask_repeats: bool) -> None:
         """Turns the repeated-entity mask on / off for every batch this loader produces from now on: with it `entity` holds the pair
@@ -104,6 +121,9 @@ class DevicePairLoader:
     def batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
         sel = self.pairs[lo:lo + self.batch_size] if order is None else self.pairs[order[lo:lo + self.batch_size]]
         out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        if self.pair_weight is not None:
+            w = self.pair_weight
+            out["pair_weight"] = w[lo:lo + self.batch_size].clone() if order is None else w[order[lo:lo + self.batch_size]]
         if self.log_q is not None:
             out["notice"]["log_q"] = self.log_q[0][sel[:, 0]]
             out["company"]["log_q"] = self.log_q[1][sel[:, 1]]
@@ -124,6 +144,19 @@ class DevicePairLoader:
         flat[:, :n] = ent
         out = torch.zeros((nb, 2, Bp), dtype=torch.int32, device=self.pairs.device)
         out[:, :, :B] = flat.view(2, nb, B).transpose(0, 1)
+        return out
+
+    def epoch_pair_weight(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """f32 [n_batches, Bp] (Bp = batch_size rounded up to 4): the pairs' raw weights in this epoch's order, batch k's at [k, :m],
+        every slice 16 bytes aligned as epoch_log_q's -- ONE gather per epoch.  None without pair_weight."""
+        if self.pair_weight is None:
+            return None
+        n, B = self.pairs.shape[0], self.batch_size
+        nb, Bp = (n + B - 1) // B, (B + 3) // 4 * 4
+        flat = torch.zeros(nb * B, dtype=torch.float32, device=self.pairs.device)
+        flat[:n] = self.pair_weight if order is None else self.pair_weight[order]
+        out = torch.zeros((nb, Bp), dtype=torch.float32, device=self.pairs.device)
+        out[:, :B] = flat.view(nb, B)
         return out
 
     def epoch_log_q(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -181,8 +214,12 @@ class DevicePairLoader:
         ent = self.epoch_entity(order)
         if ent is not None and U > 1:
             raise NotImplementedError("the repeated-entity mask is not supported by the unrolled step")
+        pw = self.epoch_pair_weight(order)
+        if pw is not None and U > 1:
+            raise NotImplementedError("pair weights are not supported by the unrolled step")
         kw = lambda lo, m: {**({} if lq is None else {"log_q": (lq[lo // B, 0, :m], lq[lo // B, 1, :m])}),
-                            **({} if ent is None else {"entity": (ent[lo // B, 0, :m], ent[lo // B, 1, :m])})}
+                            **({} if ent is None else {"entity": (ent[lo // B, 0, :m], ent[lo // B, 1, :m])}),
+                            **({} if pw is None else {"pair_weight": pw[lo // B, :m]})}
         lo = 0
         while U > 1 and lo + U * B <= n:                      # unrolled.UnrolledTrainStep: U full batches per graph launch
             for r in graphed_step.steps_from_store(self.notice, self.company, self.pairs, order, [lo + j * B for j in range(U)]):
@@ -214,6 +251,8 @@ class DevicePairLoader:
         if self.entity is not None:
             out["notice"]["entity"] = sel[:, 0].to(torch.int32)
             out["company"]["entity"] = sel[:, 1].to(torch.int32)
+        if self.pair_weight is not None:
+            out["pair_weight"] = self.pair_weight[:r].clone()
         return out
 
 

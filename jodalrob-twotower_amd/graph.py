@@ -31,6 +31,7 @@ class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
     _log_q_ok = True               # batches may carry "log_q" (the logQ correction); the unrolled / segmented steps refuse them
     _entity_ok = True              # batches may carry "entity" (the repeated-entity mask); likewise
+    _pair_weight_ok = True         # batches may carry "pair_weight" (per-pair sample weights); likewise
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
@@ -63,6 +64,14 @@ class GraphedTrainStep:
                 raise NotImplementedError(f"the repeated-entity mask (a batch with 'entity') is not supported by {type(self).__name__}")
             if getattr(task, "exchange", None) is not None:
                 raise NotImplementedError("the repeated-entity mask (a batch with 'entity') is not supported by the sharded task")
+        # pair weights: an example batch with "pair_weight" gets a static f32 [B] buffer, filled at every hand-over through one more
+        # copy segment; the captured forward reads it (the weights' preparation launch is part of the capture)
+        self._has_pair_weight = example_batch.get("pair_weight") is not None
+        if self._has_pair_weight:
+            if not self._pair_weight_ok:
+                raise NotImplementedError(f"pair weights (a batch with 'pair_weight') are not supported by {type(self).__name__}")
+            if getattr(task, "exchange", None) is not None:
+                raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
@@ -84,6 +93,9 @@ class GraphedTrainStep:
             for side in ("notice", "company"):
                 t = example_batch[side].get("entity")
                 self.static[side]["entity"] = self._check_entity(t, side, B, dev).clone() if t is not None else self._ent_iota.clone()
+        if self._has_pair_weight:
+            B = example_batch["notice"]["dense"].shape[0]
+            self.static["pair_weight"] = self._check_pair_weight(example_batch["pair_weight"], B, dev).clone()
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
@@ -447,6 +459,27 @@ class GraphedTrainStep:
         t = t.contiguous()
         return t if t.data_ptr() % 16 == 0 else t.clone()
 
+    @staticmethod
+    def _check_pair_weight(t, B, dev):
+        """t as a contiguous, 16-byte aligned f32 [B] on dev (as _check_log_q)"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"pair_weight must be a float32 tensor of shape [{B}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != dev:
+            raise ValueError(f"pair_weight is on {t.device}, the captured step on {dev}")
+        t = t.contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    def _pair_weight_pairs(self, w, who):
+        """the copy segment of this step's pair weights into the static buffer, after the with / without check"""
+        if (w is not None) != self._has_pair_weight:
+            raise ValueError("pair_weight mismatch: the step was captured " + ("with" if self._has_pair_weight else "without") +
+                             f" pair weights, {who} " + ("has none" if self._has_pair_weight else "carries them"))
+        if w is None:
+            return []
+        sw = self.static["pair_weight"]
+        return [(sw, GraphedTrainStep._check_pair_weight(w, sw.shape[0], sw.device))]
+
     def _entity_pairs(self, ent_n, ent_c):
         """copy segments of this step's entity ids into the static buffers (a side given as None: the row indices)"""
         B, dev = self._ent_iota.shape[0], self._ent_iota.device
@@ -476,6 +509,7 @@ class GraphedTrainStep:
                              " entity ids, the batch " + ("has none" if self._has_entity else "carries them"))
         if self._has_entity:
             pairs += self._entity_pairs(ent_n, ent_c)
+        pairs += self._pair_weight_pairs(batch.get("pair_weight"), "the batch")
         for side in ("notice", "company"):
             d, v = batch[side]["dense"], batch[side]["kjt"].values()
             sd, sv = self.static[side]["dense"], self.static[side]["kjt"].values()
@@ -511,7 +545,7 @@ class GraphedTrainStep:
         return self.result
 
     def step_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor] = None, offset: int = 0,
-                        log_q=None, entity=None):
+                        log_q=None, entity=None, pair_weight=None):
         """Train on the B pairs `pairs[order[offset : offset + B]]` (order None: `pairs[offset : offset + B]`) gathered straight
         out of the device-resident feature stores into the static buffers -- ONE launch (tt_batch_ingest_store: dense rows, ids,
         key-major fused rows, the step scalars) and the replay; nothing per step crosses PCIe and no batch tensors are built
@@ -521,7 +555,8 @@ class GraphedTrainStep:
         log_q: (notice, company) f32 [B] of this step's pairs for a step captured with a log_q (DevicePairLoader.step_batches passes
         slices of its per-epoch array): two more copy segments of the same launch.
         entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
-        DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise."""
+        DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise.
+        pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment."""
         if (log_q is not None) != self._has_log_q:
             raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
                              " a log_q, step_from_store got " + ("none" if self._has_log_q else "one"))
@@ -529,6 +564,7 @@ class GraphedTrainStep:
             raise ValueError("entity mismatch: the step was captured " + ("with" if self._has_entity else "without") +
                              " entity ids, step_from_store got " + ("none" if self._has_entity else "them"))
         extra = (self._log_q_pairs(*log_q) if log_q is not None else []) + (self._entity_pairs(*entity) if entity is not None else [])
+        extra += self._pair_weight_pairs(pair_weight, "step_from_store")
         self._ingest_from_store(notice_store, company_store, pairs, order, offset, extra=extra or None)
         self._mark_slot()
         return self._replay()

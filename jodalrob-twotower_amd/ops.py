@@ -527,6 +527,32 @@ def _mask_args(ent, lq, n_lq):
     return (L.ptr(ent[0]), L.ptr(ent[1])) + (tuple(map(L.ptr, lq)) if lq else (None,) * n_lq)
 
 
+# per-pair sample weights (the *_pw entries of include/twotower.h): the score wrappers take the normalised weights `pw` =
+# score_pair_weights(w, B, dev) as an optional argument and call the _pw entry when it is given; ent / lq combine with it
+def score_pair_weights(w, B, dev):
+    """g = w' B / sum(w') as the *_pw entries read it (tt_score_prepare_pw, one launch): f32 [round_up(B, 64)], 0 past B; w' = the raw
+    weights w (f32 [B] on `dev`) with every entry that is not a positive finite number set to 0; all 0 when the sum is 0."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError(f"pair_weight must be a torch.Tensor, got {type(w).__name__}")
+    if w.dtype != torch.float32:
+        raise TypeError(f"pair_weight must be float32, got {w.dtype}")
+    if w.dim() != 1 or w.shape[0] != B:
+        raise ValueError(f"pair_weight must have shape [{B}], got {list(w.shape)}")
+    if w.device != torch.device(dev):
+        raise ValueError(f"pair_weight is on {w.device}, the scores on {dev}")
+    w = w.contiguous()
+    g = torch.empty((B + 63) // 64 * 64, dtype=torch.float32, device=w.device)
+    with _timed("tt_score_prepare_pw"):
+        L.check(L.load().tt_score_prepare_pw(L.ctx(w.device), L.ptr(w), B, L.ptr(g), L.stream(w.device)), "tt_score_prepare_pw")
+    return g
+
+
+def _pw_args(pw, ent, lq, n_lq):
+    """the _pw entries' (g, ent_n, ent_c, lq...) arguments: NULL where the call has no ids / no logQ vectors"""
+    return (L.ptr(pw),) + ((L.ptr(ent[0]), L.ptr(ent[1])) if ent is not None else (None, None)) \
+        + (tuple(map(L.ptr, lq)) if lq else (None,) * n_lq)
+
+
 def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True, lq_b=None, ent=None):
     """lq_b: the B rows' log sampling probabilities [Rb] (tt_score_dir_fwd_lq).
     ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask (tt_score_dir_fwd_mask, square problems)."""
@@ -549,13 +575,21 @@ def score_dir_fwd(A, Bm, inv_t, shift, diag_offset=0, want_sumscore=True, lq_b=N
     return f[0], f[1], rank, f[2]
 
 
-def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=None, lq_c=None):
+def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=None, lq_c=None, pw=None):
     """Returns (out8, loss): the loss is its own 0-dim tensor so that autograd sees a plain output.
-    lq_n / lq_c (both or neither): the corrected positives (tt_score_loss_finish_lq)."""
+    lq_n / lq_c (both or neither): the corrected positives (tt_score_loss_finish_lq).
+    pw: score_pair_weights' g -- the weighted loss (tt_score_loss_finish_pw)."""
     dev = rowsum.device
     lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
     out = torch.empty(8, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
+    if pw is not None:
+        name = "tt_score_loss_finish_pw"
+        with _timed(name):
+            L.check(getattr(L.load(), name)(L.ctx(dev), B, shift, L.ptr(pw), *(map(L.ptr, lq) if lq else (None, None)), L.ptr(rowsum),
+                                            L.ptr(colsum), L.ptr(diag), L.ptr(row_rank), L.ptr(col_rank), L.ptr(sumscore), L.ptr(out),
+                                            L.ptr(loss), L.stream(dev)), name)
+        return out, loss
     name = "tt_score_loss_finish_lq" if lq else "tt_score_loss_finish"
     with _timed(name):
         L.check(getattr(L.load(), name)(L.ctx(dev), B, shift, *map(L.ptr, lq), L.ptr(rowsum), L.ptr(colsum), L.ptr(diag),
@@ -564,12 +598,19 @@ def score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumsco
     return out, loss
 
 
-def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=None, lq_b=None, ent=None):
+def score_dir_bwd(A, Bm, inv_t, shift, diag_offset, sumexp_a, sumexp_b, d_loss, scale, lq_a=None, lq_b=None, ent=None, pw=None):
     """lq_a / lq_b (both or neither): the log sampling probabilities of the A rows [Ra] and the B rows [Rb] (tt_score_dir_bwd_lq).
-    ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask (tt_score_dir_bwd_mask, square problems)."""
+    ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask (tt_score_dir_bwd_mask, square problems).
+    pw: score_pair_weights' g -- the weighted gradient (tt_score_dir_bwd_pw, square problems; ent / lq optional)."""
     dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
     lq = _lq_pair(lq_a, lq_b, Ra, Rb, dev, ("lq_a", "lq_b"))
     dA = torch.empty_like(A)
+    if pw is not None:
+        name = "tt_score_dir_bwd_pw"
+        with _timed(name):
+            L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, diag_offset, *_pw_args(pw, ent, lq, 2),
+                                            L.ptr(sumexp_a), L.ptr(sumexp_b), L.ptr(d_loss), scale, L.ptr(dA), L.stream(dev)), name)
+        return dA
     if ent is not None:
         name = "tt_score_dir_bwd_mask"
         with _timed(name):
@@ -659,12 +700,15 @@ def score_pack2_fp8(X0, X1, scale0: float = 1.0, scale1: float = 1.0):
 
 
 def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False,
-             lq_n=None, lq_c=None, ent=None):
-    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq, score_fwd_sym_mask): returns (rowsum, colsum, diag,
-    row_rank, (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n / lq_c given,
-    tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None.  ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask
-    (tt_score_fwd_sym_bf16_mask, bf16 operands only)."""
+             lq_n=None, lq_c=None, ent=None, pw=None):
+    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq, score_fwd_sym_mask, score_fwd_sym_pw): returns (rowsum,
+    colsum, diag, row_rank, (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n /
+    lq_c given, tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None.  ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask
+    (tt_score_fwd_sym_bf16_mask, bf16 operands only).  pw: score_pair_weights' g -- the weighted loss and FOLDED reciprocals g / sum
+    (tt_score_fwd_sym_bf16_pw, bf16 operands only; ent / lq optional)."""
     dev = Np.device
+    if pw is not None and (fp8 or x3):
+        raise ValueError("the weighted symmetric forward takes bf16 operands only")
     if lq_n is not None and fp8:
         raise ValueError("the logQ-corrected symmetric forward has no fp8 form")
     if ent is not None and (fp8 or x3):
@@ -683,7 +727,9 @@ def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool =
         ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
     name = ("tt_score_fwd_sym_fp8" if fp8 else ("tt_score_fwd_sym_bf16x3" if x3 else "tt_score_fwd_sym_bf16")) + ("_lq" if lq else "")
     w_out = (L.ptr(f[5]), L.ptr(f[6])) if lq else ()
-    if ent is not None:
+    if pw is not None:
+        name, pre, w_out = "tt_score_fwd_sym_bf16_pw", _pw_args(pw, ent, lq, 2), w_out or (None, None)
+    elif ent is not None:
         name, pre, w_out = "tt_score_fwd_sym_bf16_mask", _mask_args(ent, lq, 2), w_out or (None, None)
     else:
         pre = tuple(map(L.ptr, lq))
@@ -717,8 +763,16 @@ def score_fwd_sym_mask(Np, Cp, B, D, inv_t, shift, ent, lq_n=None, lq_c=None, sc
     return r[:5] + (r[7],) + r[5:7]
 
 
+def score_fwd_sym_pw(Np, Cp, B, D, inv_t, shift, pw, ent=None, lq_n=None, lq_c=None, scale_n: float = 1.0, want_rank: bool = True):
+    """score_fwd_sym with per-pair sample weights (tt_score_fwd_sym_bf16_pw): pw = score_pair_weights(w, B, dev); ent (from
+    score_mask_ids) and lq_n / lq_c optional.  Returns as score_fwd_sym_mask; (inv_row, inv_col) are the folded g / rowsum, g / colsum
+    that score_bwd_bf16(..., pw=) requires, rowsum / colsum the unweighted sums."""
+    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, False, lq_n, lq_c, ent, pw)
+    return r[:5] + (r[7],) + r[5:7]
+
+
 def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n: float = 1.0, inv=None, fp8: bool = False,
-                   x3: bool = False, w=None, ent=None):
+                   x3: bool = False, w=None, ent=None, pw=None):
     """inv: (inv_row, inv_col) from score_fwd_bf16(..., with_inv=True) with the same scale_n (optional).
     fp8: the operands are tt_score_pack2_fp8 buffers (tt_score_bwd_fp8); x3: score_pack2_bf16x3 buffers (tt_score_bwd_bf16x3).
     w: (w_n, w_c) from score_fwd_sym_lq, with its rowsum / colsum / inv: the logQ-corrected backward
@@ -728,6 +782,10 @@ def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, sc
         raise ValueError("the logQ-corrected backward has no fp8 form")
     if ent is not None and (fp8 or x3):
         raise ValueError("the masked backward takes bf16 operands only")
+    if pw is not None and (fp8 or x3):
+        raise ValueError("the weighted backward takes bf16 operands only")
+    if pw is not None and inv is None:
+        raise ValueError("the weighted backward needs inv, the weighted forward's folded reciprocals")
     dN = torch.empty((B, D), dtype=torch.float32, device=dev)
     dC = torch.empty((B, D), dtype=torch.float32, device=dev)
     arr = (L.ScoreBwdDir * 2)()
@@ -740,7 +798,9 @@ def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, sc
         lq[0][0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))              # direction (N, C): A = notices, B = companies
         lq[0][1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
     name = ("tt_score_bwd_fp8" if fp8 else ("tt_score_bwd_bf16x3" if x3 else "tt_score_bwd_bf16")) + ("_lq" if lq else "")
-    if ent is not None:                                            # (ent: score_mask_ids' padded arrays, with the masked forward's sums)
+    if pw is not None:                                             # (pw: score_pair_weights' g, with the weighted forward's inv)
+        name, lq = "tt_score_bwd_bf16_pw", _pw_args(pw, ent, None, 0) + (lq[0] if lq else None,)
+    elif ent is not None:                                          # (ent: score_mask_ids' padded arrays, with the masked forward's sums)
         name, lq = "tt_score_bwd_bf16_mask", (L.ptr(ent[0]), L.ptr(ent[1]), lq[0] if lq else None)
     with _timed(name):
         L.check(getattr(L.load(), name)(L.ctx(dev), arr, *lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)

@@ -90,6 +90,7 @@ class SegmentedTrainStep(GraphedTrainStep):
     """GraphedTrainStep whose capture is cut at every collective (see the module docstring).  Same interface and results."""
     _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
     _entity_ok = False             # the repeated-entity mask likewise
+    _pair_weight_ok = False        # pair weights likewise
 
     segmented = True
 

@@ -54,11 +54,14 @@ class _ScoreCEFn(torch.autograd.Function):
     gradients of the corrected softmax, metrics on the raw scores.
     ent_n / ent_c (int32 [B], either or both; a missing side counts as all-distinct): the repeated-entity mask (include/twotower.h
     *_mask entries) -- pairs a != b whose rows share a notice or a company leave both softmax sums; score_dtype 'bf16' and 'fp32'
-    only; combines with lq_n / lq_c; metrics on the raw scores."""
+    only; combines with lq_n / lq_c; metrics on the raw scores.
+    pair_w (f32 [B] raw per-pair sample weights): the weighted mean of the pairs' terms (include/twotower.h *_pw entries) -- entries
+    that are not positive finite numbers count as 0; score_dtype 'bf16' and 'fp32' only; combines with lq_* and ent_*; the sums and
+    the metrics are the unweighted ones."""
 
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
-                lq_n=None, lq_c=None, ent_n=None, ent_c=None):
+                lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
@@ -71,6 +74,13 @@ class _ScoreCEFn(torch.autograd.Function):
             if c.shape != n.shape:
                 raise ValueError("the repeated-entity mask needs as many notice rows as company rows")
             ent = ops.score_mask_ids(ent_n, ent_c, B, n.device)
+        pw = None
+        if pair_w is not None:
+            if fp8 or x3:
+                raise ValueError(f"pair weights have no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
+            if c.shape != n.shape:
+                raise ValueError("pair weights need as many notice rows as company rows")
+            pw = ops.score_pair_weights(pair_w, B, n.device)
         if lq:
             if fp8:
                 raise ValueError("the logQ correction has no fp8 form")
@@ -100,14 +110,14 @@ class _ScoreCEFn(torch.autograd.Function):
                 scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
                 Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
         # the kernel form, once.  Symmetric: ONE sweep of the B x B tiles serves both softmax directions -- the steady state of
-        # training, and always for fp8, the logQ correction and the repeated-entity mask (their row ranks and metrics are the raw
-        # scores').  Otherwise the
+        # training, and always for fp8, the logQ correction, the repeated-entity mask and pair weights (their row ranks and metrics
+        # are the raw scores').  Otherwise the
         # first call's diagnostics (column / full ranks) on the two-direction kernel, or the f32 path's two directional sweeps.
         w = None
-        if Np is not None and (fp8 or lq or ent is not None or not (want_col_rank or full_rank)):
+        if Np is not None and (fp8 or lq or ent is not None or pw is not None or not (want_col_rank or full_rank)):
             rowsum, colsum, diag, row_rank, inv, out8, loss, w = ops._fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, fp8, x3,
-                                                                              lq_n, lq_c, ent)
-            if (lq or ent is not None) and want_col_rank:
+                                                                              lq_n, lq_c, ent, pw)
+            if (lq or ent is not None or pw is not None) and want_col_rank:
                 # the first call's column top-1 rate (a diagnostic only) from the uncorrected two-direction kernel
                 col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
                 out8 = out8.clone()
@@ -123,9 +133,9 @@ class _ScoreCEFn(torch.autograd.Function):
                 colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n, ent=ent)
                 if lq:
                     w = (lq_n.contiguous(), lq_c.contiguous())
-            out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c)
+            out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c, pw=pw)
         ctx.packed = None if Np is None else (Np, Cp, scale_n, inv)
-        ctx.fp8, ctx.x3, ctx.lq, ctx.ent = fp8, x3, w, ent
+        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = fp8, x3, w, ent, pw
         ctx.save_for_backward(n, c, rowsum, colsum)
         ctx.inv_t, ctx.shift = inv_t, shift
         ctx.mark_non_differentiable(out8, row_rank)
@@ -137,19 +147,19 @@ class _ScoreCEFn(torch.autograd.Function):
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return (None,) * 13
+            return (None,) * 14
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
         if ctx.packed is not None:
             Np, Cp, scale_n, inv = ctx.packed
             dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, fp8=ctx.fp8,
-                                        x3=ctx.x3, w=ctx.lq, ent=ctx.ent)
+                                        x3=ctx.x3, w=ctx.lq, ent=ctx.ent, pw=ctx.pw)
         else:
             lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
-            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent)
-            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent)
-        return (dN, dC) + (None,) * 11
+            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent, pw=ctx.pw)
+            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent, pw=ctx.pw)
+        return (dN, dC) + (None,) * 12
 
 
 class _Result(dict):
@@ -225,8 +235,12 @@ class TwoTowerTrainTask(nn.Module):
             raise ValueError(f"Notice와 Company 배치 크기가 다릅니다: {nb} vs {cb}")
         lq = self._batch_log_q(notice_input, company_input, nb)
         ent = self._batch_entity(notice_input, company_input, nb)
+        pw = self._batch_pair_weight(batch, nb)
         notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
-        if ent is not None:
+        if pw is not None:
+            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
+                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw)
+        elif ent is not None:
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
                                            not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent)
         elif lq is None:
@@ -252,6 +266,8 @@ class TwoTowerTrainTask(nn.Module):
         """(result dict as forward(batch, return_metrics=True), 0-based rank of each positive in its row) from ONE pass
         through the towers -- what the evaluator needs per batch (src/evaluation/evaluator.py:123-155 calls the model once
         and ranks its similarity matrix).  Ranks come from the exact-f32 score sweep, as diagonal_ranks()."""
+        if batch.get("pair_weight") is not None:
+            raise ValueError("forward_with_ranks does not take a batch with 'pair_weight' (evaluation is unweighted)")
         with torch.no_grad():
             n, c = self.two_tower_model(batch["notice"], batch["company"])
             if n.size(0) != c.size(0):
@@ -312,9 +328,41 @@ class TwoTowerTrainTask(nn.Module):
                 raise ValueError(f"batch['{name}']['entity'] is on {t.device}, the batch on {ref.device}")
         return ent_n, ent_c
 
-    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None):
+    def _batch_pair_weight(self, batch, B):
+        """f32 [B] raw per-pair sample weights from batch["pair_weight"], or None when the batch carries none.  Refuses what the
+        weighted loss does not cover -- never ignores a pair_weight."""
+        t = batch.get("pair_weight")
+        if t is None:
+            return None
+        if self._dense_loss:
+            raise ValueError("pair weights (a batch with 'pair_weight') are not supported by the dense loss path "
+                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
+        if self.score_dtype in ("fp8", "bf16x3"):
+            raise ValueError(f"pair weights (a batch with 'pair_weight') are not supported for score_dtype={self.score_dtype!r}")
+        ref = batch["notice"]["dense"]
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"batch['pair_weight'] must be a float32 tensor of shape [{B}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != ref.device:
+            raise ValueError(f"batch['pair_weight'] is on {t.device}, the batch on {ref.device}")
+        return t
+
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None):
         """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it.
-        log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn).  entity: (ent_n, ent_c) -- the repeated-entity mask."""
+        log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn).  entity: (ent_n, ent_c) -- the repeated-entity mask.
+        pair_weight: f32 [B] -- per-pair sample weights; combines with both."""
+        if pair_weight is not None:
+            if self._dense_loss or self.score_dtype in ("fp8", "bf16x3"):
+                raise ValueError("pair weights cover the fused cross-entropy with score_dtype fp32 / bf16 only")
+            if n.shape != c.shape:
+                raise ValueError("pair weights need as many notice rows as company rows")
+            lqs = log_q if log_q is not None else (None, None)
+            ents = entity if entity is not None else (None, None)
+            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
+            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
+                pn, pc = (None, None), (None, None)
+            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], ents[0], ents[1],
+                                    pair_weight)
         if entity is not None:
             if self._dense_loss or self.score_dtype in ("fp8", "bf16x3"):
                 raise ValueError("the repeated-entity mask covers the fused cross-entropy with score_dtype fp32 / bf16 only")

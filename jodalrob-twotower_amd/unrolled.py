@@ -30,6 +30,7 @@ class UnrolledTrainStep(GraphedTrainStep):
     steps; `step` / `step_from_store` (one step: an epoch's remainder) go through a single-step sibling captured on first use."""
     _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
     _entity_ok = False             # the repeated-entity mask likewise
+    _pair_weight_ok = False        # pair weights likewise
 
     def __init__(self, task, optimizer, example_batch: Dict, unroll: int = 2, **kw):
         if int(unroll) < 2:

@@ -109,6 +109,9 @@ def main():
     ap.add_argument("--mask-repeats", action="store_true",
                     help="mask the in-batch negatives that repeat a row's notice or company (the repeated-entity mask): the train loader "
                          "attaches each pair's notice / company index (evaluation stays unmasked); combines with --logq-correction")
+    ap.add_argument("--pair-weight", choices=["inv-notice-count"], default=None,
+                    help="per-pair sample weights of the in-batch softmax: inv-notice-count = 1 / (pairs of the row's notice), every notice "
+                         "counts once; attached to the train loader only; combines with --mask-repeats and --logq-correction")
     ap.add_argument("--logq-correction", action="store_true",
                     help="logQ sampling-bias correction of the in-batch softmax: log sampling probabilities estimated from the TRAIN pairs, "
                          "attached to the train loader only (evaluation stays uncorrected)")
@@ -146,6 +149,9 @@ def main():
                                                                test_mode=True, pair_limit=config["pair_limit"], device=device)
     if a.mask_repeats:
         train_loader.set_mask_repeats(True)
+    if a.pair_weight == "inv-notice-count":
+        from jodalrob_twotower_amd.pair_weights import inverse_count_weights
+        train_loader.set_pair_weight(inverse_count_weights(train_loader.pairs, "notice"))
     if a.logq_correction:                                # exact: batches are uniform draws from this fixed pair list
         from jodalrob_twotower_amd.sampling_bias import log_sampling_probs
         tp = train_loader.pairs
