@@ -424,6 +424,7 @@ typedef struct tt_tower_params {
 #define TT_TOWER_UNFUSED_TAIL 1
 #define TT_TOWER_UNFUSED_FRONT 2 /* keep projection GEMM, block GEMM and slab/statistics pass as separate launches */
 #define TT_TOWER_UNFUSED_BACK 4  /* first-block weight / data gradients and the projection's weight gradient as separate launches */
+#define TT_TOWER_UNFUSED_GATHER 8 /* never gather the embedding rows in the one-launch front (tt_towers_fwd_gathers answers 0) */
 
 typedef struct tt_tower_acts { /* caller-allocated; kept between forward and backward */
   const float* dense;          /* [B, din] */
@@ -442,6 +443,15 @@ typedef struct tt_tower_acts { /* caller-allocated; kept between forward and bac
   const float* bn_sync_all; /* sync_phase 2 in:  [sync_ranks][3][hidden[0]] */
   int64_t bn_sync_stride;   /* floats between two ranks' triples in bn_sync_all (0 = 3 * hidden[0]): lets one all-gather
                                carry every tower's statistics */
+  /* Optional: the forward GATHERS x[:, h0:] itself, inside the one-launch front, instead of finding it filled by a lookup
+   * launch (all zero = x is already filled).  gather_rows are this tower's fused table rows in slot order, [B][gather_K] int32
+   * (its slice of what tt_embed_lookup_rows_fwd reads); x[b, h0 + k E + e] = bf16(gather_table[gather_rows[b][k]][e]) -- the bits
+   * that lookup stores -- and x is written whole, as before.  Only passes for which tt_towers_fwd_gathers() answers 1 take
+   * these fields; any other pass returns TT_ERR_UNSUPPORTED when they are set. */
+  const float* gather_table;  /* [rows][gather_E] f32, 16-byte aligned */
+  const int32_t* gather_rows;
+  int32_t gather_K;           /* keys of this tower: gather_K * gather_E == params.kcat_e */
+  int32_t gather_E;           /* 8, 16, ... 256 */
 } tt_tower_acts;
 
 typedef struct tt_tower_grads { /* every buffer is overwritten, not accumulated */
@@ -481,6 +491,13 @@ int tt_tower_mlp_bwd(tt_ctx* ctx, const tt_tower_params* p, const tt_tower_acts*
 int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* p, const tt_tower_acts* const* a,
                       int64_t B, int32_t train, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
                       void* const* workspaces, const size_t* workspace_bytes, tt_stream stream);
+/* 1 if tt_towers_mlp_fwd on exactly these arguments (gather fields of every a[t] filled in) runs the gathering front and so
+ * needs no lookup launch in front of it; 0 otherwise -- then the caller clears the fields and looks the rows up as before.
+ * It asks for: a training pass with sync_phase 0 that takes the one-launch front (ONE hidden block <= 64 wide, d_out <= 64,
+ * bf16 compute and x, din and h0 + kcat_e multiples of 64, h0 a multiple of 32 <= 128), bf16 weight shadows on every tower,
+ * gather_E a power of two in 8..256, gather_K * gather_E == kcat_e, gather_K <= 152 (the index tile fits the CU's LDS), a
+ * 16-byte-aligned table, and TT_TOWER_UNFUSED_GATHER on no tower.  No device work. */
+int tt_towers_fwd_gathers(int32_t n, const tt_tower_params* const* p, const tt_tower_acts* const* a, int64_t B, int32_t train);
 int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* p, const tt_tower_acts* const* a,
                       const float* const* d_emb, const tt_tower_grads* const* g, int64_t B, int32_t train,
                       float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* const* workspaces,

@@ -21,6 +21,7 @@ TT_GRAD_SPARSE, TT_GRAD_DENSE_SET, TT_GRAD_DENSE_ACC = 0, 1, 2
 TT_TOWER_UNFUSED_TAIL = 1
 TT_TOWER_UNFUSED_FRONT = 2
 TT_TOWER_UNFUSED_BACK = 4
+TT_TOWER_UNFUSED_GATHER = 8
 TT_GRAD_SHORT_SEGMENTS = 0x100
 TT_GRAD_PLANNED = 0x200
 TT_GRAD_DEFER_FINISH = 0x400
@@ -87,7 +88,8 @@ class TowerParams(C.Structure):
 
 class TowerActs(C.Structure):
     _fields_ = [("dense", vp), ("x", vp), ("pre", _H), ("act", _H), ("mean", _H), ("rstd", _H), ("y", vp), ("emb", vp), ("emb_packed", vp), ("emb_pack_scale", f32),
-                ("bn_sync_local", vp), ("bn_sync_all", vp), ("bn_sync_stride", i64)]
+                ("bn_sync_local", vp), ("bn_sync_all", vp), ("bn_sync_stride", i64),
+                ("gather_table", vp), ("gather_rows", vp), ("gather_K", i32), ("gather_E", i32)]
 
 
 class TowerGrads(C.Structure):
@@ -142,6 +144,7 @@ SIGNATURES = {
                                    f32, u64, vp, vp, sz, vp]),
     "tt_towers_mlp_fwd": (C.c_int, [vp, i32, C.POINTER(C.POINTER(TowerParams)), C.POINTER(C.POINTER(TowerActs)), i64, i32, f32, u64,
                                     vp, C.POINTER(vp), C.POINTER(sz), vp]),
+    "tt_towers_fwd_gathers": (C.c_int, [i32, C.POINTER(C.POINTER(TowerParams)), C.POINTER(C.POINTER(TowerActs)), i64, i32]),
     "tt_towers_mlp_bwd": (C.c_int, [vp, i32, C.POINTER(C.POINTER(TowerParams)), C.POINTER(C.POINTER(TowerActs)), C.POINTER(vp),
                                     C.POINTER(C.POINTER(TowerGrads)), i64, i32, f32, u64, vp, C.POINTER(vp), C.POINTER(sz), vp]),
     "tt_score_dir_fwd": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),

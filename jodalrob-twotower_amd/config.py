@@ -39,6 +39,7 @@ class Settings:
     graph_ingest_rows: bool = True       # ... which also leaves the rows in slot order: the captured lookup reads those (tt_embed_lookup_rows_fwd)
     graph_ingest_lookup: bool = False    # the hand-over launch ALSO does the lookup (tt_batch_ingest_lookup): one launch fewer, measured neutral
     #                                      (both halves are bandwidth-bound: 0.2332 vs 0.2339 ms per step, profiles/NOTES.md round 4) -- off
+    front_gather: bool = True            # a captured step's towers gather the embedding rows inside their one-launch front: no lookup launch
     grad_planned: bool = True            # the keyed duplicate-row plan also prepares embed_grad's long-row list (one launch fewer)
 
     @classmethod

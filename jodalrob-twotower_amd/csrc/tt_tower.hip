@@ -437,11 +437,13 @@ struct FrontArgs {
   const float* w; const float* bias; float* pre;
   BnStatArgs s;
   const uint16_t* w_proj16; const uint16_t* w16;   // W16: bf16 shadows of w_proj / w (tt_tower_params.w_proj_bf16 / w_bf16)
+  const float* table; const int32_t* rows; int K, E;   // GATHER: the table, this side's fused rows [B][K] (slot order), keys, row width
 };
 constexpr int kFS = 136;                                         // bf16 elements per LDS row of a 128-wide k stage
 constexpr int kFrontThreads = 512;                               // 8 waves at up to 256 registers: three stages of loads in flight
 constexpr int kFrontA = 64 * kFS * 2, kFrontB = 128 * kFS * 2;   // bytes of one A / B stage buffer
 constexpr int kFrontLds = 2 * kFrontA + 2 * kFrontB + kFrontA + 4 * 64 * 12;
+constexpr int kFrontLdsMax = 160 * 1024;                         // with the GATHER form's index tile (64 x K fused rows) behind it
 
 using tl_bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
 __device__ __forceinline__ void front_put4(__bf16* dst, const float4& v, bool live) {
@@ -460,7 +462,15 @@ __device__ __forceinline__ T front_ld(const void* base, uint32_t off) {
 // W16 (round 4): the weights come as bf16 shadows -- pieces of 8 elements laid out like the x pieces (row (t >> 4) + 32 pass,
 // k = 8 (t & 15)), copied into LDS as they are: 213 of the 637 KB a notice workgroup moved were the f32 halves of values it rounded
 // to bf16 anyway, and the 112 registers of weight pieces in flight become 56 (no scratch).  Same bits in LDS, same results.
-template <bool W16>
+//
+// GATHER: the embedding rows are gathered HERE instead of by a lookup launch in front (tt_embed_lookup_rows_fwd): the 16-byte
+// piece of x at k >= h0 is 8 consecutive f32 of table row rows[b][(k - h0) / E], loaded as two float4 on the x pieces' schedule
+// (three stages ahead, a dead piece re-reads a live address and is zeroed), rounded with tt_f2bf and packed as the lookup's
+// 32-byte-lane store does on the way into the A stage -- the same bits in LDS -- and stored to x[:, h0:] by the thread that
+// converted it: x stays the complete output gemm_back and the row gradients read, while the lookup's write of it, its write-back,
+// this kernel's re-read and one launch go.  The block's 64 x K fused rows wait in an LDS tile behind the statistics area
+// (one coalesced read, issued in front of the projection's loads).  E a power of two >= 8: a piece never straddles two rows.
+template <bool W16, bool GATHER = false>
 __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontArgs> batch) {
   const FrontArgs& f = batch.a[blockIdx.y];
   const BnStatArgs& a = f.s;
@@ -472,6 +482,7 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
   __bf16* Pt = reinterpret_cast<__bf16*>(front_smem + 2 * kFrontA + 2 * kFrontB);    // [64][kFS] projection tile
   Wf (*sh)[64] = reinterpret_cast<Wf (*)[64]>(front_smem + 3 * kFrontA + 2 * kFrontB);
   float* part = reinterpret_cast<float*>(bufB);                                      // partial tiles (after the MFMAs): 32 KB
+  int32_t* idxs = reinterpret_cast<int32_t*>(front_smem + kFrontLds);                // GATHER: [64][K] fused rows of the block
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, lh = lane >> 5;
   const int c = t & 63, rq = t >> 6;
   const int r0 = blockIdx.x * a.rows_per_chunk, r1 = min(B, r0 + a.rows_per_chunk);
@@ -488,7 +499,22 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
   const int pn = (wave >> 1) * 32 + li;                         // this lane's projection column
   const float bp = pn < h0 ? f.b_proj[pn] : 0.f;
   float x0 = 0.f, s = 0.f, q = 0.f, cnt = 0.f;
+  const int gK = GATHER ? f.K : 0, gE = GATHER ? f.E : 8, gsh = __builtin_ctz(gE), gke = kx - h0;
+  // GATHER: where this thread's piece `ps` of block stage `st` lies in the table (a dead piece -- below h0 or past kx -- reads
+  // the piece of the sample's first key at the lane's own column: a live address, never ONE for the whole grid)
+  auto gather_src = [&](int st, int ps) -> const float4* {
+    const int kr = 128 * st + xk - h0;
+    const int kk = (kr >= 0 && kr < gke) ? kr : (xk & (gE - 1));
+    const int64_t row = idxs[(xrow + 32 * ps) * gK + (kk >> gsh)];
+    return reinterpret_cast<const float4*>(f.table + row * gE + (kk & (gE - 1)));
+  };
   for (int b0 = r0; b0 < r1; b0 += 64) {
+    int32_t gi[4];                                          // GATHER: the block's fused rows, 512 per pass (past the batch: its last row's last key)
+    if (GATHER) {
+      const int64_t g0 = (int64_t)b0 * gK, glast = (int64_t)B * gK - 1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gi[j] = f.rows[min(g0 + min(t + 512 * j, 64 * gK - 1), glast)];
+    }
     // ---- everything that can be requested now: the projection's two stages, the block GEMM's first three ----
     constexpr int NPB = W16 ? 4 : 8, NQB = W16 ? 2 : 4;     // weight pieces per thread and stage: projection / block
     float4 pa[2][4], pb[2][NPB];                            // (W16: the float4 holds 8 bf16 -- moved, never computed on)
@@ -509,8 +535,16 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
       for (int ps = 0; ps < NPB; ++ps) pb[st][ps] = W16 ? front_ld<float4>(f.w_proj16, ob[ps] + ko16) : front_ld<float4>(f.w_proj, ob[ps] + ko);
     }
     uint4 qa[3][2];
+    float4 qg[3][2][2];                                     // GATHER: the x pieces as the f32 they are gathered from
     float4 qb[3][NQB];
     uint32_t ox[2], ow[NQB];
+    if (GATHER) {                                           // the index tile: every gather of this block reads it
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (t + 512 * j < 64 * gK) idxs[t + 512 * j] = gi[j];
+      for (int i = t + 2048; i < 64 * gK; i += 512) idxs[i] = f.rows[min((int64_t)b0 * gK + i, (int64_t)B * gK - 1)];   // (K > 32)
+      __syncthreads();
+    }
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) ox[ps] = (uint32_t)(min(b0 + xrow + 32 * ps, B - 1) * (int)f.ldx + xkb) * 2u;
 #pragma unroll
@@ -520,7 +554,17 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
     for (int u = 0; u < 2; ++u) {
       const int ka = 128 * u + xk, kb = 128 * u + fk;
 #pragma unroll
-      for (int ps = 0; ps < 2; ++ps) qa[u][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 256u * u : 0u));
+      for (int ps = 0; ps < 2; ++ps) {
+        if (GATHER) {
+          qg[u][ps][0] = qg[u][ps][1] = float4{0.f, 0.f, 0.f, 0.f};
+          if (128 * u + 128 > h0) {                         // (a stage wholly below h0 is the projection tile's: nothing to gather)
+            const float4* src = gather_src(u, ps);
+            qg[u][ps][0] = src[0]; qg[u][ps][1] = src[1];
+          }
+        } else {
+          qa[u][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 256u * u : 0u));
+        }
+      }
 #pragma unroll
       for (int ps = 0; ps < NQB; ++ps)
         qb[u][ps] = W16 ? front_ld<float4>(f.w16, ow[ps] + (ka < kx ? 256u * u : 0u)) : front_ld<float4>(f.w, ow[ps] + (kb < kx ? 512u * u : 0u));
@@ -546,7 +590,14 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
       {                                                     // third block stage, into the registers the projection just freed
         const int ka = 256 + xk, kb = 256 + fk;
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps) qa[2][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 512u : 0u));
+        for (int ps = 0; ps < 2; ++ps) {
+          if (GATHER) {
+            const float4* src = gather_src(2, ps);
+            qg[2][ps][0] = src[0]; qg[2][ps][1] = src[1];
+          } else {
+            qa[2][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 512u : 0u));
+          }
+        }
 #pragma unroll
         for (int ps = 0; ps < NQB; ++ps)
           qb[2][ps] = W16 ? front_ld<float4>(f.w16, ow[ps] + (ka < kx ? 512u : 0u)) : front_ld<float4>(f.w, ow[ps] + (kb < kx ? 1024u : 0u));
@@ -591,8 +642,22 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
           __bf16* A = bufA + (st & 1) * 64 * kFS;
           __bf16* Bm = bufB + (st & 1) * 128 * kFS;
 #pragma unroll
-          for (int ps = 0; ps < 2; ++ps)
-            *reinterpret_cast<uint4*>(A + (xrow + 32 * ps) * kFS + xk) = (128 * st + xk < kx) ? qa[u][ps] : uint4{0u, 0u, 0u, 0u};
+          for (int ps = 0; ps < 2; ++ps) {
+            if (GATHER) {                                   // rounded and packed as lookup_wave_kernel's 32-byte lanes do; this thread owns the piece of x
+              const float4 lo = qg[u][ps][0], hi = qg[u][ps][1];
+              const bool live = 128 * st + xk >= h0 && 128 * st + xk < kx;
+              uint4 o;
+              o.x = (uint32_t)tt_f2bf(lo.x) | ((uint32_t)tt_f2bf(lo.y) << 16);
+              o.y = (uint32_t)tt_f2bf(lo.z) | ((uint32_t)tt_f2bf(lo.w) << 16);
+              o.z = (uint32_t)tt_f2bf(hi.x) | ((uint32_t)tt_f2bf(hi.y) << 16);
+              o.w = (uint32_t)tt_f2bf(hi.z) | ((uint32_t)tt_f2bf(hi.w) << 16);
+              *reinterpret_cast<uint4*>(A + (xrow + 32 * ps) * kFS + xk) = live ? o : uint4{0u, 0u, 0u, 0u};
+              if (live && b0 + xrow + 32 * ps < r1)
+                *reinterpret_cast<uint4*>(f.x + (int64_t)(b0 + xrow + 32 * ps) * f.ldx + 128 * st + xk) = o;
+            } else {
+              *reinterpret_cast<uint4*>(A + (xrow + 32 * ps) * kFS + xk) = (128 * st + xk < kx) ? qa[u][ps] : uint4{0u, 0u, 0u, 0u};
+            }
+          }
 #pragma unroll
           for (int ps = 0; ps < NQB; ++ps) {
             if (W16) *reinterpret_cast<float4*>(Bm + (xrow + 32 * ps) * kFS + xk) = (128 * st + xk < kx) ? qb[u][ps] : float4{0.f, 0.f, 0.f, 0.f};
@@ -602,7 +667,14 @@ __global__ __launch_bounds__(kFrontThreads) void tower_front_kernel(Batch<FrontA
           {                                                 // three stages ahead, into the registers just stored
             const int ka = 128 * (st + 3) + xk, kb = 128 * (st + 3) + fk;
 #pragma unroll
-            for (int ps = 0; ps < 2; ++ps) qa[u][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 256u * (uint32_t)(st + 3) : 0u));
+            for (int ps = 0; ps < 2; ++ps) {
+              if (GATHER) {
+                const float4* src = gather_src(st + 3, ps);
+                qg[u][ps][0] = src[0]; qg[u][ps][1] = src[1];
+              } else {
+                qa[u][ps] = front_ld<uint4>(f.x, ox[ps] + (ka < kx ? 256u * (uint32_t)(st + 3) : 0u));
+              }
+            }
 #pragma unroll
             for (int ps = 0; ps < NQB; ++ps)
               qb[u][ps] = W16 ? front_ld<float4>(f.w16, ow[ps] + (ka < kx ? 256u * (uint32_t)(st + 3) : 0u))
@@ -1459,6 +1531,26 @@ inline bool front_fusable(int n, const tt_tower_params* const* P, const tt_tower
   }
   return true;
 }
+// the front reads bf16 shadows of both weights (its one block is block 0)
+inline bool front_w16(const tt_tower_params* p) {
+  return p->w_proj_bf16 && p->w_bf16[0] && tt_aligned(p->w_proj_bf16, 16) && tt_aligned(p->w_bf16[0], 16);
+}
+inline bool wants_gather(const tt_tower_acts* a) { return a->gather_table || a->gather_rows || a->gather_K || a->gather_E; }
+// the gathering front (tower_front_kernel<true, true>): the one-launch front of a whole training pass on bf16 shadows, every
+// tower with a table of 16-byte-aligned rows of E = 8, 16, ... 256 floats (a 16-byte piece of x never straddles two rows), its
+// fused rows, x[:, h0:] exactly K rows wide and an index tile that fits behind the kernel's own LDS
+inline bool front_gathers(int n, const tt_tower_params* const* P, const tt_tower_acts* const* A, int64_t B, int train) {
+  if (B < 1 || !tail_fusable(n, P, train) || !front_fusable(n, P, A)) return false;
+  for (int t = 0; t < n; ++t) {
+    const tt_tower_params* p = P[t]; const tt_tower_acts* a = A[t];
+    if (p->sync_phase != 0 || (p->flags & TT_TOWER_UNFUSED_GATHER) || !front_w16(p)) return false;
+    if (!a->gather_table || !a->gather_rows || !tt_aligned(a->gather_table, 16) || !tt_aligned(a->gather_rows, 4)) return false;
+    const int K = a->gather_K, E = a->gather_E;
+    if (K < 1 || E < 8 || E > 256 || (E & (E - 1)) != 0 || (int64_t)K * E != p->kcat_e) return false;
+    if (kFrontLds + 64 * (int64_t)K * (int64_t)sizeof(int32_t) > kFrontLdsMax) return false;
+  }
+  return true;
+}
 // the wide forward tail (tail_fwd_wide_kernel): training, bf16 operands, last hidden width <= 256, output <= 128 -- shapes the
 // narrow fused tail does not take
 inline bool wide_tail_ok(int n, const tt_tower_params* const* P, int train) {
@@ -1722,20 +1814,27 @@ inline Batch<TailFwdArgs> tail_fwd_args(const Pass& p, int i, const Batch<BnStat
 }
 // The fused narrow tail (tail_fusable) from block i's pre-activations -- or, behind a split-K block GEMM, its slabs `nd` -- to the
 // unit rows: the chunk statistics in the same pass as slabs (+ bias) -> pre, then everything else in one kernel.  Ends the pass.
-int fwd_narrow_tail(const Pass& p, int i, Batch<BnStatArgs>& bs, const NtDeferred* nd, bool front, const BlockDims& dim) {
+int fwd_narrow_tail(const Pass& p, int i, Batch<BnStatArgs>& bs, const NtDeferred* nd, bool front, bool gather, const BlockDims& dim) {
   tt_ctx* ctx = p.ctx; hipStream_t st = p.st; const int n = p.n;
   if (p.phase != 2) {
     if (front) {                                      // projection + block Linear + chunk statistics in one launch
       Batch<FrontArgs> fb{};
       bool w16 = true;                                // every tower brings bf16 shadows of both weights (16-byte aligned)
+      int kmax = 0;
       for (int t = 0; t < n; ++t) {
         const tt_tower_params* P = p.P[t]; const tt_tower_acts* A = p.A[t];
         const int wx = P->h0 + P->kcat_e;
         fb.a[t] = FrontArgs{A->dense, P->din, P->din, P->w_proj, P->b_proj, P->h0, reinterpret_cast<uint16_t*>(A->x), wx, wx, P->w[i], P->b[i],
-                            A->pre[i], bs.a[t], reinterpret_cast<const uint16_t*>(P->w_proj_bf16), reinterpret_cast<const uint16_t*>(P->w_bf16[i])};
-        w16 = w16 && P->w_proj_bf16 && P->w_bf16[i] && tt_aligned(P->w_proj_bf16, 16) && tt_aligned(P->w_bf16[i], 16);
+                            A->pre[i], bs.a[t], reinterpret_cast<const uint16_t*>(P->w_proj_bf16), reinterpret_cast<const uint16_t*>(P->w_bf16[i]),
+                            A->gather_table, A->gather_rows, A->gather_K, A->gather_E};
+        w16 = w16 && front_w16(P);
+        kmax = A->gather_K > kmax ? A->gather_K : kmax;
       }
-      if (w16) {
+      if (gather) {                                   // (front_gathers: every tower brings shadows, rows and a table)
+        const int lds = kFrontLds + 64 * kmax * (int)sizeof(int32_t);     // + the index tile of the tower with the most keys
+        TT_LDS_ONCE(kFrontLdsMax, tower_front_kernel<true, true>);
+        tower_front_kernel<true, true><<<dim3((unsigned)dim.cmax, (unsigned)n), kFrontThreads, lds, st>>>(fb);
+      } else if (w16) {
         TT_LDS_ONCE(kFrontLds, tower_front_kernel<true>);
         tower_front_kernel<true><<<dim3((unsigned)dim.cmax, (unsigned)n), kFrontThreads, kFrontLds, st>>>(fb);
       } else {
@@ -1906,6 +2005,12 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
   const int nh = p.nh, phase = p.phase;
   const bool fused = tail_fusable(n, P, train);
   const bool front = fused && front_fusable(n, P, A);    // projection + block Linear + chunk statistics in one launch
+  const bool gather = front_gathers(n, P, A, B, train);  // ... and the embedding rows of x gathered in it
+  for (int t = 0; t < n && !gather; ++t)                 // nobody else fills x[:, h0:]: the caller asks tt_towers_fwd_gathers first
+    if (wants_gather(A[t])) {
+      tt_set_error("tt_towers_mlp_fwd: gather fields set on a pass that cannot gather (tt_towers_fwd_gathers says which can)");
+      return TT_ERR_UNSUPPORTED;
+    }
   if (phase != 2 && !front) {
     GemmNT nt[TT_MAX_SIDES];                              // x[:, 0:h0] = dense W_proj^T + b_proj        (base_tower.py:133)
     for (int t = 0; t < n; ++t) {
@@ -1926,7 +2031,7 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     const BlockDims dim = block_dims(p, i);
     if (phase != 2 && !(front && tail))
       if (int rc = launch_layer_nt(p, i, tail ? nd : nullptr)) return rc;
-    if (tail) return fwd_narrow_tail(p, i, bs, nd, front, dim);
+    if (tail) return fwd_narrow_tail(p, i, bs, nd, front, gather, dim);
     if (train) {
       if (phase != 2) {
         bn_stats_partial_kernel<<<dim3((unsigned)tt_cdiv(dim.hmax, 64), (unsigned)dim.cmax, (unsigned)n), kThreads, 0, st>>>(bs);
@@ -1954,6 +2059,15 @@ int tt_towers_mlp_fwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, c
     if (A[t]->emb_packed)
       if (int rc = tt_score_pack_bf16(ctx, A[t]->emb, B, P[t]->d_out, A[t]->emb_pack_scale, A[t]->emb_packed, stream)) return rc;
   return TT_OK;
+}
+
+int tt_towers_fwd_gathers(int32_t n, const tt_tower_params* const* P, const tt_tower_acts* const* A, int64_t B, int32_t train) {
+  if (n < 1 || n > TT_MAX_SIDES || !P || !A) return 0;
+  for (int t = 0; t < n; ++t)
+    if (!P[t] || !A[t] || P[t]->n_hidden < 0 || P[t]->n_hidden > TT_MAX_HIDDEN || !A[t]->dense || !A[t]->x) return 0;
+  for (int t = 0; t < n; ++t)
+    if (P[t]->n_hidden != P[0]->n_hidden || P[t]->compute_dtype != P[0]->compute_dtype) return 0;
+  return front_gathers(n, P, A, B, train) ? 1 : 0;
 }
 
 int tt_towers_mlp_bwd(tt_ctx* ctx, int32_t n, const tt_tower_params* const* P, const tt_tower_acts* const* A,

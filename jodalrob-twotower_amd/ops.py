@@ -449,6 +449,14 @@ def towers_fwd(params_list, acts_list, B, train, p_drop, seed, dev, seed_dev=Non
                                            L.stream(dev)), "tt_towers_mlp_fwd")
 
 
+def towers_fwd_gathers(params_list, acts_list, B, train) -> bool:
+    """tt_towers_fwd_gathers: will towers_fwd / tower_fwd on these arguments (gather fields filled) gather the embedding rows itself?"""
+    n = len(params_list)
+    P = (C.POINTER(L.TowerParams) * n)(*[C.pointer(p) for p in params_list])
+    A = (C.POINTER(L.TowerActs) * n)(*[C.pointer(a) for a in acts_list])
+    return bool(L.load().tt_towers_fwd_gathers(n, P, A, B, int(train)))
+
+
 def towers_bwd(params_list, acts_list, d_embs, grads_list, B, train, p_drop, seed, dev, seed_dev=None):
     n = len(params_list)
     _, wptrs, wsizes = _tower_workspaces(params_list, B, dev)

@@ -47,6 +47,42 @@ def _al(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def _one_call(sides, key) -> bool:
+    """Several towers that share B, depth and key(side) run as one fused call (_run_pass)"""
+    return len(sides) > 1 and len({(s.B, s.tower.n_hidden) + key(s) for s in sides}) == 1
+
+
+def _fwd_key(s):
+    """What the towers of one fused forward call must share, besides B and depth"""
+    return (s.train, s.p_drop)
+
+
+def _front_gathers(group, live, store, sm, B) -> bool:
+    """The towers' forward gathers the embedding rows of this store's sides inside its one-launch front, from the hand-over
+    launch's slot-order rows `sm`: when settings.front_gather is on, the sides are exactly the towers of ONE forward call and
+    the library says it will (tt_towers_fwd_gathers -- the shapes are its business).  Fills the gather fields of the sides'
+    activation structs; the caller then launches no lookup."""
+    sides = [g[0] for g in group]
+    if not all(s.tower.front_gather for s in sides) or any(g[2] for g in group) or len(sides) != len(live) or any(a is not b for a, b in zip(sides, live)):
+        return False
+    if _sync_comm(live) is not None or not (len(live) == 1 or _one_call(live, _fwd_key)):
+        return False
+    Ks = [len(s.tower.categorical_embedder.keys) for s in sides]
+    if sm.dtype != torch.int32 or not sm.is_contiguous() or sm.numel() != B * sum(Ks) or sm.device != store.weight.device or not store.weight.is_contiguous():
+        return False
+    base = 0
+    for s, K in zip(sides, Ks):
+        a = s.acts_struct
+        a.gather_table, a.gather_rows, a.gather_K, a.gather_E = store.weight.data_ptr(), sm.data_ptr() + 4 * base, K, store.weight.shape[1]
+        base += B * K
+    if ops.towers_fwd_gathers([s.tower._params() for s in sides], [s.acts_struct for s in sides], B, sides[0].train):
+        return True
+    for s in sides:
+        a = s.acts_struct
+        a.gather_table, a.gather_rows, a.gather_K, a.gather_E = None, None, 0, 0
+    return False
+
+
 def _run_pass(items, one, many, key, sync):
     """The dispatch of a tower pass, forward or backward, over items = (side, *that side's arguments of the C call): SyncBN in
     two calls around ONE all-gather (twotower.h: sync_phase); one fused call (horizontal fusion: one launch per layer step covers
@@ -56,7 +92,7 @@ def _run_pass(items, one, many, key, sync):
     rank order).  A batched call runs on the first side's seed, which every side then takes.  Returns the SyncBN buffers or None."""
     sides = [it[0] for it in items]
     comm = _sync_comm(sides)
-    if comm is None and not (len(sides) > 1 and len({(s.B, s.tower.n_hidden) + key(s) for s in sides}) == 1):
+    if comm is None and not _one_call(sides, key):
         for s, *args in items:
             one(s.tower._params(), *args, s.B, s.train, s.p_drop, s.seed, s.emb.device, s.tower._seed_dev)
         return None
@@ -116,6 +152,7 @@ class BaseTower(nn.Module):
         self.dx_dtype = torch.bfloat16 if io in ("dx", "both") else torch.float32
         # the fused launches against the separate kernels they replaced (tests): config.Settings
         self.unfused_tail, self.unfused_front, self.unfused_back = settings.tower_unfused_tail, settings.tower_unfused_front, settings.tower_unfused_back
+        self.front_gather = settings.front_gather    # a captured step's forward gathers the embedding rows in its front launch (_front_gathers)
         self.categorical_keys = list(categorical_keys)
         self.exchange = None            # set by the distributed task: sharded-table row exchange
         self.sync_comm = None           # set by the distributed task (sync_bn=True): BN statistics over all ranks' rows
@@ -173,7 +210,7 @@ class BaseTower(nn.Module):
         for lin, bn in zip(lins, bns):
             tensors += [lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
         w16 = self._w16
-        key = tuple(t.data_ptr() for t in tensors) + tuple(b.num_batches_tracked.data_ptr() for b in bns) + (self.mlp_dtype, self.x_dtype, self.dx_dtype, self.unfused_tail, self.unfused_front, self.unfused_back) + \
+        key = tuple(t.data_ptr() for t in tensors) + tuple(b.num_batches_tracked.data_ptr() for b in bns) + (self.mlp_dtype, self.x_dtype, self.dx_dtype, self.unfused_tail, self.unfused_front, self.unfused_back, self.front_gather) + \
             ((w16[0].data_ptr(),) + tuple(w.data_ptr() for w in w16[1]) if w16 is not None else ())
         if key != self._struct_key:
             for t in tensors:
@@ -189,7 +226,7 @@ class BaseTower(nn.Module):
                 compute_dtype=ops.TT_BF16 if self.mlp_dtype == "bf16" else ops.TT_F32,
                 x_dtype=ops.TT_BF16 if self.x_dtype == torch.bfloat16 else ops.TT_F32,
                 dx_dtype=ops.TT_BF16 if self.dx_dtype == torch.bfloat16 else ops.TT_F32,
-                flags=(ops.L.TT_TOWER_UNFUSED_TAIL if self.unfused_tail else 0) | (ops.L.TT_TOWER_UNFUSED_FRONT if self.unfused_front else 0) | (ops.L.TT_TOWER_UNFUSED_BACK if self.unfused_back else 0),
+                flags=(ops.L.TT_TOWER_UNFUSED_TAIL if self.unfused_tail else 0) | (ops.L.TT_TOWER_UNFUSED_FRONT if self.unfused_front else 0) | (ops.L.TT_TOWER_UNFUSED_BACK if self.unfused_back else 0) | (0 if self.front_gather else ops.L.TT_TOWER_UNFUSED_GATHER),
                 w_proj_bf16=None if w16 is None else w16[0], w_bf16=() if w16 is None else w16[1])
             self._struct_key = key
         return self._params_struct
@@ -336,6 +373,7 @@ class _TowersFn(torch.autograd.Function):
                 lookups.setdefault(id(emb.store), []).append((s, emb.lookup_side(values, s.x[:, tw.tower_hidden_dims[0]:]), px is not None))
         # fused lookup (+ duplicate-row plan when a backward will follow) per store
         plans = []
+        live = [s for s in sides if s.B]
         exch = towers[0].exchange
         ctx.exch, ctx.exch_state = exch, None
         if exch is not None:            # sharded table: ids -> owners, pooled rows <- owners (distributed.py)
@@ -360,8 +398,9 @@ class _TowersFn(torch.autograd.Function):
             if all(g[2] for g in group) and km is not None:
                 rows = None                             # the hand-over launch has filled x already (tt_batch_ingest_lookup)
             elif sm is not None and store.weight.shape[1] % 4 == 0 and all(g[1].out.stride(0) % 4 == 0 for g in group):
-                rows = None                             # ... or left the clamped fused rows in slot order: no id decoding here
-                ops.embed_lookup_rows(store.weight, sm, [g[1] for g in group], B)
+                rows = None                             # ... or left the clamped fused rows in slot order: no id decoding here,
+                if not _front_gathers(group, live, store, sm, B):     # and no launch where the towers' front gathers from them itself
+                    ops.embed_lookup_rows(store.weight, sm, [g[1] for g in group], B)
             else:
                 rows = ops.embed_lookup(store.weight, [g[1] for g in group], B, want_rows=grad_on and km is None)
             plans.append([store, [g[0] for g in group], None, rows if km is None else km, grad_on, km is not None])
@@ -384,8 +423,7 @@ class _TowersFn(torch.autograd.Function):
                         plan = ops.dedup_plan(rows, store.rows)
                     plan.keep = rows                    # keep the sort input alive until it has run
                 pl[:] = [store, psides, plan]
-        live = [s for s in sides if s.B]
-        keep = _run_pass([(s, s.acts_struct) for s in live], ops.tower_fwd, ops.towers_fwd, lambda s: (s.train, s.p_drop),
+        keep = _run_pass([(s, s.acts_struct) for s in live], ops.tower_fwd, ops.towers_fwd, _fwd_key,
                          (1, "bn_sync_local", "bn_sync_all", "bn_sync_stride", 3))
         for s in live if keep else ():
             s.sync_keep = keep
