@@ -767,6 +767,55 @@ int tt_score_dir_bwd_pw(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra
                         float shift, int64_t diag_offset, const float* g, const int32_t* ent_n, const int32_t* ent_c,
                         const float* lq_a, const float* lq_b, const float* sumexp_a, const float* sumexp_b,
                         const float* d_loss, float scale, float* dA, tt_stream stream);
+/* ---- shared extra negatives of the in-batch softmax (mixed negative sampling, Yang et al. 2020; DPR / ANCE hard negatives) ------
+ * Besides the B company rows of its batch every notice is contrasted with M extra company rows X [M, D] (unit rows, this step's own
+ * tower outputs), shared by all rows: M more COLUMNS of the row-direction softmax.  The extras have no positive and stand in no
+ * column sum.  With S = N C^T / T, Z = N X^T / T and the fixed shift 1/T:
+ *   row logits R[a, b] = S[a, b] - lq_c[b], Rx[a, m] = Z[a, m] - lq_x[m];  column logits as before (S[a, b] - lq_n[a])
+ *   mask (ids given): in-batch pairs as the _mask entries; extra m is masked for row a iff ent_x[m] == ent_c[a] (the row's own
+ *   company or a repeat of it) -- notice ids play no part for extras
+ *   loss = 0.5 * [ mean_a (lse(R'[a, :] u Rx'[a, :]) - R[a, a]) + mean_b (lse_a C'[:, b] - C[b, b]) ]
+ *   W = softmax over the B + M row entries (first B columns) + softmax(C', 0) - 2 I;  Wx = that row softmax's last M columns
+ *   dN = (1/T)/(2B) (W C + Wx X),  dC = (1/T)/(2B) W^T N,  dX = (1/T)/(2B) Wx^T N
+ * Metrics: accuracy (out8[1]) and row_rank are over the B + M raw scores, the extras BEHIND every in-batch column (a tie with an
+ * extra does not beat the positive); positive / negative mean, gap, out8[6], colsum / inv_col and diag are the in-batch ones --
+ * colsum and diag bit for bit those of the same call without extras.  bf16 operands and the f32 parity path.
+ * Optional arguments: lq_n / lq_c (both or neither; then 2/T <= 40) with lq_x (NULL: the extras count as log q = 0); ent_n / ent_c
+ * (both or neither) with ent_x (NULL: no extra is ever masked).  NULL lq_* = uncorrected, NULL ent_* = unmasked.
+ *
+ * tt_score_fwd_sym_bf16_xneg: tt_score_fwd_sym_bf16 (/_lq /_mask) with ONE sweep launch whose company tiles run past the in-batch
+ * tiles into X_packed, a packed image of its own (tt_score_pack_bf16, scale 1) -- the extras start on a tile boundary whatever
+ * B mod 32 is.  rowsum / inv_row include the extras; w_x [round_up(M, 64)] (out, 16-byte aligned): the extras' sampling weights
+ * (1 without the correction, 0 past M) for the backward.  workspace: tt_score_fwd_sym_xneg_workspace_bytes(B, M, D).  Per-row
+ * arrays as the _lq / _mask entries; ent_x int32 [M], lq_x f32 [M].  Bitwise reproducible.
+ * tt_score_bwd_bf16_xneg: the extras' share of the backward, ONE launch over the two rectangular directions, after the square
+ * backward (tt_score_bwd_bf16 / _lq / _mask on that forward's sums, which stores dN and dC): dN += (1/T)/(2B) Wx X and
+ * dX = (1/T)/(2B) Wx^T N, weight of (a, m) = e_am w_x[m] inv_row[a], rounded to bf16 as the second MFMA operand.  ab_scale: the
+ * scale of the notice image (the extras' image is unscaled), divided out of dX.  inv_row [round_up(B, 32)], w_x [round_up(M, 32)]
+ * (16-byte aligned): that forward's; ent_c [round_up(B, 32)] / ent_x [round_up(M, 32)] (both or neither, 16-byte aligned, entries
+ * past the end ignored).  `scale` = inv_t / (2 B).  Never hosted by the towers' backward launch: a queued score backward is
+ * launched in front of it.
+ * f32 parity path: tt_score_dir_fwd_xneg adds the extras to the row direction of tt_score_dir_fwd (/_lq /_mask): sumexp[a] +=
+ * sum_m e_am w_m and rank[a] += #{m: s_am > diag[a]}, diag [B] that call's diagonal; then tt_score_loss_finish as before.
+ * tt_score_dir_bwd_xneg is one rectangular direction: x_is_b != 0: A = N [Ra = B], Bm = X [Rb = M] (ent_a = ent_c, ent_b = ent_x) ->
+ * dN's extra term (accumulate != 0: added to dA); x_is_b == 0: A = X, Bm = N (ent_a = ent_x, ent_b = ent_c) -> dX.  rowsum: the
+ * notice rows' sums (with the extras), lq_x the extras' log probabilities or NULL. */
+size_t tt_score_fwd_sym_xneg_workspace_bytes(int64_t B, int64_t M, int32_t D);
+int tt_score_fwd_sym_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* C_packed, const void* X_packed, int64_t B,
+                               int64_t M, int32_t D, float inv_t, float shift, float ab_scale, int32_t want_rank,
+                               const int32_t* ent_n, const int32_t* ent_c, const int32_t* ent_x, const float* lq_n,
+                               const float* lq_c, const float* lq_x, float* rowsum, float* colsum, float* inv_row,
+                               float* inv_col, float* w_n, float* w_c, float* w_x, float* diag, int32_t* row_rank, float* out8,
+                               float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream);
+int tt_score_bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed, int64_t B, int64_t M, int32_t D, float inv_t,
+                           float shift, float ab_scale, const float* inv_row, const float* w_x, const int32_t* ent_c,
+                           const int32_t* ent_x, const float* d_loss, float scale, float* dN, float* dX, tt_stream stream);
+int tt_score_dir_fwd_xneg(tt_ctx* ctx, const float* N, const float* X, int64_t B, int64_t M, int32_t D, float inv_t, float shift,
+                          const int32_t* ent_c, const int32_t* ent_x, const float* lq_x, const float* diag, float* sumexp,
+                          int32_t* rank, tt_stream stream);
+int tt_score_dir_bwd_xneg(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                          int32_t x_is_b, const int32_t* ent_a, const int32_t* ent_b, const float* lq_x, const float* rowsum,
+                          const float* d_loss, float scale, int32_t accumulate, float* dA, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

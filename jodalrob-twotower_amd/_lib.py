@@ -187,6 +187,12 @@ SIGNATURES = {
     "tt_score_bwd_bf16_pw": (C.c_int, [vp, C.POINTER(ScoreBwdDir), vp, vp, vp, C.POINTER(ScoreBwdLq), i32, i32, f32, f32, vp, f32, vp]),
     "tt_score_loss_finish_pw": (C.c_int, [vp, i64, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tt_score_dir_bwd_pw": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]),
+    "tt_score_fwd_sym_xneg_workspace_bytes": (sz, [i64, i64, i32]),
+    "tt_score_fwd_sym_bf16_xneg": (C.c_int, [vp, vp, vp, vp, i64, i64, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "tt_score_bwd_bf16_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, f32, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
+    "tt_score_dir_fwd_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_score_dir_bwd_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp]),
     "tt_score_matrix": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, vp, i64, vp]),
     "tt_score_dense_workspace_bytes": (sz, [i64, i32]),
     "tt_score_dense_fwd": (C.c_int, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp, vp]),

@@ -74,14 +74,20 @@ __device__ __forceinline__ float diag_score(const float* __restrict__ A, const f
 // LQ (tt_score_dir_fwd_lq): sumexp adds exp(s - shift) w_b, w_b = tt_lq_weight(lq_b[b]) the B row's sampling weight
 // MK (tt_score_dir_fwd_mask; square, diag_off == 0): a pair a != b whose rows share a notice or a company id adds nothing to sumexp;
 // the diagonal, the ranks and the score sums stay on the raw scores
-template <bool VEC, bool LQ = false, bool MK = false>
+// XN (tt_score_dir_fwd_xneg): the B rows are shared extra negatives -- rows without a positive.  The A rows' diagonals come IN
+// (diag_in, the in-batch direction's), sumexp and rank are ADDED to: sumexp[a] += sum_m e_am w_m, rank[a] += #{m: s_am > diag[a]} (an
+// extra sits behind every in-batch column: a tie does not beat the positive).  The mask (MK) is the company-only compare
+// ent_c[a] == ent_x[m]; LQ weighs with lq_b = the extras' log probabilities.  No diag, no score sum out.
+template <bool VEC, bool LQ = false, bool MK = false, bool XN = false>
 __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 float* __restrict__ sumexp, float* __restrict__ diag_out,
                                                                 int32_t* __restrict__ rank_out, float* __restrict__ sumscore,
                                                                 const float* __restrict__ lq_b = nullptr,
                                                                 const int32_t* __restrict__ ent_n = nullptr,
-                                                                const int32_t* __restrict__ ent_c = nullptr) {
+                                                                const int32_t* __restrict__ ent_c = nullptr,
+                                                                const int32_t* __restrict__ ent_x = nullptr,
+                                                                const float* __restrict__ diag_in = nullptr) {
   __shared__ float As[RB * LDK];
   __shared__ float Bs[CB * LDK];
   __shared__ float diag_s[RB];
@@ -94,6 +100,8 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
   const int nch = (D + DK - 1) / DK;
   if (t < RB) {
     const int64_t a = r0 + t, b = a + diag_off;
+    if constexpr (XN) diag_s[t] = a < Ra ? diag_in[a] : 0.f;
+    else
     diag_s[t] = (a < Ra && b >= 0 && b < Rb) ? diag_score(A, Bm, a, b, D, inv_t) : 0.f;
   }
   if (nch == 1) stage<RB, VEC>(A, Ra, D, r0, 0, As, t);
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t a = r0 + wr * 32 + rowmap(r, lh);
-      ean[r] = a < Ra ? ent_n[a] : 0;
+      ean[r] = (!XN && a < Ra) ? ent_n[a] : 0;
       eac[r] = a < Ra ? ent_c[a] : 0;
     }
   }
@@ -131,12 +139,21 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
       const bool cv = col < Rb;
       const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 1.f;
       [[maybe_unused]] int ebn = 0, ebc = 0;
-      if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
+      if constexpr (MK && XN) ebc = cv ? ent_x[col] : 0;
+      else if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float s = (h == 0 ? acc0[r] : acc1[r]) * inv_t;
         const int64_t pos = r0 + wr * 32 + rowmap(r, lh) + diag_off;
-        if constexpr (MK) {
+        if constexpr (XN) {
+          if (cv) {
+            float e = __expf(s - shift);
+            if constexpr (MK) e = eac[r] == ebc ? 0.f : e;
+            if constexpr (LQ) se[r] += e * wb;
+            else se[r] += e;
+            rk[r] += s > dg[r] ? 1 : 0;
+          }
+        } else if constexpr (MK) {
           // the plain instantiations' contractions written out (hipcc fuses s - shift and ss += s with the product s = acc / T there,
           // and does not behind the select here): an inert mask gives the plain entry's sums and metrics bit for bit
           if (cv) {
@@ -167,6 +184,13 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
     }
   }
   __syncthreads();
+  if constexpr (XN) {
+    if (t < RB && r0 + t < Ra) {
+      sumexp[r0 + t] += part_e[0][t] + part_e[1][t];       // (the in-batch sum first, then the extras')
+      rank_out[r0 + t] += part_r[0][t] + part_r[1][t];
+    }
+    return;
+  }
   if (t < RB && r0 + t < Ra) {
     sumexp[r0 + t] = part_e[0][t] + part_e[1][t];
     diag_out[r0 + t] = diag_s[t];
@@ -180,7 +204,11 @@ __global__ __launch_bounds__(kThreads) void score_dir_fwd_kernel(const float* __
 // MK (tt_score_dir_bwd_mask; square, diag_off == 0): a masked pair (score_dir_fwd_kernel) weighs nothing
 // PW (tt_score_dir_bwd_pw; square, diag_off == 0): per-pair sample weights g -- the reciprocals are g_a / sumexp_a and g_b / sumexp_b,
 // the diagonal's -2 is -2 g_a
-template <int NCH, bool VEC, bool LQ = false, bool MK = false, bool PW = false>
+// XN (tt_score_dir_bwd_xneg): one rectangular direction of the shared extra negatives -- rows without a positive and the one-sided
+// weight e_ab fa[a] fb[b]: on the side of the notices f = 1 / rowsum (sumexp_a or sumexp_b, the other NULL), on the side of the
+// extras f = their sampling weight (LQ: lq_a or lq_b, the other NULL) or 1.  MK: the company-only compare ent_n[a] == ent_c[b] (here
+// the A rows' and the B rows' company ids).  pw_g != NULL: dA += (dN's extra term, behind the square backward's).
+template <int NCH, bool VEC, bool LQ = false, bool MK = false, bool PW = false, bool XN = false>
 __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int64_t Ra,
                                                                 int64_t Rb, int D, float inv_t, float shift, int64_t diag_off,
                                                                 const float* __restrict__ sumexp_a, const float* __restrict__ sumexp_b,
@@ -202,6 +230,11 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t a = r0 + wr * 32 + rowmap(r, lh);
+    if constexpr (XN) {
+      ia[r] = a < Ra ? (sumexp_a ? 1.f / sumexp_a[a] : ((LQ && lq_a) ? tt_lq_weight(lq_a[a]) : 1.f)) : 0.f;
+      if constexpr (MK) ean[r] = a < Ra ? ent_n[a] : 0;
+      continue;
+    }
     ia[r] = a < Ra ? 1.f / sumexp_a[a] : 0.f;
     if constexpr (PW) { ga[r] = a < Ra ? pw_g[a] : 0.f; ia[r] *= ga[r]; }
     if constexpr (LQ) ua[r] = a < Ra ? tt_lq_weight(lq_a[a]) : 0.f;
@@ -230,16 +263,25 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
       const int cl = wc * 64 + h * 32 + li;
       const int64_t col = c0 + cl;
       const bool cv = col < Rb;
-      float ib = cv ? 1.f / sumexp_b[col] : 0.f;
+      float ib;
+      if constexpr (XN) ib = cv ? (sumexp_b ? 1.f / sumexp_b[col] : ((LQ && lq_b) ? tt_lq_weight(lq_b[col]) : 1.f)) : 0.f;
+      else ib = cv ? 1.f / sumexp_b[col] : 0.f;
       if constexpr (PW) ib *= cv ? pw_g[col] : 0.f;
-      const float wb = LQ && cv ? tt_lq_weight(lq_b[col]) : 0.f;
+      const float wb = (LQ && !XN && cv) ? tt_lq_weight(lq_b[col]) : 0.f;
       [[maybe_unused]] int ebn = 0, ebc = 0;
-      if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
+      if constexpr (MK && XN) ebc = cv ? ent_c[col] : 0;
+      else if constexpr (MK) { ebn = cv ? ent_n[col] : 0; ebc = cv ? ent_c[col] : 0; }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 32 + rowmap(r, lh);
         const float s = (h == 0 ? acc0[r] : acc1[r]) * inv_t;
         float w = 0.f;
+        if constexpr (XN) {
+          if (cv) {
+            w = __expf(s - shift) * (ia[r] * ib);
+            if constexpr (MK) { if (ean[r] == ebc) w = 0.f; }
+          }
+        } else
         if (cv) {
           if constexpr (LQ) w = __expf(s - shift) * (wb * ia[r] + ua[r] * ib);
           else w = __expf(s - shift) * (ia[r] + ib);
@@ -281,6 +323,12 @@ __global__ __launch_bounds__(kThreads) void score_dir_bwd_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t a = r0 + wr * 32 + rowmap(r, lh);
+      if constexpr (XN) {
+        if (a < Ra && d < D) {
+          const float v = dacc[ch][r] * g;
+          dA[a * D + d] = pw_g ? dA[a * D + d] + v : v;
+        }
+      } else
       if (a < Ra && d < D) dA[a * D + d] = dacc[ch][r] * g;
     }
   }
@@ -818,6 +866,63 @@ int tt_score_dir_bwd_mask(tt_ctx* ctx, const float* A, const float* Bm, int64_t 
   }
   if (int rc = mask_dir_check("tt_score_dir_bwd_mask", Ra, Rb, diag_offset, inv_t, lq_a != nullptr)) return rc;
   return dir_bwd(A, Bm, Ra, Rb, D, inv_t, shift, diag_offset, lq_a, lq_b, sumexp_a, sumexp_b, d_loss, scale, dA, stream, ent_n, ent_c);
+}
+
+// the extra-negative entries of the f32 parity path (include/twotower.h): rows without a positive, the company-only mask
+int tt_score_dir_fwd_xneg(tt_ctx* ctx, const float* N, const float* X, int64_t B, int64_t M, int32_t D, float inv_t, float shift,
+                          const int32_t* ent_c, const int32_t* ent_x, const float* lq_x, const float* diag, float* sumexp,
+                          int32_t* rank, tt_stream stream) {
+  TT_CHECK_ARG(ctx && N && X && diag && sumexp && rank, "tt_score_dir_fwd_xneg: NULL argument");
+  TT_CHECK_ARG(B >= 1 && M >= 1 && D >= 1, "tt_score_dir_fwd_xneg: bad shape");
+  TT_CHECK_ARG(B < ((int64_t)1 << 31) && M < ((int64_t)1 << 31), "tt_score_dir_fwd_xneg: too many rows");
+  TT_CHECK_ARG((ent_c != nullptr) == (ent_x != nullptr), "tt_score_dir_fwd_xneg: ent_c and ent_x go together");
+  if (2.f * fabsf(inv_t) > (lq_x ? kLqMaxTwoInvT : 80.f)) {
+    tt_set_error("tt_score_dir_fwd_xneg: 1/temperature = %g: needs 2/T <= %g", inv_t, lq_x ? kLqMaxTwoInvT : 80.f);
+    return TT_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  tt_dispatch([&](auto vec, auto lq, auto mk) {
+    score_dir_fwd_kernel<vec, lq, mk, true><<<(unsigned)tt_cdiv(B, RB), kThreads, 0, st>>>(N, X, B, M, D, inv_t, shift, 0, sumexp, nullptr, rank,
+                                                                                          nullptr, lq_x, nullptr, ent_c, ent_x, diag);
+  }, vec_ok(N, D) && vec_ok(X, D), lq_x != nullptr, ent_c != nullptr);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+int tt_score_dir_bwd_xneg(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
+                          int32_t x_is_b, const int32_t* ent_a, const int32_t* ent_b, const float* lq_x, const float* rowsum,
+                          const float* d_loss, float scale, int32_t accumulate, float* dA, tt_stream stream) {
+  TT_CHECK_ARG(ctx && A && Bm && rowsum && d_loss && dA, "tt_score_dir_bwd_xneg: NULL argument");
+  TT_CHECK_ARG(Ra >= 1 && Rb >= 1 && D >= 1, "tt_score_dir_bwd_xneg: bad shape");
+  TT_CHECK_ARG((ent_a != nullptr) == (ent_b != nullptr), "tt_score_dir_bwd_xneg: ent_a and ent_b go together");
+  if (D > 4 * DK) {
+    tt_set_error("tt_score_dir_bwd_xneg: D=%d > %d not supported", D, 4 * DK);
+    return TT_ERR_UNSUPPORTED;
+  }
+  if (2.f * fabsf(inv_t) > (lq_x ? kLqMaxTwoInvT : 80.f)) {
+    tt_set_error("tt_score_dir_bwd_xneg: 1/temperature = %g: needs 2/T <= %g", inv_t, lq_x ? kLqMaxTwoInvT : 80.f);
+    return TT_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float* const se_a = x_is_b ? rowsum : nullptr;     // the notices' side carries the reciprocal, the extras' side the weight
+  const float* const se_b = x_is_b ? nullptr : rowsum;
+  const float* const lq_a = x_is_b ? nullptr : lq_x;
+  const float* const lq_b = x_is_b ? lq_x : nullptr;
+  const float* const acc_flag = accumulate ? d_loss : nullptr;   // (the kernel's pw_g slot: non-NULL = add to dA)
+  const auto go = [&](auto nch) {
+    tt_dispatch([&](auto vec, auto lq, auto mk) {
+      score_dir_bwd_kernel<nch, vec, lq, mk, false, true><<<(unsigned)tt_cdiv(Ra, RB), kThreads, 0, st>>>(
+          A, Bm, Ra, Rb, D, inv_t, shift, 0, se_a, se_b, d_loss, scale, dA, lq_a, lq_b, ent_a, ent_b, acc_flag);
+    }, vec_ok(A, D) && vec_ok(Bm, D), lq_x != nullptr, ent_a != nullptr);
+  };
+  switch ((D + DK - 1) / DK) {
+    case 1: go(tt_c<1>); break;
+    case 2: go(tt_c<2>); break;
+    case 3: go(tt_c<3>); break;
+    default: go(tt_c<4>); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
 }
 
 // the pair-weight entries of the f32 parity path: g from tt_score_prepare_pw; ids and logQ vectors optional

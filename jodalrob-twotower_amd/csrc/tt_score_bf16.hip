@@ -605,6 +605,171 @@ __global__ __launch_bounds__(NW * 64) void score_bwd_bf16_kernel(BwdArgs args) {
   }
 }
 
+// ---- backward of the shared extra negatives (tt_score_bwd_bf16_xneg): the b-split form over two RECTANGULAR directions ------------
+// Direction 0: the notice rows a against the extras m -> dN's extra term (added to what the square backward stored); direction 1: the
+// extras against the notice rows -> dX.  The weight of (a, m) is the one-sided case of softmax_term, e_am w_x[m] / rowsum_a: the
+// extras stand in no column sum, so there is no second reciprocal and nothing is loaded for it.  Per direction fa is the per-row
+// factor of its A rows and fb that of its B rows (direction 0: the forward's inv_row and w_x, direction 1 the other way round): the
+// weight is e fa fb in both.  No positive.  MK: a pair is masked iff the notice row's company id equals the extra's (ea / eb, loaded
+// behind the S product as ELATE does).  Sweep, tree and store as score_bwd_bf16_kernel's.
+struct XnegDir {
+  const __bf16* a_rows;
+  const __bf16* b_rows;
+  const __bf16* b_frag;
+  int Ra, Rb;
+  const float* fa;     // [Ra]
+  const float* fb;     // [round_up(Rb, 32)], 16-byte aligned
+  const int32_t* ea;   // (MK) [Ra]
+  const int32_t* eb;   // (MK) [round_up(Rb, 32)], 16-byte aligned
+  float* dA;
+  float out_scale;
+  int accumulate;      // dA += instead of dA =
+};
+struct XnegArgs {
+  XnegDir d[2];
+  float c1, c2;
+  const float* d_loss;
+  int D;
+};
+
+template <int KS, int AT, int NW, bool UNIT, bool MK>
+__global__ __launch_bounds__(NW * 64) void score_bwd_xneg_kernel(XnegArgs args) {
+  constexpr int Dp = KS * 16, ROWS = 32 * AT, DT = KS / 2;
+  __shared__ float red[(NW / 2) * ROWS * Dp];
+  const bool d1 = blockIdx.y != 0;
+  const __bf16* const a_rows = d1 ? args.d[1].a_rows : args.d[0].a_rows;
+  const __bf16* const b_rows = d1 ? args.d[1].b_rows : args.d[0].b_rows;
+  const __bf16* const b_frag = d1 ? args.d[1].b_frag : args.d[0].b_frag;
+  const float* const fa = d1 ? args.d[1].fa : args.d[0].fa;
+  const float* const fb = d1 ? args.d[1].fb : args.d[0].fb;
+  [[maybe_unused]] const int32_t* const ea = d1 ? args.d[1].ea : args.d[0].ea;
+  [[maybe_unused]] const int32_t* const eb = d1 ? args.d[1].eb : args.d[0].eb;
+  float* const dA = d1 ? args.d[1].dA : args.d[0].dA;
+  const float out_scale = d1 ? args.d[1].out_scale : args.d[0].out_scale;
+  const bool accumulate = (d1 ? args.d[1].accumulate : args.d[0].accumulate) != 0;
+  const int Ra = d1 ? args.d[1].Ra : args.d[0].Ra, Rb = d1 ? args.d[1].Rb : args.d[0].Rb;
+  const float c1 = args.c1, c2 = args.c2;
+  const int a0 = (int)blockIdx.x * ROWS;
+  if (a0 >= Ra) return;
+  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nT = (Rb + 31) / 32;
+  bf16x8 ares[AT][KS];
+  float ia[AT];
+  [[maybe_unused]] int eaa[AT];
+#pragma unroll
+  for (int i = 0; i < AT; ++i) {
+    load_bfrag<KS>(a_rows, a0 / 32 + i, c, h, ares[i]);
+    const int a = a0 + 32 * i + c;
+    ia[i] = a < Ra ? fa[a] : 0.f;
+    if constexpr (MK) eaa[i] = a < Ra ? ea[a] : 0;
+  }
+  f32x16 dacc[AT][DT];
+  zero_acc(dacc);
+  const int tlast = nT - 1;
+  auto compute = [&](const BwdTile<KS>& T, int t) {
+    const int b_lo = 32 * t;
+    float ib[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { ib[4 * q] = T.iv[q].x; ib[4 * q + 1] = T.iv[q].y; ib[4 * q + 2] = T.iv[q].z; ib[4 * q + 3] = T.iv[q].w; }
+    if (b_lo + 31 >= Rb) {                                     // the ragged last tile: rows past the end weigh nothing
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ib[r] = b_lo + rowmap(r, h) < Rb ? ib[r] : 0.f;
+    }
+    [[maybe_unused]] int ebb[16];
+#pragma unroll
+    for (int i = 0; i < AT; ++i) {
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.b[s], ares[i][s], acc, 0, 0, 0);
+      if constexpr (MK) {
+        if (i == 0) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int4 v = *reinterpret_cast<const int4*>(eb + b_lo + 4 * h + 8 * q);
+            ebb[4 * q] = v.x; ebb[4 * q + 1] = v.y; ebb[4 * q + 2] = v.z; ebb[4 * q + 3] = v.w;
+          }
+        }
+      }
+      float w[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = UNIT ? __builtin_amdgcn_exp2f(acc[r]) : __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], c1, c2));
+        w[r] = e * (ia[i] * ib[r]);
+        if constexpr (MK) w[r] = eaa[i] == ebb[r] ? 0.f : w[r];
+      }
+      bf16x8 wf[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wf[s][j] = (__bf16)w[8 * s + j];
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int d = 0; d < DT; ++d) dacc[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s], T.bm[s][d], dacc[i][d], 0, 0, 0);
+    }
+  };
+  BwdTile<KS> T0, T1;
+  if constexpr (KS == 16) {                                    // D = 256: one tile in flight, as the masked square form
+    for (int t = wave; t < nT; t += NW) {
+      bwd_tile_load<KS, false, false>(T0, b_rows, b_frag, fb, t, c, h);
+      compute(T0, t);
+    }
+  } else {
+    bwd_tile_load<KS, false, false>(T0, b_rows, b_frag, fb, min(wave, tlast), c, h);
+    __builtin_amdgcn_sched_barrier(0);
+    for (int t = wave; t < nT; t += 2 * NW) {
+      bwd_tile_load<KS, false, false>(T1, b_rows, b_frag, fb, min(t + NW, tlast), c, h);
+      compute(T0, t);
+      bwd_tile_load<KS, false, false>(T0, b_rows, b_frag, fb, min(t + 2 * NW, tlast), c, h);
+      if (t + NW < nT) compute(T1, t + NW);
+    }
+  }
+  // fixed-order tree over the NW waves: upper half writes, lower half adds
+#pragma unroll
+  for (int half = NW / 2; half >= 1; half >>= 1) {
+    if (wave >= half && wave < 2 * half) {
+      float* slab = red + (wave - half) * ROWS * Dp;
+#pragma unroll
+      for (int i = 0; i < AT; ++i)
+#pragma unroll
+        for (int d = 0; d < DT; ++d)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c] = dacc[i][d][r];
+    }
+    __syncthreads();
+    if (wave < half) {
+      const float* slab = red + wave * ROWS * Dp;
+#pragma unroll
+      for (int i = 0; i < AT; ++i)
+#pragma unroll
+        for (int d = 0; d < DT; ++d)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dacc[i][d][r] += slab[(32 * i + rowmap(r, h)) * Dp + 32 * d + c];
+    }
+    __syncthreads();
+  }
+  if (wave == 0) {
+    const float g = args.d_loss[0] * out_scale;
+#pragma unroll
+    for (int i = 0; i < AT; ++i)
+#pragma unroll
+      for (int d = 0; d < DT; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int a = a0 + 32 * i + rowmap(r, h);
+          const int dd = 32 * d + c;
+          if (a < Ra && dd < args.D) {
+            float* const p = dA + (int64_t)a * args.D + dd;
+            const float v = dacc[i][d][r] * g;
+            *p = accumulate ? *p + v : v;                      // (dN: the square backward's term first, then this one)
+          }
+        }
+  }
+}
+
 // ---- backward, b-split form with ONE streamed image (D <= 64) ---------------------------------------------------------
 // Ablations of the kernel above (compile-time, tools/bench_score.py, B = 8192, D = 64): full 50.0 us; without the exp2 45.9;
 // without the gradient MFMAs 35.7; without ANY MFMA or exp2 32.4 -- two thirds of the time is moving the opposite side's
@@ -1650,6 +1815,48 @@ static int bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g
   return TT_OK;
 }
 
+// tt_score_bwd_bf16_xneg: one launch of score_bwd_xneg_kernel over (N, X) -> dN += and (X, N) -> dX, on the masked launches' tiles.
+// Never queued for the towers' backward launch; a queued score backward goes in front of it (it stores the dN this launch adds to).
+static int bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed, int64_t B, int64_t M, int32_t D, float inv_t, float shift,
+                         float ab_scale, const float* inv_row, const float* w_x, const int32_t* ent_c, const int32_t* ent_x,
+                         const float* d_loss, float scale, float* dN, float* dX, tt_stream stream, const char* who) {
+  TT_CHECK_ARG(ctx && N_packed && X_packed && inv_row && w_x && d_loss && dN && dX, "%s: NULL argument", who);
+  TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && M >= 1 && M < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld M=%lld D=%d", who,
+               (long long)B, (long long)M, D);
+  TT_CHECK_ARG(tt_aligned(inv_row, 16) && tt_aligned(w_x, 16), "%s: inv_row / w_x must be 16-byte aligned", who);
+  TT_CHECK_ARG((ent_c != nullptr) == (ent_x != nullptr), "%s: ent_c and ent_x go together", who);
+  TT_CHECK_ARG(!ent_c || (tt_aligned(ent_c, 16) && tt_aligned(ent_x, 16)), "%s: ent_c / ent_x not 16-byte aligned", who);
+  if (2.f * fabsf(inv_t) > 80.f) {
+    tt_set_error("%s: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", who, inv_t);
+    return TT_ERR_UNSUPPORTED;
+  }
+  const float ab = ab_scale == 0.f ? 1.f : ab_scale;
+  const PackedView vn = view(N_packed, B, D), vx = view(X_packed, M, D);
+  XnegArgs a{};
+  a.d[0] = XnegDir{vn.rows, vx.rows, vx.frag, (int)B, (int)M, inv_row, w_x, ent_c, ent_x, dN, scale, 1};          // B image = X: unscaled
+  a.d[1] = XnegDir{vx.rows, vn.rows, vn.frag, (int)M, (int)B, w_x, inv_row, ent_x, ent_c, dX, scale / ab, 0};     // B image = the notices'
+  a.c1 = inv_t * kLog2e / ab;
+  a.c2 = -shift * kLog2e;
+  a.d_loss = d_loss;
+  a.D = D;
+  const bool unit = ab == inv_t * kLog2e;
+  const int64_t maxRa = B > M ? B : M;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
+  const auto go = [&](auto ks, auto at) {
+    const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * at), 2);
+    tt_dispatch([&](auto u, auto m) { score_bwd_xneg_kernel<ks, at, 4, u, m><<<grid, 4 * 64, 0, st>>>(a); }, unit, ent_c != nullptr);
+  };
+  switch (padded_d(D)) {
+    case 32: go(tt_c<2>, tt_c<2>); break;
+    case 64: go(tt_c<4>, tt_c<2>); break;
+    case 128: go(tt_c<8>, tt_c<1>); break;
+    default: go(tt_c<16>, tt_c<1>); break;
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 // tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq.
 // One form for every shape: the b-split kernel (the rows and fragment images streamed per wave, no LDS in the tile loop).  It
 // takes any B and D <= 256 with no operand staging of its own -- the transposing form's parked tiles (100 KB of LDS) and the
@@ -1701,6 +1908,13 @@ int tt_score_bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float*
                          const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
                          float scale, tt_stream stream) {
   return bwd_bf16_pw(ctx, dirs, g, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_pw");
+}
+
+int tt_score_bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed, int64_t B, int64_t M, int32_t D, float inv_t,
+                           float shift, float ab_scale, const float* inv_row, const float* w_x, const int32_t* ent_c,
+                           const int32_t* ent_x, const float* d_loss, float scale, float* dN, float* dX, tt_stream stream) {
+  return bwd_bf16_xneg(ctx, N_packed, X_packed, B, M, D, inv_t, shift, ab_scale, inv_row, w_x, ent_c, ent_x, d_loss, scale, dN, dX, stream,
+                       "tt_score_bwd_bf16_xneg");
 }
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,

@@ -68,6 +68,12 @@ struct SymArgs {
   const float* lq_c;
   const int32_t* ent_n;                // MK kernels: [R] notice / company ids of the rows (the same row stands for one pair)
   const int32_t* ent_c;
+  // XN kernels (tt_score_fwd_sym_bf16_xneg): Rx shared extra negatives, a packed image of their own -- workgroups blockIdx.x >= ngi
+  // sweep ITS tiles (nTx of them) against the notice tiles
+  const void* x_rows;
+  int Rx, nTx, ngi;
+  const float* lq_x;                   // [Rx] log sampling probabilities of the extras (LQ) or NULL: weight 1
+  const int32_t* ent_x;                // [Rx] company ids of the extras (MK) or NULL: never masked
 };
 
 // Notice tiles are staged through LDS once per WORKGROUP (all 8 waves sweep the same tiles I): read straight from L2 by
@@ -104,7 +110,13 @@ struct SymStage {
 // before it enters either sum; the maxima (ranks) and the diagonal stay on the raw scores.  The a rows' two ids ride in LDS behind
 // s_wn, [2][NI * 32], read one pair per swept tile; the resident tile's 2 x 16 ids are per register -- at D = 256 in LDS, [2][wave][32],
 // as WLDS keeps the weights (ELDS).  Ids past R are never compared: those rows are only met on the per-element path, behind `valid`.
-template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false, bool MK = false>
+// XN: shared extra negatives (tt_score_fwd_sym_bf16_xneg).  The company tiles run past the in-batch ones into the extras' own image:
+// a workgroup blockIdx.x >= ngi keeps 8 tiles of X resident (`isx`, workgroup-uniform).  Such a tile has no positive, so no diagonal
+// and every maximum in the "after the positive" slot (a tie with an extra does not beat the positive); it feeds the row direction
+// only -- the column accumulators are dropped; its LQ weight comes from lq_x (NULL: 1), its mask is ent_c[a] == ent_x[m] alone
+// (NULL ent_x: never).  The row partials land in slab rows ngi .., which finish1 adds behind the in-batch ones.  The in-batch
+// workgroups run the code of the form without extras: colsum and diag keep their bits.
+template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false, bool MK = false, bool XN = false>
 __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   using ST = SymStage<KS, FP8, X3>;
   constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, kImgB = ST::kImgB, K64 = FP8 ? KS / 4 : 1, KL = X3 ? KS : 1;
@@ -124,14 +136,19 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   constexpr bool WLDS = LQ && X3 && KS == 16;
   float* s_wc = s_wn + NI * 32 + wave * 32;
   static_assert(!MK || (!FP8 && !X3 && JT == 1), "the repeated-entity mask: bf16 operands only");
+  static_assert(!XN || (!FP8 && !X3 && JT == 1), "extra negatives: bf16 operands only");
   constexpr bool ELDS = MK && KS == 16;
   int* s_ean = reinterpret_cast<int*>(s_wn + (LQ ? NI * 32 + kSymWaves * 32 : 0));   // (MK) [NI * 32] notice ids of the a rows
   int* s_eac = s_ean + NI * 32;                                                       //      their company ids
   int* s_ebn = s_eac + NI * 32 + wave * 32;                                           // (ELDS) the resident tile's ids, [2][wave][32]
   int* s_ebc = s_ebn + kSymWaves * 32;
-  const int J0 = ((int)blockIdx.x * kSymWaves + wave) * JT;  // this wave's company tiles J0 .. J0 + JT - 1
+  bool isx = false;                                        // (XN) this workgroup's resident tiles are tiles of the extras' image
+  if constexpr (XN) isx = (int)blockIdx.x >= g.ngi;
+  const int J0 = XN ? (((int)blockIdx.x - (isx ? g.ngi : 0)) * kSymWaves + wave)
+                    : ((int)blockIdx.x * kSymWaves + wave) * JT;  // this wave's company tiles J0 .. J0 + JT - 1
   const int I0 = (int)blockIdx.y * NI, I1 = min(I0 + NI, nT);
-  const bool active = J0 < nT;
+  const int nTj = XN && isx ? g.nTx : nT, Rj = XN && isx ? g.Rx : R;   // the resident side's tiles / rows
+  const bool active = J0 < nTj;
   for (int i = lane; i < slots; i += 64) { s_sum[i] = 0.f; s_mb[i] = kNegBig; s_ma[i] = kNegBig; }
   float wb[JT][WLDS ? 1 : 16];                             // (LQ) company weights w_b of the resident tiles, 0 past R
   if constexpr (LQ) {
@@ -142,6 +159,13 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
     }
     if constexpr (WLDS) {
       if (lane < 32) s_wc[lane] = 32 * J0 + lane < R ? tt_lq_weight(g.lq_c[32 * J0 + lane]) : 0.f;
+    } else if constexpr (XN) {
+      const float* const lqj = isx ? g.lq_x : g.lq_c;      // (NULL lq_x: the extras uncorrected -- weight tt_lq_weight(0))
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int b = 32 * J0 + rowmap(r, h);
+        wb[0][(WLDS ? 0 : r)] = b < Rj ? tt_lq_weight(lqj ? lqj[b] : 0.f) : 0.f;
+      }
     } else {
 #pragma unroll
       for (int j = 0; j < JT; ++j)
@@ -159,7 +183,23 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
       s_ean[i] = a < R ? g.ent_n[a] : 0;                  // (read after the sweep's first barrier)
       s_eac[i] = a < R ? g.ent_c[a] : 0;
     }
-    if constexpr (ELDS) {
+    if (XN && isx) {                                       // the extras' company ids; no notice ids (never read: `masked`)
+      const bool have = g.ent_x != nullptr;
+      if constexpr (ELDS) {
+        if (lane < 32) {
+          const int b = 32 * J0 + lane;
+          s_ebn[lane] = 0;
+          s_ebc[lane] = (have && b < Rj) ? g.ent_x[b] : 0;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int b = 32 * J0 + rowmap(r, h);
+          ebn[(ELDS ? 0 : r)] = 0;
+          ebc[(ELDS ? 0 : r)] = (have && b < Rj) ? g.ent_x[b] : 0;
+        }
+      }
+    } else if constexpr (ELDS) {
       if (lane < 32) {
         const int b = 32 * J0 + lane;
         s_ebn[lane] = b < R ? g.ent_n[b] : 0;
@@ -174,8 +214,15 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
       }
     }
   }
+  const bool xmask = XN && MK && isx && g.ent_x != nullptr;   // (XN) the extras carry ids
   // (MK) is (a, register r of the resident tile) a masked pair?  (the diagonal: the caller's business)
   auto masked = [&](int ean, int eac, int r) -> bool {
+    if constexpr (XN) {
+      if (isx) {                                           // an extra: the row's own company, or a repeat of it
+        if constexpr (ELDS) return xmask && eac == s_ebc[rowmap(r, h)];
+        else return xmask && eac == ebc[(ELDS ? 0 : r)];
+      }
+    }
     if constexpr (ELDS) return same_entity(ean, eac, s_ebn[rowmap(r, h)], s_ebc[rowmap(r, h)]);
     else return same_entity(ean, eac, ebn[(ELDS ? 0 : r)], ebc[(ELDS ? 0 : r)]);
   };
@@ -196,11 +243,11 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   float dg_keep[JT];                                       // the positives of tile J (met once per wave, if J is in this chunk)
 #pragma unroll
   for (int j = 0; j < JT; ++j) {
-    jact[j] = J0 + j < nT;
-    jfull[j] = jact[j] && J0 + j < n_full;
+    jact[j] = J0 + j < nTj;
+    jfull[j] = jact[j] && J0 + j < (XN ? Rj / 32 : n_full);
     dg_keep[j] = kNegBig;
     if (FP8) load_f8frag<K64>(reinterpret_cast<const char*>(g.b_rows), jact[j] ? J0 + j : 0, c, h, bres8[j]);
-    else load_bfrag<(FP8 ? 1 : KS)>(reinterpret_cast<const __bf16*>(g.b_rows), jact[j] ? J0 + j : 0, c, h, bres[j]);
+    else load_bfrag<(FP8 ? 1 : KS)>(reinterpret_cast<const __bf16*>(XN && isx ? g.x_rows : g.b_rows), jact[j] ? J0 + j : 0, c, h, bres[j]);
     if (X3) load_bfrag<KL>(reinterpret_cast<const __bf16*>(g.b_lo), jact[j] ? J0 + j : 0, c, h, bres_lo[j]);
   }
   // stage loader: the stage's tiles go STRAIGHT into the LDS buffer by LDS-DMA (global_load_lds_dwordx4: lane l of a wave writes
@@ -279,7 +326,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
           const int J = J0 + j;
-          if (I < I1 && I != J && I < n_full && jfull[j]) {  // plain tile: 32 x 32 valid scores, all on one side of the positives
+          if (I < I1 && (I != J || (XN && isx)) && I < n_full && jfull[j]) {  // plain tile: 32 x 32 valid scores, all on one side of the positives
             float e[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) e[r] = ex(acc[j][r]);
@@ -288,15 +335,19 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
               for (int r = 0; r < 16; ++r) e[r] = masked(ean, eac, r) ? 0.f : e[r];
             }
             if constexpr (LQ) {
+              if (!(XN && isx)) {                          // (the extras stand in no column sum)
 #pragma unroll
               for (int r = 0; r < 16; ++r) colacc[j][r] = __builtin_fmaf(e[r], ua, colacc[j][r]);
+              }
               float t0 = e[0] * wreg(j, 0), t1 = e[8] * wreg(j, 8);
 #pragma unroll
               for (int r = 1; r < 8; ++r) { t0 = __builtin_fmaf(e[r], wreg(j, r), t0); t1 = __builtin_fmaf(e[8 + r], wreg(j, 8 + r), t1); }
               rs_tot += half_sum(t0 + t1);
             } else {
+            if (!(XN && isx)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) colacc[j][r] = add_asm(colacc[j][r], e[r]);
+            }
             float t0 = (e[0] + e[1]) + (e[2] + e[3]), t1 = (e[4] + e[5]) + (e[6] + e[7]);
             float t2 = (e[8] + e[9]) + (e[10] + e[11]), t3 = (e[12] + e[13]) + (e[14] + e[15]);
             rs_tot += half_sum((t0 + t1) + (t2 + t3));
@@ -307,7 +358,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
               for (int r = 3; r < 15; r += 2) m = max3_asm(m, acc[j][r], acc[j][r + 1]);
               m = half_max(fmaxf(m, acc[j][15]));
               // every b of tile J lies before (J < I) / after the positive of every a of tile I
-              if (J < I) xb_tot = fmaxf(xb_tot, m);
+              if (J < I && !(XN && isx)) xb_tot = fmaxf(xb_tot, m);
               else xa_tot = fmaxf(xa_tot, m);
             }
           } else if (I < I1 && jact[j]) {                  // the diagonal tile and the ragged last tiles: per element
@@ -317,8 +368,17 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
             for (int r = 0; r < 16; ++r) {
               const int b = 32 * J + rowmap(r, h);
               const float x = acc[j][r];
-              const bool valid = b < R && a < R;
+              const bool valid = b < Rj && a < R;
               float e = valid ? ex(x) : 0.f;
+              if constexpr (XN) {
+                if (isx) {                                 // an extra: no positive, no column sum, behind every in-batch column
+                  if constexpr (MK) e = masked(ean, eac, r) ? 0.f : e;
+                  if constexpr (LQ) rsum = __builtin_fmaf(e, wreg(j, r), rsum);
+                  else rsum += e;
+                  xa = valid ? fmaxf(xa, x) : xa;
+                  continue;
+                }
+              }
               if constexpr (MK) e = (b != a && masked(ean, eac, r)) ? 0.f : e;
               if constexpr (LQ) {
                 colacc[j][r] = __builtin_fmaf(e, ua, colacc[j][r]);
@@ -335,14 +395,14 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
             xb_tot = fmaxf(xb_tot, half_max(xb));
             xa_tot = fmaxf(xa_tot, half_max(xa));
             dg = half_max(dg);
-            if (I == J) dg_keep[j] = dg;                   // taken from the MFMA result itself, so ties compare bit for bit
+            if (I == J && !(XN && isx)) dg_keep[j] = dg;                   // taken from the MFMA result itself, so ties compare bit for bit
           }
         }
         if (I < I1 && h == 0) { s_sum[il] = rs_tot; s_mb[il] = xb_tot; s_ma[il] = xa_tot; }
       }
     }
   }
-  if (active) {
+  if (active && !(XN && isx)) {
 #pragma unroll
     for (int j = 0; j < JT; ++j) {
       const int J = J0 + j;
@@ -411,6 +471,7 @@ struct Fin1Args {
   const float* lq_n; const float* lq_c;  // LQ: [R] log sampling probabilities of the notice / company rows
   float* w_n; float* w_c;              // LQ: their weights tt_lq_weight(lq) (0 past R): what tt_score_bwd_bf16_lq takes
   const float* pw_g;                   // PW: [round_up(R, 64)] normalised pair weights (tt_score_prepare_pw)
+  const float* lq_x; float* w_x; int Rx;   // XN: the extras' log probabilities (or NULL) -> their weights [round_up(Rx, 64)], 0 past Rx
 };
 
 __device__ __forceinline__ float slab_sum4(const float* __restrict__ slab, int64_t Rp, int n, int q, int i) {
@@ -441,9 +502,16 @@ __device__ __forceinline__ float slab_max4(const float* __restrict__ slab, int64
 // PW (tt_score_fwd_sym_bf16_pw): row i's loss term times its pair weight g_i, and the reciprocals FOLDED, g_i / rowsum_i and
 // g_i / colsum_i -- the backward's off-diagonal weights e_ab (ia + ib) and e_ab (ua ib + wb ia) are then the weighted ones as they
 // stand.  rowsum / colsum stay the unweighted sums.  (g_i = 1: every product below is exact -- the plain entry's bits.)
-template <bool LQ = false, bool PW = false>
+// XN (tt_score_fwd_sym_bf16_xneg): n_groups counts the extras' slab rows too; the extras' weights w_x go out for the backward (1
+// without a correction: there the weight of an extra is the bare reciprocal's factor).
+template <bool LQ = false, bool PW = false, bool XN = false>
 __global__ __launch_bounds__(256) void score_sym_finish1_kernel(Fin1Args f) {
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
+  if constexpr (XN) {
+    const int Rxp = (f.Rx + 63) / 64 * 64;
+    for (int m = (int)blockIdx.x * 256 + t; m < Rxp; m += (int)gridDim.x * 256)
+      f.w_x[m] = m < f.Rx ? (LQ ? tt_lq_weight(f.lq_x ? f.lq_x[m] : 0.f) : 1.f) : 0.f;
+  }
   const int i = blockIdx.x * kFinRows + lane;              // slab rows are padded: i < Rp always
   const int Dp = f.KS * 16, stride = 4 + 2 * Dp;
   float* part = f.part + (int64_t)blockIdx.x * stride;
@@ -619,15 +687,19 @@ __global__ __launch_bounds__(kPwThreads) void score_prepare_pw_kernel(const floa
 
 struct SymLayout {
   int nT, NI, n_groups, n_chunks, n_wg, Dp;
+  int nTx, n_groups_x;                 // extra negatives: their tiles and J groups (0 without)
   int64_t Rp;
   size_t off_rs, off_mb, off_ma, off_cs, off_diag, off_part, off_part2, bytes;
 };
 
-inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D) {
+// Rx extra negatives add slab rows only: NI, the chunks and with them the column sums' order are the in-batch problem's
+inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D, int64_t Rx = 0) {
   SymLayout L;
   L.Dp = padded_d(D);
   L.nT = (int)tt_cdiv(R, 32);
   L.n_groups = (int)tt_cdiv(L.nT, kSymWaves);
+  L.nTx = (int)tt_cdiv(Rx, 32);
+  L.n_groups_x = (int)tt_cdiv(L.nTx, kSymWaves);
   // notice tiles per workgroup: enough workgroups for ~2 per CU, at least 4 tiles per sweep, at most 32 (LDS: 3 * 8 * NI * 128 B)
   int ni = (int)tt_cdiv((int64_t)L.nT * L.n_groups, 2 * (ctx ? ctx->num_cus : 256));
   ni = ni < 4 ? 4 : (ni > 16 ? 16 : ni);                  // 16 tiles: 48 KB of LDS slots per workgroup
@@ -638,9 +710,9 @@ inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D) {
   L.Rp = rup((int64_t)L.n_chunks * ni * 32, 256);          // slab rows cover every slot a workgroup writes (>= R)
   size_t o = 0;
   auto take = [&](size_t n) { size_t at = o; o += (n + 255) & ~size_t(255); return at; };
-  L.off_rs = take(sizeof(float) * L.n_groups * L.Rp);
-  L.off_mb = take(sizeof(float) * L.n_groups * L.Rp);
-  L.off_ma = take(sizeof(float) * L.n_groups * L.Rp);
+  L.off_rs = take(sizeof(float) * (L.n_groups + L.n_groups_x) * L.Rp);
+  L.off_mb = take(sizeof(float) * (L.n_groups + L.n_groups_x) * L.Rp);
+  L.off_ma = take(sizeof(float) * (L.n_groups + L.n_groups_x) * L.Rp);
   L.off_cs = take(sizeof(float) * L.n_chunks * L.Rp);
   L.off_diag = take(sizeof(float) * L.Rp);
   L.off_part = take(sizeof(float) * L.n_wg * (4 + 2 * 256));   // (sized for the widest record: fp8 operands pad D up to 64)
@@ -656,9 +728,11 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
                        int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
                        bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
                        float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr,
-                       const float* pw_g = nullptr) {
+                       const float* pw_g = nullptr, const void* X_packed = nullptr, int64_t M = 0, const float* lq_x = nullptr,
+                       const int32_t* ent_x = nullptr, float* w_x = nullptr) {
   const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
   const bool mk = ent_n != nullptr;                        // tt_score_fwd_sym_bf16_mask passes both (checked there)
+  const bool xn = X_packed != nullptr;                     // tt_score_fwd_sym_bf16_xneg (M, w_x checked there)
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
   TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
@@ -672,7 +746,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   }
   tt_ctx sized = *ctx;
   sized.num_cus = 256;                                     // the layout must not depend on the device: it sizes the workspace
-  SymLayout L = sym_layout(&sized, B, D);
+  SymLayout L = sym_layout(&sized, B, D, M);
   if (fp8) L.Dp = padded_d8(D);                            // (the part record is sized for 256 columns: sym_layout)
   if (workspace_bytes < L.bytes) {
     tt_set_error("%s: workspace %zu < required %zu", who, workspace_bytes, L.bytes);
@@ -701,46 +775,61 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   g.lq_c = lq_c;
   g.ent_n = ent_n;
   g.ent_c = ent_c;
+  if (xn) {
+    g.x_rows = view(X_packed, M, D).rows;
+    g.Rx = (int)M; g.nTx = L.nTx; g.ngi = L.n_groups;
+    g.lq_x = lq_x; g.ent_x = ent_x;
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // fp8, D = 256: two company tiles per wave (half the workgroups along J, half the slab rows)
   const int jt = (fp8 && L.Dp == 256) ? 2 : 1;
-  const int n_groups = (int)tt_cdiv(L.nT, kSymWaves * jt);
+  const int n_groups = (int)tt_cdiv(L.nT, kSymWaves * jt) + L.n_groups_x;     // (extras: bf16 operands, jt = 1)
   const dim3 grid((unsigned)n_groups, (unsigned)L.n_chunks);
   const size_t slot_bytes = sizeof(float) * 3 * kSymWaves * L.NI * 32;
   const size_t wn_bytes = sizeof(float) * (L.NI * 32 + kSymWaves * 32);   // (LQ) notice weights (+ company weights, x3 D = 256)
   const size_t ent_bytes = sizeof(int) * 2 * (L.NI * 32 + kSymWaves * 32); // (MK) the a rows' ids (+ the resident tiles', D = 256)
   // one launch per form (fp8 has neither an x3 nor an LQ form, the mask bf16 operands only); only the x3, LQ and MK forms set their LDS limit
-  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc, auto mkc) -> int {
+  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc, auto mkc, auto xnc) -> int {
     constexpr int JT = fp8c && ks == 16 ? 2 : 1;                  // = jt
     const size_t lds = slot_bytes + 2 * SymStage<ks, fp8c, x3c>::kBytes + (lqc ? wn_bytes : 0) + (mkc ? ent_bytes : 0);
     return tt_dispatch([&](auto u) -> int {
-      if constexpr (x3c || lqc || mkc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc>);
-      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc><<<grid, kSymThreads, lds, st>>>(g);
+      if constexpr (x3c || lqc || mkc || xnc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc>);
+      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc><<<grid, kSymThreads, lds, st>>>(g);
       return TT_OK;
     }, unit);
   };
   const std::false_type no{};
   int rc;
-  if (mk) {
+  if (xn) {
+    const std::true_type yes{};
+    rc = tt_dispatch([&](auto lqc, auto mkc) {
+      switch (L.Dp) {
+        case 32: return go(tt_c<2>, no, no, lqc, mkc, yes);
+        case 64: return go(tt_c<4>, no, no, lqc, mkc, yes);
+        case 128: return go(tt_c<8>, no, no, lqc, mkc, yes);
+        default: return go(tt_c<16>, no, no, lqc, mkc, yes);
+      }
+    }, lq, mk);
+  } else if (mk) {
     const std::true_type yes{};
     rc = tt_dispatch([&](auto lqc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, yes);
-        case 64: return go(tt_c<4>, no, no, lqc, yes);
-        case 128: return go(tt_c<8>, no, no, lqc, yes);
-        default: return go(tt_c<16>, no, no, lqc, yes);
+        case 32: return go(tt_c<2>, no, no, lqc, yes, no);
+        case 64: return go(tt_c<4>, no, no, lqc, yes, no);
+        case 128: return go(tt_c<8>, no, no, lqc, yes, no);
+        default: return go(tt_c<16>, no, no, lqc, yes, no);
       }
     }, lq);
   } else if (fp8) {
     const std::true_type yes{};
-    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no) : go(tt_c<16>, yes, no, no, no));
+    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no, no) : go(tt_c<16>, yes, no, no, no, no));
   } else {
     rc = tt_dispatch([&](auto x3c, auto lqc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, x3c, lqc, no);
-        case 64: return go(tt_c<4>, no, x3c, lqc, no);
-        case 128: return go(tt_c<8>, no, x3c, lqc, no);
-        default: return go(tt_c<16>, no, x3c, lqc, no);
+        case 32: return go(tt_c<2>, no, x3c, lqc, no, no);
+        case 64: return go(tt_c<4>, no, x3c, lqc, no, no);
+        case 128: return go(tt_c<8>, no, x3c, lqc, no, no);
+        default: return go(tt_c<16>, no, x3c, lqc, no, no);
       }
     }, x3, lq);
   }
@@ -757,7 +846,9 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   f.part = reinterpret_cast<float*>(ws + L.off_part);
   f.lq_n = lq_n; f.lq_c = lq_c; f.w_n = w_n; f.w_c = w_c;
   f.pw_g = pw_g;
-  if (pw_g) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
+  f.lq_x = lq_x; f.w_x = w_x; f.Rx = (int)M;
+  if (xn) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, false, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
+  else if (pw_g) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
   else if (lq) score_sym_finish1_kernel<true><<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   else score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   TT_LAUNCH_CHECK();
@@ -838,6 +929,31 @@ int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_mask", false, lq_n, lq_c,
                      lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c);
+}
+
+size_t tt_score_fwd_sym_xneg_workspace_bytes(int64_t B, int64_t M, int32_t D) {
+  if (B < 1 || M < 1 || D < 1 || D > 256) return 0;
+  tt_ctx fake{};
+  fake.num_cus = 256;
+  return sym_layout(&fake, B, D, M).bytes;
+}
+
+int tt_score_fwd_sym_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* C_packed, const void* X_packed, int64_t B, int64_t M,
+                               int32_t D, float inv_t, float shift, float ab_scale, int32_t want_rank, const int32_t* ent_n,
+                               const int32_t* ent_c, const int32_t* ent_x, const float* lq_n, const float* lq_c, const float* lq_x,
+                               float* rowsum, float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* w_x,
+                               float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
+                               tt_stream stream) {
+  TT_CHECK_ARG(X_packed && w_x, "tt_score_fwd_sym_bf16_xneg: NULL X_packed / w_x");
+  TT_CHECK_ARG(M >= 1 && M < ((int64_t)1 << 30), "tt_score_fwd_sym_bf16_xneg: bad M=%lld", (long long)M);
+  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "tt_score_fwd_sym_bf16_xneg: ent_n and ent_c go together");
+  TT_CHECK_ARG(!ent_x || ent_c, "tt_score_fwd_sym_bf16_xneg: ent_x needs ent_n / ent_c");
+  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_xneg: lq_n and lq_c go together");
+  TT_CHECK_ARG(!lq_x || lq_n, "tt_score_fwd_sym_bf16_xneg: lq_x needs lq_n / lq_c");
+  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_xneg: the logQ correction needs w_n / w_c");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_xneg", false, lq_n, lq_c,
+                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c, nullptr, X_packed, M, lq_x, ent_x, w_x);
 }
 
 int tt_score_prepare_pw(tt_ctx* ctx, const float* w, int64_t B, float* g_out, tt_stream stream) {

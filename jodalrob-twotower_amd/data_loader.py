@@ -43,18 +43,27 @@ class DeviceFeatureStore:
         return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids)}
 
 
+NEGATIVE_SEED_OFFSET = 0x5851F42D                  # the extras' generator: the loader's seed plus this
+
+
 class DevicePairLoader:
     """Iterates over (notice_idx, company_idx) pairs in batches; len() = number of batches (drop_last=False,
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
-                 shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None):
+                 shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None, extra_negatives: int = 0,
+                 negative_pool=None):
         """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
         task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
         log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
         every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction.
         pair_weight: optional f32 [P], one raw sample weight per row of `pairs` (pair_weights.inverse_count_weights): every batch
-        then carries "pair_weight" [B] and the train task takes the weighted mean of the pairs' loss terms."""
+        then carries "pair_weight" [B] and the train task takes the weighted mean of the pairs' loss terms.
+        extra_negatives: M > 0: every batch carries "negatives", M company rows drawn uniformly (with replacement) from the company
+        store -- or from negative_pool, an int64 tensor of company rows such as mined hard negatives -- which the train task contrasts
+        with every notice of the batch besides the in-batch companies.  They carry "log_q" = log(1 / pool size) when the loader
+        corrects and "entity" = the company row when mask_repeats is on.  Drawn per epoch from a generator of their own: a seed's pair
+        order is the same with and without extras."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
@@ -70,6 +79,52 @@ class DevicePairLoader:
         self.set_log_q(log_q)
         self.pair_weight = None
         self.set_pair_weight(pair_weight)
+        self._neg_gen = torch.Generator(device=self.pairs.device)
+        self._neg_gen.manual_seed((int(seed) + NEGATIVE_SEED_OFFSET) & ((1 << 63) - 1))
+        self.extra_negatives, self.negative_pool = 0, None
+        self.set_extra_negatives(extra_negatives, negative_pool)
+
+    def set_extra_negatives(self, extra_negatives: int, negative_pool=None) -> None:
+        """M >= 0 shared extra negatives per batch (0: none), drawn from the whole company store or from `negative_pool` (int64 [n >= 1]
+        company rows)"""
+        M = int(extra_negatives)
+        if M < 0:
+            raise ValueError(f"extra_negatives must be >= 0, got {M}")
+        if M > 0 and self.pair_weight is not None:
+            raise ValueError("extra_negatives do not combine with pair_weight")
+        pool = None
+        if negative_pool is not None:
+            t = negative_pool
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] < 1:
+                raise ValueError(f"negative_pool: need an int64 tensor of shape [n >= 1], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            if int(t.min()) < 0 or int(t.max()) >= len(self.company):
+                raise KeyError("negative_pool refers to a company that is not in the feature store")
+            pool = t.to(self.pairs.device).contiguous()
+        if M > 0 and pool is None and len(self.company) < 1:
+            raise ValueError("extra_negatives: the company store is empty")
+        if M > 0 and len(self.company) - 1 > np.iinfo(np.int32).max:
+            raise ValueError("extra_negatives: a company row does not fit int32")
+        self.extra_negatives, self.negative_pool = M, pool
+
+    def epoch_negatives(self) -> Optional[torch.Tensor]:
+        """int64 [n_batches, M]: this epoch's extra negatives, batch k's company rows at [k] -- ONE draw per epoch from the extras' own
+        seeded generator (the pair order's generator is not touched).  None without extras."""
+        if not self.extra_negatives:
+            return None
+        n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
+        idx = torch.randint(0, n_pool, (len(self), self.extra_negatives), generator=self._neg_gen, device=self.pairs.device)
+        return self.negative_pool[idx] if self.negative_pool is not None else idx
+
+    def negatives(self, rows: torch.Tensor) -> Dict:
+        """the batch entry "negatives" of the company rows `rows` (int64 [M])"""
+        out = self.company.gather(rows.contiguous())
+        if self.log_q is not None:
+            n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
+            out["log_q"] = torch.full((rows.shape[0],), -float(np.log(n_pool)), dtype=torch.float32, device=rows.device)
+        if self.entity is not None:
+            out["entity"] = rows.to(torch.int32)
+        return out
 
     def set_pair_weight(self, pair_weight) -> None:
         """f32 [P] raw sample weights, one per row of the pair table, or None: turns pair weights on / off for every batch this
@@ -77,6 +132,8 @@ class DevicePairLoader:
         if pair_weight is None:
             self.pair_weight = None
             return
+        if getattr(self, "extra_negatives", 0):
+            raise ValueError("pair_weight does not combine with extra_negatives")
         P = self.pairs.shape[0]
         t = pair_weight
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != P:
@@ -118,7 +175,10 @@ class DevicePairLoader:
         n = self.pairs.shape[0]
         return torch.randperm(n, generator=self._gen, device=self.pairs.device) if self.shuffle else None
 
-    def batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
+    def batch(self, order: Optional[torch.Tensor], lo: int, negatives: Optional[torch.Tensor] = None) -> Dict:
+        """negatives: this batch's row of epoch_negatives() (a loader with extras: required)"""
+        if (negatives is not None) != bool(self.extra_negatives):
+            raise ValueError("batch(): a loader with extra_negatives needs this batch's row of epoch_negatives(), one without takes none")
         sel = self.pairs[lo:lo + self.batch_size] if order is None else self.pairs[order[lo:lo + self.batch_size]]
         out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
         if self.pair_weight is not None:
@@ -130,6 +190,8 @@ class DevicePairLoader:
         if self.entity is not None:
             out["notice"]["entity"] = sel[:, 0].to(torch.int32)
             out["company"]["entity"] = sel[:, 1].to(torch.int32)
+        if negatives is not None:
+            out["negatives"] = self.negatives(negatives)
         return out
 
     def epoch_entity(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -178,8 +240,9 @@ class DevicePairLoader:
 
     def __iter__(self) -> Iterator[Dict]:
         order = self.epoch_order()
-        for lo in range(0, self.pairs.shape[0], self.batch_size):
-            yield self.batch(order, lo)
+        neg = self.epoch_negatives()
+        for k, lo in enumerate(range(0, self.pairs.shape[0], self.batch_size)):
+            yield self.batch(order, lo, None if neg is None else neg[k])
 
     def eval_batches(self, graphed_eval, eager_eval=None, max_batches: Optional[int] = None) -> int:
         """One pass over the pairs in order (no shuffling is applied here: the reference's test loader does not shuffle) through a
@@ -193,7 +256,7 @@ class DevicePairLoader:
             if lo + B <= n:
                 graphed_eval.step_from_store(self.notice, self.company, self.pairs, order, lo)
             elif eager_eval is not None:
-                graphed_eval.add_eager(eager_eval(self.batch(order, lo)))
+                graphed_eval.add_eager(eager_eval(self._plain_batch(order, lo)))
             else:
                 continue
             done += 1
@@ -208,6 +271,21 @@ class DevicePairLoader:
         order = self.epoch_order()
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))
+        neg = self.epoch_negatives()
+        if neg is not None:
+            # extra negatives: no store-fed hand-over -- the batches __iter__ yields, through the captured step's plain-copy hand-over
+            # step(batch) (a step captured on a batch with the same M), the ragged one through ragged_step or the eager callable
+            if U > 1:
+                raise NotImplementedError("extra negatives are not supported by the unrolled step")
+            for k, lo in enumerate(range(0, n, B)):
+                b = self.batch(order, lo, neg[k])
+                if lo + B <= n and graphed_step is not None:
+                    yield graphed_step.step(b)
+                elif ragged_step is not None and lo + B > n and ragged_step.static["notice"]["dense"].shape[0] == n - lo:
+                    yield ragged_step.step(b)
+                elif eager_step is not None:
+                    yield eager_step(b)
+            return
         lq = self.epoch_log_q(order)
         if lq is not None and U > 1:
             raise NotImplementedError("the logQ correction is not supported by the unrolled step")
@@ -233,6 +311,14 @@ class DevicePairLoader:
             elif eager_step is not None:
                 yield eager_step(self.batch(order, lo))
 
+    def _plain_batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
+        """batch(order, lo) without extras, whatever the loader draws for training (evaluation ranks the batch's own companies)"""
+        M, self.extra_negatives = self.extra_negatives, 0
+        try:
+            return self.batch(order, lo)
+        finally:
+            self.extra_negatives = M
+
     def ragged_example(self) -> Optional[Dict]:
         """A batch of the remainder's size (pairs % batch_size), or None when the epoch has no ragged batch: the example a second
         captured step is built from."""
@@ -253,6 +339,10 @@ class DevicePairLoader:
             out["company"]["entity"] = sel[:, 1].to(torch.int32)
         if self.pair_weight is not None:
             out["pair_weight"] = self.pair_weight[:r].clone()
+        if self.extra_negatives:                              # (an example of the right shapes: the extras' generator is not touched)
+            n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
+            idx = torch.arange(self.extra_negatives, device=self.pairs.device) % n_pool
+            out["negatives"] = self.negatives(self.negative_pool[idx] if self.negative_pool is not None else idx)
         return out
 
 

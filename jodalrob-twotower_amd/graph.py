@@ -27,11 +27,15 @@ from .kjt import KeyedJaggedTensor
 from .optim import FusedAdam
 
 
+_MAX_COPIES = 8                    # copy segments per tt_copy_multi launch (include/twotower.h: TT_MAX_COPIES)
+
+
 class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
     _log_q_ok = True               # batches may carry "log_q" (the logQ correction); the unrolled / segmented steps refuse them
     _entity_ok = True              # batches may carry "entity" (the repeated-entity mask); likewise
     _pair_weight_ok = True         # batches may carry "pair_weight" (per-pair sample weights); likewise
+    _negatives_ok = True           # batches may carry "negatives" (shared extra negatives); likewise
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
@@ -72,6 +76,14 @@ class GraphedTrainStep:
                 raise NotImplementedError(f"pair weights (a batch with 'pair_weight') are not supported by {type(self).__name__}")
             if getattr(task, "exchange", None) is not None:
                 raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")
+        # shared extra negatives: an example batch with "negatives" gets static M-row buffers (features, ids and whichever of log_q /
+        # entity it carries), filled at every hand-over by more copy segments; the hand-over is the plain-copy one (_setup_ingest)
+        self._has_negatives = example_batch.get("negatives") is not None
+        if self._has_negatives:
+            if not self._negatives_ok:
+                raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
+            if getattr(task, "exchange", None) is not None:
+                raise NotImplementedError("extra negatives (a batch with 'negatives') are not supported by the sharded task")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
@@ -96,6 +108,12 @@ class GraphedTrainStep:
         if self._has_pair_weight:
             B = example_batch["notice"]["dense"].shape[0]
             self.static["pair_weight"] = self._check_pair_weight(example_batch["pair_weight"], B, dev).clone()
+        if self._has_negatives:
+            neg = example_batch["negatives"]
+            self.static["negatives"] = {"dense": neg["dense"].clone(), "kjt": KeyedJaggedTensor(neg["kjt"].keys(), neg["kjt"].values().clone())}
+            for k in ("log_q", "entity"):
+                if neg.get(k) is not None:
+                    self.static["negatives"][k] = neg[k].clone()
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
@@ -170,7 +188,7 @@ class GraphedTrainStep:
         per-key plan: returns (store, embedders, rows_km, static id tensors, B) or None (then the batch is handed over by plain
         copies and the plan gathers its rows out of the lookup's slot-major array)."""
         self._x_static, self._rows_sm = None, None
-        if not settings.graph_ingest:
+        if not settings.graph_ingest or getattr(self, "_has_negatives", False):     # (extras: the company side is B + M rows)
             return None
         model = getattr(self.task, "two_tower_model", None)
         towers = [getattr(model, n, None) for n in ("notice_tower", "company_tower")]
@@ -339,6 +357,8 @@ class GraphedTrainStep:
             if e.store is not store or not e.keys:
                 continue
             ids = self.static[side]["kjt"].values().view(-1, len(e.keys))
+            if side == "company" and getattr(self, "_has_negatives", False):     # the extras go through the company tower too
+                ids = torch.cat([ids, self.static["negatives"]["kjt"].values().view(-1, len(e.keys))], 0)
             rows.append((ids.clamp(min=0).minimum(e._key_vocab - 1) + e._key_row_offset).reshape(-1))      # cat_embed.py:114-117
         return torch.unique(torch.cat(rows)) if rows else None
 
@@ -480,6 +500,30 @@ class GraphedTrainStep:
         sw = self.static["pair_weight"]
         return [(sw, GraphedTrainStep._check_pair_weight(w, sw.shape[0], sw.device))]
 
+    def _negatives_pairs(self, neg):
+        """copy segments of this step's extra negatives into the static M-row buffers, after the with / without check (the task
+        validates what the buffers then hold)"""
+        if (neg is not None) != self._has_negatives:
+            raise ValueError("negatives mismatch: the step was captured " + ("with" if self._has_negatives else "without") +
+                             " extra negatives, the batch " + ("has none" if self._has_negatives else "carries them"))
+        if neg is None:
+            return []
+        sn = self.static["negatives"]
+        if {k for k in ("log_q", "entity") if neg.get(k) is not None} != {k for k in ("log_q", "entity") if k in sn}:
+            raise ValueError("negatives mismatch: the batch's extras carry other optional entries (log_q / entity) than the captured ones")
+        out = []
+        for name, dst, src in [("dense", sn["dense"], neg["dense"]), ("kjt", sn["kjt"].values(), neg["kjt"].values())] + \
+                [(k, sn[k], neg[k]) for k in ("log_q", "entity") if k in sn]:
+            if not isinstance(src, torch.Tensor) or src.shape != dst.shape or src.dtype != dst.dtype or src.device != dst.device:
+                raise ValueError(f"negatives['{name}'] must be a {dst.dtype} tensor of shape {list(dst.shape)} on {dst.device} "
+                                 "(the captured step has one M)")
+            src = src.contiguous()
+            if src.data_ptr() % 16 or dst.data_ptr() % 16:         # (the copy launch moves 16-byte pieces)
+                dst.copy_(src, non_blocking=True)
+            else:
+                out.append((dst, src))
+        return out
+
     def _entity_pairs(self, ent_n, ent_c):
         """copy segments of this step's entity ids into the static buffers (a side given as None: the row indices)"""
         B, dev = self._ent_iota.shape[0], self._ent_iota.device
@@ -497,6 +541,7 @@ class GraphedTrainStep:
         pairs, src_ids = [], []                                 # src_ids per side: where this step's ids are read from
         if batch is None:
             return pairs, None
+        pairs += self._negatives_pairs(batch.get("negatives"))
         lq_n, lq_c = batch["notice"].get("log_q"), batch["company"].get("log_q")
         if (lq_n is not None or lq_c is not None) != self._has_log_q:
             raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
@@ -532,7 +577,9 @@ class GraphedTrainStep:
             self._run_ingest(pairs + [self._fill_slot()], src_ids)
             self._mark_slot()
         else:
-            ops.copy_multi(pairs + [self._fill_slot()])         # ONE launch: the four batch buffers + the scalars
+            segs = pairs + [self._fill_slot()]                  # ONE launch: the four batch buffers + the scalars (extras with
+            for i in range(0, len(segs), _MAX_COPIES):          # log_q and entity on every side: 13 segments, two launches)
+                ops.copy_multi(segs[i:i + _MAX_COPIES])
             self._mark_slot()
         return self._replay()
 
@@ -557,6 +604,8 @@ class GraphedTrainStep:
         entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
         DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise.
         pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment."""
+        if self._has_negatives:
+            raise NotImplementedError("extra negatives: no store-fed hand-over -- a step captured with 'negatives' takes step(batch)")
         if (log_q is not None) != self._has_log_q:
             raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
                              " a log_q, step_from_store got " + ("none" if self._has_log_q else "one"))

@@ -820,6 +820,113 @@ def score_bwd_bf16_lq(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale,
     return score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n, inv, x3=x3, w=w)
 
 
+# shared extra negatives (the *_xneg entries of include/twotower.h): M extra company rows X enter every notice's row-direction softmax
+def score_xneg_ids(ent_x, M, dev):
+    """the extras' company ids as the *_xneg entries read them: int32 [round_up(M, 64)], 16-byte aligned, zero (ignored) past M"""
+    e = _ent_vec(ent_x, M, dev, "ent_x")
+    Mp = (M + 63) // 64 * 64
+    if M == Mp and e.is_contiguous() and e.data_ptr() % 16 == 0:
+        return e
+    out = torch.zeros(Mp, dtype=torch.int32, device=dev)
+    out[:M] = e
+    return out
+
+
+def _xneg_check(B, M, ent, ent_x, lq, lq_x):
+    if M < 1:
+        raise ValueError(f"extra negatives: M must be >= 1, got {M}")
+    if ent_x is not None and ent is None:
+        raise ValueError("extra negatives: ent_x needs the batch's ids (ent)")
+    if lq_x is not None and not lq:
+        raise ValueError("extra negatives: lq_x needs lq_n / lq_c")
+
+
+def score_fwd_sym_xneg(Np, Cp, Xp, B, M, D, inv_t, shift, ent=None, ent_x=None, lq_n=None, lq_c=None, lq_x=None, scale_n: float = 1.0,
+                       want_rank: bool = True):
+    """score_fwd_sym (/_lq /_mask) with M shared extra negatives (tt_score_fwd_sym_bf16_xneg): Xp = score_pack_bf16(X) (scale 1), ent =
+    score_mask_ids(...) or None, ent_x = score_xneg_ids(...) or None (never masked), lq_x f32 [M] or None (log q = 0).  Returns
+    (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, w_x, out8, loss): rowsum / inv_row include the extras, w = (w_n, w_c) with
+    logQ else None, w_x [round_up(M, 64)] the extras' weights -- what score_bwd_bf16_xneg takes."""
+    dev = Np.device
+    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
+    _xneg_check(B, M, ent, ent_x, lq, lq_x)
+    if lq:
+        _lq_check_t(inv_t)
+    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
+    Bp, Mp = (B + 63) // 64 * 64, (M + 63) // 64 * 64
+    f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
+    w_x = torch.empty(Mp, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    out8 = torch.empty(8, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lib = L.load()
+    nbytes = lib.tt_score_fwd_sym_xneg_workspace_bytes(B, M, D)
+    if L.riders_deferred(dev, 2):                                      # (as _fwd_sym: the partial records outlive the shared scratch)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out8._tt_keep = ws
+    else:
+        ws = L.workspace(dev, nbytes)
+    e = (L.ptr(ent[0]), L.ptr(ent[1])) if ent is not None else (None, None)
+    name = "tt_score_fwd_sym_bf16_xneg"
+    with _timed(name):
+        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), L.ptr(Xp), B, M, D, inv_t, shift, scale_n, int(want_rank), *e,
+                                   L.ptr(ent_x) if ent_x is not None else None, *(map(L.ptr, lq) if lq else (None, None)),
+                                   L.ptr(lqx) if lqx is not None else None, L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]),
+                                   *((L.ptr(f[5]), L.ptr(f[6])) if lq else (None, None)), L.ptr(w_x), L.ptr(f[2]), L.ptr(rank),
+                                   L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
+    w = (f[5][:B], f[6][:B]) if lq else None
+    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), w, w_x, out8, loss
+
+
+def score_bwd_bf16_xneg(Np, Xp, B, M, D, inv_t, shift, inv_row, w_x, d_loss, scale, dN, scale_n: float = 1.0, ent_c=None, ent_x=None):
+    """The extras' share of the backward (tt_score_bwd_bf16_xneg), AFTER score_bwd_bf16 on the same forward's sums: adds (1/T)/(2B) Wx X
+    to dN in place and returns dX [M, D].  inv_row / w_x: score_fwd_sym_xneg's (views of its padded arrays); ent_c = the ent[1] of
+    score_mask_ids and ent_x = score_xneg_ids(...), both or neither."""
+    dev = Np.device
+    if (ent_c is None) != (ent_x is None):
+        raise ValueError("extra negatives: ent_c and ent_x go together")
+    if not (dN.is_contiguous() and dN.dtype == torch.float32 and tuple(dN.shape) == (B, D)):
+        raise ValueError(f"dN must be a contiguous float32 [{B}, {D}] tensor")
+    dX = torch.empty((M, D), dtype=torch.float32, device=dev)
+    name = "tt_score_bwd_bf16_xneg"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(Np), L.ptr(Xp), B, M, D, inv_t, shift, scale_n, L.ptr(inv_row), L.ptr(w_x),
+                                        L.ptr(ent_c) if ent_c is not None else None, L.ptr(ent_x) if ent_x is not None else None,
+                                        L.ptr(d_loss), scale, L.ptr(dN), L.ptr(dX), L.stream(dev)), name)
+    return dX
+
+
+def score_dir_fwd_xneg(n, x, inv_t, shift, diag, sumexp, rank, lq_x=None, ent_c=None, ent_x=None):
+    """f32 parity path (tt_score_dir_fwd_xneg): adds the extras x [M, D] to the row direction of score_dir_fwd(n, c, ...) IN PLACE --
+    sumexp[a] += sum_m e_am w_m, rank[a] += #{m: s_am > diag[a]}.  ent_c / ent_x (both or neither): the company-only mask."""
+    dev, B, M, D = n.device, n.shape[0], x.shape[0], n.shape[1]
+    if (ent_c is None) != (ent_x is None):
+        raise ValueError("extra negatives: ent_c and ent_x go together")
+    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
+    name = "tt_score_dir_fwd_xneg"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(n), L.ptr(x), B, M, D, inv_t, shift, L.ptr(ent_c) if ent_c is not None else None,
+                                        L.ptr(ent_x) if ent_x is not None else None, L.ptr(lqx) if lqx is not None else None,
+                                        L.ptr(diag), L.ptr(sumexp), L.ptr(rank), L.stream(dev)), name)
+
+
+def score_dir_bwd_xneg(A, Bm, inv_t, shift, x_is_b, rowsum, d_loss, scale, lq_x=None, ent_a=None, ent_b=None, out=None):
+    """f32 parity path (tt_score_dir_bwd_xneg), one rectangular direction of the extras: x_is_b: A = N, Bm = X -> dN's extra term, added
+    to `out` (the square backward's dN); else A = X, Bm = N -> dX (returned).  rowsum: the notice rows' sums with the extras."""
+    dev, Ra, Rb, D = A.device, A.shape[0], Bm.shape[0], A.shape[1]
+    if (ent_a is None) != (ent_b is None):
+        raise ValueError("extra negatives: ent_a and ent_b go together")
+    lqx = None if lq_x is None else _lq_vec(lq_x, Rb if x_is_b else Ra, dev, "lq_x")
+    dA = out if out is not None else torch.empty_like(A)
+    name = "tt_score_dir_bwd_xneg"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), L.ptr(A), L.ptr(Bm), Ra, Rb, D, inv_t, shift, int(bool(x_is_b)),
+                                        L.ptr(ent_a) if ent_a is not None else None, L.ptr(ent_b) if ent_b is not None else None,
+                                        L.ptr(lqx) if lqx is not None else None, L.ptr(rowsum), L.ptr(d_loss), scale,
+                                        int(out is not None), L.ptr(dA), L.stream(dev)), name)
+    return dA
+
+
 def score_dir_fwd_lq(A, Bm, inv_t, shift, lq_b, diag_offset=0, want_sumscore=True):
     """score_dir_fwd(..., lq_b=lq_b)"""
     return score_dir_fwd(A, Bm, inv_t, shift, diag_offset, want_sumscore, lq_b=lq_b)

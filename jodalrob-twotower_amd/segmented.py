@@ -91,6 +91,7 @@ class SegmentedTrainStep(GraphedTrainStep):
     _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
     _entity_ok = False             # the repeated-entity mask likewise
     _pair_weight_ok = False        # pair weights likewise
+    _negatives_ok = False          # extra negatives likewise
 
     segmented = True
 

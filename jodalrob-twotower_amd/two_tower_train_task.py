@@ -18,6 +18,8 @@ import torch.nn as nn
 
 from . import ops
 from .config import settings
+from .kjt import KeyedJaggedTensor
+from .towers import run_towers
 from .two_tower_model import TwoTowerModel, create_two_tower_model
 
 LAZY_SIM_BATCH = 2048
@@ -57,16 +59,23 @@ class _ScoreCEFn(torch.autograd.Function):
     only; combines with lq_n / lq_c; metrics on the raw scores.
     pair_w (f32 [B] raw per-pair sample weights): the weighted mean of the pairs' terms (include/twotower.h *_pw entries) -- entries
     that are not positive finite numbers count as 0; score_dtype 'bf16' and 'fp32' only; combines with lq_* and ent_*; the sums and
-    the metrics are the unweighted ones."""
+    the metrics are the unweighted ones.
+    x (f32 [M, D] unit rows, with optional lq_x f32 [M] / ent_x int32 [M]): shared extra negatives (include/twotower.h *_xneg
+    entries) -- M more columns of every notice's row-direction softmax, no positive, no column sum; an extra is masked for row a iff
+    ent_x[m] == ent_c[a]; score_dtype 'bf16' and 'fp32' only; combines with lq_* and ent_*, not with pair_w.  The node packs N, C and
+    X itself.  accuracy / row_rank are over the B + M scores, the other metrics the in-batch ones."""
 
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
-                lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None):
+                lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None, x=None, lq_x=None, ent_x=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
         lq = lq_n is not None
         fp8, x3 = score_dtype == "fp8", score_dtype == "bf16x3"
+        if x is not None:
+            return _ScoreCEFn._forward_xneg(ctx, n, c, inv_t, score_dtype, want_col_rank, lq_n, lq_c, ent_n, ent_c, pair_w, x, lq_x, ent_x)
+        ctx.xn = None
         ent = None
         if ent_n is not None or ent_c is not None:
             if fp8 or x3:
@@ -143,11 +152,72 @@ class _ScoreCEFn(torch.autograd.Function):
         return loss, out8, row_rank
 
     @staticmethod
+    def _forward_xneg(ctx, n, c, inv_t, score_dtype, want_col_rank, lq_n, lq_c, ent_n, ent_c, pair_w, x, lq_x, ent_x):
+        """forward with shared extra negatives x [M, D]: always the symmetric sweep (bf16) or the directional sweeps plus the extras'
+        rectangular one (fp32)"""
+        B, D = n.shape
+        dev, shift, lq = n.device, abs(inv_t), lq_n is not None
+        if score_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"extra negatives have no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
+        if pair_w is not None:
+            raise ValueError("extra negatives do not combine with pair weights")
+        if c.shape != n.shape:
+            raise ValueError("extra negatives need as many notice rows as company rows")
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1 or x.device != dev:
+            raise ValueError(f"the extra negatives must be a [M >= 1, {D}] tensor on {dev}")
+        x = x.contiguous().float()
+        M = x.shape[0]
+        ent = exs = None
+        if ent_n is not None or ent_c is not None:
+            ent = ops.score_mask_ids(ent_n, ent_c, B, dev)
+        if ent_x is not None:
+            if ent_c is None:
+                raise ValueError("the extras' entity ids are compared with the batch's company ids: ent_c is missing")
+            exs = ops.score_xneg_ids(ent_x, M, dev)
+        if lq:
+            ops._lq_check_t(inv_t)
+            if lq_x is None:                                 # a missing log_q on the extras counts as zeros
+                lq_x = torch.zeros(M, dtype=torch.float32, device=dev)
+        elif lq_x is not None:
+            raise ValueError("the extras carry log_q but the batch is not corrected")
+        w = None
+        if score_dtype == "bf16":
+            scale_n = ops.score_unit_scale(inv_t)
+            Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
+            Xp = ops.score_pack_bf16(x, 1.0)
+            rowsum, colsum, diag, row_rank, inv, w, w_x, out8, loss = ops.score_fwd_sym_xneg(Np, Cp, Xp, B, M, D, inv_t, shift, ent, exs, lq_n, lq_c,
+                                                                                             lq_x, scale_n, True)
+            if want_col_rank:                                # the first call's column top-1 rate (a diagnostic only)
+                col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n)[4]
+                out8 = out8.clone()
+                out8[5] = (col_rank == 0).float().mean()
+            ctx.packed = (Np, Cp, scale_n, inv)
+            ctx.xn = (Xp, w_x, exs, None)
+        else:
+            rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c, ent=ent)
+            colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n, ent=ent)
+            ops.score_dir_fwd_xneg(n, x, inv_t, shift, diag, rowsum, row_rank, lq_x=lq_x, ent_c=ent[1] if exs is not None else None,
+                                   ent_x=exs)
+            if lq:
+                w = (lq_n.contiguous(), lq_c.contiguous())
+            out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c)
+            ctx.packed = None
+            ctx.xn = (None, None, exs, lq_x)
+        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = False, False, w, ent, None
+        ctx.save_for_backward(n, c, rowsum, colsum, x)
+        ctx.inv_t, ctx.shift = inv_t, shift
+        ctx.mark_non_differentiable(out8, row_rank)
+        ctx.set_materialize_grads(False)
+        return loss, out8, row_rank
+
+    @staticmethod
     def backward(ctx, d_loss, _d_out8, _d_rank):
+        if ctx.xn is not None:
+            return _ScoreCEFn._backward_xneg(ctx, d_loss)
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return (None,) * 14
+            return (None,) * 17
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
@@ -159,7 +229,33 @@ class _ScoreCEFn(torch.autograd.Function):
             lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
             dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent, pw=ctx.pw)
             dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent, pw=ctx.pw)
-        return (dN, dC) + (None,) * 12
+        return (dN, dC) + (None,) * 15
+
+    @staticmethod
+    def _backward_xneg(ctx, d_loss):
+        """the square backward on the forward's sums (which include the extras), then the extras' two rectangular directions: dN +=
+        and dX, in this order"""
+        n, c, rowsum, colsum, x = ctx.saved_tensors
+        B, D = n.shape
+        M = x.shape[0]
+        if d_loss is None:
+            return (None,) * 17
+        if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
+            d_loss = d_loss.contiguous().float()
+        scale = ctx.inv_t / (2.0 * B)
+        Xp, w_x, exs, lq_x = ctx.xn
+        ec = ctx.ent[1] if exs is not None else None
+        if ctx.packed is not None:
+            Np, Cp, scale_n, inv = ctx.packed
+            dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, w=ctx.lq, ent=ctx.ent)
+            dX = ops.score_bwd_bf16_xneg(Np, Xp, B, M, D, ctx.inv_t, ctx.shift, inv[0], w_x, d_loss, scale, dN, scale_n, ent_c=ec, ent_x=exs)
+        else:
+            lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
+            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent)
+            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent)
+            ops.score_dir_bwd_xneg(n, x, ctx.inv_t, ctx.shift, True, rowsum, d_loss, scale, lq_x=lq_x, ent_a=ec, ent_b=exs, out=dN)
+            dX = ops.score_dir_bwd_xneg(x, n, ctx.inv_t, ctx.shift, False, rowsum, d_loss, scale, lq_x=lq_x, ent_a=exs, ent_b=ec)
+        return (dN, dC) + (None,) * 12 + (dX, None, None)
 
 
 class _Result(dict):
@@ -236,8 +332,14 @@ class TwoTowerTrainTask(nn.Module):
         lq = self._batch_log_q(notice_input, company_input, nb)
         ent = self._batch_entity(notice_input, company_input, nb)
         pw = self._batch_pair_weight(batch, nb)
-        notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
-        if pw is not None:
+        neg = self._batch_negatives(batch, company_input, nb, lq, ent, pw)
+        if neg is not None:
+            notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, neg, nb, lq, ent)
+        else:
+            notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
+        if neg is not None:
+            pass                                             # (scored above, with the extras)
+        elif pw is not None:
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
                                            not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw)
         elif ent is not None:
@@ -268,6 +370,8 @@ class TwoTowerTrainTask(nn.Module):
         and ranks its similarity matrix).  Ranks come from the exact-f32 score sweep, as diagonal_ranks()."""
         if batch.get("pair_weight") is not None:
             raise ValueError("forward_with_ranks does not take a batch with 'pair_weight' (evaluation is unweighted)")
+        if batch.get("negatives") is not None:
+            raise ValueError("forward_with_ranks does not take a batch with 'negatives' (evaluation ranks the batch's own companies)")
         with torch.no_grad():
             n, c = self.two_tower_model(batch["notice"], batch["company"])
             if n.size(0) != c.size(0):
@@ -346,6 +450,67 @@ class TwoTowerTrainTask(nn.Module):
         if t.device != ref.device:
             raise ValueError(f"batch['pair_weight'] is on {t.device}, the batch on {ref.device}")
         return t
+
+    def _forward_negatives(self, notice_input, company_input, neg, B, lq, ent):
+        """(notice embeddings, company embeddings, loss, out8) of a batch with shared extra negatives: the M rows ride behind the batch's
+        companies through ONE company-tower pass (in train mode its BatchNorm batch statistics run over the B + M rows), the output is
+        split into C and X, and the score node takes X as M more columns of every notice's row-direction softmax"""
+        both = {"dense": torch.cat([company_input["dense"], neg["dense"]], 0),
+                "kjt": KeyedJaggedTensor(company_input["kjt"].keys(), torch.cat([company_input["kjt"].values(), neg["kjt"].values()], 0))}
+        n_emb, cx = run_towers([self.two_tower_model.notice_tower, self.two_tower_model.company_tower], [notice_input, both])
+        c_emb, x_emb = cx[:B], cx[B:]
+        lqs, ents = lq if lq is not None else (None, None), ent if ent is not None else (None, None)
+        loss, out8, _ = _ScoreCEFn.apply(n_emb, c_emb, 1.0 / float(self.temperature), self.score_dtype, not hasattr(self, "_pair_check_done"),
+                                         False, None, None, None, lqs[0], lqs[1], ents[0], ents[1], None, x_emb, neg.get("log_q"),
+                                         neg.get("entity"))
+        return n_emb, c_emb, loss, out8
+
+    def _negatives_ok(self):
+        """may a batch carry 'negatives'?  (the sharded task overrides it)"""
+        return True
+
+    def _batch_negatives(self, batch, company_input, B, lq, ent, pw):
+        """batch["negatives"] validated -- {"dense" [M, Dc], "kjt"} with optional "log_q" f32 [M] and "entity" int32 [M], M >= 1 company
+        rows every notice of the batch is contrasted with besides the in-batch ones -- or None when the batch carries none.  Refuses
+        what the loss with extras does not cover -- never ignores the entry."""
+        neg = batch.get("negatives")
+        if neg is None:
+            return None
+        if not self._negatives_ok():
+            raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
+        if pw is not None:
+            raise ValueError("extra negatives (a batch with 'negatives') do not combine with 'pair_weight'")
+        if self._dense_loss:
+            raise ValueError("extra negatives (a batch with 'negatives') are not supported by the dense loss path "
+                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
+        if self.score_dtype in ("fp8", "bf16x3"):
+            raise ValueError(f"extra negatives (a batch with 'negatives') are not supported for score_dtype={self.score_dtype!r}")
+        ref = company_input["dense"]
+        d = neg.get("dense") if isinstance(neg, dict) else None
+        if not isinstance(d, torch.Tensor) or d.dim() != 2 or d.shape[1] != ref.shape[1] or d.dtype != ref.dtype or "kjt" not in neg:
+            raise ValueError(f"batch['negatives'] must be a company-side input {{'dense' [M, {ref.shape[1]}] {ref.dtype}, 'kjt'}}")
+        M = d.shape[0]
+        if M < 1:
+            raise ValueError("batch['negatives'] must hold at least one row (M >= 1)")
+        if d.device != ref.device:
+            raise ValueError(f"batch['negatives']['dense'] is on {d.device}, the batch on {ref.device}")
+        K = len(company_input["kjt"].keys())
+        v = neg["kjt"].values()
+        if list(neg["kjt"].keys()) != list(company_input["kjt"].keys()) or v.numel() != M * K or v.device != ref.device:
+            raise ValueError(f"batch['negatives']['kjt'] must carry the company side's {K} keys for {M} rows on {ref.device}")
+        for name, dt, given in (("log_q", torch.float32, lq is not None), ("entity", torch.int32, ent is not None and ent[1] is not None)):
+            t = neg.get(name)
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.shape[0] != M:
+                raise ValueError(f"batch['negatives']['{name}'] must be a {str(dt).replace('torch.', '')} tensor of shape [{M}], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            if t.device != ref.device:
+                raise ValueError(f"batch['negatives']['{name}'] is on {t.device}, the batch on {ref.device}")
+            if not given:
+                raise ValueError(f"batch['negatives']['{name}'] needs batch['company']['{name}']: the extras' {name} has nothing to be "
+                                 "compared with")
+        return neg
 
     def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None):
         """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it.

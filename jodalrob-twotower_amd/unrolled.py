@@ -31,6 +31,7 @@ class UnrolledTrainStep(GraphedTrainStep):
     _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
     _entity_ok = False             # the repeated-entity mask likewise
     _pair_weight_ok = False        # pair weights likewise
+    _negatives_ok = False          # extra negatives likewise
 
     def __init__(self, task, optimizer, example_batch: Dict, unroll: int = 2, **kw):
         if int(unroll) < 2:

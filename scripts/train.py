@@ -115,6 +115,11 @@ def main():
     ap.add_argument("--logq-correction", action="store_true",
                     help="logQ sampling-bias correction of the in-batch softmax: log sampling probabilities estimated from the TRAIN pairs, "
                          "attached to the train loader only (evaluation stays uncorrected)")
+    ap.add_argument("--extra-negatives", type=int, default=0, metavar="M",
+                    help="shared extra negatives: every train batch carries M more company rows, drawn uniformly from the company store, "
+                         "that every notice of the batch is contrasted with besides the in-batch companies (mixed negative sampling); "
+                         "combines with --mask-repeats and --logq-correction, not with --pair-weight; with --fast the captured step takes "
+                         "them through its plain-copy hand-over")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
     a = ap.parse_args()
     config = {"batch_size": a.batch_size, "test_split": 0.2, "shuffle_seed": 42, "pair_limit": a.pairs,
@@ -157,6 +162,8 @@ def main():
         tp = train_loader.pairs
         train_loader.set_log_q((log_sampling_probs(tp[:, 0], len(train_loader.notice)),
                                 log_sampling_probs(tp[:, 1], len(train_loader.company))))
+    if a.extra_negatives:
+        train_loader.set_extra_negatives(a.extra_negatives)
     train_task = create_two_tower_train_task(schema.notice.categorical, schema.company.categorical, metadata_path=str(meta),
                                              categorical_embedding_dim=config["categorical_embedding_dim"],
                                              notice_dense_input_dim=config["notice_dense_input_dim"],
@@ -190,9 +197,10 @@ def main():
     if a.fast and len(train_loader) > 1:                 # (a loader of one ragged batch has nothing to capture)
         from jodalrob_twotower_amd.graph import GraphedTrainStep
         train_task.train()
-        state = train_loader._gen.get_state()
+        state, neg_state = train_loader._gen.get_state(), train_loader._neg_gen.get_state()
         example = next(iter(train_loader))               # shapes only: the capture's warm-up steps leave no trace (preserve_state)
         train_loader._gen.set_state(state)
+        train_loader._neg_gen.set_state(neg_state)
         graphed = GraphedTrainStep(train_task, optimizer, example, warmup=1, accumulate_metrics=True)
         rag = train_loader.ragged_example()              # the epoch's last, smaller batch gets a captured step of its own size:
         if rag is not None and rag["notice"]["dense"].shape[0] >= 2:       # launched eagerly it costs six full steps of host time
