@@ -34,7 +34,10 @@ class EmbeddingStore:
         self.grad_mode = grad_mode
         self.weight: Optional[torch.Tensor] = None      # [R, E] f32
         self.grad: Optional[torch.Tensor] = None        # dense mode: [R, E]
-        self.sparse_grad = None                         # sparse mode: (DedupPlan, grad_rows [M, E])
+        # sparse mode: the gradients waiting for the optimiser, [(member embedders or None = the whole store, DedupPlan, grad_rows
+        # [M, E])].  Entries over disjoint embedders coexist (towers passes of different batch sizes, or two autograd nodes, file one
+        # per side): their rows are disjoint.  A new entry replaces every entry it overlaps: the latest backward wins (file_sparse_grad)
+        self._sparse_pending: list = []
         self.defer_long_finish = False                  # GraphedTrainStep: the optimiser's launch finishes the long rows
         self.members: List["CategoricalEmbedder"] = []
         self.version = 0
@@ -46,6 +49,32 @@ class EmbeddingStore:
         # one pass (`ingest_x_fresh`), because an optimiser step in between changes the table rows they were copied from.
         self.ingest = None
         self.ingest_x_fresh = False
+
+    # ---- sparse mode: the pending gradients ------------------------------------------------------
+    def sparse_grads(self) -> list:
+        """Every pending (DedupPlan, grad_rows [M, E]), in the order of their embedders' first row (whichever order autograd ran
+        the nodes in).  The optimiser applies each with the same step number: disjoint rows, so that is exactly one step."""
+        key = lambda e: min((m.row_base for m in e[0]), default=0) if e[0] is not None else 0
+        return [(plan, rows) for _, plan, rows in sorted(self._sparse_pending, key=key)]
+
+    @property
+    def sparse_grad(self):
+        """The pending (DedupPlan, grad_rows) of a step that filed ONE gradient (every towers pass whose sides share a batch size
+        does), None when nothing is pending.  With several pending entries there is no single pair: read sparse_grads()."""
+        if len(self._sparse_pending) > 1:
+            raise RuntimeError(f"{len(self._sparse_pending)} sparse gradients are pending on this store: read sparse_grads()")
+        return self._sparse_pending[0][1:] if self._sparse_pending else None
+
+    @sparse_grad.setter
+    def sparse_grad(self, pair):
+        self._sparse_pending = [] if pair is None else [(None, pair[0], pair[1])]
+
+    def file_sparse_grad(self, plan, grad_rows, members=None):
+        """File a gradient over the rows of `members` (embedders of this store; None: the whole store).  It replaces every pending
+        entry that covers one of them -- sparse mode does not accumulate across backward passes -- and joins the others."""
+        ids = None if members is None else {id(m) for m in members}
+        keep = [e for e in self._sparse_pending if ids is not None and e[0] is not None and ids.isdisjoint(id(m) for m in e[0])]
+        self._sparse_pending = keep + [(None if members is None else tuple(members), plan, grad_rows)]
 
     def rows_km_for(self, id_tensors) -> Optional[torch.Tensor]:
         """The key-major rows of ops.batch_ingest if they describe exactly `id_tensors` as they are now, else None."""
@@ -139,13 +168,14 @@ class EmbeddingStore:
             m._bind_grads()
 
     # ---- gradient bookkeeping (called from the autograd backward) ------------------------------
-    def accumulate_grad(self, plan: ops.DedupPlan, srcs, B: int, short_segments: bool = False):
-        """srcs: [(d_out view [B, K*E], K)] in slot order of `plan`."""
+    def accumulate_grad(self, plan: ops.DedupPlan, srcs, B: int, short_segments: bool = False, members=None):
+        """srcs: [(d_out view [B, K*E], K)] in slot order of `plan`.  members: the embedders whose rows `plan` covers (None: the
+        whole store) -- sparse mode files the gradient under them (file_sparse_grad)."""
         if self.grad_mode == "sparse":
             grad_rows = torch.empty((max(plan.M, 1), self.E), dtype=torch.float32, device=self.device)
             ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_SPARSE, grad_rows, short_segments, self.grad_counters(),
                            defer_finish=self.defer_long_finish)
-            self.sparse_grad = (plan, grad_rows)
+            self.file_sparse_grad(plan, grad_rows, members)
             return
         params = self.optim_parameters()
         fresh = any(p.grad is None for p in params) or self.grad is None
@@ -336,7 +366,7 @@ class _LookupFn(torch.autograd.Function):
         emb = ctx.emb
         if ctx.plan is not None:
             d_out = d_out.contiguous()
-            emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B)
+            emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B, members=[emb])
         return (None, None) + (None,) * len(emb.keys)
 
 

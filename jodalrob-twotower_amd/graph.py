@@ -321,8 +321,8 @@ class GraphedTrainStep:
                     L.set_defer_slab_reduce(dev, False)      # (flushes)
             self.opt.step()
             for st in stores:                          # a store this optimiser did not step: nobody else will finish its gradient
-                if st.sparse_grad is not None:
-                    ops.embed_grad_finish(st.sparse_grad[0])
+                for plan, _ in st.sparse_grads():
+                    ops.embed_grad_finish(plan)
             if self.metric_sums is not None:           # (behind the backward: a riding loss reduction has written out8 by now)
                 self.metric_sums.add_(res.out8)
         finally:

@@ -204,7 +204,8 @@ class FusedAdam(torch.optim.Optimizer):
             st = self._state_of(store)
             sparse, rowwise = store.grad_mode == "sparse", _kind(group) == "rowwise_adagrad"
             if sparse:
-                pending = store.sparse_grad is not None      # (None also once a fused launch above has applied it)
+                entries = store.sparse_grads()               # (empty also once a fused launch above has applied the one entry)
+                pending = bool(entries)
             else:
                 pending = store.grad is not None and all(p.grad is not None for p in members)
             if not pending:
@@ -212,11 +213,13 @@ class FusedAdam(torch.optim.Optimizer):
             st["step"] += 1
             lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
             if sparse:
-                plan, grad_rows = store.sparse_grad
-                if rowwise:
-                    ops.rowwise_adagrad_sparse(store.weight, st["sum"], plan, grad_rows, lr, eps, wd, hp)
-                else:
-                    ops.adam_sparse(store.weight, st["m"], st["v"], plan, grad_rows, st["step"], lr, b1, b2, eps, wd, hp)
+                # several entries (one per side of a pass with unequal batch sizes, one per autograd node): disjoint rows, each
+                # applied at the SAME step number -- one step of the store
+                for plan, grad_rows in entries:
+                    if rowwise:
+                        ops.rowwise_adagrad_sparse(store.weight, st["sum"], plan, grad_rows, lr, eps, wd, hp)
+                    else:
+                        ops.adam_sparse(store.weight, st["m"], st["v"], plan, grad_rows, st["step"], lr, b1, b2, eps, wd, hp)
                 store.sparse_grad = None
             elif rowwise:
                 ops.rowwise_adagrad_dense(store.weight, st["sum"], store.grad, lr, eps, wd, hp)
@@ -243,7 +246,8 @@ class FusedAdam(torch.optim.Optimizer):
         if len(cands) != 1:
             return None
         store, tgroup = cands[0]
-        if store.grad_mode != "sparse" or store.sparse_grad is None or store.sparse_grad[0].M < 1:
+        pending = store.sparse_grads() if store.grad_mode == "sparse" else []
+        if len(pending) != 1 or pending[0][0].M < 1:          # (several pending entries: the per-store branch applies each)
             return None
         st = self._state_of(store)
         return (store, st, tgroup) if tgroup is not group or st["step"] + 1 == s_no else None

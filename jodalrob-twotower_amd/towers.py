@@ -522,7 +522,9 @@ class _TowersFn(torch.autograd.Function):
                 if d is None:       # this tower received no gradient: contribute zeros
                     d = torch.zeros((s.B, K * store.E), dtype=s.tower.dx_dtype, device=store.device)
                 srcs.append((d, K))
-            store.accumulate_grad(plan, srcs, plan_sides[0].B)
+            # (filed under the sides' embedders: the per-side plans of a pass with unequal batch sizes, or of two passes over one
+            # store, each keep their gradient until the optimiser steps)
+            store.accumulate_grad(plan, srcs, plan_sides[0].B, members=[s.tower.categorical_embedder for s in plan_sides])
         return (None, *grads)
 
 

@@ -210,7 +210,8 @@ def test_xneg_eager_task_is_the_node_on_the_tower_outputs(tt, manifest, score_dt
 
 
 def test_xneg_trains_the_extras_table_rows(tt, manifest):
-    """a company id that only an extra carries: its embedding row moves in an eager step, a row nobody carries does not"""
+    """a company id that only an extra carries: its embedding row moves in an eager step, a row nobody carries does not; on the notice
+    side of the same store a row the batch carries moves too, and one nobody carries does not"""
     from jodalrob_twotower_amd.optim import FusedAdam
     from jodalrob_twotower_amd.kjt import KeyedJaggedTensor
     task, b, B = _small_task(tt, manifest, score_dtype="bf16")
@@ -228,6 +229,15 @@ def test_xneg_trains_the_extras_table_rows(tt, manifest):
     v[2, 0] = only_extra
     bn["negatives"]["kjt"] = KeyedJaggedTensor(b["company"]["kjt"].keys(), v.reshape(-1))
     before = emb.embeddings[key0].weight.detach().clone()
+    # the notice side of the same store: an id the batch carries, and one nobody carries
+    nemb = task.two_tower_model.notice_tower.categorical_embedder
+    nkey, Kn = nemb.keys[-1], len(nemb.keys)
+    n_ids = bn["notice"]["kjt"].values().view(B, Kn)[:, -1]
+    Vn = nemb.embeddings[nkey].weight.shape[0]
+    n_carried = int(n_ids[0])
+    n_nobody = next(i for i in range(Vn) if not bool((n_ids == i).any()))
+    assert 0 <= n_carried < Vn
+    n_before = nemb.embeddings[nkey].weight.detach().clone()
     opt = FusedAdam.for_task(task, lr=1e-2, weight_decay=0.0)
     opt.zero_grad()
     task(bn).backward()
@@ -236,6 +246,9 @@ def test_xneg_trains_the_extras_table_rows(tt, manifest):
     after = emb.embeddings[key0].weight.detach()
     assert not torch.equal(after[only_extra], before[only_extra])
     assert torch.equal(after[nobody], before[nobody])
+    n_after = nemb.embeddings[nkey].weight.detach()
+    assert not torch.equal(n_after[n_carried], n_before[n_carried])
+    assert torch.equal(n_after[n_nobody], n_before[n_nobody])
 
 
 def _decorated(b, B, seed):
