@@ -926,6 +926,31 @@ int tt_filt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const flo
                               const int64_t* excl_offsets, const int32_t* excl_rows, const uint32_t* tags, int32_t W,
                               const uint32_t* q_any, const uint32_t* q_all, void* workspace, size_t workspace_bytes,
                               tt_stream stream);
+/* Retrieval under a per-query score ceiling (hard-negative mining): the exclusion entries with `ceil` after `excl_rows`.
+ *   ceil f32 [nQ], required, 4-byte aligned: a row with s(q, c) >= ceil[q] never enters query q's top-k, so the k slots hold the
+ *   best rows BELOW the ceiling (value descending, ties to the lower index; slots beyond them are -inf / -1).  A tie with the
+ *   ceiling is removed.  ceil[q] = +inf or NaN removes nothing, -inf removes every row.
+ *   rank: unchanged -- the positive's place among all rows outside E_q; the ceiling bounds the top-k only.
+ *   excl_offsets and excl_rows may both be NULL (no lists); one NULL and one not is an error.
+ * With every ceiling +inf the results are bitwise those of the plain entry (with lists: of the exclusion entry); they are bitwise
+ * identical across runs and split counts.  Same workspace (tt_retrieve_workspace_bytes), launches and graph capture rules as the
+ * plain entries.  A bad argument returns TT_ERR_INVALID_ARG and launches nothing. */
+int tt_ceil_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, const float* ceil, void* workspace,
+                               size_t workspace_bytes, tt_stream stream);
+int tt_ceil_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, const float* ceil, void* workspace,
+                              size_t workspace_bytes, tt_stream stream);
+/* Scores of given (query, catalogue row) pairs: out[q] = s(q, rows[q]), f32 [nQ], bit for bit the score the retrieval sweep forms
+ * for that pair (the same images, scales and instruction sequence: the retrieval entries' positive-score launch, writing to the
+ * caller).  rows [nQ] int32 (rows_i64 = 0) or int64 (1); NaN where rows[q] is outside [0, nC).  One launch on `stream`, no
+ * workspace, no synchronisation.  Operands as tt_retrieve_topk_bf16 / _f32. */
+int tt_pair_scores_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                        const void* rows, int32_t rows_i64, float* out, tt_stream stream);
+int tt_pair_scores_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                       const void* rows, int32_t rows_i64, float* out, tt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Generic Linear used by the one-off feature projection -- replaces FeatureProjector.forward

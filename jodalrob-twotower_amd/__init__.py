@@ -18,9 +18,11 @@ from .feature_preprocessor import FeaturePreprocessor                           
 from .evaluator import TwoTowerEvaluator                                          # noqa: F401
 from .optim import FusedAdam                                                      # noqa: F401
 from .retrieval import CatalogIndex                                               # noqa: F401
+from .hard_negatives import MinedNegatives, mine_hard_negatives                   # noqa: F401
 
 __all__ = ["KeyedJaggedTensor", "build_batch_kjt", "SideSchema", "PairSchema", "TorchRecSchema",
            "build_torchrec_schema_from_meta", "classify_columns", "CategoricalEmbedder", "EmbeddingStore",
            "create_categorical_embedder", "BaseTower", "NoticeTower", "CompanyTower", "TwoTowerModel",
            "create_two_tower_model", "TwoTowerTrainTask", "create_two_tower_train_task", "FeatureProjector",
-           "FeaturePreprocessor", "TwoTowerEvaluator", "FusedAdam", "CatalogIndex"]
+           "FeaturePreprocessor", "TwoTowerEvaluator", "FusedAdam", "CatalogIndex", "MinedNegatives",
+           "mine_hard_negatives"]

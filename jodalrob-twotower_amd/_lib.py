@@ -207,6 +207,10 @@ SIGNATURES = {
     "tt_filt_retrieve_topk_bf16": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
     "tt_filt_retrieve_topk_f32": (C.c_int, [vp, vp, i64, vp, i64, i32, f32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz,
                                             vp]),
+    "tt_ceil_retrieve_topk_bf16": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "tt_ceil_retrieve_topk_f32": (C.c_int, [vp, vp, i64, vp, i64, i32, f32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "tt_pair_scores_bf16": (C.c_int, [vp, vp, i64, vp, i64, i32, vp, i32, vp, vp]),
+    "tt_pair_scores_f32": (C.c_int, [vp, vp, i64, vp, i64, i32, f32, vp, i32, vp, vp]),
     "tt_linear_fwd": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, i64, i32, i32, i32, vp]),
     "tt_route_workspace_bytes": (sz, [i64, i32]),
     "tt_route_bucket": (C.c_int, [vp, vp, vp, i64, i32, i32, C.POINTER(i32), i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -27,6 +27,12 @@
 // the same point as the excluded ones.  A tile's 32 W tag words are contiguous: the wave reads them with one coalesced load
 // (W > 2: two, 16 rows each) a tile ahead, one word per lane, and every lane fetches the words of its 16 rows with ds_bpermute.
 //
+// Score ceilings (tt_ceil_retrieve_topk_*: the sweep's CEIL = true instantiations): query q's scores at or above ceil[q] leave its
+// top-k -- after the rank counts, which never see the ceiling, and before the k-th-best filter, so that the k slots go to the best
+// rows BELOW the ceiling (hard-negative mining under a positive-aware ceiling).  One register and one compare per score; a NaN
+// ceiling compares false and removes nothing.  tt_pair_scores_* is the pos launch alone, writing to the caller: the score of a
+// (query, row) pair exactly as the sweep forms it, which is what such a ceiling is derived from.
+//
 // k up to 512 (the sweep's and the merge's BIGK = true instantiations, k > 64): the same sweep with one wave per workgroup and
 // a region of ret_big_slots(k) slots per query, up to the CU's whole 160 KB of LDS at k > 256; the splits are capped so that
 // S k <= 2048, which keeps the merge's selection and the workspace of the k = 64 call.  k <= 64 runs the code it always ran.
@@ -154,6 +160,7 @@ struct RetArgs {
   const uint32_t* q_any;      // [nQ][W] or NULL: a row must share a bit with a non-zero mask
   const uint32_t* q_all;      // [nQ][W] or NULL: a row must hold every bit of the mask
   int W;                      // 1 .. 4
+  const float* ceil;          // [nQ] score ceilings (CEIL sweep only): s >= ceil[q] never enters query q's top-k
 };
 
 __device__ __forceinline__ int64_t positive_of(const RetArgs& a, int64_t q) { return a.pos64 ? a.pos64[q] : (int64_t)a.pos32[q]; }
@@ -207,7 +214,8 @@ __device__ __forceinline__ void filter_tile(f32x16& acc, int h, uint32_t tg0, ui
 // ---- sweep ------------------------------------------------------------------------------------------------------------------
 // BIGK (64 < k <= 512): one wave per workgroup and ret_big_slots(k) slots per query, up to the CU's whole 160 KB; select() skips
 // the key bits its bounds share.  Everything else -- tiles, EXCL / FILT steps, the filter, the rank counts -- is the k <= 64 form's.
-template <class Tile, bool EXCL, bool FILT, bool BIGK>
+// CEIL: the per-query score ceiling of the top-k (built without FILT only).
+template <class Tile, bool EXCL, bool FILT, bool BIGK, bool CEIL = false>
 __global__ __launch_bounds__((BIGK ? 1 : kRetWaves) * 64) void retrieve_sweep_kernel(Tile tile, RetArgs a) {
   constexpr int NW = BIGK ? 1 : kRetWaves;
   extern __shared__ uint32_t ret_lds[];
@@ -276,8 +284,10 @@ __global__ __launch_bounds__((BIGK ? 1 : kRetWaves) * 64) void retrieve_sweep_ke
     }
     load_tags(tb);
   }
+  float cl = INFINITY;                                          // CEIL: the query's ceiling (a lane past nQ keeps nothing)
+  if constexpr (CEIL) cl = qok ? a.ceil[q] : -INFINITY;
   int rcnt = 0;
-  float thr = -INFINITY;                                        // the query's k-th best so far (both lanes of a query agree)
+  float thr = -INFINITY;                                       // the query's k-th best so far (both lanes of a query agree)
   int cnt = 0;                                                  // filled slots of the query's region
   float top = -INFINITY;                                        // BIGK: no score this lane put into the region exceeds it
 
@@ -414,6 +424,10 @@ __global__ __launch_bounds__((BIGK ? 1 : kRetWaves) * 64) void retrieve_sweep_ke
           rcnt += (acc[r] > sp || (acc[r] == sp && row < p)) ? 1 : 0;
         }
       }
+    }
+    if constexpr (CEIL) {                                       // after the rank counts: the rank is among all eligible rows
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = acc[r] >= cl ? -INFINITY : acc[r];   // (a NaN ceiling: false, nothing goes)
     }
     if (want_topk) {
       float m = max3_asm(acc[0], acc[1], acc[2]);
@@ -578,13 +592,14 @@ bool ret_shape_ok(int64_t nQ, int64_t nC, int D, int k) {
   return nQ >= 1 && nC >= 1 && nC < (int64_t(1) << 31) && D >= 1 && D <= 256 && k >= 0 && k <= kRetMaxK && k <= nC;
 }
 
-struct RetFilt {              // attribute filter of a call (tags == NULL: none)
+struct RetFilt {              // attribute filter of a call (tags == NULL: none), or its score ceilings (ceil == NULL: none)
   const uint32_t* tags;
   int32_t W;
   const uint32_t* q_any;
   const uint32_t* q_all;
+  const float* ceil;
 };
-constexpr RetFilt kNoFilt{nullptr, 0, nullptr, nullptr};
+constexpr RetFilt kNoFilt{nullptr, 0, nullptr, nullptr, nullptr};
 
 template <class Tile>
 int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k, const void* positives,
@@ -624,6 +639,7 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   a.q_any = flt.q_any;
   a.q_all = flt.q_all;
   a.W = flt.W;
+  a.ceil = flt.ceil;
   if (positives) {
     retrieve_pos_kernel<Tile><<<(unsigned)nQt, 64, 0, st>>>(tile, a);
     TT_LAUNCH_CHECK();
@@ -632,18 +648,21 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   if (k > kRetSmallK) {                                         // large-k form: one wave per workgroup, up to the CU's whole LDS
     const size_t lds = (size_t)ret_big_slots(k) * 32 * 8;
     const dim3 grid((unsigned)nQt, (unsigned)S);
-#define TT_RET_BIG(E, F)                                                                 \
+#define TT_RET_BIG(E, ...)                                                               \
   do {                                                                                   \
-    TT_LDS_ONCE(kRetBigLds, &retrieve_sweep_kernel<Tile, E, F, true>);                   \
-    retrieve_sweep_kernel<Tile, E, F, true><<<grid, 64, lds, st>>>(tile, a);             \
+    TT_LDS_ONCE(kRetBigLds, &retrieve_sweep_kernel<Tile, E, __VA_ARGS__>);               \
+    retrieve_sweep_kernel<Tile, E, __VA_ARGS__><<<grid, 64, lds, st>>>(tile, a);         \
   } while (0)
-    if (flt.tags) {
-      if (excl_off) TT_RET_BIG(true, true);
-      else TT_RET_BIG(false, true);
+    if (flt.ceil) {
+      if (excl_off) TT_RET_BIG(true, false, true, true);
+      else TT_RET_BIG(false, false, true, true);
+    } else if (flt.tags) {
+      if (excl_off) TT_RET_BIG(true, true, true);
+      else TT_RET_BIG(false, true, true);
     } else if (excl_off) {
-      TT_RET_BIG(true, false);
+      TT_RET_BIG(true, false, true);
     } else {
-      TT_RET_BIG(false, false);
+      TT_RET_BIG(false, false, true);
     }
 #undef TT_RET_BIG
     TT_LAUNCH_CHECK();
@@ -655,7 +674,10 @@ int ret_launch(tt_ctx* ctx, const Tile& tile, int64_t nQ, int64_t nC, int32_t k,
   }
   const size_t lds = (size_t)kRetWaves * (k + kRetCap) * 32 * 8;
   const dim3 grid((unsigned)tt_cdiv(nQt, kRetWaves), (unsigned)S);
-  if (flt.tags) {
+  if (flt.ceil) {
+    if (excl_off) retrieve_sweep_kernel<Tile, true, false, false, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+    else retrieve_sweep_kernel<Tile, false, false, false, true><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
+  } else if (flt.tags) {
     if (excl_off) retrieve_sweep_kernel<Tile, true, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
     else retrieve_sweep_kernel<Tile, false, true, false><<<grid, kRetWaves * 64, lds, st>>>(tile, a);
   } else if (excl_off) {
@@ -729,6 +751,28 @@ int ret_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC
   return ret_launch(ctx, tile, nQ, nC, k, positives, positives_i64, vals, idx, rank, excl_off, excl_rows, flt, workspace, st);
 }
 
+// tt_pair_scores_*: the pos launch with the caller's rows as positives and the caller's array as sp
+template <int KS>
+TileBf16<KS> pair_tile_bf16(const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D) {
+  TileBf16<KS> tile{};
+  tile.q_rows = view(Q_packed, nQ, D).rows;
+  tile.c_rows = view(C_packed, nC, D).rows;
+  return tile;
+}
+
+template <class Tile>
+int pair_launch(const Tile& tile, int64_t nQ, int64_t nC, const void* rows, int32_t rows_i64, float* out, hipStream_t st) {
+  RetArgs a{};
+  a.nQ = nQ;
+  a.nC = nC;
+  a.pos32 = rows_i64 ? nullptr : reinterpret_cast<const int32_t*>(rows);
+  a.pos64 = rows_i64 ? reinterpret_cast<const int64_t*>(rows) : nullptr;
+  a.sp = out;
+  retrieve_pos_kernel<Tile><<<(unsigned)tt_cdiv(nQ, 32), 64, 0, st>>>(tile, a);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -787,7 +831,7 @@ int tt_filt_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, co
   TT_RET_CHECK_BF16("tt_filt_retrieve_topk_bf16");
   TT_RET_CHECK_FILT("tt_filt_retrieve_topk_bf16");
   return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
-                  RetFilt{tags, W, q_any, q_all}, workspace, reinterpret_cast<hipStream_t>(stream));
+                  RetFilt{tags, W, q_any, q_all, nullptr}, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 int tt_filt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
@@ -799,7 +843,64 @@ int tt_filt_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const flo
   TT_CHECK_ARG(Q && Cm, "tt_filt_retrieve_topk_f32: NULL embeddings");
   TT_RET_CHECK_FILT("tt_filt_retrieve_topk_f32");
   return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
-                 RetFilt{tags, W, q_any, q_all}, workspace, reinterpret_cast<hipStream_t>(stream));
+                 RetFilt{tags, W, q_any, q_all, nullptr}, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ceiling entries: the exclusion pair both given or both NULL, the ceilings required
+#define TT_RET_CHECK_CEIL(NAME)                                                                                                   \
+  TT_CHECK_ARG(ceil != nullptr && tt_aligned(ceil, 4), NAME ": ceil NULL or not 4-byte aligned");                                \
+  TT_CHECK_ARG((excl_offsets == nullptr) == (excl_rows == nullptr), NAME ": excl_offsets and excl_rows go together");            \
+  TT_CHECK_ARG(tt_aligned(excl_offsets, 8) && tt_aligned(excl_rows, 4), NAME ": excl_offsets not 8- or excl_rows not 4-byte aligned")
+
+int tt_ceil_retrieve_topk_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                               int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                               const int64_t* excl_offsets, const int32_t* excl_rows, const float* ceil, void* workspace,
+                               size_t workspace_bytes, tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_ceil_retrieve_topk_bf16");
+  TT_RET_CHECK_BF16("tt_ceil_retrieve_topk_bf16");
+  TT_RET_CHECK_CEIL("tt_ceil_retrieve_topk_bf16");
+  return ret_bf16(ctx, Q_packed, nQ, C_packed, nC, D, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
+                  RetFilt{nullptr, 0, nullptr, nullptr, ceil}, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int tt_ceil_retrieve_topk_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                              int32_t k, const void* positives, int32_t positives_i64, float* vals, int64_t* idx, int32_t* rank,
+                              const int64_t* excl_offsets, const int32_t* excl_rows, const float* ceil, void* workspace,
+                              size_t workspace_bytes, tt_stream stream) {
+  TT_RET_CHECK_COMMON("tt_ceil_retrieve_topk_f32");
+  TT_CHECK_ARG(Q && Cm, "tt_ceil_retrieve_topk_f32: NULL embeddings");
+  TT_RET_CHECK_CEIL("tt_ceil_retrieve_topk_f32");
+  return ret_f32(ctx, Q, nQ, Cm, nC, D, inv_t, k, positives, positives_i64, vals, idx, rank, excl_offsets, excl_rows,
+                 RetFilt{nullptr, 0, nullptr, nullptr, ceil}, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+#define TT_PAIR_CHECK(NAME)                                                                                                       \
+  TT_CHECK_ARG(ctx != nullptr, NAME ": NULL context");                                                                           \
+  TT_CHECK_ARG(ret_shape_ok(nQ, nC, D, 0), NAME ": bad shape nQ=%lld nC=%lld D=%d (need nQ >= 1, 1 <= nC < 2^31, "               \
+               "1 <= D <= 256)", (long long)nQ, (long long)nC, D);                                                               \
+  TT_CHECK_ARG(rows != nullptr && tt_aligned(rows, rows_i64 ? 8 : 4), NAME ": rows NULL or misaligned");                         \
+  TT_CHECK_ARG(out != nullptr && tt_aligned(out, 4), NAME ": out NULL or not 4-byte aligned")
+
+int tt_pair_scores_bf16(tt_ctx* ctx, const void* Q_packed, int64_t nQ, const void* C_packed, int64_t nC, int32_t D,
+                        const void* rows, int32_t rows_i64, float* out, tt_stream stream) {
+  TT_PAIR_CHECK("tt_pair_scores_bf16");
+  TT_RET_CHECK_BF16("tt_pair_scores_bf16");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Dp = padded_d(D);
+  if (Dp == 32) return pair_launch(pair_tile_bf16<2>(Q_packed, nQ, C_packed, nC, D), nQ, nC, rows, rows_i64, out, st);
+  if (Dp == 64) return pair_launch(pair_tile_bf16<4>(Q_packed, nQ, C_packed, nC, D), nQ, nC, rows, rows_i64, out, st);
+  if (Dp == 128) return pair_launch(pair_tile_bf16<8>(Q_packed, nQ, C_packed, nC, D), nQ, nC, rows, rows_i64, out, st);
+  return pair_launch(pair_tile_bf16<16>(Q_packed, nQ, C_packed, nC, D), nQ, nC, rows, rows_i64, out, st);
+}
+
+int tt_pair_scores_f32(tt_ctx* ctx, const float* Q, int64_t nQ, const float* Cm, int64_t nC, int32_t D, float inv_t,
+                       const void* rows, int32_t rows_i64, float* out, tt_stream stream) {
+  TT_PAIR_CHECK("tt_pair_scores_f32");
+  TT_CHECK_ARG(Q && Cm, "tt_pair_scores_f32: NULL embeddings");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (D % 4 == 0 && tt_aligned(Q, 16) && tt_aligned(Cm, 16))                    // the sweep's own choice of tile
+    return pair_launch(TileF32<true>{Q, Cm, nQ, nC, D, inv_t, nullptr}, nQ, nC, rows, rows_i64, out, st);
+  return pair_launch(TileF32<false>{Q, Cm, nQ, nC, D, inv_t, nullptr}, nQ, nC, rows, rows_i64, out, st);
 }
 
 }  // extern "C"

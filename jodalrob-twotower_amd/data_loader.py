@@ -52,7 +52,7 @@ class DevicePairLoader:
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
                  shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None, extra_negatives: int = 0,
-                 negative_pool=None):
+                 negative_pool=None, mined=None, hard_fraction: float = 1.0):
         """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
         task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
         log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
@@ -63,7 +63,11 @@ class DevicePairLoader:
         store -- or from negative_pool, an int64 tensor of company rows such as mined hard negatives -- which the train task contrasts
         with every notice of the batch besides the in-batch companies.  They carry "log_q" = log(1 / pool size) when the loader
         corrects and "entity" = the company row when mask_repeats is on.  Drawn per epoch from a generator of their own: a seed's pair
-        order is the same with and without extras."""
+        order is the same with and without extras.
+        mined: a hard_negatives.MinedNegatives (or its int32 table [len(notice), per_notice], -1 = empty): the first
+        H = round(hard_fraction * M) extras of a batch are drawn, uniformly with replacement, from the rows mined for THAT batch's
+        notices; the other M - H, and all of a batch whose notices have no mined row, are drawn from the store as above.  A mined
+        slot's "log_q" is -log(number of candidates of its batch), its proposal's.  Not together with negative_pool."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
@@ -82,14 +86,33 @@ class DevicePairLoader:
         self._neg_gen = torch.Generator(device=self.pairs.device)
         self._neg_gen.manual_seed((int(seed) + NEGATIVE_SEED_OFFSET) & ((1 << 63) - 1))
         self.extra_negatives, self.negative_pool = 0, None
-        self.set_extra_negatives(extra_negatives, negative_pool)
+        self.mined, self.hard_slots, self._epoch_cand = None, 0, None
+        self.set_extra_negatives(extra_negatives, negative_pool, mined, hard_fraction)
 
-    def set_extra_negatives(self, extra_negatives: int, negative_pool=None) -> None:
+    def set_extra_negatives(self, extra_negatives: int, negative_pool=None, mined=None, hard_fraction: float = 1.0) -> None:
         """M >= 0 shared extra negatives per batch (0: none), drawn from the whole company store or from `negative_pool` (int64 [n >= 1]
-        company rows)"""
+        company rows) -- or, with `mined` (a MinedNegatives or its table), the first round(hard_fraction * M) of them from the rows
+        mined for the batch's own notices"""
         M = int(extra_negatives)
         if M < 0:
             raise ValueError(f"extra_negatives must be >= 0, got {M}")
+        table, H = None, 0
+        hard_fraction = float(hard_fraction)
+        if not 0.0 < hard_fraction <= 1.0:
+            raise ValueError(f"hard_fraction must be in (0, 1], got {hard_fraction}")
+        if mined is not None:
+            if M == 0:
+                raise ValueError("mined negatives need extra_negatives > 0")
+            if negative_pool is not None:
+                raise ValueError("mined negatives do not combine with negative_pool")
+            t = getattr(mined, "table", mined)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != len(self.notice) \
+                    or t.shape[1] < 1:
+                raise ValueError(f"mined: need an int32 table of shape [{len(self.notice)}, per_notice >= 1], got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+            if int(t.max()) >= len(self.company):
+                raise KeyError("mined refers to a company that is not in the feature store")
+            table, H = t.to(self.pairs.device).contiguous(), int(round(hard_fraction * M))
         if M > 0 and self.pair_weight is not None:
             raise ValueError("extra_negatives do not combine with pair_weight")
         pool = None
@@ -106,22 +129,54 @@ class DevicePairLoader:
         if M > 0 and len(self.company) - 1 > np.iinfo(np.int32).max:
             raise ValueError("extra_negatives: a company row does not fit int32")
         self.extra_negatives, self.negative_pool = M, pool
+        self.mined, self.hard_slots, self._epoch_cand = table, H, None
 
-    def epoch_negatives(self) -> Optional[torch.Tensor]:
+    def epoch_negatives(self, order: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """int64 [n_batches, M]: this epoch's extra negatives, batch k's company rows at [k] -- ONE draw per epoch from the extras' own
-        seeded generator (the pair order's generator is not touched).  None without extras."""
+        seeded generator (the pair order's generator is not touched).  None without extras.
+        order: this epoch's epoch_order().  A loader with mined negatives draws a batch's first H slots from the rows mined for that
+        batch's notices, so a shuffling one needs the order and raises without it."""
         if not self.extra_negatives:
             return None
         n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
         idx = torch.randint(0, n_pool, (len(self), self.extra_negatives), generator=self._neg_gen, device=self.pairs.device)
+        if self.mined is not None:
+            return self._draw_mined(idx, order)
         return self.negative_pool[idx] if self.negative_pool is not None else idx
 
-    def negatives(self, rows: torch.Tensor) -> Dict:
-        """the batch entry "negatives" of the company rows `rows` (int64 [M])"""
+    def _draw_mined(self, idx: torch.Tensor, order: Optional[torch.Tensor]) -> torch.Tensor:
+        """idx [n_batches, M], the uniform draw, with the first H slots of every batch that has candidates replaced by a uniform draw
+        (with replacement) among them: the valid entries of the mined table's rows of the batch's notices, one entry per pair of the
+        batch.  One vectorised pass; the candidates' count per batch is kept for the slots' log q."""
+        if self.shuffle and order is None:
+            raise ValueError("epoch_negatives(): a shuffling loader with mined negatives needs this epoch's order")
+        n, B, H, dev = self.pairs.shape[0], self.batch_size, self.hard_slots, self.pairs.device
+        nb = len(self)
+        rows_n = torch.full((nb * B,), -1, dtype=torch.int64, device=dev)
+        rows_n[:n] = self.pairs[:, 0] if order is None else self.pairs[order, 0]
+        cand = torch.where(rows_n[:, None] >= 0, self.mined[rows_n.clamp(min=0)].to(torch.int64), rows_n[:, None]).view(nb, -1)
+        upto = torch.cumsum((cand >= 0).to(torch.int64), 1)                 # [nb, B * per_notice]: valid entries up to each
+        count = upto[:, -1]
+        self._epoch_cand = count
+        if H == 0 or nb == 0:
+            return idx
+        u = torch.rand((nb, H), generator=self._neg_gen, device=dev, dtype=torch.float64)
+        j = (u * count[:, None]).to(torch.int64).clamp(max=(count[:, None] - 1).clamp(min=0))       # the j-th valid entry
+        at = torch.searchsorted(upto, j + 1).clamp(max=cand.shape[1] - 1)
+        hard = cand.gather(1, at)
+        idx[:, :H] = torch.where(count[:, None] > 0, hard, idx[:, :H])
+        return idx
+
+    def negatives(self, rows: torch.Tensor, n_cand: Optional[torch.Tensor] = None) -> Dict:
+        """the batch entry "negatives" of the company rows `rows` (int64 [M]).  n_cand (mined negatives): the 0-d count of the batch's
+        mined candidates -- the first H slots were drawn from that many rows (0: the batch fell back to the store)."""
         out = self.company.gather(rows.contiguous())
         if self.log_q is not None:
             n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
             out["log_q"] = torch.full((rows.shape[0],), -float(np.log(n_pool)), dtype=torch.float32, device=rows.device)
+            if n_cand is not None and self.hard_slots:
+                lq = -torch.log(n_cand.clamp(min=1).to(torch.float32))
+                out["log_q"][:self.hard_slots] = torch.where(n_cand > 0, lq, out["log_q"][0])
         if self.entity is not None:
             out["entity"] = rows.to(torch.int32)
         return out
@@ -191,7 +246,8 @@ class DevicePairLoader:
             out["notice"]["entity"] = sel[:, 0].to(torch.int32)
             out["company"]["entity"] = sel[:, 1].to(torch.int32)
         if negatives is not None:
-            out["negatives"] = self.negatives(negatives)
+            mined = self.mined is not None and self._epoch_cand is not None
+            out["negatives"] = self.negatives(negatives, self._epoch_cand[lo // self.batch_size] if mined else None)
         return out
 
     def epoch_entity(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -240,7 +296,7 @@ class DevicePairLoader:
 
     def __iter__(self) -> Iterator[Dict]:
         order = self.epoch_order()
-        neg = self.epoch_negatives()
+        neg = self.epoch_negatives(order)
         for k, lo in enumerate(range(0, self.pairs.shape[0], self.batch_size)):
             yield self.batch(order, lo, None if neg is None else neg[k])
 
@@ -271,7 +327,7 @@ class DevicePairLoader:
         order = self.epoch_order()
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))
-        neg = self.epoch_negatives()
+        neg = self.epoch_negatives(order)
         if neg is not None:
             # extra negatives: no store-fed hand-over -- the batches __iter__ yields, through the captured step's plain-copy hand-over
             # step(batch) (a step captured on a batch with the same M), the ragged one through ragged_step or the eager callable

@@ -1041,12 +1041,13 @@ def retrieve_workspace_bytes(nQ: int, nC: int, D: int, k: int) -> int:
     return int(L.load().tt_retrieve_workspace_bytes(int(nQ), int(nC), int(D), int(k)))
 
 
-def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=None, filt=None):
+def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=None, filt=None, ceil=None):
     """One tt_retrieve_topk_* call: Q / C are packed bf16 images (bf16=True) or f32 [n, D] rows.  Returns (vals, idx, rank);
     vals / idx are None for k = 0, rank is None without positives.  exclude=(offsets int64 [nQ + 1], rows int32): per-query
     exclusion lists in CSR form, each list ascending (tt_excl_retrieve_topk_*).  filt=(tags int32 [nC, W], W, any, all):
     attribute filter (tt_filt_retrieve_topk_*, with or without exclude); any / all are int32 [nQ, W] masks or None, not
-    both None."""
+    both None.  ceil: f32 [nQ] per-query score ceilings of the top-k (tt_ceil_retrieve_topk_*, with or without exclude, never with
+    filt)."""
     dev = C.device
     lib = L.load()
     vals = torch.empty((nQ, k), dtype=torch.float32, device=dev) if k else None
@@ -1068,6 +1069,24 @@ def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=Non
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     pos_i64 = 1 if positives is not None and positives.dtype == torch.int64 else 0
+    if ceil is not None:
+        if filt is not None:
+            raise ValueError("a score ceiling does not combine with an attribute filter")
+        if ceil.dtype != torch.float32 or ceil.shape != (nQ,) or not ceil.is_contiguous() or ceil.device != dev:
+            raise ValueError(f"the score ceilings must be a contiguous float32 tensor of shape ({nQ},) on {dev}")
+        off, rows = (off, rows) if exclude is not None else (None, None)
+        name = "tt_ceil_retrieve_topk_bf16" if bf16 else "tt_ceil_retrieve_topk_f32"
+        with _timed(name):
+            if bf16:
+                rc = lib.tt_ceil_retrieve_topk_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, k, L.ptr(positives), pos_i64,
+                                                    L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(ceil),
+                                                    L.ptr(workspace), workspace.numel(), L.stream(dev))
+            else:
+                rc = lib.tt_ceil_retrieve_topk_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, k, L.ptr(positives), pos_i64,
+                                                   L.ptr(vals), L.ptr(idx), L.ptr(rank), L.ptr(off), L.ptr(rows), L.ptr(ceil),
+                                                   L.ptr(workspace), workspace.numel(), L.stream(dev))
+            L.check(rc, name)
+        return vals, idx, rank
     if filt is not None:
         tags, W, m_any, m_all = filt
         W = int(W)
@@ -1114,12 +1133,13 @@ def _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude=Non
     return vals, idx, rank
 
 
-def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None, exclude=None, filt=None):
+def retrieve_topk(Q, nQ, C, nC, D, k, inv_t=1.0, bf16=False, positives=None, workspace=None, exclude=None, filt=None, ceil=None):
     """Top-k of every query over the whole catalogue (tt_retrieve_topk_bf16 / _f32): (vals f32 [nQ, k], idx int64 [nQ, k]),
     value descending, ties to the lower index.  With positives, (vals, idx, rank) from the same sweep.  exclude=(offsets,
     rows): query q's rows rows[offsets[q]:offsets[q+1]] (ascending) are left out of its top-k and rank
-    (tt_excl_retrieve_topk_*).  filt=(tags, W, any, all): only rows eligible under the query's masks (tt_filt_retrieve_topk_*)."""
-    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude, filt)
+    (tt_excl_retrieve_topk_*).  filt=(tags, W, any, all): only rows eligible under the query's masks (tt_filt_retrieve_topk_*).
+    ceil: f32 [nQ]: only rows that score below ceil[q] enter query q's top-k; the rank is unchanged (tt_ceil_retrieve_topk_*)."""
+    vals, idx, rank = _retrieve(Q, nQ, C, nC, D, k, inv_t, bf16, positives, workspace, exclude, filt, ceil)
     return (vals, idx) if positives is None else (vals, idx, rank)
 
 
@@ -1128,6 +1148,25 @@ def retrieve_rank(Q, nQ, C, nC, D, positives, inv_t=1.0, bf16=False, workspace=N
     #{c : s > s_p} + #{c < p : s == s_p}, -1 for a positive outside [0, nC).  With exclude=(offsets, rows), only rows outside
     the query's list count; with filt=(tags, W, any, all), only eligible rows."""
     return _retrieve(Q, nQ, C, nC, D, 0, inv_t, bf16, positives, workspace, exclude, filt)[2]
+
+
+def pair_scores(Q, nQ, C, nC, D, rows, inv_t=1.0, bf16=False):
+    """f32 [nQ]: the score of query q against catalogue row rows[q] (int32 / int64 [nQ]), bit for bit what the retrieval sweep
+    computes for that pair (tt_pair_scores_bf16 / _f32; operands as retrieve_topk's); NaN for a row outside [0, nC)."""
+    dev = C.device
+    if rows.dtype not in (torch.int32, torch.int64) or rows.shape != (nQ,) or not rows.is_contiguous() or rows.device != dev:
+        raise ValueError(f"rows must be a contiguous int32/int64 tensor of shape ({nQ},) on {dev}")
+    lib = L.load()
+    out = torch.empty(nQ, dtype=torch.float32, device=dev)
+    i64 = 1 if rows.dtype == torch.int64 else 0
+    name = "tt_pair_scores_bf16" if bf16 else "tt_pair_scores_f32"
+    with _timed(name):
+        if bf16:
+            rc = lib.tt_pair_scores_bf16(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, L.ptr(rows), i64, L.ptr(out), L.stream(dev))
+        else:
+            rc = lib.tt_pair_scores_f32(L.ctx(dev), L.ptr(Q), nQ, L.ptr(C), nC, D, inv_t, L.ptr(rows), i64, L.ptr(out), L.stream(dev))
+        L.check(rc, name)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- misc

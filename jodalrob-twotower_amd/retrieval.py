@@ -24,6 +24,12 @@ sweep (tt_filt_retrieve_topk_bf16 / _f32), and combinable with exclude=.  onehot
     tags = equality_bits(region_code, 315) | onehot_bits(licence_class, 12, first_bit=18)      # fields: disjoint bit ranges
     index = CatalogIndex.from_store(model, company_store, tags=tags)
     index.search(q, 10, require=equality_bits(wanted_region, 315))                             # -1: don't care
+
+search and search_with_rank also take max_score=, an f32 [nQ] score ceiling per query: only rows that score BELOW max_score[i]
+enter query i's top-k, inside the sweep (tt_ceil_retrieve_topk_bf16 / _f32), so that all k slots go to rows under the ceiling;
+the rank never sees it.  It combines with exclude= and is refused together with allow= / require=.  pair_scores gives the score
+of a (query, row) pair bit for bit as the sweep forms it -- what a ceiling relative to a known positive is derived from
+(hard_negatives.mine_hard_negatives).
 """
 from __future__ import annotations
 
@@ -279,35 +285,66 @@ class CatalogIndex:
             self._ws[key] = ws
         return ws
 
-    def _call(self, Q: torch.Tensor, k: int, positives, exclude=None, filt=None):
+    def _check_max_score(self, max_score, filt, nQ: int):
+        """None, or the ceilings as a contiguous f32 [nQ] tensor.  No host synchronisation: a search with a ceiling stays
+        capturable."""
+        if max_score is None:
+            return None
+        if filt is not None:
+            raise ValueError("max_score= does not combine with allow= / require=")
+        if not torch.is_tensor(max_score) or max_score.dtype != torch.float32:
+            raise ValueError("max_score must be a float32 tensor")
+        if max_score.shape != (nQ,):
+            raise ValueError(f"max_score must have shape ({nQ},), got {tuple(max_score.shape)}")
+        if max_score.device != self.device:
+            raise ValueError(f"max_score on {max_score.device}, catalogue on {self.device}")
+        return max_score.detach().contiguous()
+
+    def _call(self, Q: torch.Tensor, k: int, positives, exclude=None, filt=None, ceil=None):
         nQ = Q.shape[0]
         ws = self._workspace(nQ, k)
         if self.score_dtype == "bf16":
             q = ops.score_pack_bf16(Q, 1.0)
-            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws, exclude, filt)
-        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws, exclude, filt)
+            return ops._retrieve(q, nQ, self.data, self.size, self.dim, k, self.inv_t, True, positives, ws, exclude, filt, ceil)
+        return ops._retrieve(Q, nQ, self.data, self.size, self.dim, k, self.inv_t, False, positives, ws, exclude, filt, ceil)
 
-    def search(self, Q: torch.Tensor, k: int = 10, exclude=None, allow=None, require=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def pair_scores(self, Q: torch.Tensor, rows) -> torch.Tensor:
+        """f32 [nQ]: the score of query i against catalogue row rows[i] (an integer tensor [nQ]), bit for bit the value a search
+        computes for that pair -- for a bf16 index the queries are packed as search packs them.  NaN where rows[i] is outside
+        [0, nC)."""
+        Q = self._check_queries(Q)
+        rows = self._check_positives(rows, Q.shape[0])
+        nQ = Q.shape[0]
+        if self.score_dtype == "bf16":
+            return ops.pair_scores(ops.score_pack_bf16(Q, 1.0), nQ, self.data, self.size, self.dim, rows, self.inv_t, True)
+        return ops.pair_scores(Q, nQ, self.data, self.size, self.dim, rows, self.inv_t, False)
+
+    def search(self, Q: torch.Tensor, k: int = 10, exclude=None, allow=None, require=None,
+               max_score=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(vals f32 [nQ, k], idx int64 [nQ, k]): every query's k best catalogue rows, value descending, ties to the lower
         index.  1 <= k <= min(512, catalogue size).  exclude=(offsets int64 [nQ + 1], rows): query i's rows
         rows[offsets[i]:offsets[i+1]] are left out; if fewer than k rows remain, the last slots are -inf / -1.
         allow / require (an index with tags only): integer masks [nQ] or [nQ, W]; only rows that share a bit with a non-zero
-        allow[i] and hold every bit of require[i] are eligible for query i.  They combine with exclude."""
+        allow[i] and hold every bit of require[i] are eligible for query i.  They combine with exclude.
+        max_score: f32 [nQ] on the index's device: only rows with a score below max_score[i] are kept for query i (a tie with
+        the ceiling goes; NaN or +inf keeps every row, -inf none).  Combines with exclude; ValueError with allow / require."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
         ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
-        vals, idx, _ = self._call(Q, k, None, ex, self._check_filter(allow, require, Q.shape[0]))
+        filt = self._check_filter(allow, require, Q.shape[0])
+        vals, idx, _ = self._call(Q, k, None, ex, filt, self._check_max_score(max_score, filt, Q.shape[0]))
         return vals, idx
 
     def search_with_rank(self, Q: torch.Tensor, k: int, positives, exclude=None, allow=None,
-                         require=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         require=None, max_score=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """search() and rank() from one sweep over the catalogue (the same exclusion lists and masks for both);
-        1 <= k <= min(512, catalogue size)."""
+        1 <= k <= min(512, catalogue size).  max_score bounds the top-k only: the rank is that of the call without it."""
         k = self._check_k(k)
         Q = self._check_queries(Q)
         pos = self._check_positives(positives, Q.shape[0])
         ex = None if exclude is None else self._check_exclude(exclude, Q.shape[0])
-        return self._call(Q, k, pos, ex, self._check_filter(allow, require, Q.shape[0]))
+        filt = self._check_filter(allow, require, Q.shape[0])
+        return self._call(Q, k, pos, ex, filt, self._check_max_score(max_score, filt, Q.shape[0]))
 
     def rank(self, Q: torch.Tensor, positives, exclude=None, allow=None, require=None) -> torch.Tensor:
         """int32 [nQ]: 0-based rank of catalogue row positives[i] for query i among ALL catalogue rows,

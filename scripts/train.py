@@ -120,8 +120,21 @@ def main():
                          "that every notice of the batch is contrasted with besides the in-batch companies (mixed negative sampling); "
                          "combines with --mask-repeats and --logq-correction, not with --pair-weight; with --fast the captured step takes "
                          "them through its plain-copy hand-over")
+    ap.add_argument("--mine-negatives", type=int, default=0, metavar="E",
+                    help="hard-negative mining: before every E-th epoch, mine the train pairs' notices against the whole company catalogue "
+                         "with the current weights (score ceiling relative to each notice's own positives, known companies excluded) and "
+                         "draw each batch's extras from the rows mined for that batch's notices; needs --extra-negatives M")
+    ap.add_argument("--mine-k", type=int, default=64, help="rows searched per notice under the ceiling")
+    ap.add_argument("--mine-per-notice", type=int, default=8, help="rows kept per notice (the best of the --mine-k)")
+    ap.add_argument("--mine-ceiling", type=float, nargs=2, default=(0.95, 0.0), metavar=("A", "B"),
+                    help="score ceiling A * s_min + B, s_min the lowest score of the notice's known companies")
+    ap.add_argument("--hard-fraction", type=float, default=1.0, metavar="F", help="share of the M extras drawn from the mined rows")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
     a = ap.parse_args()
+    if a.mine_negatives < 0:
+        ap.error("--mine-negatives must be >= 0")
+    if not a.extra_negatives and (a.mine_negatives or a.hard_fraction != 1.0):
+        ap.error("--mine-negatives / --hard-fraction need --extra-negatives M")
     config = {"batch_size": a.batch_size, "test_split": 0.2, "shuffle_seed": 42, "pair_limit": a.pairs,
               "categorical_embedding_dim": 32, "notice_dense_input_dim": 256, "company_dense_input_dim": 128,
               "tower_hidden_dims": [int(h) for h in a.hidden.split(",")], "final_embedding_dim": a.final_dim, "dropout_rate": 0.1,
@@ -216,6 +229,14 @@ def main():
     for epoch in range(start_epoch, config["num_epochs"]):
         print(f"\nEpoch {epoch + 1}/{config['num_epochs']}")
         t_e0 = time.time()
+        if a.mine_negatives and (epoch - start_epoch) % a.mine_negatives == 0:
+            from jodalrob_twotower_amd.hard_negatives import mine_hard_negatives
+            mined = mine_hard_negatives(train_task, train_loader.notice, train_loader.company, train_loader.pairs, k=a.mine_k,
+                                        per_notice=a.mine_per_notice, ceiling=tuple(a.mine_ceiling), seed=config["shuffle_seed"] + epoch)
+            train_loader.set_extra_negatives(a.extra_negatives, mined=mined, hard_fraction=a.hard_fraction)
+            torch.cuda.synchronize()
+            n_mined = int((mined.table >= 0).sum())
+            print(f"mined {n_mined} hard negatives for {int((mined.table[:, 0] >= 0).sum())} notices in {time.time() - t_e0:.2f} s")
         train_task.train()
         train_losses, train_accuracies, n_epoch_steps = [], [], 0
         for g in (graphed, ragged):
