@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- training pairs/sec of the two-tower step on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the outputs of the
+last one if --dump-outputs asks for them, and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, the configuration and what the timed region gives for free: `host_enqueue_ms_per_step`, `final_loss`).  Everything
+else the benchmark measures runs with --full, behind the same timed region: the per-step device-time median, the lookup
+`roofline` with its dispatch-overhead calibration, `mfma`, the host-fed and store-fed legs, `cpu_baseline`, the HBM-resident
+lookup leg, configs[4], --breakdown, --lookup-wg-dump, and at N > 1 the strong-scaling and one-GPU legs beside the weak one.
 
 Self-contained for every N: with --gpus N > 1 and no WORLD_SIZE in the environment it starts its own N rank processes (one
 per GPU, before anything touches a GPU) and rank 0 prints the JSON line; under `python -m torch.distributed.run` it uses the
@@ -22,7 +29,7 @@ batch whose ids and dense features are already resident in HBM.
           split over N GPUs; latency-bound) and `one_gpu_same_tables` (the unsharded single-GPU step on the SAME 100 M +
           10 M-row tables, measured by rank 0 in the same run: the like-for-like denominator of a speed-up).
 
-Prints ONE JSON line (rank 0).  `roofline` is the embedding-lookup kernel (the kernel BASELINE.json's metric names);
+Prints ONE JSON line (rank 0).  With --full: `roofline` is the embedding-lookup kernel (the kernel BASELINE.json's metric names);
 `mfma` the score GEMMs; `value_with_h2d` the same step fed from pinned host batches through a staging stream;
 `cpu_baseline` times oracle/oracle_torch.py (checker code, used here only as the reported baseline) on the host cores.
 """
@@ -48,6 +55,9 @@ MFMA_FP8_PEAK_TFLOPS = 5000.0     # dense fp8 through the block-scaled f8f6f4 in
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps also measure everything that is not the headline figure: device-time median, lookup roofline, "
+                         "mfma, host-fed and store-fed legs, cpu_baseline, HBM-resident lookup, configs[4]; at N > 1 all three legs")
     # defaults: 2000 timed steps behind 200 warm-up steps = half a second of GPU time.  Round 4 measured what a short region costs: 100 steps
     # behind 20 (23 ms) read 0.2308-0.2332 ms per step where 4000 behind 200 read 0.2263-0.2265 -- the first replays of a cold process are
     # slower and the region's fixed ends (first enqueue, final synchronise: ~0.15 ms) weigh 0.6 % at 100 steps (profiles/NOTES.md)
@@ -63,17 +73,18 @@ def parse(argv=None):
     ap.add_argument("--score-dtype", choices=["bf16", "fp32", "fp8"], default="bf16")
     ap.add_argument("--mlp-dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--pool", type=int, default=8, help="distinct pre-generated batches cycled through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work budget of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline sample")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU work budget of the cpu_baseline sample")
     ap.add_argument("--mode", choices=["graph", "eager"], default="graph",
                     help="graph: whole step replayed from one captured HIP graph; eager: launched from Python")
     ap.add_argument("--force-dist", action="store_true", help="use the sharded-table path even on one GPU")
-    ap.add_argument("--legs", default=None, help="multi-GPU: comma list of strong,weak,one_gpu (default all three)")
+    ap.add_argument("--legs", default=None, help="multi-GPU: comma list of strong,weak,one_gpu (default: weak, the leg that gives `value`; with --full all "
+                    "three).  Without --full: one of weak, strong")
     ap.add_argument("--negatives", choices=["local", "global"], default=None,
                     help="multi-GPU, overrides the leg's default: in-batch negatives of the rank's own batch or of the GLOBAL batch")
     ap.add_argument("--sync-bn", action="store_true", help="multi-GPU: BatchNorm statistics over all ranks' rows also in the weak leg")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-to-device-inclusive leg")
-    ap.add_argument("--breakdown", action="store_true", help="extra instrumented pass: per-kernel HIP-event times")
+    ap.add_argument("--no-h2d", action="store_true", help="--full: skip the host-fed and the store-fed leg")
+    ap.add_argument("--breakdown", action="store_true", help="--full: extra instrumented pass: per-kernel HIP-event times")
     ap.add_argument("--fp8-grad", type=int, default=1, choices=[0, 1], help="TT_OPT_FP8_GRAD with --score-dtype fp8: 1 e4m3 gradient products "
                     "(default), 0 bf16 gradient products")
     ap.add_argument("--no-riders", action="store_true", help="plan compaction / loss reduction as launches of their own (A/B of TT_OPT_DEFER_RIDERS)")
@@ -81,18 +92,24 @@ def parse(argv=None):
     ap.add_argument("--dist-segmented", action="store_true", help="sharded path: the compute between two collectives as graphs of its own, the "
                     "collectives eager (the fallback when a capture with RCCL nodes fails; this flag forces it)")
     ap.add_argument("--no-lookup-profile", action="store_true", help="do not stamp the lookup launches (no `roofline` object then)")
-    ap.add_argument("--lookup-wg-dump", default=None, help="write the lookup's per-workgroup stamps to this .npy (tools/lookup_wg.py)")
+    ap.add_argument("--lookup-wg-dump", default=None, help="--full: write the lookup's per-workgroup stamps to this .npy (tools/lookup_wg.py)")
     ap.add_argument("--fused-handover", action="store_true", help="hand-over and lookup as ONE launch (tt_batch_ingest_lookup; measured neutral, off by default)")
     ap.add_argument("--lookup-from-ids", action="store_true", help="the captured lookup decodes the int64 ids itself (round 3's kernel input) instead of "
                     "reading the hand-over launch's precomputed rows")
     ap.add_argument("--lookup-nt", action="store_true", help="TT_OPT_LOOKUP_NT: non-temporal stores of the looked-up rows (A/B)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the HBM-resident lookup leg and the configs[4] leg of the default run")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the HBM-resident lookup leg and the configs[4] leg")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps write what the last one computed (result dict, trained state; fixed samples of the "
                          "large arrays) as DIR/<name>.npy, float32 / float64, at most 64 MB (rank 0; the leg that gives `value`)")
     ap.add_argument("--unroll", type=int, default=1, help="training steps per graph launch (unrolled.UnrolledTrainStep: the hand-over launches become "
                                                           "graph nodes re-pointed per launch; one graph launch costs ~8 us on this runtime); unsharded step only")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:                                     # a plain run measures the headline figure only: say so instead of dropping a request
+        if args.breakdown or args.lookup_wg_dump:
+            ap.error("--breakdown and --lookup-wg-dump are measurements of their own: add --full")
+        if args.legs is not None and args.legs not in ("weak", "strong"):
+            ap.error("--legs with more than the leg that gives `value` (weak or strong): add --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -291,6 +308,17 @@ class Leg:
         ops.set_timer(None)
         if dump_dir is not None:                                 # (the second pass below overwrites the captured step's results)
             dump_outputs(dump_dir, self.task, res)
+        if not args.full:
+            # plain run: the headline figure is complete here.  (The lookup stamps stay ON in the captured step -- they are part of
+            # the timed launches -- but nothing reads them, calibrates against them or times a second pass.)
+            if self.profile is not None:
+                self.profile.close()
+            ex = getattr(self.task, "exchange", None)
+            if self.sharded and ex is not None and hasattr(ex, "check_overflow"):
+                ex.check_overflow()                              # a bucket overflow in the timed region invalidates the result
+            self.dt, self.t_enqueue, self.loss = ctx["max_over_ranks"](dt), t_enqueue, float(res["loss"].detach())
+            self.device_ms_median = None
+            return self.dt
         # the captured step's hand-over launch also does the lookup (tt_batch_ingest_lookup)?  Then the stamps are that launch's:
         # its tile workgroups (the gather phase) come first, the copy roles behind them
         self.fused_handover = self.gstep is not None and getattr(self.gstep, "_x_static", None) is not None
@@ -480,7 +508,7 @@ def base_line(args, leg, world, scaling, B_global):
     return {
         "metric": "training pairs/sec at batch 8192 (embedding-lookup HBM GB/s in roofline)",
         "value": B_global * args.steps / dt, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "device_ms_per_step_median": leg.device_ms_median,
+        "ms_per_step": dt / args.steps * 1e3, **({"device_ms_per_step_median": leg.device_ms_median} if args.full else {}),
         "host_enqueue_ms_per_step": leg.t_enqueue / args.steps * 1e3,
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
         "dtype": ("bf16" if bf else f"score {args.score_dtype} / mlp {args.mlp_dtype}") +
@@ -619,8 +647,11 @@ def bench_single(args, ctx, sharded):
     out["config"] = config_of(args, leg, 1, ctx, B, ("configs[1]: " if is_c1 else "variant of configs[1]: ") +
                               f"32+6 real keys, {rows_n}-row notice + {rows_c}-row company tables, batch {B}, E=32, towers [{args.hidden}], "
                               f"final {args.final_dim}, in-batch negatives, dropout 0.1")
-    out["roofline"] = roofline_of(args, leg, 1)
     out["final_loss"] = leg.loss
+    if not args.full:
+        leg.close()
+        return out
+    out["roofline"] = roofline_of(args, leg, 1)
     try:
         out["mfma"] = score_mfma_leg(args, ctx["dev"], B, args.final_dim)
     except Exception as e:                                # an instrumentation leg must not lose the line
@@ -667,7 +698,7 @@ def bench_multi(args, ctx):
     world, rank = ctx["world"], ctx["rank"]
     rows_n = args.rows_notice or 100_000_000              # configs[2]: over ALL GPUs (row r lives on GPU r mod N)
     rows_c = args.rows_company or 10_000_000
-    legs = (args.legs or "strong,weak,one_gpu").split(",")
+    legs = (args.legs or ("strong,weak,one_gpu" if args.full else "weak")).split(",")
     Bg = args.batch
     if Bg % world:
         raise SystemExit(f"--batch {Bg} must be a multiple of the {world} ranks")
@@ -688,7 +719,8 @@ def bench_multi(args, ctx):
         out["config"] = config_of(args, leg, world, ctx, Bg * world, f"VARIANT of {cname} (weak-scaling leg): {desc}; {Bg} pairs PER GPU (global batch "
                                   f"{Bg * world}), per-rank in-batch negatives and BatchNorm statistics (data-parallel semantics); {cname} as SURVEY 8(d) "
                                   f"states it -- GLOBAL batch {Bg}, global negatives + SyncBN -- is `value_global_batch_{Bg}` / `strong_scaling`")
-        out["roofline"] = roofline_of(args, leg, world)
+        if args.full:
+            out["roofline"] = roofline_of(args, leg, world)
         out["final_loss"] = leg.loss
         leg.close()
     if "strong" in legs:
@@ -701,7 +733,9 @@ def bench_multi(args, ctx):
         cfg = config_of(args, leg, world, ctx, Bg, f"{cname}: {desc}; GLOBAL batch {Bg} ({Bg // world} pairs per GPU), global in-batch negatives + SyncBN")
         if out is None:
             out = st
-            out["config"], out["roofline"], out["final_loss"] = cfg, roofline_of(args, leg, world), leg.loss
+            out["config"], out["final_loss"] = cfg, leg.loss
+            if args.full:
+                out["roofline"] = roofline_of(args, leg, world)
         else:
             strong = {k: st[k] for k in ("value", "unit", "ms_per_step", "device_ms_per_step_median", "host_enqueue_ms_per_step", "scaling")}
             strong["config"] = cfg
@@ -955,7 +989,7 @@ def hbm_resident_lookup_leg(args, ctx, rows_n: int = 100_000_000, rows_c: int = 
 
 
 def configs4_leg(args, ctx):
-    """BASELINE configs[4] in the default run (never `value`): final_embedding_dim 256, batch 65536, fp8 (e4m3) MFMA score matrix,
+    """BASELINE configs[4] in the --full run (never `value`): final_embedding_dim 256, batch 65536, fp8 (e4m3) MFMA score matrix,
     fused sparse Adam on the embedding rows; 1 M + 1 M-row tables; a few replayed steps + the score kernels' MFMA figure."""
     import copy
     a4 = copy.copy(args)

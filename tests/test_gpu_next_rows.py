@@ -465,7 +465,7 @@ def test_fast_evaluation_equals_batch_loop(tt, tmp_path):
 
 
 def test_bench_multi_gpu_path_with_two_ranks_on_one_gpu():
-    """`bench.py --gpus 2` end to end with two REAL ranks sharing the one GPU (collectives staged through gloo, the sharded step captured in
+    """`bench.py --gpus 2 --full` end to end with two REAL ranks sharing the one GPU (collectives staged through gloo, the sharded step captured in
     segments): the weak leg incl. everything the bench does around a captured step -- bucket calibration over the batch pool, the lookup
     stamps, the dispatch-overhead calibration that re-launches the step's lookup, the roofline object, teardown before the process group
     goes.  Round 4 found that calibration indexing a rank's table SHARD with global key offsets (a GPU memory fault on every N > 1 run,
@@ -476,7 +476,7 @@ def test_bench_multi_gpu_path_with_two_ranks_on_one_gpu():
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()      # a free rendezvous port
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--rows-notice", "400000", "--rows-company",
-                        "200000", "--no-cpu-baseline", "--dist-segmented", "--legs", "weak", "--pool", "3"], capture_output=True, text=True, timeout=600, env=env, cwd=str(root))
+                        "200000", "--full", "--no-cpu-baseline", "--dist-segmented", "--legs", "weak", "--pool", "3"], capture_output=True, text=True, timeout=600, env=env, cwd=str(root))
     assert "Memory access fault" not in r.stderr and "Memory access fault" not in r.stdout, r.stderr[-2000:]
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -487,15 +487,21 @@ def test_bench_multi_gpu_path_with_two_ranks_on_one_gpu():
 
 
 def test_bench_dump_outputs(tmp_path):
-    """`bench.py --dump-outputs DIR`: the timed steps' count is --steps, the line carries ms_per_step, and DIR holds the LAST timed step's
+    """`bench.py --dump-outputs DIR`, a plain run (no --full): the timed steps' count is --steps, the line carries the headline figure
+    (value = batch / ms_per_step) and none of the measurements that --full adds behind it, and DIR holds the LAST timed step's
     outputs -- its loss is the line's final_loss -- as float32 / float64 .npy files, 64 MB at most, with the similarity matrix and the
     embedding tables as fixed row samples."""
     out = tmp_path / "dump"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--no-cpu-baseline", "--no-h2d",
-                        "--no-extra-legs", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
     assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0
+    assert d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["metric"].startswith("training pairs/sec") and "bf16" in d["dtype"]
+    assert d["value"] == pytest.approx(8192 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    moved = {"device_ms_per_step_median", "roofline", "mfma", "value_with_h2d", "value_with_h2d_bf16_dense", "value_with_device_store",
+             "kernel_breakdown", "cpu_baseline", "roofline_hbm_resident", "configs4"}
+    assert not moved & set(d), sorted(moved & set(d))
     files = {f.name[:-4]: np.load(f) for f in out.glob("*.npy")}
     assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
     assert all(a.dtype in (np.float32, np.float64) for a in files.values())

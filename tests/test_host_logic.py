@@ -185,6 +185,26 @@ def test_bench_self_launch_plumbing():
     assert r3.returncode != 0
 
 
+def test_bench_full_option():
+    """bench.py's --full is off by default; a plain run refuses the options that ask for a measurement beside the headline figure
+    (it names --full) instead of dropping them, and takes the one leg that gives `value` at N > 1.  Argument parsing only: no GPU."""
+    import importlib.util
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("_tt_bench_args", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert plain.full is False and plain.legs is None and plain.dump_outputs is None
+    full = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "1", "--full", "--breakdown", "--lookup-wg-dump", "x.npy"])
+    assert full.full is True and full.breakdown and (full.steps, full.warmup) == (5, 1)
+    assert bench.parse(["--gpus", "2", "--legs", "strong"]).legs == "strong"
+    assert bench.parse(["--gpus", "2", "--full", "--legs", "strong,weak,one_gpu"]).legs == "strong,weak,one_gpu"
+    for argv in (["--breakdown"], ["--lookup-wg-dump", "x.npy"], ["--gpus", "2", "--legs", "weak,strong"], ["--gpus", "2", "--legs", "one_gpu"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse(argv)
+        assert e.value.code == 2, argv
+
+
 def test_train_test_split_is_sklearns():
     """Membership and order of the train / test pair lists == sklearn.model_selection.train_test_split(random_state=seed), the
     call the reference's test-mode loader makes (unified_bid_data_loader.py:1222-1226).  Fixture: oracle/gen_split_fixture.py
