@@ -118,6 +118,7 @@ int tt_ctx_set_option(tt_ctx* ctx, int32_t option, int32_t value);
  * epoch, before a checkpoint, when a captured step is closed). */
 #define TT_DEVERR_CHAIN_TIMEOUT 1u
 #define TT_DEVERR_ROW_RANGE 2u
+#define TT_DEVERR_CELLS_PLAN 4u   /* tt_score_cells_plan: its counters summed to more cells than the list's capacity */
 int tt_ctx_check_device_errors(tt_ctx* ctx, tt_stream stream);
 /* The hand-over launch as a node of a captured graph.  A tt_batch_ingest* call on a stream that is being captured becomes a kernel
  * node; tt_handover_captured_node hands that node out (NULL if the last call was not captured) and forgets it.  Later, between
@@ -816,6 +817,46 @@ int tt_score_dir_fwd_xneg(tt_ctx* ctx, const float* N, const float* X, int64_t B
 int tt_score_dir_bwd_xneg(tt_ctx* ctx, const float* A, const float* Bm, int64_t Ra, int64_t Rb, int32_t D, float inv_t, float shift,
                           int32_t x_is_b, const int32_t* ent_a, const int32_t* ent_b, const float* lq_x, const float* rowsum,
                           const float* d_loss, float scale, int32_t accumulate, float* dA, tt_stream stream);
+/* ---- masked cells of the in-batch softmax: a per-step sparse list of (row, column) pairs that are never negatives ------------------
+ * cells int32 [capacity, 2], rows (a, j): a in [0, B) a notice row, j in [0, B + M) a column -- j < B in-batch column j, j >= B
+ * extra j - B (M = 0 without extras).  Only the first min(*count, capacity) rows are read; *count lies in DEVICE memory.  Any
+ * order, duplicates allowed; cells with j == a (the positive) and cells outside the ranges are dropped.  With Omega the cleaned
+ * set, R, Rx, C the row / extras / column logits of the _lq / _xneg entries:
+ *   R', Rx' = R, Rx with the cells of Omega at -inf;  C' = C with the cells (a, b) of Omega, b < B, at -inf (column b loses row a)
+ *   loss, W, Wx, dN, dC, dX: the _xneg formulas (the _lq / plain ones without extras) on R', Rx', C'
+ * The positive is never masked, so no sum is empty.  Metrics (out8[1:], diag, row_rank) stay on the raw scores; colsum and diag of
+ * a call with an empty Omega are bit for bit those of the call without cells.  bf16 operands only.
+ *
+ * tt_score_cells_plan: buckets the cleaned list by 32 x 32 tile pair (a / 32, j / 32); the extras' tiles start on their own boundary
+ * at nT = ceil(B / 32), extra m in tile nT + m / 32, as X_packed does.  plan (out, int32, 16-byte aligned):
+ * [nT * (nT + nTx) + 1] offsets, tile pairs in row-major order (notice tile, column tile), then [capacity] local codes
+ * (a % 32) * 32 + (j' % 32) (j' = j, or j - B for an extra), tile pair by tile pair.  Counts and offsets are deterministic; the order
+ * inside a tile pair is not (masking is idempotent).  A fixed grid over `capacity`: the call can sit in a captured graph while
+ * *count and the list change between replays.  plan: tt_score_cells_plan_bytes(B, M, capacity); workspace:
+ * tt_score_cells_plan_workspace_bytes(B, M) -- the tile pairs' counters, memory of the call's own (not scratch another launch of
+ * the step may be using).  capacity >= 1 (a list that is always empty still needs one slot).  The two entries below take the plan's
+ * `capacity` again: a span is never read past the codes array, whatever the offsets hold.
+ * tt_score_fwd_sym_bf16_cells: tt_score_fwd_sym_bf16 (/_lq, /_xneg unmasked) on Omega.  X_packed NULL (then M = 0, lq_x / w_x
+ * ignored) or the extras' image; lq_n / lq_c both or neither, lq_x optional with them.  workspace: tt_score_fwd_sym_workspace_bytes
+ * (M = 0) or tt_score_fwd_sym_xneg_workspace_bytes.
+ * tt_score_bwd_bf16_cells: the backward on that forward's sums -- the square problem (dirs as tt_score_bwd_bf16, two directions
+ * (N, C) and (C, N) in this order, inv_a / inv_b optional, lq optional) and, with X_packed, the extras' two rectangular directions
+ * behind it (dN +=, dX as tt_score_bwd_bf16_xneg; inv_row / w_x / dX then required).  A listed pair weighs nothing in either
+ * direction.  The b-split form at every shape; never hosted by the towers' backward launch: a queued score backward is launched in
+ * front of it. */
+size_t tt_score_cells_plan_bytes(int64_t B, int64_t M, int64_t capacity);
+size_t tt_score_cells_plan_workspace_bytes(int64_t B, int64_t M);
+int tt_score_cells_plan(tt_ctx* ctx, const int32_t* cells, const int32_t* count, int64_t capacity, int64_t B, int64_t M,
+                        int32_t* plan, size_t plan_bytes, void* workspace, size_t workspace_bytes, tt_stream stream);
+int tt_score_fwd_sym_bf16_cells(tt_ctx* ctx, const void* N_packed, const void* C_packed, const void* X_packed, int64_t B,
+                                int64_t M, int32_t D, float inv_t, float shift, float ab_scale, int32_t want_rank,
+                                const int32_t* plan, int64_t capacity, const float* lq_n, const float* lq_c, const float* lq_x, float* rowsum,
+                                float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* w_x, float* diag,
+                                int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
+                                tt_stream stream);
+int tt_score_bwd_bf16_cells(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* plan, int64_t capacity, const tt_score_bwd_lq* lq,
+                            const void* X_packed, int64_t M, const float* inv_row, const float* w_x, float* dX, int32_t D,
+                            float inv_t, float shift, const float* d_loss, float scale, tt_stream stream);
 /* Dense loss path: the loss variants the fused kernels do not cover, on the MATERIALISED score matrix --
  * label-smoothed cross-entropy (loss_type 0; two_tower_train_task.py:114-133, F.cross_entropy(label_smoothing=e) in both
  * directions) and cosine-embedding loss (loss_type 1; :135-158: F.cosine_embedding_loss of [s] against [1], positives on the

@@ -193,6 +193,13 @@ SIGNATURES = {
     "tt_score_bwd_bf16_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, f32, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
     "tt_score_dir_fwd_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "tt_score_dir_bwd_xneg": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, f32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp]),
+    "tt_score_cells_plan_bytes": (sz, [i64, i64, i64]),
+    "tt_score_cells_plan_workspace_bytes": (sz, [i64, i64]),
+    "tt_score_cells_plan": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, sz, vp, sz, vp]),
+    "tt_score_fwd_sym_bf16_cells": (C.c_int, [vp, vp, vp, vp, i64, i64, i32, f32, f32, f32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, vp, vp, vp, vp, sz, vp]),
+    "tt_score_bwd_bf16_cells": (C.c_int, [vp, C.POINTER(ScoreBwdDir), vp, i64, C.POINTER(ScoreBwdLq), vp, i64, vp, vp, vp, i32, f32, f32, vp, f32,
+                                          vp]),
     "tt_score_matrix": (C.c_int, [vp, vp, vp, i64, i64, i32, f32, vp, i64, vp]),
     "tt_score_dense_workspace_bytes": (sz, [i64, i32]),
     "tt_score_dense_fwd": (C.c_int, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp, vp]),

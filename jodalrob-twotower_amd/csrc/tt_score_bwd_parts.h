@@ -5,9 +5,10 @@
 // second product, rows8's block scaling, the hosted tail -- and, for now, everything that works on a lane's 16-element arrays (the
 // reciprocals' preparation, the ragged mask, the diagonal's -2, the conversion to fragments), the two-buffer sweep and the
 // cross-wave tree and the store of dA: written as parts they changed hipcc's register allocation of the kernels that sit at an occupancy step (NOTES).
-// Included by tt_score_bf16.hip only, and in an unnamed namespace as its kernels are.
+// Included by tt_score_bf16.hip and, through tt_score_bwd_bsplit.h, by tt_score_cells.hip; in an unnamed namespace as the kernels are.
 #pragma once
 #include "tt_score_bf16.h"
+#include "tt_score_cells.h"
 
 namespace {
 
@@ -65,6 +66,12 @@ struct BwdArgs {
   // PW kernels (tt_score_bwd_bf16_pw; the b-split form): the normalised pair weights g (tt_score_prepare_pw), one array for both
   // directions; inv_a / inv_b are then the weighted forward's folded reciprocals
   const float* pw_g;
+};
+// KP kernels (tt_score_bwd_bf16_cells; the b-split form): the masked cells' plan behind the other arguments, one for both directions --
+// direction 1 reads a tile pair with its local coordinates swapped.  A type of its own: every other instantiation keeps its argument
+// block, and with it its code, as it was.
+struct BwdArgsKP : BwdArgs {
+  TtCellsPlan kp;
 };
 
 // ---- the direction select ----------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 // images' columns instead of the kernel adding 67 M products.
 #include "tt_score_bf16.h"
 #include "tt_deferred.h"
+#include "tt_score_cells.h"
 
 #include <stdlib.h>
 
@@ -75,6 +76,11 @@ struct SymArgs {
   const float* lq_x;                   // [Rx] log sampling probabilities of the extras (LQ) or NULL: weight 1
   const int32_t* ent_x;                // [Rx] company ids of the extras (MK) or NULL: never masked
 };
+// KP kernels (tt_score_fwd_sym_bf16_cells) take the masked cells' plan behind the other arguments: a type of their own, so that every
+// other instantiation keeps its argument block -- and with it its code -- as it was
+struct SymArgsKP : SymArgs {
+  TtCellsPlan kp;
+};
 
 // Notice tiles are staged through LDS once per WORKGROUP (all 8 waves sweep the same tiles I): read straight from L2 by
 // every wave, the operand stream was 4 KB per 32 x 32 tile -- 268 MB per launch at B = 8192, D = 64 -- and the kernel ran at
@@ -116,8 +122,12 @@ struct SymStage {
 // only -- the column accumulators are dropped; its LQ weight comes from lq_x (NULL: 1), its mask is ent_c[a] == ent_x[m] alone
 // (NULL ent_x: never).  The row partials land in slab rows ngi .., which finish1 adds behind the in-batch ones.  The in-batch
 // workgroups run the code of the form without extras: colsum and diag keep their bits.
-template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false, bool MK = false, bool XN = false>
-__global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
+// KP: masked cells (tt_score_fwd_sym_bf16_cells).  Per swept tile pair the wave reads the pair's two plan offsets (wave-uniform) and,
+// only when the span is not empty, walks its cells into one 16-bit mask per lane (tt_cells_mask); e_ab of a listed cell is zeroed
+// where masked() zeroes it -- behind ex(), in front of both sums; the maxima, dg and the rank path never see it.  The plan holds no
+// diagonal cell.  An extras' tile (isx) is column tile nT + J of the plan.
+template <int KS, bool UNIT, bool FP8, int JT, bool X3 = false, bool LQ = false, bool MK = false, bool XN = false, bool KP = false>
+__global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(std::conditional_t<KP, SymArgsKP, SymArgs> g) {
   using ST = SymStage<KS, FP8, X3>;
   constexpr int TS = ST::TS, LPT = ST::LPT, kTileB = ST::kTileB, kImgB = ST::kImgB, K64 = FP8 ? KS / 4 : 1, KL = X3 ? KS : 1;
   static_assert(!X3 || (!FP8 && JT == 1), "bf16x3: bf16 images, one company tile per wave");
@@ -137,6 +147,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
   float* s_wc = s_wn + NI * 32 + wave * 32;
   static_assert(!MK || (!FP8 && !X3 && JT == 1), "the repeated-entity mask: bf16 operands only");
   static_assert(!XN || (!FP8 && !X3 && JT == 1), "extra negatives: bf16 operands only");
+  static_assert(!KP || (!FP8 && !X3 && JT == 1 && !MK), "masked cells: bf16 operands only, not beside the repeated-entity mask");
   constexpr bool ELDS = MK && KS == 16;
   int* s_ean = reinterpret_cast<int*>(s_wn + (LQ ? NI * 32 + kSymWaves * 32 : 0));   // (MK) [NI * 32] notice ids of the a rows
   int* s_eac = s_ean + NI * 32;                                                       //      their company ids
@@ -326,10 +337,20 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
           const int J = J0 + j;
+          [[maybe_unused]] unsigned km = 0;                // (KP) this lane's listed elements of the tile pair
+          if constexpr (KP) {
+            if (I < I1 && jact[j]) km = tt_cells_mask(g.kp, I, (XN && isx) ? nT + J : J, c, h, false);
+          }
           if (I < I1 && (I != J || (XN && isx)) && I < n_full && jfull[j]) {  // plain tile: 32 x 32 valid scores, all on one side of the positives
             float e[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) e[r] = ex(acc[j][r]);
+            if constexpr (KP) {
+              if (__builtin_amdgcn_ballot_w64(km != 0)) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) e[r] = (km >> r) & 1u ? 0.f : e[r];
+              }
+            }
             if constexpr (MK) {                            // (I != J: no positive in this tile)
 #pragma unroll
               for (int r = 0; r < 16; ++r) e[r] = masked(ean, eac, r) ? 0.f : e[r];
@@ -373,6 +394,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
               if constexpr (XN) {
                 if (isx) {                                 // an extra: no positive, no column sum, behind every in-batch column
                   if constexpr (MK) e = masked(ean, eac, r) ? 0.f : e;
+                  if constexpr (KP) e = (km >> r) & 1u ? 0.f : e;
                   if constexpr (LQ) rsum = __builtin_fmaf(e, wreg(j, r), rsum);
                   else rsum += e;
                   xa = valid ? fmaxf(xa, x) : xa;
@@ -380,6 +402,7 @@ __global__ __launch_bounds__(kSymThreads) void score_fwd_sym_kernel(SymArgs g) {
                 }
               }
               if constexpr (MK) e = (b != a && masked(ean, eac, r)) ? 0.f : e;
+              if constexpr (KP) e = (b != a && ((km >> r) & 1u)) ? 0.f : e;
               if constexpr (LQ) {
                 colacc[j][r] = __builtin_fmaf(e, ua, colacc[j][r]);
                 rsum = __builtin_fmaf(e, wreg(j, r), rsum);
@@ -729,10 +752,11 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
                        bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
                        float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr,
                        const float* pw_g = nullptr, const void* X_packed = nullptr, int64_t M = 0, const float* lq_x = nullptr,
-                       const int32_t* ent_x = nullptr, float* w_x = nullptr) {
+                       const int32_t* ent_x = nullptr, float* w_x = nullptr, const int32_t* plan = nullptr, int64_t cell_capacity = 0) {
   const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
   const bool mk = ent_n != nullptr;                        // tt_score_fwd_sym_bf16_mask passes both (checked there)
   const bool xn = X_packed != nullptr;                     // tt_score_fwd_sym_bf16_xneg (M, w_x checked there)
+  const bool kp = plan != nullptr;                         // tt_score_fwd_sym_bf16_cells (never with ent_*)
   TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
   TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
@@ -755,7 +779,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
   const float ab = ab_scale == 0.f ? 1.f : ab_scale;
   const bool unit = ab == inv_t * kLog2e;                  // exactly: the caller got the scale from tt_score_unit_scale(inv_t)
-  SymArgs g{};
+  SymArgsKP g{};                                           // (the kernels without cells take its SymArgs part)
   g.a_rows = fp8 ? static_cast<const void*>(view8(N_packed, B, D).rows8) : static_cast<const void*>(view(N_packed, B, D).rows);
   g.b_rows = fp8 ? static_cast<const void*>(view8(C_packed, B, D).rows8) : static_cast<const void*>(view(C_packed, B, D).rows);
   if (x3) {
@@ -780,6 +804,7 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
     g.Rx = (int)M; g.nTx = L.nTx; g.ngi = L.n_groups;
     g.lq_x = lq_x; g.ent_x = ent_x;
   }
+  if (kp) g.kp = tt_cells_view(plan, B, M, cell_capacity);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // fp8, D = 256: two company tiles per wave (half the workgroups along J, half the slab rows)
   const int jt = (fp8 && L.Dp == 256) ? 2 : 1;
@@ -789,47 +814,56 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   const size_t wn_bytes = sizeof(float) * (L.NI * 32 + kSymWaves * 32);   // (LQ) notice weights (+ company weights, x3 D = 256)
   const size_t ent_bytes = sizeof(int) * 2 * (L.NI * 32 + kSymWaves * 32); // (MK) the a rows' ids (+ the resident tiles', D = 256)
   // one launch per form (fp8 has neither an x3 nor an LQ form, the mask bf16 operands only); only the x3, LQ and MK forms set their LDS limit
-  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc, auto mkc, auto xnc) -> int {
+  const auto go = [&](auto ks, auto fp8c, auto x3c, auto lqc, auto mkc, auto xnc, auto kpc) -> int {
     constexpr int JT = fp8c && ks == 16 ? 2 : 1;                  // = jt
     const size_t lds = slot_bytes + 2 * SymStage<ks, fp8c, x3c>::kBytes + (lqc ? wn_bytes : 0) + (mkc ? ent_bytes : 0);
     return tt_dispatch([&](auto u) -> int {
-      if constexpr (x3c || lqc || mkc || xnc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc>);
-      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc><<<grid, kSymThreads, lds, st>>>(g);
+      if constexpr (x3c || lqc || mkc || xnc || kpc) TT_LDS_ONCE(lds, &score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc, kpc>);
+      score_fwd_sym_kernel<ks, u, fp8c, JT, x3c, lqc, mkc, xnc, kpc><<<grid, kSymThreads, lds, st>>>(g);
       return TT_OK;
     }, unit);
   };
   const std::false_type no{};
   int rc;
-  if (xn) {
+  if (kp) {                                                // masked cells: LQ off / on, XN off / on, never MK
+    rc = tt_dispatch([&](auto lqc, auto xnc) {
+      switch (L.Dp) {
+        case 32: return go(tt_c<2>, no, no, lqc, no, xnc, std::true_type{});
+        case 64: return go(tt_c<4>, no, no, lqc, no, xnc, std::true_type{});
+        case 128: return go(tt_c<8>, no, no, lqc, no, xnc, std::true_type{});
+        default: return go(tt_c<16>, no, no, lqc, no, xnc, std::true_type{});
+      }
+    }, lq, xn);
+  } else if (xn) {
     const std::true_type yes{};
     rc = tt_dispatch([&](auto lqc, auto mkc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, mkc, yes);
-        case 64: return go(tt_c<4>, no, no, lqc, mkc, yes);
-        case 128: return go(tt_c<8>, no, no, lqc, mkc, yes);
-        default: return go(tt_c<16>, no, no, lqc, mkc, yes);
+        case 32: return go(tt_c<2>, no, no, lqc, mkc, yes, no);
+        case 64: return go(tt_c<4>, no, no, lqc, mkc, yes, no);
+        case 128: return go(tt_c<8>, no, no, lqc, mkc, yes, no);
+        default: return go(tt_c<16>, no, no, lqc, mkc, yes, no);
       }
     }, lq, mk);
   } else if (mk) {
     const std::true_type yes{};
     rc = tt_dispatch([&](auto lqc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, yes, no);
-        case 64: return go(tt_c<4>, no, no, lqc, yes, no);
-        case 128: return go(tt_c<8>, no, no, lqc, yes, no);
-        default: return go(tt_c<16>, no, no, lqc, yes, no);
+        case 32: return go(tt_c<2>, no, no, lqc, yes, no, no);
+        case 64: return go(tt_c<4>, no, no, lqc, yes, no, no);
+        case 128: return go(tt_c<8>, no, no, lqc, yes, no, no);
+        default: return go(tt_c<16>, no, no, lqc, yes, no, no);
       }
     }, lq);
   } else if (fp8) {
     const std::true_type yes{};
-    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no, no) : go(tt_c<16>, yes, no, no, no, no));
+    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no, no, no) : go(tt_c<16>, yes, no, no, no, no, no));
   } else {
     rc = tt_dispatch([&](auto x3c, auto lqc) {
       switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, x3c, lqc, no, no);
-        case 64: return go(tt_c<4>, no, x3c, lqc, no, no);
-        case 128: return go(tt_c<8>, no, x3c, lqc, no, no);
-        default: return go(tt_c<16>, no, x3c, lqc, no, no);
+        case 32: return go(tt_c<2>, no, x3c, lqc, no, no, no);
+        case 64: return go(tt_c<4>, no, x3c, lqc, no, no, no);
+        case 128: return go(tt_c<8>, no, x3c, lqc, no, no, no);
+        default: return go(tt_c<16>, no, x3c, lqc, no, no, no);
       }
     }, x3, lq);
   }
@@ -976,6 +1010,23 @@ int tt_score_fwd_sym_bf16_pw(tt_ctx* ctx, const void* N_packed, const void* C_pa
   return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
                      out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_pw", false, lq_n, lq_c,
                      lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c, g);
+}
+
+int tt_score_fwd_sym_bf16_cells(tt_ctx* ctx, const void* N_packed, const void* C_packed, const void* X_packed, int64_t B, int64_t M,
+                                int32_t D, float inv_t, float shift, float ab_scale, int32_t want_rank, const int32_t* plan,
+                                int64_t capacity, const float* lq_n, const float* lq_c, const float* lq_x, float* rowsum, float* colsum, float* inv_row,
+                                float* inv_col, float* w_n, float* w_c, float* w_x, float* diag, int32_t* row_rank, float* out8,
+                                float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(plan && tt_aligned(plan, 16), "tt_score_fwd_sym_bf16_cells: plan NULL or not 16-byte aligned");
+  TT_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 30), "tt_score_fwd_sym_bf16_cells: bad capacity %lld", (long long)capacity);
+  TT_CHECK_ARG(X_packed ? (M >= 1 && M < ((int64_t)1 << 30) && w_x) : M == 0, "tt_score_fwd_sym_bf16_cells: bad M=%lld (extras need M >= 1 and w_x)",
+               (long long)M);
+  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_cells: lq_n and lq_c go together");
+  TT_CHECK_ARG(!lq_x || (lq_n && X_packed), "tt_score_fwd_sym_bf16_cells: lq_x needs lq_n / lq_c and the extras");
+  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_cells: the logQ correction needs w_n / w_c");
+  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
+                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_cells", false, lq_n, lq_c,
+                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, nullptr, nullptr, nullptr, X_packed, M, lq_x, nullptr, w_x, plan, capacity);
 }
 
 }  // extern "C"

@@ -52,7 +52,7 @@ class DevicePairLoader:
 
     def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
                  shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None, extra_negatives: int = 0,
-                 negative_pool=None, mined=None, hard_fraction: float = 1.0):
+                 negative_pool=None, mined=None, hard_fraction: float = 1.0, mask_known: bool = False, known_pairs=None):
         """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
         task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
         log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
@@ -67,7 +67,12 @@ class DevicePairLoader:
         mined: a hard_negatives.MinedNegatives (or its int32 table [len(notice), per_notice], -1 = empty): the first
         H = round(hard_fraction * M) extras of a batch are drawn, uniformly with replacement, from the rows mined for THAT batch's
         notices; the other M - H, and all of a batch whose notices have no mined row, are drawn from the store as above.  A mined
-        slot's "log_q" is -log(number of candidates of its batch), its proposal's.  Not together with negative_pool."""
+        slot's "log_q" is -log(number of candidates of its batch), its proposal's.  Not together with negative_pool.
+        mask_known: every batch carries "masked_cells" int32 [L, 2]: the cells (row a, column j) whose column -- an in-batch company
+        (j < B) or an extra (j >= B) -- is a KNOWN company of row a's notice, the positive itself left out; the train task takes them
+        out of both softmax directions.  known_pairs: [P', 2] entity rows (notice index, company index), default the loader's own pair
+        table (a caller may pass train plus validation pairs).  Not together with mask_repeats (these cells hold every repeat) or
+        pair_weight."""
         self.notice, self.company, self.batch_size, self.shuffle = notice, company, batch_size, shuffle
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         if len(pairs) and (pairs[:, 0].max() >= len(notice) or pairs[:, 1].max() >= len(company) or pairs.min() < 0):
@@ -88,6 +93,104 @@ class DevicePairLoader:
         self.extra_negatives, self.negative_pool = 0, None
         self.mined, self.hard_slots, self._epoch_cand = None, 0, None
         self.set_extra_negatives(extra_negatives, negative_pool, mined, hard_fraction)
+        self.known, self.max_cells, self.eager_cell_batches = None, 0, 0
+        self.set_mask_known(mask_known, known_pairs)
+
+    def set_mask_known(self, mask_known: bool, known_pairs=None) -> None:
+        """Turns the known-pair mask on / off for every batch this loader produces from now on.  known_pairs: [P', 2] (notice index,
+        company index) rows, default the loader's pair table.  Keeps the per-notice lists of known companies (CSR, as
+        retrieval.exclusions_from_pairs builds them)."""
+        self.known, self.max_cells = None, 0
+        if not mask_known:
+            return
+        if self.entity is not None:
+            raise ValueError("mask_known does not combine with mask_repeats: the known pairs' cells hold every repeat")
+        if self.pair_weight is not None:
+            raise ValueError("mask_known does not combine with pair_weight")
+        from .retrieval import exclusions_from_pairs
+        dev = self.pairs.device
+        kp = self.pairs if known_pairs is None else torch.as_tensor(np.asarray(known_pairs, dtype=np.int64).reshape(-1, 2)).to(dev)
+        if kp.numel() and (int(kp[:, 0].min()) < 0 or int(kp[:, 0].max()) >= len(self.notice)):
+            raise KeyError("known_pairs refers to a notice that is not in the feature store")
+        if len(self.company) - 1 > np.iinfo(np.int32).max:
+            raise ValueError("mask_known: a company row does not fit int32")
+        try:
+            off, rows = exclusions_from_pairs(torch.arange(len(self.notice), device=dev), kp, len(self.company))
+        except ValueError as e:
+            raise KeyError("known_pairs refers to a company that is not in the feature store") from e
+        self.known = (off, rows.to(torch.int64))
+
+    CELLS_CHUNK_BATCHES = 8            # batches joined at a time by epoch_cells: what bounds its transient memory
+
+    def epoch_cells(self, order: Optional[torch.Tensor] = None, negatives: Optional[torch.Tensor] = None):
+        """This epoch's masked cells, or None without mask_known: (cells int32 [T, 2], bounds) -- batch k's cells are
+        cells[bounds[k][0]:bounds[k][1]] (bounds: a host list of n_batches (lo, hi) pairs; every lo is even, so every batch's slice
+        starts 16 bytes aligned and a captured step takes it as one copy segment of its hand-over -- an odd batch is followed by one
+        unused row), rows (a, j) local to the batch: a the row, j < m an in-batch column, j >= m extra j - m (m = the batch's size;
+        the ragged last batch has its own).  A cell is listed when column j's company is a known company of row a's notice and
+        j != a; each (a, j) once, rows ascending.  order / negatives: this epoch's epoch_order() and epoch_negatives().
+        Vectorised device passes over CELLS_CHUNK_BATCHES batches at a time and ONE read of the per-batch counts at the end (their
+        largest is kept as self.max_cells).  Memory: the result, 8 bytes per cell of the epoch, plus the join's transient arrays --
+        about ten int64 arrays over the (row, known company) keys and the hits of ONE chunk, i.e. some 100 bytes per cell of the
+        chunk's batches (a pair table in which a few companies bid everywhere lists a few per cent of B * (B + M) cells per batch)."""
+        if self.known is None:
+            return None
+        if self.shuffle and order is None:
+            raise ValueError("epoch_cells(): a shuffling loader needs this epoch's order")
+        if (negatives is not None) != bool(self.extra_negatives):
+            raise ValueError("epoch_cells(): a loader with extra_negatives needs this epoch's epoch_negatives(), one without takes none")
+        n, B, dev = self.pairs.shape[0], self.batch_size, self.pairs.device
+        nb = len(self)
+        sel = self.pairs if order is None else self.pairs[order]
+        parts = [self._chunk_cells(sel, negatives, b0, min(b0 + self.CELLS_CHUNK_BATCHES, nb))
+                 for b0 in range(0, nb, self.CELLS_CHUNK_BATCHES)]
+        k = torch.cat([p[0] for p in parts]) if parts else torch.zeros(0, dtype=torch.int64, device=dev)
+        aj = torch.cat([p[1] for p in parts]) if parts else torch.zeros((0, 2), dtype=torch.int32, device=dev)
+        counts = torch.bincount(k, minlength=nb)
+        padded = (counts + 1) // 2 * 2                                     # every batch starts on an even row
+        start = torch.cumsum(padded, 0) - padded
+        first = torch.cumsum(counts, 0) - counts
+        host = torch.stack([start, counts]).tolist()                      # the epoch's one read of the counts
+        cells = torch.zeros((int(sum(host[1])) + int(sum(c & 1 for c in host[1])), 2), dtype=torch.int32, device=dev)
+        cells[start[k] + (torch.arange(k.shape[0], dtype=torch.int64, device=dev) - first[k])] = aj
+        bounds = [(lo, lo + c) for lo, c in zip(host[0], host[1])]
+        self.max_cells = max(host[1], default=0)
+        return cells, bounds
+
+    def _chunk_cells(self, sel, negatives, b0, b1):
+        """(batch index int64 [T], (a, j) int32 [T, 2]) of the batches b0 .. b1 - 1, sorted by batch, row, column"""
+        n, B, M, dev = self.pairs.shape[0], self.batch_size, self.extra_negatives, self.pairs.device
+        Nc, nbc = len(self.company), b1 - b0
+        koff, krows = self.known
+        r0, r1 = b0 * B, min(b1 * B, n)
+        sub = sel[r0:r1]
+        # the columns of every batch: its companies, then its extras; a slot past the ragged batch's end never matches
+        cols = torch.full((nbc * B,), -1, dtype=torch.int64, device=dev)
+        cols[:r1 - r0] = sub[:, 1]
+        cols = cols.view(nbc, B)
+        if M:
+            cols = torch.cat([cols, negatives[b0:b1].to(torch.int64)], 1)
+        bk = torch.arange(nbc, dtype=torch.int64, device=dev)[:, None]
+        ckey, cperm = torch.sort(torch.where(cols >= 0, bk * Nc + cols, torch.full_like(cols, -1)).view(-1), stable=True)
+        # every (row, known company of its notice): the row's batch and that company as one key, looked up among the columns' keys
+        deg = koff[sub[:, 0] + 1] - koff[sub[:, 0]]
+        row = torch.repeat_interleave(torch.arange(r1 - r0, dtype=torch.int64, device=dev), deg)
+        first = torch.cumsum(deg, 0) - deg
+        comp = krows[koff[sub[row, 0]] + (torch.arange(row.shape[0], dtype=torch.int64, device=dev) - first[row])]
+        key = (row // B) * Nc + comp
+        lo = torch.searchsorted(ckey, key, right=False)
+        cnt = torch.searchsorted(ckey, key, right=True) - lo
+        hit = torch.repeat_interleave(torch.arange(key.shape[0], dtype=torch.int64, device=dev), cnt)   # a company met twice: both columns
+        cfirst = torch.cumsum(cnt, 0) - cnt
+        pos = cperm[lo[hit] + (torch.arange(hit.shape[0], dtype=torch.int64, device=dev) - cfirst[hit])] % (B + M)
+        a = row[hit] % B
+        kb = row[hit] // B
+        size = torch.clamp(n - (kb + b0) * B, max=B)                      # the batch's own row count: where its extras' columns start
+        j = torch.where(pos < B, pos, pos - B + size)
+        keep = j != a
+        kb, a, j = kb[keep], a[keep], j[keep]
+        srt = torch.argsort((kb * B + a) * (B + M) + j)                    # by batch, row, column
+        return kb[srt] + b0, torch.stack([a[srt], j[srt]], 1).to(torch.int32)
 
     def set_extra_negatives(self, extra_negatives: int, negative_pool=None, mined=None, hard_fraction: float = 1.0) -> None:
         """M >= 0 shared extra negatives per batch (0: none), drawn from the whole company store or from `negative_pool` (int64 [n >= 1]
@@ -189,6 +292,8 @@ class DevicePairLoader:
             return
         if getattr(self, "extra_negatives", 0):
             raise ValueError("pair_weight does not combine with extra_negatives")
+        if getattr(self, "known", None) is not None:
+            raise ValueError("pair_weight does not combine with mask_known")
         P = self.pairs.shape[0]
         t = pair_weight
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != P:
@@ -200,6 +305,8 @@ class DevicePairLoader:
         """Turns the repeated-entity mask on / off for every batch this loader produces from now on: with it `entity` holds the pair
         table's columns as int32 [2, P] (notice indices, company indices)."""
         self.entity = None
+        if mask_repeats and getattr(self, "known", None) is not None:
+            raise ValueError("mask_repeats does not combine with mask_known: the known pairs' cells hold every repeat")
         if mask_repeats:
             if self.pairs.numel() and int(self.pairs.max()) > np.iinfo(np.int32).max:
                 raise ValueError("mask_repeats: an entity index does not fit int32")
@@ -230,10 +337,13 @@ class DevicePairLoader:
         n = self.pairs.shape[0]
         return torch.randperm(n, generator=self._gen, device=self.pairs.device) if self.shuffle else None
 
-    def batch(self, order: Optional[torch.Tensor], lo: int, negatives: Optional[torch.Tensor] = None) -> Dict:
-        """negatives: this batch's row of epoch_negatives() (a loader with extras: required)"""
+    def batch(self, order: Optional[torch.Tensor], lo: int, negatives: Optional[torch.Tensor] = None, cells=None) -> Dict:
+        """negatives: this batch's row of epoch_negatives() (a loader with extras: required); cells: epoch_cells()'s result (a loader
+        with mask_known: required)"""
         if (negatives is not None) != bool(self.extra_negatives):
             raise ValueError("batch(): a loader with extra_negatives needs this batch's row of epoch_negatives(), one without takes none")
+        if (cells is not None) != (self.known is not None):
+            raise ValueError("batch(): a loader with mask_known needs this epoch's epoch_cells(), one without takes none")
         sel = self.pairs[lo:lo + self.batch_size] if order is None else self.pairs[order[lo:lo + self.batch_size]]
         out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
         if self.pair_weight is not None:
@@ -248,6 +358,9 @@ class DevicePairLoader:
         if negatives is not None:
             mined = self.mined is not None and self._epoch_cand is not None
             out["negatives"] = self.negatives(negatives, self._epoch_cand[lo // self.batch_size] if mined else None)
+        if cells is not None:
+            k = lo // self.batch_size
+            out["masked_cells"] = cells[0][cells[1][k][0]:cells[1][k][1]]
         return out
 
     def epoch_entity(self, order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -297,8 +410,9 @@ class DevicePairLoader:
     def __iter__(self) -> Iterator[Dict]:
         order = self.epoch_order()
         neg = self.epoch_negatives(order)
+        cells = self.epoch_cells(order, neg)
         for k, lo in enumerate(range(0, self.pairs.shape[0], self.batch_size)):
-            yield self.batch(order, lo, None if neg is None else neg[k])
+            yield self.batch(order, lo, None if neg is None else neg[k], cells)
 
     def eval_batches(self, graphed_eval, eager_eval=None, max_batches: Optional[int] = None) -> int:
         """One pass over the pairs in order (no shuffling is applied here: the reference's test loader does not shuffle) through a
@@ -328,13 +442,28 @@ class DevicePairLoader:
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))
         neg = self.epoch_negatives(order)
-        if neg is not None:
-            # extra negatives: no store-fed hand-over -- the batches __iter__ yields, through the captured step's plain-copy hand-over
-            # step(batch) (a step captured on a batch with the same M), the ragged one through ragged_step or the eager callable
+        cells = self.epoch_cells(order, neg)
+        if neg is not None or cells is not None:
+            # extra negatives / masked cells: no store-fed hand-over -- the batches __iter__ yields, through the captured step's plain-copy
+            # hand-over step(batch) (a step captured on a batch with the same M), the ragged one through ragged_step or the eager callable
             if U > 1:
-                raise NotImplementedError("extra negatives are not supported by the unrolled step")
+                raise NotImplementedError("extra negatives and masked cells are not supported by the unrolled step")
             for k, lo in enumerate(range(0, n, B)):
-                b = self.batch(order, lo, neg[k])
+                b = self.batch(order, lo, None if neg is None else neg[k], cells)
+                if cells is not None and eager_step is not None:
+                    # the captured step this batch would take; with more cells than it has room for (.step would raise) the batch goes
+                    # through the eager step instead -- counted in self.eager_cell_batches and warned about once per loader
+                    g = graphed_step if lo + B <= n else (ragged_step if ragged_step is not None and
+                                                          ragged_step.static["notice"]["dense"].shape[0] == n - lo else None)
+                    if g is not None and b["masked_cells"].shape[0] > getattr(g, "cell_capacity", 0):
+                        self.eager_cell_batches += 1
+                        if self.eager_cell_batches == 1:
+                            import warnings
+                            warnings.warn(f"a batch carries {b['masked_cells'].shape[0]} masked cells, the captured step has room for "
+                                          f"{g.cell_capacity} (cell_capacity): such batches run through the eager step "
+                                          "(DevicePairLoader.eager_cell_batches counts them)")
+                        yield eager_step(b)
+                        continue
                 if lo + B <= n and graphed_step is not None:
                     yield graphed_step.step(b)
                 elif ragged_step is not None and lo + B > n and ragged_step.static["notice"]["dense"].shape[0] == n - lo:
@@ -368,12 +497,14 @@ class DevicePairLoader:
                 yield eager_step(self.batch(order, lo))
 
     def _plain_batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
-        """batch(order, lo) without extras, whatever the loader draws for training (evaluation ranks the batch's own companies)"""
+        """batch(order, lo) without extras or masked cells, whatever the loader draws for training (evaluation ranks the batch's own
+        companies)"""
         M, self.extra_negatives = self.extra_negatives, 0
+        known, self.known = self.known, None
         try:
             return self.batch(order, lo)
         finally:
-            self.extra_negatives = M
+            self.extra_negatives, self.known = M, known
 
     def ragged_example(self) -> Optional[Dict]:
         """A batch of the remainder's size (pairs % batch_size), or None when the epoch has no ragged batch: the example a second
@@ -399,6 +530,8 @@ class DevicePairLoader:
             n_pool = self.negative_pool.shape[0] if self.negative_pool is not None else len(self.company)
             idx = torch.arange(self.extra_negatives, device=self.pairs.device) % n_pool
             out["negatives"] = self.negatives(self.negative_pool[idx] if self.negative_pool is not None else idx)
+        if self.known is not None:                            # (an example of the right form: an empty list)
+            out["masked_cells"] = torch.zeros((0, 2), dtype=torch.int32, device=self.pairs.device)
         return out
 
 

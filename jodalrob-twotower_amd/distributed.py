@@ -550,6 +550,9 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
     def _negatives_ok(self):
         return False                                   # extra negatives (a batch with 'negatives'): not by the sharded task
 
+    def _cells_ok(self):
+        return False                                   # masked cells (a batch with 'masked_cells'): not by the sharded task
+
     def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None):
         if pair_weight is not None:
             raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")

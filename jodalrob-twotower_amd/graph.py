@@ -36,10 +36,12 @@ class GraphedTrainStep:
     _entity_ok = True              # batches may carry "entity" (the repeated-entity mask); likewise
     _pair_weight_ok = True         # batches may carry "pair_weight" (per-pair sample weights); likewise
     _negatives_ok = True           # batches may carry "negatives" (shared extra negatives); likewise
+    _cells_ok = True               # batches may carry "masked_cells" (pairs that are never negatives); likewise
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
-                 accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None, fuse_score_tail: bool = True):
+                 accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None, fuse_score_tail: bool = True,
+                 cell_capacity: Optional[int] = None):
         """defer_long / defer_slabs: the long rows' finish rides in the optimiser's launch and the towers' slab reduction in the
         embedding gradient's (both bit-identical to the separate launches; the arguments exist for that comparison).
         fuse_score_tail: the score backward waits for the towers' backward, which launches it with its own first kernel's work in
@@ -51,7 +53,9 @@ class GraphedTrainStep:
         accumulate_metrics: `metric_sums` (device, 8 floats: loss, accuracy, positive mean, negative mean, gap, ...: twotower.h
         tt_score_loss_finish) += the step's figures inside the replay -- an epoch's mean loss / accuracy (the reference driver's
         avg_train_loss: scripts/train.py:357-358) without a host sync per step.  metric_sums: add into THIS tensor (another captured
-        step's sums: the two then share one epoch total; what it holds survives this object's warm-up)."""
+        step's sums: the two then share one epoch total; what it holds survives this object's warm-up).
+        cell_capacity: rows of the static masked-cells buffer of a step captured on a batch with "masked_cells" (default: four times
+        the example's, at least 1024); a later batch with more cells is refused."""
         # logQ correction: an example batch with "log_q" (either side) gives both sides a static [B] buffer; every hand-over then
         # brings this step's values as two more copy segments of its one launch (the captured forward reads the buffers)
         self._has_log_q = any(example_batch[side].get("log_q") is not None for side in ("notice", "company"))
@@ -84,6 +88,17 @@ class GraphedTrainStep:
                 raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
             if getattr(task, "exchange", None) is not None:
                 raise NotImplementedError("extra negatives (a batch with 'negatives') are not supported by the sharded task")
+        # masked cells: an example batch with "masked_cells" gets a static int32 [capacity, 2] buffer and a device count (one more word of
+        # the step's scalars); every hand-over brings this step's L cells as one more copy segment, and the plan launches that bucket
+        # them are nodes of the captured graph (their grids depend on the capacity alone)
+        self._has_cells = example_batch.get("masked_cells") is not None
+        if self._has_cells:
+            if not self._cells_ok:
+                raise NotImplementedError(f"masked cells (a batch with 'masked_cells') are not supported by {type(self).__name__}")
+            if getattr(task, "exchange", None) is not None:
+                raise NotImplementedError("masked cells (a batch with 'masked_cells') are not supported by the sharded task")
+        elif cell_capacity is not None:
+            raise ValueError("cell_capacity: the example batch carries no 'masked_cells'")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
@@ -115,9 +130,9 @@ class GraphedTrainStep:
                 if neg.get(k) is not None:
                     self.static["negatives"][k] = neg[k].clone()
         ng = len(optimizer.param_groups)
-        # per-step scalars (Adam step sizes, dropout seed) travel through a RING of pinned host slots: the copy
+        # per-step scalars (Adam step sizes, dropout seed, the masked cells' count) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
-        self._n_scalar = ng * 8 + 2
+        self._n_scalar = ng * 8 + 2 + (2 if self._has_cells else 0)
         self._slot_len = (self._n_scalar + 3) // 4 * 4                 # 16-byte slots
         self._ring = 64
         self._host_ring = torch.zeros(self._ring, self._slot_len, dtype=torch.float32).pin_memory()
@@ -125,9 +140,18 @@ class GraphedTrainStep:
         self._slot = 0
         self._unmarked = []                                            # ring slots filled since the last _mark_slot
         self._host = self._host_ring[0, :self._n_scalar]
-        self._dev = torch.zeros(ng * 8 + 2, dtype=torch.float32, device=dev)
+        self._dev = torch.zeros(self._n_scalar, dtype=torch.float32, device=dev)
         self._hp_dev = self._dev[:ng * 8].view(ng, 8)
-        self._seed_dev = self._dev[ng * 8:].view(torch.int64)          # 2 floats = one 64-bit word
+        self._seed_dev = self._dev[ng * 8:ng * 8 + 2].view(torch.int64)          # 2 floats = one 64-bit word
+        if self._has_cells:
+            ex = self._check_cells(example_batch["masked_cells"], dev, None)
+            cap = max(4 * ex.shape[0], 1024) if cell_capacity is None else int(cell_capacity)
+            if cap < max(ex.shape[0], 1):
+                raise ValueError(f"cell_capacity = {cap}: the example batch carries {ex.shape[0]} cells (and at least 1)")
+            self.cell_capacity, self._cells_n = cap, ex.shape[0]
+            self.static["masked_cells"] = torch.zeros((cap, 2), dtype=torch.int32, device=dev)
+            self.static["masked_cells"][:ex.shape[0]] = ex
+            self.static["masked_cells_count"] = self._dev[ng * 8 + 2:ng * 8 + 3].view(torch.int32)      # (the scalars' copy fills it)
         self._ones = torch.ones((), dtype=torch.float32, device=dev)
         self._towers = [m for m in task.modules() if hasattr(m, "_seed_dev") and hasattr(m, "dense_parameters")]
         self.metric_sums = torch.zeros(8, dtype=torch.float32, device=dev) if (accumulate_metrics and return_metrics) else None
@@ -437,7 +461,9 @@ class GraphedTrainStep:
                 continue
             hp = ops.adam_hparams(step, float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
             host[gi * 8: gi * 8 + 6] = torch.tensor(hp)
-        host[ng * 8:].view(torch.int64).random_()
+        host[ng * 8:ng * 8 + 2].view(torch.int64).random_()
+        if self._has_cells:
+            host[ng * 8 + 2:ng * 8 + 4].view(torch.int32)[0] = self._cells_n
         return (self._dev, host)
 
     def _mark_slot(self):
@@ -489,6 +515,39 @@ class GraphedTrainStep:
             raise ValueError(f"pair_weight is on {t.device}, the captured step on {dev}")
         t = t.contiguous()
         return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    @staticmethod
+    def _check_cells(t, dev, capacity):
+        """t as a contiguous int32 [L, 2] on dev, L <= capacity (L is the tensor's shape: no synchronisation)"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2:
+            raise ValueError(f"masked_cells must be an int32 tensor of shape [L, 2], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != dev:
+            raise ValueError(f"masked_cells is on {t.device}, the captured step on {dev}")
+        if capacity is not None and t.shape[0] > capacity:
+            raise ValueError(f"masked_cells: {t.shape[0]} cells, the step was captured with cell_capacity = {capacity}")
+        return t.contiguous()
+
+    def _cells_check(self, batch):
+        """this step's cells after the with / without and the capacity checks -- before anything is copied"""
+        cells = None if batch is None else batch.get("masked_cells")
+        if batch is not None and (cells is not None) != self._has_cells:
+            raise ValueError("masked_cells mismatch: the step was captured " + ("with" if self._has_cells else "without") +
+                             " masked cells, the batch " + ("has none" if self._has_cells else "carries them"))
+        return None if cells is None else self._check_cells(cells, self._dev.device, self.cell_capacity)
+
+    def _cells_pairs(self, cells):
+        """the copy segment of this step's cells into the head of the static buffer; their count goes with the step's scalars"""
+        if cells is None:
+            return []
+        self._cells_n = n = cells.shape[0]
+        if n == 0:
+            return []
+        dst = self.static["masked_cells"][:n]
+        if cells.data_ptr() % 16:                               # (the copy launch moves 16-byte pieces: a slice of an epoch's array)
+            dst.copy_(cells, non_blocking=True)
+            return []
+        return [(dst, cells)]
 
     def _pair_weight_pairs(self, w, who):
         """the copy segment of this step's pair weights into the static buffer, after the with / without check"""
@@ -569,7 +628,9 @@ class GraphedTrainStep:
 
     def step(self, batch: Optional[Dict] = None):
         """Train on `batch` (or on whatever the static buffers hold); returns the static result."""
+        cells = self._cells_check(batch)
         pairs, src_ids = self._handover_pairs(batch)
+        pairs += self._cells_pairs(cells)
         if self._ingest is not None:
             # ONE launch: the four batch buffers + the scalars + the key-major rows of this step's ids -- also when nobody handed a
             # batch over: the static id buffers may have been written to by means no version counter sees (`.data`), and the
@@ -604,6 +665,8 @@ class GraphedTrainStep:
         entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
         DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise.
         pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment."""
+        if self._has_cells:
+            raise NotImplementedError("masked cells: no store-fed hand-over -- a step captured with 'masked_cells' takes step(batch)")
         if self._has_negatives:
             raise NotImplementedError("extra negatives: no store-fed hand-over -- a step captured with 'negatives' takes step(batch)")
         if (log_q is not None) != self._has_log_q:

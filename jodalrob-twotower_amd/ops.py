@@ -927,6 +927,129 @@ def score_dir_bwd_xneg(A, Bm, inv_t, shift, x_is_b, rowsum, d_loss, scale, lq_x=
     return dA
 
 
+# masked cells (the *_cells entries of include/twotower.h): a sparse per-step list of (row, column) pairs that are never negatives
+def score_cells_check(cells, dev, name="masked_cells"):
+    """int32 [L, 2] on `dev`, L >= 0 (validated: no device sync); returns it contiguous"""
+    if not isinstance(cells, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(cells).__name__}")
+    if cells.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {cells.dtype}")
+    if cells.dim() != 2 or cells.shape[1] != 2:
+        raise ValueError(f"{name} must have shape [L, 2], got {list(cells.shape)}")
+    if cells.device != torch.device(dev):
+        raise ValueError(f"{name} is on {cells.device}, the scores on {dev}")
+    return cells.contiguous()
+
+
+def score_cells_plan(cells, B, M=0, count=None, out=None):
+    """The masked cells bucketed by 32 x 32 tile pair (tt_score_cells_plan), what score_fwd_sym_cells / score_bwd_bf16_cells take.
+    cells int32 [capacity, 2] rows (a, j), a in [0, B), j in [0, B + M) (j >= B: extra j - B); cells on the diagonal or outside the
+    ranges are dropped, duplicates and order are free.  count: int32 [1] on the device -- only the first min(count, capacity) rows are
+    read (None: all of them); the launches' grids depend on the capacity alone, so the call can be captured with a static `cells` buffer
+    and a device count.  out: a plan buffer of an earlier call with the same B, M and capacity, refilled in place."""
+    dev = cells.device
+    cells = score_cells_check(cells, dev)
+    L_ = cells.shape[0]
+    cap = max(L_, 1)
+    if L_ == 0:                                                        # (the entry wants one slot; the count says it is unused)
+        cells = torch.zeros((1, 2), dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev) if count is None else count
+    if count is None:
+        count = torch.full((1,), L_, dtype=torch.int32, device=dev)
+    elif not (isinstance(count, torch.Tensor) and count.dtype == torch.int32 and count.numel() == 1 and count.device == dev):
+        raise ValueError(f"count must be an int32 tensor of one element on {dev}")
+    lib = L.load()
+    n = lib.tt_score_cells_plan_bytes(B, M, cap) // 4
+    if n == 0:
+        raise ValueError(f"masked cells: bad shape B={B} M={M} capacity={cap}")
+    plan = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
+    if plan.dtype != torch.int32 or plan.numel() < n or plan.device != dev or not plan.is_contiguous():
+        raise ValueError(f"out must be a contiguous int32 tensor of at least {n} elements on {dev}")
+    # the tile pairs' counters: memory of this call's own, kept with the plan (not the stream's shared scratch)
+    ws = torch.empty(lib.tt_score_cells_plan_workspace_bytes(B, M), dtype=torch.uint8, device=dev)
+    with _timed("tt_score_cells_plan"):
+        L.check(lib.tt_score_cells_plan(L.ctx(dev), L.ptr(cells), L.ptr(count), cap, B, M, L.ptr(plan), plan.numel() * 4, L.ptr(ws),
+                                        ws.numel(), L.stream(dev)), "tt_score_cells_plan")
+    plan._tt_keep = (cells, count, ws)
+    plan._tt_cap = cap
+    return plan
+
+
+def score_cells_unpack(plan, B, M=0):
+    """(offsets int64 [nT * (nT + nTx) + 1], codes int32 [offsets[-1]]) of a plan, on the host -- a debugging / test aid (synchronises)"""
+    nT, nTx = (B + 31) // 32, (M + 31) // 32
+    n_pairs = nT * (nT + nTx)
+    at = (n_pairs + 1 + 3) // 4 * 4
+    p = plan.cpu()
+    off = p[:n_pairs + 1].long()
+    return off, p[at:at + int(off[-1])]
+
+
+def score_fwd_sym_cells(Np, Cp, B, D, inv_t, shift, plan, Xp=None, M=0, lq_n=None, lq_c=None, lq_x=None, scale_n: float = 1.0,
+                        want_rank: bool = True):
+    """score_fwd_sym (/_lq, /_xneg without ids) on the masked cells of `plan` = score_cells_plan(cells, B, M)
+    (tt_score_fwd_sym_bf16_cells).  Returns as score_fwd_sym_xneg: (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, w_x, out8,
+    loss), w_x None without extras."""
+    dev = Np.device
+    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
+    if (Xp is None) != (M == 0):
+        raise ValueError("masked cells: the extras' image Xp and M >= 1 go together")
+    if lq_x is not None and (not lq or Xp is None):
+        raise ValueError("masked cells: lq_x needs lq_n / lq_c and the extras")
+    if lq:
+        _lq_check_t(inv_t)
+    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
+    Bp, Mp = (B + 63) // 64 * 64, (M + 63) // 64 * 64
+    f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
+    w_x = torch.empty(Mp, dtype=torch.float32, device=dev) if M else None
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    out8 = torch.empty(8, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lib = L.load()
+    nbytes = lib.tt_score_fwd_sym_xneg_workspace_bytes(B, M, D) if M else lib.tt_score_fwd_sym_workspace_bytes(B, D)
+    if L.riders_deferred(dev, 2):                                      # (as _fwd_sym: the partial records outlive the shared scratch)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out8._tt_keep = ws
+    else:
+        ws = L.workspace(dev, nbytes)
+    name = "tt_score_fwd_sym_bf16_cells"
+    with _timed(name):
+        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), L.ptr(Xp), B, M, D, inv_t, shift, scale_n, int(want_rank), L.ptr(plan),
+                                   int(plan._tt_cap), *(map(L.ptr, lq) if lq else (None, None)), L.ptr(lqx), L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]),
+                                   L.ptr(f[4]), *((L.ptr(f[5]), L.ptr(f[6])) if lq else (None, None)), L.ptr(w_x), L.ptr(f[2]), L.ptr(rank),
+                                   L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
+    w = (f[5][:B], f[6][:B]) if lq else None
+    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), w, w_x, out8, loss
+
+
+def score_bwd_bf16_cells(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, plan, scale_n: float = 1.0, inv=None, w=None,
+                         Xp=None, M=0, w_x=None):
+    """The backward on score_fwd_sym_cells' sums (tt_score_bwd_bf16_cells): returns (dN, dC, dX), dX None without extras.  inv / w: that
+    forward's (views of its padded arrays); with extras (Xp, M, w_x) inv is required -- its inv_row is the extras' row factor."""
+    dev = Np.device
+    if (Xp is None) != (M == 0) or (Xp is None) != (w_x is None):
+        raise ValueError("masked cells: the extras' image Xp, M >= 1 and w_x go together")
+    if Xp is not None and inv is None:
+        raise ValueError("masked cells: the extras' backward needs inv, the forward's reciprocals")
+    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dX = torch.empty((M, D), dtype=torch.float32, device=dev) if M else None
+    arr = (L.ScoreBwdDir * 2)()
+    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
+    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)
+    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)
+    lq = None
+    if w is not None:
+        lq = (L.ScoreBwdLq * 2)()
+        lq[0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))
+        lq[1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
+    name = "tt_score_bwd_bf16_cells"
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), arr, L.ptr(plan), int(plan._tt_cap), lq, L.ptr(Xp), M, ir, L.ptr(w_x), L.ptr(dX), D, inv_t, shift,
+                                        L.ptr(d_loss), scale, L.stream(dev)), name)
+    return dN, dC, dX
+
+
 def score_dir_fwd_lq(A, Bm, inv_t, shift, lq_b, diag_offset=0, want_sumscore=True):
     """score_dir_fwd(..., lq_b=lq_b)"""
     return score_dir_fwd(A, Bm, inv_t, shift, diag_offset, want_sumscore, lq_b=lq_b)

@@ -92,6 +92,7 @@ class SegmentedTrainStep(GraphedTrainStep):
     _entity_ok = False             # the repeated-entity mask likewise
     _pair_weight_ok = False        # pair weights likewise
     _negatives_ok = False          # extra negatives likewise
+    _cells_ok = False              # masked cells likewise
 
     segmented = True
 

@@ -63,16 +63,26 @@ class _ScoreCEFn(torch.autograd.Function):
     x (f32 [M, D] unit rows, with optional lq_x f32 [M] / ent_x int32 [M]): shared extra negatives (include/twotower.h *_xneg
     entries) -- M more columns of every notice's row-direction softmax, no positive, no column sum; an extra is masked for row a iff
     ent_x[m] == ent_c[a]; score_dtype 'bf16' and 'fp32' only; combines with lq_* and ent_*, not with pair_w.  The node packs N, C and
-    X itself.  accuracy / row_rank are over the B + M scores, the other metrics the in-batch ones."""
+    X itself.  accuracy / row_rank are over the B + M scores, the other metrics the in-batch ones.
+    cells (int32 [L, 2] rows (a, j), a < B, j < B + M; with optional cell_count int32 [1] on the device: only the first cell_count rows
+    count): masked cells (include/twotower.h *_cells entries) -- the listed pairs leave the row softmax (in-batch columns and extras)
+    and, for j < B, the column softmax; the diagonal and cells out of range are ignored; score_dtype 'bf16' only; combines with lq_*
+    and x (with lq_x), not with ent_* or pair_w; metrics on the raw scores."""
 
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
-                lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None, x=None, lq_x=None, ent_x=None):
+                lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None, x=None, lq_x=None, ent_x=None, cells=None, cell_count=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
         lq = lq_n is not None
         fp8, x3 = score_dtype == "fp8", score_dtype == "bf16x3"
+        ctx.kp = None
+        if cells is not None:
+            if ent_n is not None or ent_c is not None or ent_x is not None:
+                raise ValueError("masked cells do not combine with the repeated-entity mask (cells built from the pair table hold every repeat)")
+            return _ScoreCEFn._forward_cells(ctx, n, c, inv_t, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c, pair_w, x,
+                                             lq_x, cells, cell_count)
         if x is not None:
             return _ScoreCEFn._forward_xneg(ctx, n, c, inv_t, score_dtype, want_col_rank, lq_n, lq_c, ent_n, ent_c, pair_w, x, lq_x, ent_x)
         ctx.xn = None
@@ -211,13 +221,81 @@ class _ScoreCEFn(torch.autograd.Function):
         return loss, out8, row_rank
 
     @staticmethod
+    def _forward_cells(ctx, n, c, inv_t, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c, pair_w, x, lq_x, cells, cell_count):
+        """forward with masked cells (and optionally extras x [M, D]): the plan launches, then the symmetric sweep on it"""
+        B, D = n.shape
+        dev, shift, lq = n.device, abs(inv_t), lq_n is not None
+        if score_dtype != "bf16":
+            raise ValueError(f"masked cells have no {score_dtype} form (score_dtype 'bf16')")
+        if pair_w is not None:
+            raise ValueError("masked cells do not combine with pair weights")
+        if c.shape != n.shape:
+            raise ValueError("masked cells need as many notice rows as company rows")
+        cells = ops.score_cells_check(cells, dev)
+        M, Xp = 0, None
+        if x is not None:
+            if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1 or x.device != dev:
+                raise ValueError(f"the extra negatives must be a [M >= 1, {D}] tensor on {dev}")
+            x = x.contiguous().float()
+            M = x.shape[0]
+        if lq:
+            ops._lq_check_t(inv_t)
+            if x is not None and lq_x is None:               # a missing log_q on the extras counts as zeros
+                lq_x = torch.zeros(M, dtype=torch.float32, device=dev)
+        elif lq_x is not None:
+            raise ValueError("the extras carry log_q but the batch is not corrected")
+        if x is None and packed_n is not None and packed_c is not None:
+            Np, Cp = packed_n, packed_c
+            scale_n = 1.0 if scale_n is None else scale_n
+        else:
+            scale_n = ops.score_unit_scale(inv_t)
+            Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
+        if x is not None:
+            Xp = ops.score_pack_bf16(x, 1.0)
+        plan = ops.score_cells_plan(cells, B, M, count=cell_count)
+        rowsum, colsum, diag, row_rank, inv, w, w_x, out8, loss = ops.score_fwd_sym_cells(Np, Cp, B, D, inv_t, shift, plan, Xp, M, lq_n, lq_c,
+                                                                                          lq_x, scale_n, True)
+        if want_col_rank:                                    # the first call's column top-1 rate (a diagnostic only)
+            col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n)[4]
+            out8 = out8.clone()
+            out8[5] = (col_rank == 0).float().mean()
+        ctx.packed = (Np, Cp, scale_n, inv)
+        ctx.kp = (plan, Xp, w_x, M)
+        ctx.xn = None
+        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = False, False, w, None, None
+        if x is not None:
+            ctx.save_for_backward(n, c, rowsum, colsum, x)
+        else:
+            ctx.save_for_backward(n, c, rowsum, colsum)
+        ctx.inv_t, ctx.shift = inv_t, shift
+        ctx.mark_non_differentiable(out8, row_rank)
+        ctx.set_materialize_grads(False)
+        return loss, out8, row_rank
+
+    @staticmethod
+    def _backward_cells(ctx, d_loss):
+        n, c, rowsum, colsum = ctx.saved_tensors[:4]
+        B, D = n.shape
+        if d_loss is None:
+            return (None,) * 19
+        if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
+            d_loss = d_loss.contiguous().float()
+        plan, Xp, w_x, M = ctx.kp
+        Np, Cp, scale_n, inv = ctx.packed
+        dN, dC, dX = ops.score_bwd_bf16_cells(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, ctx.inv_t / (2.0 * B), plan, scale_n,
+                                              inv, w=ctx.lq, Xp=Xp, M=M, w_x=w_x)
+        return (dN, dC) + (None,) * 12 + (dX, None, None, None, None)
+
+    @staticmethod
     def backward(ctx, d_loss, _d_out8, _d_rank):
+        if ctx.kp is not None:
+            return _ScoreCEFn._backward_cells(ctx, d_loss)
         if ctx.xn is not None:
             return _ScoreCEFn._backward_xneg(ctx, d_loss)
         n, c, rowsum, colsum = ctx.saved_tensors
         B, D = n.shape
         if d_loss is None:
-            return (None,) * 17
+            return (None,) * 19
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
@@ -229,7 +307,7 @@ class _ScoreCEFn(torch.autograd.Function):
             lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
             dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent, pw=ctx.pw)
             dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent, pw=ctx.pw)
-        return (dN, dC) + (None,) * 15
+        return (dN, dC) + (None,) * 17
 
     @staticmethod
     def _backward_xneg(ctx, d_loss):
@@ -239,7 +317,7 @@ class _ScoreCEFn(torch.autograd.Function):
         B, D = n.shape
         M = x.shape[0]
         if d_loss is None:
-            return (None,) * 17
+            return (None,) * 19
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
         scale = ctx.inv_t / (2.0 * B)
@@ -255,7 +333,7 @@ class _ScoreCEFn(torch.autograd.Function):
             dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent)
             ops.score_dir_bwd_xneg(n, x, ctx.inv_t, ctx.shift, True, rowsum, d_loss, scale, lq_x=lq_x, ent_a=ec, ent_b=exs, out=dN)
             dX = ops.score_dir_bwd_xneg(x, n, ctx.inv_t, ctx.shift, False, rowsum, d_loss, scale, lq_x=lq_x, ent_a=exs, ent_b=ec)
-        return (dN, dC) + (None,) * 12 + (dX, None, None)
+        return (dN, dC) + (None,) * 12 + (dX, None, None, None, None)
 
 
 class _Result(dict):
@@ -333,12 +411,16 @@ class TwoTowerTrainTask(nn.Module):
         ent = self._batch_entity(notice_input, company_input, nb)
         pw = self._batch_pair_weight(batch, nb)
         neg = self._batch_negatives(batch, company_input, nb, lq, ent, pw)
+        cells = self._batch_cells(batch, nb, ent, pw)
         if neg is not None:
-            notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, neg, nb, lq, ent)
+            notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, neg, nb, lq, ent, cells)
         else:
             notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
         if neg is not None:
             pass                                             # (scored above, with the extras)
+        elif cells is not None:
+            loss, out8, _ = self._score_ce_cells(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
+                                                 not hasattr(self, "_pair_check_done"), lq, cells)
         elif pw is not None:
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
                                            not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw)
@@ -372,6 +454,8 @@ class TwoTowerTrainTask(nn.Module):
             raise ValueError("forward_with_ranks does not take a batch with 'pair_weight' (evaluation is unweighted)")
         if batch.get("negatives") is not None:
             raise ValueError("forward_with_ranks does not take a batch with 'negatives' (evaluation ranks the batch's own companies)")
+        if batch.get("masked_cells") is not None:
+            raise ValueError("forward_with_ranks does not take a batch with 'masked_cells' (evaluation filters with exclusion lists)")
         with torch.no_grad():
             n, c = self.two_tower_model(batch["notice"], batch["company"])
             if n.size(0) != c.size(0):
@@ -451,7 +535,50 @@ class TwoTowerTrainTask(nn.Module):
             raise ValueError(f"batch['pair_weight'] is on {t.device}, the batch on {ref.device}")
         return t
 
-    def _forward_negatives(self, notice_input, company_input, neg, B, lq, ent):
+    def _cells_ok(self):
+        """may a batch carry 'masked_cells'?  (the sharded task overrides it)"""
+        return True
+
+    def _batch_cells(self, batch, B, ent, pw):
+        """(cells int32 [L, 2], count int32 [1] or None) from batch["masked_cells"] (pairs that are never negatives: rows (a, j), a < B,
+        j < B + M) and the optional batch["masked_cells_count"] (a device count of the rows in use, for static buffers), or None when
+        the batch carries none.  Refuses what the masked loss does not cover -- never ignores the entry."""
+        t = batch.get("masked_cells")
+        if t is None:
+            return None
+        if not self._cells_ok():
+            raise NotImplementedError(f"masked cells (a batch with 'masked_cells') are not supported by {type(self).__name__}")
+        if ent is not None:
+            raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'entity': cells built from the pair table "
+                             "already hold every repeat")
+        if pw is not None:
+            raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'pair_weight'")
+        if self._dense_loss:
+            raise ValueError("masked cells (a batch with 'masked_cells') are not supported by the dense loss path "
+                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
+        if self.score_dtype != "bf16":
+            raise ValueError(f"masked cells (a batch with 'masked_cells') are not supported for score_dtype={self.score_dtype!r}")
+        ref = batch["notice"]["dense"]
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2:
+            raise ValueError(f"batch['masked_cells'] must be an int32 tensor of shape [L, 2], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
+        if t.device != ref.device:
+            raise ValueError(f"batch['masked_cells'] is on {t.device}, the batch on {ref.device}")
+        n = batch.get("masked_cells_count")
+        if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.numel() == 1 and n.device == ref.device):
+            raise ValueError(f"batch['masked_cells_count'] must be an int32 tensor of one element on {ref.device}")
+        return t, n
+
+    def _score_ce_cells(self, n, c, inv_t, first_call, log_q, cells):
+        """_score_ce with masked cells (no extras): the towers' packed operand images where they emitted them"""
+        lqs = log_q if log_q is not None else (None, None)
+        pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
+        if pn is None or pc is None or pc[1] != 1.0:
+            pn, pc = (None, None), (None, None)
+        return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], None, None, None, None,
+                                None, None, cells[0], cells[1])
+
+    def _forward_negatives(self, notice_input, company_input, neg, B, lq, ent, cells=None):
         """(notice embeddings, company embeddings, loss, out8) of a batch with shared extra negatives: the M rows ride behind the batch's
         companies through ONE company-tower pass (in train mode its BatchNorm batch statistics run over the B + M rows), the output is
         split into C and X, and the score node takes X as M more columns of every notice's row-direction softmax"""
@@ -462,7 +589,7 @@ class TwoTowerTrainTask(nn.Module):
         lqs, ents = lq if lq is not None else (None, None), ent if ent is not None else (None, None)
         loss, out8, _ = _ScoreCEFn.apply(n_emb, c_emb, 1.0 / float(self.temperature), self.score_dtype, not hasattr(self, "_pair_check_done"),
                                          False, None, None, None, lqs[0], lqs[1], ents[0], ents[1], None, x_emb, neg.get("log_q"),
-                                         neg.get("entity"))
+                                         neg.get("entity"), *(cells if cells is not None else (None, None)))
         return n_emb, c_emb, loss, out8
 
     def _negatives_ok(self):

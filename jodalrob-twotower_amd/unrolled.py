@@ -32,6 +32,7 @@ class UnrolledTrainStep(GraphedTrainStep):
     _entity_ok = False             # the repeated-entity mask likewise
     _pair_weight_ok = False        # pair weights likewise
     _negatives_ok = False          # extra negatives likewise
+    _cells_ok = False              # masked cells likewise
 
     def __init__(self, task, optimizer, example_batch: Dict, unroll: int = 2, **kw):
         if int(unroll) < 2:

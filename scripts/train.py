@@ -109,6 +109,11 @@ def main():
     ap.add_argument("--mask-repeats", action="store_true",
                     help="mask the in-batch negatives that repeat a row's notice or company (the repeated-entity mask): the train loader "
                          "attaches each pair's notice / company index (evaluation stays unmasked); combines with --logq-correction")
+    ap.add_argument("--mask-known", action="store_true",
+                    help="mask every known (notice, company) pair of the TRAIN pair table out of the in-batch softmax: an in-batch company or "
+                         "an extra that is a known bidder of a row's notice is no negative of that row (the train loader attaches the cells; "
+                         "evaluation stays unmasked); needs --fast (bf16 score kernels); combines with --logq-correction, --extra-negatives and "
+                         "--mine-negatives, holds every repeat --mask-repeats would mask and is an error with it or with --pair-weight")
     ap.add_argument("--pair-weight", choices=["inv-notice-count"], default=None,
                     help="per-pair sample weights of the in-batch softmax: inv-notice-count = 1 / (pairs of the row's notice), every notice "
                          "counts once; attached to the train loader only; combines with --mask-repeats and --logq-correction")
@@ -131,6 +136,10 @@ def main():
     ap.add_argument("--hard-fraction", type=float, default=1.0, metavar="F", help="share of the M extras drawn from the mined rows")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
     a = ap.parse_args()
+    if a.mask_known and (a.mask_repeats or a.pair_weight):
+        ap.error("--mask-known does not combine with --mask-repeats (its cells hold every repeat) or --pair-weight")
+    if a.mask_known and not a.fast:
+        ap.error("--mask-known needs --fast: masked cells run on the bf16 score kernels only (the f32 parity path has no cells form)")
     if a.mine_negatives < 0:
         ap.error("--mine-negatives must be >= 0")
     if not a.extra_negatives and (a.mine_negatives or a.hard_fraction != 1.0):
@@ -177,6 +186,8 @@ def main():
                                 log_sampling_probs(tp[:, 1], len(train_loader.company))))
     if a.extra_negatives:
         train_loader.set_extra_negatives(a.extra_negatives)
+    if a.mask_known:
+        train_loader.set_mask_known(True)
     train_task = create_two_tower_train_task(schema.notice.categorical, schema.company.categorical, metadata_path=str(meta),
                                              categorical_embedding_dim=config["categorical_embedding_dim"],
                                              notice_dense_input_dim=config["notice_dense_input_dim"],
@@ -214,10 +225,12 @@ def main():
         example = next(iter(train_loader))               # shapes only: the capture's warm-up steps leave no trace (preserve_state)
         train_loader._gen.set_state(state)
         train_loader._neg_gen.set_state(neg_state)
-        graphed = GraphedTrainStep(train_task, optimizer, example, warmup=1, accumulate_metrics=True)
+        # masked cells: room for twice the example epoch's fullest batch (a fuller one goes through the eager step: step_batches)
+        cap = {"cell_capacity": max(1024, 2 * train_loader.max_cells)} if a.mask_known else {}
+        graphed = GraphedTrainStep(train_task, optimizer, example, warmup=1, accumulate_metrics=True, **cap)
         rag = train_loader.ragged_example()              # the epoch's last, smaller batch gets a captured step of its own size:
         if rag is not None and rag["notice"]["dense"].shape[0] >= 2:       # launched eagerly it costs six full steps of host time
-            ragged = GraphedTrainStep(train_task, optimizer, rag, warmup=1, accumulate_metrics=True)
+            ragged = GraphedTrainStep(train_task, optimizer, rag, warmup=1, accumulate_metrics=True, **cap)
     if a.fast:                                           # one-off: capture the evaluation pass too (outside the epoch clock, like the step's capture)
         evaluator._fast_eval(train_task, test_loader)
     log = _AsyncLog(device) if a.fast else None
