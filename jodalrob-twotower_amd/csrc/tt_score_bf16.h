@@ -80,6 +80,9 @@ __device__ __forceinline__ f32x16 mfma_f8(const i32x8& a, const i32x8& b, const 
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, kFp8ScaleE8M0, 0, kFp8ScaleE8M0);
 }
 
+// the operand images of a score entry: bf16, split bf16 [hi | lo], or fp8 (e4m3) for the S products
+enum class Operands { bf16, bf16x3, fp8 };
+
 struct PackedView {
   const __bf16* rows;
   const __bf16* frag;

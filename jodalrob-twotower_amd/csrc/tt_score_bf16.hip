@@ -1074,8 +1074,6 @@ static int fwd_bf16(tt_ctx* ctx, const tt_score_fwd_dir* dirs, int32_t n_dirs, i
 }
 
 // ---- backward: the launch arguments of every form, then one launch per form --------------------------------------------
-enum class Operands { bf16, bf16x3, fp8 };
-
 struct BwdSetup {
   BwdArgs a;
   int64_t maxRa;
@@ -1134,26 +1132,23 @@ static int bwd_setup(BwdSetup& s, Operands op, tt_ctx* ctx, const tt_score_bwd_d
   return TT_OK;
 }
 
-// b-split form (score_bwd_bf16_kernel)
-template <int KS, int AT, int NW, bool X3>
+// b-split form (score_bwd_bf16_kernel): X3 split-bf16 operands, MK the repeated-entity mask, PW pair weights
+template <int KS, int AT, int NW, bool X3, bool MK = false, bool PW = false>
 static void launch_bsplit(const BwdSetup& s, hipStream_t st) {
   const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
-  tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, X3, l><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
+  tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, X3, l, MK, PW><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
 }
 
-// its masked instantiations (tt_score_bwd_bf16_mask)
-template <int KS, int AT, int NW>
-static void launch_bsplit_mk(const BwdSetup& s, hipStream_t st) {
-  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
-  tt_dispatch([&](auto u, auto l) { score_bwd_bf16_kernel<KS, AT, NW, u, false, l, true><<<grid, NW * 64, 0, st>>>(s.a); }, s.unit, s.lq);
-}
-
-// its pair-weight instantiations (tt_score_bwd_bf16_pw), with and without the mask
-template <int KS, int AT, int NW>
-static void launch_bsplit_pw(const BwdSetup& s, hipStream_t st) {
-  const dim3 grid((unsigned)tt_cdiv(s.maxRa, 32 * AT), (unsigned)s.n_dirs);
-  tt_dispatch([&](auto u, auto l, auto m) { score_bwd_bf16_kernel<KS, AT, NW, u, false, l, m, true><<<grid, NW * 64, 0, st>>>(s.a); },
-              s.unit, s.lq, s.a.ent_n != nullptr);
+// (KS, AT) per padded D = 32, 64, 128, 256 of the forms that run one wave per SIMD (NW = 4): two a tiles per workgroup at D <= 64 --
+// half the workgroups, half the L2 bytes of the streamed b images.  f(tt_c<KS>, tt_c<AT>).
+template <class F>
+static void one_wave_tile(int Dp, F&& f) {
+  switch (Dp) {
+    case 32: f(tt_c<2>, tt_c<2>); break;
+    case 64: f(tt_c<4>, tt_c<2>); break;
+    case 128: f(tt_c<8>, tt_c<1>); break;
+    default: f(tt_c<16>, tt_c<1>); break;
+  }
 }
 
 // one streamed image, transposing LDS reads (score_bwd_tr_kernel)
@@ -1248,71 +1243,86 @@ static int bwd_bf16(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_bw
   return TT_OK;
 }
 
-// tt_score_bwd_bf16_mask: the square problem with the repeated-entity mask (lq NULL: uncorrected).
-// One form for every shape, the b-split kernel: it takes any B and D <= 256 and the ids ride with its streamed tiles.  Masked
-// instantiations of the transposing and the workgroup-staged forms: not built (profiles/NOTES.md, "repeated-entity mask").  One wave
-// per SIMD, two a tiles per workgroup at D <= 64, as the bf16x3 launches -- the b ids of two tiles in flight are 64 registers.
-// Never queued for the towers' backward launch: a queued score backward goes in front of it.
-static int bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* ent_n, const int32_t* ent_c, const tt_score_bwd_lq* lq,
-                         int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss, float scale, tt_stream stream,
-                         const char* who) {
-  TT_CHECK_ARG(ent_n && ent_c && tt_aligned(ent_n, 16) && tt_aligned(ent_c, 16), "%s: ent_n / ent_c NULL or not 16-byte aligned", who);
-  BwdSetup s;
-  if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
-  for (int i = 0; i < n_dirs; ++i)
-    if (dirs[i].Ra != dirs[i].Rb || dirs[i].diag_offset != 0 || dirs[i].Ra != dirs[0].Ra) {
-      tt_set_error("%s: the repeated-entity mask covers the square problem only (Ra == Rb, diag_offset == 0)", who);
-      return TT_ERR_UNSUPPORTED;
-    }
-  s.a.ent_n = ent_n;
-  s.a.ent_c = ent_c;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
-  switch (padded_d(D)) {
-    case 32: launch_bsplit_mk<2, 2, 4>(s, st); break;
-    case 64: launch_bsplit_mk<4, 2, 4>(s, st); break;
-    case 128: launch_bsplit_mk<8, 1, 4>(s, st); break;
-    default: launch_bsplit_mk<16, 1, 4>(s, st); break;
-  }
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+// the optional terms of the square backward entries (tt_score_bwd_bf16_mask / _pw / _cells); `term` names the entry's own in messages
+struct SquareTerms {
+  const char* term;
+  const int32_t *ent_n, *ent_c;          // the repeated-entity mask (both or neither)
+  const float* g;                        // pair weights (with them, the weighted forward's folded reciprocals are required)
+  const int32_t* plan;                   // masked cells, with the extras' share behind them:
+  int64_t capacity, M;
+  const void* X_packed;
+  const float *inv_row, *w_x;
+  float* dX;
+};
+
+static XnegArgs xneg_args(const PackedView& vn, const PackedView& vx, int64_t B, int64_t M, const float* inv_row, const float* w_x,
+                          const int32_t* ent_c, const int32_t* ent_x, float* dN, float* dX, int32_t D, float inv_t, float shift,
+                          const float* d_loss, float scale, float ab) {
+  XnegArgs a{};
+  a.d[0] = XnegDir{vn.rows, vx.rows, vx.frag, (int)B, (int)M, inv_row, w_x, ent_c, ent_x, dN, scale, 1};          // B image = X: unscaled
+  a.d[1] = XnegDir{vx.rows, vn.rows, vn.frag, (int)M, (int)B, w_x, inv_row, ent_x, ent_c, dX, scale / ab, 0};     // B image = the notices'
+  a.c1 = inv_t * kLog2e / ab;
+  a.c2 = -shift * kLog2e;
+  a.d_loss = d_loss;
+  a.D = D;
+  return a;
 }
 
-// tt_score_bwd_bf16_pw: the square problem with per-pair sample weights; ent_n / ent_c NULL: unmasked, lq NULL: uncorrected.
-// As the masked entry: the b-split kernel for every shape, on the masked launches' tiles (one wave per SIMD) with or without ids,
-// never queued for the towers' backward launch.  The reciprocals must be the weighted forward's: without them the kernel would form
-// unweighted ones from the sums.
-static int bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g, const int32_t* ent_n, const int32_t* ent_c,
-                       const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss, float scale,
-                       tt_stream stream, const char* who) {
-  TT_CHECK_ARG(g, "%s: NULL g", who);
-  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "%s: ent_n and ent_c go together", who);
-  TT_CHECK_ARG(!ent_n || (tt_aligned(ent_n, 16) && tt_aligned(ent_c, 16)), "%s: ent_n / ent_c not 16-byte aligned", who);
+// tt_score_bwd_bf16_mask / _pw / _cells: the square problem with the repeated-entity mask, per-pair sample weights or masked cells (lq
+// NULL: uncorrected).  One form for every shape, the b-split kernel: it takes any B and D <= 256 and the ids ride with its streamed
+// tiles.  Masked instantiations of the transposing and the workgroup-staged forms: not built (profiles/NOTES.md, "repeated-entity
+// mask").  One wave per SIMD, as the bf16x3 launches -- the b ids of two tiles in flight are 64 registers.  Never queued for the
+// towers' backward launch: a queued score backward goes in front of it.  Pair weights: the reciprocals must be the weighted forward's
+// -- without them the kernel would form unweighted ones from the sums.  Cells: the kernels, their tiles and their launches are
+// tt_score_cells.hip's, with X_packed the extras' two rectangular directions behind the square ones, all on one plan.
+static int bwd_square_terms(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const SquareTerms& t, const tt_score_bwd_lq* lq, int32_t n_dirs,
+                            int32_t D, float inv_t, float shift, const float* d_loss, float scale, tt_stream stream, const char* who) {
+  TT_CHECK_ARG((t.ent_n != nullptr) == (t.ent_c != nullptr), "%s: ent_n and ent_c go together", who);
+  TT_CHECK_ARG(!t.ent_n || (tt_aligned(t.ent_n, 16) && tt_aligned(t.ent_c, 16)), "%s: ent_n / ent_c not 16-byte aligned", who);
   BwdSetup s;
   if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
   for (int i = 0; i < n_dirs; ++i) {
     if (dirs[i].Ra != dirs[i].Rb || dirs[i].diag_offset != 0 || dirs[i].Ra != dirs[0].Ra) {
-      tt_set_error("%s: pair weights cover the square problem only (Ra == Rb, diag_offset == 0)", who);
+      tt_set_error("%s: %s the square problem only (Ra == Rb, diag_offset == 0)", who, t.term);
       return TT_ERR_UNSUPPORTED;
     }
-    TT_CHECK_ARG(dirs[i].inv_a && dirs[i].inv_b, "%s: direction %d: inv_a / inv_b (the weighted forward's folded reciprocals) are required", who, i);
+    TT_CHECK_ARG(!t.g || (dirs[i].inv_a && dirs[i].inv_b), "%s: direction %d: inv_a / inv_b (the weighted forward's folded reciprocals) are required",
+                 who, i);
   }
-  s.a.ent_n = ent_n;
-  s.a.ent_c = ent_c;
-  s.a.pw_g = g;
+  s.a.ent_n = t.ent_n;
+  s.a.ent_c = t.ent_c;
+  s.a.pw_g = t.g;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
-  switch (padded_d(D)) {
-    case 32: launch_bsplit_pw<2, 2, 4>(s, st); break;
-    case 64: launch_bsplit_pw<4, 2, 4>(s, st); break;
-    case 128: launch_bsplit_pw<8, 1, 4>(s, st); break;
-    default: launch_bsplit_pw<16, 1, 4>(s, st); break;
+  if (!t.plan) {
+    if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
+    const int Dp = padded_d(D);
+    if (t.g) tt_dispatch([&](auto m) { one_wave_tile(Dp, [&](auto ks, auto at) { launch_bsplit<ks, at, 4, false, m, true>(s, st); }); }, t.ent_n != nullptr);
+    else one_wave_tile(Dp, [&](auto ks, auto at) { launch_bsplit<ks, at, 4, false, true>(s, st); });
+    TT_LAUNCH_CHECK();
+    return TT_OK;
   }
-  TT_LAUNCH_CHECK();
-  return TT_OK;
+  const int64_t B = dirs[0].Ra, M = t.M;
+  TT_CHECK_ARG(dirs[0].dA != dirs[1].dA && dirs[0].A_packed == dirs[1].B_packed && dirs[1].A_packed == dirs[0].B_packed,
+               "%s: the directions must be (N, C) and (C, N)", who);
+  if (t.X_packed) {
+    TT_CHECK_ARG(M >= 1 && M < ((int64_t)1 << 30) && t.inv_row && t.w_x && t.dX, "%s: the extras need M >= 1, inv_row, w_x and dX", who);
+    TT_CHECK_ARG(tt_aligned(t.inv_row, 16) && tt_aligned(t.w_x, 16), "%s: inv_row / w_x must be 16-byte aligned", who);
+  } else {
+    TT_CHECK_ARG(M == 0, "%s: M = %lld without X_packed", who, (long long)M);
+  }
+  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
+  // the KP instantiations live in tt_score_cells.hip (tt_score_bwd_bsplit.h): the launch arguments go over as bytes, as a queued
+  // score backward's do (both translation units build BwdArgs / XnegArgs from the same header)
+  static_assert(std::is_trivially_copyable<BwdArgs>::value && std::is_trivially_copyable<XnegArgs>::value, "the arguments travel as bytes");
+  if (int rc = tt_score_bwd_cells_square(&s.a, sizeof(s.a), s.maxRa, s.unit, s.lq, D, t.plan, t.capacity, B, M, st)) return rc;
+  if (!t.X_packed) return TT_OK;
+  const float ab = dirs[0].ab_scale == 0.f ? 1.f : dirs[0].ab_scale;
+  const XnegArgs a = xneg_args(view(dirs[0].A_packed, B, D), view(t.X_packed, M, D), B, M, t.inv_row, t.w_x, nullptr, nullptr, dirs[0].dA,
+                               t.dX, D, inv_t, shift, d_loss, scale, ab);
+  return tt_score_bwd_cells_xneg(&a, sizeof(a), s.unit, D, t.plan, t.capacity, B, M, st);
 }
 
-// tt_score_bwd_bf16_xneg: one launch of score_bwd_xneg_kernel over (N, X) -> dN += and (X, N) -> dX, on the masked launches' tiles.
+// tt_score_bwd_bf16_xneg: one launch of score_bwd_xneg_kernel over (N, X) -> dN += and (X, N) -> dX, on the one-wave-per-SIMD tiles.
 // Never queued for the towers' backward launch; a queued score backward goes in front of it (it stores the dN this launch adds to).
 static int bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed, int64_t B, int64_t M, int32_t D, float inv_t, float shift,
                          float ab_scale, const float* inv_row, const float* w_x, const int32_t* ent_c, const int32_t* ent_x,
@@ -1328,73 +1338,18 @@ static int bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed
     return TT_ERR_UNSUPPORTED;
   }
   const float ab = ab_scale == 0.f ? 1.f : ab_scale;
-  const PackedView vn = view(N_packed, B, D), vx = view(X_packed, M, D);
-  XnegArgs a{};
-  a.d[0] = XnegDir{vn.rows, vx.rows, vx.frag, (int)B, (int)M, inv_row, w_x, ent_c, ent_x, dN, scale, 1};          // B image = X: unscaled
-  a.d[1] = XnegDir{vx.rows, vn.rows, vn.frag, (int)M, (int)B, w_x, inv_row, ent_x, ent_c, dX, scale / ab, 0};     // B image = the notices'
-  a.c1 = inv_t * kLog2e / ab;
-  a.c2 = -shift * kLog2e;
-  a.d_loss = d_loss;
-  a.D = D;
+  const XnegArgs a = xneg_args(view(N_packed, B, D), view(X_packed, M, D), B, M, inv_row, w_x, ent_c, ent_x, dN, dX, D, inv_t, shift, d_loss,
+                               scale, ab);
   const bool unit = ab == inv_t * kLog2e;
   const int64_t maxRa = B > M ? B : M;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
-  const auto go = [&](auto ks, auto at) {
+  one_wave_tile(padded_d(D), [&](auto ks, auto at) {
     const dim3 grid((unsigned)tt_cdiv(maxRa, 32 * at), 2);
     tt_dispatch([&](auto u, auto m) { score_bwd_xneg_kernel<ks, at, 4, u, m><<<grid, 4 * 64, 0, st>>>(a); }, unit, ent_c != nullptr);
-  };
-  switch (padded_d(D)) {
-    case 32: go(tt_c<2>, tt_c<2>); break;
-    case 64: go(tt_c<4>, tt_c<2>); break;
-    case 128: go(tt_c<8>, tt_c<1>); break;
-    default: go(tt_c<16>, tt_c<1>); break;
-  }
+  });
   TT_LAUNCH_CHECK();
   return TT_OK;
-}
-
-// tt_score_bwd_bf16_cells: the square problem with masked cells (lq NULL: uncorrected) and, with X_packed, the extras' two rectangular
-// directions behind it, all on one plan.  As the masked entry: the b-split kernel at every shape, never queued for the towers' backward
-// launch.  The arguments are checked and built here; the kernels, their tiles and their launches are tt_score_cells.hip's.
-static int bwd_bf16_cells(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* plan, int64_t capacity, const tt_score_bwd_lq* lq, const void* X_packed,
-                          int64_t M, const float* inv_row, const float* w_x, float* dX, int32_t D, float inv_t, float shift,
-                          const float* d_loss, float scale, tt_stream stream, const char* who) {
-  TT_CHECK_ARG(plan && tt_aligned(plan, 16), "%s: plan NULL or not 16-byte aligned", who);
-  TT_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 30), "%s: bad capacity %lld", who, (long long)capacity);
-  BwdSetup s;
-  if (int rc = bwd_setup(s, Operands::bf16, ctx, dirs, lq, 2, D, inv_t, shift, d_loss, scale, who)) return rc;
-  for (int i = 0; i < 2; ++i)
-    if (dirs[i].Ra != dirs[i].Rb || dirs[i].diag_offset != 0 || dirs[i].Ra != dirs[0].Ra) {
-      tt_set_error("%s: masked cells cover the square problem only (Ra == Rb, diag_offset == 0)", who);
-      return TT_ERR_UNSUPPORTED;
-    }
-  const int64_t B = dirs[0].Ra;
-  TT_CHECK_ARG(dirs[0].dA != dirs[1].dA && dirs[0].A_packed == dirs[1].B_packed && dirs[1].A_packed == dirs[0].B_packed,
-               "%s: the directions must be (N, C) and (C, N)", who);
-  if (X_packed) {
-    TT_CHECK_ARG(M >= 1 && M < ((int64_t)1 << 30) && inv_row && w_x && dX, "%s: the extras need M >= 1, inv_row, w_x and dX", who);
-    TT_CHECK_ARG(tt_aligned(inv_row, 16) && tt_aligned(w_x, 16), "%s: inv_row / w_x must be 16-byte aligned", who);
-  } else {
-    TT_CHECK_ARG(M == 0, "%s: M = %lld without X_packed", who, (long long)M);
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = tt_deferred_flush(ctx, TT_DQ_SCORE_BWD)) return rc;
-  // the KP instantiations live in tt_score_cells.hip (tt_score_bwd_bsplit.h): the launch arguments go over as bytes, as a queued
-  // score backward's do (both translation units build BwdArgs / XnegArgs from the same header)
-  static_assert(std::is_trivially_copyable<BwdArgs>::value && std::is_trivially_copyable<XnegArgs>::value, "the arguments travel as bytes");
-  if (int rc = tt_score_bwd_cells_square(&s.a, sizeof(s.a), s.maxRa, s.unit, s.lq, D, plan, capacity, B, M, st)) return rc;
-  if (!X_packed) return TT_OK;
-  const float ab = dirs[0].ab_scale == 0.f ? 1.f : dirs[0].ab_scale;
-  const PackedView vn = view(dirs[0].A_packed, B, D), vx = view(X_packed, M, D);
-  XnegArgs a{};
-  a.d[0] = XnegDir{vn.rows, vx.rows, vx.frag, (int)B, (int)M, inv_row, w_x, nullptr, nullptr, dirs[0].dA, scale, 1};
-  a.d[1] = XnegDir{vx.rows, vn.rows, vn.frag, (int)M, (int)B, w_x, inv_row, nullptr, nullptr, dX, scale / ab, 0};
-  a.c1 = inv_t * kLog2e / ab;
-  a.c2 = -shift * kLog2e;
-  a.d_loss = d_loss;
-  a.D = D;
-  return tt_score_bwd_cells_xneg(&a, sizeof(a), s.unit, D, plan, capacity, B, M, st);
 }
 
 // tt_score_bwd_bf16x3 and, with lq != NULL, tt_score_bwd_bf16x3_lq.
@@ -1407,13 +1362,7 @@ static int bwd_bf16x3(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_score_
   BwdSetup s;
   if (int rc = bwd_setup(s, Operands::bf16x3, ctx, dirs, lq, n_dirs, D, inv_t, shift, d_loss, scale, who)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // two a tiles per workgroup at D <= 64: half the workgroups, half the L2 bytes of the streamed b images
-  switch (padded_d(D)) {
-    case 32: launch_bsplit<2, 2, 4, true>(s, st); break;
-    case 64: launch_bsplit<4, 2, 4, true>(s, st); break;
-    case 128: launch_bsplit<8, 1, 4, true>(s, st); break;
-    default: launch_bsplit<16, 1, 4, true>(s, st); break;
-  }
+  one_wave_tile(padded_d(D), [&](auto ks, auto at) { launch_bsplit<ks, at, 4, true>(s, st); });
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -1441,13 +1390,19 @@ int tt_score_bwd_bf16_lq(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const tt_sco
 int tt_score_bwd_bf16_mask(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* ent_n, const int32_t* ent_c,
                            const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
                            float scale, tt_stream stream) {
-  return bwd_bf16_mask(ctx, dirs, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_mask");
+  TT_CHECK_ARG(ent_n && ent_c, "tt_score_bwd_bf16_mask: ent_n / ent_c NULL or not 16-byte aligned");
+  SquareTerms t{"the repeated-entity mask covers"};
+  t.ent_n = ent_n; t.ent_c = ent_c;
+  return bwd_square_terms(ctx, dirs, t, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_mask");
 }
 
 int tt_score_bwd_bf16_pw(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const float* g, const int32_t* ent_n, const int32_t* ent_c,
                          const tt_score_bwd_lq* lq, int32_t n_dirs, int32_t D, float inv_t, float shift, const float* d_loss,
                          float scale, tt_stream stream) {
-  return bwd_bf16_pw(ctx, dirs, g, ent_n, ent_c, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_pw");
+  TT_CHECK_ARG(g, "tt_score_bwd_bf16_pw: NULL g");
+  SquareTerms t{"pair weights cover"};
+  t.g = g; t.ent_n = ent_n; t.ent_c = ent_c;
+  return bwd_square_terms(ctx, dirs, t, lq, n_dirs, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_pw");
 }
 
 int tt_score_bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_packed, int64_t B, int64_t M, int32_t D, float inv_t,
@@ -1460,7 +1415,11 @@ int tt_score_bwd_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* X_pack
 int tt_score_bwd_bf16_cells(tt_ctx* ctx, const tt_score_bwd_dir* dirs, const int32_t* plan, int64_t capacity, const tt_score_bwd_lq* lq,
                             const void* X_packed, int64_t M, const float* inv_row, const float* w_x, float* dX, int32_t D, float inv_t, float shift,
                             const float* d_loss, float scale, tt_stream stream) {
-  return bwd_bf16_cells(ctx, dirs, plan, capacity, lq, X_packed, M, inv_row, w_x, dX, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_cells");
+  TT_CHECK_ARG(plan && tt_aligned(plan, 16), "tt_score_bwd_bf16_cells: plan NULL or not 16-byte aligned");
+  TT_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 30), "tt_score_bwd_bf16_cells: bad capacity %lld", (long long)capacity);
+  SquareTerms t{"masked cells cover"};
+  t.plan = plan; t.capacity = capacity; t.M = M; t.X_packed = X_packed; t.inv_row = inv_row; t.w_x = w_x; t.dX = dX;
+  return bwd_square_terms(ctx, dirs, t, lq, 2, D, inv_t, shift, d_loss, scale, stream, "tt_score_bwd_bf16_cells");
 }
 
 int tt_score_bwd_fp8(tt_ctx* ctx, const tt_score_bwd_dir* dirs, int32_t n_dirs, int32_t D, float inv_t, float shift,

@@ -746,19 +746,86 @@ inline SymLayout sym_layout(const tt_ctx* ctx, int64_t R, int D, int64_t Rx = 0)
 
 }  // namespace
 
-static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
-                       float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col, float* diag,
-                       int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream,
-                       bool fp8, const char* who, bool x3 = false, const float* lq_n = nullptr, const float* lq_c = nullptr,
-                       float* w_n = nullptr, float* w_c = nullptr, const int32_t* ent_n = nullptr, const int32_t* ent_c = nullptr,
-                       const float* pw_g = nullptr, const void* X_packed = nullptr, int64_t M = 0, const float* lq_x = nullptr,
-                       const int32_t* ent_x = nullptr, float* w_x = nullptr, const int32_t* plan = nullptr, int64_t cell_capacity = 0) {
-  const bool lq = lq_n != nullptr;                         // the *_lq entries pass all four (checked there)
-  const bool mk = ent_n != nullptr;                        // tt_score_fwd_sym_bf16_mask passes both (checked there)
-  const bool xn = X_packed != nullptr;                     // tt_score_fwd_sym_bf16_xneg (M, w_x checked there)
-  const bool kp = plan != nullptr;                         // tt_score_fwd_sym_bf16_cells (never with ent_*)
-  TT_CHECK_ARG(ctx && N_packed && C_packed && rowsum && colsum && inv_row && inv_col && diag && out8 && workspace, "%s: NULL argument", who);
-  TT_CHECK_ARG(!want_rank || row_rank, "%s: want_rank needs row_rank", who);
+// one call of the symmetric forward: what every entry requires, the operand kind, and the optional terms grouped as they travel
+struct SymCall {
+  const char* who;
+  Operands op;
+  const void *N_packed, *C_packed;
+  int64_t B;
+  int32_t D;
+  float inv_t, shift, ab_scale;
+  int32_t want_rank;
+  float *rowsum, *colsum, *inv_row, *inv_col, *diag;
+  int32_t* row_rank;
+  float *out8, *loss_out;
+  void* workspace;
+  size_t workspace_bytes;
+  tt_stream stream;
+  struct { const float *lq_n, *lq_c; float *w_n, *w_c; } lq;        // logQ: the log sampling probabilities in, the sampling weights out
+  struct { const int32_t *ent_n, *ent_c; } ids;                      // the repeated-entity mask
+  const float* pw_g;                                                 // pair weights (tt_score_prepare_pw's g)
+  struct { const void* X_packed; int64_t M; const float* lq_x; const int32_t* ent_x; float* w_x; } x;   // shared extra negatives
+  struct { const int32_t* plan; int64_t capacity; } cells;           // masked cells
+};
+
+// the required part of a SymCall `s` from an entry's own parameters (every entry names them alike)
+#define TT_SYM_CALL(s, who_, op_)                                                                                                  \
+  SymCall s{};                                                                                                                     \
+  s.who = who_; s.op = op_; s.N_packed = N_packed; s.C_packed = C_packed; s.B = B; s.D = D; s.inv_t = inv_t; s.shift = shift;      \
+  s.ab_scale = ab_scale; s.want_rank = want_rank; s.rowsum = rowsum; s.colsum = colsum; s.inv_row = inv_row; s.inv_col = inv_col;  \
+  s.diag = diag; s.row_rank = row_rank; s.out8 = out8; s.loss_out = loss_out; s.workspace = workspace;                             \
+  s.workspace_bytes = workspace_bytes; s.stream = stream
+
+// the terms an entry is for (sym_check_terms: those it requires; the fields of the others stay NULL / 0 in its SymCall)
+enum : unsigned { kTermLq = 1, kTermIds = 2, kTermPw = 4, kTermXneg = 8, kTermCells = 16 };
+
+// every pairing and range rule of the optional terms, once
+static int sym_check_terms(const SymCall& s, unsigned needs) {
+  const auto& q = s.lq;
+  const auto& x = s.x;
+  const bool m_ok = x.M >= 1 && x.M < ((int64_t)1 << 30);
+  TT_CHECK_ARG(!(needs & kTermLq) || (q.lq_n && q.lq_c && q.w_n && q.w_c), "%s: NULL argument", s.who);
+  TT_CHECK_ARG(!(needs & kTermIds) || (s.ids.ent_n && s.ids.ent_c), "%s: NULL ent_n / ent_c", s.who);
+  TT_CHECK_ARG(!(needs & kTermPw) || s.pw_g, "%s: NULL g", s.who);
+  TT_CHECK_ARG(!(needs & kTermXneg) || (x.X_packed && x.w_x), "%s: NULL X_packed / w_x", s.who);
+  TT_CHECK_ARG(!(needs & kTermCells) || (s.cells.plan && tt_aligned(s.cells.plan, 16)), "%s: plan NULL or not 16-byte aligned", s.who);
+  TT_CHECK_ARG(!(needs & kTermCells) || (s.cells.capacity >= 1 && s.cells.capacity < ((int64_t)1 << 30)), "%s: bad capacity %lld", s.who,
+               (long long)s.cells.capacity);
+  TT_CHECK_ARG(x.X_packed ? (m_ok && x.w_x) : x.M == 0, "%s: bad M=%lld (extras need M >= 1 and w_x)", s.who, (long long)x.M);
+  TT_CHECK_ARG((s.ids.ent_n != nullptr) == (s.ids.ent_c != nullptr), "%s: ent_n and ent_c go together", s.who);
+  TT_CHECK_ARG(!x.ent_x || s.ids.ent_c, "%s: ent_x needs ent_n / ent_c", s.who);
+  TT_CHECK_ARG((q.lq_n != nullptr) == (q.lq_c != nullptr), "%s: lq_n and lq_c go together", s.who);
+  TT_CHECK_ARG(!x.lq_x || (q.lq_n && x.X_packed), "%s: lq_x needs lq_n / lq_c and the extras", s.who);
+  TT_CHECK_ARG(!q.lq_n || (q.w_n && q.w_c), "%s: the logQ correction needs w_n / w_c", s.who);
+  return TT_OK;
+}
+
+// padded D = 32, 64, 128, 256 -> f(tt_c<KS>), KS = D / 16 k-steps
+template <class F>
+static int sym_by_dp(int Dp, F&& f) {
+  switch (Dp) {
+    case 32: return f(tt_c<2>);
+    case 64: return f(tt_c<4>);
+    case 128: return f(tt_c<8>);
+    default: return f(tt_c<16>);
+  }
+}
+
+static int sym_forward(tt_ctx* ctx, const SymCall& s, unsigned needs = 0) {
+  if (int rc = sym_check_terms(s, needs)) return rc;
+  const char* who = s.who;
+  const void *N_packed = s.N_packed, *C_packed = s.C_packed, *X_packed = s.x.X_packed;
+  const int64_t B = s.B, M = s.x.M;
+  const int32_t D = s.D;
+  const float inv_t = s.inv_t, shift = s.shift;
+  const bool fp8 = s.op == Operands::fp8, x3 = s.op == Operands::bf16x3;
+  const bool lq = s.lq.lq_n != nullptr;                    // with lq_c, w_n and w_c (sym_check_terms); without, no weights are written
+  const bool mk = s.ids.ent_n != nullptr;
+  const bool xn = X_packed != nullptr;
+  const bool kp = s.cells.plan != nullptr;                 // (never with ent_*: tt_score_fwd_sym_bf16_cells takes none)
+  TT_CHECK_ARG(ctx && N_packed && C_packed && s.rowsum && s.colsum && s.inv_row && s.inv_col && s.diag && s.out8 && s.workspace,
+               "%s: NULL argument", who);
+  TT_CHECK_ARG(!s.want_rank || s.row_rank, "%s: want_rank needs row_rank", who);
   TT_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 30) && D >= 1 && D <= 256, "%s: bad shape B=%lld D=%d", who, (long long)B, D);
   if (2.f * fabsf(inv_t) > 80.f) {
     tt_set_error("%s: 1/temperature = %g: fixed-shift softmax needs 2/T <= 80", who, inv_t);
@@ -772,12 +839,12 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   sized.num_cus = 256;                                     // the layout must not depend on the device: it sizes the workspace
   SymLayout L = sym_layout(&sized, B, D, M);
   if (fp8) L.Dp = padded_d8(D);                            // (the part record is sized for 256 columns: sym_layout)
-  if (workspace_bytes < L.bytes) {
-    tt_set_error("%s: workspace %zu < required %zu", who, workspace_bytes, L.bytes);
+  if (s.workspace_bytes < L.bytes) {
+    tt_set_error("%s: workspace %zu < required %zu", who, s.workspace_bytes, L.bytes);
     return TT_ERR_WORKSPACE;
   }
-  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-  const float ab = ab_scale == 0.f ? 1.f : ab_scale;
+  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(s.workspace) + 255) & ~uintptr_t(255));
+  const float ab = s.ab_scale == 0.f ? 1.f : s.ab_scale;
   const bool unit = ab == inv_t * kLog2e;                  // exactly: the caller got the scale from tt_score_unit_scale(inv_t)
   SymArgsKP g{};                                           // (the kernels without cells take its SymArgs part)
   g.a_rows = fp8 ? static_cast<const void*>(view8(N_packed, B, D).rows8) : static_cast<const void*>(view(N_packed, B, D).rows);
@@ -794,18 +861,18 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   g.ma = reinterpret_cast<float*>(ws + L.off_ma);
   g.cs = reinterpret_cast<float*>(ws + L.off_cs);
   g.diag_raw = reinterpret_cast<float*>(ws + L.off_diag);
-  g.want_rank = want_rank ? 1 : 0;
-  g.lq_n = lq_n;
-  g.lq_c = lq_c;
-  g.ent_n = ent_n;
-  g.ent_c = ent_c;
+  g.want_rank = s.want_rank ? 1 : 0;
+  g.lq_n = s.lq.lq_n;
+  g.lq_c = s.lq.lq_c;
+  g.ent_n = s.ids.ent_n;
+  g.ent_c = s.ids.ent_c;
   if (xn) {
     g.x_rows = view(X_packed, M, D).rows;
     g.Rx = (int)M; g.nTx = L.nTx; g.ngi = L.n_groups;
-    g.lq_x = lq_x; g.ent_x = ent_x;
+    g.lq_x = s.x.lq_x; g.ent_x = s.x.ent_x;
   }
-  if (kp) g.kp = tt_cells_view(plan, B, M, cell_capacity);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (kp) g.kp = tt_cells_view(s.cells.plan, B, M, s.cells.capacity);
+  hipStream_t st = reinterpret_cast<hipStream_t>(s.stream);
   // fp8, D = 256: two company tiles per wave (half the workgroups along J, half the slab rows)
   const int jt = (fp8 && L.Dp == 256) ? 2 : 1;
   const int n_groups = (int)tt_cdiv(L.nT, kSymWaves * jt) + L.n_groups_x;     // (extras: bf16 operands, jt = 1)
@@ -824,48 +891,22 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
     }, unit);
   };
   const std::false_type no{};
+  const std::true_type yes{};
+  // the legal flag sets: cells take LQ and XN, the extras LQ and MK, the mask LQ, fp8 nothing, plain bf16 X3 and LQ
   int rc;
-  if (kp) {                                                // masked cells: LQ off / on, XN off / on, never MK
-    rc = tt_dispatch([&](auto lqc, auto xnc) {
-      switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, no, xnc, std::true_type{});
-        case 64: return go(tt_c<4>, no, no, lqc, no, xnc, std::true_type{});
-        case 128: return go(tt_c<8>, no, no, lqc, no, xnc, std::true_type{});
-        default: return go(tt_c<16>, no, no, lqc, no, xnc, std::true_type{});
-      }
-    }, lq, xn);
+  if (kp) {
+    rc = tt_dispatch([&](auto lqc, auto xnc) { return sym_by_dp(L.Dp, [&](auto ks) { return go(ks, no, no, lqc, no, xnc, yes); }); }, lq, xn);
   } else if (xn) {
-    const std::true_type yes{};
-    rc = tt_dispatch([&](auto lqc, auto mkc) {
-      switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, mkc, yes, no);
-        case 64: return go(tt_c<4>, no, no, lqc, mkc, yes, no);
-        case 128: return go(tt_c<8>, no, no, lqc, mkc, yes, no);
-        default: return go(tt_c<16>, no, no, lqc, mkc, yes, no);
-      }
-    }, lq, mk);
+    rc = tt_dispatch([&](auto lqc, auto mkc) { return sym_by_dp(L.Dp, [&](auto ks) { return go(ks, no, no, lqc, mkc, yes, no); }); }, lq, mk);
   } else if (mk) {
-    const std::true_type yes{};
-    rc = tt_dispatch([&](auto lqc) {
-      switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, no, lqc, yes, no, no);
-        case 64: return go(tt_c<4>, no, no, lqc, yes, no, no);
-        case 128: return go(tt_c<8>, no, no, lqc, yes, no, no);
-        default: return go(tt_c<16>, no, no, lqc, yes, no, no);
-      }
-    }, lq);
+    rc = tt_dispatch([&](auto lqc) { return sym_by_dp(L.Dp, [&](auto ks) { return go(ks, no, no, lqc, yes, no, no); }); }, lq);
   } else if (fp8) {
-    const std::true_type yes{};
-    rc = L.Dp == 64 ? go(tt_c<4>, yes, no, no, no, no, no) : (L.Dp == 128 ? go(tt_c<8>, yes, no, no, no, no, no) : go(tt_c<16>, yes, no, no, no, no, no));
+    rc = sym_by_dp(L.Dp, [&](auto ks) -> int {
+      if constexpr (ks == 2) return TT_ERR_INVALID_ARG;      // (never: padded_d8 >= 64 -- fp8 has no K = 32 form to instantiate)
+      else return go(ks, yes, no, no, no, no, no);
+    });
   } else {
-    rc = tt_dispatch([&](auto x3c, auto lqc) {
-      switch (L.Dp) {
-        case 32: return go(tt_c<2>, no, x3c, lqc, no, no, no);
-        case 64: return go(tt_c<4>, no, x3c, lqc, no, no, no);
-        case 128: return go(tt_c<8>, no, x3c, lqc, no, no, no);
-        default: return go(tt_c<16>, no, x3c, lqc, no, no, no);
-      }
-    }, x3, lq);
+    rc = tt_dispatch([&](auto x3c, auto lqc) { return sym_by_dp(L.Dp, [&](auto ks) { return go(ks, no, x3c, lqc, no, no, no); }); }, x3, lq);
   }
   if (rc) return rc;
   TT_LAUNCH_CHECK();
@@ -873,20 +914,20 @@ static int sym_forward(tt_ctx* ctx, const void* N_packed, const void* C_packed, 
   f.rs = g.rs; f.mb = g.mb; f.ma = g.ma; f.cs = g.cs; f.diag_raw = g.diag_raw;
   f.n_groups = n_groups; f.n_chunks = L.n_chunks; f.R = (int)B; f.KS = L.Dp / 16; f.Rp = L.Rp;
   f.kexp = exp2f(g.c2); f.unscale = inv_t / ab; f.shift = shift; f.unit = unit ? 1 : 0; f.want_rank = g.want_rank;
-  f.rowsum = rowsum; f.colsum = colsum; f.inv_row = inv_row; f.inv_col = inv_col; f.diag = diag; f.row_rank = row_rank;
+  f.rowsum = s.rowsum; f.colsum = s.colsum; f.inv_row = s.inv_row; f.inv_col = s.inv_col; f.diag = s.diag; f.row_rank = s.row_rank;
   f.a_rows = g.a_rows; f.b_rows = g.b_rows;
   f.fp8 = fp8 ? 1 : 0;
   f.a_lo = g.a_lo; f.b_lo = g.b_lo;
   f.part = reinterpret_cast<float*>(ws + L.off_part);
-  f.lq_n = lq_n; f.lq_c = lq_c; f.w_n = w_n; f.w_c = w_c;
-  f.pw_g = pw_g;
-  f.lq_x = lq_x; f.w_x = w_x; f.Rx = (int)M;
+  f.lq_n = s.lq.lq_n; f.lq_c = s.lq.lq_c; f.w_n = lq ? s.lq.w_n : nullptr; f.w_c = lq ? s.lq.w_c : nullptr;
+  f.pw_g = s.pw_g;
+  f.lq_x = s.x.lq_x; f.w_x = s.x.w_x; f.Rx = (int)M;
   if (xn) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, false, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
-  else if (pw_g) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
+  else if (s.pw_g) tt_dispatch([&](auto lqc) { score_sym_finish1_kernel<lqc, true><<<(unsigned)L.n_wg, 256, 0, st>>>(f); }, lq);
   else if (lq) score_sym_finish1_kernel<true><<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   else score_sym_finish1_kernel<<<(unsigned)L.n_wg, 256, 0, st>>>(f);
   TT_LAUNCH_CHECK();
-  Finish2Rider fr{f.part, L.n_wg, L.Dp, (float)B, f.unscale, out8, loss_out};
+  Finish2Rider fr{f.part, L.n_wg, L.Dp, (float)B, f.unscale, s.out8, s.loss_out};
   if (L.n_wg >= 256) {                                   // large batches: fold the records 32 to one before the one-workgroup reduction
     float* part2 = reinterpret_cast<float*>(ws + L.off_part2);
     const int n2 = (int)tt_cdiv(L.n_wg, kFin2Fold);
@@ -914,42 +955,42 @@ int tt_score_fwd_sym_bf16(tt_ctx* ctx, const void* N_packed, const void* C_packe
                           float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col,
                           float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
                           tt_stream stream) {
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16");
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16", Operands::bf16);
+  return sym_forward(ctx, s);
 }
 
 int tt_score_fwd_sym_fp8(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
                          float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col,
                          float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
                          tt_stream stream) {
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, true, "tt_score_fwd_sym_fp8");
+  TT_SYM_CALL(s, "tt_score_fwd_sym_fp8", Operands::fp8);
+  return sym_forward(ctx, s);
 }
 
 int tt_score_fwd_sym_bf16x3(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
                             float ab_scale, int32_t want_rank, float* rowsum, float* colsum, float* inv_row, float* inv_col,
                             float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
                             tt_stream stream) {
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3", true);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16x3", Operands::bf16x3);
+  return sym_forward(ctx, s);
 }
 
 int tt_score_fwd_sym_bf16_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t, float shift,
                              float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c, float* rowsum, float* colsum,
                              float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8,
                              float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
-  TT_CHECK_ARG(lq_n && lq_c && w_n && w_c, "tt_score_fwd_sym_bf16_lq: NULL argument");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_lq", false, lq_n, lq_c, w_n, w_c);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16_lq", Operands::bf16);
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermLq);
 }
 
 int tt_score_fwd_sym_bf16x3_lq(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
                                float shift, float ab_scale, int32_t want_rank, const float* lq_n, const float* lq_c, float* rowsum,
                                float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* diag, int32_t* row_rank,
                                float* out8, float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
-  TT_CHECK_ARG(lq_n && lq_c && w_n && w_c, "tt_score_fwd_sym_bf16x3_lq: NULL argument");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16x3_lq", true, lq_n, lq_c, w_n, w_c);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16x3_lq", Operands::bf16x3);
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermLq);
 }
 
 int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_packed, int64_t B, int32_t D, float inv_t,
@@ -957,12 +998,10 @@ int tt_score_fwd_sym_bf16_mask(tt_ctx* ctx, const void* N_packed, const void* C_
                                const float* lq_n, const float* lq_c, float* rowsum, float* colsum, float* inv_row, float* inv_col,
                                float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
                                size_t workspace_bytes, tt_stream stream) {
-  TT_CHECK_ARG(ent_n && ent_c, "tt_score_fwd_sym_bf16_mask: NULL ent_n / ent_c");
-  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_mask: lq_n and lq_c go together");
-  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_mask: the logQ correction needs w_n / w_c");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_mask", false, lq_n, lq_c,
-                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16_mask", Operands::bf16);
+  s.ids = {ent_n, ent_c};
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermIds);
 }
 
 size_t tt_score_fwd_sym_xneg_workspace_bytes(int64_t B, int64_t M, int32_t D) {
@@ -978,16 +1017,11 @@ int tt_score_fwd_sym_bf16_xneg(tt_ctx* ctx, const void* N_packed, const void* C_
                                float* rowsum, float* colsum, float* inv_row, float* inv_col, float* w_n, float* w_c, float* w_x,
                                float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace, size_t workspace_bytes,
                                tt_stream stream) {
-  TT_CHECK_ARG(X_packed && w_x, "tt_score_fwd_sym_bf16_xneg: NULL X_packed / w_x");
-  TT_CHECK_ARG(M >= 1 && M < ((int64_t)1 << 30), "tt_score_fwd_sym_bf16_xneg: bad M=%lld", (long long)M);
-  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "tt_score_fwd_sym_bf16_xneg: ent_n and ent_c go together");
-  TT_CHECK_ARG(!ent_x || ent_c, "tt_score_fwd_sym_bf16_xneg: ent_x needs ent_n / ent_c");
-  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_xneg: lq_n and lq_c go together");
-  TT_CHECK_ARG(!lq_x || lq_n, "tt_score_fwd_sym_bf16_xneg: lq_x needs lq_n / lq_c");
-  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_xneg: the logQ correction needs w_n / w_c");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_xneg", false, lq_n, lq_c,
-                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c, nullptr, X_packed, M, lq_x, ent_x, w_x);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16_xneg", Operands::bf16);
+  s.x = {X_packed, M, lq_x, ent_x, w_x};
+  s.ids = {ent_n, ent_c};
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermXneg);
 }
 
 int tt_score_prepare_pw(tt_ctx* ctx, const float* w, int64_t B, float* g_out, tt_stream stream) {
@@ -1003,13 +1037,11 @@ int tt_score_fwd_sym_bf16_pw(tt_ctx* ctx, const void* N_packed, const void* C_pa
                              const float* lq_n, const float* lq_c, float* rowsum, float* colsum, float* inv_row, float* inv_col,
                              float* w_n, float* w_c, float* diag, int32_t* row_rank, float* out8, float* loss_out, void* workspace,
                              size_t workspace_bytes, tt_stream stream) {
-  TT_CHECK_ARG(g, "tt_score_fwd_sym_bf16_pw: NULL g");
-  TT_CHECK_ARG((ent_n != nullptr) == (ent_c != nullptr), "tt_score_fwd_sym_bf16_pw: ent_n and ent_c go together");
-  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_pw: lq_n and lq_c go together");
-  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_pw: the logQ correction needs w_n / w_c");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_pw", false, lq_n, lq_c,
-                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, ent_n, ent_c, g);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16_pw", Operands::bf16);
+  s.pw_g = g;
+  s.ids = {ent_n, ent_c};
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermPw);
 }
 
 int tt_score_fwd_sym_bf16_cells(tt_ctx* ctx, const void* N_packed, const void* C_packed, const void* X_packed, int64_t B, int64_t M,
@@ -1017,16 +1049,11 @@ int tt_score_fwd_sym_bf16_cells(tt_ctx* ctx, const void* N_packed, const void* C
                                 int64_t capacity, const float* lq_n, const float* lq_c, const float* lq_x, float* rowsum, float* colsum, float* inv_row,
                                 float* inv_col, float* w_n, float* w_c, float* w_x, float* diag, int32_t* row_rank, float* out8,
                                 float* loss_out, void* workspace, size_t workspace_bytes, tt_stream stream) {
-  TT_CHECK_ARG(plan && tt_aligned(plan, 16), "tt_score_fwd_sym_bf16_cells: plan NULL or not 16-byte aligned");
-  TT_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 30), "tt_score_fwd_sym_bf16_cells: bad capacity %lld", (long long)capacity);
-  TT_CHECK_ARG(X_packed ? (M >= 1 && M < ((int64_t)1 << 30) && w_x) : M == 0, "tt_score_fwd_sym_bf16_cells: bad M=%lld (extras need M >= 1 and w_x)",
-               (long long)M);
-  TT_CHECK_ARG((lq_n != nullptr) == (lq_c != nullptr), "tt_score_fwd_sym_bf16_cells: lq_n and lq_c go together");
-  TT_CHECK_ARG(!lq_x || (lq_n && X_packed), "tt_score_fwd_sym_bf16_cells: lq_x needs lq_n / lq_c and the extras");
-  TT_CHECK_ARG(!lq_n || (w_n && w_c), "tt_score_fwd_sym_bf16_cells: the logQ correction needs w_n / w_c");
-  return sym_forward(ctx, N_packed, C_packed, B, D, inv_t, shift, ab_scale, want_rank, rowsum, colsum, inv_row, inv_col, diag, row_rank,
-                     out8, loss_out, workspace, workspace_bytes, stream, false, "tt_score_fwd_sym_bf16_cells", false, lq_n, lq_c,
-                     lq_n ? w_n : nullptr, lq_n ? w_c : nullptr, nullptr, nullptr, nullptr, X_packed, M, lq_x, nullptr, w_x, plan, capacity);
+  TT_SYM_CALL(s, "tt_score_fwd_sym_bf16_cells", Operands::bf16);
+  s.cells = {plan, capacity};
+  s.x = {X_packed, M, lq_x, nullptr, w_x};
+  s.lq = {lq_n, lq_c, w_n, w_c};
+  return sym_forward(ctx, s, kTermCells);
 }
 
 }  // extern "C"

@@ -553,7 +553,7 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
     def _cells_ok(self):
         return False                                   # masked cells (a batch with 'masked_cells'): not by the sharded task
 
-    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None):
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None, cells=None):
         if pair_weight is not None:
             raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")
         if log_q is not None:

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -707,112 +707,198 @@ def score_pack2_fp8(X0, X1, scale0: float = 1.0, scale1: float = 1.0):
     return b0, b1
 
 
-def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False,
-             lq_n=None, lq_c=None, ent=None, pw=None):
-    """The symmetric forward of every form (score_fwd_sym, score_fwd_sym_lq, score_fwd_sym_mask, score_fwd_sym_pw): returns (rowsum,
-    colsum, diag, row_rank, (inv_row, inv_col), out8, loss, w), w = (w_n, w_c) the sampling weights of the logQ-corrected form (lq_n /
-    lq_c given, tt_score_fwd_sym_bf16_lq / _bf16x3_lq), else None.  ent: (ent_n, ent_c) from score_mask_ids -- the repeated-entity mask
-    (tt_score_fwd_sym_bf16_mask, bf16 operands only).  pw: score_pair_weights' g -- the weighted loss and FOLDED reciprocals g / sum
-    (tt_score_fwd_sym_bf16_pw, bf16 operands only; ent / lq optional)."""
+class ScoreTerms(NamedTuple):
+    """The optional terms of the in-batch softmax as the score entries take them; None: the term is absent."""
+    lq: Optional[tuple] = None        # (lq_n, lq_c) f32 [B]: logQ sampling-bias correction
+    ent: Optional[tuple] = None       # score_mask_ids' (ent_n, ent_c): the repeated-entity mask
+    pw: Optional[torch.Tensor] = None   # score_pair_weights' g: per-pair sample weights
+    extras: Optional[tuple] = None    # (Xp, M, lq_x, ent_x): shared extra negatives -- score_pack_bf16(X), lq_x f32 [M] / score_xneg_ids or None
+    plan: Optional[torch.Tensor] = None   # score_cells_plan's plan: masked cells
+
+
+class SymOut(NamedTuple):
+    """What the symmetric forward leaves: inv = (inv_row, inv_col); w = (w_n, w_c) with logQ, w_x [round_up(M, 64)] with extras, else None."""
+    rowsum: torch.Tensor
+    colsum: torch.Tensor
+    diag: torch.Tensor
+    row_rank: torch.Tensor
+    inv: tuple
+    w: Optional[tuple]
+    w_x: Optional[torch.Tensor]
+    out8: torch.Tensor
+    loss: torch.Tensor
+
+
+_NO_TERMS = ScoreTerms()
+_SYM_ENTRY = {"bf16": "tt_score_fwd_sym_bf16", "bf16x3": "tt_score_fwd_sym_bf16x3", "fp8": "tt_score_fwd_sym_fp8"}
+_BWD_ENTRY = {"bf16": "tt_score_bwd_bf16", "bf16x3": "tt_score_bwd_bf16x3", "fp8": "tt_score_bwd_fp8"}
+
+
+def _operands(fp8, x3):
+    return "fp8" if fp8 else ("bf16x3" if x3 else "bf16")
+
+
+def _sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, operands, terms: ScoreTerms) -> SymOut:
+    """The symmetric forward of every form (the tt_score_fwd_sym_* entries): operands 'bf16', 'bf16x3' or 'fp8', the packing of Np / Cp."""
     dev = Np.device
-    if pw is not None and (fp8 or x3):
+    other = operands != "bf16"
+    if terms.pw is not None and other:
         raise ValueError("the weighted symmetric forward takes bf16 operands only")
-    if lq_n is not None and fp8:
+    if terms.lq is not None and operands == "fp8":
         raise ValueError("the logQ-corrected symmetric forward has no fp8 form")
-    if ent is not None and (fp8 or x3):
+    if terms.ent is not None and other:
         raise ValueError("the masked symmetric forward takes bf16 operands only")
-    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
-    Bp = (B + 63) // 64 * 64                                           # the kernel fills the entries past B (read by tt_score_bwd_bf16)
+    lq = _lq_pair(*(terms.lq or (None, None)), B, B, dev, ("lq_n", "lq_c"))
+    Xp, M, lq_x, ent_x = terms.extras or (None, 0, None, None)
+    ent, pw, plan = terms.ent, terms.pw, terms.plan
+    if plan is not None:
+        if (Xp is None) != (M == 0):
+            raise ValueError("masked cells: the extras' image Xp and M >= 1 go together")
+        if lq_x is not None and (not lq or Xp is None):
+            raise ValueError("masked cells: lq_x needs lq_n / lq_c and the extras")
+    elif terms.extras is not None:
+        _xneg_check(B, M, ent, ent_x, lq, lq_x)
+    if lq and (plan is not None or terms.extras is not None):
+        _lq_check_t(inv_t)
+    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
+    Bp, Mp = (B + 63) // 64 * 64, (M + 63) // 64 * 64            # the kernel fills the entries past B (read by tt_score_bwd_bf16)
     f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
+    w_x = torch.empty(Mp, dtype=torch.float32, device=dev) if M else None
     rank = torch.empty(B, dtype=torch.int32, device=dev)
     out8 = torch.empty(8, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     lib = L.load()
+    nbytes = lib.tt_score_fwd_sym_xneg_workspace_bytes(B, M, D) if M else lib.tt_score_fwd_sym_workspace_bytes(B, D)
     if L.riders_deferred(dev, 2):    # the last reduction runs later (inside the towers' backward launch): its partial records must
-        ws = torch.empty(lib.tt_score_fwd_sym_workspace_bytes(B, D), dtype=torch.uint8, device=dev)     # outlive the shared scratch's next user
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)         # outlive the shared scratch's next user
         out8._tt_keep = ws
     else:
-        ws = L.workspace(dev, lib.tt_score_fwd_sym_workspace_bytes(B, D))
-    name = ("tt_score_fwd_sym_fp8" if fp8 else ("tt_score_fwd_sym_bf16x3" if x3 else "tt_score_fwd_sym_bf16")) + ("_lq" if lq else "")
-    w_out = (L.ptr(f[5]), L.ptr(f[6])) if lq else ()
-    if pw is not None:
-        name, pre, w_out = "tt_score_fwd_sym_bf16_pw", _pw_args(pw, ent, lq, 2), w_out or (None, None)
+        ws = L.workspace(dev, nbytes)
+    # the entry of the terms present and its argument order: (name, operands' head, terms before the sums, weights behind them)
+    lqp = tuple(map(L.ptr, lq)) or (None, None)
+    entp = (L.ptr(ent[0]), L.ptr(ent[1])) if ent is not None else (None, None)
+    wp = (L.ptr(f[5]), L.ptr(f[6])) if lq else (None, None)
+    head = (L.ptr(Np), L.ptr(Cp), B, D) if Xp is None and plan is None else (L.ptr(Np), L.ptr(Cp), L.ptr(Xp), B, M, D)
+    if plan is not None:
+        name, pre, wout = "tt_score_fwd_sym_bf16_cells", (L.ptr(plan), int(plan._tt_cap), *lqp, L.ptr(lqx)), wp + (L.ptr(w_x),)
+    elif terms.extras is not None:
+        name, pre, wout = "tt_score_fwd_sym_bf16_xneg", (*entp, L.ptr(ent_x), *lqp, L.ptr(lqx)), wp + (L.ptr(w_x),)
+    elif pw is not None:
+        name, pre, wout = "tt_score_fwd_sym_bf16_pw", (L.ptr(pw), *entp, *lqp), wp
     elif ent is not None:
-        name, pre, w_out = "tt_score_fwd_sym_bf16_mask", _mask_args(ent, lq, 2), w_out or (None, None)
+        name, pre, wout = "tt_score_fwd_sym_bf16_mask", (*entp, *lqp), wp
     else:
-        pre = tuple(map(L.ptr, lq))
+        name, pre, wout = _SYM_ENTRY[operands] + ("_lq" if lq else ""), (lqp if lq else ()), (wp if lq else ())
     with _timed(name):
-        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), B, D, inv_t, shift, scale_n, int(want_rank), *pre,
-                                   L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]), *w_out, L.ptr(f[2]), L.ptr(rank), L.ptr(out8),
-                                   L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
-    w = (f[5][:B], f[6][:B]) if lq else None
-    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), out8, loss, w
+        L.check(getattr(lib, name)(L.ctx(dev), *head, inv_t, shift, scale_n, int(want_rank), *pre, L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]),
+                                   L.ptr(f[4]), *wout, L.ptr(f[2]), L.ptr(rank), L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(),
+                                   L.stream(dev)), name)
+    return SymOut(f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), (f[5][:B], f[6][:B]) if lq else None, w_x, out8, loss)
+
+
+def _lq_terms(lq_n, lq_c):
+    return None if lq_n is None else (lq_n, lq_c)
+
+
+def _sym8(o: SymOut):
+    """the documented tuple of score_fwd_sym_lq / _mask / _pw"""
+    return o.rowsum, o.colsum, o.diag, o.row_rank, o.inv, o.w, o.out8, o.loss
+
+
+def _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False,
+             lq_n=None, lq_c=None, ent=None, pw=None):
+    """_sym_fwd by flags: (rowsum, colsum, diag, row_rank, (inv_row, inv_col), out8, loss, w)"""
+    o = _sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, _operands(fp8, x3), ScoreTerms(_lq_terms(lq_n, lq_c), ent, pw))
+    return o.rowsum, o.colsum, o.diag, o.row_rank, o.inv, o.out8, o.loss, o.w
 
 
 def score_fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n: float = 1.0, want_rank: bool = True, fp8: bool = False, x3: bool = False):
     """Single-pass symmetric forward of the square problem (tt_score_fwd_sym_bf16 / _fp8 / _bf16x3): returns (rowsum, colsum, diag,
     row_rank, (inv_row, inv_col), out8, loss) -- loss its own 0-dim tensor so that autograd sees a plain output."""
-    return _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, fp8, x3)[:7]
+    o = _sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, _operands(fp8, x3), _NO_TERMS)
+    return o.rowsum, o.colsum, o.diag, o.row_rank, o.inv, o.out8, o.loss
 
 
 def score_fwd_sym_lq(Np, Cp, B, D, inv_t, shift, lq_n, lq_c, scale_n: float = 1.0, want_rank: bool = True, x3: bool = False):
     """logQ-corrected score_fwd_sym (tt_score_fwd_sym_bf16_lq / _bf16x3_lq): lq_n / lq_c f32 [B] log sampling probabilities of
     the batch's notices / companies.  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), (w_n, w_c), out8, loss):
     (w_n, w_c) are the sampling weights score_bwd_bf16(..., w=) takes."""
-    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, x3, lq_n, lq_c)
-    return r[:5] + (r[7],) + r[5:7]
+    return _sym8(_sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, _operands(False, x3), ScoreTerms(_lq_terms(lq_n, lq_c))))
 
 
 def score_fwd_sym_mask(Np, Cp, B, D, inv_t, shift, ent, lq_n=None, lq_c=None, scale_n: float = 1.0, want_rank: bool = True):
     """score_fwd_sym with the repeated-entity mask (tt_score_fwd_sym_bf16_mask): ent = score_mask_ids(ent_n, ent_c, B, dev); lq_n /
     lq_c optional (both or neither).  Returns (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, out8, loss), w = (w_n, w_c)
     with logQ, else None -- what score_bwd_bf16(..., w=, ent=) takes."""
-    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, False, lq_n, lq_c, ent)
-    return r[:5] + (r[7],) + r[5:7]
+    return _sym8(_sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, "bf16", ScoreTerms(_lq_terms(lq_n, lq_c), ent)))
 
 
 def score_fwd_sym_pw(Np, Cp, B, D, inv_t, shift, pw, ent=None, lq_n=None, lq_c=None, scale_n: float = 1.0, want_rank: bool = True):
     """score_fwd_sym with per-pair sample weights (tt_score_fwd_sym_bf16_pw): pw = score_pair_weights(w, B, dev); ent (from
     score_mask_ids) and lq_n / lq_c optional.  Returns as score_fwd_sym_mask; (inv_row, inv_col) are the folded g / rowsum, g / colsum
     that score_bwd_bf16(..., pw=) requires, rowsum / colsum the unweighted sums."""
-    r = _fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, False, False, lq_n, lq_c, ent, pw)
-    return r[:5] + (r[7],) + r[5:7]
+    return _sym8(_sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, "bf16", ScoreTerms(_lq_terms(lq_n, lq_c), ent, pw)))
+
+
+def _bwd_sym(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n, inv, operands, w, terms: ScoreTerms, w_x=None):
+    """The backward of every form on _sym_fwd's sums (the tt_score_bwd_* entries): (dN, dC, dX), dX None without extras.  w / w_x / inv:
+    that forward's.  Extras without a plan: the square backward, then their two rectangular directions (score_bwd_bf16_xneg)."""
+    dev = Np.device
+    other = operands != "bf16"
+    ent, pw, plan = terms.ent, terms.pw, terms.plan
+    Xp, M, _, ent_x = terms.extras or (None, 0, None, None)
+    if w is not None and operands == "fp8":
+        raise ValueError("the logQ-corrected backward has no fp8 form")
+    if ent is not None and other:
+        raise ValueError("the masked backward takes bf16 operands only")
+    if pw is not None and other:
+        raise ValueError("the weighted backward takes bf16 operands only")
+    if pw is not None and inv is None:
+        raise ValueError("the weighted backward needs inv, the weighted forward's folded reciprocals")
+    if plan is not None:
+        if (Xp is None) != (M == 0) or (Xp is None) != (w_x is None):
+            raise ValueError("masked cells: the extras' image Xp, M >= 1 and w_x go together")
+        if Xp is not None and inv is None:
+            raise ValueError("masked cells: the extras' backward needs inv, the forward's reciprocals")
+    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dX = None
+    arr = (L.ScoreBwdDir * 2)()
+    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
+    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)   # B = company: unscaled
+    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)  # B = notice image
+    lq = None
+    if w is not None:                                                  # (w_n / w_c are views of arrays padded to 64 rows, as the kernels read them)
+        lq = (L.ScoreBwdLq * 2)()
+        lq[0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))                 # direction (N, C): A = notices, B = companies
+        lq[1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
+    entp = (L.ptr(ent[0]), L.ptr(ent[1])) if ent is not None else (None, None)
+    tail = (D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev))
+    if plan is not None:
+        dX = torch.empty((M, D), dtype=torch.float32, device=dev) if M else None
+        name, args = "tt_score_bwd_bf16_cells", (L.ptr(plan), int(plan._tt_cap), lq, L.ptr(Xp), M, ir, L.ptr(w_x), L.ptr(dX))
+    elif pw is not None:                                               # (pw: score_pair_weights' g, with the weighted forward's inv)
+        name, args = "tt_score_bwd_bf16_pw", (L.ptr(pw), *entp, lq, 2)
+    elif ent is not None:                                              # (ent: score_mask_ids' padded arrays, with the masked forward's sums)
+        name, args = "tt_score_bwd_bf16_mask", (*entp, lq, 2)
+    else:
+        name, args = _BWD_ENTRY[operands] + ("_lq" if lq else ""), ((lq, 2) if lq else (2,))
+    with _timed(name):
+        L.check(getattr(L.load(), name)(L.ctx(dev), arr, *args, *tail), name)
+    if plan is None and terms.extras is not None:
+        dX = score_bwd_bf16_xneg(Np, Xp, B, M, D, inv_t, shift, inv[0], w_x, d_loss, scale, dN, scale_n,
+                                 ent_c=ent[1] if ent_x is not None else None, ent_x=ent_x)
+    return dN, dC, dX
 
 
 def score_bwd_bf16(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n: float = 1.0, inv=None, fp8: bool = False,
                    x3: bool = False, w=None, ent=None, pw=None):
     """inv: (inv_row, inv_col) from score_fwd_bf16(..., with_inv=True) with the same scale_n (optional).
     fp8: the operands are tt_score_pack2_fp8 buffers (tt_score_bwd_fp8); x3: score_pack2_bf16x3 buffers (tt_score_bwd_bf16x3).
-    w: (w_n, w_c) from score_fwd_sym_lq, with its rowsum / colsum / inv: the logQ-corrected backward
-    (tt_score_bwd_bf16_lq / _bf16x3_lq; w_n / w_c are views of arrays padded to 64 rows, as the kernels read them)."""
-    dev = Np.device
-    if w is not None and fp8:
-        raise ValueError("the logQ-corrected backward has no fp8 form")
-    if ent is not None and (fp8 or x3):
-        raise ValueError("the masked backward takes bf16 operands only")
-    if pw is not None and (fp8 or x3):
-        raise ValueError("the weighted backward takes bf16 operands only")
-    if pw is not None and inv is None:
-        raise ValueError("the weighted backward needs inv, the weighted forward's folded reciprocals")
-    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
-    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
-    arr = (L.ScoreBwdDir * 2)()
-    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
-    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)   # B = company: unscaled
-    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)  # B = notice image
-    lq = ()
-    if w is not None:
-        lq = ((L.ScoreBwdLq * 2)(),)
-        lq[0][0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))              # direction (N, C): A = notices, B = companies
-        lq[0][1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
-    name = ("tt_score_bwd_fp8" if fp8 else ("tt_score_bwd_bf16x3" if x3 else "tt_score_bwd_bf16")) + ("_lq" if lq else "")
-    if pw is not None:                                             # (pw: score_pair_weights' g, with the weighted forward's inv)
-        name, lq = "tt_score_bwd_bf16_pw", _pw_args(pw, ent, None, 0) + (lq[0] if lq else None,)
-    elif ent is not None:                                          # (ent: score_mask_ids' padded arrays, with the masked forward's sums)
-        name, lq = "tt_score_bwd_bf16_mask", (L.ptr(ent[0]), L.ptr(ent[1]), lq[0] if lq else None)
-    with _timed(name):
-        L.check(getattr(L.load(), name)(L.ctx(dev), arr, *lq, 2, D, inv_t, shift, L.ptr(d_loss), scale, L.stream(dev)), name)
-    return dN, dC
+    w: (w_n, w_c) from score_fwd_sym_lq, with its rowsum / colsum / inv: the logQ-corrected backward (tt_score_bwd_bf16_lq / _bf16x3_lq).
+    ent / pw: as score_fwd_sym_mask / _pw took them (tt_score_bwd_bf16_mask / _pw); pw requires inv."""
+    return _bwd_sym(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n, inv, _operands(fp8, x3), w,
+                    ScoreTerms(ent=ent, pw=pw))[:2]
 
 
 def score_bwd_bf16_lq(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, w, scale_n: float = 1.0, inv=None, x3: bool = False):
@@ -847,35 +933,8 @@ def score_fwd_sym_xneg(Np, Cp, Xp, B, M, D, inv_t, shift, ent=None, ent_x=None, 
     score_mask_ids(...) or None, ent_x = score_xneg_ids(...) or None (never masked), lq_x f32 [M] or None (log q = 0).  Returns
     (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, w_x, out8, loss): rowsum / inv_row include the extras, w = (w_n, w_c) with
     logQ else None, w_x [round_up(M, 64)] the extras' weights -- what score_bwd_bf16_xneg takes."""
-    dev = Np.device
-    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
-    _xneg_check(B, M, ent, ent_x, lq, lq_x)
-    if lq:
-        _lq_check_t(inv_t)
-    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
-    Bp, Mp = (B + 63) // 64 * 64, (M + 63) // 64 * 64
-    f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
-    w_x = torch.empty(Mp, dtype=torch.float32, device=dev)
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    out8 = torch.empty(8, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    lib = L.load()
-    nbytes = lib.tt_score_fwd_sym_xneg_workspace_bytes(B, M, D)
-    if L.riders_deferred(dev, 2):                                      # (as _fwd_sym: the partial records outlive the shared scratch)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        out8._tt_keep = ws
-    else:
-        ws = L.workspace(dev, nbytes)
-    e = (L.ptr(ent[0]), L.ptr(ent[1])) if ent is not None else (None, None)
-    name = "tt_score_fwd_sym_bf16_xneg"
-    with _timed(name):
-        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), L.ptr(Xp), B, M, D, inv_t, shift, scale_n, int(want_rank), *e,
-                                   L.ptr(ent_x) if ent_x is not None else None, *(map(L.ptr, lq) if lq else (None, None)),
-                                   L.ptr(lqx) if lqx is not None else None, L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]), L.ptr(f[4]),
-                                   *((L.ptr(f[5]), L.ptr(f[6])) if lq else (None, None)), L.ptr(w_x), L.ptr(f[2]), L.ptr(rank),
-                                   L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
-    w = (f[5][:B], f[6][:B]) if lq else None
-    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), w, w_x, out8, loss
+    return tuple(_sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, "bf16",
+                          ScoreTerms(_lq_terms(lq_n, lq_c), ent, extras=(Xp, M, lq_x, ent_x))))
 
 
 def score_bwd_bf16_xneg(Np, Xp, B, M, D, inv_t, shift, inv_row, w_x, d_loss, scale, dN, scale_n: float = 1.0, ent_c=None, ent_x=None):
@@ -990,64 +1049,16 @@ def score_fwd_sym_cells(Np, Cp, B, D, inv_t, shift, plan, Xp=None, M=0, lq_n=Non
     """score_fwd_sym (/_lq, /_xneg without ids) on the masked cells of `plan` = score_cells_plan(cells, B, M)
     (tt_score_fwd_sym_bf16_cells).  Returns as score_fwd_sym_xneg: (rowsum, colsum, diag, row_rank, (inv_row, inv_col), w, w_x, out8,
     loss), w_x None without extras."""
-    dev = Np.device
-    lq = _lq_pair(lq_n, lq_c, B, B, dev, ("lq_n", "lq_c"))
-    if (Xp is None) != (M == 0):
-        raise ValueError("masked cells: the extras' image Xp and M >= 1 go together")
-    if lq_x is not None and (not lq or Xp is None):
-        raise ValueError("masked cells: lq_x needs lq_n / lq_c and the extras")
-    if lq:
-        _lq_check_t(inv_t)
-    lqx = None if lq_x is None else _lq_vec(lq_x, M, dev, "lq_x")
-    Bp, Mp = (B + 63) // 64 * 64, (M + 63) // 64 * 64
-    f = torch.empty((7 if lq else 5, Bp), dtype=torch.float32, device=dev)    # rowsum, colsum, diag, 1/rowsum', 1/colsum'[, w_n, w_c]
-    w_x = torch.empty(Mp, dtype=torch.float32, device=dev) if M else None
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    out8 = torch.empty(8, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    lib = L.load()
-    nbytes = lib.tt_score_fwd_sym_xneg_workspace_bytes(B, M, D) if M else lib.tt_score_fwd_sym_workspace_bytes(B, D)
-    if L.riders_deferred(dev, 2):                                      # (as _fwd_sym: the partial records outlive the shared scratch)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        out8._tt_keep = ws
-    else:
-        ws = L.workspace(dev, nbytes)
-    name = "tt_score_fwd_sym_bf16_cells"
-    with _timed(name):
-        L.check(getattr(lib, name)(L.ctx(dev), L.ptr(Np), L.ptr(Cp), L.ptr(Xp), B, M, D, inv_t, shift, scale_n, int(want_rank), L.ptr(plan),
-                                   int(plan._tt_cap), *(map(L.ptr, lq) if lq else (None, None)), L.ptr(lqx), L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[3]),
-                                   L.ptr(f[4]), *((L.ptr(f[5]), L.ptr(f[6])) if lq else (None, None)), L.ptr(w_x), L.ptr(f[2]), L.ptr(rank),
-                                   L.ptr(out8), L.ptr(loss), L.ptr(ws), ws.numel(), L.stream(dev)), name)
-    w = (f[5][:B], f[6][:B]) if lq else None
-    return f[0][:B], f[1][:B], f[2][:B], rank, (f[3][:B], f[4][:B]), w, w_x, out8, loss
+    return tuple(_sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, want_rank, "bf16",
+                          ScoreTerms(_lq_terms(lq_n, lq_c), extras=(Xp, M, lq_x, None), plan=plan)))
 
 
 def score_bwd_bf16_cells(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, plan, scale_n: float = 1.0, inv=None, w=None,
                          Xp=None, M=0, w_x=None):
     """The backward on score_fwd_sym_cells' sums (tt_score_bwd_bf16_cells): returns (dN, dC, dX), dX None without extras.  inv / w: that
     forward's (views of its padded arrays); with extras (Xp, M, w_x) inv is required -- its inv_row is the extras' row factor."""
-    dev = Np.device
-    if (Xp is None) != (M == 0) or (Xp is None) != (w_x is None):
-        raise ValueError("masked cells: the extras' image Xp, M >= 1 and w_x go together")
-    if Xp is not None and inv is None:
-        raise ValueError("masked cells: the extras' backward needs inv, the forward's reciprocals")
-    dN = torch.empty((B, D), dtype=torch.float32, device=dev)
-    dC = torch.empty((B, D), dtype=torch.float32, device=dev)
-    dX = torch.empty((M, D), dtype=torch.float32, device=dev) if M else None
-    arr = (L.ScoreBwdDir * 2)()
-    ir, ic = (L.ptr(inv[0]), L.ptr(inv[1])) if inv is not None else (None, None)
-    arr[0] = L.ScoreBwdDir(L.ptr(Np), L.ptr(Cp), B, B, 0, L.ptr(rowsum), L.ptr(colsum), L.ptr(dN), scale_n, 1.0, ir, ic)
-    arr[1] = L.ScoreBwdDir(L.ptr(Cp), L.ptr(Np), B, B, 0, L.ptr(colsum), L.ptr(rowsum), L.ptr(dC), scale_n, scale_n, ic, ir)
-    lq = None
-    if w is not None:
-        lq = (L.ScoreBwdLq * 2)()
-        lq[0] = L.ScoreBwdLq(L.ptr(w[0]), L.ptr(w[1]))
-        lq[1] = L.ScoreBwdLq(L.ptr(w[1]), L.ptr(w[0]))
-    name = "tt_score_bwd_bf16_cells"
-    with _timed(name):
-        L.check(getattr(L.load(), name)(L.ctx(dev), arr, L.ptr(plan), int(plan._tt_cap), lq, L.ptr(Xp), M, ir, L.ptr(w_x), L.ptr(dX), D, inv_t, shift,
-                                        L.ptr(d_loss), scale, L.stream(dev)), name)
-    return dN, dC, dX
+    return _bwd_sym(Np, Cp, B, D, inv_t, shift, rowsum, colsum, d_loss, scale, scale_n, inv, "bf16", w,
+                    ScoreTerms(extras=(Xp, M, None, None), plan=plan), w_x)
 
 
 def score_dir_fwd_lq(A, Bm, inv_t, shift, lq_b, diag_offset=0, want_sumscore=True):

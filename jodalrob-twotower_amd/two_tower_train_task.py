@@ -10,7 +10,7 @@ tt_score_dir_bwd recomputes the tiles for the gradients.  `similarity_matrix` is
 """
 from __future__ import annotations
 
-from typing import Dict, Union
+from typing import Dict, NamedTuple, Optional, Union
 
 import torch
 from ._lib import no_dynamo as _no_dynamo
@@ -74,38 +74,31 @@ class _ScoreCEFn(torch.autograd.Function):
                 lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None, x=None, lq_x=None, ent_x=None, cells=None, cell_count=None):
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
-        shift = abs(inv_t)                                   # unit rows: |s| <= 1/T
+        dev, shift = n.device, abs(inv_t)                    # unit rows: |s| <= 1/T
         lq = lq_n is not None
         fp8, x3 = score_dtype == "fp8", score_dtype == "bf16x3"
-        ctx.kp = None
-        if cells is not None:
-            if ent_n is not None or ent_c is not None or ent_x is not None:
-                raise ValueError("masked cells do not combine with the repeated-entity mask (cells built from the pair table hold every repeat)")
-            return _ScoreCEFn._forward_cells(ctx, n, c, inv_t, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c, pair_w, x,
-                                             lq_x, cells, cell_count)
-        if x is not None:
-            return _ScoreCEFn._forward_xneg(ctx, n, c, inv_t, score_dtype, want_col_rank, lq_n, lq_c, ent_n, ent_c, pair_w, x, lq_x, ent_x)
-        ctx.xn = None
-        ent = None
-        if ent_n is not None or ent_c is not None:
-            if fp8 or x3:
-                raise ValueError(f"the repeated-entity mask has no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
-            if c.shape != n.shape:
-                raise ValueError("the repeated-entity mask needs as many notice rows as company rows")
-            ent = ops.score_mask_ids(ent_n, ent_c, B, n.device)
-        pw = None
-        if pair_w is not None:
-            if fp8 or x3:
-                raise ValueError(f"pair weights have no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
-            if c.shape != n.shape:
-                raise ValueError("pair weights need as many notice rows as company rows")
-            pw = ops.score_pair_weights(pair_w, B, n.device)
+        present = frozenset(k for k, v in (("lq", lq_n), ("ent", ent_n), ("ent", ent_c), ("ent_c", ent_c), ("pw", pair_w), ("extras", x),
+                                           ("cells", cells), ("ent_x", ent_x), ("lq_x", lq_x)) if v is not None)
+        _score_terms_check(score_dtype, c.shape == n.shape, present)
         if lq:
-            if fp8:
-                raise ValueError("the logQ correction has no fp8 form")
             ops._lq_check_t(inv_t)
+        # the terms' arrays as the entries read them
+        M = 0
+        if x is not None:
+            if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1 or x.device != dev:
+                raise ValueError(f"the extra negatives must be a [M >= 1, {D}] tensor on {dev}")
+            x = x.contiguous().float()
+            M = x.shape[0]
+            if lq and lq_x is None:                          # a missing log_q on the extras counts as zeros
+                lq_x = torch.zeros(M, dtype=torch.float32, device=dev)
+            packed_n = packed_c = scale_n = None             # with extras the node packs N, C and X itself
+        if cells is not None:
+            cells = ops.score_cells_check(cells, dev)
+        ent = ops.score_mask_ids(ent_n, ent_c, B, dev) if "ent" in present else None
+        exs = ops.score_xneg_ids(ent_x, M, dev) if x is not None and ent_x is not None else None
+        pw = ops.score_pair_weights(pair_w, B, dev) if pair_w is not None else None
         # the operands, once per mode
-        Np = Cp = None
+        Np = Cp = Xp = None
         if fp8:
             # e4m3 operands for the S products (v_mfma_scale_f32_32x32x64_f8f6f4: twice the bf16 MFMA rate), everything else as
             # the bf16 path; always the single-pass forward and the workgroup-staged backward (BASELINE configs[4])
@@ -128,15 +121,20 @@ class _ScoreCEFn(torch.autograd.Function):
             else:
                 scale_n = ops.score_unit_scale(inv_t) if scale_n is None else scale_n
                 Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
+            if x is not None:
+                Xp = ops.score_pack_bf16(x, 1.0)
         # the kernel form, once.  Symmetric: ONE sweep of the B x B tiles serves both softmax directions -- the steady state of
-        # training, and always for fp8, the logQ correction, the repeated-entity mask and pair weights (their row ranks and metrics
-        # are the raw scores').  Otherwise the
-        # first call's diagnostics (column / full ranks) on the two-direction kernel, or the f32 path's two directional sweeps.
-        w = None
-        if Np is not None and (fp8 or lq or ent is not None or pw is not None or not (want_col_rank or full_rank)):
-            rowsum, colsum, diag, row_rank, inv, out8, loss, w = ops._fwd_sym(Np, Cp, B, D, inv_t, shift, scale_n, True, fp8, x3,
-                                                                              lq_n, lq_c, ent, pw)
-            if (lq or ent is not None or pw is not None) and want_col_rank:
+        # training, and always for fp8 and for every optional term (their row ranks and metrics are the raw scores').  Otherwise the
+        # first call's diagnostics (column / full ranks) on the two-direction kernel, or the f32 path's two directional sweeps (plus
+        # the extras' rectangular one).
+        any_term = bool(present & _TERM_FORMS.keys())
+        terms = ops.ScoreTerms(ent=ent, pw=pw)
+        inv = w = w_x = None
+        if Np is not None and (fp8 or any_term or not (want_col_rank or full_rank)):
+            plan = ops.score_cells_plan(cells, B, M, count=cell_count) if cells is not None else None
+            terms = ops.ScoreTerms((lq_n, lq_c) if lq else None, ent, pw, (Xp, M, lq_x, exs) if x is not None else None, plan)
+            rowsum, colsum, diag, row_rank, inv, w, w_x, out8, loss = ops._sym_fwd(Np, Cp, B, D, inv_t, shift, scale_n, True, score_dtype, terms)
+            if any_term and want_col_rank:
                 # the first call's column top-1 rate (a diagnostic only) from the uncorrected two-direction kernel
                 col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n, x3=x3)[4]
                 out8 = out8.clone()
@@ -150,190 +148,127 @@ class _ScoreCEFn(torch.autograd.Function):
             else:
                 rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c, ent=ent)
                 colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n, ent=ent)
+                if x is not None:
+                    terms = terms._replace(extras=(None, M, lq_x, exs))
+                    ops.score_dir_fwd_xneg(n, x, inv_t, shift, diag, rowsum, row_rank, lq_x=lq_x, ent_c=ent[1] if exs is not None else None,
+                                           ent_x=exs)
                 if lq:
                     w = (lq_n.contiguous(), lq_c.contiguous())
             out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c, pw=pw)
-        ctx.packed = None if Np is None else (Np, Cp, scale_n, inv)
-        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = fp8, x3, w, ent, pw
-        ctx.save_for_backward(n, c, rowsum, colsum)
-        ctx.inv_t, ctx.shift = inv_t, shift
+        ctx.rec = _Saved(inv_t, shift, score_dtype, None if Np is None else (Np, Cp, scale_n, inv), w, w_x, terms)
+        ctx.save_for_backward(n, c, rowsum, colsum, *(() if x is None else (x,)))
         ctx.mark_non_differentiable(out8, row_rank)
         ctx.set_materialize_grads(False)                     # else autograd zero-fills grads for out8 / row_rank every step
         return loss, out8, row_rank
 
     @staticmethod
-    def _forward_xneg(ctx, n, c, inv_t, score_dtype, want_col_rank, lq_n, lq_c, ent_n, ent_c, pair_w, x, lq_x, ent_x):
-        """forward with shared extra negatives x [M, D]: always the symmetric sweep (bf16) or the directional sweeps plus the extras'
-        rectangular one (fp32)"""
-        B, D = n.shape
-        dev, shift, lq = n.device, abs(inv_t), lq_n is not None
-        if score_dtype not in ("bf16", "fp32"):
-            raise ValueError(f"extra negatives have no {score_dtype} form (score_dtype 'bf16' or 'fp32')")
-        if pair_w is not None:
-            raise ValueError("extra negatives do not combine with pair weights")
-        if c.shape != n.shape:
-            raise ValueError("extra negatives need as many notice rows as company rows")
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1 or x.device != dev:
-            raise ValueError(f"the extra negatives must be a [M >= 1, {D}] tensor on {dev}")
-        x = x.contiguous().float()
-        M = x.shape[0]
-        ent = exs = None
-        if ent_n is not None or ent_c is not None:
-            ent = ops.score_mask_ids(ent_n, ent_c, B, dev)
-        if ent_x is not None:
-            if ent_c is None:
-                raise ValueError("the extras' entity ids are compared with the batch's company ids: ent_c is missing")
-            exs = ops.score_xneg_ids(ent_x, M, dev)
-        if lq:
-            ops._lq_check_t(inv_t)
-            if lq_x is None:                                 # a missing log_q on the extras counts as zeros
-                lq_x = torch.zeros(M, dtype=torch.float32, device=dev)
-        elif lq_x is not None:
-            raise ValueError("the extras carry log_q but the batch is not corrected")
-        w = None
-        if score_dtype == "bf16":
-            scale_n = ops.score_unit_scale(inv_t)
-            Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
-            Xp = ops.score_pack_bf16(x, 1.0)
-            rowsum, colsum, diag, row_rank, inv, w, w_x, out8, loss = ops.score_fwd_sym_xneg(Np, Cp, Xp, B, M, D, inv_t, shift, ent, exs, lq_n, lq_c,
-                                                                                             lq_x, scale_n, True)
-            if want_col_rank:                                # the first call's column top-1 rate (a diagnostic only)
-                col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n)[4]
-                out8 = out8.clone()
-                out8[5] = (col_rank == 0).float().mean()
-            ctx.packed = (Np, Cp, scale_n, inv)
-            ctx.xn = (Xp, w_x, exs, None)
-        else:
-            rowsum, diag, row_rank, sumscore = ops.score_dir_fwd(n, c, inv_t, shift, 0, True, lq_b=lq_c, ent=ent)
-            colsum, _, col_rank, _ = ops.score_dir_fwd(c, n, inv_t, shift, 0, False, lq_b=lq_n, ent=ent)
-            ops.score_dir_fwd_xneg(n, x, inv_t, shift, diag, rowsum, row_rank, lq_x=lq_x, ent_c=ent[1] if exs is not None else None,
-                                   ent_x=exs)
-            if lq:
-                w = (lq_n.contiguous(), lq_c.contiguous())
-            out8, loss = ops.score_loss_finish(B, shift, rowsum, colsum, diag, row_rank, col_rank, sumscore, lq_n=lq_n, lq_c=lq_c)
-            ctx.packed = None
-            ctx.xn = (None, None, exs, lq_x)
-        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = False, False, w, ent, None
-        ctx.save_for_backward(n, c, rowsum, colsum, x)
-        ctx.inv_t, ctx.shift = inv_t, shift
-        ctx.mark_non_differentiable(out8, row_rank)
-        ctx.set_materialize_grads(False)
-        return loss, out8, row_rank
-
-    @staticmethod
-    def _forward_cells(ctx, n, c, inv_t, score_dtype, want_col_rank, packed_n, packed_c, scale_n, lq_n, lq_c, pair_w, x, lq_x, cells, cell_count):
-        """forward with masked cells (and optionally extras x [M, D]): the plan launches, then the symmetric sweep on it"""
-        B, D = n.shape
-        dev, shift, lq = n.device, abs(inv_t), lq_n is not None
-        if score_dtype != "bf16":
-            raise ValueError(f"masked cells have no {score_dtype} form (score_dtype 'bf16')")
-        if pair_w is not None:
-            raise ValueError("masked cells do not combine with pair weights")
-        if c.shape != n.shape:
-            raise ValueError("masked cells need as many notice rows as company rows")
-        cells = ops.score_cells_check(cells, dev)
-        M, Xp = 0, None
-        if x is not None:
-            if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1 or x.device != dev:
-                raise ValueError(f"the extra negatives must be a [M >= 1, {D}] tensor on {dev}")
-            x = x.contiguous().float()
-            M = x.shape[0]
-        if lq:
-            ops._lq_check_t(inv_t)
-            if x is not None and lq_x is None:               # a missing log_q on the extras counts as zeros
-                lq_x = torch.zeros(M, dtype=torch.float32, device=dev)
-        elif lq_x is not None:
-            raise ValueError("the extras carry log_q but the batch is not corrected")
-        if x is None and packed_n is not None and packed_c is not None:
-            Np, Cp = packed_n, packed_c
-            scale_n = 1.0 if scale_n is None else scale_n
-        else:
-            scale_n = ops.score_unit_scale(inv_t)
-            Np, Cp = ops.score_pack2_bf16(n, c, scale_n, 1.0)
-        if x is not None:
-            Xp = ops.score_pack_bf16(x, 1.0)
-        plan = ops.score_cells_plan(cells, B, M, count=cell_count)
-        rowsum, colsum, diag, row_rank, inv, w, w_x, out8, loss = ops.score_fwd_sym_cells(Np, Cp, B, D, inv_t, shift, plan, Xp, M, lq_n, lq_c,
-                                                                                          lq_x, scale_n, True)
-        if want_col_rank:                                    # the first call's column top-1 rate (a diagnostic only)
-            col_rank = ops.score_fwd_bf16(Np, Cp, B, D, inv_t, shift, True, False, scale_n)[4]
-            out8 = out8.clone()
-            out8[5] = (col_rank == 0).float().mean()
-        ctx.packed = (Np, Cp, scale_n, inv)
-        ctx.kp = (plan, Xp, w_x, M)
-        ctx.xn = None
-        ctx.fp8, ctx.x3, ctx.lq, ctx.ent, ctx.pw = False, False, w, None, None
-        if x is not None:
-            ctx.save_for_backward(n, c, rowsum, colsum, x)
-        else:
-            ctx.save_for_backward(n, c, rowsum, colsum)
-        ctx.inv_t, ctx.shift = inv_t, shift
-        ctx.mark_non_differentiable(out8, row_rank)
-        ctx.set_materialize_grads(False)
-        return loss, out8, row_rank
-
-    @staticmethod
-    def _backward_cells(ctx, d_loss):
+    def backward(ctx, d_loss, _d_out8, _d_rank):
+        """the square backward on the forward's sums (which include the extras), then the extras' two rectangular directions: dN +=
+        and dX, in this order (one launch with masked cells)"""
+        if d_loss is None:
+            return _node_grads()
         n, c, rowsum, colsum = ctx.saved_tensors[:4]
         B, D = n.shape
-        if d_loss is None:
-            return (None,) * 19
         if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
             d_loss = d_loss.contiguous().float()
-        plan, Xp, w_x, M = ctx.kp
-        Np, Cp, scale_n, inv = ctx.packed
-        dN, dC, dX = ops.score_bwd_bf16_cells(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, ctx.inv_t / (2.0 * B), plan, scale_n,
-                                              inv, w=ctx.lq, Xp=Xp, M=M, w_x=w_x)
-        return (dN, dC) + (None,) * 12 + (dX, None, None, None, None)
-
-    @staticmethod
-    def backward(ctx, d_loss, _d_out8, _d_rank):
-        if ctx.kp is not None:
-            return _ScoreCEFn._backward_cells(ctx, d_loss)
-        if ctx.xn is not None:
-            return _ScoreCEFn._backward_xneg(ctx, d_loss)
-        n, c, rowsum, colsum = ctx.saved_tensors
-        B, D = n.shape
-        if d_loss is None:
-            return (None,) * 19
-        if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
-            d_loss = d_loss.contiguous().float()
-        scale = ctx.inv_t / (2.0 * B)
-        if ctx.packed is not None:
-            Np, Cp, scale_n, inv = ctx.packed
-            dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, fp8=ctx.fp8,
-                                        x3=ctx.x3, w=ctx.lq, ent=ctx.ent, pw=ctx.pw)
+        r = ctx.rec
+        scale = r.inv_t / (2.0 * B)
+        if r.packed is not None:
+            Np, Cp, scale_n, inv = r.packed
+            dN, dC, dX = ops._bwd_sym(Np, Cp, B, D, r.inv_t, r.shift, rowsum, colsum, d_loss, scale, scale_n, inv, r.operands, r.w, r.terms, r.w_x)
         else:
-            lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
-            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent, pw=ctx.pw)
-            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent, pw=ctx.pw)
-        return (dN, dC) + (None,) * 17
+            ent, pw = r.terms.ent, r.terms.pw
+            lqn, lqc = r.w if r.w is not None else (None, None)
+            dN = ops.score_dir_bwd(n, c, r.inv_t, r.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ent, pw=pw)
+            dC = ops.score_dir_bwd(c, n, r.inv_t, r.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ent, pw=pw)
+            dX = None
+            if r.terms.extras is not None:
+                x, (_, _, lq_x, exs) = ctx.saved_tensors[4], r.terms.extras
+                ec = ent[1] if exs is not None else None
+                ops.score_dir_bwd_xneg(n, x, r.inv_t, r.shift, True, rowsum, d_loss, scale, lq_x=lq_x, ent_a=ec, ent_b=exs, out=dN)
+                dX = ops.score_dir_bwd_xneg(x, n, r.inv_t, r.shift, False, rowsum, d_loss, scale, lq_x=lq_x, ent_a=exs, ent_b=ec)
+        return _node_grads(n=dN, c=dC, x=dX)
 
-    @staticmethod
-    def _backward_xneg(ctx, d_loss):
-        """the square backward on the forward's sums (which include the extras), then the extras' two rectangular directions: dN +=
-        and dX, in this order"""
-        n, c, rowsum, colsum, x = ctx.saved_tensors
-        B, D = n.shape
-        M = x.shape[0]
-        if d_loss is None:
-            return (None,) * 19
-        if d_loss.dtype != torch.float32 or not d_loss.is_contiguous():
-            d_loss = d_loss.contiguous().float()
-        scale = ctx.inv_t / (2.0 * B)
-        Xp, w_x, exs, lq_x = ctx.xn
-        ec = ctx.ent[1] if exs is not None else None
-        if ctx.packed is not None:
-            Np, Cp, scale_n, inv = ctx.packed
-            dN, dC = ops.score_bwd_bf16(Np, Cp, B, D, ctx.inv_t, ctx.shift, rowsum, colsum, d_loss, scale, scale_n, inv, w=ctx.lq, ent=ctx.ent)
-            dX = ops.score_bwd_bf16_xneg(Np, Xp, B, M, D, ctx.inv_t, ctx.shift, inv[0], w_x, d_loss, scale, dN, scale_n, ent_c=ec, ent_x=exs)
-        else:
-            lqn, lqc = ctx.lq if ctx.lq is not None else (None, None)
-            dN = ops.score_dir_bwd(n, c, ctx.inv_t, ctx.shift, 0, rowsum, colsum, d_loss, scale, lq_a=lqn, lq_b=lqc, ent=ctx.ent)
-            dC = ops.score_dir_bwd(c, n, ctx.inv_t, ctx.shift, 0, colsum, rowsum, d_loss, scale, lq_a=lqc, lq_b=lqn, ent=ctx.ent)
-            ops.score_dir_bwd_xneg(n, x, ctx.inv_t, ctx.shift, True, rowsum, d_loss, scale, lq_x=lq_x, ent_a=ec, ent_b=exs, out=dN)
-            dX = ops.score_dir_bwd_xneg(x, n, ctx.inv_t, ctx.shift, False, rowsum, d_loss, scale, lq_x=lq_x, ent_a=exs, ent_b=ec)
-        return (dN, dC) + (None,) * 12 + (dX, None, None, None, None)
+
+class _Saved(NamedTuple):
+    """what _ScoreCEFn.forward leaves for its backward: packed = (Np, Cp, scale_n, inv) or None on the f32 path; w = the forward's
+    sampling weights (the f32 path: the log q vectors); terms as the backward entries take them"""
+    inv_t: float
+    shift: float
+    operands: str
+    packed: Optional[tuple]
+    w: Optional[tuple]
+    w_x: Optional[torch.Tensor]
+    terms: "ops.ScoreTerms"
+
+
+_NODE_INPUTS = _ScoreCEFn.forward.__code__.co_varnames[1:_ScoreCEFn.forward.__code__.co_argcount]
+_NODE_SLOT = {name: i for i, name in enumerate(_NODE_INPUTS)}
+
+
+def _node_grads(**grads):
+    """_ScoreCEFn.backward's return: one slot per forward input, filled by parameter name"""
+    out = [None] * len(_NODE_INPUTS)
+    for name, g in grads.items():
+        out[_NODE_SLOT[name]] = g
+    return tuple(out)
+
+
+# ---- the one table of what combines: the node decides with it, the task's batch validators ask it ----------------------------------
+_TERM_FORMS = {"cells": ("bf16",), "extras": ("fp32", "bf16"), "ent": ("fp32", "bf16"), "pw": ("fp32", "bf16"),
+               "lq": ("fp32", "bf16", "bf16x3")}                      # term -> the score_dtypes that have a form of it
+_TERM_CLASHES = frozenset({frozenset({"cells", "ent"}), frozenset({"cells", "pw"}), frozenset({"extras", "pw"})})
+
+
+def _terms_clash(a, b):
+    return frozenset({a, b}) in _TERM_CLASHES
+
+
+def _need_form(term, score_dtype, name, hint=" (score_dtype 'bf16' or 'fp32')"):
+    if score_dtype not in _TERM_FORMS[term]:
+        raise ValueError(f"{name} no {score_dtype} form{hint}")
+
+
+def _need_square(square, name):
+    if not square:
+        raise ValueError(f"{name} as many notice rows as company rows")
+
+
+def _score_terms_check(score_dtype, square, present):
+    """Refuses what the score node does not cover; no device, no tensors.  present: the names of what the call carries, of 'lq', 'ent'
+    (either side's ids; 'ent_c' the companies'), 'pw', 'extras' (with 'ent_x' / 'lq_x'), 'cells'.  square: as many notice rows as
+    company rows.  The refusals in the order they are decided."""
+    if not present:
+        return
+    has = present.__contains__
+    cells, extras = has("cells"), has("extras")
+    if cells:
+        if (has("ent") or has("ent_x")) and _terms_clash("cells", "ent"):      # (ids on the extras are the mask's too)
+            raise ValueError("masked cells do not combine with the repeated-entity mask (cells built from the pair table hold every repeat)")
+        _need_form("cells", score_dtype, "masked cells have", " (score_dtype 'bf16')")
+        if has("pw") and _terms_clash("cells", "pw"):
+            raise ValueError("masked cells do not combine with pair weights")
+        _need_square(square, "masked cells need")
+    if extras:
+        _need_form("extras", score_dtype, "extra negatives have")
+        if has("pw") and _terms_clash("extras", "pw"):
+            raise ValueError("extra negatives do not combine with pair weights")
+        _need_square(square, "extra negatives need")
+        if has("ent_x") and not has("ent_c"):
+            raise ValueError("the extras' entity ids are compared with the batch's company ids: ent_c is missing")
+    if (cells or extras) and has("lq_x"):
+        if not has("lq"):
+            raise ValueError("the extras carry log_q but the batch is not corrected")
+        if not extras:
+            raise ValueError("masked cells: lq_x needs lq_n / lq_c and the extras")
+    if has("ent"):
+        _need_form("ent", score_dtype, "the repeated-entity mask has")
+        _need_square(square, "the repeated-entity mask needs")
+    if has("pw"):
+        _need_form("pw", score_dtype, "pair weights have")
+        _need_square(square, "pair weights need")
+    if has("lq"):
+        _need_form("lq", score_dtype, "the logQ correction has", "")
 
 
 class _Result(dict):
@@ -416,23 +351,8 @@ class TwoTowerTrainTask(nn.Module):
             notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, neg, nb, lq, ent, cells)
         else:
             notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
-        if neg is not None:
-            pass                                             # (scored above, with the extras)
-        elif cells is not None:
-            loss, out8, _ = self._score_ce_cells(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                                 not hasattr(self, "_pair_check_done"), lq, cells)
-        elif pw is not None:
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw)
-        elif ent is not None:
-            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent)
-        elif lq is None:
-            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                           not hasattr(self, "_pair_check_done"))
-        else:
-            loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                           not hasattr(self, "_pair_check_done"), log_q=lq)
+                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw, cells=cells)
         if not hasattr(self, "_pair_check_done"):                                            # :82-84
             self._verify_positive_pair_alignment(out8)
             self._pair_check_done = True
@@ -478,8 +398,8 @@ class TwoTowerTrainTask(nn.Module):
         if self._dense_loss:
             raise ValueError("the logQ correction (a batch with 'log_q') is not supported by the dense loss path "
                              "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype == "fp8":
-            raise ValueError("the logQ correction (a batch with 'log_q') is not supported for score_dtype='fp8'")
+        if self.score_dtype not in _TERM_FORMS["lq"]:
+            raise ValueError(f"the logQ correction (a batch with 'log_q') is not supported for score_dtype={self.score_dtype!r}")
         ref = notice_input["dense"]
         out = []
         for name, t in (("notice", lq_n), ("company", lq_c)):
@@ -503,7 +423,7 @@ class TwoTowerTrainTask(nn.Module):
         if self._dense_loss:
             raise ValueError("the repeated-entity mask (a batch with 'entity') is not supported by the dense loss path "
                              "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype in ("fp8", "bf16x3"):
+        if self.score_dtype not in _TERM_FORMS["ent"]:
             raise ValueError(f"the repeated-entity mask (a batch with 'entity') is not supported for score_dtype={self.score_dtype!r}")
         ref = notice_input["dense"]
         for name, t in (("notice", ent_n), ("company", ent_c)):
@@ -525,7 +445,7 @@ class TwoTowerTrainTask(nn.Module):
         if self._dense_loss:
             raise ValueError("pair weights (a batch with 'pair_weight') are not supported by the dense loss path "
                              "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype in ("fp8", "bf16x3"):
+        if self.score_dtype not in _TERM_FORMS["pw"]:
             raise ValueError(f"pair weights (a batch with 'pair_weight') are not supported for score_dtype={self.score_dtype!r}")
         ref = batch["notice"]["dense"]
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
@@ -548,15 +468,15 @@ class TwoTowerTrainTask(nn.Module):
             return None
         if not self._cells_ok():
             raise NotImplementedError(f"masked cells (a batch with 'masked_cells') are not supported by {type(self).__name__}")
-        if ent is not None:
+        if ent is not None and _terms_clash("cells", "ent"):
             raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'entity': cells built from the pair table "
                              "already hold every repeat")
-        if pw is not None:
+        if pw is not None and _terms_clash("cells", "pw"):
             raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'pair_weight'")
         if self._dense_loss:
             raise ValueError("masked cells (a batch with 'masked_cells') are not supported by the dense loss path "
                              "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype != "bf16":
+        if self.score_dtype not in _TERM_FORMS["cells"]:
             raise ValueError(f"masked cells (a batch with 'masked_cells') are not supported for score_dtype={self.score_dtype!r}")
         ref = batch["notice"]["dense"]
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2:
@@ -568,15 +488,6 @@ class TwoTowerTrainTask(nn.Module):
         if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.numel() == 1 and n.device == ref.device):
             raise ValueError(f"batch['masked_cells_count'] must be an int32 tensor of one element on {ref.device}")
         return t, n
-
-    def _score_ce_cells(self, n, c, inv_t, first_call, log_q, cells):
-        """_score_ce with masked cells (no extras): the towers' packed operand images where they emitted them"""
-        lqs = log_q if log_q is not None else (None, None)
-        pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
-        if pn is None or pc is None or pc[1] != 1.0:
-            pn, pc = (None, None), (None, None)
-        return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], None, None, None, None,
-                                None, None, cells[0], cells[1])
 
     def _forward_negatives(self, notice_input, company_input, neg, B, lq, ent, cells=None):
         """(notice embeddings, company embeddings, loss, out8) of a batch with shared extra negatives: the M rows ride behind the batch's
@@ -605,12 +516,12 @@ class TwoTowerTrainTask(nn.Module):
             return None
         if not self._negatives_ok():
             raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
-        if pw is not None:
+        if pw is not None and _terms_clash("extras", "pw"):
             raise ValueError("extra negatives (a batch with 'negatives') do not combine with 'pair_weight'")
         if self._dense_loss:
             raise ValueError("extra negatives (a batch with 'negatives') are not supported by the dense loss path "
                              "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype in ("fp8", "bf16x3"):
+        if self.score_dtype not in _TERM_FORMS["extras"]:
             raise ValueError(f"extra negatives (a batch with 'negatives') are not supported for score_dtype={self.score_dtype!r}")
         ref = company_input["dense"]
         d = neg.get("dense") if isinstance(neg, dict) else None
@@ -639,50 +550,29 @@ class TwoTowerTrainTask(nn.Module):
                                  "compared with")
         return neg
 
-    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None):
+    def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None, cells=None):
         """(loss, out8, row_rank) of the symmetric in-batch-negative softmax-CE (:99-134); the sharded task overrides it.
         log_q: (lq_n, lq_c) -- the logQ-corrected loss (_ScoreCEFn).  entity: (ent_n, ent_c) -- the repeated-entity mask.
-        pair_weight: f32 [B] -- per-pair sample weights; combines with both."""
-        if pair_weight is not None:
-            if self._dense_loss or self.score_dtype in ("fp8", "bf16x3"):
-                raise ValueError("pair weights cover the fused cross-entropy with score_dtype fp32 / bf16 only")
+        pair_weight: f32 [B] -- per-pair sample weights; combines with both.  cells: (cells, count) -- masked cells."""
+        for given, term, what, s in ((pair_weight, "pw", "pair weights", ""), (entity, "ent", "the repeated-entity mask", "s"),
+                                     (log_q, "lq", "the logQ correction", "s")):
+            if given is None:
+                continue
+            if self._dense_loss or self.score_dtype not in _TERM_FORMS[term]:
+                raise ValueError(f"{what} cover{s} the fused cross-entropy with score_dtype {' / '.join(_TERM_FORMS[term])} only")
             if n.shape != c.shape:
-                raise ValueError("pair weights need as many notice rows as company rows")
-            lqs = log_q if log_q is not None else (None, None)
-            ents = entity if entity is not None else (None, None)
-            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
-            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
-                pn, pc = (None, None), (None, None)
-            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], ents[0], ents[1],
-                                    pair_weight)
-        if entity is not None:
-            if self._dense_loss or self.score_dtype in ("fp8", "bf16x3"):
-                raise ValueError("the repeated-entity mask covers the fused cross-entropy with score_dtype fp32 / bf16 only")
-            if n.shape != c.shape:
-                raise ValueError("the repeated-entity mask needs as many notice rows as company rows")
-            lqs = log_q if log_q is not None else (None, None)
-            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
-            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
-                return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, None, None, None, lqs[0], lqs[1], entity[0], entity[1])
-            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], entity[0], entity[1])
-        if log_q is not None:
-            if self._dense_loss or self.score_dtype == "fp8":
-                raise ValueError("the logQ correction covers the fused cross-entropy with score_dtype fp32 / bf16 / bf16x3 only")
-            if n.shape != c.shape:
-                raise ValueError("the logQ correction needs as many notice rows as company rows")
-            pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)
-            if self.score_dtype != "bf16" or pn is None or pc is None or pc[1] != 1.0:
-                return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, None, None, None, log_q[0], log_q[1])
-            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], log_q[0], log_q[1])
+                raise ValueError(f"{what} need{s} as many notice rows as company rows")
         if self._dense_loss:
             if n.shape != c.shape:
                 raise ValueError("the dense loss path needs as many notice rows as company rows")
             loss, out8 = _DenseLossFn.apply(n, c, inv_t, 0 if self.loss_type == "cross_entropy" else 1, float(self.label_smoothing))
             return loss, out8, None
+        lqs, ents, kp = log_q or (None, None), entity or (None, None), cells or (None, None)
         pn, pc = getattr(n, "_tt_packed", None), getattr(c, "_tt_packed", None)     # (buffer, scale) emitted by the towers
         if self.score_dtype != "bf16" or n.shape != c.shape or pn is None or pc is None or pc[1] != 1.0:
-            return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False)
-        return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1])
+            pn, pc = (None, None), (None, None)
+        return _ScoreCEFn.apply(n, c, inv_t, self.score_dtype, first_call, False, pn[0], pc[0], pn[1], lqs[0], lqs[1], ents[0], ents[1],
+                                pair_weight, None, None, None, kp[0], kp[1])
 
     def _compute_similarity_matrix(self, notice_embeddings, company_embeddings):                # :99-112
         return self.two_tower_model.compute_similarity(notice_embeddings, company_embeddings, self.temperature)

@@ -26,7 +26,9 @@ import _known_mask_reference as KR
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(70, 0, 32, 1.0), (513, 0, 128, 0.05), (70, 1, 32, 1.0), (70, 33, 200, 0.5), (300, 263, 64, 2.0), (96, 300, 64, 1.0)]
+SHAPES = [(70, 0, 32, 1.0), (513, 0, 128, 0.05), (70, 1, 32, 1.0), (70, 33, 200, 0.5), (300, 263, 64, 2.0), (96, 300, 64, 1.0),
+          # every class of D with and without extras at a ragged B (four tiles, the last one partial)
+          (97, 0, 64, 1.0), (97, 0, 200, 1.0), (97, 40, 96, 1.0)]
 PATTERNS = ["edges", "random", "heavy"]
 
 

@@ -133,7 +133,8 @@ def _sum_rtol(mode, inv_t):
     relative error of that times 2^-24 in the term (4 such roundings allowed); at T = 1 the per-mode bound holds alone"""
     return max(SUM_RTOL[mode], 4 * 2.0 ** -24 * (2 * abs(inv_t) + L_CLAMP))
 SHAPES = [(1, 32, 1.0), (33, 1, 0.5), (257, 200, 2.0), (257, 64, 0.05), (2048, 128, 1.0), (2048, 256, 0.5),
-          (8192, 64, 1.0), (8192, 128, 0.05), (33, 256, 1.0), (2048, 32, 2.0)]
+          (8192, 64, 1.0), (8192, 128, 0.05), (33, 256, 1.0), (2048, 32, 2.0),
+          (97, 96, 1.0)]                              # (the 65..128 class of D at a ragged B: four tiles, the last one partial)
 
 
 # (the f32 parity path at B = 8192 runs at D = 64 only)

@@ -25,7 +25,8 @@ from _mask_reference import ids, reference, ref_sums, unit_scale
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 32, 1.0), (33, 1, 0.5), (65, 64, 0.05), (257, 200, 2.0), (257, 64, 0.05), (2048, 128, 1.0)]
+SHAPES = [(1, 32, 1.0), (33, 1, 0.5), (65, 64, 0.05), (257, 200, 2.0), (257, 64, 0.05), (2048, 128, 1.0),
+          (97, 96, 1.0)]                              # (the 65..128 class of D at a ragged B: four tiles, the last one partial)
 PATTERNS = ["distinct", "one_notice", "tile_edge", "groups", "heavy"]
 MODES = ["bf16", "fp32"]
 

@@ -31,7 +31,8 @@ from _pair_weight_reference import PATTERNS, normalise, reference, ref_sums, wei
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 32, 1.0), (33, 1, 0.5), (65, 64, 0.05), (257, 200, 2.0), (257, 64, 0.05), (2048, 128, 1.0)]
+SHAPES = [(1, 32, 1.0), (33, 1, 0.5), (65, 64, 0.05), (257, 200, 2.0), (257, 64, 0.05), (2048, 128, 1.0),
+          (97, 96, 1.0)]                              # (the 65..128 class of D at a ragged B: four tiles, the last one partial)
 COMBO_SHAPES = [(33, 1, 0.5), (257, 64, 0.05), (2048, 128, 1.0)]
 MODES = ["bf16", "fp32"]
 

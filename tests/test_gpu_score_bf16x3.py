@@ -76,6 +76,7 @@ X3_CASES = [  # (B, D, T)
     (2, 1, 1.0), (2, 256, 2.0),
     (63, 129, 0.05), (63, 1, 0.025),
     (65, 192, 2.0), (65, 64, 0.025), (65, 3, 1.0),
+    (97, 96, 1.0),                                        # the 65..128 class of D, ragged B
     (4097, 192, 1.0), (4097, 129, 0.025), (4097, 3, 0.05),
     (8192, 256, 0.025), (8192, 64, 1.0), (8192, 129, 0.05),
 ]
