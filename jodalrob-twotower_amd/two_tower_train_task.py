@@ -72,6 +72,8 @@ class _ScoreCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, c, inv_t, score_dtype, want_col_rank=True, full_rank=True, packed_n=None, packed_c=None, scale_n=None,
                 lq_n=None, lq_c=None, ent_n=None, ent_c=None, pair_w=None, x=None, lq_x=None, ent_x=None, cells=None, cell_count=None):
+        if n.shape[0] != c.shape[0]:                         # every path below sweeps a square problem of n's row count
+            raise ValueError(f"the score node needs as many notice rows as company rows, got {n.shape[0]} and {c.shape[0]}")
         n, c = n.contiguous().float(), c.contiguous().float()
         B, D = n.shape
         dev, shift = n.device, abs(inv_t)                    # unit rows: |s| <= 1/T

@@ -123,3 +123,18 @@ def test_validators_share_the_table():
         "cells": {"bf16"}, "extras": {"fp32", "bf16"}, "ent": {"fp32", "bf16"}, "pw": {"fp32", "bf16"}, "lq": {"fp32", "bf16", "bf16x3"}}
     clashes = {(a, b) for a in TERMS for b in TERMS if a < b and T._terms_clash(a, b)}
     assert clashes == {("cells", "ent"), ("cells", "pw"), ("extras", "pw")}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_node_refuses_unequal_row_counts(dtype):
+    """the node's own refusal (the table above answers for the terms only: a plain call passes it at any shape) -- on CPU tensors,
+    before anything is packed or launched: the library is not even loaded"""
+    import torch
+    from jodalrob_twotower_amd import _lib
+    from jodalrob_twotower_amd.two_tower_train_task import _ScoreCEFn
+    loaded = _lib._lib
+    for rows_n, rows_c in ((4, 3), (3, 4)):
+        with pytest.raises(ValueError) as e:
+            _ScoreCEFn.apply(torch.zeros(rows_n, 8), torch.zeros(rows_c, 8), 1.0, dtype)
+        assert str(e.value) == f"the score node needs as many notice rows as company rows, got {rows_n} and {rows_c}"
+    assert _lib._lib is loaded
