@@ -1135,6 +1135,57 @@ int tt_batch_ingest_store_lookup(tt_ctx* ctx, int32_t n, void* const* dst, const
                                  const int64_t* order /* [B] or NULL */, int32_t* rows_km /* or NULL */,
                                  const tt_ingest_lookup* lookup, const tt_cvt_list* cvt /* or NULL */, tt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pooled multi-valued categorical features (embedding bags) -- no reference counterpart: the reference's bags all have
+ * length one (src/towers/pairs/unified_bid_data_loader.py:835).  Same sample-major contract as the lookup above: slot =
+ * side_slot_base + b*K + k names bag (b, k); the bag's ids are ids[offsets[b*K + k] .. offsets[b*K + k + 1]) (positions),
+ * offsets the exclusive prefix sum of the KJT's lengths.  With every length 1 the two entries below give the bits of
+ * tt_embed_lookup_fwd and of tt_embed_grad_bwd over the general plan (test).
+ *
+ * tt_embed_bag_fwd, for bag (b, k) of side s, ONE launch:
+ *   row_p = key_row_offset[k] + clamp(ids[p], 0, key_vocab[k]-1)          for every position p of the bag
+ *   sum   = table[row_p0] + table[row_p1] + ...                            f32, ascending position order
+ *   out[b*ld_out + k*E .. +E) = sum (key_pool[k] == TT_POOL_SUM) | sum / length (TT_POOL_MEAN);  zeros for an empty bag;
+ *                               rounded to nearest even for TT_BF16
+ *   rows_out[P] = row_p, bag_of[P] = slot of the bag, P = (nnz of the earlier sides) + p       (either may be NULL)
+ * Positions behind a side's last bag, [offsets[B*K], nnz), belong to no bag: they get rows_out = 0 and bag_of = -1 (the
+ * gradient skips them).  The data path uses no atomics; one lane group of E/4 lanes owns a bag and adds its rows in order.
+ * E % 4 == 0, 4 <= E <= 256, table 16-byte and outputs 4-element aligned (base and ld_out): TT_ERR_UNSUPPORTED otherwise, nothing
+ * launched.  A decoded row outside [0, table_rows) reads the last row and raises TT_DEVERR_ROW_RANGE, as the lookup does.  A
+ * bag whose offsets are negative, decreasing or end beyond nnz raises TT_DEVERR_BAG_OFFSETS and is treated as empty: nothing is
+ * read through such a pair, and the positions it should have covered are not written.
+ * ---------------------------------------------------------------------------------------------- */
+#define TT_DEVERR_BAG_OFFSETS 8u
+#define TT_POOL_SUM 0
+#define TT_POOL_MEAN 1
+typedef struct tt_bag_side {
+  const int64_t* ids;            /* [nnz] */
+  const int64_t* offsets;        /* [B*K + 1] */
+  const int64_t* key_row_offset; /* [K] */
+  const int64_t* key_vocab;      /* [K] */
+  const int32_t* key_pool;       /* [K] TT_POOL_* */
+  void* out;
+  int64_t ld_out;
+  int64_t nnz;
+  int32_t K;
+  int32_t out_dtype;             /* TT_F32 / TT_BF16 */
+} tt_bag_side;
+int tt_embed_bag_fwd(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                     int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream);
+
+/* The bags' table gradient over the plan tt_dedup_plan built from rows_out (M = nnz; sorted_src then lists POSITIONS).  Position
+ * P contributes w_P * d_out[slot bag_of[P]] to its row, w_P = 1, or inv_len[bag_of[P]] when inv_len (f32 per slot: 1 / length
+ * for the mean keys' slots, 1 for the others) is not NULL; positions with bag_of < 0 contribute nothing.  Slot s of source i
+ * reads d_out_i[b*ld + k*E .. +E) as in tt_embed_grad_bwd, and mode is that entry's TT_GRAD_SPARSE / TT_GRAD_DENSE_SET /
+ * TT_GRAD_DENSE_ACC (no flags).  Atomic-free sums, bitwise reproducible: a row's contributions are added (one fused multiply-add
+ * each) in ascending position order; rows of more than 64 contributions in 64-position chunks whose partial sums the finish of
+ * tt_embed_grad_bwd adds.  E % 4 == 0, 4 <= E <= 256, out 16-byte and sources 4-element aligned (TT_ERR_UNSUPPORTED otherwise). */
+size_t tt_embed_bag_grad_workspace_bytes(int64_t nnz, int32_t E);
+int tt_embed_bag_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int64_t B, int32_t E, const int32_t* bag_of,
+                          const float* inv_len, const int32_t* sorted_src, const int32_t* seg_offsets,
+                          const int32_t* unique_rows, const int32_t* n_unique, int64_t nnz, int32_t mode, float* out,
+                          void* workspace, size_t workspace_bytes, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

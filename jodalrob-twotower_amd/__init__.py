@@ -6,7 +6,7 @@ through the C ABI of libtwotower_hip.so (include/twotower.h) into hand-written g
 The directory name carries a hyphen; import it as `jodalrob_twotower_amd` (the alias module at the
 repository root registers it).
 """
-from .kjt import KeyedJaggedTensor, build_batch_kjt                               # noqa: F401
+from .kjt import KeyedJaggedTensor, build_bag_kjt, build_batch_kjt, concat_kjt   # noqa: F401
 from .schema import (PairSchema, SideSchema, TorchRecSchema, build_torchrec_schema_from_meta,   # noqa: F401
                      classify_columns)
 from .cat_embed import CategoricalEmbedder, EmbeddingStore, create_categorical_embedder         # noqa: F401
@@ -20,7 +20,7 @@ from .optim import FusedAdam                                                    
 from .retrieval import CatalogIndex                                               # noqa: F401
 from .hard_negatives import MinedNegatives, mine_hard_negatives                   # noqa: F401
 
-__all__ = ["KeyedJaggedTensor", "build_batch_kjt", "SideSchema", "PairSchema", "TorchRecSchema",
+__all__ = ["KeyedJaggedTensor", "build_batch_kjt", "build_bag_kjt", "concat_kjt", "SideSchema", "PairSchema", "TorchRecSchema",
            "build_torchrec_schema_from_meta", "classify_columns", "CategoricalEmbedder", "EmbeddingStore",
            "create_categorical_embedder", "BaseTower", "NoticeTower", "CompanyTower", "TwoTowerModel",
            "create_two_tower_model", "TwoTowerTrainTask", "create_two_tower_train_task", "FeatureProjector",

@@ -25,6 +25,8 @@ TT_TOWER_UNFUSED_GATHER = 8
 TT_GRAD_SHORT_SEGMENTS = 0x100
 TT_GRAD_PLANNED = 0x200
 TT_GRAD_DEFER_FINISH = 0x400
+TT_POOL_SUM, TT_POOL_MEAN = 0, 1
+TT_DEVERR_BAG_OFFSETS = 8
 
 vp = C.c_void_p
 i32, i64, f32, u64, sz = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
@@ -33,6 +35,11 @@ i32, i64, f32, u64, sz = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 class EmbedSide(C.Structure):
     _fields_ = [("ids", vp), ("key_row_offset", vp), ("key_vocab", vp), ("out", vp), ("ld_out", i64),
                 ("K", i32), ("out_dtype", i32)]
+
+
+class BagSide(C.Structure):
+    _fields_ = [("ids", vp), ("offsets", vp), ("key_row_offset", vp), ("key_vocab", vp), ("key_pool", vp), ("out", vp),
+                ("ld_out", i64), ("nnz", i64), ("K", i32), ("out_dtype", i32)]
 
 
 class StoreSide(C.Structure):
@@ -234,6 +241,9 @@ SIGNATURES = {
                                          C.POINTER(IngestLookup), C.POINTER(CvtList), vp]),
     "tt_batch_ingest_store_lookup": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(EmbedSide), C.POINTER(StoreSide),
                                                i32, i64, vp, vp, C.POINTER(IngestLookup), C.POINTER(CvtList), vp]),
+    "tt_embed_bag_fwd": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, vp]),
+    "tt_embed_bag_grad_workspace_bytes": (sz, [i64, i32]),
+    "tt_embed_bag_grad_bwd": (C.c_int, [vp, C.POINTER(GradSrc), i32, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

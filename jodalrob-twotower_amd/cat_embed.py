@@ -168,13 +168,19 @@ class EmbeddingStore:
             m._bind_grads()
 
     # ---- gradient bookkeeping (called from the autograd backward) ------------------------------
-    def accumulate_grad(self, plan: ops.DedupPlan, srcs, B: int, short_segments: bool = False, members=None):
+    def accumulate_grad(self, plan: ops.DedupPlan, srcs, B: int, short_segments: bool = False, members=None, bag=None):
         """srcs: [(d_out view [B, K*E], K)] in slot order of `plan`.  members: the embedders whose rows `plan` covers (None: the
-        whole store) -- sparse mode files the gradient under them (file_sparse_grad)."""
+        whole store) -- sparse mode files the gradient under them (file_sparse_grad).  bag: the ops.BagPlan of a pooled lookup --
+        `plan` then covers its positions (M = nnz) and the reduction is ops.embed_bag_grad; filing and the dense views are the same."""
+        if bag is not None:
+            reduce = lambda mode, out: ops.embed_bag_grad(plan, bag, srcs, B, self.E, mode, out)
         if self.grad_mode == "sparse":
             grad_rows = torch.empty((max(plan.M, 1), self.E), dtype=torch.float32, device=self.device)
-            ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_SPARSE, grad_rows, short_segments, self.grad_counters(),
-                           defer_finish=self.defer_long_finish)
+            if bag is not None:
+                reduce(ops.TT_GRAD_SPARSE, grad_rows)
+            else:
+                ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_SPARSE, grad_rows, short_segments, self.grad_counters(),
+                               defer_finish=self.defer_long_finish)
             self.file_sparse_grad(plan, grad_rows, members)
             return
         params = self.optim_parameters()
@@ -183,8 +189,13 @@ class EmbeddingStore:
             self.grad = torch.empty_like(self.weight)
         if fresh:
             self.grad.zero_()                            # reference semantics: dense [V_k, E] grads
-            ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_DENSE_SET, self.grad, counters=self.grad_counters())
+            if bag is not None:
+                reduce(ops.TT_GRAD_DENSE_SET, self.grad)
+            else:
+                ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_DENSE_SET, self.grad, counters=self.grad_counters())
             self.bind_grads()
+        elif bag is not None:
+            reduce(ops.TT_GRAD_DENSE_ACC, self.grad)
         else:
             ops.embed_grad(plan, srcs, B, self.E, ops.TT_GRAD_DENSE_ACC, self.grad, counters=self.grad_counters())
 
@@ -208,9 +219,13 @@ class _Table(nn.Module):
 class CategoricalEmbedder(nn.Module):
     def __init__(self, keys: List[str], metadata_path: Union[str, Path], table_name: str, embedding_dim: int = 64,
                  device: Optional[str] = "cuda:0", safety_margin: int = 10, embedding_grad: Optional[str] = None,
-                 materialize: bool = True):
+                 materialize: bool = True, pooling=None):
         super().__init__()
         self.keys = list(keys)
+        self.pooling = self._pooling_modes(pooling, self.keys)     # None: every bag has length one (lengths are not read)
+        if self.pooling is not None and not (embedding_dim % 4 == 0 and 4 <= embedding_dim <= 256):
+            raise ValueError(f"bag mode (pooling=...) needs embedding_dim to be a multiple of 4 in [4, 256], got {embedding_dim}: the "
+                             "pooled lookup moves rows in 16-byte pieces and has no scalar form")
         self.materialize = materialize
         self.embedding_dim = embedding_dim
         self.device_str = str(device or "cuda:0")
@@ -239,7 +254,37 @@ class CategoricalEmbedder(nn.Module):
         self.register_buffer("_key_row_offset", torch.tensor(offs, dtype=torch.int64, device=dev), persistent=False)
         self.register_buffer("_key_vocab", torch.tensor([self.vocab_sizes[k] for k in self.keys], dtype=torch.int64,
                                                         device=dev), persistent=False)
+        if self.pooling is not None:
+            self.register_buffer("_key_pool", torch.tensor([ops.POOL_MODES[m] for m in self.pooling], dtype=torch.int32, device=dev),
+                                 persistent=False)
         self._bound_version = self.store.version
+
+    @staticmethod
+    def _pooling_modes(pooling, keys):
+        """pooling: None | "sum" | "mean" | {key: "sum" | "mean"} (keys the dict leaves out sum) -> per-key modes, or None"""
+        if pooling is None:
+            return None
+        if isinstance(pooling, str):
+            modes = [pooling] * len(keys)
+        elif isinstance(pooling, dict):
+            unknown = [k for k in pooling if k not in keys]
+            if unknown:
+                raise ValueError(f"pooling names keys this embedder does not have: {unknown}")
+            modes = [pooling.get(k, "sum") for k in keys]
+        else:
+            raise TypeError(f"pooling must be None, 'sum', 'mean' or a dict of them, got {type(pooling).__name__}")
+        bad = [m for m in modes if m not in ops.POOL_MODES]
+        if bad:
+            raise ValueError(f"pooling modes must be 'sum' or 'mean', got {bad[0]!r}")
+        return modes
+
+    @property
+    def bag_mode(self) -> bool:
+        return self.pooling is not None
+
+    def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor) -> ops.BagSide:
+        return ops.BagSide(values, lengths, self._key_row_offset, self._key_vocab, self._key_pool, out_view, len(self.keys),
+                           any(m == "mean" for m in self.pooling))
 
     # ---- vocab sizes: src/towers/cat_embed.py:50-85 -------------------------------------------
     def _extract_vocab_sizes(self, metadata_path, table_name: str, keys: List[str]) -> Dict[str, int]:
@@ -296,6 +341,7 @@ class CategoricalEmbedder(nn.Module):
         dev = self.store.device
         self._key_row_offset = torch.tensor(offs, dtype=torch.int64, device=dev)
         self._key_vocab = self._key_vocab.to(dev)
+        self._move_key_pool(dev)
         self._bound_version = self.store.version
         if self.store.grad is not None:
             self._bind_grads()
@@ -311,6 +357,7 @@ class CategoricalEmbedder(nn.Module):
         if not self.materialize:
             dev = fn(torch.empty(0, device=self._key_vocab.device)).device
             self._key_row_offset, self._key_vocab = self._key_row_offset.to(dev), self._key_vocab.to(dev)
+            self._move_key_pool(dev)
             self.store.device = dev
             return self
         # move the fused storage ONCE, then re-point the per-key views (keeps Parameter identity, so
@@ -321,7 +368,13 @@ class CategoricalEmbedder(nn.Module):
                 s_member._rebind()
         self._key_row_offset = self._key_row_offset.to(self.store.device)
         self._key_vocab = self._key_vocab.to(self.store.device)
+        self._move_key_pool(self.store.device)
         return self
+
+    def _move_key_pool(self, dev):
+        """(bag mode) the per-key pooling modes are part of the key directory: they move with it"""
+        if self.pooling is not None:
+            self._key_pool = self._key_pool.to(dev)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         return super().load_state_dict(state_dict, strict=strict, assign=False)   # copy through the views
@@ -339,7 +392,10 @@ class CategoricalEmbedder(nn.Module):
                 return {k: torch.zeros(1, E, device=dev) for k in self.keys}
             return torch.zeros(1, K * E, device=dev)
         values = kjt.values()
-        cat = _LookupFn.apply(self, values, *self.table_parameters())
+        if self.bag_mode:
+            cat = _LookupFn.apply(self, (values, kjt.lengths()), *self.table_parameters())
+        else:
+            cat = _LookupFn.apply(self, values, *self.table_parameters())
         if not return_dict:
             return cat
         return {k: cat[:, i * E:(i + 1) * E] for i, k in enumerate(self.keys)}
@@ -349,8 +405,23 @@ class _LookupFn(torch.autograd.Function):
     """Stand-alone differentiable lookup (used when the embedder is called outside a tower)."""
 
     @staticmethod
-    def forward(ctx, emb: CategoricalEmbedder, values: torch.Tensor, *tables):
+    def forward(ctx, emb: CategoricalEmbedder, values, *tables):
         K, E = len(emb.keys), emb.embedding_dim
+        ctx.bag = None
+        if emb.bag_mode:                                                  # (values, lengths): pooled bags
+            values, lengths = values
+            dev = emb.store.device
+            values = values.to(device=dev, dtype=torch.int64).contiguous()
+            lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+            B = lengths.numel() // max(K, 1)
+            out = torch.empty((B, K * E), dtype=torch.float32, device=dev)
+            need_grad = any(ctx.needs_input_grad)
+            ctx.emb, ctx.B, ctx.plan = emb, B, None
+            if K and B:
+                bag = ops.embed_bag_lookup(emb.store.weight, [emb.bag_side(values, lengths[:B * K], out)], B, want_rows=need_grad)
+                if bag is not None and bag.nnz:
+                    ctx.bag, ctx.plan = bag, ops.dedup_plan(bag.rows, emb.store.rows)
+            return out
         values = values.to(device=emb.store.device, dtype=torch.int64).contiguous()
         B = values.numel() // max(K, 1)                                   # :98
         out = torch.empty((B, K * E), dtype=torch.float32, device=emb.store.device)
@@ -366,8 +437,25 @@ class _LookupFn(torch.autograd.Function):
         emb = ctx.emb
         if ctx.plan is not None:
             d_out = d_out.contiguous()
-            emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B, members=[emb])
+            emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B, members=[emb], bag=ctx.bag)
         return (None, None) + (None,) * len(emb.keys)
+
+
+def bag_mode_embedders(module) -> List[str]:
+    """Names of the embedders under `module` that pool ragged bags (empty: none, or `module` is no nn.Module)"""
+    if not isinstance(module, nn.Module):
+        return []
+    return [n or "embedder" for n, m in module.named_modules() if isinstance(m, CategoricalEmbedder) and m.bag_mode]
+
+
+def refuse_bag_mode(module: nn.Module, who: str) -> None:
+    """The paths that keep a step's ids in static B*K buffers (captured, unrolled, segmented and sharded steps, the store-fed
+    hand-over) call this: ValueError when an embedder under `module` pools ragged bags."""
+    names = bag_mode_embedders(module)
+    if names:
+        raise ValueError(f"{who} does not support bag mode (categorical_pooling / CategoricalEmbedder(pooling=...)): its static id "
+                         f"buffers hold exactly B*K ids, and {', '.join(names)} pool{'s' if len(names) == 1 else ''} bags of any "
+                         "length -- run such a model through the eager step")
 
 
 def create_categorical_embedder(keys: List[str], metadata_path="meta/metadata.csv", table_name: str = "notice",

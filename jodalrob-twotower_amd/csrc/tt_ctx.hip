@@ -218,12 +218,13 @@ int tt_ctx_check_device_errors(tt_ctx* ctx, tt_stream stream) {
   // chained launch on that stream would read as prefix sums
   TT_HIP(hipMemsetAsync(ctx->chain, 0, sizeof(uint32_t) * ((size_t)kChainWords * kChainSlices + 64), st));
   TT_HIP(hipStreamSynchronize(st));
-  tt_set_error("device error word 0x%x:%s%s%s the steps since the last check are invalid (they must be rejected)", word,
+  tt_set_error("device error word 0x%x:%s%s%s%s the steps since the last check are invalid (they must be rejected)", word,
                (word & TT_DEVERR_CHAIN_TIMEOUT) ? " a chained segment-head launch gave up waiting for a predecessor tile (tt_dedup_plan / tt_dedup_plan_runs);" : "",
                (word & TT_DEVERR_ROW_RANGE) ? " a lookup decoded rows outside its table (key offsets / vocabularies that belong to another table; tt_embed_lookup_fwd / "
                                               "tt_embed_lookup_rows_fwd / tt_batch_ingest_lookup) and read the last row instead;" : "",
                (word & TT_DEVERR_CELLS_PLAN) ? " tt_score_cells_plan counted more cells than its list's capacity (its counters were disturbed): the masks of "
-                                               "that step are not the list's;" : "");
+                                               "that step are not the list's;" : "",
+               (word & TT_DEVERR_BAG_OFFSETS) ? " tt_embed_bag_fwd met bag offsets that are negative, decreasing or end beyond nnz and treated those bags as empty;" : "");
   return TT_ERR_DEVICE;
 }
 

@@ -207,19 +207,7 @@ __device__ __forceinline__ void seg_reduce_body(const SideSet& a, const int32_t*
     const int32_t s0 = seg[u], s1 = seg[u + 1];
     if (PLANNED && s1 - s0 > kLongSeg) continue;
     if (!PLANNED && !all_short && s1 - s0 > kLongSeg) {
-      const int32_t nch = (s1 - s0 + kLongSeg - 1) / kLongSeg;
-      int32_t base = 0;
-      if (lig == 0) {
-        base = atomicAdd(&ws.counters[0], nch);
-        const int32_t li = atomicAdd(&ws.counters[1], 1);
-        ws.long_row[li] = (int32_t)u;
-        ws.long_base[li] = base;
-      }
-      base = __shfl(base, 0, (int)LG);                     // the group's lanes write the chunk list together
-      for (int32_t c = (int32_t)lig; c < nch; c += (int32_t)LG) {
-        ws.chunk_lo[base + c] = s0 + c * kLongSeg;
-        ws.chunk_hi[base + c] = min(s1, s0 + (c + 1) * kLongSeg);
-      }
+      register_long_row(ws, u, s0, s1, lig, LG);
       continue;
     }
     const int64_t orow = mode == TT_GRAD_SPARSE ? (int64_t)u : (int64_t)unique_rows[u];
@@ -327,11 +315,7 @@ __global__ __launch_bounds__(kThreads) void seg_long_finish_kernel(int32_t E, ui
   // next call -- a caller that keeps the words between calls needs no zeroing launch
   // (a "last workgroup done" atomic instead cost 35 us: 2048 same-address atomics with return serialise at ~17 ns each)
   if (RESET && blockIdx.x == 0 && threadIdx.x == 0) { ws.counters[0] = 0; ws.counters[1] = 0; }
-  long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x, gridDim.x, part, [&](int32_t u, int32_t col, float tot) {
-    const int64_t orow = mode == TT_GRAD_SPARSE ? (int64_t)u : (int64_t)unique_rows[u];
-    float* o = out + orow * E + col;
-    *o = mode == TT_GRAD_DENSE_ACC ? *o + tot : tot;
-  });
+  long_rows_finish_into<VEC>(E, C, seg, unique_rows, mode, out, ws, LG, part);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -446,7 +430,7 @@ int tt_embed_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int6
   a.total_slots = (uint32_t)slots;
   const int dt = srcs[0].dtype;
   // (before any launch: a refused call leaves the caller's counters and the plan's workspace as they were)
-  if ((int64_t)(kThreads / LG) * E > kFinishMaxFloats) {
+  if (!finish_fits(E, LG)) {
     tt_set_error("tt_embed_grad_bwd: E=%d too wide for the long-row finish (max %d)", E, kFinishMaxFloats * (int)LG / kThreads);
     return TT_ERR_UNSUPPORTED;
   }

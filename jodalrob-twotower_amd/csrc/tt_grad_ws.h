@@ -59,6 +59,25 @@ struct Acc {
   }
 };
 
+// A row of more than kLongSeg slots met by an unplanned row pass (tt_grad.hip's, tt_embed_bag.hip's): the row's lane group
+// enters it into the workspace's lists -- its chunks [s0 + c * kLongSeg, ...) are summed by a chunk pass, added up by
+// long_rows_finish.  Called by every lane of the group (lig = its lane in the group of LG).
+__device__ __forceinline__ void register_long_row(const GradWs& ws, uint32_t u, int32_t s0, int32_t s1, uint32_t lig, uint32_t LG) {
+  const int32_t nch = (s1 - s0 + kLongSeg - 1) / kLongSeg;
+  int32_t base = 0;
+  if (lig == 0) {
+    base = atomicAdd(&ws.counters[0], nch);
+    const int32_t li = atomicAdd(&ws.counters[1], 1);
+    ws.long_row[li] = (int32_t)u;
+    ws.long_base[li] = base;
+  }
+  base = __shfl(base, 0, (int)LG);                     // the group's lanes write the chunk list together
+  for (int32_t c = (int32_t)lig; c < nch; c += (int32_t)LG) {
+    ws.chunk_lo[base + c] = s0 + c * kLongSeg;
+    ws.chunk_hi[base + c] = min(s1, s0 + (c + 1) * kLongSeg);
+  }
+}
+
 // one WORKGROUP per long row: its lane groups sum contiguous ranges of the row's chunk partials (8 loads in flight,
 // chunk order), the group sums are added in group order through LDS -- one or two trips however long the row is
 // (a binary key at B = 8192 has ~4096-slot rows = 256 partials)
@@ -112,5 +131,21 @@ __device__ __forceinline__ void long_rows_finish(int32_t E, uint32_t C, const in
     done(u);     // (whatever it reads was written before the barrier above; the next row's emits follow the next barrier)
   }
 }
+
+// The finish kernels' body (tt_grad.hip's, tt_embed_bag.hip's): every long row's total into `out` in `mode` (TT_GRAD_*).
+// part: kFinishMaxFloats floats of LDS.
+template <int VEC>
+__device__ __forceinline__ void long_rows_finish_into(int32_t E, uint32_t C, const int32_t* __restrict__ seg,
+                                                      const int32_t* __restrict__ unique_rows, int32_t mode, float* __restrict__ out,
+                                                      const GradWs& ws, uint32_t LG, float* __restrict__ part) {
+  long_rows_finish<VEC>(E, C, seg, ws, LG, blockIdx.x, gridDim.x, part, [&](int32_t u, int32_t col, float tot) {
+    const int64_t orow = mode == TT_GRAD_SPARSE ? (int64_t)u : (int64_t)unique_rows[u];
+    float* o = out + orow * E + col;
+    *o = mode == TT_GRAD_DENSE_ACC ? *o + tot : tot;
+  });
+}
+
+// the widest row the finish's LDS holds for lane groups of LG: (kThreads / LG) * E floats
+inline bool finish_fits(int32_t E, uint32_t LG) { return (int64_t)(kThreads / LG) * E <= kFinishMaxFloats; }
 
 }  // namespace

@@ -46,6 +46,15 @@ class DeviceFeatureStore:
 NEGATIVE_SEED_OFFSET = 0x5851F42D                  # the extras' generator: the loader's seed plus this
 
 
+def _refuse_bag_mode_step(step, who: str) -> None:
+    """The store-fed hand-over writes B*K ids per side into a captured step's static buffers: a step whose task pools ragged
+    bags (bag mode) is refused before the epoch starts (once per epoch, not per batch)."""
+    task = getattr(step, "task", None)
+    if isinstance(task, torch.nn.Module):
+        from .cat_embed import refuse_bag_mode
+        refuse_bag_mode(task, who)
+
+
 class DevicePairLoader:
     """Iterates over (notice_idx, company_idx) pairs in batches; len() = number of batches (drop_last=False,
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
@@ -418,6 +427,7 @@ class DevicePairLoader:
         """One pass over the pairs in order (no shuffling is applied here: the reference's test loader does not shuffle) through a
         GraphedEvalStep: full batches from the stores, the ragged last one through `eager_eval(batch) -> metrics dict` (skipped
         when None).  Returns the number of batches evaluated; the sums sit in `graphed_eval`."""
+        _refuse_bag_mode_step(graphed_eval, "DevicePairLoader.eval_batches")
         n, B, done = self.pairs.shape[0], self.batch_size, 0
         order = self.epoch_order()
         for lo in range(0, n, B):
@@ -438,6 +448,8 @@ class DevicePairLoader:
         through `ragged_step` (a second GraphedTrainStep captured at the remainder's size, sharing task and optimiser) or, without
         one, through `eager_step(batch)` (skipped when None).  Yields the step's result dict per batch (an unrolled step's U results
         arrive together, after its one launch: read them before the next launch overwrites them)."""
+        for st in (graphed_step, ragged_step):
+            _refuse_bag_mode_step(st, "DevicePairLoader.step_batches")
         order = self.epoch_order()
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))

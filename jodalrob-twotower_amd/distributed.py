@@ -35,7 +35,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import ops
-from .cat_embed import EmbeddingStore
+from .cat_embed import EmbeddingStore, refuse_bag_mode
 from .two_tower_model import TwoTowerModel
 from .two_tower_train_task import TwoTowerTrainTask
 
@@ -514,6 +514,7 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
     def __init__(self, two_tower_model: TwoTowerModel, store: ShardedStore, group=None, backend=None, exchange: Optional[str] = None,
                  negatives: str = "local", sync_bn: bool = False, comm=None, **kw):
         super().__init__(two_tower_model, **kw)
+        refuse_bag_mode(two_tower_model, "the sharded exchange step (" + type(self).__name__ + ")")     # its id routing sends B*K ids
         if exchange is None:             # the fixed-capacity exchange wherever it applies (row-sparse table gradients)
             exchange = "padded" if store.grad_mode == "sparse" else "exact"
         if negatives not in ("local", "global"):

@@ -172,6 +172,9 @@ class TwoTowerEvaluator:
         full batch and the model is this package's task on a GPU; cached on the evaluator.  None: the batch-by-batch loop."""
         if not (hasattr(dataloader, "eval_batches") and hasattr(model, "forward_with_ranks") and getattr(model, "exchange", None) is None):
             return None
+        from .cat_embed import bag_mode_embedders
+        if bag_mode_embedders(model):                        # ragged bags do not fit a captured pass's static id buffers: batch by batch
+            return None
         B = dataloader.batch_size
         if dataloader.pairs.shape[0] < B or dataloader.shuffle or not dataloader.pairs.is_cuda:
             return None

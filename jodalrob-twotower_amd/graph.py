@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .cat_embed import refuse_bag_mode
 from .config import settings
 from .kjt import KeyedJaggedTensor
 from .optim import FusedAdam
@@ -101,6 +102,9 @@ class GraphedTrainStep:
             raise ValueError("cell_capacity: the example batch carries no 'masked_cells'")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
+        # the static id buffers hold B*K ids: no ragged bags in a captured step -- refused here, once, so that step() and
+        # step_from_store() of a bag-mode model cannot be reached (and pay no check per step)
+        refuse_bag_mode(task, type(self).__name__)
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
         self._defer_long, self._defer_slabs, self._defer_riders = bool(defer_long), bool(defer_slabs), bool(defer_riders)
         self._fuse_score_tail = bool(fuse_score_tail)
@@ -745,6 +749,7 @@ class GraphedEvalStep:
     KEYS = ("loss", "accuracy", "similarity_gap", "positive_similarity_mean", "negative_similarity_mean", "recall@5", "recall@10", "mrr")
 
     def __init__(self, task, example_batch: Dict, warmup: int = 2):
+        refuse_bag_mode(task, type(self).__name__)
         self.task = task
         dev = example_batch["notice"]["dense"].device
         self.static = {side: {"dense": example_batch[side]["dense"].clone(),

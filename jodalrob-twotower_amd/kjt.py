@@ -49,6 +49,37 @@ class KeyedJaggedTensor:
         return f"KeyedJaggedTensor(keys={len(self._keys)}, values={tuple(self._values.shape)}, device={self._values.device})"
 
 
+def build_bag_kjt(categorical_keys: List[str], bags=None, values: torch.Tensor | None = None,
+                  lengths: torch.Tensor | None = None, device=None) -> KeyedJaggedTensor:
+    """A KJT of multi-valued features in the sample-major wire format: lengths()[b*K + k] = length of bag (b, k) (0 allowed),
+    values() = all bags' ids concatenated in that slot order.  Either `bags` -- per sample, per key, the list of ids
+    (bags[b][k]) -- or a (values [nnz], lengths [B*K]) pair.  With every length 1 this is build_batch_kjt's format."""
+    K = len(categorical_keys)
+    if (bags is None) == (values is None or lengths is None):
+        raise ValueError("build_bag_kjt takes either `bags` or both `values` and `lengths`")
+    if bags is not None:
+        if any(len(row) != K for row in bags):
+            raise ValueError(f"every sample needs one id list per key ({K} keys)")
+        lengths = torch.tensor([len(bag) for row in bags for bag in row], dtype=torch.long)
+        values = torch.tensor([int(i) for row in bags for bag in row for i in bag], dtype=torch.long)
+    else:
+        values, lengths = values.reshape(-1).to(torch.long), lengths.reshape(-1).to(torch.long)
+        if K == 0 or lengths.numel() % K != 0:
+            raise ValueError(f"{lengths.numel()} bag lengths do not divide into {K} keys")
+    if device is not None:
+        values, lengths = values.to(device), lengths.to(device)
+    return KeyedJaggedTensor(categorical_keys, values, lengths)
+
+
+def concat_kjt(a: KeyedJaggedTensor, b: KeyedJaggedTensor) -> KeyedJaggedTensor:
+    """The samples of `a` followed by the samples of `b` (same keys): values and lengths are both sample-major, so both
+    concatenate as they are."""
+    if list(a.keys()) != list(b.keys()):
+        raise ValueError("concat_kjt needs two KJTs over the same keys")
+    return KeyedJaggedTensor(list(a.keys()), torch.cat([a.values(), b.values().to(a.values().device)]),
+                             torch.cat([a.lengths(), b.lengths().to(a.lengths().device)]))
+
+
 def build_batch_kjt(categorical_data: torch.Tensor, categorical_keys: List[str]) -> KeyedJaggedTensor:
     """[B,K] ids -> KJT, the wire format of _build_batch_kjt (unified_bid_data_loader.py:827-841)."""
     b, k = categorical_data.shape

@@ -289,6 +289,103 @@ def embed_grad_finish(plan: DedupPlan):
     plan.finish_deferred = None
 
 
+# ---------------------------------------------------------------------------------------------- embedding bags
+POOL_MODES = {"sum": L.TT_POOL_SUM, "mean": L.TT_POOL_MEAN}
+
+
+@dataclass
+class BagSide:
+    ids: torch.Tensor             # int64 [nnz]: the bags' ids, concatenated in slot order (slot = b*K + k)
+    lengths: torch.Tensor         # int64 [B*K] (device): length of bag (b, k); 0 allowed
+    key_row_offset: torch.Tensor  # int64 [K] (device)
+    key_vocab: torch.Tensor       # int64 [K] (device)
+    key_pool: torch.Tensor        # int32 [K] (device): TT_POOL_SUM / TT_POOL_MEAN
+    out: torch.Tensor             # 2-D view [B, K*E] inside the destination buffer (row stride = ld)
+    K: int
+    any_mean: bool = True         # host copy of (key_pool == mean).any(): with no mean key the gradient needs no weights
+
+
+class BagPlan(NamedTuple):
+    """What embed_bag_lookup leaves for embed_bag_grad: rows / bag_of per position (int32 [nnz]), inv_len per slot (f32, None when
+    every key sums), nnz."""
+    rows: torch.Tensor
+    bag_of: torch.Tensor
+    inv_len: Optional[torch.Tensor]
+    nnz: int
+
+
+def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want_rows: bool) -> Optional[BagPlan]:
+    """tt_embed_bag_fwd: pooled lookup of every side's bags into side.out.  The offsets are torch.cumsum of the lengths and the
+    mean weights 1 / length, both formed on the device: no host synchronisation.  sum(lengths) must equal ids.numel() (ids the
+    lengths leave over belong to no bag; lengths that ask for more raise the context's device error word)."""
+    dev, E = table.device, table.shape[1]
+    if table.dtype != torch.float32 or not table.is_contiguous():
+        raise ValueError("the table must be a contiguous float32 [rows, E] tensor")
+    arr = (L.BagSide * len(sides))()
+    keep, nnz, inv = [], 0, []
+    for i, s in enumerate(sides):
+        if s.ids.dtype != torch.int64 or not s.ids.is_contiguous() or s.ids.device != dev:
+            raise ValueError("bag ids must be a contiguous int64 tensor on the table's device")
+        if s.lengths.numel() != B * s.K or s.lengths.device != dev:
+            raise ValueError(f"side {i}: {s.lengths.numel()} bag lengths for B={B}, K={s.K} (on the table's device)")
+        for name, t, dt, n in (("key_row_offset", s.key_row_offset, torch.int64, s.K), ("key_vocab", s.key_vocab, torch.int64, s.K),
+                               ("key_pool", s.key_pool, torch.int32, s.K)):
+            if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"side {i}: {name} must be a contiguous {dt} tensor of {n} elements on the table's device")
+        if s.out.device != dev or s.out.dim() != 2 or s.out.shape[0] != B or s.out.shape[1] != s.K * E:
+            raise ValueError(f"side {i}: out must be a [B, K*E] = [{B}, {s.K * E}] view on the table's device")
+        assert s.out.stride(1) == 1
+        lengths = s.lengths.to(torch.int64).reshape(-1)
+        off = torch.zeros(B * s.K + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lengths, 0, out=off[1:])
+        keep.append(off)
+        arr[i] = L.BagSide(L.ptr(s.ids), L.ptr(off), L.ptr(s.key_row_offset), L.ptr(s.key_vocab), L.ptr(s.key_pool), L.ptr(s.out),
+                           s.out.stride(0), s.ids.numel(), s.K, _dt(s.out))
+        nnz += s.ids.numel()
+        if want_rows:
+            lf = lengths.to(torch.float32)
+            mean = (s.key_pool != 0).repeat(B) & (lengths > 0)
+            one = torch.ones_like(lf)
+            inv.append(torch.where(mean, one / lf.clamp(min=1.0), one))        # fl(1 / L): one correctly rounded f32 division
+    # zero-filled: a position no bag covers (offsets the kernel refused) then names row 0 / slot 0 instead of stale memory
+    idx = torch.zeros((2, max(nnz, 1)), dtype=torch.int32, device=dev) if want_rows else None
+    with _timed("tt_embed_bag_fwd"):
+        L.check(L.load().tt_embed_bag_fwd(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                          L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
+                "tt_embed_bag_fwd")
+    if not want_rows:
+        return None
+    inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
+    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz)
+
+
+def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int, E: int, mode: int, out: torch.Tensor):
+    """tt_embed_bag_grad_bwd.  plan: dedup_plan(bag.rows, table_rows) (M = nnz); srcs: [(d_out 2-D view [B, K*E], K)] in the
+    sides' order; mode: TT_GRAD_SPARSE / TT_GRAD_DENSE_SET / TT_GRAD_DENSE_ACC."""
+    dev = out.device
+    if plan.M != bag.nnz:
+        raise ValueError(f"the plan covers {plan.M} positions, the bags {bag.nnz}")
+    slots = sum(B * K for _, K in srcs)
+    if bag.inv_len is not None and (bag.inv_len.numel() != slots or bag.inv_len.dtype != torch.float32 or bag.inv_len.device != dev):
+        raise ValueError(f"inv_len must hold one float32 per slot ({slots}) on the output's device")
+    if out.dim() != 2 or out.shape[1] != E or out.dtype != torch.float32 or not out.is_contiguous() or \
+            (mode == TT_GRAD_SPARSE and out.shape[0] < max(bag.nnz, 1)):
+        raise ValueError("out must be a contiguous float32 [rows, E] tensor (sparse mode: room for nnz rows)")
+    for d, K in srcs:
+        if d.device != dev or d.dim() != 2 or d.shape[0] != B or d.shape[1] != K * E:
+            raise ValueError(f"every source must be a [B, K*E] view on the output's device, got {tuple(d.shape)} for K={K}")
+    arr = (L.GradSrc * len(srcs))()
+    for i, (d, K) in enumerate(srcs):
+        assert d.stride(1) == 1
+        arr[i] = L.GradSrc(L.ptr(d), d.stride(0), K, _dt(d))
+    lib = L.load()
+    ws = L.workspace(dev, lib.tt_embed_bag_grad_workspace_bytes(bag.nnz, E))
+    with _timed("tt_embed_bag_grad_bwd"):
+        L.check(lib.tt_embed_bag_grad_bwd(L.ctx(dev), arr, len(srcs), B, E, L.ptr(bag.bag_of), L.ptr(bag.inv_len), L.ptr(plan.sorted_src),
+                                          L.ptr(plan.seg_offsets), L.ptr(plan.unique_rows), L.ptr(plan.n_unique), bag.nnz, mode,
+                                          L.ptr(out), L.ptr(ws), ws.numel(), L.stream(dev)), "tt_embed_bag_grad_bwd")
+
+
 # ---------------------------------------------------------------------------------------------- Adam
 def adam_dense(p, g, m, v, step, lr, b1, b2, eps, wd, hp_dev=None):
     dev = p.device

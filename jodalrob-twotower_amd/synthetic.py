@@ -44,9 +44,10 @@ def load_real_schema(path) -> dict:
 
 
 def make_batch(B: int, vocab_n: Sequence[int], vocab_c: Sequence[int], keys_n, keys_c, din_n: int, din_c: int, device,
-               seed: int, zipf_alpha: Optional[float] = None) -> dict:
+               seed: int, zipf_alpha: Optional[float] = None, bag_keys=None, mean_bag_length: float = 4.0) -> dict:
     """ids ~ U[0, V_k) per key (or Zipf(alpha) ranks mapped through a fixed multiplicative hash), dense
-    ~ N(0,1); generated on the device with a seeded generator (plumbing only)."""
+    ~ N(0,1); generated on the device with a seeded generator (plumbing only).  bag_keys: names of keys (either side) that get
+    ragged multi-valued bags of about mean_bag_length ids instead of one id (ragged_bags): input for a bag-mode model."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
 
@@ -66,8 +67,35 @@ def make_batch(B: int, vocab_n: Sequence[int], vocab_c: Sequence[int], keys_n, k
     def dense(d):
         return torch.randn((B, d), generator=g, device=device, dtype=torch.float32)
 
-    return {"notice": {"dense": dense(din_n), "kjt": KeyedJaggedTensor(list(keys_n), ids_for(vocab_n))},
-            "company": {"dense": dense(din_c), "kjt": KeyedJaggedTensor(list(keys_c), ids_for(vocab_c))}}
+    batch = {"notice": {"dense": dense(din_n), "kjt": KeyedJaggedTensor(list(keys_n), ids_for(vocab_n))},
+             "company": {"dense": dense(din_c), "kjt": KeyedJaggedTensor(list(keys_c), ids_for(vocab_c))}}
+    if bag_keys:       # (drawn from a generator of their own: the length-one ids and the dense features are the plain batch's)
+        for i, (side, vocabs) in enumerate((("notice", vocab_n), ("company", vocab_c))):
+            batch[side]["kjt"] = ragged_bags(batch[side]["kjt"], vocabs, bag_keys, mean_bag_length, seed + 7919 * (i + 1))
+    return batch
+
+
+def ragged_bags(kjt: KeyedJaggedTensor, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0) -> KeyedJaggedTensor:
+    """The length-one `kjt` with the keys named in `bag_keys` turned into ragged bags: a Poisson(mean_length) number of ids per bag
+    (empty bags included), the first one the kjt's own id, the others ~ U[0, V_k).  Keys not named keep their one id.  Returns
+    the sample-major wire format (kjt.build_bag_kjt): lengths [B*K], values = all bags concatenated in slot order."""
+    keys = list(kjt.keys())
+    K = len(keys)
+    first = kjt.values().reshape(-1, K)
+    dev, B = first.device, first.shape[0]
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    chosen = torch.tensor([k in bag_keys for k in keys], device=dev)
+    lengths = torch.where(chosen[None, :], torch.poisson(torch.full((B, K), float(mean_length), device=dev), generator=g).to(torch.int64),
+                          torch.ones((B, K), dtype=torch.int64, device=dev)).reshape(-1)
+    nnz = int(lengths.sum())                                   # (data generation: a host read is fine here)
+    slot = torch.repeat_interleave(torch.arange(B * K, device=dev), lengths)
+    v = torch.tensor(list(vocabs), dtype=torch.int64, device=dev)[slot % K]
+    values = (torch.rand(nnz, generator=g, device=dev, dtype=torch.float64) * v).to(torch.int64).clamp_(max=v - 1)
+    starts = torch.cumsum(lengths, 0) - lengths
+    has = lengths > 0
+    values[starts[has]] = first.reshape(-1)[has]
+    return KeyedJaggedTensor(keys, values, lengths)
 
 
 class SyntheticSource:

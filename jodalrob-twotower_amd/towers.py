@@ -133,10 +133,14 @@ class BaseTower(nn.Module):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 256,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None):
+                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
         super().__init__()
         if tower_hidden_dims is None:
             tower_hidden_dims = [256, 128]
+        if categorical_pooling is not None and tower_hidden_dims[0] % 4 != 0:
+            # the pooled block starts at column tower_hidden_dims[0] of the tower input and is written in 16-byte pieces (the pooled
+            # lookup has no scalar form, unlike the plain one); the embedder checks embedding_dim itself
+            raise ValueError(f"bag mode (categorical_pooling=...) needs tower_hidden_dims[0] to be a multiple of 4, got {tower_hidden_dims[0]}")
         self.mlp_dtype = mlp_dtype or settings.mlp_dtype
         if self.mlp_dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp_dtype must be 'fp32' or 'bf16', got {self.mlp_dtype!r}")
@@ -171,7 +175,7 @@ class BaseTower(nn.Module):
         self.categorical_embedder = CategoricalEmbedder(keys=self.categorical_keys, metadata_path=metadata_path,
                                                         table_name=table_name, embedding_dim=categorical_embedding_dim,
                                                         device=str(dev), embedding_grad=embedding_grad,
-                                                        materialize=materialize_tables)
+                                                        materialize=materialize_tables, pooling=categorical_pooling)
         self.dense_projection = nn.Linear(dense_input_dim, tower_hidden_dims[0])
         self._build_mlp(categorical_embedding_dim, tower_hidden_dims, final_embedding_dim, dropout_rate)
         self._struct_key = None
@@ -246,12 +250,12 @@ class NoticeTower(BaseTower):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 256,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None):
+                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
         super().__init__(categorical_keys=categorical_keys, metadata_path=metadata_path, table_name="notice",
                          categorical_embedding_dim=categorical_embedding_dim, dense_input_dim=dense_input_dim,
                          tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim,
                          dropout_rate=dropout_rate, device=device, embedding_grad=embedding_grad,
-                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype)
+                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
 
 
 class CompanyTower(BaseTower):
@@ -259,26 +263,29 @@ class CompanyTower(BaseTower):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 128,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None):
+                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
         super().__init__(categorical_keys=categorical_keys, metadata_path=metadata_path, table_name="company",
                          categorical_embedding_dim=categorical_embedding_dim, dense_input_dim=dense_input_dim,
                          tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim,
                          dropout_rate=dropout_rate, device=device, embedding_grad=embedding_grad,
-                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype)
+                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
 
 
 # --------------------------------------------------------------------------------------------------
 # one autograd node for >= 1 towers (lookup and table gradient fused across towers that share a store)
 # --------------------------------------------------------------------------------------------------
 def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torch.Tensor]:
-    flat = []
+    flat, bag_lengths = [], []
     for tw, inp in zip(towers, inputs):
         dev = tw.categorical_embedder.store.device
         dense = inp["dense"].to(dev)
         kjt = inp["kjt"]
-        values = (kjt.to(dev) if hasattr(kjt, "to") else kjt).values()
+        kjt = kjt.to(dev) if hasattr(kjt, "to") else kjt
+        values = kjt.values()
+        # a bag-mode embedder also reads the bags' lengths; any other reads the values only, as before
+        bag_lengths.append(kjt.lengths() if tw.categorical_embedder.bag_mode else None)
         flat += [dense, values] + tw.dense_parameters() + tw.categorical_embedder.table_parameters()
-    outs = _TowersFn.apply(tuple(towers), *flat)
+    outs = _TowersFn.apply(tuple(towers), tuple(bag_lengths), *flat)
     outs = list(outs) if isinstance(outs, tuple) else [outs]
     for tw, o in zip(towers, outs):                      # hand the packed images to the score step with the rows they belong to
         if tw._last_packed is not None:
@@ -287,18 +294,23 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
 
 
 class _Side:
-    __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values")
+    __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values",
+                 "lengths")
 
 
 class _TowersFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, towers, *flat):
+    def forward(ctx, towers, bag_lengths, *flat):
+        """bag_lengths: per tower, the KJT's lengths() for a bag-mode embedder, None for any other (its lengths are not read)"""
+        if len(bag_lengths) != len(towers):
+            raise ValueError(f"{len(towers)} towers but {len(bag_lengths)} bag-length entries")
         sides: List[_Side] = []
         pos = 0
         grad_on = any(ctx.needs_input_grad)       # (grad mode is always off inside Function.forward)
         spans = []
         lookups: Dict[int, list] = {}
-        for tw in towers:
+        bag_lookups: Dict[tuple, list] = {}      # (store, batch size) -> [(side, ops.BagSide)]
+        for tw, lengths in zip(towers, bag_lengths):
             emb = tw.categorical_embedder
             nd, nt = len(tw.dense_parameters()), len(emb.table_parameters())
             dense, values = flat[pos], flat[pos + 1]
@@ -310,9 +322,17 @@ class _TowersFn(torch.autograd.Function):
             dense = dense.to(dtype=torch.float32).contiguous()
             values = values.to(dtype=torch.int64).contiguous()
             B, K, E = dense.shape[0], len(emb.keys), emb.embedding_dim
-            if values.numel() != B * K:
+            if emb.bag_mode:
+                if lengths is None or lengths.numel() != B * K:
+                    raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
+                                     f"{'none' if lengths is None else lengths.numel()}")
+                if tw.exchange is not None:
+                    raise ValueError("bag mode (categorical_pooling) is not supported with the sharded table exchange")
+                lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+            elif values.numel() != B * K:
                 raise ValueError(f"kjt carries {values.numel()} ids but the batch needs B*K = {B}*{K}")
             s = _Side()
+            s.lengths = lengths if emb.bag_mode else None
             s.tower, s.B, s.train = tw, B, tw.training
             s.p_drop = tw.dropout_rate if tw.training else 0.0
             s.seed = 0 if s.p_drop <= 0 else (tw._seed_override if tw._seed_override is not None else
@@ -327,7 +347,7 @@ class _TowersFn(torch.autograd.Function):
             by_store: Dict[int, list] = {}
             for s in sides:
                 emb = s.tower.categorical_embedder
-                if s.B and len(emb.keys):
+                if s.B and len(emb.keys) and not emb.bag_mode:
                     by_store.setdefault(id(emb.store), []).append(s)
             for group in by_store.values():
                 st = group[0].tower.categorical_embedder.store
@@ -369,7 +389,9 @@ class _TowersFn(torch.autograd.Function):
                 s.packed = torch.empty(L.load().tt_score_pack_bytes(B, tw.final_embedding_dim), dtype=torch.uint8, device=dev)
                 a.emb_packed, a.emb_pack_scale = s.packed.data_ptr(), float(tw.pack_scale)
             s.acts_struct = a
-            if K and B:
+            if K and B and emb.bag_mode:     # pooled bags: launches and plans of their own, beside the plain sides of the store
+                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:])))
+            elif K and B:
                 lookups.setdefault(id(emb.store), []).append((s, emb.lookup_side(values, s.x[:, tw.tower_hidden_dims[0]:]), px is not None))
         # fused lookup (+ duplicate-row plan when a backward will follow) per store
         plans = []
@@ -404,6 +426,15 @@ class _TowersFn(torch.autograd.Function):
             else:
                 rows = ops.embed_lookup(store.weight, [g[1] for g in group], B, want_rows=grad_on and km is None)
             plans.append([store, [g[0] for g in group], None, rows if km is None else km, grad_on, km is not None])
+        # pooled bags: one launch per (store, batch size) writes the pooled block straight into x[:, h0:]; the general plan over the
+        # positions' rows (M = nnz: the keyed plans sort B ids per key, a bag-mode key holds any number)
+        bag_plans = []
+        for group in bag_lookups.values():
+            store = group[0][0].tower.categorical_embedder.store
+            bag = ops.embed_bag_lookup(store.weight, [g[1] for g in group], group[0][0].B, want_rows=grad_on)
+            if bag is not None and bag.nnz:
+                bag_plans.append((store, [g[0] for g in group], ops.dedup_plan(bag.rows, store.rows), bag))
+        ctx.bag_plans = bag_plans
         # duplicate-row plans: depend on ids only, first needed in the backward.  In line on the launch stream (a side stream
         # overlapped the sort with the score kernels, but a captured graph with two streams is replayed node by node with
         # cross-queue signals: 4-6 us gaps in front of eight kernels -- as much as the overlap saved), and BEFORE the towers'
@@ -525,7 +556,16 @@ class _TowersFn(torch.autograd.Function):
             # (filed under the sides' embedders: the per-side plans of a pass with unequal batch sizes, or of two passes over one
             # store, each keep their gradient until the optimiser steps)
             store.accumulate_grad(plan, srcs, plan_sides[0].B, members=[s.tower.categorical_embedder for s in plan_sides])
-        return (None, *grads)
+        for store, plan_sides, plan, bag in ctx.bag_plans:      # the bag-mode sides: reduced from d_x[:, h0:] in dx_dtype through bag_of
+            srcs = []
+            for s in plan_sides:
+                K = len(s.tower.categorical_embedder.keys)
+                d = dxs.get(id(s))
+                if d is None:
+                    d = torch.zeros((s.B, K * store.E), dtype=s.tower.dx_dtype, device=store.device)
+                srcs.append((d, K))
+            store.accumulate_grad(plan, srcs, plan_sides[0].B, members=[s.tower.categorical_embedder for s in plan_sides], bag=bag)
+        return (None, None, *grads)
 
 
 def tower_dense_param_names(n_hidden: int) -> List[str]:

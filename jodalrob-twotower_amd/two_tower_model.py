@@ -84,18 +84,39 @@ class _SimilarityFn(torch.autograd.Function):
         return dN, dC, None
 
 
+def _tower_pooling(spec, notice_keys, company_keys):
+    """create_two_tower_model's categorical_pooling -> (notice tower's pooling, company tower's)"""
+    if spec is None or isinstance(spec, str):
+        return spec, spec
+    if not isinstance(spec, dict):
+        raise TypeError(f"categorical_pooling must be None, 'sum', 'mean' or a dict, got {type(spec).__name__}")
+    if spec and set(spec) <= {"notice", "company"}:
+        return spec.get("notice"), spec.get("company")
+    unknown = [k for k in spec if k not in notice_keys and k not in company_keys]
+    if unknown:
+        raise ValueError(f"categorical_pooling names keys neither tower has: {unknown}")
+    pick = lambda keys: ({k: m for k, m in spec.items() if k in keys} or None)
+    return pick(notice_keys), pick(company_keys)
+
+
 def create_two_tower_model(notice_categorical_keys: List[str], company_categorical_keys: List[str],
                            metadata_path: str = "meta/metadata.csv", categorical_embedding_dim: int = 64,
                            notice_dense_input_dim: int = 256, company_dense_input_dim: int = 128,
                            tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128,
                            dropout_rate: float = 0.2, device="cuda:0", embedding_grad: Optional[str] = None,
-                           mlp_dtype: Optional[str] = None) -> TwoTowerModel:
+                           mlp_dtype: Optional[str] = None, categorical_pooling=None) -> TwoTowerModel:
+    """categorical_pooling: None (every bag has length one: lengths are not read), or what puts a tower's embedder in bag mode
+    (CategoricalEmbedder(pooling=...)): "sum" / "mean" for both towers, {"notice": spec, "company": spec} per tower (a tower left
+    out stays plain), or a {key: "sum" | "mean"} dict, of which each tower takes the entries that name its keys."""
     if tower_hidden_dims is None:
         tower_hidden_dims = [256, 128]
+    pool_n, pool_c = _tower_pooling(categorical_pooling, notice_categorical_keys, company_categorical_keys)
     common = dict(metadata_path=metadata_path, categorical_embedding_dim=categorical_embedding_dim,
                   tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim, dropout_rate=dropout_rate,
                   device=device, embedding_grad=embedding_grad, mlp_dtype=mlp_dtype)
     return TwoTowerModel(
-        notice_tower_config=dict(categorical_keys=notice_categorical_keys, dense_input_dim=notice_dense_input_dim, **common),
-        company_tower_config=dict(categorical_keys=company_categorical_keys, dense_input_dim=company_dense_input_dim, **common),
+        notice_tower_config=dict(categorical_keys=notice_categorical_keys, dense_input_dim=notice_dense_input_dim,
+                                 categorical_pooling=pool_n, **common),
+        company_tower_config=dict(categorical_keys=company_categorical_keys, dense_input_dim=company_dense_input_dim,
+                                  categorical_pooling=pool_c, **common),
         final_embedding_dim=final_embedding_dim, device=device)

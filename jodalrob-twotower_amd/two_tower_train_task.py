@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import ops
 from .config import settings
-from .kjt import KeyedJaggedTensor
+from .kjt import KeyedJaggedTensor, concat_kjt
 from .towers import run_towers
 from .two_tower_model import TwoTowerModel, create_two_tower_model
 
@@ -495,8 +495,11 @@ class TwoTowerTrainTask(nn.Module):
         """(notice embeddings, company embeddings, loss, out8) of a batch with shared extra negatives: the M rows ride behind the batch's
         companies through ONE company-tower pass (in train mode its BatchNorm batch statistics run over the B + M rows), the output is
         split into C and X, and the score node takes X as M more columns of every notice's row-direction softmax"""
-        both = {"dense": torch.cat([company_input["dense"], neg["dense"]], 0),
-                "kjt": KeyedJaggedTensor(company_input["kjt"].keys(), torch.cat([company_input["kjt"].values(), neg["kjt"].values()], 0))}
+        if self.two_tower_model.company_tower.categorical_embedder.bag_mode:      # ragged bags: the lengths ride along
+            kjt = concat_kjt(company_input["kjt"], neg["kjt"])
+        else:
+            kjt = KeyedJaggedTensor(company_input["kjt"].keys(), torch.cat([company_input["kjt"].values(), neg["kjt"].values()], 0))
+        both = {"dense": torch.cat([company_input["dense"], neg["dense"]], 0), "kjt": kjt}
         n_emb, cx = run_towers([self.two_tower_model.notice_tower, self.two_tower_model.company_tower], [notice_input, both])
         c_emb, x_emb = cx[:B], cx[B:]
         lqs, ents = lq if lq is not None else (None, None), ent if ent is not None else (None, None)
@@ -536,7 +539,9 @@ class TwoTowerTrainTask(nn.Module):
             raise ValueError(f"batch['negatives']['dense'] is on {d.device}, the batch on {ref.device}")
         K = len(company_input["kjt"].keys())
         v = neg["kjt"].values()
-        if list(neg["kjt"].keys()) != list(company_input["kjt"].keys()) or v.numel() != M * K or v.device != ref.device:
+        # (a bag-mode company tower reads M * K bag lengths; the number of ids is then free)
+        n_slots = neg["kjt"].lengths().numel() if self.two_tower_model.company_tower.categorical_embedder.bag_mode else v.numel()
+        if list(neg["kjt"].keys()) != list(company_input["kjt"].keys()) or n_slots != M * K or v.device != ref.device:
             raise ValueError(f"batch['negatives']['kjt'] must carry the company side's {K} keys for {M} rows on {ref.device}")
         for name, dt, given in (("log_q", torch.float32, lq is not None), ("entity", torch.int32, ent is not None and ent[1] is not None)):
             t = neg.get(name)
@@ -652,12 +657,13 @@ def create_two_tower_train_task(notice_categorical_keys, company_categorical_key
                                 categorical_embedding_dim: int = 64, notice_dense_input_dim: int = 256,
                                 company_dense_input_dim: int = 128, tower_hidden_dims=None, final_embedding_dim: int = 128,
                                 dropout_rate: float = 0.2, temperature: float = 1.0, loss_type: str = "cross_entropy",
-                                device="cuda:0", embedding_grad=None, score_dtype=None, mlp_dtype=None) -> TwoTowerTrainTask:
+                                device="cuda:0", embedding_grad=None, score_dtype=None, mlp_dtype=None,
+                                categorical_pooling=None) -> TwoTowerTrainTask:
     model = create_two_tower_model(notice_categorical_keys=notice_categorical_keys,
                                    company_categorical_keys=company_categorical_keys, metadata_path=metadata_path,
                                    categorical_embedding_dim=categorical_embedding_dim,
                                    notice_dense_input_dim=notice_dense_input_dim,
                                    company_dense_input_dim=company_dense_input_dim, tower_hidden_dims=tower_hidden_dims,
                                    final_embedding_dim=final_embedding_dim, dropout_rate=dropout_rate, device=device,
-                                   embedding_grad=embedding_grad, mlp_dtype=mlp_dtype)
+                                   embedding_grad=embedding_grad, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
     return TwoTowerTrainTask(two_tower_model=model, temperature=temperature, loss_type=loss_type, score_dtype=score_dtype)

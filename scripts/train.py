@@ -135,7 +135,22 @@ def main():
                     help="score ceiling A * s_min + B, s_min the lowest score of the notice's known companies")
     ap.add_argument("--hard-fraction", type=float, default=1.0, metavar="F", help="share of the M extras drawn from the mined rows")
     ap.add_argument("--results-csv", default="train_results.csv", help="the results CSV (reference: train_results.csv in the working directory)")
+    ap.add_argument("--pool", nargs="+", default=None, metavar="KEY=MODE",
+                    help="multi-valued categorical features: the named keys (either tower) hold ragged bags of ids pooled by MODE = sum | "
+                         "mean (bag mode; eager loop only).  The synthetic stores hold one id per key: every training batch draws "
+                         "--pool-length more ids per bag on average; evaluation feeds each entity's own id as a bag of one")
+    ap.add_argument("--pool-length", type=float, default=4.0, help="mean bag length of the --pool keys' synthetic bags")
     a = ap.parse_args()
+    pooling = None
+    if a.pool:
+        if a.fast:
+            ap.error("--pool needs the eager loop: a captured step's static id buffers hold exactly B*K ids (not with --fast)")
+        pooling = {}
+        for item in a.pool:
+            key, _, mode = item.partition("=")
+            if mode not in ("sum", "mean"):
+                ap.error(f"--pool {item!r}: expected KEY=sum or KEY=mean")
+            pooling[key] = mode
     if a.mask_known and (a.mask_repeats or a.pair_weight):
         ap.error("--mask-known does not combine with --mask-repeats (its cells hold every repeat) or --pair-weight")
     if a.mask_known and not a.fast:
@@ -195,6 +210,7 @@ def main():
                                              tower_hidden_dims=config["tower_hidden_dims"],
                                              final_embedding_dim=config["final_embedding_dim"], dropout_rate=config["dropout_rate"],
                                              temperature=config["temperature"], loss_type=config["loss_type"], device=device,
+                                             categorical_pooling=pooling,
                                              **(dict(embedding_grad="sparse", score_dtype="bf16", mlp_dtype="bf16") if a.fast else {}))
     optimizer = FusedAdam.for_task(train_task, lr=config["learning_rate"], weight_decay=config["weight_decay"],
                                    table_optimizer=a.table_optimizer, table_lr=a.table_lr)
@@ -211,6 +227,11 @@ def main():
         config["num_epochs"] = start_epoch + 1           # resumed after the last epoch: run one more
 
     def eager_step(batch):
+        if pooling:                                      # ragged bags for the pooled keys, drawn per step (seeded by the step number)
+            batch = dict(batch)
+            for side in ("notice", "company"):
+                batch[side] = dict(batch[side], kjt=synthetic.ragged_bags(batch[side]["kjt"], real[side]["vocab_sizes"], pooling,
+                                                                          a.pool_length, seed=config["shuffle_seed"] + steps))
         optimizer.zero_grad()
         result = train_task(batch, return_metrics=True)
         result["loss"].backward()
