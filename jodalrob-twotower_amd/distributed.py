@@ -35,6 +35,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import ops
+from .batch_terms import ROWS as TERM_ROWS
 from .cat_embed import EmbeddingStore, refuse_bag_mode
 from .two_tower_model import TwoTowerModel
 from .two_tower_train_task import TwoTowerTrainTask
@@ -548,19 +549,12 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
             self.exchange.poll_overflow()          # rejects a step whose rows did not fit the buckets (non-blocking, <= poll_lag steps late)
         return super().forward(batch, return_metrics)
 
-    def _negatives_ok(self):
-        return False                                   # extra negatives (a batch with 'negatives'): not by the sharded task
-
-    def _cells_ok(self):
-        return False                                   # masked cells (a batch with 'masked_cells'): not by the sharded task
+    _refused = frozenset({"negatives", "masked_cells"})        # refused by _batch_terms; the other three below, behind the towers
 
     def _score_ce(self, n, c, inv_t, first_call, log_q=None, entity=None, pair_weight=None, cells=None):
-        if pair_weight is not None:
-            raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")
-        if log_q is not None:
-            raise NotImplementedError("the logQ correction (a batch with 'log_q') is not supported by the sharded task")
-        if entity is not None:
-            raise NotImplementedError("the repeated-entity mask (a batch with 'entity') is not supported by the sharded task")
+        for key, given in (("pair_weight", pair_weight), ("log_q", log_q), ("entity", entity)):
+            if given is not None:
+                raise NotImplementedError(f"{TERM_ROWS[key].phrase} {TERM_ROWS[key].verb} not supported by the sharded task")
         if self.negatives == "global" and self.exchange.world > 1:
             if self._dense_loss:
                 raise NotImplementedError("global in-batch negatives support the default cross-entropy loss only")

@@ -21,6 +21,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib as L
+from . import batch_terms as T
 from . import ops
 from .cat_embed import refuse_bag_mode
 from .config import settings
@@ -29,15 +30,19 @@ from .optim import FusedAdam
 
 
 _MAX_COPIES = 8                    # copy segments per tt_copy_multi launch (include/twotower.h: TT_MAX_COPIES)
+_STEP = "the captured step"        # whose device the array checks name
+_CELLS, _NEGATIVES = T.ROWS["masked_cells"], T.ROWS["negatives"]
+
+
+def _holders(static, row):
+    """the dicts of the static buffers that hold `row`'s arrays under its key: one per side, or the top level"""
+    return [static[side] for side in T.SIDES] if row.where == "side" else [static]
 
 
 class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
-    _log_q_ok = True               # batches may carry "log_q" (the logQ correction); the unrolled / segmented steps refuse them
-    _entity_ok = True              # batches may carry "entity" (the repeated-entity mask); likewise
-    _pair_weight_ok = True         # batches may carry "pair_weight" (per-pair sample weights); likewise
-    _negatives_ok = True           # batches may carry "negatives" (shared extra negatives); likewise
-    _cells_ok = True               # batches may carry "masked_cells" (pairs that are never negatives); likewise
+    _accepts = frozenset(T.ROWS)   # the batch entries that change the loss (batch_terms.TABLE) an example batch may carry; the
+                                   # unrolled / segmented steps take none
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
@@ -57,48 +62,20 @@ class GraphedTrainStep:
         step's sums: the two then share one epoch total; what it holds survives this object's warm-up).
         cell_capacity: rows of the static masked-cells buffer of a step captured on a batch with "masked_cells" (default: four times
         the example's, at least 1024); a later batch with more cells is refused."""
-        # logQ correction: an example batch with "log_q" (either side) gives both sides a static [B] buffer; every hand-over then
-        # brings this step's values as two more copy segments of its one launch (the captured forward reads the buffers)
-        self._has_log_q = any(example_batch[side].get("log_q") is not None for side in ("notice", "company"))
-        if self._has_log_q:
-            if not self._log_q_ok:
-                raise NotImplementedError(f"the logQ correction (a batch with 'log_q') is not supported by {type(self).__name__}")
+        # the example batch's entries that change the loss (batch_terms.TABLE): each gets static buffers -- [B] per side (a side the
+        # batch does not carry: zeros / its row indices) or one [B]; the extras' M rows with whichever of log_q / entity they carry; an
+        # int32 [capacity, 2] buffer of cells and a device count, one more word of the step's scalars -- filled at every hand-over by more
+        # copy segments of its launch(es); the captured forward reads the buffers, and the launches that prepare them (the weights', the
+        # cells' plan: their grids depend on the capacity alone) are nodes of the graph.  With extras the hand-over is the plain-copy one
+        self._terms = T.present(example_batch)
+        for row in T.TABLE:
+            if row.key not in self._terms:
+                continue
+            if row.key not in self._accepts:
+                raise NotImplementedError(f"{row.phrase} {row.verb} not supported by {type(self).__name__}")
             if getattr(task, "exchange", None) is not None:
-                raise NotImplementedError("the logQ correction (a batch with 'log_q') is not supported by the sharded task")
-        # repeated-entity mask: an example batch with "entity" (either side) gives both sides a static int32 [B] buffer, filled at every
-        # hand-over through the same copy segments (a side the batch does not carry: its row indices, all-distinct)
-        self._has_entity = any(example_batch[side].get("entity") is not None for side in ("notice", "company"))
-        if self._has_entity:
-            if not self._entity_ok:
-                raise NotImplementedError(f"the repeated-entity mask (a batch with 'entity') is not supported by {type(self).__name__}")
-            if getattr(task, "exchange", None) is not None:
-                raise NotImplementedError("the repeated-entity mask (a batch with 'entity') is not supported by the sharded task")
-        # pair weights: an example batch with "pair_weight" gets a static f32 [B] buffer, filled at every hand-over through one more
-        # copy segment; the captured forward reads it (the weights' preparation launch is part of the capture)
-        self._has_pair_weight = example_batch.get("pair_weight") is not None
-        if self._has_pair_weight:
-            if not self._pair_weight_ok:
-                raise NotImplementedError(f"pair weights (a batch with 'pair_weight') are not supported by {type(self).__name__}")
-            if getattr(task, "exchange", None) is not None:
-                raise NotImplementedError("pair weights (a batch with 'pair_weight') are not supported by the sharded task")
-        # shared extra negatives: an example batch with "negatives" gets static M-row buffers (features, ids and whichever of log_q /
-        # entity it carries), filled at every hand-over by more copy segments; the hand-over is the plain-copy one (_setup_ingest)
-        self._has_negatives = example_batch.get("negatives") is not None
-        if self._has_negatives:
-            if not self._negatives_ok:
-                raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
-            if getattr(task, "exchange", None) is not None:
-                raise NotImplementedError("extra negatives (a batch with 'negatives') are not supported by the sharded task")
-        # masked cells: an example batch with "masked_cells" gets a static int32 [capacity, 2] buffer and a device count (one more word of
-        # the step's scalars); every hand-over brings this step's L cells as one more copy segment, and the plan launches that bucket
-        # them are nodes of the captured graph (their grids depend on the capacity alone)
-        self._has_cells = example_batch.get("masked_cells") is not None
-        if self._has_cells:
-            if not self._cells_ok:
-                raise NotImplementedError(f"masked cells (a batch with 'masked_cells') are not supported by {type(self).__name__}")
-            if getattr(task, "exchange", None) is not None:
-                raise NotImplementedError("masked cells (a batch with 'masked_cells') are not supported by the sharded task")
-        elif cell_capacity is not None:
+                raise NotImplementedError(f"{row.phrase} {row.verb} not supported by the sharded task")
+        if cell_capacity is not None and _CELLS.key not in self._terms:
             raise ValueError("cell_capacity: the example batch carries no 'masked_cells'")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
@@ -112,22 +89,16 @@ class GraphedTrainStep:
         self.static = {side: {"dense": example_batch[side]["dense"].clone(),
                               "kjt": KeyedJaggedTensor(example_batch[side]["kjt"].keys(), example_batch[side]["kjt"].values().clone())}
                        for side in ("notice", "company")}
-        if self._has_log_q:
-            B = example_batch["notice"]["dense"].shape[0]
-            self._lq_zero = torch.zeros(B, dtype=torch.float32, device=dev)
-            for side in ("notice", "company"):
-                t = example_batch[side].get("log_q")
-                self.static[side]["log_q"] = self._check_log_q(t, side, B, dev).clone() if t is not None else self._lq_zero.clone()
-        if self._has_entity:
-            B = example_batch["notice"]["dense"].shape[0]
-            self._ent_iota = torch.arange(B, dtype=torch.int32, device=dev)
-            for side in ("notice", "company"):
-                t = example_batch[side].get("entity")
-                self.static[side]["entity"] = self._check_entity(t, side, B, dev).clone() if t is not None else self._ent_iota.clone()
-        if self._has_pair_weight:
-            B = example_batch["notice"]["dense"].shape[0]
-            self.static["pair_weight"] = self._check_pair_weight(example_batch["pair_weight"], B, dev).clone()
-        if self._has_negatives:
+        B, self._fill = example_batch["notice"]["dense"].shape[0], {}
+        for row in T.B_TERMS:
+            if row.key not in self._terms:
+                continue
+            if row.missing:
+                self._fill[row.key] = row.fill(B, dev)
+            given = row.of(example_batch)
+            for holder, name, t in zip(_holders(self.static, row), row.names(_STEP), given if row.where == "side" else (given,)):
+                holder[row.key] = (self._fill[row.key] if t is None else T.check(t, name, row.dtype, (B,), dev, _STEP).contiguous()).clone()
+        if _NEGATIVES.key in self._terms:
             neg = example_batch["negatives"]
             self.static["negatives"] = {"dense": neg["dense"].clone(), "kjt": KeyedJaggedTensor(neg["kjt"].keys(), neg["kjt"].values().clone())}
             for k in ("log_q", "entity"):
@@ -136,7 +107,7 @@ class GraphedTrainStep:
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed, the masked cells' count) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
-        self._n_scalar = ng * 8 + 2 + (2 if self._has_cells else 0)
+        self._n_scalar = ng * 8 + 2 + (2 if _CELLS.key in self._terms else 0)
         self._slot_len = (self._n_scalar + 3) // 4 * 4                 # 16-byte slots
         self._ring = 64
         self._host_ring = torch.zeros(self._ring, self._slot_len, dtype=torch.float32).pin_memory()
@@ -147,7 +118,7 @@ class GraphedTrainStep:
         self._dev = torch.zeros(self._n_scalar, dtype=torch.float32, device=dev)
         self._hp_dev = self._dev[:ng * 8].view(ng, 8)
         self._seed_dev = self._dev[ng * 8:ng * 8 + 2].view(torch.int64)          # 2 floats = one 64-bit word
-        if self._has_cells:
+        if _CELLS.key in self._terms:
             ex = self._check_cells(example_batch["masked_cells"], dev, None)
             cap = max(4 * ex.shape[0], 1024) if cell_capacity is None else int(cell_capacity)
             if cap < max(ex.shape[0], 1):
@@ -216,7 +187,7 @@ class GraphedTrainStep:
         per-key plan: returns (store, embedders, rows_km, static id tensors, B) or None (then the batch is handed over by plain
         copies and the plan gathers its rows out of the lookup's slot-major array)."""
         self._x_static, self._rows_sm = None, None
-        if not settings.graph_ingest or getattr(self, "_has_negatives", False):     # (extras: the company side is B + M rows)
+        if not settings.graph_ingest or _NEGATIVES.key in self._terms:     # (extras: the company side is B + M rows)
             return None
         model = getattr(self.task, "two_tower_model", None)
         towers = [getattr(model, n, None) for n in ("notice_tower", "company_tower")]
@@ -385,7 +356,7 @@ class GraphedTrainStep:
             if e.store is not store or not e.keys:
                 continue
             ids = self.static[side]["kjt"].values().view(-1, len(e.keys))
-            if side == "company" and getattr(self, "_has_negatives", False):     # the extras go through the company tower too
+            if side == "company" and _NEGATIVES.key in self._terms:     # the extras go through the company tower too
                 ids = torch.cat([ids, self.static["negatives"]["kjt"].values().view(-1, len(e.keys))], 0)
             rows.append((ids.clamp(min=0).minimum(e._key_vocab - 1) + e._key_row_offset).reshape(-1))      # cat_embed.py:114-117
         return torch.unique(torch.cat(rows)) if rows else None
@@ -466,7 +437,7 @@ class GraphedTrainStep:
             hp = ops.adam_hparams(step, float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
             host[gi * 8: gi * 8 + 6] = torch.tensor(hp)
         host[ng * 8:ng * 8 + 2].view(torch.int64).random_()
-        if self._has_cells:
+        if _CELLS.key in self._terms:
             host[ng * 8 + 2:ng * 8 + 4].view(torch.int32)[0] = self._cells_n
         return (self._dev, host)
 
@@ -487,57 +458,18 @@ class GraphedTrainStep:
         self._mark_slot()
 
     @staticmethod
-    def _check_log_q(t, side, B, dev):
-        """t as a contiguous, 16-byte aligned f32 [B] on dev (the hand-over launch's copy segments must be aligned: a misaligned
-        view is copied once)"""
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"{side} log_q must be a float32 tensor of shape [{B}], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != dev:
-            raise ValueError(f"{side} log_q is on {t.device}, the captured step on {dev}")
-        t = t.contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-
-    @staticmethod
-    def _check_entity(t, side, B, dev):
-        """t as a contiguous, 16-byte aligned int32 [B] on dev (as _check_log_q)"""
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"{side} entity must be an int32 tensor of shape [{B}], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != dev:
-            raise ValueError(f"{side} entity is on {t.device}, the captured step on {dev}")
-        t = t.contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-
-    @staticmethod
-    def _check_pair_weight(t, B, dev):
-        """t as a contiguous, 16-byte aligned f32 [B] on dev (as _check_log_q)"""
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"pair_weight must be a float32 tensor of shape [{B}], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != dev:
-            raise ValueError(f"pair_weight is on {t.device}, the captured step on {dev}")
-        t = t.contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-
-    @staticmethod
     def _check_cells(t, dev, capacity):
         """t as a contiguous int32 [L, 2] on dev, L <= capacity (L is the tensor's shape: no synchronisation)"""
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2:
-            raise ValueError(f"masked_cells must be an int32 tensor of shape [L, 2], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != dev:
-            raise ValueError(f"masked_cells is on {t.device}, the captured step on {dev}")
+        T.check(t, _CELLS.key, _CELLS.dtype, _CELLS.shape, dev, _STEP)
         if capacity is not None and t.shape[0] > capacity:
             raise ValueError(f"masked_cells: {t.shape[0]} cells, the step was captured with cell_capacity = {capacity}")
         return t.contiguous()
 
     def _cells_check(self, batch):
         """this step's cells after the with / without and the capacity checks -- before anything is copied"""
-        cells = None if batch is None else batch.get("masked_cells")
-        if batch is not None and (cells is not None) != self._has_cells:
-            raise ValueError("masked_cells mismatch: the step was captured " + ("with" if self._has_cells else "without") +
-                             " masked cells, the batch " + ("has none" if self._has_cells else "carries them"))
+        cells, captured = None if batch is None else batch.get(_CELLS.key), _CELLS.key in self._terms
+        if batch is not None and (cells is not None) != captured:
+            raise ValueError(T.mismatch(_CELLS, captured))
         return None if cells is None else self._check_cells(cells, self._dev.device, self.cell_capacity)
 
     def _cells_pairs(self, cells):
@@ -545,30 +477,28 @@ class GraphedTrainStep:
         if cells is None:
             return []
         self._cells_n = n = cells.shape[0]
-        if n == 0:
-            return []
-        dst = self.static["masked_cells"][:n]
-        if cells.data_ptr() % 16:                               # (the copy launch moves 16-byte pieces: a slice of an epoch's array)
-            dst.copy_(cells, non_blocking=True)
-            return []
-        return [(dst, cells)]
+        return T.segment(self.static[_CELLS.key][:n], cells) if n else []
 
-    def _pair_weight_pairs(self, w, who):
-        """the copy segment of this step's pair weights into the static buffer, after the with / without check"""
-        if (w is not None) != self._has_pair_weight:
-            raise ValueError("pair_weight mismatch: the step was captured " + ("with" if self._has_pair_weight else "without") +
-                             f" pair weights, {who} " + ("has none" if self._has_pair_weight else "carries them"))
-        if w is None:
-            return []
-        sw = self.static["pair_weight"]
-        return [(sw, GraphedTrainStep._check_pair_weight(w, sw.shape[0], sw.device))]
+    def _term_pairs(self, key, value, who):
+        """copy segments of this step's arrays of a [B] entry -- `value`: per side (notice, company) or the one array, a side given
+        as None: what it stands for -- into the static buffers, after the with / without check; who hands it over: "the batch" or
+        "step_from_store" (the mismatch sentence names it)"""
+        row, captured = T.ROWS[key], key in self._terms
+        if (value is not None) != captured:
+            raise ValueError(T.mismatch(row, captured, who))
+        out = []
+        if value is not None:
+            for holder, name, t in zip(_holders(self.static, row), row.names(_STEP), value if row.where == "side" else (value,)):
+                dst = holder[key]
+                out += T.segment(dst, self._fill[key] if t is None else T.check(t, name, row.dtype, dst.shape, dst.device, _STEP))
+        return out
 
     def _negatives_pairs(self, neg):
         """copy segments of this step's extra negatives into the static M-row buffers, after the with / without check (the task
         validates what the buffers then hold)"""
-        if (neg is not None) != self._has_negatives:
-            raise ValueError("negatives mismatch: the step was captured " + ("with" if self._has_negatives else "without") +
-                             " extra negatives, the batch " + ("has none" if self._has_negatives else "carries them"))
+        captured = _NEGATIVES.key in self._terms
+        if (neg is not None) != captured:
+            raise ValueError(T.mismatch(_NEGATIVES, captured))
         if neg is None:
             return []
         sn = self.static["negatives"]
@@ -580,24 +510,8 @@ class GraphedTrainStep:
             if not isinstance(src, torch.Tensor) or src.shape != dst.shape or src.dtype != dst.dtype or src.device != dst.device:
                 raise ValueError(f"negatives['{name}'] must be a {dst.dtype} tensor of shape {list(dst.shape)} on {dst.device} "
                                  "(the captured step has one M)")
-            src = src.contiguous()
-            if src.data_ptr() % 16 or dst.data_ptr() % 16:         # (the copy launch moves 16-byte pieces)
-                dst.copy_(src, non_blocking=True)
-            else:
-                out.append((dst, src))
+            out += T.segment(dst, src)
         return out
-
-    def _entity_pairs(self, ent_n, ent_c):
-        """copy segments of this step's entity ids into the static buffers (a side given as None: the row indices)"""
-        B, dev = self._ent_iota.shape[0], self._ent_iota.device
-        return [(self.static[side]["entity"], self._check_entity(t, side, B, dev) if t is not None else self._ent_iota)
-                for side, t in (("notice", ent_n), ("company", ent_c))]
-
-    def _log_q_pairs(self, lq_n, lq_c):
-        """copy segments of this step's log q into the static buffers (a side given as None: zeros)"""
-        B, dev = self._lq_zero.shape[0], self._lq_zero.device
-        return [(self.static[side]["log_q"], self._check_log_q(t, side, B, dev) if t is not None else self._lq_zero)
-                for side, t in (("notice", lq_n), ("company", lq_c))]
 
     def _handover_pairs(self, batch: Optional[Dict]):
         """(copy segments, per-side id sources) that hand `batch` over into the static buffers (None: nothing to copy)."""
@@ -605,19 +519,8 @@ class GraphedTrainStep:
         if batch is None:
             return pairs, None
         pairs += self._negatives_pairs(batch.get("negatives"))
-        lq_n, lq_c = batch["notice"].get("log_q"), batch["company"].get("log_q")
-        if (lq_n is not None or lq_c is not None) != self._has_log_q:
-            raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
-                             " a log_q, the batch " + ("has none" if self._has_log_q else "carries one"))
-        if self._has_log_q:
-            pairs += self._log_q_pairs(lq_n, lq_c)
-        ent_n, ent_c = batch["notice"].get("entity"), batch["company"].get("entity")
-        if (ent_n is not None or ent_c is not None) != self._has_entity:
-            raise ValueError("entity mismatch: the step was captured " + ("with" if self._has_entity else "without") +
-                             " entity ids, the batch " + ("has none" if self._has_entity else "carries them"))
-        if self._has_entity:
-            pairs += self._entity_pairs(ent_n, ent_c)
-        pairs += self._pair_weight_pairs(batch.get("pair_weight"), "the batch")
+        for row in T.B_TERMS:
+            pairs += self._term_pairs(row.key, row.of(batch), "the batch")
         for side in ("notice", "company"):
             d, v = batch[side]["dense"], batch[side]["kjt"].values()
             sd, sv = self.static[side]["dense"], self.static[side]["kjt"].values()
@@ -669,18 +572,12 @@ class GraphedTrainStep:
         entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
         DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise.
         pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment."""
-        if self._has_cells:
-            raise NotImplementedError("masked cells: no store-fed hand-over -- a step captured with 'masked_cells' takes step(batch)")
-        if self._has_negatives:
-            raise NotImplementedError("extra negatives: no store-fed hand-over -- a step captured with 'negatives' takes step(batch)")
-        if (log_q is not None) != self._has_log_q:
-            raise ValueError("log_q mismatch: the step was captured " + ("with" if self._has_log_q else "without") +
-                             " a log_q, step_from_store got " + ("none" if self._has_log_q else "one"))
-        if (entity is not None) != self._has_entity:
-            raise ValueError("entity mismatch: the step was captured " + ("with" if self._has_entity else "without") +
-                             " entity ids, step_from_store got " + ("none" if self._has_entity else "them"))
-        extra = (self._log_q_pairs(*log_q) if log_q is not None else []) + (self._entity_pairs(*entity) if entity is not None else [])
-        extra += self._pair_weight_pairs(pair_weight, "step_from_store")
+        for row in (_CELLS, _NEGATIVES):
+            if row.key in self._terms:
+                raise NotImplementedError(f"{row.noun}: no store-fed hand-over -- a step captured with '{row.key}' takes step(batch)")
+        given, extra = {"log_q": log_q, "entity": entity, "pair_weight": pair_weight}, []
+        for row in T.B_TERMS:
+            extra += self._term_pairs(row.key, given[row.key], "step_from_store")
         self._ingest_from_store(notice_store, company_store, pairs, order, offset, extra=extra or None)
         self._mark_slot()
         return self._replay()

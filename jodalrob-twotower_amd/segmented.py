@@ -88,11 +88,7 @@ class _SegmentingComm(DistComm):
 
 class SegmentedTrainStep(GraphedTrainStep):
     """GraphedTrainStep whose capture is cut at every collective (see the module docstring).  Same interface and results."""
-    _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
-    _entity_ok = False             # the repeated-entity mask likewise
-    _pair_weight_ok = False        # pair weights likewise
-    _negatives_ok = False          # extra negatives likewise
-    _cells_ok = False              # masked cells likewise
+    _accepts = frozenset()         # batch entries that change the loss (batch_terms.TABLE) are out of scope here: refused
 
     segmented = True
 

@@ -16,7 +16,9 @@ import torch
 from ._lib import no_dynamo as _no_dynamo
 import torch.nn as nn
 
+from . import batch_terms as T
 from . import ops
+from .batch_terms import _CLASH_WHY, _TERM_CLASHES, _TERM_FORMS, _terms_clash       # (what combines: the node decides with it; also imported from here)
 from .config import settings
 from .kjt import KeyedJaggedTensor, concat_kjt
 from .towers import run_towers
@@ -204,6 +206,17 @@ class _Saved(NamedTuple):
     terms: "ops.ScoreTerms"
 
 
+class _BatchTerms(NamedTuple):
+    """what TwoTowerTrainTask._batch_terms makes of a batch: lq (lq_n, lq_c); ent (ent_n, ent_c), a side may be None; pw; neg the
+    "negatives" dict; cells (cells, count or None) -- each None when the batch carries none"""
+    lq: Optional[tuple] = None
+    ent: Optional[tuple] = None
+    pw: Optional[torch.Tensor] = None
+    neg: Optional[dict] = None
+    cells: Optional[tuple] = None
+
+
+_NO_TERMS = _BatchTerms()
 _NODE_INPUTS = _ScoreCEFn.forward.__code__.co_varnames[1:_ScoreCEFn.forward.__code__.co_argcount]
 _NODE_SLOT = {name: i for i, name in enumerate(_NODE_INPUTS)}
 
@@ -214,16 +227,6 @@ def _node_grads(**grads):
     for name, g in grads.items():
         out[_NODE_SLOT[name]] = g
     return tuple(out)
-
-
-# ---- the one table of what combines: the node decides with it, the task's batch validators ask it ----------------------------------
-_TERM_FORMS = {"cells": ("bf16",), "extras": ("fp32", "bf16"), "ent": ("fp32", "bf16"), "pw": ("fp32", "bf16"),
-               "lq": ("fp32", "bf16", "bf16x3")}                      # term -> the score_dtypes that have a form of it
-_TERM_CLASHES = frozenset({frozenset({"cells", "ent"}), frozenset({"cells", "pw"}), frozenset({"extras", "pw"})})
-
-
-def _terms_clash(a, b):
-    return frozenset({a, b}) in _TERM_CLASHES
 
 
 def _need_form(term, score_dtype, name, hint=" (score_dtype 'bf16' or 'fp32')"):
@@ -344,17 +347,13 @@ class TwoTowerTrainTask(nn.Module):
         nb, cb = notice_input["dense"].size(0), company_input["dense"].size(0)
         if nb != cb:                                                                         # :64-67
             raise ValueError(f"Notice와 Company 배치 크기가 다릅니다: {nb} vs {cb}")
-        lq = self._batch_log_q(notice_input, company_input, nb)
-        ent = self._batch_entity(notice_input, company_input, nb)
-        pw = self._batch_pair_weight(batch, nb)
-        neg = self._batch_negatives(batch, company_input, nb, lq, ent, pw)
-        cells = self._batch_cells(batch, nb, ent, pw)
-        if neg is not None:
-            notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, neg, nb, lq, ent, cells)
+        t = self._batch_terms(batch, nb)
+        if t.neg is not None:
+            notice_embeddings, company_embeddings, loss, out8 = self._forward_negatives(notice_input, company_input, t.neg, nb, t.lq, t.ent, t.cells)
         else:
             notice_embeddings, company_embeddings = self.two_tower_model(notice_input, company_input)
             loss, out8, _ = self._score_ce(notice_embeddings, company_embeddings, 1.0 / float(self.temperature),
-                                           not hasattr(self, "_pair_check_done"), log_q=lq, entity=ent, pair_weight=pw, cells=cells)
+                                           not hasattr(self, "_pair_check_done"), log_q=t.lq, entity=t.ent, pair_weight=t.pw, cells=t.cells)
         if not hasattr(self, "_pair_check_done"):                                            # :82-84
             self._verify_positive_pair_alignment(out8)
             self._pair_check_done = True
@@ -372,12 +371,9 @@ class TwoTowerTrainTask(nn.Module):
         """(result dict as forward(batch, return_metrics=True), 0-based rank of each positive in its row) from ONE pass
         through the towers -- what the evaluator needs per batch (src/evaluation/evaluator.py:123-155 calls the model once
         and ranks its similarity matrix).  Ranks come from the exact-f32 score sweep, as diagonal_ranks()."""
-        if batch.get("pair_weight") is not None:
-            raise ValueError("forward_with_ranks does not take a batch with 'pair_weight' (evaluation is unweighted)")
-        if batch.get("negatives") is not None:
-            raise ValueError("forward_with_ranks does not take a batch with 'negatives' (evaluation ranks the batch's own companies)")
-        if batch.get("masked_cells") is not None:
-            raise ValueError("forward_with_ranks does not take a batch with 'masked_cells' (evaluation filters with exclusion lists)")
+        for row in T.TABLE:
+            if row.eval_why is not None and batch.get(row.key) is not None:
+                raise ValueError(f"forward_with_ranks does not take a batch with '{row.key}' ({row.eval_why})")
         with torch.no_grad():
             n, c = self.two_tower_model(batch["notice"], batch["company"])
             if n.size(0) != c.size(0):
@@ -391,105 +387,43 @@ class TwoTowerTrainTask(nn.Module):
                           sim_thunk=lambda: ops.score_matrix(n_det, c_det, inv_t))
             return res, rank
 
-    def _batch_log_q(self, notice_input, company_input, B):
-        """(lq_n, lq_c) f32 [B] from the batch's "log_q" entries (logQ correction; a missing side counts as zeros), or None when
-        neither side carries one.  Refuses what the corrected loss does not cover -- never ignores a log_q."""
-        lq_n, lq_c = notice_input.get("log_q"), company_input.get("log_q")
-        if lq_n is None and lq_c is None:
-            return None
-        if self._dense_loss:
-            raise ValueError("the logQ correction (a batch with 'log_q') is not supported by the dense loss path "
-                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype not in _TERM_FORMS["lq"]:
-            raise ValueError(f"the logQ correction (a batch with 'log_q') is not supported for score_dtype={self.score_dtype!r}")
-        ref = notice_input["dense"]
-        out = []
-        for name, t in (("notice", lq_n), ("company", lq_c)):
-            if t is None:
-                out.append(torch.zeros(B, dtype=torch.float32, device=ref.device))
+    _refused = frozenset()         # the batch entries (keys of batch_terms.TABLE) this task does not take; the sharded task has some
+
+    def _batch_terms(self, batch, B):
+        """The batch's optional entries, validated, as the score node takes them (_BatchTerms).  One walk of batch_terms.TABLE; per
+        entry, in this order: may this task take it, what it does not combine with, the dense loss, the score_dtype's form, its
+        arrays.  Refuses what the loss does not cover -- never ignores an entry."""
+        have = T.present(batch)
+        if not have:
+            return _NO_TERMS
+        dev, out = batch["notice"]["dense"].device, {}
+        for row in T.TABLE:
+            if row.key not in have:
                 continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
-                raise ValueError(f"batch['{name}']['log_q'] must be a float32 tensor of shape [{B}], got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-            if t.device != ref.device:
-                raise ValueError(f"batch['{name}']['log_q'] is on {t.device}, the batch on {ref.device}")
-            out.append(t.contiguous())
-        return out[0], out[1]
-
-    def _batch_entity(self, notice_input, company_input, B):
-        """(ent_n, ent_c) int32 [B] (a missing side: None, all-distinct) from the batch's "entity" entries (the repeated-entity mask),
-        or None when neither side carries one.  Refuses what the masked loss does not cover -- never ignores an entity array."""
-        ent_n, ent_c = notice_input.get("entity"), company_input.get("entity")
-        if ent_n is None and ent_c is None:
-            return None
-        if self._dense_loss:
-            raise ValueError("the repeated-entity mask (a batch with 'entity') is not supported by the dense loss path "
-                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype not in _TERM_FORMS["ent"]:
-            raise ValueError(f"the repeated-entity mask (a batch with 'entity') is not supported for score_dtype={self.score_dtype!r}")
-        ref = notice_input["dense"]
-        for name, t in (("notice", ent_n), ("company", ent_c)):
-            if t is None:
+            if row.key in self._refused:
+                raise NotImplementedError(f"{row.phrase} {row.verb} not supported by {type(self).__name__}")
+            for other in T.TABLE:                              # (what it clashes with has been decided: it stands above in the table)
+                if other.term in out and _terms_clash(row.term, other.term):
+                    raise ValueError(f"{row.phrase} do not combine with '{other.key}'" + _CLASH_WHY.get(frozenset({row.term, other.term}), ""))
+            if self._dense_loss:
+                raise ValueError(f"{row.phrase} {row.verb} not supported by the dense loss path "
+                                 "(label_smoothing != 0 or loss_type='cosine_embedding')")
+            if self.score_dtype not in _TERM_FORMS[row.term]:
+                raise ValueError(f"{row.phrase} {row.verb} not supported for score_dtype={self.score_dtype!r}")
+            if row.where == "nested":
+                out[row.term] = self._check_negatives(batch, out.get("lq"), out.get("ent"))
                 continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
-                raise ValueError(f"batch['{name}']['entity'] must be an int32 tensor of shape [{B}], got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-            if t.device != ref.device:
-                raise ValueError(f"batch['{name}']['entity'] is on {t.device}, the batch on {ref.device}")
-        return ent_n, ent_c
-
-    def _batch_pair_weight(self, batch, B):
-        """f32 [B] raw per-pair sample weights from batch["pair_weight"], or None when the batch carries none.  Refuses what the
-        weighted loss does not cover -- never ignores a pair_weight."""
-        t = batch.get("pair_weight")
-        if t is None:
-            return None
-        if self._dense_loss:
-            raise ValueError("pair weights (a batch with 'pair_weight') are not supported by the dense loss path "
-                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype not in _TERM_FORMS["pw"]:
-            raise ValueError(f"pair weights (a batch with 'pair_weight') are not supported for score_dtype={self.score_dtype!r}")
-        ref = batch["notice"]["dense"]
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"batch['pair_weight'] must be a float32 tensor of shape [{B}], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != ref.device:
-            raise ValueError(f"batch['pair_weight'] is on {t.device}, the batch on {ref.device}")
-        return t
-
-    def _cells_ok(self):
-        """may a batch carry 'masked_cells'?  (the sharded task overrides it)"""
-        return True
-
-    def _batch_cells(self, batch, B, ent, pw):
-        """(cells int32 [L, 2], count int32 [1] or None) from batch["masked_cells"] (pairs that are never negatives: rows (a, j), a < B,
-        j < B + M) and the optional batch["masked_cells_count"] (a device count of the rows in use, for static buffers), or None when
-        the batch carries none.  Refuses what the masked loss does not cover -- never ignores the entry."""
-        t = batch.get("masked_cells")
-        if t is None:
-            return None
-        if not self._cells_ok():
-            raise NotImplementedError(f"masked cells (a batch with 'masked_cells') are not supported by {type(self).__name__}")
-        if ent is not None and _terms_clash("cells", "ent"):
-            raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'entity': cells built from the pair table "
-                             "already hold every repeat")
-        if pw is not None and _terms_clash("cells", "pw"):
-            raise ValueError("masked cells (a batch with 'masked_cells') do not combine with 'pair_weight'")
-        if self._dense_loss:
-            raise ValueError("masked cells (a batch with 'masked_cells') are not supported by the dense loss path "
-                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype not in _TERM_FORMS["cells"]:
-            raise ValueError(f"masked cells (a batch with 'masked_cells') are not supported for score_dtype={self.score_dtype!r}")
-        ref = batch["notice"]["dense"]
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2:
-            raise ValueError(f"batch['masked_cells'] must be an int32 tensor of shape [L, 2], got "
-                             f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-        if t.device != ref.device:
-            raise ValueError(f"batch['masked_cells'] is on {t.device}, the batch on {ref.device}")
-        n = batch.get("masked_cells_count")
-        if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.numel() == 1 and n.device == ref.device):
-            raise ValueError(f"batch['masked_cells_count'] must be an int32 tensor of one element on {ref.device}")
-        return t, n
+            v = [t if t is None else T.check(t, name, row.dtype, row.dims(B), dev, "the batch")
+                 for name, t in zip(row.names("the batch"), row.of(batch) if row.where == "side" else (batch[row.key],))]
+            if row.missing == "zeros":                         # (a missing side's ids stay None: all-distinct to the node)
+                v = [row.fill(B, dev) if t is None else t.contiguous() for t in v]
+            out[row.term] = tuple(v) if row.where == "side" else v[0]
+        if "cells" in out:             # the optional device count of the rows in use (static buffers)
+            n = batch.get("masked_cells_count")
+            if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.numel() == 1 and n.device == dev):
+                raise ValueError(f"batch['masked_cells_count'] must be an int32 tensor of one element on {dev}")
+            out["cells"] = (out["cells"], n)
+        return _BatchTerms(out.get("lq"), out.get("ent"), out.get("pw"), out.get("extras"), out.get("cells"))
 
     def _forward_negatives(self, notice_input, company_input, neg, B, lq, ent, cells=None):
         """(notice embeddings, company embeddings, loss, out8) of a batch with shared extra negatives: the M rows ride behind the batch's
@@ -508,26 +442,10 @@ class TwoTowerTrainTask(nn.Module):
                                          neg.get("entity"), *(cells if cells is not None else (None, None)))
         return n_emb, c_emb, loss, out8
 
-    def _negatives_ok(self):
-        """may a batch carry 'negatives'?  (the sharded task overrides it)"""
-        return True
-
-    def _batch_negatives(self, batch, company_input, B, lq, ent, pw):
-        """batch["negatives"] validated -- {"dense" [M, Dc], "kjt"} with optional "log_q" f32 [M] and "entity" int32 [M], M >= 1 company
-        rows every notice of the batch is contrasted with besides the in-batch ones -- or None when the batch carries none.  Refuses
-        what the loss with extras does not cover -- never ignores the entry."""
-        neg = batch.get("negatives")
-        if neg is None:
-            return None
-        if not self._negatives_ok():
-            raise NotImplementedError(f"extra negatives (a batch with 'negatives') are not supported by {type(self).__name__}")
-        if pw is not None and _terms_clash("extras", "pw"):
-            raise ValueError("extra negatives (a batch with 'negatives') do not combine with 'pair_weight'")
-        if self._dense_loss:
-            raise ValueError("extra negatives (a batch with 'negatives') are not supported by the dense loss path "
-                             "(label_smoothing != 0 or loss_type='cosine_embedding')")
-        if self.score_dtype not in _TERM_FORMS["extras"]:
-            raise ValueError(f"extra negatives (a batch with 'negatives') are not supported for score_dtype={self.score_dtype!r}")
+    def _check_negatives(self, batch, lq, ent):
+        """batch["negatives"]'s structure -- {"dense" [M, Dc], "kjt"} with optional "log_q" f32 [M] and "entity" int32 [M], M >= 1 company
+        rows every notice of the batch is contrasted with besides the in-batch ones; lq / ent: the batch's own, validated"""
+        neg, company_input = batch["negatives"], batch["company"]
         ref = company_input["dense"]
         d = neg.get("dense") if isinstance(neg, dict) else None
         if not isinstance(d, torch.Tensor) or d.dim() != 2 or d.shape[1] != ref.shape[1] or d.dtype != ref.dtype or "kjt" not in neg:
@@ -543,15 +461,10 @@ class TwoTowerTrainTask(nn.Module):
         n_slots = neg["kjt"].lengths().numel() if self.two_tower_model.company_tower.categorical_embedder.bag_mode else v.numel()
         if list(neg["kjt"].keys()) != list(company_input["kjt"].keys()) or n_slots != M * K or v.device != ref.device:
             raise ValueError(f"batch['negatives']['kjt'] must carry the company side's {K} keys for {M} rows on {ref.device}")
-        for name, dt, given in (("log_q", torch.float32, lq is not None), ("entity", torch.int32, ent is not None and ent[1] is not None)):
-            t = neg.get(name)
-            if t is None:
+        for name, given in (("log_q", lq is not None), ("entity", ent is not None and ent[1] is not None)):
+            if neg.get(name) is None:
                 continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.shape[0] != M:
-                raise ValueError(f"batch['negatives']['{name}'] must be a {str(dt).replace('torch.', '')} tensor of shape [{M}], got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', []))}")
-            if t.device != ref.device:
-                raise ValueError(f"batch['negatives']['{name}'] is on {t.device}, the batch on {ref.device}")
+            T.check(neg[name], f"batch['negatives']['{name}']", T.ROWS[name].dtype, (M,), ref.device, "the batch", a="a")
             if not given:
                 raise ValueError(f"batch['negatives']['{name}'] needs batch['company']['{name}']: the extras' {name} has nothing to be "
                                  "compared with")

@@ -28,11 +28,7 @@ from .kjt import KeyedJaggedTensor
 class UnrolledTrainStep(GraphedTrainStep):
     """GraphedTrainStep with `unroll` steps per graph launch: `step_many(batches)` / `steps_from_store(..., offsets)` run `unroll`
     steps; `step` / `step_from_store` (one step: an epoch's remainder) go through a single-step sibling captured on first use."""
-    _log_q_ok = False              # the logQ correction is out of scope here: refused (NotImplementedError)
-    _entity_ok = False             # the repeated-entity mask likewise
-    _pair_weight_ok = False        # pair weights likewise
-    _negatives_ok = False          # extra negatives likewise
-    _cells_ok = False              # masked cells likewise
+    _accepts = frozenset()         # batch entries that change the loss (batch_terms.TABLE) are out of scope here: refused
 
     def __init__(self, task, optimizer, example_batch: Dict, unroll: int = 2, **kw):
         if int(unroll) < 2:

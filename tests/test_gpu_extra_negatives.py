@@ -259,45 +259,89 @@ def _decorated(b, B, seed):
                             entity=torch.randint(0, B // 2, (B,), generator=g, device=DEV, dtype=torch.int32))}
 
 
-@pytest.mark.parametrize("decorated", [False, True])
-def test_xneg_graphed_step_equals_eager(tt, manifest, decorated):
-    """three steps on batches whose extras differ, FusedAdam: GraphedTrainStep.step(batch) (static M-row buffers, the plain-copy
-    hand-over) against the eager step, bit for bit -- per-step losses and accuracies, every weight and table row after them"""
+def _three_steps(tt, manifest, mode, M, decorated, B=64, both_ids=False, after=None):
+    """(per-step (loss, accuracy), the final state) of three FusedAdam steps on batches whose extras differ: eager, or
+    GraphedTrainStep.step(batch); after(gs, b, bs): called on the captured step before it is closed"""
     from jodalrob_twotower_amd.graph import GraphedTrainStep
     from jodalrob_twotower_amd.optim import FusedAdam
-    M, finals = 37, {}
-    for mode in ("eager", "graph"):
-        task, b, B = _small_task(tt, manifest, score_dtype="bf16")
-        if decorated:
-            b = _decorated(b, B, 11)
-        bs = [_with_negatives(b, M, 20 + k, log_q=decorated, entity=decorated) for k in range(3)]
-        opt = FusedAdam.for_task(task, lr=1e-2, weight_decay=1e-5)
-        gs = GraphedTrainStep(task, opt, bs[0], warmup=1) if mode == "graph" else None
-        losses = []
-        for bk in bs:
-            if gs is None:
-                opt.zero_grad()
-                r = task(bk, return_metrics=True)
-                r["loss"].backward()
-                opt.step()
-            else:
-                r = gs.step(bk)
-            losses.append((r["loss"].item(), r["accuracy"].item()))
-        torch.cuda.synchronize()
-        finals[mode] = (losses, {k: v.detach().cpu().clone() for k, v in task.state_dict().items()})
-        if gs is not None:
-            # a step captured with extras refuses a batch without them, another M, and the store-fed hand-over
-            with pytest.raises(ValueError, match="negatives mismatch"):
-                gs.step(b)
-            with pytest.raises(ValueError, match="one M"):
-                gs.step(_with_negatives(b, M + 1, 5, log_q=decorated, entity=decorated))
-            with pytest.raises(NotImplementedError, match="negatives"):
-                gs.step_from_store(None, None, None)
-            gs.close()
+    task, b, B = _small_task(tt, manifest, B=B, score_dtype="bf16")
+    if decorated:
+        b = _decorated(b, B, 11)
+    if both_ids:
+        b["notice"]["entity"] = torch.randint(0, B // 2, (B,), generator=torch.Generator(device=DEV).manual_seed(12), device=DEV, dtype=torch.int32)
+    bs = [_with_negatives(b, M, 20 + k, log_q=decorated, entity=decorated) for k in range(3)]
+    opt = FusedAdam.for_task(task, lr=1e-2, weight_decay=1e-5)
+    gs = GraphedTrainStep(task, opt, bs[0], warmup=1) if mode == "graph" else None
+    losses = []
+    for bk in bs:
+        if gs is None:
+            opt.zero_grad()
+            r = task(bk, return_metrics=True)
+            r["loss"].backward()
+            opt.step()
+        else:
+            r = gs.step(bk)
+        losses.append((r["loss"].item(), r["accuracy"].item()))
+    torch.cuda.synchronize()
+    state = {k: v.detach().cpu().clone() for k, v in task.state_dict().items()}
+    if gs is not None:
+        if after is not None:
+            after(gs, b, bs)
+        gs.close()
+    return losses, state
+
+
+def _assert_graph_is_eager(finals):
     assert finals["graph"][0] == finals["eager"][0], (finals["graph"][0], finals["eager"][0])
     assert len(set(finals["eager"][0])) == 3
     for k, v in finals["eager"][1].items():
         assert torch.equal(v, finals["graph"][1][k]), k
+
+
+@pytest.mark.parametrize("decorated", [False, True])
+def test_xneg_graphed_step_equals_eager(tt, manifest, decorated):
+    """three steps on batches whose extras differ, FusedAdam: GraphedTrainStep.step(batch) (static M-row buffers, the plain-copy
+    hand-over) against the eager step, bit for bit -- per-step losses and accuracies, every weight and table row after them"""
+    M = 37
+
+    def refusals(gs, b, bs):
+        # a step captured with extras refuses a batch without them, another M, and the store-fed hand-over
+        with pytest.raises(ValueError, match="negatives mismatch"):
+            gs.step(b)
+        with pytest.raises(ValueError, match="one M"):
+            gs.step(_with_negatives(b, M + 1, 5, log_q=decorated, entity=decorated))
+        with pytest.raises(NotImplementedError, match="negatives"):
+            gs.step_from_store(None, None, None)
+    _assert_graph_is_eager({mode: _three_steps(tt, manifest, mode, M, decorated, after=refusals) for mode in ("eager", "graph")})
+
+
+WIDEST_LAUNCHES = 64               # GraphedTrainStep.library_launches of the case below, read off the commit before the hand-over's
+                                   # host code was folded into one table walk
+
+
+def test_xneg_widest_handover_is_two_copy_launches(tt, manifest, monkeypatch):
+    """the widest hand-over -- extras that carry log_q and entity, log_q and entity on BOTH sides: 13 copy segments (4 of the extras, 2
+    + 2 of the sides' terms, 4 of the sides, the scalars), more than one tt_copy_multi launch takes -- at B = 40, M = 24 (neither a
+    multiple of the 32-wide tiles): bit for bit the eager steps, two copy launches per step(), and as many library launches per step
+    as before"""
+    from jodalrob_twotower_amd import ops
+    calls, seen = [], {}
+    real = ops.copy_multi
+
+    def counting(pairs):
+        calls.append(len(pairs))
+        return real(pairs)
+
+    def widest(gs, b, bs):
+        monkeypatch.setattr(ops, "copy_multi", counting)
+        gs.step(bs[0])
+        monkeypatch.setattr(ops, "copy_multi", real)
+        seen["launches"] = gs.library_launches
+    finals = {mode: _three_steps(tt, manifest, mode, 24, True, B=40, both_ids=True, after=widest) for mode in ("eager", "graph")}
+    print(f"widest hand-over: copy_multi segments per launch {calls}, library_launches {seen['launches']}")
+    _assert_graph_is_eager(finals)
+    assert calls == [8, 5]
+    assert seen["launches"] == WIDEST_LAUNCHES
 
 
 def test_xneg_other_captured_steps_refuse(tt, manifest):

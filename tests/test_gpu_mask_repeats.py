@@ -278,10 +278,10 @@ def test_mask_eager_vs_step_vs_step_from_store(tt, tmp_path):
             assert torch.equal(v, finals[mode][1][k]), (mode, k)
 
 
-def _small_task(tt, manifest, **kw):
+def _small_task(tt, manifest, B=64, **kw):
     from params_init import init_state_numpy, synth_batch_numpy
     cfg = dict(manifest["cases"]["wide_b40"])
-    cfg["B"] = 64
+    cfg["B"] = B
     task = make_task(tt, cfg, embedding_grad="sparse", mlp_dtype="fp32", **kw)
     shapes = {k: tuple(v.shape) for k, v in task.state_dict().items()}
     load_state(task, init_state_numpy(shapes, 77))

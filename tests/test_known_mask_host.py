@@ -237,30 +237,32 @@ def test_task_refusals_without_a_gpu():
     task = _cpu_task(score_dtype="bf16")
     for bad in (cells.long(), cells[:, 0], torch.zeros((3, 3), dtype=torch.int32), [[0, 1]]):
         with pytest.raises(ValueError):
-            task._batch_cells(_cpu_batch(masked_cells=bad), 6, None, None)
+            task._batch_terms(_cpu_batch(masked_cells=bad), 6)
     with pytest.raises(ValueError):
-        task._batch_cells(_cpu_batch(masked_cells=cells, masked_cells_count=torch.zeros(1)), 6, None, None)
+        task._batch_terms(_cpu_batch(masked_cells=cells, masked_cells_count=torch.zeros(1)), 6)
     with pytest.raises(ValueError):                            # with the repeated-entity mask
-        task._batch_cells(_cpu_batch(masked_cells=cells), 6, (torch.zeros(6, dtype=torch.int32), None), None)
+        b = _cpu_batch(masked_cells=cells)
+        b["notice"]["entity"] = torch.zeros(6, dtype=torch.int32)
+        task._batch_terms(b, 6)
     with pytest.raises(ValueError):                            # with pair weights
-        task._batch_cells(_cpu_batch(masked_cells=cells), 6, None, torch.ones(6))
-    assert task._batch_cells(_cpu_batch(), 6, None, None) is None
-    got = task._batch_cells(_cpu_batch(masked_cells=cells), 6, None, None)
+        task._batch_terms(_cpu_batch(masked_cells=cells, pair_weight=torch.ones(6)), 6)
+    assert task._batch_terms(_cpu_batch(), 6).cells is None
+    got = task._batch_terms(_cpu_batch(masked_cells=cells), 6).cells
     assert got[0] is cells and got[1] is None
     for dt in ("fp32", "fp8", "bf16x3"):
         with pytest.raises(ValueError):
-            _cpu_task(score_dtype=dt)._batch_cells(_cpu_batch(masked_cells=cells), 6, None, None)
+            _cpu_task(score_dtype=dt)._batch_terms(_cpu_batch(masked_cells=cells), 6)
     dense = _cpu_task(score_dtype="bf16")
     dense._dense_loss = True
     with pytest.raises(ValueError):
-        dense._batch_cells(_cpu_batch(masked_cells=cells), 6, None, None)
+        dense._batch_terms(_cpu_batch(masked_cells=cells), 6)
     with pytest.raises(ValueError):
         task.forward_with_ranks(_cpu_batch(masked_cells=cells))
-    task._cells_ok = lambda: False                             # what the sharded task answers
+    task._refused = frozenset({"masked_cells"})                # what the sharded task declares
     with pytest.raises(NotImplementedError):
-        task._batch_cells(_cpu_batch(masked_cells=cells), 6, None, None)
+        task._batch_terms(_cpu_batch(masked_cells=cells), 6)
     from jodalrob_twotower_amd.distributed import DistributedTwoTowerTrainTask
-    assert DistributedTwoTowerTrainTask._cells_ok(None) is False
+    assert "masked_cells" in DistributedTwoTowerTrainTask._refused
 
 
 def test_score_node_signature_keeps_positional_calls():

@@ -68,7 +68,7 @@ def test_log_sampling_probs_matches_bincount():
 
 
 def _fake_task(score_dtype="bf16", dense=False):
-    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense)
+    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense, _refused=frozenset())
 
 
 def _side(B, lq):
@@ -83,7 +83,8 @@ def test_task_refuses_log_q_it_does_not_cover():
     from jodalrob_twotower_amd.distributed import DistributedTwoTowerTrainTask
     B = 8
     lq = torch.zeros(B)
-    f = TwoTowerTrainTask._batch_log_q
+    def f(task, notice, company, B):
+        return TwoTowerTrainTask._batch_terms(task, {"notice": notice, "company": company}, B).lq
     assert f(_fake_task(), _side(B, None), _side(B, None), B) is None
     with pytest.raises(ValueError, match="fp8"):
         f(_fake_task("fp8"), _side(B, lq), _side(B, None), B)
@@ -103,7 +104,7 @@ def test_steps_declare_log_q_support():
     from jodalrob_twotower_amd.graph import GraphedTrainStep
     from jodalrob_twotower_amd.segmented import SegmentedTrainStep
     from jodalrob_twotower_amd.unrolled import UnrolledTrainStep
-    assert GraphedTrainStep._log_q_ok and not UnrolledTrainStep._log_q_ok and not SegmentedTrainStep._log_q_ok
+    assert "log_q" in GraphedTrainStep._accepts and "log_q" not in UnrolledTrainStep._accepts and "log_q" not in SegmentedTrainStep._accepts
 
 
 class _FakeStore:

@@ -117,7 +117,7 @@ def test_loader_refuses_an_index_beyond_int32():
 
 
 def _fake_task(score_dtype="bf16", dense=False):
-    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense)
+    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense, _refused=frozenset())
 
 
 def _side(B, ent):
@@ -132,7 +132,8 @@ def test_task_refuses_entity_ids_it_does_not_cover():
     from jodalrob_twotower_amd.distributed import DistributedTwoTowerTrainTask
     B = 8
     ent = torch.arange(B, dtype=torch.int32)
-    f = TwoTowerTrainTask._batch_entity
+    def f(task, notice, company, B):
+        return TwoTowerTrainTask._batch_terms(task, {"notice": notice, "company": company}, B).ent
     assert f(_fake_task(), _side(B, None), _side(B, None), B) is None
     for dt in ("fp8", "bf16x3"):
         with pytest.raises(ValueError, match=dt):
@@ -153,7 +154,7 @@ def test_unrolled_segmented_and_sharded_steps_refuse_entity_ids():
     from jodalrob_twotower_amd.graph import GraphedTrainStep
     from jodalrob_twotower_amd.segmented import SegmentedTrainStep
     from jodalrob_twotower_amd.unrolled import UnrolledTrainStep
-    assert GraphedTrainStep._entity_ok and not UnrolledTrainStep._entity_ok and not SegmentedTrainStep._entity_ok
+    assert "entity" in GraphedTrainStep._accepts and "entity" not in UnrolledTrainStep._accepts and "entity" not in SegmentedTrainStep._accepts
     ex = {"notice": {"dense": torch.zeros(4, 2), "entity": torch.zeros(4, dtype=torch.int32)}, "company": {"dense": torch.zeros(4, 2)}}
     with pytest.raises(NotImplementedError, match="UnrolledTrainStep"):
         UnrolledTrainStep(None, None, ex, unroll=2)

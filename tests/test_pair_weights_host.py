@@ -149,7 +149,7 @@ def test_inverse_count_weights():
 
 
 def _fake_task(score_dtype="bf16", dense=False):
-    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense)
+    return SimpleNamespace(score_dtype=score_dtype, _dense_loss=dense, _refused=frozenset())
 
 
 def _batch(B, w):
@@ -164,7 +164,8 @@ def test_task_refuses_pair_weights_it_does_not_cover():
     from jodalrob_twotower_amd.distributed import DistributedTwoTowerTrainTask
     B = 8
     w = torch.ones(B)
-    f = TwoTowerTrainTask._batch_pair_weight
+    def f(task, batch, B):
+        return TwoTowerTrainTask._batch_terms(task, batch, B).pw
     assert f(_fake_task(), _batch(B, None), B) is None
     assert f(_fake_task("fp32"), _batch(B, w), B) is w
     for dt in ("fp8", "bf16x3"):
@@ -192,7 +193,8 @@ def test_unrolled_segmented_and_sharded_steps_refuse_pair_weights():
     from jodalrob_twotower_amd.graph import GraphedTrainStep
     from jodalrob_twotower_amd.segmented import SegmentedTrainStep
     from jodalrob_twotower_amd.unrolled import UnrolledTrainStep
-    assert GraphedTrainStep._pair_weight_ok and not UnrolledTrainStep._pair_weight_ok and not SegmentedTrainStep._pair_weight_ok
+    assert "pair_weight" in GraphedTrainStep._accepts and "pair_weight" not in UnrolledTrainStep._accepts
+    assert "pair_weight" not in SegmentedTrainStep._accepts
     ex = {"notice": {"dense": torch.zeros(4, 2)}, "company": {"dense": torch.zeros(4, 2)}, "pair_weight": torch.ones(4)}
     with pytest.raises(NotImplementedError, match="UnrolledTrainStep"):
         UnrolledTrainStep(None, None, ex, unroll=2)
@@ -201,14 +203,14 @@ def test_unrolled_segmented_and_sharded_steps_refuse_pair_weights():
     with pytest.raises(NotImplementedError, match="sharded"):
         GraphedTrainStep(SimpleNamespace(exchange=object()), None, ex)
     # a captured step's with / without check (no device needed: the check comes first)
-    step = SimpleNamespace(_has_pair_weight=False)
-    assert GraphedTrainStep._pair_weight_pairs(step, None, "the batch") == []
+    step = SimpleNamespace(_terms=frozenset())
+    assert GraphedTrainStep._term_pairs(step, "pair_weight", None, "the batch") == []
     with pytest.raises(ValueError, match="pair_weight mismatch"):
-        GraphedTrainStep._pair_weight_pairs(step, torch.ones(4), "the batch")
-    step = SimpleNamespace(_has_pair_weight=True, static={"pair_weight": torch.zeros(4)})
+        GraphedTrainStep._term_pairs(step, "pair_weight", torch.ones(4), "the batch")
+    step = SimpleNamespace(_terms=frozenset({"pair_weight"}), static={"pair_weight": torch.zeros(4)})
     with pytest.raises(ValueError, match="pair_weight mismatch"):
-        GraphedTrainStep._pair_weight_pairs(step, None, "step_from_store")
+        GraphedTrainStep._term_pairs(step, "pair_weight", None, "step_from_store")
     with pytest.raises(ValueError, match="shape"):
-        GraphedTrainStep._pair_weight_pairs(step, torch.ones(5), "the batch")
-    (dst, src), = GraphedTrainStep._pair_weight_pairs(step, torch.ones(4), "the batch")
+        GraphedTrainStep._term_pairs(step, "pair_weight", torch.ones(5), "the batch")
+    (dst, src), = GraphedTrainStep._term_pairs(step, "pair_weight", torch.ones(4), "the batch")
     assert dst is step.static["pair_weight"] and src.data_ptr() % 16 == 0
