@@ -1186,6 +1186,49 @@ int tt_embed_bag_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, 
                           const int32_t* unique_rows, const int32_t* n_unique, int64_t nnz, int32_t mode, float* out,
                           void* workspace, size_t workspace_bytes, tt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The capacity form of the pooled lookup: what a captured step runs on static id buffers.  Launch geometry depends on the
+ * capacities alone; how many ids are live is device data.
+ *
+ * tt_embed_bag_fwd_cap: tt_embed_bag_fwd with side.nnz the CAPACITY of the side's id buffer; the live count is offsets[B*K].  Pooled
+ * outputs, and rows_out / bag_of of every position a bag covers, are bit for bit tt_embed_bag_fwd's.  Every other position of the
+ * side -- [offsets[B*K], capacity), and any position whose bag's offsets were refused -- gets rows_out = table_rows (the PAD ROW, one
+ * past the last row) and bag_of = -1, written by the whole grid in a grid-stride pass: rows_out / bag_of need no fill in front.
+ * The sides lie behind one another in position space (side 1 starts at side 0's capacity).  Nothing is read from ids at a
+ * position no bag covers: the tail of a static buffer holds stale ids.  table_rows < INT32_MAX.
+ *
+ * tt_bag_prepare, for every side (two launches, no wait between workgroups):
+ *   offsets[i] = lengths[0] + ... + lengths[i-1], i in [0, B*K]                     (int64)
+ *   inv_len[side_slot_base + i] = 1 / (float)lengths[i], one correctly rounded f32 division, where key_pool[i % K] is TT_POOL_MEAN
+ *                                 and lengths[i] > 0; 1 otherwise                   (inv_len may be NULL)
+ * A side with a negative length, with a total above `capacity`, or -- count not NULL -- with a total other than *count (the number
+ * of ids the host handed over, a device word) raises TT_DEVERR_BAG_OFFSETS and gets offsets all zero: its bags count as empty and
+ * nothing is read through them.  workspace: tt_bag_prepare_workspace_bytes(side_slots = B*K per side, n_sides), 8-byte aligned.
+ *
+ * tt_dedup_plan_pad: tt_dedup_plan over keys in [0, table_rows]; the key table_rows is the pad row.  It sorts last, stays in
+ * unique_rows / seg_offsets behind the real rows (seg_offsets[n_unique] is the end of the last real row) and is NOT counted in
+ * n_unique.  The sort is stable by position, so the real rows' segments list their positions in the order tt_dedup_plan gives on
+ * the live positions alone.  M = 0 and M pads (n_unique = 0) are valid.  Workspace: tt_dedup_workspace_bytes(M).
+ *
+ * The gradient: tt_embed_bag_grad_bwd with nnz = the total capacity; it visits the first n_unique rows only, so the pad segment is
+ * never read (sparse mode: out has room for capacity rows).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct tt_bag_lengths {
+  const int64_t* lengths;        /* [B*K] */
+  const int32_t* key_pool;       /* [K] TT_POOL_* (NULL allowed when inv_len is NULL) */
+  const int32_t* count;          /* device word: ids handed over, or NULL */
+  int64_t* offsets;              /* out [B*K + 1] */
+  int64_t capacity;
+  int32_t K;
+} tt_bag_lengths;
+int tt_embed_bag_fwd_cap(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                         int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream);
+size_t tt_bag_prepare_workspace_bytes(const int64_t* side_slots, int32_t n_sides);
+int tt_bag_prepare(tt_ctx* ctx, const tt_bag_lengths* sides, int32_t n_sides, int64_t B, float* inv_len, void* workspace,
+                   size_t workspace_bytes, tt_stream stream);
+int tt_dedup_plan_pad(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
+                      int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,10 @@ class BagSide(C.Structure):
                 ("ld_out", i64), ("nnz", i64), ("K", i32), ("out_dtype", i32)]
 
 
+class BagLengths(C.Structure):
+    _fields_ = [("lengths", vp), ("key_pool", vp), ("count", vp), ("offsets", vp), ("capacity", i64), ("K", i32)]
+
+
 class StoreSide(C.Structure):
     _fields_ = [("entity", vp), ("entity_stride", i64), ("dense_store", vp), ("cat_store", vp), ("dense_out", vp), ("ids_out", vp),
                 ("dense_dim", i32), ("n_rows", i32)]
@@ -244,6 +248,10 @@ SIGNATURES = {
     "tt_embed_bag_fwd": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, vp]),
     "tt_embed_bag_grad_workspace_bytes": (sz, [i64, i32]),
     "tt_embed_bag_grad_bwd": (C.c_int, [vp, C.POINTER(GradSrc), i32, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
+    "tt_embed_bag_fwd_cap": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, vp]),
+    "tt_bag_prepare_workspace_bytes": (sz, [C.POINTER(i64), i32]),
+    "tt_bag_prepare": (C.c_int, [vp, C.POINTER(BagLengths), i32, i64, vp, vp, sz, vp]),
+    "tt_dedup_plan_pad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -282,9 +282,10 @@ class CategoricalEmbedder(nn.Module):
     def bag_mode(self) -> bool:
         return self.pooling is not None
 
-    def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor) -> ops.BagSide:
+    def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor, count: Optional[torch.Tensor] = None) -> ops.BagSide:
+        """count: the device word of a captured step's static id buffer -- `values` is then that buffer, its size the capacity"""
         return ops.BagSide(values, lengths, self._key_row_offset, self._key_vocab, self._key_pool, out_view, len(self.keys),
-                           any(m == "mean" for m in self.pooling))
+                           any(m == "mean" for m in self.pooling), None if count is None else values.numel(), count)
 
     # ---- vocab sizes: src/towers/cat_embed.py:50-85 -------------------------------------------
     def _extract_vocab_sizes(self, metadata_path, table_name: str, keys: List[str]) -> Dict[str, int]:

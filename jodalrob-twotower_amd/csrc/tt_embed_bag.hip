@@ -36,6 +36,8 @@ struct BagSet {
   uint32_t* dev_err;
   int32_t* rows_out;
   int32_t* bag_of;
+  int32_t pad_row;       // < 0: tt_embed_bag_fwd.  >= 0 (table_rows): the capacity form -- every position no bag covers gets (pad_row, -1)
+  uint32_t total_pos;    // (capacity form) all sides' capacities
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float
       }
     }
     // positions behind the side's last bag belong to no bag: row 0, bag -1 (the gradient skips them)
-    if (slot + 1 == (si + 1 < a.n ? a.s[si + 1].slot_base : a.total_slots)) {
+    if (a.pad_row < 0 && slot + 1 == (si + 1 < a.n ? a.s[si + 1].slot_base : a.total_slots)) {
       const int64_t t0 = s.offs[local + 1];
       if (t0 >= 0 && t0 <= s.nnz)
         for (int64_t p = t0 + lig; p < s.nnz; p += LG) {
@@ -118,6 +120,183 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float
           if (a.bag_of) a.bag_of[s.pos_base + p] = -1;
         }
     }
+  }
+  if (a.pad_row < 0) return;
+  // capacity form: nnz is the CAPACITY of a static id buffer and the live count offs[B*K] is device data.  The whole grid walks
+  // position space (the sides lie behind one another: side 1 starts at side 0's capacity) and writes (pad_row, -1) wherever no
+  // bag covers: [live, capacity), and a position below `live` whose bag was refused above.  Nothing is read from ids here.
+  for (uint32_t P = gthread; P < a.total_pos; P += gridDim.x * blockDim.x) {
+    int si = 0;
+#pragma unroll
+    for (int i = 1; i < TT_MAX_SIDES; ++i)
+      if (i < a.n && P >= a.s[i].pos_base) si = i;
+    const BagSideDev& s = a.s[si];
+    const int64_t p = (int64_t)(P - s.pos_base);
+    const uint32_t S = (si + 1 < a.n ? a.s[si + 1].slot_base : a.total_slots) - s.slot_base;
+    const int64_t live = s.offs[S];
+    bool covered = false;
+    if (p < live) {
+      // the bag that holds p: the last slot whose offset is <= p (offsets ascend; where they do not, a pair was refused and
+      // the error word is up -- the search still stays inside [0, S])
+      uint32_t lo = 0, hi = S;                                 // first slot in (lo, hi] whose offset is > p
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s.offs[mid + 1] > p) hi = mid; else lo = mid + 1;
+      }
+      if (lo < S) {
+        const int64_t o0 = s.offs[lo], o1 = s.offs[lo + 1];
+        covered = o0 >= 0 && o0 <= p && p < o1 && o1 <= s.nnz;
+      }
+    }
+    if (!covered) {
+      if (a.rows_out) a.rows_out[P] = a.pad_row;
+      if (a.bag_of) a.bag_of[P] = -1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// tt_bag_prepare: offsets (exclusive prefix sum of the lengths) and mean weights of every side, grid-wide in two launches with no
+// wait between workgroups: tile totals, then every tile adds up its side's earlier totals (<= 2048 words) and scans its own part.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPrepPer = 8;                           // slots per thread: 64 bytes of lengths
+constexpr int kPrepTile = kThreads * kPrepPer;
+
+struct PrepSide {
+  const int64_t* lengths;
+  const int32_t* pool;
+  const int32_t* count;      // the id count the host handed over (device word), or NULL
+  int64_t* offs;
+  int64_t capacity;
+  uint32_t slots;            // B*K
+  uint32_t slot_base;
+  uint32_t tile_base;
+  int32_t K;
+};
+struct PrepSet {
+  PrepSide s[TT_MAX_SIDES];
+  int32_t n;
+  uint32_t tiles;
+  float* inv_len;            // [total slots] or NULL
+  int64_t* tile_sum;         // [tiles]; a tile with a negative length reports kPrepBad
+  uint32_t* dev_err;
+};
+constexpr int64_t kPrepBad = (int64_t)1 << 62;         // larger than any sum of 2^31 lengths that could fit a buffer
+
+__device__ __forceinline__ int prep_side_of(const PrepSet& a, uint32_t tile) {
+  int si = 0;
+#pragma unroll
+  for (int i = 1; i < TT_MAX_SIDES; ++i)
+    if (i < a.n && tile >= a.s[i].tile_base) si = i;
+  return si;
+}
+
+// the thread's kPrepPer lengths (0 behind the side's end): 16-byte loads where the whole run lies inside
+__device__ __forceinline__ void prep_load(const PrepSide& s, uint32_t first, int64_t (&len)[kPrepPer]) {
+  if (first + kPrepPer <= s.slots && (reinterpret_cast<uintptr_t>(s.lengths) & 15) == 0) {
+    const longlong2* q = reinterpret_cast<const longlong2*>(s.lengths + first);
+#pragma unroll
+    for (int j = 0; j < kPrepPer / 2; ++j) {
+      const longlong2 t = q[j];
+      len[2 * j] = t.x; len[2 * j + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kPrepPer; ++j) len[j] = first + j < s.slots ? s.lengths[first + j] : 0;
+  }
+}
+
+// sum over the workgroup (every thread gets it); sh: 2 * 4 words
+__device__ __forceinline__ int64_t prep_block_sum(int64_t v, int64_t* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(kThreads) void bag_prep_reduce_kernel(PrepSet a) {
+  __shared__ int64_t sh[8];
+  const PrepSide& s = a.s[prep_side_of(a, blockIdx.x)];
+  const uint32_t first = (blockIdx.x - s.tile_base) * kPrepTile + threadIdx.x * kPrepPer;
+  int64_t len[kPrepPer], t = 0, bad = 0;
+  prep_load(s, first, len);
+#pragma unroll
+  for (int j = 0; j < kPrepPer; ++j) {
+    bad |= (len[j] < 0 || len[j] > s.capacity) ? 1 : 0;      // (also keeps the sums far from overflow)
+    t += len[j];
+  }
+  const int64_t tot = prep_block_sum(t, sh);
+  const int64_t anybad = prep_block_sum(bad, sh + 4);
+  if (threadIdx.x == 0) a.tile_sum[blockIdx.x] = anybad ? kPrepBad : tot;
+}
+
+__global__ __launch_bounds__(kThreads) void bag_prep_scan_kernel(PrepSet a) {
+  __shared__ int64_t sh[8];
+  __shared__ int64_t wsum[4];
+  const int si = prep_side_of(a, blockIdx.x);
+  const PrepSide& s = a.s[si];
+  const uint32_t ntile = (si + 1 < a.n ? a.s[si + 1].tile_base : a.tiles) - s.tile_base, tile = blockIdx.x - s.tile_base;
+  // the side's total and this tile's start: integer sums, any order gives the same bits
+  int64_t before = 0, all = 0, bad = 0;
+  for (uint32_t b = threadIdx.x; b < ntile; b += kThreads) {
+    const int64_t v = a.tile_sum[s.tile_base + b];
+    bad |= v >= kPrepBad ? 1 : 0;
+    all += v >= kPrepBad ? 0 : v;
+    if (b < tile) before += v >= kPrepBad ? 0 : v;
+  }
+  before = prep_block_sum(before, sh);
+  all = prep_block_sum(all, sh + 4);
+  __syncthreads();
+  bad = prep_block_sum(bad, sh);
+  // refused: a negative length, a total above the capacity, or another total than the host handed over -- the side's bags then all
+  // count as empty (offsets all zero: every position of the side is a pad) and the context's error word says so
+  const bool refused = bad != 0 || all > s.capacity || (s.count && (int64_t)*s.count != all);
+  if (refused && tile == 0 && threadIdx.x == 0 && a.dev_err) atomicOr(a.dev_err, TT_DEVERR_BAG_OFFSETS);
+  const uint32_t first = tile * kPrepTile + threadIdx.x * kPrepPer;
+  int64_t len[kPrepPer], t = 0;
+  prep_load(s, first, len);
+#pragma unroll
+  for (int j = 0; j < kPrepPer; ++j) t += len[j];
+  int64_t x = t;                                             // inclusive scan of the threads' sums
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t y = __shfl_up(x, o);
+    if (lane >= (uint32_t)o) x += y;
+  }
+  __syncthreads();
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  int64_t run = before + x - t;
+  for (uint32_t w = 0; w < wave; ++w) run += wsum[w];
+  // offs[i] = sum of the lengths before slot i (16-byte stores where the run is whole); the side's last slot also writes offs[slots]
+  int64_t o[kPrepPer + 1];
+#pragma unroll
+  for (int j = 0; j <= kPrepPer; ++j) {
+    o[j] = refused ? 0 : run;
+    if (j < kPrepPer) run += len[j];
+  }
+  if (first + kPrepPer <= s.slots && (reinterpret_cast<uintptr_t>(s.offs) & 15) == 0) {
+    longlong2* q = reinterpret_cast<longlong2*>(s.offs + first);
+#pragma unroll
+    for (int j = 0; j < kPrepPer / 2; ++j) q[j] = make_longlong2(o[2 * j], o[2 * j + 1]);
+    if (first + kPrepPer == s.slots) s.offs[s.slots] = o[kPrepPer];
+  } else {
+#pragma unroll
+    for (int j = 0; j < kPrepPer; ++j)
+      if (first + j < s.slots) {
+        s.offs[first + j] = o[j];
+        if (first + j + 1 == s.slots) s.offs[s.slots] = o[j + 1];
+      }
+  }
+  if (a.inv_len) {
+#pragma unroll
+    for (int j = 0; j < kPrepPer; ++j)
+      if (first + j < s.slots) {
+        const uint32_t k = (first + j) % (uint32_t)s.K;
+        a.inv_len[s.slot_base + first + j] = (s.pool[k] != TT_POOL_SUM && len[j] > 0) ? __fdiv_rn(1.0f, (float)len[j]) : 1.0f;
+      }
   }
 }
 
@@ -259,10 +438,9 @@ static int bag_unsupported(const char* who, const char* what) {
 
 }  // namespace
 
-extern "C" {
-
-int tt_embed_bag_fwd(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
-                     int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream) {
+// tt_embed_bag_fwd (cap false) and its capacity form (cap true: nnz is each side's capacity, uncovered positions get table_rows / -1)
+static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                        int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream, bool cap) {
   TT_CHECK_ARG(ctx && table && sides, "tt_embed_bag_fwd: NULL argument");
   TT_CHECK_ARG(n_sides >= 1 && n_sides <= TT_MAX_SIDES, "tt_embed_bag_fwd: n_sides=%d not in [1,%d]", n_sides, TT_MAX_SIDES);
   TT_CHECK_ARG(B >= 0 && table_rows >= 1 && table_rows <= INT32_MAX, "tt_embed_bag_fwd: bad B=%lld rows=%lld", (long long)B, (long long)table_rows);
@@ -295,7 +473,66 @@ int tt_embed_bag_fwd(tt_ctx* ctx, const float* table, int64_t table_rows, int32_
   a.dev_err = ctx->dev_err;
   a.rows_out = rows_out;
   a.bag_of = bag_of;
-  bag_fwd_kernel<<<grid_for(ctx, slots * a.LG), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  a.pad_row = cap ? (int32_t)table_rows : -1;
+  a.total_pos = (uint32_t)positions;
+  // (capacity form: the grid is sized by the bags and the capacities, never by the live count)
+  const int64_t threads = cap && positions > slots * a.LG ? positions : slots * a.LG;
+  bag_fwd_kernel<<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
+extern "C" {
+
+int tt_embed_bag_fwd(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                     int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream) {
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, false);
+}
+
+int tt_embed_bag_fwd_cap(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                         int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream) {
+  TT_CHECK_ARG(table_rows < INT32_MAX, "tt_embed_bag_fwd_cap: no room for the pad row behind %lld rows", (long long)table_rows);
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, true);
+}
+
+size_t tt_bag_prepare_workspace_bytes(const int64_t* side_slots, int32_t n_sides) {
+  size_t tiles = 0;
+  for (int i = 0; side_slots && i < n_sides; ++i) tiles += (size_t)tt_cdiv(side_slots[i] > 0 ? side_slots[i] : 1, kPrepTile);
+  return sizeof(int64_t) * (tiles > 0 ? tiles : 1);
+}
+
+int tt_bag_prepare(tt_ctx* ctx, const tt_bag_lengths* sides, int32_t n_sides, int64_t B, float* inv_len, void* workspace,
+                   size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(ctx && sides && workspace, "tt_bag_prepare: NULL argument");
+  TT_CHECK_ARG(n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 0, "tt_bag_prepare: n_sides=%d B=%lld", n_sides, (long long)B);
+  if (!tt_aligned(workspace, 8)) return bag_unsupported("tt_bag_prepare", "the workspace must be 8-byte aligned");
+  PrepSet a{};
+  a.n = n_sides;
+  int64_t slots = 0, tiles = 0, per_side[TT_MAX_SIDES];
+  for (int i = 0; i < n_sides; ++i) {
+    const tt_bag_lengths& s = sides[i];
+    TT_CHECK_ARG(s.K >= 1 && s.capacity >= 0 && s.capacity < ((int64_t)1 << 31), "tt_bag_prepare: side %d has K=%d capacity=%lld", i, s.K,
+                 (long long)s.capacity);
+    TT_CHECK_ARG(s.lengths && s.offsets && (s.key_pool || !inv_len), "tt_bag_prepare: side %d has NULL pointers", i);
+    per_side[i] = B * s.K;
+    a.s[i] = PrepSide{s.lengths, s.key_pool, s.count, s.offsets, s.capacity, (uint32_t)per_side[i], (uint32_t)slots, (uint32_t)tiles, s.K};
+    slots += per_side[i];
+    tiles += tt_cdiv(per_side[i] > 0 ? per_side[i] : 1, kPrepTile);
+  }
+  TT_CHECK_ARG(slots < ((int64_t)1 << 31), "tt_bag_prepare: %lld bags exceed the 2^31 index range", (long long)slots);
+  if (slots == 0) return TT_OK;
+  if (workspace_bytes < tt_bag_prepare_workspace_bytes(per_side, n_sides)) {
+    tt_set_error("tt_bag_prepare: workspace %zu < required %zu", workspace_bytes, tt_bag_prepare_workspace_bytes(per_side, n_sides));
+    return TT_ERR_WORKSPACE;
+  }
+  a.tiles = (uint32_t)tiles;
+  a.inv_len = inv_len;
+  a.tile_sum = reinterpret_cast<int64_t*>(workspace);
+  a.dev_err = ctx->dev_err;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  bag_prep_reduce_kernel<<<(int)tiles, kThreads, 0, st>>>(a);
+  TT_LAUNCH_CHECK();
+  bag_prep_scan_kernel<<<(int)tiles, kThreads, 0, st>>>(a);
   TT_LAUNCH_CHECK();
   return TT_OK;
 }

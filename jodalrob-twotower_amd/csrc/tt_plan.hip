@@ -760,8 +760,10 @@ extern "C" {
 
 size_t tt_dedup_workspace_bytes(int64_t M) { return dedup_layout(nullptr, M).bytes; }
 
-int tt_dedup_plan(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
-                  int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream) {
+// tt_dedup_plan (pad false) and tt_dedup_plan_pad (pad true: keys in [0, table_rows], the key table_rows a pad that sorts last and is
+// not counted -- one more key value for the digit plan, drop_from for the heads)
+static int dedup_plan_impl(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
+                           int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream, bool pad) {
   TT_CHECK_ARG(ctx && sorted_src && unique_rows && seg_offsets && n_unique, "tt_dedup_plan: NULL output");
   TT_CHECK_ARG(M >= 0 && M < ((int64_t)1 << 31) - kSortTile, "tt_dedup_plan: M=%lld out of range", (long long)M);
   TT_CHECK_ARG(table_rows >= 1 && table_rows <= INT32_MAX, "tt_dedup_plan: table_rows=%lld out of range", (long long)table_rows);
@@ -779,7 +781,7 @@ int tt_dedup_plan(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_row
   DedupWs w = dedup_layout(reinterpret_cast<char*>(workspace), M);
   const uint32_t nblk = (uint32_t)tt_cdiv(M, kSortTile);
   int bits = 1;
-  while (((int64_t)1 << bits) < table_rows) ++bits;
+  while (((int64_t)1 << bits) < table_rows + (pad ? 1 : 0)) ++bits;
   // digit plan: fewest passes with 8- or 11-bit digits
   int digit = 8, passes = (bits + 7) / 8;
   if ((bits + 10) / 11 < passes) { digit = 11; passes = (bits + 10) / 11; }
@@ -796,7 +798,18 @@ int tt_dedup_plan(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_row
     kin = kout;
     vin = vout;
   }
-  return launch_heads(ctx, st, w, M, nblk, n_unique, unique_rows, seg_offsets, 0xFFFFFFFFu);
+  return launch_heads(ctx, st, w, M, nblk, n_unique, unique_rows, seg_offsets, pad ? (uint32_t)table_rows : 0xFFFFFFFFu);
+}
+
+int tt_dedup_plan(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
+                  int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  return dedup_plan_impl(ctx, rows, M, table_rows, sorted_src, unique_rows, seg_offsets, n_unique, workspace, workspace_bytes, stream, false);
+}
+
+int tt_dedup_plan_pad(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
+                      int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  TT_CHECK_ARG(table_rows < INT32_MAX, "tt_dedup_plan_pad: no room for the pad key behind %lld rows", (long long)table_rows);
+  return dedup_plan_impl(ctx, rows, M, table_rows, sorted_src, unique_rows, seg_offsets, n_unique, workspace, workspace_bytes, stream, true);
 }
 
 int tt_dedup_plan_runs(tt_ctx* ctx, const int32_t* rows, int32_t G, int64_t C, int64_t row_limit, int32_t* sorted_src,

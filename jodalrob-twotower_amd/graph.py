@@ -23,7 +23,7 @@ import torch
 from . import _lib as L
 from . import batch_terms as T
 from . import ops
-from .cat_embed import refuse_bag_mode
+from .cat_embed import bag_mode_embedders, refuse_bag_mode
 from .config import settings
 from .kjt import KeyedJaggedTensor
 from .optim import FusedAdam
@@ -34,6 +34,33 @@ _STEP = "the captured step"        # whose device the array checks name
 _CELLS, _NEGATIVES = T.ROWS["masked_cells"], T.ROWS["negatives"]
 
 
+def resolve_bag_capacity(bag_capacity, nnz: Dict[str, int]) -> Dict[str, int]:
+    """The capacity in ids of every bag-mode side's static id buffer.  bag_capacity: an int (every side), a {side: int} dict, or
+    "auto" (four times the example batch's ids, at least 1024, as cell_capacity); nnz: {side: ids of the example batch} of the
+    bag-mode sides.  ValueError for anything else, for a side the dict leaves out and for a capacity below the example's ids."""
+    out = {}
+    for side, n in nnz.items():
+        if isinstance(bag_capacity, str):
+            if bag_capacity != "auto":
+                raise ValueError(f"bag_capacity must be an int, a dict of ints per side or 'auto', got {bag_capacity!r}")
+            cap = max(4 * n, 1024)
+        elif isinstance(bag_capacity, dict):
+            unknown = [k for k in bag_capacity if k not in nnz]
+            if unknown:
+                raise ValueError(f"bag_capacity names sides that are not in bag mode: {unknown} (bag mode: {list(nnz)})")
+            if side not in bag_capacity:
+                raise ValueError(f"bag_capacity gives no capacity for the bag-mode side '{side}'")
+            cap = bag_capacity[side]
+        else:
+            cap = bag_capacity
+        if isinstance(cap, bool) or not isinstance(cap, int):
+            raise ValueError(f"bag_capacity must be an int, a dict of ints per side or 'auto', got {cap!r} for '{side}'")
+        if cap < max(n, 1):
+            raise ValueError(f"bag_capacity = {cap} for '{side}': the example batch carries {n} ids there (and at least 1)")
+        out[side] = cap
+    return out
+
+
 def _holders(static, row):
     """the dicts of the static buffers that hold `row`'s arrays under its key: one per side, or the top level"""
     return [static[side] for side in T.SIDES] if row.where == "side" else [static]
@@ -41,13 +68,15 @@ def _holders(static, row):
 
 class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
+    _bag_capture = True            # bag_capacity is honoured (the unrolled / segmented steps keep refusing bag mode)
+    _bag: Dict[str, int] = {}      # {side: capacity} of the bag-mode sides (none: a plain model)
     _accepts = frozenset(T.ROWS)   # the batch entries that change the loss (batch_terms.TABLE) an example batch may carry; the
                                    # unrolled / segmented steps take none
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
                  accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None, fuse_score_tail: bool = True,
-                 cell_capacity: Optional[int] = None):
+                 cell_capacity: Optional[int] = None, bag_capacity=None):
         """defer_long / defer_slabs: the long rows' finish rides in the optimiser's launch and the towers' slab reduction in the
         embedding gradient's (both bit-identical to the separate launches; the arguments exist for that comparison).
         fuse_score_tail: the score backward waits for the towers' backward, which launches it with its own first kernel's work in
@@ -61,7 +90,10 @@ class GraphedTrainStep:
         avg_train_loss: scripts/train.py:357-358) without a host sync per step.  metric_sums: add into THIS tensor (another captured
         step's sums: the two then share one epoch total; what it holds survives this object's warm-up).
         cell_capacity: rows of the static masked-cells buffer of a step captured on a batch with "masked_cells" (default: four times
-        the example's, at least 1024); a later batch with more cells is refused."""
+        the example's, at least 1024); a later batch with more cells is refused.
+        bag_capacity: None -- a bag-mode model (categorical_pooling) is refused; an int, a {"notice": n, "company": n} dict or "auto"
+        (four times the example batch's ids, at least 1024) -- the capacity in ids of every bag-mode side's static id buffer: the
+        captured step then runs the pooled lookup's capacity form, a later batch with more ids is refused."""
         # the example batch's entries that change the loss (batch_terms.TABLE): each gets static buffers -- [B] per side (a side the
         # batch does not carry: zeros / its row indices) or one [B]; the extras' M rows with whichever of log_q / entity they carry; an
         # int32 [capacity, 2] buffer of cells and a device count, one more word of the step's scalars -- filled at every hand-over by more
@@ -81,13 +113,13 @@ class GraphedTrainStep:
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
         # the static id buffers hold B*K ids: no ragged bags in a captured step -- refused here, once, so that step() and
         # step_from_store() of a bag-mode model cannot be reached (and pay no check per step)
-        refuse_bag_mode(task, type(self).__name__)
+        self._bag = self._bag_sides(task, example_batch, bag_capacity)           # {side: capacity} of the bag-mode sides
+        self.bag_capacity = dict(self._bag) or None
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
         self._defer_long, self._defer_slabs, self._defer_riders = bool(defer_long), bool(defer_slabs), bool(defer_riders)
         self._fuse_score_tail = bool(fuse_score_tail)
         dev = example_batch["notice"]["dense"].device
-        self.static = {side: {"dense": example_batch[side]["dense"].clone(),
-                              "kjt": KeyedJaggedTensor(example_batch[side]["kjt"].keys(), example_batch[side]["kjt"].values().clone())}
+        self.static = {side: {"dense": example_batch[side]["dense"].clone(), "kjt": self._static_kjt(example_batch[side]["kjt"], side, dev)}
                        for side in ("notice", "company")}
         B, self._fill = example_batch["notice"]["dense"].shape[0], {}
         for row in T.B_TERMS:
@@ -107,7 +139,8 @@ class GraphedTrainStep:
         ng = len(optimizer.param_groups)
         # per-step scalars (Adam step sizes, dropout seed, the masked cells' count) travel through a RING of pinned host slots: the copy
         # kernel reads the slot when it executes, and the host may be many steps ahead of the GPU by then
-        self._n_scalar = ng * 8 + 2 + (2 if _CELLS.key in self._terms else 0)
+        self._bag_word = ng * 8 + 2 + (2 if _CELLS.key in self._terms else 0)     # a bag-mode side's id count: one word each
+        self._n_scalar = self._bag_word + len(self._bag)
         self._slot_len = (self._n_scalar + 3) // 4 * 4                 # 16-byte slots
         self._ring = 64
         self._host_ring = torch.zeros(self._ring, self._slot_len, dtype=torch.float32).pin_memory()
@@ -127,6 +160,10 @@ class GraphedTrainStep:
             self.static["masked_cells"] = torch.zeros((cap, 2), dtype=torch.int32, device=dev)
             self.static["masked_cells"][:ex.shape[0]] = ex
             self.static["masked_cells_count"] = self._dev[ng * 8 + 2:ng * 8 + 3].view(torch.int32)      # (the scalars' copy fills it)
+        for i, side in enumerate(self._bag):       # the count word rides with the step's scalars; the warm-up reads the example's
+            word = self._dev[self._bag_word + i:self._bag_word + i + 1].view(torch.int32)
+            word.fill_(self._bag_n[side])
+            self.static[side]["kjt"].bag_count = word
         self._ones = torch.ones((), dtype=torch.float32, device=dev)
         self._towers = [m for m in task.modules() if hasattr(m, "_seed_dev") and hasattr(m, "dense_parameters")]
         self.metric_sums = torch.zeros(8, dtype=torch.float32, device=dev) if (accumulate_metrics and return_metrics) else None
@@ -173,6 +210,65 @@ class GraphedTrainStep:
         # the capture itself ran the host-side bookkeeping of one optimiser step (per captured body) without executing it
         optimizer.advance_steps(-self._steps_per_replay)
 
+    def _bag_sides(self, task, example_batch, bag_capacity) -> Dict[str, int]:
+        """{side: capacity} of the sides whose embedder pools bags, after the refusals (no device work)"""
+        self._bag_n = {}
+        if not bag_mode_embedders(task):
+            if bag_capacity is not None:
+                raise ValueError("bag_capacity: the model has no bag-mode embedder (categorical_pooling)")
+            return {}
+        # the static id buffers hold B*K ids: without a capacity no ragged bags in a captured step -- refused here, once, so that
+        # step() and step_from_store() of such a model cannot be reached (and pay no check per step)
+        if bag_capacity is None or not self._bag_capture:
+            refuse_bag_mode(task, type(self).__name__)
+        if _NEGATIVES.key in self._terms:          # (the company side would splice two padded id buffers)
+            raise NotImplementedError(f"{_NEGATIVES.phrase} {_NEGATIVES.verb} not supported by a captured bag-mode step")
+        model = getattr(task, "two_tower_model", None)
+        sides = {side: example_batch[side]["kjt"].values().numel() for side, name in (("notice", "notice_tower"), ("company", "company_tower"))
+                 if getattr(getattr(getattr(model, name, None), "categorical_embedder", None), "bag_mode", False)}
+        if not sides or getattr(task, "exchange", None) is not None:
+            refuse_bag_mode(task, type(self).__name__)
+        self._bag_n = dict(sides)                  # ids the static buffer holds now (the count word of the next hand-over)
+        return resolve_bag_capacity(bag_capacity, sides)
+
+    def _static_kjt(self, kjt, side, dev):
+        """the static KJT of a side: its ids; a bag-mode side: an id buffer of the capacity (the example's ids at its head) and the
+        [B*K] lengths (its count word is attached once the scalars exist)"""
+        if side not in self._bag:
+            return KeyedJaggedTensor(kjt.keys(), kjt.values().clone())
+        v = kjt.values().to(device=dev, dtype=torch.int64).reshape(-1)
+        buf = torch.zeros(self._bag[side], dtype=torch.int64, device=dev)
+        buf[:v.numel()] = v
+        return KeyedJaggedTensor(kjt.keys(), buf, kjt.lengths().to(device=dev, dtype=torch.int64).reshape(-1).clone())
+
+    def _bag_check(self, batch):
+        """a bag-mode side's ids fit the capacity and its lengths are B*K -- before anything is copied"""
+        if batch is None:
+            return
+        for side, cap in self._bag.items():
+            kjt, st = batch[side]["kjt"], self.static[side]["kjt"]
+            if kjt.values().numel() > cap:
+                raise ValueError(f"{side}: {kjt.values().numel()} ids, the step was captured with bag_capacity = {cap}")
+            if kjt.lengths().numel() != st.lengths().numel():
+                raise ValueError(f"{side}: {kjt.lengths().numel()} bag lengths, the captured step holds B*K = {st.lengths().numel()}")
+
+    def _bag_pairs(self, side, kjt):
+        """copy segments of a bag-mode side's ids (into the head of the static buffer) and lengths; the count goes with the scalars"""
+        st = self.static[side]["kjt"]
+        v, ln = kjt.values().reshape(-1), kjt.lengths().reshape(-1)
+        sv, sl = st.values(), st.lengths()
+        n = v.numel()
+        self._bag_n[side] = n
+        out = []
+        for dst, src in ((sv[:n], v), (sl, ln)):
+            if not dst.numel():
+                continue
+            if src.device == dst.device and src.dtype == dst.dtype:
+                out += T.segment(dst, src)
+            else:
+                dst.copy_(src, non_blocking=True)
+        return out
+
     def _capture(self, mode: str):
         """Captures self._body() into self.graph (ONE graph; segmented.SegmentedTrainStep cuts it at the collectives instead)."""
         self.graph = torch.cuda.CUDAGraph()
@@ -187,8 +283,8 @@ class GraphedTrainStep:
         per-key plan: returns (store, embedders, rows_km, static id tensors, B) or None (then the batch is handed over by plain
         copies and the plan gathers its rows out of the lookup's slot-major array)."""
         self._x_static, self._rows_sm = None, None
-        if not settings.graph_ingest or _NEGATIVES.key in self._terms:     # (extras: the company side is B + M rows)
-            return None
+        if not settings.graph_ingest or _NEGATIVES.key in self._terms or self._bag:     # (extras: the company side is B + M rows;
+            return None                                                                  # bags: a side holds any number of ids)
         model = getattr(self.task, "two_tower_model", None)
         towers = [getattr(model, n, None) for n in ("notice_tower", "company_tower")]
         if model is None or any(t is None for t in towers):
@@ -355,6 +451,12 @@ class GraphedTrainStep:
             e = tw.categorical_embedder
             if e.store is not store or not e.keys:
                 continue
+            if side in self._bag:                  # the key of a position follows from the lengths (a synchronisation: construction only)
+                kjt, K = self.static[side]["kjt"], len(e.keys)
+                key = torch.repeat_interleave(torch.arange(kjt.lengths().numel(), device=kjt.lengths().device) % K, kjt.lengths())
+                ids = kjt.values()[:self._bag_n[side]][:key.numel()]
+                rows.append(ids.clamp(min=0).minimum(e._key_vocab[key] - 1) + e._key_row_offset[key])
+                continue
             ids = self.static[side]["kjt"].values().view(-1, len(e.keys))
             if side == "company" and _NEGATIVES.key in self._terms:     # the extras go through the company tower too
                 ids = torch.cat([ids, self.static["negatives"]["kjt"].values().view(-1, len(e.keys))], 0)
@@ -439,6 +541,8 @@ class GraphedTrainStep:
         host[ng * 8:ng * 8 + 2].view(torch.int64).random_()
         if _CELLS.key in self._terms:
             host[ng * 8 + 2:ng * 8 + 4].view(torch.int32)[0] = self._cells_n
+        for i, side in enumerate(self._bag):
+            host[self._bag_word + i:self._bag_word + i + 1].view(torch.int32)[0] = self._bag_n[side]
         return (self._dev, host)
 
     def _mark_slot(self):
@@ -524,6 +628,14 @@ class GraphedTrainStep:
         for side in ("notice", "company"):
             d, v = batch[side]["dense"], batch[side]["kjt"].values()
             sd, sv = self.static[side]["dense"], self.static[side]["kjt"].values()
+            if side in self._bag:
+                if d.device == sd.device and d.dtype == sd.dtype and d.is_contiguous():
+                    pairs += [(sd, d)]
+                else:
+                    sd.copy_(d, non_blocking=True)
+                pairs += self._bag_pairs(side, batch[side]["kjt"])
+                src_ids.append(sv)
+                continue
             if d.device == sd.device and d.dtype == sd.dtype and v.dtype == sv.dtype and d.is_contiguous() and v.is_contiguous():
                 pairs += [(sd, d), (sv, v)]
                 src_ids.append(v)
@@ -536,6 +648,7 @@ class GraphedTrainStep:
     def step(self, batch: Optional[Dict] = None):
         """Train on `batch` (or on whatever the static buffers hold); returns the static result."""
         cells = self._cells_check(batch)
+        self._bag_check(batch)
         pairs, src_ids = self._handover_pairs(batch)
         pairs += self._cells_pairs(cells)
         if self._ingest is not None:
@@ -575,6 +688,8 @@ class GraphedTrainStep:
         for row in (_CELLS, _NEGATIVES):
             if row.key in self._terms:
                 raise NotImplementedError(f"{row.noun}: no store-fed hand-over -- a step captured with '{row.key}' takes step(batch)")
+        if self._bag:                              # (a DeviceFeatureStore holds one id per key)
+            refuse_bag_mode(self.task, "step_from_store")
         given, extra = {"log_q": log_q, "entity": entity, "pair_weight": pair_weight}, []
         for row in T.B_TERMS:
             extra += self._term_pairs(row.key, given[row.key], "step_from_store")

@@ -18,6 +18,10 @@ class KeyedJaggedTensor:
         self._keys = list(keys)
         self._values = values
         self._lengths = lengths
+        # a captured bag-mode step's static KJT (graph.GraphedTrainStep(bag_capacity=...)): values() is an id buffer of a fixed capacity
+        # and bag_count the int32 device word with the number of ids handed over -- the towers then run the pooled lookup's
+        # capacity form (ops.BagSide.capacity).  None everywhere else.
+        self.bag_count = None
 
     @classmethod
     def from_lengths_sync(cls, keys, values, lengths):
@@ -36,7 +40,9 @@ class KeyedJaggedTensor:
 
     def to(self, device, non_blocking: bool = False) -> "KeyedJaggedTensor":
         lengths = None if self._lengths is None else self._lengths.to(device, non_blocking=non_blocking)
-        return KeyedJaggedTensor(self._keys, self._values.to(device, non_blocking=non_blocking), lengths)
+        out = KeyedJaggedTensor(self._keys, self._values.to(device, non_blocking=non_blocking), lengths)
+        out.bag_count = None if self.bag_count is None else self.bag_count.to(device, non_blocking=non_blocking)
+        return out
 
     def device(self) -> torch.device:
         return self._values.device

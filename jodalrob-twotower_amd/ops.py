@@ -303,38 +303,125 @@ class BagSide:
     out: torch.Tensor             # 2-D view [B, K*E] inside the destination buffer (row stride = ld)
     K: int
     any_mean: bool = True         # host copy of (key_pool == mean).any(): with no mean key the gradient needs no weights
+    capacity: Optional[int] = None   # the CAPACITY form (a captured step's static buffers): ids holds `capacity` ids, of which the
+                                     # first sum(lengths) are live -- device data; the tail is stale and never read
+    count: Optional[torch.Tensor] = None   # (capacity form) int32 [1] on the device: the id count the host handed over, compared
+                                           # with sum(lengths) on the device; None: not compared
 
 
 class BagPlan(NamedTuple):
     """What embed_bag_lookup leaves for embed_bag_grad: rows / bag_of per position (int32 [nnz]), inv_len per slot (f32, None when
-    every key sums), nnz."""
+    every key sums), nnz.  The capacity form: nnz is the sides' total capacity and pad_row (= table rows) what `rows` holds where no
+    bag covers -- the plan over such rows is bag_dedup_plan's padded one."""
     rows: torch.Tensor
     bag_of: torch.Tensor
     inv_len: Optional[torch.Tensor]
     nnz: int
+    pad_row: Optional[int] = None
+
+
+def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
+    if s.ids.dtype != torch.int64 or not s.ids.is_contiguous() or s.ids.device != dev:
+        raise ValueError("bag ids must be a contiguous int64 tensor on the table's device")
+    if s.lengths.numel() != B * s.K or s.lengths.device != dev:
+        raise ValueError(f"side {i}: {s.lengths.numel()} bag lengths for B={B}, K={s.K} (on the table's device)")
+    for name, t, dt, n in (("key_row_offset", s.key_row_offset, torch.int64, s.K), ("key_vocab", s.key_vocab, torch.int64, s.K),
+                           ("key_pool", s.key_pool, torch.int32, s.K)):
+        if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"side {i}: {name} must be a contiguous {dt} tensor of {n} elements on the table's device")
+    if s.out.device != dev or s.out.dim() != 2 or s.out.shape[0] != B or s.out.shape[1] != s.K * E:
+        raise ValueError(f"side {i}: out must be a [B, K*E] = [{B}, {s.K * E}] view on the table's device")
+    assert s.out.stride(1) == 1
+
+
+def bag_prepare(lengths: Sequence[torch.Tensor], key_pools: Sequence[torch.Tensor], Ks: Sequence[int], B: int, capacities: Sequence[int],
+                counts: Optional[Sequence[Optional[torch.Tensor]]] = None, want_inv_len: bool = True):
+    """tt_bag_prepare: per side the offsets (int64 [B*K + 1], exclusive prefix sum of the int64 `lengths`) and, for all sides, inv_len
+    (f32 per slot: 1 / length for a mean key's non-empty bag, 1 otherwise) -- the values embed_bag_lookup's torch formulas give.  A side
+    whose total exceeds its capacity or differs from its count word (int32 [1], device) raises the device error word and gets
+    offsets all zero.  Returns (offsets per side, inv_len or None)."""
+    dev, n = lengths[0].device, len(lengths)
+    arr = (L.BagLengths * n)()
+    offs, slots = [], (L.i64 * n)()
+    for i, (ln, pool, K, cap) in enumerate(zip(lengths, key_pools, Ks, capacities)):
+        if ln.dtype != torch.int64 or not ln.is_contiguous() or ln.numel() != B * K or ln.device != dev:
+            raise ValueError(f"side {i}: lengths must be a contiguous int64 tensor of B*K = {B * K} elements on one device")
+        if pool.dtype != torch.int32 or pool.numel() != K or pool.device != dev or not pool.is_contiguous():
+            raise ValueError(f"side {i}: key_pool must be a contiguous int32 tensor of {K} elements on the lengths' device")
+        cnt = None if counts is None else counts[i]
+        if cnt is not None and (cnt.dtype != torch.int32 or cnt.numel() != 1 or cnt.device != dev):
+            raise ValueError(f"side {i}: the count must be one int32 word on the lengths' device")
+        off = torch.empty(B * K + 1, dtype=torch.int64, device=dev)
+        offs.append(off)
+        slots[i] = B * K
+        arr[i] = L.BagLengths(L.ptr(ln), L.ptr(pool), L.ptr(cnt), L.ptr(off), int(cap), K)
+    inv_len = torch.empty(sum(B * K for K in Ks), dtype=torch.float32, device=dev) if want_inv_len else None
+    lib = L.load()
+    ws = torch.empty(lib.tt_bag_prepare_workspace_bytes(slots, n) // 8, dtype=torch.int64, device=dev)
+    with _timed("tt_bag_prepare"):
+        L.check(lib.tt_bag_prepare(L.ctx(dev), arr, n, B, L.ptr(inv_len), L.ptr(ws), ws.numel() * 8, L.stream(dev)), "tt_bag_prepare")
+    return offs, inv_len
+
+
+def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int, want_rows: bool) -> Optional[BagPlan]:
+    """The capacity form of embed_bag_lookup: tt_bag_prepare + tt_embed_bag_fwd_cap.  No launch here depends on how many ids are live."""
+    dev, E = table.device, table.shape[1]
+    for i, s in enumerate(sides):
+        _check_bag_side(i, s, B, E, dev)
+        if s.capacity is None or s.capacity != s.ids.numel():
+            raise ValueError(f"side {i}: the capacity form takes every side with capacity = ids.numel() (got {s.capacity}, {s.ids.numel()} ids)")
+    any_mean = any(s.any_mean for s in sides)
+    offs, inv_len = bag_prepare([s.lengths.reshape(-1) for s in sides], [s.key_pool for s in sides], [s.K for s in sides], B,
+                                [s.capacity for s in sides], [s.count for s in sides], want_inv_len=want_rows and any_mean)
+    arr = (L.BagSide * len(sides))()
+    for i, (s, off) in enumerate(zip(sides, offs)):
+        arr[i] = L.BagSide(L.ptr(s.ids), L.ptr(off), L.ptr(s.key_row_offset), L.ptr(s.key_vocab), L.ptr(s.key_pool), L.ptr(s.out),
+                           s.out.stride(0), s.capacity, s.K, _dt(s.out))
+    cap = sum(s.capacity for s in sides)
+    idx = torch.empty((2, max(cap, 1)), dtype=torch.int32, device=dev) if want_rows else None      # (the launch writes every position)
+    with _timed("tt_embed_bag_fwd"):
+        L.check(L.load().tt_embed_bag_fwd_cap(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                              L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
+                "tt_embed_bag_fwd_cap")
+    if not want_rows:
+        return None
+    return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0])
+
+
+def bag_dedup_plan(bag: BagPlan, table_rows: int) -> DedupPlan:
+    """The duplicate-row plan over a pooled lookup's positions: dedup_plan, or for the capacity form tt_dedup_plan_pad (M = the
+    capacity; the pad row sorts last and is not counted in n_unique)."""
+    if bag.pad_row is None:
+        return dedup_plan(bag.rows, table_rows)
+    if bag.pad_row != table_rows:
+        raise ValueError(f"the bags' pad row is {bag.pad_row}, the table has {table_rows} rows")
+    rows = bag.rows
+    dev, M = rows.device, rows.numel()
+    buf = torch.empty(3 * M + 2, dtype=torch.int32, device=dev)
+    plan = DedupPlan(buf[:M], buf[M:2 * M], buf[2 * M:3 * M + 1], buf[3 * M + 1:], M)
+    lib = L.load()
+    ws = L.workspace(dev, lib.tt_dedup_workspace_bytes(M))
+    with _timed("tt_dedup_plan"):
+        L.check(lib.tt_dedup_plan_pad(L.ctx(dev), L.ptr(rows), M, table_rows, L.ptr(plan.sorted_src), L.ptr(plan.unique_rows),
+                                      L.ptr(plan.seg_offsets), L.ptr(plan.n_unique), L.ptr(ws), ws.numel(), L.stream(dev)),
+                "tt_dedup_plan_pad")
+    return plan
 
 
 def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want_rows: bool) -> Optional[BagPlan]:
     """tt_embed_bag_fwd: pooled lookup of every side's bags into side.out.  The offsets are torch.cumsum of the lengths and the
     mean weights 1 / length, both formed on the device: no host synchronisation.  sum(lengths) must equal ids.numel() (ids the
-    lengths leave over belong to no bag; lengths that ask for more raise the context's device error word)."""
+    lengths leave over belong to no bag; lengths that ask for more raise the context's device error word).  Sides with a
+    `capacity` take the capacity form (every side then): tt_bag_prepare + tt_embed_bag_fwd_cap, the same pooled bits."""
     dev, E = table.device, table.shape[1]
     if table.dtype != torch.float32 or not table.is_contiguous():
         raise ValueError("the table must be a contiguous float32 [rows, E] tensor")
+    if any(s.capacity is not None for s in sides):
+        return _embed_bag_lookup_cap(table, sides, B, want_rows)
     arr = (L.BagSide * len(sides))()
     keep, nnz, inv = [], 0, []
     for i, s in enumerate(sides):
-        if s.ids.dtype != torch.int64 or not s.ids.is_contiguous() or s.ids.device != dev:
-            raise ValueError("bag ids must be a contiguous int64 tensor on the table's device")
-        if s.lengths.numel() != B * s.K or s.lengths.device != dev:
-            raise ValueError(f"side {i}: {s.lengths.numel()} bag lengths for B={B}, K={s.K} (on the table's device)")
-        for name, t, dt, n in (("key_row_offset", s.key_row_offset, torch.int64, s.K), ("key_vocab", s.key_vocab, torch.int64, s.K),
-                               ("key_pool", s.key_pool, torch.int32, s.K)):
-            if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
-                raise ValueError(f"side {i}: {name} must be a contiguous {dt} tensor of {n} elements on the table's device")
-        if s.out.device != dev or s.out.dim() != 2 or s.out.shape[0] != B or s.out.shape[1] != s.K * E:
-            raise ValueError(f"side {i}: out must be a [B, K*E] = [{B}, {s.K * E}] view on the table's device")
-        assert s.out.stride(1) == 1
+        _check_bag_side(i, s, B, E, dev)
         lengths = s.lengths.to(torch.int64).reshape(-1)
         off = torch.zeros(B * s.K + 1, dtype=torch.int64, device=dev)
         torch.cumsum(lengths, 0, out=off[1:])

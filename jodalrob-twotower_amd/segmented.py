@@ -88,6 +88,7 @@ class _SegmentingComm(DistComm):
 
 class SegmentedTrainStep(GraphedTrainStep):
     """GraphedTrainStep whose capture is cut at every collective (see the module docstring).  Same interface and results."""
+    _bag_capture = False           # bag mode stays refused here, with or without bag_capacity
     _accepts = frozenset()         # batch entries that change the loss (batch_terms.TABLE) are out of scope here: refused
 
     segmented = True

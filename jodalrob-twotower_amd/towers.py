@@ -283,7 +283,11 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
         kjt = kjt.to(dev) if hasattr(kjt, "to") else kjt
         values = kjt.values()
         # a bag-mode embedder also reads the bags' lengths; any other reads the values only, as before
-        bag_lengths.append(kjt.lengths() if tw.categorical_embedder.bag_mode else None)
+        # (a captured step's static KJT: values() is a buffer of a fixed capacity and bag_count the device word with the id count the
+        # host handed over -- the pair says "capacity form": ops.BagSide)
+        count = getattr(kjt, "bag_count", None)
+        lengths = kjt.lengths() if tw.categorical_embedder.bag_mode else None
+        bag_lengths.append(lengths if count is None or lengths is None else (lengths, count))
         flat += [dense, values] + tw.dense_parameters() + tw.categorical_embedder.table_parameters()
     outs = _TowersFn.apply(tuple(towers), tuple(bag_lengths), *flat)
     outs = list(outs) if isinstance(outs, tuple) else [outs]
@@ -295,7 +299,7 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
 
 class _Side:
     __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values",
-                 "lengths")
+                 "lengths", "count")
 
 
 class _TowersFn(torch.autograd.Function):
@@ -322,6 +326,9 @@ class _TowersFn(torch.autograd.Function):
             dense = dense.to(dtype=torch.float32).contiguous()
             values = values.to(dtype=torch.int64).contiguous()
             B, K, E = dense.shape[0], len(emb.keys), emb.embedding_dim
+            count = None
+            if isinstance(lengths, tuple):      # (lengths, count): the capacity form
+                lengths, count = lengths
             if emb.bag_mode:
                 if lengths is None or lengths.numel() != B * K:
                     raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
@@ -333,6 +340,7 @@ class _TowersFn(torch.autograd.Function):
                 raise ValueError(f"kjt carries {values.numel()} ids but the batch needs B*K = {B}*{K}")
             s = _Side()
             s.lengths = lengths if emb.bag_mode else None
+            s.count = count if emb.bag_mode else None
             s.tower, s.B, s.train = tw, B, tw.training
             s.p_drop = tw.dropout_rate if tw.training else 0.0
             s.seed = 0 if s.p_drop <= 0 else (tw._seed_override if tw._seed_override is not None else
@@ -390,7 +398,7 @@ class _TowersFn(torch.autograd.Function):
                 a.emb_packed, a.emb_pack_scale = s.packed.data_ptr(), float(tw.pack_scale)
             s.acts_struct = a
             if K and B and emb.bag_mode:     # pooled bags: launches and plans of their own, beside the plain sides of the store
-                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:])))
+                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:], s.count)))
             elif K and B:
                 lookups.setdefault(id(emb.store), []).append((s, emb.lookup_side(values, s.x[:, tw.tower_hidden_dims[0]:]), px is not None))
         # fused lookup (+ duplicate-row plan when a backward will follow) per store
@@ -433,7 +441,7 @@ class _TowersFn(torch.autograd.Function):
             store = group[0][0].tower.categorical_embedder.store
             bag = ops.embed_bag_lookup(store.weight, [g[1] for g in group], group[0][0].B, want_rows=grad_on)
             if bag is not None and bag.nnz:
-                bag_plans.append((store, [g[0] for g in group], ops.dedup_plan(bag.rows, store.rows), bag))
+                bag_plans.append((store, [g[0] for g in group], ops.bag_dedup_plan(bag, store.rows), bag))
         ctx.bag_plans = bag_plans
         # duplicate-row plans: depend on ids only, first needed in the backward.  In line on the launch stream (a side stream
         # overlapped the sort with the score kernels, but a captured graph with two streams is replayed node by node with

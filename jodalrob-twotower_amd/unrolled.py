@@ -28,6 +28,7 @@ from .kjt import KeyedJaggedTensor
 class UnrolledTrainStep(GraphedTrainStep):
     """GraphedTrainStep with `unroll` steps per graph launch: `step_many(batches)` / `steps_from_store(..., offsets)` run `unroll`
     steps; `step` / `step_from_store` (one step: an epoch's remainder) go through a single-step sibling captured on first use."""
+    _bag_capture = False           # bag mode stays refused here, with or without bag_capacity
     _accepts = frozenset()         # batch entries that change the loss (batch_terms.TABLE) are out of scope here: refused
 
     def __init__(self, task, optimizer, example_batch: Dict, unroll: int = 2, **kw):

@@ -140,6 +140,13 @@ def main():
                          "mean (bag mode; eager loop only).  The synthetic stores hold one id per key: every training batch draws "
                          "--pool-length more ids per bag on average; evaluation feeds each entity's own id as a bag of one")
     ap.add_argument("--pool-length", type=float, default=4.0, help="mean bag length of the --pool keys' synthetic bags")
+    ap.add_argument("--pool-capture", nargs="?", type=float, const=2.0, default=None, metavar="FACTOR",
+                    help="with --pool: the pooled loop runs as a captured step (GraphedTrainStep(bag_capacity=...)) whose static id "
+                         "buffers hold FACTOR (default 2) times the first batch's ids per bag-mode side; a batch that does not fit "
+                         "takes the eager step and is counted")
+    ap.add_argument("--seed", type=int, default=None, help="seed torch's generators (weights, dropout) before the model is built")
+    ap.add_argument("--dropout-rate", type=float, default=0.1, help="the towers' dropout rate (reference: 0.1)")
+    ap.add_argument("--log-interval", type=int, default=20, help="steps between the loop's progress lines (reference: 20)")
     a = ap.parse_args()
     pooling = None
     if a.pool:
@@ -151,6 +158,12 @@ def main():
             if mode not in ("sum", "mean"):
                 ap.error(f"--pool {item!r}: expected KEY=sum or KEY=mean")
             pooling[key] = mode
+    if a.pool_capture is not None and not a.pool:
+        ap.error("--pool-capture needs --pool")
+    if a.pool_capture is not None and a.pool_capture < 1.0:
+        ap.error("--pool-capture FACTOR must be >= 1")
+    if a.log_interval < 1:
+        ap.error("--log-interval must be >= 1")
     if a.mask_known and (a.mask_repeats or a.pair_weight):
         ap.error("--mask-known does not combine with --mask-repeats (its cells hold every repeat) or --pair-weight")
     if a.mask_known and not a.fast:
@@ -161,12 +174,14 @@ def main():
         ap.error("--mine-negatives / --hard-fraction need --extra-negatives M")
     config = {"batch_size": a.batch_size, "test_split": 0.2, "shuffle_seed": 42, "pair_limit": a.pairs,
               "categorical_embedding_dim": 32, "notice_dense_input_dim": 256, "company_dense_input_dim": 128,
-              "tower_hidden_dims": [int(h) for h in a.hidden.split(",")], "final_embedding_dim": a.final_dim, "dropout_rate": 0.1,
+              "tower_hidden_dims": [int(h) for h in a.hidden.split(",")], "final_embedding_dim": a.final_dim, "dropout_rate": a.dropout_rate,
               "temperature": 1.0, "loss_type": "cross_entropy", "learning_rate": 1e-3, "weight_decay": 1e-5, "num_epochs": a.epochs,
-              "warmup_ratio": 0.05, "log_interval": 20, "output_dir": a.output_dir,
+              "warmup_ratio": 0.05, "log_interval": a.log_interval, "output_dir": a.output_dir,
               "gpu_optimization": ("MI355X HIP graph replay + device-resident stores + bf16 MFMA / sparse FusedAdam" if a.fast
                                    else "MI355X HIP kernels, eager, f32 parity mode")}
     device = torch.device("cuda:0")
+    if a.seed is not None:
+        torch.manual_seed(a.seed)
     real = synthetic.load_real_schema(ROOT / "jodalrob-twotower_amd" / "schema_real.json")
     tmp = Path(tempfile.mkdtemp(prefix="tt_train_"))
     meta_rows = [synthetic.META_HEADER]
@@ -226,12 +241,29 @@ def main():
     if start_epoch >= config["num_epochs"]:
         config["num_epochs"] = start_epoch + 1           # resumed after the last epoch: run one more
 
+    pool_step, pool_eager = None, 0                      # --pool-capture: the captured bag-mode step; batches that took the eager one
+
     def eager_step(batch):
+        nonlocal pool_step, pool_eager
         if pooling:                                      # ragged bags for the pooled keys, drawn per step (seeded by the step number)
             batch = dict(batch)
             for side in ("notice", "company"):
                 batch[side] = dict(batch[side], kjt=synthetic.ragged_bags(batch[side]["kjt"], real[side]["vocab_sizes"], pooling,
                                                                           a.pool_length, seed=config["shuffle_seed"] + steps))
+        if a.pool_capture is not None and train_task.training:
+            if pool_step is None:                        # captured on the first batch (its warm-up leaves no trace: preserve_state)
+                import math
+                from jodalrob_twotower_amd.graph import GraphedTrainStep
+                model = train_task.two_tower_model
+                caps = {side: max(1, math.ceil(a.pool_capture * batch[side]["kjt"].values().numel()))
+                        for side, tw in (("notice", model.notice_tower), ("company", model.company_tower)) if tw.categorical_embedder.bag_mode}
+                pool_step = GraphedTrainStep(train_task, optimizer, batch, warmup=1, bag_capacity=caps)
+                print(f"--pool-capture: captured with bag_capacity = {caps}")
+            fits = batch["notice"]["dense"].shape == pool_step.static["notice"]["dense"].shape and \
+                all(batch[side]["kjt"].values().numel() <= cap for side, cap in pool_step.bag_capacity.items())
+            if fits:
+                return pool_step.step(batch)
+            pool_eager += 1                              # a fuller (or the epoch's last, smaller) batch
         optimizer.zero_grad()
         result = train_task(batch, return_metrics=True)
         result["loss"].backward()
@@ -341,6 +373,10 @@ def main():
             break
     torch.cuda.synchronize()
     t_epochs = time.time() - t_loop
+    if a.pool_capture is not None:
+        print(f"--pool-capture: {steps - pool_eager} captured steps, {pool_eager} batches took the eager step")
+        if pool_step is not None:
+            pool_step.close()
     print(f"throughput: {pairs_seen / t_epochs:,.0f} pairs/s over {steps} steps incl. evaluation "
           f"({'fast: captured step fed from the device stores' if a.fast else 'eager reference loop'}); "
           f"training {t_train * 1e3:.1f} ms = {pairs_seen / max(t_train, 1e-9):,.0f} pairs/s = {t_train * 1e3 / max(steps, 1):.4f} ms/step, "
