@@ -1229,6 +1229,50 @@ int tt_bag_prepare(tt_ctx* ctx, const tt_bag_lengths* sides, int32_t n_sides, in
 int tt_dedup_plan_pad(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table_rows, int32_t* sorted_src, int32_t* unique_rows,
                       int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The batch gather out of a device-resident store of per-entity BAGS: tt_batch_ingest_store's two-level gather (pair -> entity
+ * row -> features) for multi-valued features, into the sample-major bag wire format a captured bag-mode step's static buffers
+ * hold.  A store keeps dense_store f32 [N, dense_dim] and its bags as CSR over (entity, key) slots: the bag of entity e, key k
+ * is values[offsets[e*K + k] .. offsets[e*K + k + 1]), so an entity's K bags are ONE contiguous run of ids.  For side i,
+ * sample b (o and e as in tt_batch_ingest_store; e is always clamped into [0, n_rows)):
+ *   dense_out[b, :]        = dense_store[e, :]                                         (f32 copy)
+ *   lengths_out[b*K + k]   = offsets[e*K + k + 1] - offsets[e*K + k]
+ *   ids_out[start_b .. start_b + run_b) = values[offsets[e*K] .. offsets[(e+1)*K]),    run_b = that run's length,
+ *                                         start_b = run_0 + ... + run_(b-1)            (the offsets tt_bag_prepare forms again)
+ * plus the n copy segments (the step scalars: the count word of a captured step travels there -- this entry does not read it).
+ * Two launches, no workgroup waits on another: lengths, dense rows, copy segments and one total per tile of tt_bag_store_tile()
+ * samples; then every tile's workgroups add up the side's earlier totals, scan their tile and copy its ids -- 16-byte stores on the
+ * destination's 16-byte grid fed by 16-byte loads where the source is aligned alike and by 8-byte loads otherwise (ids_out may be
+ * 8 mod 16); a position is found in its tile's runs by bisection, so a long run spreads over lanes and workgroups.
+ * total = run_0 + ... + run_(B-1).  With total > capacity, or total != expect when expect >= 0, NO id is written and
+ * TT_DEVERR_BAG_OFFSETS is raised; lengths, dense rows and copy segments are written all the same (tt_bag_prepare then refuses
+ * the side through its own checks).  Nothing is ever written at or beyond ids_out[capacity]; ids_out[total .. capacity) keeps what
+ * it held.  A run that leaves [0, nnz] (offsets the store's owner did not validate) refuses the side the same way and is not read.
+ * workspace: tt_bag_store_gather_workspace_bytes(B, n_sides), 8-byte aligned.  B * K < 2^31, capacity < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct tt_bag_store_side {
+  const int64_t* entity;     /* entity index per pair, read at [o * entity_stride] */
+  int64_t entity_stride;
+  const float* dense_store;  /* [N, dense_dim] */
+  const int64_t* offsets;    /* [N*K + 1] */
+  const int64_t* values;     /* [nnz] */
+  float* dense_out;          /* [B, dense_dim] */
+  int64_t* lengths_out;      /* [B*K] */
+  int64_t* ids_out;          /* [capacity] */
+  int64_t nnz;
+  int64_t capacity;
+  int64_t expect;            /* the id count the host believes (what it puts into the step's count word), or -1 */
+  int32_t dense_dim;
+  int32_t n_rows;            /* entity rows N of the store, >= 1 */
+  int32_t K;
+  int32_t reserved;
+} tt_bag_store_side;
+int tt_bag_store_tile(void);
+size_t tt_bag_store_gather_workspace_bytes(int64_t B, int32_t n_sides);
+int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
+                        const tt_bag_store_side* sides, int32_t n_sides, int64_t B, const int64_t* order /* [B] or NULL */,
+                        void* workspace, size_t workspace_bytes, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

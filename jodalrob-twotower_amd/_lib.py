@@ -51,6 +51,12 @@ class StoreSide(C.Structure):
                 ("dense_dim", i32), ("n_rows", i32)]
 
 
+class BagStoreSide(C.Structure):
+    _fields_ = [("entity", vp), ("entity_stride", i64), ("dense_store", vp), ("offsets", vp), ("values", vp), ("dense_out", vp),
+                ("lengths_out", vp), ("ids_out", vp), ("nnz", i64), ("capacity", i64), ("expect", i64), ("dense_dim", i32), ("n_rows", i32),
+                ("K", i32), ("reserved", i32)]
+
+
 TT_MAX_CVT = 8
 
 
@@ -252,6 +258,9 @@ SIGNATURES = {
     "tt_bag_prepare_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tt_bag_prepare": (C.c_int, [vp, C.POINTER(BagLengths), i32, i64, vp, vp, sz, vp]),
     "tt_dedup_plan_pad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    "tt_bag_store_tile": (C.c_int, []),
+    "tt_bag_store_gather_workspace_bytes": (sz, [i64, i32]),
+    "tt_bag_store_gather": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSide), i32, i64, vp, vp, sz, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -224,7 +224,9 @@ int tt_ctx_check_device_errors(tt_ctx* ctx, tt_stream stream) {
                                               "tt_embed_lookup_rows_fwd / tt_batch_ingest_lookup) and read the last row instead;" : "",
                (word & TT_DEVERR_CELLS_PLAN) ? " tt_score_cells_plan counted more cells than its list's capacity (its counters were disturbed): the masks of "
                                                "that step are not the list's;" : "",
-               (word & TT_DEVERR_BAG_OFFSETS) ? " tt_embed_bag_fwd met bag offsets that are negative, decreasing or end beyond nnz and treated those bags as empty;" : "");
+               (word & TT_DEVERR_BAG_OFFSETS) ? " tt_embed_bag_fwd met bag offsets that are negative, decreasing or end beyond nnz and treated those bags as empty; "
+                                                "(the same bit: tt_bag_prepare / tt_bag_store_gather refused a side whose id total exceeds its capacity or is "
+                                                "not the count handed over -- its bags count as empty, no id was written);" : "");
   return TT_ERR_DEVICE;
 }
 

@@ -5,6 +5,7 @@
 #include "tt_common.h"
 #include "tt_deferred.h"
 #include "tt_embed_slots.h"
+#include "tt_copy_role.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -215,23 +216,7 @@ __global__ __launch_bounds__(kThreads) void batch_gather_kernel(const int64_t* _
   }
 }
 
-struct CopyArgs {
-  char* dst[TT_MAX_COPIES];
-  const char* src[TT_MAX_COPIES];
-  int64_t bytes[TT_MAX_COPIES];
-};
-
-// one copy segment per grid row: the 16-byte body strided over the row's workgroups, the byte tail by its first workgroup
-__device__ __forceinline__ void copy_segment_role(const CopyArgs& a, int seg) {
-  const int64_t n16 = a.bytes[seg] / 16, tail0 = n16 * 16;
-  const float4* __restrict__ s = reinterpret_cast<const float4*>(a.src[seg]);
-  float4* __restrict__ d = reinterpret_cast<float4*>(a.dst[seg]);
-  const int64_t stride = (int64_t)gridDim.x * role_threads();
-  for (int64_t i = (int64_t)blockIdx.x * role_threads() + threadIdx.x; i < n16; i += stride) d[i] = s[i];
-  if (blockIdx.x == 0)
-    for (int64_t i = tail0 + threadIdx.x; i < a.bytes[seg]; i += role_threads()) a.dst[seg][i] = a.src[seg][i];
-}
-
+// (CopyArgs and copy_segment_role: tt_copy_role.h)
 __global__ __launch_bounds__(kThreads) void copy_multi_kernel(CopyArgs a) { copy_segment_role(a, blockIdx.y); }
 
 // Batch hand-over of a graph-replayed step (tt_batch_ingest*): the copy segments of copy_multi_kernel plus, per side, the fused

@@ -43,15 +43,102 @@ class DeviceFeatureStore:
         return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids)}
 
 
+class DeviceBagFeatureStore:
+    """One tower's entities with MULTI-VALUED categorical features, resident on the device: dense f32 [N, Din] and the bags as CSR
+    over (entity, key) slots -- offsets int64 [N*K + 1], values int64 [nnz]; the bag of entity e, key k is
+    values[offsets[e*K + k] : offsets[e*K + k + 1]].  An entity's K bags are one contiguous run, so a batch's values() in the
+    sample-major wire format (kjt.build_bag_kjt: slot b*K + k) is the concatenation of its entities' runs: what
+    ops.bag_store_gather packs without a host round trip.  Ids are stored verbatim; the lookup clamps them as ever."""
+
+    def __init__(self, store: Dict, categorical_keys, device):
+        """store: {"dense_projected", "categorical_offsets", "categorical_values"}, host arrays or tensors.  ValueError -- checked
+        here, once -- unless the offsets start at 0, never decrease, end at len(values) and number N*K + 1 for dense's N."""
+        self.device = torch.device(device)
+        self.keys = list(categorical_keys)
+        def resident(x, dtype):
+            t = x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x))
+            return t.to(device=self.device, dtype=dtype).contiguous()
+        self.dense = resident(store["dense_projected"], torch.float32)
+        self.offsets = resident(store["categorical_offsets"], torch.int64).reshape(-1)
+        self.values = resident(store["categorical_values"], torch.int64).reshape(-1)
+        if self.dense.dim() != 2:
+            raise ValueError("dense_projected must be [N, Din]")
+        N, K = self.dense.shape[0], len(self.keys)
+        if self.offsets.numel() != N * K + 1:
+            raise ValueError(f"categorical_offsets: {self.offsets.numel()} entries, {N} entities of {K} keys need N*K + 1 = {N * K + 1}")
+        if int(self.offsets[0]) != 0:
+            raise ValueError("categorical_offsets must start at 0")
+        if N * K and bool((self.offsets[1:] < self.offsets[:-1]).any()):
+            raise ValueError("categorical_offsets must not decrease")
+        if int(self.offsets[-1]) != self.values.numel():
+            raise ValueError(f"categorical_offsets end at {int(self.offsets[-1])}, categorical_values holds {self.values.numel()} ids")
+        ends = self.offsets[::K] if K else self.offsets.new_zeros(N + 1)
+        self.run_lengths = (ends[1:] - ends[:-1]).contiguous()            # int64 [N]: the ids per entity
+
+    @classmethod
+    def from_bags(cls, dense, bags, categorical_keys, device):
+        """bags[e][k]: the list of ids of entity e, key k"""
+        K = len(categorical_keys)
+        if any(len(row) != K for row in bags):
+            raise ValueError(f"every entity needs one id list per key ({K} keys)")
+        lengths = np.array([len(bag) for row in bags for bag in row], dtype=np.int64)
+        values = np.array([int(i) for row in bags for bag in row for i in bag], dtype=np.int64)
+        offsets = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lengths)])
+        return cls({"dense_projected": dense, "categorical_offsets": offsets, "categorical_values": values}, categorical_keys, device)
+
+    @classmethod
+    def from_single(cls, store: DeviceFeatureStore):
+        """the plain store's entities, every bag of length one"""
+        n = store.categorical.numel()
+        return cls({"dense_projected": store.dense, "categorical_offsets": torch.arange(n + 1, dtype=torch.int64, device=store.device),
+                    "categorical_values": store.categorical.reshape(-1)}, store.keys, store.device)
+
+    def __len__(self):
+        return self.dense.shape[0]
+
+    def gather(self, entity_idx: torch.Tensor, n_ids: Optional[int] = None) -> Dict:
+        """{"dense", "kjt"} of the entities `entity_idx` (int64 [B]; an index outside the store is clamped into it), the kjt in the
+        bag wire format -- DeviceFeatureStore.gather's duck type.  n_ids: the batch's id count, when the caller knows it
+        (DevicePairLoader.epoch_bag_ids); without it this call reads ONE word back from the device to size values() -- a host
+        synchronisation per call.  A wrong n_ids writes no ids and raises the device error word (_lib.check_device_errors)."""
+        B, K = entity_idx.numel(), len(self.keys)
+        idx = entity_idx.to(torch.int64).reshape(-1).contiguous()
+        if n_ids is None:
+            n_ids = int(self.run_lengths[idx.clamp(0, max(len(self) - 1, 0))].sum()) if B and len(self) else 0
+        dense = torch.empty((B, self.dense.shape[1]), dtype=torch.float32, device=self.device)
+        lengths = torch.empty(B * K, dtype=torch.int64, device=self.device)
+        ids = torch.empty(int(n_ids), dtype=torch.int64, device=self.device)
+        if B:
+            ops.bag_store_gather([], [ops.BagStoreSide(idx, 1, self.dense, self.offsets, self.values, K, dense, lengths, ids, int(n_ids))], B)
+        return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids, lengths)}
+
+
+def batch_id_counts(run_lengths: torch.Tensor, entities: torch.Tensor, batch_size: int) -> torch.Tensor:
+    """int64 [n_batches]: the ids of every batch of `entities` (int64 [n], in epoch order; the last batch may be ragged) --
+    run_lengths[entities] summed per batch.  Plain torch on whatever device the arguments live on."""
+    n = entities.numel()
+    nb = (n + batch_size - 1) // batch_size
+    runs = torch.zeros(nb * batch_size, dtype=torch.int64, device=entities.device)
+    runs[:n] = run_lengths[entities]
+    return runs.view(nb, batch_size).sum(1)
+
+
 NEGATIVE_SEED_OFFSET = 0x5851F42D                  # the extras' generator: the loader's seed plus this
 
 
-def _refuse_bag_mode_step(step, who: str) -> None:
-    """The store-fed hand-over writes B*K ids per side into a captured step's static buffers: a step whose task pools ragged
-    bags (bag mode) is refused before the epoch starts (once per epoch, not per batch)."""
+def _refuse_bag_mode_step(step, who: str, stores=None) -> None:
+    """The store-fed hand-over of plain stores writes B*K ids per side into a captured step's static buffers: a step whose task pools
+    ragged bags (bag mode) is refused before the epoch starts (once per epoch, not per batch) -- unless every side that pools is fed
+    from a DeviceBagFeatureStore (`stores`: the (notice, company) stores of a loader that may hold some)."""
     task = getattr(step, "task", None)
     if isinstance(task, torch.nn.Module):
         from .cat_embed import refuse_bag_mode
+        model = getattr(task, "two_tower_model", None)
+        towers = [getattr(model, name, None) for name in ("notice_tower", "company_tower")]
+        if stores is not None and all(isinstance(st, DeviceBagFeatureStore) or
+                                      not getattr(getattr(tw, "categorical_embedder", None), "bag_mode", True)
+                                      for st, tw in zip(stores, towers)):
+            return
         refuse_bag_mode(task, who)
 
 
@@ -59,10 +146,11 @@ class DevicePairLoader:
     """Iterates over (notice_idx, company_idx) pairs in batches; len() = number of batches (drop_last=False,
     as torch's DataLoader default used by the reference: unified_bid_data_loader.py:1090-1110)."""
 
-    def __init__(self, notice: DeviceFeatureStore, company: DeviceFeatureStore, pairs: np.ndarray, batch_size: int,
+    def __init__(self, notice, company, pairs: np.ndarray, batch_size: int,
                  shuffle: bool, seed: int = 42, log_q=None, mask_repeats: bool = False, pair_weight=None, extra_negatives: int = 0,
                  negative_pool=None, mined=None, hard_fraction: float = 1.0, mask_known: bool = False, known_pairs=None):
-        """mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
+        """notice / company: a DeviceFeatureStore or, for multi-valued features, a DeviceBagFeatureStore (either side, or both).
+        mask_repeats: every batch carries "entity" [B] int32 on both sides -- the pair's notice and company indices -- and the train
         task masks the in-batch negatives that repeat a row's notice or company (the repeated-entity mask).
         log_q: optional (notice [Nn], company [Nc]) f32 log sampling probabilities per entity (sampling_bias.log_sampling_probs):
         every batch then carries "log_q" [B] on both sides and the train task applies the logQ correction.
@@ -104,6 +192,7 @@ class DevicePairLoader:
         self.set_extra_negatives(extra_negatives, negative_pool, mined, hard_fraction)
         self.known, self.max_cells, self.eager_cell_batches = None, 0, 0
         self.set_mask_known(mask_known, known_pairs)
+        self.eager_bag_batches = 0         # step_batches: batches with more ids than the captured step's bag_capacity
 
     def set_mask_known(self, mask_known: bool, known_pairs=None) -> None:
         """Turns the known-pair mask on / off for every batch this loader produces from now on.  known_pairs: [P', 2] (notice index,
@@ -346,15 +435,42 @@ class DevicePairLoader:
         n = self.pairs.shape[0]
         return torch.randperm(n, generator=self._gen, device=self.pairs.device) if self.shuffle else None
 
-    def batch(self, order: Optional[torch.Tensor], lo: int, negatives: Optional[torch.Tensor] = None, cells=None) -> Dict:
+    def bag_stores(self):
+        """[(side, store, column of the pair table)] of the sides fed from a DeviceBagFeatureStore"""
+        return [(side, st, col) for side, st, col in (("notice", self.notice, 0), ("company", self.company, 1))
+                if isinstance(st, DeviceBagFeatureStore)]
+
+    def epoch_bag_ids(self, order: Optional[torch.Tensor] = None) -> Optional[Dict[str, np.ndarray]]:
+        """{side: int64 host array [n_batches]} -- the id count of every batch of this epoch on each side fed from a bag store (None:
+        no such side).  Summed on the device from run_lengths[pairs[order]] (batch_id_counts) and read back ONCE per epoch: with it
+        neither batch() nor the store-fed hand-over synchronises per batch.  order: this epoch's epoch_order()."""
+        sides = self.bag_stores()
+        if not sides:
+            return None
+        if self.shuffle and order is None:
+            raise ValueError("epoch_bag_ids(): a shuffling loader needs this epoch's order")
+        sel = self.pairs if order is None else self.pairs[order]
+        counts = torch.stack([batch_id_counts(st.run_lengths, sel[:, col], self.batch_size) for _, st, col in sides]).cpu().numpy()
+        return {side: counts[i] for i, (side, _, _) in enumerate(sides)}
+
+    def _gather(self, side: str, idx: torch.Tensor, bag_ids, k: int) -> Dict:
+        st = self.notice if side == "notice" else self.company
+        if isinstance(st, DeviceBagFeatureStore):
+            return st.gather(idx, None if bag_ids is None else int(bag_ids[side][k]))
+        return st.gather(idx)
+
+    def batch(self, order: Optional[torch.Tensor], lo: int, negatives: Optional[torch.Tensor] = None, cells=None, bag_ids=None) -> Dict:
         """negatives: this batch's row of epoch_negatives() (a loader with extras: required); cells: epoch_cells()'s result (a loader
-        with mask_known: required)"""
+        with mask_known: required); bag_ids: epoch_bag_ids()'s result (a loader with bag stores: optional -- without it every bag
+        store's gather reads its id count back from the device)"""
         if (negatives is not None) != bool(self.extra_negatives):
             raise ValueError("batch(): a loader with extra_negatives needs this batch's row of epoch_negatives(), one without takes none")
         if (cells is not None) != (self.known is not None):
             raise ValueError("batch(): a loader with mask_known needs this epoch's epoch_cells(), one without takes none")
         sel = self.pairs[lo:lo + self.batch_size] if order is None else self.pairs[order[lo:lo + self.batch_size]]
-        out = {"notice": self.notice.gather(sel[:, 0].contiguous()), "company": self.company.gather(sel[:, 1].contiguous())}
+        k = lo // self.batch_size
+        out = {"notice": self._gather("notice", sel[:, 0].contiguous(), bag_ids, k),
+               "company": self._gather("company", sel[:, 1].contiguous(), bag_ids, k)}
         if self.pair_weight is not None:
             w = self.pair_weight
             out["pair_weight"] = w[lo:lo + self.batch_size].clone() if order is None else w[order[lo:lo + self.batch_size]]
@@ -420,8 +536,9 @@ class DevicePairLoader:
         order = self.epoch_order()
         neg = self.epoch_negatives(order)
         cells = self.epoch_cells(order, neg)
+        bag = self.epoch_bag_ids(order)
         for k, lo in enumerate(range(0, self.pairs.shape[0], self.batch_size)):
-            yield self.batch(order, lo, None if neg is None else neg[k], cells)
+            yield self.batch(order, lo, None if neg is None else neg[k], cells, **({} if bag is None else {"bag_ids": bag}))
 
     def eval_batches(self, graphed_eval, eager_eval=None, max_batches: Optional[int] = None) -> int:
         """One pass over the pairs in order (no shuffling is applied here: the reference's test loader does not shuffle) through a
@@ -449,19 +566,23 @@ class DevicePairLoader:
         one, through `eager_step(batch)` (skipped when None).  Yields the step's result dict per batch (an unrolled step's U results
         arrive together, after its one launch: read them before the next launch overwrites them)."""
         for st in (graphed_step, ragged_step):
-            _refuse_bag_mode_step(st, "DevicePairLoader.step_batches")
+            _refuse_bag_mode_step(st, "DevicePairLoader.step_batches", (self.notice, self.company))
         order = self.epoch_order()
         n, B = self.pairs.shape[0], self.batch_size
         U = int(getattr(graphed_step, "unroll", 1))
         neg = self.epoch_negatives(order)
         cells = self.epoch_cells(order, neg)
+        bag = self.epoch_bag_ids(order)
+        if bag is not None and neg is None and cells is None:
+            yield from self._step_bag_batches(graphed_step, eager_step, ragged_step, order, bag)
+            return
         if neg is not None or cells is not None:
             # extra negatives / masked cells: no store-fed hand-over -- the batches __iter__ yields, through the captured step's plain-copy
             # hand-over step(batch) (a step captured on a batch with the same M), the ragged one through ragged_step or the eager callable
             if U > 1:
                 raise NotImplementedError("extra negatives and masked cells are not supported by the unrolled step")
             for k, lo in enumerate(range(0, n, B)):
-                b = self.batch(order, lo, None if neg is None else neg[k], cells)
+                b = self.batch(order, lo, None if neg is None else neg[k], cells, **({} if bag is None else {"bag_ids": bag}))
                 if cells is not None and eager_step is not None:
                     # the captured step this batch would take; with more cells than it has room for (.step would raise) the batch goes
                     # through the eager step instead -- counted in self.eager_cell_batches and warned about once per loader
@@ -507,6 +628,38 @@ class DevicePairLoader:
                 yield ragged_step.step_from_store(self.notice, self.company, self.pairs, order, lo, **kw(lo, n - lo))
             elif eager_step is not None:
                 yield eager_step(self.batch(order, lo))
+
+    def _step_bag_batches(self, graphed_step, eager_step, ragged_step, order, bag):
+        """step_batches of a loader with bag stores (no extras, no masked cells): a batch whose id counts fit the captured step's
+        bag_capacity goes through its store-fed hand-over (GraphedTrainStep.step_from_store(..., bag_ids=...): no host
+        synchronisation, the counts come from epoch_bag_ids); one over the capacity goes through `eager_step` -- counted in
+        self.eager_bag_batches and warned about once per loader; the ragged last batch through `ragged_step` or `eager_step` as ever."""
+        n, B = self.pairs.shape[0], self.batch_size
+        if int(getattr(graphed_step, "unroll", 1)) > 1:
+            raise NotImplementedError("bag stores are not supported by the unrolled step")
+        lq, ent, pw = self.epoch_log_q(order), self.epoch_entity(order), self.epoch_pair_weight(order)
+        for k, lo in enumerate(range(0, n, B)):
+            m = min(B, n - lo)
+            g = graphed_step if m == B else (ragged_step if ragged_step is not None and
+                                             ragged_step.static["notice"]["dense"].shape[0] == m else None)
+            ids = {side: int(c[k]) for side, c in bag.items()}
+            cap = (getattr(g, "bag_capacity", None) or {}) if g is not None else {}
+            over = {side: c for side, c in ids.items() if side in cap and c > cap[side]}
+            if g is not None and over and eager_step is not None:
+                self.eager_bag_batches += 1
+                if self.eager_bag_batches == 1:
+                    import warnings
+                    side, c = next(iter(over.items()))
+                    warnings.warn(f"a batch carries {c} ids on the {side} side, the captured step has room for {cap[side]} "
+                                  "(bag_capacity): such batches run through the eager step (DevicePairLoader.eager_bag_batches counts them)")
+                g = None
+            if g is not None:
+                kw = {**({} if lq is None else {"log_q": (lq[k, 0, :m], lq[k, 1, :m])}),
+                      **({} if ent is None else {"entity": (ent[k, 0, :m], ent[k, 1, :m])}),
+                      **({} if pw is None else {"pair_weight": pw[k, :m]})}
+                yield g.step_from_store(self.notice, self.company, self.pairs, order, lo, bag_ids=ids, **kw)
+            elif eager_step is not None:
+                yield eager_step(self.batch(order, lo, bag_ids=bag))
 
     def _plain_batch(self, order: Optional[torch.Tensor], lo: int) -> Dict:
         """batch(order, lo) without extras or masked cells, whatever the loader draws for training (evaluation ranks the batch's own

@@ -25,6 +25,7 @@ from . import batch_terms as T
 from . import ops
 from .cat_embed import bag_mode_embedders, refuse_bag_mode
 from .config import settings
+from .data_loader import DeviceBagFeatureStore
 from .kjt import KeyedJaggedTensor
 from .optim import FusedAdam
 
@@ -673,7 +674,7 @@ class GraphedTrainStep:
         return self.result
 
     def step_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor] = None, offset: int = 0,
-                        log_q=None, entity=None, pair_weight=None):
+                        log_q=None, entity=None, pair_weight=None, bag_ids=None):
         """Train on the B pairs `pairs[order[offset : offset + B]]` (order None: `pairs[offset : offset + B]`) gathered straight
         out of the device-resident feature stores into the static buffers -- ONE launch (tt_batch_ingest_store: dense rows, ids,
         key-major fused rows, the step scalars) and the replay; nothing per step crosses PCIe and no batch tensors are built
@@ -684,30 +685,94 @@ class GraphedTrainStep:
         slices of its per-epoch array): two more copy segments of the same launch.
         entity: (notice, company) int32 [B] ids of this step's pairs for a step captured with entity ids (the repeated-entity mask;
         DevicePairLoader(mask_repeats=True).step_batches passes slices of its per-epoch array): likewise.
-        pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment."""
+        pair_weight: f32 [B] weights of this step's pairs for a step captured with pair weights: one more copy segment.
+        A step captured with bag_capacity: every bag-mode side takes a data_loader.DeviceBagFeatureStore, and tt_bag_store_gather (two
+        launches, which also carry the copy segments) fills the side's static dense buffer, its [B*K] lengths and the head of its static
+        id buffer; a side that is not in bag mode keeps its DeviceFeatureStore and goes through tt_batch_ingest_store alone.
+        bag_ids: {side: this batch's id count} of the bag-mode sides (DevicePairLoader.epoch_bag_ids) -- it goes into the count word
+        with the step's scalars, as step(batch)'s; a count above the capacity is refused before anything is launched, one that is not
+        the batch's raises the device error word and the captured step runs the side's bags as empty.  Without bag_ids the counts are
+        summed from the stores' run_lengths and READ BACK from the device: correct, and a host synchronisation per step."""
         for row in (_CELLS, _NEGATIVES):
             if row.key in self._terms:
                 raise NotImplementedError(f"{row.noun}: no store-fed hand-over -- a step captured with '{row.key}' takes step(batch)")
-        if self._bag:                              # (a DeviceFeatureStore holds one id per key)
+        stores = {"notice": notice_store, "company": company_store}
+        if any(not isinstance(stores[side], DeviceBagFeatureStore) for side in self._bag):      # (a DeviceFeatureStore holds one id per key)
             refuse_bag_mode(self.task, "step_from_store")
+        for side, fs in stores.items():
+            if isinstance(fs, DeviceBagFeatureStore) and side not in self._bag:
+                raise ValueError(f"step_from_store: the {side} side is fed from a DeviceBagFeatureStore, but that side's embedder does not pool bags "
+                                 "(categorical_pooling): its static id buffer holds exactly B*K ids")
+        counts = self._bag_counts(stores, pairs, order, offset, bag_ids) if self._bag else None
         given, extra = {"log_q": log_q, "entity": entity, "pair_weight": pair_weight}, []
         for row in T.B_TERMS:
             extra += self._term_pairs(row.key, given[row.key], "step_from_store")
-        self._ingest_from_store(notice_store, company_store, pairs, order, offset, extra=extra or None)
+        if self._bag:
+            self._ingest_from_bag_stores(stores, pairs, order, offset, counts, extra)
+        else:
+            self._ingest_from_store(notice_store, company_store, pairs, order, offset, extra=extra or None)
         self._mark_slot()
         return self._replay()
+
+    def _store_pairs(self, pairs: torch.Tensor, order: Optional[torch.Tensor], offset: int):
+        """(the flat pair list, the first element of this batch's first pair) after the checks every store-fed hand-over makes"""
+        B = self.static["notice"]["dense"].shape[0]
+        if pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+            raise ValueError("step_from_store: pairs must be a contiguous int64 [P, 2] tensor")
+        if order is None and (offset < 0 or offset + B > pairs.shape[0]):
+            raise ValueError("step_from_store: the batch runs past the pair list")
+        return pairs.view(-1), (0 if order is not None else 2 * offset)
+
+    def _bag_counts(self, stores, pairs, order, offset, bag_ids) -> Dict[str, int]:
+        """{side: ids of this batch} of the bag-mode sides, each within the side's capacity -- nothing is launched or changed before"""
+        B = self.static["notice"]["dense"].shape[0]
+        if bag_ids is None:
+            self._store_pairs(pairs, order, offset)
+            if order is not None and (offset < 0 or offset + B > order.numel()):
+                raise ValueError("step_from_store: the batch runs past the order")
+            sel = pairs[offset:offset + B] if order is None else pairs[order[offset:offset + B]]
+            sums = torch.stack([stores[side].run_lengths[sel[:, 0 if side == "notice" else 1]].sum() for side in self._bag]).tolist()
+            bag_ids = dict(zip(self._bag, sums))              # (the one device read of this form)
+        if set(bag_ids) != set(self._bag):
+            raise ValueError(f"step_from_store: bag_ids names {sorted(bag_ids)}, the step's bag-mode sides are {sorted(self._bag)}")
+        counts = {side: int(bag_ids[side]) for side in self._bag}
+        for side, n in counts.items():
+            if n > self._bag[side]:
+                raise ValueError(f"{side}: {n} ids, the step was captured with bag_capacity = {self._bag[side]}")
+            if n < 0:
+                raise ValueError(f"step_from_store: bag_ids['{side}'] = {n}")
+        return counts
+
+    def _ingest_from_bag_stores(self, stores, pairs, order, offset, counts, extra):
+        """The hand-over launches of a bag-mode step_from_store: tt_batch_ingest_store for the sides that are not in bag mode (none:
+        no launch), then tt_bag_store_gather for the bag-mode sides with the copy segments `extra` and the step's scalars."""
+        B = self.static["notice"]["dense"].shape[0]
+        flat, base = self._store_pairs(pairs, order, offset)
+        model = self.task.two_tower_model
+        embs = {"notice": model.notice_tower.categorical_embedder, "company": model.company_tower.categorical_embedder}
+        bags, lookups, plains = [], [], []
+        for i, side in enumerate(("notice", "company")):
+            fs, e, sd, kjt = stores[side], embs[side], self.static[side]["dense"], self.static[side]["kjt"]
+            if side in self._bag:
+                if len(fs.keys) != len(e.keys):
+                    raise ValueError(f"step_from_store: the {side} store holds {len(fs.keys)} keys, the embedder {len(e.keys)}")
+                bags.append(ops.BagStoreSide(flat[base + i:], 2, fs.dense, fs.offsets, fs.values, len(e.keys), sd, kjt.lengths(), kjt.values(),
+                                             counts[side]))
+            else:
+                lookups.append(ops.LookupSide(None, e._key_row_offset, e._key_vocab, None, len(e.keys)))
+                plains.append(ops.StoreSide(flat[base + i:], 2, fs.dense, fs.categorical, sd, kjt.values()))
+        off = offset if order is not None else 0
+        if plains:
+            ops.batch_ingest_store([], lookups, plains, B, order, None, off)
+        self._bag_n.update(counts)                              # (the count word of this hand-over: _fill_slot reads it)
+        ops.bag_store_gather(extra + [self._fill_slot()], bags, B, order, off)
 
     def _ingest_from_store(self, notice_store, company_store, pairs: torch.Tensor, order: Optional[torch.Tensor], offset: int, ahead: int = 0,
                            extra=None):
         """The hand-over launch of step_from_store (tt_batch_ingest_store) into the static buffers; `ahead`: _fill_slot; `extra`:
         more copy segments for the same launch."""
         B = self.static["notice"]["dense"].shape[0]
-        if pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-            raise ValueError("step_from_store: pairs must be a contiguous int64 [P, 2] tensor")
-        if order is None and (offset < 0 or offset + B > pairs.shape[0]):
-            raise ValueError("step_from_store: the batch runs past the pair list")
-        flat = pairs.view(-1)
-        base = 0 if order is not None else 2 * offset
+        flat, base = self._store_pairs(pairs, order, offset)
         model = self.task.two_tower_model
         embs = [model.notice_tower.categorical_embedder, model.company_tower.categorical_embedder]
         sides, stores = [], []

@@ -1672,6 +1672,62 @@ def batch_ingest_store(pairs, sides: Sequence[LookupSide], stores: Sequence[Stor
                                                int(table_rows), _cvt_list(cvt), L.stream(dev)), "tt_batch_ingest_store")
 
 
+BAG_STORE_TILE = 256          # samples per scan tile of tt_bag_store_gather (tt_bag_store_tile(): the kernel's kStoreTile)
+
+
+@dataclass
+class BagStoreSide:
+    """One tower's device-resident bag store as the source of a batch (tt_bag_store_side)."""
+    entity: torch.Tensor          # int64: entity index per pair, element [o * entity_stride]
+    entity_stride: int
+    dense_store: torch.Tensor     # f32 [N, dense_dim]
+    offsets: torch.Tensor         # int64 [N*K + 1]
+    values: torch.Tensor          # int64 [nnz]
+    K: int
+    dense_out: torch.Tensor       # f32 [B, dense_dim]
+    lengths_out: torch.Tensor     # int64 [B*K]
+    ids_out: torch.Tensor         # int64 [capacity]: the run total fills its head, the rest keeps what it held
+    expect: int = -1              # the id count the host believes, or -1
+
+
+def bag_store_gather(pairs, sides: Sequence[BagStoreSide], B: int, order: Optional[torch.Tensor] = None, order_offset: int = 0):
+    """tt_bag_store_gather: the batch `order[order_offset : order_offset + B]` of the pair list gathered out of device-resident bag
+    stores into the sample-major bag wire format (+ the copy segments `pairs`), two launches and no host round trip.  A side whose
+    ids do not fit ids_out, or do not number `expect`, gets no ids and raises the device error word (_lib.check_device_errors)."""
+    dev = sides[0].dense_out.device
+    arr = (L.BagStoreSide * len(sides))()
+    for i, t in enumerate(sides):
+        if t.entity.dtype != torch.int64 or t.entity.dim() != 1 or t.entity_stride < 1 or t.entity.device != dev:
+            raise ValueError(f"bag_store_gather: side {i}: entity must be a 1-D int64 view on {dev}")
+        need = (B - 1) * t.entity_stride + 1 if order is None else 1
+        if t.entity.numel() < need:
+            raise ValueError(f"bag_store_gather: side {i}: the batch runs past the pair list ({t.entity.numel()} entries, {need} needed)")
+        N, dd = t.dense_store.shape
+        if t.dense_store.dtype != torch.float32 or not t.dense_store.is_contiguous() or N < 1 or \
+                any(x.dtype != torch.int64 or x.dim() != 1 or not x.is_contiguous() or x.device != dev for x in (t.offsets, t.values)) or \
+                t.offsets.numel() != N * t.K + 1:
+            raise ValueError(f"bag_store_gather: side {i}: need contiguous f32 [N, D] features, int64 [N*{t.K} + 1] offsets and int64 ids")
+        if t.dense_out.shape != (B, dd) or not t.dense_out.is_contiguous() or t.dense_out.dtype != torch.float32 or \
+                t.lengths_out.numel() != B * t.K or t.lengths_out.dtype != torch.int64 or not t.lengths_out.is_contiguous() or \
+                t.ids_out.dim() != 1 or t.ids_out.dtype != torch.int64 or not t.ids_out.is_contiguous():
+            raise ValueError(f"bag_store_gather: side {i}: outputs must be contiguous f32 [{B}, {dd}], int64 [{B * t.K}] and a 1-D int64 id buffer")
+        arr[i] = L.BagStoreSide(L.ptr(t.entity), t.entity_stride, L.ptr(t.dense_store), L.ptr(t.offsets), L.ptr(t.values), L.ptr(t.dense_out),
+                                L.ptr(t.lengths_out), L.ptr(t.ids_out), t.values.numel(), t.ids_out.numel(), int(t.expect), dd,
+                                min(int(N), 2 ** 31 - 1), t.K, 0)
+    n, dst, src, nb = _copy_segments(pairs, "bag_store_gather")
+    if order is not None:
+        if order.dtype != torch.int64 or not order.is_contiguous() or order_offset < 0 or order_offset + B > order.numel():
+            raise ValueError("bag_store_gather: order must be a contiguous int64 tensor holding the batch's B entries")
+        order_ptr = L.vp(order.data_ptr() + 8 * order_offset)
+    else:
+        order_ptr = L.vp(0)
+    lib = L.load()
+    ws = L.workspace(dev, lib.tt_bag_store_gather_workspace_bytes(B, len(sides)))
+    with _timed("tt_bag_store_gather"):
+        L.check(lib.tt_bag_store_gather(L.ctx(dev), n, dst, src, nb, arr, len(sides), B, order_ptr, L.ptr(ws), ws.numel(), L.stream(dev)),
+                "tt_bag_store_gather")
+
+
 # ---------------------------------------------------------------------------------------------- multi-GPU routing
 def route_bucket(plan: DedupPlan, G: int, C: int, pad_id: Sequence[int], pad_u: int, overflow: torch.Tensor, expand: bool = False):
     """Distinct rows of `plan` -> fixed-capacity owner buckets.  Returns (send_ids [G*C] i32, send_u [G*C] i32,

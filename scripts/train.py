@@ -144,13 +144,23 @@ def main():
                     help="with --pool: the pooled loop runs as a captured step (GraphedTrainStep(bag_capacity=...)) whose static id "
                          "buffers hold FACTOR (default 2) times the first batch's ids per bag-mode side; a batch that does not fit "
                          "takes the eager step and is counted")
+    ap.add_argument("--pool-store", action="store_true",
+                    help="with --pool: every entity's bags are drawn ONCE (the --pool keys: Poisson(--pool-length) ids, the entity's own "
+                         "first) into device-resident bag stores (DeviceBagFeatureStore) that training AND evaluation read, so the "
+                         "model is evaluated on the bags it is trained on.  The model is built as under --fast (bf16 operands, sparse "
+                         "gradients) with or without it; with --fast the epoch runs through step_batches on a step captured with "
+                         "--pool-capture FACTOR (default 2) times the pair table's mean ids per batch, fed by the stores' own hand-over")
     ap.add_argument("--seed", type=int, default=None, help="seed torch's generators (weights, dropout) before the model is built")
     ap.add_argument("--dropout-rate", type=float, default=0.1, help="the towers' dropout rate (reference: 0.1)")
     ap.add_argument("--log-interval", type=int, default=20, help="steps between the loop's progress lines (reference: 20)")
     a = ap.parse_args()
     pooling = None
+    if a.pool_store and not a.pool:
+        ap.error("--pool-store needs --pool")
+    if a.pool_store and a.fast and (a.extra_negatives or a.mask_known):
+        ap.error("--pool-store --fast: no store-fed hand-over with --extra-negatives or --mask-known")
     if a.pool:
-        if a.fast:
+        if a.fast and not a.pool_store:
             ap.error("--pool needs the eager loop: a captured step's static id buffers hold exactly B*K ids (not with --fast)")
         pooling = {}
         for item in a.pool:
@@ -204,6 +214,12 @@ def main():
     train_loader, test_loader = create_unified_bid_dataloaders(source, schema, batch_size=config["batch_size"],
                                                                test_split=config["test_split"], shuffle_seed=config["shuffle_seed"],
                                                                test_mode=True, pair_limit=config["pair_limit"], device=device)
+    if a.pool_store:                                     # the towers that pool read per-entity bags, drawn once; both loaders share them
+        bag_stores = [synthetic.bag_store(st, real[side]["vocab_sizes"], pooling, a.pool_length, seed=config["shuffle_seed"] + i)
+                      if any(k in pooling for k in st.keys) else st
+                      for i, (side, st) in enumerate((("notice", train_loader.notice), ("company", train_loader.company)))]
+        for ld in (train_loader, test_loader):
+            ld.notice, ld.company = bag_stores
     if a.mask_repeats:
         train_loader.set_mask_repeats(True)
     if a.pair_weight == "inv-notice-count":
@@ -226,7 +242,7 @@ def main():
                                              final_embedding_dim=config["final_embedding_dim"], dropout_rate=config["dropout_rate"],
                                              temperature=config["temperature"], loss_type=config["loss_type"], device=device,
                                              categorical_pooling=pooling,
-                                             **(dict(embedding_grad="sparse", score_dtype="bf16", mlp_dtype="bf16") if a.fast else {}))
+                                             **(dict(embedding_grad="sparse", score_dtype="bf16", mlp_dtype="bf16") if (a.fast or a.pool_store) else {}))
     optimizer = FusedAdam.for_task(train_task, lr=config["learning_rate"], weight_decay=config["weight_decay"],
                                    table_optimizer=a.table_optimizer, table_lr=a.table_lr)
     warmup_steps = max(1, int(len(train_loader) * config["warmup_ratio"]))
@@ -245,12 +261,14 @@ def main():
 
     def eager_step(batch):
         nonlocal pool_step, pool_eager
-        if pooling:                                      # ragged bags for the pooled keys, drawn per step (seeded by the step number)
+        if graphed is not None and pooling:              # --pool-store --fast: a batch step_batches could not replay
+            pool_eager += 1
+        if pooling and not a.pool_store:                 # ragged bags for the pooled keys, drawn per step (seeded by the step number)
             batch = dict(batch)
             for side in ("notice", "company"):
                 batch[side] = dict(batch[side], kjt=synthetic.ragged_bags(batch[side]["kjt"], real[side]["vocab_sizes"], pooling,
                                                                           a.pool_length, seed=config["shuffle_seed"] + steps))
-        if a.pool_capture is not None and train_task.training:
+        if a.pool_capture is not None and train_task.training and graphed is None:
             if pool_step is None:                        # captured on the first batch (its warm-up leaves no trace: preserve_state)
                 import math
                 from jodalrob_twotower_amd.graph import GraphedTrainStep
@@ -280,6 +298,13 @@ def main():
         train_loader._neg_gen.set_state(neg_state)
         # masked cells: room for twice the example epoch's fullest batch (a fuller one goes through the eager step: step_batches)
         cap = {"cell_capacity": max(1024, 2 * train_loader.max_cells)} if a.mask_known else {}
+        if a.pool_store:                                 # bag_capacity: FACTOR times the pair table's mean ids per batch (the example fits)
+            import math
+            factor = 2.0 if a.pool_capture is None else a.pool_capture
+            caps = {side: max(math.ceil(factor * float(st.run_lengths[train_loader.pairs[:, col]].sum()) * config["batch_size"] / len(train_loader.pairs)),
+                              example[side]["kjt"].values().numel(), 1) for side, st, col in train_loader.bag_stores()}
+            cap["bag_capacity"] = caps
+            print(f"--pool-store: captured with bag_capacity = {caps}")
         graphed = GraphedTrainStep(train_task, optimizer, example, warmup=1, accumulate_metrics=True, **cap)
         rag = train_loader.ragged_example()              # the epoch's last, smaller batch gets a captured step of its own size:
         if rag is not None and rag["notice"]["dense"].shape[0] >= 2:       # launched eagerly it costs six full steps of host time
@@ -373,7 +398,10 @@ def main():
             break
     torch.cuda.synchronize()
     t_epochs = time.time() - t_loop
-    if a.pool_capture is not None:
+    if a.pool_store and graphed is not None:
+        print(f"--pool-store: {steps - pool_eager} captured steps, {pool_eager} batches took the eager step "
+              f"({train_loader.eager_bag_batches} over the capacity)")
+    elif a.pool_capture is not None:
         print(f"--pool-capture: {steps - pool_eager} captured steps, {pool_eager} batches took the eager step")
         if pool_step is not None:
             pool_step.close()
