@@ -1230,6 +1230,45 @@ int tt_dedup_plan_pad(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table
                       int32_t* seg_offsets, int32_t* n_unique, void* workspace, size_t workspace_bytes, tt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weighted bags: one f32 weight per id, in the order of ids (a KeyedJaggedTensor's weights(), torch.nn.EmbeddingBag's
+ * per_sample_weights).  Bag (b, k) over positions p0 < p1 < ... of length L pools to
+ *   sum:  w_p0 * row_p0 + w_p1 * row_p1 + ...
+ *   mean: that sum / L -- the divisor is the NUMBER of ids, as in the unweighted mean, not the sum of the weights.  A weighted
+ *         average is sum pooling over weights the caller has normalised.
+ * An empty bag pools to zeros.  Weights are data, used verbatim: negative, zero and non-finite values are not special-cased, and no
+ * gradient flows to them.
+ *
+ * Arithmetic (f32): a bag's first position is one multiply, acc = w * x; every later one is one fused multiply-add,
+ * acc = fma(w, x, acc), in ascending position order; the mean divides as the unweighted entry does (acc / (float)L, only when
+ * L > 1).  With every weight 1.0 these are the bits of tt_embed_bag_fwd, a -0 row included.
+ *
+ * tt_embed_bag_fwd_w / tt_embed_bag_fwd_cap_w: the arguments of tt_embed_bag_fwd / tt_embed_bag_fwd_cap, and
+ *   weights: HOST array of n_sides DEVICE pointers, each f32 [side.nnz] ([capacity] in the capacity form); a NULL entry is a
+ *            side whose ids all weigh 1.  Read with 4-byte loads: 4-byte alignment is all they need.
+ *   w_out:   f32 [all sides' positions], laid out like rows_out / bag_of; may be NULL, but not when rows_out is given and a
+ *            side has weights (TT_ERR_INVALID_ARG).  For every position a bag covers w_out[P] = that position's weight, 1.0f
+ *            on a side without weights.  Positions no bag covers -- trailing ids, refused offsets, the capacity form's pads --
+ *            are NOT written; the gradient never reads them (bag_of < 0 there).
+ * Nothing is read from weights[i] at a position no bag covers, as nothing is read from ids there.  Whatever the unweighted
+ * entries refuse these refuse too, before any launch.
+ *
+ * tt_embed_bag_grad_bwd_w: tt_embed_bag_grad_bwd plus pos_w, f32 [nnz] (the forward's w_out), or NULL for the unweighted
+ * coefficients (then the launches of tt_embed_bag_grad_bwd).  Position P contributes c_P * d_out[slot bag_of[P]]:
+ * c_P = pos_w[P] when inv_len is NULL, else the one f32 product pos_w[P] * inv_len[bag_of[P]]; each contribution is one
+ * acc = fma(c_P, x, acc) in plan order.  Chunking, workspace and the long-row finish are tt_embed_bag_grad_bwd's; with every
+ * weight 1.0 so are the bits.  No atomics on the data path in either direction.
+ * ---------------------------------------------------------------------------------------------- */
+int tt_embed_bag_fwd_w(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                       int64_t B, int32_t* rows_out, int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream);
+int tt_embed_bag_fwd_cap_w(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides,
+                           int32_t n_sides, int64_t B, int32_t* rows_out, int32_t* bag_of, const float* const* weights,
+                           float* w_out, tt_stream stream);
+int tt_embed_bag_grad_bwd_w(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int64_t B, int32_t E, const int32_t* bag_of,
+                            const float* inv_len, const float* pos_w, const int32_t* sorted_src, const int32_t* seg_offsets,
+                            const int32_t* unique_rows, const int32_t* n_unique, int64_t nnz, int32_t mode, float* out,
+                            void* workspace, size_t workspace_bytes, tt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The batch gather out of a device-resident store of per-entity BAGS: tt_batch_ingest_store's two-level gather (pair -> entity
  * row -> features) for multi-valued features, into the sample-major bag wire format a captured bag-mode step's static buffers
  * hold.  A store keeps dense_store f32 [N, dense_dim] and its bags as CSR over (entity, key) slots: the bag of entity e, key k

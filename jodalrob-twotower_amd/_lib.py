@@ -258,6 +258,9 @@ SIGNATURES = {
     "tt_bag_prepare_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tt_bag_prepare": (C.c_int, [vp, C.POINTER(BagLengths), i32, i64, vp, vp, sz, vp]),
     "tt_dedup_plan_pad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    "tt_embed_bag_fwd_w": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(vp), vp, vp]),
+    "tt_embed_bag_fwd_cap_w": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(vp), vp, vp]),
+    "tt_embed_bag_grad_bwd_w": (C.c_int, [vp, C.POINTER(GradSrc), i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
     "tt_bag_store_tile": (C.c_int, []),
     "tt_bag_store_gather_workspace_bytes": (sz, [i64, i32]),
     "tt_bag_store_gather": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSide), i32, i64, vp, vp, sz, vp]),

@@ -282,10 +282,12 @@ class CategoricalEmbedder(nn.Module):
     def bag_mode(self) -> bool:
         return self.pooling is not None
 
-    def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor, count: Optional[torch.Tensor] = None) -> ops.BagSide:
-        """count: the device word of a captured step's static id buffer -- `values` is then that buffer, its size the capacity"""
+    def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor, count: Optional[torch.Tensor] = None,
+                 weights: Optional[torch.Tensor] = None) -> ops.BagSide:
+        """count: the device word of a captured step's static id buffer -- `values` is then that buffer, its size the capacity.
+        weights: the KJT's weights (one f32 per id, in the order of `values`), or None: every id weighs 1"""
         return ops.BagSide(values, lengths, self._key_row_offset, self._key_vocab, self._key_pool, out_view, len(self.keys),
-                           any(m == "mean" for m in self.pooling), None if count is None else values.numel(), count)
+                           any(m == "mean" for m in self.pooling), None if count is None else values.numel(), count, weights)
 
     # ---- vocab sizes: src/towers/cat_embed.py:50-85 -------------------------------------------
     def _extract_vocab_sizes(self, metadata_path, table_name: str, keys: List[str]) -> Dict[str, int]:
@@ -393,9 +395,11 @@ class CategoricalEmbedder(nn.Module):
                 return {k: torch.zeros(1, E, device=dev) for k in self.keys}
             return torch.zeros(1, K * E, device=dev)
         values = kjt.values()
+        weights = kjt_weights(kjt)
         if self.bag_mode:
-            cat = _LookupFn.apply(self, (values, kjt.lengths()), *self.table_parameters())
+            cat = _LookupFn.apply(self, (values, kjt.lengths(), weights), *self.table_parameters())
         else:
+            refuse_weights(weights, "CategoricalEmbedder")
             cat = _LookupFn.apply(self, values, *self.table_parameters())
         if not return_dict:
             return cat
@@ -409,17 +413,19 @@ class _LookupFn(torch.autograd.Function):
     def forward(ctx, emb: CategoricalEmbedder, values, *tables):
         K, E = len(emb.keys), emb.embedding_dim
         ctx.bag = None
-        if emb.bag_mode:                                                  # (values, lengths): pooled bags
-            values, lengths = values
+        if emb.bag_mode:                                                  # (values, lengths[, weights]): pooled bags
+            values, lengths, weights = values if len(values) == 3 else (*values, None)
             dev = emb.store.device
             values = values.to(device=dev, dtype=torch.int64).contiguous()
             lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+            if weights is not None:
+                weights = weights.detach().to(device=dev, dtype=torch.float32).contiguous()      # data: no gradient flows to them
             B = lengths.numel() // max(K, 1)
             out = torch.empty((B, K * E), dtype=torch.float32, device=dev)
             need_grad = any(ctx.needs_input_grad)
             ctx.emb, ctx.B, ctx.plan = emb, B, None
             if K and B:
-                bag = ops.embed_bag_lookup(emb.store.weight, [emb.bag_side(values, lengths[:B * K], out)], B, want_rows=need_grad)
+                bag = ops.embed_bag_lookup(emb.store.weight, [emb.bag_side(values, lengths[:B * K], out, weights=weights)], B, want_rows=need_grad)
                 if bag is not None and bag.nnz:
                     ctx.bag, ctx.plan = bag, ops.dedup_plan(bag.rows, emb.store.rows)
             return out
@@ -440,6 +446,19 @@ class _LookupFn(torch.autograd.Function):
             d_out = d_out.contiguous()
             emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B, members=[emb], bag=ctx.bag)
         return (None, None) + (None,) * len(emb.keys)
+
+
+def kjt_weights(kjt) -> Optional[torch.Tensor]:
+    """The per-id weights a KJT carries (ours or torchrec's: both answer weights_or_none()), or None"""
+    get = getattr(kjt, "weights_or_none", None)
+    return get() if get is not None else None
+
+
+def refuse_weights(weights, who: str) -> None:
+    """Weights mean something to a pooled lookup alone: an embedder that is not in bag mode raises instead of dropping them."""
+    if weights is not None:
+        raise ValueError(f"{who}: the KJT carries per-id weights, but this embedder is not in bag mode (pooling=None reads one id per "
+                         "key and no weights) -- build it with pooling='sum' / 'mean', or hand the ids over without weights")
 
 
 def bag_mode_embedders(module) -> List[str]:

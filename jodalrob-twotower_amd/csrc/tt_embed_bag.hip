@@ -3,6 +3,7 @@
 // the bag's rows with 16-byte loads and adds them in position order.  Backward: the lookup's duplicate-row plan over the
 // POSITIONS' rows (tt_plan.hip, unchanged), reduced like tt_grad.hip's rows -- same chunking, same workspace, the same long-row
 // finish body (tt_grad_ws.h) -- with the contribution of a position read through bag_of (its slot) and weighted for mean pooling.
+// The weighted form (one f32 weight per id: the _w entries) is a template parameter of the same kernels, not a copy of them.
 #include "tt_common.h"
 #include "tt_deferred.h"
 #include "tt_embed_slots.h"
@@ -46,7 +47,21 @@ struct BagSet {
 // ------------------------------------------------------------------------------------------------
 constexpr int kBagBatch = 8;
 
-__global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float* __restrict__ table) {
+// the kernel's argument.  The weighted form (W) adds the per-id weights: one f32 per position of a side (NULL: the side's ids all
+// weigh 1) and the place the gradient reads them back from, laid out like rows_out / bag_of.  The unweighted instantiation takes
+// BagSet as it is: its kernel-argument layout, like its code, does not change.
+template <bool W>
+struct BagFwdArgs : BagSet {};
+template <>
+struct BagFwdArgs<true> : BagSet {
+  const float* w[TT_MAX_SIDES];
+  float* w_out;
+};
+
+// W: acc = w * x for a bag's first position, acc = fma(w, x, acc) for every later one.  With every weight 1 these are the bits of
+// the unweighted form (1 * x = x, a -0 included; fma(1, x, acc) = acc + x).
+template <bool W>
+__global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, const float* __restrict__ table) {
   const uint32_t LG = a.LG;
   const uint32_t gthread = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lig = gthread & (LG - 1);
@@ -67,11 +82,18 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float
       o0 = o1 = 0;
     }
     const int64_t hi = s.vocab[k] - 1, base = s.off[k];
+    const float* sw = nullptr;
+    if constexpr (W) sw = a.w[si];
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t p = o0; p < o1; p += kBagBatch) {
       int64_t id[kBagBatch];
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) id[j] = p + j < o1 ? s.ids[p + j] : 0;
+      float wj[kBagBatch];                                     // (W) the trip's weights, loaded next to its ids: no new dependent level
+      if constexpr (W) {
+#pragma unroll
+        for (int j = 0; j < kBagBatch; ++j) wj[j] = (sw && p + j < o1) ? sw[p + j] : 1.f;
+      }
       float4 v[kBagBatch];
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) {
@@ -82,6 +104,9 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float
           if (lig == ((uint32_t)j & (LG - 1))) {
             if (a.rows_out) a.rows_out[s.pos_base + (p + j)] = (int32_t)row;
             if (a.bag_of) a.bag_of[s.pos_base + (p + j)] = (int32_t)slot;
+            if constexpr (W) {
+              if (a.w_out) a.w_out[s.pos_base + (p + j)] = wj[j];
+            }
           }
           if (live) v[j] = *reinterpret_cast<const float4*>(table + row * a.E + lig * 4);
         }
@@ -89,7 +114,15 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagSet a, const float
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) {
         if (p + j >= o1) continue;
-        if (p + j == o0) {                                   // the first row as it is: a bag of one id is a bit-exact copy
+        if constexpr (W) {
+          if (p + j == o0) {
+            acc.x = __fmul_rn(wj[j], v[j].x); acc.y = __fmul_rn(wj[j], v[j].y);
+            acc.z = __fmul_rn(wj[j], v[j].z); acc.w = __fmul_rn(wj[j], v[j].w);
+          } else {
+            acc.x = __fmaf_rn(wj[j], v[j].x, acc.x); acc.y = __fmaf_rn(wj[j], v[j].y, acc.y);
+            acc.z = __fmaf_rn(wj[j], v[j].z, acc.z); acc.w = __fmaf_rn(wj[j], v[j].w, acc.w);
+          }
+        } else if (p + j == o0) {                            // the first row as it is: a bag of one id is a bit-exact copy
           acc = v[j];
         } else {
           acc.x += v[j].x; acc.y += v[j].y; acc.z += v[j].z; acc.w += v[j].w;
@@ -315,6 +348,13 @@ struct BagGradSet {
   const int32_t* bag_of;
   const float* inv_len;
 };
+// (weighted form) + the weight of every position; the unweighted instantiations take BagGradSet as it is
+template <bool W>
+struct BagGradArgs : BagGradSet {};
+template <>
+struct BagGradArgs<true> : BagGradSet {
+  const float* pos_w;
+};
 
 __global__ void bag_zero_words_kernel(int32_t* __restrict__ p, int n) {
   if ((int)threadIdx.x < n) p[threadIdx.x] = 0;
@@ -322,14 +362,26 @@ __global__ void bag_zero_words_kernel(int32_t* __restrict__ p, int n) {
 
 // ordered sum over positions sorted_src[lo..hi) for one 16-byte column piece: acc = fma(w, x, acc) in that order, kBagBatch
 // gradient loads in flight.  The side's fields are picked with selects on kernel-argument scalars, as tt_grad.hip's grad_addr does.
-template <int DT>
-__device__ __forceinline__ void bag_sum_range(const BagGradSet& a, const int32_t* __restrict__ sorted_src, int32_t lo, int32_t hi,
+// W: the coefficient of position P is pos_w[P], times inv_len[slot] (one f32 product) where inv_len is given; pos_w[P] is loaded at
+// the level of bag_of[P] -- both hang off sorted_src[i].
+template <int DT, bool W>
+__device__ __forceinline__ void bag_sum_range(const BagGradArgs<W>& a, const int32_t* __restrict__ sorted_src, int32_t lo, int32_t hi,
                                               uint32_t chunk, Acc<4>& acc) {
   constexpr int ESZ = DT == TT_F32 ? 4 : 2;
   for (int32_t i = lo; i < hi; i += kBagBatch) {
     int32_t slot[kBagBatch];
+    float pw[kBagBatch];
+    if constexpr (W) {
 #pragma unroll
-    for (int j = 0; j < kBagBatch; ++j) slot[j] = i + j < hi ? a.bag_of[sorted_src[i + j]] : -1;
+      for (int j = 0; j < kBagBatch; ++j) {
+        const int32_t P = i + j < hi ? sorted_src[i + j] : -1;
+        slot[j] = P >= 0 ? a.bag_of[P] : -1;
+        pw[j] = P >= 0 ? a.pos_w[P] : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kBagBatch; ++j) slot[j] = i + j < hi ? a.bag_of[sorted_src[i + j]] : -1;
+    }
     float w[kBagBatch];
     float x[kBagBatch][4];
 #pragma unroll
@@ -352,7 +404,8 @@ __device__ __forceinline__ void bag_sum_range(const BagGradSet& a, const int32_t
       const uint32_t local = sl - sb;
       const uint32_t b = local / K, k = local - b * K;
       const char* p = base + ((int64_t)b * ld + (int64_t)(k * (uint32_t)a.E + chunk * 4)) * ESZ;
-      w[j] = a.inv_len ? a.inv_len[sl] : 1.f;
+      if constexpr (W) w[j] = a.inv_len ? __fmul_rn(pw[j], a.inv_len[sl]) : pw[j];
+      else w[j] = a.inv_len ? a.inv_len[sl] : 1.f;
       if (DT == TT_F32) {
         const float4 t4 = *reinterpret_cast<const float4*>(p);
         x[j][0] = t4.x; x[j][1] = t4.y; x[j][2] = t4.z; x[j][3] = t4.w;
@@ -383,8 +436,8 @@ __device__ __forceinline__ void bag_write_row(float* __restrict__ out, int64_t r
 
 // one lane group per distinct row; rows of more than kLongSeg positions are registered in the workspace's lists (as
 // tt_grad.hip's unplanned row pass registers them) and summed chunk by chunk by bag_chunk_kernel
-template <int DT>
-__global__ __launch_bounds__(kThreads) void bag_reduce_kernel(BagGradSet a, const int32_t* __restrict__ sorted_src,
+template <int DT, bool W>
+__global__ __launch_bounds__(kThreads) void bag_reduce_kernel(BagGradArgs<W> a, const int32_t* __restrict__ sorted_src,
                                                              const int32_t* __restrict__ seg, const int32_t* __restrict__ unique_rows,
                                                              const int32_t* __restrict__ n_unique, int32_t mode, float* __restrict__ out,
                                                              GradWs ws, uint32_t LG) {
@@ -402,14 +455,14 @@ __global__ __launch_bounds__(kThreads) void bag_reduce_kernel(BagGradSet a, cons
     if (lig < a.C) {
       Acc<4> acc;
       acc.zero();
-      bag_sum_range<DT>(a, sorted_src, s0, s1, lig, acc);
+      bag_sum_range<DT, W>(a, sorted_src, s0, s1, lig, acc);
       bag_write_row(out, orow, a.E, lig, acc, mode == TT_GRAD_DENSE_ACC);
     }
   }
 }
 
-template <int DT>
-__global__ __launch_bounds__(kThreads) void bag_chunk_kernel(BagGradSet a, const int32_t* __restrict__ sorted_src, GradWs ws, uint32_t LG) {
+template <int DT, bool W>
+__global__ __launch_bounds__(kThreads) void bag_chunk_kernel(BagGradArgs<W> a, const int32_t* __restrict__ sorted_src, GradWs ws, uint32_t LG) {
   const uint32_t nchunks = (uint32_t)ws.counters[0];
   if (blockIdx.x == 0 && threadIdx.x == 0) ws.counters[2] = ws.counters[1];      // snapshot for the finish
   const uint32_t gthread = blockIdx.x * blockDim.x + threadIdx.x;
@@ -419,7 +472,7 @@ __global__ __launch_bounds__(kThreads) void bag_chunk_kernel(BagGradSet a, const
     if (lig >= a.C) continue;
     Acc<4> acc;
     acc.zero();
-    bag_sum_range<DT>(a, sorted_src, ws.chunk_lo[c], ws.chunk_hi[c], lig, acc);
+    bag_sum_range<DT, W>(a, sorted_src, ws.chunk_lo[c], ws.chunk_hi[c], lig, acc);
     bag_write_row(ws.chunk_partial, (int64_t)c, a.E, lig, acc, false);
   }
 }
@@ -440,13 +493,14 @@ static int bag_unsupported(const char* who, const char* what) {
 
 // tt_embed_bag_fwd (cap false) and its capacity form (cap true: nnz is each side's capacity, uncovered positions get table_rows / -1)
 static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
-                        int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream, bool cap) {
+                        int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream, bool cap, bool weighted = false,
+                        const float* const* weights = nullptr, float* w_out = nullptr) {
   TT_CHECK_ARG(ctx && table && sides, "tt_embed_bag_fwd: NULL argument");
   TT_CHECK_ARG(n_sides >= 1 && n_sides <= TT_MAX_SIDES, "tt_embed_bag_fwd: n_sides=%d not in [1,%d]", n_sides, TT_MAX_SIDES);
   TT_CHECK_ARG(B >= 0 && table_rows >= 1 && table_rows <= INT32_MAX, "tt_embed_bag_fwd: bad B=%lld rows=%lld", (long long)B, (long long)table_rows);
   if (E % 4 != 0 || E < 4 || E > 256) return bag_unsupported("tt_embed_bag_fwd", "E must be a multiple of 4 in [4, 256]");
   if (!tt_aligned(table, 16)) return bag_unsupported("tt_embed_bag_fwd", "the table must be 16-byte aligned");
-  BagSet a{};
+  BagFwdArgs<true> a{};      // (the unweighted launch passes its BagSet part)
   a.n = n_sides;
   a.E = E;
   a.C = (uint32_t)(E / 4);
@@ -454,6 +508,9 @@ static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int
   int64_t slots = 0, positions = 0;
   for (int i = 0; i < n_sides; ++i) {
     const tt_bag_side& s = sides[i];
+    a.w[i] = weighted && weights ? weights[i] : nullptr;
+    TT_CHECK_ARG(!(rows_out && a.w[i] && !w_out), "tt_embed_bag_fwd_w: rows_out with weights on side %d needs w_out", i);
+    if (!tt_aligned(a.w[i], 4) || !tt_aligned(w_out, 4)) return bag_unsupported("tt_embed_bag_fwd_w", "weights and w_out must be 4-byte aligned");
     TT_CHECK_ARG(s.K >= 1 && s.nnz >= 0, "tt_embed_bag_fwd: side %d has K=%d nnz=%lld", i, s.K, (long long)s.nnz);
     TT_CHECK_ARG(s.offsets && s.key_row_offset && s.key_vocab && s.key_pool && s.out && (s.ids || s.nnz == 0), "tt_embed_bag_fwd: side %d has NULL pointers", i);
     TT_CHECK_ARG(s.out_dtype == TT_F32 || s.out_dtype == TT_BF16, "tt_embed_bag_fwd: side %d bad out_dtype %d", i, s.out_dtype);
@@ -477,7 +534,14 @@ static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int
   a.total_pos = (uint32_t)positions;
   // (capacity form: the grid is sized by the bags and the capacities, never by the live count)
   const int64_t threads = cap && positions > slots * a.LG ? positions : slots * a.LG;
-  bag_fwd_kernel<<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  a.w_out = w_out;
+  if (weighted) {
+    bag_fwd_kernel<true><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  } else {
+    BagFwdArgs<false> u{};
+    static_cast<BagSet&>(u) = a;
+    bag_fwd_kernel<false><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(u, table);
+  }
   TT_LAUNCH_CHECK();
   return TT_OK;
 }
@@ -493,6 +557,19 @@ int tt_embed_bag_fwd_cap(tt_ctx* ctx, const float* table, int64_t table_rows, in
                          int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream) {
   TT_CHECK_ARG(table_rows < INT32_MAX, "tt_embed_bag_fwd_cap: no room for the pad row behind %lld rows", (long long)table_rows);
   return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, true);
+}
+
+int tt_embed_bag_fwd_w(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                       int64_t B, int32_t* rows_out, int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream) {
+  TT_CHECK_ARG(weights, "tt_embed_bag_fwd_w: NULL weights array (a side without weights has a NULL entry)");
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, false, true, weights, w_out);
+}
+
+int tt_embed_bag_fwd_cap_w(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                           int64_t B, int32_t* rows_out, int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream) {
+  TT_CHECK_ARG(weights, "tt_embed_bag_fwd_cap_w: NULL weights array (a side without weights has a NULL entry)");
+  TT_CHECK_ARG(table_rows < INT32_MAX, "tt_embed_bag_fwd_cap_w: no room for the pad row behind %lld rows", (long long)table_rows);
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, true, true, weights, w_out);
 }
 
 size_t tt_bag_prepare_workspace_bytes(const int64_t* side_slots, int32_t n_sides) {
@@ -543,13 +620,22 @@ int tt_embed_bag_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, 
                           const float* inv_len, const int32_t* sorted_src, const int32_t* seg_offsets, const int32_t* unique_rows,
                           const int32_t* n_unique, int64_t nnz, int32_t mode, float* out, void* workspace, size_t workspace_bytes,
                           tt_stream stream) {
+  return tt_embed_bag_grad_bwd_w(ctx, srcs, n_srcs, B, E, bag_of, inv_len, nullptr, sorted_src, seg_offsets, unique_rows, n_unique, nnz, mode,
+                                 out, workspace, workspace_bytes, stream);
+}
+
+// pos_w NULL: the unweighted kernels, launched as tt_embed_bag_grad_bwd always launched them
+int tt_embed_bag_grad_bwd_w(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, int64_t B, int32_t E, const int32_t* bag_of,
+                            const float* inv_len, const float* pos_w, const int32_t* sorted_src, const int32_t* seg_offsets,
+                            const int32_t* unique_rows, const int32_t* n_unique, int64_t nnz, int32_t mode, float* out, void* workspace,
+                            size_t workspace_bytes, tt_stream stream) {
   TT_CHECK_ARG(ctx && srcs && out, "tt_embed_bag_grad_bwd: NULL argument");
   TT_CHECK_ARG(n_srcs >= 1 && n_srcs <= TT_MAX_SIDES, "tt_embed_bag_grad_bwd: n_srcs=%d", n_srcs);
   TT_CHECK_ARG(mode >= TT_GRAD_SPARSE && mode <= TT_GRAD_DENSE_ACC, "tt_embed_bag_grad_bwd: bad mode %d (the PLANNED / DEFER_FINISH / SHORT forms are not offered)", mode);
   TT_CHECK_ARG(B >= 0 && nnz >= 0 && nnz < ((int64_t)1 << 31), "tt_embed_bag_grad_bwd: bad B / nnz");
   if (E % 4 != 0 || E < 4 || E > 256) return bag_unsupported("tt_embed_bag_grad_bwd", "E must be a multiple of 4 in [4, 256]");
   if (!tt_aligned(out, 16)) return bag_unsupported("tt_embed_bag_grad_bwd", "out must be 16-byte aligned");
-  BagGradSet a{};
+  BagGradArgs<true> a{};      // (the unweighted launches pass its BagGradSet part)
   a.n = n_srcs;
   a.E = E;
   int64_t slots = 0;
@@ -580,6 +666,7 @@ int tt_embed_bag_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, 
   a.total_slots = (uint32_t)slots;
   a.bag_of = bag_of;
   a.inv_len = inv_len;
+  a.pos_w = pos_w;
   const GradLayout gl = grad_layout(reinterpret_cast<char*>(workspace), nnz, E);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = tt_deferred_flush(ctx, TT_DQ_ALL)) return rc;      // the sources may be the products of a launch still queued
@@ -587,12 +674,18 @@ int tt_embed_bag_grad_bwd(tt_ctx* ctx, const tt_grad_src* srcs, int32_t n_srcs, 
   const int dt = srcs[0].dtype;
   bag_zero_words_kernel<<<1, 64, 0, st>>>(gl.ws.counters, 2);
   TT_LAUNCH_CHECK();
-  if (dt == TT_F32) bag_reduce_kernel<TT_F32><<<g1, kThreads, 0, st>>>(a, sorted_src, seg_offsets, unique_rows, n_unique, mode, out, gl.ws, LG);
-  else bag_reduce_kernel<TT_BF16><<<g1, kThreads, 0, st>>>(a, sorted_src, seg_offsets, unique_rows, n_unique, mode, out, gl.ws, LG);
+  BagGradArgs<false> u{};
+  static_cast<BagGradSet&>(u) = a;
+#define TT_BAG_REDUCE(DT, W, A) bag_reduce_kernel<DT, W><<<g1, kThreads, 0, st>>>(A, sorted_src, seg_offsets, unique_rows, n_unique, mode, out, gl.ws, LG)
+#define TT_BAG_CHUNK(DT, W, A) bag_chunk_kernel<DT, W><<<g2, kThreads, 0, st>>>(A, sorted_src, gl.ws, LG)
+  if (pos_w) { if (dt == TT_F32) TT_BAG_REDUCE(TT_F32, true, a); else TT_BAG_REDUCE(TT_BF16, true, a); }
+  else { if (dt == TT_F32) TT_BAG_REDUCE(TT_F32, false, u); else TT_BAG_REDUCE(TT_BF16, false, u); }
   TT_LAUNCH_CHECK();
-  if (dt == TT_F32) bag_chunk_kernel<TT_F32><<<g2, kThreads, 0, st>>>(a, sorted_src, gl.ws, LG);
-  else bag_chunk_kernel<TT_BF16><<<g2, kThreads, 0, st>>>(a, sorted_src, gl.ws, LG);
+  if (pos_w) { if (dt == TT_F32) TT_BAG_CHUNK(TT_F32, true, a); else TT_BAG_CHUNK(TT_BF16, true, a); }
+  else { if (dt == TT_F32) TT_BAG_CHUNK(TT_F32, false, u); else TT_BAG_CHUNK(TT_BF16, false, u); }
   TT_LAUNCH_CHECK();
+#undef TT_BAG_REDUCE
+#undef TT_BAG_CHUNK
   bag_long_finish_kernel<<<g3, kThreads, 0, st>>>(E, a.C, seg_offsets, unique_rows, mode, out, gl.ws, LG);
   TT_LAUNCH_CHECK();
   return TT_OK;

@@ -23,7 +23,7 @@ import torch
 from . import _lib as L
 from . import batch_terms as T
 from . import ops
-from .cat_embed import bag_mode_embedders, refuse_bag_mode
+from .cat_embed import bag_mode_embedders, kjt_weights, refuse_bag_mode
 from .config import settings
 from .data_loader import DeviceBagFeatureStore
 from .kjt import KeyedJaggedTensor
@@ -71,6 +71,7 @@ class GraphedTrainStep:
     _steps_per_replay = 1          # (unrolled.UnrolledTrainStep: several steps, hand-overs included, per graph launch)
     _bag_capture = True            # bag_capacity is honoured (the unrolled / segmented steps keep refusing bag mode)
     _bag: Dict[str, int] = {}      # {side: capacity} of the bag-mode sides (none: a plain model)
+    _bag_w: frozenset = frozenset()   # the bag-mode sides captured WITH per-id weights (the example KJT carried them)
     _accepts = frozenset(T.ROWS)   # the batch entries that change the loss (batch_terms.TABLE) an example batch may carry; the
                                    # unrolled / segmented steps take none
 
@@ -213,7 +214,7 @@ class GraphedTrainStep:
 
     def _bag_sides(self, task, example_batch, bag_capacity) -> Dict[str, int]:
         """{side: capacity} of the sides whose embedder pools bags, after the refusals (no device work)"""
-        self._bag_n = {}
+        self._bag_n, self._bag_w = {}, frozenset()
         if not bag_mode_embedders(task):
             if bag_capacity is not None:
                 raise ValueError("bag_capacity: the model has no bag-mode embedder (categorical_pooling)")
@@ -230,20 +231,31 @@ class GraphedTrainStep:
         if not sides or getattr(task, "exchange", None) is not None:
             refuse_bag_mode(task, type(self).__name__)
         self._bag_n = dict(sides)                  # ids the static buffer holds now (the count word of the next hand-over)
+        self._bag_w = frozenset(side for side in sides if kjt_weights(example_batch[side]["kjt"]) is not None)
+        for side in self._bag_w:
+            w, v = kjt_weights(example_batch[side]["kjt"]), example_batch[side]["kjt"].values()
+            if w.numel() != v.numel():
+                raise ValueError(f"{side}: the example batch carries {w.numel()} weights for {v.numel()} ids")
         return resolve_bag_capacity(bag_capacity, sides)
 
     def _static_kjt(self, kjt, side, dev):
         """the static KJT of a side: its ids; a bag-mode side: an id buffer of the capacity (the example's ids at its head) and the
-        [B*K] lengths (its count word is attached once the scalars exist)"""
+        [B*K] lengths (its count word is attached once the scalars exist); a side captured with weights: also an f32 weight buffer of
+        the capacity, zero-initialised, the example's weights at its head -- the towers then take the capacity form's weighted entry"""
         if side not in self._bag:
             return KeyedJaggedTensor(kjt.keys(), kjt.values().clone())
         v = kjt.values().to(device=dev, dtype=torch.int64).reshape(-1)
         buf = torch.zeros(self._bag[side], dtype=torch.int64, device=dev)
         buf[:v.numel()] = v
-        return KeyedJaggedTensor(kjt.keys(), buf, kjt.lengths().to(device=dev, dtype=torch.int64).reshape(-1).clone())
+        wbuf = None
+        if side in self._bag_w:
+            wbuf = torch.zeros(self._bag[side], dtype=torch.float32, device=dev)
+            wbuf[:v.numel()] = kjt_weights(kjt).to(device=dev, dtype=torch.float32).reshape(-1)
+        return KeyedJaggedTensor(kjt.keys(), buf, kjt.lengths().to(device=dev, dtype=torch.int64).reshape(-1).clone(), wbuf)
 
     def _bag_check(self, batch):
-        """a bag-mode side's ids fit the capacity and its lengths are B*K -- before anything is copied"""
+        """a bag-mode side's ids fit the capacity, its lengths are B*K and it carries weights (one per id) exactly when the side was
+        captured with them -- before anything is copied"""
         if batch is None:
             return
         for side, cap in self._bag.items():
@@ -252,16 +264,26 @@ class GraphedTrainStep:
                 raise ValueError(f"{side}: {kjt.values().numel()} ids, the step was captured with bag_capacity = {cap}")
             if kjt.lengths().numel() != st.lengths().numel():
                 raise ValueError(f"{side}: {kjt.lengths().numel()} bag lengths, the captured step holds B*K = {st.lengths().numel()}")
+            w = kjt_weights(kjt)
+            if (w is not None) != (side in self._bag_w):
+                raise ValueError(f"{side}: the batch carries {'per-id weights' if w is not None else 'no weights'}, the step was captured "
+                                 f"{'with' if side in self._bag_w else 'without'} them (the example batch decides)")
+            if w is not None and w.numel() != kjt.values().numel():
+                raise ValueError(f"{side}: {w.numel()} weights for {kjt.values().numel()} ids")
 
     def _bag_pairs(self, side, kjt):
-        """copy segments of a bag-mode side's ids (into the head of the static buffer) and lengths; the count goes with the scalars"""
+        """copy segments of a bag-mode side's ids (into the head of the static buffer), lengths and -- a side captured with them --
+        weights (into the head of the static weight buffer, beside the ids); the count goes with the scalars"""
         st = self.static[side]["kjt"]
         v, ln = kjt.values().reshape(-1), kjt.lengths().reshape(-1)
         sv, sl = st.values(), st.lengths()
         n = v.numel()
         self._bag_n[side] = n
         out = []
-        for dst, src in ((sv[:n], v), (sl, ln)):
+        segs = [(sv[:n], v), (sl, ln)]
+        if side in self._bag_w:
+            segs.insert(1, (st.weights()[:n], kjt_weights(kjt).reshape(-1)))
+        for dst, src in segs:
             if not dst.numel():
                 continue
             if src.device == dst.device and src.dtype == dst.dtype:
@@ -697,6 +719,9 @@ class GraphedTrainStep:
             if row.key in self._terms:
                 raise NotImplementedError(f"{row.noun}: no store-fed hand-over -- a step captured with '{row.key}' takes step(batch)")
         stores = {"notice": notice_store, "company": company_store}
+        if self._bag_w:      # (the bag stores hold ids alone)
+            raise ValueError(f"step_from_store: the step was captured with per-id weights on {sorted(self._bag_w)}, and the bag stores carry "
+                             "none -- a weighted step takes step(batch)")
         if any(not isinstance(stores[side], DeviceBagFeatureStore) for side in self._bag):      # (a DeviceFeatureStore holds one id per key)
             refuse_bag_mode(self.task, "step_from_store")
         for side, fs in stores.items():

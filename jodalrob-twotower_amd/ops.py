@@ -307,17 +307,20 @@ class BagSide:
                                      # first sum(lengths) are live -- device data; the tail is stale and never read
     count: Optional[torch.Tensor] = None   # (capacity form) int32 [1] on the device: the id count the host handed over, compared
                                            # with sum(lengths) on the device; None: not compared
+    weights: Optional[torch.Tensor] = None # f32 [nnz] ([capacity] in the capacity form): one weight per id; None: every id weighs 1
 
 
 class BagPlan(NamedTuple):
     """What embed_bag_lookup leaves for embed_bag_grad: rows / bag_of per position (int32 [nnz]), inv_len per slot (f32, None when
     every key sums), nnz.  The capacity form: nnz is the sides' total capacity and pad_row (= table rows) what `rows` holds where no
-    bag covers -- the plan over such rows is bag_dedup_plan's padded one."""
+    bag covers -- the plan over such rows is bag_dedup_plan's padded one.  pos_w: the weighted form's weight per position (f32
+    [nnz], valid where a bag covers), None when no side carried weights."""
     rows: torch.Tensor
     bag_of: torch.Tensor
     inv_len: Optional[torch.Tensor]
     nnz: int
     pad_row: Optional[int] = None
+    pos_w: Optional[torch.Tensor] = None
 
 
 def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
@@ -325,6 +328,10 @@ def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
         raise ValueError("bag ids must be a contiguous int64 tensor on the table's device")
     if s.lengths.numel() != B * s.K or s.lengths.device != dev:
         raise ValueError(f"side {i}: {s.lengths.numel()} bag lengths for B={B}, K={s.K} (on the table's device)")
+    w = s.weights
+    if w is not None and (w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev or w.numel() != s.ids.numel()):
+        raise ValueError(f"side {i}: bag weights must be a contiguous float32 tensor of ids.numel() = {s.ids.numel()} elements on the "
+                         f"table's device, got {w.dtype} x {w.numel()} on {w.device}")
     for name, t, dt, n in (("key_row_offset", s.key_row_offset, torch.int64, s.K), ("key_vocab", s.key_vocab, torch.int64, s.K),
                            ("key_pool", s.key_pool, torch.int32, s.K)):
         if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
@@ -363,6 +370,12 @@ def bag_prepare(lengths: Sequence[torch.Tensor], key_pools: Sequence[torch.Tenso
     return offs, inv_len
 
 
+def _bag_weight_args(sides: Sequence[BagSide], positions: int, want_rows: bool, dev):
+    """(host array of the sides' weight pointers, w_out or None) for the _w entries"""
+    arr = (L.vp * len(sides))(*[L.ptr(s.weights) for s in sides])
+    return arr, (torch.empty(max(positions, 1), dtype=torch.float32, device=dev) if want_rows else None)
+
+
 def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int, want_rows: bool) -> Optional[BagPlan]:
     """The capacity form of embed_bag_lookup: tt_bag_prepare + tt_embed_bag_fwd_cap.  No launch here depends on how many ids are live."""
     dev, E = table.device, table.shape[1]
@@ -379,13 +392,20 @@ def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int,
                            s.out.stride(0), s.capacity, s.K, _dt(s.out))
     cap = sum(s.capacity for s in sides)
     idx = torch.empty((2, max(cap, 1)), dtype=torch.int32, device=dev) if want_rows else None      # (the launch writes every position)
+    pos_w = None
     with _timed("tt_embed_bag_fwd"):
-        L.check(L.load().tt_embed_bag_fwd_cap(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
-                                              L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
-                "tt_embed_bag_fwd_cap")
+        if any(s.weights is not None for s in sides):
+            warr, pos_w = _bag_weight_args(sides, cap, want_rows, dev)
+            L.check(L.load().tt_embed_bag_fwd_cap_w(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                                    L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
+                                                    warr, L.ptr(pos_w), L.stream(dev)), "tt_embed_bag_fwd_cap_w")
+        else:
+            L.check(L.load().tt_embed_bag_fwd_cap(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                                  L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
+                    "tt_embed_bag_fwd_cap")
     if not want_rows:
         return None
-    return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0])
+    return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0], None if pos_w is None else pos_w[:cap])
 
 
 def bag_dedup_plan(bag: BagPlan, table_rows: int) -> DedupPlan:
@@ -436,14 +456,21 @@ def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want
             inv.append(torch.where(mean, one / lf.clamp(min=1.0), one))        # fl(1 / L): one correctly rounded f32 division
     # zero-filled: a position no bag covers (offsets the kernel refused) then names row 0 / slot 0 instead of stale memory
     idx = torch.zeros((2, max(nnz, 1)), dtype=torch.int32, device=dev) if want_rows else None
+    pos_w = None
     with _timed("tt_embed_bag_fwd"):
-        L.check(L.load().tt_embed_bag_fwd(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
-                                          L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
-                "tt_embed_bag_fwd")
+        if any(s.weights is not None for s in sides):
+            warr, pos_w = _bag_weight_args(sides, nnz, want_rows, dev)
+            L.check(L.load().tt_embed_bag_fwd_w(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                                L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
+                                                warr, L.ptr(pos_w), L.stream(dev)), "tt_embed_bag_fwd_w")
+        else:
+            L.check(L.load().tt_embed_bag_fwd(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                              L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None, L.stream(dev)),
+                    "tt_embed_bag_fwd")
     if not want_rows:
         return None
     inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
-    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz)
+    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz])
 
 
 def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int, E: int, mode: int, out: torch.Tensor):
@@ -455,6 +482,9 @@ def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int,
     slots = sum(B * K for _, K in srcs)
     if bag.inv_len is not None and (bag.inv_len.numel() != slots or bag.inv_len.dtype != torch.float32 or bag.inv_len.device != dev):
         raise ValueError(f"inv_len must hold one float32 per slot ({slots}) on the output's device")
+    pw = bag.pos_w
+    if pw is not None and (pw.numel() != bag.nnz or pw.dtype != torch.float32 or pw.device != dev or not pw.is_contiguous()):
+        raise ValueError(f"pos_w must hold one float32 per position ({bag.nnz}) on the output's device")
     if out.dim() != 2 or out.shape[1] != E or out.dtype != torch.float32 or not out.is_contiguous() or \
             (mode == TT_GRAD_SPARSE and out.shape[0] < max(bag.nnz, 1)):
         raise ValueError("out must be a contiguous float32 [rows, E] tensor (sparse mode: room for nnz rows)")
@@ -468,6 +498,11 @@ def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int,
     lib = L.load()
     ws = L.workspace(dev, lib.tt_embed_bag_grad_workspace_bytes(bag.nnz, E))
     with _timed("tt_embed_bag_grad_bwd"):
+        if pw is not None:
+            L.check(lib.tt_embed_bag_grad_bwd_w(L.ctx(dev), arr, len(srcs), B, E, L.ptr(bag.bag_of), L.ptr(bag.inv_len), L.ptr(pw),
+                                                L.ptr(plan.sorted_src), L.ptr(plan.seg_offsets), L.ptr(plan.unique_rows), L.ptr(plan.n_unique),
+                                                bag.nnz, mode, L.ptr(out), L.ptr(ws), ws.numel(), L.stream(dev)), "tt_embed_bag_grad_bwd_w")
+            return
         L.check(lib.tt_embed_bag_grad_bwd(L.ctx(dev), arr, len(srcs), B, E, L.ptr(bag.bag_of), L.ptr(bag.inv_len), L.ptr(plan.sorted_src),
                                           L.ptr(plan.seg_offsets), L.ptr(plan.unique_rows), L.ptr(plan.n_unique), bag.nnz, mode,
                                           L.ptr(out), L.ptr(ws), ws.numel(), L.stream(dev)), "tt_embed_bag_grad_bwd")

@@ -44,10 +44,11 @@ def load_real_schema(path) -> dict:
 
 
 def make_batch(B: int, vocab_n: Sequence[int], vocab_c: Sequence[int], keys_n, keys_c, din_n: int, din_c: int, device,
-               seed: int, zipf_alpha: Optional[float] = None, bag_keys=None, mean_bag_length: float = 4.0) -> dict:
+               seed: int, zipf_alpha: Optional[float] = None, bag_keys=None, mean_bag_length: float = 4.0, bag_weights=None) -> dict:
     """ids ~ U[0, V_k) per key (or Zipf(alpha) ranks mapped through a fixed multiplicative hash), dense
     ~ N(0,1); generated on the device with a seeded generator (plumbing only).  bag_keys: names of keys (either side) that get
-    ragged multi-valued bags of about mean_bag_length ids instead of one id (ragged_bags): input for a bag-mode model."""
+    ragged multi-valued bags of about mean_bag_length ids instead of one id (ragged_bags): input for a bag-mode model;
+    bag_weights: ragged_bags' `weights` (None | "uniform") for those sides."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
 
@@ -71,14 +72,19 @@ def make_batch(B: int, vocab_n: Sequence[int], vocab_c: Sequence[int], keys_n, k
              "company": {"dense": dense(din_c), "kjt": KeyedJaggedTensor(list(keys_c), ids_for(vocab_c))}}
     if bag_keys:       # (drawn from a generator of their own: the length-one ids and the dense features are the plain batch's)
         for i, (side, vocabs) in enumerate((("notice", vocab_n), ("company", vocab_c))):
-            batch[side]["kjt"] = ragged_bags(batch[side]["kjt"], vocabs, bag_keys, mean_bag_length, seed + 7919 * (i + 1))
+            batch[side]["kjt"] = ragged_bags(batch[side]["kjt"], vocabs, bag_keys, mean_bag_length, seed + 7919 * (i + 1), bag_weights)
     return batch
 
 
-def ragged_bags(kjt: KeyedJaggedTensor, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0) -> KeyedJaggedTensor:
+def ragged_bags(kjt: KeyedJaggedTensor, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0,
+                weights=None) -> KeyedJaggedTensor:
     """The length-one `kjt` with the keys named in `bag_keys` turned into ragged bags: a Poisson(mean_length) number of ids per bag
     (empty bags included), the first one the kjt's own id, the others ~ U[0, V_k).  Keys not named keep their one id.  Returns
-    the sample-major wire format (kjt.build_bag_kjt): lengths [B*K], values = all bags concatenated in slot order."""
+    the sample-major wire format (kjt.build_bag_kjt): lengths [B*K], values = all bags concatenated in slot order.
+    weights: None -- a KJT without weights; "uniform" -- one f32 weight per id ~ U[0.5, 1.5) (seeded: drawn behind the ids, which stay
+    the ids of weights=None), the first id of every bag weighing 1."""
+    if weights not in (None, "uniform"):
+        raise ValueError(f"ragged_bags: weights must be None or 'uniform', got {weights!r}")
     keys = list(kjt.keys())
     K = len(keys)
     first = kjt.values().reshape(-1, K)
@@ -95,7 +101,11 @@ def ragged_bags(kjt: KeyedJaggedTensor, vocabs: Sequence[int], bag_keys, mean_le
     starts = torch.cumsum(lengths, 0) - lengths
     has = lengths > 0
     values[starts[has]] = first.reshape(-1)[has]
-    return KeyedJaggedTensor(keys, values, lengths)
+    w = None
+    if weights == "uniform":
+        w = (torch.rand(nnz, generator=g, device=dev, dtype=torch.float32) + 0.5).clamp_(max=1.4999999)
+        w[starts[has]] = 1.0
+    return KeyedJaggedTensor(keys, values, lengths, w)
 
 
 def bag_store(store, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0):

@@ -24,7 +24,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .config import settings
-from .cat_embed import CategoricalEmbedder, EmbeddingStore
+from .cat_embed import CategoricalEmbedder, EmbeddingStore, kjt_weights, refuse_weights
 
 
 _DEBUG_KEEP = None   # set to a list by debugging tools
@@ -285,9 +285,16 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
         # a bag-mode embedder also reads the bags' lengths; any other reads the values only, as before
         # (a captured step's static KJT: values() is a buffer of a fixed capacity and bag_count the device word with the id count the
         # host handed over -- the pair says "capacity form": ops.BagSide)
+        # a KJT with weights: (lengths, count or None, weights) -- the pooled lookup's weighted form
         count = getattr(kjt, "bag_count", None)
+        weights = kjt_weights(kjt)
+        if not tw.categorical_embedder.bag_mode:
+            refuse_weights(weights, type(tw).__name__)
         lengths = kjt.lengths() if tw.categorical_embedder.bag_mode else None
-        bag_lengths.append(lengths if count is None or lengths is None else (lengths, count))
+        if lengths is not None and weights is not None:
+            bag_lengths.append((lengths, count, weights))
+        else:
+            bag_lengths.append(lengths if count is None or lengths is None else (lengths, count))
         flat += [dense, values] + tw.dense_parameters() + tw.categorical_embedder.table_parameters()
     outs = _TowersFn.apply(tuple(towers), tuple(bag_lengths), *flat)
     outs = list(outs) if isinstance(outs, tuple) else [outs]
@@ -299,13 +306,14 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
 
 class _Side:
     __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values",
-                 "lengths", "count")
+                 "lengths", "count", "weights")
 
 
 class _TowersFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, towers, bag_lengths, *flat):
-        """bag_lengths: per tower, the KJT's lengths() for a bag-mode embedder, None for any other (its lengths are not read)"""
+        """bag_lengths: per tower, the KJT's lengths() for a bag-mode embedder -- or (lengths, count) for the capacity form, or
+        (lengths, count or None, weights) for a KJT with per-id weights -- None for any other (its lengths are not read)"""
         if len(bag_lengths) != len(towers):
             raise ValueError(f"{len(towers)} towers but {len(bag_lengths)} bag-length entries")
         sides: List[_Side] = []
@@ -326,9 +334,9 @@ class _TowersFn(torch.autograd.Function):
             dense = dense.to(dtype=torch.float32).contiguous()
             values = values.to(dtype=torch.int64).contiguous()
             B, K, E = dense.shape[0], len(emb.keys), emb.embedding_dim
-            count = None
-            if isinstance(lengths, tuple):      # (lengths, count): the capacity form
-                lengths, count = lengths
+            count = weights = None
+            if isinstance(lengths, tuple):      # (lengths, count): the capacity form; (lengths, count, weights): weighted bags
+                lengths, count, weights = lengths if len(lengths) == 3 else (*lengths, None)
             if emb.bag_mode:
                 if lengths is None or lengths.numel() != B * K:
                     raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
@@ -336,11 +344,14 @@ class _TowersFn(torch.autograd.Function):
                 if tw.exchange is not None:
                     raise ValueError("bag mode (categorical_pooling) is not supported with the sharded table exchange")
                 lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+                if weights is not None:
+                    weights = weights.to(device=dev, dtype=torch.float32).contiguous()
             elif values.numel() != B * K:
                 raise ValueError(f"kjt carries {values.numel()} ids but the batch needs B*K = {B}*{K}")
             s = _Side()
             s.lengths = lengths if emb.bag_mode else None
             s.count = count if emb.bag_mode else None
+            s.weights = weights if emb.bag_mode else None
             s.tower, s.B, s.train = tw, B, tw.training
             s.p_drop = tw.dropout_rate if tw.training else 0.0
             s.seed = 0 if s.p_drop <= 0 else (tw._seed_override if tw._seed_override is not None else
@@ -398,7 +409,7 @@ class _TowersFn(torch.autograd.Function):
                 a.emb_packed, a.emb_pack_scale = s.packed.data_ptr(), float(tw.pack_scale)
             s.acts_struct = a
             if K and B and emb.bag_mode:     # pooled bags: launches and plans of their own, beside the plain sides of the store
-                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:], s.count)))
+                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:], s.count, s.weights)))
             elif K and B:
                 lookups.setdefault(id(emb.store), []).append((s, emb.lookup_side(values, s.x[:, tw.tower_hidden_dims[0]:]), px is not None))
         # fused lookup (+ duplicate-row plan when a backward will follow) per store

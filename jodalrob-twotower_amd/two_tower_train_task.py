@@ -20,6 +20,7 @@ from . import batch_terms as T
 from . import ops
 from .batch_terms import _CLASH_WHY, _TERM_CLASHES, _TERM_FORMS, _terms_clash       # (what combines: the node decides with it; also imported from here)
 from .config import settings
+from .cat_embed import kjt_weights, refuse_weights
 from .kjt import KeyedJaggedTensor, concat_kjt
 from .towers import run_towers
 from .two_tower_model import TwoTowerModel, create_two_tower_model
@@ -432,6 +433,8 @@ class TwoTowerTrainTask(nn.Module):
         if self.two_tower_model.company_tower.categorical_embedder.bag_mode:      # ragged bags: the lengths ride along
             kjt = concat_kjt(company_input["kjt"], neg["kjt"])
         else:
+            for k in (company_input["kjt"], neg["kjt"]):
+                refuse_weights(kjt_weights(k), "the company tower")
             kjt = KeyedJaggedTensor(company_input["kjt"].keys(), torch.cat([company_input["kjt"].values(), neg["kjt"].values()], 0))
         both = {"dense": torch.cat([company_input["dense"], neg["dense"]], 0), "kjt": kjt}
         n_emb, cx = run_towers([self.two_tower_model.notice_tower, self.two_tower_model.company_tower], [notice_input, both])

@@ -140,6 +140,10 @@ def main():
                          "mean (bag mode; eager loop only).  The synthetic stores hold one id per key: every training batch draws "
                          "--pool-length more ids per bag on average; evaluation feeds each entity's own id as a bag of one")
     ap.add_argument("--pool-length", type=float, default=4.0, help="mean bag length of the --pool keys' synthetic bags")
+    ap.add_argument("--pool-weights", action="store_true",
+                    help="with --pool: every id of the pooled towers' bags carries a weight (the KJT's weights(): U[0.5, 1.5), a bag's first "
+                         "id weighing 1) -- the weighted pooled lookup, in the eager loop and with --pool-capture; not with --pool-store "
+                         "(the bag stores hold ids alone)")
     ap.add_argument("--pool-capture", nargs="?", type=float, const=2.0, default=None, metavar="FACTOR",
                     help="with --pool: the pooled loop runs as a captured step (GraphedTrainStep(bag_capacity=...)) whose static id "
                          "buffers hold FACTOR (default 2) times the first batch's ids per bag-mode side; a batch that does not fit "
@@ -157,6 +161,10 @@ def main():
     pooling = None
     if a.pool_store and not a.pool:
         ap.error("--pool-store needs --pool")
+    if a.pool_weights and not a.pool:
+        ap.error("--pool-weights needs --pool")
+    if a.pool_weights and a.pool_store:
+        ap.error("--pool-weights: not with --pool-store -- the device-resident bag stores hold ids alone (weighted stores are not built yet)")
     if a.pool_store and a.fast and (a.extra_negatives or a.mask_known):
         ap.error("--pool-store --fast: no store-fed hand-over with --extra-negatives or --mask-known")
     if a.pool:
@@ -266,8 +274,10 @@ def main():
         if pooling and not a.pool_store:                 # ragged bags for the pooled keys, drawn per step (seeded by the step number)
             batch = dict(batch)
             for side in ("notice", "company"):
+                weighted = a.pool_weights and any(k in pooling for k in batch[side]["kjt"].keys())      # (a tower that pools nothing takes none)
                 batch[side] = dict(batch[side], kjt=synthetic.ragged_bags(batch[side]["kjt"], real[side]["vocab_sizes"], pooling,
-                                                                          a.pool_length, seed=config["shuffle_seed"] + steps))
+                                                                          a.pool_length, seed=config["shuffle_seed"] + steps,
+                                                                          weights="uniform" if weighted else None))
         if a.pool_capture is not None and train_task.training and graphed is None:
             if pool_step is None:                        # captured on the first batch (its warm-up leaves no trace: preserve_state)
                 import math

@@ -11,6 +11,8 @@ ALGORITHMIC: the bytes the operation has to move by its definition over that tim
   gradient  read  nnz * (E * 4 + 8)  [the bag's d_out row, sorted_src, bag_of];  write U * E * 4
   plain     read  M * (E * 4 + 4);                                          write U * E * 4
 (the gradient's d_out rows are re-read once per id of the bag, so its algorithmic bytes count each read).
+--weighted: every id carries an f32 weight ~ U[0.5, 1.5) (tt_embed_bag_fwd_w / tt_embed_bag_grad_bwd_w): the lookup reads nnz * 4 more
+bytes and writes nnz * 4 more (w_out), the gradient reads nnz * 4 more (pos_w); the plain figures beside it are unchanged.
 One JSON line per mean length; --out writes them as a JSON list too."""
 import argparse
 import json
@@ -30,6 +32,8 @@ ap.add_argument("--rows", type=int, default=1_000_000, help="table rows per towe
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--lengths", type=float, nargs="+", default=[1, 4, 16])
 ap.add_argument("--out-dtype", choices=["f32", "bf16"], default="bf16", help="element type of the lookup output (the bench's x is bf16)")
+ap.add_argument("--weighted", action="store_true", help="per-id weights: the _w entries (lookup and gradient)")
+ap.add_argument("--tag", default="", help="copied into every result line (e.g. the run number, or 'parent')")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -77,7 +81,12 @@ for mean in a.lengths:
     outs = [torch.empty((B, K * E), dtype=odt, device=dev) for K in Ks]
     sides = [ops.BagSide(batch[s]["kjt"].values(), batch[s]["kjt"].lengths(), offs[i], voc[i], pool[i], outs[i], Ks[i], True)
              for i, s in enumerate(("notice", "company"))]
+    if a.weighted:
+        gw = torch.Generator(device=dev).manual_seed(11)
+        for s in sides:
+            s.weights = torch.rand(s.ids.numel(), generator=gw, device=dev) + 0.5
     nnz, slots = sum(int(s.ids.numel()) for s in sides), B * sum(Ks)
+    wb = nnz * 4 if a.weighted else 0
     bag = ops.embed_bag_lookup(table, sides, B, want_rows=True)
     plan = ops.dedup_plan(bag.rows, total)
     U = int(plan.n_unique.item())
@@ -99,15 +108,16 @@ for mean in a.lengths:
     t_plain = timed(["tt_embed_lookup_fwd"], lambda: ops.embed_lookup(table, psides, Bp, want_rows=True), a.iters)["tt_embed_lookup_fwd"]
     t_pgrad = timed(["tt_embed_grad_bwd"], lambda: ops.embed_grad(pplan, psrcs, Bp, E, ops.TT_GRAD_SPARSE, pgrad), a.iters)["tt_embed_grad_bwd"]
     gbs = lambda nbytes, us: round(nbytes / (us * 1e-6) / 1e9, 1)
-    r = {"mean_bag_length": mean, "B": B, "E": E, "keys": sum(Ks), "nnz": nnz, "unique_rows": U, "out_dtype": a.out_dtype,
-         "bag_lookup_us": round(t_bag, 2), "bag_lookup_GBps": gbs(nnz * (E * 4 + 8) + slots * 8 + slots * E * osz + nnz * 8, t_bag),
+    r = {"tag": a.tag, "weighted": a.weighted, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(Ks), "nnz": nnz, "unique_rows": U, "out_dtype": a.out_dtype,
+         "bag_lookup_us": round(t_bag, 2), "bag_lookup_GBps": gbs(nnz * (E * 4 + 8) + slots * 8 + slots * E * osz + nnz * 8 + 2 * wb, t_bag),
          "plain_lookup_rows": M, "plain_lookup_us": round(t_plain, 2), "plain_lookup_GBps": gbs(M * (E * 4 + 8) + M * E * osz + M * 4, t_plain),
          "bag_over_plain_lookup_time_at_equal_rows": round(t_bag / t_plain * M / nnz, 3),
-         "bag_grad_us": round(t_bgrad, 2), "bag_grad_GBps": gbs(nnz * (E * 4 + 8) + U * E * 4, t_bgrad),
+         "bag_grad_us": round(t_bgrad, 2), "bag_grad_GBps": gbs(nnz * (E * 4 + 8) + U * E * 4 + wb, t_bgrad),
          "plain_grad_us": round(t_pgrad, 2), "plain_grad_unique_rows": pU, "plain_grad_GBps": gbs(M * (E * 4 + 4) + pU * E * 4, t_pgrad),
          "bag_over_plain_grad_time_at_equal_rows": round(t_bgrad / t_pgrad * M / nnz, 3)}
     results.append(r)
     print(json.dumps(r), flush=True)
 if a.out:
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(json.dumps(results, indent=1) + "\n")
+    old = json.loads(Path(a.out).read_text()) if a.tag and Path(a.out).exists() else []      # (tagged runs append: one file per spread)
+    Path(a.out).write_text(json.dumps(old + results, indent=1) + "\n")

@@ -14,7 +14,9 @@ first --pool-keys keys of each tower hold ragged bags of Poisson(mean) ids (mean
   * plain_captured_launches         library_launches of the PLAIN model's captured step at this shape (this path must not change).
 
 Step times: a host clock around --steps steps that end in a device synchronise, after --warmup steps, in ms per step.  Run it
-several times (fresh processes) for a spread: every run prints one JSON line per mean length; --out appends them to a JSON list."""
+several times (fresh processes) for a spread: every run prints one JSON line per mean length; --out appends them to a JSON list.
+--weighted: every id of the bag-mode sides carries an f32 weight (synthetic.ragged_bags(weights="uniform")): the eager and the
+captured step then run the weighted entries (tt_embed_bag_fwd_w / _cap_w / tt_embed_bag_grad_bwd_w), and so do the launch-level figures."""
 import argparse
 import contextlib
 import io
@@ -46,6 +48,7 @@ ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--pool", type=int, default=4, help="batches the steps rotate through")
 ap.add_argument("--iters", type=int, default=50, help="calls per launch-level figure")
 ap.add_argument("--tag", default="", help="copied into every result line (e.g. the run number, or 'parent')")
+ap.add_argument("--weighted", action="store_true", help="per-id weights on the bag-mode sides: the weighted entries")
 ap.add_argument("--eager-only", action="store_true", help="the eager step only (a checkout without bag_capacity)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
@@ -75,7 +78,8 @@ def make_task(pooling):
 def batches(mean, n):
     bag_keys = set(pooled["notice"]) | set(pooled["company"])
     return [synthetic.make_batch(B, vocabs["notice"], vocabs["company"], keys["notice"], keys["company"], 256, 128, dev, seed=1234 + 7919 * i,
-                                 **({} if mean is None else dict(bag_keys=bag_keys, mean_bag_length=mean))) for i in range(n)]
+                                 **({} if mean is None else dict(bag_keys=bag_keys, mean_bag_length=mean)),
+                                 **(dict(bag_weights="uniform") if a.weighted and mean is not None else {})) for i in range(n)]
 
 
 def clock(step, pool):
@@ -127,7 +131,7 @@ results = []
 for mean in a.lengths:
     pool = batches(mean, a.pool)
     nnz = {s: max(b[s]["kjt"].values().numel() for b in pool) for s in keys}
-    r = {"tag": a.tag, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(len(k) for k in keys.values()), "pooled_keys_per_tower": a.pool_keys,
+    r = {"tag": a.tag, "weighted": a.weighted, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(len(k) for k in keys.values()), "pooled_keys_per_tower": a.pool_keys,
          "rows_per_tower": a.rows, "nnz": nnz, "steps": a.steps, "plain_captured_launches": plain_launches}
     pooling = {k: "mean" for s in keys for k in pooled[s]}
     task, opt = make_task(pooling)
@@ -160,11 +164,12 @@ for mean in a.lengths:
         Ks = [len(keys[s]) for s in keys]
         pools = [e._key_pool for e in embs]
         live = [v.numel() for v in ids]
+        wts = [b[s]["kjt"].weights_or_none() for s in keys]
         r["torch_prepare_us"] = round(events(lambda: torch_prepare(lengths, pools)), 2)
         r["prepare_us"] = round(events(lambda: ops.bag_prepare(lengths, pools, Ks, B, live, None)), 2)
         table = embs[0].store.weight
         outs = [torch.empty((B, K * E), dtype=torch.bfloat16, device=dev) for K in Ks]
-        exact = [e.bag_side(v, ln, o) for e, v, ln, o in zip(embs, ids, lengths, outs)]
+        exact = [e.bag_side(v, ln, o, weights=w) for e, v, ln, o, w in zip(embs, ids, lengths, outs, wts)]
         bag = ops.embed_bag_lookup(table, exact, B, want_rows=True)
         r["lookup_us"] = round(events(lambda: ops.embed_bag_lookup(table, exact, B, want_rows=True)), 2)
         r["plan_us"] = round(events(lambda: ops.dedup_plan(bag.rows, table.shape[0])), 2)
@@ -173,7 +178,8 @@ for mean in a.lengths:
             caps = [int(-(-n * f // 1)) for n in live]
             bufs = [torch.cat([v, torch.full((c - v.numel(),), 1 << 40, dtype=torch.int64, device=dev)]) for v, c in zip(ids, caps)]
             counts = [torch.tensor([n], dtype=torch.int32, device=dev) for n in live]
-            cap_sides = [e.bag_side(v, ln, o, cnt) for e, v, ln, o, cnt in zip(embs, bufs, lengths, outs, counts)]
+            wbufs = [None if w is None else torch.cat([w, torch.zeros(c - w.numel(), device=dev)]) for w, c in zip(wts, caps)]
+            cap_sides = [e.bag_side(v, ln, o, cnt, w) for e, v, ln, o, cnt, w in zip(embs, bufs, lengths, outs, counts, wbufs)]
             bagc = ops.embed_bag_lookup(table, cap_sides, B, want_rows=True)
             r["lookup_cap_us"][str(f)] = round(events(lambda: ops.embed_bag_lookup(table, cap_sides, B, want_rows=True)), 2)   # (prepare included)
             r["plan_pad_us"][str(f)] = round(events(lambda: ops.bag_dedup_plan(bagc, table.shape[0])), 2)
