@@ -1312,6 +1312,38 @@ int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* co
                         const tt_bag_store_side* sides, int32_t n_sides, int64_t B, const int64_t* order /* [B] or NULL */,
                         void* workspace, size_t workspace_bytes, tt_stream stream);
 
+/* tt_bag_store_gather for stores that keep one f32 weight per id (a KJT's weights(): a share, a confidence), in the order of
+ * `values`.  Everything tt_bag_store_gather writes, and for a side with weights
+ *   weights_out[start_b + j] = weights[offsets[e*K] + j]     for j in [0, run_b)     (a 32-bit copy, bit for bit)
+ * in the same two launches: the thread that moves an id piece moves its positions' weights.  A side with weights == NULL moves
+ * ids alone; a call whose sides all do is tt_bag_store_gather.  A refused side (total > capacity, total != expect, a run outside
+ * [0, nnz]) gets neither ids nor weights.  Nothing is written at or beyond weights_out[capacity]; weights_out[total .. capacity)
+ * keeps what it held; a source index outside [0, nnz) is not read.  weights and weights_out need 4-byte alignment, whatever
+ * ids_out's is.  With nnz > 0, weights and weights_out are both set or both NULL (TT_ERR_INVALID_ARG otherwise) -- except that, as
+ * ids_out, weights_out may be NULL where capacity == 0 (a batch without ids: such a side has nowhere to put a weight). */
+typedef struct tt_bag_store_side_w {
+  const int64_t* entity;
+  int64_t entity_stride;
+  const float* dense_store;
+  const int64_t* offsets;
+  const int64_t* values;
+  float* dense_out;
+  int64_t* lengths_out;
+  int64_t* ids_out;
+  int64_t nnz;
+  int64_t capacity;
+  int64_t expect;
+  int32_t dense_dim;
+  int32_t n_rows;
+  int32_t K;
+  int32_t reserved;
+  const float* weights;      /* [nnz], or NULL: this side moves ids alone */
+  float* weights_out;        /* [capacity] */
+} tt_bag_store_side_w;
+int tt_bag_store_gather_w(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
+                          const tt_bag_store_side_w* sides, int32_t n_sides, int64_t B, const int64_t* order /* [B] or NULL */,
+                          void* workspace, size_t workspace_bytes, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

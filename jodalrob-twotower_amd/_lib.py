@@ -57,6 +57,10 @@ class BagStoreSide(C.Structure):
                 ("K", i32), ("reserved", i32)]
 
 
+class BagStoreSideW(C.Structure):          # tt_bag_store_side_w: BagStoreSide's fields, then the per-id weights
+    _fields_ = BagStoreSide._fields_ + [("weights", vp), ("weights_out", vp)]
+
+
 TT_MAX_CVT = 8
 
 
@@ -264,6 +268,7 @@ SIGNATURES = {
     "tt_bag_store_tile": (C.c_int, []),
     "tt_bag_store_gather_workspace_bytes": (sz, [i64, i32]),
     "tt_bag_store_gather": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSide), i32, i64, vp, vp, sz, vp]),
+    "tt_bag_store_gather_w": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSideW), i32, i64, vp, vp, sz, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

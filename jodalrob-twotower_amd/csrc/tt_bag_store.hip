@@ -4,7 +4,8 @@
 // the concatenation of its entities' runs at the exclusive prefix sum of the runs' lengths -- the offsets tt_bag_prepare forms
 // again inside the captured graph.  Two launches, no workgroup waits on another (as tt_bag_prepare): the first writes the
 // lengths, the dense rows, the copy segments and one total per tile of kStoreTile samples; every workgroup of the second adds up
-// its side's earlier totals, scans its own tile and copies its share of the tile's ids.
+// its side's earlier totals, scans its own tile and copies its share of the tile's ids.  tt_bag_store_gather_w: a store that keeps
+// one f32 weight per id; the second launch's weighted instantiation moves the weights with the ids, bit for bit.
 #include "tt_common.h"
 #include "tt_embed_slots.h"
 #include "tt_copy_role.h"
@@ -43,6 +44,13 @@ struct BagStoreArgs {
   uint32_t* dev_err;
   int32_t n_copy, n_sides, B;
   uint32_t tiles;
+};
+
+// the weighted pack kernel's second argument: the sides' per-id weights (NULL: this side moves ids alone).  A record of its own,
+// so the unweighted kernels keep their one argument as it was.
+struct BagStoreWeights {
+  const uint32_t* w[TT_MAX_SIDES];       // [nnz] f32, moved as 32-bit words: bit for bit
+  uint32_t* w_out[TT_MAX_SIDES];         // [capacity]
 };
 
 __device__ __forceinline__ int store_side_of(const BagStoreArgs& a, uint32_t tile) {
@@ -138,7 +146,13 @@ __global__ __launch_bounds__(kThreads) void bag_store_lengths_kernel(BagStoreArg
 // DESTINATION's 16-byte grid: a piece whose two ids lie in the tile is one 16-byte store, fed by one 16-byte load when its ids are
 // neighbours in the store at a 16-byte aligned address and by two 8-byte loads otherwise; a piece at the tile's edge moves 8 bytes.
 // A position is found in the tile's runs by bisection, so a long run spreads over lanes and workgroups like any other.
-__global__ __launch_bounds__(kThreads) void bag_store_pack_kernel(BagStoreArgs a) {
+// W: the side's per-id weights ride with the ids -- the thread that owns piece q also moves the two floats of its positions, one
+// 8-byte load when the sources are neighbours at an 8-byte aligned address, one 8-byte store when both positions are live and the
+// destination is 8-byte aligned, 4-byte accesses otherwise (weights and weights_out are 4-byte aligned, whatever ids_out is).
+// (Wt: BagStoreWeights for W, nothing otherwise -- the unweighted instantiation takes the one argument it always took)
+template <bool W, class... Wt>
+__global__ __launch_bounds__(kThreads) void bag_store_pack_kernel(BagStoreArgs a, Wt... wt) {
+  static_assert(sizeof...(Wt) == (W ? 1 : 0), "the weighted form takes one BagStoreWeights");
   __shared__ int64_t s_start[kStoreTile + 1];
   __shared__ int64_t s_src[kStoreTile];
   __shared__ int64_t sh[4];
@@ -194,8 +208,16 @@ __global__ __launch_bounds__(kThreads) void bag_store_pack_kernel(BagStoreArgs a
   const int64_t A = (int64_t)((reinterpret_cast<uintptr_t>(s.ids_out) >> 3) & 1);              // ids_out is 8 mod 16: piece q holds ids 2q - 1, 2q
   const int64_t q_hi = (te - 1 + A) >> 1;
   const int64_t stride = (int64_t)gridDim.y * kThreads;
+  [[maybe_unused]] const uint32_t* wsrc = nullptr;
+  [[maybe_unused]] uint32_t* wdst = nullptr;
+  if constexpr (W) {
+    const BagStoreWeights& aw = (wt, ...);
+    wsrc = aw.w[si];
+    wdst = aw.w_out[si];
+  }
   for (int64_t q0 = ((ts + A) >> 1) + (int64_t)blockIdx.y * kThreads + threadIdx.x; q0 <= q_hi; q0 += kStoreTrip * stride) {
     longlong2 v[kStoreTrip];
+    uint2 wv[W ? kStoreTrip : 1];
     int live[kStoreTrip];
 #pragma unroll
     for (int j = 0; j < kStoreTrip; ++j) {
@@ -217,6 +239,17 @@ __global__ __launch_bounds__(kThreads) void bag_store_pack_kernel(BagStoreArgs a
         if (lv & 1) v[j].x = s.values[i0];
         if (lv & 2) v[j].y = s.values[i1];
       }
+      if constexpr (W) {
+        wv[j] = make_uint2(0, 0);
+        if (wsrc) {                                                  // (lv == 0 where a source index left the store: nothing is read)
+          if (lv == 3 && i1 == i0 + 1 && (reinterpret_cast<uintptr_t>(wsrc + i0) & 7) == 0) {
+            wv[j] = *reinterpret_cast<const uint2*>(wsrc + i0);
+          } else {
+            if (lv & 1) wv[j].x = wsrc[i0];
+            if (lv & 2) wv[j].y = wsrc[i1];
+          }
+        }
+      }
       live[j] = lv;
     }
 #pragma unroll
@@ -225,24 +258,24 @@ __global__ __launch_bounds__(kThreads) void bag_store_pack_kernel(BagStoreArgs a
       if (live[j] == 3) *reinterpret_cast<longlong2*>(s.ids_out + p0) = v[j];
       else if (live[j] == 1) s.ids_out[p0] = v[j].x;
       else if (live[j] == 2) s.ids_out[p0 + 1] = v[j].y;
+      if constexpr (W) {
+        if (wdst) {
+          if (live[j] == 3 && (reinterpret_cast<uintptr_t>(wdst + p0) & 7) == 0) *reinterpret_cast<uint2*>(wdst + p0) = wv[j];
+          else {
+            if (live[j] & 1) wdst[p0] = wv[j].x;
+            if (live[j] & 2) wdst[p0 + 1] = wv[j].y;
+          }
+        }
+      }
     }
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int tt_bag_store_tile(void) { return kStoreTile; }
-
-size_t tt_bag_store_gather_workspace_bytes(int64_t B, int32_t n_sides) {
-  const int64_t tiles = tt_cdiv(B > 0 ? B : 1, kStoreTile) * (n_sides > 0 ? n_sides : 1);
-  return sizeof(int64_t) * (size_t)tiles;
-}
-
-int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
-                        const tt_bag_store_side* sides, int32_t n_sides, int64_t B, const int64_t* order, void* workspace,
-                        size_t workspace_bytes, tt_stream stream) {
+// both entries: Side = tt_bag_store_side (ids alone: the kernels and arguments of old) or tt_bag_store_side_w
+template <class Side>
+int bag_store_gather_impl(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes, const Side* sides,
+                          int32_t n_sides, int64_t B, const int64_t* order, void* workspace, size_t workspace_bytes, tt_stream stream) {
+  constexpr bool kW = std::is_same<Side, tt_bag_store_side_w>::value;
   TT_CHECK_ARG(ctx && n >= 0 && n <= TT_MAX_COPIES && (n == 0 || (dst && src && bytes)), "tt_bag_store_gather: bad copy arguments");
   TT_CHECK_ARG(sides && workspace && n_sides >= 1 && n_sides <= TT_MAX_SIDES && B >= 1 && B < ((int64_t)1 << 31),
                "tt_bag_store_gather: bad side arguments");
@@ -255,6 +288,8 @@ int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* co
     return TT_ERR_WORKSPACE;
   }
   BagStoreArgs a{};
+  BagStoreWeights aw{};
+  bool weighted = false;
   int64_t mx = 0, dense_pieces = 0, tiles = 0;
   for (int i = 0; i < n; ++i) {
     TT_CHECK_ARG(bytes[i] >= 0 && (bytes[i] == 0 || (dst[i] && src[i])), "tt_bag_store_gather: segment %d NULL", i);
@@ -266,7 +301,22 @@ int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* co
   }
   bool vec = true;
   for (int i = 0; i < n_sides; ++i) {
-    const tt_bag_store_side& t = sides[i];
+    const Side& t = sides[i];
+    if constexpr (kW) {
+      // weights and weights_out go together; as ids_out, weights_out may be NULL where capacity == 0 (and weights where nnz == 0):
+      // such a side has nowhere to put a weight, or none to move, and runs as a side without weights
+      const float* w = t.weights;
+      float* wo = t.weights_out;
+      TT_CHECK_ARG(wo || !w || t.nnz <= 0 || t.capacity == 0, "tt_bag_store_gather_w: side %d: weights without weights_out (capacity=%lld)", i,
+                   (long long)t.capacity);
+      TT_CHECK_ARG(w || !wo || t.nnz <= 0, "tt_bag_store_gather_w: side %d: weights_out without weights (nnz=%lld)", i, (long long)t.nnz);
+      TT_CHECK_ARG(tt_aligned(w, 4) && tt_aligned(wo, 4), "tt_bag_store_gather_w: side %d weights not 4-byte aligned", i);
+      if (w && wo) {
+        aw.w[i] = reinterpret_cast<const uint32_t*>(w);
+        aw.w_out[i] = reinterpret_cast<uint32_t*>(wo);
+        weighted = true;
+      }
+    }
     TT_CHECK_ARG(t.K >= 1 && t.n_rows >= 1 && t.entity && t.entity_stride >= 1 && t.offsets && t.lengths_out && t.dense_dim >= 0 &&
                  (t.dense_dim == 0 || (t.dense_store && t.dense_out)), "tt_bag_store_gather: side %d NULL / bad shape", i);
     TT_CHECK_ARG(t.nnz >= 0 && t.capacity >= 0 && t.capacity < ((int64_t)1 << 31) && (t.values || t.nnz == 0) && (t.ids_out || t.capacity == 0),
@@ -303,9 +353,34 @@ int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* co
   // launch 2: the tiles' ids, every tile shared by enough workgroups to put two on each CU
   int64_t split = tt_cdiv((int64_t)ctx->num_cus * 2, tiles);
   split = split < 1 ? 1 : (split > kStoreMaxSplit ? kStoreMaxSplit : split);
-  bag_store_pack_kernel<<<dim3((unsigned)tiles, (unsigned)split), kThreads, 0, st>>>(a);
+  const dim3 g2((unsigned)tiles, (unsigned)split);
+  if (weighted) bag_store_pack_kernel<true><<<g2, kThreads, 0, st>>>(a, aw);
+  else bag_store_pack_kernel<false><<<g2, kThreads, 0, st>>>(a);
   TT_LAUNCH_CHECK();
   return TT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tt_bag_store_tile(void) { return kStoreTile; }
+
+size_t tt_bag_store_gather_workspace_bytes(int64_t B, int32_t n_sides) {
+  const int64_t tiles = tt_cdiv(B > 0 ? B : 1, kStoreTile) * (n_sides > 0 ? n_sides : 1);
+  return sizeof(int64_t) * (size_t)tiles;
+}
+
+int tt_bag_store_gather(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
+                        const tt_bag_store_side* sides, int32_t n_sides, int64_t B, const int64_t* order, void* workspace,
+                        size_t workspace_bytes, tt_stream stream) {
+  return bag_store_gather_impl(ctx, n, dst, src, bytes, sides, n_sides, B, order, workspace, workspace_bytes, stream);
+}
+
+int tt_bag_store_gather_w(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
+                          const tt_bag_store_side_w* sides, int32_t n_sides, int64_t B, const int64_t* order, void* workspace,
+                          size_t workspace_bytes, tt_stream stream) {
+  return bag_store_gather_impl(ctx, n, dst, src, bytes, sides, n_sides, B, order, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -48,11 +48,14 @@ class DeviceBagFeatureStore:
     over (entity, key) slots -- offsets int64 [N*K + 1], values int64 [nnz]; the bag of entity e, key k is
     values[offsets[e*K + k] : offsets[e*K + k + 1]].  An entity's K bags are one contiguous run, so a batch's values() in the
     sample-major wire format (kjt.build_bag_kjt: slot b*K + k) is the concatenation of its entities' runs: what
-    ops.bag_store_gather packs without a host round trip.  Ids are stored verbatim; the lookup clamps them as ever."""
+    ops.bag_store_gather packs without a host round trip.  Ids are stored verbatim; the lookup clamps them as ever.
+    Optional per-id weights (an entity's share per industry code, a confidence per licence): `weights` f32 [nnz], entry p the weight
+    of values[p], stored verbatim as the ids are; gather() then returns a KJT with weights().  None: the store holds ids alone."""
 
     def __init__(self, store: Dict, categorical_keys, device):
-        """store: {"dense_projected", "categorical_offsets", "categorical_values"}, host arrays or tensors.  ValueError -- checked
-        here, once -- unless the offsets start at 0, never decrease, end at len(values) and number N*K + 1 for dense's N."""
+        """store: {"dense_projected", "categorical_offsets", "categorical_values"} and optionally "categorical_weights", host arrays
+        or tensors.  ValueError -- checked here, once -- unless the offsets start at 0, never decrease, end at len(values) and number
+        N*K + 1 for dense's N, and the weights (when given) are exactly len(values) entries in one dimension."""
         self.device = torch.device(device)
         self.keys = list(categorical_keys)
         def resident(x, dtype):
@@ -74,17 +77,33 @@ class DeviceBagFeatureStore:
             raise ValueError(f"categorical_offsets end at {int(self.offsets[-1])}, categorical_values holds {self.values.numel()} ids")
         ends = self.offsets[::K] if K else self.offsets.new_zeros(N + 1)
         self.run_lengths = (ends[1:] - ends[:-1]).contiguous()            # int64 [N]: the ids per entity
+        self.weights = None
+        w = store.get("categorical_weights")
+        if w is not None:
+            w = w if torch.is_tensor(w) else torch.as_tensor(np.asarray(w))
+            if w.dim() != 1 or w.numel() != self.values.numel():             # (refused, not reshaped)
+                raise ValueError(f"categorical_weights: shape {list(w.shape)}, categorical_values holds {self.values.numel()} ids "
+                                 f"(one weight per id: [{self.values.numel()}])")
+            self.weights = w.to(device=self.device, dtype=torch.float32).contiguous()
 
     @classmethod
-    def from_bags(cls, dense, bags, categorical_keys, device):
-        """bags[e][k]: the list of ids of entity e, key k"""
+    def from_bags(cls, dense, bags, categorical_keys, device, weights=None):
+        """bags[e][k]: the list of ids of entity e, key k; weights[e][k][i]: the weight of bags[e][k][i] (a nested list shaped exactly
+        like `bags`), or None"""
         K = len(categorical_keys)
         if any(len(row) != K for row in bags):
             raise ValueError(f"every entity needs one id list per key ({K} keys)")
         lengths = np.array([len(bag) for row in bags for bag in row], dtype=np.int64)
         values = np.array([int(i) for row in bags for bag in row for i in bag], dtype=np.int64)
         offsets = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lengths)])
-        return cls({"dense_projected": dense, "categorical_offsets": offsets, "categorical_values": values}, categorical_keys, device)
+        store = {"dense_projected": dense, "categorical_offsets": offsets, "categorical_values": values}
+        if weights is not None:
+            if len(weights) != len(bags) or any(not isinstance(wr, (list, tuple)) or len(wr) != K for wr in weights):
+                raise ValueError(f"weights must list, per entity, one weight list per key ({len(bags)} entities, {K} keys)")
+            if any(not isinstance(wb, (list, tuple)) or len(wb) != len(bag) for row, wr in zip(bags, weights) for bag, wb in zip(row, wr)):
+                raise ValueError("every bag needs one weight per id: a weight list does not have its bag's length")
+            store["categorical_weights"] = np.array([float(w) for wr in weights for wb in wr for w in wb], dtype=np.float32)
+        return cls(store, categorical_keys, device)
 
     @classmethod
     def from_single(cls, store: DeviceFeatureStore):
@@ -100,7 +119,8 @@ class DeviceBagFeatureStore:
         """{"dense", "kjt"} of the entities `entity_idx` (int64 [B]; an index outside the store is clamped into it), the kjt in the
         bag wire format -- DeviceFeatureStore.gather's duck type.  n_ids: the batch's id count, when the caller knows it
         (DevicePairLoader.epoch_bag_ids); without it this call reads ONE word back from the device to size values() -- a host
-        synchronisation per call.  A wrong n_ids writes no ids and raises the device error word (_lib.check_device_errors)."""
+        synchronisation per call.  A wrong n_ids writes no ids and raises the device error word (_lib.check_device_errors).
+        A store with weights: the kjt carries weights() f32 [n_ids], position for position beside the ids, from the same launches."""
         B, K = entity_idx.numel(), len(self.keys)
         idx = entity_idx.to(torch.int64).reshape(-1).contiguous()
         if n_ids is None:
@@ -108,9 +128,15 @@ class DeviceBagFeatureStore:
         dense = torch.empty((B, self.dense.shape[1]), dtype=torch.float32, device=self.device)
         lengths = torch.empty(B * K, dtype=torch.int64, device=self.device)
         ids = torch.empty(int(n_ids), dtype=torch.int64, device=self.device)
+        if self.weights is None:
+            if B:
+                ops.bag_store_gather([], [ops.BagStoreSide(idx, 1, self.dense, self.offsets, self.values, K, dense, lengths, ids, int(n_ids))], B)
+            return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids, lengths)}
+        w = torch.empty(int(n_ids), dtype=torch.float32, device=self.device)
         if B:
-            ops.bag_store_gather([], [ops.BagStoreSide(idx, 1, self.dense, self.offsets, self.values, K, dense, lengths, ids, int(n_ids))], B)
-        return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids, lengths)}
+            ops.bag_store_gather([], [ops.BagStoreSide(idx, 1, self.dense, self.offsets, self.values, K, dense, lengths, ids, int(n_ids),
+                                                       self.weights, w)], B)
+        return {"dense": dense, "kjt": KeyedJaggedTensor(self.keys, ids, lengths, w)}
 
 
 def batch_id_counts(run_lengths: torch.Tensor, entities: torch.Tensor, batch_size: int) -> torch.Tensor:

@@ -711,6 +711,9 @@ class GraphedTrainStep:
         A step captured with bag_capacity: every bag-mode side takes a data_loader.DeviceBagFeatureStore, and tt_bag_store_gather (two
         launches, which also carry the copy segments) fills the side's static dense buffer, its [B*K] lengths and the head of its static
         id buffer; a side that is not in bag mode keeps its DeviceFeatureStore and goes through tt_batch_ingest_store alone.
+        A side captured with per-id weights takes a store that carries them (DeviceBagFeatureStore(... "categorical_weights")): the same
+        two launches fill the head of its static weight buffer beside the ids.  A weighted step on a store without weights, and a
+        weighted store on a side captured without them, are refused before anything is launched.
         bag_ids: {side: this batch's id count} of the bag-mode sides (DevicePairLoader.epoch_bag_ids) -- it goes into the count word
         with the step's scalars, as step(batch)'s; a count above the capacity is refused before anything is launched, one that is not
         the batch's raises the device error word and the captured step runs the side's bags as empty.  Without bag_ids the counts are
@@ -719,9 +722,14 @@ class GraphedTrainStep:
             if row.key in self._terms:
                 raise NotImplementedError(f"{row.noun}: no store-fed hand-over -- a step captured with '{row.key}' takes step(batch)")
         stores = {"notice": notice_store, "company": company_store}
-        if self._bag_w:      # (the bag stores hold ids alone)
-            raise ValueError(f"step_from_store: the step was captured with per-id weights on {sorted(self._bag_w)}, and the bag stores carry "
-                             "none -- a weighted step takes step(batch)")
+        for side in sorted(self._bag_w):      # (the weights come out of the store: its gather fills the static weight buffer)
+            if not isinstance(stores[side], DeviceBagFeatureStore) or getattr(stores[side], "weights", None) is None:
+                raise ValueError(f"step_from_store: the step was captured with per-id weights on {sorted(self._bag_w)}, and the {side} store "
+                                 "carries none -- it takes a DeviceBagFeatureStore with categorical_weights, or step(batch)")
+        for side in self._bag:
+            if side not in self._bag_w and getattr(stores[side], "weights", None) is not None:
+                raise ValueError(f"step_from_store: the {side} store carries per-id weights, but the step was captured without them on that "
+                                 "side (the example batch decides): they would be dropped silently")
         if any(not isinstance(stores[side], DeviceBagFeatureStore) for side in self._bag):      # (a DeviceFeatureStore holds one id per key)
             refuse_bag_mode(self.task, "step_from_store")
         for side, fs in stores.items():
@@ -781,8 +789,9 @@ class GraphedTrainStep:
             if side in self._bag:
                 if len(fs.keys) != len(e.keys):
                     raise ValueError(f"step_from_store: the {side} store holds {len(fs.keys)} keys, the embedder {len(e.keys)}")
+                w = side in self._bag_w                      # (the static weight buffer beside the id buffer: the same capacity)
                 bags.append(ops.BagStoreSide(flat[base + i:], 2, fs.dense, fs.offsets, fs.values, len(e.keys), sd, kjt.lengths(), kjt.values(),
-                                             counts[side]))
+                                             counts[side], fs.weights if w else None, kjt.weights() if w else None))
             else:
                 lookups.append(ops.LookupSide(None, e._key_row_offset, e._key_vocab, None, len(e.keys)))
                 plains.append(ops.StoreSide(flat[base + i:], 2, fs.dense, fs.categorical, sd, kjt.values()))

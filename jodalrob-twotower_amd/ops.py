@@ -1723,14 +1723,39 @@ class BagStoreSide:
     lengths_out: torch.Tensor     # int64 [B*K]
     ids_out: torch.Tensor         # int64 [capacity]: the run total fills its head, the rest keeps what it held
     expect: int = -1              # the id count the host believes, or -1
+    weights: Optional[torch.Tensor] = None        # f32 [nnz]: one weight per entry of `values` (None: the side moves ids alone)
+    weights_out: Optional[torch.Tensor] = None    # f32 [capacity]: position for position beside ids_out
+
+
+def _check_bag_store_weights(i: int, t: BagStoreSide, dev) -> None:
+    """ValueError unless side i's weights / weights_out are both absent, or both contiguous f32 on `dev` with one entry per id"""
+    if (t.weights is None) != (t.weights_out is None):
+        raise ValueError(f"bag_store_gather: side {i}: weights and weights_out go together, "
+                         f"{'weights_out' if t.weights is None else 'weights'} alone was given")
+    if t.weights is None:
+        return
+    for name, x in (("weights", t.weights), ("weights_out", t.weights_out)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"bag_store_gather: side {i}: {name} must be a contiguous 1-D float32 tensor on {dev}")
+    if t.weights.numel() != t.values.numel():
+        raise ValueError(f"bag_store_gather: side {i}: {t.weights.numel()} weights for {t.values.numel()} ids of the store")
+    if t.weights_out.numel() != t.ids_out.numel():
+        raise ValueError(f"bag_store_gather: side {i}: weights_out holds {t.weights_out.numel()} entries, ids_out {t.ids_out.numel()}")
 
 
 def bag_store_gather(pairs, sides: Sequence[BagStoreSide], B: int, order: Optional[torch.Tensor] = None, order_offset: int = 0):
     """tt_bag_store_gather: the batch `order[order_offset : order_offset + B]` of the pair list gathered out of device-resident bag
     stores into the sample-major bag wire format (+ the copy segments `pairs`), two launches and no host round trip.  A side whose
-    ids do not fit ids_out, or do not number `expect`, gets no ids and raises the device error word (_lib.check_device_errors)."""
+    ids do not fit ids_out, or do not number `expect`, gets no ids and raises the device error word (_lib.check_device_errors).
+    A side with `weights` also gets weights_out[p] = the weight of the id at ids_out[p], bit for bit, from the same two launches
+    (tt_bag_store_gather_w; a refused side gets neither); without any such side this is the unweighted entry with its arguments."""
     dev = sides[0].dense_out.device
-    arr = (L.BagStoreSide * len(sides))()
+    weighted = False
+    for i, t in enumerate(sides):
+        if t.weights is not None or t.weights_out is not None:
+            _check_bag_store_weights(i, t, dev)
+            weighted = True
+    arr = ((L.BagStoreSideW if weighted else L.BagStoreSide) * len(sides))()
     for i, t in enumerate(sides):
         if t.entity.dtype != torch.int64 or t.entity.dim() != 1 or t.entity_stride < 1 or t.entity.device != dev:
             raise ValueError(f"bag_store_gather: side {i}: entity must be a 1-D int64 view on {dev}")
@@ -1746,6 +1771,11 @@ def bag_store_gather(pairs, sides: Sequence[BagStoreSide], B: int, order: Option
                 t.lengths_out.numel() != B * t.K or t.lengths_out.dtype != torch.int64 or not t.lengths_out.is_contiguous() or \
                 t.ids_out.dim() != 1 or t.ids_out.dtype != torch.int64 or not t.ids_out.is_contiguous():
             raise ValueError(f"bag_store_gather: side {i}: outputs must be contiguous f32 [{B}, {dd}], int64 [{B * t.K}] and a 1-D int64 id buffer")
+        if weighted:
+            arr[i] = L.BagStoreSideW(L.ptr(t.entity), t.entity_stride, L.ptr(t.dense_store), L.ptr(t.offsets), L.ptr(t.values), L.ptr(t.dense_out),
+                                     L.ptr(t.lengths_out), L.ptr(t.ids_out), t.values.numel(), t.ids_out.numel(), int(t.expect), dd,
+                                     min(int(N), 2 ** 31 - 1), t.K, 0, L.ptr(t.weights), L.ptr(t.weights_out))
+            continue
         arr[i] = L.BagStoreSide(L.ptr(t.entity), t.entity_stride, L.ptr(t.dense_store), L.ptr(t.offsets), L.ptr(t.values), L.ptr(t.dense_out),
                                 L.ptr(t.lengths_out), L.ptr(t.ids_out), t.values.numel(), t.ids_out.numel(), int(t.expect), dd,
                                 min(int(N), 2 ** 31 - 1), t.K, 0)
@@ -1758,6 +1788,11 @@ def bag_store_gather(pairs, sides: Sequence[BagStoreSide], B: int, order: Option
         order_ptr = L.vp(0)
     lib = L.load()
     ws = L.workspace(dev, lib.tt_bag_store_gather_workspace_bytes(B, len(sides)))
+    if weighted:
+        with _timed("tt_bag_store_gather_w"):
+            L.check(lib.tt_bag_store_gather_w(L.ctx(dev), n, dst, src, nb, arr, len(sides), B, order_ptr, L.ptr(ws), ws.numel(), L.stream(dev)),
+                    "tt_bag_store_gather_w")
+        return
     with _timed("tt_bag_store_gather"):
         L.check(lib.tt_bag_store_gather(L.ctx(dev), n, dst, src, nb, arr, len(sides), B, order_ptr, L.ptr(ws), ws.numel(), L.stream(dev)),
                 "tt_bag_store_gather")

@@ -108,17 +108,21 @@ def ragged_bags(kjt: KeyedJaggedTensor, vocabs: Sequence[int], bag_keys, mean_le
     return KeyedJaggedTensor(keys, values, lengths, w)
 
 
-def bag_store(store, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0):
+def bag_store(store, vocabs: Sequence[int], bag_keys, mean_length: float = 4.0, seed: int = 0, weights=None):
     """A data_loader.DeviceBagFeatureStore over the entities of the plain `store` (a DeviceFeatureStore), its bags drawn ONCE: the
     keys named in `bag_keys` get a Poisson(mean_length) number of ids per entity (empty bags included), the first one the entity's own
     id, the others ~ U[0, V_k); the other keys keep their one id (ragged_bags over the whole store, seeded).  Every batch gathered
-    from the result -- for training, evaluation or a catalogue -- sees the same bags of an entity."""
+    from the result -- for training, evaluation or a catalogue -- sees the same bags of an entity.
+    weights: None, or "uniform" -- the store also keeps one weight per id (ragged_bags(weights="uniform"): drawn behind the ids, so the
+    ids are those of the unweighted store of the same seed)."""
     from .data_loader import DeviceBagFeatureStore
-    kjt = ragged_bags(KeyedJaggedTensor(list(store.keys), store.categorical.reshape(-1)), vocabs, bag_keys, mean_length, seed)
+    kjt = ragged_bags(KeyedJaggedTensor(list(store.keys), store.categorical.reshape(-1)), vocabs, bag_keys, mean_length, seed, weights)
     offsets = torch.zeros(kjt.lengths().numel() + 1, dtype=torch.int64, device=store.device)
     torch.cumsum(kjt.lengths(), 0, out=offsets[1:])
-    return DeviceBagFeatureStore({"dense_projected": store.dense, "categorical_offsets": offsets, "categorical_values": kjt.values()},
-                                 store.keys, store.device)
+    d = {"dense_projected": store.dense, "categorical_offsets": offsets, "categorical_values": kjt.values()}
+    if kjt.weights_or_none() is not None:
+        d["categorical_weights"] = kjt.weights()
+    return DeviceBagFeatureStore(d, store.keys, store.device)
 
 
 class SyntheticSource:

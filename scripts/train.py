@@ -157,6 +157,10 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="seed torch's generators (weights, dropout) before the model is built")
     ap.add_argument("--dropout-rate", type=float, default=0.1, help="the towers' dropout rate (reference: 0.1)")
     ap.add_argument("--log-interval", type=int, default=20, help="steps between the loop's progress lines (reference: 20)")
+    ap.add_argument("--pool-store-weights", action="store_true",
+                    help="with --pool ... --pool-store: the bag stores also keep one weight per id (U[0.5, 1.5), a bag's first id "
+                         "weighing 1), drawn once with the bags -- training (also --fast: the store-fed hand-over moves the weights "
+                         "with the ids) and evaluation read them")
     a = ap.parse_args()
     pooling = None
     if a.pool_store and not a.pool:
@@ -164,7 +168,10 @@ def main():
     if a.pool_weights and not a.pool:
         ap.error("--pool-weights needs --pool")
     if a.pool_weights and a.pool_store:
-        ap.error("--pool-weights: not with --pool-store -- the device-resident bag stores hold ids alone (weighted stores are not built yet)")
+        ap.error("--pool-weights: not with --pool-store -- the device-resident bag stores hold ids alone (weighted stores are not built yet)"
+                 "; --pool-store-weights draws per-entity weights into the stores")
+    if a.pool_store_weights and not a.pool_store:
+        ap.error("--pool-store-weights needs --pool ... --pool-store")
     if a.pool_store and a.fast and (a.extra_negatives or a.mask_known):
         ap.error("--pool-store --fast: no store-fed hand-over with --extra-negatives or --mask-known")
     if a.pool:
@@ -223,7 +230,8 @@ def main():
                                                                test_split=config["test_split"], shuffle_seed=config["shuffle_seed"],
                                                                test_mode=True, pair_limit=config["pair_limit"], device=device)
     if a.pool_store:                                     # the towers that pool read per-entity bags, drawn once; both loaders share them
-        bag_stores = [synthetic.bag_store(st, real[side]["vocab_sizes"], pooling, a.pool_length, seed=config["shuffle_seed"] + i)
+        bag_stores = [synthetic.bag_store(st, real[side]["vocab_sizes"], pooling, a.pool_length, seed=config["shuffle_seed"] + i,
+                                          weights="uniform" if a.pool_store_weights else None)
                       if any(k in pooling for k in st.keys) else st
                       for i, (side, st) in enumerate((("notice", train_loader.notice), ("company", train_loader.company)))]
         for ld in (train_loader, test_loader):

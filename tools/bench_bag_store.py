@@ -15,7 +15,11 @@ lengths 1 / 4 / 16.  Per mean length, in THREE fresh processes (run one after th
 
 Times: device events around --steps steps (every shape warmed up first), per step / per call.  The parent process collects the
 children's lines, prints a summary per mean length -- (b) over the prebuilt floor, (b) against the FASTEST of the three eager runs,
-and the run-to-run spread of (b) -- and writes everything to --out (default profiles/bag_store_bench.json)."""
+and the run-to-run spread of (b) -- and writes everything to --out (default profiles/bag_store_bench.json).
+
+--weighted: the stores also keep one f32 weight per id (synthetic.bag_store(weights="uniform")): (a) is tt_bag_store_gather_w moving ids
+and weights (12 bytes per id each way instead of 8), (b) the store-fed step of a step captured with weights, (c) the weighted captured
+and eager steps on prebuilt weighted batches.  Default --out: profiles/bag_store_weights_bench.json."""
 import argparse
 import contextlib
 import io
@@ -43,12 +47,15 @@ ap.add_argument("--batches", type=int, default=8, help="batches the steps rotate
 ap.add_argument("--iters", type=int, default=200, help="calls of the gather alone")
 ap.add_argument("--processes", type=int, default=3)
 ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
-ap.add_argument("--out", default=str(ROOT / "profiles" / "bag_store_bench.json"))
+ap.add_argument("--weighted", action="store_true", help="stores with per-id weights: the weighted gather and the weighted steps")
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+if a.out is None:
+    a.out = str(ROOT / "profiles" / ("bag_store_weights_bench.json" if a.weighted else "bag_store_bench.json"))
 
 
-def gather_bytes(B, sides):
-    """bytes tt_bag_store_gather must move for one batch; sides: [(Din, K, ids of the batch)]"""
+def gather_bytes(B, sides, weighted=False):
+    """bytes tt_bag_store_gather(_w) must move for one batch; sides: [(Din, K, ids of the batch)]"""
     total = 0
     for din, K, n in sides:
         total += 8 * B                      # the pair list's entity indices
@@ -56,6 +63,7 @@ def gather_bytes(B, sides):
         total += 8 * B * (K + 1)            # a sample's K + 1 offsets
         total += 8 * B * K                  # lengths out
         total += 2 * 8 * n                  # ids, in and out
+        total += 2 * 4 * n if weighted else 0      # their weights, in and out
     return total
 
 
@@ -110,27 +118,29 @@ def child():
     P = a.batches * B
     pairs = torch.randint(0, N, (P, 2), generator=g, device=dev).cpu().numpy()
     for mean in a.lengths:
-        stores = {s: synthetic.bag_store(plain[s], vocabs[s], pooled[s], mean, seed=7 + i) for i, s in enumerate(keys)}
+        stores = {s: synthetic.bag_store(plain[s], vocabs[s], pooled[s], mean, seed=7 + i, **({"weights": "uniform"} if a.weighted else {}))
+                  for i, s in enumerate(keys)}
         loader = DevicePairLoader(stores["notice"], stores["company"], pairs, B, shuffle=True, seed=5)
         order = loader.epoch_order()
         counts = loader.epoch_bag_ids(order)
         ids = [{s: int(counts[s][k]) for s in keys} for k in range(a.batches)]
         caps = {s: max(math.ceil(a.factor * float(counts[s].mean())), int(counts[s].max())) for s in keys}
         prebuilt = [loader.batch(order, k * B, bag_ids=counts) for k in range(a.batches)]
-        r = {"process": a.child, "mean_bag_length": mean, "B": B, "E": E, "pooled_keys_per_tower": a.pool_keys, "rows_per_tower": a.rows,
+        r = {"process": a.child, "weighted": a.weighted, "mean_bag_length": mean, "B": B, "E": E, "pooled_keys_per_tower": a.pool_keys, "rows_per_tower": a.rows,
              "entities": N, "ids_per_batch": {s: float(counts[s].mean()) for s in keys}, "capacity": caps, "steps": a.steps, "rounds": a.rounds}
         # (a) the gather alone, into buffers of the step's capacity
         bufs = {s: (torch.empty((B, din[s]), device=dev), torch.empty(B * len(keys[s]), dtype=torch.int64, device=dev),
                     torch.empty(caps[s], dtype=torch.int64, device=dev)) for s in keys}
         flat = loader.pairs.view(-1)
+        wargs = {s: (stores[s].weights, torch.empty(caps[s], dtype=torch.float32, device=dev)) if a.weighted else () for s in keys}
 
         def gather(i):
             k = i % a.batches
-            ops.bag_store_gather([], [ops.BagStoreSide(flat[j:], 2, stores[s].dense, stores[s].offsets, stores[s].values, len(keys[s]), *bufs[s], ids[k][s])
-                                      for j, s in enumerate(keys)], B, order, k * B)
+            ops.bag_store_gather([], [ops.BagStoreSide(flat[j:], 2, stores[s].dense, stores[s].offsets, stores[s].values, len(keys[s]), *bufs[s], ids[k][s],
+                                                       *wargs[s]) for j, s in enumerate(keys)], B, order, k * B)
         events(gather, 2 * a.batches)
         r["gather_us"] = round(events(gather, a.iters) * 1e3, 2)
-        r["gather_bytes"] = int(np.mean([gather_bytes(B, [(din[s], len(keys[s]), ids[k][s]) for s in keys]) for k in range(a.batches)]))
+        r["gather_bytes"] = int(np.mean([gather_bytes(B, [(din[s], len(keys[s]), ids[k][s]) for s in keys], a.weighted) for k in range(a.batches)]))
         r["gather_GBps"] = round(r["gather_bytes"] / (r["gather_us"] * 1e-6) / 1e9, 1)
         # (b), (c): three tasks on the same weights
         (tb, ob), (tc, oc), (te, oe) = make_task(), make_task(), make_task()
@@ -163,7 +173,7 @@ def child():
         _lib.check_device_errors(dev)
         gb.close()
         gc.close()
-        del tb, ob, tc, oc, te, oe, gb, gc, stores, loader, prebuilt, bufs
+        del tb, ob, tc, oc, te, oe, gb, gc, stores, loader, prebuilt, bufs, wargs
         print("RESULT " + json.dumps(r), flush=True)
 
 
@@ -183,7 +193,7 @@ def parent():
     for mean in a.lengths:
         runs = [r for r in lines if r["mean_bag_length"] == mean]
         b, c, e = [r["store_fed_ms"] for r in runs], [r["prebuilt_ms"] for r in runs], [r["eager_ms"] for r in runs]
-        s = {"mean_bag_length": mean, "store_fed_ms": b, "prebuilt_ms": c, "eager_ms": e, "gather_us": [r["gather_us"] for r in runs],
+        s = {"mean_bag_length": mean, "weighted": a.weighted, "store_fed_ms": b, "prebuilt_ms": c, "eager_ms": e, "gather_us": [r["gather_us"] for r in runs],
              "gather_GBps": [r["gather_GBps"] for r in runs], "store_fed_over_prebuilt": round(sorted(b)[len(b) // 2] / sorted(c)[len(c) // 2], 3),
              "store_fed_spread_ms": round(max(b) - min(b), 4), "fastest_eager_ms": min(e), "slowest_store_fed_ms": max(b),
              "eager_minus_store_fed_ms": round(min(e) - max(b), 4), "store_fed_below_fastest_eager": max(b) < min(e)}
