@@ -1235,8 +1235,8 @@ int tt_dedup_plan_pad(tt_ctx* ctx, const int32_t* rows, int64_t M, int64_t table
  *   sum:  w_p0 * row_p0 + w_p1 * row_p1 + ...
  *   mean: that sum / L -- the divisor is the NUMBER of ids, as in the unweighted mean, not the sum of the weights.  A weighted
  *         average is sum pooling over weights the caller has normalised.
- * An empty bag pools to zeros.  Weights are data, used verbatim: negative, zero and non-finite values are not special-cased, and no
- * gradient flows to them.
+ * An empty bag pools to zeros.  Weights are data, used verbatim: negative, zero and non-finite values are not special-cased.  These
+ * entries form no gradient for them; tt_embed_bag_weight_grad (below) does.
  *
  * Arithmetic (f32): a bag's first position is one multiply, acc = w * x; every later one is one fused multiply-add,
  * acc = fma(w, x, acc), in ascending position order; the mean divides as the unweighted entry does (acc / (float)L, only when
@@ -1343,6 +1343,52 @@ typedef struct tt_bag_store_side_w {
 int tt_bag_store_gather_w(tt_ctx* ctx, int32_t n, void* const* dst, const void* const* src, const int64_t* bytes,
                           const tt_bag_store_side_w* sides, int32_t n_sides, int64_t B, const int64_t* order /* [B] or NULL */,
                           void* workspace, size_t workspace_bytes, tt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gradients FOR the per-id weights of a weighted bag (torch.nn.EmbeddingBag(per_sample_weights=) differentiates with respect
+ * to them), and learned position weights built on them (torchrec's PositionWeightedModule: one weight per bag position).
+ *
+ * tt_embed_bag_weight_grad, ONE launch over the positions of a bag plan (rows / bag_of as tt_embed_bag_fwd[_cap][_w] wrote them,
+ * inv_len per slot or NULL: what tt_embed_bag_grad_bwd takes).  srcs[i] is side i's source as in tt_embed_bag_grad_bwd (f32 or
+ * bf16, all requested sides alike, row stride ld); side_nnz[i] the side's positions (its capacity in the capacity form), the sides
+ * lying behind one another in rows / bag_of; g_out a HOST array of n_sides DEVICE pointers, each f32 [side_nnz[i]], laid out like
+ * the _w entries' `weights`.  A side whose pointer is NULL is skipped: nothing of it is read or written, its source included.
+ * For position P of a requested side, slot = bag_of[P]:
+ *   slot >= 0:  g[p] = c * (d[0]*x[0] + ... + d[E-1]*x[E-1]),  x = table row rows[P], d = the E columns of the slot's source row
+ *               (bf16 widened exactly), c = inv_len[slot] when inv_len is given, else 1.  The forward weight is NOT a factor.
+ *   slot <  0:  g[p] = 0.0f, and nothing is read through rows[P] (trailing ids, refused offsets, the capacity form's pads -- the
+ *               pad row lies one past the table).  A slot outside the side or a row outside the table is treated the same way.
+ * Arithmetic (f32): each of the E/4 lanes of a position forms d0*x0, then three fused multiply-adds over its 16-byte piece; the
+ * lanes' partial sums are added by a fixed xor tree over the lane group (the power of two >= E/4), then one product with c.  The
+ * order depends on E alone: two runs give equal bits.  No atomics, no workspace.  E % 4 == 0 and 4 <= E <= 256, the table 16-byte
+ * and the sources 4-element aligned (TT_ERR_UNSUPPORTED otherwise), as the bag entries.
+ *
+ * Position weights: param is a flat f32 [n_param] vector; key k of a side reads param[pw_offset[k] .. pw_offset[k] + pw_len[k]),
+ * pw_offset[k] = -1 for a key without position weights (pw_offset / pw_len: int32 [K] on the device).
+ * tt_bag_position_weights_fwd: for position j of bag (b, k) (offsets int64 [B*K + 1], as tt_embed_bag_fwd reads them)
+ *   w[p] = param[pw_offset[k] + min(j, pw_len[k] - 1)]   -- a 32-bit copy; positions at or beyond pw_len share the LAST weight
+ *   w[p] = 1.0f for a key without position weights and for every position no bag covers ([offsets[B*K], nnz), refused pairs).
+ * tt_bag_position_weights_bwd: d_param[e] = the sum of w[p] (here: the per-id gradient, the field `w` read instead of written)
+ * over all positions of all sides that read element e, 0 for an element nobody reads.  One workgroup per element, threads striding
+ * over the samples and adding their positions in ascending order, then a fixed tree: no atomics, and launch geometry and
+ * order depend on the shapes alone -- two runs give equal bits.  A side with w == NULL contributes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int tt_embed_bag_weight_grad(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_grad_src* srcs, int32_t n_sides,
+                             int64_t B, const int32_t* rows, const int32_t* bag_of, const float* inv_len, const int64_t* side_nnz,
+                             float* const* g_out, tt_stream stream);
+typedef struct tt_bag_pw_side {
+  const int64_t* offsets;    /* [B*K + 1] */
+  const int32_t* pw_offset;  /* [K]: first element of key k in param, or -1 */
+  const int32_t* pw_len;     /* [K]: max_len of key k (>= 1 where pw_offset >= 0) */
+  float* w;                  /* [nnz]: fwd writes the weights; bwd reads the per-id gradient */
+  int64_t nnz;
+  int32_t K;
+  int32_t reserved;
+} tt_bag_pw_side;
+int tt_bag_position_weights_fwd(tt_ctx* ctx, const float* param, int64_t n_param, const tt_bag_pw_side* sides, int32_t n_sides,
+                                int64_t B, tt_stream stream);
+int tt_bag_position_weights_bwd(tt_ctx* ctx, float* d_param, int64_t n_param, const tt_bag_pw_side* sides, int32_t n_sides,
+                                int64_t B, tt_stream stream);
 
 #ifdef __cplusplus
 }

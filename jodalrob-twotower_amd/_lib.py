@@ -46,6 +46,10 @@ class BagLengths(C.Structure):
     _fields_ = [("lengths", vp), ("key_pool", vp), ("count", vp), ("offsets", vp), ("capacity", i64), ("K", i32)]
 
 
+class BagPwSide(C.Structure):              # tt_bag_pw_side
+    _fields_ = [("offsets", vp), ("pw_offset", vp), ("pw_len", vp), ("w", vp), ("nnz", i64), ("K", i32), ("reserved", i32)]
+
+
 class StoreSide(C.Structure):
     _fields_ = [("entity", vp), ("entity_stride", i64), ("dense_store", vp), ("cat_store", vp), ("dense_out", vp), ("ids_out", vp),
                 ("dense_dim", i32), ("n_rows", i32)]
@@ -269,6 +273,9 @@ SIGNATURES = {
     "tt_bag_store_gather_workspace_bytes": (sz, [i64, i32]),
     "tt_bag_store_gather": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSide), i32, i64, vp, vp, sz, vp]),
     "tt_bag_store_gather_w": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(BagStoreSideW), i32, i64, vp, vp, sz, vp]),
+    "tt_embed_bag_weight_grad": (C.c_int, [vp, vp, i64, i32, C.POINTER(GradSrc), i32, i64, vp, vp, vp, C.POINTER(i64), C.POINTER(vp), vp]),
+    "tt_bag_position_weights_fwd": (C.c_int, [vp, vp, i64, C.POINTER(BagPwSide), i32, i64, vp]),
+    "tt_bag_position_weights_bwd": (C.c_int, [vp, vp, i64, C.POINTER(BagPwSide), i32, i64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

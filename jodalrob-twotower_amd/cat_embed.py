@@ -258,6 +258,55 @@ class CategoricalEmbedder(nn.Module):
             self.register_buffer("_key_pool", torch.tensor([ops.POOL_MODES[m] for m in self.pooling], dtype=torch.int32, device=dev),
                                  persistent=False)
         self._bound_version = self.store.version
+        self.position_weights: Optional[Dict[str, int]] = None     # {key: max_len} once add_position_weights has run
+
+    def add_position_weights(self, position_weights: Dict[str, int]) -> "CategoricalEmbedder":
+        """Learned position weights (torchrec's PositionWeightedModule): position j of a bag of `key` weighs
+        position_weight[offset(key) + min(j, max_len - 1)], one f32 nn.Parameter over all the keys named here, initialised to 1.0 --
+        at initialisation the pooled lookup is the unweighted one, bit for bit.  Positions at or beyond max_len SHARE the key's last
+        weight (torchrec would index out of range there).  The parameter is an ordinary non-table parameter: named
+        `position_weight`, in state_dict, trained by the towers' optimiser group.  A key left out weighs 1 at every position.
+        Part of building the embedder -- BaseTower(categorical_position_weights=...) calls it: ValueError without pooling, for keys this
+        embedder does not have (in bag mode every key of the embedder is pooled: no other key can be), for max_len < 1, and when
+        called twice."""
+        if not isinstance(position_weights, dict) or not position_weights:
+            raise ValueError(f"position_weights must be a non-empty {{key: max_len}} dict, got {position_weights!r}")
+        if self.pooling is None:
+            raise ValueError("position_weights need bag mode: this embedder was built without pooling=..., so none of its keys is "
+                             f"pooled (got position weights for {sorted(position_weights)})")
+        if self.position_weights is not None:
+            raise ValueError("this embedder already has position weights")
+        unknown = [k for k in position_weights if k not in self.keys]
+        if unknown:
+            raise ValueError(f"position_weights names keys this embedder does not have: {unknown}")
+        bad = {k: n for k, n in position_weights.items() if isinstance(n, bool) or not isinstance(n, int) or n < 1}
+        if bad:
+            raise ValueError(f"position_weights: max_len must be an integer >= 1, got {bad}")
+        offs, lens, total = [], [], 0
+        for k in self.keys:
+            n = position_weights.get(k)
+            offs.append(-1 if n is None else total)
+            lens.append(0 if n is None else n)
+            total += n or 0
+        dev = self.store.device
+        self.position_weights = {k: position_weights[k] for k in self.keys if k in position_weights}
+        self.position_weight = nn.Parameter(torch.ones(total, dtype=torch.float32, device=dev))
+        self.register_buffer("_pw_offset", torch.tensor(offs, dtype=torch.int32, device=dev), persistent=False)
+        self.register_buffer("_pw_len", torch.tensor(lens, dtype=torch.int32, device=dev), persistent=False)
+        return self
+
+    def bag_weights(self, kjt) -> Optional[torch.Tensor]:
+        """(bag mode) the per-id weights the pooled lookup takes for `kjt`: the KJT's own, or with position weights the parameter
+        expanded over the bags' positions (differentiable: _PosWeightFn) -- never both: one source of weights per embedder."""
+        weights = kjt_weights(kjt)
+        if self.position_weights is None:
+            return weights
+        if weights is not None:
+            raise ValueError("this embedder learns position weights (position_weights=...), and the KJT carries per-id weights of its "
+                             "own: one source of weights per embedder -- hand the ids over without weights")
+        if getattr(kjt, "bag_count", None) is not None:
+            raise ValueError("position weights are not supported on a captured step's static id buffers -- run the eager step")
+        return _PosWeightFn.apply(self, kjt.lengths(), int(kjt.values().numel()), self.position_weight)
 
     @staticmethod
     def _pooling_modes(pooling, keys):
@@ -361,6 +410,7 @@ class CategoricalEmbedder(nn.Module):
             dev = fn(torch.empty(0, device=self._key_vocab.device)).device
             self._key_row_offset, self._key_vocab = self._key_row_offset.to(dev), self._key_vocab.to(dev)
             self._move_key_pool(dev)
+            self._move_position_weights(fn, dev)
             self.store.device = dev
             return self
         # move the fused storage ONCE, then re-point the per-key views (keeps Parameter identity, so
@@ -372,7 +422,19 @@ class CategoricalEmbedder(nn.Module):
         self._key_row_offset = self._key_row_offset.to(self.store.device)
         self._key_vocab = self._key_vocab.to(self.store.device)
         self._move_key_pool(self.store.device)
+        self._move_position_weights(fn, self.store.device)
         return self
+
+    def _move_position_weights(self, fn, dev):
+        """the position-weight parameter is no view of the store: it moves like any module parameter (identity kept)"""
+        if getattr(self, "position_weights", None) is not None:
+            p = self.position_weight
+            if fn(p.data).dtype != torch.float32:
+                raise TypeError("position weights are kept in float32")
+            p.data = fn(p.data)
+            if p.grad is not None:
+                p.grad.data = fn(p.grad.data)
+            self._pw_offset, self._pw_len = self._pw_offset.to(dev), self._pw_len.to(dev)
 
     def _move_key_pool(self, dev):
         """(bag mode) the per-key pooling modes are part of the key directory: they move with it"""
@@ -395,8 +457,10 @@ class CategoricalEmbedder(nn.Module):
                 return {k: torch.zeros(1, E, device=dev) for k in self.keys}
             return torch.zeros(1, K * E, device=dev)
         values = kjt.values()
-        weights = kjt_weights(kjt)
-        if self.bag_mode:
+        weights = self.bag_weights(kjt) if self.bag_mode else kjt_weights(kjt)
+        if self.bag_mode and weights_need_grad(weights):      # a tensor input of the node: its backward returns their gradient
+            cat = _LookupFn.apply(self, (values, kjt.lengths(), _WEIGHTS_FIRST), weights, *self.table_parameters())
+        elif self.bag_mode:
             cat = _LookupFn.apply(self, (values, kjt.lengths(), weights), *self.table_parameters())
         else:
             refuse_weights(weights, "CategoricalEmbedder")
@@ -413,8 +477,12 @@ class _LookupFn(torch.autograd.Function):
     def forward(ctx, emb: CategoricalEmbedder, values, *tables):
         K, E = len(emb.keys), emb.embedding_dim
         ctx.bag = None
+        ctx.w_grad = False
         if emb.bag_mode:                                                  # (values, lengths[, weights]): pooled bags
             values, lengths, weights = values if len(values) == 3 else (*values, None)
+            if weights is _WEIGHTS_FIRST:                                 # differentiable weights: the first tensor input
+                weights, tables, ctx.w_grad = tables[0], tables[1:], True
+                ctx.w_shape, ctx.w_dtype, ctx.w_device = weights.shape, weights.dtype, weights.device
             dev = emb.store.device
             values = values.to(device=dev, dtype=torch.int64).contiguous()
             lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
@@ -442,10 +510,74 @@ class _LookupFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         emb = ctx.emb
+        g_w = ()
         if ctx.plan is not None:
             d_out = d_out.contiguous()
             emb.store.accumulate_grad(ctx.plan, [(d_out, len(emb.keys))], ctx.B, members=[emb], bag=ctx.bag)
-        return (None, None) + (None,) * len(emb.keys)
+        if ctx.w_grad:
+            g = None
+            if ctx.bag is not None and ctx.needs_input_grad[2]:           # from the d_out the table gradient read
+                g = ops.bag_weight_grad(emb.store.weight, ctx.bag, [(d_out, len(emb.keys))], ctx.B, [True])[0]
+                g = g.reshape(ctx.w_shape).to(device=ctx.w_device, dtype=ctx.w_dtype)
+            g_w = (g,)
+        return (None, None) + g_w + (None,) * len(emb.keys)
+
+
+class _PosWeightFn(torch.autograd.Function):
+    """The position-weight parameter expanded over a KJT's bags (tt_bag_position_weights_fwd), and the sum of the per-id gradient
+    back into it (tt_bag_position_weights_bwd)."""
+
+    @staticmethod
+    def forward(ctx, emb: CategoricalEmbedder, lengths, nnz: int, param):
+        K = len(emb.keys)
+        dev = param.device
+        lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+        B = lengths.numel() // max(K, 1)
+        ctx.side = ops.PosWeightSide(lengths[:B * K], emb._pw_offset, emb._pw_len, nnz, K)
+        ctx.B = B
+        ctx.save_for_backward(param)
+        if not (K and B):
+            return torch.ones(nnz, dtype=torch.float32, device=dev)
+        return ops.bag_position_weights(param.detach(), [ctx.side], B)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (param,) = ctx.saved_tensors
+        if not (ctx.side.K and ctx.B):
+            return None, None, None, torch.zeros_like(param)
+        g = g.to(dtype=torch.float32).contiguous()
+        return None, None, None, ops.bag_position_weights_bwd(param.detach(), [ctx.side], ctx.B, [g])
+
+
+_WEIGHTS_FIRST = object()      # _LookupFn: in the place of the weights -- "they are the first tensor input"
+
+
+def weights_need_grad(weights) -> bool:
+    """Per-id weights somebody wants a gradient for (a leaf that requires grad, or the expanded position weights) while autograd
+    records; any other weights are data, handed over exactly as before."""
+    return weights is not None and weights.requires_grad and torch.is_grad_enabled()
+
+
+def position_weighted_embedders(module) -> List[str]:
+    """Names of the embedders under `module` that learn position weights"""
+    if not isinstance(module, nn.Module):
+        return []
+    return [n or "embedder" for n, m in module.named_modules() if isinstance(m, CategoricalEmbedder) and m.position_weights is not None]
+
+
+def refuse_learned_weights(module, who: str, kjts=()) -> None:
+    """The captured steps call this before they capture anything: ValueError when an embedder under `module` learns position weights
+    or one of the example KJTs carries weights that require grad -- the gradient for per-id weights runs in the eager step only."""
+    names = position_weighted_embedders(module)
+    if names:
+        raise ValueError(f"{who} does not support learned position weights (categorical_position_weights / add_position_weights) yet: "
+                         f"{', '.join(names)} would need the per-id weight gradient inside the captured step -- run such a model "
+                         "through the eager step")
+    for kjt in kjts:
+        w = kjt_weights(kjt) if kjt is not None else None
+        if w is not None and w.requires_grad:
+            raise ValueError(f"{who} does not support per-id weights that require grad yet: the captured step forms no gradient for "
+                             "them -- detach them, or run the eager step")
 
 
 def kjt_weights(kjt) -> Optional[torch.Tensor]:

@@ -23,7 +23,7 @@ import torch
 from . import _lib as L
 from . import batch_terms as T
 from . import ops
-from .cat_embed import bag_mode_embedders, kjt_weights, refuse_bag_mode
+from .cat_embed import bag_mode_embedders, kjt_weights, refuse_bag_mode, refuse_learned_weights
 from .config import settings
 from .data_loader import DeviceBagFeatureStore
 from .kjt import KeyedJaggedTensor
@@ -113,6 +113,9 @@ class GraphedTrainStep:
             raise ValueError("cell_capacity: the example batch carries no 'masked_cells'")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
+        # learned position weights and per-id weights that require grad need the per-id weight gradient, which the captured step
+        # does not run yet: refused before anything is built or captured
+        refuse_learned_weights(task, type(self).__name__, [example_batch[side].get("kjt") for side in T.SIDES if side in example_batch])
         # the static id buffers hold B*K ids: no ragged bags in a captured step -- refused here, once, so that step() and
         # step_from_store() of a bag-mode model cannot be reached (and pay no check per step)
         self._bag = self._bag_sides(task, example_batch, bag_capacity)           # {side: capacity} of the bag-mode sides

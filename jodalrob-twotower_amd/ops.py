@@ -314,13 +314,15 @@ class BagPlan(NamedTuple):
     """What embed_bag_lookup leaves for embed_bag_grad: rows / bag_of per position (int32 [nnz]), inv_len per slot (f32, None when
     every key sums), nnz.  The capacity form: nnz is the sides' total capacity and pad_row (= table rows) what `rows` holds where no
     bag covers -- the plan over such rows is bag_dedup_plan's padded one.  pos_w: the weighted form's weight per position (f32
-    [nnz], valid where a bag covers), None when no side carried weights."""
+    [nnz], valid where a bag covers), None when no side carried weights.  side_nnz: the positions of each side (they lie behind one
+    another in rows / bag_of), what bag_weight_grad splits its result by; None on a plan built by hand: one side of nnz positions."""
     rows: torch.Tensor
     bag_of: torch.Tensor
     inv_len: Optional[torch.Tensor]
     nnz: int
     pad_row: Optional[int] = None
     pos_w: Optional[torch.Tensor] = None
+    side_nnz: Optional[tuple] = None
 
 
 def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
@@ -405,7 +407,8 @@ def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int,
                     "tt_embed_bag_fwd_cap")
     if not want_rows:
         return None
-    return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0], None if pos_w is None else pos_w[:cap])
+    return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0], None if pos_w is None else pos_w[:cap],
+                   tuple(s.capacity for s in sides))
 
 
 def bag_dedup_plan(bag: BagPlan, table_rows: int) -> DedupPlan:
@@ -470,7 +473,8 @@ def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want
     if not want_rows:
         return None
     inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
-    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz])
+    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz],
+                   tuple(s.ids.numel() for s in sides))
 
 
 def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int, E: int, mode: int, out: torch.Tensor):
@@ -506,6 +510,101 @@ def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int,
         L.check(lib.tt_embed_bag_grad_bwd(L.ctx(dev), arr, len(srcs), B, E, L.ptr(bag.bag_of), L.ptr(bag.inv_len), L.ptr(plan.sorted_src),
                                           L.ptr(plan.seg_offsets), L.ptr(plan.unique_rows), L.ptr(plan.n_unique), bag.nnz, mode,
                                           L.ptr(out), L.ptr(ws), ws.numel(), L.stream(dev)), "tt_embed_bag_grad_bwd")
+
+
+def bag_weight_grad(table: torch.Tensor, bag: BagPlan, srcs: Sequence[tuple], B: int, want: Sequence[bool]) -> List[Optional[torch.Tensor]]:
+    """tt_embed_bag_weight_grad: the gradient for the per-id weights of a pooled lookup, per side f32 [side positions] (None where
+    `want` is False: nothing of such a side is read or written).  g[p] = c * <d_out[slot of p], table[row of p]>, c the mean
+    weight of the slot (bag.inv_len) or 1; 0.0 where no bag covers p.  bag: the plan of embed_bag_lookup, plain or capacity form;
+    srcs: [(d_out 2-D view [B, K*E], K)] in the sides' order, as embed_bag_grad takes them."""
+    dev, E = table.device, table.shape[1]
+    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2:
+        raise ValueError("the table must be a contiguous float32 [rows, E] tensor")
+    side_nnz = bag.side_nnz if bag.side_nnz is not None else (bag.nnz,)
+    if len(srcs) != len(side_nnz) or len(want) != len(srcs) or sum(side_nnz) != bag.nnz:
+        raise ValueError(f"{len(srcs)} sources and {len(want)} requests for a plan of {len(side_nnz)} sides ({sum(side_nnz)} of {bag.nnz} positions)")
+    for name, t in (("rows", bag.rows), ("bag_of", bag.bag_of)):
+        if t.dtype != torch.int32 or t.numel() != bag.nnz or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"the plan's {name} must be a contiguous int32 tensor of nnz = {bag.nnz} elements on the table's device")
+    if bag.pad_row is not None and bag.pad_row != table.shape[0]:
+        raise ValueError(f"the bags' pad row is {bag.pad_row}, the table has {table.shape[0]} rows")
+    slots = sum(B * K for _, K in srcs)
+    if bag.inv_len is not None and (bag.inv_len.numel() != slots or bag.inv_len.dtype != torch.float32 or bag.inv_len.device != dev):
+        raise ValueError(f"inv_len must hold one float32 per slot ({slots}) on the table's device")
+    arr = (L.GradSrc * len(srcs))()
+    for i, (d, K) in enumerate(srcs):
+        if not want[i]:
+            arr[i] = L.GradSrc(None, 0, K, TT_F32)
+            continue
+        if d.device != dev or d.dim() != 2 or d.shape[0] != B or d.shape[1] != K * E:
+            raise ValueError(f"every source must be a [B, K*E] view on the table's device, got {tuple(d.shape)} for K={K}")
+        assert d.stride(1) == 1
+        arr[i] = L.GradSrc(L.ptr(d), d.stride(0), K, _dt(d))
+    outs = [torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n] if w else None for n, w in zip(side_nnz, want)]
+    if not any(want):
+        return outs
+    nn_arr = (L.i64 * len(srcs))(*[int(n) for n in side_nnz])
+    garr = (L.vp * len(srcs))(*[L.ptr(o) for o in outs])
+    with _timed("tt_embed_bag_weight_grad"):
+        L.check(L.load().tt_embed_bag_weight_grad(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(srcs), B, L.ptr(bag.rows),
+                                                  L.ptr(bag.bag_of), L.ptr(bag.inv_len), nn_arr, garr, L.stream(dev)),
+                "tt_embed_bag_weight_grad")
+    return outs
+
+
+@dataclass
+class PosWeightSide:
+    lengths: torch.Tensor         # int64 [B*K] (device): length of bag (b, k)
+    pw_offset: torch.Tensor       # int32 [K] (device): first element of key k in the parameter, -1: the key has no position weights
+    pw_len: torch.Tensor          # int32 [K] (device): max_len of key k
+    nnz: int                      # ids of the side (sum(lengths), or more: the rest belongs to no bag)
+    K: int
+    offsets: Optional[torch.Tensor] = None   # int64 [B*K + 1]: formed from the lengths on first use, kept for the backward
+
+
+def _pos_weight_sides(param: torch.Tensor, sides: Sequence[PosWeightSide], B: int, bufs: Sequence[Optional[torch.Tensor]]):
+    dev = param.device
+    if param.dtype != torch.float32 or not param.is_contiguous() or param.dim() != 1 or param.numel() < 1:
+        raise ValueError("the position weights must be a contiguous, non-empty float32 vector")
+    arr = (L.BagPwSide * len(sides))()
+    for i, (s, w) in enumerate(zip(sides, bufs)):
+        if s.lengths.dtype != torch.int64 or s.lengths.numel() != B * s.K or s.lengths.device != dev:
+            raise ValueError(f"side {i}: {s.lengths.numel()} int64 bag lengths for B={B}, K={s.K} (on the parameter's device)")
+        for name, t in (("pw_offset", s.pw_offset), ("pw_len", s.pw_len)):
+            if t.dtype != torch.int32 or t.numel() != s.K or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"side {i}: {name} must be a contiguous int32 tensor of {s.K} elements on the parameter's device")
+        if w is not None and (w.dtype != torch.float32 or w.numel() != s.nnz or w.device != dev or not w.is_contiguous()):
+            raise ValueError(f"side {i}: one contiguous float32 per id ({s.nnz}) on the parameter's device")
+        if s.offsets is None:
+            s.offsets = torch.zeros(B * s.K + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(s.lengths.reshape(-1), 0, out=s.offsets[1:])
+        arr[i] = L.BagPwSide(L.ptr(s.offsets), L.ptr(s.pw_offset), L.ptr(s.pw_len), L.ptr(w), s.nnz, s.K, 0)
+    return arr
+
+
+def bag_position_weights(param: torch.Tensor, sides: Sequence[PosWeightSide], B: int) -> List[torch.Tensor]:
+    """tt_bag_position_weights_fwd: per side the f32 weight of every id, w[p] = param[pw_offset[k] + min(j, pw_len[k] - 1)] for
+    position j of bag (b, k) -- a copy, bit for bit; 1.0 for a key without position weights and for ids no bag covers.  Positions
+    at or beyond a key's max_len share its last weight."""
+    dev = param.device
+    outs = [torch.empty(max(s.nnz, 1), dtype=torch.float32, device=dev)[:s.nnz] for s in sides]
+    arr = _pos_weight_sides(param, sides, B, outs)
+    with _timed("tt_bag_position_weights_fwd"):
+        L.check(L.load().tt_bag_position_weights_fwd(L.ctx(dev), L.ptr(param), param.numel(), arr, len(sides), B, L.stream(dev)),
+                "tt_bag_position_weights_fwd")
+    return outs
+
+
+def bag_position_weights_bwd(param: torch.Tensor, sides: Sequence[PosWeightSide], B: int, gs: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """tt_bag_position_weights_bwd: the gradient of `param` (f32, its shape) from the per-id gradients gs (per side f32 [nnz], None: the
+    side contributes nothing): each element sums the ids that read it, in an order the shapes alone fix; 0 where nobody reads."""
+    dev = param.device
+    arr = _pos_weight_sides(param, sides, B, gs)
+    out = torch.empty_like(param)
+    with _timed("tt_bag_position_weights_bwd"):
+        L.check(L.load().tt_bag_position_weights_bwd(L.ctx(dev), L.ptr(out), param.numel(), arr, len(sides), B, L.stream(dev)),
+                "tt_bag_position_weights_bwd")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- Adam

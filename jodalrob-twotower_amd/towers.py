@@ -24,7 +24,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .config import settings
-from .cat_embed import CategoricalEmbedder, EmbeddingStore, kjt_weights, refuse_weights
+from .cat_embed import CategoricalEmbedder, EmbeddingStore, kjt_weights, refuse_weights, weights_need_grad
 
 
 _DEBUG_KEEP = None   # set to a list by debugging tools
@@ -133,7 +133,7 @@ class BaseTower(nn.Module):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 256,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
+                 mlp_dtype: Optional[str] = None, categorical_position_weights=None, categorical_pooling=None):
         super().__init__()
         if tower_hidden_dims is None:
             tower_hidden_dims = [256, 128]
@@ -176,6 +176,8 @@ class BaseTower(nn.Module):
                                                         table_name=table_name, embedding_dim=categorical_embedding_dim,
                                                         device=str(dev), embedding_grad=embedding_grad,
                                                         materialize=materialize_tables, pooling=categorical_pooling)
+        if categorical_position_weights is not None:      # {key: max_len}: learned position weights of the pooled keys (refusals: there)
+            self.categorical_embedder.add_position_weights(categorical_position_weights)
         self.dense_projection = nn.Linear(dense_input_dim, tower_hidden_dims[0])
         self._build_mlp(categorical_embedding_dim, tower_hidden_dims, final_embedding_dim, dropout_rate)
         self._struct_key = None
@@ -250,12 +252,13 @@ class NoticeTower(BaseTower):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 256,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
+                 mlp_dtype: Optional[str] = None, categorical_position_weights=None, categorical_pooling=None):
         super().__init__(categorical_keys=categorical_keys, metadata_path=metadata_path, table_name="notice",
                          categorical_embedding_dim=categorical_embedding_dim, dense_input_dim=dense_input_dim,
                          tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim,
                          dropout_rate=dropout_rate, device=device, embedding_grad=embedding_grad,
-                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
+                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype,
+                         categorical_position_weights=categorical_position_weights, categorical_pooling=categorical_pooling)
 
 
 class CompanyTower(BaseTower):
@@ -263,19 +266,20 @@ class CompanyTower(BaseTower):
                  categorical_embedding_dim: int = 64, dense_input_dim: int = 128,
                  tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128, dropout_rate: float = 0.2,
                  device="cuda:0", embedding_grad: Optional[str] = None, materialize_tables: bool = True,
-                 mlp_dtype: Optional[str] = None, categorical_pooling=None):
+                 mlp_dtype: Optional[str] = None, categorical_position_weights=None, categorical_pooling=None):
         super().__init__(categorical_keys=categorical_keys, metadata_path=metadata_path, table_name="company",
                          categorical_embedding_dim=categorical_embedding_dim, dense_input_dim=dense_input_dim,
                          tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim,
                          dropout_rate=dropout_rate, device=device, embedding_grad=embedding_grad,
-                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
+                         materialize_tables=materialize_tables, mlp_dtype=mlp_dtype,
+                         categorical_position_weights=categorical_position_weights, categorical_pooling=categorical_pooling)
 
 
 # --------------------------------------------------------------------------------------------------
 # one autograd node for >= 1 towers (lookup and table gradient fused across towers that share a store)
 # --------------------------------------------------------------------------------------------------
 def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torch.Tensor]:
-    flat, bag_lengths = [], []
+    flat, bag_lengths, w_inputs = [], [], []
     for tw, inp in zip(towers, inputs):
         dev = tw.categorical_embedder.store.device
         dense = inp["dense"].to(dev)
@@ -287,16 +291,22 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
         # host handed over -- the pair says "capacity form": ops.BagSide)
         # a KJT with weights: (lengths, count or None, weights) -- the pooled lookup's weighted form
         count = getattr(kjt, "bag_count", None)
-        weights = kjt_weights(kjt)
         if not tw.categorical_embedder.bag_mode:
+            weights = kjt_weights(kjt)
             refuse_weights(weights, type(tw).__name__)
+        else:                                     # the KJT's own weights, or the embedder's position weights expanded over its bags
+            weights = tw.categorical_embedder.bag_weights(kjt)
         lengths = kjt.lengths() if tw.categorical_embedder.bag_mode else None
-        if lengths is not None and weights is not None:
+        if lengths is not None and weights_need_grad(weights):
+            # weights somebody differentiates: tensor inputs of the node, behind every tower's own (the entry names which)
+            bag_lengths.append((lengths, count, _WeightInput(len(w_inputs))))
+            w_inputs.append(weights)
+        elif lengths is not None and weights is not None:
             bag_lengths.append((lengths, count, weights))
         else:
             bag_lengths.append(lengths if count is None or lengths is None else (lengths, count))
         flat += [dense, values] + tw.dense_parameters() + tw.categorical_embedder.table_parameters()
-    outs = _TowersFn.apply(tuple(towers), tuple(bag_lengths), *flat)
+    outs = _TowersFn.apply(tuple(towers), tuple(bag_lengths), *flat, *w_inputs)
     outs = list(outs) if isinstance(outs, tuple) else [outs]
     for tw, o in zip(towers, outs):                      # hand the packed images to the score step with the rows they belong to
         if tw._last_packed is not None:
@@ -306,14 +316,24 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
 
 class _Side:
     __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values",
-                 "lengths", "count", "weights")
+                 "lengths", "count", "weights", "w_flat")
+
+
+class _WeightInput:
+    """In the place of a side's weights in _TowersFn's bag_lengths: they are tensor input `index` behind the towers' own inputs,
+    and the backward returns their gradient."""
+    __slots__ = ("index",)
+
+    def __init__(self, index: int):
+        self.index = index
 
 
 class _TowersFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, towers, bag_lengths, *flat):
         """bag_lengths: per tower, the KJT's lengths() for a bag-mode embedder -- or (lengths, count) for the capacity form, or
-        (lengths, count or None, weights) for a KJT with per-id weights -- None for any other (its lengths are not read)"""
+        (lengths, count or None, weights) for a KJT with per-id weights -- None for any other (its lengths are not read).  weights a
+        _WeightInput: differentiable weights, passed behind the towers' inputs in `flat`"""
         if len(bag_lengths) != len(towers):
             raise ValueError(f"{len(towers)} towers but {len(bag_lengths)} bag-length entries")
         sides: List[_Side] = []
@@ -322,6 +342,7 @@ class _TowersFn(torch.autograd.Function):
         spans = []
         lookups: Dict[int, list] = {}
         bag_lookups: Dict[tuple, list] = {}      # (store, batch size) -> [(side, ops.BagSide)]
+        w_base = len(flat) - sum(isinstance(l, tuple) and isinstance(l[-1], _WeightInput) for l in bag_lengths)
         for tw, lengths in zip(towers, bag_lengths):
             emb = tw.categorical_embedder
             nd, nt = len(tw.dense_parameters()), len(emb.table_parameters())
@@ -337,6 +358,11 @@ class _TowersFn(torch.autograd.Function):
             count = weights = None
             if isinstance(lengths, tuple):      # (lengths, count): the capacity form; (lengths, count, weights): weighted bags
                 lengths, count, weights = lengths if len(lengths) == 3 else (*lengths, None)
+            w_ref = weights.index if isinstance(weights, _WeightInput) else None
+            if w_ref is not None:
+                w_ref += w_base
+                weights = flat[w_ref]
+                w_like = (weights.shape, weights.dtype, weights.device)
             if emb.bag_mode:
                 if lengths is None or lengths.numel() != B * K:
                     raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
@@ -352,6 +378,7 @@ class _TowersFn(torch.autograd.Function):
             s.lengths = lengths if emb.bag_mode else None
             s.count = count if emb.bag_mode else None
             s.weights = weights if emb.bag_mode else None
+            s.w_flat = None if w_ref is None else (w_ref, *w_like)      # where the weights' gradient goes, and what it must look like
             s.tower, s.B, s.train = tw, B, tw.training
             s.p_drop = tw.dropout_rate if tw.training else 0.0
             s.seed = 0 if s.p_drop <= 0 else (tw._seed_override if tw._seed_override is not None else
@@ -584,6 +611,13 @@ class _TowersFn(torch.autograd.Function):
                     d = torch.zeros((s.B, K * store.E), dtype=s.tower.dx_dtype, device=store.device)
                 srcs.append((d, K))
             store.accumulate_grad(plan, srcs, plan_sides[0].B, members=[s.tower.categorical_embedder for s in plan_sides], bag=bag)
+            # the gradient for differentiable per-id weights, from the same views; no side asks: no launch
+            want = [s.w_flat is not None and ctx.needs_input_grad[2 + s.w_flat[0]] for s in plan_sides]
+            if any(want):
+                for s, g in zip(plan_sides, ops.bag_weight_grad(store.weight, bag, srcs, plan_sides[0].B, want)):
+                    if g is not None:
+                        at, shape, dtype, wdev = s.w_flat
+                        grads[at] = g.reshape(shape).to(device=wdev, dtype=dtype)
         return (None, None, *grads)
 
 

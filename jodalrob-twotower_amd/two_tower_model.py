@@ -99,24 +99,44 @@ def _tower_pooling(spec, notice_keys, company_keys):
     return pick(notice_keys), pick(company_keys)
 
 
+def _tower_position_weights(spec, notice_keys, company_keys):
+    """create_two_tower_model's categorical_position_weights -> (notice tower's {key: max_len} or None, company tower's)"""
+    if spec is None:
+        return None, None
+    if not isinstance(spec, dict) or not spec:
+        raise ValueError(f"categorical_position_weights must be None or a non-empty dict, got {spec!r}")
+    if set(spec) <= {"notice", "company"}:
+        return spec.get("notice"), spec.get("company")
+    unknown = [k for k in spec if k not in notice_keys and k not in company_keys]
+    if unknown:
+        raise ValueError(f"categorical_position_weights names keys neither tower has: {unknown}")
+    pick = lambda keys: ({k: n for k, n in spec.items() if k in keys} or None)
+    return pick(notice_keys), pick(company_keys)
+
+
 def create_two_tower_model(notice_categorical_keys: List[str], company_categorical_keys: List[str],
                            metadata_path: str = "meta/metadata.csv", categorical_embedding_dim: int = 64,
                            notice_dense_input_dim: int = 256, company_dense_input_dim: int = 128,
                            tower_hidden_dims: Optional[List[int]] = None, final_embedding_dim: int = 128,
                            dropout_rate: float = 0.2, device="cuda:0", embedding_grad: Optional[str] = None,
-                           mlp_dtype: Optional[str] = None, categorical_pooling=None) -> TwoTowerModel:
+                           mlp_dtype: Optional[str] = None, categorical_position_weights=None,
+                           categorical_pooling=None) -> TwoTowerModel:
     """categorical_pooling: None (every bag has length one: lengths are not read), or what puts a tower's embedder in bag mode
     (CategoricalEmbedder(pooling=...)): "sum" / "mean" for both towers, {"notice": spec, "company": spec} per tower (a tower left
-    out stays plain), or a {key: "sum" | "mean"} dict, of which each tower takes the entries that name its keys."""
+    out stays plain), or a {key: "sum" | "mean"} dict, of which each tower takes the entries that name its keys.
+    categorical_position_weights: None, or learned position weights for pooled keys (CategoricalEmbedder.add_position_weights):
+    a {key: max_len} dict, of which each tower takes its keys, or {"notice": {...}, "company": {...}}.  A key of a tower that does
+    not pool, an unknown key or max_len < 1 is a ValueError here."""
     if tower_hidden_dims is None:
         tower_hidden_dims = [256, 128]
     pool_n, pool_c = _tower_pooling(categorical_pooling, notice_categorical_keys, company_categorical_keys)
+    pw_n, pw_c = _tower_position_weights(categorical_position_weights, notice_categorical_keys, company_categorical_keys)
     common = dict(metadata_path=metadata_path, categorical_embedding_dim=categorical_embedding_dim,
                   tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim, dropout_rate=dropout_rate,
                   device=device, embedding_grad=embedding_grad, mlp_dtype=mlp_dtype)
     return TwoTowerModel(
         notice_tower_config=dict(categorical_keys=notice_categorical_keys, dense_input_dim=notice_dense_input_dim,
-                                 categorical_pooling=pool_n, **common),
+                                 categorical_position_weights=pw_n, categorical_pooling=pool_n, **common),
         company_tower_config=dict(categorical_keys=company_categorical_keys, dense_input_dim=company_dense_input_dim,
-                                  categorical_pooling=pool_c, **common),
+                                  categorical_position_weights=pw_c, categorical_pooling=pool_c, **common),
         final_embedding_dim=final_embedding_dim, device=device)

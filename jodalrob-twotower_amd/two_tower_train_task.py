@@ -574,12 +574,13 @@ def create_two_tower_train_task(notice_categorical_keys, company_categorical_key
                                 company_dense_input_dim: int = 128, tower_hidden_dims=None, final_embedding_dim: int = 128,
                                 dropout_rate: float = 0.2, temperature: float = 1.0, loss_type: str = "cross_entropy",
                                 device="cuda:0", embedding_grad=None, score_dtype=None, mlp_dtype=None,
-                                categorical_pooling=None) -> TwoTowerTrainTask:
+                                categorical_position_weights=None, categorical_pooling=None) -> TwoTowerTrainTask:
     model = create_two_tower_model(notice_categorical_keys=notice_categorical_keys,
                                    company_categorical_keys=company_categorical_keys, metadata_path=metadata_path,
                                    categorical_embedding_dim=categorical_embedding_dim,
                                    notice_dense_input_dim=notice_dense_input_dim,
                                    company_dense_input_dim=company_dense_input_dim, tower_hidden_dims=tower_hidden_dims,
                                    final_embedding_dim=final_embedding_dim, dropout_rate=dropout_rate, device=device,
-                                   embedding_grad=embedding_grad, mlp_dtype=mlp_dtype, categorical_pooling=categorical_pooling)
+                                   embedding_grad=embedding_grad, mlp_dtype=mlp_dtype,
+                                   categorical_position_weights=categorical_position_weights, categorical_pooling=categorical_pooling)
     return TwoTowerTrainTask(two_tower_model=model, temperature=temperature, loss_type=loss_type, score_dtype=score_dtype)

@@ -161,8 +161,23 @@ def main():
                     help="with --pool ... --pool-store: the bag stores also keep one weight per id (U[0.5, 1.5), a bag's first id "
                          "weighing 1), drawn once with the bags -- training (also --fast: the store-fed hand-over moves the weights "
                          "with the ids) and evaluation read them")
+    ap.add_argument("--pool-position-weights", type=int, default=None, metavar="MAXLEN",
+                    help="with --pool: every pooled key learns one weight per bag position (MAXLEN of them, initialised to 1; later "
+                         "positions share the last) -- the eager loop only: not with --pool-weights / --pool-store-weights (one source "
+                         "of weights per embedder), --pool-capture or --pool-store --fast")
     a = ap.parse_args()
     pooling = None
+    if a.pool_position_weights is not None:
+        if not a.pool:
+            ap.error("--pool-position-weights needs --pool")
+        if a.pool_position_weights < 1:
+            ap.error("--pool-position-weights MAXLEN must be >= 1")
+        if a.pool_weights or a.pool_store_weights:
+            ap.error("--pool-position-weights: not with --pool-weights / --pool-store-weights -- one source of weights per embedder")
+        if a.pool_capture is not None:
+            ap.error("--pool-position-weights: not with --pool-capture -- the captured step forms no gradient for weights; use the eager loop")
+        if a.pool_store and a.fast:
+            ap.error("--pool-position-weights: not with --pool-store --fast -- the captured step forms no gradient for weights; use the eager loop")
     if a.pool_store and not a.pool:
         ap.error("--pool-store needs --pool")
     if a.pool_weights and not a.pool:
@@ -258,6 +273,8 @@ def main():
                                              final_embedding_dim=config["final_embedding_dim"], dropout_rate=config["dropout_rate"],
                                              temperature=config["temperature"], loss_type=config["loss_type"], device=device,
                                              categorical_pooling=pooling,
+                                             categorical_position_weights=({k: a.pool_position_weights for k in pooling}
+                                                                           if a.pool_position_weights is not None else None),
                                              **(dict(embedding_grad="sparse", score_dtype="bf16", mlp_dtype="bf16") if (a.fast or a.pool_store) else {}))
     optimizer = FusedAdam.for_task(train_task, lr=config["learning_rate"], weight_decay=config["weight_decay"],
                                    table_optimizer=a.table_optimizer, table_lr=a.table_lr)

@@ -13,6 +13,11 @@ ALGORITHMIC: the bytes the operation has to move by its definition over that tim
 (the gradient's d_out rows are re-read once per id of the bag, so its algorithmic bytes count each read).
 --weighted: every id carries an f32 weight ~ U[0.5, 1.5) (tt_embed_bag_fwd_w / tt_embed_bag_grad_bwd_w): the lookup reads nnz * 4 more
 bytes and writes nnz * 4 more (w_out), the gradient reads nnz * 4 more (pos_w); the plain figures beside it are unchanged.
+--weight-grad (implies --weighted): also the gradient FOR the per-id weights (tt_embed_bag_weight_grad, both sides asked for, f32
+sources) beside the weighted lookup on the same batch in the same process -- it gathers the same nnz table rows, which makes the
+lookup its yardstick:
+  weight gradient  read  nnz * (E * 4 + 8)  [rows + rows_out, bag_of]  + nnz * E * 4 [the bag's d_out row, once per id] + nnz * 4 [inv_len];
+                   write nnz * 4
 One JSON line per mean length; --out writes them as a JSON list too."""
 import argparse
 import json
@@ -33,9 +38,11 @@ ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--lengths", type=float, nargs="+", default=[1, 4, 16])
 ap.add_argument("--out-dtype", choices=["f32", "bf16"], default="bf16", help="element type of the lookup output (the bench's x is bf16)")
 ap.add_argument("--weighted", action="store_true", help="per-id weights: the _w entries (lookup and gradient)")
+ap.add_argument("--weight-grad", action="store_true", help="also time tt_embed_bag_weight_grad beside the weighted lookup (implies --weighted)")
 ap.add_argument("--tag", default="", help="copied into every result line (e.g. the run number, or 'parent')")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
+a.weighted = a.weighted or a.weight_grad
 dev = torch.device("cuda:0")
 B, E = a.batch, 32
 odt = torch.bfloat16 if a.out_dtype == "bf16" else torch.float32
@@ -115,6 +122,10 @@ for mean in a.lengths:
          "bag_grad_us": round(t_bgrad, 2), "bag_grad_GBps": gbs(nnz * (E * 4 + 8) + U * E * 4 + wb, t_bgrad),
          "plain_grad_us": round(t_pgrad, 2), "plain_grad_unique_rows": pU, "plain_grad_GBps": gbs(M * (E * 4 + 4) + pU * E * 4, t_pgrad),
          "bag_over_plain_grad_time_at_equal_rows": round(t_bgrad / t_pgrad * M / nnz, 3)}
+    if a.weight_grad:
+        t_wg = timed(["tt_embed_bag_weight_grad"], lambda: ops.bag_weight_grad(table, bag, srcs, B, [True, True]), a.iters)["tt_embed_bag_weight_grad"]
+        r.update({"weight_grad_us": round(t_wg, 2), "weight_grad_GBps": gbs(nnz * (E * 4 + 8) + nnz * E * 4 + nnz * 4 + nnz * 4, t_wg),
+                  "weight_grad_over_weighted_lookup_time": round(t_wg / t_bag, 3)})
     results.append(r)
     print(json.dumps(r), flush=True)
 if a.out:

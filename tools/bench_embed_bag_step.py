@@ -16,7 +16,10 @@ first --pool-keys keys of each tower hold ragged bags of Poisson(mean) ids (mean
 Step times: a host clock around --steps steps that end in a device synchronise, after --warmup steps, in ms per step.  Run it
 several times (fresh processes) for a spread: every run prints one JSON line per mean length; --out appends them to a JSON list.
 --weighted: every id of the bag-mode sides carries an f32 weight (synthetic.ragged_bags(weights="uniform")): the eager and the
-captured step then run the weighted entries (tt_embed_bag_fwd_w / _cap_w / tt_embed_bag_grad_bwd_w), and so do the launch-level figures."""
+captured step then run the weighted entries (tt_embed_bag_fwd_w / _cap_w / tt_embed_bag_grad_bwd_w), and so do the launch-level figures.
+--position-weights MAXLEN: the pooled keys of both towers learn MAXLEN position weights each (categorical_position_weights): the
+eager step then also expands the parameter, forms the per-id weight gradient and reduces it; eager only (the captured step
+refuses such a model), not with --weighted (one source of weights per embedder).  Its yardstick is the eager --weighted step."""
 import argparse
 import contextlib
 import io
@@ -49,9 +52,14 @@ ap.add_argument("--pool", type=int, default=4, help="batches the steps rotate th
 ap.add_argument("--iters", type=int, default=50, help="calls per launch-level figure")
 ap.add_argument("--tag", default="", help="copied into every result line (e.g. the run number, or 'parent')")
 ap.add_argument("--weighted", action="store_true", help="per-id weights on the bag-mode sides: the weighted entries")
+ap.add_argument("--position-weights", type=int, default=None, metavar="MAXLEN", help="learned position weights on the pooled keys (eager only)")
 ap.add_argument("--eager-only", action="store_true", help="the eager step only (a checkout without bag_capacity)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
+if a.position_weights is not None:
+    if a.weighted:
+        ap.error("--position-weights: not with --weighted (one source of weights per embedder)")
+    a.eager_only = True
 dev = torch.device("cuda:0")
 B, E = a.batch, 32
 schema = synthetic.load_real_schema(ROOT / "jodalrob-twotower_amd" / "schema_real.json")
@@ -69,7 +77,9 @@ def make_task(pooling):
                                               notice_dense_input_dim=256, company_dense_input_dim=128,
                                               tower_hidden_dims=[int(h) for h in a.hidden.split(",")], final_embedding_dim=a.final_dim,
                                               dropout_rate=0.1, temperature=1.0, device=dev, embedding_grad="sparse", score_dtype="bf16",
-                                              mlp_dtype="bf16", categorical_pooling=pooling)
+                                              mlp_dtype="bf16", categorical_pooling=pooling,
+                                              **({} if a.position_weights is None or pooling is None else
+                                                 dict(categorical_position_weights={k: a.position_weights for k in pooling})))
     task.train()
     task._pair_check_done = True
     return task, FusedAdam.for_task(task, lr=1e-3, weight_decay=1e-5)
@@ -131,7 +141,7 @@ results = []
 for mean in a.lengths:
     pool = batches(mean, a.pool)
     nnz = {s: max(b[s]["kjt"].values().numel() for b in pool) for s in keys}
-    r = {"tag": a.tag, "weighted": a.weighted, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(len(k) for k in keys.values()), "pooled_keys_per_tower": a.pool_keys,
+    r = {"tag": a.tag, "weighted": a.weighted, "position_weights": a.position_weights, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(len(k) for k in keys.values()), "pooled_keys_per_tower": a.pool_keys,
          "rows_per_tower": a.rows, "nnz": nnz, "steps": a.steps, "plain_captured_launches": plain_launches}
     pooling = {k: "mean" for s in keys for k in pooled[s]}
     task, opt = make_task(pooling)
