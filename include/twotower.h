@@ -1390,6 +1390,35 @@ int tt_bag_position_weights_fwd(tt_ctx* ctx, const float* param, int64_t n_param
 int tt_bag_position_weights_bwd(tt_ctx* ctx, float* d_param, int64_t n_param, const tt_bag_pw_side* sides, int32_t n_sides,
                                 int64_t B, tt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The pooled lookup with a position-weight SOURCE: tt_embed_bag_fwd_w / tt_embed_bag_fwd_cap_w whose sides each take their
+ * weights from one of three places -- srcs[i] (a HOST array of n_sides entries):
+ *   weights != NULL:  a per-id array, exactly the _w entries' weights[i];
+ *   param != NULL:    the position-weight parameter, f32 [n_param] with the key directory pw_offset / pw_len (int32 [K], device):
+ *                     position j of a bag of key k weighs param[clamp(pw_offset[k] + min(j, pw_len[k] - 1), 0 .. n_param - 1)],
+ *                     1.0f where pw_offset[k] < 0 -- the index of tt_bag_position_weights_fwd, formed inside the lookup's launch
+ *                     from the key and the position in the bag it already holds: no expansion launch, no search over the offsets;
+ *   neither:          the side's ids all weigh 1.
+ * Both on one side: TT_ERR_INVALID_ARG.  A param needs pw_offset, pw_len and 1 <= n_param < 2^31 (TT_ERR_INVALID_ARG) and 4-byte
+ * alignment (TT_ERR_UNSUPPORTED).  The sides of one launch may differ in their source.  The value goes through the _w entries'
+ * arithmetic and into w_out (required with rows_out when any side has a source).  out, rows_out, bag_of and w_out at every
+ * position a bag covers are bit for bit what tt_bag_position_weights_fwd followed by tt_embed_bag_fwd[_cap]_w writes; in the
+ * capacity form positions no bag covers keep (pad row, -1).  A call without any param launches the _w kernel.  ONE launch.
+ * (`_posw`, not `_pw`: that suffix names the score entries' pair-weight family.)
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct tt_bag_weight_src {
+  const float* weights;      /* [side.nnz] per-id weights, or NULL */
+  const float* param;        /* [n_param] position-weight parameter, or NULL */
+  const int32_t* pw_offset;  /* [K]: first element of key k in param, or -1 */
+  const int32_t* pw_len;     /* [K]: max_len of key k */
+  int64_t n_param;
+} tt_bag_weight_src;
+int tt_embed_bag_fwd_posw(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                        int64_t B, int32_t* rows_out, int32_t* bag_of, const tt_bag_weight_src* srcs, float* w_out, tt_stream stream);
+int tt_embed_bag_fwd_cap_posw(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides,
+                            int32_t n_sides, int64_t B, int32_t* rows_out, int32_t* bag_of, const tt_bag_weight_src* srcs,
+                            float* w_out, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,10 @@ class BagPwSide(C.Structure):              # tt_bag_pw_side
     _fields_ = [("offsets", vp), ("pw_offset", vp), ("pw_len", vp), ("w", vp), ("nnz", i64), ("K", i32), ("reserved", i32)]
 
 
+class BagWeightSrc(C.Structure):           # tt_bag_weight_src
+    _fields_ = [("weights", vp), ("param", vp), ("pw_offset", vp), ("pw_len", vp), ("n_param", i64)]
+
+
 class StoreSide(C.Structure):
     _fields_ = [("entity", vp), ("entity_stride", i64), ("dense_store", vp), ("cat_store", vp), ("dense_out", vp), ("ids_out", vp),
                 ("dense_dim", i32), ("n_rows", i32)]
@@ -276,6 +280,8 @@ SIGNATURES = {
     "tt_embed_bag_weight_grad": (C.c_int, [vp, vp, i64, i32, C.POINTER(GradSrc), i32, i64, vp, vp, vp, C.POINTER(i64), C.POINTER(vp), vp]),
     "tt_bag_position_weights_fwd": (C.c_int, [vp, vp, i64, C.POINTER(BagPwSide), i32, i64, vp]),
     "tt_bag_position_weights_bwd": (C.c_int, [vp, vp, i64, C.POINTER(BagPwSide), i32, i64, vp]),
+    "tt_embed_bag_fwd_posw": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(BagWeightSrc), vp, vp]),
+    "tt_embed_bag_fwd_cap_posw": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(BagWeightSrc), vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

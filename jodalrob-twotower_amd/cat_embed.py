@@ -297,7 +297,9 @@ class CategoricalEmbedder(nn.Module):
 
     def bag_weights(self, kjt) -> Optional[torch.Tensor]:
         """(bag mode) the per-id weights the pooled lookup takes for `kjt`: the KJT's own, or with position weights the parameter
-        expanded over the bags' positions (differentiable: _PosWeightFn) -- never both: one source of weights per embedder."""
+        expanded over the bags' positions (differentiable: _PosWeightFn) -- never both: one source of weights per embedder.  On a
+        captured step's static id buffers (the KJT carries bag_count) the parameter is not expanded: the answer is an
+        ops.BagPosWeights source, which the towers' pooled lookup reads by position itself (towers.run_towers)."""
         weights = kjt_weights(kjt)
         if self.position_weights is None:
             return weights
@@ -305,7 +307,7 @@ class CategoricalEmbedder(nn.Module):
             raise ValueError("this embedder learns position weights (position_weights=...), and the KJT carries per-id weights of its "
                              "own: one source of weights per embedder -- hand the ids over without weights")
         if getattr(kjt, "bag_count", None) is not None:
-            raise ValueError("position weights are not supported on a captured step's static id buffers -- run the eager step")
+            return ops.BagPosWeights(self.position_weight, self._pw_offset, self._pw_len)
         return _PosWeightFn.apply(self, kjt.lengths(), int(kjt.values().numel()), self.position_weight)
 
     @staticmethod
@@ -332,11 +334,12 @@ class CategoricalEmbedder(nn.Module):
         return self.pooling is not None
 
     def bag_side(self, values: torch.Tensor, lengths: torch.Tensor, out_view: torch.Tensor, count: Optional[torch.Tensor] = None,
-                 weights: Optional[torch.Tensor] = None) -> ops.BagSide:
+                 weights: Optional[torch.Tensor] = None, pos_weights: Optional[ops.BagPosWeights] = None) -> ops.BagSide:
         """count: the device word of a captured step's static id buffer -- `values` is then that buffer, its size the capacity.
-        weights: the KJT's weights (one f32 per id, in the order of `values`), or None: every id weighs 1"""
+        weights: the KJT's weights (one f32 per id, in the order of `values`), or None: every id weighs 1.  pos_weights: the
+        position-weight source in their place (bag_weights on a static KJT)"""
         return ops.BagSide(values, lengths, self._key_row_offset, self._key_vocab, self._key_pool, out_view, len(self.keys),
-                           any(m == "mean" for m in self.pooling), None if count is None else values.numel(), count, weights)
+                           any(m == "mean" for m in self.pooling), None if count is None else values.numel(), count, weights, pos_weights)
 
     # ---- vocab sizes: src/towers/cat_embed.py:50-85 -------------------------------------------
     def _extract_vocab_sizes(self, metadata_path, table_name: str, keys: List[str]) -> Dict[str, int]:
@@ -458,6 +461,9 @@ class CategoricalEmbedder(nn.Module):
             return torch.zeros(1, K * E, device=dev)
         values = kjt.values()
         weights = self.bag_weights(kjt) if self.bag_mode else kjt_weights(kjt)
+        if isinstance(weights, ops.BagPosWeights):
+            raise ValueError("position weights on a captured step's static id buffers run through the towers (GraphedTrainStep("
+                             "learned_weights=True)), not through a stand-alone embedder call")
         if self.bag_mode and weights_need_grad(weights):      # a tensor input of the node: its backward returns their gradient
             cat = _LookupFn.apply(self, (values, kjt.lengths(), _WEIGHTS_FIRST), weights, *self.table_parameters())
         elif self.bag_mode:
@@ -565,11 +571,16 @@ def position_weighted_embedders(module) -> List[str]:
     return [n or "embedder" for n, m in module.named_modules() if isinstance(m, CategoricalEmbedder) and m.position_weights is not None]
 
 
-def refuse_learned_weights(module, who: str, kjts=()) -> None:
+def refuse_learned_weights(module, who: str, kjts=(), learned: bool = False) -> None:
     """The captured steps call this before they capture anything: ValueError when an embedder under `module` learns position weights
-    or one of the example KJTs carries weights that require grad -- the gradient for per-id weights runs in the eager step only."""
+    or one of the example KJTs carries weights that require grad -- the gradient for per-id weights runs in the eager step only.
+    learned: the caller captures position weights (GraphedTrainStep(learned_weights=True)): those pass, and a model without any is
+    refused; weights that require grad stay refused."""
     names = position_weighted_embedders(module)
-    if names:
+    if learned and not names:
+        raise ValueError(f"{who}(learned_weights=True): no embedder of the model learns position weights (categorical_position_weights "
+                         "/ add_position_weights)")
+    if names and not learned:
         raise ValueError(f"{who} does not support learned position weights (categorical_position_weights / add_position_weights) yet: "
                          f"{', '.join(names)} would need the per-id weight gradient inside the captured step -- run such a model "
                          "through the eager step")

@@ -3,6 +3,7 @@
 //   tt_bag_position_weights_*:  w[P] = param[pw_offset[k] + min(j, pw_len[k] - 1)] for position j of bag (b, k), and the sum of g
 //                               over the positions that read each parameter element
 // The kernels of tt_embed_bag.hip are not touched: these read what its forward left (rows, bag_of, inv_len) and write f32 per position.
+#include "tt_bag_pw.h"
 #include "tt_common.h"
 #include "tt_deferred.h"
 #include "tt_embed_slots.h"
@@ -141,14 +142,6 @@ struct PwSet {
   int64_t n_param;
 };
 
-// the parameter element position j of a bag of key k reads, or -1 (the key has none): clamped into the parameter
-__device__ __forceinline__ int64_t pw_index(const PwSideDev& s, uint32_t k, int64_t j, int64_t n_param) {
-  const int32_t off = s.pw_off[k], len = s.pw_len[k];
-  if (off < 0 || len < 1) return -1;
-  int64_t e = (int64_t)off + (j < len - 1 ? j : len - 1);
-  return e < n_param ? e : n_param - 1;
-}
-
 __global__ __launch_bounds__(kThreads) void bag_pw_fwd_kernel(PwSet a, const float* __restrict__ param) {
   for (uint32_t P = blockIdx.x * blockDim.x + threadIdx.x; P < a.total_pos; P += gridDim.x * blockDim.x) {
     int si = 0;
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void bag_pw_fwd_kernel(PwSet a, const flo
     if (lo < S) {
       const int64_t o0 = s.offs[lo], o1 = s.offs[lo + 1];
       if (o0 >= 0 && o0 <= p && p < o1 && o1 <= s.nnz) {
-        const int64_t e = pw_index(s, lo % (uint32_t)s.K, p - o0, a.n_param);
+        const int64_t e = pw_index(s.pw_off, s.pw_len, lo % (uint32_t)s.K, p - o0, a.n_param);      // (tt_bag_pw.h)
         if (e >= 0) w = param[e];
       }
     }

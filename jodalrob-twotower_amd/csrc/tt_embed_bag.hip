@@ -3,7 +3,9 @@
 // the bag's rows with 16-byte loads and adds them in position order.  Backward: the lookup's duplicate-row plan over the
 // POSITIONS' rows (tt_plan.hip, unchanged), reduced like tt_grad.hip's rows -- same chunking, same workspace, the same long-row
 // finish body (tt_grad_ws.h) -- with the contribution of a position read through bag_of (its slot) and weighted for mean pooling.
-// The weighted form (one f32 weight per id: the _w entries) is a template parameter of the same kernels, not a copy of them.
+// The weighted form (one f32 weight per id: the _w entries) is a template parameter of the same kernels, not a copy of them; so is
+// the forward's position-weight source (the _posw entries: a side's weights read out of a learned parameter by position in the bag).
+#include "tt_bag_pw.h"
 #include "tt_common.h"
 #include "tt_deferred.h"
 #include "tt_embed_slots.h"
@@ -50,17 +52,29 @@ constexpr int kBagBatch = 8;
 // the kernel's argument.  The weighted form (W) adds the per-id weights: one f32 per position of a side (NULL: the side's ids all
 // weigh 1) and the place the gradient reads them back from, laid out like rows_out / bag_of.  The unweighted instantiation takes
 // BagSet as it is: its kernel-argument layout, like its code, does not change.
-template <bool W>
+// W is the forward's weight form: 0 none, 1 per-id arrays, 2 per side a per-id array, a position-weight parameter or nothing.
+template <int W>
 struct BagFwdArgs : BagSet {};
 template <>
-struct BagFwdArgs<true> : BagSet {
+struct BagFwdArgs<1> : BagSet {
   const float* w[TT_MAX_SIDES];
   float* w_out;
+};
+// the _posw entries: per side a position-weight parameter (NULL: the side takes w[si], or weighs 1) and its key directory
+template <>
+struct BagFwdArgs<2> : BagFwdArgs<1> {
+  const float* pw_param[TT_MAX_SIDES];
+  const int32_t* pw_off[TT_MAX_SIDES];
+  const int32_t* pw_len[TT_MAX_SIDES];
+  int64_t pw_n[TT_MAX_SIDES];
 };
 
 // W: acc = w * x for a bag's first position, acc = fma(w, x, acc) for every later one.  With every weight 1 these are the bits of
 // the unweighted form (1 * x = x, a -0 included; fma(1, x, acc) = acc + x).
-template <bool W>
+// W == 2: a side with a parameter reads position j of a bag of key k from param[pw_index_at(off[k], len[k], j)] (tt_bag_pw.h), 1
+// for a key without; the value takes the place of the per-id weight in the same chain and in w_out.  The sides of one launch may
+// differ: parameter, per-id array, none.
+template <int W>
 __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, const float* __restrict__ table) {
   const uint32_t LG = a.LG;
   const uint32_t gthread = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,14 +97,36 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
     }
     const int64_t hi = s.vocab[k] - 1, base = s.off[k];
     const float* sw = nullptr;
-    if constexpr (W) sw = a.w[si];
+    if constexpr (W != 0) sw = a.w[si];
+    const float* pp = nullptr;                                 // (W == 2) the side's parameter and this bag's key entry
+    int32_t poff = -1, plen = 0;
+    int64_t pn = 0;
+    if constexpr (W == 2) {
+      pp = a.pw_param[si];
+      if (pp) {
+        poff = a.pw_off[si][k]; plen = a.pw_len[si][k];
+        pn = a.pw_n[si];
+      }
+    }
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t p = o0; p < o1; p += kBagBatch) {
       int64_t id[kBagBatch];
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) id[j] = p + j < o1 ? s.ids[p + j] : 0;
       float wj[kBagBatch];                                     // (W) the trip's weights, loaded next to its ids: no new dependent level
-      if constexpr (W) {
+      if constexpr (W == 2) {
+#pragma unroll
+        for (int j = 0; j < kBagBatch; ++j) {
+          wj[j] = 1.f;
+          if (p + j >= o1) continue;
+          if (pp) {
+            const int64_t e = pw_index_at(poff, plen, p + j - o0, pn);
+            if (e >= 0) wj[j] = pp[e];
+          } else if (sw) {
+            wj[j] = sw[p + j];
+          }
+        }
+      } else if constexpr (W != 0) {
 #pragma unroll
         for (int j = 0; j < kBagBatch; ++j) wj[j] = (sw && p + j < o1) ? sw[p + j] : 1.f;
       }
@@ -104,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
           if (lig == ((uint32_t)j & (LG - 1))) {
             if (a.rows_out) a.rows_out[s.pos_base + (p + j)] = (int32_t)row;
             if (a.bag_of) a.bag_of[s.pos_base + (p + j)] = (int32_t)slot;
-            if constexpr (W) {
+            if constexpr (W != 0) {
               if (a.w_out) a.w_out[s.pos_base + (p + j)] = wj[j];
             }
           }
@@ -114,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) {
         if (p + j >= o1) continue;
-        if constexpr (W) {
+        if constexpr (W != 0) {
           if (p + j == o0) {
             acc.x = __fmul_rn(wj[j], v[j].x); acc.y = __fmul_rn(wj[j], v[j].y);
             acc.z = __fmul_rn(wj[j], v[j].z); acc.w = __fmul_rn(wj[j], v[j].w);
@@ -494,13 +530,14 @@ static int bag_unsupported(const char* who, const char* what) {
 // tt_embed_bag_fwd (cap false) and its capacity form (cap true: nnz is each side's capacity, uncovered positions get table_rows / -1)
 static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
                         int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream, bool cap, bool weighted = false,
-                        const float* const* weights = nullptr, float* w_out = nullptr) {
+                        const float* const* weights = nullptr, float* w_out = nullptr, const tt_bag_weight_src* wsrc = nullptr) {
   TT_CHECK_ARG(ctx && table && sides, "tt_embed_bag_fwd: NULL argument");
   TT_CHECK_ARG(n_sides >= 1 && n_sides <= TT_MAX_SIDES, "tt_embed_bag_fwd: n_sides=%d not in [1,%d]", n_sides, TT_MAX_SIDES);
   TT_CHECK_ARG(B >= 0 && table_rows >= 1 && table_rows <= INT32_MAX, "tt_embed_bag_fwd: bad B=%lld rows=%lld", (long long)B, (long long)table_rows);
   if (E % 4 != 0 || E < 4 || E > 256) return bag_unsupported("tt_embed_bag_fwd", "E must be a multiple of 4 in [4, 256]");
   if (!tt_aligned(table, 16)) return bag_unsupported("tt_embed_bag_fwd", "the table must be 16-byte aligned");
-  BagFwdArgs<true> a{};      // (the unweighted launch passes its BagSet part)
+  BagFwdArgs<2> a{};         // (the per-id launch passes its BagFwdArgs<1> part, the unweighted one its BagSet part)
+  bool any_pw = false;
   a.n = n_sides;
   a.E = E;
   a.C = (uint32_t)(E / 4);
@@ -509,7 +546,21 @@ static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int
   for (int i = 0; i < n_sides; ++i) {
     const tt_bag_side& s = sides[i];
     a.w[i] = weighted && weights ? weights[i] : nullptr;
-    TT_CHECK_ARG(!(rows_out && a.w[i] && !w_out), "tt_embed_bag_fwd_w: rows_out with weights on side %d needs w_out", i);
+    if (wsrc) {                                                // the _posw entries: one source per side, or none
+      const tt_bag_weight_src& ws = wsrc[i];
+      TT_CHECK_ARG(!(ws.weights && ws.param), "tt_embed_bag_fwd_posw: side %d has both per-id weights and a position-weight parameter", i);
+      a.w[i] = ws.weights;
+      if (ws.param) {
+        TT_CHECK_ARG(ws.pw_offset && ws.pw_len, "tt_embed_bag_fwd_posw: side %d has a parameter without pw_offset / pw_len", i);
+        TT_CHECK_ARG(ws.n_param >= 1 && ws.n_param < ((int64_t)1 << 31), "tt_embed_bag_fwd_posw: side %d bad n_param=%lld", i, (long long)ws.n_param);
+        if (!tt_aligned(ws.param, 4) || !tt_aligned(ws.pw_offset, 4) || !tt_aligned(ws.pw_len, 4))
+          return bag_unsupported("tt_embed_bag_fwd_posw", "the parameter and its key directory must be 4-byte aligned");
+        a.pw_param[i] = ws.param; a.pw_off[i] = ws.pw_offset; a.pw_len[i] = ws.pw_len; a.pw_n[i] = ws.n_param;
+        any_pw = true;
+      }
+    }
+    TT_CHECK_ARG(!(rows_out && (a.w[i] || a.pw_param[i]) && !w_out), "%s: rows_out with weights on side %d needs w_out",
+                 wsrc ? "tt_embed_bag_fwd_posw" : "tt_embed_bag_fwd_w", i);
     if (!tt_aligned(a.w[i], 4) || !tt_aligned(w_out, 4)) return bag_unsupported("tt_embed_bag_fwd_w", "weights and w_out must be 4-byte aligned");
     TT_CHECK_ARG(s.K >= 1 && s.nnz >= 0, "tt_embed_bag_fwd: side %d has K=%d nnz=%lld", i, s.K, (long long)s.nnz);
     TT_CHECK_ARG(s.offsets && s.key_row_offset && s.key_vocab && s.key_pool && s.out && (s.ids || s.nnz == 0), "tt_embed_bag_fwd: side %d has NULL pointers", i);
@@ -535,12 +586,14 @@ static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int
   // (capacity form: the grid is sized by the bags and the capacities, never by the live count)
   const int64_t threads = cap && positions > slots * a.LG ? positions : slots * a.LG;
   a.w_out = w_out;
-  if (weighted) {
-    bag_fwd_kernel<true><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  if (any_pw) {
+    bag_fwd_kernel<2><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, table);
+  } else if (weighted) {
+    bag_fwd_kernel<1><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(static_cast<const BagFwdArgs<1>&>(a), table);
   } else {
-    BagFwdArgs<false> u{};
+    BagFwdArgs<0> u{};
     static_cast<BagSet&>(u) = a;
-    bag_fwd_kernel<false><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(u, table);
+    bag_fwd_kernel<0><<<grid_for(ctx, threads), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(u, table);
   }
   TT_LAUNCH_CHECK();
   return TT_OK;
@@ -570,6 +623,20 @@ int tt_embed_bag_fwd_cap_w(tt_ctx* ctx, const float* table, int64_t table_rows, 
   TT_CHECK_ARG(weights, "tt_embed_bag_fwd_cap_w: NULL weights array (a side without weights has a NULL entry)");
   TT_CHECK_ARG(table_rows < INT32_MAX, "tt_embed_bag_fwd_cap_w: no room for the pad row behind %lld rows", (long long)table_rows);
   return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, true, true, weights, w_out);
+}
+
+// a call whose sides all lack a parameter launches the _w kernel (with per-id weights or none: its bits)
+int tt_embed_bag_fwd_posw(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                        int64_t B, int32_t* rows_out, int32_t* bag_of, const tt_bag_weight_src* srcs, float* w_out, tt_stream stream) {
+  TT_CHECK_ARG(srcs, "tt_embed_bag_fwd_posw: NULL weight sources (a side without weights has an all-NULL entry)");
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, false, true, nullptr, w_out, srcs);
+}
+
+int tt_embed_bag_fwd_cap_posw(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
+                            int64_t B, int32_t* rows_out, int32_t* bag_of, const tt_bag_weight_src* srcs, float* w_out, tt_stream stream) {
+  TT_CHECK_ARG(srcs, "tt_embed_bag_fwd_cap_posw: NULL weight sources (a side without weights has an all-NULL entry)");
+  TT_CHECK_ARG(table_rows < INT32_MAX, "tt_embed_bag_fwd_cap_posw: no room for the pad row behind %lld rows", (long long)table_rows);
+  return bag_fwd_impl(ctx, table, table_rows, E, sides, n_sides, B, rows_out, bag_of, stream, true, true, nullptr, w_out, srcs);
 }
 
 size_t tt_bag_prepare_workspace_bytes(const int64_t* side_slots, int32_t n_sides) {

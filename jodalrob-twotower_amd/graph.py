@@ -72,13 +72,14 @@ class GraphedTrainStep:
     _bag_capture = True            # bag_capacity is honoured (the unrolled / segmented steps keep refusing bag mode)
     _bag: Dict[str, int] = {}      # {side: capacity} of the bag-mode sides (none: a plain model)
     _bag_w: frozenset = frozenset()   # the bag-mode sides captured WITH per-id weights (the example KJT carried them)
+    _bag_pw: frozenset = frozenset()  # the bag-mode sides whose embedder learns position weights (learned_weights=True)
     _accepts = frozenset(T.ROWS)   # the batch entries that change the loss (batch_terms.TABLE) an example batch may carry; the
                                    # unrolled / segmented steps take none
 
     def __init__(self, task, optimizer: FusedAdam, example_batch: Dict, return_metrics: bool = True, warmup: int = 3,
                  defer_long: bool = True, defer_slabs: bool = True, defer_riders: bool = True, preserve_state: bool = True,
                  accumulate_metrics: bool = False, metric_sums: Optional[torch.Tensor] = None, fuse_score_tail: bool = True,
-                 cell_capacity: Optional[int] = None, bag_capacity=None):
+                 cell_capacity: Optional[int] = None, bag_capacity=None, learned_weights: bool = False):
         """defer_long / defer_slabs: the long rows' finish rides in the optimiser's launch and the towers' slab reduction in the
         embedding gradient's (both bit-identical to the separate launches; the arguments exist for that comparison).
         fuse_score_tail: the score backward waits for the towers' backward, which launches it with its own first kernel's work in
@@ -95,7 +96,11 @@ class GraphedTrainStep:
         the example's, at least 1024); a later batch with more cells is refused.
         bag_capacity: None -- a bag-mode model (categorical_pooling) is refused; an int, a {"notice": n, "company": n} dict or "auto"
         (four times the example batch's ids, at least 1024) -- the capacity in ids of every bag-mode side's static id buffer: the
-        captured step then runs the pooled lookup's capacity form, a later batch with more ids is refused."""
+        captured step then runs the pooled lookup's capacity form, a later batch with more ids is refused.
+        learned_weights: False -- a model whose embedders learn position weights (categorical_position_weights) is refused; True (with
+        bag_capacity) -- it is captured: the pooled lookup reads the parameter by position, the backward forms its gradient over the
+        capacity and FusedAdam steps it inside the graph.  Per-id data weights on such a side, weights that
+        require grad, and the unrolled / segmented / sharded steps stay refused."""
         # the example batch's entries that change the loss (batch_terms.TABLE): each gets static buffers -- [B] per side (a side the
         # batch does not carry: zeros / its row indices) or one [B]; the extras' M rows with whichever of log_q / entity they carry; an
         # int32 [capacity, 2] buffer of cells and a device count, one more word of the step's scalars -- filled at every hand-over by more
@@ -113,12 +118,21 @@ class GraphedTrainStep:
             raise ValueError("cell_capacity: the example batch carries no 'masked_cells'")
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedTrainStep needs jodalrob_twotower_amd.optim.FusedAdam (device-side hyper-parameters)")
-        # learned position weights and per-id weights that require grad need the per-id weight gradient, which the captured step
-        # does not run yet: refused before anything is built or captured
-        refuse_learned_weights(task, type(self).__name__, [example_batch[side].get("kjt") for side in T.SIDES if side in example_batch])
+        # learned position weights need the per-id weight gradient, which the captured step runs on request alone
+        # (learned_weights=True); per-id weights that require grad it never does: refused before anything is built or captured
+        who = type(self).__name__
+        if learned_weights:
+            if not self._bag_capture or getattr(task, "exchange", None) is not None:
+                raise ValueError(f"{who}(learned_weights=True): learned position weights are captured by GraphedTrainStep on an unsharded "
+                                 "task alone -- the unrolled, segmented and sharded steps refuse them; run the eager step")
+            if bag_capacity is None:
+                raise ValueError(f"{who}(learned_weights=True) needs bag_capacity: position weights belong to pooled keys, and a captured "
+                                 "bag-mode step runs on static id buffers of a fixed capacity")
+        refuse_learned_weights(task, who, [example_batch[side].get("kjt") for side in T.SIDES if side in example_batch],
+                               learned=bool(learned_weights))
         # the static id buffers hold B*K ids: no ragged bags in a captured step -- refused here, once, so that step() and
         # step_from_store() of a bag-mode model cannot be reached (and pay no check per step)
-        self._bag = self._bag_sides(task, example_batch, bag_capacity)           # {side: capacity} of the bag-mode sides
+        self._bag = self._bag_sides(task, example_batch, bag_capacity, bool(learned_weights))    # {side: capacity} of the bag-mode sides
         self.bag_capacity = dict(self._bag) or None
         self.task, self.opt, self.return_metrics = task, optimizer, return_metrics
         self._defer_long, self._defer_slabs, self._defer_riders = bool(defer_long), bool(defer_slabs), bool(defer_riders)
@@ -215,9 +229,9 @@ class GraphedTrainStep:
         # the capture itself ran the host-side bookkeeping of one optimiser step (per captured body) without executing it
         optimizer.advance_steps(-self._steps_per_replay)
 
-    def _bag_sides(self, task, example_batch, bag_capacity) -> Dict[str, int]:
+    def _bag_sides(self, task, example_batch, bag_capacity, learned_weights: bool = False) -> Dict[str, int]:
         """{side: capacity} of the sides whose embedder pools bags, after the refusals (no device work)"""
-        self._bag_n, self._bag_w = {}, frozenset()
+        self._bag_n, self._bag_w, self._bag_pw = {}, frozenset(), frozenset()
         if not bag_mode_embedders(task):
             if bag_capacity is not None:
                 raise ValueError("bag_capacity: the model has no bag-mode embedder (categorical_pooling)")
@@ -235,6 +249,12 @@ class GraphedTrainStep:
             refuse_bag_mode(task, type(self).__name__)
         self._bag_n = dict(sides)                  # ids the static buffer holds now (the count word of the next hand-over)
         self._bag_w = frozenset(side for side in sides if kjt_weights(example_batch[side]["kjt"]) is not None)
+        if learned_weights:
+            self._bag_pw = frozenset(side for side in sides
+                                     if getattr(model, f"{side}_tower").categorical_embedder.position_weights is not None)
+            for side in sorted(self._bag_pw & self._bag_w):
+                raise ValueError(f"{side}: the example batch carries per-id weights, and the side's embedder learns position weights: "
+                                 "one source of weights per embedder -- hand the ids over without weights")
         for side in self._bag_w:
             w, v = kjt_weights(example_batch[side]["kjt"]), example_batch[side]["kjt"].values()
             if w.numel() != v.numel():
@@ -268,6 +288,9 @@ class GraphedTrainStep:
             if kjt.lengths().numel() != st.lengths().numel():
                 raise ValueError(f"{side}: {kjt.lengths().numel()} bag lengths, the captured step holds B*K = {st.lengths().numel()}")
             w = kjt_weights(kjt)
+            if w is not None and side in self._bag_pw:
+                raise ValueError(f"{side}: the batch carries per-id weights, and the side's embedder learns position weights: one source "
+                                 "of weights per embedder -- hand the ids over without weights")
             if (w is not None) != (side in self._bag_w):
                 raise ValueError(f"{side}: the batch carries {'per-id weights' if w is not None else 'no weights'}, the step was captured "
                                  f"{'with' if side in self._bag_w else 'without'} them (the example batch decides)")
@@ -729,6 +752,10 @@ class GraphedTrainStep:
             if not isinstance(stores[side], DeviceBagFeatureStore) or getattr(stores[side], "weights", None) is None:
                 raise ValueError(f"step_from_store: the step was captured with per-id weights on {sorted(self._bag_w)}, and the {side} store "
                                  "carries none -- it takes a DeviceBagFeatureStore with categorical_weights, or step(batch)")
+        for side in sorted(getattr(self, "_bag_pw", ())):
+            if getattr(stores[side], "weights", None) is not None:
+                raise ValueError(f"step_from_store: the {side} store carries per-id weights, and the side's embedder learns position weights: "
+                                 "one source of weights per embedder -- it takes a plain DeviceBagFeatureStore")
         for side in self._bag:
             if side not in self._bag_w and getattr(stores[side], "weights", None) is not None:
                 raise ValueError(f"step_from_store: the {side} store carries per-id weights, but the step was captured without them on that "

@@ -294,6 +294,15 @@ POOL_MODES = {"sum": L.TT_POOL_SUM, "mean": L.TT_POOL_MEAN}
 
 
 @dataclass
+class BagPosWeights:
+    """A pooled side's position-weight SOURCE: the lookup reads position j of a bag of key k from
+    param[pw_offset[k] + min(j, pw_len[k] - 1)] itself (1.0 for a key with pw_offset < 0) instead of taking one weight per id."""
+    param: torch.Tensor           # f32 [n_param] (device), contiguous: the learned parameter
+    pw_offset: torch.Tensor       # int32 [K] (device): first element of key k in param, -1: the key has no position weights
+    pw_len: torch.Tensor          # int32 [K] (device): max_len of key k
+
+
+@dataclass
 class BagSide:
     ids: torch.Tensor             # int64 [nnz]: the bags' ids, concatenated in slot order (slot = b*K + k)
     lengths: torch.Tensor         # int64 [B*K] (device): length of bag (b, k); 0 allowed
@@ -308,6 +317,7 @@ class BagSide:
     count: Optional[torch.Tensor] = None   # (capacity form) int32 [1] on the device: the id count the host handed over, compared
                                            # with sum(lengths) on the device; None: not compared
     weights: Optional[torch.Tensor] = None # f32 [nnz] ([capacity] in the capacity form): one weight per id; None: every id weighs 1
+    pos_weights: Optional[BagPosWeights] = None   # the weights come out of a position-weight parameter; never beside `weights`
 
 
 class BagPlan(NamedTuple):
@@ -315,7 +325,8 @@ class BagPlan(NamedTuple):
     every key sums), nnz.  The capacity form: nnz is the sides' total capacity and pad_row (= table rows) what `rows` holds where no
     bag covers -- the plan over such rows is bag_dedup_plan's padded one.  pos_w: the weighted form's weight per position (f32
     [nnz], valid where a bag covers), None when no side carried weights.  side_nnz: the positions of each side (they lie behind one
-    another in rows / bag_of), what bag_weight_grad splits its result by; None on a plan built by hand: one side of nnz positions."""
+    another in rows / bag_of), what bag_weight_grad splits its result by; None on a plan built by hand: one side of nnz positions.  offsets:
+    (capacity form) per side the int64 [B*K + 1] offsets tt_bag_prepare formed -- what bag_position_weights_bwd walks."""
     rows: torch.Tensor
     bag_of: torch.Tensor
     inv_len: Optional[torch.Tensor]
@@ -323,6 +334,7 @@ class BagPlan(NamedTuple):
     pad_row: Optional[int] = None
     pos_w: Optional[torch.Tensor] = None
     side_nnz: Optional[tuple] = None
+    offsets: Optional[tuple] = None
 
 
 def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
@@ -334,6 +346,17 @@ def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
     if w is not None and (w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev or w.numel() != s.ids.numel()):
         raise ValueError(f"side {i}: bag weights must be a contiguous float32 tensor of ids.numel() = {s.ids.numel()} elements on the "
                          f"table's device, got {w.dtype} x {w.numel()} on {w.device}")
+    pw = s.pos_weights
+    if pw is not None:
+        if w is not None:
+            raise ValueError(f"side {i}: per-id weights and a position-weight source on one side -- one source of weights per side")
+        if pw.param.dtype != torch.float32 or not pw.param.is_contiguous() or pw.param.device != dev or pw.param.dim() != 1 or \
+                pw.param.numel() < 1:
+            raise ValueError(f"side {i}: the position weights must be a contiguous, non-empty float32 vector on the table's device, got "
+                             f"{pw.param.dtype} x {tuple(pw.param.shape)} on {pw.param.device}")
+        for name, t in (("pw_offset", pw.pw_offset), ("pw_len", pw.pw_len)):
+            if t.dtype != torch.int32 or t.numel() != s.K or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"side {i}: {name} must be a contiguous int32 tensor of {s.K} elements on the table's device")
     for name, t, dt, n in (("key_row_offset", s.key_row_offset, torch.int64, s.K), ("key_vocab", s.key_vocab, torch.int64, s.K),
                            ("key_pool", s.key_pool, torch.int32, s.K)):
         if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
@@ -378,6 +401,16 @@ def _bag_weight_args(sides: Sequence[BagSide], positions: int, want_rows: bool, 
     return arr, (torch.empty(max(positions, 1), dtype=torch.float32, device=dev) if want_rows else None)
 
 
+def _bag_source_args(sides: Sequence[BagSide], positions: int, want_rows: bool, dev):
+    """(host array of the sides' weight sources, w_out or None) for the _posw entries"""
+    arr = (L.BagWeightSrc * len(sides))()
+    for i, s in enumerate(sides):
+        pw = s.pos_weights
+        arr[i] = L.BagWeightSrc(L.ptr(s.weights), None, None, None, 0) if pw is None else \
+            L.BagWeightSrc(None, L.ptr(pw.param), L.ptr(pw.pw_offset), L.ptr(pw.pw_len), pw.param.numel())
+    return arr, (torch.empty(max(positions, 1), dtype=torch.float32, device=dev) if want_rows else None)
+
+
 def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int, want_rows: bool) -> Optional[BagPlan]:
     """The capacity form of embed_bag_lookup: tt_bag_prepare + tt_embed_bag_fwd_cap.  No launch here depends on how many ids are live."""
     dev, E = table.device, table.shape[1]
@@ -396,7 +429,12 @@ def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int,
     idx = torch.empty((2, max(cap, 1)), dtype=torch.int32, device=dev) if want_rows else None      # (the launch writes every position)
     pos_w = None
     with _timed("tt_embed_bag_fwd"):
-        if any(s.weights is not None for s in sides):
+        if any(s.pos_weights is not None for s in sides):
+            sarr, pos_w = _bag_source_args(sides, cap, want_rows, dev)
+            L.check(L.load().tt_embed_bag_fwd_cap_posw(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                                     L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
+                                                     sarr, L.ptr(pos_w), L.stream(dev)), "tt_embed_bag_fwd_cap_posw")
+        elif any(s.weights is not None for s in sides):
             warr, pos_w = _bag_weight_args(sides, cap, want_rows, dev)
             L.check(L.load().tt_embed_bag_fwd_cap_w(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
                                                     L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
@@ -408,7 +446,7 @@ def _embed_bag_lookup_cap(table: torch.Tensor, sides: Sequence[BagSide], B: int,
     if not want_rows:
         return None
     return BagPlan(idx[0, :cap], idx[1, :cap], inv_len, cap, table.shape[0], None if pos_w is None else pos_w[:cap],
-                   tuple(s.capacity for s in sides))
+                   tuple(s.capacity for s in sides), tuple(offs))
 
 
 def bag_dedup_plan(bag: BagPlan, table_rows: int) -> DedupPlan:
@@ -461,7 +499,12 @@ def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want
     idx = torch.zeros((2, max(nnz, 1)), dtype=torch.int32, device=dev) if want_rows else None
     pos_w = None
     with _timed("tt_embed_bag_fwd"):
-        if any(s.weights is not None for s in sides):
+        if any(s.pos_weights is not None for s in sides):
+            sarr, pos_w = _bag_source_args(sides, nnz, want_rows, dev)
+            L.check(L.load().tt_embed_bag_fwd_posw(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
+                                                 L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
+                                                 sarr, L.ptr(pos_w), L.stream(dev)), "tt_embed_bag_fwd_posw")
+        elif any(s.weights is not None for s in sides):
             warr, pos_w = _bag_weight_args(sides, nnz, want_rows, dev)
             L.check(L.load().tt_embed_bag_fwd_w(L.ctx(dev), L.ptr(table), table.shape[0], E, arr, len(sides), B,
                                                 L.ptr(idx[0]) if want_rows else None, L.ptr(idx[1]) if want_rows else None,
@@ -474,7 +517,7 @@ def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want
         return None
     inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
     return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz],
-                   tuple(s.ids.numel() for s in sides))
+                   tuple(s.ids.numel() for s in sides), tuple(keep))
 
 
 def embed_bag_grad(plan: DedupPlan, bag: BagPlan, srcs: Sequence[tuple], B: int, E: int, mode: int, out: torch.Tensor):

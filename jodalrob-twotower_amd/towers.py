@@ -297,7 +297,15 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
         else:                                     # the KJT's own weights, or the embedder's position weights expanded over its bags
             weights = tw.categorical_embedder.bag_weights(kjt)
         lengths = kjt.lengths() if tw.categorical_embedder.bag_mode else None
-        if lengths is not None and weights_need_grad(weights):
+        if isinstance(weights, ops.BagPosWeights):
+            # a static KJT of an embedder with position weights: the lookup reads the parameter by position.  With autograd on the
+            # parameter is a tensor input of the node (its gradient: the backward's capacity-form chain); otherwise it is data
+            if weights.param.requires_grad and torch.is_grad_enabled():
+                bag_lengths.append((lengths, count, _WeightInput(len(w_inputs), weights)))
+                w_inputs.append(weights.param)
+            else:
+                bag_lengths.append((lengths, count, weights))
+        elif lengths is not None and weights_need_grad(weights):
             # weights somebody differentiates: tensor inputs of the node, behind every tower's own (the entry names which)
             bag_lengths.append((lengths, count, _WeightInput(len(w_inputs))))
             w_inputs.append(weights)
@@ -316,16 +324,18 @@ def run_towers(towers: Sequence[BaseTower], inputs: Sequence[Dict]) -> List[torc
 
 class _Side:
     __slots__ = ("tower", "B", "acts", "acts_struct", "buf", "x", "emb", "train", "seed", "p_drop", "sync_keep", "packed", "values",
-                 "lengths", "count", "weights", "w_flat")
+                 "lengths", "count", "weights", "w_flat", "pos_weights")
 
 
 class _WeightInput:
     """In the place of a side's weights in _TowersFn's bag_lengths: they are tensor input `index` behind the towers' own inputs,
-    and the backward returns their gradient."""
-    __slots__ = ("index",)
+    and the backward returns their gradient.  source: the input is a position-weight PARAMETER (ops.BagPosWeights, whose directory
+    says how the lookup reads it), not one weight per id."""
+    __slots__ = ("index", "source")
 
-    def __init__(self, index: int):
+    def __init__(self, index: int, source=None):
         self.index = index
+        self.source = source
 
 
 class _TowersFn(torch.autograd.Function):
@@ -359,10 +369,13 @@ class _TowersFn(torch.autograd.Function):
             if isinstance(lengths, tuple):      # (lengths, count): the capacity form; (lengths, count, weights): weighted bags
                 lengths, count, weights = lengths if len(lengths) == 3 else (*lengths, None)
             w_ref = weights.index if isinstance(weights, _WeightInput) else None
+            pos_weights = weights.source if w_ref is not None else (weights if isinstance(weights, ops.BagPosWeights) else None)
             if w_ref is not None:
                 w_ref += w_base
                 weights = flat[w_ref]
                 w_like = (weights.shape, weights.dtype, weights.device)
+            if pos_weights is not None:         # the parameter as the lookup's source (its data: autograd sees the node's input)
+                pos_weights, weights = ops.BagPosWeights(pos_weights.param.detach(), pos_weights.pw_offset, pos_weights.pw_len), None
             if emb.bag_mode:
                 if lengths is None or lengths.numel() != B * K:
                     raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
@@ -378,6 +391,7 @@ class _TowersFn(torch.autograd.Function):
             s.lengths = lengths if emb.bag_mode else None
             s.count = count if emb.bag_mode else None
             s.weights = weights if emb.bag_mode else None
+            s.pos_weights = pos_weights if emb.bag_mode else None
             s.w_flat = None if w_ref is None else (w_ref, *w_like)      # where the weights' gradient goes, and what it must look like
             s.tower, s.B, s.train = tw, B, tw.training
             s.p_drop = tw.dropout_rate if tw.training else 0.0
@@ -436,7 +450,7 @@ class _TowersFn(torch.autograd.Function):
                 a.emb_packed, a.emb_pack_scale = s.packed.data_ptr(), float(tw.pack_scale)
             s.acts_struct = a
             if K and B and emb.bag_mode:     # pooled bags: launches and plans of their own, beside the plain sides of the store
-                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:], s.count, s.weights)))
+                bag_lookups.setdefault((id(emb.store), B), []).append((s, emb.bag_side(values, s.lengths, s.x[:, tw.tower_hidden_dims[0]:], s.count, s.weights, s.pos_weights)))
             elif K and B:
                 lookups.setdefault(id(emb.store), []).append((s, emb.lookup_side(values, s.x[:, tw.tower_hidden_dims[0]:]), px is not None))
         # fused lookup (+ duplicate-row plan when a backward will follow) per store
@@ -614,10 +628,18 @@ class _TowersFn(torch.autograd.Function):
             # the gradient for differentiable per-id weights, from the same views; no side asks: no launch
             want = [s.w_flat is not None and ctx.needs_input_grad[2 + s.w_flat[0]] for s in plan_sides]
             if any(want):
-                for s, g in zip(plan_sides, ops.bag_weight_grad(store.weight, bag, srcs, plan_sides[0].B, want)):
-                    if g is not None:
-                        at, shape, dtype, wdev = s.w_flat
-                        grads[at] = g.reshape(shape).to(device=wdev, dtype=dtype)
+                gs = ops.bag_weight_grad(store.weight, bag, srcs, plan_sides[0].B, want)
+                for i, (s, g) in enumerate(zip(plan_sides, gs)):
+                    if g is None:
+                        continue
+                    at, shape, dtype, wdev = s.w_flat
+                    if s.pos_weights is not None:
+                        # the parameter's gradient: the per-id gradient over the side's whole capacity (0 where no bag covers) summed
+                        # through the offsets tt_bag_prepare formed -- no launch here depends on how many ids are live
+                        pw, K = s.pos_weights, len(s.tower.categorical_embedder.keys)
+                        side = ops.PosWeightSide(s.lengths, pw.pw_offset, pw.pw_len, g.numel(), K, offsets=bag.offsets[i])
+                        g = ops.bag_position_weights_bwd(pw.param, [side], s.B, [g])
+                    grads[at] = g.reshape(shape).to(device=wdev, dtype=dtype)
         return (None, None, *grads)
 
 

@@ -164,9 +164,17 @@ def main():
     ap.add_argument("--pool-position-weights", type=int, default=None, metavar="MAXLEN",
                     help="with --pool: every pooled key learns one weight per bag position (MAXLEN of them, initialised to 1; later "
                          "positions share the last) -- the eager loop only: not with --pool-weights / --pool-store-weights (one source "
-                         "of weights per embedder), --pool-capture or --pool-store --fast")
+                         "of weights per embedder), --pool-capture or --pool-store --fast (unless --pool-position-weights-captured)")
+    ap.add_argument("--pool-position-weights-captured", action="store_true",
+                    help="with --pool-position-weights and --pool-capture or --pool-store --fast: the captured step trains the position "
+                         "weights itself (GraphedTrainStep(learned_weights=True)): the pooled lookup reads them by position, their "
+                         "gradient is formed over the capacity inside the graph")
     a = ap.parse_args()
     pooling = None
+    if a.pool_position_weights_captured and a.pool_position_weights is None:
+        ap.error("--pool-position-weights-captured needs --pool-position-weights MAXLEN")
+    if a.pool_position_weights_captured and a.pool_capture is None and not (a.pool_store and a.fast):
+        ap.error("--pool-position-weights-captured needs a captured step: --pool-capture FACTOR or --pool-store --fast")
     if a.pool_position_weights is not None:
         if not a.pool:
             ap.error("--pool-position-weights needs --pool")
@@ -174,9 +182,9 @@ def main():
             ap.error("--pool-position-weights MAXLEN must be >= 1")
         if a.pool_weights or a.pool_store_weights:
             ap.error("--pool-position-weights: not with --pool-weights / --pool-store-weights -- one source of weights per embedder")
-        if a.pool_capture is not None:
+        if a.pool_capture is not None and not a.pool_position_weights_captured:
             ap.error("--pool-position-weights: not with --pool-capture -- the captured step forms no gradient for weights; use the eager loop")
-        if a.pool_store and a.fast:
+        if a.pool_store and a.fast and not a.pool_position_weights_captured:
             ap.error("--pool-position-weights: not with --pool-store --fast -- the captured step forms no gradient for weights; use the eager loop")
     if a.pool_store and not a.pool:
         ap.error("--pool-store needs --pool")
@@ -310,7 +318,8 @@ def main():
                 model = train_task.two_tower_model
                 caps = {side: max(1, math.ceil(a.pool_capture * batch[side]["kjt"].values().numel()))
                         for side, tw in (("notice", model.notice_tower), ("company", model.company_tower)) if tw.categorical_embedder.bag_mode}
-                pool_step = GraphedTrainStep(train_task, optimizer, batch, warmup=1, bag_capacity=caps)
+                pool_step = GraphedTrainStep(train_task, optimizer, batch, warmup=1, bag_capacity=caps,
+                                             learned_weights=a.pool_position_weights_captured)
                 print(f"--pool-capture: captured with bag_capacity = {caps}")
             fits = batch["notice"]["dense"].shape == pool_step.static["notice"]["dense"].shape and \
                 all(batch[side]["kjt"].values().numel() <= cap for side, cap in pool_step.bag_capacity.items())
@@ -339,6 +348,8 @@ def main():
             caps = {side: max(math.ceil(factor * float(st.run_lengths[train_loader.pairs[:, col]].sum()) * config["batch_size"] / len(train_loader.pairs)),
                               example[side]["kjt"].values().numel(), 1) for side, st, col in train_loader.bag_stores()}
             cap["bag_capacity"] = caps
+            if a.pool_position_weights_captured:
+                cap["learned_weights"] = True
             print(f"--pool-store: captured with bag_capacity = {caps}")
         graphed = GraphedTrainStep(train_task, optimizer, example, warmup=1, accumulate_metrics=True, **cap)
         rag = train_loader.ragged_example()              # the epoch's last, smaller batch gets a captured step of its own size:

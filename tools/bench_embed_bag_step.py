@@ -18,8 +18,11 @@ several times (fresh processes) for a spread: every run prints one JSON line per
 --weighted: every id of the bag-mode sides carries an f32 weight (synthetic.ragged_bags(weights="uniform")): the eager and the
 captured step then run the weighted entries (tt_embed_bag_fwd_w / _cap_w / tt_embed_bag_grad_bwd_w), and so do the launch-level figures.
 --position-weights MAXLEN: the pooled keys of both towers learn MAXLEN position weights each (categorical_position_weights): the
-eager step then also expands the parameter, forms the per-id weight gradient and reduces it; eager only (the captured step
-refuses such a model), not with --weighted (one source of weights per embedder).  Its yardstick is the eager --weighted step."""
+eager step then also expands the parameter, forms the per-id weight gradient and reduces it; the captured leg is
+GraphedTrainStep(learned_weights=True): the pooled lookup reads the parameter by position and the gradient chain runs over the
+capacity inside the graph.  Not with --weighted (one source of weights per embedder); the launch-level figures are left out.  Its
+yardsticks are the eager step of the same model and the captured --weighted step.
+--captured-only: no eager leg (eager_ms is null).  --steps-only: no launch-level figures."""
 import argparse
 import contextlib
 import io
@@ -52,14 +55,15 @@ ap.add_argument("--pool", type=int, default=4, help="batches the steps rotate th
 ap.add_argument("--iters", type=int, default=50, help="calls per launch-level figure")
 ap.add_argument("--tag", default="", help="copied into every result line (e.g. the run number, or 'parent')")
 ap.add_argument("--weighted", action="store_true", help="per-id weights on the bag-mode sides: the weighted entries")
-ap.add_argument("--position-weights", type=int, default=None, metavar="MAXLEN", help="learned position weights on the pooled keys (eager only)")
+ap.add_argument("--position-weights", type=int, default=None, metavar="MAXLEN", help="learned position weights on the pooled keys of both towers")
+ap.add_argument("--captured-only", action="store_true", help="skip the eager leg")
+ap.add_argument("--steps-only", action="store_true", help="skip the launch-level figures (a kernel trace then holds the steps' launches alone)")
 ap.add_argument("--eager-only", action="store_true", help="the eager step only (a checkout without bag_capacity)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.position_weights is not None:
     if a.weighted:
         ap.error("--position-weights: not with --weighted (one source of weights per embedder)")
-    a.eager_only = True
 dev = torch.device("cuda:0")
 B, E = a.batch, 32
 schema = synthetic.load_real_schema(ROOT / "jodalrob-twotower_amd" / "schema_real.json")
@@ -144,26 +148,30 @@ for mean in a.lengths:
     r = {"tag": a.tag, "weighted": a.weighted, "position_weights": a.position_weights, "mean_bag_length": mean, "B": B, "E": E, "keys": sum(len(k) for k in keys.values()), "pooled_keys_per_tower": a.pool_keys,
          "rows_per_tower": a.rows, "nnz": nnz, "steps": a.steps, "plain_captured_launches": plain_launches}
     pooling = {k: "mean" for s in keys for k in pooled[s]}
-    task, opt = make_task(pooling)
+    r["eager_ms"] = None
+    if not a.captured_only:
+        task, opt = make_task(pooling)
 
-    def eager(b):
-        opt.zero_grad()
-        res = task(b, return_metrics=True)
-        res["loss"].backward()
-        opt.step()
-    r["eager_ms"] = round(clock(eager, pool), 4)
-    del task, opt
+        def eager(b):
+            opt.zero_grad()
+            res = task(b, return_metrics=True)
+            res["loss"].backward()
+            opt.step()
+        r["eager_ms"] = round(clock(eager, pool), 4)
+        del task, opt
     if not a.eager_only:
         r["captured_ms"], r["captured_launches"], r["capacity"] = {}, {}, {}
         for f in a.factors:
             task, opt = make_task(pooling)
             caps = {s: int(-(-nnz[s] * f // 1)) for s in keys}
-            g = GraphedTrainStep(task, opt, pool[0], warmup=2, bag_capacity=caps)
+            g = GraphedTrainStep(task, opt, pool[0], warmup=2, bag_capacity=caps,
+                                 **(dict(learned_weights=True) if a.position_weights is not None else {}))
             r["captured_ms"][str(f)] = round(clock(g.step, pool), 4)
             r["captured_launches"][str(f)] = g.library_launches
             r["capacity"][str(f)] = caps
             g.close()
             del task, opt, g
+    if not a.eager_only and a.position_weights is None and not a.steps_only:
         # the launches alone, on pool[0]
         task, _ = make_task(pooling)
         m = task.two_tower_model
