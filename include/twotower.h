@@ -1419,6 +1419,21 @@ int tt_embed_bag_fwd_cap_posw(tt_ctx* ctx, const float* table, int64_t table_row
                             int32_t n_sides, int64_t B, int32_t* rows_out, int32_t* bag_of, const tt_bag_weight_src* srcs,
                             float* w_out, tt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The ROWS-ONLY form of the pooled lookup: what a rank of the row-wise sharded step runs, whose table lives on other ranks.
+ * tt_embed_bag_rows writes into rows_out / bag_of -- and tt_embed_bag_rows_w into w_out -- exactly the words tt_embed_bag_fwd[_w]
+ * writes there for the same sides, bit for bit: the fused row of every position a bag covers (ids clamped as in the lookup; a row
+ * outside [0, table_rows) stored as table_rows - 1 with TT_DEVERR_ROW_RANGE), (0, -1) for the positions behind a side's last
+ * bag, TT_DEVERR_BAG_OFFSETS and an empty bag for a refused offset pair.  table_rows is the GLOBAL row count.  No table is
+ * read and no pooled output written: a side's out / ld_out / out_dtype (and key_pool) are not looked at and may be NULL / 0.
+ * The same kernel template as the lookup (a rows-only instantiation), ONE launch, no atomics on the data path, no LDS.
+ * weights / w_out: as tt_embed_bag_fwd_w takes them.  There is no capacity form and no position-weight source.
+ * ---------------------------------------------------------------------------------------------- */
+int tt_embed_bag_rows(tt_ctx* ctx, int64_t table_rows, const tt_bag_side* sides, int32_t n_sides, int64_t B, int32_t* rows_out,
+                      int32_t* bag_of, tt_stream stream);
+int tt_embed_bag_rows_w(tt_ctx* ctx, int64_t table_rows, const tt_bag_side* sides, int32_t n_sides, int64_t B, int32_t* rows_out,
+                        int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -282,6 +282,8 @@ SIGNATURES = {
     "tt_bag_position_weights_bwd": (C.c_int, [vp, vp, i64, C.POINTER(BagPwSide), i32, i64, vp]),
     "tt_embed_bag_fwd_posw": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(BagWeightSrc), vp, vp]),
     "tt_embed_bag_fwd_cap_posw": (C.c_int, [vp, vp, i64, i32, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(BagWeightSrc), vp, vp]),
+    "tt_embed_bag_rows": (C.c_int, [vp, i64, C.POINTER(BagSide), i32, i64, vp, vp, vp]),
+    "tt_embed_bag_rows_w": (C.c_int, [vp, i64, C.POINTER(BagSide), i32, i64, vp, vp, C.POINTER(vp), vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -53,6 +53,10 @@ constexpr int kBagBatch = 8;
 // weigh 1) and the place the gradient reads them back from, laid out like rows_out / bag_of.  The unweighted instantiation takes
 // BagSet as it is: its kernel-argument layout, like its code, does not change.
 // W is the forward's weight form: 0 none, 1 per-id arrays, 2 per side a per-id array, a position-weight parameter or nothing.
+// 3 and 4 are the ROWS-ONLY forms of 0 and 1 (tt_embed_bag_rows[_w]): the same walk over the bags and the same words in rows_out /
+// bag_of / w_out, but no table is read and no pooled output written -- what a rank of the sharded step runs, whose table is not local.
+constexpr bool bag_weighted(int W) { return W == 1 || W == 2 || W == 4; }
+constexpr bool bag_rows_only(int W) { return W >= 3; }
 template <int W>
 struct BagFwdArgs : BagSet {};
 template <>
@@ -61,6 +65,8 @@ struct BagFwdArgs<1> : BagSet {
   float* w_out;
 };
 // the _posw entries: per side a position-weight parameter (NULL: the side takes w[si], or weighs 1) and its key directory
+template <>
+struct BagFwdArgs<4> : BagFwdArgs<1> {};
 template <>
 struct BagFwdArgs<2> : BagFwdArgs<1> {
   const float* pw_param[TT_MAX_SIDES];
@@ -74,13 +80,14 @@ struct BagFwdArgs<2> : BagFwdArgs<1> {
 // W == 2: a side with a parameter reads position j of a bag of key k from param[pw_index_at(off[k], len[k], j)] (tt_bag_pw.h), 1
 // for a key without; the value takes the place of the per-id weight in the same chain and in w_out.  The sides of one launch may
 // differ: parameter, per-id array, none.
+// Rows-only forms: the lane group is kBagBatch lanes wide (lane j writes position j of a trip) and `table` is NULL.
 template <int W>
 __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, const float* __restrict__ table) {
   const uint32_t LG = a.LG;
   const uint32_t gthread = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lig = gthread & (LG - 1);
   const uint32_t ngroups = gridDim.x * blockDim.x / LG;
-  const bool live = lig < a.C;
+  [[maybe_unused]] const bool live = lig < a.C;
   for (uint32_t slot = gthread / LG; slot < a.total_slots; slot += ngroups) {
     int si = 0;
 #pragma unroll
@@ -88,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
       if (i < a.n && slot >= a.s[i].slot_base) si = i;
     const BagSideDev& s = a.s[si];
     const uint32_t local = slot - s.slot_base;
-    const uint32_t b = local / (uint32_t)s.K;
+    [[maybe_unused]] const uint32_t b = local / (uint32_t)s.K;
     const uint32_t k = local - b * (uint32_t)s.K;
     int64_t o0 = s.offs[local], o1 = s.offs[local + 1];
     if (o0 < 0 || o1 < o0 || o1 > s.nnz) {                   // nothing is read through such a pair: the bag counts as empty
@@ -97,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
     }
     const int64_t hi = s.vocab[k] - 1, base = s.off[k];
     const float* sw = nullptr;
-    if constexpr (W != 0) sw = a.w[si];
+    if constexpr (bag_weighted(W)) sw = a.w[si];
     const float* pp = nullptr;                                 // (W == 2) the side's parameter and this bag's key entry
     int32_t poff = -1, plen = 0;
     int64_t pn = 0;
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
         pn = a.pw_n[si];
       }
     }
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t p = o0; p < o1; p += kBagBatch) {
       int64_t id[kBagBatch];
 #pragma unroll
@@ -126,31 +133,33 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
             wj[j] = sw[p + j];
           }
         }
-      } else if constexpr (W != 0) {
+      } else if constexpr (bag_weighted(W)) {
 #pragma unroll
         for (int j = 0; j < kBagBatch; ++j) wj[j] = (sw && p + j < o1) ? sw[p + j] : 1.f;
       }
-      float4 v[kBagBatch];
+      [[maybe_unused]] float4 v[kBagBatch];
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) {
-        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (!bag_rows_only(W)) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p + j < o1) {
           const int64_t idc = id[j] < 0 ? 0 : (id[j] > hi ? hi : id[j]);             // clamp: cat_embed.py:117 (as the lookup)
           const int64_t row = row_in_table(base + idc, a.table_rows, a.dev_err);
           if (lig == ((uint32_t)j & (LG - 1))) {
             if (a.rows_out) a.rows_out[s.pos_base + (p + j)] = (int32_t)row;
             if (a.bag_of) a.bag_of[s.pos_base + (p + j)] = (int32_t)slot;
-            if constexpr (W != 0) {
+            if constexpr (bag_weighted(W)) {
               if (a.w_out) a.w_out[s.pos_base + (p + j)] = wj[j];
             }
           }
-          if (live) v[j] = *reinterpret_cast<const float4*>(table + row * a.E + lig * 4);
+          if constexpr (!bag_rows_only(W)) {
+            if (live) v[j] = *reinterpret_cast<const float4*>(table + row * a.E + lig * 4);
+          }
         }
       }
 #pragma unroll
       for (int j = 0; j < kBagBatch; ++j) {
-        if (p + j >= o1) continue;
-        if constexpr (W != 0) {
+        if (bag_rows_only(W) || p + j >= o1) continue;
+        if constexpr (bag_weighted(W)) {
           if (p + j == o0) {
             acc.x = __fmul_rn(wj[j], v[j].x); acc.y = __fmul_rn(wj[j], v[j].y);
             acc.z = __fmul_rn(wj[j], v[j].z); acc.w = __fmul_rn(wj[j], v[j].w);
@@ -166,11 +175,11 @@ __global__ __launch_bounds__(kThreads) void bag_fwd_kernel(BagFwdArgs<W> a, cons
       }
     }
     const int64_t len = o1 - o0;
-    if (len > 1 && s.pool[k] == TT_POOL_MEAN) {
+    if (!bag_rows_only(W) && len > 1 && s.pool[k] == TT_POOL_MEAN) {
       const float l = (float)len;
       acc.x /= l; acc.y /= l; acc.z /= l; acc.w /= l;
     }
-    if (live) {
+    if (!bag_rows_only(W) && live) {
       const int64_t col = (int64_t)b * s.ld + (int64_t)k * a.E + lig * 4;
       if (s.dtype == TT_F32) {
         *reinterpret_cast<float4*>(s.out + col * 4) = acc;
@@ -599,7 +608,62 @@ static int bag_fwd_impl(tt_ctx* ctx, const float* table, int64_t table_rows, int
   return TT_OK;
 }
 
+// tt_embed_bag_rows[_w]: the rows-only launch.  No table, no E, no outputs: a side's `out` fields are not looked at.
+static int bag_rows_impl(tt_ctx* ctx, int64_t table_rows, const tt_bag_side* sides, int32_t n_sides, int64_t B, int32_t* rows_out,
+                         int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream, const char* who) {
+  TT_CHECK_ARG(ctx && sides, "%s: NULL argument", who);
+  TT_CHECK_ARG(n_sides >= 1 && n_sides <= TT_MAX_SIDES, "%s: n_sides=%d not in [1,%d]", who, n_sides, TT_MAX_SIDES);
+  TT_CHECK_ARG(B >= 0 && table_rows >= 1 && table_rows <= INT32_MAX, "%s: bad B=%lld rows=%lld", who, (long long)B, (long long)table_rows);
+  BagFwdArgs<4> a{};         // (the unweighted launch passes its BagSet part)
+  a.n = n_sides;
+  a.C = a.LG = kBagBatch;
+  int64_t slots = 0, positions = 0;
+  for (int i = 0; i < n_sides; ++i) {
+    const tt_bag_side& s = sides[i];
+    a.w[i] = weights ? weights[i] : nullptr;
+    TT_CHECK_ARG(!(rows_out && a.w[i] && !w_out), "%s: rows_out with weights on side %d needs w_out", who, i);
+    if (!tt_aligned(a.w[i], 4) || !tt_aligned(w_out, 4)) return bag_unsupported(who, "weights and w_out must be 4-byte aligned");
+    TT_CHECK_ARG(s.K >= 1 && s.nnz >= 0, "%s: side %d has K=%d nnz=%lld", who, i, s.K, (long long)s.nnz);
+    TT_CHECK_ARG(s.offsets && s.key_row_offset && s.key_vocab && (s.ids || s.nnz == 0), "%s: side %d has NULL pointers", who, i);
+    a.s[i] = BagSideDev{s.ids, s.offsets, s.key_row_offset, s.key_vocab, s.key_pool, nullptr, 0, s.nnz, (uint32_t)slots, (uint32_t)positions,
+                        s.K, TT_F32};
+    slots += B * s.K;
+    positions += s.nnz;
+  }
+  TT_CHECK_ARG(slots * a.LG < ((int64_t)1 << 31) && positions < ((int64_t)1 << 31), "%s: %lld bags / %lld ids exceed the 2^31 index range", who,
+               (long long)slots, (long long)positions);
+  if (slots == 0) return TT_OK;
+  a.total_slots = (uint32_t)slots;
+  a.table_rows = (int32_t)table_rows;
+  a.dev_err = ctx->dev_err;
+  a.rows_out = rows_out;
+  a.bag_of = bag_of;
+  a.pad_row = -1;
+  a.total_pos = (uint32_t)positions;
+  a.w_out = w_out;
+  if (weights) {
+    bag_fwd_kernel<4><<<grid_for(ctx, slots * a.LG), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a, nullptr);
+  } else {
+    BagFwdArgs<3> u{};
+    static_cast<BagSet&>(u) = a;
+    bag_fwd_kernel<3><<<grid_for(ctx, slots * a.LG), kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(u, nullptr);
+  }
+  TT_LAUNCH_CHECK();
+  return TT_OK;
+}
+
 extern "C" {
+
+int tt_embed_bag_rows(tt_ctx* ctx, int64_t table_rows, const tt_bag_side* sides, int32_t n_sides, int64_t B, int32_t* rows_out,
+                      int32_t* bag_of, tt_stream stream) {
+  return bag_rows_impl(ctx, table_rows, sides, n_sides, B, rows_out, bag_of, nullptr, nullptr, stream, "tt_embed_bag_rows");
+}
+
+int tt_embed_bag_rows_w(tt_ctx* ctx, int64_t table_rows, const tt_bag_side* sides, int32_t n_sides, int64_t B, int32_t* rows_out,
+                        int32_t* bag_of, const float* const* weights, float* w_out, tt_stream stream) {
+  TT_CHECK_ARG(weights, "tt_embed_bag_rows_w: NULL weights array (a side without weights has a NULL entry)");
+  return bag_rows_impl(ctx, table_rows, sides, n_sides, B, rows_out, bag_of, weights, w_out, stream, "tt_embed_bag_rows_w");
+}
 
 int tt_embed_bag_fwd(tt_ctx* ctx, const float* table, int64_t table_rows, int32_t E, const tt_bag_side* sides, int32_t n_sides,
                      int64_t B, int32_t* rows_out, int32_t* bag_of, tt_stream stream) {

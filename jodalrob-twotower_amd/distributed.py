@@ -16,6 +16,9 @@ The reference is single-GPU (no collective anywhere: SURVEY.md §2.1); this is n
   * towers   : dense weights replicated; gradients summed with one all-reduce per tower over the flat
                gradient buffer tt_tower_mlp_bwd fills (0.3 MB: latency-bound, a single call).
                BatchNorm statistics are per rank (as torch DDP without SyncBatchNorm).
+  * bags     : a bag-mode model (categorical_pooling; pooled_exchange=True) routes its bag POSITIONS instead of slots
+               (forward_bags): global rows from the rows-only pooled lookup, the received f32 rows pooled by the
+               pooled lookup itself, gradients reduced through the bag reduction before they travel.  Eager step.
 
 xGMI is point-to-point (7 links per GPU), so the pooled-row all-to-all places each peer's chunk on its
 own link; ring-shaped collectives are avoided on the data path.
@@ -26,6 +29,7 @@ object.  `HipBackend` (the product path) calls the C ABI; the CPU/gloo tests inj
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import List, Optional, Sequence
 
@@ -36,8 +40,8 @@ import torch.nn as nn
 
 from . import ops
 from .batch_terms import ROWS as TERM_ROWS
-from .cat_embed import EmbeddingStore, refuse_bag_mode
-from .two_tower_model import TwoTowerModel
+from .cat_embed import EmbeddingStore, position_weighted_embedders, refuse_bag_mode
+from .two_tower_model import TwoTowerModel, _tower_pooling
 from .two_tower_train_task import TwoTowerTrainTask
 
 
@@ -148,6 +152,46 @@ class HipBackend:
         # max_per_row: the most contributions a row can get (padded exchange: one per rank); 0 = unknown
         store.accumulate_grad(plan, [(d_rows, 1)], d_rows.shape[0], short_segments=0 < max_per_row <= 64)
 
+    # ---- pooled bags (forward_bags of both exchanges) --------------------------------------------------------
+    def bag_rows(self, sides: Sequence[ops.BagSide], B: int, table_rows: int) -> ops.BagPlan:
+        """the bag plan of this rank's positions over the GLOBAL row space (rows, bag_of, inv_len, pos_w): no table is read"""
+        return ops.embed_bag_rows(sides, B, table_rows)
+
+    def pool_rows(self, received: torch.Tensor, idx: torch.Tensor, sides: Sequence[ops.BagSide], B: int):
+        """out_side[b, k*E:(k+1)*E] = pool of received[idx[P]] over the bag's positions P -- the pooled lookup with the received
+        rows as its table: ids idx (int64 [nnz], the sides behind one another), row offset 0, vocabulary = the buffer's rows; lengths,
+        pooling modes and per-id weights are the side's own"""
+        dev = received.device
+        if received.shape[0] == 0:
+            received = torch.zeros((1, received.shape[1]), dtype=torch.float32, device=dev)
+        M = received.shape[0]
+        psides, base = [], 0
+        for s in sides:
+            n = s.ids.numel()
+            psides.append(dataclasses.replace(s, ids=idx[base:base + n], key_row_offset=_const_i64(dev, s.K, 0),
+                                              key_vocab=_const_i64(dev, s.K, M)))
+            base += n
+        ops.embed_bag_lookup(received, psides, B, want_rows=False)
+
+    def collect_bag_grads(self, srcs, order: torch.Tensor, bag: ops.BagPlan, B: int, E: int) -> torch.Tensor:
+        """d_bucket[i] = c * w * d_out[slot] of position order[i] (c: the slot's mean weight, w: the id's weight; zeros for a
+        position no bag covers) -- an identity-segment plan through tt_embed_bag_grad_bwd[_w], as collect_grads does for slots"""
+        M, dev = order.numel(), order.device
+        ar = torch.arange(M + 1, dtype=torch.int32, device=dev)
+        plan = ops.DedupPlan(order, ar[:M], ar, torch.full((1,), M, dtype=torch.int32, device=dev), M)
+        out = torch.empty((max(M, 1), E), dtype=torch.float32, device=dev)
+        ops.embed_bag_grad(plan, bag, srcs, B, E, ops.TT_GRAD_SPARSE, out)
+        return out[:M]
+
+    def bag_local_plan(self, bag: ops.BagPlan, table_rows: int):
+        """duplicate-row plan of this rank's POSITIONS (M = nnz) over the global row space"""
+        return ops.dedup_plan(bag.rows, table_rows)
+
+    def reduce_bags_into_buckets(self, plan, pos_u: torch.Tensor, bag: ops.BagPlan, srcs, B: int, E: int, out: torch.Tensor) -> torch.Tensor:
+        """row pos_u[u] of `out` = summed gradient of plan row u over its positions; the other rows keep what they held"""
+        ops.embed_bag_grad(dataclasses.replace(plan, unique_rows=pos_u), bag, srcs, B, E, ops.TT_GRAD_DENSE_SET, out)
+        return out
+
     # ---- steps of the fixed-capacity exchange (PaddedRowExchange) --------------------------------------------
     def local_plan(self, rows: torch.Tensor, side_K: Sequence[int], B: int, table_rows: int = 0, key_major: bool = False, E: int = 0):
         """duplicate-row plan of this rank's slots over the GLOBAL row space (table_rows = its size: sets the sort's digit
@@ -191,6 +235,15 @@ class HipBackend:
         out = torch.empty((max(plan.M, 1), E), dtype=torch.float32, device=plan.unique_rows.device)
         ops.embed_grad(plan, srcs, B, E, ops.TT_GRAD_SPARSE, out, counters=counters)
         return out
+
+
+def _refuse_bag_sources(sides: Sequence[ops.BagSide]) -> None:
+    for i, s in enumerate(sides):
+        if s.pos_weights is not None:
+            raise ValueError(f"side {i}: learned position weights are not carried across the sharded table exchange (forward_bags takes "
+                             "per-id data weights or none)")
+        if s.capacity is not None:
+            raise ValueError(f"side {i}: the sharded table exchange has no capacity form of the pooled lookup (eager step only)")
 
 
 class DistComm:
@@ -273,8 +326,30 @@ class RowExchange:
         return out
 
     def forward(self, sides: Sequence[ops.LookupSide], B: int, want_grad: bool):
-        G, be = self.world, self.backend
+        be = self.backend
         rows = be.global_rows(sides, B, self.E, self.store.global_rows)          # int32 [M], slot order
+        pooled, inv, state = self._route(rows, want_grad)
+        be.place_rows(pooled, inv, sides, B)
+        return state
+
+    def forward_bags(self, sides: Sequence[ops.BagSide], B: int, want_grad: bool):
+        """The pooled form of `forward`: every side is a ragged bag side (a plain side rides along as sum bags of length one --
+        ops.bag_side_from_lookup).  The rank's POSITIONS are routed like slots: their global rows come from the rows-only form of
+        the pooled lookup, the received rows are pooled by the pooled lookup itself with the [M, E] receive buffer as its table, and
+        the backward sends each position's weighted contribution to the row's owner.  The pooled bits are the unsharded lookup's:
+        the same f32 rows added in the same order.  Position-weight sources are refused (ValueError)."""
+        be = self.backend
+        _refuse_bag_sources(sides)
+        bag = be.bag_rows(sides, B, self.store.global_rows)                      # rows / bag_of per position, no table read
+        pooled, inv, state = self._route(bag.rows, want_grad)
+        be.pool_rows(pooled, inv, sides, B)
+        if state is not None:
+            state["bag"] = bag
+        return state
+
+    def _route(self, rows: torch.Tensor, want_grad: bool):
+        """rows int32 [M] (global) -> (their rows [M, E] in bucket order, inv: entry -> bucket position, the backward's state)"""
+        G, be = self.world, self.backend
         M = rows.numel()
         order, counts = be.bucket_by_owner(rows, G)                              # slots grouped by owner
         send_ids = torch.div(rows[order.long()], G, rounding_mode="floor").to(torch.int64)
@@ -286,12 +361,14 @@ class RowExchange:
         pooled = self._a2a(pooled_local, recv_splits, send_splits)               # [M, E] in bucket order
         inv = torch.empty(M, dtype=torch.int64, device=rows.device)
         inv[order.long()] = torch.arange(M, dtype=torch.int64, device=rows.device)
-        be.place_rows(pooled, inv, sides, B)
-        return {"order": order, "send": send_splits, "recv": recv_splits, "plan": plan} if want_grad else None
+        return pooled, inv, ({"order": order, "send": send_splits, "recv": recv_splits, "plan": plan} if want_grad else None)
 
     def backward(self, state, srcs, B: int):
         be = self.backend
-        d_bucket = be.collect_grads(srcs, state["order"], B, self.E)
+        if state.get("bag") is not None:                                         # forward_bags' state: contributions per position
+            d_bucket = be.collect_bag_grads(srcs, state["order"], state["bag"], B, self.E)
+        else:
+            d_bucket = be.collect_grads(srcs, state["order"], B, self.E)
         d_rows = self._a2a(d_bucket, state["send"], state["recv"])               # to the owners
         if state["plan"] is not None:
             be.owner_accumulate(self.store, state["plan"], d_rows)
@@ -334,7 +411,8 @@ class PaddedRowExchange(RowExchange):
         #                                  never puts uninitialised memory on the wire: it carries zeros or an older step's sum
         self._flag_host, self._flag_event, self._flag_pending = None, None, False
         self.poll_lag = 2                # steps a raised overflow may lag behind the step that caused it
-        self.wire_bf16 = True            # looked-up rows travel as bf16 (the towers round them to bf16 anyway: bit-identical)
+        self.wire_bf16 = True            # looked-up rows travel as bf16 (the towers round them to bf16 anyway: bit-identical) -- length-one
+        #                                  traffic (forward) only: forward_bags' rows always travel as f32
         self.grad_wire_bf16 = False      # row gradients travel as f32
 
     def local_rows_of(self, g: int) -> int:
@@ -441,8 +519,55 @@ class PaddedRowExchange(RowExchange):
             return None
         return {"plan": plan, "send_u": send_u, "pos_u": pos_u, "owner_plan": be.owner_plan(recv_ids, self.store.local_rows, G), "padded": True}
 
+    def forward_bags(self, sides: Sequence[ops.BagSide], B: int, want_grad: bool):
+        """The pooled form of `forward` (see RowExchange.forward_bags): the duplicate-row plan is taken over the rank's POSITIONS
+        (M = nnz), each distinct row travels once, and the received rows -- buf [G*C + 1, E] -- are pooled by the pooled lookup
+        with the positions' bucket entries as its ids.  A row that did not fit pools the zero row behind the buckets; the overflow
+        flag, poll_overflow and the calibration (on the plan's distinct rows) work as for plain rows.
+        Pooled rows travel as f32 whatever the tower input dtype is: a bag adds its rows in f32 and rounds once, and rounding
+        every row to bf16 on the wire would change the pooled bits against the unsharded step -- `wire_bf16` applies to length-one
+        traffic (`forward`) only, and `grad_wire_bf16` likewise.  Eager only; a rank whose step holds no id at all is refused."""
+        G, be, E = self.world, self.backend, self.E
+        _refuse_bag_sources(sides)
+        bag = be.bag_rows(sides, B, self.store.global_rows)
+        if bag.nnz == 0:
+            raise ValueError("forward_bags: this rank's step holds no id at all (every bag is empty): nothing to route")
+        plan = be.bag_local_plan(bag, self.store.global_rows)
+        if self.C is None:
+            self._calibrate(plan, bag.rows.device)
+        pads = [self.local_rows_of(g) for g in range(G)]
+        if self._overflow is None:
+            self._overflow = be.new_flag(bag.rows.device)
+        if isinstance(be, HipBackend):       # routing and the positions' bucket entries from one launch
+            send_ids, _send_u, pos_u, _counts, idx_pos = be.route_bucket(plan, G, self.C, pads, -1, self._overflow, expand=True)
+        else:
+            send_ids, _send_u, pos_u, _counts = be.route_bucket(plan, G, self.C, pads, -1, self._overflow)
+            idx_pos = be.route_expand(plan, pos_u)
+        recv_ids = self._a2a_equal(send_ids)                                     # [G*C] local row ids, pad = my local_rows
+        pooled_local = be.gather_rows(self.store.weight, recv_ids, torch.float32)
+        buf = self._rows_buffer(pooled_local)
+        self._a2a_equal(pooled_local, buf[:G * self.C])                          # [G*C, E] in my send order (+ the zero row)
+        be.pool_rows(buf, idx_pos, sides, B)
+        if not want_grad:
+            return None
+        return {"plan": plan, "pos_u": pos_u, "bag": bag, "owner_plan": be.owner_plan(recv_ids, self.store.local_rows, G), "padded": True}
+
+    def _bags_backward(self, state, srcs, B: int):
+        """every distinct row's sum over its positions, written at its bucket entry of the zero-initialised send buffer (the
+        reduction's dense-set mode with the bucket positions as row indices), then to the owners"""
+        be, dev = self.backend, state["pos_u"].device
+        n = self.world * self.C + 1
+        sb = self._send_buf
+        if sb is None or sb.shape[0] != n or sb.device != dev:
+            sb = self._send_buf = torch.zeros((n, self.E), dtype=torch.float32, device=dev)
+        send = be.reduce_bags_into_buckets(state["plan"], state["pos_u"], state["bag"], srcs, B, self.E, sb)
+        d_rows = self._a2a_equal(send[:self.world * self.C])
+        be.owner_accumulate(self.store, state["owner_plan"], d_rows, self.world)
+
     def backward(self, state, srcs, B: int):
         be = self.backend
+        if state.get("bag") is not None:
+            return self._bags_backward(state, srcs, B)
         # opt-in (grad_wire_bf16): the per-rank row sums travel as bf16 and are added in f32 by their owner -- half the bytes of
         # the step's largest message, at 2^-9 relative rounding per contribution
         wire = torch.bfloat16 if (self.grad_wire_bf16 and self.E % 8 == 0) else torch.float32
@@ -513,9 +638,19 @@ class DistributedTwoTowerTrainTask(TwoTowerTrainTask):
     """TwoTowerTrainTask whose tables are row-wise sharded over the process group."""
 
     def __init__(self, two_tower_model: TwoTowerModel, store: ShardedStore, group=None, backend=None, exchange: Optional[str] = None,
-                 negatives: str = "local", sync_bn: bool = False, comm=None, **kw):
+                 negatives: str = "local", sync_bn: bool = False, comm=None, pooled_exchange: bool = False, **kw):
+        """pooled_exchange: accept bag-mode embedders (categorical_pooling) -- the towers then route the bags' positions through
+        the exchange's forward_bags (eager step; per-id data weights allowed, learned position weights and weights that require
+        grad refused).  False (the default) keeps refusing a bag-mode model."""
         super().__init__(two_tower_model, **kw)
-        refuse_bag_mode(two_tower_model, "the sharded exchange step (" + type(self).__name__ + ")")     # its id routing sends B*K ids
+        if not pooled_exchange:
+            refuse_bag_mode(two_tower_model, "the sharded exchange step (" + type(self).__name__ + ")")     # its id routing sends B*K ids
+        elif position_weighted_embedders(two_tower_model):
+            raise ValueError("the sharded exchange step (" + type(self).__name__ + ") does not support learned position weights "
+                             "(categorical_position_weights / add_position_weights): " +
+                             ", ".join(position_weighted_embedders(two_tower_model)) + " would need the weight gradient across the "
+                             "exchange -- per-id data weights on the KJT are supported")
+        self.pooled_exchange = bool(pooled_exchange)
         if exchange is None:             # the fixed-capacity exchange wherever it applies (row-sparse table gradients)
             exchange = "padded" if store.grad_mode == "sparse" else "exact"
         if negatives not in ("local", "global"):
@@ -610,8 +745,11 @@ def create_distributed_train_task(notice_categorical_keys, company_categorical_k
                                   dropout_rate: float = 0.2, temperature: float = 1.0, loss_type: str = "cross_entropy",
                                   device="cuda:0", embedding_grad: Optional[str] = "sparse", score_dtype=None, mlp_dtype=None,
                                   group=None, backend=None, seed: int = 0, exchange: Optional[str] = None,
-                                  negatives: str = "local", sync_bn: bool = False, comm=None) -> DistributedTwoTowerTrainTask:
+                                  negatives: str = "local", sync_bn: bool = False, comm=None,
+                                  categorical_pooling=None) -> DistributedTwoTowerTrainTask:
     """Same arguments as create_two_tower_train_task; requires an initialised process group.
+    categorical_pooling: as create_two_tower_model takes it ("sum" / "mean", {"notice": spec, "company": spec} or {key: mode}),
+    passed to both towers: bag mode across the exchange (DistributedTwoTowerTrainTask(pooled_exchange=True)), eager step only.
     exchange: None = "padded" (dedup-first fixed-capacity all-to-alls, every step of the routing inside the .so, capturable)
     with row-sparse table gradients, "exact" with dense ones.  "exact" (RowExchange: exact bucket sizes, one host sync
     and a few ATen index ops per step, eager only) is the simple implementation the padded one is tested against."""
@@ -622,9 +760,11 @@ def create_distributed_train_task(notice_categorical_keys, company_categorical_k
     common = dict(metadata_path=metadata_path, categorical_embedding_dim=categorical_embedding_dim,
                   tower_hidden_dims=tower_hidden_dims, final_embedding_dim=final_embedding_dim, dropout_rate=dropout_rate,
                   device=device, embedding_grad=embedding_grad, materialize_tables=False, mlp_dtype=mlp_dtype)
+
+    pool_n, pool_c = _tower_pooling(categorical_pooling, notice_categorical_keys, company_categorical_keys)
     model = TwoTowerModel(
-        notice_tower_config=dict(categorical_keys=notice_categorical_keys, dense_input_dim=notice_dense_input_dim, **common),
-        company_tower_config=dict(categorical_keys=company_categorical_keys, dense_input_dim=company_dense_input_dim, **common),
+        notice_tower_config=dict(categorical_keys=notice_categorical_keys, dense_input_dim=notice_dense_input_dim, categorical_pooling=pool_n, **common),
+        company_tower_config=dict(categorical_keys=company_categorical_keys, dense_input_dim=company_dense_input_dim, categorical_pooling=pool_c, **common),
         final_embedding_dim=final_embedding_dim, device=device)
     ne, ce = model.notice_tower.categorical_embedder, model.company_tower.categorical_embedder
     ne.set_row_base(0)
@@ -632,5 +772,5 @@ def create_distributed_train_task(notice_categorical_keys, company_categorical_k
     store = ShardedStore(categorical_embedding_dim, ne.total_rows + ce.total_rows, dist.get_rank(group),
                          dist.get_world_size(group), torch.device(device), embedding_grad or "sparse", seed)
     return DistributedTwoTowerTrainTask(model, store, group=group, backend=backend, exchange=exchange, negatives=negatives, sync_bn=sync_bn, comm=comm,
-                                        temperature=temperature,
+                                        pooled_exchange=categorical_pooling is not None, temperature=temperature,
                                         loss_type=loss_type, score_dtype=score_dtype)

@@ -337,7 +337,7 @@ class BagPlan(NamedTuple):
     offsets: Optional[tuple] = None
 
 
-def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
+def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev, check_out: bool = True):
     if s.ids.dtype != torch.int64 or not s.ids.is_contiguous() or s.ids.device != dev:
         raise ValueError("bag ids must be a contiguous int64 tensor on the table's device")
     if s.lengths.numel() != B * s.K or s.lengths.device != dev:
@@ -361,6 +361,8 @@ def _check_bag_side(i: int, s: BagSide, B: int, E: int, dev):
                            ("key_pool", s.key_pool, torch.int32, s.K)):
         if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError(f"side {i}: {name} must be a contiguous {dt} tensor of {n} elements on the table's device")
+    if not check_out:          # (embed_bag_rows without an output: nothing is written through the side)
+        return
     if s.out.device != dev or s.out.dim() != 2 or s.out.shape[0] != B or s.out.shape[1] != s.K * E:
         raise ValueError(f"side {i}: out must be a [B, K*E] = [{B}, {s.K * E}] view on the table's device")
     assert s.out.stride(1) == 1
@@ -515,6 +517,67 @@ def embed_bag_lookup(table: torch.Tensor, sides: Sequence[BagSide], B: int, want
                     "tt_embed_bag_fwd")
     if not want_rows:
         return None
+    inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
+    return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz],
+                   tuple(s.ids.numel() for s in sides), tuple(keep))
+
+
+_UNIT_BAGS: dict = {}
+
+
+def bag_side_from_lookup(side: LookupSide, B: int) -> BagSide:
+    """A plain side as sum bags of length one (a bag of one id is a bit-exact copy of its row in the pooled lookup): what lets a
+    plain tower ride along when the other tower pools across the sharded exchange.  The constant lengths / modes are cached."""
+    dev = side.ids.device
+    key = (str(dev), B, side.K)
+    c = _UNIT_BAGS.get(key)
+    if c is None:
+        c = _UNIT_BAGS[key] = (torch.ones(B * side.K, dtype=torch.int64, device=dev), torch.zeros(side.K, dtype=torch.int32, device=dev))
+    return BagSide(side.ids, c[0], side.key_row_offset, side.key_vocab, c[1], side.out, side.K, any_mean=False)
+
+
+def embed_bag_rows(sides: Sequence[BagSide], B: int, table_rows: int) -> BagPlan:
+    """tt_embed_bag_rows[_w]: the plan embed_bag_lookup(..., want_rows=True) returns for these sides -- rows, bag_of, inv_len, nnz, pos_w,
+    side_nnz, offsets, bit for bit -- without a table: no row is read and no side's `out` written (it may be None; one that is given
+    is checked as the lookup checks it, against E = its width / K).  table_rows: the GLOBAL row count of the row space the sides'
+    key_row_offset live in.  What a rank of the row-wise sharded step runs before it routes the rows to their owners.  Offsets and
+    inv_len are the lookup's torch formulas: no host synchronisation.  Position-weight sources and the capacity form: ValueError."""
+    if not sides:
+        raise ValueError("embed_bag_rows: no sides")
+    dev = sides[0].ids.device
+    if not (1 <= int(table_rows) <= 2 ** 31 - 1):
+        raise ValueError(f"embed_bag_rows: table_rows must lie in [1, 2^31), got {table_rows}")
+    arr = (L.BagSide * len(sides))()
+    keep, nnz, inv = [], 0, []
+    for i, s in enumerate(sides):
+        if s.pos_weights is not None:
+            raise ValueError(f"side {i}: embed_bag_rows takes no position-weight source (the sharded step does not carry learned position "
+                             "weights across the exchange)")
+        if s.capacity is not None:
+            raise ValueError(f"side {i}: embed_bag_rows has no capacity form")
+        _check_bag_side(i, s, B, s.out.shape[1] // max(s.K, 1) if s.out is not None and s.out.dim() == 2 else 0, dev,
+                        check_out=s.out is not None)
+        lengths = s.lengths.to(torch.int64).reshape(-1)
+        off = torch.zeros(B * s.K + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lengths, 0, out=off[1:])
+        keep.append(off)
+        arr[i] = L.BagSide(L.ptr(s.ids), L.ptr(off), L.ptr(s.key_row_offset), L.ptr(s.key_vocab), L.ptr(s.key_pool), None, 0,
+                           s.ids.numel(), s.K, TT_F32)
+        nnz += s.ids.numel()
+        lf = lengths.to(torch.float32)
+        mean = (s.key_pool != 0).repeat(B) & (lengths > 0)
+        one = torch.ones_like(lf)
+        inv.append(torch.where(mean, one / lf.clamp(min=1.0), one))
+    idx = torch.zeros((2, max(nnz, 1)), dtype=torch.int32, device=dev)
+    pos_w = None
+    with _timed("tt_embed_bag_rows"):
+        if any(s.weights is not None for s in sides):
+            warr, pos_w = _bag_weight_args(sides, nnz, True, dev)
+            L.check(L.load().tt_embed_bag_rows_w(L.ctx(dev), int(table_rows), arr, len(sides), B, L.ptr(idx[0]), L.ptr(idx[1]), warr,
+                                                 L.ptr(pos_w), L.stream(dev)), "tt_embed_bag_rows_w")
+        else:
+            L.check(L.load().tt_embed_bag_rows(L.ctx(dev), int(table_rows), arr, len(sides), B, L.ptr(idx[0]), L.ptr(idx[1]),
+                                               L.stream(dev)), "tt_embed_bag_rows")
     inv_len = torch.cat(inv) if any(s.any_mean for s in sides) else None
     return BagPlan(idx[0, :nnz], idx[1, :nnz], inv_len, nnz, None, None if pos_w is None else pos_w[:nnz],
                    tuple(s.ids.numel() for s in sides), tuple(keep))

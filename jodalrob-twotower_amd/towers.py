@@ -380,8 +380,18 @@ class _TowersFn(torch.autograd.Function):
                 if lengths is None or lengths.numel() != B * K:
                     raise ValueError(f"bag mode: the kjt must carry B*K = {B}*{K} bag lengths, got "
                                      f"{'none' if lengths is None else lengths.numel()}")
-                if tw.exchange is not None:
-                    raise ValueError("bag mode (categorical_pooling) is not supported with the sharded table exchange")
+                if tw.exchange is not None:         # the sharded step pools across the exchange's forward_bags -- or refuses, before any launch
+                    if not hasattr(tw.exchange, "forward_bags"):
+                        raise ValueError("bag mode (categorical_pooling) is not supported with the sharded table exchange")
+                    if pos_weights is not None:
+                        raise ValueError("learned position weights are not supported with the sharded table exchange: the weight "
+                                         "gradient does not cross it (per-id data weights on the KJT are)")
+                    if w_ref is not None:
+                        raise ValueError("per-id weights that require grad are not supported with the sharded table exchange: it forms "
+                                         "no gradient for them -- detach them")
+                    if count is not None:
+                        raise ValueError("the sharded table exchange has no capacity form of the pooled lookup (a static KJT with "
+                                         "bag_count): run the eager step on an ordinary KJT")
                 lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
                 if weights is not None:
                     weights = weights.to(device=dev, dtype=torch.float32).contiguous()
@@ -460,10 +470,21 @@ class _TowersFn(torch.autograd.Function):
         ctx.exch, ctx.exch_state = exch, None
         if exch is not None:            # sharded table: ids -> owners, pooled rows <- owners (distributed.py)
             group = [g for grp in lookups.values() for g in grp]
-            if group:
+            bags = [g for grp in bag_lookups.values() for g in grp]
+            if bags:
+                # at least one tower pools: every side goes through ONE pooled route (one plan, one set of all-to-alls per step) --
+                # a plain side as sum bags of length one, bit-exact copies of its rows
+                Bx = bags[0][0].B
+                both = bags + [(g[0], ops.bag_side_from_lookup(g[1], g[0].B)) for g in group]
+                if any(g[0].B != Bx for g in both):
+                    raise ValueError("the sharded table exchange pools the towers of one step together: they must share one batch size")
+                both.sort(key=lambda g: live.index(g[0]))                 # tower order: the order the backward hands d_x over in
+                ctx.exch_state = exch.forward_bags([g[1] for g in both], Bx, grad_on)
+                ctx.exch_sides = [g[0] for g in both]
+            elif group:
                 ctx.exch_state = exch.forward([g[1] for g in group], group[0][0].B, grad_on)
                 ctx.exch_sides = [g[0] for g in group]
-            lookups = {}
+            lookups, bag_lookups = {}, {}
         for group in lookups.values():
             store: EmbeddingStore = group[0][0].tower.categorical_embedder.store
             B = group[0][0].B
